@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Gibbs iterations/s (and effective samples/s) of the marker-effect sampler on a synthetic N x P SNP panel.
 
-    python bench.py --gpus N --steps K --warmup W [--config C4|C2|C3]
+    python bench.py --gpus N --steps K --warmup W [--config C4|C2|C3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what takes work of its own: the
+roofline (five extra profiled iterations), effective sample sizes, the compact-storage, chains-per-GPU and chains-per-pass legs
+and the CPU baseline.  --dump-outputs DIR writes what the timed path hands its caller after the last step (the chain's state and
+the posterior means) as DIR/<name>.npy in float64; the inputs are seeded, so two builds can be compared output for output.
 
 A "step" is one full Gibbs iteration (varE draw, intercept draw, sweep of all P SNPs with residual update, variance
 draws, posterior accumulation).  Default workload = the configuration BASELINE.json's north-star target is stated on and
@@ -37,6 +42,25 @@ CONFIGS = {
     "C3": (10000, 100000, [("BayesB", 100000)], "configs[2]: BayesB (variable-selection indicators)"),
 }
 N_TRACE_LOCI = 128  # ESS of varE, of each varBeta / pi, and the minimum over a fixed set of 128 effects
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+
+
+def dump_outputs(folder, arrays, limit=DUMP_LIMIT):
+    """arrays: name -> array; written as folder/<name>.npy in float64.  When they exceed `limit` bytes together, every long array
+    keeps the same fixed, seeded sample of its positions (in order), so two runs still compare element for element."""
+    os.makedirs(folder, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        small = {k for k, a in arrays.items() if a.size <= 4096}
+        room = limit - sum(arrays[k].nbytes for k in small) - 4096 * len(arrays)   # (headroom for the .npy headers)
+        keep = max(1, room // (8 * max(1, len(arrays) - len(small))))
+        for k in sorted(set(arrays) - small):
+            if arrays[k].size > keep:
+                idx = np.sort(np.random.default_rng(20250509).choice(arrays[k].size, keep, replace=False))
+                arrays[k] = arrays[k][idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(folder, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def split_sets(P, sets):
@@ -185,21 +209,28 @@ def main():
     ap.add_argument("--config", default="C4", choices=sorted(CONFIGS))
     ap.add_argument("--N", type=int, default=None, help="override the number of individuals (parity / contract tests)")
     ap.add_argument("--P", type=int, default=None, help="override the number of SNPs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-compact", action="store_true", help="skip the extra leg in compact (one byte per genotype) storage")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-compact", action="store_true", help="--full without the extra leg in compact (one byte per genotype) storage")
     ap.add_argument("--chains-per-gpu", type=int, default=0,
-                    help="extra leg: that many independent chains side by side on the GPU (aggregate it/s; pays where one chain is not bandwidth-bound)")
+                    help="extra leg of --full: that many independent chains side by side on the GPU (aggregate it/s; pays where one chain is not bandwidth-bound)")
     ap.add_argument("--chains-per-pass", type=int, default=-1,
-                    help="extra leg: that many independent chains in ONE fused sweep launch per iteration, the panel streamed once for all of them "
+                    help="extra leg of --full: that many independent chains in ONE fused sweep launch per iteration, the panel streamed once for all of them "
                          "(aggregate it/s beside the single-chain value; 2..8; default: 8 on shards of at most 64 rows, 2 on taller ones; 0 or 1: skip)")
     ap.add_argument("--storage", default="f32", choices=["f32", "u8"],
                     help="panel storage of the MAIN measurement (default f32 = the headline; u8 = compact storage, for profiling that mode)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N > 1 on one GPU)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses GPU 0 (the persistent kernels then run one after the other)")
-    ap.add_argument("--cpu-cols", type=int, default=None, help="columns of the CPU baseline sample (default: about 1.6e8 / N)")
+    ap.add_argument("--cpu-cols", type=int, default=None, help="columns of the CPU baseline sample of --full (default: about 1.6e8 / N)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--seed-offset", type=int, default=0, help="chain seed = 1001 + rank + this (tests: a rank's chain run alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step and the posterior means as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, effective sample sizes, the compact-storage / chains-per-GPU / chains-per-pass legs and the "
+                         "CPU baseline (off: the headline alone)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -250,31 +281,9 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # effective sample sizes over the K timed iterations (rank 0's chain), Geyer's initial positive sequence
-    # (only when at least 200 kept iterations back the estimate: below that the figure is noise)
-    ess, ess_min = None, None
-    if K >= 200:
-        tr, trx = s.get_trace(K), s.get_trace_ext(K)
-        ess = {"varE": ess_geyer(tr["varE"]),
-               "varBeta": [ess_geyer(trx["varBeta"][:, i]) for i in range(ntvb)],
-               "beta_min_of_%d" % len(loci): min(ess_geyer(trx["beta"][:, i]) for i in range(len(loci)))}
-        if any(m == "BayesB" for m, _, _ in sets):
-            ess["pi"] = [ess_geyer(trx["pi"][:, i]) for i in range(s.nsets)]
-        ess_min = min([ess["varE"], ess["beta_min_of_%d" % len(loci)]] + ess["varBeta"] + ess.get("pi", []))
-    # dominant-kernel launch duration, HIP events on the library's own stream (five extra iterations, averaged)
-    profs = [s.profile_iteration() for _ in range(5)]
-    prof = dict(profs[0], avg_ms=float(np.mean([p["avg_ms"] for p in profs])))
-    achieved = prof["bytes_per_launch"] / (prof["avg_ms"] * 1e-3) / 1e9
-    bytes_iter = (1.0 if compact_main else 4.0) * N * P
-    # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the committed rocprofv3
-    # summary of the SAME workload (tools/profile_round.sh) is quoted when the configuration matches, else null
-    traffic, traffic_src = None, None
-    pmc = next((q for q in (os.path.join(ROOT, "profiles", f"{tag}_pmc_k_sweep_{args.config}{'u8' if compact_main else ''}.json") for tag in ("r04", "r03", "r02"))
-                if os.path.exists(q)), "")
-    if pmc and not overridden and prof["launches"] == 1:
-        pj = json.load(open(pmc))
-        traffic, traffic_src = pj["hbm_bytes_per_launch"], f"profiles/{os.path.basename(pmc)} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)"
-    # posterior means across chains: ONE all-reduce of the packed sums over RCCL / xGMI
+    # what the timed path hands its caller: the chain's state after the last timed step, and the posterior means across chains
+    # (ONE all-reduce of the packed sums over RCCL / xGMI; iterations past the schedule, such as the profiled ones below, are not kept)
+    state = s.get_state() if (rank == 0 and args.dump_outputs) else None
     allreduce_ms = None
     n = s.posterior_len()
     buf = torch.zeros(n, device="cuda", dtype=torch.float64)
@@ -287,6 +296,37 @@ def main():
         allreduce_ms = (time.perf_counter() - ta) * 1e3
     pooled = ngp.multichain.unpack_means(buf.cpu().numpy(), P, s.nvb, s.nsets)
     nkept, post_mean_varE = pooled["nKept"], pooled["varE"]
+    if state is not None:
+        dump_outputs(args.dump_outputs, {
+            "ycorr": state["ycorr"], "beta": state["beta"], "delta": state["delta"], "varBeta": state["varBeta"], "piHat": state["piHat"],
+            "varE": [state["varE"]], "b": [state["b"]],
+            "post_beta": pooled["beta"], "post_beta_sd": pooled["beta_sd"], "post_delta": pooled["delta"], "post_varBeta": pooled["varBeta"],
+            "post_pi": pooled["pi"], "post_varE": [pooled["varE"]], "post_b": [pooled["b"]]})
+    if args.full:
+        # effective sample sizes over the K timed iterations (rank 0's chain), Geyer's initial positive sequence
+        # (only when at least 200 kept iterations back the estimate: below that the figure is noise)
+        ess, ess_min = None, None
+        if K >= 200:
+            tr, trx = s.get_trace(K), s.get_trace_ext(K)
+            ess = {"varE": ess_geyer(tr["varE"]),
+                   "varBeta": [ess_geyer(trx["varBeta"][:, i]) for i in range(ntvb)],
+                   "beta_min_of_%d" % len(loci): min(ess_geyer(trx["beta"][:, i]) for i in range(len(loci)))}
+            if any(m == "BayesB" for m, _, _ in sets):
+                ess["pi"] = [ess_geyer(trx["pi"][:, i]) for i in range(s.nsets)]
+            ess_min = min([ess["varE"], ess["beta_min_of_%d" % len(loci)]] + ess["varBeta"] + ess.get("pi", []))
+        # dominant-kernel launch duration, HIP events on the library's own stream (five extra iterations, averaged)
+        profs = [s.profile_iteration() for _ in range(5)]
+        prof = dict(profs[0], avg_ms=float(np.mean([p["avg_ms"] for p in profs])))
+        achieved = prof["bytes_per_launch"] / (prof["avg_ms"] * 1e-3) / 1e9
+        bytes_iter = (1.0 if compact_main else 4.0) * N * P
+        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the committed rocprofv3
+        # summary of the SAME workload (tools/profile_round.sh) is quoted when the configuration matches, else null
+        traffic, traffic_src = None, None
+        pmc = next((q for q in (os.path.join(ROOT, "profiles", f"{tag}_pmc_k_sweep_{args.config}{'u8' if compact_main else ''}.json") for tag in ("r04", "r03", "r02"))
+                    if os.path.exists(q)), "")
+        if pmc and not overridden and prof["launches"] == 1:
+            pj = json.load(open(pmc))
+            traffic, traffic_src = pj["hbm_bytes_per_launch"], f"profiles/{os.path.basename(pmc)} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)"
     R, S, nblk = s.layout()
     mode, lag = s.config()
     variant, nchain = s.streamer()
@@ -319,7 +359,9 @@ def main():
                 "layout": {"rows_per_shard": R, "shards": S, "blocks": nblk, "engine": mode, "lag": lag, "near_lags": s.near(),
                            "streamer": variant, "gemv_chains": nchain},
             },
-            "roofline": {
+        }
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "ngp::k_sweep<false> (the persistent sweep kernel: one launch streams the whole N x P panel once; models with a Tuple / BayesR set run the k_sweep_tup / k_sweep_r instantiations)" if prof["launches"] == 1 else "ngp::k_step (one 64-SNP column block per launch)",
                 "achieved": achieved,
@@ -333,8 +375,8 @@ def main():
                 "launches_per_iteration": prof["launches"],
                 "iteration_achieved": bytes_iter * (K / dt) / 1e9,
                 "iteration_frac": bytes_iter * (K / dt) / 1e9 / HBM_PEAK_GBS,
-            },
-            "effective_samples": {
+            }
+            out["effective_samples"] = {
                 "estimator": "Geyer initial positive sequence over the timed iterations of rank 0's chain (every iteration kept)",
                 "ess": ess,
                 "ess_min": ess_min,
@@ -342,15 +384,16 @@ def main():
                 "ess_varE_per_sec": None if ess is None else ess["varE"] / dt,
                 "note": "single-chain figures; with n_gpus chains the pooled rate is n_gpus times these"
                         + ("" if ess is not None else "; not estimated: fewer than 200 timed iterations (run with --steps 1000 for an ESS figure)"),
-            },
+            }
+        out.update({
             "device_iter_ms": tm["iter_ms"] / max(tm["iters"], 1),
             "census_retries": main_census["retries"], "exclusive": bool(main_census["exclusive"]),   # launches run again alone on the device
             "setup_s": setup_s, "setup_parts_ms": setup_parts,   # allocation (+ zeroing) | tile generation | Gram window
             "allreduce_ms": allreduce_ms,
             "posterior_mean_varE": post_mean_varE,
             "pooled_kept_samples": nkept,
-        }
-        if world == 1 and not args.no_compact and not compact_main:
+        })
+        if args.full and world == 1 and not args.no_compact and not compact_main:
             # the same workload with the panel kept one byte per genotype (ngp_set_storage: analytic centring, no fp32 rounding of
             # the panel) -- reported BESIDE the fp32 headline above, never instead of it
             s.close()
@@ -400,7 +443,7 @@ def main():
                 "speedup_vs_single_chain": (KB * K / kdt) / (K / cdt)}
             for c in cs:
                 c.close()
-        if world == 1 and args.chains_per_gpu > 1 and not compact_main:
+        if args.full and world == 1 and args.chains_per_gpu > 1 and not compact_main:
             # independent chains side by side on ONE GPU (disjoint CU shares, one thread each inside the library): the aggregate
             # rate of the same metric where a single chain is bound by its sampler workgroup -- beside the single-chain value
             try:
@@ -426,8 +469,8 @@ def main():
             for c in cs:
                 c.close()
         if args.chains_per_pass < 0:  # default: what the fused kernel serves at this shape (phase streamer: 8 chains, row-owning streamer: 2)
-            args.chains_per_pass = (2 if N >= 64 * 247 else 8) if (world == 1 and not compact_main and N <= 224 * 240) else 0
-        if world == 1 and args.chains_per_pass > 1 and not compact_main:
+            args.chains_per_pass = (2 if N >= 64 * 247 else 8) if (args.full and world == 1 and not compact_main and N <= 224 * 240) else 0
+        if args.full and world == 1 and args.chains_per_pass > 1 and not compact_main:
             # K independent chains in ONE fused sweep launch per iteration: every streamer forms X_t'[y_1 .. y_K] from each tile it
             # reads, so one pass over the panel (4 N P algorithmic bytes) serves K iterations' worth of sampling -- the aggregate
             # rate BESIDE the single-chain value above, never instead of it; each chain is bit for bit the chain it is alone
@@ -466,7 +509,7 @@ def main():
             }
             for c in cs:
                 c.close()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cols = args.cpu_cols or int(max(256, min(P, 1.6e8 // N)))
             out["cpu_baseline"] = cpu_baseline(N, P, sets, min(cols, P), args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = its / out["cpu_baseline"]["value"]

@@ -11,8 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_has_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C4", "--N", "2000", "--P", "6400", "--steps", "8", "--warmup", "1",
-                          "--cpu-cols", "640", "--cpu-seconds", "2", "--chains-per-gpu", "2", "--chains-per-pass", "3"], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "C4", "--N", "2000", "--P", "6400", "--steps", "8",
+                          "--warmup", "1", "--cpu-cols", "640", "--cpu-seconds", "2", "--chains-per-gpu", "2", "--chains-per-pass", "3"], capture_output=True, text=True,
                          timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -1,7 +1,7 @@
 #!/bin/bash
 O=gpurun_out/r04m; mkdir -p $O
 timeout -k 10 900 python -m pytest tests/test_bench_contract.py tests/test_host_api.py tests/test_gpu_chains_per_pass.py -m gpu -q > $O/pytest.txt 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.txt; tail -8 $O/pytest.txt
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r04m/bench_default.json") if l.startswith("{")][0])
