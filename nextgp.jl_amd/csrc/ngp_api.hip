@@ -78,6 +78,202 @@ struct HSet {
 
 std::string g_create_err;
 
+/* ---- the plan of the persistent sweep: how a panel is swept, decided in one place ---------------------------------------- */
+
+// what the caller asked for before the panel was set (ngp_configure, ngp_set_storage, ngp_set_near_lags, ngp_set_max_shards,
+// ngp_set_streamer)
+struct PlanRequest {
+    int storage = 0;       // 0: centred fp32 tiles; 1: compact -- byte tiles + Float64 column means (ngp_set_storage)
+    int mode = 1;          // 1: persistent sweep kernel, 0: one streaming + one recursion launch per block
+    int lag = 8;           // look-ahead D of the persistent sweep (blocks); shards taller than 128 rows are capped at 5
+    bool lag_auto = true;  // lag not chosen by the caller (ngp_configure): tall shards then take the measured best
+    int near_req = 0;      // near lags requested (0 = automatic)
+    int max_shards_req = 0;  // streamer workgroups the persistent sweep may use (0 = all CUs but the sampler's and the reducers')
+    int streamer_req = 0;  // streamer variant requested: 0 automatic, 1 phase streamer, 2 row-owning waves + loader wave, 4 / 6 = 2 with
+                           // two / three shards per workgroup at any N (automatic only above one resident wave of 256-row shards)
+};
+
+// what plan_sweep decided for a panel: everything the launches of its sweeps derive from
+struct SweepPlan {
+    int mode = 1;          // engine in force: the request, or 0 where the panel is too tall for one resident wave of streamers
+    int64_t R = 0, S = 0;  // rows per shard, shards
+    int V = 1;             // shards per streamer workgroup (role_streamer_rows_tall: 2, 3); the sweep's grid has S / V streamers
+    int D = 1;             // Gram planes stored per block (= lag in mode 1, 1 in mode 0)
+    int NG = 1;            // reducer groups = ceil(S/32)
+    int near = 3;          // look-ahead lags 1..near corrected by the sampler itself, farther ones by the reducers
+    int streamer = 1;      // variant in force (persistent sweep only): 1 phase streamer, 2 row-owning waves, 3 the same over byte tiles
+    int nchain = 8;        // GEMV chains per shard partial: 8 (phase streamer, per-block engine) or 7 (row-owning waves)
+};
+
+constexpr size_t NGP_LDS_MAX = 160 * 1024;  // LDS of a gfx950 CU: the most one workgroup may take
+
+// rows per shard R: a multiple of 4 -- 4*odd where that fits under the cap when the shard count is left to the library (the layouts
+// of the first versions, kept so that results stay comparable; with quad-major tiles any multiple of 4 reads conflict-free), the
+// smallest multiple of 4 that serves an explicit ngp_set_max_shards (there every workgroup counts: 10k rows on 209 shards are 48 rows
+// each, 52 would leave 16 CUs idle); S = ceil(N/R)
+void choose_layout(int64_t N, int64_t max_shards, int64_t r_cap, int64_t *R, int64_t *S, bool prefer_odd = true) {
+    int64_t r0 = (N + max_shards - 1) / max_shards;
+    int64_t m = (r0 + 3) / 4;
+    if (m < 1) m = 1;
+    if (prefer_odd && (m & 1) == 0 && 4 * (m + 1) <= r_cap) m += 1;
+    int64_t r = 4 * m;
+    if (r > r_cap) r = r_cap;
+    *R = r;
+    *S = (N + r - 1) / r;
+}
+
+// LDS of the sampler workgroup: 3 Gram planes, the dlt ring, 6 vectors of the block, 2 of ints, scalars -- and the staging area of
+// the chains the kernel carries: none in the lean kernel, Tuple coefficients in the full ones, BayesR coefficients on top in the _r ones
+size_t sampler_lds(SweepKernel k) {
+    const size_t base = (size_t)(3 * 4096 + 2 * NGP_RING * NGP_BLK + 6 * NGP_BLK) * sizeof(double) + 2 * NGP_BLK * sizeof(int) + 320;
+    if (k == SweepKernel::lean) return base;
+    if (k == SweepKernel::r || k == SweepKernel::multi_r) return base + NGP_SAMPLER_TUPLE_LDS + NGP_SAMPLER_R_LDS;
+    return base + NGP_SAMPLER_TUPLE_LDS;
+}
+
+// LDS of a streamer workgroup serving K chains (K = 1: the single-chain kernels)
+size_t streamer_lds(const SweepPlan &p, int K) {
+    const int R = (int)p.R;
+    if (K > 1) return p.streamer == 3 ? ngp_rows_multi_lds_bytes(R, K, true) : (p.streamer == 2 ? ngp_rows_multi_lds_bytes(R, K) : ngp_multi_lds_bytes(R, K));
+    if (p.streamer >= 2) {  // ring of 2 NQ + H slots | shard | 2 x 7 x 64 chain partials | 2 x 72 dlt | 2 x 8 row sums | flags | 1 KiB sink
+        const size_t nq = (p.streamer == 3) ? (size_t)R / 16 : (size_t)R / 4, hq = std::min<size_t>(NGP_ROWS_HMAX, (nq + 1) / 2);
+        return (2 * nq + hq) * NGP_QS + (size_t)p.V * ((R + 7) & ~7) * 8 + 2 * NGP_ROWS_NW * NGP_BLK * 8 + 2 * NGP_DLS * 8 + 16 * 8 + 64 + 1024;
+    }
+    // phase streamer: two tiles (quads NGP_QS bytes apart) | shard | partials | flags
+    return 2 * (size_t)(R / 4) * NGP_QS + (size_t)R * 16 + 4096 + 2 * 512 + 128 + 3072 + (size_t)R * 64;
+}
+
+// dynamic LDS a launch of kernel k over K chains takes: the streamer's or the sampler's need, whichever is larger; the single-chain
+// kernels add 8 KiB for the diagnostic timeline where that fits
+size_t sweep_lds(const SweepPlan &p, SweepKernel k, int K = 1) {
+    const size_t streamer = streamer_lds(p, K);
+    size_t lds = std::max(streamer, sampler_lds(k));
+    if (K == 1 && streamer + 8192 <= NGP_LDS_MAX) lds = std::max(lds, streamer + 8192);
+    return lds;
+}
+
+// reducer workgroups of a fused launch serve two chains each from NGP_PAIR_FROM chains on (phase streamer only)
+int fused_pair(const SweepPlan &p, int K) { return (p.streamer == 1 && K >= NGP_PAIR_FROM) ? 1 : 0; }
+
+// workgroups of a sweep launch over K chains: per chain a sampler and a reducer per group of shards (per pair of chains where the
+// reducers pair), and S / V streamers
+int64_t sweep_grid(const SweepPlan &p, int K = 1) { return K + ngp_multi_reducers(K, p.NG, fused_pair(p, K)) + p.S / p.V; }
+
+// the kernel of a sweep launch over K chains (K = 1: one chain; K >= 2: a fused pass); diag: time stamps or a timing mode are on;
+// tup / rset: a chain has a Tuple / a BayesR set
+SweepKernel pick_kernel(const SweepPlan &p, int K, bool diag, bool tup, bool rset) {
+    if (K > 1) {  // (BayesR: the samplers of k_sweep_r, their class coefficients staged in LDS -- where that fits beside the
+                  // sampler's own; else the chain of k_sweep_multi(_tup))
+        if (rset && sweep_lds(p, SweepKernel::multi_r, K) <= NGP_LDS_MAX) return SweepKernel::multi_r;
+        return tup ? SweepKernel::multi_tup : SweepKernel::multi;
+    }
+    if (p.V > 1) return SweepKernel::tall;  // several shards per streamer workgroup: a kernel of its own (no diagnostics there)
+    if (diag) return SweepKernel::diag;     // diagnostic instantiation: stamps and timing modes exist only there
+    // a BayesR set: the flavour that fetches its coefficients ahead, where its LDS fits
+    if (rset && sweep_lds(p, SweepKernel::r) <= NGP_LDS_MAX) return SweepKernel::r;
+    // Models with a Tuple or a BayesR set run the kernel that carries those chains (k_sweep<false>, the kernel of BayesPR / BayesB /
+    // BayesC, does not: ngp_sweep.h, role_sampler).  Every other model takes the lean kernel at every shape (in round 3 tall fp32
+    // shards ran 1.7-2 % faster in the full kernel -- register allocation, not design; since the round-4 hand-off the lean
+    // kernel is level or ahead there too: 23.4-23.6 against 23.3-23.9 ms per iteration at 50k x 600k).
+    if (tup || rset) return SweepKernel::tup;
+    return SweepKernel::lean;
+}
+
+// host address of a sweep kernel: each translation unit of ngp_sweep_inst.hip knows the kernels it defines
+const void *sweep_kernel(SweepKernel k) {
+    for (auto unit : {sweep_kernel_0, sweep_kernel_1, sweep_kernel_2, sweep_kernel_3})
+        if (const void *f = unit(k)) return f;
+    return nullptr;
+}
+
+// one launch of a sweep kernel; args: the SweepArgs (single-chain kernels) or the MultiArgs (fused ones) it takes
+void launch_sweep_kernel(SweepKernel k, int64_t grid, size_t lds, hipStream_t stream, void *args) {
+    void *a[] = {args};
+    (void)hipLaunchKernel(sweep_kernel(k), dim3((unsigned)grid), dim3(NGP_WG), a, lds, stream);
+}
+
+// How a panel of N rows is swept on a device of cu_count CUs.  Pure: no allocation, no HIP call.  Returns NGP_OK, or the error code
+// of a request the sweep cannot serve with its message in *msg.
+int plan_sweep(int64_t N, int cu_count, const PlanRequest &q, SweepPlan *out, const char **msg) {
+    SweepPlan p;
+    p.mode = q.mode;
+    // persistent mode: sampler + reducers + S streamers must all be resident, one workgroup per CU
+    int64_t max_shards = cu_count - 1 - (cu_count + NGP_GRP - 1) / NGP_GRP;
+    if (q.max_shards_req > 0) max_shards = std::min<int64_t>(max_shards, q.max_shards_req);
+    if (q.storage == 1) {
+        // compact storage: byte tiles, units of 16 rows, the row-owning roles only (persistent sweep)
+        if (q.mode != 1) { *msg = "compact storage runs in the persistent sweep (ngp_configure mode 1) only"; return NGP_ERR_ARG; }
+        const int64_t r0 = (N + max_shards - 1) / max_shards;
+        p.R = 16 * std::max<int64_t>(1, (r0 + 15) / 16);
+        if (p.R > NGP_U8_MAX_R) { *msg = "N too large for one resident wave of streamers in compact storage"; return NGP_ERR_ARG; }
+        p.S = (N + p.R - 1) / p.R;
+        p.streamer = 3;
+        p.nchain = NGP_ROWS_NW;
+        // delay line: 8 VGPRs per lag and update task of a lane (1, 2 or 4 tasks: ngp_u8_tasks)
+        const int nt = ngp_u8_tasks((int)p.R);
+        const int want = q.lag_auto ? 8 : q.lag;
+        // the instantiated lags (ngp_sweep.h, variant 3): the largest one not above the request
+        if (nt == 1) p.D = want >= 12 ? 12 : (want >= 8 ? 8 : (want >= 6 ? 6 : (want >= 4 ? 4 : 3)));
+        else if (nt == 2) p.D = want >= 8 ? 8 : 4;
+        else p.D = 4;
+        p.near = q.near_req ? q.near_req : ((p.R > 128) ? 2 : 3);
+    } else {
+        if (p.mode == 1) {
+            // Taller than one resident wave of 256-row shards: every streamer workgroup owns V = 2 (lag 3) or 3 (lag 2) shards of at
+            // most 224 rows (role_streamer_rows_tall) -- S = V W shards, W workgroups, 1 + ceil(V W / 32) + W <= CUs.
+            int tallV = 0;
+            int64_t w_max = 0;
+            for (int v = 2; v <= 3 && !tallV; v++) {
+                if (q.streamer_req != 0 && q.streamer_req != 2 * v) continue;
+                if (q.streamer_req == 0 && N <= max_shards * 256) continue;
+                SweepPlan t;  // (W workgroups of v shards each)
+                t.V = v;
+                auto fits = [&](int64_t w) { t.S = v * w; t.NG = (int)((t.S + NGP_GRP - 1) / NGP_GRP); return sweep_grid(t) <= cu_count; };
+                int64_t w = cu_count - 1;
+                while (w > 1 && !fits(w)) w--;
+                if (q.max_shards_req > 0) w = std::max<int64_t>(1, std::min<int64_t>(w, q.max_shards_req / v));
+                if (N <= v * w * NGP_ROWS_MAX_R && q.lag >= 3) { tallV = v; w_max = w; }
+            }
+            if (tallV) {
+                choose_layout(N, tallV * w_max, NGP_ROWS_MAX_R, &p.R, &p.S, q.max_shards_req <= 0);
+                p.S = (p.S + tallV - 1) / tallV * tallV;  // (all-padding shards at the end if need be: zero tiles, zero rows of ycorr)
+                p.V = tallV;
+            } else if (N > max_shards * 256) p.mode = 0;  // too many rows for one resident wave of streamers (2 LDS tile slots + partials)
+            else choose_layout(N, max_shards, 256, &p.R, &p.S, q.max_shards_req <= 0);  // 8 R / 4 update tasks <= 512 threads, two 1040 R / 4 byte LDS slots
+        }
+        if (p.mode == 0) choose_layout(N, 256, 508, &p.R, &p.S);  // LDS bound of k_step: R*264 + 4096 <= 160 KiB
+        p.D = (p.mode == 1) ? std::min(q.lag, 8) : 1;
+        // streamer variant (ngp_sweep.h): the row-owning waves serve shards of up to NGP_ROWS_MAX_R rows at lags 3..6 and are the
+        // default from 64-row shards on
+        // (from 64-row shards on since the publisher stopped waiting for the block's barrier: 20k x 100k 3.66 -> 3.26 ms, 28k x 100k
+        // 3.97 -> 3.45, 16k x 100k 3.38 -> 3.16, equal at 52-60 rows, the phase streamer ahead at 44 rows: 1.86 against 1.99 us per block)
+        if (p.mode == 1 && p.R <= NGP_ROWS_MAX_R && q.lag >= 3 && (q.streamer_req == 2 || (q.streamer_req == 0 && p.R >= 64))) p.streamer = 2;
+        if (p.V > 1) p.streamer = 2;
+        p.nchain = (p.streamer == 2) ? NGP_ROWS_NW : 8;
+        if (p.streamer == 2) {
+            if (p.D > 6) p.D = 6;  // register delay line: 32 VGPRs per lag
+            if (p.V > 1) p.D = (p.V == 2) ? 3 : 2;  // ... and per shard of the workgroup
+        } else if (p.mode == 1 && p.R > 128 && p.D > 5) p.D = 5;  // tall shards: the register delay line holds 5 tiles at most
+        // short shards (phase streamer), lag left to the library: 6.  Lag 8 was the better one while the shard partials crossed two hops (rounds 1-3);
+        // with the one-hop fixed-point sums: 10k x 100k 2.66-2.71 ms at lag 6 against 2.77-2.81 at lag 8 (7: 2.82-2.91, 5: 3.16-3.21, 4: 3.02-3.16),
+        // 8k x 100k 2.64 / 2.70, 14k x 100k 2.83 / 2.87, eight chains per pass 1839 / 1775 it/s (tools/r4_run41.sh)
+        else if (p.mode == 1 && q.lag_auto && p.D > 6) p.D = 6;
+        // a fourth near lag overloads the sampler CU at short shards (+17 % time at 10k x 100k); the phase streamer of tall shards,
+        // where with lag 5 nothing is left for the reducers then, saves 8 % with it; with the row-owning streamer (lag 6) the sampler
+        // CU is again the busier end (its Gram traffic: 32 KB per near lag and block) and three near lags measure better
+        // (row-owning streamer on tall shards: two near lags measured 1.5 % better still -- the far path is one hop since dlt travels as granules)
+        p.near = q.near_req ? q.near_req : ((p.mode == 1 && p.streamer == 2 && p.R >= 64) ? 2 : ((p.mode == 1 && p.R > 128) ? 4 : 3));
+    }
+    p.NG = (int)((p.S + NGP_GRP - 1) / NGP_GRP);
+    if (p.mode == 1) {
+        // the sampler adds more than 8 group sums only where it fetches them one block ahead (lags 2-3: fetch_group_sums)
+        if (!(p.NG <= 8 || p.D <= 3)) { *msg = "internal: more shard groups than the sampler adds"; return NGP_ERR_STATE; }
+        if (sweep_lds(p, SweepKernel::tup) > NGP_LDS_MAX) { *msg = "panel too tall for the persistent sweep (LDS)"; return NGP_ERR_ARG; }
+    }
+    *out = p;
+    return NGP_OK;
+}
+
 }  // namespace
 
 struct ngp_handle {
@@ -85,26 +281,12 @@ struct ngp_handle {
     uint64_t seed = 0;
     uint32_t chain = 0;
     hipStream_t stream = nullptr;
-    int64_t N = 0, P = 0, R = 0, S = 0, NBLK = 0, Ppad = 0, L = 0;
-    size_t lds_step = 0, lds_sweep = 0, lds_rows = 0;
-    size_t lds_sweep_lean = 0;  // the same without the sampler's staging area of Tuple coefficients: what k_sweep<false> is launched with
-    size_t lds_sweep_r = 0;     // with the BayesR staging area as well: what k_sweep_r is launched with (0: does not fit -> k_sweep_tup)
-    int mode = 1;      // 1: persistent sweep kernel, 0: one streaming + one recursion launch per block
-    int lag = 8;       // look-ahead D of the persistent sweep (blocks); shards taller than 128 rows are capped at 5
-    bool lag_auto = true;  // lag not chosen by the caller (ngp_configure): tall shards then take the measured best
-    int near_req = 0;  // near lags requested (0 = automatic)
-    int near = 3;      // look-ahead lags 1..near corrected by the sampler itself, farther ones by the reducers
-    int max_shards_req = 0;  // streamer workgroups the persistent sweep may use (0 = all CUs but the sampler's and the reducers')
-    int storage = 0;       // 0: centred fp32 tiles; 1: compact -- byte tiles + Float64 column means (ngp_set_storage)
+    int64_t N = 0, P = 0, NBLK = 0, Ppad = 0, L = 0;
+    size_t lds_step = 0;
+    PlanRequest req;  // how the caller wants the panel swept (its mode becomes 0 where plan_sweep falls back to mode 0)
+    SweepPlan plan;   // how it is swept: plan_sweep's decision, or the owner's plan for a shared panel
     double *d_mean = nullptr;  // compact storage: column means, Ppad
-    int streamer_req = 0;  // streamer variant requested: 0 automatic, 1 phase streamer, 2 row-owning waves + loader wave, 4 / 6 = 2 with
-                           // two / three shards per workgroup at any N (automatic only above one resident wave of 256-row shards)
     bool panel_open = false;  // between ngp_begin_panel and ngp_end_panel: columns may still arrive, the Gram window does not exist yet
-    int V = 1;             // shards per streamer workgroup (role_streamer_rows_tall: 2, 3); the sweep's grid has S / V streamers
-    int streamer = 1;      // variant in force (persistent sweep only)
-    int nchain = 8;        // GEMV chains per shard partial: 8 (phase streamer, per-block engine) or 7 (row-owning waves)
-    int D = 1;         // Gram planes stored per block (= lag in mode 1, 1 in mode 0)
-    int NG = 1;        // reducer groups = ceil(S/32)
     int cu_count = 256;
     double *d_cdlt = nullptr;
     unsigned long long *d_cacc = nullptr;   // fixed-point accumulators of X_t'ycorr (inside d_ccnt: zeroed with the counters by k_prep)
@@ -181,7 +363,9 @@ struct ngp_handle {
     // diagnostics (ngp_debug_set_mode): != 0 makes every chain invalid, ngp_run / ngp_sweep_set then return NGP_ERR_DEBUG
     int dbg_mode = 0;
     int gram_engine = 0;  // 0: Gram window by the fp64 VALU kernel (k_gram_part), 1: on the matrix cores (k_gram_part_mfma, bit-identical); the knob's bit 10
-    int knob = 0;  // pacing of the loader wave of the row-owning streamer: s_sleep units after every four requests (ngp_debug_set_knob)
+    int knob = 0;  // ngp_debug_set_knob, timing only: bits 0-2 pace the loader wave of the row-owning streamer (s_sleep units after every four
+                   // requests), bit 4 counts every partial before the block's barrier, bit 8 flips the publisher's early signal (the
+                   // streamers read these through SweepArgs.knob); bit 10 builds the Gram window on the matrix cores (gram_engine)
     bool adding_r = false;  // ngp_add_marker_set is being called by ngp_add_marker_set_r
     bool poisoned = false;  // a sweep gave up half-way (abort word): the chain state is unusable until ngp_set_y / ngp_set_state
     bool exclusive = false;  // a grid of this handle was once not co-resident beside other chains' grids: its calls now lease the whole device
@@ -257,10 +441,10 @@ struct CuLease {
     int dev = -1, n = 0, cap = 0, want = 0;
     bool excl = false;
     explicit CuLease(ngp_handle *h, int64_t grid_override = 0) {
-        if (h->mode != 1) return;
+        if (h->plan.mode != 1) return;
         // workgroups are handed to the 8 XCDs in turn, so a grid occupies ceil(grid / 8) CUs of EVERY XCD: the unit of the lease
         // (three grids of 85 workgroups -- 255 of 256 CUs -- do not fit: 3 x 11 > 32 per XCD; measured, they wait for each other)
-        dev = h->device & 63; want = (int)(((grid_override > 0 ? grid_override : 1 + h->NG + h->S / h->V) + 7) / 8);
+        dev = h->device & 63; want = (int)(((grid_override > 0 ? grid_override : sweep_grid(h->plan)) + 7) / 8);
         cap = std::max(1, h->cu_count / 8);
         acquire(h->exclusive);
     }
@@ -303,21 +487,6 @@ void dfree(T *&p) {
     if (p) { (void)hipFree(p); p = nullptr; }
 }
 
-// rows per shard R: a multiple of 4 -- 4*odd where that fits under the cap when the shard count is left to the library (the layouts
-// of the first versions, kept so that results stay comparable; with quad-major tiles any multiple of 4 reads conflict-free), the
-// smallest multiple of 4 that serves an explicit ngp_set_max_shards (there every workgroup counts: 10k rows on 209 shards are 48 rows
-// each, 52 would leave 16 CUs idle); S = ceil(N/R)
-void choose_layout(int64_t N, int64_t max_shards, int64_t r_cap, int64_t *R, int64_t *S, bool prefer_odd = true) {
-    int64_t r0 = (N + max_shards - 1) / max_shards;
-    int64_t m = (r0 + 3) / 4;
-    if (m < 1) m = 1;
-    if (prefer_odd && (m & 1) == 0 && 4 * (m + 1) <= r_cap) m += 1;
-    int64_t r = 4 * m;
-    if (r > r_cap) r = r_cap;
-    *R = r;
-    *S = (N + r - 1) / r;
-}
-
 // drop this handle's reference to its panel arrays; the last reference frees them
 void release_panel(ngp_handle *h) {
     if (h->pm) {
@@ -340,94 +509,20 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     REQUIRE(N <= (int64_t)508 * 1024, NGP_ERR_ARG, "N too large for this build (max 520192)");
     release_panel(h);  // (handles that share the old panel keep it alive)
     h->N = N; h->P = P;
-    if (owner) {  // the owner's layout, engine and storage, as they are
-        h->mode = owner->mode; h->lag = owner->lag; h->lag_auto = owner->lag_auto; h->near_req = owner->near_req; h->near = owner->near;
-        h->max_shards_req = owner->max_shards_req; h->storage = owner->storage; h->streamer_req = owner->streamer_req;
-        h->lds_rows = owner->lds_rows;
-        h->streamer = owner->streamer; h->nchain = owner->nchain; h->D = owner->D; h->NG = owner->NG; h->R = owner->R; h->S = owner->S;
-        h->V = owner->V;
+    if (owner) {  // the owner's requests and plan, as they are
+        h->req = owner->req;
+        h->plan = owner->plan;
     } else {
-    // persistent mode: sampler + reducers + S streamers must all be resident, one workgroup per CU
-    int64_t max_shards = 256;
-    h->V = 1;
-    if (h->storage == 1) {
-        // compact storage: byte tiles, units of 16 rows, the row-owning roles only (persistent sweep)
-        REQUIRE(h->mode == 1, NGP_ERR_ARG, "compact storage runs in the persistent sweep (ngp_configure mode 1) only");
-        max_shards = h->cu_count - 1 - (h->cu_count + NGP_GRP - 1) / NGP_GRP;
-        if (h->max_shards_req > 0) max_shards = std::min<int64_t>(max_shards, h->max_shards_req);
-        const int64_t r0 = (N + max_shards - 1) / max_shards;
-        h->R = 16 * std::max<int64_t>(1, (r0 + 15) / 16);
-        REQUIRE(h->R <= NGP_U8_MAX_R, NGP_ERR_ARG, "N too large for one resident wave of streamers in compact storage");
-        h->S = (N + h->R - 1) / h->R;
-        h->NG = (int)((h->S + NGP_GRP - 1) / NGP_GRP);
-        h->streamer = 3;
-        h->nchain = NGP_ROWS_NW;
-        // delay line: 8 VGPRs per lag and update task of a lane (1, 2 or 4 tasks: ngp_u8_tasks)
-        const int nt = ngp_u8_tasks((int)h->R);
-        const int want = h->lag_auto ? 8 : h->lag;
-        int D;  // the instantiated lags (ngp_sweep.h, variant 3): the largest one not above the request
-        if (nt == 1) D = want >= 12 ? 12 : (want >= 8 ? 8 : (want >= 6 ? 6 : (want >= 4 ? 4 : 3)));
-        else if (nt == 2) D = want >= 8 ? 8 : 4;
-        else D = 4;
-        h->D = D;
-        h->near = h->near_req ? h->near_req : ((h->R > 128) ? 2 : 3);
-    } else {
-    if (h->mode == 1) {
-        max_shards = h->cu_count - 1 - (h->cu_count + NGP_GRP - 1) / NGP_GRP;
-        if (h->max_shards_req > 0) max_shards = std::min<int64_t>(max_shards, h->max_shards_req);
-        // Taller than one resident wave of 256-row shards: every streamer workgroup owns V = 2 (lag 3) or 3 (lag 2) shards of at
-        // most 224 rows (role_streamer_rows_tall) -- S = V W shards, W workgroups, 1 + ceil(V W / 32) + W <= CUs.
-        int tallV = 0;
-        int64_t w_max = 0;
-        for (int v = 2; v <= 3 && !tallV; v++) {
-            if (h->streamer_req != 0 && h->streamer_req != 2 * v) continue;
-            if (h->streamer_req == 0 && N <= max_shards * 256) continue;
-            int64_t w = h->cu_count - 1;
-            while (w > 1 && 1 + (v * w + NGP_GRP - 1) / NGP_GRP + w > h->cu_count) w--;
-            if (h->max_shards_req > 0) w = std::max<int64_t>(1, std::min<int64_t>(w, h->max_shards_req / v));
-            if (N <= v * w * NGP_ROWS_MAX_R && h->lag >= 3) { tallV = v; w_max = w; }
-        }
-        if (tallV) {
-            choose_layout(N, tallV * w_max, NGP_ROWS_MAX_R, &h->R, &h->S, h->max_shards_req <= 0);
-            h->S = (h->S + tallV - 1) / tallV * tallV;  // (all-padding shards at the end if need be: zero tiles, zero rows of ycorr)
-            h->V = tallV;
-        } else if (N > max_shards * 256) h->mode = 0;  // too many rows for one resident wave of streamers (2 LDS tile slots + partials)
-        else choose_layout(N, max_shards, 256, &h->R, &h->S, h->max_shards_req <= 0);  // 8 R / 4 update tasks <= 512 threads, two 1040 R / 4 byte LDS slots
+        const char *msg = nullptr;
+        if (int e = plan_sweep(N, h->cu_count, h->req, &h->plan, &msg)) return fail(h, e, msg);
+        h->req.mode = h->plan.mode;  // (a panel too tall for the persistent sweep leaves the handle in mode 0)
     }
-    if (h->mode == 0) choose_layout(N, 256, 508, &h->R, &h->S);  // LDS bound of k_step: R*264 + 4096 <= 160 KiB
-    h->NG = (int)((h->S + NGP_GRP - 1) / NGP_GRP);
-    h->D = (h->mode == 1) ? std::min(h->lag, 8) : 1;
-    // streamer variant (ngp_sweep.h): the row-owning waves serve shards of up to NGP_ROWS_MAX_R rows at lags 3..6 and are the
-    // default from 64-row shards on
-    h->streamer = 1;
-    // (from 64-row shards on since the publisher stopped waiting for the block's barrier: 20k x 100k 3.66 -> 3.26 ms, 28k x 100k
-    // 3.97 -> 3.45, 16k x 100k 3.38 -> 3.16, equal at 52-60 rows, the phase streamer ahead at 44 rows: 1.86 against 1.99 us per block)
-    if (h->mode == 1 && h->R <= NGP_ROWS_MAX_R && h->lag >= 3 && (h->streamer_req == 2 || (h->streamer_req == 0 && h->R >= 64))) h->streamer = 2;
-    if (h->V > 1) h->streamer = 2;
-    h->nchain = (h->streamer == 2) ? NGP_ROWS_NW : 8;
-    if (h->streamer == 2) {
-        if (h->D > 6) h->D = 6;  // register delay line: 32 VGPRs per lag
-        if (h->V > 1) h->D = (h->V == 2) ? 3 : 2;  // ... and per shard of the workgroup
-    } else if (h->mode == 1 && h->R > 128 && h->D > 5) h->D = 5;  // tall shards: the register delay line holds 5 tiles at most
-    // short shards (phase streamer), lag left to the library: 6.  Lag 8 was the better one while the shard partials crossed two hops (rounds 1-3);
-    // with the one-hop fixed-point sums: 10k x 100k 2.66-2.71 ms at lag 6 against 2.77-2.81 at lag 8 (7: 2.82-2.91, 5: 3.16-3.21, 4: 3.02-3.16),
-    // 8k x 100k 2.64 / 2.70, 14k x 100k 2.83 / 2.87, eight chains per pass 1839 / 1775 it/s (tools/r4_run41.sh)
-    else if (h->mode == 1 && h->lag_auto && h->D > 6) h->D = 6;
-    // a fourth near lag overloads the sampler CU at short shards (+17 % time at 10k x 100k); the phase streamer of tall shards,
-    // where with lag 5 nothing is left for the reducers then, saves 8 % with it; with the row-owning streamer (lag 6) the sampler
-    // CU is again the busier end (its Gram traffic: 32 KB per near lag and block) and three near lags measure better
-    // (row-owning streamer on tall shards: two near lags measured 1.5 % better still -- the far path is one hop since dlt travels as granules)
-    h->near = h->near_req ? h->near_req : ((h->mode == 1 && h->streamer == 2 && h->R >= 64) ? 2 : ((h->mode == 1 && h->R > 128) ? 4 : 3));
-    }
-    }
-    // the sampler adds more than 8 group sums only where it fetches them one block ahead (lags 2-3: fetch_group_sums)
-    if (h->mode == 1 && !owner) REQUIRE(h->NG <= 8 || h->D <= 3, NGP_ERR_STATE, "internal: more shard groups than the sampler adds");
     h->NBLK = (P + NGP_BLK - 1) / NGP_BLK;
     h->Ppad = h->NBLK * NGP_BLK;
-    h->L = h->R * h->S;
-    h->lds_step = (size_t)h->R * 264 + 4096;
+    h->L = h->plan.R * h->plan.S;
+    h->lds_step = (size_t)h->plan.R * 264 + 4096;
     int rc;
-    size_t tile_elems = (size_t)h->R * NGP_BLK;
+    size_t tile_elems = (size_t)h->plan.R * NGP_BLK;
     const size_t pp = (size_t)h->Ppad;
     if (owner) {
         h->d_tiles = owner->d_tiles; h->d_mean = owner->d_mean; h->d_gramx = owner->d_gramx; h->d_mpm = owner->d_mpm;
@@ -437,10 +532,10 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     // column means: what the analytic centring of the compact storage uses; kept for the fp32 tiles too (ngp_get_storage: a host
     // can then rebuild any centred row of the panel from the genotype codes)
     if ((rc = dalloc(h, &h->d_mean, (size_t)h->Ppad))) return rc;
-    if (h->storage == 1) {  // one byte per element (R is a multiple of 16), held behind the same pointer
-        if ((rc = dalloc(h, &h->d_tiles, (size_t)h->NBLK * h->S * tile_elems / 4))) return rc;
-    } else if ((rc = dalloc(h, &h->d_tiles, (size_t)h->NBLK * h->S * tile_elems))) return rc;
-    if ((rc = dalloc(h, &h->d_gramx, (size_t)h->NBLK * h->D * NGP_BLK * NGP_BLK))) return rc;
+    if (h->req.storage == 1) {  // one byte per element (R is a multiple of 16), held behind the same pointer
+        if ((rc = dalloc(h, &h->d_tiles, (size_t)h->NBLK * h->plan.S * tile_elems / 4))) return rc;
+    } else if ((rc = dalloc(h, &h->d_tiles, (size_t)h->NBLK * h->plan.S * tile_elems))) return rc;
+    if ((rc = dalloc(h, &h->d_gramx, (size_t)h->NBLK * h->plan.D * NGP_BLK * NGP_BLK))) return rc;
     if ((rc = dalloc(h, &h->d_mpm, pp))) return rc;
     h->pm = new PanelMem();
     h->pm->tiles = h->d_tiles; h->pm->mean = h->d_mean; h->pm->gramx = h->d_gramx; h->pm->mpm = h->d_mpm;
@@ -461,7 +556,7 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     if ((rc = dalloc(h, &h->d_sum_beta2, pp))) return rc;
     if ((rc = dalloc(h, &h->d_sum_delta, pp))) return rc;
     if ((rc = dalloc(h, &h->d_ycorr, (size_t)h->L))) return rc;
-    if ((rc = dalloc(h, &h->d_part, (size_t)h->S * NGP_BLK))) return rc;
+    if ((rc = dalloc(h, &h->d_part, (size_t)h->plan.S * NGP_BLK))) return rc;
     if ((rc = dalloc(h, &h->d_dlt, NGP_BLK))) return rc;
     if ((rc = dalloc(h, &h->d_sets, 16))) return rc;
     if ((rc = dalloc(h, &h->d_scal, 1))) return rc;
@@ -481,46 +576,21 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     dfree(h->d_trace_loci); dfree(h->d_tr_beta); dfree(h->d_tr_vb); dfree(h->d_tr_pi);
     h->ntl = 0; h->ntvb = 0; h->trace_ext_cap = 0;
     h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false;
-    if (h->storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_step));
-    if (h->mode == 1) {
-        const size_t lds_sampler = (size_t)(3 * 4096 + 2 * NGP_RING * NGP_BLK + 6 * NGP_BLK) * sizeof(double) + 2 * NGP_BLK * sizeof(int) + 320 + NGP_SAMPLER_TUPLE_LDS;
-        const size_t lds_max = 160 * 1024;
-        const size_t misc = (size_t)h->R * 16 + 4096 + 2 * 512 + 128 + 3072 + (size_t)h->R * 64;
-        const size_t TB = (size_t)(h->R / 4) * NGP_QS;  // LDS footprint of one tile (quads NGP_QS bytes apart)
-        h->lds_sweep = std::max(2 * TB + misc, lds_sampler);
-        if (2 * TB + misc + 8192 <= lds_max) h->lds_sweep = std::max(h->lds_sweep, 2 * TB + misc + 8192);  // room for the diagnostic timeline
-        if (h->streamer >= 2) {  // ring of 2 NQ + H slots | shard | 2 x 7 x 64 chain partials | 2 x 72 dlt | 2 x 8 row sums | flags | 1 KiB sink
-            const size_t nq = (h->streamer == 3) ? (size_t)h->R / 16 : (size_t)h->R / 4, hq = std::min<size_t>(NGP_ROWS_HMAX, (nq + 1) / 2);
-            const size_t need = (2 * nq + hq) * NGP_QS + (size_t)h->V * ((h->R + 7) & ~7) * 8 + 2 * NGP_ROWS_NW * NGP_BLK * 8 + 2 * NGP_DLS * 8 + 16 * 8 + 64 + 1024;
-            h->lds_rows = need;
-            h->lds_sweep = std::max(need, lds_sampler);
-            if (need + 8192 <= lds_max) h->lds_sweep = std::max(h->lds_sweep, need + 8192);
+    if (h->req.storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_step));
+    if (h->plan.mode == 1) {
+        // the single-chain kernels, each with the LDS this plan launches it with (k_sweep_r where that fits)
+        for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::tall}) {
+            const size_t lds = sweep_lds(h->plan, k);
+            if (lds <= NGP_LDS_MAX) HCHK(hipFuncSetAttribute(sweep_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
-        {   // the lean kernel (models of BayesPR / BayesB / BayesC sets) has no use for the sampler's BayesR / Tuple staging area
-            const size_t lean_sampler = lds_sampler - NGP_SAMPLER_TUPLE_LDS;
-            const size_t streamer_need = (h->streamer >= 2) ? h->lds_rows : 2 * TB + misc;
-            h->lds_sweep_lean = std::max(streamer_need, lean_sampler);
-            if (streamer_need + 8192 <= lds_max) h->lds_sweep_lean = std::max(h->lds_sweep_lean, streamer_need + 8192);
-        }
-        {   // k_sweep_r: the sampler's BayesR staging area on top
-            const size_t streamer_need = (h->streamer >= 2) ? h->lds_rows : 2 * TB + misc;
-            size_t r = std::max(streamer_need, lds_sampler + (size_t)NGP_SAMPLER_R_LDS);
-            if (streamer_need + 8192 <= lds_max) r = std::max(r, streamer_need + 8192);
-            h->lds_sweep_r = (r <= lds_max) ? r : 0;
-            if (h->lds_sweep_r) HCHK(sweep_r_set_max_lds((int)h->lds_sweep_r));
-        }
-        if (h->lds_sweep > lds_max) return fail(h, NGP_ERR_ARG, "panel too tall for the persistent sweep (LDS)");
-        HCHK(sweep_set_max_lds_0((int)h->lds_sweep));
-        HCHK(sweep_set_max_lds_1((int)h->lds_sweep));
-        HCHK(sweep_tup_set_max_lds((int)h->lds_sweep));
-        if (h->V > 1) HCHK(sweep_tall_set_max_lds((int)h->lds_sweep));
         // every workgroup of the persistent kernel waits for others: the whole grid must be resident at once, one workgroup
         // per CU.  Checked here, not assumed (a grid that does not fit would only show up as a spin timeout).
         int wg_per_cu = 0;
-        if (h->V > 1) HCHK(sweep_tall_occupancy(&wg_per_cu, h->lds_sweep));
-        else HCHK(sweep_occupancy_0(&wg_per_cu, h->lds_sweep));
-        if (wg_per_cu < 1 || 1 + h->NG + h->S / h->V > (int64_t)wg_per_cu * h->cu_count)
-            return fail(h, NGP_ERR_STATE, "persistent sweep: grid of " + std::to_string(1 + h->NG + h->S / h->V) + " workgroups cannot be co-resident (" +
+        const SweepKernel occ = h->plan.V > 1 ? SweepKernel::tall : SweepKernel::lean;  // (at the LDS of the full kernel: the most but k_sweep_r's)
+        HCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_per_cu, sweep_kernel(occ), NGP_WG, sweep_lds(h->plan, SweepKernel::tup)));
+        const int64_t grid = sweep_grid(h->plan);
+        if (wg_per_cu < 1 || grid > (int64_t)wg_per_cu * h->cu_count)
+            return fail(h, NGP_ERR_STATE, "persistent sweep: grid of " + std::to_string(grid) + " workgroups cannot be co-resident (" +
                                               std::to_string(wg_per_cu) + " per CU x " + std::to_string(h->cu_count) + " CUs); use ngp_configure(mode 0)");
         if ((rc = dalloc(h, &h->d_cdlt, (size_t)NGP_RING * NGP_BLK))) return rc;
         if ((rc = dalloc(h, &h->d_cdltg, (size_t)NGP_RING * NGP_BLK * 2))) return rc;
@@ -547,20 +617,20 @@ int refresh_mpm_max(ngp_handle *h) {
 }
 
 int build_gram8(ngp_handle *h) {  // compact storage: exact integer dot products, then G = dot - N (m_k m_j)
-    const size_t per_block = (size_t)h->S * NGP_BLK * NGP_BLK * sizeof(uint32_t);
+    const size_t per_block = (size_t)h->plan.S * NGP_BLK * NGP_BLK * sizeof(uint32_t);
     int nb_max = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->NBLK, ((size_t)1 << 30) / per_block));
     nb_max = std::min(nb_max, 32768);
     uint32_t *d_gpart = nullptr;
     int rc;
-    if ((rc = dalloc(h, &d_gpart, (size_t)nb_max * h->S * NGP_BLK * NGP_BLK))) return rc;
-    for (int d = 0; d < h->D; d++)
+    if ((rc = dalloc(h, &d_gpart, (size_t)nb_max * h->plan.S * NGP_BLK * NGP_BLK))) return rc;
+    for (int d = 0; d < h->plan.D; d++)
         for (int64_t t0 = 0; t0 < h->NBLK; t0 += nb_max) {
             int nb = (int)std::min<int64_t>(nb_max, h->NBLK - t0);
-            hipLaunchKernelGGL(k_gram8_part, dim3((unsigned)h->S, (unsigned)nb), dim3(256), 0, h->stream, (const uint8_t *)h->d_tiles, d_gpart,
-                               (int)h->R, (int)h->S, (int)t0, d);
+            hipLaunchKernelGGL(k_gram8_part, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, (const uint8_t *)h->d_tiles, d_gpart,
+                               (int)h->plan.R, (int)h->plan.S, (int)t0, d);
             long long ne = (long long)nb * NGP_BLK * NGP_BLK;
             hipLaunchKernelGGL(k_gram8_reduce, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, d_gpart, h->d_gramx, h->d_mpm,
-                               h->d_mean, (long long)h->N, (int)h->S, (int)t0, nb, d, h->D);
+                               h->d_mean, (long long)h->N, (int)h->plan.S, (int)t0, nb, d, h->plan.D);
         }
     hipError_t e = hipStreamSynchronize(h->stream);
     dfree(d_gpart);
@@ -571,26 +641,26 @@ int build_gram8(ngp_handle *h) {  // compact storage: exact integer dot products
 }
 
 int build_gram(ngp_handle *h) {
-    if (h->storage == 1) return build_gram8(h);
+    if (h->req.storage == 1) return build_gram8(h);
     // batches of blocks so the shard-partial scratch stays <= ~1 GiB
-    const size_t per_block = (size_t)h->S * NGP_BLK * NGP_BLK * sizeof(double);
+    const size_t per_block = (size_t)h->plan.S * NGP_BLK * NGP_BLK * sizeof(double);
     int nb_max = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->NBLK, ((size_t)1 << 30) / per_block));
     nb_max = std::min(nb_max, 32768);
     double *d_gpart = nullptr;
     int rc;
-    if ((rc = dalloc(h, &d_gpart, (size_t)nb_max * h->S * NGP_BLK * NGP_BLK))) return rc;
-    for (int d = 0; d < h->D; d++)
+    if ((rc = dalloc(h, &d_gpart, (size_t)nb_max * h->plan.S * NGP_BLK * NGP_BLK))) return rc;
+    for (int d = 0; d < h->plan.D; d++)
         for (int64_t t0 = 0; t0 < h->NBLK; t0 += nb_max) {
             int nb = (int)std::min<int64_t>(nb_max, h->NBLK - t0);
             if (h->gram_engine == 0)  // fp64 VALU contraction: the default (1.63 ms per launch at 50k x 600k against 1.84 on the matrix cores)
-                hipLaunchKernelGGL(k_gram_part, dim3((unsigned)h->S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_gpart, (int)h->R,
-                                   (int)h->S, (int)t0, d);
+                hipLaunchKernelGGL(k_gram_part, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_gpart, (int)h->plan.R,
+                                   (int)h->plan.S, (int)t0, d);
             else                      // matrix cores (ngp_debug_set_knob bit 10 before the panel is set): v_mfma_f64_16x16x4_f64, the same sums in the same order
-                hipLaunchKernelGGL(k_gram_part_mfma, dim3((unsigned)h->S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_gpart, (int)h->R,
-                                   (int)h->S, (int)t0, d);
+                hipLaunchKernelGGL(k_gram_part_mfma, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_gpart, (int)h->plan.R,
+                                   (int)h->plan.S, (int)t0, d);
             long long ne = (long long)nb * NGP_BLK * NGP_BLK;
             hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, d_gpart, h->d_gramx, h->d_mpm,
-                               (int)h->S, (int)t0, nb, d, h->D);
+                               (int)h->plan.S, (int)t0, nb, d, h->plan.D);
         }
     hipError_t e = hipStreamSynchronize(h->stream);
     dfree(d_gpart);
@@ -618,7 +688,7 @@ int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64
     REQUIRE(M != nullptr, NGP_ERR_ARG, "null panel pointer");
     REQUIRE(ld >= h->N, NGP_ERR_ARG, "leading dimension smaller than N");
     REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "column range outside the panel");
-    REQUIRE(h->storage == 0 || sizeof(TIn) == 1, NGP_ERR_ARG,
+    REQUIRE(h->req.storage == 0 || sizeof(TIn) == 1, NGP_ERR_ARG,
             "compact storage takes genotype codes: ngp_panel_columns_u8, ngp_set_panel_u8, ngp_load_panel_file or ngp_generate_panel");
     const int64_t N = h->N;
     const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, ((int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
@@ -636,13 +706,13 @@ int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64
         hipLaunchKernelGGL(k_cols_mean<TIn>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, h->stream, (const TIn *)d_g, (long long)N, (long long)ld,
                            (long long)nc, centre, d_mu, d_bad);
         if constexpr (sizeof(TIn) == 1) {
-            if (h->storage == 1)  // the codes stay codes (the means are what the analytic centring uses)
+            if (h->req.storage == 1)  // the codes stay codes (the means are what the analytic centring uses)
                 hipLaunchKernelGGL(k_cols_fill8, dim3((unsigned)((h->L / 16 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles,
-                                   (const uint8_t *)d_g, (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->R, (int)h->S);
+                                   (const uint8_t *)d_g, (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->plan.R, (int)h->plan.S);
         }
-        if (h->storage == 0)
+        if (h->req.storage == 0)
         hipLaunchKernelGGL(k_cols_fill<TIn>, dim3((unsigned)((h->L / 4 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, h->d_tiles, (const TIn *)d_g,
-                           (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->R, (int)h->S, (const double *)d_mu);
+                           (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->plan.R, (int)h->plan.S, (const double *)d_mu);
         e = hipStreamSynchronize(h->stream);  // the staging buffer is reused by the next chunk
     }
     unsigned bad = 0;
@@ -752,16 +822,15 @@ bool is_kept(const ngp_handle *h, int64_t it) {  // src/samplers.jl:26
     return ((it - h->burnIn) % h->thin) == 0;
 }
 
-// one sweep over blocks [tb0, tb1): persistent kernel (mode 1) or two launches per block (mode 0)
 // launch arguments of the persistent sweep over blocks [tb0, tb1) of this handle's chain (advances the launch nonce)
 void fill_sweep_args(ngp_handle *h, int64_t tb0, int64_t tb1, SweepArgs &A) {
-    const int R = (int)h->R, S = (int)h->S;
+    const int R = (int)h->plan.R, S = (int)h->plan.S;
     A.tiles = h->d_tiles; A.ycorr = h->d_ycorr; A.gramx = h->d_gramx;
     const bool tf = wants_tinv(h) && h->tinv_blocks == h->NBLK;
     A.tinv = (tf && h->lin_any) ? h->d_tinv : nullptr;
     A.blin = (tf && h->lin_any) ? h->d_blin : nullptr;
     A.lin_all = (tf && h->lin_any) ? h->lin_all : 0;
-    A.V = h->V; A.D = h->D; A.R = R; A.S = S; A.NG = h->NG; A.near = h->near; A.fine_ok = 0; A.t0 = (int)tb0; A.t1 = (int)tb1;
+    A.V = h->plan.V; A.D = h->plan.D; A.R = R; A.S = S; A.NG = h->plan.NG; A.near = h->plan.near; A.fine_ok = 0; A.t0 = (int)tb0; A.t1 = (int)tb1;
     A.beta = h->d_beta; A.delta = h->d_delta; A.c = h->d_c; A.w = h->d_w; A.q = h->d_q; A.mpm = h->d_mpm; A.chi = h->d_chi;
     A.setof = h->d_setof; A.vbidx = h->d_vbidx; A.sets = h->d_sets; A.varBeta = h->d_varBeta;
     A.rcls = h->d_rcls; A.rhs0 = h->d_rhs0; A.scal = h->d_scal; A.Ppad = h->Ppad;
@@ -774,37 +843,23 @@ void fill_sweep_args(ngp_handle *h, int64_t tb0, int64_t tb1, SweepArgs &A) {
     A.census_tbl = h->d_census_tbl; A.iter_tag = (unsigned)(h->iter + 1);
     A.census_fail = (h->dbg_census_fail_iter > 0 && !h->exclusive) ? (unsigned)h->dbg_census_fail_iter : 0u;
     A.dbg = h->d_dbg;
-    A.fine_ok = ((size_t)2 * (R / 4) * NGP_QS + (size_t)R * 80 + 8320 + 8192 <= h->lds_sweep) ? 1 : 0;  // diagnostic timeline fits in LDS
-    A.variant = h->streamer; A.knob = h->knob;
-    if (h->streamer >= 2) A.fine_ok = (h->lds_rows + 8192 <= h->lds_sweep) ? 1 : 0;
+    A.fine_ok = (streamer_lds(h->plan, 1) + 8192 <= sweep_lds(h->plan, SweepKernel::diag)) ? 1 : 0;  // diagnostic timeline fits in LDS
+    A.variant = h->plan.streamer; A.knob = h->knob;
     A.mean = h->d_mean; A.N = h->N;
     A.dbg_mode = h->dbg_mode;
 }
 
 // one sweep over blocks [tb0, tb1): persistent kernel (mode 1) or two launches per block (mode 0)
 void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
-    const int R = (int)h->R, S = (int)h->S;
-    if (h->mode == 1) {
+    const int R = (int)h->plan.R, S = (int)h->plan.S;
+    if (h->plan.mode == 1) {
         // (the hand-off counters were zeroed by k_prep, which precedes every sweep in the stream)
         SweepArgs A;
         fill_sweep_args(h, tb0, tb1, A);
-        h->last_grid = 1 + h->NG + S / h->V;
+        const SweepKernel k = pick_kernel(h->plan, 1, h->d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0);
+        h->last_grid = sweep_grid(h->plan);
         if (evs) (void)hipEventRecord(evs[0], h->stream);
-        if (h->V > 1)  // several shards per streamer workgroup: a kernel of its own (no diagnostics there)
-            sweep_tall_launch((unsigned)h->last_grid, h->lds_sweep, h->stream, A);
-        else if (h->d_dbg || h->dbg_mode)  // diagnostic instantiation: stamps and timing modes exist only there
-            sweep_launch_1((unsigned)h->last_grid, h->lds_sweep, h->stream, A);
-        else if (h->nclass_total > 0 && h->lds_sweep_r && !(h->knob & 65536))  // a BayesR set: the flavour that fetches its coefficients ahead
-            sweep_r_launch((unsigned)h->last_grid, h->lds_sweep_r, h->stream, A);
-        // Models with a Tuple or a BayesR set run the kernel that carries those chains (k_sweep<false>, the kernel of BayesPR / BayesB /
-        // BayesC, does not: ngp_sweep.h, role_sampler).  Every other model takes the lean kernel at every shape (in round 3 tall fp32
-        // shards ran 1.7-2 % faster in the full kernel -- register allocation, not design; since the round-4 hand-off the lean
-        // kernel is level or ahead there too: 23.4-23.6 against 23.3-23.9 ms per iteration at 50k x 600k).  Knob bit 14 forces the
-        // full kernel.
-        else if (h->ntuple > 0 || h->nclass_total > 0 || (h->knob & 16384))
-            sweep_tup_launch((unsigned)h->last_grid, h->lds_sweep, h->stream, A);
-        else
-            sweep_launch_0((unsigned)h->last_grid, h->lds_sweep_lean, h->stream, A);
+        launch_sweep_kernel(k, h->last_grid, sweep_lds(h->plan, k), h->stream, &A);
         if (evs) (void)hipEventRecord(evs[1], h->stream);
         h->sweep_launches += 1;
         return;
@@ -817,7 +872,7 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
                            S, (int)t, do_upd, do_gemv);
         if (evs && do_gemv) (void)hipEventRecord(evs[e++], h->stream);
         if (do_gemv)
-            hipLaunchKernelGGL(k_recur, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_gramx, h->D, S, (int)t, h->d_beta, h->d_delta,
+            hipLaunchKernelGGL(k_recur, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_gramx, h->plan.D, S, (int)t, h->d_beta, h->d_delta,
                                h->d_c, h->d_w, h->d_q, h->d_mpm, h->d_chi, h->d_setof, h->d_vbidx, h->d_sets, h->d_varBeta, h->d_dlt, h->d_rcls,
                                (long long)h->Ppad, h->d_rhs0, h->d_scal, h->d_tup, h->d_tupc, h->d_tupg,
                                (const double *)((wants_tinv(h) && h->tinv_blocks == h->NBLK && h->lin_any) ? h->d_tinv : nullptr), (const unsigned *)h->d_blin);
@@ -827,7 +882,7 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
 
 // placement census of the last sweep launch (SweepArgs.census_tbl): who arrived, and where
 std::string census_report(ngp_handle *h) {
-    const size_t grid = (size_t)(h->last_grid > 0 ? h->last_grid : 1 + h->NG + h->S / h->V);
+    const size_t grid = (size_t)(h->last_grid > 0 ? h->last_grid : sweep_grid(h->plan));
     std::vector<unsigned long long> tb(grid, 0ull);
     if (!h->d_census_tbl || hipMemcpy(tb.data(), h->d_census_tbl, grid * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return "(no census)";
     int per_xcc[16] = {0}, per_se[16][8] = {{0}};
@@ -853,7 +908,7 @@ std::string census_report(ngp_handle *h) {
 // says which iteration; the abort words are cleared, the caller runs it again with the device to itself) or an error (poisoned)
 #define NGP_RETRY_CENSUS 1
 int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
-    if (h->mode != 1) return NGP_OK;
+    if (h->plan.mode != 1) return NGP_OK;
     unsigned w[2] = {0, 0};
     HCHK(hipMemcpy(w, h->d_abort, sizeof(w), hipMemcpyDeviceToHost));
     if (w[0] == 0) return NGP_OK;
@@ -907,7 +962,7 @@ int sample_enqueue(ngp_handle *h);  // (below)
 // T = inv(L) of every linear block from this iteration's coefficients (k_tinv; behind k_prep in the stream, in front of the sweep)
 void launch_tinv(ngp_handle *h) {  // (sync_linear_blocks has run for this call's active set)
     if (!wants_tinv(h) || h->tinv_blocks != h->NBLK || !h->lin_any) return;
-    hipLaunchKernelGGL(k_tinv, dim3((unsigned)h->NBLK), dim3(64), 0, h->stream, (const double *)h->d_gramx, h->D, (const double *)h->d_c,
+    hipLaunchKernelGGL(k_tinv, dim3((unsigned)h->NBLK), dim3(64), 0, h->stream, (const double *)h->d_gramx, h->plan.D, (const double *)h->d_c,
                        (const unsigned *)h->d_blin, h->d_tinv, (const unsigned *)h->d_abort, (const double *)h->d_tupc, (long long)h->Ppad);
 }
 
@@ -924,7 +979,7 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->d_setof, h->d_loc,
                        h->d_vbidx, h->d_sets, h->d_scal, h->d_varBeta, h->d_mpm, h->d_lhs0, h->d_rhs0, h->d_beta, h->d_c, h->d_w,
                        h->d_q, h->d_T, h->d_chi, -1, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->d_regs, h->d_regchi, h->d_rcls,
-                       h->d_ccnt, (long long)(h->mode == 1 ? h->ccnt_words : 0), h->d_abort, h->d_tup, h->d_tupc, h->d_tupg);
+                       h->d_ccnt, (long long)(h->plan.mode == 1 ? h->ccnt_words : 0), h->d_abort, h->d_tup, h->d_tupc, h->d_tupg);
     launch_tinv(h);
 }
 
@@ -1224,16 +1279,16 @@ int32_t ngp_end_panel(ngp_handle *h) {
 static void ingest_u8_chunk(ngp_handle *h, const uint8_t *d_g, int64_t N, int64_t ld, int64_t t0, int64_t nb, int64_t ncols, int centre,
                             double *d_mu) {
     const int64_t c0 = t0 * NGP_BLK;
-    if (h->storage == 1) {  // the bytes stay bytes; the means go to the handle
+    if (h->req.storage == 1) {  // the bytes stay bytes; the means go to the handle
         hipLaunchKernelGGL(k_u8_colmean, dim3((unsigned)ncols), dim3(256), 0, h->stream, d_g, (long long)N, (long long)ld, (int)centre,
                            h->d_mean + c0);
-        hipLaunchKernelGGL(k_u8_fill8, dim3((unsigned)h->S, (unsigned)nb), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles, d_g, (long long)N,
-                           (long long)ld, (long long)ncols, (int)h->R, (int)h->S, (long long)t0);
+        hipLaunchKernelGGL(k_u8_fill8, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles, d_g, (long long)N,
+                           (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0);
     } else {
         hipLaunchKernelGGL(k_u8_colmean, dim3((unsigned)ncols), dim3(256), 0, h->stream, d_g, (long long)N, (long long)ld, (int)centre, d_mu);
         (void)hipMemcpyAsync(h->d_mean + c0, d_mu, (size_t)ncols * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-        hipLaunchKernelGGL(k_u8_fill, dim3((unsigned)h->S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_g, (long long)N,
-                           (long long)ld, (long long)ncols, (int)h->R, (int)h->S, (long long)t0, d_mu);
+        hipLaunchKernelGGL(k_u8_fill, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_g, (long long)N,
+                           (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0, d_mu);
     }
 }
 
@@ -1397,12 +1452,12 @@ int32_t ngp_generate_panel(ngp_handle *h, int64_t N, int64_t P, double maf_lo, d
     hipLaunchKernelGGL(k_gen_colmean, dim3((unsigned)P), dim3(256), 0, h->stream, (long long)N, (long long)P, maf_lo, maf_hi, panel_seed,
                        d_mu, d_thr);
     (void)hipMemcpyAsync(h->d_mean, d_mu, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-    if (h->storage == 1) {
-        hipLaunchKernelGGL(k_gen_fill8, dim3((unsigned)h->S, (unsigned)h->NBLK), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles, (long long)N,
-                           (long long)P, (int)h->R, (int)h->S, panel_seed, d_thr);
+    if (h->req.storage == 1) {
+        hipLaunchKernelGGL(k_gen_fill8, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles, (long long)N,
+                           (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_thr);
     } else
-    hipLaunchKernelGGL(k_gen_fill, dim3((unsigned)h->S, (unsigned)h->NBLK), dim3(256), 0, h->stream, h->d_tiles, (long long)N,
-                       (long long)P, (int)h->R, (int)h->S, panel_seed, d_mu, d_thr);
+    hipLaunchKernelGGL(k_gen_fill, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, h->d_tiles, (long long)N,
+                       (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_mu, d_thr);
     hipError_t e = hipStreamSynchronize(h->stream);
     dfree(d_mu); dfree(d_thr);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("generate_panel: ") + hipGetErrorString(e));
@@ -1432,8 +1487,8 @@ int32_t ngp_get_layout(ngp_handle *h, int64_t *R, int64_t *S, int64_t *nblk) {
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
-    if (R) *R = h->R;
-    if (S) *S = h->S;
+    if (R) *R = h->plan.R;
+    if (S) *S = h->plan.S;
     if (nblk) *nblk = h->NBLK;
     return NGP_OK;
     NGP_CATCH(h)
@@ -1458,7 +1513,7 @@ int32_t ngp_get_gram(ngp_handle *h, int64_t t, double *out) {
     REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(out && t >= 0 && t < h->NBLK, NGP_ERR_ARG, "block index out of range");
-    HCHK(hipMemcpy(out, h->d_gramx + (size_t)t * h->D * NGP_BLK * NGP_BLK, NGP_BLK * NGP_BLK * sizeof(double), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(out, h->d_gramx + (size_t)t * h->plan.D * NGP_BLK * NGP_BLK, NGP_BLK * NGP_BLK * sizeof(double), hipMemcpyDeviceToHost));
     // the device keeps entry [k][j] for j > k only (plus x'x in mpm); hand back the symmetric block
     double diag[NGP_BLK];
     HCHK(hipMemcpy(diag, h->d_mpm + (size_t)t * NGP_BLK, sizeof(diag), hipMemcpyDeviceToHost));
@@ -1482,11 +1537,11 @@ int32_t ngp_xbeta(ngp_handle *h, const double *beta, int64_t P, double *out, int
     if ((rc = dalloc(h, &d_o, (size_t)h->L))) { dfree(d_b); return rc; }
     hipError_t e = hipMemcpyAsync(d_b, beta, (size_t)P * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess && (size_t)h->Ppad > (size_t)P) e = hipMemsetAsync(d_b + P, 0, ((size_t)h->Ppad - (size_t)P) * sizeof(double), h->stream);
-    if (h->storage == 1)
-        hipLaunchKernelGGL(k_xbeta8, dim3((unsigned)h->S), dim3(256), 0, h->stream, (const uint8_t *)h->d_tiles, h->d_mean, d_b, d_o, (int)h->R,
-                           (int)h->S, (long long)h->NBLK, (long long)h->N);
+    if (h->req.storage == 1)
+        hipLaunchKernelGGL(k_xbeta8, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, (const uint8_t *)h->d_tiles, h->d_mean, d_b, d_o, (int)h->plan.R,
+                           (int)h->plan.S, (long long)h->NBLK, (long long)h->N);
     else
-    hipLaunchKernelGGL(k_xbeta, dim3((unsigned)h->S), dim3(256), 0, h->stream, h->d_tiles, d_b, d_o, (int)h->R, (int)h->S,
+    hipLaunchKernelGGL(k_xbeta, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, h->d_tiles, d_b, d_o, (int)h->plan.R, (int)h->plan.S,
                        (long long)h->NBLK);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1683,26 +1738,18 @@ int prepare_run(ngp_handle *h, int64_t niter) {
 // K chains per pass over the panel (k_sweep_multi, ngp_sweep.h): can these handles' chains share ONE sweep launch?  They must
 // share one panel (ngp_share_panel) and run the engine the fused kernel is built for: persistent sweep, fp32 tiles, phase streamer
 // on shards of at most 64 rows, lag 6 or 8, no diagnostics -- and the fused grid must fit the device.
-// reducer workgroups of a fused launch serve two chains each from NGP_PAIR_FROM chains on (phase streamer only; knob bits 11 / 12
-// force it on / off for timing)
-int fused_pair(const ngp_handle *h0, int n) {
-    if (h0->streamer != 1 || n < 2) return 0;
-    if (h0->knob & 2048) return 1;
-    if (h0->knob & 4096) return 0;
-    return n >= NGP_PAIR_FROM ? 1 : 0;
-}
 
 bool fusable(ngp_handle **hs, int n) {
     if (n < 2 || n > NGP_MAXC) return false;
     ngp_handle *h0 = hs[0];
-    if (!h0->pm || h0->mode != 1 || h0->V != 1) return false;
-    const bool phase = h0->storage == 0 && h0->streamer == 1 && h0->R <= 64 && (h0->D == 6 || h0->D == 8);   // role_streamer_multi
-    const bool rows = h0->storage == 0 && h0->streamer == 2 && (h0->D >= 4 && h0->D <= 6) && n == 2 &&        // role_streamer_rows_multi
-                      ngp_rows_multi_lds_bytes((int)h0->R, n) <= (size_t)160 * 1024;
+    if (!h0->pm || h0->plan.mode != 1 || h0->plan.V != 1) return false;
+    const bool phase = h0->req.storage == 0 && h0->plan.streamer == 1 && h0->plan.R <= 64 && (h0->plan.D == 6 || h0->plan.D == 8);   // role_streamer_multi
+    const bool rows = h0->req.storage == 0 && h0->plan.streamer == 2 && (h0->plan.D >= 4 && h0->plan.D <= 6) && n == 2 &&        // role_streamer_rows_multi
+                      streamer_lds(h0->plan, n) <= NGP_LDS_MAX;
     bool bytes = false;                                                                                     // ... over byte tiles
-    if (h0->storage == 1 && h0->streamer == 3 && n <= 3 && ngp_rows_multi_lds_bytes((int)h0->R, n, true) <= (size_t)160 * 1024) {
-        const int nt = ngp_u8_tasks((int)h0->R);  // update tasks per lane: what the delay line leaves for more chains' arithmetic
-        bytes = (nt == 1 && (h0->D == 4 || h0->D == 6 || h0->D == 8)) || (nt == 2 && (h0->D == 4 || h0->D == 8)) || (nt == 4 && n == 2 && h0->D == 4);
+    if (h0->req.storage == 1 && h0->plan.streamer == 3 && n <= 3 && streamer_lds(h0->plan, n) <= NGP_LDS_MAX) {
+        const int nt = ngp_u8_tasks((int)h0->plan.R);  // update tasks per lane: what the delay line leaves for more chains' arithmetic
+        bytes = (nt == 1 && (h0->plan.D == 4 || h0->plan.D == 6 || h0->plan.D == 8)) || (nt == 2 && (h0->plan.D == 4 || h0->plan.D == 8)) || (nt == 4 && n == 2 && h0->plan.D == 4);
     }
     if (!phase && !rows && !bytes) return false;
     for (int i = 0; i < n; i++) {
@@ -1710,7 +1757,7 @@ bool fusable(ngp_handle **hs, int n) {
         if (h->pm != h0->pm || h->device != h0->device || h->dbg_mode != 0 || h->d_dbg || h->dbg_census_fail_iter > 0) return false;
     }
     // (the samplers sit at blocks 0, 8, .., 8 (n - 1) of the grid -- one XCD under round-robin placement: the grid must reach the last)
-    const int64_t grid = (int64_t)n + ngp_multi_reducers(n, h0->NG, fused_pair(h0, n)) + h0->S;
+    const int64_t grid = sweep_grid(h0->plan, n);
     return grid <= h0->cu_count && grid > (int64_t)8 * (n - 1);
 }
 
@@ -1721,39 +1768,27 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     int rc;
     for (int i = 0; i < n; i++)
         if ((rc = prepare_run(hs[i], niter))) { if (i) h->err = hs[i]->err; return rc; }
-    const int pair = fused_pair(h, n);
-    const int64_t grid = (int64_t)n + ngp_multi_reducers(n, h->NG, pair) + h->S;
-    const size_t lds_sampler = (size_t)(3 * 4096 + 2 * NGP_RING * NGP_BLK + 6 * NGP_BLK) * sizeof(double) + 2 * NGP_BLK * sizeof(int) + 320 + NGP_SAMPLER_TUPLE_LDS;
-    const size_t lds = std::max(h->streamer == 3 ? ngp_rows_multi_lds_bytes((int)h->R, n, true)
-                                                 : (h->streamer == 2 ? ngp_rows_multi_lds_bytes((int)h->R, n) : ngp_multi_lds_bytes((int)h->R, n)), lds_sampler);
-    REQUIRE(lds <= 160 * 1024, NGP_ERR_STATE, "fused sweep: LDS of a streamer with this many chains exceeds 160 KiB");
     bool tup = false, rset = false;  // a chain with a Tuple / BayesR set: the fused kernel whose samplers hold that chain
     for (int i = 0; i < n; i++) { tup = tup || hs[i]->ntuple > 0; rset = rset || hs[i]->nclass_total > 0; }
-    // (BayesR: the samplers of k_sweep_r, their class coefficients staged in LDS -- where that fits beside the sampler's own; else the chain of k_sweep_multi(_tup))
-    const size_t lds_r = std::max(lds, lds_sampler + (size_t)NGP_SAMPLER_R_LDS);
-    const bool use_r = rset && lds_r <= (size_t)160 * 1024 && !(h->knob & 65536);
-    const size_t lds_launch = use_r ? lds_r : lds;
-    HCHK(use_r ? sweep_multi_r_set_max_lds((int)lds_launch) : (tup ? sweep_multi_tup_set_max_lds((int)lds_launch) : sweep_multi_set_max_lds((int)lds_launch)));
+    const SweepKernel kern = pick_kernel(h->plan, n, false, tup, rset);
+    const int64_t grid = sweep_grid(h->plan, n);
+    const size_t lds = sweep_lds(h->plan, kern, n);
+    REQUIRE(lds <= NGP_LDS_MAX, NGP_ERR_STATE, "fused sweep: LDS of a streamer with this many chains exceeds 160 KiB");
+    HCHK(hipFuncSetAttribute(sweep_kernel(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // One abort word: the leader's.  The sweep runs on the leader's stream; every chain's small kernels (head, coefficients, variance
     // draws, posterior sums: six launches of a few microseconds each) stay on the chain's OWN stream, tied to the sweep by events --
     // the K chains' small kernels then run side by side instead of one chain after the other (eight chains: 0.34 ms of a 4.35-ms pass).
-    // knob bit 13: everything on the leader's stream, as the first version did.
-    const bool serial = (h->knob & 8192) != 0;
-    std::vector<hipStream_t> st((size_t)n);
     std::vector<unsigned *> ab((size_t)n);
     std::vector<hipEvent_t> evp((size_t)n, nullptr);
     hipEvent_t evs = nullptr;
     for (int i = 0; i < n; i++) HCHK(hipStreamSynchronize(hs[i]->stream));
-    for (int i = 0; i < n; i++) {
-        st[i] = hs[i]->stream; ab[i] = hs[i]->d_abort; hs[i]->d_abort = h->d_abort;
-        if (serial) hs[i]->stream = h->stream;
-    }
+    for (int i = 0; i < n; i++) { ab[i] = hs[i]->d_abort; hs[i]->d_abort = h->d_abort; }
     auto restore = [&]() {
-        for (int i = 0; i < n; i++) { hs[i]->stream = st[i]; hs[i]->d_abort = ab[i]; if (evp[i]) (void)hipEventDestroy(evp[i]); }
+        for (int i = 0; i < n; i++) { hs[i]->d_abort = ab[i]; if (evp[i]) (void)hipEventDestroy(evp[i]); }
         if (evs) (void)hipEventDestroy(evs);
     };
     // (a scope guard: an exception on the way -- a std::string or std::vector that cannot allocate -- unwinds to the ABI's barrier
-    // with every handle's own abort word and stream back in place; ngp_destroy would otherwise free the leader's buffer once per handle)
+    // with every handle's own abort word back in place; ngp_destroy would otherwise free the leader's buffer once per handle)
     struct Guard {
         decltype(restore) &f;
         bool armed = true;
@@ -1761,14 +1796,12 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
         void now() { if (armed) { armed = false; f(); } }
     } guard{restore};
     hipError_t e = hipSuccess;
-    if (!serial) {
-        for (int i = 1; i < n && e == hipSuccess; i++) e = hipEventCreateWithFlags(&evp[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&evs, hipEventDisableTiming);
-        if (e != hipSuccess) { guard.now(); return fail(h, NGP_ERR_HIP, std::string("fused run: ") + hipGetErrorString(e)); }
-    }
+    for (int i = 1; i < n && e == hipSuccess; i++) e = hipEventCreateWithFlags(&evp[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&evs, hipEventDisableTiming);
+    if (e != hipSuccess) { guard.now(); return fail(h, NGP_ERR_HIP, std::string("fused run: ") + hipGetErrorString(e)); }
     auto sync_all = [&]() {
         hipError_t r = hipStreamSynchronize(h->stream);
-        if (!serial) for (int i = 1; i < n; i++) { hipError_t q = hipStreamSynchronize(hs[i]->stream); if (r == hipSuccess) r = q; }
+        for (int i = 1; i < n; i++) { hipError_t q = hipStreamSynchronize(hs[i]->stream); if (r == hipSuccess) r = q; }
         return r;
     };
     CuLease lease(h, grid);
@@ -1776,24 +1809,20 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     rc = NGP_OK;
     for (int64_t it = 0; it < niter && rc == NGP_OK && e == hipSuccess; ++it) {
         MultiArgs M;
-        M.K = n; M.pair = pair;
+        M.K = n; M.pair = fused_pair(h->plan, n);
         for (int i = 0; i < n; i++) {
             iteration_pre(hs[i], it, false);
             fill_sweep_args(hs[i], 0, hs[i]->NBLK, M.a[i]);
-            if (!serial && i > 0) {  // the sweep waits for this chain's coefficients (and cleared hand-off counters)
+            if (i > 0) {  // the sweep waits for this chain's coefficients (and cleared hand-off counters)
                 (void)hipEventRecord(evp[i], hs[i]->stream);
                 (void)hipStreamWaitEvent(h->stream, evp[i], 0);
             }
         }
         for (int i = 1; i < n; i++) { M.a[i].census = nullptr; M.a[i].xcc_w = M.a[0].xcc_w; }
-        if (use_r) sweep_multi_r_launch((unsigned)grid, lds_launch, h->stream, M);
-        else if (tup) sweep_multi_tup_launch((unsigned)grid, lds_launch, h->stream, M);
-        else sweep_multi_launch((unsigned)grid, lds_launch, h->stream, M);
+        launch_sweep_kernel(kern, grid, lds, h->stream, &M);
         h->sweep_launches += 1; h->last_grid = grid;
-        if (!serial) {
-            (void)hipEventRecord(evs, h->stream);
-            for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(hs[i]->stream, evs, 0);
-        }
+        (void)hipEventRecord(evs, h->stream);
+        for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(hs[i]->stream, evs, 0);
         for (int i = 0; i < n && rc == NGP_OK; i++) { rc = iteration_post(hs[i], it); if (rc && i) h->err = hs[i]->err; }
         if (rc) break;
         if ((it & 15) == 15 || it + 1 == niter) {  // bound the launch queue
@@ -2015,7 +2044,7 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
         hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->d_setof, h->d_loc,
                            h->d_vbidx, h->d_sets, h->d_scal, h->d_varBeta, h->d_mpm, h->d_lhs0, h->d_rhs0, h->d_beta, h->d_c, h->d_w,
                            h->d_q, h->d_T, h->d_chi, (int)set_id, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->d_regs, h->d_regchi, h->d_rcls,
-                           h->d_ccnt, (long long)(h->mode == 1 ? h->ccnt_words : 0), h->d_abort, h->d_tup, h->d_tupc, h->d_tupg);
+                           h->d_ccnt, (long long)(h->plan.mode == 1 ? h->ccnt_words : 0), h->d_abort, h->d_tup, h->d_tupc, h->d_tupg);
         launch_tinv(h);
         launch_sweep(h, tb0, tb1, nullptr);
         launch_variance(h, (int)set_id, it);
@@ -2092,7 +2121,7 @@ int32_t ngp_profile_iteration(ngp_handle *h, double *avg_ms, int64_t *launches, 
     int rc;
     if ((rc = enter(h))) return rc;
     if ((rc = ready(h))) return rc;
-    const int64_t n = (h->mode == 1) ? 1 : h->NBLK;
+    const int64_t n = (h->plan.mode == 1) ? 1 : h->NBLK;
     std::vector<hipEvent_t> evs((size_t)(2 * n));
     for (auto &e : evs) HCHK(hipEventCreate(&e));
     if (h->trace_cap < 1) {
@@ -2115,8 +2144,8 @@ int32_t ngp_profile_iteration(ngp_handle *h, double *avg_ms, int64_t *launches, 
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("profile_iteration: ") + hipGetErrorString(e));
     if (avg_ms) *avg_ms = tot / (double)n;
     if (launches) *launches = n;
-    const double bpe = (h->storage == 1) ? 1.0 : 4.0;  // algorithmic bytes per genotype: the panel is read once per iteration
-    if (bytes_per_launch) *bytes_per_launch = (h->mode == 1) ? (double)h->N * (double)h->P * bpe : (double)h->N * NGP_BLK * bpe;
+    const double bpe = (h->req.storage == 1) ? 1.0 : 4.0;  // algorithmic bytes per genotype: the panel is read once per iteration
+    if (bytes_per_launch) *bytes_per_launch = (h->plan.mode == 1) ? (double)h->N * (double)h->P * bpe : (double)h->N * NGP_BLK * bpe;
     return rc;
     NGP_CATCH(h)
 }
@@ -2140,7 +2169,7 @@ int32_t ngp_configure(ngp_handle *h, int32_t mode, int32_t lag) {
     REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_configure must precede the panel upload");
     REQUIRE(mode == 0 || mode == 1, NGP_ERR_ARG, "mode must be 0 (per-block launches) or 1 (persistent sweep)");
     REQUIRE(lag >= 1 && lag <= NGP_MAX_LAG, NGP_ERR_ARG, "lag must be in 1..12 (above 8: compact storage)");
-    h->mode = mode; h->lag = lag; h->lag_auto = false;
+    h->req.mode = mode; h->req.lag = lag; h->req.lag_auto = false;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2151,7 +2180,7 @@ int32_t ngp_set_near_lags(ngp_handle *h, int32_t near) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_near_lags must precede the panel upload");
     REQUIRE(near >= 0 && near <= 4, NGP_ERR_ARG, "near lags: 0 (automatic) or 1..4");
-    h->near_req = near;
+    h->req.near_req = near;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2160,7 +2189,7 @@ int32_t ngp_get_near_lags(ngp_handle *h, int32_t *near) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    if (near) *near = h->near;
+    if (near) *near = h->plan.near;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2188,8 +2217,8 @@ int32_t ngp_get_config(ngp_handle *h, int32_t *mode, int32_t *lag) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    if (mode) *mode = h->mode;
-    if (lag) *lag = h->D;
+    if (mode) *mode = h->req.mode;  // (after the panel: the engine in force, see alloc_panel)
+    if (lag) *lag = h->plan.D;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2262,7 +2291,7 @@ int32_t ngp_set_streamer(ngp_handle *h, int32_t variant) {
     REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_streamer must precede the panel upload");
     REQUIRE((variant >= 0 && variant <= 2) || variant == 4 || variant == 6, NGP_ERR_ARG,
             "streamer variant: 0 (automatic), 1 (phase streamer), 2 (row-owning waves) or 4 / 6 (row-owning waves, two / three shards per workgroup)");
-    h->streamer_req = variant;
+    h->req.streamer_req = variant;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2273,7 +2302,7 @@ int32_t ngp_set_max_shards(ngp_handle *h, int32_t max_shards) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_max_shards must precede the panel upload");
     REQUIRE(max_shards >= 0, NGP_ERR_ARG, "max_shards: 0 (automatic) or a positive number of streamer workgroups");
-    h->max_shards_req = max_shards;
+    h->req.max_shards_req = max_shards;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2316,9 +2345,12 @@ int32_t ngp_shards_for_pass(ngp_handle *h, int32_t chains, int32_t *max_shards) 
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(chains >= 1 && chains <= NGP_MAXC && max_shards, NGP_ERR_ARG, "chains per pass: 1..8");
+    SweepPlan p;  // (the phase streamer, one shard per workgroup: the engine this serves)
     int s = h->cu_count;
-    const int pair = (chains >= NGP_PAIR_FROM && !(h->knob & 4096)) || (h->knob & 2048) ? 1 : 0;  // (fused_pair, for the phase streamer this serves)
-    while (s >= 1 && (int64_t)chains + ngp_multi_reducers(chains, (s + NGP_GRP - 1) / NGP_GRP, pair) + s > h->cu_count) --s;
+    for (; s >= 1; --s) {
+        p.S = s; p.NG = (s + NGP_GRP - 1) / NGP_GRP;
+        if (sweep_grid(p, chains) <= h->cu_count) break;
+    }
     REQUIRE(s >= 1, NGP_ERR_ARG, "too many chains for this device");
     *max_shards = s;
     return NGP_OK;
@@ -2331,7 +2363,7 @@ int32_t ngp_set_storage(ngp_handle *h, int32_t storage) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_storage must precede the panel upload");
     REQUIRE(storage == NGP_STORAGE_F32 || storage == NGP_STORAGE_U8, NGP_ERR_ARG, "storage: 0 (fp32 tiles) or 1 (compact: bytes + column means)");
-    h->storage = storage;
+    h->req.storage = storage;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2340,7 +2372,7 @@ int32_t ngp_get_storage(ngp_handle *h, int32_t *storage, double *means, int64_t 
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    if (storage) *storage = h->storage;
+    if (storage) *storage = h->req.storage;
     if (means) {
         REQUIRE(h->d_tiles != nullptr && h->d_mean != nullptr, NGP_ERR_STATE, "column means exist after the panel is set");
         REQUIRE(P == h->P, NGP_ERR_ARG, "means buffer must hold P entries");
@@ -2355,8 +2387,8 @@ int32_t ngp_get_streamer(ngp_handle *h, int32_t *variant, int32_t *gemv_chains) 
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    if (variant) *variant = (h->mode == 1) ? h->streamer : 0;
-    if (gemv_chains) *gemv_chains = h->nchain;
+    if (variant) *variant = (h->req.mode == 1) ? h->plan.streamer : 0;
+    if (gemv_chains) *gemv_chains = h->plan.nchain;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2871,7 +2903,7 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
     tp.k = k; tp.col0 = col0; tp.nloc = nloc; tp.vb_off = h->nvb; tp.df = df;
     for (int a = 0; a < k * k; a++) tp.scale[a] = scale[a];
     HCHK(hipMemcpy(h->d_tup + si, &tp, sizeof(DTup), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_tuple_gkk, dim3((unsigned)((nloc * k + 255) / 256)), dim3(256), 0, h->stream, h->d_gramx, h->D, h->d_mpm, tp, h->d_tupg,
+    hipLaunchKernelGGL(k_tuple_gkk, dim3((unsigned)((nloc * k + 255) / 256)), dim3(256), 0, h->stream, h->d_gramx, h->plan.D, h->d_mpm, tp, h->d_tupg,
                        (long long)h->Ppad);
     DSet ds;
     memset(&ds, 0, sizeof(ds));
@@ -3048,8 +3080,8 @@ int32_t ngp_get_census(ngp_handle *h, uint64_t *out, int64_t n, int64_t *grid, i
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->mode == 1, NGP_ERR_STATE, "no persistent sweep on this handle");
-    const int64_t g = h->last_grid > 0 ? h->last_grid : 1 + h->NG + h->S / h->V;
+    REQUIRE(h->d_tiles != nullptr && h->plan.mode == 1, NGP_ERR_STATE, "no persistent sweep on this handle");
+    const int64_t g = h->last_grid > 0 ? h->last_grid : sweep_grid(h->plan);
     if (grid) *grid = g;
     if (retries) *retries = h->census_retries;
     if (exclusive) *exclusive = h->exclusive ? 1 : 0;

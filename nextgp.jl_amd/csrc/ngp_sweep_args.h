@@ -134,30 +134,19 @@ __host__ __device__ inline size_t ngp_rows_multi_lds_bytes(int R, int K, bool u8
     const size_t nq = (size_t)R / (u8 ? 16 : 4), hq = nq + 1 < 2 * (size_t)NGP_ROWS_HMAX ? (nq + 1) / 2 : (size_t)NGP_ROWS_HMAX;
     return (2 * nq + hq) * NGP_QS + (size_t)K * ngp_rows_multi_chain_doubles(R) * 8 + 64 + 64 + 1024;
 }
-hipError_t sweep_multi_set_max_lds(int bytes);
-void sweep_multi_launch(unsigned grid, size_t lds_bytes, hipStream_t stream, const MultiArgs &M);
-hipError_t sweep_multi_tup_set_max_lds(int bytes);  // (chains with a Tuple set: k_sweep_multi_tup, the Tuple translation unit)
-void sweep_multi_tup_launch(unsigned grid, size_t lds_bytes, hipStream_t stream, const MultiArgs &M);
-hipError_t sweep_multi_r_set_max_lds(int bytes);  // (chains with a BayesR set: k_sweep_multi_r, the BayesR translation unit)
-void sweep_multi_r_launch(unsigned grid, size_t lds_bytes, hipStream_t stream, const MultiArgs &M);
 
-// Host entry points of the two instantiations of the persistent kernel (ngp_sweep_inst.hip is compiled twice, once per value of
-// NGP_INST_DBG, so that the production kernel and the diagnostic one build in parallel and apart from the API's own kernels):
-// _0 = k_sweep<false>, _1 = k_sweep<true> (time stamps and timing modes exist only there).
-hipError_t sweep_set_max_lds_0(int bytes);
-hipError_t sweep_set_max_lds_1(int bytes);
-hipError_t sweep_occupancy_0(int *wg_per_cu, size_t lds_bytes);
-void sweep_launch_0(unsigned grid, size_t lds_bytes, hipStream_t stream, const SweepArgs &A);
-// k_sweep_r (models with a BayesR set; fourth translation unit, -DNGP_INST_DBG=3)
-hipError_t sweep_r_set_max_lds(int bytes);
-void sweep_r_launch(unsigned grid, size_t lds_bytes, hipStream_t stream, const SweepArgs &A);
-// k_sweep_tup (models with a Tuple set; third translation unit, -DNGP_INST_DBG=2)
-hipError_t sweep_tup_set_max_lds(int bytes);
-void sweep_tup_launch(unsigned grid, size_t lds_bytes, hipStream_t stream, const SweepArgs &A);
-// k_sweep_tall (several shards per streamer workgroup; lives in the second translation unit)
-hipError_t sweep_tall_set_max_lds(int bytes);
-hipError_t sweep_tall_occupancy(int *wg_per_cu, size_t lds_bytes);
-void sweep_tall_launch(unsigned grid, size_t lds_bytes, hipStream_t stream, const SweepArgs &A);
-void sweep_launch_1(unsigned grid, size_t lds_bytes, hipStream_t stream, const SweepArgs &A);
+// The sweep kernels (ngp_sweep.h).  ngp_sweep_inst.hip is compiled once per value of NGP_INST_DBG, so that the units build in parallel
+// and apart from the API's own kernels; sweep_kernel_<NGP_INST_DBG> returns the host address of a kernel its unit defines, nullptr for
+// the others:
+//   0: lean = k_sweep<false> (models of BayesPR / BayesB / BayesC sets), multi = k_sweep_multi (K chains per pass)
+//   1: diag = k_sweep<true> (time stamps and timing modes exist only there), tall = k_sweep_tall (several shards per workgroup)
+//   2: tup = k_sweep_tup (models with a Tuple set), multi_tup = k_sweep_multi_tup
+//   3: r = k_sweep_r (models with a BayesR set), multi_r = k_sweep_multi_r
+// The single-chain kernels take a SweepArgs, the multi ones a MultiArgs.
+enum class SweepKernel { lean, diag, tup, r, tall, multi, multi_tup, multi_r };
+const void *sweep_kernel_0(SweepKernel k);
+const void *sweep_kernel_1(SweepKernel k);
+const void *sweep_kernel_2(SweepKernel k);
+const void *sweep_kernel_3(SweepKernel k);
 
 }  // namespace ngp
