@@ -177,6 +177,22 @@ int32_t ngp_set_fixed(ngp_handle *h, const double *b, const double *sum_b, int64
 int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N);
 /* E.df, E.scale (src/mme.jl:87-94). */
 int32_t ngp_set_residual_prior(ngp_handle *h, double df, double scale);
+/* Weighted residuals, the reference's E.str == "D" (src/mme.jl:71-75): w = E.iVarStr, w_i = 1 / d_ii, N entries, each finite and > 0
+ * (else NGP_ERR_ARG).  To be called BEFORE the panel (any ngp_set_panel_*, ngp_begin_panel, ngp_generate_panel, ngp_load_panel_file,
+ * ngp_share_panel; NGP_ERR_STATE afterwards); the panel's N must then equal this N (NGP_ERR_ARG at the panel call).  w = NULL with
+ * N = 0 removes the weights again (before the panel).  Compact storage (NGP_STORAGE_U8) takes no weights (NGP_ERR_ARG either way round).
+ * The chain is the reference's weighted chain run on the row-scaled problem, s_i = sqrt(w_i) (IEEE sqrt on the host):
+ *   tiles      x~_ij = (float)(s_i * ((double)x_ij - mu_j))   (one fp64 multiply after the centring, then the usual rounding to fp32;
+ *                                                              mu_j the unweighted column mean that ngp_get_storage reports; padding 0)
+ *   residual   y~_i = s_i * ycorr_i on the way in (ngp_set_y, ngp_set_state, ngp_sweep_set[_dev]);
+ *              ycorr_i = y~_i / s_i on the way out (ngp_get_state, ngp_sweep_set[_dev]); ngp_xbeta returns (X~ beta)_i / s_i
+ *   fixed sets X~ = s_i * X_ij on the device; X~'X~ and its ridge (src/mme.jl:133-152) from the scaled columns
+ *   intercept  rhs from sum_i s_i y~_i, lhs from sum_w = w_0 + w_1 + ... + w_{N-1} (fp64, left to right, summed once here)
+ * so x'Wx (ngp_get_mpm, the Gram window), x'W ycorr and sum w ycorr^2 (varE) come out of the unchanged sweep.  Weights of all ones
+ * reproduce the unweighted chain bit for bit.  A handle that shares a panel (ngp_share_panel) takes the owner's weights; snapshots hold
+ * the scaled residual and refuse a handle with other weights.  ngp_get_residual_weights copies w back (NGP_ERR_STATE: none set). */
+int32_t ngp_set_residual_weights(ngp_handle *h, const double *w, int64_t N);
+int32_t ngp_get_residual_weights(ngp_handle *h, double *w, int64_t N);
 /* Whether the model has the intercept column (src/functions.jl:41-47); default on. */
 int32_t ngp_set_intercept(ngp_handle *h, int32_t on);
 /* chainLength, burnIn, outputFreq of runSampler! (src/samplers.jl:23-26): iterations

@@ -106,7 +106,7 @@ SYMBOLS = [
     "ngp_get_timing", "ngp_profile_iteration", "ngp_draws_indexed", "ngp_eval_math", "ngp_configure", "ngp_get_config", "ngp_debug_stamps", "ngp_set_near_lags", "ngp_get_near_lags",
     "ngp_set_streamer", "ngp_get_streamer", "ngp_set_storage", "ngp_get_storage", "ngp_set_max_shards", "ngp_shards_for_chains", "ngp_run_many", "ngp_write_panel_file", "ngp_read_panel_header", "ngp_load_panel_file", "ngp_debug_set_mode", "ngp_debug_set_knob", "ngp_set_posterior_sums", "ngp_save_snapshot", "ngp_load_snapshot",
     "ngp_set_trace_loci", "ngp_get_trace_ext", "ngp_allreduce_posterior", "ngp_add_marker_set_r", "ngp_get_class_state", "ngp_set_class_state", "ngp_add_fixed_set", "ngp_get_fixed", "ngp_set_fixed", "ngp_debug_throw", "ngp_get_census", "ngp_debug_set_virtual_device", "ngp_debug_fail_census", "ngp_add_marker_set_tuple", "ngp_share_panel", "ngp_shards_for_pass", "ngp_set_sample_file",
-    "ngp_set_chain_form", "ngp_get_chain_form", "ngp_get_setup_timing",
+    "ngp_set_chain_form", "ngp_get_chain_form", "ngp_get_setup_timing", "ngp_set_residual_weights", "ngp_get_residual_weights",
 ]
 
 _lib = None
@@ -436,6 +436,26 @@ class Sampler:
 
     def set_intercept(self, on):
         self._chk(self.L.ngp_set_intercept(self.h, C.c_int32(int(on))))
+
+    def set_residual_weights(self, w):
+        """Weighted residuals (E.str == "D"): w = E.iVarStr = 1 ./ d, N entries, before the panel; None removes them."""
+        if w is None:
+            self._chk(self.L.ngp_set_residual_weights(self.h, None, C.c_int64(0)))
+            return
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        self._chk(self.L.ngp_set_residual_weights(self.h, _p(w, C.c_double), C.c_int64(len(w))))
+
+    def residual_weights(self):
+        """The weights set on this handle (or taken from the panel's owner), None when it has none."""
+        n = getattr(self, "N", None)
+        if n is None:
+            return None
+        out = np.zeros(n)
+        rc = self.L.ngp_get_residual_weights(self.h, _p(out, C.c_double), C.c_int64(n))
+        if rc == -2:
+            return None
+        self._chk(rc)
+        return out
 
     def set_schedule(self, chainLength, burnIn, thin):
         self._chk(self.L.ngp_set_schedule(self.h, C.c_int64(chainLength), C.c_int64(burnIn), C.c_int64(thin)))

@@ -7,6 +7,7 @@ Same names, argument meaning and output files as the reference, so a model scrip
     runLMEM(f, data, nChain, nBurn, nThin; VCV, ...)    runLMEM(f, data, nChain, nBurn, nThin, VCV=..., ...)   src/MCMC.jl:31-41
     BayesPR(r, v) / BayesB(pi, v; estimatePi)           BayesPR(r, v) / BayesB(pi, v, estimatePi=...)          src/runTime.jl:30-61
     Random("I", v)          (residual prior, key :e)    Random("I", v)                (key "e")                 src/runTime.jl:135-146
+    Random(dvec, v)         (weighted residuals, "D")   Random(d, v), d_ii per record (key "e")                 src/mme.jl:71-75
     SNP(M, "geno.txt"[, "map.txt"]) in the formula      the same text inside the formula string                src/runTime.jl:13-28
     summaryMCMC("betaM"; outFolder)                     summaryMCMC("betaM", outFolder=...)                    src/misc.jl:241-244
 
@@ -377,6 +378,11 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     if not snps:
         raise ValueError("the accelerated path needs at least one SNP(...) term")
     y = np.asarray(userData[lhs], dtype=np.float64)
+    # weighted residuals, E.str == "D" (src/mme.jl:71-75): w = inv.(d), set on the handle before its panel (the rows are scaled at upload)
+    w_res = _residual_weights(VCV.get("e", Random("I", 100.0)), len(y))
+    if w_res is not None and storage in ("u8", 1):
+        raise NotImplementedError('weighted residuals (Random(d, v)) with storage="u8": compact storage takes no residual weights '
+                                  '(its byte tiles are centred analytically); use the default fp32 tiles')
     # folderHandler (src/misc.jl:221-232) -- without the silent rm -r
     if os.path.isdir(outFolder) and os.listdir(outFolder):
         if not overwrite:
@@ -445,6 +451,8 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         raise ValueError('chains > 1: samples "text", "binary" or "none"')
     skw = dict(mode=engine[0], lag=engine[1]) if engine else {}
     smp = Sampler(device=device, seed=seed, chain=chain, storage=storage, **skw)
+    if w_res is not None:  # (the chains that share this panel take its weights with it)
+        smp.set_residual_weights(w_res)
     if max_shards:  # an explicit shard count (ngp_set_max_shards): e.g. the layout of a fused run, to repeat one of its chains alone
         smp.set_max_shards(int(max_shards))
     elif K > 1:  # the layout with which K chains share one fused sweep launch (fp32 tiles), or the device side by side
@@ -483,12 +491,28 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     return _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples)
 
 
+def _residual_weights(e_prior, N):
+    """Residual structure of Random(str, v) under key "e" (src/mme.jl:63-79): None for "I" (or empty), else the weights
+    w = 1 ./ d of a "D" structure given as the length-N vector d (E.iVarStr = inv.(str), the same IEEE division)."""
+    st = e_prior.str
+    if st is None or (isinstance(st, str) and st in ("I", "")):
+        return None
+    if isinstance(st, str) or np.ndim(st) != 1:
+        raise NotImplementedError(f"residual structure {st!r}: only \"I\" and a vector \"D\" (d_ii per record) exist (src/mme.jl:63-79)")
+    d = np.asarray(st, dtype=np.float64)
+    if len(d) == 0:
+        return None
+    if len(d) != N:
+        raise ValueError(f"residual structure D: {len(d)} entries for {N} records")
+    if not np.all(np.isfinite(d)) or np.any(d <= 0.0):
+        raise ValueError("residual structure D: every d_ii must be finite and > 0")
+    return 1.0 / d
+
+
 def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin):
     """Priors, fixed-effect sets, marker sets, y and the schedule of ONE chain's handle (its panel is set); returns (sets, fixed_names)."""
     # residual prior (src/mme.jl:63-94)
-    e_prior = VCV.get("e", Random("I", 100.0))
-    if not (e_prior.str in ("I", "", None) or (isinstance(e_prior.str, (list, tuple)) and len(e_prior.str) == 0)):
-        raise NotImplementedError("weighted residuals (E.str == \"D\") stay on the Julia path (src/mme.jl:71-75)")
+    e_prior = VCV.get("e", Random("I", 100.0))  # (a "D" structure's weights were set on the handle before its panel: runLMEM)
     e_df = 4.0
     e_scale = 0.0005 if e_prior.v == 0.0 else e_prior.v * (e_df - 2.0) / e_df
     smp.set_residual_prior(e_df, e_scale)

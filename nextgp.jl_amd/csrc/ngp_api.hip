@@ -348,6 +348,11 @@ struct ngp_handle {
     std::vector<int32_t> h_loc, h_vbidx;
     int64_t nvb = 0;
     double e_df = 4.0, e_scale = 0.0005;
+    // weighted residuals (ngp_set_residual_weights, E.str == "D"): w as given (empty = unweighted), their sum (index order) and the
+    // row scales s = sqrt(w) on the device (L entries, padding rows 0) -- null for an unweighted handle, which then runs the unweighted code
+    std::vector<double> h_rw;
+    double sum_w = 0.0;
+    double *d_rs = nullptr;
     int intercept = 1;
     int64_t chainLength = 0, burnIn = 0, thin = 1;
     int64_t iter = 0;
@@ -507,6 +512,15 @@ void release_panel(ngp_handle *h) {
 int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr) {
     REQUIRE(N > 0 && P > 0, NGP_ERR_ARG, "panel dimensions must be positive");
     REQUIRE(N <= (int64_t)508 * 1024, NGP_ERR_ARG, "N too large for this build (max 520192)");
+    if (owner) {  // the owner's rows were scaled by the owner's weights: a sharer takes them (and may not bring others)
+        REQUIRE(h->h_rw.empty() || h->h_rw == owner->h_rw, NGP_ERR_ARG, "ngp_share_panel: this handle's residual weights differ from the owner's");
+        h->h_rw = owner->h_rw; h->sum_w = owner->sum_w;
+    }
+    if (!h->h_rw.empty()) {
+        REQUIRE((int64_t)h->h_rw.size() == N, NGP_ERR_ARG, "residual weights hold " + std::to_string(h->h_rw.size()) + " entries, the panel " +
+                                                               std::to_string(N) + " rows");
+        REQUIRE(h->req.storage == 0, NGP_ERR_ARG, "residual weights with compact storage (NGP_STORAGE_U8) are not supported: use fp32 tiles");
+    }
     release_panel(h);  // (handles that share the old panel keep it alive)
     h->N = N; h->P = P;
     if (owner) {  // the owner's requests and plan, as they are
@@ -556,6 +570,13 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     if ((rc = dalloc(h, &h->d_sum_beta2, pp))) return rc;
     if ((rc = dalloc(h, &h->d_sum_delta, pp))) return rc;
     if ((rc = dalloc(h, &h->d_ycorr, (size_t)h->L))) return rc;
+    dfree(h->d_rs);
+    if (!h->h_rw.empty()) {  // row scales s_i = sqrt(w_i), before any tile is filled (the fills read them)
+        std::vector<double> rs((size_t)h->L, 0.0);
+        for (int64_t i = 0; i < N; i++) rs[(size_t)i] = std::sqrt(h->h_rw[(size_t)i]);
+        if ((rc = dalloc(h, &h->d_rs, (size_t)h->L))) return rc;
+        HCHK(hipMemcpy(h->d_rs, rs.data(), rs.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     if ((rc = dalloc(h, &h->d_part, (size_t)h->plan.S * NGP_BLK))) return rc;
     if ((rc = dalloc(h, &h->d_dlt, NGP_BLK))) return rc;
     if ((rc = dalloc(h, &h->d_sets, 16))) return rc;
@@ -614,6 +635,22 @@ int refresh_mpm_max(ngp_handle *h) {
     for (double v : m) if (v > mx) mx = v;
     h->mpm_max = mx;
     return NGP_OK;
+}
+
+// weighted residuals: N rows of a device vector into the row-scaled problem (dst = s src) or back out of it (dst = src / s), on the
+// handle's stream; dst may be src.  Unweighted handles never get here.
+void launch_rows(ngp_handle *h, double *dst, const double *src, bool descale) {
+    const unsigned nb = (unsigned)((h->N + 255) / 256);
+    if (descale) hipLaunchKernelGGL(k_row_descale, dim3(nb), dim3(256), 0, h->stream, dst, src, (const double *)h->d_rs, (long long)h->N);
+    else hipLaunchKernelGGL(k_row_scale, dim3(nb), dim3(256), 0, h->stream, dst, src, (const double *)h->d_rs, (long long)h->N);
+}
+
+// FNV-1a over the bytes of the weights: what a snapshot of a weighted chain records of them (ngp_save_snapshot)
+uint64_t weights_digest(const std::vector<double> &w) {
+    uint64_t x = 1469598103934665603ull;
+    const unsigned char *p = (const unsigned char *)w.data();
+    for (size_t k = 0; k < w.size() * sizeof(double); k++) { x ^= p[k]; x *= 1099511628211ull; }
+    return x;
 }
 
 int build_gram8(ngp_handle *h) {  // compact storage: exact integer dot products, then G = dot - N (m_k m_j)
@@ -712,7 +749,8 @@ int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64
         }
         if (h->req.storage == 0)
         hipLaunchKernelGGL(k_cols_fill<TIn>, dim3((unsigned)((h->L / 4 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, h->d_tiles, (const TIn *)d_g,
-                           (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->plan.R, (int)h->plan.S, (const double *)d_mu);
+                           (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->plan.R, (int)h->plan.S, (const double *)d_mu,
+                           (const double *)h->d_rs);
         e = hipStreamSynchronize(h->stream);  // the staging buffer is reused by the next chunk
     }
     unsigned bad = 0;
@@ -970,7 +1008,8 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
     hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->L, (long long)h->N, h->d_scal, h->e_df,
-                       h->e_scale, h->intercept, 1, h->seed, (uint64_t)h->chain, it, h->d_tr_varE, h->d_tr_b, (long long)trace_idx, h->d_abort, h->mpm_max);
+                       h->e_scale, h->intercept, 1, h->seed, (uint64_t)h->chain, it, h->d_tr_varE, h->d_tr_b, (long long)trace_idx, h->d_abort, h->mpm_max,
+                       (const double *)h->d_rs, h->sum_w);
     for (size_t f = 0; f < h->fix.size(); f++)  // the other fixed-effect sets, in the order they were added (src/samplers.jl:39-41)
         hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->N, h->fix[f].d_X, (int)h->fix[f].ncol, h->fix[f].d_xpx0,
                            h->fix[f].d_xpxR, h->fix[f].d_lhs0, h->fix[f].d_rhs0, h->d_bfix + h->fix[f].off, h->d_scal, (int)f, h->seed,
@@ -1220,7 +1259,7 @@ int32_t ngp_destroy(ngp_handle *h) {
     dfree(h->d_c); dfree(h->d_w); dfree(h->d_q); dfree(h->d_T); dfree(h->d_chi); dfree(h->d_setof); dfree(h->d_loc);
     dfree(h->d_tinv); dfree(h->d_blin);
     dfree(h->d_vbidx); dfree(h->d_delta); dfree(h->d_sum_beta); dfree(h->d_sum_beta2); dfree(h->d_sum_delta);
-    dfree(h->d_ycorr); dfree(h->d_part); dfree(h->d_dlt); dfree(h->d_sets); dfree(h->d_scal); dfree(h->d_varBeta);
+    dfree(h->d_ycorr); dfree(h->d_rs); dfree(h->d_part); dfree(h->d_dlt); dfree(h->d_sets); dfree(h->d_scal); dfree(h->d_varBeta);
     dfree(h->d_sum_varBeta); dfree(h->d_regs); dfree(h->d_seg_k0); dfree(h->d_seg_len); dfree(h->d_segpart); dfree(h->d_regchi);
     for (auto &fx : h->fix) { dfree(fx.d_X); dfree(fx.d_xpx0); dfree(fx.d_xpxR); dfree(fx.d_lhs0); dfree(fx.d_rhs0); }
     dfree(h->d_bfix); dfree(h->d_sum_bfix);
@@ -1288,7 +1327,7 @@ static void ingest_u8_chunk(ngp_handle *h, const uint8_t *d_g, int64_t N, int64_
         hipLaunchKernelGGL(k_u8_colmean, dim3((unsigned)ncols), dim3(256), 0, h->stream, d_g, (long long)N, (long long)ld, (int)centre, d_mu);
         (void)hipMemcpyAsync(h->d_mean + c0, d_mu, (size_t)ncols * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
         hipLaunchKernelGGL(k_u8_fill, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_g, (long long)N,
-                           (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0, d_mu);
+                           (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0, d_mu, (const double *)h->d_rs);
     }
 }
 
@@ -1332,6 +1371,7 @@ int32_t ngp_set_panel_u8(ngp_handle *h, const uint8_t *G, int64_t N, int64_t P, 
 namespace {
 struct PanelHeader { char magic[8]; int64_t N, P; int32_t bits, zero; };
 }
+#define NGP_SNAP_WEIGHTED ((int64_t)1 << 62)  // snapshot: the fixed-set count's flag of a weighted chain (ngp_save_snapshot)
 
 int32_t ngp_write_panel_file(const char *path, const uint8_t *G, int64_t N, int64_t P, int64_t ld, int32_t bits) {
     NGP_TRY
@@ -1457,7 +1497,7 @@ int32_t ngp_generate_panel(ngp_handle *h, int64_t N, int64_t P, double maf_lo, d
                            (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_thr);
     } else
     hipLaunchKernelGGL(k_gen_fill, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, h->d_tiles, (long long)N,
-                       (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_mu, d_thr);
+                       (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_mu, d_thr, (const double *)h->d_rs);
     hipError_t e = hipStreamSynchronize(h->stream);
     dfree(d_mu); dfree(d_thr);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("generate_panel: ") + hipGetErrorString(e));
@@ -1543,6 +1583,7 @@ int32_t ngp_xbeta(ngp_handle *h, const double *beta, int64_t P, double *out, int
     else
     hipLaunchKernelGGL(k_xbeta, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, h->d_tiles, d_b, d_o, (int)h->plan.R, (int)h->plan.S,
                        (long long)h->NBLK);
+    if (h->d_rs) launch_rows(h, d_o, d_o, true);  // the tiles hold s x: X beta = (X~ beta) / s
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     dfree(d_b); dfree(d_o);
@@ -1653,6 +1694,7 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     for (int64_t i = 0; i < N; i++) REQUIRE(std::isfinite(y[i]), NGP_ERR_ARG, "non-finite phenotype");
     HCHK(hipMemsetAsync(h->d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
     HCHK(hipMemcpyAsync(h->d_ycorr, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // src/mme.jl:57
+    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: y~ = s y
     HCHK(hipMemsetAsync(h->d_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));                  // src/mme.jl:443
     HCHK(hipMemsetAsync(h->d_delta, 1, (size_t)h->Ppad, h->stream));                                  // src/mme.jl:444
     HCHK(hipMemsetAsync(h->d_scal, 0, sizeof(DScal), h->stream));
@@ -1688,6 +1730,37 @@ int32_t ngp_set_residual_prior(ngp_handle *h, double df, double scale) {
     if ((rc = enter(h))) return rc;
     REQUIRE(std::isfinite(df) && std::isfinite(scale) && df > 0 && scale >= 0, NGP_ERR_ARG, "bad residual prior");
     h->e_df = df; h->e_scale = scale;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+// weighted residuals (E.str == "D", src/mme.jl:71-75): kept on the host until the panel is set, which scales its rows by sqrt(w)
+int32_t ngp_set_residual_weights(ngp_handle *h, const double *w, int64_t N) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->d_tiles == nullptr && h->pm == nullptr, NGP_ERR_STATE,
+            "residual weights must be set before the panel (they scale its rows) and before ngp_set_y");
+    if (w == nullptr && N == 0) { h->h_rw.clear(); h->sum_w = 0.0; return NGP_OK; }
+    REQUIRE(w != nullptr && N > 0, NGP_ERR_ARG, "residual weights: N > 0 entries (or NULL and 0 to remove them)");
+    REQUIRE(h->req.storage == NGP_STORAGE_F32, NGP_ERR_ARG,
+            "residual weights with compact storage (NGP_STORAGE_U8) are not supported: the byte tiles centre analytically and cannot carry row scales");
+    double sw = 0.0;
+    for (int64_t i = 0; i < N; i++) {
+        REQUIRE(std::isfinite(w[i]) && w[i] > 0.0, NGP_ERR_ARG, "residual weights must be finite and > 0 (w_i = 1 / d_ii)");
+        sw = sw + w[i];  // sum_w: index order, left to right (the intercept's lhs, k_head)
+    }
+    h->h_rw.assign(w, w + N);
+    h->sum_w = sw;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+int32_t ngp_get_residual_weights(ngp_handle *h, double *w, int64_t N) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(!h->h_rw.empty(), NGP_ERR_STATE, "no residual weights set on this handle");
+    REQUIRE(w != nullptr && N == (int64_t)h->h_rw.size(), NGP_ERR_ARG, "residual weights buffer must hold N entries");
+    std::copy(h->h_rw.begin(), h->h_rw.end(), w);
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -1877,7 +1950,15 @@ int32_t ngp_get_state(ngp_handle *h, double *ycorr, double *beta, int64_t *delta
     if ((rc = enter(h))) return rc;
     REQUIRE(h->d_tiles != nullptr && h->have_y, NGP_ERR_STATE, "panel / y not set");
     HCHK(hipStreamSynchronize(h->stream));
-    if (ycorr) HCHK(hipMemcpy(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
+    if (ycorr && h->d_rs) {  // weighted residuals: ycorr = y~ / s
+        double *d_t = nullptr;
+        if ((rc = dalloc(h, &d_t, (size_t)h->N))) return rc;
+        launch_rows(h, d_t, h->d_ycorr, true);
+        hipError_t e = hipMemcpyAsync(ycorr, d_t, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        dfree(d_t);
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("get_state: ") + hipGetErrorString(e));
+    } else if (ycorr) HCHK(hipMemcpy(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
     if (beta) HCHK(hipMemcpy(beta, h->d_beta, (size_t)h->P * sizeof(double), hipMemcpyDeviceToHost));
     if (delta) {
         std::vector<uint8_t> d((size_t)h->P);
@@ -1909,6 +1990,7 @@ int32_t ngp_set_state(ngp_handle *h, const double *ycorr, const double *beta, co
     REQUIRE(std::isfinite(varE) && (varE > 0.0 || (varE == 0.0 && iter == 0)) && std::isfinite(b) && iter >= 0, NGP_ERR_ARG,
             "bad scalar state (varE must be finite and positive)");
     if (ycorr) HCHK(hipMemcpy(h->d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice));
+    if (ycorr && h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: y~ = s ycorr
     if (beta) HCHK(hipMemcpy(h->d_beta, beta, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
     if (delta) {
         std::vector<uint8_t> d((size_t)h->P);
@@ -2031,6 +2113,7 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
     for (int attempt = 0;; ++attempt) {
         HCHK(hipMemsetAsync(h->d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
         HCHK(hipMemcpyAsync(h->d_ycorr, ycorr, (size_t)h->N * sizeof(double), in, h->stream));
+        if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
         HCHK(hipMemcpyAsync(h->d_beta + hs.col0, beta, (size_t)hs.ncol * sizeof(double), in, h->stream));
         HCHK(hipMemcpyAsync(h->d_varBeta + hs.vb_off, varBeta, (size_t)nvbs * sizeof(double), in, h->stream));
         if (has_pi) {
@@ -2040,7 +2123,8 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
         hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->d_scal, varE);
         // (no draws, no intercept: ycorr'ycorr of the caller's residual sets the scale of the fixed-point accumulators)
         hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->L, (long long)h->N, h->d_scal, h->e_df,
-                           h->e_scale, 0, 0, h->seed, (uint64_t)h->chain, it, (double *)nullptr, (double *)nullptr, (long long)0, h->d_abort, h->mpm_max);
+                           h->e_scale, 0, 0, h->seed, (uint64_t)h->chain, it, (double *)nullptr, (double *)nullptr, (long long)0, h->d_abort, h->mpm_max,
+                           (const double *)h->d_rs, h->sum_w);
         hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->d_setof, h->d_loc,
                            h->d_vbidx, h->d_sets, h->d_scal, h->d_varBeta, h->d_mpm, h->d_lhs0, h->d_rhs0, h->d_beta, h->d_c, h->d_w,
                            h->d_q, h->d_T, h->d_chi, (int)set_id, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->d_regs, h->d_regchi, h->d_rcls,
@@ -2060,6 +2144,7 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
         if (rc) return rc;
         break;
     }
+    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, true);  // ... and back: the caller's ycorr is unscaled (d_ycorr is scratch here)
     HCHK(hipMemcpyAsync(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), out, h->stream));
     HCHK(hipMemcpyAsync(beta, h->d_beta + hs.col0, (size_t)hs.ncol * sizeof(double), out, h->stream));
     HCHK(hipMemcpyAsync(varBeta, h->d_varBeta + hs.vb_off, (size_t)nvbs * sizeof(double), out, h->stream));
@@ -2363,6 +2448,8 @@ int32_t ngp_set_storage(ngp_handle *h, int32_t storage) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_storage must precede the panel upload");
     REQUIRE(storage == NGP_STORAGE_F32 || storage == NGP_STORAGE_U8, NGP_ERR_ARG, "storage: 0 (fp32 tiles) or 1 (compact: bytes + column means)");
+    REQUIRE(storage == NGP_STORAGE_F32 || h->h_rw.empty(), NGP_ERR_ARG,
+            "residual weights with compact storage (NGP_STORAGE_U8) are not supported: the byte tiles centre analytically and cannot carry row scales");
     h->req.storage = storage;
     return NGP_OK;
     NGP_CATCH(h)
@@ -2442,6 +2529,7 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     int64_t iter = 0, nk = 0;
     if ((rc = ngp_get_state(h, yc.data(), be.data(), de.data(), vb.data(), pi.data(), &varE, &b, &iter))) return rc;
     if ((rc = ngp_get_posterior_sums(h, sb.data(), sb2.data(), sd.data(), sv.data(), sp.data(), &svE, &sbb, &nk))) return rc;
+    if (h->d_rs) HCHK(hipMemcpy(yc.data(), h->d_ycorr, N * sizeof(double), hipMemcpyDeviceToHost));  // weighted: the scaled y~ as it is (bit-exact resume)
     std::vector<uint8_t> d8(P);
     for (size_t k = 0; k < P; k++) d8[k] = (uint8_t)(de[k] != 0);
     const std::string tmp = std::string(path) + ".tmp";
@@ -2455,8 +2543,10 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     W("NGPSNAP2", 8); W(hdr, sizeof(hdr)); W(ids, sizeof(ids));
     {   // model signature: a snapshot only loads into the model it was taken from (equal counts are not enough)
         for (auto &hs : h->sets) { const int64_t sg[5] = {hs.method, hs.K + 16 * hs.tk, hs.nreg, hs.col0, hs.ncol}; W(sg, sizeof(sg)); }
-        const int64_t nfs = (int64_t)h->fix.size();
+        // (weighted residuals: bit 62 of the fixed-set count says so, and a digest of the weights follows it -- unweighted bytes unchanged)
+        const int64_t nfs = (int64_t)h->fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED);
         W(&nfs, 8);
+        if (!h->h_rw.empty()) { const uint64_t dg = weights_digest(h->h_rw); W(&dg, 8); }
         for (auto &fx : h->fix) W(&fx.ncol, 8);
     }
     W(scal, sizeof(scal));
@@ -2508,6 +2598,18 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         }
         int64_t nfs = -1;
         Rd(&nfs, 8);
+        const bool snap_w = ok && nfs >= 0 && (nfs & NGP_SNAP_WEIGHTED) != 0;
+        uint64_t dg = 0;
+        if (snap_w) { nfs &= ~NGP_SNAP_WEIGHTED; Rd(&dg, 8); }
+        if (ok && snap_w != !h->h_rw.empty()) {
+            fclose(f);
+            return fail(h, NGP_ERR_ARG, snap_w ? "snapshot of a chain with residual weights: this handle has none (ngp_set_residual_weights)"
+                                               : "snapshot of a chain without residual weights: this handle has them");
+        }
+        if (ok && snap_w && dg != weights_digest(h->h_rw)) {
+            fclose(f);
+            return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its residual weights differ)");
+        }
         same = same && ok && nfs == (int64_t)h->fix.size();
         if (same)
             for (auto &fx : h->fix) { int64_t nc = -1; Rd(&nc, 8); same = same && nc == fx.ncol; }
@@ -2541,6 +2643,7 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
     for (size_t k = 0; k < P; k++) de[k] = d8[k];
     h->poisoned = true;  // until the whole restore has gone through: a failure half-way must not leave a mixed state behind as valid
     if ((rc = ngp_set_state(h, yc.data(), be.data(), de.data(), vb.data(), pi.data(), scal[0], scal[1], hdr[4]))) { h->poisoned = true; return rc; }
+    if (h->d_rs) HCHK(hipMemcpy(h->d_ycorr, yc.data(), N * sizeof(double), hipMemcpyHostToDevice));  // weighted: y~ as saved, not s (y~ / s)
     h->poisoned = true;  // (ngp_set_state has just declared the state valid: not before the sums, fixed effects and classes are in)
     if ((rc = ngp_set_posterior_sums(h, sb.data(), sb2.data(), sd.data(), sv.data(), sp.data(), scal[2], scal[3], hdr[5]))) return rc;
     for (size_t si = 0; si < ns; si++) h->sets[si].fine_calls = fc[si];
@@ -2971,6 +3074,16 @@ int32_t ngp_add_fixed_set(ngp_handle *h, const double *X, int64_t N, int64_t nco
             REQUIRE(std::isfinite(v), NGP_ERR_ARG, "non-finite value in a fixed-effect column");
             xc[(size_t)a * N + i] = v;
         }
+    if (h->d_rs) {  // weighted residuals: the columns of the row-scaled problem, X~ = s X (on the device); X~'X~ below is X'WX
+        double *d_x = nullptr;
+        if ((rc = dalloc(h, &d_x, xc.size()))) return rc;
+        hipError_t e = hipMemcpyAsync(d_x, xc.data(), xc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+        for (int64_t a = 0; a < ncol && e == hipSuccess; a++) launch_rows(h, d_x + (size_t)a * N, d_x + (size_t)a * N, false);
+        if (e == hipSuccess) e = hipMemcpyAsync(xc.data(), d_x, xc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        dfree(d_x);
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("add_fixed_set: ") + hipGetErrorString(e));
+    }
     for (int64_t a = 0; a < ncol; a++)
         for (int64_t b = 0; b <= a; b++) {
             double acc = 0.0;

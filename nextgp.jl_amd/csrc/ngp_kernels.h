@@ -24,16 +24,27 @@ __global__ __launch_bounds__(1024) void k_head(double *__restrict__ ycorr, long 
                                                double e_df, double e_scale, int intercept, int draw_varE, uint64_t seed,
                                                uint64_t chain, uint64_t it, double *__restrict__ tr_varE,
                                                double *__restrict__ tr_b, long long trace_idx, const unsigned *__restrict__ abort_w,
-                                               double mpm_max) {
+                                               double mpm_max, const double *__restrict__ rs, double sum_w) {
+    // rs != null: weighted residuals (ngp_set_residual_weights) -- ycorr holds y~ = s ycorr, rs the row scales s (L entries, padding 0),
+    // sum_w = sum of the weights.  The intercept's column is then s: rhs from s'y~ (+ sum_w b), lhs from sum_w, y~ -= s db; the same
+    // reduction tree and draw keys, so weights of one give the unweighted chain bit for bit.  yy = y~'y~ = sum w ycorr^2 either way.
     if (abort_w && *abort_w != 0u) return;  // an earlier sweep of this call gave up (ngp_sweep_args.h, abort_w)
     __shared__ double wyy[16], wsy[16];
     __shared__ double s_db;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     double ayy = 0.0, asy = 0.0;
-    for (long long i = tid; i < L; i += 1024) {
-        double v = ycorr[i];
-        ayy = __builtin_fma(v, v, ayy);
-        asy = asy + v;
+    if (rs) {
+        for (long long i = tid; i < L; i += 1024) {
+            double v = ycorr[i];
+            ayy = __builtin_fma(v, v, ayy);
+            asy = asy + rs[i] * v;
+        }
+    } else {
+        for (long long i = tid; i < L; i += 1024) {
+            double v = ycorr[i];
+            ayy = __builtin_fma(v, v, ayy);
+            asy = asy + v;
+        }
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
@@ -69,7 +80,7 @@ __global__ __launch_bounds__(1024) void k_head(double *__restrict__ ycorr, long 
         }
         double db = 0.0;
         if (intercept) {
-            double Nd = (double)N;
+            double Nd = rs ? sum_w : (double)N;
             double bo = sc->b;
             double tb = Nd * bo;
             double sb = sy + tb;
@@ -94,8 +105,24 @@ __global__ __launch_bounds__(1024) void k_head(double *__restrict__ ycorr, long 
     __syncthreads();
     if (intercept) {
         double db = s_db;
-        for (long long i = tid; i < N; i += 1024) ycorr[i] = ycorr[i] - db;
+        if (rs)
+            for (long long i = tid; i < N; i += 1024) ycorr[i] = ycorr[i] - rs[i] * db;
+        else
+            for (long long i = tid; i < N; i += 1024) ycorr[i] = ycorr[i] - db;
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// weighted residuals at the ABI (ngp_set_residual_weights): n rows scaled by s (y~ = s ycorr, one multiply) or brought back
+// (ycorr = y~ / s, one IEEE division); dst may be src
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_row_scale(double *dst, const double *src, const double *__restrict__ rs, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = rs[i] * src[i];
+}
+__global__ __launch_bounds__(256) void k_row_descale(double *dst, const double *src, const double *__restrict__ rs, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[i] / rs[i];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1201,7 +1228,7 @@ __global__ __launch_bounds__(256) void k_gen_colmean(long long N, long long P, d
     }
 }
 __global__ __launch_bounds__(256) void k_gen_fill(float *__restrict__ tiles, long long N, long long P, int R, int S, uint64_t pseed,
-                                                  const double *__restrict__ mu, const uint32_t *__restrict__ thr) {
+                                                  const double *__restrict__ mu, const uint32_t *__restrict__ thr, const double *__restrict__ rs) {
     const int s = blockIdx.x;
     const long long t = blockIdx.y;
     float *tp = tiles + ((size_t)t * S + s) * ((size_t)R * NGP_BLK);
@@ -1211,7 +1238,7 @@ __global__ __launch_bounds__(256) void k_gen_fill(float *__restrict__ tiles, lon
         float v = 0.0f;
         if (i < N && j < P) {
             int g = panel_gij(panel_colkey(pseed, j), i, thr[j]);
-            v = (float)((double)g - mu[j]);
+            v = rs ? (float)(rs[i] * ((double)g - mu[j])) : (float)((double)g - mu[j]);  // rs: row scales of weighted residuals
         }
         tp[idx] = v;
     }
@@ -1235,7 +1262,7 @@ __global__ __launch_bounds__(64) void k_cols_mean(const TIn *__restrict__ g, lon
 // thread = (column c of the chunk, quad Q of the padded panel): rows 4 Q .. 4 Q + 3 live in one shard (R is a multiple of 4)
 template <typename TIn>
 __global__ __launch_bounds__(256) void k_cols_fill(float *__restrict__ tiles, const TIn *__restrict__ g, long long N, long long ld,
-                                                   long long col0, int R, int S, const double *__restrict__ mu) {
+                                                   long long col0, int R, int S, const double *__restrict__ mu, const double *__restrict__ rs) {
     const long long Q = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long i0 = 4 * Q;
     if (i0 >= (long long)R * S) return;
@@ -1245,7 +1272,8 @@ __global__ __launch_bounds__(256) void k_cols_fill(float *__restrict__ tiles, co
     const double m = mu[c];
     float v[4];
 #pragma unroll
-    for (int r = 0; r < 4; r++) v[r] = (i0 + r < N) ? (float)((double)col[i0 + r] - m) : 0.0f;
+    for (int r = 0; r < 4; r++)  // rs: row scales of weighted residuals, (float)(s_i * (x_ij - mu_j))
+        v[r] = (i0 + r < N) ? (rs ? (float)(rs[i0 + r] * ((double)col[i0 + r] - m)) : (float)((double)col[i0 + r] - m)) : 0.0f;
     float *tp = tiles + ((size_t)(j >> 6) * S + s) * ((size_t)R * NGP_BLK) + tile_off(ii, jj);
     *(float4 *)tp = make_float4(v[0], v[1], v[2], v[3]);
 }
@@ -1291,7 +1319,8 @@ __global__ __launch_bounds__(256) void k_u8_colmean(const uint8_t *__restrict__ 
     if (threadIdx.x == 0) mu[jc] = centre ? (double)(wsum[0] + wsum[1] + wsum[2] + wsum[3]) / (double)N : 0.0;
 }
 __global__ __launch_bounds__(256) void k_u8_fill(float *__restrict__ tiles, const uint8_t *__restrict__ G, long long N, long long ld,
-                                                 long long ncols, int R, int S, long long t0, const double *__restrict__ mu) {
+                                                 long long ncols, int R, int S, long long t0, const double *__restrict__ mu,
+                                                 const double *__restrict__ rs) {
     const int s = blockIdx.x;
     const long long tb = blockIdx.y;  // block of the chunk
     float *tp = tiles + ((size_t)(t0 + tb) * S + s) * ((size_t)R * NGP_BLK);
@@ -1299,7 +1328,8 @@ __global__ __launch_bounds__(256) void k_u8_fill(float *__restrict__ tiles, cons
         const int ii = ((idx >> 8) << 2) + (idx & 3), jj = (idx >> 2) & (NGP_BLK - 1);  // idx is the quad-major offset
         const long long i = (long long)s * R + ii, jc = tb * NGP_BLK + jj;
         float v = 0.0f;
-        if (i < N && jc < ncols) v = (float)((double)G[(size_t)jc * ld + i] - mu[jc]);
+        if (i < N && jc < ncols)  // rs: row scales of weighted residuals
+            v = rs ? (float)(rs[i] * ((double)G[(size_t)jc * ld + i] - mu[jc])) : (float)((double)G[(size_t)jc * ld + i] - mu[jc]);
         tp[idx] = v;
     }
 }

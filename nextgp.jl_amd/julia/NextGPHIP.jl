@@ -208,6 +208,16 @@ end
 
 set_y!(h::Handle, y::Vector{Float64}) = check(h, ccall((:ngp_set_y, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, y, length(y)))
 set_residual_prior!(h::Handle, df, scale) = check(h, ccall((:ngp_set_residual_prior, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), h.ptr, df, scale))
+# weighted residuals, E.str == "D" (src/mme.jl:71-75): w = E.iVarStr (w_i = 1 / d_ii), BEFORE the panel -- its rows are scaled at upload
+set_residual_weights!(h::Handle, w::Vector{Float64}) =
+    check(h, ccall((:ngp_set_residual_weights, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, w, length(w)))
+function residual_weights(h::Handle, N::Integer)      # the weights in force (nothing: none set)
+    w = zeros(Float64, N)
+    rc = ccall((:ngp_get_residual_weights, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, w, N)
+    rc == -2 && return nothing
+    check(h, rc)
+    return w
+end
 set_schedule!(h::Handle, n, burn, thin) = check(h, ccall((:ngp_set_schedule, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Int64), h.ptr, n, burn, thin))
 run!(h::Handle, niter) = check(h, ccall((:ngp_run, LIB), Int32, (Ptr{Cvoid}, Int64), h.ptr, niter))
 
@@ -263,8 +273,9 @@ factors, blocked groups) and Symbol marker sets with BayesPR / BayesB / BayesC /
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
                      seed::Integer=1, device::Integer=0)
     isempty(Z) || error("random effects present: use the fine seam (NextGPHIP.sweep!) instead")
-    E.str == "I" || error("weighted residuals: use the reference sampler")
+    (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
     h = Handle(device=device, seed=seed)
+    E.str == "D" && set_residual_weights!(h, Vector{Float64}(E.iVarStr))   # before the panel (src/mme.jl:71-75)
     sets = collect(keys(M))                       # Dict order, as src/samplers.jl:50
     # consecutive column ranges of ONE panel on the device, handed over set by set (no hcat of the M[s].data on the host)
     begin_panel!(h, size(M[sets[1]].data, 1), sum(M[s].dims[2] for s in sets))
