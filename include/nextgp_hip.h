@@ -172,7 +172,27 @@ int32_t ngp_add_fixed_set(ngp_handle *h, const double *X, int64_t N, int64_t nco
 int32_t ngp_get_fixed(ngp_handle *h, double *b, double *sum_b, int64_t *ncols_total);
 int32_t ngp_set_fixed(ngp_handle *h, const double *b, const double *sum_b, int64_t ncols_total);
 
-/* Phenotypes; resets the chain: ycorr = y (src/mme.jl:57), b = 0, beta = 0, delta = 1, iter = 0, every variance and pi back to
+/* A (1|g) random-effect set (src/mme.jl:165-272, sampled by sampleZ! / sampleVarU, src/functions.jl:57-72, 92-97, 498-501): record i
+ * belongs to level level[i] in 0..q-1 (Z one-hot, N x q); K = the structure's precision (Z.iVarStr: I, A^-1 or inv(Sigma)) as CSR
+ * (k_ptr q + 1 entries, k_col / k_val k_ptr[q] entries, any column order within a row), all three NULL = identity.  Refused
+ * (NGP_ERR_ARG, the handle unchanged): a level outside 0..q-1, a non-finite entry, a K that is not exactly symmetric, a diagonal entry
+ * missing or <= 0, df <= 0, scale < 0, varU0 <= 0.  Levels without records are valid (zpz = 0: drawn from the prior conditional).
+ * df = 3 + 1 and scale = v (df - 2) / df are the caller's (src/mme.jl:265-272), varU0 = v.  Sets are sampled after the fixed-effect
+ * sets, in the order they are added; each iteration: Yi = Z'ycorr / varE + zpz u / varE without touching ycorr, Gauss-Seidel over K in
+ * level order (Z'Z taken as diagonal, as the reference does), ycorr -= Z du, varU = (scale df + u'Ku) / chi2(df + q).  Under weighted
+ * residuals zpz_l = sum of w over the level's records and Z'W ycorr is used.  Summation orders and draw keys: DESIGN.md, "Random-effect
+ * sets".  A handle that shares a panel has its own random-effect sets.  With them, the packed posterior (ngp_posterior_len), the records
+ * of ngp_set_sample_file and snapshots carry u and varU (see there); handles without them keep every layout unchanged. */
+int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
+                           double df, double scale, double varU0, int32_t *set_id);
+/* Current u (q), their posterior sums (q), varU and its sum; any pointer may be NULL.  ngp_set_random restores them (resume). */
+int32_t ngp_get_random(ngp_handle *h, int32_t set_id, double *u, double *sum_u, double *varU, double *sum_varU);
+int32_t ngp_set_random(ngp_handle *h, int32_t set_id, const double *u, const double *sum_u, double varU, double sum_varU);
+/* Fine seam of one random-effect set: sampleZ!(zSet, Z, u, ycorr, varE, varU) (src/functions.jl:92-97) on the caller's arrays, updated
+ * in place (ycorr N, u q, varU one double).  Keyed like ngp_sweep_set: the set's own call counter is the iteration of its draws. */
+int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *u, double *varU);
+
+/* Phenotypes; resets the chain: ycorr = y (src/mme.jl:57), b = 0, beta = 0, delta = 1, u = 0, varU = varU0, iter = 0, every variance and pi back to
  * the values given to ngp_add_marker_set (src/mme.jl:351-360, 516), all posterior sums and nKept zero. */
 int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N);
 /* E.df, E.scale (src/mme.jl:87-94). */
@@ -217,8 +237,9 @@ int32_t ngp_get_posterior_sums(ngp_handle *h, double *sum_beta, double *sum_beta
                                double *sum_pi, double *sum_varE, double *sum_b, int64_t *nKept);
 /* Same sums packed into a DEVICE buffer [sum_beta P | sum_beta2 P | sum_delta P | sum_varBeta nvb |
  * sum_pi 2*nsets | class-probability sums of the BayesR sets, K each | sums of the fixed effects beyond the intercept, all
- * columns of all sets in order (ngp_get_fixed) | sum_varE | sum_b | nKept] so the host can all-reduce them over RCCL without a
- * PCIe round trip.  len = 3P + nvb + 2 nsets + sum K + nfixcol + 3 doubles. */
+ * columns of all sets in order (ngp_get_fixed) | with random-effect sets: sums of u, set after set, then the sums of varU, one per set |
+ * sum_varE | sum_b | nKept] so the host can all-reduce them over RCCL without a PCIe round trip.  len = 3P + nvb + 2 nsets + sum K +
+ * nfixcol (+ sum q + nrand) + 3 doubles. */
 int32_t ngp_posterior_len(ngp_handle *h, int64_t *len);
 int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len);
 
@@ -344,7 +365,8 @@ int32_t ngp_run_many(ngp_handle **hs, int32_t n, int64_t niter);
  * stream, written by a thread of the library); ngp_run returns when its last record is in the file.  NULL closes the file.  Layout:
  * "NGPSMP01" | int64 P, nvb, nsets, nfix, nclass, record bytes | per set int64 {method, K, col0, ncol, variance entries, tuple k} |
  * records: int64 iteration | varE | b | b_fixed[nfix] | beta[P] | varBeta[nvb] | piHat[2 nsets] | class probabilities[nclass] |
- * delta[P] (bytes, padded to 8). */
+ * delta[P] (bytes, padded to 8).  A chain with random-effect sets writes "NGPSMP02": the header goes on with int64 nrand | q per set, and
+ * every record holds u (set after set) and varU[nrand] between b_fixed and beta. */
 int32_t ngp_set_sample_file(ngp_handle *h, const char *path);
 /* Placement census of the last persistent-sweep launch: out[b] = (XCC id + 1) << 32 | HW_REG_HW_ID of workgroup b (0: never resident),
  * n >= *grid entries.  Every launch of the persistent kernel opens with a census of its own grid (all of its workgroups wait for

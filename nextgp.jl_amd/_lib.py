@@ -15,22 +15,43 @@ LIB_PATH = os.environ.get("NGP_HIP_LIB") or os.path.join(_HERE, "libnextgp_hip.s
 METHOD_BAYESPR, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESR, METHOD_TUPLE = 0, 1, 2, 3, 4
 
 
+def _sample_header(f, path):
+    """(P, nvb, nsets, nfix, nclass, record bytes, sets, random-effect q per set) of an open sample file, positioned at its first record."""
+    magic = f.read(8)
+    if magic not in (b"NGPSMP01", b"NGPSMP02"):
+        raise NextGPHipError(f"not a sample file: {path}")
+    P, nvb, nsets, nfix, ncls, rec = (int(v) for v in np.frombuffer(f.read(48), dtype=np.int64))
+    sets = [dict(zip(("method", "K", "col0", "ncol", "nvb", "tk"), np.frombuffer(f.read(48), dtype=np.int64).tolist())) for _ in range(nsets)]
+    rq = []
+    if magic == b"NGPSMP02":  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
+        nr = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
+        rq = np.frombuffer(f.read(8 * nr), dtype=np.int64).tolist()
+    return P, nvb, nsets, nfix, ncls, rec, sets, rq
+
+
+def _split_random(d, o, rq):
+    """u of every random-effect set (list) and varU (array) from record doubles d (last axis) at offset o; returns (u, varU, new offset)."""
+    u = []
+    for q in rq:
+        u.append(d[..., o:o + q]); o += q
+    vu = d[..., o:o + len(rq)]; o += len(rq)
+    return u, vu, o
+
+
 def read_sample_file(path):
     """Binary sample file of ngp_set_sample_file -> dict(iter[n], varE[n], b[n], b_fixed[n, nfix], beta[n, P], varBeta[n, nvb], piHat[n, 2 nsets],
-    class_pi[n, nclass], delta[n, P] (uint8), sets=[dict(method, K, col0, ncol, nvb, tk)])."""
+    class_pi[n, nclass], delta[n, P] (uint8), sets=[dict(method, K, col0, ncol, nvb, tk)], u=[[n, q] per random-effect set], varU[n, nrand])."""
     with open(path, "rb") as f:
-        if f.read(8) != b"NGPSMP01":
-            raise NextGPHipError(f"not a sample file: {path}")
-        P, nvb, nsets, nfix, ncls, rec = np.frombuffer(f.read(48), dtype=np.int64)
-        sets = [dict(zip(("method", "K", "col0", "ncol", "nvb", "tk"), np.frombuffer(f.read(48), dtype=np.int64).tolist())) for _ in range(nsets)]
+        P, nvb, nsets, nfix, ncls, rec, sets, rq = _sample_header(f, path)
         raw = np.frombuffer(f.read(), dtype=np.uint8)
     n = len(raw) // rec
     raw = raw[:n * rec].reshape(n, rec)
-    nd = 3 + nfix + P + nvb + 2 * nsets + ncls
+    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls
     d = raw[:, :nd * 8].copy().view(np.float64)
     o = 3
     out = dict(iter=raw[:, :8].copy().view(np.int64)[:, 0], varE=d[:, 1], b=d[:, 2], sets=sets)
     out["b_fixed"] = d[:, o:o + nfix]; o += nfix
+    out["u"], out["varU"], o = _split_random(d, o, rq)
     out["beta"] = d[:, o:o + P]; o += P
     out["varBeta"] = d[:, o:o + nvb]; o += nvb
     out["piHat"] = d[:, o:o + 2 * nsets]; o += 2 * nsets
@@ -44,22 +65,20 @@ def iter_sample_file(path):
     5 GB): yields dicts with the fields of read_sample_file for a single kept iteration.  Memory-mapped, nothing is copied but
     the record being looked at."""
     with open(path, "rb") as f:
-        if f.read(8) != b"NGPSMP01":
-            raise NextGPHipError(f"not a sample file: {path}")
-        P, nvb, nsets, nfix, ncls, rec = (int(v) for v in np.frombuffer(f.read(48), dtype=np.int64))
-        sets = [dict(zip(("method", "K", "col0", "ncol", "nvb", "tk"), np.frombuffer(f.read(48), dtype=np.int64).tolist())) for _ in range(nsets)]
+        P, nvb, nsets, nfix, ncls, rec, sets, rq = _sample_header(f, path)
         off = f.tell()
         size = os.fstat(f.fileno()).st_size
     n = (size - off) // rec
     if n <= 0:
         return
-    nd = 3 + nfix + P + nvb + 2 * nsets + ncls
+    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls
     mm = np.memmap(path, dtype=np.uint8, mode="r", offset=off, shape=(n, rec))
     for i in range(n):
         d = np.frombuffer(mm[i, :nd * 8].tobytes(), dtype=np.float64)
         o = 3
         out = dict(iter=int(np.frombuffer(mm[i, :8].tobytes(), dtype=np.int64)[0]), varE=d[1], b=d[2], sets=sets)
         out["b_fixed"] = d[o:o + nfix]; o += nfix
+        out["u"], out["varU"], o = _split_random(d, o, rq)
         out["beta"] = d[o:o + P]; o += P
         out["varBeta"] = d[o:o + nvb]; o += nvb
         out["piHat"] = d[o:o + 2 * nsets]; o += 2 * nsets
@@ -67,6 +86,21 @@ def iter_sample_file(path):
         out["delta"] = np.asarray(mm[i, nd * 8:nd * 8 + P])
         yield out
     del mm
+
+
+def k_csr(K):
+    """A random-effect set's K as CSR arrays (int64 k_ptr, int32 k_col, float64 k_val): a (k_ptr, k_col, k_val) triple is passed on as
+    it is, a dense q x q array by its nonzero entries, row by row, columns ascending."""
+    if isinstance(K, tuple):
+        kp, kc, kv = K
+        return (np.ascontiguousarray(kp, dtype=np.int64), np.ascontiguousarray(kc, dtype=np.int32), np.ascontiguousarray(kv, dtype=np.float64))
+    K = np.asarray(K, dtype=np.float64)
+    if K.ndim != 2 or K.shape[0] != K.shape[1]:
+        raise ValueError("K: a q x q matrix or a CSR triple")
+    nz = K != 0.0
+    kp = np.concatenate([[0], np.cumsum(nz.sum(axis=1))]).astype(np.int64)
+    rows, cols = np.nonzero(nz)
+    return kp, np.ascontiguousarray(cols, dtype=np.int32), np.ascontiguousarray(K[rows, cols], dtype=np.float64)
 
 
 def tuple_columns(col0, nloc, k):
@@ -107,6 +141,7 @@ SYMBOLS = [
     "ngp_set_streamer", "ngp_get_streamer", "ngp_set_storage", "ngp_get_storage", "ngp_set_max_shards", "ngp_shards_for_chains", "ngp_run_many", "ngp_write_panel_file", "ngp_read_panel_header", "ngp_load_panel_file", "ngp_debug_set_mode", "ngp_debug_set_knob", "ngp_set_posterior_sums", "ngp_save_snapshot", "ngp_load_snapshot",
     "ngp_set_trace_loci", "ngp_get_trace_ext", "ngp_allreduce_posterior", "ngp_add_marker_set_r", "ngp_get_class_state", "ngp_set_class_state", "ngp_add_fixed_set", "ngp_get_fixed", "ngp_set_fixed", "ngp_debug_throw", "ngp_get_census", "ngp_debug_set_virtual_device", "ngp_debug_fail_census", "ngp_add_marker_set_tuple", "ngp_share_panel", "ngp_shards_for_pass", "ngp_set_sample_file",
     "ngp_set_chain_form", "ngp_get_chain_form", "ngp_get_setup_timing", "ngp_set_residual_weights", "ngp_get_residual_weights",
+    "ngp_add_random_set", "ngp_get_random", "ngp_set_random", "ngp_sample_random_set",
 ]
 
 _lib = None
@@ -386,6 +421,41 @@ class Sampler:
         a = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
         c = None if sum_b is None else np.ascontiguousarray(sum_b, dtype=np.float64)
         self._chk(self.L.ngp_set_fixed(self.h, _p(a, C.c_double), _p(c, C.c_double), C.c_int64(getattr(self, "nfixcol", 0))))
+
+    def add_random_set(self, level, q, K=None, df=4.0, scale=None, varU0=100.0):
+        """(1|g) random-effect set (src/mme.jl:165-272): level[i] in 0..q-1 per record, K the structure's precision (None = identity; a
+        scipy-free CSR triple (k_ptr, k_col, k_val), or a dense q x q array, sent as its nonzeros).  scale defaults to varU0 (df - 2) / df
+        (src/mme.jl:265-272).  Sampled after the fixed-effect sets, in the order added; returns the set id."""
+        lv = np.ascontiguousarray(level, dtype=np.int32)
+        if scale is None:
+            scale = varU0 * (df - 2.0) / df
+        kp, kc, kv = k_csr(K) if K is not None else (None, None, None)
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_random_set(self.h, _p(lv, C.c_int32), C.c_int64(int(q)), _p(kp, C.c_int64), _p(kc, C.c_int32), _p(kv, C.c_double),
+                                            C.c_double(df), C.c_double(scale), C.c_double(varU0), C.byref(sid)))
+        self.rand_q = getattr(self, "rand_q", []) + [int(q)]
+        return sid.value
+
+    def get_random(self, set_id):
+        q = self.rand_q[set_id]
+        u = np.empty(q); su = np.empty(q); v, sv = C.c_double(), C.c_double()
+        self._chk(self.L.ngp_get_random(self.h, C.c_int32(set_id), _p(u, C.c_double), _p(su, C.c_double), C.byref(v), C.byref(sv)))
+        return dict(u=u, sum_u=su, varU=v.value, sum_varU=sv.value)
+
+    def set_random(self, set_id, u=None, sum_u=None, varU=100.0, sum_varU=0.0):
+        a = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+        b = None if sum_u is None else np.ascontiguousarray(sum_u, dtype=np.float64)
+        for x in (a, b):
+            if x is not None and len(x) != self.rand_q[set_id]:
+                raise ValueError("u / sum_u need q entries")
+        self._chk(self.L.ngp_set_random(self.h, C.c_int32(set_id), _p(a, C.c_double), _p(b, C.c_double), C.c_double(varU), C.c_double(sum_varU)))
+
+    def sample_random_set(self, set_id, varE, ycorr, u, varU):
+        """Fine seam (sampleZ!): ycorr and u are updated in place; returns the new varU."""
+        assert ycorr.dtype == np.float64 and u.dtype == np.float64 and len(ycorr) == self.N and len(u) == self.rand_q[set_id]
+        vu = C.c_double(varU)
+        self._chk(self.L.ngp_sample_random_set(self.h, C.c_int32(set_id), C.c_double(varE), _p(ycorr, C.c_double), _p(u, C.c_double), C.byref(vu)))
+        return vu.value
 
     def add_marker_set_r(self, col0, ncol, df, scale, varBeta0, vClass, pi, estPi=False, lhs0=None, rhs0=None):
         """BayesR set: class multipliers vClass of the set's single variance, class probabilities pi (src/mme.jl:374-383)."""

@@ -11,9 +11,9 @@ Same names, argument meaning and output files as the reference, so a model scrip
     SNP(M, "geno.txt"[, "map.txt"]) in the formula      the same text inside the formula string                src/runTime.jl:13-28
     summaryMCMC("betaM"; outFolder)                     summaryMCMC("betaM", outFolder=...)                    src/misc.jl:241-244
 
-Interpreted here: the response, the intercept `1`, covariate / factor columns (optionally grouped by `blockThese`) and `SNP(...)`
-terms.  Interactions, `PED(...)`, `(1|g)` terms, GBLUP priors, BayesRC/LV are outside the accelerated
-path and raise NotImplementedError naming the reference code that handles them.
+Interpreted here: the response, the intercept `1`, covariate / factor columns (optionally grouped by `blockThese`), `(1|g)` random
+effects and `SNP(...)` terms.  Interactions, `PED(...)`, correlated (Tuple) random effects, GBLUP priors, BayesRC/LV are outside the
+accelerated path and raise NotImplementedError naming the reference code that handles them.
 All arithmetic happens in libnextgp_hip.so; this file only parses, reshapes and writes files.
 """
 import os
@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["BayesPR", "BayesB", "BayesC", "BayesR", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files"]
+__all__ = ["BayesPR", "BayesB", "BayesC", "BayesR", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -110,14 +110,17 @@ class ParsedFormula(tuple):
     everything itself (no state is left on the function: two models parsed in turn, or from threads, cannot pick up each other's
     covariates)."""
 
-    def __new__(cls, lhs, intercept, snps, covariates):
+    def __new__(cls, lhs, intercept, snps, covariates, random=()):
         t = super().__new__(cls, (lhs, intercept, snps))
         t.covariates = list(covariates)
+        t.random = list(random)  # grouping columns of the (1|g) terms, in formula order
         return t
 
 
-def parse_formula(formula):
-    """'y ~ 1 + x + SNP(M, "geno.txt", "map.txt")' -> ParsedFormula (lhs, intercept, [GenomicTerm, ...]; .covariates = ['x'])."""
+def parse_formula(formula, random_effects=False):
+    """'y ~ 1 + x + SNP(M, "geno.txt", "map.txt")' -> ParsedFormula (lhs, intercept, [GenomicTerm, ...]; .covariates = ['x']).
+    random_effects=True also takes (1|g) terms (.random = ['g'], in formula order), as runLMEM does; without it they are refused, as
+    they were before the device sampled them."""
     if "~" not in formula:
         raise ValueError("formula needs a '~'")
     lhs, rhs = [t.strip() for t in formula.split("~", 1)]
@@ -134,8 +137,16 @@ def parse_formula(formula):
             cur += ch
     if cur.strip():
         terms.append(cur.strip())
-    intercept, snps, covs = False, [], []
+    intercept, snps, covs, rnd = False, [], [], []
     for t in terms:
+        m = re.fullmatch(r"\(?\s*1\s*\|\s*([A-Za-z_][A-Za-z_0-9]*)\s*\)?", t)
+        if m and t.count("(") == t.count(")"):
+            if not random_effects:
+                raise NotImplementedError(f"term '{t}': (1|g) random effects are refused by parse_formula(formula) and would stay on the "
+                                          "reference's Julia path (src/functions.jl:57-110); runLMEM and parse_formula(formula, "
+                                          "random_effects=True) take them to the device")
+            rnd.append(m.group(1))  # (1|g): a random effect of the levels of column g (src/prepMatVec.jl:136-153)
+            continue
         if t == "1":
             intercept = True
         elif t == "0":
@@ -146,15 +157,52 @@ def parse_formula(formula):
                 raise ValueError(f"SNP term needs a name and a path: {t}")
             unq = [a.strip("\"'") for a in args]
             snps.append(GenomicTerm(unq[0], unq[1], unq[2] if len(unq) > 2 else ""))
-        elif t.startswith("PED(") or "|" in t:
-            raise NotImplementedError(f"term '{t}': pedigree / (1|g) random effects stay on the reference's Julia path "
-                                      "(src/functions.jl:57-110, src/mme.jl:165-272); they are outside the accelerated sweep")
+        elif t.startswith("PED("):
+            raise NotImplementedError(f"term '{t}': building A^-1 from a pedigree needs PedigreeBase (src/mme.jl:26-37, src/prepMatVec.jl:136-153), "
+                                      "so PED terms stay on the reference's Julia path; its coarse seam hands the Ainv it built to the device")
+        elif "|" in t:
+            raise NotImplementedError(f"term '{t}': only (1|g) random intercepts are on the accelerated path; random slopes and correlated "
+                                      "(Tuple) random effects stay on the reference's Julia path (src/functions.jl:75-89, 100-110)")
         elif re.fullmatch(r"[A-Za-z_][A-Za-z_0-9]*", t):
             covs.append(t)  # a column of the data: covariate or factor (src/prepMatVec.jl:150-165)
         else:
             raise NotImplementedError(f"term '{t}': interactions / function terms stay on the reference's Julia path (StatsModels, "
                                       "src/prepMatVec.jl:150-165); use the fine seam (ngp_sweep_set) to combine them with the GPU sweep")
-    return ParsedFormula(lhs, intercept, snps, covs)
+    return ParsedFormula(lhs, intercept, snps, covs, rnd)
+
+
+def random_levels(col):
+    """(1|g) incidence as level codes: (level[N] int32 in 0..q-1, level names).  The levels are the sorted unique values of the
+    column -- the column order StatsModels' modelcols gives Z (src/prepMatVec.jl:143-150) -- and u, its sums and the header of the
+    u file all follow that order (the reference's header is unique(data.g), first appearance: DESIGN.md, "Random-effect sets")."""
+    col = np.asarray(col)
+    names, codes = np.unique(col, return_inverse=True)
+    return codes.astype(np.int32), [str(v) for v in names.tolist()]
+
+
+def random_prior(VCV, g, q):
+    """(K, df, scale, v) of the (1|g) set from VCV["1|g"] or VCV["(1|g)"] (src/mme.jl:25-46, 265-272): Random("I", v) -> K = None
+    (identity), Random(Sigma, v) with a q x q covariance Sigma -> K = inv(Sigma) in fp64; no entry -> Random("I", 100)."""
+    prior = VCV.get(f"1|{g}", VCV.get(f"(1|{g})"))
+    if prior is None:
+        prior = Random("I", 100.0)                               # src/mme.jl:40-44
+    if not isinstance(prior, RandomEffectType):
+        raise ValueError(f"prior of (1|{g}): Random(str, v)")
+    st = prior.str
+    if st is None or (isinstance(st, str) and st in ("I", "")):
+        K = None
+    elif isinstance(st, str):
+        raise NotImplementedError(f"(1|{g}) with structure {st!r}: \"A\" / \"G\" need the pedigree / genomic matrix the reference builds "
+                                  "(PedigreeBase, src/mme.jl:26-37); pass the covariance matrix itself, or use the Julia coarse seam")
+    else:
+        S = np.asarray(st, dtype=np.float64)
+        if S.shape != (q, q):
+            raise ValueError(f"(1|{g}): the covariance matrix must be {q} x {q} (one row per level)")
+        K = np.linalg.inv(S)                                     # src/mme.jl:36: inv(priorVCV[zSet].str)
+        K = (K + K.T) / 2.0                                      # (exactly symmetric, as the library requires)
+    df = 3.0 + 1.0                                               # src/mme.jl:261
+    v = float(prior.v)
+    return K, df, v * (df - 2.0) / df, v                         # src/mme.jl:265-272
 
 
 def design_columns(name, col):
@@ -294,6 +342,12 @@ def _out(folder, name, row):
         f.write("\t".join(row) + "\n")
 
 
+def random_file_names(g):
+    """(u file, varU file, varU header) of the (1|g) set: Julia prints the key :(1|g) as "1 | g" (u$zSet / varU$zSet, src/samplers.jl:63-73,
+    src/outFiles.jl:17-21) and heads the varU file with join(zSet.args)[2:end] = "1g" (src/mme.jl:548-556)."""
+    return f"u1 | {g}", f"varU1 | {g}", f"1{g}"
+
+
 def _var_names(s):
     """Header of var<set>Out: reg_r (src/mme.jl:593-595); for correlated sets one column per entry of the region's k x k matrix."""
     if s["k"] > 1:
@@ -311,7 +365,7 @@ def summaryMCMC(param, outFolder=None):
     return np.loadtxt(os.path.join(outFolder, f"{param}Out"), delimiter="\t", skiprows=1, ndmin=2).mean(axis=0, keepdims=True)
 
 
-def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed):
+def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, randoms=()):
     """Binary sample stream (ngp_set_sample_file) -> the rows of the reference's *Out text files (src/samplers.jl:56-104), appended
     behind the header rows: the same text, number for number, as writing them at every kept iteration.  Record by record -- one
     kept iteration in memory at a time, every *Out file open for appending -- so a long chain of a large model converts in
@@ -332,6 +386,10 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed):
             n += 1
             row("b", (_fmt(S["b"]) if intercept else []) + (_fmt(S["b_fixed"]) if has_fixed else []))
             row("varE", _fmt(S["varE"]))
+            for r, rd in enumerate(randoms):                 # src/samplers.jl:60-75
+                un, vn, _ = random_file_names(rd["g"])
+                row(un, _fmt(S["u"][r]))
+                row(vn, _fmt(S["varU"][r]))
             vb_off, cls_off = 0, 0
             for k, s in enumerate(sets):
                 K = len(s["prior"].pi) if isinstance(s["prior"], BayesRType) else 0
@@ -373,7 +431,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         raise NotImplementedError("userPedData: pedigree effects stay on the Julia path (src/mme.jl:26-46)")
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
-    parsed = parse_formula(formula)
+    parsed = parse_formula(formula, random_effects=True)
     lhs, intercept, snps = parsed
     if not snps:
         raise ValueError("the accelerated path needs at least one SNP(...) term")
@@ -485,10 +543,11 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin)
              for sc in samplers]
     sets, fixed_names = built[0]
+    randoms = samplers[0].randoms
     folders = [outFolder] if K == 1 else [os.path.join(outFolder, f"chain{chain + c}") for c in range(K)]
     for f in folders:
         os.makedirs(f, exist_ok=True)
-    return _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples)
+    return _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
 
 
 def _residual_weights(e_prior, N):
@@ -542,6 +601,13 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
         else:
             smp.add_fixed_set(Xc)
         fixed_names += names
+    # (1|g) random-effect sets, after the fixed effects, in formula order (src/samplers.jl:43-46; set-up src/mme.jl:165-272)
+    smp.randoms = []
+    for g in parsed.random:
+        level, names = random_levels(userData[g])
+        K, rdf, rscale, v = random_prior(VCV, g, len(names))
+        rid = smp.add_random_set(level, len(names), K=K, df=rdf, scale=rscale, varU0=v)
+        smp.randoms.append(dict(id=rid, g=g, levels=names, q=len(names)))
     # marker sets (src/mme.jl:287-347, 492-520; correlated sets :448-489)
     sets = []
     for unit in units:
@@ -593,7 +659,7 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
     return sets, fixed_names
 
 
-def _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples):
+def _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms=()):
     """Header rows, the chain(s), the *Out rows and the posterior means (pooled over the chains when there are several)."""
     if samples not in ("text", "text-sync", "binary", "none"):
         raise ValueError('samples: "text", "text-sync", "binary" or "none"')
@@ -601,7 +667,7 @@ def _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, n
         paths = [os.path.join(f, "samples.ngpsmp") for f in folders]
         for sc, f, pth in zip(samplers, folders, paths):
             if samples == "text":
-                _write_headers(f, sets, fixed_names)
+                _write_headers(f, sets, fixed_names, randoms)
             if samples in ("text", "binary"):
                 sc.set_sample_file(pth)
         samplers[0].get_timing()
@@ -617,23 +683,27 @@ def _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, n
             if samples in ("text", "binary"):
                 sc.set_sample_file(None)
             if samples == "text":
-                samples_to_out_files(pth, f, sets, intercept, len(fixed_names) > int(intercept))
+                samples_to_out_files(pth, f, sets, intercept, len(fixed_names) > int(intercept), randoms)
                 os.remove(pth)
-            results.append(_posterior_means(sc, sets, fixed_names, intercept))
+            results.append(_posterior_means(sc, sets, fixed_names, intercept, randoms))
         pooled = _pool_results(results)
         pooled["fused"] = bool(fused)
         return pooled
     smp, outFolder = samplers[0], folders[0]
     # header rows (src/mme.jl:543-595)
     if samples in ("text", "text-sync"):
-        _write_headers(outFolder, sets, fixed_names)
-    return _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin, samples)
+        _write_headers(outFolder, sets, fixed_names, randoms)
+    return _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
 
 
-def _write_headers(outFolder, sets, fixed_names):
+def _write_headers(outFolder, sets, fixed_names, randoms=()):
     """Header rows of the *Out files (src/mme.jl:543-595)."""
     _out(outFolder, "b", fixed_names)
     _out(outFolder, "varE", ["e"])
+    for rd in randoms:   # src/mme.jl:548-556; the u header lists the levels in the order of u (random_levels)
+        un, vn, vh = random_file_names(rd["g"])
+        _out(outFolder, un, rd["levels"])
+        _out(outFolder, vn, [vh])
     for s in sets:
         names = [f"M{i + 1}" for i in range(s["P"])]  # src/prepMatVec.jl:131
         for nm in s["members"]:
@@ -646,7 +716,7 @@ def _write_headers(outFolder, sets, fixed_names):
         _out(outFolder, f"var{s['name']}", _var_names(s))
 
 
-def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin, samples):
+def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms=()):
     # the chain (src/samplers.jl:29-105): kept iterations = burnIn+thin : thin : chainLength
     done = 0
     smp_path = os.path.join(outFolder, "samples.ngpsmp")
@@ -659,6 +729,11 @@ def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin,
             st = smp.get_state()
             _out(outFolder, "b", (_fmt(st["b"]) if intercept else []) + (_fmt(smp.get_fixed()["b"]) if len(fixed_names) > int(intercept) else []))
             _out(outFolder, "varE", _fmt(st["varE"]))
+            for rd in randoms:
+                un, vn, _ = random_file_names(rd["g"])
+                rr = smp.get_random(rd["id"])
+                _out(outFolder, un, _fmt(rr["u"]))
+                _out(outFolder, vn, _fmt(rr["varU"]))
             vb_off = 0
             for k, s in enumerate(sets):
                 for m, nm in enumerate(s["members"]):
@@ -674,12 +749,12 @@ def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin,
     if samples in ("text", "binary"):
         smp.set_sample_file(None)
     if samples == "text":
-        samples_to_out_files(smp_path, outFolder, sets, intercept, len(fixed_names) > int(intercept))
+        samples_to_out_files(smp_path, outFolder, sets, intercept, len(fixed_names) > int(intercept), randoms)
         os.remove(smp_path)
-    return _posterior_means(smp, sets, fixed_names, intercept)
+    return _posterior_means(smp, sets, fixed_names, intercept, randoms)
 
 
-def _posterior_means(smp, sets, fixed_names, intercept):
+def _posterior_means(smp, sets, fixed_names, intercept, randoms=()):
     ps = smp.get_posterior_sums()
     n = max(ps["nKept"], 1)
     res = dict(nKept=ps["nKept"], b=ps["sum_b"] / n, varE=ps["sum_varE"] / n, sets={}, fixed_names=fixed_names,
@@ -695,6 +770,10 @@ def _posterior_means(smp, sets, fixed_names, intercept):
         if isinstance(s["prior"], BayesRType):
             res["sets"][s["name"]]["pi"] = smp.get_class_state(s["id"])["sum_pi"] / n
         vb_off += s["nvb"]
+    res["random"] = {}
+    for rd in randoms:   # posterior means of u (levels in random_levels order) and varU, keyed as Julia prints the term
+        rr = smp.get_random(rd["id"])
+        res["random"][f"1 | {rd['g']}"] = dict(u=rr["sum_u"] / n, varU=rr["sum_varU"] / n, levels=rd["levels"])
     res["sampler"] = smp
     return res
 
@@ -710,4 +789,6 @@ def _pool_results(results):
                   sampler=results[0]["sampler"], samplers=[r["sampler"] for r in results])
     for nm in results[0]["sets"]:
         pooled["sets"][nm] = {k: avg(lambda r, k=k: r["sets"][nm][k]) for k in results[0]["sets"][nm]}
+    pooled["random"] = {nm: dict(u=avg(lambda r: r["random"][nm]["u"]), varU=float(avg(lambda r: r["random"][nm]["varU"])),
+                                 levels=results[0]["random"][nm]["levels"]) for nm in results[0].get("random", {})}
     return pooled

@@ -22,6 +22,7 @@
 
 #include "../../include/nextgp_hip.h"
 #include "ngp_kernels.h"
+#include "ngp_random.h"
 #include "ngp_sweep_args.h"
 
 using namespace ngp;
@@ -32,6 +33,21 @@ struct HFix {  // one fixed-effect set beyond the intercept
     int64_t ncol, off;
     double *d_X = nullptr, *d_xpx0 = nullptr, *d_xpxR = nullptr, *d_lhs0 = nullptr, *d_rhs0 = nullptr;
 };
+
+struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled after the fixed-effect sets (src/samplers.jl:43-46)
+    int64_t q = 0;
+    double df = 0.0, scale = 0.0, varU0 = 0.0;
+    bool offdiag = false;      // K has entries off its diagonal: Gauss-Seidel (k_rand_gs); otherwise every level is drawn on its own
+    uint64_t fine_calls = 0;   // ngp_sample_random_set calls (their iteration key, as ngp_sweep_set's)
+    long long *d_lptr = nullptr, *d_kptr = nullptr;  // records of level l: d_lrows[d_lptr[l] .. d_lptr[l + 1]); CSR of K
+    int *d_lrows = nullptr, *d_level = nullptr, *d_kcol = nullptr;
+    double *d_kval = nullptr, *d_kdiag = nullptr, *d_zpz = nullptr;
+    double *d_u = nullptr, *d_sum_u = nullptr;
+    double *d_vu = nullptr;    // [varU, sum_varU]
+    double *d_scr = nullptr;   // NGP_RS_ROWS x q scratch (ngp_random.h)
+    uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
+};
+void free_rand(HRand &r);  // (below)
 
 struct PanelMem {  // d_tiles / d_mean / d_gramx / d_mpm of one uploaded panel; handles that share it hold a reference each
     void *tiles = nullptr, *mean = nullptr, *gramx = nullptr, *mpm = nullptr;
@@ -317,6 +333,8 @@ struct ngp_handle {
     double *d_varBeta = nullptr, *d_sum_varBeta = nullptr;
     int64_t vb_cap = 0;
     std::vector<HFix> fix;           // fixed-effect sets beyond the intercept (src/functions.jl:22-53), in sampling order
+    std::vector<HRand> rnd;          // (1|g) random-effect sets (src/functions.jl:57-110), sampled after the fixed-effect sets, in order
+    int64_t nrandcol = 0;            // sum of q over the random-effect sets
     int64_t nfixcol = 0;
     double *d_bfix = nullptr, *d_sum_bfix = nullptr;
     double *d_rcls = nullptr;        // BayesR per-locus class coefficients [4][NGP_RMAX][Ppad] (allocated with the first BayesR set)
@@ -594,6 +612,8 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     // with the marker sets -- k_fixed would read d_X of the old N, k_post beta[loci[k]] beyond the new P
     for (auto &fx : h->fix) { dfree(fx.d_X); dfree(fx.d_xpx0); dfree(fx.d_xpxR); dfree(fx.d_lhs0); dfree(fx.d_rhs0); }
     h->fix.clear(); h->nfixcol = 0; dfree(h->d_bfix); dfree(h->d_sum_bfix);
+    for (auto &r : h->rnd) free_rand(r);  // (the random-effect sets too: their records are rows of the old panel)
+    h->rnd.clear(); h->nrandcol = 0;
     dfree(h->d_trace_loci); dfree(h->d_tr_beta); dfree(h->d_tr_vb); dfree(h->d_tr_pi);
     h->ntl = 0; h->ntvb = 0; h->trace_ext_cap = 0;
     h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false;
@@ -1004,6 +1024,25 @@ void launch_tinv(ngp_handle *h) {  // (sync_linear_blocks has run for this call'
                        (const unsigned *)h->d_blin, h->d_tinv, (const unsigned *)h->d_abort, (const double *)h->d_tupc, (long long)h->Ppad);
 }
 
+// one random-effect set on h->stream (ngp_random.h): level sums and draws, Gauss-Seidel for a general K, ycorr update, varU
+void launch_random(ngp_handle *h, int r, uint64_t it) {
+    HRand &R = h->rnd[(size_t)r];
+    const long long q = (long long)R.q;
+    hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->d_ycorr, (const double *)h->d_rs, q,
+                       (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag,
+                       (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr,
+                       (int)R.offdiag, (const DScal *)h->d_scal, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->d_abort);
+    if (R.offdiag) {
+        const int use_lds = (size_t)q * sizeof(double) <= NGP_LDS_MAX;
+        hipLaunchKernelGGL(k_rand_gs, dim3(1), dim3(64), use_lds ? (size_t)q * sizeof(double) : 0, h->stream, q, (const long long *)R.d_kptr,
+                           (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr, use_lds, (const unsigned *)h->d_abort);
+    }
+    hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->d_ycorr, (const double *)h->d_rs, (long long)h->N,
+                       (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), (const unsigned *)h->d_abort);
+    hipLaunchKernelGGL(k_rand_var, dim3(1), dim3(1024), 0, h->stream, q, (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval,
+                       (const double *)R.d_u, R.d_vu, R.df, R.scale, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->d_abort);
+}
+
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
@@ -1014,6 +1053,8 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
         hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->N, h->fix[f].d_X, (int)h->fix[f].ncol, h->fix[f].d_xpx0,
                            h->fix[f].d_xpxR, h->fix[f].d_lhs0, h->fix[f].d_rhs0, h->d_bfix + h->fix[f].off, h->d_scal, (int)f, h->seed,
                            (uint64_t)h->chain, it, h->d_abort);
+    for (size_t r = 0; r < h->rnd.size(); r++)  // the random-effect sets, in the order they were added (src/samplers.jl:43-46)
+        launch_random(h, (int)r, it);
     }
     hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->d_setof, h->d_loc,
                        h->d_vbidx, h->d_sets, h->d_scal, h->d_varBeta, h->d_mpm, h->d_lhs0, h->d_rhs0, h->d_beta, h->d_c, h->d_w,
@@ -1040,6 +1081,10 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
         if (h->nfixcol > 0)
             hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((h->nfixcol + 255) / 256)), dim3(256), 0, h->stream, (long long)h->nfixcol, h->d_bfix,
                                h->d_sum_bfix, h->d_abort);
+        for (auto &R : h->rnd) {  // random-effect sets: u and varU (src/samplers.jl:60-75)
+            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((R.q + 255) / 256)), dim3(256), 0, h->stream, (long long)R.q, R.d_u, R.d_sum_u, h->d_abort);
+            hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, 1LL, R.d_vu, R.d_vu + 1, h->d_abort);
+        }
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
     return NGP_OK;
@@ -1098,14 +1143,16 @@ int set_class_state_dev(ngp_handle *h, int si, const double *pi, const double *s
     return NGP_OK;
 }
 
-// doubles of the packed posterior (ngp_export_posterior_device): 3P + nvb + 2 nsets + sum K + fixed-effect columns + 3
+// doubles of the packed posterior (ngp_export_posterior_device): 3P + nvb + 2 nsets + sum K + fixed-effect columns
+// (+ sum q + number of random-effect sets) + 3
 int64_t posterior_words(const ngp_handle *h) {
-    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->nfixcol + 3;
+    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->nfixcol + h->nrandcol + (int64_t)h->rnd.size() + 3;
 }
 
 // ---- sample stream (ngp_set_sample_file) ----
 size_t sample_rec_bytes(const ngp_handle *h) {
-    const size_t nd = 3 + (size_t)h->nfixcol + (size_t)h->P + (size_t)h->nvb + 2 * h->sets.size() + (size_t)h->nclass_total;
+    const size_t nd = 3 + (size_t)h->nfixcol + (size_t)(h->nrandcol + (int64_t)h->rnd.size()) + (size_t)h->P + (size_t)h->nvb + 2 * h->sets.size() +
+                      (size_t)h->nclass_total;
     return nd * 8 + (((size_t)h->P + 7) & ~(size_t)7);
 }
 void sample_writer_loop(SampleStream *S) {
@@ -1159,8 +1206,14 @@ int sample_enqueue(ngp_handle *h) {
                 return fail(h, NGP_ERR_NOMEM, "sample ring");
         }
         const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
-        bool ok = std::fwrite("NGPSMP01", 1, 8, S->f) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f) == 1;
+        // (a chain with random-effect sets: "NGPSMP02", and the header ends in int64 nrand | q per set)
+        bool ok = std::fwrite(h->rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f) == 1;
         for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f) == 1; }
+        if (!h->rnd.empty()) {
+            const int64_t nr = (int64_t)h->rnd.size();
+            ok = ok && std::fwrite(&nr, 8, 1, S->f) == 1;
+            for (auto &R : h->rnd) ok = ok && std::fwrite(&R.q, 8, 1, S->f) == 1;
+        }
         if (!ok) return fail(h, NGP_ERR_ARG, "cannot write the sample file header: " + S->path);
         S->header_written = true;
     } else if (S->rec_bytes != sample_rec_bytes(h)) {
@@ -1175,8 +1228,23 @@ int sample_enqueue(ngp_handle *h) {
     }
     const long long n = std::max<long long>(std::max<long long>(h->P, h->nvb), std::max<long long>(h->nfixcol, 1));
     hipLaunchKernelGGL(k_sample_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, S->d_slot[slot], (long long)h->P, (long long)h->nvb,
-                       (int)h->sets.size(), (long long)h->nfixcol, (long long)h->nclass_total, (long long)h->iter, h->d_beta, h->d_delta, h->d_varBeta,
-                       h->d_sets, h->d_scal, h->d_bfix, h->d_abort);
+                       (int)h->sets.size(), (long long)h->nfixcol, (long long)(h->nrandcol + (int64_t)h->rnd.size()), (long long)h->nclass_total,
+                       (long long)h->iter, h->d_beta, h->d_delta, h->d_varBeta, h->d_sets, h->d_scal, h->d_bfix, h->d_abort);
+    {   // random-effect sets: u (set after set), then varU of every set, behind b_fixed
+        double *o = (double *)S->d_slot[slot] + 3 + h->nfixcol;
+        int64_t off = 0;
+        hipError_t e0 = hipSuccess;
+        for (size_t r = 0; r < h->rnd.size() && e0 == hipSuccess; r++) {
+            e0 = hipMemcpyAsync(o + off, h->rnd[r].d_u, (size_t)h->rnd[r].q * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+            if (e0 == hipSuccess) e0 = hipMemcpyAsync(o + h->nrandcol + (int64_t)r, h->rnd[r].d_vu, sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+            off += h->rnd[r].q;
+        }
+        if (e0 != hipSuccess) {
+            { std::lock_guard<std::mutex> lk(S->mu); S->busy[slot] = false; }
+            S->cv.notify_all();
+            return fail(h, NGP_ERR_HIP, std::string("sample stream: ") + hipGetErrorString(e0));
+        }
+    }
     // (a HIP call that fails here gives the slot back: the next enqueue would otherwise wait for it forever instead of reporting)
     hipError_t e = hipEventRecord(S->ev_packed[slot], h->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(S->copy_stream, S->ev_packed[slot], 0);
@@ -1263,6 +1331,7 @@ int32_t ngp_destroy(ngp_handle *h) {
     dfree(h->d_sum_varBeta); dfree(h->d_regs); dfree(h->d_seg_k0); dfree(h->d_seg_len); dfree(h->d_segpart); dfree(h->d_regchi);
     for (auto &fx : h->fix) { dfree(fx.d_X); dfree(fx.d_xpx0); dfree(fx.d_xpxR); dfree(fx.d_lhs0); dfree(fx.d_rhs0); }
     dfree(h->d_bfix); dfree(h->d_sum_bfix);
+    for (auto &r : h->rnd) free_rand(r);
     dfree(h->d_tup); dfree(h->d_tupc); dfree(h->d_tupg); dfree(h->d_tsegpart); dfree(h->d_tregs); dfree(h->d_tseg_l0); dfree(h->d_tseg_len); dfree(h->d_tseg_set);
     dfree(h->d_tr_varE); dfree(h->d_tr_b); dfree(h->d_trace_loci); dfree(h->d_tr_beta); dfree(h->d_tr_vb); dfree(h->d_tr_pi);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1372,6 +1441,7 @@ namespace {
 struct PanelHeader { char magic[8]; int64_t N, P; int32_t bits, zero; };
 }
 #define NGP_SNAP_WEIGHTED ((int64_t)1 << 62)  // snapshot: the fixed-set count's flag of a weighted chain (ngp_save_snapshot)
+#define NGP_SNAP_RANDOM ((int64_t)1 << 61)    // ... and of a chain with random-effect sets
 
 int32_t ngp_write_panel_file(const char *path, const uint8_t *G, int64_t N, int64_t P, int64_t ld, int32_t bits) {
     NGP_TRY
@@ -1716,6 +1786,14 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     if (h->nfixcol > 0) {
         HCHK(hipMemsetAsync(h->d_bfix, 0, (size_t)h->nfixcol * sizeof(double), h->stream));
         HCHK(hipMemsetAsync(h->d_sum_bfix, 0, (size_t)h->nfixcol * sizeof(double), h->stream));
+    }
+    for (auto &R : h->rnd) {  // u = 0, varU = its prior value (src/mme.jl:200, 265-272), empty sums
+        const double vu[2] = {R.varU0, 0.0};
+        HCHK(hipMemsetAsync(R.d_u, 0, (size_t)R.q * sizeof(double), h->stream));
+        HCHK(hipMemsetAsync(R.d_sum_u, 0, (size_t)R.q * sizeof(double), h->stream));
+        HCHK(hipMemcpyAsync(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));
+        R.fine_calls = 0;
     }
     HCHK(hipStreamSynchronize(h->stream));
     h->iter = 0; h->have_y = true; h->poisoned = false; h->ntrace = 0;
@@ -2084,6 +2162,16 @@ int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len
     const size_t nfix_at = tail.size();
     tail.resize(nfix_at + (size_t)h->nfixcol);  // fixed-effect sums beyond the intercept (all columns of all sets, in order)
     if (h->nfixcol > 0) HCHK(hipMemcpy(tail.data() + nfix_at, h->d_sum_bfix, (size_t)h->nfixcol * sizeof(double), hipMemcpyDeviceToHost));
+    if (!h->rnd.empty()) {  // random-effect sets: sums of u (set after set), then the sums of varU
+        const size_t r_at = tail.size();
+        tail.resize(r_at + (size_t)h->nrandcol + h->rnd.size());
+        size_t off = r_at;
+        for (size_t r = 0; r < h->rnd.size(); r++) {
+            HCHK(hipMemcpy(tail.data() + off, h->rnd[r].d_sum_u, (size_t)h->rnd[r].q * sizeof(double), hipMemcpyDeviceToHost));
+            HCHK(hipMemcpy(tail.data() + r_at + (size_t)h->nrandcol + r, h->rnd[r].d_vu + 1, sizeof(double), hipMemcpyDeviceToHost));
+            off += (size_t)h->rnd[r].q;
+        }
+    }
     tail.push_back(sc.sum_varE); tail.push_back(sc.sum_b); tail.push_back((double)sc.nKept);
     HCHK(hipMemcpy(o + 3 * h->P + h->nvb, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice));
     return NGP_OK;
@@ -2544,9 +2632,14 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     {   // model signature: a snapshot only loads into the model it was taken from (equal counts are not enough)
         for (auto &hs : h->sets) { const int64_t sg[5] = {hs.method, hs.K + 16 * hs.tk, hs.nreg, hs.col0, hs.ncol}; W(sg, sizeof(sg)); }
         // (weighted residuals: bit 62 of the fixed-set count says so, and a digest of the weights follows it -- unweighted bytes unchanged)
-        const int64_t nfs = (int64_t)h->fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED);
+        const int64_t nfs = (int64_t)h->fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->rnd.empty() ? 0 : NGP_SNAP_RANDOM);
         W(&nfs, 8);
         if (!h->h_rw.empty()) { const uint64_t dg = weights_digest(h->h_rw); W(&dg, 8); }
+        if (!h->rnd.empty()) {  // random-effect sets: int64 nrand | per set int64 q, uint64 digest of its levels and K
+            const int64_t nr = (int64_t)h->rnd.size();
+            W(&nr, 8);
+            for (auto &R : h->rnd) { W(&R.q, 8); W(&R.sig, 8); }
+        }
         for (auto &fx : h->fix) W(&fx.ncol, 8);
     }
     W(scal, sizeof(scal));
@@ -2566,6 +2659,14 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
             if ((rc = ngp_get_class_state(h, (int32_t)si, cp, cs, &K))) { fclose(f); remove(tmp.c_str()); return rc; }
             W(cp, (size_t)K * 8); W(cs, (size_t)K * 8);
         }
+    for (size_t r = 0; r < h->rnd.size() && ok; r++) {  // random-effect sets: u[q] | sum_u[q] | varU | sum_varU | fine_calls
+        const HRand &R = h->rnd[r];
+        std::vector<double> a((size_t)R.q), b2((size_t)R.q);
+        double vu[2];
+        if (hipMemcpy(a.data(), R.d_u, a.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(b2.data(), R.d_sum_u, b2.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost) != hipSuccess) { fclose(f); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the random-effect sets"); }
+        W(a.data(), a.size() * 8); W(b2.data(), b2.size() * 8); W(vu, sizeof(vu)); W(&R.fine_calls, 8);
+    }
     if (fclose(f) != 0) ok = false;
     if (!ok || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return fail(h, NGP_ERR_ARG, std::string("writing the snapshot failed: ") + path); }
     return NGP_OK;
@@ -2599,8 +2700,29 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         int64_t nfs = -1;
         Rd(&nfs, 8);
         const bool snap_w = ok && nfs >= 0 && (nfs & NGP_SNAP_WEIGHTED) != 0;
+        const bool snap_r = ok && nfs >= 0 && (nfs & NGP_SNAP_RANDOM) != 0;
         uint64_t dg = 0;
         if (snap_w) { nfs &= ~NGP_SNAP_WEIGHTED; Rd(&dg, 8); }
+        if (snap_r) nfs &= ~NGP_SNAP_RANDOM;
+        if (ok && snap_r != !h->rnd.empty()) {
+            fclose(f);
+            return fail(h, NGP_ERR_ARG, snap_r ? "snapshot of a chain with random-effect sets: this handle has none (ngp_add_random_set)"
+                                               : "snapshot of a chain without random-effect sets: this handle has them");
+        }
+        if (snap_r) {
+            int64_t nr = -1;
+            Rd(&nr, 8);
+            bool rsame = ok && nr == (int64_t)h->rnd.size();
+            for (size_t r = 0; rsame && r < h->rnd.size(); r++) {
+                int64_t q = -1; uint64_t sg = 0;
+                Rd(&q, 8); Rd(&sg, 8);
+                rsame = ok && q == h->rnd[r].q && sg == h->rnd[r].sig;
+            }
+            if (!rsame) {
+                fclose(f);
+                return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its random-effect sets differ: levels, level coding or K)");
+            }
+        }
         if (ok && snap_w != !h->h_rw.empty()) {
             fclose(f);
             return fail(h, NGP_ERR_ARG, snap_w ? "snapshot of a chain with residual weights: this handle has none (ngp_set_residual_weights)"
@@ -2635,6 +2757,13 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
     Rd(fb.data(), (size_t)h->nfixcol * 8); Rd(fs.data(), (size_t)h->nfixcol * 8);
     std::vector<double> cls((size_t)2 * std::max<int64_t>(h->nclass_total, 1));
     Rd(cls.data(), (size_t)2 * h->nclass_total * 8);
+    std::vector<std::vector<double>> ru(h->rnd.size()), rsu(h->rnd.size());
+    std::vector<double> rvu(2 * h->rnd.size() + 1);
+    std::vector<uint64_t> rfc(h->rnd.size() + 1);
+    for (size_t r = 0; r < h->rnd.size(); r++) {
+        ru[r].resize((size_t)h->rnd[r].q); rsu[r].resize((size_t)h->rnd[r].q);
+        Rd(ru[r].data(), ru[r].size() * 8); Rd(rsu[r].data(), rsu[r].size() * 8); Rd(rvu.data() + 2 * r, 16); Rd(rfc.data() + r, 8);
+    }
     char extra;
     const bool at_end = fread(&extra, 1, 1, f) == 0;
     fclose(f);
@@ -2656,6 +2785,13 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
                 if ((rc = set_class_state_dev(h, (int)si, cls.data() + off, cls.data() + off + K))) return rc;
                 off += 2 * K;
             }
+    }
+    for (size_t r = 0; r < h->rnd.size(); r++) {
+        HRand &R = h->rnd[r];
+        HCHK(hipMemcpy(R.d_u, ru[r].data(), ru[r].size() * 8, hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(R.d_sum_u, rsu[r].data(), rsu[r].size() * 8, hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(R.d_vu, rvu.data() + 2 * r, 16, hipMemcpyHostToDevice));
+        R.fine_calls = rfc[r];
     }
     h->seed = ids[0]; h->chain = (uint32_t)ids[1];  // the draws continue the interrupted chain's streams
     h->poisoned = false;
@@ -2735,7 +2871,7 @@ int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp
     HCHK(hipMemcpyAsync(h->d_sum_beta2, o + h->P, pb, hipMemcpyDeviceToDevice, h->stream));
     HCHK(hipMemcpyAsync(h->d_sum_delta, o + 2 * h->P, pb, hipMemcpyDeviceToDevice, h->stream));
     if (h->nvb) HCHK(hipMemcpyAsync(h->d_sum_varBeta, o + 3 * h->P, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->nfixcol + 3);
+    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->nfixcol + (size_t)h->nrandcol + h->rnd.size() + 3);
     HCHK(hipMemcpyAsync(tail.data(), o + 3 * h->P + h->nvb, tail.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
     for (size_t si = 0; si < h->sets.size(); si++)
@@ -2753,7 +2889,16 @@ int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp
     if (h->nfixcol > 0) HCHK(hipMemcpy(h->d_sum_bfix, tail.data() + tf, (size_t)h->nfixcol * sizeof(double), hipMemcpyHostToDevice));
     DScal sc;
     HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
-    const size_t t0 = tf + (size_t)h->nfixcol;
+    {
+        const size_t r_at = tf + (size_t)h->nfixcol;
+        size_t off = r_at;
+        for (size_t r = 0; r < h->rnd.size(); r++) {
+            HCHK(hipMemcpy(h->rnd[r].d_sum_u, tail.data() + off, (size_t)h->rnd[r].q * sizeof(double), hipMemcpyHostToDevice));
+            HCHK(hipMemcpy(h->rnd[r].d_vu + 1, tail.data() + r_at + (size_t)h->nrandcol + r, sizeof(double), hipMemcpyHostToDevice));
+            off += (size_t)h->rnd[r].q;
+        }
+    }
+    const size_t t0 = tf + (size_t)h->nfixcol + (size_t)h->nrandcol + h->rnd.size();
     sc.sum_varE = tail[t0]; sc.sum_b = tail[t0 + 1]; sc.nKept = (long long)std::llround(tail[t0 + 2]);
     HCHK(hipMemcpy(h->d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
     HCHK(hipStreamSynchronize(h->stream));
@@ -2802,7 +2947,7 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
     for (int i = 0; i < n; i++) {
         REQUIRE(hs[i]->d_tiles != nullptr, NGP_ERR_STATE, "ngp_allreduce_posterior: a handle has no panel");
         REQUIRE(hs[i]->P == h->P && hs[i]->nvb == h->nvb && hs[i]->sets.size() == h->sets.size() && hs[i]->nfixcol == h->nfixcol &&
-                    hs[i]->nclass_total == h->nclass_total,
+                    hs[i]->nclass_total == h->nclass_total && hs[i]->nrandcol == h->nrandcol && hs[i]->rnd.size() == h->rnd.size(),
                 NGP_ERR_ARG, "ngp_allreduce_posterior: the chains do not share one model");
         for (int k = 0; k < i; k++) REQUIRE(hs[k] != hs[i], NGP_ERR_ARG, "ngp_allreduce_posterior: a handle is listed twice");
     }
@@ -3150,6 +3295,200 @@ int32_t ngp_set_fixed(ngp_handle *h, const double *b, const double *sum_b, int64
     if (b) HCHK(hipMemcpy(h->d_bfix, b, (size_t)h->nfixcol * sizeof(double), hipMemcpyHostToDevice));
     if (sum_b) HCHK(hipMemcpy(h->d_sum_bfix, sum_b, (size_t)h->nfixcol * sizeof(double), hipMemcpyHostToDevice));
     return NGP_OK;
+    NGP_CATCH(h)
+}
+
+}  // extern "C"
+
+namespace {
+void free_rand(HRand &r) {
+    dfree(r.d_lptr); dfree(r.d_kptr); dfree(r.d_lrows); dfree(r.d_level); dfree(r.d_kcol); dfree(r.d_kval); dfree(r.d_kdiag); dfree(r.d_zpz);
+    dfree(r.d_u); dfree(r.d_sum_u); dfree(r.d_vu); dfree(r.d_scr);
+}
+uint64_t bytes_digest(uint64_t x, const void *p, size_t n) {  // FNV-1a, continued from x
+    const unsigned char *c = (const unsigned char *)p;
+    for (size_t k = 0; k < n; k++) { x ^= c[k]; x *= 1099511628211ull; }
+    return x;
+}
+template <class T>
+int upload(ngp_handle *h, T **d, const std::vector<T> &v) {
+    int rc;
+    if ((rc = dalloc(h, d, v.size()))) return rc;
+    if (!v.empty()) HCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+/* A (1|g) random-effect set (src/mme.jl:165-272; sampled by sampleZ!, src/functions.jl:57-72, 92-97, 498-501).  Every argument is
+ * checked before anything changes: a refused call leaves the handle as it was. */
+int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
+                           double df, double scale, double varU0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
+    REQUIRE(level != nullptr && q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: levels of N records and 1 <= q < 2^31");
+    REQUIRE(h->rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
+    REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
+    const bool ident = !k_ptr && !k_col && !k_val;
+    REQUIRE(ident || (k_ptr && k_col && k_val), NGP_ERR_ARG, "random-effect set: K as CSR (k_ptr, k_col, k_val), or all three NULL for the identity");
+    const int64_t N = h->N;
+    for (int64_t i = 0; i < N; i++) REQUIRE(level[i] >= 0 && (int64_t)level[i] < q, NGP_ERR_ARG, "random-effect set: a record's level is outside 0..q-1");
+    // K: rows with their columns ascending (the summation order of DESIGN.md), symmetric, finite, with a positive diagonal
+    std::vector<long long> kp((size_t)q + 1);
+    std::vector<int> kc;
+    std::vector<double> kv, kd((size_t)q);
+    bool offdiag = false;
+    if (ident) {
+        kc.resize((size_t)q); kv.assign((size_t)q, 1.0);
+        for (int64_t l = 0; l <= q; l++) kp[(size_t)l] = l;
+        for (int64_t l = 0; l < q; l++) { kc[(size_t)l] = (int)l; kd[(size_t)l] = 1.0; }
+    } else {
+        REQUIRE(k_ptr[0] == 0, NGP_ERR_ARG, "random-effect set: k_ptr[0] must be 0");
+        for (int64_t l = 0; l < q; l++) REQUIRE(k_ptr[l + 1] >= k_ptr[l], NGP_ERR_ARG, "random-effect set: k_ptr must not decrease");
+        const int64_t nnz = k_ptr[q];
+        REQUIRE(nnz <= ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: K has too many entries");
+        kc.resize((size_t)nnz); kv.resize((size_t)nnz);
+        std::vector<std::pair<int, double>> row;
+        for (int64_t l = 0; l < q; l++) {
+            row.clear();
+            for (int64_t k = k_ptr[l]; k < k_ptr[l + 1]; k++) {
+                REQUIRE(k_col[k] >= 0 && (int64_t)k_col[k] < q, NGP_ERR_ARG, "random-effect set: a column of K is outside 0..q-1");
+                REQUIRE(std::isfinite(k_val[k]), NGP_ERR_ARG, "random-effect set: non-finite entry in K");
+                row.emplace_back(k_col[k], k_val[k]);
+            }
+            std::sort(row.begin(), row.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+            bool diag = false;
+            for (size_t k = 0; k < row.size(); k++) {
+                REQUIRE(k == 0 || row[k].first != row[k - 1].first, NGP_ERR_ARG, "random-effect set: K has a repeated entry");
+                kc[(size_t)k_ptr[l] + k] = row[k].first; kv[(size_t)k_ptr[l] + k] = row[k].second;
+                if (row[k].first == l) { diag = true; kd[(size_t)l] = row[k].second; }
+                else offdiag = true;
+            }
+            REQUIRE(diag && kd[(size_t)l] > 0.0, NGP_ERR_ARG, "random-effect set: every diagonal entry of K must be present and > 0");
+            kp[(size_t)l] = k_ptr[l];
+        }
+        kp[(size_t)q] = nnz;
+        for (int64_t l = 0; l < q; l++)  // symmetry: K[l][c] == K[c][l] exactly (row c is sorted: binary search)
+            for (long long k = kp[(size_t)l]; k < kp[(size_t)l + 1]; k++) {
+                const int c = kc[(size_t)k];
+                const auto b = kc.begin() + kp[(size_t)c], e = kc.begin() + kp[(size_t)c + 1];
+                const auto it = std::lower_bound(b, e, (int)l);
+                REQUIRE(it != e && *it == (int)l && kv[(size_t)(it - kc.begin())] == kv[(size_t)k], NGP_ERR_ARG, "random-effect set: K is not symmetric");
+            }
+    }
+    // records grouped by level: a stable counting sort of the record indices (ascending within a level)
+    std::vector<long long> lp((size_t)q + 1, 0);
+    std::vector<int> lr((size_t)N), lv((size_t)N);
+    for (int64_t i = 0; i < N; i++) lp[(size_t)level[i] + 1]++;
+    for (int64_t l = 0; l < q; l++) lp[(size_t)l + 1] += lp[(size_t)l];
+    {
+        std::vector<long long> pos(lp.begin(), lp.end() - 1);
+        for (int64_t i = 0; i < N; i++) { lr[(size_t)pos[(size_t)level[i]]++] = (int)i; lv[(size_t)i] = level[i]; }
+    }
+    // zpz_l = z_l'z_l (src/mme.jl:193-196): the record count; weighted residuals: sum of w over the level's records in that order (:183-188)
+    std::vector<double> zpz((size_t)q, 0.0);
+    for (int64_t l = 0; l < q; l++) {
+        if (h->h_rw.empty()) { zpz[(size_t)l] = (double)(lp[(size_t)l + 1] - lp[(size_t)l]); continue; }
+        double a = 0.0;
+        for (long long k = lp[(size_t)l]; k < lp[(size_t)l + 1]; k++) a = a + h->h_rw[(size_t)lr[(size_t)k]];
+        zpz[(size_t)l] = a;
+    }
+    HRand R;
+    R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = offdiag;
+    R.sig = bytes_digest(bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull, lv.data(), lv.size() * 4), kp.data(), kp.size() * 8), kc.data(),
+                                      kc.size() * 4), kv.data(), kv.size() * 8);
+    const double vu[2] = {varU0, 0.0};
+    auto undo = [&](int code) { free_rand(R); return code; };
+    if ((rc = upload(h, &R.d_lptr, lp)) || (rc = upload(h, &R.d_lrows, lr)) || (rc = upload(h, &R.d_level, lv)) || (rc = upload(h, &R.d_kptr, kp)) ||
+        (rc = upload(h, &R.d_kcol, kc)) || (rc = upload(h, &R.d_kval, kv)) || (rc = upload(h, &R.d_kdiag, kd)) || (rc = upload(h, &R.d_zpz, zpz)))
+        return undo(rc);
+    if ((rc = dalloc(h, &R.d_u, (size_t)q)) || (rc = dalloc(h, &R.d_sum_u, (size_t)q)) || (rc = dalloc(h, &R.d_vu, 2)) ||
+        (rc = dalloc(h, &R.d_scr, (size_t)NGP_RS_ROWS * (size_t)q)))
+        return undo(rc);
+    hipError_t e = hipMemset(R.d_u, 0, (size_t)q * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(R.d_sum_u, 0, (size_t)q * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(R.d_scr, 0, (size_t)NGP_RS_ROWS * (size_t)q * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice);
+    if (e == hipSuccess && offdiag) e = hipFuncSetAttribute((const void *)k_rand_gs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NGP_LDS_MAX);
+    if (e != hipSuccess) { free_rand(R); return fail(h, NGP_ERR_HIP, std::string("add_random_set: ") + hipGetErrorString(e)); }
+    if (set_id) *set_id = (int32_t)h->rnd.size();
+    h->rnd.push_back(R);
+    h->nrandcol += q;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_random(ngp_handle *h, int32_t set_id, double *u, double *sum_u, double *varU, double *sum_varU) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    const HRand &R = h->rnd[(size_t)set_id];
+    HCHK(hipStreamSynchronize(h->stream));
+    double vu[2];
+    HCHK(hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost));
+    if (u) HCHK(hipMemcpy(u, R.d_u, (size_t)R.q * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_u) HCHK(hipMemcpy(sum_u, R.d_sum_u, (size_t)R.q * sizeof(double), hipMemcpyDeviceToHost));
+    if (varU) *varU = vu[0];
+    if (sum_varU) *sum_varU = vu[1];
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_random(ngp_handle *h, int32_t set_id, const double *u, const double *sum_u, double varU, double sum_varU) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    REQUIRE(std::isfinite(varU) && varU > 0.0 && std::isfinite(sum_varU), NGP_ERR_ARG, "varU must be finite and > 0, sum_varU finite");
+    const HRand &R = h->rnd[(size_t)set_id];
+    if (u) for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
+    if (sum_u) for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(sum_u[l]), NGP_ERR_ARG, "non-finite sum of a random effect");
+    HCHK(hipStreamSynchronize(h->stream));
+    const double vu[2] = {varU, sum_varU};
+    HCHK(hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice));
+    if (u) HCHK(hipMemcpy(R.d_u, u, (size_t)R.q * sizeof(double), hipMemcpyHostToDevice));
+    if (sum_u) HCHK(hipMemcpy(R.d_sum_u, sum_u, (size_t)R.q * sizeof(double), hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Fine seam of one random-effect set: sampleZ!(zSet, Z, u, ycorr, varE, varU) of src/functions.jl:92-97 on the caller's arrays (ycorr N,
+ * u q, varU one double; updated in place), keyed like ngp_sweep_set (the set's own call counter is the iteration of its draws). */
+int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *u, double *varU) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    REQUIRE(ycorr && u && varU, NGP_ERR_ARG, "null state pointer");
+    REQUIRE(std::isfinite(varE) && varE > 0.0, NGP_ERR_ARG, "varE must be finite and positive");
+    REQUIRE(std::isfinite(*varU) && *varU > 0.0, NGP_ERR_ARG, "varU must be finite and positive");
+    HRand &R = h->rnd[(size_t)set_id];
+    for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
+    const uint64_t it = ++R.fine_calls;
+    HCHK(hipStreamSynchronize(h->stream));
+    double vin[2];
+    HCHK(hipMemcpy(vin, R.d_vu, sizeof(vin), hipMemcpyDeviceToHost));
+    vin[0] = *varU;  // (the sum of varU stays)
+    HCHK(hipMemcpyAsync(h->d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
+    HCHK(hipMemcpyAsync(R.d_u, u, (size_t)R.q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(R.d_vu, vin, sizeof(vin), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->d_scal, varE);
+    launch_random(h, (int)set_id, it);
+    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, true);  // ... and back (d_ycorr is scratch here)
+    HCHK(hipMemcpyAsync(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipMemcpyAsync(u, R.d_u, (size_t)R.q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipMemcpyAsync(varU, R.d_vu, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    return check_abort(h);
     NGP_CATCH(h)
 }
 

@@ -1056,7 +1056,7 @@ __global__ __launch_bounds__(256) void k_post(int do_accum, long long P, long lo
 // class probabilities [nclass] | delta[P] as bytes.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sample_pack(unsigned char *__restrict__ rec, long long P, long long nvb, int nsets, long long nfix,
-                                                     long long nclass, long long iter, const double *__restrict__ beta,
+                                                     long long nrand, long long nclass, long long iter, const double *__restrict__ beta,
                                                      const uint8_t *__restrict__ delta, const double *__restrict__ varBeta,
                                                      const DSet *__restrict__ sets, const DScal *__restrict__ sc, const double *__restrict__ bfix,
                                                      const unsigned *__restrict__ abort_w) {
@@ -1064,7 +1064,8 @@ __global__ __launch_bounds__(256) void k_sample_pack(unsigned char *__restrict__
     long long *hd = (long long *)rec;
     double *d = (double *)rec + 1;
     if (abort_w && *abort_w != 0u) { if (k == 0) hd[0] = -1; return; }
-    double *o_fix = d + 2, *o_beta = o_fix + nfix, *o_vb = o_beta + P, *o_pi = o_vb + nvb, *o_cls = o_pi + 2 * nsets;
+    // (nrand: words of the random-effect sets between b_fixed and beta, u and varU, copied there by the caller; 0 without such sets)
+    double *o_fix = d + 2, *o_beta = o_fix + nfix + nrand, *o_vb = o_beta + P, *o_pi = o_vb + nvb, *o_cls = o_pi + 2 * nsets;
     uint8_t *o_delta = (uint8_t *)(o_cls + nclass);
     if (k == 0) {
         hd[0] = iter; d[0] = sc->varE; d[1] = sc->b;

@@ -22,6 +22,8 @@
 #define NGP_KIND_R_UNIFORM 8    // BayesR: the fresh uniform of every comparison of the class search (src/functions.jl:261)
 #define NGP_KIND_R_DIRICHLET 9  // BayesR: gamma draws of the Dirichlet (src/functions.jl:536-538)
 #define NGP_KIND_T_WISHART 11   // Tuple sets: Bartlett factor of a region's inverse-Wishart draw, (set << 40) | (region << 8) | (i << 4) | j
+#define NGP_KIND_U_NORMAL 12    // random-effect sets: the normal of a level's draw, (set << 40) | level (src/functions.jl:70)
+#define NGP_KIND_U_CHI2 13      // random-effect sets: the chi-square of varU, keyed by the set (src/functions.jl:498-501)
 
 #define NGP_GOLD 0x9E3779B97F4A7C15ULL
 

@@ -158,16 +158,22 @@ set_sample_file!(h::Handle, path::Union{AbstractString,Nothing}) =
 # f(sets, sample) for every record of the file, one record in memory at a time (a record is 9 bytes per locus)
 function foreach_sample(f, path::AbstractString)
     open(path, "r") do io
-        String(read(io, 8)) == "NGPSMP01" || error("not a sample file: $path")
+        magic = String(read(io, 8))
+        magic in ("NGPSMP01", "NGPSMP02") || error("not a sample file: $path")
         P, nvb, nsets, nfix, ncls, rec = ntuple(_ -> read(io, Int64), 6)
         sets = [ntuple(_ -> read(io, Int64), 6) for _ in 1:nsets]     # (method, K, col0, ncol, variance entries, tuple k)
-        nd = 3 + nfix + P + nvb + 2 * nsets + ncls
+        rq = magic == "NGPSMP02" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each
+        nr = sum(rq; init = 0) + length(rq)                           # u (set after set) and varU between b_fixed and beta
+        nd = 3 + nfix + nr + P + nvb + 2 * nsets + ncls
         raw = Vector{UInt8}(undef, rec)
         while !eof(io)
             readbytes!(io, raw, rec) == rec || break
             d = reinterpret(Float64, view(raw, 1:8 * nd))
-            o = 3
-            f(sets, (iter = reinterpret(Int64, view(raw, 1:8))[1], varE = d[2], b = d[3], b_fixed = d[o + 1:o + nfix],
+            ro = 3 + nfix
+            u = [d[ro + sum(rq[1:r-1]; init = 0) + 1:ro + sum(rq[1:r]; init = 0)] for r in eachindex(rq)]
+            varU = d[ro + sum(rq; init = 0) + 1:ro + nr]
+            o = 3 + nr
+            f(sets, (iter = reinterpret(Int64, view(raw, 1:8))[1], varE = d[2], b = d[3], b_fixed = d[4:3 + nfix], u = u, varU = varU,
                      beta = d[o + nfix + 1:o + nfix + P], varBeta = d[o + nfix + P + 1:o + nfix + P + nvb],
                      piHat = d[o + nfix + P + nvb + 1:o + nfix + P + nvb + 2 * nsets],
                      class_pi = d[o + nfix + P + nvb + 2 * nsets + 1:nd], delta = raw[8 * nd + 1:8 * nd + P]))
@@ -180,6 +186,57 @@ function read_sample_file(path::AbstractString)
         sets = st; push!(samples, smp)
     end
     return (sets = sets, samples = samples)
+end
+
+# (1|g) random-effect set (ngp_add_random_set): level[i] in 0..q-1 per record, K = Z.iVarStr (any AbstractMatrix) sent as CSR
+function add_random_set!(h::Handle, level::Vector{Int32}, q::Integer, K, df::Float64, scale::Float64, varU0::Float64)
+    kp = Vector{Int64}(undef, q + 1); kc = Int32[]; kv = Float64[]
+    kp[1] = 0
+    for l in 1:q                                 # row l of K, columns ascending (K is symmetric: row l == column l)
+        col = K[:, l]
+        for c in 1:q
+            col[c] == 0.0 && continue
+            push!(kc, c - 1); push!(kv, Float64(col[c]))
+        end
+        kp[l + 1] = length(kc)
+    end
+    id = Ref{Int32}(0)
+    check(h, ccall((:ngp_add_random_set, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Float64, Float64, Float64, Ref{Int32}),
+                   h.ptr, level, q, kp, kc, kv, df, scale, varU0, id))
+    return id[]
+end
+# the level of every record from the one-hot incidence Z.data (src/prepMatVec.jl:143-150); rows that are not one-hot are refused
+function random_levels(Zd::AbstractMatrix)
+    lv = Vector{Int32}(undef, size(Zd, 1))
+    for i in 1:size(Zd, 1)
+        r = findall(!iszero, Zd[i, :])
+        (length(r) == 1 && Zd[i, r[1]] == 1) || error("random effect: row $i of Z is not one-hot (random slopes stay on the reference path)")
+        lv[i] = r[1] - 1
+    end
+    return lv
+end
+function random_state(h::Handle, set_id::Integer, q::Integer)
+    u = Vector{Float64}(undef, q); su = similar(u); v = Ref{Float64}(0.0); sv = Ref{Float64}(0.0)
+    check(h, ccall((:ngp_get_random, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}), h.ptr, set_id, u, su, v, sv))
+    return (u = u, sum_u = su, varU = v[], sum_varU = sv[])
+end
+set_random!(h::Handle, set_id::Integer, u::Vector{Float64}, sum_u::Vector{Float64}, varU::Float64, sum_varU::Float64) =
+    check(h, ccall((:ngp_set_random, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Float64), h.ptr, set_id, u, sum_u, varU, sum_varU))
+
+"""
+    sampleZ!(h, set_id, zSet, Z, u, ycorr, varE, varU)
+
+Fine seam of one (1|g) set: same argument list as the reference's `functions.sampleZ!(zSet, Z, u, ycorr, varE, varU)`
+(src/functions.jl:92-97) plus the handle and the set id (from `add_random_set!`).  Mutates `u[Z[zSet].pos]`, `ycorr` and `varU[zSet]`.
+"""
+function sampleZ!(h::Handle, set_id::Integer, zSet, Z, u, ycorr::Vector{Float64}, varE::Float64, varU)
+    uv = vec(u[Z[zSet].pos])                     # 1 x q Matrix{Float64}: vec() shares the memory
+    v = Ref{Float64}(Float64(varU[zSet]))
+    check(h, ccall((:ngp_sample_random_set, LIB), Int32, (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                   h.ptr, set_id, varE, ycorr, uv, v))
+    varU[zSet] = v[]
+    return nothing
 end
 
 function class_state(h::Handle, set_id::Integer)
@@ -268,11 +325,12 @@ end
     runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut; seed=1)
 
 Coarse seam: drop-in for `samplers.runSampler!` (src/samplers.jl:23) for models made of fixed effects (intercept, covariates,
-factors, blocked groups) and Symbol marker sets with BayesPR / BayesB / BayesC / BayesR priors.  Anything else falls back to the reference sampler.
+factors, blocked groups), Symbol / Expr random effects -- (1|g) terms and PED sets, whose Ainv the reference has built -- and Symbol marker
+sets with BayesPR / BayesB / BayesC / BayesR priors.  Anything else falls back to the reference sampler.
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
                      seed::Integer=1, device::Integer=0)
-    isempty(Z) || error("random effects present: use the fine seam (NextGPHIP.sweep!) instead")
+    all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110)")
     (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
     h = Handle(device=device, seed=seed)
     E.str == "D" && set_residual_weights!(h, Vector{Float64}(E.iVarStr))   # before the panel (src/mme.jl:71-75)
@@ -311,6 +369,14 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
                        h.ptr, Xd, size(Xd, 1), size(Xd, 2), size(Xd, 1), Float64.(X[x].lhs), Float64.(X[x].rhs), Ref{Int32}(0)))
     end
     nfix = isempty(xsets) ? 0 : sum(X[x].nCol for x in xsets)
+    # random effects, after the fixed effects in the order of keys(Z) (src/samplers.jl:43-46): the level of every row from Z.data,
+    # K = Z.iVarStr (I, Ainv or inv(str), src/mme.jl:26-37), df / scale / varU as the reference set them up (src/mme.jl:255-272)
+    zsets = collect(keys(Z))
+    zids = Dict{Any,Int32}()
+    for z in zsets
+        q = size(Z[z].data, 2)
+        zids[z] = add_random_set!(h, random_levels(Z[z].data), q, Z[z].iVarStr, Float64(Z[z].df), Float64(Z[z].scale), Float64(varU[z]))
+    end
     set_y!(h, Vector{Float64}(ycorr))            # ycorr == y at this point (src/mme.jl:57)
     set_residual_prior!(h, E.df, E.scale)
     check(h, ccall((:ngp_set_intercept, LIB), Int32, (Ptr{Cvoid}, Int32), h.ptr, 0))
@@ -325,6 +391,10 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     foreach_sample(smpfile) do sinfo, smp
         open(io -> writedlm(io, smp.b_fixed'), outPut * "/bOut", "a")       # src/samplers.jl:57
         open(io -> writedlm(io, smp.varE), outPut * "/varEOut", "a")        # src/samplers.jl:58
+        for (r, z) in enumerate(zsets)                                      # src/samplers.jl:60-75
+            open(io -> writedlm(io, smp.u[r]'), outPut * "/u$(z)Out", "a")
+            open(io -> writedlm(io, smp.varU[r:r]'), outPut * "/varU$(z)Out", "a")
+        end
         c0 = 0; v0 = 0; k0 = 0
         for (k, s) in enumerate(sets)
             P = M[s].dims[2]
@@ -352,6 +422,11 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
                    h.ptr, ycorr, bet, del, vb, pih, ve, bb, it))
     check(h, ccall((:ngp_get_fixed, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}), h.ptr, bfix, sbfix, nfx))
     b[1:nfix] .= bfix[1:nfix]                    # positions follow keys(X), like X[xSet].pos (src/mme.jl:112-117)
+    for z in zsets
+        rs = random_state(h, zids[z], size(Z[z].data, 2))
+        vec(u[Z[z].pos]) .= rs.u
+        varU[z] = rs.varU
+    end
     c0 = 0; v0 = 0
     for s in sets
         P = M[s].dims[2]; nr = length(varBeta[s])
