@@ -8,13 +8,13 @@
 
 #include <algorithm>
 #include <chrono>
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -29,9 +29,49 @@ using namespace ngp;
 
 namespace {
 
+// Owning device array: move-only, the destructor frees it.  alloc() (zeroed) and alloc_raw() (not zeroed: staging buffers, sample
+// ring slots, all-reduce buffers) free the old array first.  Reads as a T * wherever a launch or a copy takes one.  This type and
+// PinnedArray are the only code of this file that allocates or frees device or pinned host memory.
+template <typename T>
+struct DevArray {
+    T *p = nullptr;
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    DevArray(DevArray &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevArray &operator=(DevArray &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevArray() { reset(); }
+    void reset() { if (p) { (void)hipFree(p); p = nullptr; } }
+    hipError_t alloc_raw(size_t n) { reset(); const hipError_t e = hipMalloc((void **)&p, n * sizeof(T)); if (e != hipSuccess) p = nullptr; return e; }
+    int alloc(ngp_handle *h, size_t n);  // n (at least 1) zeroed entries on h's stream; NGP_ERR_NOMEM / NGP_ERR_HIP through fail() (below)
+    T *get() const { return p; }
+    operator T *() const { return p; }
+};
+
+// Owning pinned host array (hipHostMalloc): the counterpart of DevArray for staging through the host
+template <typename T>
+struct PinnedArray {
+    T *p = nullptr;
+    PinnedArray() = default;
+    PinnedArray(const PinnedArray &) = delete;
+    PinnedArray &operator=(const PinnedArray &) = delete;
+    PinnedArray(PinnedArray &&o) noexcept : p(o.p) { o.p = nullptr; }
+    PinnedArray &operator=(PinnedArray &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~PinnedArray() { reset(); }
+    void reset() { if (p) { (void)hipHostFree(p); p = nullptr; } }
+    hipError_t alloc_raw(size_t n) { reset(); const hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault); if (e != hipSuccess) p = nullptr; return e; }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+};
+
+struct FileCloser {
+    void operator()(FILE *f) const { std::fclose(f); }
+};
+using File = std::unique_ptr<FILE, FileCloser>;  // a FILE * closed when it goes out of scope (release() it to check fclose)
+
 struct HFix {  // one fixed-effect set beyond the intercept
-    int64_t ncol, off;
-    double *d_X = nullptr, *d_xpx0 = nullptr, *d_xpxR = nullptr, *d_lhs0 = nullptr, *d_rhs0 = nullptr;
+    int64_t ncol = 0, off = 0;
+    DevArray<double> d_X, d_xpx0, d_xpxR, d_lhs0, d_rhs0;
 };
 
 struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled after the fixed-effect sets (src/samplers.jl:43-46)
@@ -39,19 +79,21 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     double df = 0.0, scale = 0.0, varU0 = 0.0;
     bool offdiag = false;      // K has entries off its diagonal: Gauss-Seidel (k_rand_gs); otherwise every level is drawn on its own
     uint64_t fine_calls = 0;   // ngp_sample_random_set calls (their iteration key, as ngp_sweep_set's)
-    long long *d_lptr = nullptr, *d_kptr = nullptr;  // records of level l: d_lrows[d_lptr[l] .. d_lptr[l + 1]); CSR of K
-    int *d_lrows = nullptr, *d_level = nullptr, *d_kcol = nullptr;
-    double *d_kval = nullptr, *d_kdiag = nullptr, *d_zpz = nullptr;
-    double *d_u = nullptr, *d_sum_u = nullptr;
-    double *d_vu = nullptr;    // [varU, sum_varU]
-    double *d_scr = nullptr;   // NGP_RS_ROWS x q scratch (ngp_random.h)
+    DevArray<long long> d_lptr, d_kptr;  // records of level l: d_lrows[d_lptr[l] .. d_lptr[l + 1]); CSR of K
+    DevArray<int> d_lrows, d_level, d_kcol;
+    DevArray<double> d_kval, d_kdiag, d_zpz;
+    DevArray<double> d_u, d_sum_u;
+    DevArray<double> d_vu;     // [varU, sum_varU]
+    DevArray<double> d_scr;    // NGP_RS_ROWS x q scratch (ngp_random.h)
     uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
 };
-void free_rand(HRand &r);  // (below)
 
-struct PanelMem {  // d_tiles / d_mean / d_gramx / d_mpm of one uploaded panel; handles that share it hold a reference each
-    void *tiles = nullptr, *mean = nullptr, *gramx = nullptr, *mpm = nullptr;
-    std::atomic<int> refs{1};
+// The arrays of one uploaded panel: the handles that share it (ngp_share_panel) hold a std::shared_ptr each
+struct PanelMem {
+    DevArray<float> tiles;  // fp32 tiles, or (compact storage) one byte per element behind the same pointer
+    DevArray<double> mean;  // column means, Ppad
+    DevArray<double> gramx, mpm;  // Gram window (D planes per block), x'x
+    double mpm_max = 0.0;   // max_j x_j'x_j of the panel (scale of the accumulators, k_head)
 };
 
 // Kept samples streamed to a binary file while the chain runs (ngp_set_sample_file): a ring of NSLOT records on the device, copied to
@@ -59,12 +101,13 @@ struct PanelMem {  // d_tiles / d_mean / d_gramx / d_mpm of one uploaded panel; 
 // ring slot, when the writer is NSLOT samples behind.
 struct SampleStream {
     static constexpr int NSLOT = 4;
-    FILE *f = nullptr;
+    File f;
     std::string path;
     size_t rec_bytes = 0;
     bool header_written = false;
     int device = 0;
-    unsigned char *d_slot[NSLOT] = {nullptr, nullptr, nullptr, nullptr}, *h_slot[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
+    DevArray<unsigned char> d_slot[NSLOT];
+    PinnedArray<unsigned char> h_slot[NSLOT];
     hipEvent_t ev_packed[NSLOT] = {nullptr, nullptr, nullptr, nullptr}, ev_copied[NSLOT] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t copy_stream = nullptr;
     std::thread writer;
@@ -74,6 +117,7 @@ struct SampleStream {
     bool busy[NSLOT] = {false, false, false, false};
     bool stop = false, io_error = false;
     int64_t nenq = 0, nwritten = 0, ndropped = 0;
+    ~SampleStream();  // (below) joins the writer before the slots are freed
 };
 
 struct HSet {
@@ -290,6 +334,72 @@ int plan_sweep(int64_t N, int cu_count, const PlanRequest &q, SweepPlan *out, co
     return NGP_OK;
 }
 
+// The chain's arrays on one panel (sized by its N, P and plan): allocated whole by alloc_panel, dropped whole with the panel
+struct ChainMem {
+    DevArray<double> d_lhs0, d_rhs0, d_beta, d_c, d_w, d_q, d_T, d_chi;
+    DevArray<int8_t> d_setof;
+    DevArray<int32_t> d_loc, d_vbidx;
+    DevArray<uint8_t> d_delta;
+    DevArray<double> d_sum_beta, d_sum_beta2, d_sum_delta;
+    DevArray<double> d_ycorr, d_part, d_dlt;
+    DevArray<double> d_rs;  // weighted residuals: row scales s = sqrt(w) (L entries, padding rows 0); null for an unweighted handle
+    DevArray<DSet> d_sets;
+    DevArray<DScal> d_scal;
+    // persistent sweep: the dlt ring, dlt as tagged granules, and the hand-off words -- fixed-point accumulators (RING x 8 copies x
+    // 64 x 8 bytes) | dlt flag (one line) | census counters (one line) | census table (placement of each workgroup, 2 words each),
+    // all zeroed by k_prep
+    DevArray<double> d_cdlt;
+    DevArray<unsigned long long> d_cdltg;
+    DevArray<unsigned> d_ccnt;
+    size_t ccnt_words = 0;
+    size_t census_off = 0;  // word offset of the census counters inside d_ccnt
+    unsigned long long *d_census_tbl = nullptr;  // view: the census table inside d_ccnt (placement of the last launch's workgroups)
+    DevArray<unsigned> abort_mem;  // this chain's abort word (32 words)
+    unsigned *d_abort = nullptr;   // view: the abort word the launches read -- abort_mem, or a fused run's leader's (run_fused)
+    // inverse form of the linear blocks' chain (k_tinv, DESIGN.md section 2 step 5i): T per block, written before every sweep
+    DevArray<double> d_tinv;
+    int64_t tinv_blocks = 0;       // blocks d_tinv was allocated for
+    DevArray<unsigned> d_blin;     // [NBLK] 1 = linear block (static for a model and an active set: written by sync_linear_blocks)
+    int blin_for = -2;             // active set d_blin was written for (-1: the whole model, -2: stale)
+    int lin_all = 0, lin_any = 0;  // every / any block of d_blin is linear
+};
+
+// The model's arrays beyond the chain's: what a new panel discards (alloc_panel resets the whole group)
+struct ModelMem {
+    DevArray<double> d_varBeta, d_sum_varBeta;
+    int64_t vb_cap = 0;                // entries d_varBeta / d_sum_varBeta were allocated for
+    DevArray<double> d_rcls;           // BayesR per-locus class coefficients [4][NGP_RMAX][Ppad] (allocated with the first BayesR set)
+    // PR region tables
+    DevArray<DReg> d_regs;
+    DevArray<long long> d_seg_k0;
+    DevArray<int32_t> d_seg_len;
+    DevArray<int32_t> d_seg_set;       // set of every variance segment
+    DevArray<double> d_segpart, d_regchi;
+    // Tuple sets (src/functions.jl:140-154): per-set constants, coefficient rows, region tables of the inverse-Wishart draws
+    DevArray<DTup> d_tup;
+    DevArray<double> d_tupc, d_tupg, d_tsegpart;
+    DevArray<DTReg> d_tregs;
+    DevArray<long long> d_tseg_l0;
+    DevArray<int32_t> d_tseg_len, d_tseg_set;
+    std::vector<HFix> fix;             // fixed-effect sets beyond the intercept (src/functions.jl:22-53), in sampling order
+    int64_t nfixcol = 0;               // sum of ncol over them: entries of d_bfix / d_sum_bfix
+    DevArray<double> d_bfix, d_sum_bfix;
+    std::vector<HRand> rnd;            // (1|g) random-effect sets (src/functions.jl:57-110), sampled after the fixed-effect sets, in order
+    int64_t nrandcol = 0;              // sum of q over the random-effect sets
+    // optional per-iteration traces of selected effects, variances and pi (ngp_set_trace_loci)
+    DevArray<int64_t> d_trace_loci;
+    int64_t ntl = 0, ntvb = 0;
+    DevArray<double> d_tr_beta, d_tr_vb, d_tr_pi;
+    int64_t trace_ext_cap = 0;         // iterations d_tr_beta / d_tr_vb / d_tr_pi were allocated for
+};
+
+// Buffers that live as long as the handle
+struct HandleMem {
+    DevArray<double> d_tr_varE, d_tr_b;  // varE / b traces of the last run
+    int64_t trace_cap = 0;               // iterations they were allocated for
+    DevArray<unsigned long long> d_dbg;  // time stamps (ngp_debug_stamps)
+};
+
 }  // namespace
 
 struct ngp_handle {
@@ -301,61 +411,22 @@ struct ngp_handle {
     size_t lds_step = 0;
     PlanRequest req;  // how the caller wants the panel swept (its mode becomes 0 where plan_sweep falls back to mode 0)
     SweepPlan plan;   // how it is swept: plan_sweep's decision, or the owner's plan for a shared panel
-    double *d_mean = nullptr;  // compact storage: column means, Ppad
+    // device memory, by lifetime: the panel (null: no panel set), the chain's arrays on it, the model's, the handle's own
+    std::shared_ptr<PanelMem> pm;
+    ChainMem cm;
+    ModelMem mm;
+    HandleMem hm;
     bool panel_open = false;  // between ngp_begin_panel and ngp_end_panel: columns may still arrive, the Gram window does not exist yet
     int cu_count = 256;
-    double *d_cdlt = nullptr;
-    unsigned long long *d_cacc = nullptr;   // fixed-point accumulators of X_t'ycorr (inside d_ccnt: zeroed with the counters by k_prep)
-    double mpm_max = 0.0;                   // max_j x_j'x_j of the panel (scale of the accumulators, k_head)
     double setup_ms[3] = {0.0, 0.0, 0.0};   // wall time of the last panel set-up: device allocation (+ zeroing) | tiles (generation / upload) | Gram window
-    unsigned long long *d_cdltg = nullptr;  // dlt as tagged granules
     unsigned launch_seq = 0;                // launch nonce of the granule tags
-    unsigned *d_ccnt = nullptr, *d_abort = nullptr;
-    unsigned long long *d_dbg = nullptr;
-    size_t ccnt_words = 0;
-    float *d_tiles = nullptr;
-    double *d_gramx = nullptr, *d_mpm = nullptr, *d_lhs0 = nullptr, *d_rhs0 = nullptr, *d_beta = nullptr;
-    double *d_c = nullptr, *d_w = nullptr, *d_q = nullptr, *d_T = nullptr, *d_chi = nullptr;
-    // inverse form of the linear blocks' chain (k_tinv, DESIGN.md section 2 step 5i): T per block, written before every sweep
-    double *d_tinv = nullptr;
-    int64_t tinv_blocks = 0;  // blocks d_tinv was allocated for
-    unsigned *d_blin = nullptr;   // [NBLK] 1 = linear block (static for a model and an active set: written by sync_linear_blocks)
-    int blin_for = -2;            // active set d_blin was written for (-1: the whole model, -2: stale)
-    int lin_all = 0, lin_any = 0; // every / any block of d_blin is linear
     int chain_form = 0;       // ngp_set_chain_form: 0 = every block by the 64-step chain (default), 1 = linear blocks as dlt = T e0
-    int8_t *d_setof = nullptr;
-    int32_t *d_loc = nullptr, *d_vbidx = nullptr;
-    uint8_t *d_delta = nullptr;
-    double *d_sum_beta = nullptr, *d_sum_beta2 = nullptr, *d_sum_delta = nullptr;
-    double *d_ycorr = nullptr, *d_part = nullptr, *d_dlt = nullptr;
-    DSet *d_sets = nullptr;
-    DScal *d_scal = nullptr;
-    double *d_varBeta = nullptr, *d_sum_varBeta = nullptr;
-    int64_t vb_cap = 0;
-    std::vector<HFix> fix;           // fixed-effect sets beyond the intercept (src/functions.jl:22-53), in sampling order
-    std::vector<HRand> rnd;          // (1|g) random-effect sets (src/functions.jl:57-110), sampled after the fixed-effect sets, in order
-    int64_t nrandcol = 0;            // sum of q over the random-effect sets
-    int64_t nfixcol = 0;
-    double *d_bfix = nullptr, *d_sum_bfix = nullptr;
-    double *d_rcls = nullptr;        // BayesR per-locus class coefficients [4][NGP_RMAX][Ppad] (allocated with the first BayesR set)
-    int32_t *d_seg_set = nullptr;    // set of every variance segment
     std::vector<int32_t> h_seg_set;
     int64_t nclass_total = 0;        // sum of K over the BayesR sets (entries of the packed posterior)
-    // Tuple sets (src/functions.jl:140-154): per-set constants, coefficient rows, region tables of the inverse-Wishart draws
-    DTup *d_tup = nullptr;
-    double *d_tupc = nullptr, *d_tupg = nullptr, *d_tsegpart = nullptr;
-    DTReg *d_tregs = nullptr;
-    long long *d_tseg_l0 = nullptr;
-    int32_t *d_tseg_len = nullptr, *d_tseg_set = nullptr;
     std::vector<DTReg> h_tregs;
     std::vector<long long> h_tseg_l0;
     std::vector<int32_t> h_tseg_len, h_tseg_set;
     int ntuple = 0;
-    // PR region tables
-    DReg *d_regs = nullptr;
-    long long *d_seg_k0 = nullptr;
-    int32_t *d_seg_len = nullptr;
-    double *d_segpart = nullptr, *d_regchi = nullptr;
     std::vector<DReg> h_regs;
     std::vector<long long> h_seg_k0;
     std::vector<int32_t> h_seg_len;
@@ -366,18 +437,15 @@ struct ngp_handle {
     std::vector<int32_t> h_loc, h_vbidx;
     int64_t nvb = 0;
     double e_df = 4.0, e_scale = 0.0005;
-    // weighted residuals (ngp_set_residual_weights, E.str == "D"): w as given (empty = unweighted), their sum (index order) and the
-    // row scales s = sqrt(w) on the device (L entries, padding rows 0) -- null for an unweighted handle, which then runs the unweighted code
+    // weighted residuals (ngp_set_residual_weights, E.str == "D"): w as given (empty = unweighted) and their sum (index order); the
+    // row scales on the device are cm.d_rs
     std::vector<double> h_rw;
     double sum_w = 0.0;
-    double *d_rs = nullptr;
     int intercept = 1;
     int64_t chainLength = 0, burnIn = 0, thin = 1;
     int64_t iter = 0;
     bool have_y = false;
-    // traces
-    double *d_tr_varE = nullptr, *d_tr_b = nullptr;
-    int64_t ntrace = 0, trace_cap = 0;
+    int64_t ntrace = 0;  // iterations in hm.d_tr_varE / hm.d_tr_b
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double iter_ms = 0.0;
@@ -395,16 +463,8 @@ struct ngp_handle {
     int64_t last_grid = 0;       // workgroups of the last sweep launch this handle led (fused launches: K (1 + NG) + S)
     int64_t census_retries = 0;  // launches that ended at the census and were run again with the device to themselves
     int64_t dbg_census_fail_iter = 0;  // ngp_debug_fail_census: the sweep of this iteration ends at its census (once)
-    SampleStream *smp = nullptr;        // ngp_set_sample_file
-    struct PanelMem *pm = nullptr;      // the panel's device arrays (tiles, Gram window, x'x, means), shared by reference count: ngp_share_panel
+    std::unique_ptr<SampleStream> smp;  // ngp_set_sample_file
     int vdev = -1;           // ngp_debug_set_virtual_device: the device ngp_allreduce_posterior groups this handle under (-1: the real one)
-    unsigned long long *d_census_tbl = nullptr;  // placement of the workgroups of the last sweep launch (inside d_ccnt)
-    size_t census_off = 0;   // word offset of the census counters inside d_ccnt
-    // optional per-iteration traces of selected effects, variances and pi (ngp_set_trace_loci)
-    int64_t *d_trace_loci = nullptr;
-    int64_t ntl = 0, ntvb = 0;
-    double *d_tr_beta = nullptr, *d_tr_vb = nullptr, *d_tr_pi = nullptr;
-    int64_t trace_ext_cap = 0;
     std::string err;
 };
 
@@ -497,36 +557,31 @@ int enter(ngp_handle *h) {
 }
 
 template <typename T>
-int dalloc(ngp_handle *h, T **p, size_t n) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
+int DevArray<T>::alloc(ngp_handle *h, size_t n) {
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    hipError_t e = alloc_raw(std::max<size_t>(n, 1));
     if (e != hipSuccess) return fail(h, NGP_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    e = hipMemsetAsync(*p, 0, std::max<size_t>(n, 1) * sizeof(T), h->stream);
+    e = hipMemsetAsync(p, 0, bytes, h->stream);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
     return NGP_OK;
 }
-template <typename T>
-void dfree(T *&p) {
-    if (p) { (void)hipFree(p); p = nullptr; }
+
+// No panel, hence no chain arrays and no model: where a panel set-up starts (a new panel is a new model -- the fixed-effect and
+// random-effect sets hold rows of the old N, the trace selection loci of the old P) and what a failed one leaves behind
+void drop_panel(ngp_handle *h) {
+    h->pm.reset();  // (handles that share the old panel keep it alive)
+    h->cm = ChainMem();
+    h->mm = ModelMem();
+    h->sets.clear(); h->nvb = 0; h->nclass_total = 0; h->ntuple = 0;
+    h->h_setof.clear(); h->h_loc.clear(); h->h_vbidx.clear();
+    h->h_regs.clear(); h->h_seg_k0.clear(); h->h_seg_len.clear(); h->h_seg_set.clear();
+    h->h_tregs.clear(); h->h_tseg_l0.clear(); h->h_tseg_len.clear(); h->h_tseg_set.clear();
+    h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false;
 }
 
-// drop this handle's reference to its panel arrays; the last reference frees them
-void release_panel(ngp_handle *h) {
-    if (h->pm) {
-        if (h->pm->refs.fetch_sub(1) == 1) {
-            (void)hipFree(h->pm->tiles); (void)hipFree(h->pm->mean); (void)hipFree(h->pm->gramx); (void)hipFree(h->pm->mpm);
-            delete h->pm;
-        }
-        h->pm = nullptr;
-    } else {  // arrays of an allocation that failed half-way (no store yet)
-        if (h->d_tiles) (void)hipFree(h->d_tiles);
-        if (h->d_mean) (void)hipFree(h->d_mean);
-        if (h->d_gramx) (void)hipFree(h->d_gramx);
-        if (h->d_mpm) (void)hipFree(h->d_mpm);
-    }
-    h->d_tiles = nullptr; h->d_mean = nullptr; h->d_gramx = nullptr; h->d_mpm = nullptr;
-}
-
+// A new panel of N x P (owner: ngp_share_panel's, whose arrays and plan are taken as they are).  The old panel goes first, so that
+// two never coexist on the device; the new one is built aside and installed only once complete -- a set-up that fails leaves the
+// handle without a panel.
 int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr) {
     REQUIRE(N > 0 && P > 0, NGP_ERR_ARG, "panel dimensions must be positive");
     REQUIRE(N <= (int64_t)508 * 1024, NGP_ERR_ARG, "N too large for this build (max 520192)");
@@ -539,121 +594,98 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
                                                                std::to_string(N) + " rows");
         REQUIRE(h->req.storage == 0, NGP_ERR_ARG, "residual weights with compact storage (NGP_STORAGE_U8) are not supported: use fp32 tiles");
     }
-    release_panel(h);  // (handles that share the old panel keep it alive)
-    h->N = N; h->P = P;
+    drop_panel(h);
+    PlanRequest req = h->req;
+    SweepPlan plan;
     if (owner) {  // the owner's requests and plan, as they are
-        h->req = owner->req;
-        h->plan = owner->plan;
+        req = owner->req;
+        plan = owner->plan;
     } else {
         const char *msg = nullptr;
-        if (int e = plan_sweep(N, h->cu_count, h->req, &h->plan, &msg)) return fail(h, e, msg);
-        h->req.mode = h->plan.mode;  // (a panel too tall for the persistent sweep leaves the handle in mode 0)
+        if (int e = plan_sweep(N, h->cu_count, req, &plan, &msg)) return fail(h, e, msg);
+        req.mode = plan.mode;  // (a panel too tall for the persistent sweep leaves the handle in mode 0)
     }
-    h->NBLK = (P + NGP_BLK - 1) / NGP_BLK;
-    h->Ppad = h->NBLK * NGP_BLK;
-    h->L = h->plan.R * h->plan.S;
-    h->lds_step = (size_t)h->plan.R * 264 + 4096;
+    const int64_t NBLK = (P + NGP_BLK - 1) / NGP_BLK, L = plan.R * plan.S;
+    const size_t pp = (size_t)(NBLK * NGP_BLK), lds_step = (size_t)plan.R * 264 + 4096;
     int rc;
-    size_t tile_elems = (size_t)h->plan.R * NGP_BLK;
-    const size_t pp = (size_t)h->Ppad;
-    if (owner) {
-        h->d_tiles = owner->d_tiles; h->d_mean = owner->d_mean; h->d_gramx = owner->d_gramx; h->d_mpm = owner->d_mpm;
-        h->mpm_max = owner->mpm_max;
-        h->pm = owner->pm; h->pm->refs.fetch_add(1);
-    } else {
-    // column means: what the analytic centring of the compact storage uses; kept for the fp32 tiles too (ngp_get_storage: a host
-    // can then rebuild any centred row of the panel from the genotype codes)
-    if ((rc = dalloc(h, &h->d_mean, (size_t)h->Ppad))) return rc;
-    if (h->req.storage == 1) {  // one byte per element (R is a multiple of 16), held behind the same pointer
-        if ((rc = dalloc(h, &h->d_tiles, (size_t)h->NBLK * h->plan.S * tile_elems / 4))) return rc;
-    } else if ((rc = dalloc(h, &h->d_tiles, (size_t)h->NBLK * h->plan.S * tile_elems))) return rc;
-    if ((rc = dalloc(h, &h->d_gramx, (size_t)h->NBLK * h->plan.D * NGP_BLK * NGP_BLK))) return rc;
-    if ((rc = dalloc(h, &h->d_mpm, pp))) return rc;
-    h->pm = new PanelMem();
-    h->pm->tiles = h->d_tiles; h->pm->mean = h->d_mean; h->pm->gramx = h->d_gramx; h->pm->mpm = h->d_mpm;
+    std::shared_ptr<PanelMem> pm = owner ? owner->pm : std::make_shared<PanelMem>();
+    if (!owner) {
+        const size_t tile_elems = (size_t)plan.R * NGP_BLK;
+        // column means: what the analytic centring of the compact storage uses; kept for the fp32 tiles too (ngp_get_storage: a host
+        // can then rebuild any centred row of the panel from the genotype codes)
+        if ((rc = pm->mean.alloc(h, pp))) return rc;
+        if (req.storage == 1) {  // one byte per element (R is a multiple of 16), held behind the same pointer
+            if ((rc = pm->tiles.alloc(h, (size_t)NBLK * plan.S * tile_elems / 4))) return rc;
+        } else if ((rc = pm->tiles.alloc(h, (size_t)NBLK * plan.S * tile_elems))) return rc;
+        if ((rc = pm->gramx.alloc(h, (size_t)NBLK * plan.D * NGP_BLK * NGP_BLK))) return rc;
+        if ((rc = pm->mpm.alloc(h, pp))) return rc;
     }
-    if ((rc = dalloc(h, &h->d_lhs0, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_rhs0, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_beta, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_c, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_w, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_q, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_T, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_chi, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_setof, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_loc, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_vbidx, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_delta, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_sum_beta, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_sum_beta2, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_sum_delta, pp))) return rc;
-    if ((rc = dalloc(h, &h->d_ycorr, (size_t)h->L))) return rc;
-    dfree(h->d_rs);
+    ChainMem c;
+    for (DevArray<double> *a : {&c.d_lhs0, &c.d_rhs0, &c.d_beta, &c.d_c, &c.d_w, &c.d_q, &c.d_T, &c.d_chi})
+        if ((rc = a->alloc(h, pp))) return rc;
+    if ((rc = c.d_setof.alloc(h, pp))) return rc;
+    if ((rc = c.d_loc.alloc(h, pp))) return rc;
+    if ((rc = c.d_vbidx.alloc(h, pp))) return rc;
+    if ((rc = c.d_delta.alloc(h, pp))) return rc;
+    for (DevArray<double> *a : {&c.d_sum_beta, &c.d_sum_beta2, &c.d_sum_delta})
+        if ((rc = a->alloc(h, pp))) return rc;
+    if ((rc = c.d_ycorr.alloc(h, (size_t)L))) return rc;
     if (!h->h_rw.empty()) {  // row scales s_i = sqrt(w_i), before any tile is filled (the fills read them)
-        std::vector<double> rs((size_t)h->L, 0.0);
+        std::vector<double> rs((size_t)L, 0.0);
         for (int64_t i = 0; i < N; i++) rs[(size_t)i] = std::sqrt(h->h_rw[(size_t)i]);
-        if ((rc = dalloc(h, &h->d_rs, (size_t)h->L))) return rc;
-        HCHK(hipMemcpy(h->d_rs, rs.data(), rs.size() * sizeof(double), hipMemcpyHostToDevice));
+        if ((rc = c.d_rs.alloc(h, (size_t)L))) return rc;
+        HCHK(hipMemcpy(c.d_rs, rs.data(), rs.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if ((rc = dalloc(h, &h->d_part, (size_t)h->plan.S * NGP_BLK))) return rc;
-    if ((rc = dalloc(h, &h->d_dlt, NGP_BLK))) return rc;
-    if ((rc = dalloc(h, &h->d_sets, 16))) return rc;
-    if ((rc = dalloc(h, &h->d_scal, 1))) return rc;
-    HCHK(hipMemsetAsync(h->d_setof, 0xFF, pp, h->stream));
-    HCHK(hipMemsetAsync(h->d_delta, 1, pp, h->stream));
-    h->h_setof.assign(pp, -1);
-    h->h_loc.assign(pp, 0);
-    h->h_vbidx.assign(pp, 0);
-    h->sets.clear(); h->nvb = 0; h->h_regs.clear(); h->h_seg_k0.clear(); h->h_seg_len.clear(); h->h_seg_set.clear(); h->nclass_total = 0;
-    dfree(h->d_rcls);
-    dfree(h->d_tup); dfree(h->d_tupc); dfree(h->d_tupg); h->h_tregs.clear(); h->h_tseg_l0.clear(); h->h_tseg_len.clear(); h->h_tseg_set.clear(); h->ntuple = 0;
-    dfree(h->d_varBeta); dfree(h->d_sum_varBeta); h->vb_cap = 0;
-    // a new panel is a new model: the fixed-effect sets (N rows of the OLD panel) and the trace selection (loci of the old P) go
-    // with the marker sets -- k_fixed would read d_X of the old N, k_post beta[loci[k]] beyond the new P
-    for (auto &fx : h->fix) { dfree(fx.d_X); dfree(fx.d_xpx0); dfree(fx.d_xpxR); dfree(fx.d_lhs0); dfree(fx.d_rhs0); }
-    h->fix.clear(); h->nfixcol = 0; dfree(h->d_bfix); dfree(h->d_sum_bfix);
-    for (auto &r : h->rnd) free_rand(r);  // (the random-effect sets too: their records are rows of the old panel)
-    h->rnd.clear(); h->nrandcol = 0;
-    dfree(h->d_trace_loci); dfree(h->d_tr_beta); dfree(h->d_tr_vb); dfree(h->d_tr_pi);
-    h->ntl = 0; h->ntvb = 0; h->trace_ext_cap = 0;
-    h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false;
-    if (h->req.storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_step));
-    if (h->plan.mode == 1) {
+    if ((rc = c.d_part.alloc(h, (size_t)plan.S * NGP_BLK))) return rc;
+    if ((rc = c.d_dlt.alloc(h, NGP_BLK))) return rc;
+    if ((rc = c.d_sets.alloc(h, 16))) return rc;
+    if ((rc = c.d_scal.alloc(h, 1))) return rc;
+    HCHK(hipMemsetAsync(c.d_setof, 0xFF, pp, h->stream));
+    HCHK(hipMemsetAsync(c.d_delta, 1, pp, h->stream));
+    if (req.storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
+    if (plan.mode == 1) {
         // the single-chain kernels, each with the LDS this plan launches it with (k_sweep_r where that fits)
         for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::tall}) {
-            const size_t lds = sweep_lds(h->plan, k);
+            const size_t lds = sweep_lds(plan, k);
             if (lds <= NGP_LDS_MAX) HCHK(hipFuncSetAttribute(sweep_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
         // every workgroup of the persistent kernel waits for others: the whole grid must be resident at once, one workgroup
         // per CU.  Checked here, not assumed (a grid that does not fit would only show up as a spin timeout).
         int wg_per_cu = 0;
-        const SweepKernel occ = h->plan.V > 1 ? SweepKernel::tall : SweepKernel::lean;  // (at the LDS of the full kernel: the most but k_sweep_r's)
-        HCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_per_cu, sweep_kernel(occ), NGP_WG, sweep_lds(h->plan, SweepKernel::tup)));
-        const int64_t grid = sweep_grid(h->plan);
+        const SweepKernel occ = plan.V > 1 ? SweepKernel::tall : SweepKernel::lean;  // (at the LDS of the full kernel: the most but k_sweep_r's)
+        HCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_per_cu, sweep_kernel(occ), NGP_WG, sweep_lds(plan, SweepKernel::tup)));
+        const int64_t grid = sweep_grid(plan);
         if (wg_per_cu < 1 || grid > (int64_t)wg_per_cu * h->cu_count)
             return fail(h, NGP_ERR_STATE, "persistent sweep: grid of " + std::to_string(grid) + " workgroups cannot be co-resident (" +
                                               std::to_string(wg_per_cu) + " per CU x " + std::to_string(h->cu_count) + " CUs); use ngp_configure(mode 0)");
-        if ((rc = dalloc(h, &h->d_cdlt, (size_t)NGP_RING * NGP_BLK))) return rc;
-        if ((rc = dalloc(h, &h->d_cdltg, (size_t)NGP_RING * NGP_BLK * 2))) return rc;
-        // fixed-point accumulators (RING x 8 copies x 64 x 8 bytes) | dlt flag (one line) | census counters (one line) | census table
-        // (placement of each workgroup, 2 words each); all zeroed by k_prep
-        h->census_off = (size_t)NGP_RING * NGP_FX_COPIES * NGP_BLK * 2 + 32;
-        h->ccnt_words = h->census_off + 32 + 2 * (size_t)320;  // (320 >= any grid, also the fused grid of K chains per pass)
-        if ((rc = dalloc(h, &h->d_ccnt, h->ccnt_words))) return rc;
-        h->d_census_tbl = (unsigned long long *)(h->d_ccnt + h->census_off + 32);
+        if ((rc = c.d_cdlt.alloc(h, (size_t)NGP_RING * NGP_BLK))) return rc;
+        if ((rc = c.d_cdltg.alloc(h, (size_t)NGP_RING * NGP_BLK * 2))) return rc;
+        c.census_off = (size_t)NGP_RING * NGP_FX_COPIES * NGP_BLK * 2 + 32;
+        c.ccnt_words = c.census_off + 32 + 2 * (size_t)320;  // (320 >= any grid, also the fused grid of K chains per pass)
+        if ((rc = c.d_ccnt.alloc(h, c.ccnt_words))) return rc;
+        c.d_census_tbl = (unsigned long long *)(c.d_ccnt.get() + c.census_off + 32);
     }
-    if ((rc = dalloc(h, &h->d_abort, 32))) return rc;
+    if ((rc = c.abort_mem.alloc(h, 32))) return rc;
+    c.d_abort = c.abort_mem;
     HCHK(hipStreamSynchronize(h->stream));
+    // complete: install it
+    h->N = N; h->P = P; h->NBLK = NBLK; h->Ppad = (int64_t)pp; h->L = L; h->lds_step = lds_step;
+    h->req = req; h->plan = plan;
+    h->pm = std::move(pm);
+    h->cm = std::move(c);
+    h->h_setof.assign(pp, -1);
+    h->h_loc.assign(pp, 0);
+    h->h_vbidx.assign(pp, 0);
     return NGP_OK;
 }
 
 // max_j x_j'x_j: with ycorr'ycorr it bounds every X_t'ycorr (the scale of the fixed-point accumulators, k_head)
 int refresh_mpm_max(ngp_handle *h) {
     std::vector<double> m((size_t)h->Ppad);
-    HCHK(hipMemcpy(m.data(), h->d_mpm, (size_t)h->Ppad * sizeof(double), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(m.data(), h->pm->mpm, (size_t)h->Ppad * sizeof(double), hipMemcpyDeviceToHost));
     double mx = 0.0;
     for (double v : m) if (v > mx) mx = v;
-    h->mpm_max = mx;
+    h->pm->mpm_max = mx;
     return NGP_OK;
 }
 
@@ -661,8 +693,8 @@ int refresh_mpm_max(ngp_handle *h) {
 // handle's stream; dst may be src.  Unweighted handles never get here.
 void launch_rows(ngp_handle *h, double *dst, const double *src, bool descale) {
     const unsigned nb = (unsigned)((h->N + 255) / 256);
-    if (descale) hipLaunchKernelGGL(k_row_descale, dim3(nb), dim3(256), 0, h->stream, dst, src, (const double *)h->d_rs, (long long)h->N);
-    else hipLaunchKernelGGL(k_row_scale, dim3(nb), dim3(256), 0, h->stream, dst, src, (const double *)h->d_rs, (long long)h->N);
+    if (descale) hipLaunchKernelGGL(k_row_descale, dim3(nb), dim3(256), 0, h->stream, dst, src, (const double *)h->cm.d_rs, (long long)h->N);
+    else hipLaunchKernelGGL(k_row_scale, dim3(nb), dim3(256), 0, h->stream, dst, src, (const double *)h->cm.d_rs, (long long)h->N);
 }
 
 // FNV-1a over the bytes of the weights: what a snapshot of a weighted chain records of them (ngp_save_snapshot)
@@ -677,20 +709,19 @@ int build_gram8(ngp_handle *h) {  // compact storage: exact integer dot products
     const size_t per_block = (size_t)h->plan.S * NGP_BLK * NGP_BLK * sizeof(uint32_t);
     int nb_max = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->NBLK, ((size_t)1 << 30) / per_block));
     nb_max = std::min(nb_max, 32768);
-    uint32_t *d_gpart = nullptr;
+    DevArray<uint32_t> d_gpart;
     int rc;
-    if ((rc = dalloc(h, &d_gpart, (size_t)nb_max * h->plan.S * NGP_BLK * NGP_BLK))) return rc;
+    if ((rc = d_gpart.alloc(h, (size_t)nb_max * h->plan.S * NGP_BLK * NGP_BLK))) return rc;
     for (int d = 0; d < h->plan.D; d++)
         for (int64_t t0 = 0; t0 < h->NBLK; t0 += nb_max) {
             int nb = (int)std::min<int64_t>(nb_max, h->NBLK - t0);
-            hipLaunchKernelGGL(k_gram8_part, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, (const uint8_t *)h->d_tiles, d_gpart,
+            hipLaunchKernelGGL(k_gram8_part, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, (const uint8_t *)h->pm->tiles.get(), d_gpart,
                                (int)h->plan.R, (int)h->plan.S, (int)t0, d);
             long long ne = (long long)nb * NGP_BLK * NGP_BLK;
-            hipLaunchKernelGGL(k_gram8_reduce, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, d_gpart, h->d_gramx, h->d_mpm,
-                               h->d_mean, (long long)h->N, (int)h->plan.S, (int)t0, nb, d, h->plan.D);
+            hipLaunchKernelGGL(k_gram8_reduce, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, d_gpart, h->pm->gramx, h->pm->mpm,
+                               h->pm->mean, (long long)h->N, (int)h->plan.S, (int)t0, nb, d, h->plan.D);
         }
     hipError_t e = hipStreamSynchronize(h->stream);
-    dfree(d_gpart);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("gram: ") + hipGetErrorString(e));
     e = hipGetLastError();
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("gram launch: ") + hipGetErrorString(e));
@@ -703,24 +734,23 @@ int build_gram(ngp_handle *h) {
     const size_t per_block = (size_t)h->plan.S * NGP_BLK * NGP_BLK * sizeof(double);
     int nb_max = (int)std::max<size_t>(1, std::min<size_t>((size_t)h->NBLK, ((size_t)1 << 30) / per_block));
     nb_max = std::min(nb_max, 32768);
-    double *d_gpart = nullptr;
+    DevArray<double> d_gpart;
     int rc;
-    if ((rc = dalloc(h, &d_gpart, (size_t)nb_max * h->plan.S * NGP_BLK * NGP_BLK))) return rc;
+    if ((rc = d_gpart.alloc(h, (size_t)nb_max * h->plan.S * NGP_BLK * NGP_BLK))) return rc;
     for (int d = 0; d < h->plan.D; d++)
         for (int64_t t0 = 0; t0 < h->NBLK; t0 += nb_max) {
             int nb = (int)std::min<int64_t>(nb_max, h->NBLK - t0);
             if (h->gram_engine == 0)  // fp64 VALU contraction: the default (1.63 ms per launch at 50k x 600k against 1.84 on the matrix cores)
-                hipLaunchKernelGGL(k_gram_part, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_gpart, (int)h->plan.R,
+                hipLaunchKernelGGL(k_gram_part, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->pm->tiles, d_gpart, (int)h->plan.R,
                                    (int)h->plan.S, (int)t0, d);
             else                      // matrix cores (ngp_debug_set_knob bit 10 before the panel is set): v_mfma_f64_16x16x4_f64, the same sums in the same order
-                hipLaunchKernelGGL(k_gram_part_mfma, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_gpart, (int)h->plan.R,
+                hipLaunchKernelGGL(k_gram_part_mfma, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->pm->tiles, d_gpart, (int)h->plan.R,
                                    (int)h->plan.S, (int)t0, d);
             long long ne = (long long)nb * NGP_BLK * NGP_BLK;
-            hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, d_gpart, h->d_gramx, h->d_mpm,
+            hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, d_gpart, h->pm->gramx, h->pm->mpm,
                                (int)h->plan.S, (int)t0, nb, d, h->plan.D);
         }
     hipError_t e = hipStreamSynchronize(h->stream);
-    dfree(d_gpart);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("gram: ") + hipGetErrorString(e));
     e = hipGetLastError();
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("gram launch: ") + hipGetErrorString(e));
@@ -741,7 +771,7 @@ template <typename TIn>
 int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64_t ld, int centre) {
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->panel_open && h->d_tiles != nullptr, NGP_ERR_STATE, "ngp_panel_columns_* needs an open panel (ngp_begin_panel)");
+    REQUIRE(h->panel_open && h->pm, NGP_ERR_STATE, "ngp_panel_columns_* needs an open panel (ngp_begin_panel)");
     REQUIRE(M != nullptr, NGP_ERR_ARG, "null panel pointer");
     REQUIRE(ld >= h->N, NGP_ERR_ARG, "leading dimension smaller than N");
     REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "column range outside the panel");
@@ -749,34 +779,32 @@ int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64
             "compact storage takes genotype codes: ngp_panel_columns_u8, ngp_set_panel_u8, ngp_load_panel_file or ngp_generate_panel");
     const int64_t N = h->N;
     const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, ((int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
-    TIn *d_g = nullptr;
-    unsigned *d_bad = nullptr;
-    if (hipMalloc((void **)&d_g, (size_t)cchunk * ld * sizeof(TIn)) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
-    if ((rc = dalloc(h, &d_bad, 1))) { (void)hipFree(d_g); return rc; }
+    DevArray<TIn> d_g;
+    DevArray<unsigned> d_bad;
+    if (d_g.alloc_raw((size_t)cchunk * ld) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
+    if ((rc = d_bad.alloc(h, 1))) return rc;
     hipError_t e = hipSuccess;
     for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += cchunk) {
         const int64_t nc = std::min<int64_t>(cchunk, ncol - c0);
         // the last column may be shorter than ld in the caller's buffer: nc - 1 full columns + N elements
         e = hipMemcpyAsync(d_g, M + (size_t)c0 * ld, ((size_t)(nc - 1) * ld + (size_t)N) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
         if (e != hipSuccess) break;
-        double *d_mu = h->d_mean + col0 + c0;
+        double *d_mu = h->pm->mean + col0 + c0;
         hipLaunchKernelGGL(k_cols_mean<TIn>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, h->stream, (const TIn *)d_g, (long long)N, (long long)ld,
                            (long long)nc, centre, d_mu, d_bad);
         if constexpr (sizeof(TIn) == 1) {
             if (h->req.storage == 1)  // the codes stay codes (the means are what the analytic centring uses)
-                hipLaunchKernelGGL(k_cols_fill8, dim3((unsigned)((h->L / 16 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles,
+                hipLaunchKernelGGL(k_cols_fill8, dim3((unsigned)((h->L / 16 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, (uint8_t *)h->pm->tiles.get(),
                                    (const uint8_t *)d_g, (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->plan.R, (int)h->plan.S);
         }
         if (h->req.storage == 0)
-        hipLaunchKernelGGL(k_cols_fill<TIn>, dim3((unsigned)((h->L / 4 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, h->d_tiles, (const TIn *)d_g,
+        hipLaunchKernelGGL(k_cols_fill<TIn>, dim3((unsigned)((h->L / 4 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, h->pm->tiles, (const TIn *)d_g,
                            (long long)N, (long long)ld, (long long)(col0 + c0), (int)h->plan.R, (int)h->plan.S, (const double *)d_mu,
-                           (const double *)h->d_rs);
+                           (const double *)h->cm.d_rs);
         e = hipStreamSynchronize(h->stream);  // the staging buffer is reused by the next chunk
     }
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost);
-    (void)hipFree(d_g);
-    dfree(d_bad);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("panel columns: ") + hipGetErrorString(e));
     REQUIRE(bad == 0u, NGP_ERR_ARG, "non-finite genotype value in panel");
     return NGP_OK;
@@ -785,7 +813,7 @@ int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64
 int end_panel(ngp_handle *h) {
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->panel_open && h->d_tiles != nullptr, NGP_ERR_STATE, "no open panel (ngp_begin_panel)");
+    REQUIRE(h->panel_open && h->pm, NGP_ERR_STATE, "no open panel (ngp_begin_panel)");
     h->panel_open = false;
     return build_gram(h);
 }
@@ -813,8 +841,8 @@ bool wants_tinv(const ngp_handle *h) {
 // one: those lanes are inactive): their chain takes the inverse form (k_tinv).  Static for a model; the table goes to the device when
 // the model or the active set changed.  A Tuple set owns its blocks to the end of the last one (ncol = its span).
 int sync_linear_blocks(ngp_handle *h, int active_set) {
-    if (!wants_tinv(h) || h->tinv_blocks != h->NBLK) { h->lin_all = 0; h->lin_any = 0; return NGP_OK; }
-    if (h->blin_for == active_set) return NGP_OK;
+    if (!wants_tinv(h) || h->cm.tinv_blocks != h->NBLK) { h->cm.lin_all = 0; h->cm.lin_any = 0; return NGP_OK; }
+    if (h->cm.blin_for == active_set) return NGP_OK;
     // 1 = BayesPR / unowned / inactive lanes only; 1 + k = a block of a k-set Tuple (its chain is linear too: one step per locus);
     // 0 = a lane of BayesB / BayesC / BayesR: the step chains
     std::vector<unsigned> bl((size_t)h->NBLK, 1u);
@@ -826,50 +854,50 @@ int sync_linear_blocks(ngp_handle *h, int active_set) {
     }
     int64_t n1 = 0, nany = 0;
     for (unsigned v : bl) { n1 += (v == 1u); nany += (v != 0u); }
-    h->lin_all = (n1 == h->NBLK) ? 1 : 0;
-    h->lin_any = (nany > 0) ? 1 : 0;
-    HCHK(hipMemcpyAsync(h->d_blin, bl.data(), (size_t)h->NBLK * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    h->cm.lin_all = (n1 == h->NBLK) ? 1 : 0;
+    h->cm.lin_any = (nany > 0) ? 1 : 0;
+    HCHK(hipMemcpyAsync(h->cm.d_blin, bl.data(), (size_t)h->NBLK * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
     HCHK(hipStreamSynchronize(h->stream));  // (bl is a local)
-    h->blin_for = active_set;
+    h->cm.blin_for = active_set;
     return NGP_OK;
 }
 
 int sync_tables(ngp_handle *h) {
     int rc;
-    if (wants_tinv(h) && h->tinv_blocks != h->NBLK) {
-        if ((rc = dalloc(h, &h->d_tinv, (size_t)h->NBLK * NGP_BLK * NGP_BLK))) return rc;
-        if ((rc = dalloc(h, &h->d_blin, (size_t)h->NBLK))) return rc;
-        h->tinv_blocks = h->NBLK;
-        h->blin_for = -2;
+    if (wants_tinv(h) && h->cm.tinv_blocks != h->NBLK) {
+        if ((rc = h->cm.d_tinv.alloc(h, (size_t)h->NBLK * NGP_BLK * NGP_BLK))) return rc;
+        if ((rc = h->cm.d_blin.alloc(h, (size_t)h->NBLK))) return rc;
+        h->cm.tinv_blocks = h->NBLK;
+        h->cm.blin_for = -2;
     }
-    if (h->tables_dirty) h->blin_for = -2;
+    if (h->tables_dirty) h->cm.blin_for = -2;
     if (!h->tables_dirty) return NGP_OK;
     const size_t pp = (size_t)h->Ppad;
-    HCHK(hipMemcpy(h->d_setof, h->h_setof.data(), pp, hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->d_loc, h->h_loc.data(), pp * sizeof(int32_t), hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->d_vbidx, h->h_vbidx.data(), pp * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = dalloc(h, &h->d_regs, h->h_regs.size()))) return rc;
-    if ((rc = dalloc(h, &h->d_seg_k0, h->h_seg_k0.size()))) return rc;
-    if ((rc = dalloc(h, &h->d_seg_len, h->h_seg_len.size()))) return rc;
-    if ((rc = dalloc(h, &h->d_segpart, h->h_seg_k0.size()))) return rc;
-    if ((rc = dalloc(h, &h->d_seg_set, h->h_seg_set.size()))) return rc;
-    if ((rc = dalloc(h, &h->d_regchi, h->h_regs.size()))) return rc;
+    HCHK(hipMemcpy(h->cm.d_setof, h->h_setof.data(), pp, hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_loc, h->h_loc.data(), pp * sizeof(int32_t), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_vbidx, h->h_vbidx.data(), pp * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = h->mm.d_regs.alloc(h, h->h_regs.size()))) return rc;
+    if ((rc = h->mm.d_seg_k0.alloc(h, h->h_seg_k0.size()))) return rc;
+    if ((rc = h->mm.d_seg_len.alloc(h, h->h_seg_len.size()))) return rc;
+    if ((rc = h->mm.d_segpart.alloc(h, h->h_seg_k0.size()))) return rc;
+    if ((rc = h->mm.d_seg_set.alloc(h, h->h_seg_set.size()))) return rc;
+    if ((rc = h->mm.d_regchi.alloc(h, h->h_regs.size()))) return rc;
     if (!h->h_regs.empty()) {
-        HCHK(hipMemcpy(h->d_regs, h->h_regs.data(), h->h_regs.size() * sizeof(DReg), hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->d_seg_k0, h->h_seg_k0.data(), h->h_seg_k0.size() * sizeof(long long), hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->d_seg_len, h->h_seg_len.data(), h->h_seg_len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->d_seg_set, h->h_seg_set.data(), h->h_seg_set.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_regs, h->h_regs.data(), h->h_regs.size() * sizeof(DReg), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_seg_k0, h->h_seg_k0.data(), h->h_seg_k0.size() * sizeof(long long), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_seg_len, h->h_seg_len.data(), h->h_seg_len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_seg_set, h->h_seg_set.data(), h->h_seg_set.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     if (!h->h_tregs.empty()) {
-        if ((rc = dalloc(h, &h->d_tregs, h->h_tregs.size()))) return rc;
-        if ((rc = dalloc(h, &h->d_tseg_l0, h->h_tseg_l0.size()))) return rc;
-        if ((rc = dalloc(h, &h->d_tseg_len, h->h_tseg_len.size()))) return rc;
-        if ((rc = dalloc(h, &h->d_tseg_set, h->h_tseg_set.size()))) return rc;
-        if ((rc = dalloc(h, &h->d_tsegpart, h->h_tseg_l0.size() * NGP_TPAIRS))) return rc;
-        HCHK(hipMemcpy(h->d_tregs, h->h_tregs.data(), h->h_tregs.size() * sizeof(DTReg), hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->d_tseg_l0, h->h_tseg_l0.data(), h->h_tseg_l0.size() * sizeof(long long), hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->d_tseg_len, h->h_tseg_len.data(), h->h_tseg_len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->d_tseg_set, h->h_tseg_set.data(), h->h_tseg_set.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if ((rc = h->mm.d_tregs.alloc(h, h->h_tregs.size()))) return rc;
+        if ((rc = h->mm.d_tseg_l0.alloc(h, h->h_tseg_l0.size()))) return rc;
+        if ((rc = h->mm.d_tseg_len.alloc(h, h->h_tseg_len.size()))) return rc;
+        if ((rc = h->mm.d_tseg_set.alloc(h, h->h_tseg_set.size()))) return rc;
+        if ((rc = h->mm.d_tsegpart.alloc(h, h->h_tseg_l0.size() * NGP_TPAIRS))) return rc;
+        HCHK(hipMemcpy(h->mm.d_tregs, h->h_tregs.data(), h->h_tregs.size() * sizeof(DTReg), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_tseg_l0, h->h_tseg_l0.data(), h->h_tseg_l0.size() * sizeof(long long), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_tseg_len, h->h_tseg_len.data(), h->h_tseg_len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.d_tseg_set, h->h_tseg_set.data(), h->h_tseg_set.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     h->tables_dirty = false;
     return NGP_OK;
@@ -883,27 +911,27 @@ bool is_kept(const ngp_handle *h, int64_t it) {  // src/samplers.jl:26
 // launch arguments of the persistent sweep over blocks [tb0, tb1) of this handle's chain (advances the launch nonce)
 void fill_sweep_args(ngp_handle *h, int64_t tb0, int64_t tb1, SweepArgs &A) {
     const int R = (int)h->plan.R, S = (int)h->plan.S;
-    A.tiles = h->d_tiles; A.ycorr = h->d_ycorr; A.gramx = h->d_gramx;
-    const bool tf = wants_tinv(h) && h->tinv_blocks == h->NBLK;
-    A.tinv = (tf && h->lin_any) ? h->d_tinv : nullptr;
-    A.blin = (tf && h->lin_any) ? h->d_blin : nullptr;
-    A.lin_all = (tf && h->lin_any) ? h->lin_all : 0;
+    A.tiles = h->pm->tiles; A.ycorr = h->cm.d_ycorr; A.gramx = h->pm->gramx;
+    const bool tf = wants_tinv(h) && h->cm.tinv_blocks == h->NBLK;
+    A.tinv = (tf && h->cm.lin_any) ? h->cm.d_tinv : nullptr;
+    A.blin = (tf && h->cm.lin_any) ? h->cm.d_blin : nullptr;
+    A.lin_all = (tf && h->cm.lin_any) ? h->cm.lin_all : 0;
     A.V = h->plan.V; A.D = h->plan.D; A.R = R; A.S = S; A.NG = h->plan.NG; A.near = h->plan.near; A.fine_ok = 0; A.t0 = (int)tb0; A.t1 = (int)tb1;
-    A.beta = h->d_beta; A.delta = h->d_delta; A.c = h->d_c; A.w = h->d_w; A.q = h->d_q; A.mpm = h->d_mpm; A.chi = h->d_chi;
-    A.setof = h->d_setof; A.vbidx = h->d_vbidx; A.sets = h->d_sets; A.varBeta = h->d_varBeta;
-    A.rcls = h->d_rcls; A.rhs0 = h->d_rhs0; A.scal = h->d_scal; A.Ppad = h->Ppad;
-    A.tup = h->ntuple ? h->d_tup : nullptr; A.tupc = h->d_tupc; A.tupg = h->d_tupg;
-    A.acc = (unsigned long long *)h->d_ccnt; A.dlt = h->d_cdlt; A.dltg = h->d_cdltg;
+    A.beta = h->cm.d_beta; A.delta = h->cm.d_delta; A.c = h->cm.d_c; A.w = h->cm.d_w; A.q = h->cm.d_q; A.mpm = h->pm->mpm; A.chi = h->cm.d_chi;
+    A.setof = h->cm.d_setof; A.vbidx = h->cm.d_vbidx; A.sets = h->cm.d_sets; A.varBeta = h->mm.d_varBeta;
+    A.rcls = h->mm.d_rcls; A.rhs0 = h->cm.d_rhs0; A.scal = h->cm.d_scal; A.Ppad = h->Ppad;
+    A.tup = h->ntuple ? h->mm.d_tup : nullptr; A.tupc = h->mm.d_tupc; A.tupg = h->mm.d_tupg;
+    A.acc = (unsigned long long *)h->cm.d_ccnt.get(); A.dlt = h->cm.d_cdlt; A.dltg = h->cm.d_cdltg;
     h->launch_seq = (h->launch_seq % 4095u) + 1u;  // 1..4095: never the zero the ring is born with
     A.nonce = h->launch_seq;
-    A.flag_dlt = h->d_ccnt + (size_t)NGP_RING * NGP_FX_COPIES * NGP_BLK * 2; A.abort_w = h->d_abort; A.xcc_w = h->d_abort + 16;
-    A.census = (h->dbg_mode == 0) ? h->d_ccnt + h->census_off : nullptr;  // timing modes leave roles out: no census there
-    A.census_tbl = h->d_census_tbl; A.iter_tag = (unsigned)(h->iter + 1);
+    A.flag_dlt = h->cm.d_ccnt + (size_t)NGP_RING * NGP_FX_COPIES * NGP_BLK * 2; A.abort_w = h->cm.d_abort; A.xcc_w = h->cm.d_abort + 16;
+    A.census = (h->dbg_mode == 0) ? h->cm.d_ccnt + h->cm.census_off : nullptr;  // timing modes leave roles out: no census there
+    A.census_tbl = h->cm.d_census_tbl; A.iter_tag = (unsigned)(h->iter + 1);
     A.census_fail = (h->dbg_census_fail_iter > 0 && !h->exclusive) ? (unsigned)h->dbg_census_fail_iter : 0u;
-    A.dbg = h->d_dbg;
+    A.dbg = h->hm.d_dbg;
     A.fine_ok = (streamer_lds(h->plan, 1) + 8192 <= sweep_lds(h->plan, SweepKernel::diag)) ? 1 : 0;  // diagnostic timeline fits in LDS
     A.variant = h->plan.streamer; A.knob = h->knob;
-    A.mean = h->d_mean; A.N = h->N;
+    A.mean = h->pm->mean; A.N = h->N;
     A.dbg_mode = h->dbg_mode;
 }
 
@@ -914,7 +942,7 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
         // (the hand-off counters were zeroed by k_prep, which precedes every sweep in the stream)
         SweepArgs A;
         fill_sweep_args(h, tb0, tb1, A);
-        const SweepKernel k = pick_kernel(h->plan, 1, h->d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0);
+        const SweepKernel k = pick_kernel(h->plan, 1, h->hm.d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0);
         h->last_grid = sweep_grid(h->plan);
         if (evs) (void)hipEventRecord(evs[0], h->stream);
         launch_sweep_kernel(k, h->last_grid, sweep_lds(h->plan, k), h->stream, &A);
@@ -926,14 +954,14 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
     for (int64_t t = tb0; t <= tb1; t++) {
         const int do_upd = t > tb0, do_gemv = t < tb1;
         if (evs && do_gemv) (void)hipEventRecord(evs[e++], h->stream);
-        hipLaunchKernelGGL(k_step, dim3((unsigned)S), dim3(256), h->lds_step, h->stream, h->d_tiles, h->d_ycorr, h->d_dlt, h->d_part, R,
+        hipLaunchKernelGGL(k_step, dim3((unsigned)S), dim3(256), h->lds_step, h->stream, h->pm->tiles, h->cm.d_ycorr, h->cm.d_dlt, h->cm.d_part, R,
                            S, (int)t, do_upd, do_gemv);
         if (evs && do_gemv) (void)hipEventRecord(evs[e++], h->stream);
         if (do_gemv)
-            hipLaunchKernelGGL(k_recur, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_gramx, h->plan.D, S, (int)t, h->d_beta, h->d_delta,
-                               h->d_c, h->d_w, h->d_q, h->d_mpm, h->d_chi, h->d_setof, h->d_vbidx, h->d_sets, h->d_varBeta, h->d_dlt, h->d_rcls,
-                               (long long)h->Ppad, h->d_rhs0, h->d_scal, h->d_tup, h->d_tupc, h->d_tupg,
-                               (const double *)((wants_tinv(h) && h->tinv_blocks == h->NBLK && h->lin_any) ? h->d_tinv : nullptr), (const unsigned *)h->d_blin);
+            hipLaunchKernelGGL(k_recur, dim3(1), dim3(256), 0, h->stream, h->cm.d_part, h->pm->gramx, h->plan.D, S, (int)t, h->cm.d_beta, h->cm.d_delta,
+                               h->cm.d_c, h->cm.d_w, h->cm.d_q, h->pm->mpm, h->cm.d_chi, h->cm.d_setof, h->cm.d_vbidx, h->cm.d_sets, h->mm.d_varBeta, h->cm.d_dlt, h->mm.d_rcls,
+                               (long long)h->Ppad, h->cm.d_rhs0, h->cm.d_scal, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg,
+                               (const double *)((wants_tinv(h) && h->cm.tinv_blocks == h->NBLK && h->cm.lin_any) ? h->cm.d_tinv : nullptr), (const unsigned *)h->cm.d_blin);
     }
     h->sweep_launches += 2 * (tb1 - tb0) + 1;
 }
@@ -942,7 +970,7 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
 std::string census_report(ngp_handle *h) {
     const size_t grid = (size_t)(h->last_grid > 0 ? h->last_grid : sweep_grid(h->plan));
     std::vector<unsigned long long> tb(grid, 0ull);
-    if (!h->d_census_tbl || hipMemcpy(tb.data(), h->d_census_tbl, grid * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return "(no census)";
+    if (!h->cm.d_census_tbl || hipMemcpy(tb.data(), h->cm.d_census_tbl, grid * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return "(no census)";
     int per_xcc[16] = {0}, per_se[16][8] = {{0}};
     size_t arrived = 0;
     std::string missing;
@@ -968,9 +996,9 @@ std::string census_report(ngp_handle *h) {
 int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
     if (h->plan.mode != 1) return NGP_OK;
     unsigned w[2] = {0, 0};
-    HCHK(hipMemcpy(w, h->d_abort, sizeof(w), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(w, h->cm.d_abort, sizeof(w), hipMemcpyDeviceToHost));
     if (w[0] == 0) return NGP_OK;
-    (void)hipMemset(h->d_abort, 0, sizeof(w));
+    (void)hipMemset(h->cm.d_abort, 0, sizeof(w));
     if (w[0] == NGP_ABORT_CENSUS && iter_failed && !h->exclusive) {
         // iter_tag holds the low 32 bits of the iteration: the launches in flight are at most 16 iterations ahead of it
         const int64_t base = (h->iter + 1) & ~(int64_t)0xFFFFFFFF;
@@ -994,23 +1022,23 @@ int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
 void launch_variance(ngp_handle *h, int active_set, uint64_t it) {
     const long long nseg = (long long)h->h_seg_k0.size(), nreg = (long long)h->h_regs.size();
     if (nseg > 0) {
-        hipLaunchKernelGGL(k_regssq, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, h->stream, nseg, h->d_seg_k0, h->d_seg_len,
-                           h->d_beta, h->d_segpart, h->d_abort);
+        hipLaunchKernelGGL(k_regssq, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, h->stream, nseg, h->mm.d_seg_k0, h->mm.d_seg_len,
+                           h->cm.d_beta, h->mm.d_segpart, h->cm.d_abort);
         if (h->nclass_total > 0)
-            hipLaunchKernelGGL(k_rssq, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, h->stream, nseg, h->d_seg_k0, h->d_seg_len, h->d_seg_set,
-                               h->d_sets, h->d_beta, h->d_delta, h->d_segpart, h->d_abort);
-        hipLaunchKernelGGL(k_regdraw, dim3((unsigned)((nreg + 63) / 64)), dim3(64), 0, h->stream, nreg, h->d_regs, h->d_segpart,
-                           h->d_sets, h->d_varBeta, active_set, h->d_regchi, h->seed, (uint64_t)h->chain, it, h->d_abort);
+            hipLaunchKernelGGL(k_rssq, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, h->stream, nseg, h->mm.d_seg_k0, h->mm.d_seg_len, h->mm.d_seg_set,
+                               h->cm.d_sets, h->cm.d_beta, h->cm.d_delta, h->mm.d_segpart, h->cm.d_abort);
+        hipLaunchKernelGGL(k_regdraw, dim3((unsigned)((nreg + 63) / 64)), dim3(64), 0, h->stream, nreg, h->mm.d_regs, h->mm.d_segpart,
+                           h->cm.d_sets, h->mm.d_varBeta, active_set, h->mm.d_regchi, h->seed, (uint64_t)h->chain, it, h->cm.d_abort);
     }
     if (!h->h_tregs.empty()) {  // Tuple sets: Sb = B_r'B_r per region, then the inverse-Wishart draw of its variance matrix
         const long long ntseg = (long long)h->h_tseg_l0.size(), ntreg = (long long)h->h_tregs.size();
-        hipLaunchKernelGGL(k_tuple_ssq, dim3((unsigned)((ntseg + 3) / 4)), dim3(256), 0, h->stream, ntseg, h->d_tseg_l0, h->d_tseg_len, h->d_tseg_set,
-                           h->d_tup, h->d_beta, h->d_tsegpart, h->d_abort);
-        hipLaunchKernelGGL(k_tuple_draw, dim3((unsigned)((ntreg + 63) / 64)), dim3(64), 0, h->stream, ntreg, h->d_tregs, h->d_tsegpart, h->d_tup,
-                           h->d_varBeta, active_set, h->seed, (uint64_t)h->chain, it, h->d_abort);
+        hipLaunchKernelGGL(k_tuple_ssq, dim3((unsigned)((ntseg + 3) / 4)), dim3(256), 0, h->stream, ntseg, h->mm.d_tseg_l0, h->mm.d_tseg_len, h->mm.d_tseg_set,
+                           h->mm.d_tup, h->cm.d_beta, h->mm.d_tsegpart, h->cm.d_abort);
+        hipLaunchKernelGGL(k_tuple_draw, dim3((unsigned)((ntreg + 63) / 64)), dim3(64), 0, h->stream, ntreg, h->mm.d_tregs, h->mm.d_tsegpart, h->mm.d_tup,
+                           h->mm.d_varBeta, active_set, h->seed, (uint64_t)h->chain, it, h->cm.d_abort);
     }
-    hipLaunchKernelGGL(k_pidraw, dim3(1), dim3(64), 0, h->stream, (int)h->sets.size(), h->d_sets, active_set, h->seed,
-                       (uint64_t)h->chain, it, h->d_abort);
+    hipLaunchKernelGGL(k_pidraw, dim3(1), dim3(64), 0, h->stream, (int)h->sets.size(), h->cm.d_sets, active_set, h->seed,
+                       (uint64_t)h->chain, it, h->cm.d_abort);
 }
 
 // resume_mid: the head of this iteration (varE, intercept, fixed-effect sets) has run already -- its sweep ended at the census
@@ -1019,47 +1047,47 @@ int sample_enqueue(ngp_handle *h);  // (below)
 
 // T = inv(L) of every linear block from this iteration's coefficients (k_tinv; behind k_prep in the stream, in front of the sweep)
 void launch_tinv(ngp_handle *h) {  // (sync_linear_blocks has run for this call's active set)
-    if (!wants_tinv(h) || h->tinv_blocks != h->NBLK || !h->lin_any) return;
-    hipLaunchKernelGGL(k_tinv, dim3((unsigned)h->NBLK), dim3(64), 0, h->stream, (const double *)h->d_gramx, h->plan.D, (const double *)h->d_c,
-                       (const unsigned *)h->d_blin, h->d_tinv, (const unsigned *)h->d_abort, (const double *)h->d_tupc, (long long)h->Ppad);
+    if (!wants_tinv(h) || h->cm.tinv_blocks != h->NBLK || !h->cm.lin_any) return;
+    hipLaunchKernelGGL(k_tinv, dim3((unsigned)h->NBLK), dim3(64), 0, h->stream, (const double *)h->pm->gramx, h->plan.D, (const double *)h->cm.d_c,
+                       (const unsigned *)h->cm.d_blin, h->cm.d_tinv, (const unsigned *)h->cm.d_abort, (const double *)h->mm.d_tupc, (long long)h->Ppad);
 }
 
 // one random-effect set on h->stream (ngp_random.h): level sums and draws, Gauss-Seidel for a general K, ycorr update, varU
 void launch_random(ngp_handle *h, int r, uint64_t it) {
-    HRand &R = h->rnd[(size_t)r];
+    HRand &R = h->mm.rnd[(size_t)r];
     const long long q = (long long)R.q;
-    hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->d_ycorr, (const double *)h->d_rs, q,
+    hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, (const double *)h->cm.d_rs, q,
                        (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag,
                        (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr,
-                       (int)R.offdiag, (const DScal *)h->d_scal, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->d_abort);
+                       (int)R.offdiag, (const DScal *)h->cm.d_scal, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
     if (R.offdiag) {
         const int use_lds = (size_t)q * sizeof(double) <= NGP_LDS_MAX;
         hipLaunchKernelGGL(k_rand_gs, dim3(1), dim3(64), use_lds ? (size_t)q * sizeof(double) : 0, h->stream, q, (const long long *)R.d_kptr,
-                           (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr, use_lds, (const unsigned *)h->d_abort);
+                           (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr, use_lds, (const unsigned *)h->cm.d_abort);
     }
-    hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->d_ycorr, (const double *)h->d_rs, (long long)h->N,
-                       (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), (const unsigned *)h->d_abort);
+    hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr, (const double *)h->cm.d_rs, (long long)h->N,
+                       (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), (const unsigned *)h->cm.d_abort);
     hipLaunchKernelGGL(k_rand_var, dim3(1), dim3(1024), 0, h->stream, q, (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval,
-                       (const double *)R.d_u, R.d_vu, R.df, R.scale, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->d_abort);
+                       (const double *)R.d_u, R.d_vu, R.df, R.scale, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
 }
 
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
-    hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->L, (long long)h->N, h->d_scal, h->e_df,
-                       h->e_scale, h->intercept, 1, h->seed, (uint64_t)h->chain, it, h->d_tr_varE, h->d_tr_b, (long long)trace_idx, h->d_abort, h->mpm_max,
-                       (const double *)h->d_rs, h->sum_w);
-    for (size_t f = 0; f < h->fix.size(); f++)  // the other fixed-effect sets, in the order they were added (src/samplers.jl:39-41)
-        hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->N, h->fix[f].d_X, (int)h->fix[f].ncol, h->fix[f].d_xpx0,
-                           h->fix[f].d_xpxR, h->fix[f].d_lhs0, h->fix[f].d_rhs0, h->d_bfix + h->fix[f].off, h->d_scal, (int)f, h->seed,
-                           (uint64_t)h->chain, it, h->d_abort);
-    for (size_t r = 0; r < h->rnd.size(); r++)  // the random-effect sets, in the order they were added (src/samplers.jl:43-46)
+    hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->L, (long long)h->N, h->cm.d_scal, h->e_df,
+                       h->e_scale, h->intercept, 1, h->seed, (uint64_t)h->chain, it, h->hm.d_tr_varE, h->hm.d_tr_b, (long long)trace_idx, h->cm.d_abort, h->pm->mpm_max,
+                       (const double *)h->cm.d_rs, h->sum_w);
+    for (size_t f = 0; f < h->mm.fix.size(); f++)  // the other fixed-effect sets, in the order they were added (src/samplers.jl:39-41)
+        hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->N, h->mm.fix[f].d_X, (int)h->mm.fix[f].ncol, h->mm.fix[f].d_xpx0,
+                           h->mm.fix[f].d_xpxR, h->mm.fix[f].d_lhs0, h->mm.fix[f].d_rhs0, h->mm.d_bfix + h->mm.fix[f].off, h->cm.d_scal, (int)f, h->seed,
+                           (uint64_t)h->chain, it, h->cm.d_abort);
+    for (size_t r = 0; r < h->mm.rnd.size(); r++)  // the random-effect sets, in the order they were added (src/samplers.jl:43-46)
         launch_random(h, (int)r, it);
     }
-    hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->d_setof, h->d_loc,
-                       h->d_vbidx, h->d_sets, h->d_scal, h->d_varBeta, h->d_mpm, h->d_lhs0, h->d_rhs0, h->d_beta, h->d_c, h->d_w,
-                       h->d_q, h->d_T, h->d_chi, -1, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->d_regs, h->d_regchi, h->d_rcls,
-                       h->d_ccnt, (long long)(h->plan.mode == 1 ? h->ccnt_words : 0), h->d_abort, h->d_tup, h->d_tupc, h->d_tupg);
+    hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->cm.d_setof, h->cm.d_loc,
+                       h->cm.d_vbidx, h->cm.d_sets, h->cm.d_scal, h->mm.d_varBeta, h->pm->mpm, h->cm.d_lhs0, h->cm.d_rhs0, h->cm.d_beta, h->cm.d_c, h->cm.d_w,
+                       h->cm.d_q, h->cm.d_T, h->cm.d_chi, -1, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->mm.d_regs, h->mm.d_regchi, h->mm.d_rcls,
+                       h->cm.d_ccnt, (long long)(h->plan.mode == 1 ? h->cm.ccnt_words : 0), h->cm.d_abort, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg);
     launch_tinv(h);
 }
 
@@ -1067,23 +1095,23 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
     const uint64_t it = (uint64_t)(h->iter + 1);
     launch_variance(h, -1, it);
     h->iter += 1;
-    const bool do_trace = h->d_trace_loci && trace_idx < h->trace_ext_cap, do_accum = is_kept(h, h->iter);
+    const bool do_trace = h->mm.d_trace_loci && trace_idx < h->mm.trace_ext_cap, do_accum = is_kept(h, h->iter);
     if (do_trace || do_accum) {
         long long n = 16;
-        if (do_trace) n = std::max<long long>(n, std::max<long long>(std::max<long long>(h->ntl, h->ntvb), (long long)h->sets.size()));
+        if (do_trace) n = std::max<long long>(n, std::max<long long>(std::max<long long>(h->mm.ntl, h->mm.ntvb), (long long)h->sets.size()));
         if (do_accum) n = std::max<long long>(n, std::max<long long>(h->P, h->nvb));
         hipLaunchKernelGGL(k_post, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int)do_accum, (long long)h->P, (long long)h->nvb,
-                           (int)h->sets.size(), h->d_beta, h->d_delta, h->d_varBeta, h->d_sum_beta, h->d_sum_beta2, h->d_sum_delta,
-                           h->d_sum_varBeta, h->d_sets, h->d_scal, (int)do_trace, (long long)h->ntl, (const long long *)h->d_trace_loci,
-                           (long long)h->ntvb, h->d_tr_beta, h->d_tr_vb, h->d_tr_pi, (long long)trace_idx, h->d_abort);
+                           (int)h->sets.size(), h->cm.d_beta, h->cm.d_delta, h->mm.d_varBeta, h->cm.d_sum_beta, h->cm.d_sum_beta2, h->cm.d_sum_delta,
+                           h->mm.d_sum_varBeta, h->cm.d_sets, h->cm.d_scal, (int)do_trace, (long long)h->mm.ntl, (const long long *)h->mm.d_trace_loci.get(),
+                           (long long)h->mm.ntvb, h->mm.d_tr_beta, h->mm.d_tr_vb, h->mm.d_tr_pi, (long long)trace_idx, h->cm.d_abort);
     }
     if (do_accum) {
-        if (h->nfixcol > 0)
-            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((h->nfixcol + 255) / 256)), dim3(256), 0, h->stream, (long long)h->nfixcol, h->d_bfix,
-                               h->d_sum_bfix, h->d_abort);
-        for (auto &R : h->rnd) {  // random-effect sets: u and varU (src/samplers.jl:60-75)
-            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((R.q + 255) / 256)), dim3(256), 0, h->stream, (long long)R.q, R.d_u, R.d_sum_u, h->d_abort);
-            hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, 1LL, R.d_vu, R.d_vu + 1, h->d_abort);
+        if (h->mm.nfixcol > 0)
+            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((h->mm.nfixcol + 255) / 256)), dim3(256), 0, h->stream, (long long)h->mm.nfixcol, h->mm.d_bfix,
+                               h->mm.d_sum_bfix, h->cm.d_abort);
+        for (auto &R : h->mm.rnd) {  // random-effect sets: u and varU (src/samplers.jl:60-75)
+            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((R.q + 255) / 256)), dim3(256), 0, h->stream, (long long)R.q, R.d_u, R.d_sum_u, h->cm.d_abort);
+            hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, 1LL, R.d_vu, R.d_vu + 1, h->cm.d_abort);
         }
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
@@ -1131,14 +1159,13 @@ int run_iterations(ngp_handle *h, int64_t niter, CuLease &lease, hipEvent_t *evs
 // class probabilities / their posterior sums of a BayesR set (either may be null); also clears the class counters
 int set_class_state_dev(ngp_handle *h, int si, const double *pi, const double *sum_pi) {
     const int K = h->sets[(size_t)si].K;
-    double *d = nullptr;
+    DevArray<double> d;
     int rc;
-    if ((rc = dalloc(h, &d, (size_t)2 * NGP_RMAX))) return rc;
+    if ((rc = d.alloc(h, (size_t)2 * NGP_RMAX))) return rc;
     if (pi) HCHK(hipMemcpyAsync(d, pi, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (sum_pi) HCHK(hipMemcpyAsync(d + NGP_RMAX, sum_pi, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_set_class_state, dim3(1), dim3(1), 0, h->stream, h->d_sets, si, K, pi ? d : nullptr, sum_pi ? d + NGP_RMAX : nullptr);
+    hipLaunchKernelGGL(k_set_class_state, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, K, pi ? d.get() : nullptr, sum_pi ? d + NGP_RMAX : nullptr);
     hipError_t e = hipStreamSynchronize(h->stream);
-    dfree(d);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("class state: ") + hipGetErrorString(e));
     return NGP_OK;
 }
@@ -1146,12 +1173,12 @@ int set_class_state_dev(ngp_handle *h, int si, const double *pi, const double *s
 // doubles of the packed posterior (ngp_export_posterior_device): 3P + nvb + 2 nsets + sum K + fixed-effect columns
 // (+ sum q + number of random-effect sets) + 3
 int64_t posterior_words(const ngp_handle *h) {
-    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->nfixcol + h->nrandcol + (int64_t)h->rnd.size() + 3;
+    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->mm.nfixcol + h->mm.nrandcol + (int64_t)h->mm.rnd.size() + 3;
 }
 
 // ---- sample stream (ngp_set_sample_file) ----
 size_t sample_rec_bytes(const ngp_handle *h) {
-    const size_t nd = 3 + (size_t)h->nfixcol + (size_t)(h->nrandcol + (int64_t)h->rnd.size()) + (size_t)h->P + (size_t)h->nvb + 2 * h->sets.size() +
+    const size_t nd = 3 + (size_t)h->mm.nfixcol + (size_t)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()) + (size_t)h->P + (size_t)h->nvb + 2 * h->sets.size() +
                       (size_t)h->nclass_total;
     return nd * 8 + (((size_t)h->P + 7) & ~(size_t)7);
 }
@@ -1166,9 +1193,9 @@ void sample_writer_loop(SampleStream *S) {
             slot = S->queue.front();
         }
         const bool ok = hipEventSynchronize(S->ev_copied[slot]) == hipSuccess;
-        const long long it = *(const long long *)S->h_slot[slot];
+        const long long it = *(const long long *)S->h_slot[slot].get();
         bool wrote = false, bad = !ok;
-        if (ok && it >= 0) { wrote = true; bad = std::fwrite(S->h_slot[slot], 1, S->rec_bytes, S->f) != S->rec_bytes; }
+        if (ok && it >= 0) { wrote = true; bad = std::fwrite(S->h_slot[slot], 1, S->rec_bytes, S->f.get()) != S->rec_bytes; }
         {
             std::lock_guard<std::mutex> lk(S->mu);
             S->queue.pop_front();
@@ -1179,40 +1206,33 @@ void sample_writer_loop(SampleStream *S) {
         S->cv.notify_all();
     }
 }
-void sample_close(ngp_handle *h) {
-    SampleStream *S = h->smp;
-    if (!S) return;
-    { std::lock_guard<std::mutex> lk(S->mu); S->stop = true; }
-    S->cv.notify_all();
-    if (S->writer.joinable()) S->writer.join();
-    if (S->f) std::fclose(S->f);
-    for (int i = 0; i < SampleStream::NSLOT; i++) {
-        if (S->d_slot[i]) (void)hipFree(S->d_slot[i]);
-        if (S->h_slot[i]) (void)hipHostFree(S->h_slot[i]);
-        if (S->ev_packed[i]) (void)hipEventDestroy(S->ev_packed[i]);
-        if (S->ev_copied[i]) (void)hipEventDestroy(S->ev_copied[i]);
+SampleStream::~SampleStream() {  // (the members -- ring slots, file -- are freed after this body: once the writer has stopped)
+    { std::lock_guard<std::mutex> lk(mu); stop = true; }
+    cv.notify_all();
+    if (writer.joinable()) writer.join();
+    for (int i = 0; i < NSLOT; i++) {
+        if (ev_packed[i]) (void)hipEventDestroy(ev_packed[i]);
+        if (ev_copied[i]) (void)hipEventDestroy(ev_copied[i]);
     }
-    if (S->copy_stream) (void)hipStreamDestroy(S->copy_stream);
-    delete S;
-    h->smp = nullptr;
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
 }
 // the kept sample of the iteration just enqueued on h->stream goes into the next ring slot, from there to the host on the copy stream
 int sample_enqueue(ngp_handle *h) {
-    SampleStream *S = h->smp;
+    SampleStream *S = h->smp.get();
     if (!S->header_written) {  // the model is final now: sizes and the file header
         S->rec_bytes = sample_rec_bytes(h);
         for (int i = 0; i < SampleStream::NSLOT; i++) {
-            if (hipMalloc((void **)&S->d_slot[i], S->rec_bytes) != hipSuccess || hipHostMalloc((void **)&S->h_slot[i], S->rec_bytes, hipHostMallocDefault) != hipSuccess)
+            if (S->d_slot[i].alloc_raw(S->rec_bytes) != hipSuccess || S->h_slot[i].alloc_raw(S->rec_bytes) != hipSuccess)
                 return fail(h, NGP_ERR_NOMEM, "sample ring");
         }
-        const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
+        const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->mm.nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
         // (a chain with random-effect sets: "NGPSMP02", and the header ends in int64 nrand | q per set)
-        bool ok = std::fwrite(h->rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f) == 1;
-        for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f) == 1; }
-        if (!h->rnd.empty()) {
-            const int64_t nr = (int64_t)h->rnd.size();
-            ok = ok && std::fwrite(&nr, 8, 1, S->f) == 1;
-            for (auto &R : h->rnd) ok = ok && std::fwrite(&R.q, 8, 1, S->f) == 1;
+        bool ok = std::fwrite(h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
+        for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f.get()) == 1; }
+        if (!h->mm.rnd.empty()) {
+            const int64_t nr = (int64_t)h->mm.rnd.size();
+            ok = ok && std::fwrite(&nr, 8, 1, S->f.get()) == 1;
+            for (auto &R : h->mm.rnd) ok = ok && std::fwrite(&R.q, 8, 1, S->f.get()) == 1;
         }
         if (!ok) return fail(h, NGP_ERR_ARG, "cannot write the sample file header: " + S->path);
         S->header_written = true;
@@ -1226,18 +1246,18 @@ int sample_enqueue(ngp_handle *h) {
         if (S->io_error) return fail(h, NGP_ERR_ARG, "writing the sample file failed: " + S->path);
         S->busy[slot] = true;
     }
-    const long long n = std::max<long long>(std::max<long long>(h->P, h->nvb), std::max<long long>(h->nfixcol, 1));
+    const long long n = std::max<long long>(std::max<long long>(h->P, h->nvb), std::max<long long>(h->mm.nfixcol, 1));
     hipLaunchKernelGGL(k_sample_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, S->d_slot[slot], (long long)h->P, (long long)h->nvb,
-                       (int)h->sets.size(), (long long)h->nfixcol, (long long)(h->nrandcol + (int64_t)h->rnd.size()), (long long)h->nclass_total,
-                       (long long)h->iter, h->d_beta, h->d_delta, h->d_varBeta, h->d_sets, h->d_scal, h->d_bfix, h->d_abort);
+                       (int)h->sets.size(), (long long)h->mm.nfixcol, (long long)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()), (long long)h->nclass_total,
+                       (long long)h->iter, h->cm.d_beta, h->cm.d_delta, h->mm.d_varBeta, h->cm.d_sets, h->cm.d_scal, h->mm.d_bfix, h->cm.d_abort);
     {   // random-effect sets: u (set after set), then varU of every set, behind b_fixed
-        double *o = (double *)S->d_slot[slot] + 3 + h->nfixcol;
+        double *o = (double *)S->d_slot[slot].get() + 3 + h->mm.nfixcol;
         int64_t off = 0;
         hipError_t e0 = hipSuccess;
-        for (size_t r = 0; r < h->rnd.size() && e0 == hipSuccess; r++) {
-            e0 = hipMemcpyAsync(o + off, h->rnd[r].d_u, (size_t)h->rnd[r].q * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-            if (e0 == hipSuccess) e0 = hipMemcpyAsync(o + h->nrandcol + (int64_t)r, h->rnd[r].d_vu, sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-            off += h->rnd[r].q;
+        for (size_t r = 0; r < h->mm.rnd.size() && e0 == hipSuccess; r++) {
+            e0 = hipMemcpyAsync(o + off, h->mm.rnd[r].d_u, (size_t)h->mm.rnd[r].q * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+            if (e0 == hipSuccess) e0 = hipMemcpyAsync(o + h->mm.nrandcol + (int64_t)r, h->mm.rnd[r].d_vu, sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+            off += h->mm.rnd[r].q;
         }
         if (e0 != hipSuccess) {
             { std::lock_guard<std::mutex> lk(S->mu); S->busy[slot] = false; }
@@ -1262,17 +1282,32 @@ int sample_enqueue(ngp_handle *h) {
 }
 // end of a run: every enqueued sample is in the file when the call returns
 int sample_flush(ngp_handle *h) {
-    SampleStream *S = h->smp;
+    SampleStream *S = h->smp.get();
     if (!S) return NGP_OK;
     std::unique_lock<std::mutex> lk(S->mu);
     S->cv.wait(lk, [&] { return S->queue.empty(); });
-    if (S->f) std::fflush(S->f);
+    if (S->f) std::fflush(S->f.get());
     if (S->io_error) return fail(h, NGP_ERR_ARG, "writing the sample file failed: " + S->path);
     return NGP_OK;
 }
 
+// an array and its posterior sums, grown to cap (zeroed) entries with their first n entries kept: varBeta, the fixed effects' b
+int grow_pair(ngp_handle *h, DevArray<double> &a, DevArray<double> &sum_a, int64_t n, int64_t cap) {
+    DevArray<double> na, ns;
+    int rc;
+    if ((rc = na.alloc(h, (size_t)cap))) return rc;
+    if ((rc = ns.alloc(h, (size_t)cap))) return rc;
+    if (n > 0) {
+        HCHK(hipMemcpyAsync(na, a, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HCHK(hipMemcpyAsync(ns, sum_a, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    HCHK(hipStreamSynchronize(h->stream));
+    a = std::move(na); sum_a = std::move(ns);
+    return NGP_OK;
+}
+
 int ready(ngp_handle *h) {
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: ngp_end_panel builds the Gram window the sweep needs");
     REQUIRE(h->have_y, NGP_ERR_STATE, "y not set");
     REQUIRE(!h->sets.empty(), NGP_ERR_STATE, "no marker set added");
@@ -1321,19 +1356,7 @@ int32_t ngp_destroy(ngp_handle *h) {
     if (!h) return NGP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    sample_close(h);
-    release_panel(h);
-     dfree(h->d_cdlt); dfree(h->d_cdltg); dfree(h->d_rcls); dfree(h->d_seg_set); dfree(h->d_ccnt); dfree(h->d_abort); dfree(h->d_dbg); dfree(h->d_mpm); dfree(h->d_lhs0); dfree(h->d_rhs0); dfree(h->d_beta);
-    dfree(h->d_c); dfree(h->d_w); dfree(h->d_q); dfree(h->d_T); dfree(h->d_chi); dfree(h->d_setof); dfree(h->d_loc);
-    dfree(h->d_tinv); dfree(h->d_blin);
-    dfree(h->d_vbidx); dfree(h->d_delta); dfree(h->d_sum_beta); dfree(h->d_sum_beta2); dfree(h->d_sum_delta);
-    dfree(h->d_ycorr); dfree(h->d_rs); dfree(h->d_part); dfree(h->d_dlt); dfree(h->d_sets); dfree(h->d_scal); dfree(h->d_varBeta);
-    dfree(h->d_sum_varBeta); dfree(h->d_regs); dfree(h->d_seg_k0); dfree(h->d_seg_len); dfree(h->d_segpart); dfree(h->d_regchi);
-    for (auto &fx : h->fix) { dfree(fx.d_X); dfree(fx.d_xpx0); dfree(fx.d_xpxR); dfree(fx.d_lhs0); dfree(fx.d_rhs0); }
-    dfree(h->d_bfix); dfree(h->d_sum_bfix);
-    for (auto &r : h->rnd) free_rand(r);
-    dfree(h->d_tup); dfree(h->d_tupc); dfree(h->d_tupg); dfree(h->d_tsegpart); dfree(h->d_tregs); dfree(h->d_tseg_l0); dfree(h->d_tseg_len); dfree(h->d_tseg_set);
-    dfree(h->d_tr_varE); dfree(h->d_tr_b); dfree(h->d_trace_loci); dfree(h->d_tr_beta); dfree(h->d_tr_vb); dfree(h->d_tr_pi);
+    h->smp.reset();  // (stops the sample writer; the device arrays go with the handle)
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1389,14 +1412,14 @@ static void ingest_u8_chunk(ngp_handle *h, const uint8_t *d_g, int64_t N, int64_
     const int64_t c0 = t0 * NGP_BLK;
     if (h->req.storage == 1) {  // the bytes stay bytes; the means go to the handle
         hipLaunchKernelGGL(k_u8_colmean, dim3((unsigned)ncols), dim3(256), 0, h->stream, d_g, (long long)N, (long long)ld, (int)centre,
-                           h->d_mean + c0);
-        hipLaunchKernelGGL(k_u8_fill8, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles, d_g, (long long)N,
+                           h->pm->mean + c0);
+        hipLaunchKernelGGL(k_u8_fill8, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, (uint8_t *)h->pm->tiles.get(), d_g, (long long)N,
                            (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0);
     } else {
         hipLaunchKernelGGL(k_u8_colmean, dim3((unsigned)ncols), dim3(256), 0, h->stream, d_g, (long long)N, (long long)ld, (int)centre, d_mu);
-        (void)hipMemcpyAsync(h->d_mean + c0, d_mu, (size_t)ncols * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-        hipLaunchKernelGGL(k_u8_fill, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->d_tiles, d_g, (long long)N,
-                           (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0, d_mu, (const double *)h->d_rs);
+        (void)hipMemcpyAsync(h->pm->mean + c0, d_mu, (size_t)ncols * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        hipLaunchKernelGGL(k_u8_fill, dim3((unsigned)h->plan.S, (unsigned)nb), dim3(256), 0, h->stream, h->pm->tiles, d_g, (long long)N,
+                           (long long)ld, (long long)ncols, (int)h->plan.R, (int)h->plan.S, (long long)t0, d_mu, (const double *)h->cm.d_rs);
     }
 }
 
@@ -1412,10 +1435,10 @@ int32_t ngp_set_panel_u8(ngp_handle *h, const uint8_t *G, int64_t N, int64_t P, 
     // staged through the device in chunks of whole 64-column blocks (about 64 MiB of genotypes at a time)
     const int64_t blk_bytes = (int64_t)NGP_BLK * ld;
     const int64_t nb_chunk = std::max<int64_t>(1, std::min<int64_t>(h->NBLK, ((int64_t)64 << 20) / blk_bytes));
-    uint8_t *d_g = nullptr;
-    double *d_mu = nullptr;
-    if (hipMalloc((void **)&d_g, (size_t)nb_chunk * blk_bytes) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
-    if ((rc = dalloc(h, &d_mu, (size_t)nb_chunk * NGP_BLK))) { (void)hipFree(d_g); return rc; }
+    DevArray<uint8_t> d_g;
+    DevArray<double> d_mu;
+    if (d_g.alloc_raw((size_t)nb_chunk * blk_bytes) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
+    if ((rc = d_mu.alloc(h, (size_t)nb_chunk * NGP_BLK))) return rc;
     hipError_t e = hipSuccess;
     for (int64_t t0 = 0; t0 < h->NBLK && e == hipSuccess; t0 += nb_chunk) {
         const int64_t nb = std::min<int64_t>(nb_chunk, h->NBLK - t0);
@@ -1427,8 +1450,7 @@ int32_t ngp_set_panel_u8(ngp_handle *h, const uint8_t *G, int64_t N, int64_t P, 
         ingest_u8_chunk(h, d_g, N, ld, t0, nb, ncols, centre, d_mu);
         e = hipStreamSynchronize(h->stream);  // the staging buffer is reused by the next chunk
     }
-    (void)hipFree(d_g);
-    dfree(d_mu);
+    d_g.reset(); d_mu.reset();  // (before the Gram window's scratch is allocated)
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("set_panel_u8: ") + hipGetErrorString(e));
     return build_gram(h);
     NGP_CATCH(h)
@@ -1447,26 +1469,26 @@ int32_t ngp_write_panel_file(const char *path, const uint8_t *G, int64_t N, int6
     NGP_TRY
     if (!path || !G || N <= 0 || P <= 0 || ld < N || (bits != 8 && bits != 2)) return NGP_ERR_ARG;
     std::vector<uint8_t> packed(bits == 2 ? (size_t)(N + 3) / 4 : 0);  // before the file is opened: an allocation failure leaves nothing behind
-    FILE *f = std::fopen(path, "wb");
+    File f(std::fopen(path, "wb"));
     if (!f) return NGP_ERR_ARG;
     PanelHeader hd;
     std::memcpy(hd.magic, "NGPPNL01", 8);
     hd.N = N; hd.P = P; hd.bits = bits; hd.zero = 0;
-    bool ok = std::fwrite(&hd, sizeof hd, 1, f) == 1;
+    bool ok = std::fwrite(&hd, sizeof hd, 1, f.get()) == 1;
     for (int64_t j = 0; j < P && ok; j++) {
         const uint8_t *col = G + (size_t)j * ld;
         if (bits == 8) {
-            ok = std::fwrite(col, 1, (size_t)N, f) == (size_t)N;
+            ok = std::fwrite(col, 1, (size_t)N, f.get()) == (size_t)N;
         } else {
             std::fill(packed.begin(), packed.end(), 0);
             for (int64_t i = 0; i < N; i++) {
                 if (col[i] > 2) { ok = false; break; }  // two bits hold the allele counts 0, 1, 2
                 packed[(size_t)i >> 2] |= (uint8_t)(col[i] << (2 * (i & 3)));
             }
-            if (ok) ok = std::fwrite(packed.data(), 1, packed.size(), f) == packed.size();
+            if (ok) ok = std::fwrite(packed.data(), 1, packed.size(), f.get()) == packed.size();
         }
     }
-    ok = (std::fclose(f) == 0) && ok;
+    ok = (std::fclose(f.release()) == 0) && ok;  // (a failed close is a failed write)
     return ok ? NGP_OK : NGP_ERR_ARG;
     NGP_CATCH(nullptr)
 }
@@ -1474,12 +1496,11 @@ int32_t ngp_write_panel_file(const char *path, const uint8_t *G, int64_t N, int6
 int32_t ngp_read_panel_header(const char *path, int64_t *N, int64_t *P, int32_t *bits) {
     NGP_TRY
     if (!path) return NGP_ERR_ARG;
-    FILE *f = std::fopen(path, "rb");
+    File f(std::fopen(path, "rb"));
     if (!f) return NGP_ERR_ARG;
     PanelHeader hd;
-    const bool ok = std::fread(&hd, sizeof hd, 1, f) == 1 && std::memcmp(hd.magic, "NGPPNL01", 8) == 0 && hd.N > 0 && hd.P > 0 &&
+    const bool ok = std::fread(&hd, sizeof hd, 1, f.get()) == 1 && std::memcmp(hd.magic, "NGPPNL01", 8) == 0 && hd.N > 0 && hd.P > 0 &&
                     (hd.bits == 8 || hd.bits == 2);
-    std::fclose(f);
     if (!ok) return NGP_ERR_ARG;
     if (N) *N = hd.N;
     if (P) *P = hd.P;
@@ -1493,26 +1514,25 @@ int32_t ngp_load_panel_file(ngp_handle *h, const char *path, int32_t centre) {
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(path != nullptr, NGP_ERR_ARG, "null path");
-    FILE *f = std::fopen(path, "rb");
+    File f(std::fopen(path, "rb"));
     REQUIRE(f != nullptr, NGP_ERR_ARG, std::string("cannot open panel file ") + path);
     PanelHeader hd;
-    if (std::fread(&hd, sizeof hd, 1, f) != 1 || std::memcmp(hd.magic, "NGPPNL01", 8) != 0 || hd.N <= 0 || hd.P <= 0 || (hd.bits != 8 && hd.bits != 2)) {
-        std::fclose(f);
+    if (std::fread(&hd, sizeof hd, 1, f.get()) != 1 || std::memcmp(hd.magic, "NGPPNL01", 8) != 0 || hd.N <= 0 || hd.P <= 0 || (hd.bits != 8 && hd.bits != 2))
         return fail(h, NGP_ERR_ARG, std::string("not a panel file (magic NGPPNL01, bits 8 or 2): ") + path);
-    }
     const int64_t N = hd.N, P = hd.P;
-    if ((rc = alloc_panel(h, N, P))) { std::fclose(f); return rc; }
+    if ((rc = alloc_panel(h, N, P))) return rc;
     // the file streams through a pinned host buffer in chunks of whole 64-column blocks; two-bit columns are unpacked on the host
     const int64_t colbytes = (hd.bits == 8) ? N : (N + 3) / 4;
     const int64_t blk_bytes = (int64_t)NGP_BLK * N;
     const int64_t nb_chunk = std::max<int64_t>(1, std::min<int64_t>(h->NBLK, ((int64_t)64 << 20) / blk_bytes));
-    uint8_t *d_g = nullptr, *h_g = nullptr;
-    double *d_mu = nullptr;
+    DevArray<uint8_t> d_g;
+    PinnedArray<uint8_t> h_g;
+    DevArray<double> d_mu;
     std::vector<uint8_t> packed((hd.bits == 2) ? (size_t)colbytes : 0);
-    hipError_t e = hipMalloc((void **)&d_g, (size_t)nb_chunk * blk_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h_g, (size_t)nb_chunk * blk_bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { std::fclose(f); if (d_g) (void)hipFree(d_g); return fail(h, NGP_ERR_NOMEM, "staging buffers"); }
-    if ((rc = dalloc(h, &d_mu, (size_t)nb_chunk * NGP_BLK))) { std::fclose(f); (void)hipFree(d_g); (void)hipHostFree(h_g); return rc; }
+    hipError_t e = d_g.alloc_raw((size_t)nb_chunk * blk_bytes);
+    if (e == hipSuccess) e = h_g.alloc_raw((size_t)nb_chunk * blk_bytes);
+    if (e != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffers");
+    if ((rc = d_mu.alloc(h, (size_t)nb_chunk * NGP_BLK))) return rc;
     std::string why;
     for (int64_t t0 = 0; t0 < h->NBLK && e == hipSuccess && why.empty(); t0 += nb_chunk) {
         const int64_t nb = std::min<int64_t>(nb_chunk, h->NBLK - t0);
@@ -1520,9 +1540,9 @@ int32_t ngp_load_panel_file(ngp_handle *h, const char *path, int32_t centre) {
         for (int64_t jc = 0; jc < ncols && why.empty(); jc++) {
             uint8_t *dst = h_g + (size_t)jc * N;
             if (hd.bits == 8) {
-                if (std::fread(dst, 1, (size_t)N, f) != (size_t)N) why = "panel file truncated";
+                if (std::fread(dst, 1, (size_t)N, f.get()) != (size_t)N) why = "panel file truncated";
             } else {
-                if (std::fread(packed.data(), 1, packed.size(), f) != packed.size()) { why = "panel file truncated"; break; }
+                if (std::fread(packed.data(), 1, packed.size(), f.get()) != packed.size()) { why = "panel file truncated"; break; }
                 for (int64_t i = 0; i < N; i++) {
                     const uint8_t g = (uint8_t)((packed[(size_t)i >> 2] >> (2 * (i & 3))) & 3u);
                     if (g == 3) { why = "panel file holds a missing genotype (code 3): impute before loading"; break; }
@@ -1536,12 +1556,9 @@ int32_t ngp_load_panel_file(ngp_handle *h, const char *path, int32_t centre) {
         ingest_u8_chunk(h, d_g, N, N, t0, nb, ncols, centre, d_mu);
         e = hipStreamSynchronize(h->stream);  // both staging buffers are reused by the next chunk
     }
-    std::fclose(f);
-    (void)hipFree(d_g);
-    (void)hipHostFree(h_g);
-    dfree(d_mu);
-    if (!why.empty()) { release_panel(h); return fail(h, NGP_ERR_ARG, why); }
-    if (e != hipSuccess) { release_panel(h); return fail(h, NGP_ERR_HIP, std::string("load_panel_file: ") + hipGetErrorString(e)); }
+    f.reset(); d_g.reset(); h_g.reset(); d_mu.reset();  // (before the Gram window's scratch is allocated)
+    if (!why.empty()) { drop_panel(h); return fail(h, NGP_ERR_ARG, why); }
+    if (e != hipSuccess) { drop_panel(h); return fail(h, NGP_ERR_HIP, std::string("load_panel_file: ") + hipGetErrorString(e)); }
     return build_gram(h);
     NGP_CATCH(h)
 }
@@ -1555,21 +1572,21 @@ int32_t ngp_generate_panel(ngp_handle *h, int64_t N, int64_t P, double maf_lo, d
     if ((rc = alloc_panel(h, N, P))) return rc;
     (void)hipStreamSynchronize(h->stream);  // (the allocations' zeroing: timed with them)
     const auto ts1 = std::chrono::steady_clock::now();
-    double *d_mu = nullptr;
-    uint32_t *d_thr = nullptr;
-    if ((rc = dalloc(h, &d_mu, (size_t)P))) return rc;
-    if ((rc = dalloc(h, &d_thr, (size_t)P))) { dfree(d_mu); return rc; }
+    DevArray<double> d_mu;
+    DevArray<uint32_t> d_thr;
+    if ((rc = d_mu.alloc(h, (size_t)P))) return rc;
+    if ((rc = d_thr.alloc(h, (size_t)P))) return rc;
     hipLaunchKernelGGL(k_gen_colmean, dim3((unsigned)P), dim3(256), 0, h->stream, (long long)N, (long long)P, maf_lo, maf_hi, panel_seed,
                        d_mu, d_thr);
-    (void)hipMemcpyAsync(h->d_mean, d_mu, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+    (void)hipMemcpyAsync(h->pm->mean, d_mu, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
     if (h->req.storage == 1) {
-        hipLaunchKernelGGL(k_gen_fill8, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, (uint8_t *)h->d_tiles, (long long)N,
+        hipLaunchKernelGGL(k_gen_fill8, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, (uint8_t *)h->pm->tiles.get(), (long long)N,
                            (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_thr);
     } else
-    hipLaunchKernelGGL(k_gen_fill, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, h->d_tiles, (long long)N,
-                       (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_mu, d_thr, (const double *)h->d_rs);
+    hipLaunchKernelGGL(k_gen_fill, dim3((unsigned)h->plan.S, (unsigned)h->NBLK), dim3(256), 0, h->stream, h->pm->tiles, (long long)N,
+                       (long long)P, (int)h->plan.R, (int)h->plan.S, panel_seed, d_mu, d_thr, (const double *)h->cm.d_rs);
     hipError_t e = hipStreamSynchronize(h->stream);
-    dfree(d_mu); dfree(d_thr);
+    d_mu.reset(); d_thr.reset();  // (before the Gram window's scratch is allocated)
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("generate_panel: ") + hipGetErrorString(e));
     const auto ts2 = std::chrono::steady_clock::now();
     rc = build_gram(h);
@@ -1596,7 +1613,7 @@ int32_t ngp_get_layout(ngp_handle *h, int64_t *R, int64_t *S, int64_t *nblk) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     if (R) *R = h->plan.R;
     if (S) *S = h->plan.S;
     if (nblk) *nblk = h->NBLK;
@@ -1608,10 +1625,10 @@ int32_t ngp_get_mpm(ngp_handle *h, double *out, int64_t P) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(out && P == h->P, NGP_ERR_ARG, "mpm buffer must hold P entries");
-    HCHK(hipMemcpy(out, h->d_mpm, (size_t)P * sizeof(double), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(out, h->pm->mpm, (size_t)P * sizeof(double), hipMemcpyDeviceToHost));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -1620,13 +1637,13 @@ int32_t ngp_get_gram(ngp_handle *h, int64_t t, double *out) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(out && t >= 0 && t < h->NBLK, NGP_ERR_ARG, "block index out of range");
-    HCHK(hipMemcpy(out, h->d_gramx + (size_t)t * h->plan.D * NGP_BLK * NGP_BLK, NGP_BLK * NGP_BLK * sizeof(double), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(out, h->pm->gramx + (size_t)t * h->plan.D * NGP_BLK * NGP_BLK, NGP_BLK * NGP_BLK * sizeof(double), hipMemcpyDeviceToHost));
     // the device keeps entry [k][j] for j > k only (plus x'x in mpm); hand back the symmetric block
     double diag[NGP_BLK];
-    HCHK(hipMemcpy(diag, h->d_mpm + (size_t)t * NGP_BLK, sizeof(diag), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(diag, h->pm->mpm + (size_t)t * NGP_BLK, sizeof(diag), hipMemcpyDeviceToHost));
     for (int k = 0; k < NGP_BLK; k++) {
         out[k * NGP_BLK + k] = diag[k];
         for (int j = k + 1; j < NGP_BLK; j++) out[j * NGP_BLK + k] = out[k * NGP_BLK + j];
@@ -1639,24 +1656,23 @@ int32_t ngp_xbeta(ngp_handle *h, const double *beta, int64_t P, double *out, int
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(beta && out && P == h->P && N == h->N, NGP_ERR_ARG, "xbeta: size mismatch");
-    double *d_b = nullptr, *d_o = nullptr;
-    if ((rc = dalloc(h, &d_b, (size_t)h->Ppad))) return rc;
-    if ((rc = dalloc(h, &d_o, (size_t)h->L))) { dfree(d_b); return rc; }
+    DevArray<double> d_b, d_o;
+    if ((rc = d_b.alloc(h, (size_t)h->Ppad))) return rc;
+    if ((rc = d_o.alloc(h, (size_t)h->L))) return rc;
     hipError_t e = hipMemcpyAsync(d_b, beta, (size_t)P * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess && (size_t)h->Ppad > (size_t)P) e = hipMemsetAsync(d_b + P, 0, ((size_t)h->Ppad - (size_t)P) * sizeof(double), h->stream);
     if (h->req.storage == 1)
-        hipLaunchKernelGGL(k_xbeta8, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, (const uint8_t *)h->d_tiles, h->d_mean, d_b, d_o, (int)h->plan.R,
+        hipLaunchKernelGGL(k_xbeta8, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, (const uint8_t *)h->pm->tiles.get(), h->pm->mean, d_b, d_o, (int)h->plan.R,
                            (int)h->plan.S, (long long)h->NBLK, (long long)h->N);
     else
-    hipLaunchKernelGGL(k_xbeta, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, h->d_tiles, d_b, d_o, (int)h->plan.R, (int)h->plan.S,
+    hipLaunchKernelGGL(k_xbeta, dim3((unsigned)h->plan.S), dim3(256), 0, h->stream, h->pm->tiles, d_b, d_o, (int)h->plan.R, (int)h->plan.S,
                        (long long)h->NBLK);
-    if (h->d_rs) launch_rows(h, d_o, d_o, true);  // the tiles hold s x: X beta = (X~ beta) / s
+    if (h->cm.d_rs) launch_rows(h, d_o, d_o, true);  // the tiles hold s x: X beta = (X~ beta) / s
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    dfree(d_b); dfree(d_o);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("xbeta: ") + hipGetErrorString(e));
     return NGP_OK;
     NGP_CATCH(h)
@@ -1668,7 +1684,7 @@ int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t me
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
     REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
@@ -1699,20 +1715,12 @@ int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t me
     HSet hs{col0, ncol, method, df, scale, nreg, h->nvb, estPi, 0, pi0, std::vector<double>(varBeta0, varBeta0 + nreg)};
     // grow varBeta storage
     const int64_t new_nvb = h->nvb + nreg;
-    if (new_nvb > h->vb_cap) {
-        int64_t cap = std::max<int64_t>(new_nvb, 2 * h->vb_cap);
-        double *nv = nullptr, *ns = nullptr;
-        if ((rc = dalloc(h, &nv, (size_t)cap))) return rc;
-        if ((rc = dalloc(h, &ns, (size_t)cap))) return rc;
-        if (h->nvb > 0) {
-            HCHK(hipMemcpyAsync(nv, h->d_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HCHK(hipMemcpyAsync(ns, h->d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
-        HCHK(hipStreamSynchronize(h->stream));
-        dfree(h->d_varBeta); dfree(h->d_sum_varBeta);
-        h->d_varBeta = nv; h->d_sum_varBeta = ns; h->vb_cap = cap;
+    if (new_nvb > h->mm.vb_cap) {
+        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
+        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
+        h->mm.vb_cap = cap;
     }
-    HCHK(hipMemcpy(h->d_varBeta + h->nvb, varBeta0, (size_t)nreg * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, varBeta0, (size_t)nreg * sizeof(double), hipMemcpyHostToDevice));
     for (int64_t r = 0; r < nreg; r++)
         for (int64_t l = reg_start[r]; l < reg_stop[r]; l++) {
             int64_t k = col0 + l;
@@ -1737,19 +1745,19 @@ int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t me
         }
     }
     std::vector<double> z((size_t)ncol, 0.0);
-    HCHK(hipMemcpy(h->d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
     DSet ds;
     memset(&ds, 0, sizeof(ds));
     ds.method = method; ds.estPi = estPi; ds.df = df; ds.scale = scale; ds.sdf = scale * df; ds.col0 = col0; ds.ncol = ncol;
-    HCHK(hipMemcpy(h->d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
     const double p1 = pi0, p0 = 1.0 - pi0;
-    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, si, p0, p1);  // src/mme.jl:351,360
+    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, p0, p1);  // src/mme.jl:351,360
     HCHK(hipStreamSynchronize(h->stream));
     h->nvb = new_nvb;
     h->sets.push_back(hs);
     h->tables_dirty = true;
-    h->trace_ext_cap = 0;  // d_tr_pi holds one column per set: sized again by the next traced ngp_run
+    h->mm.trace_ext_cap = 0;  // d_tr_pi holds one column per set: sized again by the next traced ngp_run
     if (set_id) *set_id = si;
     return NGP_OK;
     NGP_CATCH(h)
@@ -1759,35 +1767,35 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(y && N == h->N, NGP_ERR_ARG, "y must have N entries");
     for (int64_t i = 0; i < N; i++) REQUIRE(std::isfinite(y[i]), NGP_ERR_ARG, "non-finite phenotype");
-    HCHK(hipMemsetAsync(h->d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
-    HCHK(hipMemcpyAsync(h->d_ycorr, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // src/mme.jl:57
-    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: y~ = s y
-    HCHK(hipMemsetAsync(h->d_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));                  // src/mme.jl:443
-    HCHK(hipMemsetAsync(h->d_delta, 1, (size_t)h->Ppad, h->stream));                                  // src/mme.jl:444
-    HCHK(hipMemsetAsync(h->d_scal, 0, sizeof(DScal), h->stream));
-    HCHK(hipMemsetAsync(h->d_sum_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
-    HCHK(hipMemsetAsync(h->d_sum_beta2, 0, (size_t)h->Ppad * sizeof(double), h->stream));
-    HCHK(hipMemsetAsync(h->d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
+    HCHK(hipMemsetAsync(h->cm.d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
+    HCHK(hipMemcpyAsync(h->cm.d_ycorr, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // src/mme.jl:57
+    if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: y~ = s y
+    HCHK(hipMemsetAsync(h->cm.d_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));                  // src/mme.jl:443
+    HCHK(hipMemsetAsync(h->cm.d_delta, 1, (size_t)h->Ppad, h->stream));                                  // src/mme.jl:444
+    HCHK(hipMemsetAsync(h->cm.d_scal, 0, sizeof(DScal), h->stream));
+    HCHK(hipMemsetAsync(h->cm.d_sum_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
+    HCHK(hipMemsetAsync(h->cm.d_sum_beta2, 0, (size_t)h->Ppad * sizeof(double), h->stream));
+    HCHK(hipMemsetAsync(h->cm.d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     // a second chain on the same handle starts from the priors, with empty posterior sums (src/mme.jl:351-360, 516)
-    if (h->nvb > 0) HCHK(hipMemsetAsync(h->d_sum_varBeta, 0, (size_t)h->nvb * sizeof(double), h->stream));
+    if (h->nvb > 0) HCHK(hipMemsetAsync(h->mm.d_sum_varBeta, 0, (size_t)h->nvb * sizeof(double), h->stream));
     for (size_t si = 0; si < h->sets.size(); si++) {
         const HSet &hs = h->sets[si];
-        HCHK(hipMemcpyAsync(h->d_varBeta + hs.vb_off, hs.vb0.data(), hs.vb0.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)si, 1.0 - hs.pi0, hs.pi0);
-        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)si, 0.0, 0.0);
+        HCHK(hipMemcpyAsync(h->mm.d_varBeta + hs.vb_off, hs.vb0.data(), hs.vb0.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, 1.0 - hs.pi0, hs.pi0);
+        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, 0.0, 0.0);
         if (hs.K > 0) {
             int rc2 = set_class_state_dev(h, (int)si, hs.rpi.data(), std::vector<double>((size_t)hs.K, 0.0).data());
             if (rc2) return rc2;
         }
     }
-    if (h->nfixcol > 0) {
-        HCHK(hipMemsetAsync(h->d_bfix, 0, (size_t)h->nfixcol * sizeof(double), h->stream));
-        HCHK(hipMemsetAsync(h->d_sum_bfix, 0, (size_t)h->nfixcol * sizeof(double), h->stream));
+    if (h->mm.nfixcol > 0) {
+        HCHK(hipMemsetAsync(h->mm.d_bfix, 0, (size_t)h->mm.nfixcol * sizeof(double), h->stream));
+        HCHK(hipMemsetAsync(h->mm.d_sum_bfix, 0, (size_t)h->mm.nfixcol * sizeof(double), h->stream));
     }
-    for (auto &R : h->rnd) {  // u = 0, varU = its prior value (src/mme.jl:200, 265-272), empty sums
+    for (auto &R : h->mm.rnd) {  // u = 0, varU = its prior value (src/mme.jl:200, 265-272), empty sums
         const double vu[2] = {R.varU0, 0.0};
         HCHK(hipMemsetAsync(R.d_u, 0, (size_t)R.q * sizeof(double), h->stream));
         HCHK(hipMemsetAsync(R.d_sum_u, 0, (size_t)R.q * sizeof(double), h->stream));
@@ -1816,7 +1824,7 @@ int32_t ngp_set_residual_weights(ngp_handle *h, const double *w, int64_t N) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles == nullptr && h->pm == nullptr, NGP_ERR_STATE,
+    REQUIRE(!h->pm, NGP_ERR_STATE,
             "residual weights must be set before the panel (they scale its rows) and before ngp_set_y");
     if (w == nullptr && N == 0) { h->h_rw.clear(); h->sum_w = 0.0; return NGP_OK; }
     REQUIRE(w != nullptr && N > 0, NGP_ERR_ARG, "residual weights: N > 0 entries (or NULL and 0 to remove them)");
@@ -1870,17 +1878,17 @@ int prepare_run(ngp_handle *h, int64_t niter) {
     if ((rc = ready(h))) return rc;
     REQUIRE(niter >= 0, NGP_ERR_ARG, "niter must be >= 0");
     REQUIRE(!h->poisoned, NGP_ERR_STATE, "an earlier sweep was abandoned half-way: set the state again (ngp_set_y / ngp_set_state)");
-    REQUIRE(h->ntvb <= h->nvb, NGP_ERR_STATE, "more variance traces requested than the model has variance components");
-    if (h->ntl + h->ntvb + (int64_t)h->sets.size() > 0 && h->d_trace_loci && niter > h->trace_ext_cap) {
-        if ((rc = dalloc(h, &h->d_tr_beta, (size_t)niter * std::max<int64_t>(h->ntl, 1)))) return rc;
-        if ((rc = dalloc(h, &h->d_tr_vb, (size_t)niter * std::max<int64_t>(h->ntvb, 1)))) return rc;
-        if ((rc = dalloc(h, &h->d_tr_pi, (size_t)niter * std::max<size_t>(h->sets.size(), 1)))) return rc;
-        h->trace_ext_cap = niter;
+    REQUIRE(h->mm.ntvb <= h->nvb, NGP_ERR_STATE, "more variance traces requested than the model has variance components");
+    if (h->mm.ntl + h->mm.ntvb + (int64_t)h->sets.size() > 0 && h->mm.d_trace_loci && niter > h->mm.trace_ext_cap) {
+        if ((rc = h->mm.d_tr_beta.alloc(h, (size_t)niter * std::max<int64_t>(h->mm.ntl, 1)))) return rc;
+        if ((rc = h->mm.d_tr_vb.alloc(h, (size_t)niter * std::max<int64_t>(h->mm.ntvb, 1)))) return rc;
+        if ((rc = h->mm.d_tr_pi.alloc(h, (size_t)niter * std::max<size_t>(h->sets.size(), 1)))) return rc;
+        h->mm.trace_ext_cap = niter;
     }
-    if (niter > h->trace_cap) {
-        if ((rc = dalloc(h, &h->d_tr_varE, (size_t)niter))) return rc;
-        if ((rc = dalloc(h, &h->d_tr_b, (size_t)niter))) return rc;
-        h->trace_cap = niter;
+    if (niter > h->hm.trace_cap) {
+        if ((rc = h->hm.d_tr_varE.alloc(h, (size_t)niter))) return rc;
+        if ((rc = h->hm.d_tr_b.alloc(h, (size_t)niter))) return rc;
+        h->hm.trace_cap = niter;
     }
     h->ntrace = niter;
     return NGP_OK;
@@ -1905,7 +1913,7 @@ bool fusable(ngp_handle **hs, int n) {
     if (!phase && !rows && !bytes) return false;
     for (int i = 0; i < n; i++) {
         ngp_handle *h = hs[i];
-        if (h->pm != h0->pm || h->device != h0->device || h->dbg_mode != 0 || h->d_dbg || h->dbg_census_fail_iter > 0) return false;
+        if (h->pm != h0->pm || h->device != h0->device || h->dbg_mode != 0 || h->hm.d_dbg || h->dbg_census_fail_iter > 0) return false;
     }
     // (the samplers sit at blocks 0, 8, .., 8 (n - 1) of the grid -- one XCD under round-robin placement: the grid must reach the last)
     const int64_t grid = sweep_grid(h0->plan, n);
@@ -1929,27 +1937,29 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     // One abort word: the leader's.  The sweep runs on the leader's stream; every chain's small kernels (head, coefficients, variance
     // draws, posterior sums: six launches of a few microseconds each) stay on the chain's OWN stream, tied to the sweep by events --
     // the K chains' small kernels then run side by side instead of one chain after the other (eight chains: 0.34 ms of a 4.35-ms pass).
-    std::vector<unsigned *> ab((size_t)n);
-    std::vector<hipEvent_t> evp((size_t)n, nullptr);
-    hipEvent_t evs = nullptr;
+    struct Events {  // evp[i]: chain i's coefficients are in (i >= 1); evs: the sweep is done.  Destroyed however the call ends.
+        std::vector<hipEvent_t> evp;
+        hipEvent_t evs = nullptr;
+        ~Events() {
+            for (hipEvent_t x : evp) if (x) (void)hipEventDestroy(x);
+            if (evs) (void)hipEventDestroy(evs);
+        }
+    } ev;
+    ev.evp.assign((size_t)n, nullptr);
     for (int i = 0; i < n; i++) HCHK(hipStreamSynchronize(hs[i]->stream));
-    for (int i = 0; i < n; i++) { ab[i] = hs[i]->d_abort; hs[i]->d_abort = h->d_abort; }
-    auto restore = [&]() {
-        for (int i = 0; i < n; i++) { hs[i]->d_abort = ab[i]; if (evp[i]) (void)hipEventDestroy(evp[i]); }
-        if (evs) (void)hipEventDestroy(evs);
-    };
-    // (a scope guard: an exception on the way -- a std::string or std::vector that cannot allocate -- unwinds to the ABI's barrier
-    // with every handle's own abort word back in place; ngp_destroy would otherwise free the leader's buffer once per handle)
-    struct Guard {
-        decltype(restore) &f;
-        bool armed = true;
-        ~Guard() { if (armed) f(); }
-        void now() { if (armed) { armed = false; f(); } }
-    } guard{restore};
+    // Every chain's launches read the leader's word through their d_abort view.  The guard only puts each view back to the
+    // handle's own word when the call ends, an exception on the way included; it frees nothing (each word stays owned by its
+    // handle's abort_mem).
+    struct AbortViews {
+        ngp_handle **hs;
+        int n;
+        ~AbortViews() { for (int i = 0; i < n; i++) hs[i]->cm.d_abort = hs[i]->cm.abort_mem; }
+    } views{hs, n};
+    for (int i = 1; i < n; i++) hs[i]->cm.d_abort = h->cm.d_abort;
     hipError_t e = hipSuccess;
-    for (int i = 1; i < n && e == hipSuccess; i++) e = hipEventCreateWithFlags(&evp[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&evs, hipEventDisableTiming);
-    if (e != hipSuccess) { guard.now(); return fail(h, NGP_ERR_HIP, std::string("fused run: ") + hipGetErrorString(e)); }
+    for (int i = 1; i < n && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ev.evp[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev.evs, hipEventDisableTiming);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("fused run: ") + hipGetErrorString(e));
     auto sync_all = [&]() {
         hipError_t r = hipStreamSynchronize(h->stream);
         for (int i = 1; i < n; i++) { hipError_t q = hipStreamSynchronize(hs[i]->stream); if (r == hipSuccess) r = q; }
@@ -1965,15 +1975,15 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
             iteration_pre(hs[i], it, false);
             fill_sweep_args(hs[i], 0, hs[i]->NBLK, M.a[i]);
             if (i > 0) {  // the sweep waits for this chain's coefficients (and cleared hand-off counters)
-                (void)hipEventRecord(evp[i], hs[i]->stream);
-                (void)hipStreamWaitEvent(h->stream, evp[i], 0);
+                (void)hipEventRecord(ev.evp[i], hs[i]->stream);
+                (void)hipStreamWaitEvent(h->stream, ev.evp[i], 0);
             }
         }
         for (int i = 1; i < n; i++) { M.a[i].census = nullptr; M.a[i].xcc_w = M.a[0].xcc_w; }
         launch_sweep_kernel(kern, grid, lds, h->stream, &M);
         h->sweep_launches += 1; h->last_grid = grid;
-        (void)hipEventRecord(evs, h->stream);
-        for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(hs[i]->stream, evs, 0);
+        (void)hipEventRecord(ev.evs, h->stream);
+        for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(hs[i]->stream, ev.evs, 0);
         for (int i = 0; i < n && rc == NGP_OK; i++) { rc = iteration_post(hs[i], it); if (rc && i) h->err = hs[i]->err; }
         if (rc) break;
         if ((it & 15) == 15 || it + 1 == niter) {  // bound the launch queue
@@ -1988,7 +1998,6 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     else (void)sync_all();
     if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    guard.now();
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("fused run: ") + hipGetErrorString(e));
     if (rc) return rc;
     float ms = 0.f;
@@ -2026,31 +2035,30 @@ int32_t ngp_get_state(ngp_handle *h, double *ycorr, double *beta, int64_t *delta
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->have_y, NGP_ERR_STATE, "panel / y not set");
+    REQUIRE(h->pm && h->have_y, NGP_ERR_STATE, "panel / y not set");
     HCHK(hipStreamSynchronize(h->stream));
-    if (ycorr && h->d_rs) {  // weighted residuals: ycorr = y~ / s
-        double *d_t = nullptr;
-        if ((rc = dalloc(h, &d_t, (size_t)h->N))) return rc;
-        launch_rows(h, d_t, h->d_ycorr, true);
+    if (ycorr && h->cm.d_rs) {  // weighted residuals: ycorr = y~ / s
+        DevArray<double> d_t;
+        if ((rc = d_t.alloc(h, (size_t)h->N))) return rc;
+        launch_rows(h, d_t, h->cm.d_ycorr, true);
         hipError_t e = hipMemcpyAsync(ycorr, d_t, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        dfree(d_t);
         if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("get_state: ") + hipGetErrorString(e));
-    } else if (ycorr) HCHK(hipMemcpy(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
-    if (beta) HCHK(hipMemcpy(beta, h->d_beta, (size_t)h->P * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (ycorr) HCHK(hipMemcpy(ycorr, h->cm.d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
+    if (beta) HCHK(hipMemcpy(beta, h->cm.d_beta, (size_t)h->P * sizeof(double), hipMemcpyDeviceToHost));
     if (delta) {
         std::vector<uint8_t> d((size_t)h->P);
-        HCHK(hipMemcpy(d.data(), h->d_delta, (size_t)h->P, hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(d.data(), h->cm.d_delta, (size_t)h->P, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < h->P; k++) delta[k] = d[k];
     }
-    if (varBeta && h->nvb) HCHK(hipMemcpy(varBeta, h->d_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToHost));
+    if (varBeta && h->nvb) HCHK(hipMemcpy(varBeta, h->mm.d_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToHost));
     if (piHat && !h->sets.empty()) {
         std::vector<DSet> ds(h->sets.size());
-        HCHK(hipMemcpy(ds.data(), h->d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(ds.data(), h->cm.d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < ds.size(); s++) { piHat[2 * s] = ds[s].piHat0; piHat[2 * s + 1] = ds[s].piHat1; }
     }
     DScal sc;
-    HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
     if (varE) *varE = sc.varE;
     if (b) *b = sc.b;
     if (iter) *iter = h->iter;
@@ -2063,26 +2071,26 @@ int32_t ngp_set_state(ngp_handle *h, const double *ycorr, const double *beta, co
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->have_y, NGP_ERR_STATE, "panel / y not set");
+    REQUIRE(h->pm && h->have_y, NGP_ERR_STATE, "panel / y not set");
     // (varE is 0 before the first iteration -- ngp_set_y -- and drawn before it is used; any later state has varE > 0)
     REQUIRE(std::isfinite(varE) && (varE > 0.0 || (varE == 0.0 && iter == 0)) && std::isfinite(b) && iter >= 0, NGP_ERR_ARG,
             "bad scalar state (varE must be finite and positive)");
-    if (ycorr) HCHK(hipMemcpy(h->d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice));
-    if (ycorr && h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: y~ = s ycorr
-    if (beta) HCHK(hipMemcpy(h->d_beta, beta, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
+    if (ycorr) HCHK(hipMemcpy(h->cm.d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice));
+    if (ycorr && h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: y~ = s ycorr
+    if (beta) HCHK(hipMemcpy(h->cm.d_beta, beta, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
     if (delta) {
         std::vector<uint8_t> d((size_t)h->P);
         for (int64_t k = 0; k < h->P; k++) d[k] = (uint8_t)(delta[k] != 0);
-        HCHK(hipMemcpy(h->d_delta, d.data(), (size_t)h->P, hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->cm.d_delta, d.data(), (size_t)h->P, hipMemcpyHostToDevice));
     }
-    if (varBeta && h->nvb) HCHK(hipMemcpy(h->d_varBeta, varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyHostToDevice));
+    if (varBeta && h->nvb) HCHK(hipMemcpy(h->mm.d_varBeta, varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyHostToDevice));
     if (piHat)
         for (size_t s = 0; s < h->sets.size(); s++)
-            hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)s, piHat[2 * s], piHat[2 * s + 1]);
+            hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)s, piHat[2 * s], piHat[2 * s + 1]);
     DScal sc;
-    HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
     sc.varE = varE; sc.iVarE = 1.0 / varE; sc.b = b;
-    HCHK(hipMemcpy(h->d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
     HCHK(hipStreamSynchronize(h->stream));
     h->iter = iter;
     if (ycorr && beta) h->poisoned = false;
@@ -2096,8 +2104,8 @@ int32_t ngp_get_trace(ngp_handle *h, double *varE, double *b, int64_t n) {
     if ((rc = enter(h))) return rc;
     n = std::min(n, h->ntrace);
     if (n <= 0) return NGP_OK;
-    if (varE) HCHK(hipMemcpy(varE, h->d_tr_varE, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    if (b) HCHK(hipMemcpy(b, h->d_tr_b, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (varE) HCHK(hipMemcpy(varE, h->hm.d_tr_varE, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (b) HCHK(hipMemcpy(b, h->hm.d_tr_b, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2107,20 +2115,20 @@ int32_t ngp_get_posterior_sums(ngp_handle *h, double *sum_beta, double *sum_beta
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     HCHK(hipStreamSynchronize(h->stream));
     const size_t pb = (size_t)h->P * sizeof(double);
-    if (sum_beta) HCHK(hipMemcpy(sum_beta, h->d_sum_beta, pb, hipMemcpyDeviceToHost));
-    if (sum_beta2) HCHK(hipMemcpy(sum_beta2, h->d_sum_beta2, pb, hipMemcpyDeviceToHost));
-    if (sum_delta) HCHK(hipMemcpy(sum_delta, h->d_sum_delta, pb, hipMemcpyDeviceToHost));
-    if (sum_varBeta && h->nvb) HCHK(hipMemcpy(sum_varBeta, h->d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_beta) HCHK(hipMemcpy(sum_beta, h->cm.d_sum_beta, pb, hipMemcpyDeviceToHost));
+    if (sum_beta2) HCHK(hipMemcpy(sum_beta2, h->cm.d_sum_beta2, pb, hipMemcpyDeviceToHost));
+    if (sum_delta) HCHK(hipMemcpy(sum_delta, h->cm.d_sum_delta, pb, hipMemcpyDeviceToHost));
+    if (sum_varBeta && h->nvb) HCHK(hipMemcpy(sum_varBeta, h->mm.d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToHost));
     if (sum_pi && !h->sets.empty()) {
         std::vector<DSet> ds(h->sets.size());
-        HCHK(hipMemcpy(ds.data(), h->d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(ds.data(), h->cm.d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < ds.size(); s++) { sum_pi[2 * s] = ds[s].sum_pi0; sum_pi[2 * s + 1] = ds[s].sum_pi1; }
     }
     DScal sc;
-    HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
     if (sum_varE) *sum_varE = sc.sum_varE;
     if (sum_b) *sum_b = sc.sum_b;
     if (nKept) *nKept = sc.nKept;
@@ -2142,34 +2150,34 @@ int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     const int64_t need = posterior_words(h);
     REQUIRE(device_ptr && len == need, NGP_ERR_ARG, "export buffer length mismatch (see ngp_posterior_len)");
     double *o = (double *)device_ptr;
     const size_t pb = (size_t)h->P * sizeof(double);
-    HCHK(hipMemcpyAsync(o, h->d_sum_beta, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(o + h->P, h->d_sum_beta2, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(o + 2 * h->P, h->d_sum_delta, pb, hipMemcpyDeviceToDevice, h->stream));
-    if (h->nvb) HCHK(hipMemcpyAsync(o + 3 * h->P, h->d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipMemcpyAsync(o, h->cm.d_sum_beta, pb, hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipMemcpyAsync(o + h->P, h->cm.d_sum_beta2, pb, hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipMemcpyAsync(o + 2 * h->P, h->cm.d_sum_delta, pb, hipMemcpyDeviceToDevice, h->stream));
+    if (h->nvb) HCHK(hipMemcpyAsync(o + 3 * h->P, h->mm.d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     std::vector<DSet> ds(h->sets.size());
     HCHK(hipStreamSynchronize(h->stream));
-    if (!ds.empty()) HCHK(hipMemcpy(ds.data(), h->d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
+    if (!ds.empty()) HCHK(hipMemcpy(ds.data(), h->cm.d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
     DScal sc;
-    HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
     std::vector<double> tail;
     for (auto &s : ds) { tail.push_back(s.sum_pi0); tail.push_back(s.sum_pi1); }
     for (auto &s : ds) for (int v = 0; v < s.K; v++) tail.push_back(s.sum_pic[v]);  // BayesR class probabilities, set by set
     const size_t nfix_at = tail.size();
-    tail.resize(nfix_at + (size_t)h->nfixcol);  // fixed-effect sums beyond the intercept (all columns of all sets, in order)
-    if (h->nfixcol > 0) HCHK(hipMemcpy(tail.data() + nfix_at, h->d_sum_bfix, (size_t)h->nfixcol * sizeof(double), hipMemcpyDeviceToHost));
-    if (!h->rnd.empty()) {  // random-effect sets: sums of u (set after set), then the sums of varU
+    tail.resize(nfix_at + (size_t)h->mm.nfixcol);  // fixed-effect sums beyond the intercept (all columns of all sets, in order)
+    if (h->mm.nfixcol > 0) HCHK(hipMemcpy(tail.data() + nfix_at, h->mm.d_sum_bfix, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyDeviceToHost));
+    if (!h->mm.rnd.empty()) {  // random-effect sets: sums of u (set after set), then the sums of varU
         const size_t r_at = tail.size();
-        tail.resize(r_at + (size_t)h->nrandcol + h->rnd.size());
+        tail.resize(r_at + (size_t)h->mm.nrandcol + h->mm.rnd.size());
         size_t off = r_at;
-        for (size_t r = 0; r < h->rnd.size(); r++) {
-            HCHK(hipMemcpy(tail.data() + off, h->rnd[r].d_sum_u, (size_t)h->rnd[r].q * sizeof(double), hipMemcpyDeviceToHost));
-            HCHK(hipMemcpy(tail.data() + r_at + (size_t)h->nrandcol + r, h->rnd[r].d_vu + 1, sizeof(double), hipMemcpyDeviceToHost));
-            off += (size_t)h->rnd[r].q;
+        for (size_t r = 0; r < h->mm.rnd.size(); r++) {
+            HCHK(hipMemcpy(tail.data() + off, h->mm.rnd[r].d_sum_u, (size_t)h->mm.rnd[r].q * sizeof(double), hipMemcpyDeviceToHost));
+            HCHK(hipMemcpy(tail.data() + r_at + (size_t)h->mm.nrandcol + r, h->mm.rnd[r].d_vu + 1, sizeof(double), hipMemcpyDeviceToHost));
+            off += (size_t)h->mm.rnd[r].q;
         }
     }
     tail.push_back(sc.sum_varE); tail.push_back(sc.sum_b); tail.push_back((double)sc.nKept);
@@ -2182,7 +2190,7 @@ namespace {
 // one fine-seam call; dev: the caller's arrays (and piHat) are DEVICE memory of this handle's device, delta is int64 there too
 int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *beta, int64_t *delta, double *varBeta, double *piHat, bool dev) {
     int rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(set_id >= 0 && set_id < (int)h->sets.size(), NGP_ERR_ARG, "unknown set id");
     REQUIRE(ycorr && beta && varBeta, NGP_ERR_ARG, "null state pointer");
     REQUIRE(std::isfinite(varE) && varE > 0.0, NGP_ERR_ARG, "varE must be finite and positive");
@@ -2199,24 +2207,24 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
     const int64_t tb0 = hs.col0 / NGP_BLK, tb1 = (hs.col0 + hs.ncol - 1) / NGP_BLK + 1;
     CuLease lease(h);
     for (int attempt = 0;; ++attempt) {
-        HCHK(hipMemsetAsync(h->d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
-        HCHK(hipMemcpyAsync(h->d_ycorr, ycorr, (size_t)h->N * sizeof(double), in, h->stream));
-        if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
-        HCHK(hipMemcpyAsync(h->d_beta + hs.col0, beta, (size_t)hs.ncol * sizeof(double), in, h->stream));
-        HCHK(hipMemcpyAsync(h->d_varBeta + hs.vb_off, varBeta, (size_t)nvbs * sizeof(double), in, h->stream));
+        HCHK(hipMemsetAsync(h->cm.d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
+        HCHK(hipMemcpyAsync(h->cm.d_ycorr, ycorr, (size_t)h->N * sizeof(double), in, h->stream));
+        if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
+        HCHK(hipMemcpyAsync(h->cm.d_beta + hs.col0, beta, (size_t)hs.ncol * sizeof(double), in, h->stream));
+        HCHK(hipMemcpyAsync(h->mm.d_varBeta + hs.vb_off, varBeta, (size_t)nvbs * sizeof(double), in, h->stream));
         if (has_pi) {
-            if (dev) hipLaunchKernelGGL(k_set_pi_dev, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)set_id, (const double *)piHat);
-            else hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)set_id, piHat[0], piHat[1]);
+            if (dev) hipLaunchKernelGGL(k_set_pi_dev, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)set_id, (const double *)piHat);
+            else hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)set_id, piHat[0], piHat[1]);
         }
-        hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->d_scal, varE);
+        hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->cm.d_scal, varE);
         // (no draws, no intercept: ycorr'ycorr of the caller's residual sets the scale of the fixed-point accumulators)
-        hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->d_ycorr, (long long)h->L, (long long)h->N, h->d_scal, h->e_df,
-                           h->e_scale, 0, 0, h->seed, (uint64_t)h->chain, it, (double *)nullptr, (double *)nullptr, (long long)0, h->d_abort, h->mpm_max,
-                           (const double *)h->d_rs, h->sum_w);
-        hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->d_setof, h->d_loc,
-                           h->d_vbidx, h->d_sets, h->d_scal, h->d_varBeta, h->d_mpm, h->d_lhs0, h->d_rhs0, h->d_beta, h->d_c, h->d_w,
-                           h->d_q, h->d_T, h->d_chi, (int)set_id, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->d_regs, h->d_regchi, h->d_rcls,
-                           h->d_ccnt, (long long)(h->plan.mode == 1 ? h->ccnt_words : 0), h->d_abort, h->d_tup, h->d_tupc, h->d_tupg);
+        hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->L, (long long)h->N, h->cm.d_scal, h->e_df,
+                           h->e_scale, 0, 0, h->seed, (uint64_t)h->chain, it, (double *)nullptr, (double *)nullptr, (long long)0, h->cm.d_abort, h->pm->mpm_max,
+                           (const double *)h->cm.d_rs, h->sum_w);
+        hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->cm.d_setof, h->cm.d_loc,
+                           h->cm.d_vbidx, h->cm.d_sets, h->cm.d_scal, h->mm.d_varBeta, h->pm->mpm, h->cm.d_lhs0, h->cm.d_rhs0, h->cm.d_beta, h->cm.d_c, h->cm.d_w,
+                           h->cm.d_q, h->cm.d_T, h->cm.d_chi, (int)set_id, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->mm.d_regs, h->mm.d_regchi, h->mm.d_rcls,
+                           h->cm.d_ccnt, (long long)(h->plan.mode == 1 ? h->cm.ccnt_words : 0), h->cm.d_abort, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg);
         launch_tinv(h);
         launch_sweep(h, tb0, tb1, nullptr);
         launch_variance(h, (int)set_id, it);
@@ -2232,13 +2240,13 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
         if (rc) return rc;
         break;
     }
-    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, true);  // ... and back: the caller's ycorr is unscaled (d_ycorr is scratch here)
-    HCHK(hipMemcpyAsync(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), out, h->stream));
-    HCHK(hipMemcpyAsync(beta, h->d_beta + hs.col0, (size_t)hs.ncol * sizeof(double), out, h->stream));
-    HCHK(hipMemcpyAsync(varBeta, h->d_varBeta + hs.vb_off, (size_t)nvbs * sizeof(double), out, h->stream));
+    if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, true);  // ... and back: the caller's ycorr is unscaled (d_ycorr is scratch here)
+    HCHK(hipMemcpyAsync(ycorr, h->cm.d_ycorr, (size_t)h->N * sizeof(double), out, h->stream));
+    HCHK(hipMemcpyAsync(beta, h->cm.d_beta + hs.col0, (size_t)hs.ncol * sizeof(double), out, h->stream));
+    HCHK(hipMemcpyAsync(varBeta, h->mm.d_varBeta + hs.vb_off, (size_t)nvbs * sizeof(double), out, h->stream));
     if (dev) {
-        if (delta) hipLaunchKernelGGL(k_delta_widen, dim3((unsigned)((hs.ncol + 255) / 256)), dim3(256), 0, h->stream, (const uint8_t *)(h->d_delta + hs.col0), (long long *)delta, (long long)hs.ncol);
-        if (piHat) hipLaunchKernelGGL(k_get_pi_dev, dim3(1), dim3(1), 0, h->stream, (const DSet *)h->d_sets, (int)set_id, piHat);
+        if (delta) hipLaunchKernelGGL(k_delta_widen, dim3((unsigned)((hs.ncol + 255) / 256)), dim3(256), 0, h->stream, (const uint8_t *)(h->cm.d_delta + hs.col0), (long long *)delta, (long long)hs.ncol);
+        if (piHat) hipLaunchKernelGGL(k_get_pi_dev, dim3(1), dim3(1), 0, h->stream, (const DSet *)h->cm.d_sets, (int)set_id, piHat);
     }
     HCHK(hipStreamSynchronize(h->stream));
     HCHK(hipGetLastError());
@@ -2246,12 +2254,12 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
     if (dev) return NGP_OK;
     if (delta) {
         std::vector<uint8_t> d((size_t)hs.ncol);
-        HCHK(hipMemcpy(d.data(), h->d_delta + hs.col0, (size_t)hs.ncol, hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(d.data(), h->cm.d_delta + hs.col0, (size_t)hs.ncol, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < hs.ncol; k++) delta[k] = d[k];
     }
     if (piHat) {
         DSet ds;
-        HCHK(hipMemcpy(&ds, h->d_sets + set_id, sizeof(DSet), hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(&ds, h->cm.d_sets + set_id, sizeof(DSet), hipMemcpyDeviceToHost));
         piHat[0] = ds.piHat0; piHat[1] = ds.piHat1;
     }
     return NGP_OK;
@@ -2297,10 +2305,10 @@ int32_t ngp_profile_iteration(ngp_handle *h, double *avg_ms, int64_t *launches, 
     const int64_t n = (h->plan.mode == 1) ? 1 : h->NBLK;
     std::vector<hipEvent_t> evs((size_t)(2 * n));
     for (auto &e : evs) HCHK(hipEventCreate(&e));
-    if (h->trace_cap < 1) {
-        if ((rc = dalloc(h, &h->d_tr_varE, 1))) return rc;
-        if ((rc = dalloc(h, &h->d_tr_b, 1))) return rc;
-        h->trace_cap = 1;
+    if (h->hm.trace_cap < 1) {
+        if ((rc = h->hm.d_tr_varE.alloc(h, 1))) return rc;
+        if ((rc = h->hm.d_tr_b.alloc(h, 1))) return rc;
+        h->hm.trace_cap = 1;
     }
     h->ntrace = 1;
     CuLease lease(h);
@@ -2328,9 +2336,9 @@ int32_t ngp_debug_stamps(ngp_handle *h, int32_t enable, uint64_t *out, int64_t n
     int rc;
     if ((rc = enter(h))) return rc;
     const size_t words = (size_t)2 << 20;
-    if (enable && !h->d_dbg) { if ((rc = dalloc(h, &h->d_dbg, words))) return rc; HCHK(hipStreamSynchronize(h->stream)); }
-    if (out && h->d_dbg) HCHK(hipMemcpy(out, h->d_dbg, std::min<size_t>((size_t)n, words) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (!enable && h->d_dbg) { HCHK(hipStreamSynchronize(h->stream)); dfree(h->d_dbg); }
+    if (enable && !h->hm.d_dbg) { if ((rc = h->hm.d_dbg.alloc(h, words))) return rc; HCHK(hipStreamSynchronize(h->stream)); }
+    if (out && h->hm.d_dbg) HCHK(hipMemcpy(out, h->hm.d_dbg, std::min<size_t>((size_t)n, words) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (!enable && h->hm.d_dbg) { HCHK(hipStreamSynchronize(h->stream)); h->hm.d_dbg.reset(); }
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2339,7 +2347,7 @@ int32_t ngp_configure(ngp_handle *h, int32_t mode, int32_t lag) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_configure must precede the panel upload");
+    REQUIRE(!h->pm, NGP_ERR_STATE, "ngp_configure must precede the panel upload");
     REQUIRE(mode == 0 || mode == 1, NGP_ERR_ARG, "mode must be 0 (per-block launches) or 1 (persistent sweep)");
     REQUIRE(lag >= 1 && lag <= NGP_MAX_LAG, NGP_ERR_ARG, "lag must be in 1..12 (above 8: compact storage)");
     h->req.mode = mode; h->req.lag = lag; h->req.lag_auto = false;
@@ -2351,7 +2359,7 @@ int32_t ngp_set_near_lags(ngp_handle *h, int32_t near) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_near_lags must precede the panel upload");
+    REQUIRE(!h->pm, NGP_ERR_STATE, "ngp_set_near_lags must precede the panel upload");
     REQUIRE(near >= 0 && near <= 4, NGP_ERR_ARG, "near lags: 0 (automatic) or 1..4");
     h->req.near_req = near;
     return NGP_OK;
@@ -2402,13 +2410,12 @@ int32_t ngp_draws_indexed(ngp_handle *h, uint64_t iter, uint64_t kind, uint64_t 
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(out && n > 0, NGP_ERR_ARG, "bad output buffer");
-    double *d = nullptr;
-    if ((rc = dalloc(h, &d, (size_t)n))) return rc;
+    DevArray<double> d;
+    if ((rc = d.alloc(h, (size_t)n))) return rc;
     hipLaunchKernelGGL(k_draws_indexed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->seed, (uint64_t)h->chain, iter, kind,
                        index0, what, p1, p2, (long long)n, d);
     hipError_t e = hipMemcpyAsync(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    dfree(d);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("draws: ") + hipGetErrorString(e));
     return NGP_OK;
     NGP_CATCH(h)
@@ -2419,14 +2426,13 @@ int32_t ngp_eval_math(ngp_handle *h, int32_t which, const double *in, int64_t n,
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(in && out && n > 0, NGP_ERR_ARG, "bad buffers");
-    double *di = nullptr, *dout = nullptr;
-    if ((rc = dalloc(h, &di, (size_t)n))) return rc;
-    if ((rc = dalloc(h, &dout, (size_t)n))) { dfree(di); return rc; }
+    DevArray<double> di, dout;
+    if ((rc = di.alloc(h, (size_t)n))) return rc;
+    if ((rc = dout.alloc(h, (size_t)n))) return rc;
     hipError_t e = hipMemcpyAsync(di, in, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream);
     hipLaunchKernelGGL(k_eval_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, which, di, (long long)n, dout);
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    dfree(di); dfree(dout);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("eval_math: ") + hipGetErrorString(e));
     return NGP_OK;
     NGP_CATCH(h)
@@ -2461,7 +2467,7 @@ int32_t ngp_set_streamer(ngp_handle *h, int32_t variant) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_streamer must precede the panel upload");
+    REQUIRE(!h->pm, NGP_ERR_STATE, "ngp_set_streamer must precede the panel upload");
     REQUIRE((variant >= 0 && variant <= 2) || variant == 4 || variant == 6, NGP_ERR_ARG,
             "streamer variant: 0 (automatic), 1 (phase streamer), 2 (row-owning waves) or 4 / 6 (row-owning waves, two / three shards per workgroup)");
     h->req.streamer_req = variant;
@@ -2473,7 +2479,7 @@ int32_t ngp_set_max_shards(ngp_handle *h, int32_t max_shards) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_max_shards must precede the panel upload");
+    REQUIRE(!h->pm, NGP_ERR_STATE, "ngp_set_max_shards must precede the panel upload");
     REQUIRE(max_shards >= 0, NGP_ERR_ARG, "max_shards: 0 (automatic) or a positive number of streamer workgroups");
     h->req.max_shards_req = max_shards;
     return NGP_OK;
@@ -2502,7 +2508,7 @@ int32_t ngp_share_panel(ngp_handle *h, ngp_handle *owner) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(owner && owner != h && owner->d_tiles != nullptr && owner->pm != nullptr, NGP_ERR_ARG, "ngp_share_panel: the owner has no panel");
+    REQUIRE(owner && owner != h && owner->pm, NGP_ERR_ARG, "ngp_share_panel: the owner has no panel");
     REQUIRE(owner->device == h->device, NGP_ERR_ARG, "ngp_share_panel: both handles must be on one device");
     REQUIRE(!owner->panel_open, NGP_ERR_STATE, "ngp_share_panel: the owner's panel is still open (ngp_end_panel)");
     HCHK(hipStreamSynchronize(owner->stream));
@@ -2534,7 +2540,7 @@ int32_t ngp_set_storage(ngp_handle *h, int32_t storage) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles == nullptr, NGP_ERR_STATE, "ngp_set_storage must precede the panel upload");
+    REQUIRE(!h->pm, NGP_ERR_STATE, "ngp_set_storage must precede the panel upload");
     REQUIRE(storage == NGP_STORAGE_F32 || storage == NGP_STORAGE_U8, NGP_ERR_ARG, "storage: 0 (fp32 tiles) or 1 (compact: bytes + column means)");
     REQUIRE(storage == NGP_STORAGE_F32 || h->h_rw.empty(), NGP_ERR_ARG,
             "residual weights with compact storage (NGP_STORAGE_U8) are not supported: the byte tiles centre analytically and cannot carry row scales");
@@ -2549,10 +2555,10 @@ int32_t ngp_get_storage(ngp_handle *h, int32_t *storage, double *means, int64_t 
     if ((rc = enter(h))) return rc;
     if (storage) *storage = h->req.storage;
     if (means) {
-        REQUIRE(h->d_tiles != nullptr && h->d_mean != nullptr, NGP_ERR_STATE, "column means exist after the panel is set");
+        REQUIRE(h->pm, NGP_ERR_STATE, "column means exist after the panel is set");
         REQUIRE(P == h->P, NGP_ERR_ARG, "means buffer must hold P entries");
         HCHK(hipStreamSynchronize(h->stream));
-        HCHK(hipMemcpy(means, h->d_mean, (size_t)P * sizeof(double), hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(means, h->pm->mean, (size_t)P * sizeof(double), hipMemcpyDeviceToHost));
     }
     return NGP_OK;
     NGP_CATCH(h)
@@ -2573,23 +2579,23 @@ int32_t ngp_set_posterior_sums(ngp_handle *h, const double *sum_beta, const doub
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->have_y, NGP_ERR_STATE, "panel / y not set");
+    REQUIRE(h->pm && h->have_y, NGP_ERR_STATE, "panel / y not set");
     REQUIRE(sum_beta && sum_beta2 && sum_delta && nKept >= 0 && std::isfinite(sum_varE) && std::isfinite(sum_b), NGP_ERR_ARG, "bad posterior sums");
     REQUIRE(h->nvb == 0 || sum_varBeta, NGP_ERR_ARG, "sum_varBeta missing");
     REQUIRE(h->sets.empty() || sum_pi, NGP_ERR_ARG, "sum_pi missing");
     HCHK(hipStreamSynchronize(h->stream));
     const size_t pb = (size_t)h->P * sizeof(double);
-    HCHK(hipMemcpy(h->d_sum_beta, sum_beta, pb, hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->d_sum_beta2, sum_beta2, pb, hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->d_sum_delta, sum_delta, pb, hipMemcpyHostToDevice));
-    if (h->nvb) HCHK(hipMemcpy(h->d_sum_varBeta, sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_sum_beta, sum_beta, pb, hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_sum_beta2, sum_beta2, pb, hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_sum_delta, sum_delta, pb, hipMemcpyHostToDevice));
+    if (h->nvb) HCHK(hipMemcpy(h->mm.d_sum_varBeta, sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyHostToDevice));
     for (size_t si = 0; si < h->sets.size(); si++)
-        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)si, sum_pi[2 * si], sum_pi[2 * si + 1]);
+        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, sum_pi[2 * si], sum_pi[2 * si + 1]);
     HCHK(hipStreamSynchronize(h->stream));
     DScal sc;
-    HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
     sc.sum_varE = sum_varE; sc.sum_b = sum_b; sc.nKept = nKept;
-    HCHK(hipMemcpy(h->d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2606,7 +2612,7 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->have_y, NGP_ERR_STATE, "panel / y not set");
+    REQUIRE(h->pm && h->have_y, NGP_ERR_STATE, "panel / y not set");
     REQUIRE(path != nullptr, NGP_ERR_ARG, "null path");
     REQUIRE(!h->poisoned, NGP_ERR_STATE, "the chain state is invalid (abandoned sweep)");
     const size_t N = (size_t)h->N, P = (size_t)h->P, nvb = (size_t)h->nvb, ns = h->sets.size();
@@ -2617,14 +2623,14 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     int64_t iter = 0, nk = 0;
     if ((rc = ngp_get_state(h, yc.data(), be.data(), de.data(), vb.data(), pi.data(), &varE, &b, &iter))) return rc;
     if ((rc = ngp_get_posterior_sums(h, sb.data(), sb2.data(), sd.data(), sv.data(), sp.data(), &svE, &sbb, &nk))) return rc;
-    if (h->d_rs) HCHK(hipMemcpy(yc.data(), h->d_ycorr, N * sizeof(double), hipMemcpyDeviceToHost));  // weighted: the scaled y~ as it is (bit-exact resume)
+    if (h->cm.d_rs) HCHK(hipMemcpy(yc.data(), h->cm.d_ycorr, N * sizeof(double), hipMemcpyDeviceToHost));  // weighted: the scaled y~ as it is (bit-exact resume)
     std::vector<uint8_t> d8(P);
     for (size_t k = 0; k < P; k++) d8[k] = (uint8_t)(de[k] != 0);
     const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
+    File f(fopen(tmp.c_str(), "wb"));
     if (!f) return fail(h, NGP_ERR_ARG, "cannot open " + tmp + " for writing");
     bool ok = true;
-    auto W = [&](const void *p, size_t n) { if (n && fwrite(p, 1, n, f) != n) ok = false; };
+    auto W = [&](const void *p, size_t n) { if (n && fwrite(p, 1, n, f.get()) != n) ok = false; };
     const int64_t hdr[6] = {h->N, h->P, h->nvb, (int64_t)ns, iter, nk};
     const uint64_t ids[2] = {h->seed, (uint64_t)h->chain};
     const double scal[4] = {varE, b, svE, sbb};
@@ -2632,42 +2638,42 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     {   // model signature: a snapshot only loads into the model it was taken from (equal counts are not enough)
         for (auto &hs : h->sets) { const int64_t sg[5] = {hs.method, hs.K + 16 * hs.tk, hs.nreg, hs.col0, hs.ncol}; W(sg, sizeof(sg)); }
         // (weighted residuals: bit 62 of the fixed-set count says so, and a digest of the weights follows it -- unweighted bytes unchanged)
-        const int64_t nfs = (int64_t)h->fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->rnd.empty() ? 0 : NGP_SNAP_RANDOM);
+        const int64_t nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM);
         W(&nfs, 8);
         if (!h->h_rw.empty()) { const uint64_t dg = weights_digest(h->h_rw); W(&dg, 8); }
-        if (!h->rnd.empty()) {  // random-effect sets: int64 nrand | per set int64 q, uint64 digest of its levels and K
-            const int64_t nr = (int64_t)h->rnd.size();
+        if (!h->mm.rnd.empty()) {  // random-effect sets: int64 nrand | per set int64 q, uint64 digest of its levels and K
+            const int64_t nr = (int64_t)h->mm.rnd.size();
             W(&nr, 8);
-            for (auto &R : h->rnd) { W(&R.q, 8); W(&R.sig, 8); }
+            for (auto &R : h->mm.rnd) { W(&R.q, 8); W(&R.sig, 8); }
         }
-        for (auto &fx : h->fix) W(&fx.ncol, 8);
+        for (auto &fx : h->mm.fix) W(&fx.ncol, 8);
     }
     W(scal, sizeof(scal));
     W(yc.data(), N * 8); W(be.data(), P * 8); W(d8.data(), P); W(vb.data(), nvb * 8); W(pi.data(), 2 * ns * 8);
     W(sb.data(), P * 8); W(sb2.data(), P * 8); W(sd.data(), P * 8); W(sv.data(), nvb * 8); W(sp.data(), 2 * ns * 8);
     for (auto &hs : h->sets) W(&hs.fine_calls, 8);
     {   // fixed-effect sets beyond the intercept: effects and their posterior sums
-        std::vector<double> fb((size_t)std::max<int64_t>(h->nfixcol, 1)), fs((size_t)std::max<int64_t>(h->nfixcol, 1));
+        std::vector<double> fb((size_t)std::max<int64_t>(h->mm.nfixcol, 1)), fs((size_t)std::max<int64_t>(h->mm.nfixcol, 1));
         int64_t nf = 0;
-        if ((rc = ngp_get_fixed(h, fb.data(), fs.data(), &nf))) { fclose(f); remove(tmp.c_str()); return rc; }
+        if ((rc = ngp_get_fixed(h, fb.data(), fs.data(), &nf))) { f.reset(); remove(tmp.c_str()); return rc; }
         W(&nf, 8); W(fb.data(), (size_t)nf * 8); W(fs.data(), (size_t)nf * 8);
     }
     for (size_t si = 0; si < ns; si++)  // BayesR sets: class probabilities and their posterior sums (K each)
         if (h->sets[si].K > 0) {
             double cp[NGP_RMAX], cs[NGP_RMAX];
             int64_t K = 0;
-            if ((rc = ngp_get_class_state(h, (int32_t)si, cp, cs, &K))) { fclose(f); remove(tmp.c_str()); return rc; }
+            if ((rc = ngp_get_class_state(h, (int32_t)si, cp, cs, &K))) { f.reset(); remove(tmp.c_str()); return rc; }
             W(cp, (size_t)K * 8); W(cs, (size_t)K * 8);
         }
-    for (size_t r = 0; r < h->rnd.size() && ok; r++) {  // random-effect sets: u[q] | sum_u[q] | varU | sum_varU | fine_calls
-        const HRand &R = h->rnd[r];
+    for (size_t r = 0; r < h->mm.rnd.size() && ok; r++) {  // random-effect sets: u[q] | sum_u[q] | varU | sum_varU | fine_calls
+        const HRand &R = h->mm.rnd[r];
         std::vector<double> a((size_t)R.q), b2((size_t)R.q);
         double vu[2];
         if (hipMemcpy(a.data(), R.d_u, a.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(b2.data(), R.d_sum_u, b2.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost) != hipSuccess) { fclose(f); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the random-effect sets"); }
+            hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost) != hipSuccess) { f.reset(); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the random-effect sets"); }
         W(a.data(), a.size() * 8); W(b2.data(), b2.size() * 8); W(vu, sizeof(vu)); W(&R.fine_calls, 8);
     }
-    if (fclose(f) != 0) ok = false;
+    if (fclose(f.release()) != 0) ok = false;  // (a failed close is a failed write)
     if (!ok || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return fail(h, NGP_ERR_ARG, std::string("writing the snapshot failed: ") + path); }
     return NGP_OK;
     NGP_CATCH(h)
@@ -2677,19 +2683,17 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->have_y, NGP_ERR_STATE, "panel / y not set (build the model first, then load the snapshot)");
+    REQUIRE(h->pm && h->have_y, NGP_ERR_STATE, "panel / y not set (build the model first, then load the snapshot)");
     REQUIRE(path != nullptr, NGP_ERR_ARG, "null path");
-    FILE *f = fopen(path, "rb");
+    File f(fopen(path, "rb"));
     if (!f) return fail(h, NGP_ERR_ARG, std::string("cannot open snapshot ") + path);
     bool ok = true;
-    auto Rd = [&](void *p, size_t n) { if (n && fread(p, 1, n, f) != n) ok = false; };
+    auto Rd = [&](void *p, size_t n) { if (n && fread(p, 1, n, f.get()) != n) ok = false; };
     char magic[8]; int64_t hdr[6] = {0, 0, 0, 0, 0, 0}; uint64_t ids[2] = {0, 0}; double scal[4] = {0, 0, 0, 0};
     Rd(magic, 8); Rd(hdr, sizeof(hdr)); Rd(ids, sizeof(ids));
-    if (!ok || memcmp(magic, "NGPSNAP2", 8) != 0) { fclose(f); return fail(h, NGP_ERR_ARG, "not a snapshot file (bad magic or truncated header)"); }
-    if (hdr[0] != h->N || hdr[1] != h->P || hdr[2] != h->nvb || hdr[3] != (int64_t)h->sets.size() || hdr[4] < 0 || hdr[5] < 0) {
-        fclose(f);
+    if (!ok || memcmp(magic, "NGPSNAP2", 8) != 0) return fail(h, NGP_ERR_ARG, "not a snapshot file (bad magic or truncated header)");
+    if (hdr[0] != h->N || hdr[1] != h->P || hdr[2] != h->nvb || hdr[3] != (int64_t)h->sets.size() || hdr[4] < 0 || hdr[5] < 0)
         return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (N, P, variance components or marker sets differ)");
-    }
     {   // model signature
         bool same = true;
         for (auto &hs : h->sets) {
@@ -2704,45 +2708,35 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         uint64_t dg = 0;
         if (snap_w) { nfs &= ~NGP_SNAP_WEIGHTED; Rd(&dg, 8); }
         if (snap_r) nfs &= ~NGP_SNAP_RANDOM;
-        if (ok && snap_r != !h->rnd.empty()) {
-            fclose(f);
+        if (ok && snap_r != !h->mm.rnd.empty())
             return fail(h, NGP_ERR_ARG, snap_r ? "snapshot of a chain with random-effect sets: this handle has none (ngp_add_random_set)"
                                                : "snapshot of a chain without random-effect sets: this handle has them");
-        }
         if (snap_r) {
             int64_t nr = -1;
             Rd(&nr, 8);
-            bool rsame = ok && nr == (int64_t)h->rnd.size();
-            for (size_t r = 0; rsame && r < h->rnd.size(); r++) {
+            bool rsame = ok && nr == (int64_t)h->mm.rnd.size();
+            for (size_t r = 0; rsame && r < h->mm.rnd.size(); r++) {
                 int64_t q = -1; uint64_t sg = 0;
                 Rd(&q, 8); Rd(&sg, 8);
-                rsame = ok && q == h->rnd[r].q && sg == h->rnd[r].sig;
+                rsame = ok && q == h->mm.rnd[r].q && sg == h->mm.rnd[r].sig;
             }
-            if (!rsame) {
-                fclose(f);
+            if (!rsame)
                 return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its random-effect sets differ: levels, level coding or K)");
-            }
         }
-        if (ok && snap_w != !h->h_rw.empty()) {
-            fclose(f);
+        if (ok && snap_w != !h->h_rw.empty())
             return fail(h, NGP_ERR_ARG, snap_w ? "snapshot of a chain with residual weights: this handle has none (ngp_set_residual_weights)"
                                                : "snapshot of a chain without residual weights: this handle has them");
-        }
-        if (ok && snap_w && dg != weights_digest(h->h_rw)) {
-            fclose(f);
+        if (ok && snap_w && dg != weights_digest(h->h_rw))
             return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its residual weights differ)");
-        }
-        same = same && ok && nfs == (int64_t)h->fix.size();
+        same = same && ok && nfs == (int64_t)h->mm.fix.size();
         if (same)
-            for (auto &fx : h->fix) { int64_t nc = -1; Rd(&nc, 8); same = same && nc == fx.ncol; }
-        if (!ok) { fclose(f); return fail(h, NGP_ERR_ARG, "snapshot file is truncated (model signature)"); }
-        if (!same) {
-            fclose(f);
+            for (auto &fx : h->mm.fix) { int64_t nc = -1; Rd(&nc, 8); same = same && nc == fx.ncol; }
+        if (!ok) return fail(h, NGP_ERR_ARG, "snapshot file is truncated (model signature)");
+        if (!same)
             return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (methods, classes, regions or fixed-effect sets differ)");
-        }
     }
     Rd(scal, sizeof(scal));
-    if (ok && !(std::isfinite(scal[0]) && (scal[0] > 0.0 || (scal[0] == 0.0 && hdr[4] == 0)))) { fclose(f); return fail(h, NGP_ERR_ARG, "snapshot holds an invalid residual variance"); }
+    if (ok && !(std::isfinite(scal[0]) && (scal[0] > 0.0 || (scal[0] == 0.0 && hdr[4] == 0)))) return fail(h, NGP_ERR_ARG, "snapshot holds an invalid residual variance");
     const size_t N = (size_t)h->N, P = (size_t)h->P, nvb = (size_t)h->nvb, ns = h->sets.size();
     std::vector<double> yc(N), be(P), vb(std::max<size_t>(nvb, 1)), pi(2 * std::max<size_t>(ns, 1)), sb(P), sb2(P), sd(P), sv(std::max<size_t>(nvb, 1)),
         sp(2 * std::max<size_t>(ns, 1));
@@ -2752,31 +2746,30 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
     Rd(sb.data(), P * 8); Rd(sb2.data(), P * 8); Rd(sd.data(), P * 8); Rd(sv.data(), nvb * 8); Rd(sp.data(), 2 * ns * 8); Rd(fc.data(), ns * 8);
     int64_t nf = -1;
     Rd(&nf, 8);
-    if (ok && nf != h->nfixcol) { fclose(f); return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (fixed-effect columns differ)"); }
-    std::vector<double> fb((size_t)std::max<int64_t>(h->nfixcol, 1)), fs((size_t)std::max<int64_t>(h->nfixcol, 1));
-    Rd(fb.data(), (size_t)h->nfixcol * 8); Rd(fs.data(), (size_t)h->nfixcol * 8);
+    if (ok && nf != h->mm.nfixcol) return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (fixed-effect columns differ)");
+    std::vector<double> fb((size_t)std::max<int64_t>(h->mm.nfixcol, 1)), fs((size_t)std::max<int64_t>(h->mm.nfixcol, 1));
+    Rd(fb.data(), (size_t)h->mm.nfixcol * 8); Rd(fs.data(), (size_t)h->mm.nfixcol * 8);
     std::vector<double> cls((size_t)2 * std::max<int64_t>(h->nclass_total, 1));
     Rd(cls.data(), (size_t)2 * h->nclass_total * 8);
-    std::vector<std::vector<double>> ru(h->rnd.size()), rsu(h->rnd.size());
-    std::vector<double> rvu(2 * h->rnd.size() + 1);
-    std::vector<uint64_t> rfc(h->rnd.size() + 1);
-    for (size_t r = 0; r < h->rnd.size(); r++) {
-        ru[r].resize((size_t)h->rnd[r].q); rsu[r].resize((size_t)h->rnd[r].q);
+    std::vector<std::vector<double>> ru(h->mm.rnd.size()), rsu(h->mm.rnd.size());
+    std::vector<double> rvu(2 * h->mm.rnd.size() + 1);
+    std::vector<uint64_t> rfc(h->mm.rnd.size() + 1);
+    for (size_t r = 0; r < h->mm.rnd.size(); r++) {
+        ru[r].resize((size_t)h->mm.rnd[r].q); rsu[r].resize((size_t)h->mm.rnd[r].q);
         Rd(ru[r].data(), ru[r].size() * 8); Rd(rsu[r].data(), rsu[r].size() * 8); Rd(rvu.data() + 2 * r, 16); Rd(rfc.data() + r, 8);
     }
     char extra;
-    const bool at_end = fread(&extra, 1, 1, f) == 0;
-    fclose(f);
+    const bool at_end = fread(&extra, 1, 1, f.get()) == 0;
     if (!ok || !at_end) return fail(h, NGP_ERR_ARG, "snapshot file is truncated or has trailing bytes");
     std::vector<int64_t> de(P);
     for (size_t k = 0; k < P; k++) de[k] = d8[k];
     h->poisoned = true;  // until the whole restore has gone through: a failure half-way must not leave a mixed state behind as valid
     if ((rc = ngp_set_state(h, yc.data(), be.data(), de.data(), vb.data(), pi.data(), scal[0], scal[1], hdr[4]))) { h->poisoned = true; return rc; }
-    if (h->d_rs) HCHK(hipMemcpy(h->d_ycorr, yc.data(), N * sizeof(double), hipMemcpyHostToDevice));  // weighted: y~ as saved, not s (y~ / s)
+    if (h->cm.d_rs) HCHK(hipMemcpy(h->cm.d_ycorr, yc.data(), N * sizeof(double), hipMemcpyHostToDevice));  // weighted: y~ as saved, not s (y~ / s)
     h->poisoned = true;  // (ngp_set_state has just declared the state valid: not before the sums, fixed effects and classes are in)
     if ((rc = ngp_set_posterior_sums(h, sb.data(), sb2.data(), sd.data(), sv.data(), sp.data(), scal[2], scal[3], hdr[5]))) return rc;
     for (size_t si = 0; si < ns; si++) h->sets[si].fine_calls = fc[si];
-    if (h->nfixcol > 0 && (rc = ngp_set_fixed(h, fb.data(), fs.data(), h->nfixcol))) return rc;
+    if (h->mm.nfixcol > 0 && (rc = ngp_set_fixed(h, fb.data(), fs.data(), h->mm.nfixcol))) return rc;
     {
         size_t off = 0;
         for (size_t si = 0; si < ns; si++)
@@ -2786,8 +2779,8 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
                 off += 2 * K;
             }
     }
-    for (size_t r = 0; r < h->rnd.size(); r++) {
-        HRand &R = h->rnd[r];
+    for (size_t r = 0; r < h->mm.rnd.size(); r++) {
+        HRand &R = h->mm.rnd[r];
         HCHK(hipMemcpy(R.d_u, ru[r].data(), ru[r].size() * 8, hipMemcpyHostToDevice));
         HCHK(hipMemcpy(R.d_sum_u, rsu[r].data(), rsu[r].size() * 8, hipMemcpyHostToDevice));
         HCHK(hipMemcpy(R.d_vu, rvu.data() + 2 * r, 16, hipMemcpyHostToDevice));
@@ -2803,15 +2796,15 @@ int32_t ngp_set_trace_loci(ngp_handle *h, const int64_t *loci, int64_t n, int64_
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(n >= 0 && n <= 4096 && (n == 0 || loci) && n_varBeta >= 0, NGP_ERR_ARG, "at most 4096 traced loci");
     for (int64_t i = 0; i < n; i++) REQUIRE(loci[i] >= 0 && loci[i] < h->P, NGP_ERR_ARG, "traced locus outside the panel");
     HCHK(hipStreamSynchronize(h->stream));
-    dfree(h->d_trace_loci); dfree(h->d_tr_beta); dfree(h->d_tr_vb); dfree(h->d_tr_pi);
-    h->trace_ext_cap = 0; h->ntl = n; h->ntvb = n_varBeta;
+    h->mm.d_trace_loci.reset(); h->mm.d_tr_beta.reset(); h->mm.d_tr_vb.reset(); h->mm.d_tr_pi.reset();
+    h->mm.trace_ext_cap = 0; h->mm.ntl = n; h->mm.ntvb = n_varBeta;
     if (n == 0 && n_varBeta == 0) return NGP_OK;
-    if ((rc = dalloc(h, &h->d_trace_loci, (size_t)std::max<int64_t>(n, 1)))) return rc;
-    if (n) HCHK(hipMemcpy(h->d_trace_loci, loci, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+    if ((rc = h->mm.d_trace_loci.alloc(h, (size_t)std::max<int64_t>(n, 1)))) return rc;
+    if (n) HCHK(hipMemcpy(h->mm.d_trace_loci, loci, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2820,15 +2813,15 @@ int32_t ngp_get_trace_ext(ngp_handle *h, double *beta_tr, double *varBeta_tr, do
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_trace_loci != nullptr, NGP_ERR_STATE, "no traces requested (ngp_set_trace_loci)");
-    n = std::min(n, std::min(h->ntrace, h->trace_ext_cap));
+    REQUIRE(h->mm.d_trace_loci != nullptr, NGP_ERR_STATE, "no traces requested (ngp_set_trace_loci)");
+    n = std::min(n, std::min(h->ntrace, h->mm.trace_ext_cap));
     if (n <= 0) return NGP_OK;
     HCHK(hipStreamSynchronize(h->stream));
-    const int64_t ntvb = std::min<int64_t>(h->ntvb, h->nvb);
-    REQUIRE(ntvb == h->ntvb, NGP_ERR_STATE, "more variance traces requested than the model has variance components");
-    if (beta_tr && h->ntl) HCHK(hipMemcpy(beta_tr, h->d_tr_beta, (size_t)(n * h->ntl) * sizeof(double), hipMemcpyDeviceToHost));
-    if (varBeta_tr && h->ntvb) HCHK(hipMemcpy(varBeta_tr, h->d_tr_vb, (size_t)(n * h->ntvb) * sizeof(double), hipMemcpyDeviceToHost));
-    if (pi_tr && !h->sets.empty()) HCHK(hipMemcpy(pi_tr, h->d_tr_pi, (size_t)n * h->sets.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int64_t ntvb = std::min<int64_t>(h->mm.ntvb, h->nvb);
+    REQUIRE(ntvb == h->mm.ntvb, NGP_ERR_STATE, "more variance traces requested than the model has variance components");
+    if (beta_tr && h->mm.ntl) HCHK(hipMemcpy(beta_tr, h->mm.d_tr_beta, (size_t)(n * h->mm.ntl) * sizeof(double), hipMemcpyDeviceToHost));
+    if (varBeta_tr && h->mm.ntvb) HCHK(hipMemcpy(varBeta_tr, h->mm.d_tr_vb, (size_t)(n * h->mm.ntvb) * sizeof(double), hipMemcpyDeviceToHost));
+    if (pi_tr && !h->sets.empty()) HCHK(hipMemcpy(pi_tr, h->mm.d_tr_pi, (size_t)n * h->sets.size() * sizeof(double), hipMemcpyDeviceToHost));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2867,15 +2860,15 @@ struct Rccl {
 
 int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp_export_posterior_device
     const size_t pb = (size_t)h->P * sizeof(double);
-    HCHK(hipMemcpyAsync(h->d_sum_beta, o, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(h->d_sum_beta2, o + h->P, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(h->d_sum_delta, o + 2 * h->P, pb, hipMemcpyDeviceToDevice, h->stream));
-    if (h->nvb) HCHK(hipMemcpyAsync(h->d_sum_varBeta, o + 3 * h->P, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->nfixcol + (size_t)h->nrandcol + h->rnd.size() + 3);
+    HCHK(hipMemcpyAsync(h->cm.d_sum_beta, o, pb, hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipMemcpyAsync(h->cm.d_sum_beta2, o + h->P, pb, hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipMemcpyAsync(h->cm.d_sum_delta, o + 2 * h->P, pb, hipMemcpyDeviceToDevice, h->stream));
+    if (h->nvb) HCHK(hipMemcpyAsync(h->mm.d_sum_varBeta, o + 3 * h->P, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size() + 3);
     HCHK(hipMemcpyAsync(tail.data(), o + 3 * h->P + h->nvb, tail.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
     for (size_t si = 0; si < h->sets.size(); si++)
-        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, (int)si, tail[2 * si], tail[2 * si + 1]);
+        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, tail[2 * si], tail[2 * si + 1]);
     {
         size_t off = 2 * h->sets.size();
         for (size_t si = 0; si < h->sets.size(); si++)
@@ -2886,21 +2879,21 @@ int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp
             }
     }
     const size_t tf = 2 * h->sets.size() + (size_t)h->nclass_total;
-    if (h->nfixcol > 0) HCHK(hipMemcpy(h->d_sum_bfix, tail.data() + tf, (size_t)h->nfixcol * sizeof(double), hipMemcpyHostToDevice));
+    if (h->mm.nfixcol > 0) HCHK(hipMemcpy(h->mm.d_sum_bfix, tail.data() + tf, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyHostToDevice));
     DScal sc;
-    HCHK(hipMemcpy(&sc, h->d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
     {
-        const size_t r_at = tf + (size_t)h->nfixcol;
+        const size_t r_at = tf + (size_t)h->mm.nfixcol;
         size_t off = r_at;
-        for (size_t r = 0; r < h->rnd.size(); r++) {
-            HCHK(hipMemcpy(h->rnd[r].d_sum_u, tail.data() + off, (size_t)h->rnd[r].q * sizeof(double), hipMemcpyHostToDevice));
-            HCHK(hipMemcpy(h->rnd[r].d_vu + 1, tail.data() + r_at + (size_t)h->nrandcol + r, sizeof(double), hipMemcpyHostToDevice));
-            off += (size_t)h->rnd[r].q;
+        for (size_t r = 0; r < h->mm.rnd.size(); r++) {
+            HCHK(hipMemcpy(h->mm.rnd[r].d_sum_u, tail.data() + off, (size_t)h->mm.rnd[r].q * sizeof(double), hipMemcpyHostToDevice));
+            HCHK(hipMemcpy(h->mm.rnd[r].d_vu + 1, tail.data() + r_at + (size_t)h->mm.nrandcol + r, sizeof(double), hipMemcpyHostToDevice));
+            off += (size_t)h->mm.rnd[r].q;
         }
     }
-    const size_t t0 = tf + (size_t)h->nfixcol + (size_t)h->nrandcol + h->rnd.size();
+    const size_t t0 = tf + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size();
     sc.sum_varE = tail[t0]; sc.sum_b = tail[t0 + 1]; sc.nKept = (long long)std::llround(tail[t0 + 2]);
-    HCHK(hipMemcpy(h->d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
     HCHK(hipStreamSynchronize(h->stream));
     return NGP_OK;
 }
@@ -2945,18 +2938,25 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
     int64_t len = 0;
     if ((rc = ngp_posterior_len(h, &len))) return rc;
     for (int i = 0; i < n; i++) {
-        REQUIRE(hs[i]->d_tiles != nullptr, NGP_ERR_STATE, "ngp_allreduce_posterior: a handle has no panel");
-        REQUIRE(hs[i]->P == h->P && hs[i]->nvb == h->nvb && hs[i]->sets.size() == h->sets.size() && hs[i]->nfixcol == h->nfixcol &&
-                    hs[i]->nclass_total == h->nclass_total && hs[i]->nrandcol == h->nrandcol && hs[i]->rnd.size() == h->rnd.size(),
+        REQUIRE(hs[i]->pm, NGP_ERR_STATE, "ngp_allreduce_posterior: a handle has no panel");
+        REQUIRE(hs[i]->P == h->P && hs[i]->nvb == h->nvb && hs[i]->sets.size() == h->sets.size() && hs[i]->mm.nfixcol == h->mm.nfixcol &&
+                    hs[i]->nclass_total == h->nclass_total && hs[i]->mm.nrandcol == h->mm.nrandcol && hs[i]->mm.rnd.size() == h->mm.rnd.size(),
                 NGP_ERR_ARG, "ngp_allreduce_posterior: the chains do not share one model");
         for (int k = 0; k < i; k++) REQUIRE(hs[k] != hs[i], NGP_ERR_ARG, "ngp_allreduce_posterior: a handle is listed twice");
     }
-    std::vector<double *> buf((size_t)n, nullptr);
-    auto cleanup = [&]() { for (int i = 0; i < n; i++) if (buf[i]) { (void)hipSetDevice(hs[i]->device); (void)hipFree(buf[i]); } };
+    struct Buffers {  // the packed sums of every handle, on its device: freed there, with that device current
+        ngp_handle **hs;
+        std::vector<DevArray<double>> b;
+        ~Buffers() {
+            for (size_t i = 0; i < b.size(); i++)
+                if (b[i]) { (void)hipSetDevice(hs[i]->device); b[i].reset(); }
+        }
+    } bufs{hs, std::vector<DevArray<double>>((size_t)n)};
+    std::vector<DevArray<double>> &buf = bufs.b;
     for (int i = 0; i < n; i++) {
-        if ((rc = enter(hs[i]))) { cleanup(); return rc; }
-        if (hipMalloc((void **)&buf[i], (size_t)len * sizeof(double)) != hipSuccess) { cleanup(); return fail(h, NGP_ERR_NOMEM, "posterior buffer"); }
-        if ((rc = ngp_export_posterior_device(hs[i], buf[i], len))) { if (hs[i] != h) h->err = hs[i]->err; cleanup(); return rc; }
+        if ((rc = enter(hs[i]))) return rc;
+        if (buf[i].alloc_raw((size_t)len) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "posterior buffer");
+        if ((rc = ngp_export_posterior_device(hs[i], buf[i], len))) { if (hs[i] != h) h->err = hs[i]->err; return rc; }
     }
     // leaders: the first handle of every device; the others are added into their leader on the device
     auto devof = [](const ngp_handle *x) { return x->vdev >= 0 ? 1000 + x->vdev : x->device; };  // (virtual devices: test hook)
@@ -2975,7 +2975,7 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
             hipLaunchKernelGGL(k_add_inplace, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, L->stream, buf[leader[i]], buf[i], (long long)len);
             e = hipStreamSynchronize(L->stream);
         }
-    if (e != hipSuccess) { cleanup(); return fail(h, NGP_ERR_HIP, std::string("pooling on one device: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("pooling on one device: ") + hipGetErrorString(e));
     if (leaders.size() > 1) {
         const int nl = (int)leaders.size();
         bool one_physical = true;
@@ -2985,18 +2985,17 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
             // order -- the same packing, grouping and unpacking as across devices, everything but the ncclAllReduce call
             ngp_handle *L0 = hs[leaders[0]];
             (void)hipSetDevice(L0->device);
-            double *tot = nullptr;
-            if (hipMalloc((void **)&tot, (size_t)len * sizeof(double)) != hipSuccess) { cleanup(); return fail(h, NGP_ERR_NOMEM, "posterior buffer"); }
+            DevArray<double> tot;  // (freed at the end of this block, L0's device current)
+            if (tot.alloc_raw((size_t)len) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "posterior buffer");
             e = hipMemcpyAsync(tot, buf[leaders[0]], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, L0->stream);
             for (int i = 1; i < nl && e == hipSuccess; i++)
                 hipLaunchKernelGGL(k_add_inplace, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, L0->stream, tot, buf[leaders[i]], (long long)len);
             for (int i = 0; i < nl && e == hipSuccess; i++)
                 e = hipMemcpyAsync(buf[leaders[i]], tot, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, L0->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(L0->stream);
-            (void)hipFree(tot);
-            if (e != hipSuccess) { cleanup(); return fail(h, NGP_ERR_HIP, std::string("pooling leaders on one device: ") + hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("pooling leaders on one device: ") + hipGetErrorString(e));
         } else {
-        if (!g_rccl.load()) { cleanup(); return fail(h, NGP_ERR_HIP, g_rccl.err); }
+        if (!g_rccl.load()) return fail(h, NGP_ERR_HIP, g_rccl.err);
         std::vector<void *> comms((size_t)nl, nullptr);
         std::vector<int> devs((size_t)nl);
         for (int i = 0; i < nl; i++) devs[i] = hs[leaders[i]]->device;
@@ -3013,14 +3012,13 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
             for (int i = 0; i < nl; i++) { (void)hipSetDevice(devs[i]); (void)hipStreamSynchronize(hs[leaders[i]]->stream); }
         }
         for (int i = 0; i < nl; i++) if (comms[i]) g_rccl.CommDestroy(comms[i]);
-        if (r != 0) { cleanup(); return fail(h, NGP_ERR_HIP, std::string("RCCL all-reduce failed: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?")); }
+        if (r != 0) return fail(h, NGP_ERR_HIP, std::string("RCCL all-reduce failed: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?"));
         }
     }
     for (int i = 0; i < n; i++) {
         (void)hipSetDevice(hs[i]->device);
-        if ((rc = import_posterior_device(hs[i], buf[leader[i]]))) { if (hs[i] != h) h->err = hs[i]->err; cleanup(); return rc; }
+        if ((rc = import_posterior_device(hs[i], buf[leader[i]]))) { if (hs[i] != h) h->err = hs[i]->err; return rc; }
     }
-    cleanup();
     return NGP_OK;
     NGP_CATCH((hs ? hs[0] : nullptr))
 }
@@ -3035,7 +3033,7 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(vClass && pi && K >= 2 && K <= NGP_RMAX, NGP_ERR_ARG, "BayesR needs 2..16 variance classes with their probabilities");
     double ps = 0.0;
@@ -3046,8 +3044,8 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
     }
     REQUIRE(std::fabs(ps - 1.0) < 1e-8, NGP_ERR_ARG, "BayesR: class probabilities must sum to 1");
     REQUIRE(std::isfinite(varBeta0) && varBeta0 > 0.0, NGP_ERR_ARG, "BayesR varBeta0 must be positive");
-    if (!h->d_rcls) {
-        if ((rc = dalloc(h, &h->d_rcls, (size_t)4 * NGP_RMAX * (size_t)h->Ppad))) return rc;
+    if (!h->mm.d_rcls) {
+        if ((rc = h->mm.d_rcls.alloc(h, (size_t)4 * NGP_RMAX * (size_t)h->Ppad))) return rc;
     }
     const int64_t rs = 0, re = ncol;
     int32_t sid = -1;
@@ -3058,10 +3056,10 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
     HSet &hs = h->sets[(size_t)sid];
     hs.K = K; hs.vcls.assign(vClass, vClass + K); hs.rpi.assign(pi, pi + K);
     DSet ds;
-    HCHK(hipMemcpy(&ds, h->d_sets + sid, sizeof(DSet), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&ds, h->cm.d_sets + sid, sizeof(DSet), hipMemcpyDeviceToHost));
     ds.K = K;
     for (int v = 0; v < NGP_RMAX; v++) { ds.vcls[v] = v < K ? vClass[v] : 0.0; ds.pic[v] = 0.0; ds.logpic[v] = 0.0; ds.sum_pic[v] = 0.0; ds.ncls[v] = 0; }
-    HCHK(hipMemcpy(h->d_sets + sid, &ds, sizeof(DSet), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_sets + sid, &ds, sizeof(DSet), hipMemcpyHostToDevice));
     if ((rc = set_class_state_dev(h, sid, pi, std::vector<double>((size_t)K, 0.0).data()))) return rc;
     h->nclass_total += K;
     if (set_id) *set_id = sid;
@@ -3079,7 +3077,7 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
     REQUIRE(k >= 1 && k <= NGP_KMAX, NGP_ERR_ARG, "a tuple holds 1..4 correlated sets");
@@ -3106,24 +3104,16 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
     HSet hs{col0, span, NGP_METHOD_TUPLE, df, 0.0, nreg, h->nvb, 0, 0, 0.5, vb0};
     hs.tk = k; hs.nloc = nloc;
     const int64_t new_nvb = h->nvb + nv;
-    if (new_nvb > h->vb_cap) {
-        int64_t cap = std::max<int64_t>(new_nvb, 2 * h->vb_cap);
-        double *nvp = nullptr, *nsp = nullptr;
-        if ((rc = dalloc(h, &nvp, (size_t)cap))) return rc;
-        if ((rc = dalloc(h, &nsp, (size_t)cap))) return rc;
-        if (h->nvb > 0) {
-            HCHK(hipMemcpyAsync(nvp, h->d_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            HCHK(hipMemcpyAsync(nsp, h->d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
-        HCHK(hipStreamSynchronize(h->stream));
-        dfree(h->d_varBeta); dfree(h->d_sum_varBeta);
-        h->d_varBeta = nvp; h->d_sum_varBeta = nsp; h->vb_cap = cap;
+    if (new_nvb > h->mm.vb_cap) {
+        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
+        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
+        h->mm.vb_cap = cap;
     }
-    HCHK(hipMemcpy(h->d_varBeta + h->nvb, vb0.data(), (size_t)nv * sizeof(double), hipMemcpyHostToDevice));
-    if (!h->d_tup) {
-        if ((rc = dalloc(h, &h->d_tup, 16))) return rc;
-        if ((rc = dalloc(h, &h->d_tupc, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
-        if ((rc = dalloc(h, &h->d_tupg, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
+    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, vb0.data(), (size_t)nv * sizeof(double), hipMemcpyHostToDevice));
+    if (!h->mm.d_tup) {
+        if ((rc = h->mm.d_tup.alloc(h, 16))) return rc;
+        if ((rc = h->mm.d_tupc.alloc(h, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
+        if ((rc = h->mm.d_tupg.alloc(h, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
     }
     for (int64_t c = col0; c < std::min<int64_t>(col0 + NGP_BLK * nblk, h->Ppad); c++) h->h_setof[c] = (int8_t)-2;  // owned, no locus (unused lanes)
     for (int64_t r = 0; r < nreg; r++) {
@@ -3150,20 +3140,20 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
     memset(&tp, 0, sizeof(tp));
     tp.k = k; tp.col0 = col0; tp.nloc = nloc; tp.vb_off = h->nvb; tp.df = df;
     for (int a = 0; a < k * k; a++) tp.scale[a] = scale[a];
-    HCHK(hipMemcpy(h->d_tup + si, &tp, sizeof(DTup), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_tuple_gkk, dim3((unsigned)((nloc * k + 255) / 256)), dim3(256), 0, h->stream, h->d_gramx, h->plan.D, h->d_mpm, tp, h->d_tupg,
+    HCHK(hipMemcpy(h->mm.d_tup + si, &tp, sizeof(DTup), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_tuple_gkk, dim3((unsigned)((nloc * k + 255) / 256)), dim3(256), 0, h->stream, h->pm->gramx, h->plan.D, h->pm->mpm, tp, h->mm.d_tupg,
                        (long long)h->Ppad);
     DSet ds;
     memset(&ds, 0, sizeof(ds));
     ds.method = NGP_METHOD_TUPLE; ds.df = df; ds.col0 = col0; ds.ncol = span;
-    HCHK(hipMemcpy(h->d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->d_sets, si, 0.5, 0.5);
+    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.5, 0.5);
     HCHK(hipStreamSynchronize(h->stream));
     h->nvb = new_nvb;
     h->sets.push_back(hs);
     h->ntuple += 1;
     h->tables_dirty = true;
-    h->trace_ext_cap = 0;
+    h->mm.trace_ext_cap = 0;
     if (set_id) *set_id = si;
     return NGP_OK;
     NGP_CATCH(h)
@@ -3176,7 +3166,7 @@ int32_t ngp_get_class_state(ngp_handle *h, int32_t set_id, double *piHat, double
     REQUIRE(set_id >= 0 && set_id < (int)h->sets.size(), NGP_ERR_ARG, "unknown set id");
     HCHK(hipStreamSynchronize(h->stream));
     DSet ds;
-    HCHK(hipMemcpy(&ds, h->d_sets + set_id, sizeof(DSet), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&ds, h->cm.d_sets + set_id, sizeof(DSet), hipMemcpyDeviceToHost));
     if (K) *K = h->sets[(size_t)set_id].K;
     for (int v = 0; v < h->sets[(size_t)set_id].K; v++) {
         if (piHat) piHat[v] = ds.pic[v];
@@ -3208,10 +3198,10 @@ int32_t ngp_add_fixed_set(ngp_handle *h, const double *X, int64_t N, int64_t nco
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(X && N == h->N && ncol >= 1 && ncol <= 64 && ld >= N, NGP_ERR_ARG, "fixed-effect set: N rows, 1..64 columns");
-    REQUIRE(h->fix.size() < 16, NGP_ERR_ARG, "at most 16 fixed-effect sets");
+    REQUIRE(h->mm.fix.size() < 16, NGP_ERR_ARG, "at most 16 fixed-effect sets");
     std::vector<double> xc((size_t)N * ncol), x0((size_t)ncol * ncol), xr;
     for (int64_t a = 0; a < ncol; a++)
         for (int64_t i = 0; i < N; i++) {
@@ -3219,14 +3209,13 @@ int32_t ngp_add_fixed_set(ngp_handle *h, const double *X, int64_t N, int64_t nco
             REQUIRE(std::isfinite(v), NGP_ERR_ARG, "non-finite value in a fixed-effect column");
             xc[(size_t)a * N + i] = v;
         }
-    if (h->d_rs) {  // weighted residuals: the columns of the row-scaled problem, X~ = s X (on the device); X~'X~ below is X'WX
-        double *d_x = nullptr;
-        if ((rc = dalloc(h, &d_x, xc.size()))) return rc;
+    if (h->cm.d_rs) {  // weighted residuals: the columns of the row-scaled problem, X~ = s X (on the device); X~'X~ below is X'WX
+        DevArray<double> d_x;
+        if ((rc = d_x.alloc(h, xc.size()))) return rc;
         hipError_t e = hipMemcpyAsync(d_x, xc.data(), xc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
         for (int64_t a = 0; a < ncol && e == hipSuccess; a++) launch_rows(h, d_x + (size_t)a * N, d_x + (size_t)a * N, false);
         if (e == hipSuccess) e = hipMemcpyAsync(xc.data(), d_x, xc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        dfree(d_x);
         if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("add_fixed_set: ") + hipGetErrorString(e));
     }
     for (int64_t a = 0; a < ncol; a++)
@@ -3243,31 +3232,23 @@ int32_t ngp_add_fixed_set(ngp_handle *h, const double *X, int64_t N, int64_t nco
     }
     REQUIRE(x0[0] > 0.0 || ncol > 1, NGP_ERR_ARG, "fixed-effect column is identically zero");
     HFix fx;
-    fx.ncol = ncol; fx.off = h->nfixcol;
+    fx.ncol = ncol; fx.off = h->mm.nfixcol;
     std::vector<double> z((size_t)ncol, 0.0);
-    if ((rc = dalloc(h, &fx.d_X, xc.size()))) return rc;
-    if ((rc = dalloc(h, &fx.d_xpx0, x0.size()))) return rc;
-    if ((rc = dalloc(h, &fx.d_xpxR, xr.size()))) return rc;
-    if ((rc = dalloc(h, &fx.d_lhs0, (size_t)ncol))) return rc;
-    if ((rc = dalloc(h, &fx.d_rhs0, (size_t)ncol))) return rc;
+    if ((rc = fx.d_X.alloc(h, xc.size()))) return rc;
+    if ((rc = fx.d_xpx0.alloc(h, x0.size()))) return rc;
+    if ((rc = fx.d_xpxR.alloc(h, xr.size()))) return rc;
+    if ((rc = fx.d_lhs0.alloc(h, (size_t)ncol))) return rc;
+    if ((rc = fx.d_rhs0.alloc(h, (size_t)ncol))) return rc;
     HCHK(hipMemcpy(fx.d_X, xc.data(), xc.size() * sizeof(double), hipMemcpyHostToDevice));
     HCHK(hipMemcpy(fx.d_xpx0, x0.data(), x0.size() * sizeof(double), hipMemcpyHostToDevice));
     HCHK(hipMemcpy(fx.d_xpxR, xr.data(), xr.size() * sizeof(double), hipMemcpyHostToDevice));
     HCHK(hipMemcpy(fx.d_lhs0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
     HCHK(hipMemcpy(fx.d_rhs0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    const int64_t nn = h->nfixcol + ncol;
-    double *nb = nullptr, *nsb = nullptr;
-    if ((rc = dalloc(h, &nb, (size_t)nn))) return rc;
-    if ((rc = dalloc(h, &nsb, (size_t)nn))) return rc;
-    if (h->nfixcol > 0) {
-        HCHK(hipMemcpyAsync(nb, h->d_bfix, (size_t)h->nfixcol * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        HCHK(hipMemcpyAsync(nsb, h->d_sum_bfix, (size_t)h->nfixcol * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    }
-    HCHK(hipStreamSynchronize(h->stream));
-    dfree(h->d_bfix); dfree(h->d_sum_bfix);
-    h->d_bfix = nb; h->d_sum_bfix = nsb; h->nfixcol = nn;
-    if (set_id) *set_id = (int32_t)h->fix.size();
-    h->fix.push_back(fx);
+    const int64_t nn = h->mm.nfixcol + ncol;
+    if ((rc = grow_pair(h, h->mm.d_bfix, h->mm.d_sum_bfix, h->mm.nfixcol, nn))) return rc;
+    h->mm.nfixcol = nn;
+    if (set_id) *set_id = (int32_t)h->mm.fix.size();
+    h->mm.fix.push_back(std::move(fx));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -3276,11 +3257,11 @@ int32_t ngp_get_fixed(ngp_handle *h, double *b, double *sum_b, int64_t *ncols_to
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    if (ncols_total) *ncols_total = h->nfixcol;
-    if (h->nfixcol == 0) return NGP_OK;
+    if (ncols_total) *ncols_total = h->mm.nfixcol;
+    if (h->mm.nfixcol == 0) return NGP_OK;
     HCHK(hipStreamSynchronize(h->stream));
-    if (b) HCHK(hipMemcpy(b, h->d_bfix, (size_t)h->nfixcol * sizeof(double), hipMemcpyDeviceToHost));
-    if (sum_b) HCHK(hipMemcpy(sum_b, h->d_sum_bfix, (size_t)h->nfixcol * sizeof(double), hipMemcpyDeviceToHost));
+    if (b) HCHK(hipMemcpy(b, h->mm.d_bfix, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_b) HCHK(hipMemcpy(sum_b, h->mm.d_sum_bfix, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyDeviceToHost));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -3289,11 +3270,11 @@ int32_t ngp_set_fixed(ngp_handle *h, const double *b, const double *sum_b, int64
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(ncols_total == h->nfixcol, NGP_ERR_ARG, "fixed-effect column count mismatch");
-    if (h->nfixcol == 0) return NGP_OK;
+    REQUIRE(ncols_total == h->mm.nfixcol, NGP_ERR_ARG, "fixed-effect column count mismatch");
+    if (h->mm.nfixcol == 0) return NGP_OK;
     HCHK(hipStreamSynchronize(h->stream));
-    if (b) HCHK(hipMemcpy(h->d_bfix, b, (size_t)h->nfixcol * sizeof(double), hipMemcpyHostToDevice));
-    if (sum_b) HCHK(hipMemcpy(h->d_sum_bfix, sum_b, (size_t)h->nfixcol * sizeof(double), hipMemcpyHostToDevice));
+    if (b) HCHK(hipMemcpy(h->mm.d_bfix, b, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyHostToDevice));
+    if (sum_b) HCHK(hipMemcpy(h->mm.d_sum_bfix, sum_b, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyHostToDevice));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -3301,20 +3282,16 @@ int32_t ngp_set_fixed(ngp_handle *h, const double *b, const double *sum_b, int64
 }  // extern "C"
 
 namespace {
-void free_rand(HRand &r) {
-    dfree(r.d_lptr); dfree(r.d_kptr); dfree(r.d_lrows); dfree(r.d_level); dfree(r.d_kcol); dfree(r.d_kval); dfree(r.d_kdiag); dfree(r.d_zpz);
-    dfree(r.d_u); dfree(r.d_sum_u); dfree(r.d_vu); dfree(r.d_scr);
-}
 uint64_t bytes_digest(uint64_t x, const void *p, size_t n) {  // FNV-1a, continued from x
     const unsigned char *c = (const unsigned char *)p;
     for (size_t k = 0; k < n; k++) { x ^= c[k]; x *= 1099511628211ull; }
     return x;
 }
 template <class T>
-int upload(ngp_handle *h, T **d, const std::vector<T> &v) {
+int upload(ngp_handle *h, DevArray<T> &d, const std::vector<T> &v) {
     int rc;
-    if ((rc = dalloc(h, d, v.size()))) return rc;
-    if (!v.empty()) HCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    if ((rc = d.alloc(h, v.size()))) return rc;
+    if (!v.empty()) HCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return NGP_OK;
 }
 }  // namespace
@@ -3328,10 +3305,10 @@ int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
     REQUIRE(level != nullptr && q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: levels of N records and 1 <= q < 2^31");
-    REQUIRE(h->rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
     REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
     REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
     const bool ident = !k_ptr && !k_col && !k_val;
@@ -3403,22 +3380,21 @@ int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const
     R.sig = bytes_digest(bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull, lv.data(), lv.size() * 4), kp.data(), kp.size() * 8), kc.data(),
                                       kc.size() * 4), kv.data(), kv.size() * 8);
     const double vu[2] = {varU0, 0.0};
-    auto undo = [&](int code) { free_rand(R); return code; };
-    if ((rc = upload(h, &R.d_lptr, lp)) || (rc = upload(h, &R.d_lrows, lr)) || (rc = upload(h, &R.d_level, lv)) || (rc = upload(h, &R.d_kptr, kp)) ||
-        (rc = upload(h, &R.d_kcol, kc)) || (rc = upload(h, &R.d_kval, kv)) || (rc = upload(h, &R.d_kdiag, kd)) || (rc = upload(h, &R.d_zpz, zpz)))
-        return undo(rc);
-    if ((rc = dalloc(h, &R.d_u, (size_t)q)) || (rc = dalloc(h, &R.d_sum_u, (size_t)q)) || (rc = dalloc(h, &R.d_vu, 2)) ||
-        (rc = dalloc(h, &R.d_scr, (size_t)NGP_RS_ROWS * (size_t)q)))
-        return undo(rc);
+    if ((rc = upload(h, R.d_lptr, lp)) || (rc = upload(h, R.d_lrows, lr)) || (rc = upload(h, R.d_level, lv)) || (rc = upload(h, R.d_kptr, kp)) ||
+        (rc = upload(h, R.d_kcol, kc)) || (rc = upload(h, R.d_kval, kv)) || (rc = upload(h, R.d_kdiag, kd)) || (rc = upload(h, R.d_zpz, zpz)))
+        return rc;
+    if ((rc = R.d_u.alloc(h, (size_t)q)) || (rc = R.d_sum_u.alloc(h, (size_t)q)) || (rc = R.d_vu.alloc(h, 2)) ||
+        (rc = R.d_scr.alloc(h, (size_t)NGP_RS_ROWS * (size_t)q)))
+        return rc;
     hipError_t e = hipMemset(R.d_u, 0, (size_t)q * sizeof(double));
     if (e == hipSuccess) e = hipMemset(R.d_sum_u, 0, (size_t)q * sizeof(double));
     if (e == hipSuccess) e = hipMemset(R.d_scr, 0, (size_t)NGP_RS_ROWS * (size_t)q * sizeof(double));
     if (e == hipSuccess) e = hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice);
     if (e == hipSuccess && offdiag) e = hipFuncSetAttribute((const void *)k_rand_gs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NGP_LDS_MAX);
-    if (e != hipSuccess) { free_rand(R); return fail(h, NGP_ERR_HIP, std::string("add_random_set: ") + hipGetErrorString(e)); }
-    if (set_id) *set_id = (int32_t)h->rnd.size();
-    h->rnd.push_back(R);
-    h->nrandcol += q;
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("add_random_set: ") + hipGetErrorString(e));
+    if (set_id) *set_id = (int32_t)h->mm.rnd.size();
+    h->mm.rnd.push_back(std::move(R));
+    h->mm.nrandcol += q;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -3427,8 +3403,8 @@ int32_t ngp_get_random(ngp_handle *h, int32_t set_id, double *u, double *sum_u, 
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(set_id >= 0 && set_id < (int32_t)h->rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
-    const HRand &R = h->rnd[(size_t)set_id];
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    const HRand &R = h->mm.rnd[(size_t)set_id];
     HCHK(hipStreamSynchronize(h->stream));
     double vu[2];
     HCHK(hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost));
@@ -3444,9 +3420,9 @@ int32_t ngp_set_random(ngp_handle *h, int32_t set_id, const double *u, const dou
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(set_id >= 0 && set_id < (int32_t)h->rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     REQUIRE(std::isfinite(varU) && varU > 0.0 && std::isfinite(sum_varU), NGP_ERR_ARG, "varU must be finite and > 0, sum_varU finite");
-    const HRand &R = h->rnd[(size_t)set_id];
+    const HRand &R = h->mm.rnd[(size_t)set_id];
     if (u) for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
     if (sum_u) for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(sum_u[l]), NGP_ERR_ARG, "non-finite sum of a random effect");
     HCHK(hipStreamSynchronize(h->stream));
@@ -3464,26 +3440,26 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
-    REQUIRE(set_id >= 0 && set_id < (int32_t)h->rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     REQUIRE(ycorr && u && varU, NGP_ERR_ARG, "null state pointer");
     REQUIRE(std::isfinite(varE) && varE > 0.0, NGP_ERR_ARG, "varE must be finite and positive");
     REQUIRE(std::isfinite(*varU) && *varU > 0.0, NGP_ERR_ARG, "varU must be finite and positive");
-    HRand &R = h->rnd[(size_t)set_id];
+    HRand &R = h->mm.rnd[(size_t)set_id];
     for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
     const uint64_t it = ++R.fine_calls;
     HCHK(hipStreamSynchronize(h->stream));
     double vin[2];
     HCHK(hipMemcpy(vin, R.d_vu, sizeof(vin), hipMemcpyDeviceToHost));
     vin[0] = *varU;  // (the sum of varU stays)
-    HCHK(hipMemcpyAsync(h->d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
+    HCHK(hipMemcpyAsync(h->cm.d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
     HCHK(hipMemcpyAsync(R.d_u, u, (size_t)R.q * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HCHK(hipMemcpyAsync(R.d_vu, vin, sizeof(vin), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->d_scal, varE);
+    hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->cm.d_scal, varE);
     launch_random(h, (int)set_id, it);
-    if (h->d_rs) launch_rows(h, h->d_ycorr, h->d_ycorr, true);  // ... and back (d_ycorr is scratch here)
-    HCHK(hipMemcpyAsync(ycorr, h->d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, true);  // ... and back (d_ycorr is scratch here)
+    HCHK(hipMemcpyAsync(ycorr, h->cm.d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipMemcpyAsync(u, R.d_u, (size_t)R.q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipMemcpyAsync(varU, R.d_vu, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
@@ -3505,21 +3481,21 @@ int32_t ngp_set_sample_file(ngp_handle *h, const char *path) {
     int rc;
     if ((rc = enter(h))) return rc;
     HCHK(hipStreamSynchronize(h->stream));
-    sample_close(h);
+    h->smp.reset();
     if (!path) return NGP_OK;
-    REQUIRE(h->d_tiles != nullptr, NGP_ERR_STATE, "panel not set");
-    SampleStream *S = new SampleStream();
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    auto S = std::make_unique<SampleStream>();
     S->path = path; S->device = h->device;
-    S->f = std::fopen(path, "wb");
-    if (!S->f) { delete S; return fail(h, NGP_ERR_ARG, std::string("cannot open the sample file for writing: ") + path); }
+    S->f.reset(std::fopen(path, "wb"));
+    if (!S->f) return fail(h, NGP_ERR_ARG, std::string("cannot open the sample file for writing: ") + path);
     hipError_t e = hipStreamCreate(&S->copy_stream);
     for (int i = 0; i < SampleStream::NSLOT && e == hipSuccess; i++) {
         e = hipEventCreateWithFlags(&S->ev_packed[i], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev_copied[i], hipEventDisableTiming);
     }
-    h->smp = S;
-    if (e != hipSuccess) { sample_close(h); return fail(h, NGP_ERR_HIP, std::string("sample stream: ") + hipGetErrorString(e)); }
-    S->writer = std::thread(sample_writer_loop, S);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("sample stream: ") + hipGetErrorString(e));
+    S->writer = std::thread(sample_writer_loop, S.get());
+    h->smp = std::move(S);
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -3532,7 +3508,7 @@ int32_t ngp_get_census(ngp_handle *h, uint64_t *out, int64_t n, int64_t *grid, i
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->d_tiles != nullptr && h->plan.mode == 1, NGP_ERR_STATE, "no persistent sweep on this handle");
+    REQUIRE(h->pm && h->plan.mode == 1, NGP_ERR_STATE, "no persistent sweep on this handle");
     const int64_t g = h->last_grid > 0 ? h->last_grid : sweep_grid(h->plan);
     if (grid) *grid = g;
     if (retries) *retries = h->census_retries;
@@ -3540,7 +3516,7 @@ int32_t ngp_get_census(ngp_handle *h, uint64_t *out, int64_t n, int64_t *grid, i
     if (out) {
         REQUIRE(n >= g, NGP_ERR_ARG, "census buffer smaller than the grid");
         HCHK(hipStreamSynchronize(h->stream));
-        HCHK(hipMemcpy(out, h->d_census_tbl, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HCHK(hipMemcpy(out, h->cm.d_census_tbl, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return NGP_OK;
     NGP_CATCH(h)

@@ -948,3 +948,56 @@ def test_sample_stream_does_not_stop_the_chain_and_loses_nothing(ngp, O, tmp_pat
     S = ngp.read_sample_file(str(tmp_path / "all.ngpsmp"))
     assert S["iter"].tolist() == list(range(1, 301)) and np.array_equal(S["beta"][-1], s.get_state()["beta"])
     assert np.allclose(S["beta"].sum(axis=0), s.get_posterior_sums()["sum_beta"], rtol=1e-12, atol=1e-12)
+
+
+def test_second_panel_on_a_handle_that_holds_a_model(ngp, O):
+    """A new panel is a new model: a handle that has run a full model (BayesPR, BayesR, a Tuple set, fixed and random effects, traced
+    loci) and is then given a panel of another N and P with a smaller model runs bit for bit the chain of a fresh handle given that
+    panel, model and seed -- state, posterior sums, varE / b traces, fixed and random effects."""
+    from test_tuple_main_oracle import add_tuple, tuple_problem
+    k, nloc = 2, 40
+    X1, y1, vm, v1, span, off = tuple_problem(O, ngp, 220, nloc, k, extra=200)   # Tuple set on blocks 0-1, 200 plain columns behind
+    rng = np.random.default_rng(31)
+    old = ngp.Sampler(device=0, seed=77, chain=1)
+    old.set_panel(X1)
+    add_tuple(old, nloc, k, vm, [(0, 15), (15, nloc)])
+    add_sets(old, [(off, 100, "PR"), (off + 100, 100, "R")], v1)
+    old.add_fixed_set(rng.normal(size=(220, 2)))
+    old.add_random_set(rng.integers(0, 6, size=220), 6, varU0=0.5)
+    old.set_trace_loci([0, off + 3, off + 150], n_varBeta=2)
+    old.set_y(y1); old.set_residual_prior(4.0, 1.0); old.set_schedule(5, 1, 1)
+    old.run(5)
+
+    X2, y2, bt, v2 = make_problem(O, 150, 200, seed=9)
+    Z = rng.normal(size=(150, 1))
+    level = rng.integers(0, 4, size=150)
+
+    def second(s):
+        s.set_panel(X2)
+        add_sets(s, [(0, 120, "PR"), (120, 80, "B")], v2)
+        s.add_fixed_set(Z)
+        s.add_random_set(level, 4, varU0=0.3)
+        s.set_y(y2); s.set_residual_prior(4.0, 1.0); s.set_schedule(8, 2, 2)
+        s.run(8)
+
+    # (the wrapper counts the model it was given; the library drops that model with the old panel)
+    old.nsets, old.set_shapes, old.nfixcol, old.rand_q, old.nclasses, old.ntl, old.ntvb = 0, [], 0, [], 0, 0, 0
+    second(old)
+    fresh = ngp.Sampler(device=0, seed=77, chain=1)
+    second(fresh)
+    a, b = old.get_state(), fresh.get_state()
+    for key in ("ycorr", "beta", "delta", "varBeta", "piHat"):
+        assert np.array_equal(a[key], b[key]), key
+    assert (a["varE"], a["b"], a["iter"]) == (b["varE"], b["b"], b["iter"])
+    a, b = old.get_posterior_sums(), fresh.get_posterior_sums()
+    for key in a:
+        assert np.array_equal(a[key], b[key]), key
+    a, b = old.get_trace(8), fresh.get_trace(8)
+    assert np.array_equal(a["varE"], b["varE"]) and np.array_equal(a["b"], b["b"])
+    a, b = old.get_fixed(), fresh.get_fixed()
+    assert np.array_equal(a["b"], b["b"]) and np.array_equal(a["sum_b"], b["sum_b"])
+    a, b = old.get_random(0), fresh.get_random(0)
+    for key in a:
+        assert np.array_equal(a[key], b[key]), key
+    with pytest.raises(ngp.NextGPHipError, match="no traces requested"):   # the trace selection went with the old model
+        old.get_trace_ext(1)
