@@ -39,6 +39,8 @@ extern "C" {
 #define NGP_METHOD_BAYESC 2  /* src/runTime.jl:64-77, sampler src/functions.jl:197-235 */
 #define NGP_METHOD_BAYESR 3  /* src/runTime.jl:78-93, sampler src/functions.jl:238-289; added with ngp_add_marker_set_r */
 #define NGP_METHOD_TUPLE 4   /* correlated sets, BayesPR's Tuple method: src/functions.jl:140-154; added with ngp_add_marker_set_tuple */
+#define NGP_METHOD_BAYESLV 5 /* src/runTime.jl:116-133, sampler src/functions.jl:421-486; added with ngp_add_marker_set_lv */
+#define NGP_LV_MAXCOV 16     /* most columns of a BayesLV set's covariate matrix */
 
 typedef struct ngp_handle ngp_handle;
 
@@ -266,7 +268,8 @@ int32_t ngp_profile_iteration(ngp_handle *h, double *avg_ms, int64_t *launches, 
  * what: 0 uniform, 1 normal, 2 chisq(p1), 3 beta(p1,p2), 4 gamma(p1). */
 int32_t ngp_draws_indexed(ngp_handle *h, uint64_t iter, uint64_t kind, uint64_t index0, int32_t what, double p1, double p2,
                           int64_t n, double *out);
-/* det_log / ppnd16 evaluated on the device (bit-parity probe), n inputs -> n outputs. */
+/* det_log / ppnd16 evaluated on the device (bit-parity probe), n inputs -> n outputs.  which: 0 det_log, 1 ppnd16, 2 sqrt,
+ * 3 1 / x, 4 det_exp_any (exp for arguments of either sign: BayesLV's slice bounds). */
 int32_t ngp_eval_math(ngp_handle *h, int32_t which, const double *in, int64_t n, double *out);
 
 /* ---- streamer variants of the persistent sweep (before the panel is set) ----
@@ -384,6 +387,31 @@ int32_t ngp_debug_set_virtual_device(ngp_handle *h, int32_t vdev);
 /* Test hook of the exception barrier: throws a C++ exception inside an entry point (kind 0 std::bad_alloc, 1 std::length_error,
  * 2 a non-standard one); what comes back is a negative status and a message -- never an unwind into the caller.  h may be NULL. */
 int32_t ngp_debug_throw(ngp_handle *h, int32_t kind);
+
+/* ---- BayesLV sets: a log-linear model of the SNP variances (src/runTime.jl:116-133, src/functions.jl:421-486) ----
+ * Columns [col0, col0 + ncol) with one variance per locus (all varBeta0 at first).  The sweep is BayesPR's with one region per locus
+ * (bit for bit, given the variances); behind it the variance step draws every locus' variance by a slice step around
+ * exp(C c + zeta), then c ~ N(iCpC C'logVar, iCpC varZeta) and zeta = logVar - C c ("BayesLV sets").
+ * C: ncol x ncov covariates, column-major with leading dimension ld (ncov in 1..NGP_LV_MAXCOV), the design matrix of the variance
+ * formula (src/mme.jl:427).  The library forms C'C, adds min_i |(C'C)_ii / 10000| to its diagonal (src/mme.jl:433-436) and inverts
+ * it in Float64 by a Cholesky factorisation.  varZeta0 > 0: the variance of zeta; est_mode 0 keeps it, 1 sets it to var(zeta) and
+ * 2 to est_fraction var(logVar) after every step (estimateVarZeta false / true / a Float64).  zeta0: ncol starting values of zeta
+ * (the reference: unseeded rand(ncol), src/mme.jl:430), or NULL for keyed uniforms (kind 16); ngp_set_y goes back to them.
+ * lhs0 / rhs0 as for ngp_add_marker_set.  The set contributes ncol entries to varBeta and a [0.5, 0.5] placeholder to piHat.
+ * NGP_ERR_ARG (the handle unchanged): ncov outside 1..16, a non-finite entry of C or zeta0, varBeta0 <= 0, varZeta0 <= 0, est_mode
+ * outside 0..2, est_fraction <= 0 in mode 2, ncol < 2 with an estimated varZeta, a C'C whose Cholesky factorisation fails.
+ * The fine seam (ngp_sweep_set, ngp_sweep_set_dev) on such a set does the sweep AND the variance step: varBeta (ncol) is in / out on
+ * the caller's arrays; zeta, c and varZeta live in the handle. */
+int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double varBeta0, const double *C, int64_t ld, int32_t ncov,
+                              double varZeta0, int32_t est_mode, double est_fraction, const double *zeta0, const double *lhs0,
+                              const double *rhs0, int32_t *set_id);
+/* State of a BayesLV set: c[ncov], its posterior sums, varZeta and its sum, zeta[ncol], iCpC[ncov x ncov] (row-major, symmetric) and
+ * the number of loci whose slice was empty ("trapped", their variance kept) in the last iteration.  Any pointer may be NULL. */
+int32_t ngp_get_lv_state(ngp_handle *h, int32_t set_id, double *c, double *sum_c, double *varZeta, double *sum_varZeta, double *zeta,
+                         double *iCpC, int64_t *trapped);
+/* Resume: c / sum_c / zeta may be NULL (left as they are); varZeta > 0. */
+int32_t ngp_set_lv_state(ngp_handle *h, int32_t set_id, const double *c, const double *sum_c, double varZeta, double sum_varZeta,
+                         const double *zeta);
 
 #ifdef __cplusplus
 }

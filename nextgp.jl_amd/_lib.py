@@ -12,21 +12,34 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NGP_HIP_LIB") or os.path.join(_HERE, "libnextgp_hip.so")  # override: a library built elsewhere
 
-METHOD_BAYESPR, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESR, METHOD_TUPLE = 0, 1, 2, 3, 4
+METHOD_BAYESPR, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESR, METHOD_TUPLE, METHOD_BAYESLV = 0, 1, 2, 3, 4, 5
+LV_MAXCOV, LV_WORDS = 16, 17  # a BayesLV set in a sample record: c padded to 16 words | varZeta
 
 
 def _sample_header(f, path):
-    """(P, nvb, nsets, nfix, nclass, record bytes, sets, random-effect q per set) of an open sample file, positioned at its first record."""
+    """(P, nvb, nsets, nfix, nclass, record bytes, sets, random-effect q per set, (set, ncov) per BayesLV set) of an open sample file,
+    positioned at its first record."""
     magic = f.read(8)
-    if magic not in (b"NGPSMP01", b"NGPSMP02"):
+    if magic not in (b"NGPSMP01", b"NGPSMP02", b"NGPSMP03"):
         raise NextGPHipError(f"not a sample file: {path}")
     P, nvb, nsets, nfix, ncls, rec = (int(v) for v in np.frombuffer(f.read(48), dtype=np.int64))
     sets = [dict(zip(("method", "K", "col0", "ncol", "nvb", "tk"), np.frombuffer(f.read(48), dtype=np.int64).tolist())) for _ in range(nsets)]
     rq = []
-    if magic == b"NGPSMP02":  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
+    if magic in (b"NGPSMP02", b"NGPSMP03"):  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
         nr = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
         rq = np.frombuffer(f.read(8 * nr), dtype=np.int64).tolist()
-    return P, nvb, nsets, nfix, ncls, rec, sets, rq
+    lv = []
+    if magic == b"NGPSMP03":  # BayesLV sets: int64 nlv | (marker set, ncov) per set; records hold c[16] | varZeta behind the class probabilities
+        nl = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
+        lv = [tuple(np.frombuffer(f.read(16), dtype=np.int64).tolist()) for _ in range(nl)]
+    return P, nvb, nsets, nfix, ncls, rec, sets, rq, lv
+
+
+def _split_lv(d, o, lv):
+    """c of every BayesLV set (list of [..., ncov]) and varZeta ([..., nlv]) from record doubles d at offset o."""
+    c = [d[..., o + LV_WORDS * i:o + LV_WORDS * i + ncov] for i, (_, ncov) in enumerate(lv)]
+    vz = d[..., o + LV_MAXCOV:o + LV_WORDS * len(lv):LV_WORDS] if lv else d[..., o:o]
+    return c, vz
 
 
 def _split_random(d, o, rq):
@@ -40,13 +53,14 @@ def _split_random(d, o, rq):
 
 def read_sample_file(path):
     """Binary sample file of ngp_set_sample_file -> dict(iter[n], varE[n], b[n], b_fixed[n, nfix], beta[n, P], varBeta[n, nvb], piHat[n, 2 nsets],
-    class_pi[n, nclass], delta[n, P] (uint8), sets=[dict(method, K, col0, ncol, nvb, tk)], u=[[n, q] per random-effect set], varU[n, nrand])."""
+    class_pi[n, nclass], delta[n, P] (uint8), sets=[dict(method, K, col0, ncol, nvb, tk)], u=[[n, q] per random-effect set], varU[n, nrand],
+    lv_c=[[n, ncov] per BayesLV set], lv_varZeta[n, nlv])."""
     with open(path, "rb") as f:
-        P, nvb, nsets, nfix, ncls, rec, sets, rq = _sample_header(f, path)
+        P, nvb, nsets, nfix, ncls, rec, sets, rq, lv = _sample_header(f, path)
         raw = np.frombuffer(f.read(), dtype=np.uint8)
     n = len(raw) // rec
     raw = raw[:n * rec].reshape(n, rec)
-    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls
+    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls + LV_WORDS * len(lv)
     d = raw[:, :nd * 8].copy().view(np.float64)
     o = 3
     out = dict(iter=raw[:, :8].copy().view(np.int64)[:, 0], varE=d[:, 1], b=d[:, 2], sets=sets)
@@ -55,7 +69,8 @@ def read_sample_file(path):
     out["beta"] = d[:, o:o + P]; o += P
     out["varBeta"] = d[:, o:o + nvb]; o += nvb
     out["piHat"] = d[:, o:o + 2 * nsets]; o += 2 * nsets
-    out["class_pi"] = d[:, o:o + ncls]
+    out["class_pi"] = d[:, o:o + ncls]; o += ncls
+    out["lv_c"], out["lv_varZeta"] = _split_lv(d, o, lv)
     out["delta"] = raw[:, nd * 8:nd * 8 + P]
     return out
 
@@ -65,13 +80,13 @@ def iter_sample_file(path):
     5 GB): yields dicts with the fields of read_sample_file for a single kept iteration.  Memory-mapped, nothing is copied but
     the record being looked at."""
     with open(path, "rb") as f:
-        P, nvb, nsets, nfix, ncls, rec, sets, rq = _sample_header(f, path)
+        P, nvb, nsets, nfix, ncls, rec, sets, rq, lv = _sample_header(f, path)
         off = f.tell()
         size = os.fstat(f.fileno()).st_size
     n = (size - off) // rec
     if n <= 0:
         return
-    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls
+    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls + LV_WORDS * len(lv)
     mm = np.memmap(path, dtype=np.uint8, mode="r", offset=off, shape=(n, rec))
     for i in range(n):
         d = np.frombuffer(mm[i, :nd * 8].tobytes(), dtype=np.float64)
@@ -82,7 +97,8 @@ def iter_sample_file(path):
         out["beta"] = d[o:o + P]; o += P
         out["varBeta"] = d[o:o + nvb]; o += nvb
         out["piHat"] = d[o:o + 2 * nsets]; o += 2 * nsets
-        out["class_pi"] = d[o:o + ncls]
+        out["class_pi"] = d[o:o + ncls]; o += ncls
+        out["lv_c"], out["lv_varZeta"] = _split_lv(d, o, lv)
         out["delta"] = np.asarray(mm[i, nd * 8:nd * 8 + P])
         yield out
     del mm
@@ -142,6 +158,7 @@ SYMBOLS = [
     "ngp_set_trace_loci", "ngp_get_trace_ext", "ngp_allreduce_posterior", "ngp_add_marker_set_r", "ngp_get_class_state", "ngp_set_class_state", "ngp_add_fixed_set", "ngp_get_fixed", "ngp_set_fixed", "ngp_debug_throw", "ngp_get_census", "ngp_debug_set_virtual_device", "ngp_debug_fail_census", "ngp_add_marker_set_tuple", "ngp_share_panel", "ngp_shards_for_pass", "ngp_set_sample_file",
     "ngp_set_chain_form", "ngp_get_chain_form", "ngp_get_setup_timing", "ngp_set_residual_weights", "ngp_get_residual_weights",
     "ngp_add_random_set", "ngp_get_random", "ngp_set_random", "ngp_sample_random_set",
+    "ngp_add_marker_set_lv", "ngp_get_lv_state", "ngp_set_lv_state",
 ]
 
 _lib = None
@@ -485,6 +502,41 @@ class Sampler:
         self.nsets += 1
         self.set_shapes.append((tuple_span(nloc, k), len(rs) * k * k))
         return sid.value
+
+    def add_marker_set_lv(self, col0, ncol, varBeta0, covariates, varZeta0, est_mode=0, est_fraction=0.0, zeta0=None, lhs0=None, rhs0=None):
+        """BayesLV set (src/runTime.jl:116-133): one variance per locus whose logarithm is regressed on the covariates (ncol x ncov,
+        the design matrix of the variance formula).  est_mode 0: varZeta fixed; 1: var(zeta); 2: est_fraction * var(logVar).  zeta0: ncol
+        starting values of zeta, None for keyed uniforms.  Returns the set id."""
+        Cm = np.asfortranarray(np.asarray(covariates, dtype=np.float64).reshape(ncol, -1))
+        z0 = None if zeta0 is None else np.ascontiguousarray(zeta0, dtype=np.float64)
+        if z0 is not None and len(z0) != ncol:
+            raise ValueError("zeta0 needs one entry per locus")
+        l0 = None if lhs0 is None else np.ascontiguousarray(lhs0, dtype=np.float64)
+        r0 = None if rhs0 is None else np.ascontiguousarray(rhs0, dtype=np.float64)
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_marker_set_lv(self.h, C.c_int64(col0), C.c_int64(ncol), C.c_double(varBeta0), _p(Cm, C.c_double), C.c_int64(ncol),
+                                               C.c_int32(Cm.shape[1]), C.c_double(varZeta0), C.c_int32(int(est_mode)), C.c_double(est_fraction),
+                                               _p(z0, C.c_double), _p(l0, C.c_double), _p(r0, C.c_double), C.byref(sid)))
+        self.nsets += 1
+        self.set_shapes.append((ncol, ncol))
+        self.lv_shape = dict(getattr(self, "lv_shape", {}))
+        self.lv_shape[sid.value] = (ncol, Cm.shape[1])
+        return sid.value
+
+    def lv_state(self, set_id):
+        """dict(c[ncov], sum_c[ncov], varZeta, sum_varZeta, zeta[ncol], iCpC[ncov, ncov], trapped) of a BayesLV set."""
+        ncol, ncov = self.lv_shape[set_id]
+        c = np.empty(ncov); sc = np.empty(ncov); z = np.empty(ncol); ic = np.empty((ncov, ncov))
+        vz, svz, tr = C.c_double(), C.c_double(), C.c_int64()
+        self._chk(self.L.ngp_get_lv_state(self.h, C.c_int32(set_id), _p(c, C.c_double), _p(sc, C.c_double), C.byref(vz), C.byref(svz),
+                                          _p(z, C.c_double), _p(ic, C.c_double), C.byref(tr)))
+        return dict(c=c, sum_c=sc, varZeta=vz.value, sum_varZeta=svz.value, zeta=z, iCpC=ic, trapped=tr.value)
+
+    def set_lv_state(self, set_id, st):
+        """Resume: st as lv_state returns it (c, sum_c and zeta may be missing: left as they are)."""
+        a = {k: (None if st.get(k) is None else np.ascontiguousarray(st[k], dtype=np.float64)) for k in ("c", "sum_c", "zeta")}
+        self._chk(self.L.ngp_set_lv_state(self.h, C.c_int32(set_id), _p(a["c"], C.c_double), _p(a["sum_c"], C.c_double), C.c_double(st["varZeta"]),
+                                          C.c_double(st.get("sum_varZeta", 0.0)), _p(a["zeta"], C.c_double)))
 
     def get_class_state(self, set_id):
         pi = np.empty(16); sp = np.empty(16); K = C.c_int64()

@@ -9,10 +9,11 @@ Same names, argument meaning and output files as the reference, so a model scrip
     Random("I", v)          (residual prior, key :e)    Random("I", v)                (key "e")                 src/runTime.jl:135-146
     Random(dvec, v)         (weighted residuals, "D")   Random(d, v), d_ii per record (key "e")                 src/mme.jl:71-75
     SNP(M, "geno.txt"[, "map.txt"]) in the formula      the same text inside the formula string                src/runTime.jl:13-28
+    BayesLV(v, f, covariates, varZeta; estimateVarZeta) BayesLV(v, "0 ~ x1 + x2", {"x1": ..}, varZeta, ...)    src/runTime.jl:116-133
     summaryMCMC("betaM"; outFolder)                     summaryMCMC("betaM", outFolder=...)                    src/misc.jl:241-244
 
 Interpreted here: the response, the intercept `1`, covariate / factor columns (optionally grouped by `blockThese`), `(1|g)` random
-effects and `SNP(...)` terms.  Interactions, `PED(...)`, correlated (Tuple) random effects, GBLUP priors, BayesRC/LV are outside the
+effects and `SNP(...)` terms.  Interactions, `PED(...)`, correlated (Tuple) random effects, GBLUP priors, BayesRC are outside the
 accelerated path and raise NotImplementedError naming the reference code that handles them.
 All arithmetic happens in libnextgp_hip.so; this file only parses, reshapes and writes files.
 """
@@ -23,9 +24,9 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
+from ._lib import LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["BayesPR", "BayesB", "BayesC", "BayesR", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
+__all__ = ["BayesPR", "BayesB", "BayesC", "BayesR", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -64,6 +65,16 @@ class BayesRType:  # src/runTime.jl:78-93
 
 
 @dataclass
+class BayesLogVarType:  # src/runTime.jl:116-133
+    v: float
+    f: str               # the variance formula, e.g. "0 ~ x1 + x2" (the reference: a StatsModels @formula)
+    covariates: object   # mapping of numeric columns, one row per SNP (the reference: a DataFrame)
+    varZeta: float
+    name: str = "BayesLV"
+    estimateVarZeta: object = False   # False: varZeta fixed; True: var(zeta); a float f: f * var(logVar) (src/functions.jl:481-485)
+
+
+@dataclass
 class RandomEffectType:  # src/runTime.jl:135-146
     str: object
     v: float
@@ -92,6 +103,56 @@ def BayesC(pi, v, name="BayesC", estimatePi=False):
 def BayesR(pi, class_, v, name="BayesR", estimatePi=False):
     """BayesR(pi, class, v; estimatePi) of src/runTime.jl:87-93: `class_` = variance-class multipliers, `pi` their probabilities."""
     return BayesRType([float(x) for x in pi], [float(x) for x in class_], float(v), name, bool(estimatePi))
+
+
+def BayesLV(v, f, covariates, varZeta, name="BayesLV", estimateVarZeta=False):
+    """Log-linear model of the SNP variances (src/runTime.jl:116-133): log(var_j) = C_j c + zeta_j, zeta_j ~ N(0, varZeta).  `f` is the
+    variance formula as a string ("0 ~ x1 + x2": the left side is ignored), `covariates` a mapping of numeric columns with one row per
+    SNP of the set."""
+    if not isinstance(f, str) or "~" not in f:
+        raise ValueError('BayesLV: f is the variance formula as text, e.g. "0 ~ x1 + x2"')
+    if not (isinstance(estimateVarZeta, bool) or isinstance(estimateVarZeta, float)):
+        raise ValueError("BayesLV: estimateVarZeta is False, True or a Float64 fraction (src/runTime.jl:122)")
+    return BayesLogVarType(float(v), f, covariates, float(varZeta), name, estimateVarZeta)
+
+
+def lv_design_matrix(f, covariates):
+    """(C, names): the design matrix modelmatrix(f, covariates) builds for a BayesLV prior (src/mme.jl:427) -- an intercept column
+    first unless the formula has `0 +` / `- 1`, then the named numeric columns in formula order."""
+    rhs = re.sub(r"\s+", "", f.split("~", 1)[1])
+    toks = re.findall(r"([+-]?)([A-Za-z_0-9.]+|.)", rhs)
+    intercept, names = True, []
+    for sign, t in toks:
+        if not re.fullmatch(r"[A-Za-z_0-9.]+", t):
+            raise NotImplementedError(f"BayesLV: term {t!r} in the variance formula: interactions, functions and categorical terms are left to "
+                                      "StatsModels' modelmatrix on the Julia path (src/mme.jl:427)")
+        if t == "1":
+            intercept = sign != "-"
+        elif t == "0":
+            intercept = intercept and sign == "-"
+        elif sign == "-":
+            raise NotImplementedError(f"BayesLV: removing the term {t!r} from the variance formula is left to StatsModels (src/mme.jl:427)")
+        elif t not in names:
+            names.append(t)
+    cols = []
+    for nm in names:
+        if nm not in covariates:
+            raise KeyError(f"BayesLV: the covariates have no column {nm!r}")
+        col = np.asarray(covariates[nm])
+        if col.dtype.kind not in "fiub":
+            raise NotImplementedError(f"BayesLV: column {nm!r} is not numeric; categorical terms of the variance formula are coded by StatsModels' "
+                                      "modelmatrix in the reference (src/mme.jl:427) and are not on the accelerated path")
+        cols.append(col.astype(np.float64))
+    n = len(cols[0]) if cols else len(next(iter(covariates.values())))
+    if intercept:
+        cols.insert(0, np.ones(n)); names = ["(Intercept)"] + names
+    if not cols:
+        raise ValueError("BayesLV: the variance formula has no term")
+    if len(cols) > LV_MAXCOV:
+        raise ValueError(f"BayesLV: at most {LV_MAXCOV} columns in the design matrix of the variance formula")
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("BayesLV: the covariate columns differ in length")
+    return np.asfortranarray(np.column_stack(cols)), names
 
 
 def Random(str, v, type=1):
@@ -321,7 +382,7 @@ def prep2RegionData(outPutFolder, markerSet, mapFile, fixedRegSize):
 
 def _regions_for(prior, P, map_path, out_folder, set_name):
     """M[set][:regionArray] (src/mme.jl:324-358)."""
-    if isinstance(prior, BayesBType):
+    if isinstance(prior, (BayesBType, BayesLogVarType)):   # one region per locus (src/mme.jl:356, :421)
         return [(j, j + 1) for j in range(P)]
     if isinstance(prior, (BayesCType, BayesRType)):  # one variance for the set (nVarCov = 1, src/mme.jl:370, :381)
         return [(0, P)]
@@ -400,6 +461,9 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
                     row(f"pi{s['name']}", _fmt(S["piHat"][2 * k:2 * k + 2]))
                 if K:
                     row(f"pi{s['name']}", _fmt(S["class_pi"][cls_off:cls_off + K]))
+                if isinstance(s["prior"], BayesLogVarType):   # src/samplers.jl:89-92
+                    row(f"c{s['name']}", _fmt(S["lv_c"][s["lv"]]))
+                    row(f"varZeta{s['name']}", _fmt(S["lv_varZeta"][s["lv"]]))
                 row(f"var{s['name']}", _fmt(S["varBeta"][vb_off:vb_off + s["nvb"]]))
                 vb_off += s["nvb"]
                 cls_off += K
@@ -632,8 +696,8 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
         prior = VCV.get(t.name)
         if prior is None:  # src/mme.jl:324-329, 504, 518
             prior = BayesPR(9999, 0.05)
-        if not isinstance(prior, (BayesPRType, BayesBType, BayesCType, BayesRType)):
-            raise NotImplementedError(f"prior {type(prior).__name__} for {t.name}: only BayesPR, BayesB, BayesC and BayesR are on the accelerated path")
+        if not isinstance(prior, (BayesPRType, BayesBType, BayesCType, BayesRType, BayesLogVarType)):
+            raise NotImplementedError(f"prior {type(prior).__name__} for {t.name}: only BayesPR, BayesB, BayesC, BayesR and BayesLV are on the accelerated path")
         df = 4.0                                  # 3 + size(v,1), src/mme.jl:493
         scale = prior.v * (df - 2.0) / df         # src/mme.jl:501
         regions = regions_of(prior, P, t.map, t.name)
@@ -648,6 +712,17 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
         elif isinstance(prior, BayesCType):
             sid = smp.add_marker_set(col0, P, METHOD_BAYESC, df, scale, regions, [prior.v], pi0=prior.pi, estPi=prior.estimatePi,
                                      lhs0=lhs0, rhs0=rhs0)
+        elif isinstance(prior, BayesLogVarType):  # src/mme.jl:418-439
+            Cm, cnames = lv_design_matrix(prior.f, prior.covariates)
+            if Cm.shape[0] != P:
+                raise ValueError(f"BayesLV prior of {t.name}: {Cm.shape[0]} covariate rows for {P} SNPs")
+            est = prior.estimateVarZeta
+            sid = smp.add_marker_set_lv(col0, P, prior.v, Cm, prior.varZeta, est_mode=0 if est is False else 1 if est is True else 2,
+                                        est_fraction=float(est) if isinstance(est, float) else 0.0, lhs0=lhs0, rhs0=rhs0)
+            n_lv = sum(1 for q in sets if "lv" in q)
+            sets.append(dict(id=sid, name=t.name, members=[t.name], cols=np.arange(col0, col0 + P)[:, None], P=P, prior=prior, nreg=P, nvb=P, k=1,
+                             lv=n_lv, ncov=Cm.shape[1], cnames=cnames))
+            continue
         elif isinstance(prior, BayesRType):  # src/mme.jl:374-383
             sid = smp.add_marker_set_r(col0, P, df, scale, prior.v, prior.class_, prior.pi, estPi=prior.estimatePi, lhs0=lhs0, rhs0=rhs0)
         else:
@@ -713,6 +788,9 @@ def _write_headers(outFolder, sets, fixed_names, randoms=()):
             _out(outFolder, f"pi{s['name']}", ["pi1", "pi2"])
         if isinstance(s["prior"], BayesRType):               # one column per class (src/mme.jl:589-591)
             _out(outFolder, f"pi{s['name']}", [f"pi{v + 1}" for v in range(len(s["prior"].pi))])
+        if isinstance(s["prior"], BayesLogVarType):          # src/mme.jl:577-580
+            _out(outFolder, f"c{s['name']}", [f"c{v + 1}" for v in range(s["ncov"])])
+            _out(outFolder, f"varZeta{s['name']}", ["varZeta"])
         _out(outFolder, f"var{s['name']}", _var_names(s))
 
 
@@ -743,6 +821,10 @@ def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin,
                     _out(outFolder, f"pi{s['name']}", _fmt(st["piHat"][2 * k:2 * k + 2]))
                 if isinstance(s["prior"], BayesRType):
                     _out(outFolder, f"pi{s['name']}", _fmt(smp.get_class_state(s["id"])["piHat"]))
+                if isinstance(s["prior"], BayesLogVarType):
+                    lv = smp.lv_state(s["id"])
+                    _out(outFolder, f"c{s['name']}", _fmt(lv["c"]))
+                    _out(outFolder, f"varZeta{s['name']}", _fmt(lv["varZeta"]))
                 _out(outFolder, f"var{s['name']}", _fmt(st["varBeta"][vb_off:vb_off + s["nvb"]]))
                 vb_off += s["nvb"]
     smp.run(nChain - done)
@@ -769,6 +851,10 @@ def _posterior_means(smp, sets, fixed_names, intercept, randoms=()):
                 res["sets"][nm]["var"] = (ps["sum_varBeta"][vb_off:vb_off + s["nvb"]] / n).reshape(s["nreg"], s["k"], s["k"])
         if isinstance(s["prior"], BayesRType):
             res["sets"][s["name"]]["pi"] = smp.get_class_state(s["id"])["sum_pi"] / n
+        if isinstance(s["prior"], BayesLogVarType):   # posterior means of the variance model's coefficients and of varZeta
+            lv = smp.lv_state(s["id"])
+            res["sets"][s["name"]]["c"] = lv["sum_c"] / n
+            res["sets"][s["name"]]["varZeta"] = lv["sum_varZeta"] / n
         vb_off += s["nvb"]
     res["random"] = {}
     for rd in randoms:   # posterior means of u (levels in random_levels order) and varU, keyed as Julia prints the term

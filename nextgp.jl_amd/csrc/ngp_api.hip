@@ -23,6 +23,7 @@
 #include "../../include/nextgp_hip.h"
 #include "ngp_kernels.h"
 #include "ngp_random.h"
+#include "ngp_logvar.h"
 #include "ngp_sweep_args.h"
 
 using namespace ngp;
@@ -88,6 +89,17 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
 };
 
+struct HLv {  // the variance model of one BayesLV marker set (src/mme.jl:418-439; kernels and state layout in ngp_logvar.h)
+    int set = -1;              // its marker set
+    int64_t n = 0;             // loci
+    int ncov = 0, mode = 0;    // covariate columns; 0: varZeta fixed, 1: var(zeta), 2: frac * var(logVar)
+    double frac = 0.0, varZeta0 = 0.0;
+    std::vector<double> zeta0; // starting values given by the caller (empty: keyed uniforms, k_lv_start)
+    DevArray<double> d_C, d_iCpC, d_zeta, d_logv, d_part, d_vpart;
+    DevArray<double> d_st;     // NGP_LV_WORDS doubles: c | varZeta | their posterior sums | trapped | mean
+    DevArray<int> d_trapseg;
+};
+
 // The arrays of one uploaded panel: the handles that share it (ngp_share_panel) hold a std::shared_ptr each
 struct PanelMem {
     DevArray<float> tiles;  // fp32 tiles, or (compact storage) one byte per element behind the same pointer
@@ -134,6 +146,7 @@ struct HSet {
     std::vector<double> vcls, rpi;
     int tk = 0;               // Tuple (correlated BayesPR) set: number of correlated sets; nreg k x k variance matrices in varBeta
     int64_t nloc = 0;
+    int lv = -1;              // BayesLV set: its entry of ModelMem::lv (the device's DSet says BayesPR: the sweep is BayesPR's)
 };
 
 std::string g_create_err;
@@ -386,6 +399,7 @@ struct ModelMem {
     DevArray<double> d_bfix, d_sum_bfix;
     std::vector<HRand> rnd;            // (1|g) random-effect sets (src/functions.jl:57-110), sampled after the fixed-effect sets, in order
     int64_t nrandcol = 0;              // sum of q over the random-effect sets
+    std::vector<HLv> lv;               // variance models of the BayesLV sets (src/functions.jl:442-485), in the order of their sets
     // optional per-iteration traces of selected effects, variances and pi (ngp_set_trace_loci)
     DevArray<int64_t> d_trace_loci;
     int64_t ntl = 0, ntvb = 0;
@@ -833,7 +847,7 @@ int set_panel_host(ngp_handle *h, const TIn *M, int64_t N, int64_t P, int64_t ld
 bool wants_tinv(const ngp_handle *h) {
     if (h->chain_form != 1) return false;
     for (const HSet &st : h->sets)
-        if (st.method == NGP_METHOD_BAYESPR || st.method == NGP_METHOD_TUPLE) return true;
+        if (st.method == NGP_METHOD_BAYESPR || st.method == NGP_METHOD_BAYESLV || st.method == NGP_METHOD_TUPLE) return true;
     return false;
 }
 
@@ -848,7 +862,7 @@ int sync_linear_blocks(ngp_handle *h, int active_set) {
     std::vector<unsigned> bl((size_t)h->NBLK, 1u);
     for (size_t si = 0; si < h->sets.size(); si++) {
         const HSet &st = h->sets[si];
-        if (st.method == NGP_METHOD_BAYESPR || (active_set >= 0 && (int)si != active_set)) continue;
+        if (st.method == NGP_METHOD_BAYESPR || st.method == NGP_METHOD_BAYESLV || (active_set >= 0 && (int)si != active_set)) continue;
         const unsigned code = (st.method == NGP_METHOD_TUPLE) ? 1u + (unsigned)st.tk : 0u;
         for (int64_t t = st.col0 / NGP_BLK; t <= (st.col0 + st.ncol - 1) / NGP_BLK && t < h->NBLK; t++) bl[(size_t)t] = code;
     }
@@ -1019,7 +1033,30 @@ int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
                                     "state is invalid until ngp_set_y / ngp_set_state");
 }
 
+// the variance model of one BayesLV set on h->stream (ngp_logvar.h): slice draws, c, zeta, varZeta
+void launch_lv(ngp_handle *h, HLv &V, uint64_t it) {
+    const HSet &hs = h->sets[(size_t)V.set];
+    const long long n = (long long)V.n;
+    const unsigned gseg = (unsigned)(((n + 255) / 256 + 3) / 4);
+    const double *beta = h->cm.d_beta + hs.col0;
+    double *vb = h->mm.d_varBeta + hs.vb_off;
+    const unsigned *ab = (const unsigned *)h->cm.d_abort;
+    hipLaunchKernelGGL(k_lv_slice, dim3(gseg), dim3(256), 0, h->stream, n, V.ncov, beta, vb, (const double *)V.d_zeta, (const double *)V.d_C,
+                       (const double *)V.d_st, V.d_logv.get(), V.d_part.get(), V.d_trapseg.get(), V.set, h->seed, (uint64_t)h->chain, it, ab);
+    hipLaunchKernelGGL(k_lv_coef, dim3(1), dim3(64), 0, h->stream, n, V.ncov, (const double *)V.d_iCpC, (const double *)V.d_part,
+                       (const int *)V.d_trapseg, V.d_st.get(), V.set, h->seed, (uint64_t)h->chain, it, ab);
+    hipLaunchKernelGGL(k_lv_resid, dim3(gseg), dim3(256), 0, h->stream, n, V.ncov, (const double *)V.d_C, (const double *)V.d_st,
+                       (const double *)V.d_logv, V.d_zeta.get(), V.mode, V.d_vpart.get(), ab);
+    if (V.mode == 0) return;
+    const double *x = (V.mode == 1) ? V.d_zeta.get() : V.d_logv.get();
+    hipLaunchKernelGGL(k_lv_reduce, dim3(1), dim3(64), 0, h->stream, n, 0, V.mode, V.frac, (const double *)V.d_vpart, V.d_st.get(), ab);
+    hipLaunchKernelGGL(k_lv_ssq, dim3(gseg), dim3(256), 0, h->stream, n, x, (const double *)V.d_st, V.d_vpart.get(), ab);
+    hipLaunchKernelGGL(k_lv_reduce, dim3(1), dim3(64), 0, h->stream, n, 1, V.mode, V.frac, (const double *)V.d_vpart, V.d_st.get(), ab);
+}
+
 void launch_variance(ngp_handle *h, int active_set, uint64_t it) {
+    for (auto &V : h->mm.lv)  // BayesLV sets: their variance model instead of a region draw (src/functions.jl:442-485)
+        if (active_set < 0 || V.set == active_set) launch_lv(h, V, it);
     const long long nseg = (long long)h->h_seg_k0.size(), nreg = (long long)h->h_regs.size();
     if (nseg > 0) {
         hipLaunchKernelGGL(k_regssq, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, h->stream, nseg, h->mm.d_seg_k0, h->mm.d_seg_len,
@@ -1113,6 +1150,8 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
             hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((R.q + 255) / 256)), dim3(256), 0, h->stream, (long long)R.q, R.d_u, R.d_sum_u, h->cm.d_abort);
             hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, 1LL, R.d_vu, R.d_vu + 1, h->cm.d_abort);
         }
+        for (auto &V : h->mm.lv)  // BayesLV sets: c and varZeta (src/samplers.jl:89-92)
+            hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, (long long)NGP_LV_SUM, V.d_st, V.d_st + NGP_LV_SUM, h->cm.d_abort);
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
     return NGP_OK;
@@ -1173,13 +1212,14 @@ int set_class_state_dev(ngp_handle *h, int si, const double *pi, const double *s
 // doubles of the packed posterior (ngp_export_posterior_device): 3P + nvb + 2 nsets + sum K + fixed-effect columns
 // (+ sum q + number of random-effect sets) + 3
 int64_t posterior_words(const ngp_handle *h) {
-    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->mm.nfixcol + h->mm.nrandcol + (int64_t)h->mm.rnd.size() + 3;
+    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->mm.nfixcol + h->mm.nrandcol + (int64_t)h->mm.rnd.size() +
+           NGP_LV_SUM * (int64_t)h->mm.lv.size() + 3;  // (a BayesLV set: the sums of c, padded to 16, and of varZeta)
 }
 
 // ---- sample stream (ngp_set_sample_file) ----
 size_t sample_rec_bytes(const ngp_handle *h) {
     const size_t nd = 3 + (size_t)h->mm.nfixcol + (size_t)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()) + (size_t)h->P + (size_t)h->nvb + 2 * h->sets.size() +
-                      (size_t)h->nclass_total;
+                      (size_t)h->nclass_total + (size_t)NGP_LV_SUM * h->mm.lv.size();
     return nd * 8 + (((size_t)h->P + 7) & ~(size_t)7);
 }
 void sample_writer_loop(SampleStream *S) {
@@ -1227,12 +1267,20 @@ int sample_enqueue(ngp_handle *h) {
         }
         const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->mm.nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
         // (a chain with random-effect sets: "NGPSMP02", and the header ends in int64 nrand | q per set)
-        bool ok = std::fwrite(h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
+        // (a chain with BayesLV sets: "NGPSMP03" -- the random-effect part as in 02, also when empty, then int64 nlv | per set int64
+        // marker set, ncov; records hold c (16 words, the first ncov used) and varZeta of every such set behind the class probabilities)
+        const bool has_lv = !h->mm.lv.empty();
+        bool ok = std::fwrite(has_lv ? "NGPSMP03" : h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
         for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f.get()) == 1; }
-        if (!h->mm.rnd.empty()) {
+        if (!h->mm.rnd.empty() || has_lv) {
             const int64_t nr = (int64_t)h->mm.rnd.size();
             ok = ok && std::fwrite(&nr, 8, 1, S->f.get()) == 1;
             for (auto &R : h->mm.rnd) ok = ok && std::fwrite(&R.q, 8, 1, S->f.get()) == 1;
+        }
+        if (has_lv) {
+            const int64_t nl = (int64_t)h->mm.lv.size();
+            ok = ok && std::fwrite(&nl, 8, 1, S->f.get()) == 1;
+            for (auto &V : h->mm.lv) { const int64_t lg[2] = {V.set, V.ncov}; ok = ok && std::fwrite(lg, sizeof(lg), 1, S->f.get()) == 1; }
         }
         if (!ok) return fail(h, NGP_ERR_ARG, "cannot write the sample file header: " + S->path);
         S->header_written = true;
@@ -1248,7 +1296,7 @@ int sample_enqueue(ngp_handle *h) {
     }
     const long long n = std::max<long long>(std::max<long long>(h->P, h->nvb), std::max<long long>(h->mm.nfixcol, 1));
     hipLaunchKernelGGL(k_sample_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, S->d_slot[slot], (long long)h->P, (long long)h->nvb,
-                       (int)h->sets.size(), (long long)h->mm.nfixcol, (long long)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()), (long long)h->nclass_total,
+                       (int)h->sets.size(), (long long)h->mm.nfixcol, (long long)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()), (long long)(h->nclass_total + NGP_LV_SUM * (int64_t)h->mm.lv.size()),
                        (long long)h->iter, h->cm.d_beta, h->cm.d_delta, h->mm.d_varBeta, h->cm.d_sets, h->cm.d_scal, h->mm.d_bfix, h->cm.d_abort);
     {   // random-effect sets: u (set after set), then varU of every set, behind b_fixed
         double *o = (double *)S->d_slot[slot].get() + 3 + h->mm.nfixcol;
@@ -1259,6 +1307,10 @@ int sample_enqueue(ngp_handle *h) {
             if (e0 == hipSuccess) e0 = hipMemcpyAsync(o + h->mm.nrandcol + (int64_t)r, h->mm.rnd[r].d_vu, sizeof(double), hipMemcpyDeviceToDevice, h->stream);
             off += h->mm.rnd[r].q;
         }
+        // BayesLV sets: c | varZeta of every set, behind the class probabilities (in front of the delta bytes)
+        double *ol = (double *)S->d_slot[slot].get() + 3 + h->mm.nfixcol + h->mm.nrandcol + (int64_t)h->mm.rnd.size() + h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total;
+        for (size_t v = 0; v < h->mm.lv.size() && e0 == hipSuccess; v++)
+            e0 = hipMemcpyAsync(ol + NGP_LV_SUM * v, h->mm.lv[v].d_st, NGP_LV_SUM * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
         if (e0 != hipSuccess) {
             { std::lock_guard<std::mutex> lk(S->mu); S->busy[slot] = false; }
             S->cv.notify_all();
@@ -1303,6 +1355,17 @@ int grow_pair(ngp_handle *h, DevArray<double> &a, DevArray<double> &sum_a, int64
     }
     HCHK(hipStreamSynchronize(h->stream));
     a = std::move(na); sum_a = std::move(ns);
+    return NGP_OK;
+}
+
+// a BayesLV set's state as ngp_add_marker_set_lv leaves it: zeta = zeta0 (or the keyed uniforms), c = 0, varZeta = varZeta0, sums 0
+int lv_reset(ngp_handle *h, HLv &V) {
+    double st[NGP_LV_WORDS] = {0.0};
+    st[NGP_LV_VZ] = V.varZeta0;
+    HCHK(hipMemcpyAsync(V.d_st, st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+    if (!V.zeta0.empty()) HCHK(hipMemcpyAsync(V.d_zeta, V.zeta0.data(), (size_t)V.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    else hipLaunchKernelGGL(k_lv_start, dim3((unsigned)((V.n + 255) / 256)), dim3(256), 0, h->stream, (long long)V.n, V.d_zeta.get(), V.set, h->seed, (uint64_t)h->chain);
+    HCHK(hipStreamSynchronize(h->stream));  // (st is a local)
     return NGP_OK;
 }
 
@@ -1464,6 +1527,10 @@ struct PanelHeader { char magic[8]; int64_t N, P; int32_t bits, zero; };
 }
 #define NGP_SNAP_WEIGHTED ((int64_t)1 << 62)  // snapshot: the fixed-set count's flag of a weighted chain (ngp_save_snapshot)
 #define NGP_SNAP_RANDOM ((int64_t)1 << 61)    // ... and of a chain with random-effect sets
+// snapshot signature of a BayesLV set (added to its second word): the covariate count and how varZeta is estimated
+static int64_t lv_sig(const ngp_handle *h, const HSet &hs) {
+    return hs.lv < 0 ? 0 : 256 * ((int64_t)h->mm.lv[(size_t)hs.lv].ncov + 32 * (int64_t)h->mm.lv[(size_t)hs.lv].mode);
+}
 
 int32_t ngp_write_panel_file(const char *path, const uint8_t *G, int64_t N, int64_t P, int64_t ld, int32_t bits) {
     NGP_TRY
@@ -1802,6 +1869,10 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
         HCHK(hipMemcpyAsync(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice, h->stream));
         HCHK(hipStreamSynchronize(h->stream));
         R.fine_calls = 0;
+    }
+    for (auto &V : h->mm.lv) {  // BayesLV sets: zeta back to its start, c = 0, varZeta its prior value, empty sums (src/mme.jl:429-437)
+        int rc2 = lv_reset(h, V);
+        if (rc2) return rc2;
     }
     HCHK(hipStreamSynchronize(h->stream));
     h->iter = 0; h->have_y = true; h->poisoned = false; h->ntrace = 0;
@@ -2180,6 +2251,11 @@ int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len
             off += (size_t)h->mm.rnd[r].q;
         }
     }
+    for (auto &V : h->mm.lv) {  // BayesLV sets: sums of c (16 words) and of varZeta
+        const size_t at = tail.size();
+        tail.resize(at + NGP_LV_SUM);
+        HCHK(hipMemcpy(tail.data() + at, V.d_st + NGP_LV_SUM, NGP_LV_SUM * sizeof(double), hipMemcpyDeviceToHost));
+    }
     tail.push_back(sc.sum_varE); tail.push_back(sc.sum_b); tail.push_back((double)sc.nKept);
     HCHK(hipMemcpy(o + 3 * h->P + h->nvb, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice));
     return NGP_OK;
@@ -2200,7 +2276,7 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
     const int64_t nvbs = (int64_t)hs.vb0.size();  // variance entries of the set: regions (loci for BayesB), k x k per region for a tuple set
     // (device arrays are not read back to be looked at: a variance that is not finite poisons the chain visibly -- k_prep -- as in ngp_run)
     if (!dev) for (int64_t r = 0; r < nvbs; r++) REQUIRE(std::isfinite(varBeta[r]) && (varBeta[r] >= 0.0 || hs.tk > 1), NGP_ERR_ARG, "varBeta must be finite, >= 0");
-    const bool has_pi = hs.method != NGP_METHOD_BAYESPR && hs.method != NGP_METHOD_TUPLE;
+    const bool has_pi = hs.method != NGP_METHOD_BAYESPR && hs.method != NGP_METHOD_TUPLE && hs.method != NGP_METHOD_BAYESLV;
     if (has_pi) REQUIRE(piHat != nullptr, NGP_ERR_ARG, "BayesB / BayesC need piHat");
     const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const uint64_t it = ++hs.fine_calls;
@@ -2606,6 +2682,8 @@ int32_t ngp_set_posterior_sums(ngp_handle *h, const double *sum_beta, const doub
  *   double varE, b, sum_varE, sum_b | ycorr[N] | beta[P] | delta[P] (uint8) | varBeta[nvb] | piHat[2 nsets] |
  *   sum_beta[P] | sum_beta2[P] | sum_delta[P] | sum_varBeta[nvb] | sum_pi[2 nsets] | fine_calls[nsets] (uint64) |
  *   int64 nfix | b_fixed[nfix] | sum_b_fixed[nfix] | per BayesR set: piHat[K] | sum_pi[K]
+ *   | per BayesLV set (only with such sets): the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums) | zeta[ncol];
+ *   the signature's second word of such a set carries 256 (ncov + 32 est_mode)
  * It plays the role of the reference's append-only *Out files for a resumed run (src/outFiles.jl:17-21): what was kept
  * before the interruption is not lost. */
 int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
@@ -2636,7 +2714,7 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     const double scal[4] = {varE, b, svE, sbb};
     W("NGPSNAP2", 8); W(hdr, sizeof(hdr)); W(ids, sizeof(ids));
     {   // model signature: a snapshot only loads into the model it was taken from (equal counts are not enough)
-        for (auto &hs : h->sets) { const int64_t sg[5] = {hs.method, hs.K + 16 * hs.tk, hs.nreg, hs.col0, hs.ncol}; W(sg, sizeof(sg)); }
+        for (auto &hs : h->sets) { const int64_t sg[5] = {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs), hs.nreg, hs.col0, hs.ncol}; W(sg, sizeof(sg)); }
         // (weighted residuals: bit 62 of the fixed-set count says so, and a digest of the weights follows it -- unweighted bytes unchanged)
         const int64_t nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM);
         W(&nfs, 8);
@@ -2673,6 +2751,15 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
             hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost) != hipSuccess) { f.reset(); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the random-effect sets"); }
         W(a.data(), a.size() * 8); W(b2.data(), b2.size() * 8); W(vu, sizeof(vu)); W(&R.fine_calls, 8);
     }
+    for (size_t v = 0; v < h->mm.lv.size() && ok; v++) {  // BayesLV sets: the small state | zeta
+        const HLv &V = h->mm.lv[v];
+        std::vector<double> z((size_t)V.n);
+        double st[NGP_LV_WORDS];
+        if (hipMemcpy(st, V.d_st, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(z.data(), V.d_zeta, z.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+            f.reset(); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the BayesLV sets");
+        }
+        W(st, sizeof(st)); W(z.data(), z.size() * 8);
+    }
     if (fclose(f.release()) != 0) ok = false;  // (a failed close is a failed write)
     if (!ok || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return fail(h, NGP_ERR_ARG, std::string("writing the snapshot failed: ") + path); }
     return NGP_OK;
@@ -2699,7 +2786,7 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         for (auto &hs : h->sets) {
             int64_t sg[5] = {-1, -1, -1, -1, -1};
             Rd(sg, sizeof(sg));
-            same = same && sg[0] == hs.method && sg[1] == hs.K + 16 * hs.tk && sg[2] == hs.nreg && sg[3] == hs.col0 && sg[4] == hs.ncol;
+            same = same && sg[0] == hs.method && sg[1] == hs.K + 16 * hs.tk + lv_sig(h, hs) && sg[2] == hs.nreg && sg[3] == hs.col0 && sg[4] == hs.ncol;
         }
         int64_t nfs = -1;
         Rd(&nfs, 8);
@@ -2758,6 +2845,11 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         ru[r].resize((size_t)h->mm.rnd[r].q); rsu[r].resize((size_t)h->mm.rnd[r].q);
         Rd(ru[r].data(), ru[r].size() * 8); Rd(rsu[r].data(), rsu[r].size() * 8); Rd(rvu.data() + 2 * r, 16); Rd(rfc.data() + r, 8);
     }
+    std::vector<std::vector<double>> lvz(h->mm.lv.size()), lvst(h->mm.lv.size());
+    for (size_t v = 0; v < h->mm.lv.size(); v++) {
+        lvst[v].resize(NGP_LV_WORDS); lvz[v].resize((size_t)h->mm.lv[v].n);
+        Rd(lvst[v].data(), NGP_LV_WORDS * 8); Rd(lvz[v].data(), lvz[v].size() * 8);
+    }
     char extra;
     const bool at_end = fread(&extra, 1, 1, f.get()) == 0;
     if (!ok || !at_end) return fail(h, NGP_ERR_ARG, "snapshot file is truncated or has trailing bytes");
@@ -2785,6 +2877,10 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         HCHK(hipMemcpy(R.d_sum_u, rsu[r].data(), rsu[r].size() * 8, hipMemcpyHostToDevice));
         HCHK(hipMemcpy(R.d_vu, rvu.data() + 2 * r, 16, hipMemcpyHostToDevice));
         R.fine_calls = rfc[r];
+    }
+    for (size_t v = 0; v < h->mm.lv.size(); v++) {
+        HCHK(hipMemcpy(h->mm.lv[v].d_st, lvst[v].data(), NGP_LV_WORDS * 8, hipMemcpyHostToDevice));
+        HCHK(hipMemcpy(h->mm.lv[v].d_zeta, lvz[v].data(), lvz[v].size() * 8, hipMemcpyHostToDevice));
     }
     h->seed = ids[0]; h->chain = (uint32_t)ids[1];  // the draws continue the interrupted chain's streams
     h->poisoned = false;
@@ -2864,7 +2960,8 @@ int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp
     HCHK(hipMemcpyAsync(h->cm.d_sum_beta2, o + h->P, pb, hipMemcpyDeviceToDevice, h->stream));
     HCHK(hipMemcpyAsync(h->cm.d_sum_delta, o + 2 * h->P, pb, hipMemcpyDeviceToDevice, h->stream));
     if (h->nvb) HCHK(hipMemcpyAsync(h->mm.d_sum_varBeta, o + 3 * h->P, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size() + 3);
+    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size() +
+                             NGP_LV_SUM * h->mm.lv.size() + 3);
     HCHK(hipMemcpyAsync(tail.data(), o + 3 * h->P + h->nvb, tail.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
     for (size_t si = 0; si < h->sets.size(); si++)
@@ -2891,7 +2988,11 @@ int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp
             off += (size_t)h->mm.rnd[r].q;
         }
     }
-    const size_t t0 = tf + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size();
+    size_t t0 = tf + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size();
+    for (auto &V : h->mm.lv) {
+        HCHK(hipMemcpy(V.d_st + NGP_LV_SUM, tail.data() + t0, NGP_LV_SUM * sizeof(double), hipMemcpyHostToDevice));
+        t0 += NGP_LV_SUM;
+    }
     sc.sum_varE = tail[t0]; sc.sum_b = tail[t0 + 1]; sc.nKept = (long long)std::llround(tail[t0 + 2]);
     HCHK(hipMemcpy(h->cm.d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
     HCHK(hipStreamSynchronize(h->stream));
@@ -2940,7 +3041,8 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
     for (int i = 0; i < n; i++) {
         REQUIRE(hs[i]->pm, NGP_ERR_STATE, "ngp_allreduce_posterior: a handle has no panel");
         REQUIRE(hs[i]->P == h->P && hs[i]->nvb == h->nvb && hs[i]->sets.size() == h->sets.size() && hs[i]->mm.nfixcol == h->mm.nfixcol &&
-                    hs[i]->nclass_total == h->nclass_total && hs[i]->mm.nrandcol == h->mm.nrandcol && hs[i]->mm.rnd.size() == h->mm.rnd.size(),
+                    hs[i]->nclass_total == h->nclass_total && hs[i]->mm.nrandcol == h->mm.nrandcol && hs[i]->mm.rnd.size() == h->mm.rnd.size() &&
+                    hs[i]->mm.lv.size() == h->mm.lv.size(),
                 NGP_ERR_ARG, "ngp_allreduce_posterior: the chains do not share one model");
         for (int k = 0; k < i; k++) REQUIRE(hs[k] != hs[i], NGP_ERR_ARG, "ngp_allreduce_posterior: a handle is listed twice");
     }
@@ -3476,6 +3578,165 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
  * variance entries, tuple k} | records: int64 iteration | varE | b | b_fixed[nfix] | beta[P] | varBeta[nvb] | piHat[2 nsets] | class
  * probabilities[nclass] | delta[P] as bytes, padded to 8.  nextgp.jl_amd/api.py (samples_to_out_files) turns it into the
  * reference's *Out text files. */
+/* BayesLV marker set (include/nextgp_hip.h).  On the device the set is a BayesPR set with one variance per locus and NO region entry
+ * (h_regs / segments): k_prep draws no region chi-square for it and k_regdraw never touches it; its variances come from launch_lv. */
+int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double varBeta0, const double *C, int64_t ld, int32_t ncov,
+                              double varZeta0, int32_t est_mode, double est_fraction, const double *zeta0, const double *lhs0,
+                              const double *rhs0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
+    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
+    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
+    REQUIRE(ncov >= 1 && ncov <= NGP_LV_MAXCOV, NGP_ERR_ARG, "BayesLV: the covariate matrix needs 1..16 columns");
+    REQUIRE(C != nullptr && ld >= ncol, NGP_ERR_ARG, "BayesLV: covariates missing (ncol x ncov, column-major, ld >= ncol)");
+    REQUIRE(std::isfinite(varBeta0) && varBeta0 > 0.0, NGP_ERR_ARG, "BayesLV: varBeta0 must be finite and positive (its logarithm is modelled)");
+    REQUIRE(std::isfinite(varZeta0) && varZeta0 > 0.0, NGP_ERR_ARG, "BayesLV: varZeta0 must be finite and positive");
+    REQUIRE(est_mode >= 0 && est_mode <= 2, NGP_ERR_ARG, "BayesLV: est_mode is 0 (fixed), 1 (var(zeta)) or 2 (fraction of var(logVar))");
+    if (est_mode == 2) REQUIRE(std::isfinite(est_fraction) && est_fraction > 0.0, NGP_ERR_ARG, "BayesLV: est_fraction must be positive in mode 2");
+    if (est_mode != 0) REQUIRE(ncol >= 2, NGP_ERR_ARG, "BayesLV: an estimated varZeta needs at least two loci (a sample variance)");
+    for (int64_t k = col0; k < col0 + ncol; k++) REQUIRE(h->h_setof[k] == -1, NGP_ERR_ARG, "marker sets overlap");
+    for (int k = 0; k < ncov; k++)
+        for (int64_t l = 0; l < ncol; l++) REQUIRE(std::isfinite(C[(size_t)k * ld + l]), NGP_ERR_ARG, "BayesLV: non-finite covariate");
+    if (zeta0) for (int64_t l = 0; l < ncol; l++) REQUIRE(std::isfinite(zeta0[l]), NGP_ERR_ARG, "BayesLV: non-finite zeta0");
+    // iCpC = inv(C'C + ridge I), Float64, fixed order: (C'C)_ij = sum over the loci in ascending order of C_li C_lj (from 0.0);
+    // ridge = min_i |(C'C)_ii / 10000| (src/mme.jl:433-436); A = L L' (lower Cholesky, row by row); W = inv(L) by forward substitution,
+    // column by column; iCpC_ij = sum_{k >= max(i, j)} W_ki W_kj (ascending k)
+    const int nc = ncov;
+    std::vector<double> A((size_t)nc * nc), L((size_t)nc * nc, 0.0), W((size_t)nc * nc, 0.0), inv((size_t)nc * nc);
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j <= i; j++) {
+            double a = 0.0;
+            for (int64_t l = 0; l < ncol; l++) a = a + C[(size_t)i * ld + l] * C[(size_t)j * ld + l];
+            A[(size_t)i * nc + j] = a; A[(size_t)j * nc + i] = a;
+        }
+    double ridge = std::fabs(A[0] / 10000.0);
+    for (int i = 1; i < nc; i++) ridge = std::min(ridge, std::fabs(A[(size_t)i * nc + i] / 10000.0));
+    for (int i = 0; i < nc; i++) A[(size_t)i * nc + i] = A[(size_t)i * nc + i] + ridge;
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j <= i; j++) {
+            double sres = A[(size_t)i * nc + j];
+            for (int k = 0; k < j; k++) sres = sres - L[(size_t)i * nc + k] * L[(size_t)j * nc + k];
+            if (i == j) {
+                REQUIRE(std::isfinite(sres) && sres > 0.0, NGP_ERR_ARG, "BayesLV: C'C (+ ridge) is not positive definite (its Cholesky factorisation fails)");
+                L[(size_t)i * nc + i] = std::sqrt(sres);
+            } else {
+                L[(size_t)i * nc + j] = sres / L[(size_t)j * nc + j];
+            }
+        }
+    for (int j = 0; j < nc; j++)
+        for (int i = j; i < nc; i++) {
+            double sres = (i == j) ? 1.0 : 0.0;
+            for (int k = j; k < i; k++) sres = sres - L[(size_t)i * nc + k] * W[(size_t)k * nc + j];
+            W[(size_t)i * nc + j] = sres / L[(size_t)i * nc + i];
+        }
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j <= i; j++) {
+            double a = 0.0;
+            for (int k = i; k < nc; k++) a = a + W[(size_t)k * nc + i] * W[(size_t)k * nc + j];
+            REQUIRE(std::isfinite(a), NGP_ERR_ARG, "BayesLV: inverting C'C (+ ridge) overflowed");
+            inv[(size_t)i * nc + j] = a; inv[(size_t)j * nc + i] = a;
+        }
+    // device arrays first: a failure leaves the handle as it was
+    HLv V;
+    V.set = (int)h->sets.size(); V.n = ncol; V.ncov = ncov; V.mode = est_mode; V.frac = (est_mode == 2) ? est_fraction : 0.0; V.varZeta0 = varZeta0;
+    if (zeta0) V.zeta0.assign(zeta0, zeta0 + ncol);
+    const size_t nseg = (size_t)((ncol + 255) / 256);
+    if ((rc = V.d_C.alloc(h, (size_t)ncol * ncov))) return rc;
+    if ((rc = V.d_iCpC.alloc(h, (size_t)nc * nc))) return rc;
+    if ((rc = V.d_zeta.alloc(h, (size_t)ncol))) return rc;
+    if ((rc = V.d_logv.alloc(h, (size_t)ncol))) return rc;
+    if ((rc = V.d_part.alloc(h, nseg * (size_t)ncov))) return rc;
+    if ((rc = V.d_vpart.alloc(h, nseg))) return rc;
+    if ((rc = V.d_st.alloc(h, NGP_LV_WORDS))) return rc;
+    if ((rc = V.d_trapseg.alloc(h, nseg))) return rc;
+    for (int k = 0; k < ncov; k++)
+        HCHK(hipMemcpy(V.d_C + (size_t)k * ncol, C + (size_t)k * ld, (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(V.d_iCpC, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = lv_reset(h, V))) return rc;
+    // the marker set: BayesPR with one region per locus, outside the region tables
+    const int si = (int)h->sets.size();
+    HSet hs{col0, ncol, NGP_METHOD_BAYESLV, 4.0, 0.0, ncol, h->nvb, 0, 0, 0.5, std::vector<double>((size_t)ncol, varBeta0)};
+    hs.lv = (int)h->mm.lv.size();
+    const int64_t new_nvb = h->nvb + ncol;
+    if (new_nvb > h->mm.vb_cap) {
+        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
+        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
+        h->mm.vb_cap = cap;
+    }
+    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, hs.vb0.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> z((size_t)ncol, 0.0);
+    HCHK(hipMemcpy(h->cm.d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    DSet ds;
+    memset(&ds, 0, sizeof(ds));
+    ds.method = NGP_METHOD_BAYESPR; ds.df = 4.0; ds.col0 = col0; ds.ncol = ncol;  // (df, scale: never read -- no region draw)
+    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.5, 0.5);  // the placeholder of sets without pi
+    HCHK(hipStreamSynchronize(h->stream));
+    for (int64_t l = 0; l < ncol; l++) {
+        h->h_setof[col0 + l] = (int8_t)si;
+        h->h_loc[col0 + l] = (int32_t)l;
+        h->h_vbidx[col0 + l] = (int32_t)(h->nvb + l);
+    }
+    h->nvb = new_nvb;
+    h->sets.push_back(hs);
+    h->mm.lv.push_back(std::move(V));
+    h->tables_dirty = true;
+    h->mm.trace_ext_cap = 0;
+    if (set_id) *set_id = si;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_lv_state(ngp_handle *h, int32_t set_id, double *c, double *sum_c, double *varZeta, double *sum_varZeta, double *zeta,
+                         double *iCpC, int64_t *trapped) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int)h->sets.size() && h->sets[(size_t)set_id].lv >= 0, NGP_ERR_ARG, "not a BayesLV set");
+    const HLv &V = h->mm.lv[(size_t)h->sets[(size_t)set_id].lv];
+    HCHK(hipStreamSynchronize(h->stream));
+    double st[NGP_LV_WORDS];
+    HCHK(hipMemcpy(st, V.d_st, sizeof(st), hipMemcpyDeviceToHost));
+    for (int k = 0; k < V.ncov; k++) {
+        if (c) c[k] = st[NGP_LV_C + k];
+        if (sum_c) sum_c[k] = st[NGP_LV_SUM + k];
+    }
+    if (varZeta) *varZeta = st[NGP_LV_VZ];
+    if (sum_varZeta) *sum_varZeta = st[NGP_LV_SUM + NGP_LV_VZ];
+    if (trapped) *trapped = (int64_t)st[NGP_LV_TRAP];
+    if (zeta) HCHK(hipMemcpy(zeta, V.d_zeta, (size_t)V.n * sizeof(double), hipMemcpyDeviceToHost));
+    if (iCpC) HCHK(hipMemcpy(iCpC, V.d_iCpC, (size_t)V.ncov * V.ncov * sizeof(double), hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_lv_state(ngp_handle *h, int32_t set_id, const double *c, const double *sum_c, double varZeta, double sum_varZeta,
+                         const double *zeta) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int)h->sets.size() && h->sets[(size_t)set_id].lv >= 0, NGP_ERR_ARG, "not a BayesLV set");
+    REQUIRE(std::isfinite(varZeta) && varZeta > 0.0 && std::isfinite(sum_varZeta), NGP_ERR_ARG, "BayesLV: varZeta must be finite and positive");
+    HLv &V = h->mm.lv[(size_t)h->sets[(size_t)set_id].lv];
+    if (zeta) for (int64_t l = 0; l < V.n; l++) REQUIRE(std::isfinite(zeta[l]), NGP_ERR_ARG, "BayesLV: non-finite zeta");
+    HCHK(hipStreamSynchronize(h->stream));
+    double st[NGP_LV_WORDS];
+    HCHK(hipMemcpy(st, V.d_st, sizeof(st), hipMemcpyDeviceToHost));
+    for (int k = 0; k < V.ncov; k++) {
+        if (c) st[NGP_LV_C + k] = c[k];
+        if (sum_c) st[NGP_LV_SUM + k] = sum_c[k];
+    }
+    st[NGP_LV_VZ] = varZeta; st[NGP_LV_SUM + NGP_LV_VZ] = sum_varZeta;
+    HCHK(hipMemcpy(V.d_st, st, sizeof(st), hipMemcpyHostToDevice));
+    if (zeta) HCHK(hipMemcpy(V.d_zeta, zeta, (size_t)V.n * sizeof(double), hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
 int32_t ngp_set_sample_file(ngp_handle *h, const char *path) {
     NGP_TRY
     int rc;

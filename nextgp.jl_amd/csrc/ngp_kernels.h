@@ -1488,6 +1488,7 @@ __global__ void k_eval_math(int which, const double *__restrict__ in, long long 
         case 0: v = det_log(x); break;
         case 1: v = ppnd16(x); break;
         case 2: v = det_sqrt(x); break;
+        case 4: v = det_exp_any(x); break;
         default: v = 1.0 / x; break;
     }
     out[i] = v;

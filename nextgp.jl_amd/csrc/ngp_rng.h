@@ -24,6 +24,9 @@
 #define NGP_KIND_T_WISHART 11   // Tuple sets: Bartlett factor of a region's inverse-Wishart draw, (set << 40) | (region << 8) | (i << 4) | j
 #define NGP_KIND_U_NORMAL 12    // random-effect sets: the normal of a level's draw, (set << 40) | level (src/functions.jl:70)
 #define NGP_KIND_U_CHI2 13      // random-effect sets: the chi-square of varU, keyed by the set (src/functions.jl:498-501)
+#define NGP_KIND_LV_UNIFORM 14  // BayesLV sets: the four consecutive uniforms of a locus' slice draw, (set << 40) | locus (src/functions.jl:455-466)
+#define NGP_KIND_LV_NORMAL 15   // BayesLV sets: the normal of coefficient k of the log-variance regression, (set << 40) | k (src/functions.jl:477)
+#define NGP_KIND_LV_START 16    // BayesLV sets: the starting value of a locus' zeta (iteration 0), (set << 40) | locus (src/mme.jl:430)
 
 #define NGP_GOLD 0x9E3779B97F4A7C15ULL
 
@@ -142,6 +145,10 @@ __device__ inline double det_exp(double x) {
     const double res = under ? 0.0 : y * sc;
     return isnan_x ? x_in : res;
 }
+
+// exp for an argument of either sign (BayesLV's slice bounds): det_exp where x <= 0, its IEEE reciprocal where x > 0 (within 2 ulp);
+// x > 708 gives +inf, a NaN comes back a NaN
+__device__ inline double det_exp_any(double x) { return (x <= 0.0) ? det_exp(x) : 1.0 / det_exp(-x); }
 
 // det_exp for an argument that is <= 0 or a NaN (the class search's L - max L): the same operations, so the same bits, without the
 // guards such an argument does not need -- x < -708 (and -inf: a class that does not exist) gives 0, a NaN comes back a NaN.

@@ -108,6 +108,57 @@ function add_marker_set_r!(h::Handle, col0::Integer, ncol::Integer, df::Float64,
     return id[]
 end
 
+# BayesLV set (src/mme.jl:418-439): one variance per locus (all varBeta0 at first), covariates = M[s].covariates (the design matrix of
+# the variance formula, ncol x ncov), varZeta = M[s].varZeta[1], estVarZeta = M[s].estVarZeta (false / true / a Float64 fraction),
+# zeta0 = M[s].SNPVARRESID (the reference's unseeded start) or nothing for the library's keyed start
+function add_marker_set_lv!(h::Handle, col0::Integer, ncol::Integer, varBeta0::Float64, covariates::AbstractMatrix, varZeta::Float64,
+                            estVarZeta; zeta0=nothing, lhs0=C_NULL, rhs0=C_NULL)
+    Cm = Matrix{Float64}(covariates)
+    size(Cm, 1) == ncol || error("BayesLV: one covariate row per locus")
+    mode = estVarZeta === false ? 0 : (estVarZeta === true ? 1 : 2)
+    frac = mode == 2 ? Float64(estVarZeta) : 0.0
+    z0 = zeta0 === nothing ? C_NULL : Vector{Float64}(zeta0)
+    id = Ref{Int32}(0)
+    check(h, ccall((:ngp_add_marker_set_lv, LIB), Int32,
+                   (Ptr{Cvoid}, Int64, Int64, Float64, Ptr{Float64}, Int64, Int32, Float64, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+                   h.ptr, col0, ncol, varBeta0, Cm, size(Cm, 1), size(Cm, 2), varZeta, mode, frac, z0, lhs0, rhs0, id))
+    return id[]
+end
+
+# (c, sum_c, varZeta, sum_varZeta, zeta, iCpC, trapped) of a BayesLV set
+function lv_state(h::Handle, set_id::Integer, ncol::Integer, ncov::Integer)
+    c = Vector{Float64}(undef, ncov); sc = similar(c); zeta = Vector{Float64}(undef, ncol); ic = Matrix{Float64}(undef, ncov, ncov)
+    vz = Ref{Float64}(0.0); svz = Ref{Float64}(0.0); tr = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_lv_state, LIB), Int32,
+                   (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+                   h.ptr, set_id, c, sc, vz, svz, zeta, ic, tr))
+    return (c = c, sum_c = sc, varZeta = vz[], sum_varZeta = svz[], zeta = zeta, iCpC = ic, trapped = tr[])
+end
+
+# resume: the library's copy of a BayesLV set's state (nothing: left as it is)
+function set_lv_state!(h::Handle, set_id::Integer, varZeta::Float64; c=nothing, sum_c=nothing, sum_varZeta::Float64=0.0, zeta=nothing)
+    p(x) = x === nothing ? C_NULL : Vector{Float64}(x)
+    check(h, ccall((:ngp_set_lv_state, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}),
+                   h.ptr, set_id, p(c), p(sum_c), varZeta, sum_varZeta, p(zeta)))
+end
+
+"""
+    sampleBayesLV!(h, set_id, mSet, M, beta, delta, ycorr, varE, varBeta)
+
+Fine seam of a BayesLV set: same argument list as the reference's `sampleBayesLV!(mSet, M, beta, delta, ycorr, varE, varBeta)`
+(src/functions.jl:421) plus the handle and the set id.  One call does the sweep and the variance model; `M[mSet].c`, `varZeta`, `logVar`
+and `SNPVARRESID` are written back from the library, which holds them between the calls.
+"""
+function sampleBayesLV!(h::Handle, set_id::Integer, mSet, M, beta, delta, ycorr::Vector{Float64}, varE::Float64, varBeta)
+    sweep!(h, set_id, mSet, M, beta, delta, ycorr, varE, varBeta)
+    st = lv_state(h, set_id, length(varBeta[mSet]), length(M[mSet].c))
+    M[mSet].c .= st.c
+    M[mSet].varZeta[1] = st.varZeta
+    M[mSet].logVar .= log.(varBeta[mSet])
+    M[mSet].SNPVARRESID .= st.zeta
+    return nothing
+end
+
 # Correlated marker sets -- sampleBayesPR!(::Tuple), src/functions.jl:140-154, set-up src/mme.jl:448-489.  M[pSet].data is a Vector of
 # N x k matrices X_l (src/mme.jl:456-457); on the device the k columns of a locus sit side by side, floor(64 / k) loci per 64-column
 # block from a block boundary on (include/nextgp_hip.h, ngp_add_marker_set_tuple).  tuple_panel builds that block of the panel,
@@ -159,12 +210,15 @@ set_sample_file!(h::Handle, path::Union{AbstractString,Nothing}) =
 function foreach_sample(f, path::AbstractString)
     open(path, "r") do io
         magic = String(read(io, 8))
-        magic in ("NGPSMP01", "NGPSMP02") || error("not a sample file: $path")
+        magic in ("NGPSMP01", "NGPSMP02", "NGPSMP03") || error("not a sample file: $path")
         P, nvb, nsets, nfix, ncls, rec = ntuple(_ -> read(io, Int64), 6)
         sets = [ntuple(_ -> read(io, Int64), 6) for _ in 1:nsets]     # (method, K, col0, ncol, variance entries, tuple k)
-        rq = magic == "NGPSMP02" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each
+        rq = magic != "NGPSMP01" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each
+        # BayesLV sets ("NGPSMP03"): (marker set, ncov) of each; a record holds c (16 words, ncov used) | varZeta per set behind class_pi
+        lvs = magic == "NGPSMP03" ? [(read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64}[]
         nr = sum(rq; init = 0) + length(rq)                           # u (set after set) and varU between b_fixed and beta
-        nd = 3 + nfix + nr + P + nvb + 2 * nsets + ncls
+        ncp = 3 + nfix + nr + P + nvb + 2 * nsets + ncls               # doubles in front of the BayesLV words
+        nd = ncp + 17 * length(lvs)
         raw = Vector{UInt8}(undef, rec)
         while !eof(io)
             readbytes!(io, raw, rec) == rec || break
@@ -176,7 +230,9 @@ function foreach_sample(f, path::AbstractString)
             f(sets, (iter = reinterpret(Int64, view(raw, 1:8))[1], varE = d[2], b = d[3], b_fixed = d[4:3 + nfix], u = u, varU = varU,
                      beta = d[o + nfix + 1:o + nfix + P], varBeta = d[o + nfix + P + 1:o + nfix + P + nvb],
                      piHat = d[o + nfix + P + nvb + 1:o + nfix + P + nvb + 2 * nsets],
-                     class_pi = d[o + nfix + P + nvb + 2 * nsets + 1:nd], delta = raw[8 * nd + 1:8 * nd + P]))
+                     class_pi = d[o + nfix + P + nvb + 2 * nsets + 1:ncp],
+                     lv_c = [d[ncp + 17 * (i - 1) + 1:ncp + 17 * (i - 1) + lvs[i][2]] for i in eachindex(lvs)],
+                     lv_varZeta = [d[ncp + 17 * i] for i in eachindex(lvs)], delta = raw[8 * nd + 1:8 * nd + P]))
         end
     end
 end
@@ -326,7 +382,7 @@ end
 
 Coarse seam: drop-in for `samplers.runSampler!` (src/samplers.jl:23) for models made of fixed effects (intercept, covariates,
 factors, blocked groups), Symbol / Expr random effects -- (1|g) terms and PED sets, whose Ainv the reference has built -- and Symbol marker
-sets with BayesPR / BayesB / BayesC / BayesR priors.  Anything else falls back to the reference sampler.
+sets with BayesPR / BayesB / BayesC / BayesR / BayesLV priors.  Anything else falls back to the reference sampler.
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
                      seed::Integer=1, device::Integer=0)
@@ -348,7 +404,10 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     for s in sets
         P = M[s].dims[2]
         method = M[s].method == "BayesB" ? 1 : (M[s].method == "BayesC" ? 2 : (M[s].method == "BayesR" ? 3 : 0))
-        if method == 3   # ONE variance, class multipliers and class probabilities (src/mme.jl:374-383)
+        if M[s].method == "BayesLV"   # covariates, varZeta, estVarZeta and the reference's starting zeta (src/mme.jl:418-439)
+            ids[s] = add_marker_set_lv!(h, col0, P, Float64(varBeta[s][1]), M[s].covariates, Float64(M[s].varZeta[1]), M[s].estVarZeta;
+                                        zeta0 = M[s].SNPVARRESID, lhs0 = Float64.(M[s].lhs), rhs0 = Float64.(M[s].rhs))
+        elseif method == 3   # ONE variance, class multipliers and class probabilities (src/mme.jl:374-383)
             ids[s] = add_marker_set_r!(h, col0, P, Float64(M[s].df), Float64(M[s].scale), Float64(varBeta[s][1]), Float64.(vec(M[s].vClass)),
                                        Float64.(vec(M[s].piHat)); estPi = M[s].estPi, lhs0 = Float64.(M[s].lhs), rhs0 = Float64.(M[s].rhs))
         else
@@ -388,6 +447,7 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     run!(h, chainLength)
     set_sample_file!(h, nothing)                 # flushes and closes
     # ... and become the rows of the reference's *Out files afterwards, one record in memory at a time
+    lvsets = [s for s in sets if M[s].method == "BayesLV"]                  # in the order the library numbers them
     foreach_sample(smpfile) do sinfo, smp
         open(io -> writedlm(io, smp.b_fixed'), outPut * "/bOut", "a")       # src/samplers.jl:57
         open(io -> writedlm(io, smp.varE), outPut * "/varEOut", "a")        # src/samplers.jl:58
@@ -405,6 +465,11 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
                 K = Int(sinfo[k][2])
                 open(io -> writedlm(io, smp.class_pi[k0+1:k0+K]'), outPut * "/pi$(s)Out", "a")
                 k0 += K
+            end
+            if M[s].method == "BayesLV"                                                             # :89-92
+                i = findfirst(==(s), lvsets)
+                open(io -> writedlm(io, smp.lv_c[i]'), outPut * "/c$(s)Out", "a")
+                open(io -> writedlm(io, smp.lv_varZeta[i:i]'), outPut * "/varZeta$(s)Out", "a")
             end
             nr = length(varBeta[s])
             open(io -> writedlm(io, smp.varBeta[v0+1:v0+nr]'), outPut * "/var$(s)Out", "a")       # :101-103
@@ -432,6 +497,10 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         P = M[s].dims[2]; nr = length(varBeta[s])
         vec(beta[M[s].pos]) .= bet[c0+1:c0+P]; vec(delta[M[s].pos]) .= del[c0+1:c0+P]
         varBeta[s] isa Vector{Float64} && (varBeta[s] .= vb[v0+1:v0+nr])
+        if M[s].method == "BayesLV"               # the variance model's state as sampleBayesLV! leaves it (src/functions.jl:466-485)
+            st = lv_state(h, ids[s], P, length(M[s].c))
+            M[s].c .= st.c; M[s].varZeta[1] = st.varZeta; M[s].logVar .= log.(vb[v0+1:v0+nr]); M[s].SNPVARRESID .= st.zeta
+        end
         c0 += P; v0 += nr
     end
     return h
