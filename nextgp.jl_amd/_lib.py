@@ -35,20 +35,25 @@ def _sample_header(f, path):
     return P, nvb, nsets, nfix, ncls, rec, sets, rq, lv
 
 
-def _split_lv(d, o, lv):
-    """c of every BayesLV set (list of [..., ncov]) and varZeta ([..., nlv]) from record doubles d at offset o."""
-    c = [d[..., o + LV_WORDS * i:o + LV_WORDS * i + ncov] for i, (_, ncov) in enumerate(lv)]
-    vz = d[..., o + LV_MAXCOV:o + LV_WORDS * len(lv):LV_WORDS] if lv else d[..., o:o]
-    return c, vz
+def _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv):
+    """Where the fields of a sample record lie (the record: csrc/ngp_state.h, sample_layout): (name -> (first double, doubles) in record
+    order, doubles of the record in front of the delta bytes).  u<i> / lv<i> are the words of random-effect set i / BayesLV set i."""
+    at, o = {}, 0
+    for name, n in ([("iter", 1), ("varE", 1), ("b", 1), ("b_fixed", nfix)] + [(f"u{i}", q) for i, q in enumerate(rq)] + [("varU", len(rq)),
+                    ("beta", P), ("varBeta", nvb), ("piHat", 2 * nsets), ("class_pi", ncls)] + [(f"lv{i}", LV_WORDS) for i in range(len(lv))]):
+        at[name] = (o, n); o += n
+    return at, o
 
 
-def _split_random(d, o, rq):
-    """u of every random-effect set (list) and varU (array) from record doubles d (last axis) at offset o; returns (u, varU, new offset)."""
-    u = []
-    for q in rq:
-        u.append(d[..., o:o + q]); o += q
-    vu = d[..., o:o + len(rq)]; o += len(rq)
-    return u, vu, o
+def _sample_record(d, at, rq, lv):
+    """The named fields of record doubles d (records along every axis but the last); iter and delta are the caller's."""
+    cut = lambda name, n=None: d[..., at[name][0]:at[name][0] + (at[name][1] if n is None else n)]
+    out = {k: cut(k) for k in ("b_fixed", "varU", "beta", "varBeta", "piHat", "class_pi")}
+    out["varE"], out["b"] = d[..., at["varE"][0]][()], d[..., at["b"][0]][()]  # ([()]: a scalar, not a 0-d array, for a single record)
+    out["u"] = [cut(f"u{i}") for i in range(len(rq))]
+    out["lv_c"] = [cut(f"lv{i}", ncov) for i, (_, ncov) in enumerate(lv)]  # (c is padded to LV_MAXCOV words, varZeta follows it)
+    out["lv_varZeta"] = np.stack([d[..., at[f"lv{i}"][0] + LV_MAXCOV] for i in range(len(lv))], axis=-1) if lv else d[..., 0:0]
+    return out
 
 
 def read_sample_file(path):
@@ -60,18 +65,9 @@ def read_sample_file(path):
         raw = np.frombuffer(f.read(), dtype=np.uint8)
     n = len(raw) // rec
     raw = raw[:n * rec].reshape(n, rec)
-    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls + LV_WORDS * len(lv)
-    d = raw[:, :nd * 8].copy().view(np.float64)
-    o = 3
-    out = dict(iter=raw[:, :8].copy().view(np.int64)[:, 0], varE=d[:, 1], b=d[:, 2], sets=sets)
-    out["b_fixed"] = d[:, o:o + nfix]; o += nfix
-    out["u"], out["varU"], o = _split_random(d, o, rq)
-    out["beta"] = d[:, o:o + P]; o += P
-    out["varBeta"] = d[:, o:o + nvb]; o += nvb
-    out["piHat"] = d[:, o:o + 2 * nsets]; o += 2 * nsets
-    out["class_pi"] = d[:, o:o + ncls]; o += ncls
-    out["lv_c"], out["lv_varZeta"] = _split_lv(d, o, lv)
-    out["delta"] = raw[:, nd * 8:nd * 8 + P]
+    at, nd = _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv)
+    out = _sample_record(raw[:, :nd * 8].copy().view(np.float64), at, rq, lv)
+    out.update(iter=raw[:, :8].copy().view(np.int64)[:, 0], sets=sets, delta=raw[:, nd * 8:nd * 8 + P])
     return out
 
 
@@ -86,20 +82,11 @@ def iter_sample_file(path):
     n = (size - off) // rec
     if n <= 0:
         return
-    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + ncls + LV_WORDS * len(lv)
+    at, nd = _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv)
     mm = np.memmap(path, dtype=np.uint8, mode="r", offset=off, shape=(n, rec))
     for i in range(n):
-        d = np.frombuffer(mm[i, :nd * 8].tobytes(), dtype=np.float64)
-        o = 3
-        out = dict(iter=int(np.frombuffer(mm[i, :8].tobytes(), dtype=np.int64)[0]), varE=d[1], b=d[2], sets=sets)
-        out["b_fixed"] = d[o:o + nfix]; o += nfix
-        out["u"], out["varU"], o = _split_random(d, o, rq)
-        out["beta"] = d[o:o + P]; o += P
-        out["varBeta"] = d[o:o + nvb]; o += nvb
-        out["piHat"] = d[o:o + 2 * nsets]; o += 2 * nsets
-        out["class_pi"] = d[o:o + ncls]; o += ncls
-        out["lv_c"], out["lv_varZeta"] = _split_lv(d, o, lv)
-        out["delta"] = np.asarray(mm[i, nd * 8:nd * 8 + P])
+        out = _sample_record(np.frombuffer(mm[i, :nd * 8].tobytes(), dtype=np.float64), at, rq, lv)
+        out.update(iter=int(np.frombuffer(mm[i, :8].tobytes(), dtype=np.int64)[0]), sets=sets, delta=np.asarray(mm[i, nd * 8:nd * 8 + P]))
         yield out
     del mm
 

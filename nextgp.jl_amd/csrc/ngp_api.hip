@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <condition_variable>
+#include <cstddef>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -25,6 +26,7 @@
 #include "ngp_random.h"
 #include "ngp_logvar.h"
 #include "ngp_sweep_args.h"
+#include "ngp_state.h"
 
 using namespace ngp;
 
@@ -398,7 +400,6 @@ struct ModelMem {
     int64_t nfixcol = 0;               // sum of ncol over them: entries of d_bfix / d_sum_bfix
     DevArray<double> d_bfix, d_sum_bfix;
     std::vector<HRand> rnd;            // (1|g) random-effect sets (src/functions.jl:57-110), sampled after the fixed-effect sets, in order
-    int64_t nrandcol = 0;              // sum of q over the random-effect sets
     std::vector<HLv> lv;               // variance models of the BayesLV sets (src/functions.jl:442-485), in the order of their sets
     // optional per-iteration traces of selected effects, variances and pi (ngp_set_trace_loci)
     DevArray<int64_t> d_trace_loci;
@@ -1209,19 +1210,77 @@ int set_class_state_dev(ngp_handle *h, int si, const double *pi, const double *s
     return NGP_OK;
 }
 
-// doubles of the packed posterior (ngp_export_posterior_device): 3P + nvb + 2 nsets + sum K + fixed-effect columns
-// (+ sum q + number of random-effect sets) + 3
-int64_t posterior_words(const ngp_handle *h) {
-    return 3 * h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total + h->mm.nfixcol + h->mm.nrandcol + (int64_t)h->mm.rnd.size() +
-           NGP_LV_SUM * (int64_t)h->mm.lv.size() + 3;  // (a BayesLV set: the sums of c, padded to 16, and of varZeta)
+// ---- the chain's state as segments (ngp_state.h: the segment ids, the three layouts, the formats) ----
+// every segment of h's chain.  No device access: the staged words (st.ds, st.sc) are filled by stage()
+void describe(ngp_handle *h, ChainState &st) {
+    const size_t P8 = (size_t)h->P * 8, vb8 = (size_t)h->nvb * 8, fx8 = (size_t)h->mm.nfixcol * 8;
+    st.ds.resize(h->sets.size());
+    st.nfix = h->mm.nfixcol; st.chain64 = h->chain;
+    st.host(SEG_ITER, 0, &h->iter, 8); st.host(SEG_SEED, 0, &h->seed, 8); st.host(SEG_CHAIN, 0, &st.chain64, 8); st.host(SEG_NFIX, 0, &st.nfix, 8);
+    st.host(SEG_VARE, 0, &st.sc.varE, 8); st.host(SEG_B, 0, &st.sc.b, 8);
+    st.host(SEG_SUM_VARE, 0, &st.sc.sum_varE, 8); st.host(SEG_SUM_B, 0, &st.sc.sum_b, 8);
+    st.host(SEG_NKEPT, 0, &st.sc.nKept, 8); st.host(SEG_NKEPT_F64, 0, &st.nkept_f64, 8);
+    st.dev(SEG_YCORR, 0, h->cm.d_ycorr, (size_t)h->N * 8); st.dev(SEG_BETA, 0, h->cm.d_beta, P8); st.dev(SEG_DELTA, 0, h->cm.d_delta, (size_t)h->P);
+    st.dev(SEG_SUM_BETA, 0, h->cm.d_sum_beta, P8); st.dev(SEG_SUM_BETA2, 0, h->cm.d_sum_beta2, P8); st.dev(SEG_SUM_DELTA, 0, h->cm.d_sum_delta, P8);
+    st.dev(SEG_VARBETA, 0, h->mm.d_varBeta, vb8); st.dev(SEG_SUM_VARBETA, 0, h->mm.d_sum_varBeta, vb8);
+    st.dev(SEG_FIX, 0, h->mm.d_bfix, fx8); st.dev(SEG_SUM_FIX, 0, h->mm.d_sum_bfix, fx8);
+    for (int s = 0; s < (int)h->sets.size(); s++) {
+        DSet &d = st.ds[(size_t)s];
+        const size_t K8 = (size_t)h->sets[(size_t)s].K * 8;
+        st.host(SEG_FINE, s, &h->sets[(size_t)s].fine_calls, 8);
+        st.host(SEG_PI, s, &d.piHat0, 16); st.host(SEG_SUM_PI, s, &d.sum_pi0, 16);  // (piHat0 | piHat1 and sum_pi0 | sum_pi1 are neighbours)
+        if (K8) { st.host(SEG_CLS, s, d.pic, K8); st.host(SEG_SUM_CLS, s, d.sum_pic, K8); }
+    }
+    for (int r = 0; r < (int)h->mm.rnd.size(); r++) {
+        HRand &R = h->mm.rnd[(size_t)r];
+        st.dev(SEG_U, r, R.d_u, (size_t)R.q * 8); st.dev(SEG_SUM_U, r, R.d_sum_u, (size_t)R.q * 8);
+        st.dev(SEG_VARU, r, R.d_vu, 8); st.dev(SEG_SUM_VARU, r, R.d_vu + 1, 8); st.dev(SEG_VU, r, R.d_vu, 16);
+        st.host(SEG_RFINE, r, &R.fine_calls, 8);
+    }
+    for (int v = 0; v < (int)h->mm.lv.size(); v++) {
+        HLv &V = h->mm.lv[(size_t)v];
+        st.dev(SEG_LV, v, V.d_st, NGP_LV_SUM * 8); st.dev(SEG_SUM_LV, v, V.d_st + NGP_LV_SUM, NGP_LV_SUM * 8);
+        st.dev(SEG_LV_ALL, v, V.d_st, NGP_LV_WORDS * 8); st.dev(SEG_ZETA, v, V.d_zeta, (size_t)V.n * 8);
+    }
+}
+static_assert(offsetof(DSet, piHat1) == offsetof(DSet, piHat0) + 8 && offsetof(DSet, sum_pi1) == offsetof(DSet, sum_pi0) + 8, "SEG_PI / SEG_SUM_PI");
+
+// the words of DSet and DScal into their staging (one copy each)
+int stage(ngp_handle *h, ChainState &st) {
+    HCHK(hipStreamSynchronize(h->stream));
+    if (!st.ds.empty()) HCHK(hipMemcpy(st.ds.data(), h->cm.d_sets, st.ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(&st.sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    st.nkept_f64 = (double)st.sc.nKept;
+    return NGP_OK;
+}
+
+// ... and back, through the setters: the values (piHat, class probabilities, varE, b), the posterior sums, or both.  k_set_pi
+// recomputes logPi and clears nloci, k_set_class_state recomputes logpic and clears ncls (also for the sums alone), iVarE = 1 / varE.
+int commit(ngp_handle *h, ChainState &st, bool values, bool sums) {
+    int rc;
+    for (int s = 0; s < (int)st.ds.size(); s++) {
+        DSet &d = st.ds[(size_t)s];
+        if (values) hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, s, d.piHat0, d.piHat1);
+        if (sums) hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, s, d.sum_pi0, d.sum_pi1);
+        if (h->sets[(size_t)s].K > 0 && (rc = set_class_state_dev(h, s, values ? d.pic : nullptr, sums ? d.sum_pic : nullptr))) return rc;
+    }
+    DScal sc;  // (the other words -- db, the fixed-point scales -- stay as they are on the device)
+    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+    if (values) { sc.varE = st.sc.varE; sc.iVarE = 1.0 / sc.varE; sc.b = st.sc.b; }
+    if (sums) { sc.sum_varE = st.sc.sum_varE; sc.sum_b = st.sc.sum_b; sc.nKept = st.sc.nKept; }
+    HCHK(hipMemcpy(h->cm.d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
+    HCHK(hipStreamSynchronize(h->stream));
+    return NGP_OK;
+}
+
+// doubles of the packed posterior (ngp_posterior_len)
+int64_t posterior_words(ngp_handle *h) {
+    ChainState st;
+    describe(h, st);
+    return (int64_t)(place(st, posterior_layout).bytes / 8);
 }
 
 // ---- sample stream (ngp_set_sample_file) ----
-size_t sample_rec_bytes(const ngp_handle *h) {
-    const size_t nd = 3 + (size_t)h->mm.nfixcol + (size_t)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()) + (size_t)h->P + (size_t)h->nvb + 2 * h->sets.size() +
-                      (size_t)h->nclass_total + (size_t)NGP_LV_SUM * h->mm.lv.size();
-    return nd * 8 + (((size_t)h->P + 7) & ~(size_t)7);
-}
 void sample_writer_loop(SampleStream *S) {
     (void)hipSetDevice(S->device);
     for (;;) {
@@ -1259,16 +1318,17 @@ SampleStream::~SampleStream() {  // (the members -- ring slots, file -- are free
 // the kept sample of the iteration just enqueued on h->stream goes into the next ring slot, from there to the host on the copy stream
 int sample_enqueue(ngp_handle *h) {
     SampleStream *S = h->smp.get();
+    ChainState st;
+    describe(h, st);
+    const Plan pl = place(st, sample_layout, 8);  // (delta's bytes end the record: padded to whole words)
     if (!S->header_written) {  // the model is final now: sizes and the file header
-        S->rec_bytes = sample_rec_bytes(h);
+        S->rec_bytes = pl.bytes;
         for (int i = 0; i < SampleStream::NSLOT; i++) {
             if (S->d_slot[i].alloc_raw(S->rec_bytes) != hipSuccess || S->h_slot[i].alloc_raw(S->rec_bytes) != hipSuccess)
                 return fail(h, NGP_ERR_NOMEM, "sample ring");
         }
         const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->mm.nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
-        // (a chain with random-effect sets: "NGPSMP02", and the header ends in int64 nrand | q per set)
-        // (a chain with BayesLV sets: "NGPSMP03" -- the random-effect part as in 02, also when empty, then int64 nlv | per set int64
-        // marker set, ncov; records hold c (16 words, the first ncov used) and varZeta of every such set behind the class probabilities)
+        // (the header, by magic: ngp_state.h)
         const bool has_lv = !h->mm.lv.empty();
         bool ok = std::fwrite(has_lv ? "NGPSMP03" : h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
         for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f.get()) == 1; }
@@ -1284,7 +1344,7 @@ int sample_enqueue(ngp_handle *h) {
         }
         if (!ok) return fail(h, NGP_ERR_ARG, "cannot write the sample file header: " + S->path);
         S->header_written = true;
-    } else if (S->rec_bytes != sample_rec_bytes(h)) {
+    } else if (S->rec_bytes != pl.bytes) {
         return fail(h, NGP_ERR_STATE, "the model changed while a sample file is open (ngp_set_sample_file again)");
     }
     const int slot = (int)(S->nenq % SampleStream::NSLOT);
@@ -1294,31 +1354,21 @@ int sample_enqueue(ngp_handle *h) {
         if (S->io_error) return fail(h, NGP_ERR_ARG, "writing the sample file failed: " + S->path);
         S->busy[slot] = true;
     }
-    const long long n = std::max<long long>(std::max<long long>(h->P, h->nvb), std::max<long long>(h->mm.nfixcol, 1));
+    // k_sample_pack writes the scalars, b_fixed, beta, varBeta, pi, the class probabilities and delta; it places beta behind b_fixed
+    // and a gap, delta behind the class probabilities and a gap: the gaps are read off the plan, and what lies in them (the
+    // random-effect sets' u and varU, the BayesLV sets' c and varZeta) is copied to the plan's offsets here
+    const long long nfix = (long long)(pl.size(SEG_FIX) / 8), gap_rand = (long long)(pl.off(SEG_BETA) / 8) - 3 - nfix;
+    const long long gap_cls = (long long)((pl.off(SEG_DELTA) - pl.off(SEG_BETA)) / 8) - h->P - h->nvb - 2 * (long long)h->sets.size();
+    const long long n = std::max<long long>(std::max<long long>(h->P, h->nvb), std::max<long long>(nfix, 1));
     hipLaunchKernelGGL(k_sample_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, S->d_slot[slot], (long long)h->P, (long long)h->nvb,
-                       (int)h->sets.size(), (long long)h->mm.nfixcol, (long long)(h->mm.nrandcol + (int64_t)h->mm.rnd.size()), (long long)(h->nclass_total + NGP_LV_SUM * (int64_t)h->mm.lv.size()),
-                       (long long)h->iter, h->cm.d_beta, h->cm.d_delta, h->mm.d_varBeta, h->cm.d_sets, h->cm.d_scal, h->mm.d_bfix, h->cm.d_abort);
-    {   // random-effect sets: u (set after set), then varU of every set, behind b_fixed
-        double *o = (double *)S->d_slot[slot].get() + 3 + h->mm.nfixcol;
-        int64_t off = 0;
-        hipError_t e0 = hipSuccess;
-        for (size_t r = 0; r < h->mm.rnd.size() && e0 == hipSuccess; r++) {
-            e0 = hipMemcpyAsync(o + off, h->mm.rnd[r].d_u, (size_t)h->mm.rnd[r].q * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-            if (e0 == hipSuccess) e0 = hipMemcpyAsync(o + h->mm.nrandcol + (int64_t)r, h->mm.rnd[r].d_vu, sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-            off += h->mm.rnd[r].q;
-        }
-        // BayesLV sets: c | varZeta of every set, behind the class probabilities (in front of the delta bytes)
-        double *ol = (double *)S->d_slot[slot].get() + 3 + h->mm.nfixcol + h->mm.nrandcol + (int64_t)h->mm.rnd.size() + h->P + h->nvb + 2 * (int64_t)h->sets.size() + h->nclass_total;
-        for (size_t v = 0; v < h->mm.lv.size() && e0 == hipSuccess; v++)
-            e0 = hipMemcpyAsync(ol + NGP_LV_SUM * v, h->mm.lv[v].d_st, NGP_LV_SUM * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-        if (e0 != hipSuccess) {
-            { std::lock_guard<std::mutex> lk(S->mu); S->busy[slot] = false; }
-            S->cv.notify_all();
-            return fail(h, NGP_ERR_HIP, std::string("sample stream: ") + hipGetErrorString(e0));
-        }
-    }
+                       (int)h->sets.size(), nfix, gap_rand, gap_cls, (long long)h->iter, h->cm.d_beta, h->cm.d_delta, h->mm.d_varBeta, h->cm.d_sets,
+                       h->cm.d_scal, h->mm.d_bfix, h->cm.d_abort);
+    hipError_t e = hipSuccess;
+    for (auto &a : pl.at)
+        if (e == hipSuccess && (a.s->id == SEG_U || a.s->id == SEG_VARU || a.s->id == SEG_LV))
+            e = hipMemcpyAsync(S->d_slot[slot].get() + a.off, a.s->p, a.s->bytes, hipMemcpyDeviceToDevice, h->stream);
     // (a HIP call that fails here gives the slot back: the next enqueue would otherwise wait for it forever instead of reporting)
-    hipError_t e = hipEventRecord(S->ev_packed[slot], h->stream);
+    if (e == hipSuccess) e = hipEventRecord(S->ev_packed[slot], h->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(S->copy_stream, S->ev_packed[slot], 0);
     if (e == hipSuccess) e = hipMemcpyAsync(S->h_slot[slot], S->d_slot[slot], S->rec_bytes, hipMemcpyDeviceToHost, S->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(S->ev_copied[slot], S->copy_stream);
@@ -2222,42 +2272,12 @@ int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    const int64_t need = posterior_words(h);
-    REQUIRE(device_ptr && len == need, NGP_ERR_ARG, "export buffer length mismatch (see ngp_posterior_len)");
-    double *o = (double *)device_ptr;
-    const size_t pb = (size_t)h->P * sizeof(double);
-    HCHK(hipMemcpyAsync(o, h->cm.d_sum_beta, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(o + h->P, h->cm.d_sum_beta2, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(o + 2 * h->P, h->cm.d_sum_delta, pb, hipMemcpyDeviceToDevice, h->stream));
-    if (h->nvb) HCHK(hipMemcpyAsync(o + 3 * h->P, h->mm.d_sum_varBeta, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    std::vector<DSet> ds(h->sets.size());
-    HCHK(hipStreamSynchronize(h->stream));
-    if (!ds.empty()) HCHK(hipMemcpy(ds.data(), h->cm.d_sets, ds.size() * sizeof(DSet), hipMemcpyDeviceToHost));
-    DScal sc;
-    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
-    std::vector<double> tail;
-    for (auto &s : ds) { tail.push_back(s.sum_pi0); tail.push_back(s.sum_pi1); }
-    for (auto &s : ds) for (int v = 0; v < s.K; v++) tail.push_back(s.sum_pic[v]);  // BayesR class probabilities, set by set
-    const size_t nfix_at = tail.size();
-    tail.resize(nfix_at + (size_t)h->mm.nfixcol);  // fixed-effect sums beyond the intercept (all columns of all sets, in order)
-    if (h->mm.nfixcol > 0) HCHK(hipMemcpy(tail.data() + nfix_at, h->mm.d_sum_bfix, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyDeviceToHost));
-    if (!h->mm.rnd.empty()) {  // random-effect sets: sums of u (set after set), then the sums of varU
-        const size_t r_at = tail.size();
-        tail.resize(r_at + (size_t)h->mm.nrandcol + h->mm.rnd.size());
-        size_t off = r_at;
-        for (size_t r = 0; r < h->mm.rnd.size(); r++) {
-            HCHK(hipMemcpy(tail.data() + off, h->mm.rnd[r].d_sum_u, (size_t)h->mm.rnd[r].q * sizeof(double), hipMemcpyDeviceToHost));
-            HCHK(hipMemcpy(tail.data() + r_at + (size_t)h->mm.nrandcol + r, h->mm.rnd[r].d_vu + 1, sizeof(double), hipMemcpyDeviceToHost));
-            off += (size_t)h->mm.rnd[r].q;
-        }
-    }
-    for (auto &V : h->mm.lv) {  // BayesLV sets: sums of c (16 words) and of varZeta
-        const size_t at = tail.size();
-        tail.resize(at + NGP_LV_SUM);
-        HCHK(hipMemcpy(tail.data() + at, V.d_st + NGP_LV_SUM, NGP_LV_SUM * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    tail.push_back(sc.sum_varE); tail.push_back(sc.sum_b); tail.push_back((double)sc.nKept);
-    HCHK(hipMemcpy(o + 3 * h->P + h->nvb, tail.data(), tail.size() * sizeof(double), hipMemcpyHostToDevice));
+    ChainState st;
+    describe(h, st);
+    const Plan pl = place(st, posterior_layout);
+    REQUIRE(device_ptr && len == (int64_t)(pl.bytes / 8), NGP_ERR_ARG, "export buffer length mismatch (see ngp_posterior_len)");
+    if ((rc = stage(h, st))) return rc;
+    HCHK(copy_segments(pl, device_ptr, false, true, h->stream));
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -2676,16 +2696,36 @@ int32_t ngp_set_posterior_sums(ngp_handle *h, const double *sum_beta, const doub
     NGP_CATCH(h)
 }
 
-/* Snapshot file: the chain state and the posterior sums, little-endian, no padding:
- *   char[8] "NGPSNAP2" | int64 N, P, nvb, nsets, iter, nKept | uint64 seed | uint64 chain |
- *   model signature: per marker set int64 {method, K, nreg, col0, ncol} | int64 nfixsets | per fixed-effect set int64 ncol |
- *   double varE, b, sum_varE, sum_b | ycorr[N] | beta[P] | delta[P] (uint8) | varBeta[nvb] | piHat[2 nsets] |
- *   sum_beta[P] | sum_beta2[P] | sum_delta[P] | sum_varBeta[nvb] | sum_pi[2 nsets] | fine_calls[nsets] (uint64) |
- *   int64 nfix | b_fixed[nfix] | sum_b_fixed[nfix] | per BayesR set: piHat[K] | sum_pi[K]
- *   | per BayesLV set (only with such sets): the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums) | zeta[ncol];
- *   the signature's second word of such a set carries 256 (ncov + 32 est_mode)
- * It plays the role of the reference's append-only *Out files for a resumed run (src/outFiles.jl:17-21): what was kept
- * before the interruption is not lost. */
+/* Snapshot file: the chain state and the posterior sums (the byte sequence: ngp_state.h).  It plays the role of the reference's
+ * append-only *Out files for a resumed run (src/outFiles.jl:17-21): what was kept before the interruption is not lost. */
+namespace {
+// the model a snapshot belongs to (equal counts are not enough), in the words of the file.  An unweighted chain without
+// random-effect sets writes neither flag, digest nor random part: its bytes are those of the first snapshots.
+struct ModelSig {
+    std::vector<int64_t> sets;  // per marker set {method, K + 16 tuple k + the BayesLV word, nreg, col0, ncol}
+    int64_t nfs = 0;            // fixed-effect sets | NGP_SNAP_WEIGHTED | NGP_SNAP_RANDOM
+    uint64_t digest = 0;        // of the residual weights
+    std::vector<uint64_t> rnd;  // nrand | per set q, digest of its level coding and K
+    std::vector<int64_t> fix;   // ncol per fixed-effect set
+    ModelSig() = default;
+    explicit ModelSig(const ngp_handle *h) {
+        for (auto &hs : h->sets) sets.insert(sets.end(), {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs), hs.nreg, hs.col0, hs.ncol});
+        nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM);
+        if (!h->h_rw.empty()) digest = weights_digest(h->h_rw);
+        if (!h->mm.rnd.empty()) {
+            rnd.push_back((uint64_t)h->mm.rnd.size());
+            for (auto &R : h->mm.rnd) { rnd.push_back((uint64_t)R.q); rnd.push_back(R.sig); }
+        }
+        for (auto &fx : h->mm.fix) fix.push_back(fx.ncol);
+    }
+};
+// delta of a snapshot is 0 / 1 (a BayesR set's classes are drawn anew by the next sweep)
+void snapshot_delta_01(const Plan &body, std::vector<unsigned char> &img) {
+    unsigned char *d = img.data() + body.off(SEG_DELTA);
+    for (size_t k = 0; k < body.size(SEG_DELTA); k++) d[k] = (unsigned char)(d[k] != 0);
+}
+}  // namespace
+
 int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     NGP_TRY
     int rc;
@@ -2693,73 +2733,26 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     REQUIRE(h->pm && h->have_y, NGP_ERR_STATE, "panel / y not set");
     REQUIRE(path != nullptr, NGP_ERR_ARG, "null path");
     REQUIRE(!h->poisoned, NGP_ERR_STATE, "the chain state is invalid (abandoned sweep)");
-    const size_t N = (size_t)h->N, P = (size_t)h->P, nvb = (size_t)h->nvb, ns = h->sets.size();
-    std::vector<double> yc(N), be(P), vb(std::max<size_t>(nvb, 1)), pi(2 * std::max<size_t>(ns, 1)), sb(P), sb2(P), sd(P), sv(std::max<size_t>(nvb, 1)),
-        sp(2 * std::max<size_t>(ns, 1));
-    std::vector<int64_t> de(P);
-    double varE = 0, b = 0, svE = 0, sbb = 0;
-    int64_t iter = 0, nk = 0;
-    if ((rc = ngp_get_state(h, yc.data(), be.data(), de.data(), vb.data(), pi.data(), &varE, &b, &iter))) return rc;
-    if ((rc = ngp_get_posterior_sums(h, sb.data(), sb2.data(), sd.data(), sv.data(), sp.data(), &svE, &sbb, &nk))) return rc;
-    if (h->cm.d_rs) HCHK(hipMemcpy(yc.data(), h->cm.d_ycorr, N * sizeof(double), hipMemcpyDeviceToHost));  // weighted: the scaled y~ as it is (bit-exact resume)
-    std::vector<uint8_t> d8(P);
-    for (size_t k = 0; k < P; k++) d8[k] = (uint8_t)(de[k] != 0);
+    ChainState st;
+    describe(h, st);
+    if ((rc = stage(h, st))) return rc;
+    const Plan head = place(st, snapshot_head_layout), body = place(st, snapshot_body_layout);
+    std::vector<unsigned char> himg(head.bytes), img(body.bytes);
+    HCHK(copy_segments(head, himg.data(), true, true, h->stream));
+    HCHK(copy_segments(body, img.data(), true, true, h->stream));
+    snapshot_delta_01(body, img);
+    const ModelSig sig(h);
     const std::string tmp = std::string(path) + ".tmp";
     File f(fopen(tmp.c_str(), "wb"));
     if (!f) return fail(h, NGP_ERR_ARG, "cannot open " + tmp + " for writing");
     bool ok = true;
     auto W = [&](const void *p, size_t n) { if (n && fwrite(p, 1, n, f.get()) != n) ok = false; };
-    const int64_t hdr[6] = {h->N, h->P, h->nvb, (int64_t)ns, iter, nk};
-    const uint64_t ids[2] = {h->seed, (uint64_t)h->chain};
-    const double scal[4] = {varE, b, svE, sbb};
-    W("NGPSNAP2", 8); W(hdr, sizeof(hdr)); W(ids, sizeof(ids));
-    {   // model signature: a snapshot only loads into the model it was taken from (equal counts are not enough)
-        for (auto &hs : h->sets) { const int64_t sg[5] = {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs), hs.nreg, hs.col0, hs.ncol}; W(sg, sizeof(sg)); }
-        // (weighted residuals: bit 62 of the fixed-set count says so, and a digest of the weights follows it -- unweighted bytes unchanged)
-        const int64_t nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM);
-        W(&nfs, 8);
-        if (!h->h_rw.empty()) { const uint64_t dg = weights_digest(h->h_rw); W(&dg, 8); }
-        if (!h->mm.rnd.empty()) {  // random-effect sets: int64 nrand | per set int64 q, uint64 digest of its levels and K
-            const int64_t nr = (int64_t)h->mm.rnd.size();
-            W(&nr, 8);
-            for (auto &R : h->mm.rnd) { W(&R.q, 8); W(&R.sig, 8); }
-        }
-        for (auto &fx : h->mm.fix) W(&fx.ncol, 8);
-    }
-    W(scal, sizeof(scal));
-    W(yc.data(), N * 8); W(be.data(), P * 8); W(d8.data(), P); W(vb.data(), nvb * 8); W(pi.data(), 2 * ns * 8);
-    W(sb.data(), P * 8); W(sb2.data(), P * 8); W(sd.data(), P * 8); W(sv.data(), nvb * 8); W(sp.data(), 2 * ns * 8);
-    for (auto &hs : h->sets) W(&hs.fine_calls, 8);
-    {   // fixed-effect sets beyond the intercept: effects and their posterior sums
-        std::vector<double> fb((size_t)std::max<int64_t>(h->mm.nfixcol, 1)), fs((size_t)std::max<int64_t>(h->mm.nfixcol, 1));
-        int64_t nf = 0;
-        if ((rc = ngp_get_fixed(h, fb.data(), fs.data(), &nf))) { f.reset(); remove(tmp.c_str()); return rc; }
-        W(&nf, 8); W(fb.data(), (size_t)nf * 8); W(fs.data(), (size_t)nf * 8);
-    }
-    for (size_t si = 0; si < ns; si++)  // BayesR sets: class probabilities and their posterior sums (K each)
-        if (h->sets[si].K > 0) {
-            double cp[NGP_RMAX], cs[NGP_RMAX];
-            int64_t K = 0;
-            if ((rc = ngp_get_class_state(h, (int32_t)si, cp, cs, &K))) { f.reset(); remove(tmp.c_str()); return rc; }
-            W(cp, (size_t)K * 8); W(cs, (size_t)K * 8);
-        }
-    for (size_t r = 0; r < h->mm.rnd.size() && ok; r++) {  // random-effect sets: u[q] | sum_u[q] | varU | sum_varU | fine_calls
-        const HRand &R = h->mm.rnd[r];
-        std::vector<double> a((size_t)R.q), b2((size_t)R.q);
-        double vu[2];
-        if (hipMemcpy(a.data(), R.d_u, a.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(b2.data(), R.d_sum_u, b2.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost) != hipSuccess) { f.reset(); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the random-effect sets"); }
-        W(a.data(), a.size() * 8); W(b2.data(), b2.size() * 8); W(vu, sizeof(vu)); W(&R.fine_calls, 8);
-    }
-    for (size_t v = 0; v < h->mm.lv.size() && ok; v++) {  // BayesLV sets: the small state | zeta
-        const HLv &V = h->mm.lv[v];
-        std::vector<double> z((size_t)V.n);
-        double st[NGP_LV_WORDS];
-        if (hipMemcpy(st, V.d_st, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(z.data(), V.d_zeta, z.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-            f.reset(); remove(tmp.c_str()); return fail(h, NGP_ERR_HIP, "snapshot: reading the BayesLV sets");
-        }
-        W(st, sizeof(st)); W(z.data(), z.size() * 8);
-    }
+    const int64_t dims[4] = {h->N, h->P, h->nvb, (int64_t)h->sets.size()};
+    W("NGPSNAP2", 8); W(dims, sizeof(dims)); W(himg.data(), himg.size());
+    W(sig.sets.data(), sig.sets.size() * 8); W(&sig.nfs, 8);
+    if (sig.nfs & NGP_SNAP_WEIGHTED) W(&sig.digest, 8);
+    W(sig.rnd.data(), sig.rnd.size() * 8); W(sig.fix.data(), sig.fix.size() * 8);
+    W(img.data(), img.size());
     if (fclose(f.release()) != 0) ok = false;  // (a failed close is a failed write)
     if (!ok || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return fail(h, NGP_ERR_ARG, std::string("writing the snapshot failed: ") + path); }
     return NGP_OK;
@@ -2774,115 +2767,64 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
     REQUIRE(path != nullptr, NGP_ERR_ARG, "null path");
     File f(fopen(path, "rb"));
     if (!f) return fail(h, NGP_ERR_ARG, std::string("cannot open snapshot ") + path);
+    ChainState st;
+    describe(h, st);
+    if ((rc = stage(h, st))) return rc;
+    const Plan head = place(st, snapshot_head_layout), body = place(st, snapshot_body_layout);
+    std::vector<unsigned char> himg(head.bytes), img(body.bytes);
     bool ok = true;
     auto Rd = [&](void *p, size_t n) { if (n && fread(p, 1, n, f.get()) != n) ok = false; };
-    char magic[8]; int64_t hdr[6] = {0, 0, 0, 0, 0, 0}; uint64_t ids[2] = {0, 0}; double scal[4] = {0, 0, 0, 0};
-    Rd(magic, 8); Rd(hdr, sizeof(hdr)); Rd(ids, sizeof(ids));
+    auto word = [](const std::vector<unsigned char> &im, size_t off) { int64_t v; memcpy(&v, im.data() + off, 8); return v; };
+    auto real = [](const std::vector<unsigned char> &im, size_t off) { double v; memcpy(&v, im.data() + off, 8); return v; };
+    char magic[8]; int64_t dims[4] = {0, 0, 0, 0};
+    Rd(magic, 8); Rd(dims, sizeof(dims)); Rd(himg.data(), himg.size());
     if (!ok || memcmp(magic, "NGPSNAP2", 8) != 0) return fail(h, NGP_ERR_ARG, "not a snapshot file (bad magic or truncated header)");
-    if (hdr[0] != h->N || hdr[1] != h->P || hdr[2] != h->nvb || hdr[3] != (int64_t)h->sets.size() || hdr[4] < 0 || hdr[5] < 0)
+    const int64_t iter = word(himg, head.off(SEG_ITER));
+    if (dims[0] != h->N || dims[1] != h->P || dims[2] != h->nvb || dims[3] != (int64_t)h->sets.size() || iter < 0 || word(himg, head.off(SEG_NKEPT)) < 0)
         return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (N, P, variance components or marker sets differ)");
-    {   // model signature
-        bool same = true;
-        for (auto &hs : h->sets) {
-            int64_t sg[5] = {-1, -1, -1, -1, -1};
-            Rd(sg, sizeof(sg));
-            same = same && sg[0] == hs.method && sg[1] == hs.K + 16 * hs.tk + lv_sig(h, hs) && sg[2] == hs.nreg && sg[3] == hs.col0 && sg[4] == hs.ncol;
-        }
-        int64_t nfs = -1;
-        Rd(&nfs, 8);
-        const bool snap_w = ok && nfs >= 0 && (nfs & NGP_SNAP_WEIGHTED) != 0;
-        const bool snap_r = ok && nfs >= 0 && (nfs & NGP_SNAP_RANDOM) != 0;
-        uint64_t dg = 0;
-        if (snap_w) { nfs &= ~NGP_SNAP_WEIGHTED; Rd(&dg, 8); }
-        if (snap_r) nfs &= ~NGP_SNAP_RANDOM;
-        if (ok && snap_r != !h->mm.rnd.empty())
+    {   // model signature: the file's against this handle's
+        const ModelSig want(h);
+        ModelSig got;
+        got.sets.assign(want.sets.size(), -1); got.nfs = -1;
+        Rd(got.sets.data(), got.sets.size() * 8); Rd(&got.nfs, 8);
+        const bool snap_w = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_WEIGHTED) != 0, snap_r = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_RANDOM) != 0;
+        if (snap_w) Rd(&got.digest, 8);
+        if (ok && snap_r != !want.rnd.empty())
             return fail(h, NGP_ERR_ARG, snap_r ? "snapshot of a chain with random-effect sets: this handle has none (ngp_add_random_set)"
                                                : "snapshot of a chain without random-effect sets: this handle has them");
         if (snap_r) {
-            int64_t nr = -1;
-            Rd(&nr, 8);
-            bool rsame = ok && nr == (int64_t)h->mm.rnd.size();
-            for (size_t r = 0; rsame && r < h->mm.rnd.size(); r++) {
-                int64_t q = -1; uint64_t sg = 0;
-                Rd(&q, 8); Rd(&sg, 8);
-                rsame = ok && q == h->mm.rnd[r].q && sg == h->mm.rnd[r].sig;
-            }
-            if (!rsame)
+            got.rnd.assign(want.rnd.size(), 0);
+            Rd(got.rnd.data(), got.rnd.size() * 8);
+            if (!ok || got.rnd != want.rnd)
                 return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its random-effect sets differ: levels, level coding or K)");
         }
         if (ok && snap_w != !h->h_rw.empty())
             return fail(h, NGP_ERR_ARG, snap_w ? "snapshot of a chain with residual weights: this handle has none (ngp_set_residual_weights)"
                                                : "snapshot of a chain without residual weights: this handle has them");
-        if (ok && snap_w && dg != weights_digest(h->h_rw))
+        if (ok && snap_w && got.digest != want.digest)
             return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its residual weights differ)");
-        same = same && ok && nfs == (int64_t)h->mm.fix.size();
-        if (same)
-            for (auto &fx : h->mm.fix) { int64_t nc = -1; Rd(&nc, 8); same = same && nc == fx.ncol; }
+        bool same = ok && got.sets == want.sets && got.nfs == want.nfs;
+        if (same) { got.fix.assign(want.fix.size(), -1); Rd(got.fix.data(), got.fix.size() * 8); same = got.fix == want.fix; }
         if (!ok) return fail(h, NGP_ERR_ARG, "snapshot file is truncated (model signature)");
         if (!same)
             return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (methods, classes, regions or fixed-effect sets differ)");
     }
-    Rd(scal, sizeof(scal));
-    if (ok && !(std::isfinite(scal[0]) && (scal[0] > 0.0 || (scal[0] == 0.0 && hdr[4] == 0)))) return fail(h, NGP_ERR_ARG, "snapshot holds an invalid residual variance");
-    const size_t N = (size_t)h->N, P = (size_t)h->P, nvb = (size_t)h->nvb, ns = h->sets.size();
-    std::vector<double> yc(N), be(P), vb(std::max<size_t>(nvb, 1)), pi(2 * std::max<size_t>(ns, 1)), sb(P), sb2(P), sd(P), sv(std::max<size_t>(nvb, 1)),
-        sp(2 * std::max<size_t>(ns, 1));
-    std::vector<uint8_t> d8(P);
-    std::vector<uint64_t> fc(std::max<size_t>(ns, 1));
-    Rd(yc.data(), N * 8); Rd(be.data(), P * 8); Rd(d8.data(), P); Rd(vb.data(), nvb * 8); Rd(pi.data(), 2 * ns * 8);
-    Rd(sb.data(), P * 8); Rd(sb2.data(), P * 8); Rd(sd.data(), P * 8); Rd(sv.data(), nvb * 8); Rd(sp.data(), 2 * ns * 8); Rd(fc.data(), ns * 8);
-    int64_t nf = -1;
-    Rd(&nf, 8);
-    if (ok && nf != h->mm.nfixcol) return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (fixed-effect columns differ)");
-    std::vector<double> fb((size_t)std::max<int64_t>(h->mm.nfixcol, 1)), fs((size_t)std::max<int64_t>(h->mm.nfixcol, 1));
-    Rd(fb.data(), (size_t)h->mm.nfixcol * 8); Rd(fs.data(), (size_t)h->mm.nfixcol * 8);
-    std::vector<double> cls((size_t)2 * std::max<int64_t>(h->nclass_total, 1));
-    Rd(cls.data(), (size_t)2 * h->nclass_total * 8);
-    std::vector<std::vector<double>> ru(h->mm.rnd.size()), rsu(h->mm.rnd.size());
-    std::vector<double> rvu(2 * h->mm.rnd.size() + 1);
-    std::vector<uint64_t> rfc(h->mm.rnd.size() + 1);
-    for (size_t r = 0; r < h->mm.rnd.size(); r++) {
-        ru[r].resize((size_t)h->mm.rnd[r].q); rsu[r].resize((size_t)h->mm.rnd[r].q);
-        Rd(ru[r].data(), ru[r].size() * 8); Rd(rsu[r].data(), rsu[r].size() * 8); Rd(rvu.data() + 2 * r, 16); Rd(rfc.data() + r, 8);
-    }
-    std::vector<std::vector<double>> lvz(h->mm.lv.size()), lvst(h->mm.lv.size());
-    for (size_t v = 0; v < h->mm.lv.size(); v++) {
-        lvst[v].resize(NGP_LV_WORDS); lvz[v].resize((size_t)h->mm.lv[v].n);
-        Rd(lvst[v].data(), NGP_LV_WORDS * 8); Rd(lvz[v].data(), lvz[v].size() * 8);
-    }
+    const size_t have = fread(img.data(), 1, img.size(), f.get());
+    const double varE = real(img, body.off(SEG_VARE));
+    if (have >= body.off(SEG_VARE) + 8 && !(std::isfinite(varE) && (varE > 0.0 || (varE == 0.0 && iter == 0))))
+        return fail(h, NGP_ERR_ARG, "snapshot holds an invalid residual variance");
+    if (have >= body.off(SEG_NFIX) + 8 && word(img, body.off(SEG_NFIX)) != h->mm.nfixcol)
+        return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (fixed-effect columns differ)");
     char extra;
-    const bool at_end = fread(&extra, 1, 1, f.get()) == 0;
-    if (!ok || !at_end) return fail(h, NGP_ERR_ARG, "snapshot file is truncated or has trailing bytes");
-    std::vector<int64_t> de(P);
-    for (size_t k = 0; k < P; k++) de[k] = d8[k];
+    if (have != img.size() || fread(&extra, 1, 1, f.get()) != 0) return fail(h, NGP_ERR_ARG, "snapshot file is truncated or has trailing bytes");
+    REQUIRE(std::isfinite(real(img, body.off(SEG_B))), NGP_ERR_ARG, "bad scalar state (varE must be finite and positive)");
+    REQUIRE(std::isfinite(real(img, body.off(SEG_SUM_VARE))) && std::isfinite(real(img, body.off(SEG_SUM_B))), NGP_ERR_ARG, "bad posterior sums");
+    snapshot_delta_01(body, img);
     h->poisoned = true;  // until the whole restore has gone through: a failure half-way must not leave a mixed state behind as valid
-    if ((rc = ngp_set_state(h, yc.data(), be.data(), de.data(), vb.data(), pi.data(), scal[0], scal[1], hdr[4]))) { h->poisoned = true; return rc; }
-    if (h->cm.d_rs) HCHK(hipMemcpy(h->cm.d_ycorr, yc.data(), N * sizeof(double), hipMemcpyHostToDevice));  // weighted: y~ as saved, not s (y~ / s)
-    h->poisoned = true;  // (ngp_set_state has just declared the state valid: not before the sums, fixed effects and classes are in)
-    if ((rc = ngp_set_posterior_sums(h, sb.data(), sb2.data(), sd.data(), sv.data(), sp.data(), scal[2], scal[3], hdr[5]))) return rc;
-    for (size_t si = 0; si < ns; si++) h->sets[si].fine_calls = fc[si];
-    if (h->mm.nfixcol > 0 && (rc = ngp_set_fixed(h, fb.data(), fs.data(), h->mm.nfixcol))) return rc;
-    {
-        size_t off = 0;
-        for (size_t si = 0; si < ns; si++)
-            if (h->sets[si].K > 0) {
-                const size_t K = (size_t)h->sets[si].K;
-                if ((rc = set_class_state_dev(h, (int)si, cls.data() + off, cls.data() + off + K))) return rc;
-                off += 2 * K;
-            }
-    }
-    for (size_t r = 0; r < h->mm.rnd.size(); r++) {
-        HRand &R = h->mm.rnd[r];
-        HCHK(hipMemcpy(R.d_u, ru[r].data(), ru[r].size() * 8, hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(R.d_sum_u, rsu[r].data(), rsu[r].size() * 8, hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(R.d_vu, rvu.data() + 2 * r, 16, hipMemcpyHostToDevice));
-        R.fine_calls = rfc[r];
-    }
-    for (size_t v = 0; v < h->mm.lv.size(); v++) {
-        HCHK(hipMemcpy(h->mm.lv[v].d_st, lvst[v].data(), NGP_LV_WORDS * 8, hipMemcpyHostToDevice));
-        HCHK(hipMemcpy(h->mm.lv[v].d_zeta, lvz[v].data(), lvz[v].size() * 8, hipMemcpyHostToDevice));
-    }
-    h->seed = ids[0]; h->chain = (uint32_t)ids[1];  // the draws continue the interrupted chain's streams
+    HCHK(copy_segments(head, himg.data(), true, false, h->stream));
+    HCHK(copy_segments(body, img.data(), true, false, h->stream));
+    if ((rc = commit(h, st, true, true))) return rc;
+    h->chain = (uint32_t)st.chain64;  // (with the seed: the draws continue the interrupted chain's streams)
     h->poisoned = false;
     return NGP_OK;
     NGP_CATCH(h)
@@ -2955,48 +2897,13 @@ struct Rccl {
 } g_rccl;
 
 int import_posterior_device(ngp_handle *h, const double *o) {  // inverse of ngp_export_posterior_device
-    const size_t pb = (size_t)h->P * sizeof(double);
-    HCHK(hipMemcpyAsync(h->cm.d_sum_beta, o, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(h->cm.d_sum_beta2, o + h->P, pb, hipMemcpyDeviceToDevice, h->stream));
-    HCHK(hipMemcpyAsync(h->cm.d_sum_delta, o + 2 * h->P, pb, hipMemcpyDeviceToDevice, h->stream));
-    if (h->nvb) HCHK(hipMemcpyAsync(h->mm.d_sum_varBeta, o + 3 * h->P, (size_t)h->nvb * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    std::vector<double> tail(2 * h->sets.size() + (size_t)h->nclass_total + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size() +
-                             NGP_LV_SUM * h->mm.lv.size() + 3);
-    HCHK(hipMemcpyAsync(tail.data(), o + 3 * h->P + h->nvb, tail.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(hipStreamSynchronize(h->stream));
-    for (size_t si = 0; si < h->sets.size(); si++)
-        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, tail[2 * si], tail[2 * si + 1]);
-    {
-        size_t off = 2 * h->sets.size();
-        for (size_t si = 0; si < h->sets.size(); si++)
-            if (h->sets[si].K > 0) {
-                int rc2 = set_class_state_dev(h, (int)si, nullptr, tail.data() + off);
-                if (rc2) return rc2;
-                off += (size_t)h->sets[si].K;
-            }
-    }
-    const size_t tf = 2 * h->sets.size() + (size_t)h->nclass_total;
-    if (h->mm.nfixcol > 0) HCHK(hipMemcpy(h->mm.d_sum_bfix, tail.data() + tf, (size_t)h->mm.nfixcol * sizeof(double), hipMemcpyHostToDevice));
-    DScal sc;
-    HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
-    {
-        const size_t r_at = tf + (size_t)h->mm.nfixcol;
-        size_t off = r_at;
-        for (size_t r = 0; r < h->mm.rnd.size(); r++) {
-            HCHK(hipMemcpy(h->mm.rnd[r].d_sum_u, tail.data() + off, (size_t)h->mm.rnd[r].q * sizeof(double), hipMemcpyHostToDevice));
-            HCHK(hipMemcpy(h->mm.rnd[r].d_vu + 1, tail.data() + r_at + (size_t)h->mm.nrandcol + r, sizeof(double), hipMemcpyHostToDevice));
-            off += (size_t)h->mm.rnd[r].q;
-        }
-    }
-    size_t t0 = tf + (size_t)h->mm.nfixcol + (size_t)h->mm.nrandcol + h->mm.rnd.size();
-    for (auto &V : h->mm.lv) {
-        HCHK(hipMemcpy(V.d_st + NGP_LV_SUM, tail.data() + t0, NGP_LV_SUM * sizeof(double), hipMemcpyHostToDevice));
-        t0 += NGP_LV_SUM;
-    }
-    sc.sum_varE = tail[t0]; sc.sum_b = tail[t0 + 1]; sc.nKept = (long long)std::llround(tail[t0 + 2]);
-    HCHK(hipMemcpy(h->cm.d_scal, &sc, sizeof(DScal), hipMemcpyHostToDevice));
-    HCHK(hipStreamSynchronize(h->stream));
-    return NGP_OK;
+    ChainState st;
+    describe(h, st);
+    int rc;
+    if ((rc = stage(h, st))) return rc;
+    HCHK(copy_segments(place(st, posterior_layout), const_cast<double *>(o), false, false, h->stream));
+    st.sc.nKept = (long long)std::llround(st.nkept_f64);
+    return commit(h, st, false, true);
 }
 }  // namespace
 
@@ -3036,14 +2943,16 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
         if (!hs[i]) return fail(nullptr, NGP_ERR_ARG, "ngp_allreduce_posterior: null handle");
     ngp_handle *h = hs[0];  // errors are reported on the first handle
     int rc;
-    int64_t len = 0;
-    if ((rc = ngp_posterior_len(h, &len))) return rc;
+    if ((rc = enter(h))) return rc;
+    ChainState st0;
+    describe(h, st0);
+    const Plan pl0 = place(st0, posterior_layout);
+    const int64_t len = (int64_t)(pl0.bytes / 8);
     for (int i = 0; i < n; i++) {
         REQUIRE(hs[i]->pm, NGP_ERR_STATE, "ngp_allreduce_posterior: a handle has no panel");
-        REQUIRE(hs[i]->P == h->P && hs[i]->nvb == h->nvb && hs[i]->sets.size() == h->sets.size() && hs[i]->mm.nfixcol == h->mm.nfixcol &&
-                    hs[i]->nclass_total == h->nclass_total && hs[i]->mm.nrandcol == h->mm.nrandcol && hs[i]->mm.rnd.size() == h->mm.rnd.size() &&
-                    hs[i]->mm.lv.size() == h->mm.lv.size(),
-                NGP_ERR_ARG, "ngp_allreduce_posterior: the chains do not share one model");
+        ChainState sti;  // one model: the packed posteriors hold the same segments, each of the same length
+        describe(hs[i], sti);
+        REQUIRE(place(sti, posterior_layout).same_shape(pl0), NGP_ERR_ARG, "ngp_allreduce_posterior: the chains do not share one model");
         for (int k = 0; k < i; k++) REQUIRE(hs[k] != hs[i], NGP_ERR_ARG, "ngp_allreduce_posterior: a handle is listed twice");
     }
     struct Buffers {  // the packed sums of every handle, on its device: freed there, with that device current
@@ -3496,7 +3405,6 @@ int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("add_random_set: ") + hipGetErrorString(e));
     if (set_id) *set_id = (int32_t)h->mm.rnd.size();
     h->mm.rnd.push_back(std::move(R));
-    h->mm.nrandcol += q;
     return NGP_OK;
     NGP_CATCH(h)
 }
@@ -3574,10 +3482,7 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
  * src/samplers.jl:56-104, src/outFiles.jl:17-21: 10 MB of text per sample at P = 600,000).  From the next ngp_run on, every kept
  * iteration (ngp_set_schedule) leaves one record: packed on the device into a ring of four slots, copied to pinned host memory on a
  * second stream and written by a thread of the library's own; ngp_run returns when its last record is in the file.  path == NULL
- * closes the file.  File: "NGPSMP01" | int64 P, nvb, nsets, nfix, nclass, record bytes | per set int64 {method, K, col0, ncol,
- * variance entries, tuple k} | records: int64 iteration | varE | b | b_fixed[nfix] | beta[P] | varBeta[nvb] | piHat[2 nsets] | class
- * probabilities[nclass] | delta[P] as bytes, padded to 8.  nextgp.jl_amd/api.py (samples_to_out_files) turns it into the
- * reference's *Out text files. */
+ * closes the file.  The file: ngp_state.h.  nextgp.jl_amd/api.py (samples_to_out_files) turns it into the reference's *Out text files. */
 /* BayesLV marker set (include/nextgp_hip.h).  On the device the set is a BayesPR set with one variance per locus and NO region entry
  * (h_regs / segments): k_prep draws no region chi-square for it and k_regdraw never touches it; its variances come from launch_lv. */
 int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double varBeta0, const double *C, int64_t ld, int32_t ncov,

@@ -1051,9 +1051,10 @@ __global__ __launch_bounds__(256) void k_post(int do_accum, long long P, long lo
 
 // ------------------------------------------------------------------------------------------
 // One kept sample into a slot of the sample ring (ngp_set_sample_file: what the reference appends as text rows of b / varE / beta<set> /
-// delta<set> / pi<set> / var<set>Out at src/samplers.jl:56-104).  Record: int64 iteration (-1: invalid -- an earlier sweep of the
-// call gave up and this iteration will be run again) | varE | b | b_fixed[nfix] | beta[P] | varBeta[nvb] | piHat[2 nsets] |
-// class probabilities [nclass] | delta[P] as bytes.
+// delta<set> / pi<set> / var<set>Out at src/samplers.jl:56-104).  The record: ngp_state.h (iteration -1: invalid -- an earlier sweep
+// of the call gave up and this iteration will be run again).  This kernel writes the scalars, b_fixed, beta, varBeta, piHat, the class
+// probabilities and delta; nrand and (nclass - sum K) are the words it leaves free behind b_fixed and behind the class probabilities
+// for the random-effect and BayesLV sets, which the caller copies there (sample_enqueue).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sample_pack(unsigned char *__restrict__ rec, long long P, long long nvb, int nsets, long long nfix,
                                                      long long nrand, long long nclass, long long iter, const double *__restrict__ beta,

@@ -1,0 +1,152 @@
+// ngp_state.h -- what a chain holds, as named segments, and its three serialisations as ordered lists of segment ids.  Host only.
+//
+// A segment is a named run of bytes {id, instance, pointer, bytes}: an array on the device (or a part of one: d_vu holds varU and
+// its sum side by side, a half and the whole are different segments over the same array), a word of the handle on the host
+// (iteration, seed, fine-seam counters), or a word staged on the host because it lives inside a device struct (DSet, DScal:
+// ChainState::ds / sc; the owner of the handle reads them with one copy and writes them back through the setter kernels, whose
+// side effects -- logPi, logpic, the cleared counters, iVarE -- belong to the state).  describe() in ngp_api.hip lists the segments
+// of a handle; nothing is cached, the model grows with every ngp_add_* call.
+//
+// A layout is a list of groups of segment ids.  A group is written once per instance (marker set, BayesR set, random-effect set,
+// BayesLV set ...), its ids in the order given; a group of one id therefore means "every instance of it, in order".  place() turns
+// a layout into offsets and a total size, copy_segments() moves the segments to or from a contiguous image on the device or on
+// the host.  Sizes and offsets of the three formats are computed nowhere else.
+//
+// THE FORMATS (normative; little-endian, doubles unless said otherwise, no padding unless said otherwise)
+//
+//  Packed posterior (ngp_posterior_len, ngp_export_posterior_device, ngp_allreduce_posterior) -- posterior_layout:
+//    sum_beta[P] | sum_beta2[P] | sum_delta[P] | sum_varBeta[nvb] | sum_pi[2] per marker set | class sums[K] per BayesR set |
+//    fixed-effect sums (every column of every set) | sum_u[q] of every random-effect set, then sum_varU of every set |
+//    per BayesLV set sum_c[16], sum_varZeta | sum_varE | sum_b | nKept (as a double; rounded with llround on the way back)
+//
+//  Sample file (ngp_set_sample_file) -- record: sample_layout, padded to a multiple of 8 bytes:
+//    header  char[8] magic | int64 P, nvb, nsets, nfix, nclass, record bytes | per marker set int64 {method, K, col0, ncol, variance
+//            entries, tuple k}; magic "NGPSMP01": nothing more; "NGPSMP02" (random-effect sets): int64 nrand | int64 q per set;
+//            "NGPSMP03" (BayesLV sets): the random-effect part as in 02, also when empty, then int64 nlv | per set int64 marker set, ncov
+//    record  int64 iter (-1: a sweep of the call gave up, the record is not written) | varE | b | b_fixed[nfix] | u[q] of every
+//            random-effect set, then varU of every set | beta[P] | varBeta[nvb] | piHat[2] per marker set | class probabilities[K]
+//            per BayesR set | per BayesLV set c[16] (the first ncov used), varZeta | delta[P] (uint8)
+//
+//  Snapshot (ngp_save_snapshot / ngp_load_snapshot):
+//    char[8] "NGPSNAP2" | int64 N, P, nvb, nsets | snapshot_head_layout: int64 iter, nKept | uint64 seed, chain |
+//    model signature (ModelSig in ngp_api.hip): per marker set int64 {method, K + 16 tuple k + 256 (ncov + 32 est_mode) of a
+//      BayesLV set, nreg, col0, ncol} | int64 number of fixed-effect sets, bit 62: residual weights, bit 61: random-effect sets |
+//      with weights: uint64 digest of the weights | with random-effect sets: int64 nrand, per set int64 q, uint64 digest of its level
+//      coding and K | int64 ncol per fixed-effect set
+//    snapshot_body_layout: varE, b, sum_varE, sum_b | ycorr[N] (with residual weights the scaled residual as it lies on the
+//      device) | beta[P] | delta[P] (uint8, 0 / 1) | varBeta[nvb] | piHat[2] per set | sum_beta[P] | sum_beta2[P] | sum_delta[P] |
+//      sum_varBeta[nvb] | sum_pi[2] per set | uint64 fine_calls per set | int64 nfix | b_fixed[nfix] | sum_b_fixed[nfix] |
+//      per BayesR set piHat[K], sum_pi[K] | per random-effect set u[q], sum_u[q], varU, sum_varU, uint64 fine_calls |
+//      per BayesLV set the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums, ...), zeta[ncol]
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "ngp_common.h"
+
+namespace ngp {
+
+enum SegId : int {
+    // words of the handle (host)
+    SEG_ITER, SEG_SEED, SEG_CHAIN, SEG_NFIX, SEG_FINE, SEG_RFINE,
+    // words of DScal and DSet (staged on the host)
+    SEG_VARE, SEG_B, SEG_SUM_VARE, SEG_SUM_B, SEG_NKEPT, SEG_NKEPT_F64, SEG_PI, SEG_SUM_PI, SEG_CLS, SEG_SUM_CLS,
+    // device arrays: values ...
+    SEG_YCORR, SEG_BETA, SEG_DELTA, SEG_VARBETA, SEG_FIX, SEG_U, SEG_VARU, SEG_LV, SEG_ZETA,
+    // ... posterior sums ...
+    SEG_SUM_BETA, SEG_SUM_BETA2, SEG_SUM_DELTA, SEG_SUM_VARBETA, SEG_SUM_FIX, SEG_SUM_U, SEG_SUM_VARU, SEG_SUM_LV,
+    // ... and arrays that hold value and sum side by side, whole
+    SEG_VU, SEG_LV_ALL
+};
+
+struct Seg {
+    SegId id;
+    int inst;      // which marker set / random-effect set / BayesLV set (0 for what a chain has once)
+    void *p;
+    size_t bytes;
+    bool host;     // p is host memory
+};
+
+struct ChainState {
+    std::vector<Seg> segs;
+    // staging of the words that live inside device structs, and of words whose file form differs from the handle's
+    std::vector<DSet> ds;
+    DScal sc;
+    double nkept_f64 = 0.0;
+    int64_t nfix = 0;
+    uint64_t chain64 = 0;
+    ChainState() = default;
+    ChainState(const ChainState &) = delete;  // (the segments point into the staging members)
+    ChainState &operator=(const ChainState &) = delete;
+    void dev(SegId id, int inst, const void *p, size_t bytes) { segs.push_back({id, inst, const_cast<void *>(p), bytes, false}); }
+    void host(SegId id, int inst, void *p, size_t bytes) { segs.push_back({id, inst, p, bytes, true}); }
+};
+
+using Layout = std::vector<std::vector<SegId>>;
+
+inline const Layout posterior_layout = {{SEG_SUM_BETA}, {SEG_SUM_BETA2}, {SEG_SUM_DELTA}, {SEG_SUM_VARBETA}, {SEG_SUM_PI}, {SEG_SUM_CLS}, {SEG_SUM_FIX},
+                                        {SEG_SUM_U}, {SEG_SUM_VARU}, {SEG_SUM_LV}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_NKEPT_F64}};
+inline const Layout sample_layout = {{SEG_ITER}, {SEG_VARE}, {SEG_B}, {SEG_FIX}, {SEG_U}, {SEG_VARU}, {SEG_BETA}, {SEG_VARBETA}, {SEG_PI}, {SEG_CLS},
+                                     {SEG_LV}, {SEG_DELTA}};
+inline const Layout snapshot_head_layout = {{SEG_ITER}, {SEG_NKEPT}, {SEG_SEED}, {SEG_CHAIN}};
+inline const Layout snapshot_body_layout = {{SEG_VARE}, {SEG_B}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_YCORR}, {SEG_BETA}, {SEG_DELTA}, {SEG_VARBETA}, {SEG_PI},
+                                            {SEG_SUM_BETA}, {SEG_SUM_BETA2}, {SEG_SUM_DELTA}, {SEG_SUM_VARBETA}, {SEG_SUM_PI}, {SEG_FINE}, {SEG_NFIX}, {SEG_FIX},
+                                            {SEG_SUM_FIX}, {SEG_CLS, SEG_SUM_CLS}, {SEG_U, SEG_SUM_U, SEG_VU, SEG_RFINE}, {SEG_LV_ALL, SEG_ZETA}};
+
+// a layout applied to a chain: every segment with its byte offset, and the size of the whole
+struct Plan {
+    struct At { const Seg *s; size_t off; };
+    std::vector<At> at;
+    size_t bytes = 0;
+    const At *find(SegId id, int inst = 0) const {
+        for (auto &a : at) if (a.s->id == id && a.s->inst == inst) return &a;
+        return nullptr;
+    }
+    size_t off(SegId id) const { return find(id)->off; }           // (of a segment every chain has)
+    size_t size(SegId id) const { return find(id)->s->bytes; }
+    // the same segments of the same lengths in the same order: two chains of one model
+    bool same_shape(const Plan &o) const {
+        if (at.size() != o.at.size()) return false;
+        for (size_t i = 0; i < at.size(); i++)
+            if (at[i].s->id != o.at[i].s->id || at[i].s->bytes != o.at[i].s->bytes) return false;
+        return true;
+    }
+};
+
+// pad: the total is rounded up to a multiple of it
+inline Plan place(const ChainState &st, const Layout &L, size_t pad = 1) {
+    Plan pl;
+    for (auto &group : L)
+        for (auto &first : st.segs) {  // the instances of a group: those of its first id, in the order describe() lists them
+            if (first.id != group[0]) continue;
+            for (SegId id : group)
+                for (auto &s : st.segs)
+                    if (s.id == id && s.inst == first.inst) { pl.at.push_back({&s, pl.bytes}); pl.bytes += s.bytes; }
+        }
+    pl.bytes = (pl.bytes + pad - 1) / pad * pad;
+    return pl;
+}
+
+// gather (to_image) or scatter the segments of a plan to / from a contiguous image in device or host memory; returns once the
+// copies are through
+inline hipError_t copy_segments(const Plan &pl, void *image, bool image_host, bool to_image, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    for (auto &a : pl.at) {
+        if (a.s->bytes == 0) continue;
+        void *im = (unsigned char *)image + a.off;
+        void *dst = to_image ? im : a.s->p;
+        const void *src = to_image ? a.s->p : im;
+        const bool dst_host = to_image ? image_host : a.s->host, src_host = to_image ? a.s->host : image_host;
+        if (dst_host && src_host) { std::memcpy(dst, src, a.s->bytes); continue; }
+        const hipMemcpyKind kind = src_host ? hipMemcpyHostToDevice : (dst_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+        if ((e = hipMemcpyAsync(dst, src, a.s->bytes, kind, stream)) != hipSuccess) break;
+    }
+    const hipError_t es = hipStreamSynchronize(stream);
+    return e != hipSuccess ? e : es;
+}
+
+}  // namespace ngp

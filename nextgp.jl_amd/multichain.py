@@ -1,15 +1,19 @@
 """Independent chains, one per GPU/rank: packing and the single end-of-run reduction of posterior sums.
 
 The path shards across chains only: no collective inside the sweep; after the last
-iteration every rank holds a packed vector [sum_beta P | sum_beta2 P | sum_delta P | sum_varBeta nvb |
-sum_pi 2*nsets | BayesR class sums | fixed-effect sums | sum_varE | sum_b | nKept] (ngp_export_posterior_device) and ONE all-reduce(sum) over
-RCCL (backend "nccl" on ROCm; "gloo" in CPU tests) yields the pooled sums."""
+iteration every rank holds the packed vector of ngp_export_posterior_device (its layout: csrc/ngp_state.h) and ONE all-reduce(sum) over
+RCCL (backend "nccl" on ROCm; "gloo" in CPU tests) yields the pooled sums; the all-reduce works on the vector of any model.
+
+posterior_len, pack_posterior and unpack_means cover the models WITHOUT random-effect and BayesLV sets: [sum_beta P | sum_beta2 P |
+sum_delta P | sum_varBeta nvb | sum_pi 2*nsets | BayesR class sums | fixed-effect sums | sum_varE | sum_b | nKept].  A chain with such
+sets has their sums between the fixed-effect sums and sum_varE (Sampler.posterior_len() gives its length); these helpers neither count
+nor unpack those words."""
 import numpy as np
 
 
 def posterior_len(P, nvb, nsets, nclasses=0, nfix=0):
-    """nclasses = sum of K over the BayesR sets (their class-probability sums travel too); nfix = fixed-effect columns beyond
-    the intercept (all sets)."""
+    """Length of the packed vector of a model without random-effect and BayesLV sets (with them: Sampler.posterior_len()).  nclasses = sum
+    of K over the BayesR sets (their class-probability sums travel too); nfix = fixed-effect columns beyond the intercept (all sets)."""
     return 3 * P + nvb + 2 * nsets + nclasses + nfix + 3
 
 

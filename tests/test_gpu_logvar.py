@@ -281,6 +281,66 @@ def test_state_resume_snapshot_and_sample_file(ngp, O, tmp_path):
     _same(_everything(a), _everything(h))
 
 
+def test_snapshot_and_sample_file_of_a_model_with_every_component(ngp, O, tmp_path):
+    """Every component that travels in a snapshot and in a sample record at once: a Tuple set, BayesPR, BayesB, a BayesR set with four
+    classes, a BayesLV set with three covariates, a two-column fixed set, a diagonal random-effect set and one with a sparse K, residual
+    weights.  Snapshot after 5 of 12 iterations, loaded into a fresh handle, 7 more: everything equals the uninterrupted chain; the
+    sample file's last record is the chain's state."""
+    rng = np.random.default_rng(12)
+    N, v, off = 200, 0.01, 64
+    X, y, _, _ = make_problem(O, N, off + 400, seed=8)
+    w = rng.uniform(0.5, 2.0, N)
+    Z, lev6, lev5 = rng.normal(size=(N, 2)), rng.integers(0, 6, size=N), rng.integers(0, 5, size=N)
+    K5 = 2.0 * np.eye(5) - 0.5 * (np.eye(5, k=1) + np.eye(5, k=-1))
+    Cm = np.column_stack([np.ones(100), np.arange(100) % 2, rng.normal(size=100)])
+    vm = v * (0.6 * np.eye(2) + 0.4 * np.ones((2, 2)))
+
+    def mk():
+        s = ngp.Sampler(device=0, seed=13, chain=1)
+        s.set_residual_weights(w)
+        s.set_panel(X)
+        s.add_marker_set_tuple(0, 32, 2, 5.0, vm * 2.0, [(0, 15), (15, 32)], vm)
+        s.add_marker_set(off, 100, 0, 4.0, v * 0.5, [(0, 50), (50, 100)], [v, v])
+        s.add_marker_set(off + 100, 100, 1, 4.0, v * 0.5, [(j, j + 1) for j in range(100)], [v] * 100, pi0=0.1, estPi=True)
+        s.add_marker_set_r(off + 200, 100, 4.0, v * 0.5, v, [0.0, 0.01, 0.1, 1.0], [0.85, 0.10, 0.04, 0.01], estPi=True)
+        s.add_fixed_set(Z)
+        s.add_random_set(lev6, 6, varU0=0.5)
+        s.add_random_set(lev5, 5, K=K5, varU0=0.3)
+        s.add_marker_set_lv(off + 300, 100, v, Cm, 0.5, est_mode=1)
+        s.set_y(y); s.set_residual_prior(4.0, 0.5); s.set_schedule(12, 2, 2)
+        return s
+
+    def everything(s):
+        out = [s.get_state(), s.get_posterior_sums(), s.get_fixed(), s.get_random(0), s.get_random(1), s.get_class_state(3), s.lv_state(4)]
+        return {f"{i}.{k}": np.asarray(x) for i, d in enumerate(out) for k, x in d.items()}
+
+    a = mk()
+    a.set_sample_file(str(tmp_path / "s.ngpsmp"))
+    a.run(12)
+    a.set_sample_file(None)
+    b = mk()
+    b.run(5)
+    b.save_snapshot(str(tmp_path / "snap"))
+    c = mk()
+    c.load_snapshot(str(tmp_path / "snap"))
+    c.run(7)
+    ea, ec = everything(a), everything(c)
+    assert sorted(ea) == sorted(ec)
+    for k in ea:
+        assert np.array_equal(ea[k], ec[k]), k
+    assert open(tmp_path / "s.ngpsmp", "rb").read(8) == b"NGPSMP03"
+    S = ngp.read_sample_file(str(tmp_path / "s.ngpsmp"))
+    st, lv = a.get_state(), a.lv_state(4)
+    assert [int(i) for i in S["iter"]] == [4, 6, 8, 10, 12] and S["varE"][-1] == st["varE"] and S["b"][-1] == st["b"]
+    for k in ("beta", "varBeta", "piHat", "delta"):
+        assert np.array_equal(S[k][-1], st[k]), k
+    assert np.array_equal(S["b_fixed"][-1], a.get_fixed()["b"]) and np.array_equal(S["class_pi"][-1], a.get_class_state(3)["piHat"])
+    for r in (0, 1):
+        assert np.array_equal(S["u"][r][-1], a.get_random(r)["u"]) and S["varU"][-1, r] == a.get_random(r)["varU"]
+    assert np.array_equal(S["lv_c"][0][-1], lv["c"]) and S["lv_varZeta"][-1, 0] == lv["varZeta"]
+    assert a.posterior_len() == 3 * a.P + a.nvb + 2 * 5 + 4 + 2 + (6 + 5 + 2) + 17 + 3
+
+
 def test_posterior_len_and_pooled_sums(ngp, O):
     X, y, v, C, cov = _chain_problem(O)
     chains = [_full(ngp, X, y + 0.01 * c, v, C, cov, 5, c) for c in range(4)]

@@ -111,6 +111,49 @@ def test_runLMEM_end_to_end_matches_oracle(ngp, O, tmp_path):
         np.allclose(S["beta"][:, :P1].mean(axis=0), ngp.summaryMCMC("betaM1", outFolder=str(out))[0], rtol=0, atol=1e-15)
 
 
+def test_sample_file_readers_return_the_planted_fields(ngp, tmp_path):
+    """An "NGPSMP03" file written here with numpy -- two marker sets (one BayesR with K = 3), two fixed columns, two random-effect sets of
+    different q, one BayesLV set with ncov = 3, three records -- read back by read_sample_file and iter_sample_file, field by field.
+    Every word of a record holds its own index in the file, so a field that is cut one word off reads another number."""
+    P, nvb, nsets, nfix, K, rq, lv = 11, 4, 2, 2, 3, [3, 5], [(0, 3)]
+    sets = [[5, 0, 0, 6, 1, 0], [3, K, 6, 5, 3, 0]]
+    nd = 3 + nfix + sum(rq) + len(rq) + P + nvb + 2 * nsets + K + 17 * len(lv)
+    rec = nd * 8 + (P + 7) // 8 * 8
+    recs = []
+    for r in range(3):
+        d = 1000.0 * (r + 1) + np.arange(nd, dtype=np.float64)
+        b = d.tobytes()
+        b = np.int64(10 + 2 * r).tobytes() + b[8:]
+        delta = (np.arange(P) * (r + 1) % 4).astype(np.uint8)
+        recs.append((d, delta, b + delta.tobytes() + b"\xee" * (rec - nd * 8 - P)))
+    path = tmp_path / "planted.ngpsmp"
+    path.write_bytes(b"NGPSMP03" + np.array([P, nvb, nsets, nfix, K, rec], dtype=np.int64).tobytes() + np.array(sets, dtype=np.int64).tobytes() +
+                     np.array([len(rq)] + rq, dtype=np.int64).tobytes() + np.array([len(lv)] + [w for t in lv for w in t], dtype=np.int64).tobytes() +
+                     b"".join(x[2] for x in recs))
+    # the record, word by word: iter | varE | b | b_fixed | u of set 0, set 1 | varU x 2 | beta | varBeta | piHat | class_pi | c[16], varZeta
+    want = dict(varE=(1, 1), b=(2, 1), b_fixed=(3, 2), u0=(5, 3), u1=(8, 5), varU=(13, 2), beta=(15, P), varBeta=(26, nvb), piHat=(30, 4),
+                class_pi=(34, K), lv_c0=(37, 3), lv_varZeta=(53, 1))
+    assert want["lv_varZeta"][0] + 1 == nd
+
+    def check(S, d, delta, it):
+        assert S["iter"] == it and S["varE"] == d[1] and S["b"] == d[2]
+        for k in ("b_fixed", "varU", "beta", "varBeta", "piHat", "class_pi", "lv_varZeta"):
+            assert np.array_equal(S[k], d[want[k][0]:want[k][0] + want[k][1]]), k
+        assert len(S["u"]) == 2 and np.array_equal(S["u"][0], d[5:8]) and np.array_equal(S["u"][1], d[8:13])
+        assert len(S["lv_c"]) == 1 and np.array_equal(S["lv_c"][0], d[37:40])
+        assert S["delta"].dtype == np.uint8 and np.array_equal(S["delta"], delta)
+        assert [tuple(s.values()) for s in S["sets"]] == [tuple(s) for s in sets] and list(S["sets"][1]) == ["method", "K", "col0", "ncol", "nvb", "tk"]
+
+    A = ngp.read_sample_file(str(path))
+    assert A["beta"].shape == (3, P) and A["lv_varZeta"].shape == (3, 1) and A["u"][1].shape == (3, 5) and A["delta"].shape == (3, P)
+    rows = list(ngp._lib.iter_sample_file(str(path)))
+    assert len(rows) == 3
+    for r, (d, delta, _) in enumerate(recs):
+        check({k: ([u[r] for u in v] if k in ("u", "lv_c") else v if k == "sets" else v[r]) for k, v in A.items()}, d, delta, 10 + 2 * r)
+        check(rows[r], d, delta, 10 + 2 * r)
+        assert sorted(rows[r]) == sorted(A)
+
+
 @pytest.mark.gpu
 def test_runLMEM_bayesc_matches_oracle(ngp, O, tmp_path):
     """BayesC through the reference's interface (src/runTime.jl:64-77, src/mme.jl:362-373): one variance for the set, pi file."""
