@@ -413,6 +413,64 @@ int32_t ngp_get_lv_state(ngp_handle *h, int32_t set_id, double *c, double *sum_c
 int32_t ngp_set_lv_state(ngp_handle *h, int32_t set_id, const double *c, const double *sum_c, double varZeta, double sum_varZeta,
                          const double *zeta);
 
+/* ---- GBLUP: a SNP term with a Random("G", v) prior (src/prepMatVec.jl:122-126) ----
+ * The reference forms VanRaden's genomic relationship matrix G from the raw genotypes (makeG, src/misc.jl:145-160), inverts it and samples
+ * one breeding value per individual over the dense N x N precision K = inv(G) (sampleZ!, src/functions.jl:57-72, 92-97, 498-501).  Here:
+ * ngp_grm_begin / ngp_grm_columns_* / ngp_grm_end build G on the device, ngp_grm_invert turns it into K, ngp_add_random_set_dense makes a
+ * random-effect set of it.  The builder is independent of the genotype panel, of ngp_set_storage and of the model: it may be used on
+ * a fresh handle, and a handle has at most one matrix under construction.  All of it is fp64 (the inverse multiplies input rounding by the
+ * condition number of G); the matrix product runs on the matrix cores.
+ *
+ * ngp_grm_begin: method 1 or 2 (src/misc.jl:149-156); allocates the accumulator (N rounded up to 64, squared, doubles).
+ * ngp_grm_columns_*: ncol raw (uncentred) genotype columns, column-major with leading dimension ld >= N, host memory; staged in
+ * chunks of 256 MiB.  Per column, on the device: mean, p = mean / 2, centring, for method 2 the division by sqrt(2 p (1 - p)); then
+ * G += Xc Xc'.  _f32 and _u8 convert exactly to fp64 first: on equal values the three give the same bits.  The result does not depend on
+ * how the columns are split into calls as long as every call but the last brings a multiple of 64 columns: every entry of G is one
+ * chain of matrix-core accumulations over the columns in their order, and the sum of 2 p q (method 1) is added up in column order.
+ * Refused with NGP_ERR_ARG (G unchanged by that call's failing chunk, the builder still open): a non-finite genotype; under method 2 a
+ * column with 2 p (1 - p) = 0 (monomorphic), which the reference divides 0 by 0 and poisons G with -- the message names the column.
+ * Method 1 takes monomorphic columns as the zero columns they become.
+ * ngp_grm_end: divides by sum 2 p q (method 1) or by the number of columns (method 2), adds 0.001 to the diagonal (src/misc.jl:158) and
+ * mirrors the computed triangle: G is exactly symmetric.  A sum of 2 p q that is not positive (method 1, every column monomorphic) is
+ * NGP_ERR_ARG and drops the matrix.
+ * ngp_grm_get: the N x N matrix to the host (G after ngp_grm_end, K after ngp_grm_invert).
+ * ngp_grm_invert: Cholesky factorisation and inverse in place (rocSOLVER dpotrf / dpotri, loaded on first use: NGP_ERR_HIP with a clear
+ * message if it is absent; no host fallback), then the computed triangle is mirrored: K is exactly symmetric.  A matrix that is not
+ * positive definite is NGP_ERR_ARG with the failing pivot (the matrix is dropped); before ngp_grm_end: NGP_ERR_STATE. */
+int32_t ngp_grm_begin(ngp_handle *h, int64_t N, int32_t method);
+int32_t ngp_grm_columns_f64(ngp_handle *h, const double *M, int64_t ncol, int64_t ld);
+int32_t ngp_grm_columns_f32(ngp_handle *h, const float *M, int64_t ncol, int64_t ld);
+int32_t ngp_grm_columns_u8(ngp_handle *h, const uint8_t *M, int64_t ncol, int64_t ld);
+int32_t ngp_grm_end(ngp_handle *h);
+int32_t ngp_grm_get(ngp_handle *h, double *G_out);
+int32_t ngp_grm_invert(ngp_handle *h);
+/* A random-effect set whose K is a dense q x q matrix: GBLUP's inv(G), or Random(Sigma, v) with a large dense Sigma.  Everything
+ * ngp_add_random_set says about levels, df, scale, varU0, the sampling order, the draw keys, weighted residuals, ngp_get_random /
+ * ngp_set_random / ngp_sample_random_set, the packed posterior, sample files and snapshots holds here too (a dense set and a CSR set with
+ * the same id consume the same random numbers); what differs is the engine of the Gauss-Seidel: blocks of 64 levels, one launch per
+ * block over all compute units, K read once per iteration (8 q^2 bytes), u'Ku formed without a second pass ("Dense
+ * random-effect sets and the GRM": the normative summation orders).  A dense array given to ngp_add_random_set keeps going to the CSR
+ * engine.  level == NULL: the identity incidence of GBLUP (record i is level i; q must equal N).  K comes from ONE of
+ *   K != NULL                   a host array of q x q doubles, exactly symmetric and finite (else NGP_ERR_ARG), copied to the device;
+ *   K == NULL, k_src != NULL    the dense K of set k_src_set of ANOTHER handle on the same device, by reference: no copy is made, the
+ *                               matrix is read-only and lives as long as any set refers to it (chains = 8 is one matrix, not eight);
+ *   K == NULL, k_src == NULL    this handle's own inverted relationship matrix (ngp_grm_invert), without a copy: the set takes it
+ *                               over, the builder is empty afterwards.
+ * k_src must be a complete handle (panel or records set) that no other thread is setting up during this call.
+ * A diagonal entry of K that is not > 0 is NGP_ERR_ARG.  The model signature of snapshots digests the level coding and every entry
+ * of K, as for a CSR set; the matrix is hashed on the device (it may never have been in host memory), once, and sets that share it
+ * share the word. */
+int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q, const double *K, ngp_handle *k_src, int32_t k_src_set,
+                                 double df, double scale, double varU0, int32_t *set_id);
+/* A handle with N records and NO genotype panel -- the canonical GBLUP model y ~ 1 + SNP(M1) with VCV M1 = Random("G", v) has no
+ * marker set.  Takes the place of the panel call in the call sequence (a new model, like every ngp_set_panel_*; residual weights
+ * before it).  On such a handle ngp_set_y, the residual prior, fixed-effect sets, random-effect sets of both engines, ngp_run,
+ * ngp_run_many (side by side), sample files, snapshots, ngp_share_panel and the packed posterior work; ngp_add_marker_set*, ngp_sweep_set*
+ * and ngp_profile_iteration are refused (NGP_ERR_STATE), and ngp_run requires a random-effect set.  Internally the handle carries ONE
+ * inert block of 64 zero columns in place of the panel: state and file formats are those of a model with P = 64 and no marker set
+ * (beta and its sums 64 zeros, delta 64 ones, no variance component), nothing is ever swept. */
+int32_t ngp_set_records(ngp_handle *h, int64_t N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,8 @@ SYMBOLS = [
     "ngp_set_chain_form", "ngp_get_chain_form", "ngp_get_setup_timing", "ngp_set_residual_weights", "ngp_get_residual_weights",
     "ngp_add_random_set", "ngp_get_random", "ngp_set_random", "ngp_sample_random_set",
     "ngp_add_marker_set_lv", "ngp_get_lv_state", "ngp_set_lv_state",
+    "ngp_grm_begin", "ngp_grm_columns_f64", "ngp_grm_columns_f32", "ngp_grm_columns_u8", "ngp_grm_end", "ngp_grm_get", "ngp_grm_invert",
+    "ngp_add_random_set_dense", "ngp_set_records",
 ]
 
 _lib = None
@@ -439,6 +441,62 @@ class Sampler:
                                             C.c_double(df), C.c_double(scale), C.c_double(varU0), C.byref(sid)))
         self.rand_q = getattr(self, "rand_q", []) + [int(q)]
         return sid.value
+
+    def add_random_set_dense(self, level, q, K=None, df=4.0, scale=None, varU0=100.0):
+        """Random-effect set over a dense q x q precision (GBLUP's inv(G), or a large dense inv(Sigma)), sampled by the blocked engine.
+        level: the record's level, or None for the identity incidence (record i is level i, q == N).  K: a dense symmetric array
+        (copied to the device), (other_sampler, set_id) to share that set's matrix by reference, or None to take over this sampler's own
+        inverted relationship matrix (grm_invert).  Everything else as add_random_set; returns the set id."""
+        lv = None if level is None else np.ascontiguousarray(level, dtype=np.int32)
+        if scale is None:
+            scale = varU0 * (df - 2.0) / df
+        Kh, src, src_set = None, None, 0
+        if isinstance(K, tuple):
+            src, src_set = K[0].h, int(K[1])
+        elif K is not None:
+            Kh = np.ascontiguousarray(K, dtype=np.float64)
+            if Kh.shape != (int(q), int(q)):
+                raise ValueError("K: a q x q matrix, (other_sampler, set_id) or None")
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_random_set_dense(self.h, _p(lv, C.c_int32), C.c_int64(int(q)), _p(Kh, C.c_double), src, C.c_int32(src_set),
+                                                  C.c_double(df), C.c_double(scale), C.c_double(varU0), C.byref(sid)))
+        self.rand_q = getattr(self, "rand_q", []) + [int(q)]
+        return sid.value
+
+    # ---- GBLUP: relationship matrix on the device ------------------------------------------
+    def set_records(self, N):
+        """N records and no genotype panel (a model without marker sets); in place of set_panel."""
+        self._chk(self.L.ngp_set_records(self.h, C.c_int64(int(N))))
+        self.N, self.P = int(N), 64  # (one inert block of zero columns stands in for the panel: include/nextgp_hip.h)
+
+    def grm_begin(self, N, method=1):
+        self._chk(self.L.ngp_grm_begin(self.h, C.c_int64(int(N)), C.c_int32(int(method))))
+        self.grm_N = int(N)
+
+    def grm_columns(self, M):
+        """Raw (uncentred) genotype columns, N x ncol: uint8 and float32 are sent as they are, anything else as float64.  The first N
+        rows of a taller Fortran-ordered array (M = big[:N]) go over without a copy, with the parent's leading dimension."""
+        M = np.asarray(M)
+        t = {np.dtype(np.uint8): C.c_uint8, np.dtype(np.float32): C.c_float}.get(M.dtype, C.c_double)
+        if t is C.c_double and M.dtype != np.float64:
+            M = np.asfortranarray(M, dtype=np.float64)
+        if M.ndim != 2 or M.shape[0] != self.grm_N:
+            raise ValueError("grm_columns: an N x ncol matrix")
+        if not (M.strides[0] == M.itemsize and M.strides[1] % M.itemsize == 0 and M.strides[1] >= M.shape[0] * M.itemsize):
+            M = np.asfortranarray(M)
+        f = {C.c_uint8: self.L.ngp_grm_columns_u8, C.c_float: self.L.ngp_grm_columns_f32, C.c_double: self.L.ngp_grm_columns_f64}[t]
+        self._chk(f(self.h, _p(M, t), C.c_int64(M.shape[1]), C.c_int64(max(M.strides[1] // M.itemsize, M.shape[0]))))
+
+    def grm_end(self):
+        self._chk(self.L.ngp_grm_end(self.h))
+
+    def grm_get(self):
+        out = np.empty((self.grm_N, self.grm_N))
+        self._chk(self.L.ngp_grm_get(self.h, _p(out, C.c_double)))
+        return out  # (symmetric: row- and column-major are the same matrix)
+
+    def grm_invert(self):
+        self._chk(self.L.ngp_grm_invert(self.h))
 
     def get_random(self, set_id):
         q = self.rand_q[set_id]

@@ -26,7 +26,7 @@ import numpy as np
 
 from ._lib import LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["BayesPR", "BayesB", "BayesC", "BayesR", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
+__all__ = ["makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -171,10 +171,11 @@ class ParsedFormula(tuple):
     everything itself (no state is left on the function: two models parsed in turn, or from threads, cannot pick up each other's
     covariates)."""
 
-    def __new__(cls, lhs, intercept, snps, covariates, random=()):
+    def __new__(cls, lhs, intercept, snps, covariates, random=(), order=()):
         t = super().__new__(cls, (lhs, intercept, snps))
         t.covariates = list(covariates)
         t.random = list(random)  # grouping columns of the (1|g) terms, in formula order
+        t.order = list(order)    # ("1|", g) and ("snp", name) in formula order: where a GBLUP term stands among the (1|g) terms
         return t
 
 
@@ -198,7 +199,7 @@ def parse_formula(formula, random_effects=False):
             cur += ch
     if cur.strip():
         terms.append(cur.strip())
-    intercept, snps, covs, rnd = False, [], [], []
+    intercept, snps, covs, rnd, order = False, [], [], [], []
     for t in terms:
         m = re.fullmatch(r"\(?\s*1\s*\|\s*([A-Za-z_][A-Za-z_0-9]*)\s*\)?", t)
         if m and t.count("(") == t.count(")"):
@@ -207,6 +208,7 @@ def parse_formula(formula, random_effects=False):
                                           "reference's Julia path (src/functions.jl:57-110); runLMEM and parse_formula(formula, "
                                           "random_effects=True) take them to the device")
             rnd.append(m.group(1))  # (1|g): a random effect of the levels of column g (src/prepMatVec.jl:136-153)
+            order.append(("1|", m.group(1)))
             continue
         if t == "1":
             intercept = True
@@ -218,6 +220,7 @@ def parse_formula(formula, random_effects=False):
                 raise ValueError(f"SNP term needs a name and a path: {t}")
             unq = [a.strip("\"'") for a in args]
             snps.append(GenomicTerm(unq[0], unq[1], unq[2] if len(unq) > 2 else ""))
+            order.append(("snp", unq[0]))
         elif t.startswith("PED("):
             raise NotImplementedError(f"term '{t}': building A^-1 from a pedigree needs PedigreeBase (src/mme.jl:26-37, src/prepMatVec.jl:136-153), "
                                       "so PED terms stay on the reference's Julia path; its coarse seam hands the Ainv it built to the device")
@@ -229,7 +232,7 @@ def parse_formula(formula, random_effects=False):
         else:
             raise NotImplementedError(f"term '{t}': interactions / function terms stay on the reference's Julia path (StatsModels, "
                                       "src/prepMatVec.jl:150-165); use the fine seam (ngp_sweep_set) to combine them with the GPU sweep")
-    return ParsedFormula(lhs, intercept, snps, covs, rnd)
+    return ParsedFormula(lhs, intercept, snps, covs, rnd, order)
 
 
 def random_levels(col):
@@ -264,6 +267,63 @@ def random_prior(VCV, g, q):
     df = 3.0 + 1.0                                               # src/mme.jl:261
     v = float(prior.v)
     return K, df, v * (df - 2.0) / df, v                         # src/mme.jl:265-272
+
+
+def gblup_terms(snps, VCV, summaryStat=None):
+    """Names of the SNP terms that are GBLUP: a Random("G", v; type = 1|2) prior under the term's name (src/prepMatVec.jl:122-126).
+    What the reference would handle elsewhere and this path does not is refused here, before any device is touched."""
+    summaryStat = summaryStat or {}
+    out = []
+    for t in snps:
+        prior = VCV.get(t.name)
+        in_tuple = [key for key in VCV if isinstance(key, tuple) and t.name in key]
+        if not isinstance(prior, RandomEffectType):
+            continue
+        if not (isinstance(prior.str, str) and prior.str == "G"):
+            raise NotImplementedError(f"prior of {t.name}: a Random prior under a SNP term's name means GBLUP and needs the structure \"G\" "
+                                      "(src/prepMatVec.jl:122-126)")
+        if prior.type not in (1, 2):
+            raise ValueError("enter a valid method")                  # src/misc.jl:156
+        if in_tuple:
+            raise NotImplementedError(f"VCV key {in_tuple[0]} holds the GBLUP term {t.name}: correlated (Tuple) random effects stay on the "
+                                      "reference's Julia path (sampleZ!(::Tuple), src/functions.jl:75-89, 100-110)")
+        if t.map:
+            raise NotImplementedError(f"map file on the GBLUP term {t.name}: the reference stores it with the Z set and never reads it "
+                                      "(src/prepMatVec.jl:126); regions belong to marker priors (src/misc.jl:163-215)")
+        if t.name in summaryStat:
+            raise NotImplementedError(f"summaryStat for the GBLUP term {t.name}: summary statistics enter marker sets and fixed effects only "
+                                      "(src/mme.jl:140-147, 314-322)")
+        out.append(t.name)
+    return out
+
+
+GRM_COLUMNS_PER_CALL = 4096  # columns handed to the GRM builder per call (a multiple of 64: the result does not depend on the split)
+
+
+def _grm_build(smp, M, method):
+    """G of the raw genotypes M (N x P, any dtype read_genotypes returns) on smp's device, in column ranges: no concatenated host copy."""
+    N, P = M.shape
+    smp.grm_begin(N, method)
+    for c0 in range(0, P, GRM_COLUMNS_PER_CALL):
+        smp.grm_columns(M[:, c0:c0 + GRM_COLUMNS_PER_CALL])
+    smp.grm_end()
+
+
+def makeG(M, method=1, device=0):
+    """VanRaden's genomic relationship matrix (src/misc.jl:145-160), built on the device in fp64 (matrix cores), returned as numpy.
+    M: raw allele counts, N x P (uint8, float32 and float64 give the same bits on equal values).  Unlike the reference, M is not centred
+    in place, and method 2 refuses a monomorphic column instead of filling G with NaN."""
+    if method not in (1, 2):
+        raise ValueError("enter a valid method")
+    M = np.asarray(M)
+    if M.ndim != 2:
+        raise ValueError("makeG: an N x P genotype matrix")
+    smp = Sampler(device=device)
+    try:
+        _grm_build(smp, M, method)
+        return smp.grm_get()
+    finally:
+        smp.close()
 
 
 def design_columns(name, col):
@@ -409,6 +469,13 @@ def random_file_names(g):
     return f"u1 | {g}", f"varU1 | {g}", f"1{g}"
 
 
+def _rd_files(rd):
+    """(u file, varU file, varU header) of a random-effect set: a (1|g) term, or a GBLUP term, whose key is the Symbol of its SNP term:
+    u<name> with the header Ind1 .. IndN and varU<name> headed <name> (src/mme.jl:549-552; the reference sizes the Ind names by the
+    number of MARKERS, src/prepMatVec.jl:126 -- a slip, not copied: one name per individual)."""
+    return rd["files"] if "files" in rd else random_file_names(rd["g"])
+
+
 def _var_names(s):
     """Header of var<set>Out: reg_r (src/mme.jl:593-595); for correlated sets one column per entry of the region's k x k matrix."""
     if s["k"] > 1:
@@ -448,7 +515,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
             row("b", (_fmt(S["b"]) if intercept else []) + (_fmt(S["b_fixed"]) if has_fixed else []))
             row("varE", _fmt(S["varE"]))
             for r, rd in enumerate(randoms):                 # src/samplers.jl:60-75
-                un, vn, _ = random_file_names(rd["g"])
+                un, vn, _ = _rd_files(rd)
                 row(un, _fmt(S["u"][r]))
                 row(vn, _fmt(S["varU"][r]))
             vb_off, cls_off = 0, 0
@@ -512,11 +579,18 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         for fn in os.listdir(outFolder):
             os.remove(os.path.join(outFolder, fn))
     os.makedirs(outFolder, exist_ok=True)
-    # prep: SNP branch (src/prepMatVec.jl:113-134); marker sets become consecutive column ranges of ONE panel
-    mats = [read_genotypes(t.path) for t in snps]
-    for M in mats:
+    # prep: SNP branch (src/prepMatVec.jl:113-134); marker sets become consecutive column ranges of ONE panel.  A term whose prior is
+    # Random("G", v) is GBLUP (:122-126): its genotypes go to the GRM builder, never into the panel
+    gb_names = gblup_terms(snps, VCV, summaryStat)
+    mats_all = [read_genotypes(t.path) for t in snps]
+    for M in mats_all:
         if M.shape[0] != len(y):
             raise ValueError("genotype rows must match the phenotype records (marker files are ordered as the data, runTime.jl:23)")
+    gblup = {t.name: dict(M=M, prior=VCV[t.name]) for t, M in zip(snps, mats_all) if t.name in gb_names}
+    mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
+    snps = [t for t in snps if t.name not in gb_names]
+    if not snps:
+        storage = None   # (storage concerns panels only: a model without marker sets has none)
     if storage in ("u8", 1):  # codes stay codes: integer-valued float input is converted, anything else refused
         conv = []
         for M in mats:
@@ -526,7 +600,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
                 M = np.asfortranarray(M.astype(np.uint8))
             conv.append(M)
         mats = conv
-    if not all(M.dtype == np.uint8 for M in mats):  # one byte per genotype only when every set comes that way
+    if mats and not all(M.dtype == np.uint8 for M in mats):  # one byte per genotype only when every set comes that way
         mats = [np.asarray(M, dtype=np.float64) for M in mats]
     # Correlated marker sets: a VCV key that is a TUPLE of set names (src/mme.jl:448-489) joins those sets into one unit whose loci
     # draw their k effects together (src/functions.jl:140-154).  On the device the k columns of a locus sit side by side, from a
@@ -581,7 +655,9 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         # (compact storage: the fused kernel serves two or three chains; more run side by side on disjoint CU shares)
         smp.set_max_shards(smp.shards_for_pass(K) if (storage is None or K <= 3) else smp.shards_for_chains(K))
     kinds = {np.asarray(pc).dtype == np.uint8 for pc in pieces if pc.shape[1]}
-    if (storage is None and kinds == {False}) or kinds == {True}:
+    if not snps:   # GBLUP terms only: records, no genotype panel (ngp_set_records)
+        smp.set_records(len(y))
+    elif (storage is None and kinds == {False}) or kinds == {True}:
         # the sets go to the device one after another (ngp_begin_panel / ngp_panel_columns_* / ngp_end_panel): no concatenated host copy
         smp.begin_panel(len(y), ncols)
         c0 = 0
@@ -604,7 +680,8 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
             region_cache[name] = _regions_for(prior, P, map_path, outFolder, name)
         return region_cache[name]
 
-    built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin)
+    built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
+                          gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0])
              for sc in samplers]
     sets, fixed_names = built[0]
     randoms = samplers[0].randoms
@@ -632,8 +709,10 @@ def _residual_weights(e_prior, N):
     return 1.0 / d
 
 
-def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin):
-    """Priors, fixed-effect sets, marker sets, y and the schedule of ONE chain's handle (its panel is set); returns (sets, fixed_names)."""
+def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
+                 gblup=None, k_owner=None):
+    """Priors, fixed-effect sets, random-effect sets, marker sets, y and the schedule of ONE chain's handle (its panel is set); returns
+    (sets, fixed_names).  gblup: {term name: dict(M, prior)} of the GBLUP terms; k_owner: the chain whose dense K this one shares."""
     # residual prior (src/mme.jl:63-94)
     e_prior = VCV.get("e", Random("I", 100.0))  # (a "D" structure's weights were set on the handle before its panel: runLMEM)
     e_df = 4.0
@@ -666,8 +745,26 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
             smp.add_fixed_set(Xc)
         fixed_names += names
     # (1|g) random-effect sets, after the fixed effects, in formula order (src/samplers.jl:43-46; set-up src/mme.jl:165-272)
+    # A GBLUP term is a random-effect set too (Z = I over K = inv(G), src/prepMatVec.jl:122-126) and takes its place among them in
+    # formula order (the reference walks keys(Z) of a Dict, whose order is not defined: the documented difference of the fixed-effect sets)
     smp.randoms = []
-    for g in parsed.random:
+    gblup = gblup or {}
+    for kind, g in (parsed.order or [("1|", g) for g in parsed.random]):
+        if kind == "snp":
+            if g not in gblup:
+                continue
+            prior, N = gblup[g]["prior"], len(y)
+            rdf = 3.0 + 1.0                                          # src/mme.jl:261
+            v = float(prior.v)
+            if k_owner is None:   # G on the matrix cores, inverted on the device, handed to the set without a copy
+                _grm_build(smp, gblup[g]["M"], prior.type)
+                smp.grm_invert()
+                Ksrc = None
+            else:                 # the other chains read the first chain's matrix
+                Ksrc = (k_owner, [rd["id"] for rd in k_owner.randoms if rd.get("key") == g][0])
+            rid = smp.add_random_set_dense(None, N, K=Ksrc, df=rdf, scale=v * (rdf - 2.0) / rdf, varU0=v)   # src/mme.jl:265-272
+            smp.randoms.append(dict(id=rid, g=g, key=g, levels=[f"Ind{i + 1}" for i in range(N)], q=N, files=(f"u{g}", f"varU{g}", g)))
+            continue
         level, names = random_levels(userData[g])
         K, rdf, rscale, v = random_prior(VCV, g, len(names))
         rid = smp.add_random_set(level, len(names), K=K, df=rdf, scale=rscale, varU0=v)
@@ -748,9 +845,9 @@ def _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, n
         samplers[0].get_timing()
         Sampler.run_many(samplers, nChain)  # ONE fused sweep launch per iteration for all chains where the engine serves it
         fused = samplers[0].get_timing()["sweep_launches"] == nChain
-        if not fused:  # (the layout was chosen for a fused launch: side by side each chain's grid takes most of the device, so they take turns)
+        if not fused and sets:  # (a model without marker sets sweeps nothing; the layout was chosen for a fused launch: side by side each chain's grid takes most of the device, so they take turns)
             import warnings
-            warnings.warn(f"runLMEM(chains={K}): this layout / engine is not served by the fused sweep kernel (fp32 tiles: shards of at most "
+            warnings.warn(f"runLMEM(chains={len(samplers)}): this layout / engine is not served by the fused sweep kernel (fp32 tiles: shards of at most "
                           "64 rows with lag 6 or 8, or two chains on 64-224-row shards with lag 4-6; compact storage: two or three chains); the chains "
                           "ran one launch each per iteration. Results are the same; pass max_shards=Sampler.shards_for_chains(K) for side-by-side runs.")
         results = []
@@ -776,7 +873,7 @@ def _write_headers(outFolder, sets, fixed_names, randoms=()):
     _out(outFolder, "b", fixed_names)
     _out(outFolder, "varE", ["e"])
     for rd in randoms:   # src/mme.jl:548-556; the u header lists the levels in the order of u (random_levels)
-        un, vn, vh = random_file_names(rd["g"])
+        un, vn, vh = _rd_files(rd)
         _out(outFolder, un, rd["levels"])
         _out(outFolder, vn, [vh])
     for s in sets:
@@ -808,7 +905,7 @@ def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin,
             _out(outFolder, "b", (_fmt(st["b"]) if intercept else []) + (_fmt(smp.get_fixed()["b"]) if len(fixed_names) > int(intercept) else []))
             _out(outFolder, "varE", _fmt(st["varE"]))
             for rd in randoms:
-                un, vn, _ = random_file_names(rd["g"])
+                un, vn, _ = _rd_files(rd)
                 rr = smp.get_random(rd["id"])
                 _out(outFolder, un, _fmt(rr["u"]))
                 _out(outFolder, vn, _fmt(rr["varU"]))
@@ -859,7 +956,7 @@ def _posterior_means(smp, sets, fixed_names, intercept, randoms=()):
     res["random"] = {}
     for rd in randoms:   # posterior means of u (levels in random_levels order) and varU, keyed as Julia prints the term
         rr = smp.get_random(rd["id"])
-        res["random"][f"1 | {rd['g']}"] = dict(u=rr["sum_u"] / n, varU=rr["sum_varU"] / n, levels=rd["levels"])
+        res["random"][rd.get("key", f"1 | {rd['g']}")] = dict(u=rr["sum_u"] / n, varU=rr["sum_varU"] / n, levels=rd["levels"])
     res["sampler"] = smp
     return res
 

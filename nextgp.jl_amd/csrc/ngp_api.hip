@@ -24,6 +24,7 @@
 #include "../../include/nextgp_hip.h"
 #include "ngp_kernels.h"
 #include "ngp_random.h"
+#include "ngp_dense.h"
 #include "ngp_logvar.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
@@ -77,6 +78,23 @@ struct HFix {  // one fixed-effect set beyond the intercept
     DevArray<double> d_X, d_xpx0, d_xpxR, d_lhs0, d_rhs0;
 };
 
+// A dense q x q precision on the device (ngp_add_random_set_dense): row l at K + l ld.  Read-only once a set uses it; sets of several
+// handles (chains) may hold the same matrix, which lives as long as any of them.
+struct DenseK {
+    DevArray<double> K;
+    int64_t q = 0, ld = 0;
+    uint64_t digest = 0;  // of all q x q entries (dense_digest, once, when a set first takes the matrix): the model signature of snapshots
+};
+
+// The genomic relationship matrix under construction (ngp_grm_begin .. ngp_grm_invert): column-major with leading dimension ld = N
+// rounded up to 64, rows and columns beyond N zero.  state: 1 columns may arrive, 2 G complete (ngp_grm_end), 3 inverted.
+struct Grm {
+    std::shared_ptr<DenseK> m;
+    int state = 0, method = 1;
+    int64_t N = 0, ncols = 0;
+    double sum2pq = 0.0;  // method 1: sum of 2 p q over the columns so far, in column order
+};
+
 struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled after the fixed-effect sets (src/samplers.jl:43-46)
     int64_t q = 0;
     double df = 0.0, scale = 0.0, varU0 = 0.0;
@@ -89,6 +107,7 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     DevArray<double> d_vu;     // [varU, sum_varU]
     DevArray<double> d_scr;    // NGP_RS_ROWS x q scratch (ngp_random.h)
     uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
+    std::shared_ptr<DenseK> dk;  // a dense K (ngp_add_random_set_dense): the blocked engine of ngp_dense.h instead of k_rand_gs / k_rand_var
 };
 
 struct HLv {  // the variance model of one BayesLV marker set (src/mme.jl:418-439; kernels and state layout in ngp_logvar.h)
@@ -431,6 +450,8 @@ struct ngp_handle {
     ChainMem cm;
     ModelMem mm;
     HandleMem hm;
+    bool records_only = false;  // ngp_set_records: N records and no genotype panel (one inert block of 64 zero columns stands in for it)
+    Grm grm;                    // ngp_grm_*: independent of the panel and of the model
     bool panel_open = false;  // between ngp_begin_panel and ngp_end_panel: columns may still arrive, the Gram window does not exist yet
     int cu_count = 256;
     double setup_ms[3] = {0.0, 0.0, 0.0};   // wall time of the last panel set-up: device allocation (+ zeroing) | tiles (generation / upload) | Gram window
@@ -591,7 +612,7 @@ void drop_panel(ngp_handle *h) {
     h->h_setof.clear(); h->h_loc.clear(); h->h_vbidx.clear();
     h->h_regs.clear(); h->h_seg_k0.clear(); h->h_seg_len.clear(); h->h_seg_set.clear();
     h->h_tregs.clear(); h->h_tseg_l0.clear(); h->h_tseg_len.clear(); h->h_tseg_set.clear();
-    h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false;
+    h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false; h->records_only = false;
 }
 
 // A new panel of N x P (owner: ngp_share_panel's, whose arrays and plan are taken as they are).  The old panel goes first, so that
@@ -1094,6 +1115,26 @@ void launch_tinv(ngp_handle *h) {  // (sync_linear_blocks has run for this call'
 void launch_random(ngp_handle *h, int r, uint64_t it) {
     HRand &R = h->mm.rnd[(size_t)r];
     const long long q = (long long)R.q;
+    if (R.dk) {  // dense K: the blocked engine (ngp_dense.h), one launch per block of 64 levels between the level terms and the ycorr update
+        const double *K = R.dk->K;
+        const long long ld = (long long)R.dk->ld;
+        const unsigned *ab = (const unsigned *)h->cm.d_abort;
+        hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, (const double *)h->cm.d_rs, q,
+                           (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag,
+                           (const long long *)nullptr, (const int *)nullptr, (const double *)nullptr, R.d_u, (const double *)R.d_vu, R.d_scr, 1,
+                           (const DScal *)h->cm.d_scal, r, h->seed, (uint64_t)h->chain, it, ab);
+        hipLaunchKernelGGL(k_dense_dhi, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, K, ld, q, (const double *)R.d_u, R.d_scr, ab);
+        for (long long t = 0; t * 64 < q; t++) {
+            const long long below = q - 64 * t - 64;
+            const unsigned nwg = below > 0 ? (unsigned)((below + NGP_DENSE_WG_ROWS - 1) / NGP_DENSE_WG_ROWS) : 1u;
+            hipLaunchKernelGGL(k_dense_block, dim3(nwg), dim3(256), 0, h->stream, K, ld, q, (int)t, R.d_u, (const double *)R.d_vu, R.d_scr, ab);
+        }
+        hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr, (const double *)h->cm.d_rs, (long long)h->N,
+                           (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), ab);
+        hipLaunchKernelGGL(k_dense_var, dim3(1), dim3(1024), 0, h->stream, q, (const double *)R.d_kdiag, (const double *)R.d_u, (const double *)R.d_scr, R.d_vu,
+                           R.df, R.scale, r, h->seed, (uint64_t)h->chain, it, ab);
+        return;
+    }
     hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, (const double *)h->cm.d_rs, q,
                        (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag,
                        (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr,
@@ -1122,6 +1163,7 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     for (size_t r = 0; r < h->mm.rnd.size(); r++)  // the random-effect sets, in the order they were added (src/samplers.jl:43-46)
         launch_random(h, (int)r, it);
     }
+    if (h->records_only) return;  // no marker set: no coefficients, no sweep
     hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->cm.d_setof, h->cm.d_loc,
                        h->cm.d_vbidx, h->cm.d_sets, h->cm.d_scal, h->mm.d_varBeta, h->pm->mpm, h->cm.d_lhs0, h->cm.d_rhs0, h->cm.d_beta, h->cm.d_c, h->cm.d_w,
                        h->cm.d_q, h->cm.d_T, h->cm.d_chi, -1, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->mm.d_regs, h->mm.d_regchi, h->mm.d_rcls,
@@ -1131,7 +1173,7 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
 
 int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, traces and posterior sums; advances h->iter
     const uint64_t it = (uint64_t)(h->iter + 1);
-    launch_variance(h, -1, it);
+    if (!h->records_only) launch_variance(h, -1, it);
     h->iter += 1;
     const bool do_trace = h->mm.d_trace_loci && trace_idx < h->mm.trace_ext_cap, do_accum = is_kept(h, h->iter);
     if (do_trace || do_accum) {
@@ -1162,7 +1204,7 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
 // with nothing changed and is launched again, k_prep first (it redraws the same keyed numbers and clears the hand-off counters)
 int one_iteration(ngp_handle *h, int64_t trace_idx, hipEvent_t *evs, bool resume_mid = false) {
     iteration_pre(h, trace_idx, resume_mid);
-    launch_sweep(h, 0, h->NBLK, evs);
+    if (!h->records_only) launch_sweep(h, 0, h->NBLK, evs);
     return iteration_post(h, trace_idx);
 }
 
@@ -1423,7 +1465,8 @@ int ready(ngp_handle *h) {
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: ngp_end_panel builds the Gram window the sweep needs");
     REQUIRE(h->have_y, NGP_ERR_STATE, "y not set");
-    REQUIRE(!h->sets.empty(), NGP_ERR_STATE, "no marker set added");
+    if (h->records_only) REQUIRE(!h->mm.rnd.empty(), NGP_ERR_STATE, "no random-effect set added (a handle made by ngp_set_records has no marker sets)");
+    else REQUIRE(!h->sets.empty(), NGP_ERR_STATE, "no marker set added");
     int rc;
     if ((rc = sync_tables(h))) return rc;
     return sync_linear_blocks(h, -1);
@@ -1802,6 +1845,7 @@ int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t me
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
     REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
@@ -2287,6 +2331,7 @@ namespace {
 int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *beta, int64_t *delta, double *varBeta, double *piHat, bool dev) {
     int rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
     REQUIRE(set_id >= 0 && set_id < (int)h->sets.size(), NGP_ERR_ARG, "unknown set id");
     REQUIRE(ycorr && beta && varBeta, NGP_ERR_ARG, "null state pointer");
     REQUIRE(std::isfinite(varE) && varE > 0.0, NGP_ERR_ARG, "varE must be finite and positive");
@@ -2397,6 +2442,7 @@ int32_t ngp_profile_iteration(ngp_handle *h, double *avg_ms, int64_t *launches, 
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
     if ((rc = ready(h))) return rc;
     const int64_t n = (h->plan.mode == 1) ? 1 : h->NBLK;
     std::vector<hipEvent_t> evs((size_t)(2 * n));
@@ -2609,7 +2655,9 @@ int32_t ngp_share_panel(ngp_handle *h, ngp_handle *owner) {
     REQUIRE(!owner->panel_open, NGP_ERR_STATE, "ngp_share_panel: the owner's panel is still open (ngp_end_panel)");
     HCHK(hipStreamSynchronize(owner->stream));
     h->cu_count = owner->cu_count;
-    return alloc_panel(h, owner->N, owner->P, owner);
+    if ((rc = alloc_panel(h, owner->N, owner->P, owner))) return rc;
+    h->records_only = owner->records_only;
+    return NGP_OK;
     NGP_CATCH(h)
 }
 
@@ -3045,6 +3093,7 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(vClass && pi && K >= 2 && K <= NGP_RMAX, NGP_ERR_ARG, "BayesR needs 2..16 variance classes with their probabilities");
     double ps = 0.0;
@@ -3089,6 +3138,7 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
     REQUIRE(k >= 1 && k <= NGP_KMAX, NGP_ERR_ARG, "a tuple holds 1..4 correlated sets");
@@ -3305,6 +3355,39 @@ int upload(ngp_handle *h, DevArray<T> &d, const std::vector<T> &v) {
     if (!v.empty()) HCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return NGP_OK;
 }
+// digest of a dense K without bringing it to the host: k_dense_digest hashes every row on the device (one fixed order), the q row
+// words are folded here.  Done once per matrix; sets that share it share the word.
+int dense_digest(ngp_handle *h, const DenseK &dk, uint64_t *out) {
+    DevArray<unsigned long long> d_rh;
+    int rc;
+    if ((rc = d_rh.alloc(h, (size_t)dk.q))) return rc;
+    hipLaunchKernelGGL(k_dense_digest, dim3((unsigned)((dk.q + 3) / 4)), dim3(256), 0, h->stream, (const double *)dk.K, (long long)dk.ld, (long long)dk.q, d_rh.get());
+    std::vector<unsigned long long> rh((size_t)dk.q);
+    HCHK(hipMemcpyAsync(rh.data(), d_rh, rh.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
+    *out = bytes_digest(1469598103934665603ull, rh.data(), rh.size() * sizeof(unsigned long long));
+    return NGP_OK;
+}
+
+// levels of N records for a random-effect set: records grouped by level (a stable counting sort, ascending within a level) and
+// zpz_l = z_l'z_l (src/mme.jl:193-196): the record count; weighted residuals: sum of w over the level's records in that order (:183-188)
+void group_levels(const ngp_handle *h, const int32_t *level, int64_t q, std::vector<long long> &lp, std::vector<int> &lr, std::vector<int> &lv,
+                  std::vector<double> &zpz) {
+    const int64_t N = h->N;
+    lp.assign((size_t)q + 1, 0); lr.resize((size_t)N); lv.resize((size_t)N); zpz.assign((size_t)q, 0.0);
+    for (int64_t i = 0; i < N; i++) lp[(size_t)level[i] + 1]++;
+    for (int64_t l = 0; l < q; l++) lp[(size_t)l + 1] += lp[(size_t)l];
+    {
+        std::vector<long long> pos(lp.begin(), lp.end() - 1);
+        for (int64_t i = 0; i < N; i++) { lr[(size_t)pos[(size_t)level[i]]++] = (int)i; lv[(size_t)i] = level[i]; }
+    }
+    for (int64_t l = 0; l < q; l++) {
+        if (h->h_rw.empty()) { zpz[(size_t)l] = (double)(lp[(size_t)l + 1] - lp[(size_t)l]); continue; }
+        double a = 0.0;
+        for (long long k = lp[(size_t)l]; k < lp[(size_t)l + 1]; k++) a = a + h->h_rw[(size_t)lr[(size_t)k]];
+        zpz[(size_t)l] = a;
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -3369,23 +3452,10 @@ int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const
                 REQUIRE(it != e && *it == (int)l && kv[(size_t)(it - kc.begin())] == kv[(size_t)k], NGP_ERR_ARG, "random-effect set: K is not symmetric");
             }
     }
-    // records grouped by level: a stable counting sort of the record indices (ascending within a level)
-    std::vector<long long> lp((size_t)q + 1, 0);
-    std::vector<int> lr((size_t)N), lv((size_t)N);
-    for (int64_t i = 0; i < N; i++) lp[(size_t)level[i] + 1]++;
-    for (int64_t l = 0; l < q; l++) lp[(size_t)l + 1] += lp[(size_t)l];
-    {
-        std::vector<long long> pos(lp.begin(), lp.end() - 1);
-        for (int64_t i = 0; i < N; i++) { lr[(size_t)pos[(size_t)level[i]]++] = (int)i; lv[(size_t)i] = level[i]; }
-    }
-    // zpz_l = z_l'z_l (src/mme.jl:193-196): the record count; weighted residuals: sum of w over the level's records in that order (:183-188)
-    std::vector<double> zpz((size_t)q, 0.0);
-    for (int64_t l = 0; l < q; l++) {
-        if (h->h_rw.empty()) { zpz[(size_t)l] = (double)(lp[(size_t)l + 1] - lp[(size_t)l]); continue; }
-        double a = 0.0;
-        for (long long k = lp[(size_t)l]; k < lp[(size_t)l + 1]; k++) a = a + h->h_rw[(size_t)lr[(size_t)k]];
-        zpz[(size_t)l] = a;
-    }
+    std::vector<long long> lp;
+    std::vector<int> lr, lv;
+    std::vector<double> zpz;
+    group_levels(h, level, q, lp, lr, lv, zpz);
     HRand R;
     R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = offdiag;
     R.sig = bytes_digest(bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull, lv.data(), lv.size() * 4), kp.data(), kp.size() * 8), kc.data(),
@@ -3492,6 +3562,7 @@ int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double 
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
     REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
     REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
@@ -3724,6 +3795,307 @@ int32_t ngp_debug_throw(ngp_handle *h, int32_t kind) {
     if (kind == 1) { std::vector<double> v; v.resize(v.max_size() + 1); }
     if (kind == 2) throw 42;
     return fail(h, NGP_ERR_ARG, "ngp_debug_throw: kind must be 0, 1 or 2");
+    NGP_CATCH(h)
+}
+
+}  // extern "C"
+
+/* ---- GBLUP (src/prepMatVec.jl:122-126): the genomic relationship matrix on the device, its inverse, dense random-effect sets, and
+ * handles without a genotype panel.  Kernels and summation orders: ngp_dense.h, DESIGN.md section 2. ---- */
+namespace {
+// rocSOLVER (Cholesky factorisation and inverse of G) is loaded on first use, like RCCL: no link-time dependency
+struct RocSolver {
+    void *lib = nullptr;
+    int (*CreateHandle)(void **) = nullptr;
+    int (*DestroyHandle)(void *) = nullptr;
+    int (*SetStream)(void *, hipStream_t) = nullptr;
+    int (*Dpotrf)(void *, int, int, double *, int, int *) = nullptr;
+    int (*Dpotri)(void *, int, int, double *, int, int *) = nullptr;
+    std::string err;
+    std::mutex mu;
+    bool load() {
+        std::lock_guard<std::mutex> lk(mu);
+        if (lib) return true;
+        const char *names[] = {"librocsolver.so.0", "librocsolver.so", "/opt/rocm/lib/librocsolver.so.0", "/opt/rocm/lib/librocsolver.so"};
+        for (const char *nm : names) { lib = dlopen(nm, RTLD_NOW | RTLD_LOCAL); if (lib) break; }
+        if (!lib) { const char *d = dlerror(); err = std::string("cannot load rocSOLVER: ") + (d ? d : "?"); return false; }
+        CreateHandle = (decltype(CreateHandle))dlsym(lib, "rocblas_create_handle");
+        DestroyHandle = (decltype(DestroyHandle))dlsym(lib, "rocblas_destroy_handle");
+        SetStream = (decltype(SetStream))dlsym(lib, "rocblas_set_stream");
+        Dpotrf = (decltype(Dpotrf))dlsym(lib, "rocsolver_dpotrf");
+        Dpotri = (decltype(Dpotri))dlsym(lib, "rocsolver_dpotri");
+        if (!CreateHandle || !DestroyHandle || !SetStream || !Dpotrf || !Dpotri) { err = "rocSOLVER symbols missing"; dlclose(lib); lib = nullptr; return false; }
+        return true;
+    }
+} g_rocsolver;
+constexpr int ROCBLAS_FILL_LOWER = 122;
+
+// a range of raw genotype columns into G: staged in chunks of whole columns (256 MiB, multiples of 64 columns), centred (and scaled)
+// in fp64 on the device, then G += Xc Xc' on the matrix cores
+template <typename TIn>
+int grm_columns(ngp_handle *h, const TIn *M, int64_t ncol, int64_t ld) {
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Grm &g = h->grm;
+    REQUIRE(g.state == 1, NGP_ERR_STATE, "ngp_grm_columns_* needs an open relationship matrix (ngp_grm_begin)");
+    REQUIRE(M != nullptr && ncol > 0, NGP_ERR_ARG, "genotype columns: a matrix of at least one column");
+    REQUIRE(ld >= g.N, NGP_ERR_ARG, "leading dimension smaller than N");
+    const int64_t N = g.N, Npad = g.m->ld;
+    int64_t cchunk = std::min<int64_t>((ncol + 63) / 64 * 64, ((int64_t)256 << 20) / (int64_t)(std::max<int64_t>(ld, Npad) * (int64_t)sizeof(double)));
+    cchunk = std::max<int64_t>(64, cchunk / 64 * 64);
+    DevArray<TIn> d_g;
+    DevArray<double> d_xc, d_tp;
+    DevArray<unsigned> d_bad;
+    if (d_g.alloc_raw((size_t)cchunk * (size_t)ld) != hipSuccess || d_xc.alloc_raw((size_t)cchunk * (size_t)Npad) != hipSuccess)
+        return fail(h, NGP_ERR_NOMEM, "staging buffers of the relationship matrix");
+    if ((rc = d_tp.alloc(h, (size_t)cchunk)) || (rc = d_bad.alloc(h, 2))) return rc;
+    std::vector<double> tp((size_t)cchunk);
+    double sum2pq = g.sum2pq;
+    const int64_t col_base = g.ncols;  // columns of the calls before this one (g.ncols moves on with every chunk)
+    const unsigned nb64 = (unsigned)(Npad / 64);
+    for (int64_t c0 = 0; c0 < ncol; c0 += cchunk) {
+        const int64_t nc = std::min<int64_t>(cchunk, ncol - c0), cpad = (nc + 3) / 4 * 4;
+        const unsigned bad0[2] = {0u, 0xFFFFFFFFu};
+        hipError_t e = hipMemcpyAsync(d_bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, h->stream);
+        // (the last column may be shorter than ld in the caller's buffer: nc - 1 full columns + N elements)
+        if (e == hipSuccess) e = hipMemcpyAsync(d_g, M + (size_t)c0 * (size_t)ld, ((size_t)(nc - 1) * (size_t)ld + (size_t)N) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_grm_cols<TIn>, dim3((unsigned)cpad), dim3(64), 0, h->stream, (const TIn *)d_g, (long long)N, (long long)ld, (long long)nc,
+                               (long long)Npad, g.method, d_xc.get(), d_tp.get(), d_bad.get());
+            unsigned bad[2] = {0u, 0u};
+            e = hipMemcpyAsync(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(tp.data(), d_tp, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            // a refused chunk has not touched G: the columns of the calls (and chunks) before it stay, the builder stays open
+            if (e == hipSuccess && bad[0] != 0u) return fail(h, NGP_ERR_ARG, "non-finite genotype value in the columns of the relationship matrix");
+            if (e == hipSuccess && bad[1] != 0xFFFFFFFFu)
+                return fail(h, NGP_ERR_ARG, "relationship matrix, method 2: column " + std::to_string(col_base + c0 + (int64_t)bad[1] - 1) +
+                                                " (0-based, counted over all calls) is monomorphic: 2 p (1 - p) = 0 divides 0 by 0 (src/misc.jl:152-154)");
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_grm_syrk, dim3(nb64, nb64), dim3(256), 0, h->stream, (const double *)d_xc, (long long)Npad, (long long)cpad, g.m->K.get());
+            e = hipStreamSynchronize(h->stream);  // the staging buffers are reused by the next chunk
+        }
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("relationship matrix columns: ") + hipGetErrorString(e));
+        if (g.method == 1) for (int64_t c = 0; c < nc; c++) sum2pq = sum2pq + tp[(size_t)c];
+        g.sum2pq = sum2pq;
+        g.ncols += nc;
+    }
+    return NGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t ngp_set_records(ngp_handle *h, int64_t N) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->req.storage == NGP_STORAGE_F32, NGP_ERR_ARG, "ngp_set_records: compact storage concerns genotype panels; this handle has none");
+    // one inert block of 64 zero columns stands in for the panel: every array a chain has exists, no sweep is ever launched
+    const PlanRequest saved = h->req;
+    h->req.mode = 0;
+    rc = alloc_panel(h, N, NGP_BLK);
+    h->req = saved;
+    if (rc) return rc;
+    h->records_only = true;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_begin(ngp_handle *h, int64_t N, int32_t method) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(N >= 1 && N < ((int64_t)1 << 31) - 64, NGP_ERR_ARG, "relationship matrix: 1 <= N < 2^31");
+    REQUIRE(method == 1 || method == 2, NGP_ERR_ARG, "relationship matrix: method 1 or 2 (src/misc.jl:149-156)");
+    h->grm = Grm();  // (a matrix begun earlier and never used goes first)
+    auto m = std::make_shared<DenseK>();
+    const int64_t Npad = (N + 63) / 64 * 64;
+    if ((rc = m->K.alloc(h, (size_t)Npad * (size_t)Npad))) return rc;
+    HCHK(hipStreamSynchronize(h->stream));
+    m->q = N; m->ld = Npad;
+    h->grm.m = std::move(m); h->grm.state = 1; h->grm.method = method; h->grm.N = N;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_columns_f64(ngp_handle *h, const double *M, int64_t ncol, int64_t ld) {
+    NGP_TRY
+    return grm_columns<double>(h, M, ncol, ld);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_columns_f32(ngp_handle *h, const float *M, int64_t ncol, int64_t ld) {
+    NGP_TRY
+    return grm_columns<float>(h, M, ncol, ld);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_columns_u8(ngp_handle *h, const uint8_t *M, int64_t ncol, int64_t ld) {
+    NGP_TRY
+    return grm_columns<uint8_t>(h, M, ncol, ld);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_end(ngp_handle *h) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Grm &g = h->grm;
+    REQUIRE(g.state == 1, NGP_ERR_STATE, "ngp_grm_end needs an open relationship matrix (ngp_grm_begin)");
+    REQUIRE(g.ncols > 0, NGP_ERR_STATE, "relationship matrix: no genotype column was given");
+    const double denom = g.method == 1 ? g.sum2pq : (double)g.ncols;
+    if (!(denom > 0.0) || !std::isfinite(denom)) {
+        h->grm = Grm();
+        return fail(h, NGP_ERR_ARG, "relationship matrix, method 1: the sum of 2 p (1 - p) over the columns is not positive (every column monomorphic?): "
+                                    "G would be 0 / 0 (src/misc.jl:150); the matrix is dropped");
+    }
+    const unsigned gy = (unsigned)std::min<int64_t>(g.N, 65535);
+    hipLaunchKernelGGL(k_grm_mirror, dim3((unsigned)((g.N + 255) / 256), gy), dim3(256), 0, h->stream, g.m->K.get(), (long long)g.N, (long long)g.m->ld, 1, denom);
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    g.state = 2;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_get(ngp_handle *h, double *G_out) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Grm &g = h->grm;
+    REQUIRE(g.state >= 2, NGP_ERR_STATE, "no complete relationship matrix on this handle (ngp_grm_end; a dense set may have taken it)");
+    REQUIRE(G_out != nullptr, NGP_ERR_ARG, "null output pointer");
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy2D(G_out, (size_t)g.N * sizeof(double), g.m->K, (size_t)g.m->ld * sizeof(double), (size_t)g.N * sizeof(double), (size_t)g.N, hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_grm_invert(ngp_handle *h) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Grm &g = h->grm;
+    REQUIRE(g.state == 2, NGP_ERR_STATE, g.state == 3 ? "the relationship matrix is inverted already" : "ngp_grm_invert needs a complete relationship matrix (ngp_grm_end)");
+    if (!g_rocsolver.load()) return fail(h, NGP_ERR_HIP, g_rocsolver.err + " (ngp_grm_invert factorises on the device; there is no host fallback)");
+    struct Blas {  // a rocBLAS handle for this call, destroyed however it ends
+        void *p = nullptr;
+        ~Blas() { if (p) (void)g_rocsolver.DestroyHandle(p); }
+    } blas;
+    if (g_rocsolver.CreateHandle(&blas.p) != 0 || !blas.p || g_rocsolver.SetStream(blas.p, h->stream) != 0)
+        return fail(h, NGP_ERR_HIP, "rocblas_create_handle / rocblas_set_stream failed");
+    DevArray<int> d_info;
+    if ((rc = d_info.alloc(h, 1))) return rc;
+    int info = 0;
+    const int n = (int)g.N, lda = (int)g.m->ld;
+    // column-major, lower triangle: what k_grm_syrk computed and k_grm_mirror copied (G is symmetric, either triangle would do)
+    int st = g_rocsolver.Dpotrf(blas.p, ROCBLAS_FILL_LOWER, n, g.m->K.get(), lda, d_info.get());
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+    if (st != 0 || info != 0) {  // the factorisation has overwritten part of G: the matrix is gone either way
+        h->grm = Grm();
+        if (st != 0) return fail(h, NGP_ERR_HIP, "rocsolver_dpotrf failed (rocblas status " + std::to_string(st) + "); the relationship matrix is dropped");
+        return fail(h, NGP_ERR_ARG, "the relationship matrix is not positive definite: the Cholesky factorisation failed at pivot " + std::to_string(info) +
+                                        " (1-based); the matrix is dropped");
+    }
+    st = g_rocsolver.Dpotri(blas.p, ROCBLAS_FILL_LOWER, n, g.m->K.get(), lda, d_info.get());
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+    if (st != 0 || info != 0) {
+        h->grm = Grm();
+        if (st != 0) return fail(h, NGP_ERR_HIP, "rocsolver_dpotri failed (rocblas status " + std::to_string(st) + "); the relationship matrix is dropped");
+        return fail(h, NGP_ERR_ARG, "inverse of the relationship matrix: zero pivot " + std::to_string(info) + " (1-based); the matrix is dropped");
+    }
+    const unsigned gy = (unsigned)std::min<int64_t>(g.N, 65535);
+    hipLaunchKernelGGL(k_grm_mirror, dim3((unsigned)((g.N + 255) / 256), gy), dim3(256), 0, h->stream, g.m->K.get(), (long long)g.N, (long long)g.m->ld, 0, 1.0);
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    g.state = 3;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* A random-effect set with a dense K (ngp_dense.h).  Every argument is checked before anything changes: a refused call leaves the
+ * handle (and its relationship matrix) as it was. */
+int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q, const double *K, ngp_handle *k_src, int32_t k_src_set, double df,
+                                 double scale, double varU0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
+    REQUIRE(q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: 1 <= q < 2^31");
+    REQUIRE(level != nullptr || q == h->N, NGP_ERR_ARG, "random-effect set: level == NULL means record i is level i and needs q == N");
+    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
+    REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
+    REQUIRE(!(K && k_src), NGP_ERR_ARG, "dense random-effect set: K from a host pointer OR from a set of another handle, not both");
+    const int64_t N = h->N;
+    std::vector<int32_t> ident;
+    if (!level) { ident.resize((size_t)N); for (int64_t i = 0; i < N; i++) ident[(size_t)i] = (int32_t)i; level = ident.data(); }
+    for (int64_t i = 0; i < N; i++) REQUIRE(level[i] >= 0 && (int64_t)level[i] < q, NGP_ERR_ARG, "random-effect set: a record's level is outside 0..q-1");
+    // where K comes from: a host matrix (copied), a set of another handle (by reference), or this handle's inverted relationship matrix
+    std::shared_ptr<DenseK> dk;
+    bool from_grm = false;
+    if (K) {
+        for (int64_t l = 0; l < q; l++)
+            for (int64_t c = 0; c <= l; c++) {
+                const double a = K[(size_t)l * (size_t)q + (size_t)c];
+                REQUIRE(std::isfinite(a), NGP_ERR_ARG, "random-effect set: non-finite entry in K");
+                REQUIRE(a == K[(size_t)c * (size_t)q + (size_t)l], NGP_ERR_ARG, "random-effect set: K is not symmetric");
+            }
+        dk = std::make_shared<DenseK>();
+        if (dk->K.alloc_raw((size_t)q * (size_t)q) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "dense K");
+        dk->q = q; dk->ld = q;
+        HCHK(hipMemcpy(dk->K, K, (size_t)q * (size_t)q * sizeof(double), hipMemcpyHostToDevice));
+    } else if (k_src) {
+        // (like ngp_share_panel's owner: a complete handle of this device that no other thread is setting up during this call)
+        REQUIRE(k_src != h, NGP_ERR_ARG, "dense random-effect set: k_src is this handle (a set shares the K of a set on ANOTHER handle)");
+        REQUIRE(k_src->stream != nullptr && k_src->pm && !k_src->panel_open, NGP_ERR_ARG, "dense random-effect set: k_src has no panel or records yet (or its panel is still open)");
+        REQUIRE(k_src->device == h->device, NGP_ERR_ARG, "dense random-effect set: a shared K must be on this handle's device");
+        REQUIRE(k_src_set >= 0 && k_src_set < (int32_t)k_src->mm.rnd.size() && k_src->mm.rnd[(size_t)k_src_set].dk, NGP_ERR_ARG,
+                "dense random-effect set: k_src_set is not a dense set of k_src");
+        dk = k_src->mm.rnd[(size_t)k_src_set].dk;
+        REQUIRE(dk->q == q, NGP_ERR_ARG, "dense random-effect set: the shared K has another q");
+        HCHK(hipStreamSynchronize(k_src->stream));
+    } else {
+        REQUIRE(h->grm.state == 3, NGP_ERR_STATE, "dense random-effect set without K: this handle has no inverted relationship matrix (ngp_grm_invert)");
+        REQUIRE(h->grm.N == q, NGP_ERR_ARG, "dense random-effect set: the relationship matrix has another size than q");
+        dk = h->grm.m;
+        from_grm = true;
+    }
+    // the diagonal (k_rand_levels' lhs, k_dense_var) back from the device, and the digest of the whole matrix if nobody has taken it yet
+    std::vector<double> kd((size_t)q);
+    HCHK(hipMemcpy2D(kd.data(), sizeof(double), dk->K, (size_t)(dk->ld + 1) * sizeof(double), sizeof(double), (size_t)q, hipMemcpyDeviceToHost));
+    uint64_t kdig = dk->digest;
+    if (!k_src && (rc = dense_digest(h, *dk, &kdig))) return rc;  // (a fresh matrix; the word is stored below, once the call can no longer be refused)
+    for (int64_t l = 0; l < q; l++) REQUIRE(std::isfinite(kd[(size_t)l]) && kd[(size_t)l] > 0.0, NGP_ERR_ARG, "random-effect set: every diagonal entry of K must be > 0");
+    std::vector<long long> lp;
+    std::vector<int> lr, lv;
+    std::vector<double> zpz;
+    group_levels(h, level, q, lp, lr, lv, zpz);
+    HRand R;
+    R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = true;
+    // digest of the level coding and of every entry of K (hashed on the device: a dense K may never have been on the host)
+    R.sig = bytes_digest(bytes_digest(1469598103934665603ull ^ 0x44454E5345ull, lv.data(), lv.size() * 4), &kdig, sizeof(kdig));
+    const double vu[2] = {varU0, 0.0};
+    if ((rc = upload(h, R.d_lptr, lp)) || (rc = upload(h, R.d_lrows, lr)) || (rc = upload(h, R.d_level, lv)) || (rc = upload(h, R.d_kdiag, kd)) ||
+        (rc = upload(h, R.d_zpz, zpz)))
+        return rc;
+    if ((rc = R.d_u.alloc(h, (size_t)q)) || (rc = R.d_sum_u.alloc(h, (size_t)q)) || (rc = R.d_vu.alloc(h, 2)) ||
+        (rc = R.d_scr.alloc(h, (size_t)NGP_RS_ROWS_DENSE * (size_t)q)))
+        return rc;
+    HCHK(hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice));
+    HCHK(hipStreamSynchronize(h->stream));
+    dk->digest = kdig;
+    R.dk = std::move(dk);
+    if (from_grm) h->grm = Grm();  // consumed: the set owns the matrix now
+    if (set_id) *set_id = (int32_t)h->mm.rnd.size();
+    h->mm.rnd.push_back(std::move(R));
+    return NGP_OK;
     NGP_CATCH(h)
 }
 

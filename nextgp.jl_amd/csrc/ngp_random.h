@@ -76,8 +76,9 @@ __global__ __launch_bounds__(256) void k_rand_levels(const double *__restrict__ 
         return;
     }
     // general K: the part of dot(K[:, l], u) over the levels ABOVE l uses the values of the previous iteration, known now
+    // (kptr null: a dense K, whose dhi is k_dense_dhi's -- ngp_dense.h)
     double dhi = 0.0;
-    for (long long k = kptr[l]; k < kptr[l + 1]; k++) {
+    if (kptr) for (long long k = kptr[l]; k < kptr[l + 1]; k++) {
         const int c = kcol[k];
         if (c > l) {
             const double t = kval[k] * u[c];

@@ -262,6 +262,45 @@ function add_random_set!(h::Handle, level::Vector{Int32}, q::Integer, K, df::Flo
                    h.ptr, level, q, kp, kc, kv, df, scale, varU0, id))
     return id[]
 end
+# A random-effect set over a DENSE q x q precision (ngp_add_random_set_dense): GBLUP's Z[z].iVarStr = inv(makeG(M)), which the shim's
+# caller has built already (src/prepMatVec.jl:122-126).  level === nothing: the identity incidence (record i is level i).  K is copied to
+# the device as it is (symmetric: row- and column-major are the same matrix) and sampled by the blocked engine, K read once per iteration.
+function add_random_set_dense!(h::Handle, level::Union{Nothing,Vector{Int32}}, q::Integer, K::Matrix{Float64}, df::Float64, scale::Float64,
+                               varU0::Float64)
+    size(K) == (q, q) || error("dense random-effect set: K must be $q x $q")
+    id = Ref{Int32}(0)
+    lv = level === nothing ? Ptr{Int32}(C_NULL) : pointer(level)
+    GC.@preserve level check(h, ccall((:ngp_add_random_set_dense, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Float64}, Ptr{Cvoid}, Int32, Float64, Float64, Float64, Ref{Int32}),
+                   h.ptr, lv, q, K, C_NULL, 0, df, scale, varU0, id))
+    return id[]
+end
+# a model without marker sets (GBLUP terms only): N records in place of the panel
+const RECORDS_ONLY_P = 64   # columns of the inert block such a handle reports as its P (state and file formats)
+set_records!(h::Handle, N::Integer) = check(h, ccall((:ngp_set_records, LIB), Int32, (Ptr{Cvoid}, Int64), h.ptr, N))
+
+# VanRaden's G on the device (drop-in for misc.makeG, src/misc.jl:145-160; M is NOT centred in place): fp64 on the matrix cores
+grm_begin!(h::Handle, N::Integer, method::Integer) = check(h, ccall((:ngp_grm_begin, LIB), Int32, (Ptr{Cvoid}, Int64, Int32), h.ptr, N, method))
+grm_columns!(h::Handle, M::Matrix{Float64}) =
+    check(h, ccall((:ngp_grm_columns_f64, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64), h.ptr, M, size(M, 2), size(M, 1)))
+grm_columns!(h::Handle, M::Matrix{Float32}) =
+    check(h, ccall((:ngp_grm_columns_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64), h.ptr, M, size(M, 2), size(M, 1)))
+grm_columns!(h::Handle, M::Matrix{UInt8}) =
+    check(h, ccall((:ngp_grm_columns_u8, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt8}, Int64, Int64), h.ptr, M, size(M, 2), size(M, 1)))
+grm_end!(h::Handle) = check(h, ccall((:ngp_grm_end, LIB), Int32, (Ptr{Cvoid},), h.ptr))
+grm_invert!(h::Handle) = check(h, ccall((:ngp_grm_invert, LIB), Int32, (Ptr{Cvoid},), h.ptr))
+function grm_get(h::Handle, N::Integer)
+    G = Matrix{Float64}(undef, N, N)
+    check(h, ccall((:ngp_grm_get, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, G))
+    return G
+end
+function makeG(M::Matrix; method::Integer=1, device::Integer=0, inverse::Bool=false)
+    h = Handle(device=device)
+    grm_begin!(h, size(M, 1), method); grm_columns!(h, M); grm_end!(h)
+    inverse && grm_invert!(h)                     # inv(makeG(M)) of src/prepMatVec.jl:124 without leaving the device
+    return grm_get(h, size(M, 1))
+end
+
 # the level of every record from the one-hot incidence Z.data (src/prepMatVec.jl:143-150); rows that are not one-hot are refused
 function random_levels(Zd::AbstractMatrix)
     lv = Vector{Int32}(undef, size(Zd, 1))
@@ -391,6 +430,9 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     h = Handle(device=device, seed=seed)
     E.str == "D" && set_residual_weights!(h, Vector{Float64}(E.iVarStr))   # before the panel (src/mme.jl:71-75)
     sets = collect(keys(M))                       # Dict order, as src/samplers.jl:50
+    if isempty(sets)                              # GBLUP terms only (src/prepMatVec.jl:122-126): records, no genotype panel
+        set_records!(h, nData)
+    else
     # consecutive column ranges of ONE panel on the device, handed over set by set (no hcat of the M[s].data on the host)
     begin_panel!(h, size(M[sets[1]].data, 1), sum(M[s].dims[2] for s in sets))
     col0 = 0
@@ -399,6 +441,7 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         col0 += M[s].dims[2]
     end
     end_panel!(h)
+    end
     col0 = 0
     ids = Dict{Any,Int32}()
     for s in sets
@@ -434,7 +477,11 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     zids = Dict{Any,Int32}()
     for z in zsets
         q = size(Z[z].data, 2)
-        zids[z] = add_random_set!(h, random_levels(Z[z].data), q, Z[z].iVarStr, Float64(Z[z].df), Float64(Z[z].scale), Float64(varU[z]))
+        if Z[z].method == "GBLUP"                 # dense iVarStr = inv(G), Z = I (src/prepMatVec.jl:124-126): the blocked dense engine
+            zids[z] = add_random_set_dense!(h, nothing, q, Matrix{Float64}(Z[z].iVarStr), Float64(Z[z].df), Float64(Z[z].scale), Float64(varU[z]))
+        else                                      # every other Z set keeps the CSR call it had: no existing model changes its bits
+            zids[z] = add_random_set!(h, random_levels(Z[z].data), q, Z[z].iVarStr, Float64(Z[z].df), Float64(Z[z].scale), Float64(varU[z]))
+        end
     end
     set_y!(h, Vector{Float64}(ycorr))            # ycorr == y at this point (src/mme.jl:57)
     set_residual_prior!(h, E.df, E.scale)
@@ -477,9 +524,12 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         end
     end
     # the caller's arrays as the reference's sampler leaves them: the state after the last iteration
-    Ptot = col0
+    # read-back buffers by the HANDLE's P: a handle made by set_records! carries one inert block of RECORDS_ONLY_P zero columns, which
+    # ngp_get_state copies out like any panel's (include/nextgp_hip.h, ngp_set_records)
+    Ptot = isempty(sets) ? RECORDS_ONLY_P : col0
     bet = Vector{Float64}(undef, Ptot); del = Vector{Int64}(undef, Ptot)
-    nvb = sum(length(varBeta[s]) for s in sets); vb = Vector{Float64}(undef, nvb); pih = Vector{Float64}(undef, 2 * length(sets))
+    nvb = isempty(sets) ? 0 : sum(length(varBeta[s]) for s in sets)
+    vb = Vector{Float64}(undef, max(nvb, 1)); pih = Vector{Float64}(undef, 2 * max(length(sets), 1))
     ve = Ref{Float64}(0.0); bb = Ref{Float64}(0.0); it = Ref{Int64}(0)
     bfix = Vector{Float64}(undef, max(nfix, 1)); sbfix = similar(bfix); nfx = Ref{Int64}(0)
     check(h, ccall((:ngp_get_state, LIB), Int32,
