@@ -193,6 +193,26 @@ int32_t ngp_set_random(ngp_handle *h, int32_t set_id, const double *u, const dou
 /* Fine seam of one random-effect set: sampleZ!(zSet, Z, u, ycorr, varE, varU) (src/functions.jl:92-97) on the caller's arrays, updated
  * in place (ycorr N, u q, varU one double).  Keyed like ngp_sweep_set: the set's own call counter is the iteration of its draws. */
 int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *u, double *varU);
+/* The Gauss-Seidel engine of a CSR set whose K has off-diagonal entries (a pedigree's A^-1).  mode 1: serial, one lane walks the levels
+ * in order; mode 2: level-scheduled -- depth(l) = 0 for a row without an entry left of its diagonal, else 1 + max depth(c) over its
+ * columns c < l; rows of equal depth are independent and run one thread per row, the depths in order (one launch per depth of more than
+ * 1024 rows, one single-workgroup launch per run of narrower depths); mode 0: automatic (scheduled when q exceeds 2 levels per depth, the measured
+ * crossover: DESIGN.md, "Random-effect sets"; serial otherwise).
+ * Both engines do the same operations on the same values in the same order per row: no result depends on the mode, nor does the
+ * signature of snapshots.  Refused (NGP_ERR_ARG): a mode outside 0..2, a set with a diagonal or a dense K.  ngp_get_random_schedule
+ * returns the engine in force (0 none: diagonal or dense K, 1 serial, 2 scheduled), the number of depths and the Gauss-Seidel launches
+ * per step; any pointer may be NULL. */
+int32_t ngp_set_random_schedule(ngp_handle *h, int32_t set_id, int32_t mode);
+int32_t ngp_get_random_schedule(ngp_handle *h, int32_t set_id, int32_t *engine, int64_t *depths, int64_t *launches);
+/* A^-1 of a pedigree on the host (no device, no handle; messages through ngp_last_error(NULL)): n animals, sire[i] / dam[i] the 1-based
+ * positions of the parents in the same list, 0 = unknown, parents in front of their offspring (any other order, an index outside 0..n, an
+ * animal that is its own parent: NGP_ERR_ARG).  Inbreeding coefficients F (f_out, n entries, may be NULL) by Meuwissen and Luo's method;
+ * Henderson's rules per animal i with known parents p (one parent listed twice counts twice): d = 1 - sum_p (1 + F_p) / 4, a = 1 / d,
+ * K_ii += a, K_ip += -a/2, K_pi += -a/2, K_pp' += a/4 for every pair, in animal order -- reproducible and exactly symmetric.  CSR out:
+ * k_ptr (n + 1 entries, may be NULL), k_col / k_val (cap entries; columns ascending within a row).  nnz_out is always set; a cap smaller
+ * than it is NGP_ERR_ARG with k_ptr and f_out filled and k_col / k_val untouched: call with cap = 0 to count, then again to fill. */
+int32_t ngp_pedigree_ainv(int64_t n, const int32_t *sire, const int32_t *dam, double *f_out, int64_t *k_ptr, int32_t *k_col, double *k_val,
+                          int64_t cap, int64_t *nnz_out);
 
 /* Phenotypes; resets the chain: ycorr = y (src/mme.jl:57), b = 0, beta = 0, delta = 1, u = 0, varU = varU0, iter = 0, every variance and pi back to
  * the values given to ngp_add_marker_set (src/mme.jl:351-360, 516), all posterior sums and nKept zero. */

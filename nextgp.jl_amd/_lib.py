@@ -148,6 +148,7 @@ SYMBOLS = [
     "ngp_add_marker_set_lv", "ngp_get_lv_state", "ngp_set_lv_state",
     "ngp_grm_begin", "ngp_grm_columns_f64", "ngp_grm_columns_f32", "ngp_grm_columns_u8", "ngp_grm_end", "ngp_grm_get", "ngp_grm_invert",
     "ngp_add_random_set_dense", "ngp_set_records",
+    "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
 ]
 
 _lib = None
@@ -183,6 +184,27 @@ def write_panel_file(path, G, bits=8):
                                      C.c_int64(G.shape[0]), C.c_int32(bits))
     if rc != 0:
         raise NextGPHipError(f"ngp_write_panel_file failed ({rc}): path not writable, or codes above 2 with bits=2")
+
+
+def pedigree_ainv(sire, dam):
+    """(F, (k_ptr, k_col, k_val)): inbreeding coefficients and A^-1 as CSR (columns ascending) of a pedigree listed parents first; sire /
+    dam are 1-based positions in the list, 0 = unknown (ngp_pedigree_ainv: Henderson's rules with inbreeding, on the host)."""
+    s = np.ascontiguousarray(sire, dtype=np.int32); d = np.ascontiguousarray(dam, dtype=np.int32)
+    if s.ndim != 1 or s.shape != d.shape or len(s) < 1:
+        raise ValueError("pedigree: one sire and one dam per animal")
+    n = len(s)
+    L = load()
+    F = np.empty(n); kp = np.empty(n + 1, dtype=np.int64); nnz = C.c_int64(0)
+    rc = L.ngp_pedigree_ainv(C.c_int64(n), _p(s, C.c_int32), _p(d, C.c_int32), _p(F, C.c_double), _p(kp, C.c_int64), None, None, C.c_int64(0),
+                             C.byref(nnz))
+    if rc != 0 and nnz.value <= 0:
+        raise NextGPHipError(f"ngp_pedigree_ainv failed ({rc}): " + (L.ngp_last_error(None) or b"").decode())
+    kc = np.empty(nnz.value, dtype=np.int32); kv = np.empty(nnz.value)
+    rc = L.ngp_pedigree_ainv(C.c_int64(n), _p(s, C.c_int32), _p(d, C.c_int32), _p(F, C.c_double), _p(kp, C.c_int64), _p(kc, C.c_int32),
+                             _p(kv, C.c_double), C.c_int64(nnz.value), C.byref(nnz))
+    if rc != 0:
+        raise NextGPHipError(f"ngp_pedigree_ainv failed ({rc}): " + (L.ngp_last_error(None) or b"").decode())
+    return F, (kp, kc, kv)
 
 
 def read_panel_header(path):
@@ -518,6 +540,17 @@ class Sampler:
         vu = C.c_double(varU)
         self._chk(self.L.ngp_sample_random_set(self.h, C.c_int32(set_id), C.c_double(varE), _p(ycorr, C.c_double), _p(u, C.c_double), C.byref(vu)))
         return vu.value
+
+    def set_random_schedule(self, set_id, mode):
+        """Gauss-Seidel engine of a CSR set with off-diagonal K: 0 / "auto", 1 / "serial", 2 / "scheduled" (the bits do not depend on it)."""
+        mode = {"auto": 0, "serial": 1, "scheduled": 2}.get(mode, mode)
+        self._chk(self.L.ngp_set_random_schedule(self.h, C.c_int32(set_id), C.c_int32(int(mode))))
+
+    def get_random_schedule(self, set_id):
+        """dict(engine: 0 none / 1 serial / 2 scheduled -- the one in force, depths, launches per step)."""
+        e, d, n = C.c_int32(), C.c_int64(), C.c_int64()
+        self._chk(self.L.ngp_get_random_schedule(self.h, C.c_int32(set_id), C.byref(e), C.byref(d), C.byref(n)))
+        return dict(engine=e.value, depths=d.value, launches=n.value)
 
     def add_marker_set_r(self, col0, ncol, df, scale, varBeta0, vClass, pi, estPi=False, lhs0=None, rhs0=None):
         """BayesR set: class multipliers vClass of the set's single variance, class probabilities pi (src/mme.jl:374-383)."""

@@ -12,9 +12,11 @@ Same names, argument meaning and output files as the reference, so a model scrip
     BayesLV(v, f, covariates, varZeta; estimateVarZeta) BayesLV(v, "0 ~ x1 + x2", {"x1": ..}, varZeta, ...)    src/runTime.jl:116-133
     summaryMCMC("betaM"; outFolder)                     summaryMCMC("betaM", outFolder=...)                    src/misc.jl:241-244
 
+    makePed(pedigree, ids) / makeA(s, d)                makePed(path_or_rows, ids) / makeA(s, d)               src/misc.jl:73-115
+
 Interpreted here: the response, the intercept `1`, covariate / factor columns (optionally grouped by `blockThese`), `(1|g)` random
-effects and `SNP(...)` terms.  Interactions, `PED(...)`, correlated (Tuple) random effects, GBLUP priors, BayesRC are outside the
-accelerated path and raise NotImplementedError naming the reference code that handles them.
+effects, `PED(col)` pedigree effects (with `userPedData`) and `SNP(...)` terms.  Interactions, correlated (Tuple) random effects,
+BayesRC are outside the accelerated path and raise NotImplementedError naming the reference code that handles them.
 All arithmetic happens in libnextgp_hip.so; this file only parses, reshapes and writes files.
 """
 import os
@@ -24,9 +26,9 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
+from ._lib import pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
+__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -171,18 +173,20 @@ class ParsedFormula(tuple):
     everything itself (no state is left on the function: two models parsed in turn, or from threads, cannot pick up each other's
     covariates)."""
 
-    def __new__(cls, lhs, intercept, snps, covariates, random=(), order=()):
+    def __new__(cls, lhs, intercept, snps, covariates, random=(), order=(), ped=()):
         t = super().__new__(cls, (lhs, intercept, snps))
         t.covariates = list(covariates)
         t.random = list(random)  # grouping columns of the (1|g) terms, in formula order
-        t.order = list(order)    # ("1|", g) and ("snp", name) in formula order: where a GBLUP term stands among the (1|g) terms
+        t.order = list(order)    # ("1|", g), ("ped", col) and ("snp", name) in formula order: where a GBLUP or PED term stands among the (1|g) terms
+        t.ped = list(ped)        # columns of the PED(col) terms, in formula order
         return t
 
 
-def parse_formula(formula, random_effects=False):
+def parse_formula(formula, random_effects=False, pedigree=False):
     """'y ~ 1 + x + SNP(M, "geno.txt", "map.txt")' -> ParsedFormula (lhs, intercept, [GenomicTerm, ...]; .covariates = ['x']).
     random_effects=True also takes (1|g) terms (.random = ['g'], in formula order), as runLMEM does; without it they are refused, as
-    they were before the device sampled them."""
+    they were before the device sampled them.  pedigree=True also takes PED(col) terms (.ped = ['col'], in formula order; runLMEM
+    builds their A^-1 from userPedData); without it they are refused, as they were before makePed existed."""
     if "~" not in formula:
         raise ValueError("formula needs a '~'")
     lhs, rhs = [t.strip() for t in formula.split("~", 1)]
@@ -199,7 +203,7 @@ def parse_formula(formula, random_effects=False):
             cur += ch
     if cur.strip():
         terms.append(cur.strip())
-    intercept, snps, covs, rnd, order = False, [], [], [], []
+    intercept, snps, covs, rnd, order, ped = False, [], [], [], [], []
     for t in terms:
         m = re.fullmatch(r"\(?\s*1\s*\|\s*([A-Za-z_][A-Za-z_0-9]*)\s*\)?", t)
         if m and t.count("(") == t.count(")"):
@@ -221,6 +225,9 @@ def parse_formula(formula, random_effects=False):
             unq = [a.strip("\"'") for a in args]
             snps.append(GenomicTerm(unq[0], unq[1], unq[2] if len(unq) > 2 else ""))
             order.append(("snp", unq[0]))
+        elif pedigree and (mp := re.fullmatch(r"PED\(\s*([A-Za-z_][A-Za-z_0-9]*)\s*\)", t)):
+            ped.append(mp.group(1))  # PED(col): a random effect of every animal of the pedigree, K = A^-1 (src/prepMatVec.jl:136-153)
+            order.append(("ped", mp.group(1)))
         elif t.startswith("PED("):
             raise NotImplementedError(f"term '{t}': building A^-1 from a pedigree needs PedigreeBase (src/mme.jl:26-37, src/prepMatVec.jl:136-153), "
                                       "so PED terms stay on the reference's Julia path; its coarse seam hands the Ainv it built to the device")
@@ -232,7 +239,7 @@ def parse_formula(formula, random_effects=False):
         else:
             raise NotImplementedError(f"term '{t}': interactions / function terms stay on the reference's Julia path (StatsModels, "
                                       "src/prepMatVec.jl:150-165); use the fine seam (ngp_sweep_set) to combine them with the GPU sweep")
-    return ParsedFormula(lhs, intercept, snps, covs, rnd, order)
+    return ParsedFormula(lhs, intercept, snps, covs, rnd, order, ped)
 
 
 def random_levels(col):
@@ -267,6 +274,93 @@ def random_prior(VCV, g, q):
     df = 3.0 + 1.0                                               # src/mme.jl:261
     v = float(prior.v)
     return K, df, v * (df - 2.0) / df, v                         # src/mme.jl:265-272
+
+
+def makeA(s, d):
+    """The dense numerator relationship matrix by the tabular method (src/misc.jl:73-90): s / d are the 1-based positions of sire and dam
+    in the list, 0 = unknown, parents in front of their offspring.  A_ii = 1 + A[s_i, d_i] / 2; A_ij = (A[i, s_j] + A[i, d_j]) / 2 for
+    j > i.  The dense check of makePed's sparse A^-1 (O(n^2): small pedigrees only)."""
+    s = np.asarray(s, dtype=np.int64); d = np.asarray(d, dtype=np.int64)
+    n = len(s)
+    if len(d) != n or np.any(s < 0) or np.any(d < 0) or np.any(s > np.arange(n)) or np.any(d > np.arange(n)):
+        raise ValueError("makeA: sire / dam as 1-based positions of animals listed earlier, 0 = unknown")
+    A = np.zeros((n + 1, n + 1))                                  # (row / column n stands for the unknown parent: all zero)
+    si = np.where(s == 0, n, s - 1); di = np.where(d == 0, n, d - 1)
+    for i in range(n):
+        A[i, i] = 1.0 + A[si[i], di[i]] / 2.0
+        for j in range(i + 1, n):
+            A[i, j] = (A[i, si[j]] + A[i, di[j]]) / 2.0
+            A[j, i] = A[i, j]
+    return A[:n, :n].copy()
+
+
+def _read_ped_rows(path_or_rows):
+    if isinstance(path_or_rows, (str, os.PathLike)):
+        rows = []
+        with open(path_or_rows) as f:
+            for ln, line in enumerate(f, 1):
+                line = line.strip()
+                if not line or line.startswith("#"):
+                    continue
+                t = line.split()
+                if len(t) < 3:
+                    raise ValueError(f"pedigree file {path_or_rows}, line {ln}: ID Sire Dam expected")
+                rows.append((t[0], t[1], t[2]))
+        return rows
+    return [(str(a), str(b), str(c)) for a, b, c in path_or_rows]
+
+
+def makePed(path_or_rows, userIDs=None):
+    """(pedigree table, Ainv) from the reference's pedigree text -- `ID Sire Dam` per line, whitespace separated, `0` unknown, `#`
+    comment lines -- or from rows of such triples (src/misc.jl:98-115; PedigreeBase's part is done here and in ngp_pedigree_ainv).
+    The animals are put parents first by a stable topological order: an animal keeps its file position unless a parent comes later
+    (then the parent is moved in front of it).  Refused: duplicate IDs, a parent that is not listed, a cycle, and phenotyped IDs
+    (userIDs) outside the pedigree.  The table: dict(origID [n names in pedigree order], ID 1..n, Sire, Dam (1-based positions, 0
+    unknown), F inbreeding coefficients, pos {name: 0-based position}); Ainv: CSR arrays (k_ptr, k_col, k_val), columns ascending."""
+    rows = _read_ped_rows(path_or_rows)
+    if not rows:
+        raise ValueError("pedigree: no animal")
+    idx = {}
+    for k, (a, _, _) in enumerate(rows):
+        if a == "0":
+            raise ValueError("pedigree: an animal is called 0 (0 means unknown)")
+        if a in idx:
+            raise ValueError(f"pedigree: ID {a} is listed twice")
+        idx[a] = k
+    par = []
+    for a, sr, dm in rows:
+        for p in (sr, dm):
+            if p != "0" and p not in idx:
+                raise ValueError(f"pedigree: parent {p} of {a} is not listed as an animal")
+        par.append([idx[p] for p in (sr, dm) if p != "0"])
+    order, state = [], [0] * len(rows)                            # 0 new, 1 on the stack (its parents are being placed), 2 placed
+    for k0 in range(len(rows)):
+        if state[k0]:
+            continue
+        stack = [(k0, 0)]
+        state[k0] = 1
+        while stack:
+            k, nxt = stack.pop()
+            if nxt < len(par[k]):
+                stack.append((k, nxt + 1))
+                p = par[k][nxt]
+                if state[p] == 1:
+                    raise ValueError(f"pedigree: {rows[p][0]} is its own ancestor (a cycle)")
+                if state[p] == 0:
+                    state[p] = 1
+                    stack.append((p, 0))
+            else:
+                state[k] = 2
+                order.append(k)
+    newpos = {k: i for i, k in enumerate(order)}
+    orig = [rows[k][0] for k in order]
+    sire = np.array([0 if rows[k][1] == "0" else newpos[idx[rows[k][1]]] + 1 for k in order], dtype=np.int32)
+    dam = np.array([0 if rows[k][2] == "0" else newpos[idx[rows[k][2]]] + 1 for k in order], dtype=np.int32)
+    pos = {a: i for i, a in enumerate(orig)}
+    if userIDs is not None and not all(str(a) in pos for a in userIDs):
+        raise ValueError("ErrorException: phenotyed individuals are not a subset of pedigree")   # src/misc.jl:106, its words
+    F, Ainv = pedigree_ainv(sire, dam)
+    return dict(origID=orig, ID=np.arange(1, len(orig) + 1), Sire=sire, Dam=dam, F=F, pos=pos), Ainv
 
 
 def gblup_terms(snps, VCV, summaryStat=None):
@@ -556,17 +650,32 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     same seed) over ONE copy of the panel on the device -- one fused sweep launch per iteration where the engine serves it (the result's
     "fused" says whether it did; a warning otherwise)
     (ngp_share_panel + ngp_run_many), side by side otherwise; every chain is bit for bit the chain it is alone with that layout,
-    writes its own *Out files to outFolder/chain<c>/, and the returned means are pooled over the chains (res["chains"] holds each).
+    writes its own *Out files to outFolder/chain<c>/, and the returned means are pooled over the chains (res["chains"] holds each);
+    (6) with userPedData (a pedigree file, or rows of ID / Sire / Dam) the data stay in the caller's record order -- the reference
+    re-sorts the data frame by pedigree position; the levels of a PED(col) set are the animals in pedigree (parents-first) order either
+    way, and a record whose col is 0 (unknown: an all-zero row of Z in the reference) is refused.
     Returns a dict of posterior means taken from the on-device sums."""
-    if userPedData is not None and len(userPedData):
-        raise NotImplementedError("userPedData: pedigree effects stay on the Julia path (src/mme.jl:26-46)")
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
-    parsed = parse_formula(formula, random_effects=True)
+    parsed = parse_formula(formula, random_effects=True, pedigree=True)
     lhs, intercept, snps = parsed
-    if not snps:
+    has_ped = userPedData is not None and len(userPedData) > 0
+    if parsed.ped and not has_ped:
+        raise ValueError(f"PED({parsed.ped[0]}) needs userPedData: the pedigree file (ID Sire Dam), or its rows")
+    if not snps and not parsed.ped:
         raise ValueError("the accelerated path needs at least one SNP(...) term")
     y = np.asarray(userData[lhs], dtype=np.float64)
+    ped = None
+    if has_ped:   # makePed (src/misc.jl:98-115) once for all PED terms and all chains
+        ids = []
+        for col in parsed.ped:
+            c = [str(a) for a in np.asarray(userData[col]).tolist()]
+            if "0" in c:
+                raise NotImplementedError(f"PED({col}): a record whose {col} is 0 (unknown) has an all-zero row of Z in the reference; "
+                                          "ngp_add_random_set takes a level for every record, so such records are not on the accelerated path")
+            ids += c
+        table, Ainv = makePed(userPedData, ids)
+        ped = dict(table=table, Ainv=Ainv)
     # weighted residuals, E.str == "D" (src/mme.jl:71-75): w = inv.(d), set on the handle before its panel (the rows are scaled at upload)
     w_res = _residual_weights(VCV.get("e", Random("I", 100.0)), len(y))
     if w_res is not None and storage in ("u8", 1):
@@ -681,7 +790,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         return region_cache[name]
 
     built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
-                          gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0])
+                          gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0], ped=ped)
              for sc in samplers]
     sets, fixed_names = built[0]
     randoms = samplers[0].randoms
@@ -710,9 +819,10 @@ def _residual_weights(e_prior, N):
 
 
 def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
-                 gblup=None, k_owner=None):
+                 gblup=None, k_owner=None, ped=None):
     """Priors, fixed-effect sets, random-effect sets, marker sets, y and the schedule of ONE chain's handle (its panel is set); returns
-    (sets, fixed_names).  gblup: {term name: dict(M, prior)} of the GBLUP terms; k_owner: the chain whose dense K this one shares."""
+    (sets, fixed_names).  gblup: {term name: dict(M, prior)} of the GBLUP terms; k_owner: the chain whose dense K this one shares;
+    ped: dict(table, Ainv) of makePed when the model has userPedData."""
     # residual prior (src/mme.jl:63-94)
     e_prior = VCV.get("e", Random("I", 100.0))  # (a "D" structure's weights were set on the handle before its panel: runLMEM)
     e_df = 4.0
@@ -765,6 +875,29 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
             rid = smp.add_random_set_dense(None, N, K=Ksrc, df=rdf, scale=v * (rdf - 2.0) / rdf, varU0=v)   # src/mme.jl:265-272
             smp.randoms.append(dict(id=rid, g=g, key=g, levels=[f"Ind{i + 1}" for i in range(N)], q=N, files=(f"u{g}", f"varU{g}", g)))
             continue
+        if kind == "ped":   # PED(col): every animal of the pedigree is a level, K = A^-1 (src/prepMatVec.jl:136-153, src/mme.jl:26-46)
+            table = ped["table"]
+            level = np.array([table["pos"][str(a)] for a in np.asarray(userData[g]).tolist()], dtype=np.int32)
+            prior = VCV.get(g)
+            if prior is None:
+                prior = Random("I", 100.0)                           # src/mme.jl:40-44: the identity over the pedigree's levels
+            if not isinstance(prior, RandomEffectType):
+                raise ValueError(f"prior of PED({g}): Random(\"A\", v)")
+            if isinstance(prior.str, str) and prior.str == "A":
+                K = ped["Ainv"]
+            elif prior.str is None or (isinstance(prior.str, str) and prior.str in ("I", "")):
+                K = None
+            else:
+                raise NotImplementedError(f"PED({g}) with structure {prior.str!r}: \"A\" (the pedigree's) or \"I\" (src/mme.jl:28-33)")
+            rdf = 3.0 + 1.0                                          # src/mme.jl:261
+            v = float(prior.v)
+            n = len(table["origID"])
+            rid = smp.add_random_set(level, n, K=K, df=rdf, scale=v * (rdf - 2.0) / rdf, varU0=v)   # src/mme.jl:265-272
+            smp.randoms.append(dict(id=rid, g=g, key=g, levels=list(table["origID"]), q=n, files=(f"u{g}", f"varU{g}", g)))
+            continue
+        pr = VCV.get(f"1|{g}", VCV.get(f"(1|{g})"))
+        if ped is None and isinstance(pr, RandomEffectType) and isinstance(pr.str, str) and pr.str == "A":
+            raise ValueError(f"(1|{g}) with Random(\"A\", v) needs a pedigree: pass userPedData (and write the term as PED({g}))")
         level, names = random_levels(userData[g])
         K, rdf, rscale, v = random_prior(VCV, g, len(names))
         rid = smp.add_random_set(level, len(names), K=K, df=rdf, scale=rscale, varU0=v)

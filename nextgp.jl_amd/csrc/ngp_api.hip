@@ -17,6 +17,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <queue>
 #include <string>
 #include <thread>
 #include <vector>
@@ -108,6 +109,14 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     DevArray<double> d_scr;    // NGP_RS_ROWS x q scratch (ngp_random.h)
     uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
     std::shared_ptr<DenseK> dk;  // a dense K (ngp_add_random_set_dense): the blocked engine of ngp_dense.h instead of k_rand_gs / k_rand_var
+    // the level schedule of a CSR K with off-diagonal entries (ngp_random.h, k_rand_sched_*): rows sorted by (depth, row), and the launches
+    struct Launch { int wide; int d0, d1; long long r0, r1; };  // wide: the rows order[r0 .. r1) of depth d0; else the depths d0 .. d1 - 1 in one workgroup
+    DevArray<int> d_order;
+    DevArray<long long> d_dptr;
+    std::vector<Launch> plan;
+    int64_t ndepth = 0;
+    int sched_mode = 0;        // ngp_set_random_schedule: 0 automatic, 1 serial (k_rand_gs), 2 scheduled
+    bool scheduled() const { return sched_mode == 2 || (sched_mode == 0 && q > NGP_RS_AUTO_LEVELS_PER_DEPTH * ndepth); }
 };
 
 struct HLv {  // the variance model of one BayesLV marker set (src/mme.jl:418-439; kernels and state layout in ngp_logvar.h)
@@ -1139,7 +1148,18 @@ void launch_random(ngp_handle *h, int r, uint64_t it) {
                        (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag,
                        (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr,
                        (int)R.offdiag, (const DScal *)h->cm.d_scal, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
-    if (R.offdiag) {
+    if (R.offdiag && R.scheduled()) {  // the level schedule: one launch per wide depth, one per run of narrow depths, in depth order
+        for (const HRand::Launch &pl : R.plan) {
+            if (pl.wide)
+                hipLaunchKernelGGL(k_rand_sched_wide, dim3((unsigned)((pl.r1 - pl.r0 + 255) / 256)), dim3(256), 0, h->stream, q, (const long long *)R.d_kptr,
+                                   (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u.get(), (const double *)R.d_vu, R.d_scr.get(), (const int *)R.d_order,
+                                   pl.r0, pl.r1, (const unsigned *)h->cm.d_abort);
+            else
+                hipLaunchKernelGGL(k_rand_sched_fused, dim3(1), dim3(1024), 0, h->stream, q, (const long long *)R.d_kptr, (const int *)R.d_kcol,
+                                   (const double *)R.d_kval, R.d_u.get(), (const double *)R.d_vu, R.d_scr.get(), (const int *)R.d_order,
+                                   (const long long *)R.d_dptr, pl.d0, pl.d1, (const unsigned *)h->cm.d_abort);
+        }
+    } else if (R.offdiag) {
         const int use_lds = (size_t)q * sizeof(double) <= NGP_LDS_MAX;
         hipLaunchKernelGGL(k_rand_gs, dim3(1), dim3(64), use_lds ? (size_t)q * sizeof(double) : 0, h->stream, q, (const long long *)R.d_kptr,
                            (const int *)R.d_kcol, (const double *)R.d_kval, R.d_u, (const double *)R.d_vu, R.d_scr, use_lds, (const unsigned *)h->cm.d_abort);
@@ -3458,6 +3478,35 @@ int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const
     group_levels(h, level, q, lp, lr, lv, zpz);
     HRand R;
     R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = offdiag;
+    if (offdiag) {  // the level schedule (ngp_random.h): depths from the sorted rows, the rows by (depth, row), the launches of one step
+        std::vector<int> dep((size_t)q, 0), ord((size_t)q);
+        int maxd = 0;
+        for (int64_t l = 0; l < q; l++) {
+            int d = 0;
+            for (long long k = kp[(size_t)l]; k < kp[(size_t)l + 1] && kc[(size_t)k] < l; k++) d = std::max(d, dep[(size_t)kc[(size_t)k]] + 1);
+            dep[(size_t)l] = d;
+            maxd = std::max(maxd, d);
+        }
+        const int nd = maxd + 1;
+        std::vector<long long> dp((size_t)nd + 1, 0);
+        for (int64_t l = 0; l < q; l++) dp[(size_t)dep[(size_t)l] + 1]++;
+        for (int d = 0; d < nd; d++) dp[(size_t)d + 1] += dp[(size_t)d];
+        {
+            std::vector<long long> pos(dp.begin(), dp.end() - 1);
+            for (int64_t l = 0; l < q; l++) ord[(size_t)pos[(size_t)dep[(size_t)l]]++] = (int)l;
+        }
+        int run0 = -1;
+        for (int d = 0; d < nd; d++) {
+            if (dp[(size_t)d + 1] - dp[(size_t)d] > NGP_RS_FUSE_ROWS) {
+                if (run0 >= 0) R.plan.push_back({0, run0, d, dp[(size_t)run0], dp[(size_t)d]});
+                run0 = -1;
+                R.plan.push_back({1, d, d + 1, dp[(size_t)d], dp[(size_t)d + 1]});
+            } else if (run0 < 0) run0 = d;
+        }
+        if (run0 >= 0) R.plan.push_back({0, run0, nd, dp[(size_t)run0], dp[(size_t)nd]});
+        R.ndepth = nd;
+        if ((rc = upload(h, R.d_order, ord)) || (rc = upload(h, R.d_dptr, dp))) return rc;
+    }
     R.sig = bytes_digest(bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull, lv.data(), lv.size() * 4), kp.data(), kp.size() * 8), kc.data(),
                                       kc.size() * 4), kv.data(), kv.size() * 8);
     const double vu[2] = {varU0, 0.0};
@@ -3546,6 +3595,122 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
     HCHK(hipGetLastError());
     return check_abort(h);
     NGP_CATCH(h)
+}
+
+/* The Gauss-Seidel engine of a CSR random-effect set whose K has off-diagonal entries: 0 automatic, 1 serial (k_rand_gs), 2 level-scheduled
+ * (k_rand_sched_*).  Both engines do the same operations on the same values: the choice changes no bit of any result. */
+int32_t ngp_set_random_schedule(ngp_handle *h, int32_t set_id, int32_t mode) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    REQUIRE(mode >= 0 && mode <= 2, NGP_ERR_ARG, "random-effect schedule: 0 automatic, 1 serial, 2 level-scheduled");
+    HRand &R = h->mm.rnd[(size_t)set_id];
+    REQUIRE(!R.dk && R.offdiag, NGP_ERR_ARG, "random-effect schedule: only a CSR set whose K has off-diagonal entries runs a Gauss-Seidel engine "
+                                             "(a diagonal K draws every level on its own, a dense K runs the blocked engine)");
+    R.sched_mode = mode;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* engine: 0 none (diagonal or dense K), 1 serial, 2 level-scheduled -- the one in force; depths of the level schedule (1 for a diagonal K,
+ * 0 for a dense one); Gauss-Seidel launches per step with that engine.  Any pointer may be NULL. */
+int32_t ngp_get_random_schedule(ngp_handle *h, int32_t set_id, int32_t *engine, int64_t *depths, int64_t *launches) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    const HRand &R = h->mm.rnd[(size_t)set_id];
+    const bool gs = !R.dk && R.offdiag;
+    if (engine) *engine = !gs ? 0 : R.scheduled() ? 2 : 1;
+    if (depths) *depths = R.dk ? 0 : gs ? R.ndepth : 1;
+    if (launches) *launches = !gs ? 0 : R.scheduled() ? (int64_t)R.plan.size() : 1;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* A^-1 of a pedigree by Henderson's rules with inbreeding (host only, no device, no handle).  n animals, parents in front of their
+ * offspring; sire / dam are 1-based positions in the same list, 0 = unknown.  F by Meuwissen and Luo's walk up the ancestors of every
+ * animal (A_ii = sum_j L_ij^2 D_jj); then, per animal i with its known parents p (one listed twice counts twice):
+ *   d = 1 - sum_p (1 + F_p) / 4,  a = 1 / d,  K_ii += a,  K_ip += -a/2,  K_pi += -a/2,  K_pp' += a/4 for every pair (p, p')
+ * in animal order, (i, p) and (p, i) by the same additions: K is reproducible and exactly symmetric.  CSR out, columns ascending. */
+int32_t ngp_pedigree_ainv(int64_t n, const int32_t *sire, const int32_t *dam, double *f_out, int64_t *k_ptr, int32_t *k_col, double *k_val,
+                          int64_t cap, int64_t *nnz_out) {
+    NGP_TRY
+    ngp_handle *h = nullptr;  // (messages go where ngp_create's go: ngp_last_error(NULL))
+    REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && sire && dam, NGP_ERR_ARG, "pedigree: 1 <= n < 2^31 animals with their sires and dams");
+    REQUIRE(cap >= 0 && (cap == 0 || (k_col && k_val)), NGP_ERR_ARG, "pedigree: k_col and k_val hold cap entries");
+    for (int64_t i = 0; i < n; i++) {
+        REQUIRE(sire[i] >= 0 && (int64_t)sire[i] <= n && dam[i] >= 0 && (int64_t)dam[i] <= n, NGP_ERR_ARG, "pedigree: a parent is outside 0..n");
+        REQUIRE((int64_t)sire[i] != i + 1 && (int64_t)dam[i] != i + 1, NGP_ERR_ARG, "pedigree: an animal is its own parent");
+        REQUIRE((int64_t)sire[i] <= i && (int64_t)dam[i] <= i, NGP_ERR_ARG, "pedigree: parents must come in front of their offspring");
+    }
+    auto parents = [&](int64_t i, int64_t p[2]) { int np = 0; if (sire[i]) p[np++] = sire[i] - 1; if (dam[i]) p[np++] = dam[i] - 1; return np; };
+    // inbreeding: D_jj = 1 - sum_p (1 + F_p) / 4; ancestors of i from the youngest to the oldest, L_ij carried along
+    std::vector<double> F((size_t)n), D((size_t)n), L((size_t)n, 0.0);
+    std::priority_queue<int64_t> anc;
+    for (int64_t i = 0; i < n; i++) {
+        int64_t p[2];
+        const int np = parents(i, p);
+        double dd = 1.0;
+        for (int k = 0; k < np; k++) dd = dd - (1.0 + F[(size_t)p[k]]) / 4.0;
+        D[(size_t)i] = dd;
+        double aii = 0.0;
+        L[(size_t)i] = 1.0;
+        anc.push(i);
+        while (!anc.empty()) {
+            const int64_t j = anc.top();
+            anc.pop();
+            int64_t pj[2];
+            const int nj = parents(j, pj);
+            const double lj = L[(size_t)j];
+            for (int k = 0; k < nj; k++) {
+                if (L[(size_t)pj[k]] == 0.0) anc.push(pj[k]);  // (L of a listed ancestor is > 0: every contribution is)
+                L[(size_t)pj[k]] = L[(size_t)pj[k]] + 0.5 * lj;
+            }
+            aii = aii + lj * lj * D[(size_t)j];
+            L[(size_t)j] = 0.0;
+        }
+        F[(size_t)i] = aii - 1.0;
+    }
+    // structure: the columns each row is ever given, sorted and made unique
+    std::vector<int64_t> cnt((size_t)n + 1, 0);
+    auto each_entry = [&](auto &&fn) {  // every addition of Henderson's rules, in animal order: fn(row, column, animal, weight)
+        for (int64_t i = 0; i < n; i++) {
+            int64_t p[2];
+            const int np = parents(i, p);
+            fn(i, i, i, 1.0);
+            for (int k = 0; k < np; k++) { fn(i, p[k], i, -0.5); fn(p[k], i, i, -0.5); }
+            for (int k = 0; k < np; k++) for (int m = 0; m < np; m++) fn(p[k], p[m], i, 0.25);
+        }
+    };
+    each_entry([&](int64_t r, int64_t, int64_t, double) { cnt[(size_t)r + 1]++; });
+    for (int64_t i = 0; i < n; i++) cnt[(size_t)i + 1] += cnt[(size_t)i];
+    std::vector<int32_t> cols((size_t)cnt[(size_t)n]);
+    {
+        std::vector<int64_t> pos(cnt.begin(), cnt.end() - 1);
+        each_entry([&](int64_t r, int64_t c, int64_t, double) { cols[(size_t)pos[(size_t)r]++] = (int32_t)c; });
+    }
+    std::vector<int64_t> kp((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const auto b = cols.begin() + cnt[(size_t)i], e = cols.begin() + cnt[(size_t)i + 1];
+        std::sort(b, e);
+        kp[(size_t)i + 1] = kp[(size_t)i] + (std::unique(b, e) - b);
+    }
+    const int64_t nnz = kp[(size_t)n];
+    if (nnz_out) *nnz_out = nnz;
+    if (f_out) std::copy(F.begin(), F.end(), f_out);
+    if (k_ptr) std::copy(kp.begin(), kp.end(), k_ptr);
+    REQUIRE(cap >= nnz, NGP_ERR_ARG, "pedigree: cap is smaller than the number of entries of A^-1 (nnz_out holds it: call again)");
+    for (int64_t i = 0; i < n; i++) std::copy(cols.begin() + cnt[(size_t)i], cols.begin() + cnt[(size_t)i] + (kp[(size_t)i + 1] - kp[(size_t)i]), k_col + kp[(size_t)i]);
+    std::fill(k_val, k_val + nnz, 0.0);
+    each_entry([&](int64_t r, int64_t c, int64_t i, double w) {
+        const int32_t *b = k_col + kp[(size_t)r], *e = k_col + kp[(size_t)r + 1];
+        const double a = 1.0 / D[(size_t)i];
+        k_val[std::lower_bound(b, e, (int32_t)c) - k_col] += a * w;
+    });
+    return NGP_OK;
+    NGP_CATCH(nullptr)
 }
 
 /* Kept samples to a binary file WITHOUT stopping the chain (the reference appends text rows at every kept iteration,

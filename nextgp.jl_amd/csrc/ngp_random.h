@@ -7,6 +7,7 @@
 //   k_rand_levels   one 64-lane wave per level: Yi_l = (sum_{i in l} ycorr_i + zpz_l u_l) iVarE (ycorr untouched), lhs, 1/lhs, sd, the
 //                   keyed normal; a K without off-diagonal entries draws u_l right there, a general K leaves the terms to k_rand_gs
 //   k_rand_gs       general K: Gauss-Seidel in level order in ONE wave (only the sparse dot over the levels below l and the draw)
+//   k_rand_sched_*  the same Gauss-Seidel level-scheduled: the rows of equal depth side by side (a pedigree's A^-1: 10^5 rows, 10^2 depths)
 //   k_rand_update   ycorr_i -= du_{level(i)}  (s_i du under weighted residuals)
 //   k_rand_var      u'Ku in a fixed order, then varU = (scale df + u'Ku) / chi2(df + q)
 #pragma once
@@ -133,6 +134,68 @@ __global__ __launch_bounds__(64) void k_rand_gs(long long q, const long long *__
     if (use_lds) {
         __syncthreads();
         for (long long l = tid; l < q; l += 64) u[l] = su[l];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The same Gauss-Seidel, level-scheduled (DESIGN.md "Random-effect sets", the schedule).  depth(l) = 0 for a row without an entry
+// left of its diagonal, else 1 + max depth(c) over its columns c < l: every u_c (c < l) that row l reads belongs to a smaller
+// depth, and no row reads the u of another row of its own depth.  So the rows of one depth run side by side, one thread per row,
+// each doing the operations of k_rand_gs's loop body in the same order on the same values: the result is the same bits.
+//   order[dptr[d] .. dptr[d + 1])   the rows of depth d, ascending
+//   k_rand_sched_wide    one depth of more than NGP_RS_FUSE_ROWS rows: ceil(rows / 256) workgroups, the rows order[r0 .. r1)
+//   k_rand_sched_fused   a run of consecutive narrower depths d0 .. d1 - 1 in ONE workgroup of 1024 threads, a workgroup-scope
+//                        fence and __syncthreads() between two depths
+// The stream orders the launches; no launch waits for another workgroup.  u is read and written in global memory by many
+// threads in turn, hence neither const nor __restrict__ here.
+// ------------------------------------------------------------------------------------------
+#define NGP_RS_FUSE_ROWS 1024
+// the automatic choice of the engine (ngp_set_random_schedule, mode 0): scheduled when the set has more than this many levels per
+// depth, serial otherwise.  Measured (tools/random_gs_time.py): the serial walk costs 0.85 us per level with u in
+// LDS (1.1 us from global memory), a depth of the fused launch 1.4 - 2.2 us while it is a few rows wide; at 1.9 levels per depth the
+// two engines are 10 % apart, at 3.4 the scheduled one is 1.4 times faster
+#define NGP_RS_AUTO_LEVELS_PER_DEPTH 2
+
+__device__ __forceinline__ void rand_gs_row(long long l, long long q, const long long *__restrict__ kptr, const int *__restrict__ kcol,
+                                            const double *__restrict__ kval, double *u, double iVarU, double *scr) {
+    double dlo = 0.0;
+    for (long long k = kptr[l]; k < kptr[l + 1]; k++) {
+        const int c = kcol[k];
+        if (c < l) {
+            const double t = kval[k] * u[c];
+            dlo = dlo + t;
+        }
+    }
+    const double d = dlo + scr[NGP_RS_DHI * q + l];
+    const double t = d * iVarU;
+    const double rhs = scr[NGP_RS_YI * q + l] - t;
+    const double mean = scr[NGP_RS_INV * q + l] * rhs;
+    const double un = mean + scr[NGP_RS_TZ * q + l];
+    scr[NGP_RS_DU * q + l] = un - u[l];
+    u[l] = un;
+}
+
+__global__ __launch_bounds__(256) void k_rand_sched_wide(long long q, const long long *__restrict__ kptr, const int *__restrict__ kcol,
+                                                         const double *__restrict__ kval, double *u, const double *__restrict__ vu, double *scr,
+                                                         const int *__restrict__ order, long long r0, long long r1,
+                                                         const unsigned *__restrict__ abort_w) {
+    if (abort_w && *abort_w != 0u) return;
+    const long long i = r0 + (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= r1) return;
+    rand_gs_row((long long)order[i], q, kptr, kcol, kval, u, 1.0 / vu[0], scr);
+}
+
+__global__ __launch_bounds__(1024) void k_rand_sched_fused(long long q, const long long *__restrict__ kptr, const int *__restrict__ kcol,
+                                                           const double *__restrict__ kval, double *u, const double *__restrict__ vu, double *scr,
+                                                           const int *__restrict__ order, const long long *__restrict__ dptr, int d0, int d1,
+                                                           const unsigned *__restrict__ abort_w) {
+    if (abort_w && *abort_w != 0u) return;  // (uniform over the workgroup)
+    const double iVarU = 1.0 / vu[0];
+    for (int d = d0; d < d1; d++) {  // (uniform: every thread meets every barrier)
+        const long long r1 = dptr[d + 1];
+        for (long long i = dptr[d] + threadIdx.x; i < r1; i += 1024) rand_gs_row((long long)order[i], q, kptr, kcol, kval, u, iVarU, scr);
+        __threadfence_block();
+        __syncthreads();
     }
 }
 

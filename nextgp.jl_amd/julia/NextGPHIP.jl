@@ -262,6 +262,30 @@ function add_random_set!(h::Handle, level::Vector{Int32}, q::Integer, K, df::Flo
                    h.ptr, level, q, kp, kc, kv, df, scale, varU0, id))
     return id[]
 end
+# The Gauss-Seidel engine of a CSR set with off-diagonal K, e.g. a PED set's Ainv (ngp_set_random_schedule): 0 automatic, 1 serial,
+# 2 level-scheduled (rows of equal depth side by side).  The bits do not depend on it.  random_schedule: (engine in force, depths, launches).
+set_random_schedule!(h::Handle, set_id::Integer, mode::Integer) =
+    check(h, ccall((:ngp_set_random_schedule, LIB), Int32, (Ptr{Cvoid}, Int32, Int32), h.ptr, set_id, mode))
+function random_schedule(h::Handle, set_id::Integer)
+    e = Ref{Int32}(0); d = Ref{Int64}(0); n = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_random_schedule, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int64}, Ref{Int64}), h.ptr, set_id, e, d, n))
+    (engine = Int(e[]), depths = Int(d[]), launches = Int(n[]))
+end
+# A^-1 of a pedigree on the host (ngp_pedigree_ainv: Henderson's rules with inbreeding): sire / dam are 1-based positions in a list with
+# parents in front of their offspring, 0 = unknown.  Returns (F, k_ptr, k_col, k_val): CSR with 0-based columns, ascending within a row.
+function pedigree_ainv(sire::Vector{Int32}, dam::Vector{Int32})
+    n = length(sire)
+    length(dam) == n || error("pedigree: one sire and one dam per animal")
+    F = Vector{Float64}(undef, n); kp = Vector{Int64}(undef, n + 1); nnz = Ref{Int64}(0)
+    ccall((:ngp_pedigree_ainv, LIB), Int32, (Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Int64, Ref{Int64}),
+          n, sire, dam, F, kp, C_NULL, C_NULL, 0, nnz)                      # counts: refused for the cap, nnz set
+    nnz[] > 0 || error("ngp_pedigree_ainv: " * unsafe_string(ccall((:ngp_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    kc = Vector{Int32}(undef, nnz[]); kv = Vector{Float64}(undef, nnz[])
+    rc = ccall((:ngp_pedigree_ainv, LIB), Int32, (Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Int64, Ref{Int64}),
+               n, sire, dam, F, kp, kc, kv, nnz[], nnz)
+    rc == 0 || error("ngp_pedigree_ainv: " * unsafe_string(ccall((:ngp_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    (F, kp, kc, kv)
+end
 # A random-effect set over a DENSE q x q precision (ngp_add_random_set_dense): GBLUP's Z[z].iVarStr = inv(makeG(M)), which the shim's
 # caller has built already (src/prepMatVec.jl:122-126).  level === nothing: the identity incidence (record i is level i).  K is copied to
 # the device as it is (symmetric: row- and column-major are the same matrix) and sampled by the blocked engine, K read once per iteration.
