@@ -204,6 +204,32 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
  * per step; any pointer may be NULL. */
 int32_t ngp_set_random_schedule(ngp_handle *h, int32_t set_id, int32_t mode);
 int32_t ngp_get_random_schedule(ngp_handle *h, int32_t set_id, int32_t *engine, int64_t *depths, int64_t *launches);
+/* A correlated (Tuple) random-effect set (src/mme.jl:207-239; sampleZ!(::Tuple), src/functions.jl:75-89, 100-110, 503-506): k = 1..4
+ * components over ONE K with a k x k covariance -- (ID, Dam): direct and maternal genetic effects over one pedigree.  level is k x N,
+ * component-major: level[m N + i] in 0..q-1, or -1 for a record without a level in component m (an unknown dam: the reference's
+ * all-zero row of Z; ngp_add_random_set keeps refusing it).  K as for ngp_add_random_set, shared by the components.  scale and varU0
+ * are k x k row-major and refused unless finite and symmetric positive definite; the caller passes df = 3 + k and
+ * scale = v (df - k - 1) (src/mme.jl:265-271).  u and its sums are q x k with the k components of a level adjacent, varU and its sum
+ * k x k row-major.  Tuple sets share the id sequence of the other random-effect sets and are sampled in the order added;
+ * ngp_set_random_schedule / ngp_get_random_schedule apply (a tuple set always runs a Gauss-Seidel engine; its depths are those of the union
+ * of the patterns of K and of the record links between levels).  ngp_get_random / ngp_set_random / ngp_sample_random_set refuse a set
+ * with k > 1; the three functions below take any set (k = 1: a set of ngp_add_random_set or ngp_add_random_set_dense).
+ *
+ * THE STEP IS NOT THE REFERENCE'S LINES.  sampleZ!(::Tuple) forms Yi = Zp[i] ycorr on a ycorr that holds every component's Z u and
+ * subtracts only the K (x) inv(varU) couplings: a record of animal a with dam d leaves u_Dam[d] in animal a's right-hand side
+ * (Z_ID[:, a]'Z_Dam[:, d] != 0 is ignored).  The device draws the exact Gibbs conditional: K_lc (x) inv(varU) + W_lc / varE for c != l,
+ * W_lc[a][b] = sum of 1 (of w_i under weighted residuals) over the records with level_a = l and level_b = c.  The two agree exactly
+ * when no record links two different levels (all components on one level vector).  Per step: level sums and the k x k conditional per
+ * level, Gauss-Seidel in level order, ycorr -= sum_m du_m[level_m], varU ~ InverseWishart(df + q, scale + U K U').  Summation orders and
+ * draw keys: DESIGN.md, "Correlated random-effect sets".  A matrix that is not positive definite on the device shows as NaN in the
+ * chain, as for Tuple marker sets.  k = 1 gives ngp_add_random_set's chain bit for bit with scale_tuple = scale * df.  Packed posterior,
+ * sample records and snapshots carry u (q k) and varU (k k) where a (1|g) set has q and 1; the q word of the sample file's header and of the
+ * snapshot signature carries k - 1 in its bits from 32 up. */
+int32_t ngp_add_random_set_tuple(ngp_handle *h, const int32_t *level, int32_t k, int64_t q, const int64_t *k_ptr, const int32_t *k_col,
+                                 const double *k_val, double df, const double *scale, const double *varU0, int32_t *set_id);
+int32_t ngp_get_random_tuple(ngp_handle *h, int32_t set_id, double *u, double *sum_u, double *varU, double *sum_varU);
+int32_t ngp_set_random_tuple(ngp_handle *h, int32_t set_id, const double *u, const double *sum_u, const double *varU, const double *sum_varU);
+int32_t ngp_sample_random_set_tuple(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *u, double *varU);
 /* A^-1 of a pedigree on the host (no device, no handle; messages through ngp_last_error(NULL)): n animals, sire[i] / dam[i] the 1-based
  * positions of the parents in the same list, 0 = unknown, parents in front of their offspring (any other order, an index outside 0..n, an
  * animal that is its own parent: NGP_ERR_ARG).  Inbreeding coefficients F (f_out, n entries, may be NULL) by Meuwissen and Luo's method;

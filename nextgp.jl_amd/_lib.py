@@ -35,11 +35,16 @@ def _sample_header(f, path):
     return P, nvb, nsets, nfix, ncls, rec, sets, rq, lv
 
 
+def _rand_qk(w):
+    """(q, k) of a random-effect set from its header word: q, and k - 1 of a correlated (Tuple) set in the bits from 32 up."""
+    return int(w) & 0xFFFFFFFF, (int(w) >> 32) + 1
+
+
 def _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv):
     """Where the fields of a sample record lie (the record: csrc/ngp_state.h, sample_layout): (name -> (first double, doubles) in record
     order, doubles of the record in front of the delta bytes).  u<i> / lv<i> are the words of random-effect set i / BayesLV set i."""
     at, o = {}, 0
-    for name, n in ([("iter", 1), ("varE", 1), ("b", 1), ("b_fixed", nfix)] + [(f"u{i}", q) for i, q in enumerate(rq)] + [("varU", len(rq)),
+    for name, n in ([("iter", 1), ("varE", 1), ("b", 1), ("b_fixed", nfix)] + [(f"u{i}", q * k) for i, (q, k) in enumerate(map(_rand_qk, rq))] + [("varU", sum(k * k for _, k in map(_rand_qk, rq))),
                     ("beta", P), ("varBeta", nvb), ("piHat", 2 * nsets), ("class_pi", ncls)] + [(f"lv{i}", LV_WORDS) for i in range(len(lv))]):
         at[name] = (o, n); o += n
     return at, o
@@ -59,7 +64,8 @@ def _sample_record(d, at, rq, lv):
 def read_sample_file(path):
     """Binary sample file of ngp_set_sample_file -> dict(iter[n], varE[n], b[n], b_fixed[n, nfix], beta[n, P], varBeta[n, nvb], piHat[n, 2 nsets],
     class_pi[n, nclass], delta[n, P] (uint8), sets=[dict(method, K, col0, ncol, nvb, tk)], u=[[n, q] per random-effect set], varU[n, nrand],
-    lv_c=[[n, ncov] per BayesLV set], lv_varZeta[n, nlv])."""
+    lv_c=[[n, ncov] per BayesLV set], lv_varZeta[n, nlv]).  A correlated (Tuple) random-effect set of k components has u [n, q k] (the
+    components of a level adjacent) and k k words in varU (row-major, in set order)."""
     with open(path, "rb") as f:
         P, nvb, nsets, nfix, ncls, rec, sets, rq, lv = _sample_header(f, path)
         raw = np.frombuffer(f.read(), dtype=np.uint8)
@@ -149,6 +155,7 @@ SYMBOLS = [
     "ngp_grm_begin", "ngp_grm_columns_f64", "ngp_grm_columns_f32", "ngp_grm_columns_u8", "ngp_grm_end", "ngp_grm_get", "ngp_grm_invert",
     "ngp_add_random_set_dense", "ngp_set_records",
     "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
+    "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
 ]
 
 _lib = None
@@ -540,6 +547,54 @@ class Sampler:
         vu = C.c_double(varU)
         self._chk(self.L.ngp_sample_random_set(self.h, C.c_int32(set_id), C.c_double(varE), _p(ycorr, C.c_double), _p(u, C.c_double), C.byref(vu)))
         return vu.value
+
+    # ---- correlated (Tuple) random-effect sets: (ID, Dam), direct and maternal effects over one pedigree ----
+    def add_random_set_tuple(self, levels, q, K=None, df=None, scale=None, varU0=None):
+        """Correlated random-effect set (src/mme.jl:207-239): levels is k x N, one row per component, -1 for a record without a level in
+        that component (an unknown dam); K the shared precision as for add_random_set; varU0 the k x k starting covariance (symmetric
+        positive definite); df defaults to 3 + k and scale to varU0 (df - k - 1) (src/mme.jl:265-271).  u is q x k, varU k x k.  The
+        step draws the exact Gibbs conditional, not the reference's lines (include/nextgp_hip.h).  Returns the set id."""
+        lv = np.ascontiguousarray(np.atleast_2d(np.asarray(levels)), dtype=np.int32)
+        k = lv.shape[0]
+        if lv.ndim != 2 or not 1 <= k <= 4 or lv.shape[1] != self.N:
+            raise ValueError("levels: k x N with k in 1..4")
+        V = np.ascontiguousarray(np.asarray(varU0, dtype=np.float64).reshape(k, k))
+        if df is None:
+            df = 3.0 + k
+        S = V * (df - k - 1.0) if scale is None else np.asarray(scale, dtype=np.float64).reshape(k, k)
+        S = np.ascontiguousarray(S)
+        kp, kc, kv = k_csr(K) if K is not None else (None, None, None)
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_random_set_tuple(self.h, _p(lv, C.c_int32), C.c_int32(k), C.c_int64(int(q)), _p(kp, C.c_int64), _p(kc, C.c_int32),
+                                                  _p(kv, C.c_double), C.c_double(df), _p(S, C.c_double), _p(V, C.c_double), C.byref(sid)))
+        self.rand_q = getattr(self, "rand_q", []) + [int(q)]
+        self.rand_k = getattr(self, "rand_k", {})
+        self.rand_k[sid.value] = k
+        return sid.value
+
+    def _rand_k(self, set_id):
+        return getattr(self, "rand_k", {}).get(set_id, 1)
+
+    def get_random_tuple(self, set_id):
+        """dict(u [q, k], sum_u [q, k], varU [k, k], sum_varU [k, k]) of any random-effect set (k = 1 for a (1|g) set)."""
+        q, k = self.rand_q[set_id], self._rand_k(set_id)
+        u, su, v, sv = np.empty((q, k)), np.empty((q, k)), np.empty((k, k)), np.empty((k, k))
+        self._chk(self.L.ngp_get_random_tuple(self.h, C.c_int32(set_id), _p(u, C.c_double), _p(su, C.c_double), _p(v, C.c_double), _p(sv, C.c_double)))
+        return dict(u=u, sum_u=su, varU=v, sum_varU=sv)
+
+    def set_random_tuple(self, set_id, u=None, sum_u=None, varU=None, sum_varU=None):
+        """Restore parts of a set's state (None: left as it is); shapes as get_random_tuple returns them."""
+        q, k = self.rand_q[set_id], self._rand_k(set_id)
+        arr = lambda x, shape: None if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(shape))
+        a, b, v, sv = arr(u, (q, k)), arr(sum_u, (q, k)), arr(varU, (k, k)), arr(sum_varU, (k, k))
+        self._chk(self.L.ngp_set_random_tuple(self.h, C.c_int32(set_id), _p(a, C.c_double), _p(b, C.c_double), _p(v, C.c_double), _p(sv, C.c_double)))
+
+    def sample_random_set_tuple(self, set_id, varE, ycorr, u, varU):
+        """Fine seam (sampleZ!(::Tuple) with the exact conditional): ycorr (N), u (q x k) and varU (k x k) are updated in place."""
+        q, k = self.rand_q[set_id], self._rand_k(set_id)
+        for x, n in ((ycorr, self.N), (u, q * k), (varU, k * k)):
+            assert x.dtype == np.float64 and x.flags.c_contiguous and x.size == n
+        self._chk(self.L.ngp_sample_random_set_tuple(self.h, C.c_int32(set_id), C.c_double(varE), _p(ycorr, C.c_double), _p(u, C.c_double), _p(varU, C.c_double)))
 
     def set_random_schedule(self, set_id, mode):
         """Gauss-Seidel engine of a CSR set with off-diagonal K: 0 / "auto", 1 / "serial", 2 / "scheduled" (the bits do not depend on it)."""

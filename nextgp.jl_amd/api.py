@@ -15,8 +15,8 @@ Same names, argument meaning and output files as the reference, so a model scrip
     makePed(pedigree, ids) / makeA(s, d)                makePed(path_or_rows, ids) / makeA(s, d)               src/misc.jl:73-115
 
 Interpreted here: the response, the intercept `1`, covariate / factor columns (optionally grouped by `blockThese`), `(1|g)` random
-effects, `PED(col)` pedigree effects (with `userPedData`) and `SNP(...)` terms.  Interactions, correlated (Tuple) random effects,
-BayesRC are outside the accelerated path and raise NotImplementedError naming the reference code that handles them.
+effects, `PED(col)` pedigree effects (with `userPedData`), correlated (Tuple) pedigree effects -- a VCV key ("ID", "Dam") with a k x k
+covariance -- and `SNP(...)` terms.  Interactions and BayesRC are outside the accelerated path and raise NotImplementedError naming the reference code that handles them.
 All arithmetic happens in libnextgp_hip.so; this file only parses, reshapes and writes files.
 """
 import os
@@ -158,7 +158,8 @@ def lv_design_matrix(f, covariates):
 
 
 def Random(str, v, type=1):
-    return RandomEffectType(str, float(v), type)
+    """v: the variance, or the k x k covariance matrix of a correlated (Tuple) random effect (src/runTime.jl:135-146)."""
+    return RandomEffectType(str, float(v) if np.ndim(v) == 0 else np.array(v, dtype=np.float64), type)
 
 
 def SNP(name, path, map=""):
@@ -570,6 +571,35 @@ def _rd_files(rd):
     return rd["files"] if "files" in rd else random_file_names(rd["g"])
 
 
+def _rd_k(rd):
+    return len(rd["members"]) if "members" in rd else 1
+
+
+def _rd_headers(rd):
+    """[(file, header fields)] of a random-effect set.  A correlated (Tuple) set writes one u<member> file per component, each headed by
+    the levels, and ONE varU file named as Julia prints the key, varU(:ID, :Dam), headed ID_Dam_1 .. ID_Dam_k^2 (src/mme.jl:557-563)."""
+    if "members" not in rd:
+        un, vn, vh = _rd_files(rd)
+        return [(un, rd["levels"]), (vn, [vh])]
+    mem, k = rd["members"], len(rd["members"])
+    return [(f"u{m}", rd["levels"]) for m in mem] + [(_tuple_var_file(mem), ["_".join(mem) + f"_{i + 1}" for i in range(k * k)])]
+
+
+def _tuple_var_file(members):
+    return "varU(" + ", ".join(f":{m}" for m in members) + ")"
+
+
+def _rd_rows(rd, u, varU):
+    """[(file, fields)] of one kept sample of a random-effect set: u (q, or q x k flat with the components of a level adjacent) and varU
+    (one value, or k x k row-major; written column by column: hcat(reduce(hcat, varU)...), src/samplers.jl:63-74)."""
+    if "members" not in rd:
+        un, vn, _ = _rd_files(rd)
+        return [(un, _fmt(u)), (vn, _fmt(varU))]
+    mem, k = rd["members"], len(rd["members"])
+    U = np.asarray(u, dtype=np.float64).reshape(-1, k)
+    return [(f"u{m}", _fmt(U[:, c])) for c, m in enumerate(mem)] + [(_tuple_var_file(mem), _fmt(np.asarray(varU, dtype=np.float64).reshape(k, k).T.ravel()))]
+
+
 def _var_names(s):
     """Header of var<set>Out: reg_r (src/mme.jl:593-595); for correlated sets one column per entry of the region's k x k matrix."""
     if s["k"] > 1:
@@ -608,10 +638,12 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
             n += 1
             row("b", (_fmt(S["b"]) if intercept else []) + (_fmt(S["b_fixed"]) if has_fixed else []))
             row("varE", _fmt(S["varE"]))
+            vu_off = 0
             for r, rd in enumerate(randoms):                 # src/samplers.jl:60-75
-                un, vn, _ = _rd_files(rd)
-                row(un, _fmt(S["u"][r]))
-                row(vn, _fmt(S["varU"][r]))
+                kk = _rd_k(rd) ** 2
+                for name, fields in _rd_rows(rd, S["u"][r], S["varU"][vu_off:vu_off + kk]):
+                    row(name, fields)
+                vu_off += kk
             vb_off, cls_off = 0, 0
             for k, s in enumerate(sets):
                 K = len(s["prior"].pi) if isinstance(s["prior"], BayesRType) else 0
@@ -654,6 +686,12 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     (6) with userPedData (a pedigree file, or rows of ID / Sire / Dam) the data stay in the caller's record order -- the reference
     re-sorts the data frame by pedigree position; the levels of a PED(col) set are the animals in pedigree (parents-first) order either
     way, and a record whose col is 0 (unknown: an all-zero row of Z in the reference) is refused.
+    (7) correlated (Tuple) random effects -- VCV={("ID", "Dam"): Random("A", V)} with V a k x k covariance over the PED terms named, the
+    direct-maternal model; a 0 in such a column is a record without a level -- are drawn from the EXACT Gibbs conditional: the
+    reference's sampleZ!(::Tuple) leaves Z_ID'Z_Dam u_Dam of the other levels in a level's right-hand side (src/functions.jl:81-82), the
+    device subtracts it ("Correlated random-effect sets").  The two agree when no record links two different levels.  One
+    u<member>Out file per component and one varU(:ID, :Dam)Out (the matrix column by column); res["random"][("ID", "Dam")] holds u
+    (k x q), varU (k x k) and levels.  Refused: a GBLUP term or a (1|g) term inside a tuple, summaryStat on a tuple.
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -668,14 +706,18 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     ped = None
     if has_ped:   # makePed (src/misc.jl:98-115) once for all PED terms and all chains
         ids = []
+        ped_tuples = _random_tuples(VCV, parsed, summaryStat)
+        in_ped_tuple = {m for key in ped_tuples for m in key}
         for col in parsed.ped:
             c = [str(a) for a in np.asarray(userData[col]).tolist()]
+            if col in in_ped_tuple:   # a 0 in a tuple's column is a record without a level (ngp_add_random_set_tuple, level -1)
+                c = [a for a in c if a != "0"]
             if "0" in c:
                 raise NotImplementedError(f"PED({col}): a record whose {col} is 0 (unknown) has an all-zero row of Z in the reference; "
                                           "ngp_add_random_set takes a level for every record, so such records are not on the accelerated path")
             ids += c
         table, Ainv = makePed(userPedData, ids)
-        ped = dict(table=table, Ainv=Ainv)
+        ped = dict(table=table, Ainv=Ainv, tuples=ped_tuples)
     # weighted residuals, E.str == "D" (src/mme.jl:71-75): w = inv.(d), set on the handle before its panel (the rows are scaled at upload)
     w_res = _residual_weights(VCV.get("e", Random("I", 100.0)), len(y))
     if w_res is not None and storage in ("u8", 1):
@@ -715,7 +757,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     # draw their k effects together (src/functions.jl:140-154).  On the device the k columns of a locus sit side by side, from a
     # 64-column boundary on (ngp_add_marker_set_tuple): the panel is assembled accordingly, everything else in formula order.
     by_name = {t.name: i for i, t in enumerate(snps)}
-    tuples = [key for key in VCV if isinstance(key, tuple)]
+    tuples = [key for key in VCV if isinstance(key, tuple) and not (ped and key in ped["tuples"])]
     in_tuple = {}
     for key in tuples:
         if not all(nm in by_name for nm in key):
@@ -800,6 +842,40 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     return _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
 
 
+def _random_tuples(VCV, parsed, summaryStat):
+    """The VCV keys that are tuples of PED(col) terms, e.g. ("ID", "Dam"): correlated random effects over one pedigree with a k x k
+    covariance (src/mme.jl:207-239), checked.  Tuples of SNP terms are correlated MARKER sets and are not listed here."""
+    out = []
+    for key in VCV:
+        if not isinstance(key, tuple) or not any(m in parsed.ped for m in key):
+            continue
+        if any(m in {t.name for t in parsed[2]} for m in key):   # (a SNP term among the members: gblup_terms / the marker tuples refuse it)
+            continue
+        for m in key:
+            if m in parsed.random or str(m).replace(" ", "").strip("()").startswith("1|"):
+                raise NotImplementedError(f"VCV key {key}: a (1|g) term inside a correlated (Tuple) random effect; the reference accepts Symbols only "
+                                          "(isa(zSet, Tuple{Vararg{Symbol}}), src/mme.jl:207): write the member as PED(col)")
+            if m not in parsed.ped:
+                raise ValueError(f"correlated random effects {key}: every member needs its PED(...) term")
+        k = len(key)
+        if not 2 <= k <= 4 or len(set(key)) != k:
+            raise ValueError(f"correlated random effects {key}: 2..4 different PED terms")
+        if key in summaryStat or any(m in summaryStat for m in key):
+            raise ValueError("Not available to use summary statistics in correlated effects")   # src/mme.jl:233-235
+        prior = VCV[key]
+        if not isinstance(prior, RandomEffectType) or np.shape(prior.v) != (k, k):
+            raise ValueError(f"prior of {key}: Random(\"A\", V) with V the {k} x {k} covariance matrix")
+        if not (prior.str is None or (isinstance(prior.str, str) and prior.str in ("A", "I", ""))):
+            raise NotImplementedError(f"correlated random effects {key} with structure {prior.str!r}: \"A\" (the pedigree's) or \"I\" (src/mme.jl:28-33)")
+        for m in key:
+            if m in VCV:
+                raise ValueError(f"PED({m}) has a prior of its own and is a member of {key}: one or the other")
+        out.append(key)
+    if len({m for key in out for m in key}) != sum(len(key) for key in out):
+        raise ValueError("a PED term may be a member of one correlated (Tuple) random effect only")
+    return out
+
+
 def _residual_weights(e_prior, N):
     """Residual structure of Random(str, v) under key "e" (src/mme.jl:63-79): None for "I" (or empty), else the weights
     w = 1 ./ d of a "D" structure given as the length-N vector d (E.iVarStr = inv.(str), the same IEEE division)."""
@@ -874,6 +950,22 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
                 Ksrc = (k_owner, [rd["id"] for rd in k_owner.randoms if rd.get("key") == g][0])
             rid = smp.add_random_set_dense(None, N, K=Ksrc, df=rdf, scale=v * (rdf - 2.0) / rdf, varU0=v)   # src/mme.jl:265-272
             smp.randoms.append(dict(id=rid, g=g, key=g, levels=[f"Ind{i + 1}" for i in range(N)], q=N, files=(f"u{g}", f"varU{g}", g)))
+            continue
+        if kind == "ped" and any(g in key for key in ped["tuples"]):
+            # a correlated (Tuple) set, (ID, Dam): k PED terms over one K with a k x k covariance (src/mme.jl:207-239), placed where
+            # its first member stands in the formula.  The device draws the exact Gibbs conditional, not the reference's lines
+            # (include/nextgp_hip.h, ngp_add_random_set_tuple).
+            key = [key for key in ped["tuples"] if g in key][0]
+            if g != [m for _, m in (parsed.order or []) if m in key][0]:
+                continue
+            table, prior, k = ped["table"], VCV[key], len(key)
+            levels = np.array([[table["pos"][str(a)] if str(a) != "0" else -1 for a in np.asarray(userData[m]).tolist()] for m in key], dtype=np.int32)
+            K = ped["Ainv"] if isinstance(prior.str, str) and prior.str == "A" else None
+            rdf = 3.0 + k                                            # src/mme.jl:265
+            V = np.asarray(prior.v, dtype=np.float64)
+            n = len(table["origID"])
+            rid = smp.add_random_set_tuple(levels, n, K=K, df=rdf, scale=V * (rdf - k - 1.0), varU0=V)   # src/mme.jl:271
+            smp.randoms.append(dict(id=rid, g=key[0], key=key, members=list(key), levels=list(table["origID"]), q=n))
             continue
         if kind == "ped":   # PED(col): every animal of the pedigree is a level, K = A^-1 (src/prepMatVec.jl:136-153, src/mme.jl:26-46)
             table = ped["table"]
@@ -1005,10 +1097,9 @@ def _write_headers(outFolder, sets, fixed_names, randoms=()):
     """Header rows of the *Out files (src/mme.jl:543-595)."""
     _out(outFolder, "b", fixed_names)
     _out(outFolder, "varE", ["e"])
-    for rd in randoms:   # src/mme.jl:548-556; the u header lists the levels in the order of u (random_levels)
-        un, vn, vh = _rd_files(rd)
-        _out(outFolder, un, rd["levels"])
-        _out(outFolder, vn, [vh])
+    for rd in randoms:   # src/mme.jl:548-563; the u header lists the levels in the order of u (random_levels)
+        for name, fields in _rd_headers(rd):
+            _out(outFolder, name, fields)
     for s in sets:
         names = [f"M{i + 1}" for i in range(s["P"])]  # src/prepMatVec.jl:131
         for nm in s["members"]:
@@ -1038,10 +1129,9 @@ def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin,
             _out(outFolder, "b", (_fmt(st["b"]) if intercept else []) + (_fmt(smp.get_fixed()["b"]) if len(fixed_names) > int(intercept) else []))
             _out(outFolder, "varE", _fmt(st["varE"]))
             for rd in randoms:
-                un, vn, _ = _rd_files(rd)
-                rr = smp.get_random(rd["id"])
-                _out(outFolder, un, _fmt(rr["u"]))
-                _out(outFolder, vn, _fmt(rr["varU"]))
+                rr = smp.get_random_tuple(rd["id"])
+                for name, fields in _rd_rows(rd, rr["u"], rr["varU"]):
+                    _out(outFolder, name, fields)
             vb_off = 0
             for k, s in enumerate(sets):
                 for m, nm in enumerate(s["members"]):
@@ -1088,6 +1178,10 @@ def _posterior_means(smp, sets, fixed_names, intercept, randoms=()):
         vb_off += s["nvb"]
     res["random"] = {}
     for rd in randoms:   # posterior means of u (levels in random_levels order) and varU, keyed as Julia prints the term
+        if "members" in rd:   # a correlated (Tuple) set: u is k x q (one row per member, as the reference holds it), varU k x k
+            rr = smp.get_random_tuple(rd["id"])
+            res["random"][rd["key"]] = dict(u=rr["sum_u"].T / n, varU=rr["sum_varU"] / n, levels=rd["levels"])
+            continue
         rr = smp.get_random(rd["id"])
         res["random"][rd.get("key", f"1 | {rd['g']}")] = dict(u=rr["sum_u"] / n, varU=rr["sum_varU"] / n, levels=rd["levels"])
     res["sampler"] = smp
@@ -1105,6 +1199,6 @@ def _pool_results(results):
                   sampler=results[0]["sampler"], samplers=[r["sampler"] for r in results])
     for nm in results[0]["sets"]:
         pooled["sets"][nm] = {k: avg(lambda r, k=k: r["sets"][nm][k]) for k in results[0]["sets"][nm]}
-    pooled["random"] = {nm: dict(u=avg(lambda r: r["random"][nm]["u"]), varU=float(avg(lambda r: r["random"][nm]["varU"])),
+    pooled["random"] = {nm: dict(u=avg(lambda r: r["random"][nm]["u"]), varU=(lambda v: float(v) if np.ndim(v) == 0 else v)(avg(lambda r: r["random"][nm]["varU"])),
                                  levels=results[0]["random"][nm]["levels"]) for nm in results[0].get("random", {})}
     return pooled

@@ -14,7 +14,9 @@
 #include <condition_variable>
 #include <cstddef>
 #include <cstring>
+#include <array>
 #include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -25,6 +27,7 @@
 #include "../../include/nextgp_hip.h"
 #include "ngp_kernels.h"
 #include "ngp_random.h"
+#include "ngp_random_tuple.h"
 #include "ngp_dense.h"
 #include "ngp_logvar.h"
 #include "ngp_sweep_args.h"
@@ -98,15 +101,22 @@ struct Grm {
 
 struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled after the fixed-effect sets (src/samplers.jl:43-46)
     int64_t q = 0;
+    int tk = 1;                // components: 1, or the k of a correlated (Tuple) set (ngp_add_random_set_tuple; kernels in ngp_random_tuple.h)
     double df = 0.0, scale = 0.0, varU0 = 0.0;
+    double sdf = 0.0;          // tk = 1: scale * df (k_rand_var), the product formed once on the host
+    std::vector<double> scaleM, varU0M;  // tk x tk, row-major (tk = 1: sdf and varU0)
     bool offdiag = false;      // K has entries off its diagonal: Gauss-Seidel (k_rand_gs); otherwise every level is drawn on its own
     uint64_t fine_calls = 0;   // ngp_sample_random_set calls (their iteration key, as ngp_sweep_set's)
     DevArray<long long> d_lptr, d_kptr;  // records of level l: d_lrows[d_lptr[l] .. d_lptr[l + 1]); CSR of K
     DevArray<int> d_lrows, d_level, d_kcol;
     DevArray<double> d_kval, d_kdiag, d_zpz;
-    DevArray<double> d_u, d_sum_u;
-    DevArray<double> d_vu;     // [varU, sum_varU]
-    DevArray<double> d_scr;    // NGP_RS_ROWS x q scratch (ngp_random.h)
+    DevArray<double> d_u, d_sum_u;  // q x tk, the components of a level adjacent
+    DevArray<double> d_vu;     // [varU, sum_varU], tk x tk each
+    DevArray<double> d_scr;    // NGP_RS_ROWS x q scratch (ngp_random.h); a tuple set: tup_scr_len doubles (ngp_random_tuple.h)
+    // a tuple set (tk > 1): d_lptr / d_lrows / d_level per component; the W blocks of the header: diagonal ones dense, the others CSR
+    DevArray<long long> d_wptr;
+    DevArray<int> d_wcol;
+    DevArray<double> d_wd, d_wval, d_scaleM;
     uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
     std::shared_ptr<DenseK> dk;  // a dense K (ngp_add_random_set_dense): the blocked engine of ngp_dense.h instead of k_rand_gs / k_rand_var
     // the level schedule of a CSR K with off-diagonal entries (ngp_random.h, k_rand_sched_*): rows sorted by (depth, row), and the launches
@@ -118,6 +128,9 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     int sched_mode = 0;        // ngp_set_random_schedule: 0 automatic, 1 serial (k_rand_gs), 2 scheduled
     bool scheduled() const { return sched_mode == 2 || (sched_mode == 0 && q > NGP_RS_AUTO_LEVELS_PER_DEPTH * ndepth); }
 };
+// q of a set as the sample file's header and the snapshot signature carry it: q, and k - 1 of a tuple set in the bits from 32 up
+// (q < 2^31; a set of one component writes the word it always wrote)
+inline int64_t rand_q_word(const HRand &R) { return R.q | ((int64_t)(R.tk - 1) << 32); }
 
 struct HLv {  // the variance model of one BayesLV marker set (src/mme.jl:418-439; kernels and state layout in ngp_logvar.h)
     int set = -1;              // its marker set
@@ -1124,6 +1137,39 @@ void launch_tinv(ngp_handle *h) {  // (sync_linear_blocks has run for this call'
 void launch_random(ngp_handle *h, int r, uint64_t it) {
     HRand &R = h->mm.rnd[(size_t)r];
     const long long q = (long long)R.q;
+    if (R.tk > 1) {  // a correlated (Tuple) set: ngp_random_tuple.h
+        const int k = R.tk;
+        const unsigned *ab = (const unsigned *)h->cm.d_abort;
+        const DScal *sc = (const DScal *)h->cm.d_scal;
+        const long long *kp = R.d_kptr, *wp = R.d_wptr;
+        const int *kc = R.d_kcol, *wc = R.d_wcol;
+        const double *kv = R.d_kval, *wv = R.d_wval;
+        const TupScr T = tup_scr(R.d_scr.get(), q, k);
+        hipLaunchKernelGGL(k_tup_prep, dim3(1), dim3(64), 0, h->stream, k, (const double *)R.d_vu, T.sig, ab);
+        const int lpb = 4 / k;
+        hipLaunchKernelGGL(k_tup_levels, dim3((unsigned)((q + lpb - 1) / lpb)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, (const double *)h->cm.d_rs, q,
+                           k, (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_wd, (const double *)R.d_kdiag, kp, kc, kv,
+                           (const double *)R.d_u, R.d_scr.get(), sc, r, h->seed, (uint64_t)h->chain, it, ab);
+        if (R.scheduled()) {  // the level schedule: one launch per wide depth, one per run of narrow depths, in depth order
+            for (const HRand::Launch &pl : R.plan) {
+                if (pl.wide)
+                    hipLaunchKernelGGL(k_tup_sched_wide, dim3((unsigned)((pl.r1 - pl.r0 + 255) / 256)), dim3(256), 0, h->stream, q, k, kp, kc, kv, wp, wc, wv,
+                                       R.d_u.get(), R.d_scr.get(), sc, (const int *)R.d_order, pl.r0, pl.r1, ab);
+                else
+                    hipLaunchKernelGGL(k_tup_sched_fused, dim3(1), dim3(1024), 0, h->stream, q, k, kp, kc, kv, wp, wc, wv, R.d_u.get(), R.d_scr.get(), sc,
+                                       (const int *)R.d_order, (const long long *)R.d_dptr, pl.d0, pl.d1, ab);
+            }
+        } else {
+            const size_t ub = (size_t)q * (size_t)k * sizeof(double);
+            const int use_lds = ub <= NGP_LDS_MAX;
+            hipLaunchKernelGGL(k_tup_gs, dim3(1), dim3(64), use_lds ? ub : 0, h->stream, q, k, kp, kc, kv, wp, wc, wv, R.d_u.get(), R.d_scr.get(), sc, use_lds, ab);
+        }
+        hipLaunchKernelGGL(k_tup_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr, (const double *)h->cm.d_rs, (long long)h->N, k,
+                           (const int *)R.d_level, (const double *)T.du, ab);
+        hipLaunchKernelGGL(k_tup_var, dim3(1), dim3(1024), 0, h->stream, q, k, kp, kc, kv, (const double *)R.d_u, R.d_vu.get(), R.df, (const double *)R.d_scaleM, r,
+                           h->seed, (uint64_t)h->chain, it, ab);
+        return;
+    }
     if (R.dk) {  // dense K: the blocked engine (ngp_dense.h), one launch per block of 64 levels between the level terms and the ycorr update
         const double *K = R.dk->K;
         const long long ld = (long long)R.dk->ld;
@@ -1167,7 +1213,7 @@ void launch_random(ngp_handle *h, int r, uint64_t it) {
     hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr, (const double *)h->cm.d_rs, (long long)h->N,
                        (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), (const unsigned *)h->cm.d_abort);
     hipLaunchKernelGGL(k_rand_var, dim3(1), dim3(1024), 0, h->stream, q, (const long long *)R.d_kptr, (const int *)R.d_kcol, (const double *)R.d_kval,
-                       (const double *)R.d_u, R.d_vu, R.df, R.scale, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
+                       (const double *)R.d_u, R.d_vu, R.df, R.sdf, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
 }
 
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
@@ -1210,8 +1256,9 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
             hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((h->mm.nfixcol + 255) / 256)), dim3(256), 0, h->stream, (long long)h->mm.nfixcol, h->mm.d_bfix,
                                h->mm.d_sum_bfix, h->cm.d_abort);
         for (auto &R : h->mm.rnd) {  // random-effect sets: u and varU (src/samplers.jl:60-75)
-            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((R.q + 255) / 256)), dim3(256), 0, h->stream, (long long)R.q, R.d_u, R.d_sum_u, h->cm.d_abort);
-            hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, 1LL, R.d_vu, R.d_vu + 1, h->cm.d_abort);
+            const long long qk = (long long)R.q * R.tk, kk = (long long)R.tk * R.tk;
+            hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((qk + 255) / 256)), dim3(256), 0, h->stream, qk, R.d_u, R.d_sum_u, h->cm.d_abort);
+            hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, kk, R.d_vu, R.d_vu + kk, h->cm.d_abort);
         }
         for (auto &V : h->mm.lv)  // BayesLV sets: c and varZeta (src/samplers.jl:89-92)
             hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, (long long)NGP_LV_SUM, V.d_st, V.d_st + NGP_LV_SUM, h->cm.d_abort);
@@ -1295,8 +1342,9 @@ void describe(ngp_handle *h, ChainState &st) {
     }
     for (int r = 0; r < (int)h->mm.rnd.size(); r++) {
         HRand &R = h->mm.rnd[(size_t)r];
-        st.dev(SEG_U, r, R.d_u, (size_t)R.q * 8); st.dev(SEG_SUM_U, r, R.d_sum_u, (size_t)R.q * 8);
-        st.dev(SEG_VARU, r, R.d_vu, 8); st.dev(SEG_SUM_VARU, r, R.d_vu + 1, 8); st.dev(SEG_VU, r, R.d_vu, 16);
+        const size_t qk8 = (size_t)R.q * (size_t)R.tk * 8, kk = (size_t)R.tk * (size_t)R.tk;  // (a tuple set: u is q x k, varU k x k)
+        st.dev(SEG_U, r, R.d_u, qk8); st.dev(SEG_SUM_U, r, R.d_sum_u, qk8);
+        st.dev(SEG_VARU, r, R.d_vu, kk * 8); st.dev(SEG_SUM_VARU, r, R.d_vu + kk, kk * 8); st.dev(SEG_VU, r, R.d_vu, 2 * kk * 8);
         st.host(SEG_RFINE, r, &R.fine_calls, 8);
     }
     for (int v = 0; v < (int)h->mm.lv.size(); v++) {
@@ -1397,7 +1445,7 @@ int sample_enqueue(ngp_handle *h) {
         if (!h->mm.rnd.empty() || has_lv) {
             const int64_t nr = (int64_t)h->mm.rnd.size();
             ok = ok && std::fwrite(&nr, 8, 1, S->f.get()) == 1;
-            for (auto &R : h->mm.rnd) ok = ok && std::fwrite(&R.q, 8, 1, S->f.get()) == 1;
+            for (auto &R : h->mm.rnd) { const int64_t qw = rand_q_word(R); ok = ok && std::fwrite(&qw, 8, 1, S->f.get()) == 1; }
         }
         if (has_lv) {
             const int64_t nl = (int64_t)h->mm.lv.size();
@@ -1977,10 +2025,12 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
         HCHK(hipMemsetAsync(h->mm.d_sum_bfix, 0, (size_t)h->mm.nfixcol * sizeof(double), h->stream));
     }
     for (auto &R : h->mm.rnd) {  // u = 0, varU = its prior value (src/mme.jl:200, 265-272), empty sums
-        const double vu[2] = {R.varU0, 0.0};
-        HCHK(hipMemsetAsync(R.d_u, 0, (size_t)R.q * sizeof(double), h->stream));
-        HCHK(hipMemsetAsync(R.d_sum_u, 0, (size_t)R.q * sizeof(double), h->stream));
-        HCHK(hipMemcpyAsync(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice, h->stream));
+        const size_t qk = (size_t)R.q * (size_t)R.tk;
+        std::vector<double> vu(2 * R.varU0M.size(), 0.0);
+        std::copy(R.varU0M.begin(), R.varU0M.end(), vu.begin());
+        HCHK(hipMemsetAsync(R.d_u, 0, qk * sizeof(double), h->stream));
+        HCHK(hipMemsetAsync(R.d_sum_u, 0, qk * sizeof(double), h->stream));
+        HCHK(hipMemcpyAsync(R.d_vu, vu.data(), vu.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HCHK(hipStreamSynchronize(h->stream));
         R.fine_calls = 0;
     }
@@ -2782,7 +2832,7 @@ struct ModelSig {
         if (!h->h_rw.empty()) digest = weights_digest(h->h_rw);
         if (!h->mm.rnd.empty()) {
             rnd.push_back((uint64_t)h->mm.rnd.size());
-            for (auto &R : h->mm.rnd) { rnd.push_back((uint64_t)R.q); rnd.push_back(R.sig); }
+            for (auto &R : h->mm.rnd) { rnd.push_back((uint64_t)rand_q_word(R)); rnd.push_back(R.sig); }
         }
         for (auto &fx : h->mm.fix) fix.push_back(fx.ncol);
     }
@@ -3395,11 +3445,11 @@ void group_levels(const ngp_handle *h, const int32_t *level, int64_t q, std::vec
                   std::vector<double> &zpz) {
     const int64_t N = h->N;
     lp.assign((size_t)q + 1, 0); lr.resize((size_t)N); lv.resize((size_t)N); zpz.assign((size_t)q, 0.0);
-    for (int64_t i = 0; i < N; i++) lp[(size_t)level[i] + 1]++;
+    for (int64_t i = 0; i < N; i++) if (level[i] >= 0) lp[(size_t)level[i] + 1]++;  // (-1: a record without a level, tuple sets only)
     for (int64_t l = 0; l < q; l++) lp[(size_t)l + 1] += lp[(size_t)l];
     {
         std::vector<long long> pos(lp.begin(), lp.end() - 1);
-        for (int64_t i = 0; i < N; i++) { lr[(size_t)pos[(size_t)level[i]]++] = (int)i; lv[(size_t)i] = level[i]; }
+        for (int64_t i = 0; i < N; i++) { if (level[i] >= 0) lr[(size_t)pos[(size_t)level[i]]++] = (int)i; lv[(size_t)i] = level[i]; }
     }
     for (int64_t l = 0; l < q; l++) {
         if (h->h_rw.empty()) { zpz[(size_t)l] = (double)(lp[(size_t)l + 1] - lp[(size_t)l]); continue; }
@@ -3408,32 +3458,13 @@ void group_levels(const ngp_handle *h, const int32_t *level, int64_t q, std::vec
         zpz[(size_t)l] = a;
     }
 }
-}  // namespace
-
-extern "C" {
-
-/* A (1|g) random-effect set (src/mme.jl:165-272; sampled by sampleZ!, src/functions.jl:57-72, 92-97, 498-501).  Every argument is
- * checked before anything changes: a refused call leaves the handle as it was. */
-int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
-                           double df, double scale, double varU0, int32_t *set_id) {
-    NGP_TRY
-    int rc;
-    if ((rc = enter(h))) return rc;
-    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
-    REQUIRE(level != nullptr && q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: levels of N records and 1 <= q < 2^31");
-    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
-    REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
-    REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
+// K of a random-effect set from the caller's CSR (all three NULL: the identity), checked: rows with their columns ascending (the
+// summation order of DESIGN.md), symmetric, finite, with a positive diagonal
+int parse_k(ngp_handle *h, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val, std::vector<long long> &kp,
+            std::vector<int> &kc, std::vector<double> &kv, std::vector<double> &kd, bool &offdiag) {
+    kp.assign((size_t)q + 1, 0); kc.clear(); kv.clear(); kd.assign((size_t)q, 0.0);
+    offdiag = false;
     const bool ident = !k_ptr && !k_col && !k_val;
-    REQUIRE(ident || (k_ptr && k_col && k_val), NGP_ERR_ARG, "random-effect set: K as CSR (k_ptr, k_col, k_val), or all three NULL for the identity");
-    const int64_t N = h->N;
-    for (int64_t i = 0; i < N; i++) REQUIRE(level[i] >= 0 && (int64_t)level[i] < q, NGP_ERR_ARG, "random-effect set: a record's level is outside 0..q-1");
-    // K: rows with their columns ascending (the summation order of DESIGN.md), symmetric, finite, with a positive diagonal
-    std::vector<long long> kp((size_t)q + 1);
-    std::vector<int> kc;
-    std::vector<double> kv, kd((size_t)q);
-    bool offdiag = false;
     if (ident) {
         kc.resize((size_t)q); kv.assign((size_t)q, 1.0);
         for (int64_t l = 0; l <= q; l++) kp[(size_t)l] = l;
@@ -3472,59 +3503,206 @@ int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const
                 REQUIRE(it != e && *it == (int)l && kv[(size_t)(it - kc.begin())] == kv[(size_t)k], NGP_ERR_ARG, "random-effect set: K is not symmetric");
             }
     }
+    return NGP_OK;
+}
+
+// the launches of one step of the level schedule (ngp_random.h) from the depth of every row: the rows by (depth, row), a depth of more
+// than NGP_RS_FUSE_ROWS rows a launch of its own, a run of narrower depths one launch
+int plan_schedule(ngp_handle *h, HRand &R, const std::vector<int> &dep) {
+    const int64_t q = R.q;
+    int rc, maxd = 0;
+    for (int64_t l = 0; l < q; l++) maxd = std::max(maxd, dep[(size_t)l]);
+    std::vector<int> ord((size_t)q);
+    const int nd = maxd + 1;
+    std::vector<long long> dp((size_t)nd + 1, 0);
+    for (int64_t l = 0; l < q; l++) dp[(size_t)dep[(size_t)l] + 1]++;
+    for (int d = 0; d < nd; d++) dp[(size_t)d + 1] += dp[(size_t)d];
+    {
+        std::vector<long long> pos(dp.begin(), dp.end() - 1);
+        for (int64_t l = 0; l < q; l++) ord[(size_t)pos[(size_t)dep[(size_t)l]]++] = (int)l;
+    }
+    int run0 = -1;
+    for (int d = 0; d < nd; d++) {
+        if (dp[(size_t)d + 1] - dp[(size_t)d] > NGP_RS_FUSE_ROWS) {
+            if (run0 >= 0) R.plan.push_back({0, run0, d, dp[(size_t)run0], dp[(size_t)d]});
+            run0 = -1;
+            R.plan.push_back({1, d, d + 1, dp[(size_t)d], dp[(size_t)d + 1]});
+        } else if (run0 < 0) run0 = d;
+    }
+    if (run0 >= 0) R.plan.push_back({0, run0, nd, dp[(size_t)run0], dp[(size_t)nd]});
+    R.ndepth = nd;
+    if ((rc = upload(h, R.d_order, ord)) || (rc = upload(h, R.d_dptr, dp))) return rc;
+    return NGP_OK;
+}
+// k x k (row-major, symmetric) positive definite?  Cholesky on the host, k <= NGP_KMAX
+bool host_spd(const double *S, int k) {
+    double L[NGP_KMAX * NGP_KMAX] = {0.0};
+    for (int i = 0; i < k; i++)
+        for (int j = 0; j <= i; j++) {
+            double s = S[i * k + j];
+            for (int m = 0; m < j; m++) s -= L[i * k + m] * L[j * k + m];
+            if (i == j) { if (!(s > 0.0)) return false; L[i * k + i] = std::sqrt(s); }
+            else L[i * k + j] = s / L[j * k + j];
+        }
+    return true;
+}
+
+// A random-effect set with a CSR K and k components, behind the argument checks of ngp_add_random_set (k = 1, every level >= 0,
+// sdf = scale df) and ngp_add_random_set_tuple (level k x N component-major, -1 allowed).  k = 1 is the (1|g) set of ngp_random.h;
+// k > 1 the set of ngp_random_tuple.h: per component the records by level, the k x k blocks W_lc of the header (the diagonal ones
+// dense per level, the others CSR with ascending columns; under weighted residuals sums of w in ascending record order), and
+// the level schedule over the union of the patterns of K and of the off-diagonal blocks.
+int add_random_csr(ngp_handle *h, const int32_t *level, int k, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
+                   double df, const double *scaleM, const double *varU0M, int32_t *set_id) {
+    int rc;
+    const int64_t N = h->N;
+    const int kk = k * k;
+    std::vector<long long> kp;
+    std::vector<int> kc;
+    std::vector<double> kv, kd;
+    bool offdiag = false;
+    if ((rc = parse_k(h, q, k_ptr, k_col, k_val, kp, kc, kv, kd, offdiag))) return rc;
+    HRand R;
+    R.q = q; R.tk = k; R.df = df; R.offdiag = offdiag;
+    R.scaleM.assign(scaleM, scaleM + kk); R.varU0M.assign(varU0M, varU0M + kk);
     std::vector<long long> lp;
     std::vector<int> lr, lv;
     std::vector<double> zpz;
-    group_levels(h, level, q, lp, lr, lv, zpz);
-    HRand R;
-    R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = offdiag;
-    if (offdiag) {  // the level schedule (ngp_random.h): depths from the sorted rows, the rows by (depth, row), the launches of one step
-        std::vector<int> dep((size_t)q, 0), ord((size_t)q);
-        int maxd = 0;
-        for (int64_t l = 0; l < q; l++) {
+    std::vector<int> dep((size_t)q, 0);
+    if (k == 1) {
+        R.sdf = scaleM[0]; R.scale = scaleM[0] / df; R.varU0 = varU0M[0];
+        group_levels(h, level, q, lp, lr, lv, zpz);
+        if ((rc = upload(h, R.d_zpz, zpz))) return rc;
+        for (int64_t l = 0; l < q; l++) {  // the level schedule (ngp_random.h): depths from the sorted rows
             int d = 0;
-            for (long long k = kp[(size_t)l]; k < kp[(size_t)l + 1] && kc[(size_t)k] < l; k++) d = std::max(d, dep[(size_t)kc[(size_t)k]] + 1);
+            for (long long p = kp[(size_t)l]; p < kp[(size_t)l + 1] && kc[(size_t)p] < l; p++) d = std::max(d, dep[(size_t)kc[(size_t)p]] + 1);
             dep[(size_t)l] = d;
-            maxd = std::max(maxd, d);
         }
-        const int nd = maxd + 1;
-        std::vector<long long> dp((size_t)nd + 1, 0);
-        for (int64_t l = 0; l < q; l++) dp[(size_t)dep[(size_t)l] + 1]++;
-        for (int d = 0; d < nd; d++) dp[(size_t)d + 1] += dp[(size_t)d];
-        {
-            std::vector<long long> pos(dp.begin(), dp.end() - 1);
-            for (int64_t l = 0; l < q; l++) ord[(size_t)pos[(size_t)dep[(size_t)l]]++] = (int)l;
+    } else {
+        R.offdiag = true;  // (a tuple set always runs a Gauss-Seidel engine: its off-diagonal W blocks couple levels even under a diagonal K)
+        lp.assign((size_t)k * ((size_t)q + 1), 0); lr.assign((size_t)k * (size_t)N, 0); lv.assign(level, level + (size_t)k * (size_t)N);
+        for (int m = 0; m < k; m++) {  // component m's records by level: a stable counting sort, positions into lr from m N
+            long long *P = lp.data() + (size_t)m * ((size_t)q + 1);
+            const int32_t *lm = level + (size_t)m * (size_t)N;
+            for (int64_t i = 0; i < N; i++) if (lm[i] >= 0) P[(size_t)lm[i] + 1]++;
+            P[0] = (long long)m * N;
+            for (int64_t l = 0; l < q; l++) P[(size_t)l + 1] += P[(size_t)l];
+            std::vector<long long> pos(P, P + q);
+            for (int64_t i = 0; i < N; i++) if (lm[i] >= 0) lr[(size_t)pos[(size_t)lm[i]]++] = (int)i;
         }
-        int run0 = -1;
-        for (int d = 0; d < nd; d++) {
-            if (dp[(size_t)d + 1] - dp[(size_t)d] > NGP_RS_FUSE_ROWS) {
-                if (run0 >= 0) R.plan.push_back({0, run0, d, dp[(size_t)run0], dp[(size_t)d]});
-                run0 = -1;
-                R.plan.push_back({1, d, d + 1, dp[(size_t)d], dp[(size_t)d + 1]});
-            } else if (run0 < 0) run0 = d;
+        // the W blocks: per record i (ascending) and pair (a, b) with both levels known, w_i into block (level_a(i), level_b(i)), entry [a][b]
+        std::vector<double> wd((size_t)q * (size_t)kk, 0.0);
+        std::vector<std::map<int, std::array<double, NGP_KMAX * NGP_KMAX>>> wrow((size_t)q);
+        for (int64_t i = 0; i < N; i++) {
+            const double w = h->h_rw.empty() ? 1.0 : h->h_rw[(size_t)i];
+            for (int a = 0; a < k; a++) {
+                const int la = level[(size_t)a * (size_t)N + (size_t)i];
+                if (la < 0) continue;
+                for (int b = 0; b < k; b++) {
+                    const int lb = level[(size_t)b * (size_t)N + (size_t)i];
+                    if (lb < 0) continue;
+                    if (la == lb) { double &x = wd[(size_t)la * (size_t)kk + (size_t)(a * k + b)]; x = x + w; continue; }
+                    auto it = wrow[(size_t)la].find(lb);
+                    if (it == wrow[(size_t)la].end()) it = wrow[(size_t)la].emplace(lb, std::array<double, NGP_KMAX * NGP_KMAX>{}).first;
+                    double &x = it->second[(size_t)(a * k + b)];
+                    x = x + w;
+                }
+            }
         }
-        if (run0 >= 0) R.plan.push_back({0, run0, nd, dp[(size_t)run0], dp[(size_t)nd]});
-        R.ndepth = nd;
-        if ((rc = upload(h, R.d_order, ord)) || (rc = upload(h, R.d_dptr, dp))) return rc;
+        std::vector<long long> wp((size_t)q + 1, 0);
+        std::vector<int> wc;
+        std::vector<double> wv;
+        for (int64_t l = 0; l < q; l++) {
+            for (auto &e : wrow[(size_t)l]) { wc.push_back(e.first); wv.insert(wv.end(), e.second.begin(), e.second.begin() + kk); }
+            wp[(size_t)l + 1] = (long long)wc.size();
+        }
+        REQUIRE(wc.size() < ((size_t)1 << 31) / (size_t)kk, NGP_ERR_ARG, "tuple random-effect set: too many pairs of levels linked by records");
+        for (int64_t l = 0; l < q; l++) {  // depths over the union of the two patterns (both rows have ascending columns)
+            int d = 0;
+            for (long long p = kp[(size_t)l]; p < kp[(size_t)l + 1] && kc[(size_t)p] < l; p++) d = std::max(d, dep[(size_t)kc[(size_t)p]] + 1);
+            for (long long p = wp[(size_t)l]; p < wp[(size_t)l + 1] && wc[(size_t)p] < l; p++) d = std::max(d, dep[(size_t)wc[(size_t)p]] + 1);
+            dep[(size_t)l] = d;
+        }
+        if (wc.empty()) { wc.push_back(0); wv.assign((size_t)kk, 0.0); }  // (no empty device arrays)
+        if ((rc = upload(h, R.d_wd, wd)) || (rc = upload(h, R.d_wptr, wp)) || (rc = upload(h, R.d_wcol, wc)) || (rc = upload(h, R.d_wval, wv)) ||
+            (rc = upload(h, R.d_scaleM, R.scaleM)))
+            return rc;
     }
+    if (R.offdiag && (rc = plan_schedule(h, R, dep))) return rc;
     R.sig = bytes_digest(bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull, lv.data(), lv.size() * 4), kp.data(), kp.size() * 8), kc.data(),
                                       kc.size() * 4), kv.data(), kv.size() * 8);
-    const double vu[2] = {varU0, 0.0};
+    const size_t qk = (size_t)q * (size_t)k, nscr = k == 1 ? (size_t)NGP_RS_ROWS * (size_t)q : tup_scr_len(q, k);
+    std::vector<double> vu((size_t)2 * (size_t)kk, 0.0);
+    std::copy(R.varU0M.begin(), R.varU0M.end(), vu.begin());
     if ((rc = upload(h, R.d_lptr, lp)) || (rc = upload(h, R.d_lrows, lr)) || (rc = upload(h, R.d_level, lv)) || (rc = upload(h, R.d_kptr, kp)) ||
-        (rc = upload(h, R.d_kcol, kc)) || (rc = upload(h, R.d_kval, kv)) || (rc = upload(h, R.d_kdiag, kd)) || (rc = upload(h, R.d_zpz, zpz)))
+        (rc = upload(h, R.d_kcol, kc)) || (rc = upload(h, R.d_kval, kv)) || (rc = upload(h, R.d_kdiag, kd)) || (rc = upload(h, R.d_vu, vu)))
         return rc;
-    if ((rc = R.d_u.alloc(h, (size_t)q)) || (rc = R.d_sum_u.alloc(h, (size_t)q)) || (rc = R.d_vu.alloc(h, 2)) ||
-        (rc = R.d_scr.alloc(h, (size_t)NGP_RS_ROWS * (size_t)q)))
-        return rc;
-    hipError_t e = hipMemset(R.d_u, 0, (size_t)q * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(R.d_sum_u, 0, (size_t)q * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(R.d_scr, 0, (size_t)NGP_RS_ROWS * (size_t)q * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice);
-    if (e == hipSuccess && offdiag) e = hipFuncSetAttribute((const void *)k_rand_gs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NGP_LDS_MAX);
+    if ((rc = R.d_u.alloc(h, qk)) || (rc = R.d_sum_u.alloc(h, qk)) || (rc = R.d_scr.alloc(h, nscr))) return rc;
+    hipError_t e = hipMemset(R.d_u, 0, qk * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(R.d_sum_u, 0, qk * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(R.d_scr, 0, nscr * sizeof(double));
+    if (e == hipSuccess && R.offdiag)
+        e = hipFuncSetAttribute(k == 1 ? (const void *)k_rand_gs : (const void *)k_tup_gs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NGP_LDS_MAX);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("add_random_set: ") + hipGetErrorString(e));
     if (set_id) *set_id = (int32_t)h->mm.rnd.size();
     h->mm.rnd.push_back(std::move(R));
     return NGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+/* A (1|g) random-effect set (src/mme.jl:165-272; sampled by sampleZ!, src/functions.jl:57-72, 92-97, 498-501).  Every argument is
+ * checked before anything changes: a refused call leaves the handle as it was. */
+int32_t ngp_add_random_set(ngp_handle *h, const int32_t *level, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
+                           double df, double scale, double varU0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
+    REQUIRE(level != nullptr && q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: levels of N records and 1 <= q < 2^31");
+    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
+    REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
+    const bool ident = !k_ptr && !k_col && !k_val;
+    REQUIRE(ident || (k_ptr && k_col && k_val), NGP_ERR_ARG, "random-effect set: K as CSR (k_ptr, k_col, k_val), or all three NULL for the identity");
+    const int64_t N = h->N;
+    for (int64_t i = 0; i < N; i++) REQUIRE(level[i] >= 0 && (int64_t)level[i] < q, NGP_ERR_ARG, "random-effect set: a record's level is outside 0..q-1");
+    const double sdf = scale * df;
+    return add_random_csr(h, level, 1, q, k_ptr, k_col, k_val, df, &sdf, &varU0, set_id);
+    NGP_CATCH(h)
+}
+
+/* A correlated (Tuple) random-effect set (src/mme.jl:207-239; sampled by sampleZ!(::Tuple), src/functions.jl:75-89, 100-110, 503-506): k
+ * components over one K with a k x k covariance -- (ID, Dam), direct and maternal effects over one pedigree.  level is k x N,
+ * component-major, -1 for a record without a level in that component (an unknown dam: the all-zero row of Z).  scale and varU0 are
+ * k x k row-major, symmetric positive definite; the caller passes df = 3 + k and scale = v (df - k - 1) (src/mme.jl:265-271).  k = 1 is
+ * ngp_add_random_set's chain bit for bit with scale_tuple = scale * df.  The step draws the exact Gibbs conditional, NOT the
+ * reference's lines: see the header.  Every argument is checked before anything changes. */
+int32_t ngp_add_random_set_tuple(ngp_handle *h, const int32_t *level, int32_t k, int64_t q, const int64_t *k_ptr, const int32_t *k_col,
+                                 const double *k_val, double df, const double *scale, const double *varU0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
+    REQUIRE(k >= 1 && k <= NGP_KMAX, NGP_ERR_ARG, "tuple random-effect set: 1 <= k <= 4 components");
+    REQUIRE(level != nullptr && q >= 1 && q < ((int64_t)1 << 31) / k, NGP_ERR_ARG, "tuple random-effect set: k x N levels and 1 <= q, q k < 2^31");
+    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(scale != nullptr && varU0 != nullptr, NGP_ERR_ARG, "tuple random-effect set: scale and varU0 are k x k matrices");
+    REQUIRE(std::isfinite(df) && df > 0.0, NGP_ERR_ARG, "tuple random-effect set: df > 0, finite");
+    for (int a = 0; a < k * k; a++) REQUIRE(std::isfinite(scale[a]) && std::isfinite(varU0[a]), NGP_ERR_ARG, "tuple random-effect set: non-finite entry in scale or varU0");
+    for (int a = 0; a < k; a++)
+        for (int b = 0; b < a; b++)
+            REQUIRE(scale[a * k + b] == scale[b * k + a] && varU0[a * k + b] == varU0[b * k + a], NGP_ERR_ARG, "tuple random-effect set: scale and varU0 must be symmetric");
+    REQUIRE(host_spd(scale, k) && host_spd(varU0, k), NGP_ERR_ARG, "tuple random-effect set: scale and varU0 must be positive definite");
+    const bool ident = !k_ptr && !k_col && !k_val;
+    REQUIRE(ident || (k_ptr && k_col && k_val), NGP_ERR_ARG, "random-effect set: K as CSR (k_ptr, k_col, k_val), or all three NULL for the identity");
+    const int64_t N = h->N;
+    for (int64_t i = 0; i < (int64_t)k * N; i++)
+        REQUIRE(level[i] >= -1 && (int64_t)level[i] < q, NGP_ERR_ARG, "tuple random-effect set: a record's level is outside 0..q-1 (-1: no level in that component)");
+    return add_random_csr(h, level, (int)k, q, k_ptr, k_col, k_val, df, scale, varU0, set_id);
     NGP_CATCH(h)
 }
 
@@ -3534,6 +3712,7 @@ int32_t ngp_get_random(ngp_handle *h, int32_t set_id, double *u, double *sum_u, 
     if ((rc = enter(h))) return rc;
     REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     const HRand &R = h->mm.rnd[(size_t)set_id];
+    REQUIRE(R.tk == 1, NGP_ERR_ARG, "a correlated (Tuple) random-effect set: its state is k-fold (ngp_get_random_tuple)");
     HCHK(hipStreamSynchronize(h->stream));
     double vu[2];
     HCHK(hipMemcpy(vu, R.d_vu, sizeof(vu), hipMemcpyDeviceToHost));
@@ -3552,6 +3731,7 @@ int32_t ngp_set_random(ngp_handle *h, int32_t set_id, const double *u, const dou
     REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     REQUIRE(std::isfinite(varU) && varU > 0.0 && std::isfinite(sum_varU), NGP_ERR_ARG, "varU must be finite and > 0, sum_varU finite");
     const HRand &R = h->mm.rnd[(size_t)set_id];
+    REQUIRE(R.tk == 1, NGP_ERR_ARG, "a correlated (Tuple) random-effect set: its state is k-fold (ngp_set_random_tuple)");
     if (u) for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
     if (sum_u) for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(sum_u[l]), NGP_ERR_ARG, "non-finite sum of a random effect");
     HCHK(hipStreamSynchronize(h->stream));
@@ -3575,6 +3755,7 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
     REQUIRE(std::isfinite(varE) && varE > 0.0, NGP_ERR_ARG, "varE must be finite and positive");
     REQUIRE(std::isfinite(*varU) && *varU > 0.0, NGP_ERR_ARG, "varU must be finite and positive");
     HRand &R = h->mm.rnd[(size_t)set_id];
+    REQUIRE(R.tk == 1, NGP_ERR_ARG, "a correlated (Tuple) random-effect set: its state is k-fold (ngp_sample_random_set_tuple)");
     for (int64_t l = 0; l < R.q; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
     const uint64_t it = ++R.fine_calls;
     HCHK(hipStreamSynchronize(h->stream));
@@ -3591,6 +3772,87 @@ int32_t ngp_sample_random_set(ngp_handle *h, int32_t set_id, double varE, double
     HCHK(hipMemcpyAsync(ycorr, h->cm.d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipMemcpyAsync(u, R.d_u, (size_t)R.q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipMemcpyAsync(varU, R.d_vu, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    return check_abort(h);
+    NGP_CATCH(h)
+}
+
+/* State of a random-effect set of k components (ngp_add_random_set_tuple; a set of ngp_add_random_set is k = 1): u and sum_u are q x k with
+ * the k components of a level adjacent, varU and sum_varU k x k row-major.  Any pointer may be NULL. */
+int32_t ngp_get_random_tuple(ngp_handle *h, int32_t set_id, double *u, double *sum_u, double *varU, double *sum_varU) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    const HRand &R = h->mm.rnd[(size_t)set_id];
+    const size_t qk8 = (size_t)R.q * (size_t)R.tk * sizeof(double), kk = (size_t)R.tk * (size_t)R.tk;
+    HCHK(hipStreamSynchronize(h->stream));
+    if (u) HCHK(hipMemcpy(u, R.d_u, qk8, hipMemcpyDeviceToHost));
+    if (sum_u) HCHK(hipMemcpy(sum_u, R.d_sum_u, qk8, hipMemcpyDeviceToHost));
+    if (varU) HCHK(hipMemcpy(varU, R.d_vu, kk * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_varU) HCHK(hipMemcpy(sum_varU, R.d_vu + kk, kk * sizeof(double), hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ... and its setter; a NULL pointer leaves that part as it is.  varU must be symmetric positive definite. */
+int32_t ngp_set_random_tuple(ngp_handle *h, int32_t set_id, const double *u, const double *sum_u, const double *varU, const double *sum_varU) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    const HRand &R = h->mm.rnd[(size_t)set_id];
+    const int k = R.tk;
+    const size_t qk = (size_t)R.q * (size_t)k, kk = (size_t)k * (size_t)k;
+    if (varU) {
+        for (size_t a = 0; a < kk; a++) REQUIRE(std::isfinite(varU[a]), NGP_ERR_ARG, "non-finite entry in varU");
+        for (int a = 0; a < k; a++)
+            for (int b = 0; b < a; b++) REQUIRE(varU[a * k + b] == varU[b * k + a], NGP_ERR_ARG, "varU must be symmetric");
+        REQUIRE(host_spd(varU, k), NGP_ERR_ARG, "varU must be positive definite");
+    }
+    if (sum_varU) for (size_t a = 0; a < kk; a++) REQUIRE(std::isfinite(sum_varU[a]), NGP_ERR_ARG, "non-finite entry in sum_varU");
+    if (u) for (size_t l = 0; l < qk; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
+    if (sum_u) for (size_t l = 0; l < qk; l++) REQUIRE(std::isfinite(sum_u[l]), NGP_ERR_ARG, "non-finite sum of a random effect");
+    HCHK(hipStreamSynchronize(h->stream));
+    if (varU) HCHK(hipMemcpy(R.d_vu, varU, kk * sizeof(double), hipMemcpyHostToDevice));
+    if (sum_varU) HCHK(hipMemcpy(R.d_vu + kk, sum_varU, kk * sizeof(double), hipMemcpyHostToDevice));
+    if (u) HCHK(hipMemcpy(R.d_u, u, qk * sizeof(double), hipMemcpyHostToDevice));
+    if (sum_u) HCHK(hipMemcpy(R.d_sum_u, sum_u, qk * sizeof(double), hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Fine seam of one random-effect set of k components: sampleZ!(zSet::Tuple, ...) of src/functions.jl:100-110 on the caller's arrays (ycorr N,
+ * u q x k, varU k x k; updated in place) with the exact conditional of the header, keyed like ngp_sample_random_set. */
+int32_t ngp_sample_random_set_tuple(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *u, double *varU) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
+    REQUIRE(ycorr && u && varU, NGP_ERR_ARG, "null state pointer");
+    REQUIRE(std::isfinite(varE) && varE > 0.0, NGP_ERR_ARG, "varE must be finite and positive");
+    HRand &R = h->mm.rnd[(size_t)set_id];
+    const int k = R.tk;
+    const size_t qk = (size_t)R.q * (size_t)k, kk = (size_t)k * (size_t)k;
+    for (size_t a = 0; a < kk; a++) REQUIRE(std::isfinite(varU[a]), NGP_ERR_ARG, "non-finite entry in varU");
+    for (int a = 0; a < k; a++)
+        for (int b = 0; b < a; b++) REQUIRE(varU[a * k + b] == varU[b * k + a], NGP_ERR_ARG, "varU must be symmetric");
+    REQUIRE(host_spd(varU, k), NGP_ERR_ARG, "varU must be positive definite");
+    for (size_t l = 0; l < qk; l++) REQUIRE(std::isfinite(u[l]), NGP_ERR_ARG, "non-finite random effect");
+    const uint64_t it = ++R.fine_calls;
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpyAsync(h->cm.d_ycorr, ycorr, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: the caller's ycorr into y~ = s ycorr
+    HCHK(hipMemcpyAsync(R.d_u, u, qk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(R.d_vu, varU, kk * sizeof(double), hipMemcpyHostToDevice, h->stream));  // (the sum of varU stays)
+    hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->cm.d_scal, varE);
+    launch_random(h, (int)set_id, it);
+    if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, true);  // ... and back (d_ycorr is scratch here)
+    HCHK(hipMemcpyAsync(ycorr, h->cm.d_ycorr, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipMemcpyAsync(u, R.d_u, qk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipMemcpyAsync(varU, R.d_vu, kk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
     HCHK(hipGetLastError());
     return check_abort(h);
@@ -4244,6 +4506,7 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
     group_levels(h, level, q, lp, lr, lv, zpz);
     HRand R;
     R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = true;
+    R.sdf = scale * df; R.scaleM = {R.sdf}; R.varU0M = {varU0};
     // digest of the level coding and of every entry of K (hashed on the device: a dense K may never have been on the host)
     R.sig = bytes_digest(bytes_digest(1469598103934665603ull ^ 0x44454E5345ull, lv.data(), lv.size() * 4), &kdig, sizeof(kdig));
     const double vu[2] = {varU0, 0.0};

@@ -208,7 +208,9 @@ __global__ __launch_bounds__(256) void k_rand_update(double *__restrict__ ycorr,
     if (abort_w && *abort_w != 0u) return;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    double t = du[level[i]];
+    const int lv = level[i];
+    if (lv < 0) return;  // (a record without a level: ngp_add_random_set_tuple with k = 1)
+    double t = du[lv];
     if (rs) t = rs[i] * t;
     ycorr[i] = ycorr[i] - t;
 }
@@ -217,11 +219,11 @@ __global__ __launch_bounds__(256) void k_rand_update(double *__restrict__ ycorr,
 // varU (src/functions.jl:498-501), ONE workgroup of 1024 threads.  Thread t takes the levels t, t + 1024, ...:
 //   r_l = sum over row l of K, ascending columns, of K_lc * u_c (from 0.0);  p = u_l * r_l;  acc = acc + p (from 0.0)
 // then the butterfly of k_rand_levels inside each wave, the 16 wave sums added in wave order by thread 0 (quad = w_0 + w_1 + ...),
-//   t = scale * df;  t = t + quad;  varU = t / chi2(df + q) keyed (NGP_KIND_U_CHI2, set)
+//   t = scale * df (sdf: the one product, formed on the host);  t = t + quad;  varU = t / chi2(df + q) keyed (NGP_KIND_U_CHI2, set)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_rand_var(long long q, const long long *__restrict__ kptr, const int *__restrict__ kcol,
                                                    const double *__restrict__ kval, const double *__restrict__ u, double *__restrict__ vu,
-                                                   double df, double scale, int rset, uint64_t seed, uint64_t chain, uint64_t it,
+                                                   double df, double sdf, int rset, uint64_t seed, uint64_t chain, uint64_t it,
                                                    const unsigned *__restrict__ abort_w) {
     if (abort_w && *abort_w != 0u) return;
     __shared__ double wsum[16];
@@ -245,8 +247,7 @@ __global__ __launch_bounds__(1024) void k_rand_var(long long q, const long long 
         for (int k = 1; k < 16; k++) quad = quad + wsum[k];
         Rng r = rng_seed(seed, chain, it, NGP_KIND_U_CHI2, (uint64_t)rset);
         const double chi = rng_chisq(r, df + (double)q);
-        double t = scale * df;
-        t = t + quad;
+        const double t = sdf + quad;
         vu[0] = t / chi;
     }
 }

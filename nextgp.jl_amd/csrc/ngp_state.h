@@ -14,6 +14,10 @@
 //
 // THE FORMATS (normative; little-endian, doubles unless said otherwise, no padding unless said otherwise)
 //
+//  A correlated (Tuple) random-effect set of k components (ngp_add_random_set_tuple) has u[q k] (the k components of a level adjacent)
+//  and varU[k k] (row-major) wherever a set is written with u[q] and varU below; its q word in the sample file's header and in the
+//  snapshot signature carries k - 1 in the bits from 32 up (q < 2^31), and its digest covers the k level vectors and K.
+//
 //  Packed posterior (ngp_posterior_len, ngp_export_posterior_device, ngp_allreduce_posterior) -- posterior_layout:
 //    sum_beta[P] | sum_beta2[P] | sum_delta[P] | sum_varBeta[nvb] | sum_pi[2] per marker set | class sums[K] per BayesR set |
 //    fixed-effect sums (every column of every set) | sum_u[q] of every random-effect set, then sum_varU of every set |

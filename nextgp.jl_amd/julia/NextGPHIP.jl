@@ -213,10 +213,12 @@ function foreach_sample(f, path::AbstractString)
         magic in ("NGPSMP01", "NGPSMP02", "NGPSMP03") || error("not a sample file: $path")
         P, nvb, nsets, nfix, ncls, rec = ntuple(_ -> read(io, Int64), 6)
         sets = [ntuple(_ -> read(io, Int64), 6) for _ in 1:nsets]     # (method, K, col0, ncol, variance entries, tuple k)
-        rq = magic != "NGPSMP01" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each
+        rq = magic != "NGPSMP01" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each (a tuple set: k - 1 in the bits from 32 up)
         # BayesLV sets ("NGPSMP03"): (marker set, ncov) of each; a record holds c (16 words, ncov used) | varZeta per set behind class_pi
         lvs = magic == "NGPSMP03" ? [(read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64}[]
-        nr = sum(rq; init = 0) + length(rq)                           # u (set after set) and varU between b_fixed and beta
+        rk = [Int(w >> 32) + 1 for w in rq]                           # components of each set (1: a (1|g) / PED / GBLUP set)
+        rq = [Int(w & 0xffffffff) * k for (w, k) in zip(rq, rk)]      # words of u per set: q k, the components of a level adjacent
+        nr = sum(rq; init = 0) + sum(rk .^ 2; init = 0)               # u (set after set) and varU (k k words per set) between b_fixed and beta
         ncp = 3 + nfix + nr + P + nvb + 2 * nsets + ncls               # doubles in front of the BayesLV words
         nd = ncp + 17 * length(lvs)
         raw = Vector{UInt8}(undef, rec)
@@ -343,6 +345,49 @@ end
 set_random!(h::Handle, set_id::Integer, u::Vector{Float64}, sum_u::Vector{Float64}, varU::Float64, sum_varU::Float64) =
     check(h, ccall((:ngp_set_random, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Float64), h.ptr, set_id, u, sum_u, varU, sum_varU))
 
+# Correlated (Tuple) random-effect sets, (:ID, :Dam) (ngp_add_random_set_tuple): levels is N x k (1-based, 0 = the record has no level in
+# that component: an all-zero row of that Z), K the shared Z.iVarStr, scale and varU0 k x k.  The state is held as the reference holds
+# it: u k x q (Julia's column-major k x q IS the library's q x k with the components of a level adjacent), varU k x k (symmetric).
+# THE STEP DRAWS THE EXACT GIBBS CONDITIONAL, not the reference's lines (include/nextgp_hip.h): use these wrappers knowingly; the coarse
+# seam (runLMEM_hip) keeps sending Tuple Z sets to the reference sampler.
+function add_random_set_tuple!(h::Handle, levels::Matrix{Int32}, q::Integer, K, df::Float64, scale::Matrix{Float64}, varU0::Matrix{Float64})
+    k = size(levels, 2)
+    (size(scale) == (k, k) && size(varU0) == (k, k)) || error("tuple random-effect set: scale and varU0 must be $k x $k")
+    kp = Vector{Int64}(undef, q + 1); kc = Int32[]; kv = Float64[]
+    kp[1] = 0
+    for l in 1:q                                 # row l of K, columns ascending (K is symmetric: row l == column l)
+        col = K[:, l]
+        for c in 1:q
+            col[c] == 0.0 && continue
+            push!(kc, c - 1); push!(kv, Float64(col[c]))
+        end
+        kp[l + 1] = length(kc)
+    end
+    lv = vec(levels) .- Int32(1)                 # component-major k x N, 0-based, -1 = no level
+    id = Ref{Int32}(0)
+    check(h, ccall((:ngp_add_random_set_tuple, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Int32}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+                   h.ptr, lv, k, q, kp, kc, kv, df, Matrix(scale'), Matrix(varU0'), id))
+    return id[]
+end
+function random_state_tuple(h::Handle, set_id::Integer, q::Integer, k::Integer)
+    u = Matrix{Float64}(undef, k, q); su = similar(u); v = Matrix{Float64}(undef, k, k); sv = similar(v)
+    check(h, ccall((:ngp_get_random_tuple, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h.ptr, set_id, u, su, v, sv))
+    return (u = u, sum_u = su, varU = Matrix(v'), sum_varU = Matrix(sv'))
+end
+set_random_tuple!(h::Handle, set_id::Integer, u::Matrix{Float64}, sum_u::Matrix{Float64}, varU::Matrix{Float64}, sum_varU::Matrix{Float64}) =
+    check(h, ccall((:ngp_set_random_tuple, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   h.ptr, set_id, u, sum_u, Matrix(varU'), Matrix(sum_varU')))
+# fine seam of a tuple set: the argument list of functions.sampleZ!(zSet::Tuple, Z, u, ycorr, varE, varU) plus the handle and the set id
+function sampleZ_tuple!(h::Handle, set_id::Integer, zSet::Tuple, Z, u, ycorr::Vector{Float64}, varE::Float64, varU)
+    uv = u[Z[zSet].pos]                          # k x q Matrix{Float64}, updated in place
+    v = Matrix{Float64}(Matrix(varU[zSet])')
+    check(h, ccall((:ngp_sample_random_set_tuple, LIB), Int32, (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   h.ptr, set_id, varE, ycorr, uv, v))
+    varU[zSet] = Matrix(v')
+    return nothing
+end
+
 """
     sampleZ!(h, set_id, zSet, Z, u, ycorr, varE, varU)
 
@@ -449,7 +494,7 @@ sets with BayesPR / BayesB / BayesC / BayesR / BayesLV priors.  Anything else fa
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
                      seed::Integer=1, device::Integer=0)
-    all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110)")
+    all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110); the device draws the exact Gibbs conditional of the model, NOT the reference's lines (they leave Z_ID'Z_Dam u_Dam of the other levels in a level's right-hand side), so a run sent there would not be the reference's chain -- add_random_set_tuple! / sampleZ_tuple! are there for callers who want the exact one")
     (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
     h = Handle(device=device, seed=seed)
     E.str == "D" && set_residual_weights!(h, Vector{Float64}(E.iVarStr))   # before the panel (src/mme.jl:71-75)

@@ -9,7 +9,11 @@ the median taken; the two engines alternate.  "identity" is the same step over K
 engines sit on.  K is A^-1 by Henderson's rules WITHOUT inbreeding (a = 2 for an animal with parents, 1 for a founder), built here with numpy: the tool times the engine,
 whose cost depends on the pattern of K, and Meuwissen and Luo's walk over 10^6 animals of deep random pedigrees takes minutes.
 
-    python tools/random_gs_time.py [--sizes 1000,20000,100000,1000000] [--reps 21] [--out profiles/random_gs_time.json]
+--tuple k times a correlated (Tuple) set of k components instead (ngp_random_tuple.h): (ID, Dam[, Sire, ID]) levels of the same records
+over the same K (founders' records have no dam: level -1); there is no "identity" floor then (a tuple set always runs an engine), and
+the scalar set's serial / scheduled times of the same pedigree are measured beside it for the ratio.
+
+    python tools/random_gs_time.py [--sizes 1000,20000,100000,1000000] [--reps 21] [--tuple k] [--out profiles/random_gs_time.json]
 """
 import argparse
 import json
@@ -77,7 +81,7 @@ def time_steps(s, reps):
     return out
 
 
-def measure(ngp, q, kind, reps):
+def measure(ngp, q, kind, reps, tk=0):
     sd = pedigree(q, kind)
     K = ainv_no_inbreeding(*sd)
     rng = np.random.default_rng(3)
@@ -85,20 +89,29 @@ def measure(ngp, q, kind, reps):
     y = rng.normal(size=N) + 5.0
     level = np.arange(q - N, q, dtype=np.int32)
     hs = {}
-    for name in ("identity", "serial", "scheduled"):
+    names = ("identity", "serial", "scheduled") if not tk else ("serial", "scheduled", "tuple_serial", "tuple_scheduled")
+    for name in names:
         s = ngp.Sampler(device=0, seed=3, chain=0)
         s.set_records(N)
-        rid = s.add_random_set(level, q, K=None if name == "identity" else K, varU0=1.0)
-        if name != "identity":
-            s.set_random_schedule(rid, name)
+        if name.startswith("tuple_"):
+            levels = np.stack([level, sd[1][level], sd[0][level], level][:tk]).astype(np.int32)
+            rid = s.add_random_set_tuple(levels, q, K=K, varU0=np.eye(tk) + 0.2)
+            s.set_random_schedule(rid, name[6:])
+        else:
+            rid = s.add_random_set(level, q, K=None if name == "identity" else K, varU0=1.0)
+            if name != "identity":
+                s.set_random_schedule(rid, name)
         s.set_y(y); s.set_residual_prior(4.0, 0.5)
         hs[name] = (s, rid)
     info = hs["scheduled"][0].get_random_schedule(hs["scheduled"][1])
+    tinfo = hs["tuple_scheduled"][0].get_random_schedule(hs["tuple_scheduled"][1]) if tk else None
     # the serial walk costs about a microsecond per level: fewer repeats where one step takes a second
-    nrep = {n: (max(3, min(reps, int(2e6 / q))) if n == "serial" else reps) for n in hs}
+    nrep = {n: (max(3, min(reps, int(2e6 / q))) if n.endswith("serial") else reps) for n in hs}
     for n, (s, _) in hs.items():
         s.run(2)                                       # warm-up: code objects, first launches
     same = np.array_equal(hs["serial"][0].get_random(0)["u"], hs["scheduled"][0].get_random(0)["u"])   # the same chain so far, bit for bit
+    if tk:
+        same = same and np.array_equal(hs["tuple_serial"][0].get_random_tuple(0)["u"], hs["tuple_scheduled"][0].get_random_tuple(0)["u"])
     ts = {n: [] for n in hs}
     for k in range(reps):                              # alternate the engines
         for n, (s, _) in hs.items():
@@ -107,6 +120,8 @@ def measure(ngp, q, kind, reps):
     for s, _ in hs.values():
         s.close()
     res = dict(q=q, records=N, kind=kind, nnz_per_row=float(len(K[1]) / q), depths=info["depths"], launches=info["launches"], same_bits=bool(same))
+    if tk:
+        res.update(tuple_k=tk, tuple_depths=tinfo["depths"], tuple_launches=tinfo["launches"])
     for n in hs:
         res[n + "_ms_median"] = float(np.median(ts[n]))
         res[n + "_ms_min"] = float(np.min(ts[n]))
@@ -119,13 +134,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000,20000,100000,1000000")
     ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("--tuple", type=int, default=0, dest="tk", help="time a correlated (Tuple) set of k = 2..4 components beside the scalar set")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ngp = load_pkg()
     rows = []
     for q in (int(x) for x in a.sizes.split(",")):
         for kind in ("overlapping", "discrete"):
-            r = measure(ngp, q, kind, a.reps)
+            r = measure(ngp, q, kind, a.reps, a.tk)
             rows.append(r)
             print(json.dumps(r), flush=True)
     if a.out:
