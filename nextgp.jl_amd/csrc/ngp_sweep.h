@@ -879,9 +879,11 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
                 const int pa = u + 1 - DT;
                 const bool pollw = (wv == NGP_ROWS_POLLW) && (pa >= 0) && (u + 1 < nb + DT) && !(DBG && dbg_mode == 1);
                 // (every load of a streaming CU queues behind a microsecond of tile requests: dlt comes as self-validating granules,
-                // ONE load, requested before the previous barrier; only if that was too early is it requested again here)
+                // ONE load, requested before the previous barrier.)  Byte tiles: looked at here, and requested again if that was too
+                // early.  fp32 tiles: examined at the end of the block only -- the look held this wave for the rest of the load's round
+                // trip and its second request is one more load in the queue the tile stream fills.
                 bool have_dnext = false;
-                if (pollw) {
+                if (U8 && pollw) {
                     if (dlt_granules_valid(pg0, pg1, dlt_tag(A.nonce, pa))) {
                         have_dnext = true;
                     } else {  // asked for too early: ask again, the answer travels while this wave does its arithmetic
@@ -1062,7 +1064,8 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
                     }
                 }
                 if (wv == NGP_ROWS_POLLW && pa + 1 >= 0 && u + 2 < nb + DT && !(DBG && dbg_mode == 1)) {
-                    // dlt of the block after that: looked at behind the barrier (if the sampler is that far, the next block pays nothing)
+                    // dlt of the block after that: byte tiles look at it behind the barrier, fp32 tiles at the end of the next block
+                    // (if the sampler is that far, the next block pays nothing)
                     const unsigned long long *gp = A.dltg + ((size_t)((pa + 1) % NGP_RING) * NGP_BLK + lane) * 2;
                     pg0 = ld_u64(gp);
                     pg1 = ld_u64(gp + 1);

@@ -35,3 +35,14 @@ for k in range(8):
     rel = (F[:, :, k] - t0[:, None]) / 100.0
     print(f"{names[k]:24s}", " ".join(f"{x:6.2f}" if abs(x) < 1e6 else "     -" for x in np.median(rel, axis=0)))
 print("iteration period us:", np.median(np.diff(t0)) / 100.0)
+if s.streamer()[0] >= 2:
+    # row-owning streamer: where each row wave's block starts (stamp 0 -> 1: the poller's look at its granules + the update of its
+    # rows) and who closes the block's barrier (row waves arrive at stamp 4, the loader at stamp 2)
+    d01 = (F[:, :7, 1] - F[:, :7, 0]) / 100.0
+    print("start -> update done, us    ", " ".join(f"{x:6.2f}" for x in np.median(d01, axis=0)), " (waves 0..6, median)")
+    print("  poller (wave 6) minus the median of waves 0-5, per block:", " ".join(f"{x:5.2f}" for x in d01[:, 6] - np.median(d01[:, :6], axis=1)))
+    arr = np.concatenate([F[:, :7, 4], F[:, 7:8, 2]], axis=1)
+    print("last at the barrier (waves 0..6, loader), blocks of 16:", np.bincount(np.argmax(arr, axis=1), minlength=8))
+    print("last row wave at the barrier (waves 0..6), blocks of 16:", np.bincount(np.argmax(arr[:, :7], axis=1), minlength=7))
+    print("loader's arrival minus the last row wave's, us, per block:", " ".join(f"{x:5.2f}" for x in (arr[:, 7] - arr[:, :7].max(axis=1)) / 100.0))
+    print("poller's arrival minus the last of waves 0-5, us, per block:", " ".join(f"{x:5.2f}" for x in (arr[:, 6] - arr[:, :6].max(axis=1)) / 100.0))
