@@ -1432,11 +1432,36 @@ __device__ __attribute__((always_inline)) inline bool acc_complete(const unsigne
 }
 // a complete sum -> X_t'ycorr of this lane's column; the accumulator goes back to zero for the block that takes the slot 16 blocks on
 // (that block's terms are more than a lag behind this store: a streamer adds them only after it has seen dlt of a LATER block)
-__device__ __attribute__((always_inline)) inline double acc_take(const SweepArgs &A, const int u, const int j, const unsigned long long q, const double fxi) {
+__device__ __attribute__((always_inline)) inline void acc_zero(const SweepArgs &A, const int u, const int j) {
     unsigned long long *ap = A.acc + (size_t)(u % NGP_RING) * NGP_FX_COPIES * NGP_BLK + j;
 #pragma unroll
     for (int c = 0; c < NGP_FX_COPIES; c++) st_u64(ap + (size_t)c * NGP_BLK, 0ull);
+}
+__device__ __attribute__((always_inline)) inline double acc_value(const unsigned long long q, const double fxi) {
     return fx_to_f64((long long)q >> NGP_FX_CNT_BITS) * fxi;
+}
+__device__ __attribute__((always_inline)) inline double acc_take(const SweepArgs &A, const int u, const int j, const unsigned long long q, const double fxi) {
+    acc_zero(A, u, j);
+    return acc_value(q, fxi);
+}
+// A LOOK at a block's accumulator (wave 2 of the sampler, lag >= 4): the eight copies as they arrive, one word each, NOT added -- the sum
+// is formed when the look is examined, a block period after it was requested.  (Requested as a sum -- acc_load -- the adds, and with
+// them s_waitcnt vmcnt(0), stand right behind the eight loads: the wave sits the round trip where it asks.)
+struct AccLook { unsigned long long w[NGP_FX_COPIES]; };
+__device__ __attribute__((always_inline)) inline void look_request(const SweepArgs &A, const int u, const int j, AccLook &L) {
+    const unsigned long long *ap = A.acc + (size_t)(u % NGP_RING) * NGP_FX_COPIES * NGP_BLK + j;
+#pragma unroll
+    for (int c = 0; c < NGP_FX_COPIES; c++) L.w[c] = ld_u64(ap + (size_t)c * NGP_BLK);
+}
+// the point at which the look is examined: the words are "used" HERE, so the wait for them (the compiler's) and the adds stand here
+// and not sooner -- volatile, it keeps its place behind the barrier of the block in which the look was requested
+__device__ __attribute__((always_inline)) inline unsigned long long look_examine(AccLook &L) {
+    static_assert(NGP_FX_COPIES == 8, "eight words");
+    asm volatile("" : "+v"(L.w[0]), "+v"(L.w[1]), "+v"(L.w[2]), "+v"(L.w[3]), "+v"(L.w[4]), "+v"(L.w[5]), "+v"(L.w[6]), "+v"(L.w[7]));
+    unsigned long long q = L.w[0];
+#pragma unroll
+    for (int c = 1; c < NGP_FX_COPIES; c++) q += L.w[c];
+    return q;
 }
 // blocking form (whole wave polls the accumulator itself: one round trip from "last term added" to "in registers"); false on abort
 template <bool DBG, bool NGBIG = false>
@@ -1568,6 +1593,7 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
     int *outi = (int *)(outb + 2 * NGP_BLK);    // 2 x 64
     int *sabort = outi + 2 * NGP_BLK;
     int *totflag = sabort + 1;  // local block index + 1 whose corrected total is ready in r0[buf]
+    int *ztake = sabort + 2;    // 2 (block parity): local block + 1 whose accumulator wave 2 took in that block at lag >= 4 (0: none); wave 1 zeroes it
     int *smeth = sabort + 4;                     // method of each of the (at most 16) marker sets
     double *ssdf = (double *)(sabort + 20);      // scale * df of each set
     const int nb = A.t1 - A.t0;
@@ -1644,6 +1670,8 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
     if (tid == 0) {
         *sabort = 0;
         *totflag = 0;
+        ztake[0] = 0;
+        ztake[1] = 0;
         st_u32(A.xcc_w, xcc_id() + 1u);
         if (dbg) { dbg[NGP_DBG_ALL - 2] = xcc_id(); dbg[NGP_DBG_ALL - 1] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4); }
     }
@@ -1988,7 +2016,16 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
             }
 #undef NGP_LOAD_G
             hist[slot * NGP_BLK + j] = dsave;
-            // dlt leaves the chain wave at once as tagged granules (two fire-and-forget stores): streamers and reducers poll those.
+            // The next block's coefficients are taken over HERE, ahead of the granule stores (bo is a copy; nothing below reads cur).
+            // They were requested at the start of this block, so the s_waitcnt vmcnt(0) that the hand-over needs finds only what
+            // is a block period old: those loads and the previous block's stores.  Behind the stores -- where the hand-over used to
+            // stand -- the same wait also covered the two stores just issued (the compiler does not count across loads and stores
+            // pending together), and their acknowledgement, a round trip through the loaded fabric, stood in front of every block of
+            // the one wave whose serial path is the sweep's period.  The empty asm keeps the hand-over from sinking back.
+            cur = nxt;
+            asm volatile("" : "+v"(cur.bo), "+v"(cur.cc), "+v"(cur.ww), "+v"(cur.st), "+v"(cur.gd), "+v"(cur.tf));
+            // dlt leaves the chain wave at once as tagged granules (two fire-and-forget stores: nothing between them and the next
+            // block's total waits on vmcnt): streamers and reducers poll those.
             // (Handing this and the coefficient prefetch to wave 1 through an LDS flag was built and measured: wave 1's memory
             // operations queue behind the Gram blocks of five waves and it became the slowest wave -- 10k x 100k 1.71 -> 3.42 us
             // per block.)
@@ -1996,7 +2033,6 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
             outb[buf * NGP_BLK + j] = bo + dsave;
             outi[buf * NGP_BLK + j] = isave;
             if (dbg && j == 0) dbg[4 * (size_t)u + 1] = wall_clock64();
-            cur = nxt;
             NGP_END_OF_BLOCK();
         }
     } else if (wv == 1) {
@@ -2004,49 +2040,60 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
             tuple_prefetch(u + 1);
             rcls_prefetch(u + 1);
             if (u >= 1) publish_block<DBG>(A, u - 1, j, hist, outb, outi, smeth, ssdf);
+            // The accumulator that wave 2 took in block u-1 goes back to zero here, behind everything this wave publishes (wave 2 keeps
+            // no store of its own in its loop: a store pending with its look would turn the wait for the look into a wait for the
+            // store's acknowledgement).  Complete before the slot's next use: the stores leave in block u and are acknowledged at
+            // this wave's drain_vm in block u+1 (publish_block), ahead of that block's barrier; the chain wave issues the granules of
+            // dlt of block u+2 and later behind that barrier, so whoever has seen dlt of a block >= u+2 is ordered after the zeroing.
+            // The slot is taken by the block 16 on, whose terms a streamer or a reducer adds only after it has seen dlt of a block
+            // at least four later than the one taken (lag <= 12 = NGP_RING - 4), and the one taken is local block u or u+1.
+            // Every take of the loop of wave 2 happens before the last block, so every one is seen here.  A sweep that ends by the
+            // workgroup's abort flag may leave a taken accumulator unzeroed (take and zeroing were one step before): nothing reads
+            // it -- the abort poisons the chain until its state is set anew, k_prep zeroes every hand-off word ahead of every
+            // sweep, and a launch that fails its census ends before any role has run.
+            if (u >= 1) {
+                const int zb = __builtin_amdgcn_readfirstlane(ztake[(u - 1) & 1]);
+                if (zb != 0) acc_zero(A, zb - 1, j);
+            }
             NGP_END_OF_BLOCK();
         }
         if (nb >= 1) publish_block<DBG>(A, nb - 1, j, hist, outb, outi, smeth, ssdf);
     } else if (wv == 2) {
         // X_t'ycorr of the coming blocks -> r0 ring, from the blocks' fixed-point accumulators (ngp_common.h).  Lag >= 4: up to two blocks
-        // ahead -- the eight copies of the next accumulator are requested at the end of a block and looked at at the start of the
+        // ahead -- the eight copies of the next accumulator are requested in one block and looked at at the start of the
         // following one (the load is the probe: a complete count means the sum is final), so the memory round trip of this busy CU
         // never sits on the block period.  Lags 2-3: one block ahead, blocking.
         // (A streamer with lag >= 3 polls dlt_{u+1-D} before it publishes partial u, so the sum of block u+2 exists during block u
         // only when D >= 4.)
         if (D >= 4) {
             const double fxi = A.scal->fx_inv;
-            // One look per block, issued a WHOLE block period before it is examined: at the start of block u this wave first requests
-            // the accumulator of the block after the one whose look is in flight (speculating that that one will turn out
-            // complete -- it nearly always is: the sums stand two microseconds before they are needed), and only then examines the
-            // look requested at the start of block u-1.  Requested and examined in one go -- the round 1-3 counter probe, and the first
-            // version of this loop -- the wave sat one loaded memory round trip (1.9 us at 50k x 600k) in every block and was the last
-            // at the barrier in four blocks of five.
-            unsigned long long qa = 0ull;   // the look in flight ...
-            int la = -1;                    // ... and the block it looked at (-1: none)
+            // One look per block, in flight for a WHOLE block period: the wave examines the look it requested in the previous block
+            // and, finding it complete (it nearly always is: the sums stand two microseconds before they are needed), hands the
+            // zeroing of that accumulator to wave 1, requests the following block's look and goes to the barrier.  What it waits for
+            // at the start of a block is that one look, the only memory operation it has in flight: no request just issued, no
+            // store of its own.  (Requested and examined in one go -- the round 1-3 counter probe -- the wave sat one loaded memory
+            // round trip, 1.9 us at 50k x 600k, in every block and was the last at the barrier in four blocks of five; so it did,
+            // for 0.9 us, while a look was the SUM of eight loads: the adds and s_waitcnt vmcnt(0) stood right behind the request.)
+            AccLook lk = {};                // the look in flight ...
+            int la = -1;                    // ... and the block it looks at (-1: none)
             int next_take = 1;              // first local block whose sum has not been taken yet
+            unsigned relooks = 0;
             if (nb > 1) {  // once, at the start of the sweep: block 1 by a blocking fetch, so that the loop below runs two blocks ahead
                 double tot1;
                 if (fetch_group_sums<DBG, NGBIG>(A, 1, j, &tot1)) { r0[NGP_BLK + j] = tot1; next_take = 2; }
                 else if (j == 0) *sabort = 1;
             }
-            if (nb > 2) { qa = acc_load(A, 2, j); la = 2; }
             for (int u = 0; u < nb; ++u) {
-                // speculative request for the following block (examined a block from now: block ln must then be allowed in r0)
-                unsigned long long qn = 0ull;
-                int ln = -1;
-                {
-                    const int want = (la >= 0 ? la : next_take - 1) + 1;
-                    if (want < nb && want <= u + 3) { qn = acc_load(A, want, j); ln = want; }
-                }
+                int taken = 0;
                 if (next_take < nb && next_take <= u + 2) {  // r0[(u+2) & 3] is free: block u-2 is done
                     const bool must = (next_take == u + 1);   // the next block needs this sum
                     const unsigned terms = acc_terms(A, next_take);
-                    unsigned long long q = qa;
-                    bool ready = false;
                     int ok = 1;
-                    if (la == next_take) ready = dbg_mode == 2 || acc_complete(q, terms);
-                    else if (must || la < 0) { q = acc_load(A, next_take, j); ready = dbg_mode == 2 || acc_complete(q, terms); }  // (start of the sweep, or after a look that came too early)
+                    unsigned long long q;
+                    if (la == next_take) q = look_examine(lk);
+                    else q = acc_load(A, next_take, j);  // no look in flight (block 0 of the sweep): one round trip
+                    la = -1;
+                    bool ready = dbg_mode == 2 || acc_complete(q, terms);
                     if (!ready && must) {
                         for (unsigned spins = 0;; ++spins) {
                             __builtin_amdgcn_s_sleep(2);
@@ -2059,17 +2106,23 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
                     if (!ok) {
                         if (j == 0) *sabort = 1;
                     } else if (ready) {
-                        r0[(next_take & 3) * NGP_BLK + j] = acc_take(A, next_take, j, q, fxi);
-                        if (dbg && j == 0) dbg[4 * (size_t)next_take + 3] = wall_clock64();
+                        r0[(next_take & 3) * NGP_BLK + j] = acc_value(q, fxi);
+                        taken = next_take + 1;
                         ++next_take;
+                    } else {  // the look came too early (the sum is not needed yet): the same block is looked at again
+                        ++relooks;
+                    }
+                    const unsigned long long t_take = (dbg && taken) ? wall_clock64() : 0ull;
+                    // the ONE request of the block: examined a block from now (block next_take <= u + 3 may be in r0 then)
+                    if (ok && next_take < nb) { look_request(A, next_take, j, lk); la = next_take; }
+                    // (the diagnostic stores stand BEHIND the request: ahead of it the compiler waits for them before it lets the loads
+                    // write the look's registers)
+                    if (dbg && j == 0) {
+                        if (taken) dbg[4 * (size_t)(taken - 1) + 3] = t_take;
+                        else if (ok && !ready) dbg[NGP_DBG_RELOOK] = relooks;
                     }
                 }
-                // the speculative look becomes the look in flight if it is the right one for what comes next, else it is dropped
-                if (ln == next_take) { qa = qn; la = ln; }
-                else if (ln > next_take && ln >= 0) {  // its predecessor was not complete: look at that one again next time
-                    la = -1;
-                    if (next_take < nb && next_take <= u + 3) { qa = acc_load(A, next_take, j); la = next_take; }
-                } else la = -1;
+                if (j == 0) ztake[u & 1] = taken;
                 NGP_END_OF_BLOCK();
             }
         } else {

@@ -10,6 +10,7 @@
 #define NGP_DBG_RED (3u << 18)     // reducer 0: 2 words per block (counter complete, group sum published)
 #define NGP_DBG_W5 (5u << 17)      // sampler: 4 words per block (lag-1 wave: its Gram rows have arrived, its product is done; chain wave: has its total, has the diagonal block)
 #define NGP_DBG_ALL (7u << 17)     // every streamer: publish time of local block 800 and its XCC id
+#define NGP_DBG_RELOOK (NGP_DBG_ALL - 3)  // sampler, wave 2: looks of this launch that came too early and were repeated (a count, not a stamp)
 #define NGP_SPARSE_MAX 16  // BayesB / BayesC blocks with at most this many active lanes take the sparse chain
 // LDS distance of two quads of a tile: 1 KiB of data + 16 B, so that the update tasks (lanes = consecutive quads, same
 // columns) read conflict-free
