@@ -377,8 +377,10 @@ int32_t ngp_get_storage(ngp_handle *h, int32_t *storage, double *means, int64_t 
 int32_t ngp_debug_set_mode(ngp_handle *h, int32_t mode);
 /* Tuning knob of the row-owning streamer: pacing of its loader wave, 0..4 = s_sleep units (64 clocks) after every four tile
  * requests (default 0), + 16 = count every partial before the block's barrier, + 1024 (before the panel is set) = build the Gram window
- * on the matrix cores (v_mfma_f64_16x16x4_f64) instead of the fp64 VALU kernel: the same sums in the same order, bit for bit.  Changes timing
- * only, never results. */
+ * on the matrix cores (v_mfma_f64_16x16x4_f64) instead of the fp64 VALU kernel: the same sums in the same order, bit for bit;
+ * + 2048 = the row-owning streamers over fp32 tiles on the sampler's XCD do not warm its L2 with the next block's Gram planes;
+ * + 8192 = the warmer role (ngp_get_warmer) is withheld, + 16384 = it is offered below 160-row shards too;
+ * bits 16-27 = shard + 1 whose barrier-arrival timeline the diagnostic kernel records (0: shard 1).  Changes timing only, never results. */
 int32_t ngp_debug_set_knob(ngp_handle *h, int32_t knob);
 
 /* Resume support, second half: overwrite the posterior sums (same shapes as ngp_get_posterior_sums).  With ngp_set_state a
@@ -423,6 +425,11 @@ int32_t ngp_set_sample_file(ngp_handle *h, const char *path);
  * the chain, and the call runs it again with the whole device leased (the chains of one process then take turns) -- *retries counts
  * those, *exclusive says whether this handle now always leases the whole device.  Any pointer may be NULL. */
 int32_t ngp_get_census(ngp_handle *h, uint64_t *out, int64_t n, int64_t *grid, int64_t *retries, int32_t *exclusive);
+/* The warmer of the last persistent-sweep launch: where the last reducer workgroup has no far lag to correct and shares the sampler's
+ * XCD, it pulls the next blocks' Gram planes into that XCD's L2 in place of the streamers' loader waves (speed only).  *active = 1
+ * if it did, *blocks = blocks it warmed in that launch; both 0 where there is no such workgroup.  The role is offered beside the
+ * row-owning streamer over fp32 tiles with shards of 160 rows or more, where it was measured to pay.  Either pointer may be NULL. */
+int32_t ngp_get_warmer(ngp_handle *h, int32_t *active, int64_t *blocks);
 /* Test hook of that fallback: the sweep of iteration `iteration` (counted as ngp_get_state's iter) closes its own census as timed
  * out, once; the call must resume it and end bit for bit where an undisturbed chain ends.  0 = off. */
 int32_t ngp_debug_fail_census(ngp_handle *h, int64_t iteration);

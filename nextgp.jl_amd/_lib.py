@@ -156,6 +156,7 @@ SYMBOLS = [
     "ngp_add_random_set_dense", "ngp_set_records",
     "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
     "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
+    "ngp_get_warmer",
 ]
 
 _lib = None
@@ -815,6 +816,12 @@ class Sampler:
         self._chk(self.L.ngp_get_census(self.h, _p(tb, C.c_uint64), C.c_int64(g.value), None, None, None))
         return dict(grid=g.value, retries=r.value, exclusive=bool(e.value), xcc=(tb >> np.uint64(32)).astype(np.int64) - 1,
                     hw_id=(tb & np.uint64(0xFFFFFFFF)).astype(np.int64))
+
+    def warmer(self):
+        """The warmer of the last persistent-sweep launch (ngp_get_warmer): dict(active, blocks)."""
+        a, b = C.c_int32(), C.c_int64()
+        self._chk(self.L.ngp_get_warmer(self.h, C.byref(a), C.byref(b)))
+        return dict(active=a.value, blocks=b.value)
 
     def debug_fail_census(self, iteration):
         self._chk(self.L.ngp_debug_fail_census(self.h, C.c_int64(iteration)))

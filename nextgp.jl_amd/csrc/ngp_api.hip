@@ -515,6 +515,7 @@ struct ngp_handle {
     int knob = 0;  // ngp_debug_set_knob, timing only: bits 0-2 pace the loader wave of the row-owning streamer (s_sleep units after every four
                    // requests), bit 4 counts every partial before the block's barrier, bit 8 flips the publisher's early signal (the
                    // streamers read these through SweepArgs.knob); bit 10 builds the Gram window on the matrix cores (gram_engine)
+                   // bit 11 switches the streamers' L2 warming off, bit 13 withholds the warmer role, bit 14 offers it below 160-row shards, bits 16-27 select the shard of the diagnostic timeline (ngp_sweep.h)
     bool adding_r = false;  // ngp_add_marker_set is being called by ngp_add_marker_set_r
     bool poisoned = false;  // a sweep gave up half-way (abort word): the chain state is unusable until ngp_set_y / ngp_set_state
     bool exclusive = false;  // a grid of this handle was once not co-resident beside other chains' grids: its calls now lease the whole device
@@ -988,7 +989,21 @@ void fill_sweep_args(ngp_handle *h, int64_t tb0, int64_t tb1, SweepArgs &A) {
     A.census_fail = (h->dbg_census_fail_iter > 0 && !h->exclusive) ? (unsigned)h->dbg_census_fail_iter : 0u;
     A.dbg = h->hm.d_dbg;
     A.fine_ok = (streamer_lds(h->plan, 1) + 8192 <= sweep_lds(h->plan, SweepKernel::diag)) ? 1 : 0;  // diagnostic timeline fits in LDS
-    A.variant = h->plan.streamer; A.knob = h->knob;
+    // workgroup NG is a warmer candidate (role_warmer): one shard per streamer workgroup, its reducer without a far lag, and NG a multiple
+    // of eight, so that round-robin placement puts it on the sampler's XCD (the kernel reads the XCC ids; the fused and tall kernels ignore the bit)
+    // Not in a timing mode (ngp_debug_set_mode): those leave roles out -- no sampler whose word the warmer could read, no dlt to pace it -- and
+    // keep measuring the streamers as they always did; with knob bit 11 they show the streamers a warmer has relieved.
+    // Only beside the row-owning streamer over fp32 tiles, where the loaders' stream bounds the sweep: measured with the warmer, the phase
+    // streamer at 10k x 100k (160 KB of planes per 1.8-us block are more than one CU pulls) lost 22 %, byte tiles at 50k x 600k 1.3 %
+    // ("The warmer"; profiles/warm_helper_bench.json).  Knob bit 13 (timing only) withholds the role.
+    // And only from shards of 160 rows on: below, the sampler bounds the sweep, the loaders have time to spare, and one CU's warming reaches
+    // the L2 later than thirty loaders' (measured: R = 68 and 116 lose 1-3 % with the warmer, R = 164 gains 3 %, 196 9 %, 204 7.6 %).
+    // Knob bit 14 (timing only, the tests' way to the role at short shards) offers it at any height.
+    const bool warmer_tall = h->plan.R >= NGP_WARMER_MIN_R || (h->knob & NGP_KNOB_WARMER_ANY_R);
+    const bool warmer_idle = h->plan.NG > 0 && h->plan.NG % 8 == 0 && h->plan.near + h->plan.NG >= h->plan.D;
+    const bool warmer = h->dbg_mode == 0 && h->plan.streamer == 2 && h->plan.V == 1 && !(h->knob & NGP_KNOB_NO_WARMER) &&
+                        warmer_tall && warmer_idle;
+    A.variant = h->plan.streamer; A.knob = (h->knob & ~NGP_KNOB_WARMER) | (warmer ? NGP_KNOB_WARMER : 0);
     A.mean = h->pm->mean; A.N = h->N;
     A.dbg_mode = h->dbg_mode;
 }
@@ -4182,6 +4197,22 @@ int32_t ngp_get_census(ngp_handle *h, uint64_t *out, int64_t n, int64_t *grid, i
         HCHK(hipStreamSynchronize(h->stream));
         HCHK(hipMemcpy(out, h->cm.d_census_tbl, (size_t)g * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* The warmer of the last persistent-sweep launch (role_warmer, ngp_sweep.h): *active = 1 if workgroup NG shared the sampler's XCD and
+ * warmed its L2 in place of the streamers, *blocks = blocks it warmed.  Both are zero where there was no candidate. */
+int32_t ngp_get_warmer(ngp_handle *h, int32_t *active, int64_t *blocks) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm && h->plan.mode == 1, NGP_ERR_STATE, "no persistent sweep on this handle");
+    unsigned w[3] = {0, 0, 0};
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(w, h->cm.d_ccnt + h->cm.census_off + 8, sizeof(w), hipMemcpyDeviceToHost));
+    if (active) *active = w[1] ? 1 : 0;
+    if (blocks) *blocks = (int64_t)w[2];
     return NGP_OK;
     NGP_CATCH(h)
 }

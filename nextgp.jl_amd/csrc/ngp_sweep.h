@@ -226,6 +226,15 @@ __device__ inline void sld_u32x2(const unsigned *p0, const unsigned *p1, unsigne
                             (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a1));
     asm volatile("s_load_dword %0, %2, 0x0 glc\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v0), "=&s"(v1) : "s"(p0), "s"(p1) : "memory");
 }
+// two words that others write, both past the scalar cache, in one scalar round trip
+__device__ inline void sld_u32x2_glc(const unsigned *p0, const unsigned *p1, unsigned &v0, unsigned &v1) {
+    const unsigned long long a0 = (unsigned long long)p0, a1 = (unsigned long long)p1;
+    p0 = (const unsigned *)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a0 >> 32)) << 32) |
+                            (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a0));
+    p1 = (const unsigned *)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a1 >> 32)) << 32) |
+                            (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a1));
+    asm volatile("s_load_dword %0, %2, 0x0 glc\n\ts_load_dword %1, %3, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v0), "=&s"(v1) : "s"(p0), "s"(p1) : "memory");
+}
 // the 32 KiB the sampler stages for the chain of block t: T of a linear block, else the one-sided diagonal Gram block
 __device__ inline const double *chain_block_src(const SweepArgs &A, const long long t, const bool lin) {
     return lin ? A.tinv + (size_t)t * (NGP_BLK * NGP_BLK) : A.gramx + ((size_t)t * A.D + 0) * (NGP_BLK * NGP_BLK);
@@ -242,6 +251,15 @@ __device__ __attribute__((always_inline)) inline size_t warm_bytes(const SweepAr
 __device__ __attribute__((always_inline)) inline size_t warm_t_hi(const SweepArgs &A) { return A.tinv ? (size_t)(NGP_BLK * NGP_BLK * sizeof(double)) : 0; }
 __device__ __attribute__((always_inline)) inline size_t warm_shift(const SweepArgs &A) {
     return (A.tinv && !A.lin_all) ? (size_t)(NGP_BLK * NGP_BLK * sizeof(double)) : 0;
+}
+// The warmer's words (role_warmer), in the census block that k_prep zeroes before every launch: [0] written once it has decided: its XCC id + 1 if it
+// warms (it shares the sampler's XCD), else NGP_WARMER_DECLINED, [1] 1 = it warms, [2] blocks it has warmed
+__device__ __attribute__((always_inline)) inline unsigned *warmer_words(const SweepArgs &A) { return A.flag_dlt + 40; }
+// shard whose barrier-arrival timeline the diagnostic kernel records (NGP_FINE): bits 16-27 of the knob hold shard + 1, 0 = shard 1.
+// Read by k_sweep<true> only; the other kernels keep the constant.
+__device__ __attribute__((always_inline)) inline int fine_shard(const SweepArgs &A) {
+    const int f = (A.knob >> 16) & 0xfff;
+    return f ? f - 1 : 1;
 }
 
 // gemv4: v_j = sum_k G[k][j] * d[k], four interleaved partial sums, ((s0+s1)+(s2+s3))
@@ -291,7 +309,7 @@ __device__ inline void role_streamer(const SweepArgs &A, const int s, char *smem
     // diagnostic runs, short shards only (the workgroup's LDS is sized by the sampler then): barrier-arrival stamps of
     // every wave of streamer 1 for local blocks 800..815, staged in LDS and dumped at the end
     unsigned long long *fine = (unsigned long long *)(pp + 8 * (size_t)R);
-    const bool fine_on = dbg && s == 1 && A.fine_ok == 1;
+    const bool fine_on = dbg && s == (DBG ? fine_shard(A) : 1) && A.fine_ok == 1;
 #define NGP_FINE(k)                                                                                          \
     do {                                                                                                     \
         if (fine_on && (unsigned)(u - 800) < 16u && j == 0) fine[(((u - 800) * 8 + wv) << 3) + (k)] = wall_clock64(); \
@@ -696,7 +714,7 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
     int *sflag = (int *)(rsy + 16);
     char *scratch = (char *)(rsy + 16) + 64;                 // 1 KiB sink of the L2-warming DMA
     unsigned long long *fine = (unsigned long long *)(scratch + 1024);  // diagnostic timeline (DBG only, if it fits)
-    const bool fine_on = DBG && dbg && s == 1 && A.fine_ok == 1;
+    const bool fine_on = DBG && dbg && s == (DBG ? fine_shard(A) : 1) && A.fine_ok == 1;
 #define NGP_FINE(k)                                                                                              \
     do {                                                                                                         \
         if (fine_on && (unsigned)(u - 800) < 16u && lane == 0) fine[(((u - 800) * 8 + wv) << 3) + (k)] = wall_clock64(); \
@@ -778,10 +796,21 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
             // (the sampler's XCC id is read until it is known -- a scalar load that bypasses the scalar cache costs the
             // loader about 1.5 us, during which it requests nothing: re-read every eighth block for the whole sweep, as the phase
             // streamer does, it put 511 blocks of 6 us and more into a 50k x 600k sweep)
+            // (where workgroup NG may be the warmer -- role_warmer -- its word comes in the same round trip: a streamer on the sampler's
+            // XCD warms unless the warmer sits there too.  Both sides decide from the same two write-once words.)
+            // (fp32 tiles only: the host offers the role nowhere else, and the byte-tile loader keeps its code as it was)
             if (!xcc_known && (u & 7) == 0) {
-                const unsigned x = sld_u32(A.xcc_w);
-                xcc_known = (x != 0u);
-                same_xcd = (x == my_xcc);
+                if constexpr (U8) {
+                    const unsigned x = sld_u32(A.xcc_w);
+                    xcc_known = (x != 0u);
+                    same_xcd = (x == my_xcc);
+                } else {
+                    unsigned x, wx = 0u;
+                    if (A.knob & NGP_KNOB_WARMER) sld_u32x2_glc(A.xcc_w, warmer_words(A), x, wx);
+                    else x = sld_u32(A.xcc_w);
+                    xcc_known = (x != 0u) && (x != my_xcc || !(A.knob & NGP_KNOB_WARMER) || wx != 0u);
+                    same_xcd = (x == my_xcc) && (wx != x) && !(A.knob & NGP_KNOB_NO_WARM);
+                }
             }
             if (same_xcd && u + 1 < nb && !no_dma) {
                 const char *gb = (const char *)(A.gramx + (size_t)(A.t0 + u + 1) * DT * NGP_BLK * NGP_BLK) - w_shift;
@@ -1394,6 +1423,71 @@ __device__ __attribute__((always_inline)) inline void role_reducer(const SweepAr
             if (dbg && g == 0 && lane == 0) dbg[NGP_DBG_RED + 2 * (size_t)u + 1] = wall_clock64();
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Warmer: workgroup NG where that reducer has no far lag (host: NGP_KNOB_WARMER) and the dispatcher has put it on the sampler's XCD
+// (round-robin placement with NG = 8: XCD 0, the sampler's).  It pulls the Gram planes the sampler reads for block t -- the pieces the
+// same-XCD streamers' loaders request otherwise, which then go back to their tiles alone -- into that XCD's L2.  Wave-independent as the
+// reducers: wave w serves blocks w, w + 8, ...; block t is requested once dlt of block t - D - NGP_WARM_DIST is out, which is when a
+// streamer at the lag limit requests it.  Speed only: nobody waits for the warmer, a late or absent warmer changes no value, and its own
+// waits give up silently (no abort code).
+#ifndef NGP_WARM_DIST
+#define NGP_WARM_DIST 1
+#endif
+#define NGP_WARMER_DECLINED 0xFFu
+template <bool DBG>
+__device__ __attribute__((always_inline)) inline void role_warmer(const SweepArgs &A, char *smem) {
+    NGP_DBG_LOCALS
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nb = A.t1 - A.t0, DT = A.D;
+    unsigned *ww = warmer_words(A);
+    const unsigned my_xcc = xcc_id() + 1u;
+    // (the host offers the role in production launches only, never in a timing mode: no dbg_mode to look at here)
+    unsigned x = 0u;
+    for (unsigned spins = 0; spins < (1u << 14); ++spins) {  // the sampler's word: written as its first act (about 30 ms at the most)
+        x = ld_u32(A.xcc_w);
+        if (x != 0u) break;
+        if ((spins & 31u) == 31u && ld_u32(A.abort_w) != 0u) break;
+        __builtin_amdgcn_s_sleep(8);
+    }
+    // Its own word goes out only now, with the decision in it: its XCC id + 1 if it warms, else "declined" (no XCC id + 1 is that large) --
+    // on another XCD, or the sampler's word never came.  The same-XCD streamers warm until they have read it and go on if it declines.
+    const bool warms = (x == my_xcc);
+    if (tid == 0) {
+        if (warms) st_u32(ww + 1, 1u);
+        st_u32(ww, warms ? my_xcc : NGP_WARMER_DECLINED);
+    }
+    if (!warms) return;
+    const unsigned sink = (unsigned)(size_t)(__attribute__((address_space(3))) const char *)(smem + wv * 1024);  // 1 KiB per wave
+    const unsigned voff = (unsigned)lane * 16u;
+    const size_t gram_bytes = warm_bytes(A, min(DT, A.near + 1)), w_thi = warm_t_hi(A), w_shift = warm_shift(A);
+    unsigned done = 0u;
+    for (int t = wv; t < nb; t += NGP_WG / 64) {
+        const int a = t - DT - NGP_WARM_DIST;
+        if (a >= 0) {
+            // One granule of block a.  Not wait_dlt_granules_all: that wait wants the tag of block a itself and raises an abort code at
+            // its bound, right for a reducer, whom the sampler cannot overtake.  Nobody waits for the warmer: a late wave may find a
+            // LATER block of this launch in the slot (tag of dlt_tag: nonce << 20 | block + 1, so "same nonce, block number >= a + 1"),
+            // and at the bound it stops warming and says nothing.
+            const unsigned long long *gp = A.dltg + (size_t)(a % NGP_RING) * NGP_BLK * 2;
+            bool ok = false;
+            for (unsigned spins = 0; spins <= (NGP_SPIN_LIMIT >> 3); ++spins) {
+                const unsigned tag = (unsigned)(ld_u64(gp) >> 32);
+                if ((tag >> 20) == A.nonce && (tag & 0xFFFFFu) >= (unsigned)(a + 1)) { ok = true; break; }
+                if ((spins & 7u) == 7u && ld_u32(A.abort_w) != 0u) break;
+                __builtin_amdgcn_s_sleep(2);
+            }
+            if (!ok) break;
+        }
+        const char *gb = (const char *)(A.gramx + (size_t)(A.t0 + t) * DT * NGP_BLK * NGP_BLK) - w_shift;
+        const char *tb = (const char *)(A.tinv + (size_t)(A.t0 + t) * NGP_BLK * NGP_BLK);
+        for (size_t off = 0; off + 1024 <= gram_bytes; off += 1024) dma16_warm(sink, (off < w_thi ? tb : gb) + off, voff);
+        ++done;
+    }
+    drain_vm();
+    if (lane == 0 && done) atomicAdd(ww + 2, done);
 }
 
 // ------------------------------------------------------------------------------------------

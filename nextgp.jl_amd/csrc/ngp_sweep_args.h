@@ -25,6 +25,12 @@
 #define NGP_ABORT_CENSUS 9u        // abort code: the grid was not co-resident within NGP_CENSUS_TICKS (no state was modified)
 #define NGP_CENSUS_TICKS 2000000ull  // 20 ms of the 100 MHz wall clock
 #define NGP_DBG_STREAM (1u << 20)  // offset of streamer 0's stamps in the debug buffer
+// bits of SweepArgs.knob beyond the loader's pace and the publisher's signals (ngp_debug_set_knob):
+#define NGP_KNOB_NO_WARM 2048  // bit 11 (timing only): the row-owning streamers over fp32 tiles do not warm (role_streamer_rows), folded into same_xcd where the XCC word is read
+#define NGP_KNOB_WARMER 4096   // bit 12, set by the host alone (fill_sweep_args): workgroup NG has no far lag and takes the warmer role if it shares the sampler's XCD
+#define NGP_KNOB_NO_WARMER 8192    // bit 13 (timing only): the host withholds the warmer role
+#define NGP_KNOB_WARMER_ANY_R 16384  // bit 14 (timing only): the host offers the role below NGP_WARMER_MIN_R rows per shard too
+#define NGP_WARMER_MIN_R 160       // shard height from which the warmer was measured to pay ("The warmer")
 
 namespace ngp {
 

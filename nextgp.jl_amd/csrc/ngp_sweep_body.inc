@@ -12,9 +12,10 @@
     if ((dbg_mode == 2 && b != 0) || ((dbg_mode == 3 || dbg_mode == 4) && b == 0)) return;
     if (b == 0)
         role_sampler<DBG, false, TUP, RCLSV>(A, smem);
-    else if (b <= A.NG)
-        role_reducer<DBG>(A, b - 1, smem);
-    else {
+    else if (b <= A.NG) {
+        if (b == A.NG && (A.knob & NGP_KNOB_WARMER)) role_warmer<DBG>(A, smem);  // (that reducer would return at once: no far lag is its)
+        else role_reducer<DBG>(A, b - 1, smem);
+    } else {
         const int s = b - 1 - A.NG;
         if (A.variant == 2) {  // row-owning waves + loader wave (host: R <= NGP_ROWS_MAX_R, lag 3..6)
             switch (A.D) {

@@ -201,6 +201,13 @@ function shards_for_pass(h::Handle, chains::Integer)
     return Int(v[])
 end
 
+# The warmer of the last persistent-sweep launch (ngp_get_warmer): did the last reducer workgroup warm the sampler's L2, and how many blocks.
+function warmer(h::Handle)
+    a = Ref{Int32}(0); b = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_warmer, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}), h.ptr, a, b))
+    (active = Int(a[]), blocks = Int(b[]))
+end
+
 # Kept samples to a binary file while the chain runs (instead of a text row per kept iteration, src/samplers.jl:56-104): call before
 # run!, close with `nothing`; nextgp.jl_amd/api.py (samples_to_out_files) or the reader below turn the file into the *Out tables.
 set_sample_file!(h::Handle, path::Union{AbstractString,Nothing}) =

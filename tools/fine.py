@@ -1,4 +1,5 @@
-"""Barrier-arrival timeline of one streamer (diagnostic): per wave, time of each stamp relative to the iteration start."""
+"""Barrier-arrival timeline of one streamer (diagnostic): per wave, time of each stamp relative to the iteration start.
+python tools/fine.py lag N P streamer [shard]"""
 import sys, os, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ngp_pkg import load_pkg
@@ -9,7 +10,8 @@ P = int(sys.argv[3]) if len(sys.argv) > 3 else 100000
 s = ngp.Sampler(device=0, seed=1001, chain=0, mode=1, lag=lag, streamer=int(sys.argv[4]) if len(sys.argv) > 4 else None,
                 storage=os.environ.get("NGP_TOOL_STORAGE"))
 if "NGP_TOOL_CHAIN_FORM" in os.environ: s.set_chain_form(int(os.environ["NGP_TOOL_CHAIN_FORM"]))
-if "NGP_TOOL_KNOB" in os.environ: s.debug_set_knob(int(os.environ["NGP_TOOL_KNOB"]))
+shard = int(sys.argv[5]) if len(sys.argv) > 5 else 1  # streamer whose timeline is recorded (knob bits 16-27 hold shard + 1)
+s.debug_set_knob(int(os.environ.get("NGP_TOOL_KNOB", "0")) | ((shard + 1) << 16))
 if "NGP_TOOL_NEAR" in os.environ: s.set_near(int(os.environ["NGP_TOOL_NEAR"]))
 s.generate_panel(N, P)
 rng = np.random.default_rng(1); bt = np.zeros(P); idx = rng.choice(P, P // 100, replace=False); bt[idx] = rng.normal(size=P // 100)
@@ -30,6 +32,7 @@ t0 = F[:, :, 0].min(axis=1)  # earliest wave start of each iteration
 names = ["start", "A done", "B1 (pp written)", "B2 (ys updated)", "C gemv done", "C poll done", "iter end", "A: tile drained (w4-6)"]
 if s.streamer()[0] >= 2:  # row-owning waves (waves 0-6) + loader (wave 7: start, requests issued, counted wait done)
     names = ["start", "update done | w7 issued", "gemv done | w7 landed", "keep filled", "dlt fetched", "past barrier", "published", "-"]
+print(f"shard {shard}")
 print("stamp (us after the first wave's start of the iteration), median over 16 iterations; rows = waves 0..7")
 for k in range(8):
     rel = (F[:, :, k] - t0[:, None]) / 100.0
