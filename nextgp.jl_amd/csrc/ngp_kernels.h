@@ -279,7 +279,9 @@ __global__ __launch_bounds__(256) void k_prep(long long Ppad, const int8_t *__re
         double qv[NGP_RMAX], av[NGP_RMAX], u0 = 1.0;  // (kept for the lazy threshold below)
         for (int v = 0; v < S.K; v++) {
             const double varc = varB * S.vcls[v];
-            Rng ruu = rng_seed(seed, chain, it, NGP_KIND_R_UNIFORM, ((uint64_t)si << 40) | (l << 3) | (uint64_t)v);
+            // three bits hold the comparison: v < 8 under NGP_KIND_R_UNIFORM, v >= 8 under NGP_KIND_R_UNIFORM_HI (no bit of v reaches the locus)
+            static_assert(NGP_RMAX <= 16, "the class-search uniforms pack v & 7 into three bits under two kinds");
+            Rng ruu = rng_seed(seed, chain, it, v < 8 ? NGP_KIND_R_UNIFORM : NGP_KIND_R_UNIFORM_HI, ((uint64_t)si << 40) | (l << 3) | (uint64_t)(v & 7));
             const double uv = rng_uniform(ruu);
             ru[(size_t)v * Ppad + k] = uv;
             if (v == 0) u0 = uv;

@@ -28,6 +28,7 @@
 #define NGP_KIND_LV_NORMAL 15   // BayesLV sets: the normal of coefficient k of the log-variance regression, (set << 40) | k (src/functions.jl:477)
 #define NGP_KIND_LV_START 16    // BayesLV sets: the starting value of a locus' zeta (iteration 0), (set << 40) | locus (src/mme.jl:430)
 #define NGP_KIND_U_WISHART 17   // tuple random-effect sets: Bartlett factor of varU's inverse-Wishart draw, (set << 40) | (i << 4) | j, (i, j) != (0, 0)
+#define NGP_KIND_R_UNIFORM_HI 18  // BayesR: comparisons v >= 8 of the class search, (set << 40) | (locus << 3) | (v - 8); kind 8 keeps v < 8 with (locus << 3) | v
 
 #define NGP_GOLD 0x9E3779B97F4A7C15ULL
 

@@ -57,6 +57,7 @@
 #define KIND_PI_BETA 7
 #define KIND_R_UNIFORM 8   /* BayesR: the fresh uniform of every comparison of the class search (functions.jl:261) */
 #define KIND_R_DIRICHLET 9
+#define KIND_R_UNIFORM_HI 18 /* BayesR: comparisons v >= 8 of the class search, index (set << 40) | (l << 3) | (v - 8); kind 8 keeps v < 8 */
 /* fixed-effect columns beyond the intercept draw from KIND_FIXED_NORMAL with index ((set + 1) << 20) | column */ /* BayesR: gamma draws of the Dirichlet (functions.jl:536-538) */
 
 #define METHOD_PR 0
@@ -64,6 +65,7 @@
 #define METHOD_C 2 /* BayesC: src/functions.jl:197-235 */
 #define METHOD_R 3 /* BayesR: src/functions.jl:238-289 */
 #define RMAX 16    /* variance classes of a BayesR set (functions.jl:241-262 sizes everything by length(vClass)) */
+_Static_assert(RMAX <= 16, "the class-search uniforms pack v & 7 into three bits under two kinds");
 #define METHOD_T 4 /* correlated (Tuple) BayesPR: src/functions.jl:140-154, 513-516; set-up src/mme.jl:448-489 */
 #define KMAX 4     /* marker sets of one tuple */
 #define KIND_T_WISHART 11 /* Bartlett factor of a region's inverse-Wishart draw: index (set << 40) | (region << 8) | (i << 4) | j */
@@ -1162,7 +1164,7 @@ static void iter_ref(ora_t *h) {
                 double cum = 0.0;
                 for (int v = 0; v < K; v++) {
                     cum += ExpLogL[v] / sum;                                                      /* :259-260 */
-                    rng_seed(&r, h->seed, h->chain, it, KIND_R_UNIFORM, ((uint64_t)si << 40) | ((uint64_t)l << 3) | (uint64_t)v);
+                    rng_seed(&r, h->seed, h->chain, it, v < 8 ? KIND_R_UNIFORM : KIND_R_UNIFORM_HI, ((uint64_t)si << 40) | ((uint64_t)l << 3) | (uint64_t)(v & 7));
                     if (cum >= rng_uniform(&r)) { cls = v; break; }                               /* :261 */
                 }
                 h->delta[j] = cls + 1;                                                            /* :262, classes count from 1 */
@@ -1346,7 +1348,7 @@ static void iter_blocked(ora_t *h) {
                     double zr = rng_normal(&r);
                     for (int v = 0; v < Sx->K; v++) {
                         double varc = vb[0] * Sx->vcls[v];
-                        rng_seed(&r, h->seed, h->chain, it, KIND_R_UNIFORM, ((uint64_t)si << 40) | ((uint64_t)l << 3) | (uint64_t)v);
+                        rng_seed(&r, h->seed, h->chain, it, v < 8 ? KIND_R_UNIFORM : KIND_R_UNIFORM_HI, ((uint64_t)si << 40) | ((uint64_t)l << 3) | (uint64_t)(v & 7));
                         ru[v * PP + k] = rng_uniform(&r);
                         if (varc == 0.0) { rq[v * PP + k] = 0.0; ra[v * PP + k] = Sx->logpic[v]; rt[v * PP + k] = 0.0; }
                         else {

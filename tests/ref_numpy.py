@@ -24,7 +24,7 @@ import math
 import numpy as np
 
 KIND = dict(VARE_CHI2=1, FIXED_NORMAL=2, BETA_NORMAL=3, REGION_CHI2=4, B_UNIFORM=5, B_LOCUS_CHI2=6, PI_BETA=7, R_UNIFORM=8, R_DIRICHLET=9,
-            T_WISHART=11)
+            T_WISHART=11, R_UNIFORM_HI=18)
 
 
 class RefChain:
@@ -214,7 +214,7 @@ class RefChain:
                 cumProbs = np.cumsum(probs)
                 classSNP = nVarClass - 1
                 for v in range(nVarClass):                    # findfirst(x -> x >= rand(), cumProbs): a fresh uniform per comparison
-                    if cumProbs[v] >= self.draw("R_UNIFORM", (si << 40) | (locus << 3) | v, 0):
+                    if cumProbs[v] >= self.draw("R_UNIFORM" if v < 8 else "R_UNIFORM_HI", (si << 40) | (locus << 3) | (v & 7), 0):
                         classSNP = v
                         break
                 delta[locus] = classSNP + 1                                                       # :262
