@@ -40,6 +40,7 @@ extern "C" {
 #define NGP_METHOD_BAYESR 3  /* src/runTime.jl:78-93, sampler src/functions.jl:238-289; added with ngp_add_marker_set_r */
 #define NGP_METHOD_TUPLE 4   /* correlated sets, BayesPR's Tuple method: src/functions.jl:140-154; added with ngp_add_marker_set_tuple */
 #define NGP_METHOD_BAYESLV 5 /* src/runTime.jl:116-133, sampler src/functions.jl:421-486; added with ngp_add_marker_set_lv */
+#define NGP_METHOD_BAYESRC 6 /* BayesRCpi, annotation-informed BayesR: sampler src/functions.jl:291-360; added with ngp_add_marker_set_rc */
 #define NGP_LV_MAXCOV 16     /* most columns of a BayesLV set's covariate matrix */
 
 typedef struct ngp_handle ngp_handle;
@@ -73,7 +74,9 @@ int32_t ngp_get_near_lags(ngp_handle *h, int32_t *near);
 int32_t ngp_set_chain_form(ngp_handle *h, int32_t form);
 int32_t ngp_get_chain_form(ngp_handle *h, int32_t *form);
 /* Diagnostic only: enable != 0 makes the persistent kernel write 100 MHz time stamps (sampler: 4 words per
- * block at [4u..4u+3]; streamer 0: 2 words per block from word 2^20); out/n copies the first n words back. */
+ * block at [4u..4u+3]; streamer 0: 2 words per block from word 2^20); out/n copies the first n words back.  The stamps exist in the
+ * diagnostic kernel only, which does not carry the rule of BayesRCpi sets: enabling them on a model with such a set is NGP_ERR_ARG
+ * (and ngp_add_marker_set_rc refuses a handle whose stamps or timing mode are on). */
 int32_t ngp_debug_stamps(ngp_handle *h, int32_t enable, uint64_t *out, int64_t n);
 
 /* Marker panel, N individuals x P SNPs, column-major with leading dimension ld >= N
@@ -373,7 +376,8 @@ int32_t ngp_get_storage(ngp_handle *h, int32_t *storage, double *means, int64_t 
 
 /* Diagnostic timing modes of the persistent kernel (1..6: parts of the pipeline switched off, ngp_sweep.h).  They are an
  * explicit, per-handle setting -- never read from the environment -- and while one is active ngp_run / ngp_sweep_set do
- * their launches and then return NGP_ERR_DEBUG: the chain they leave behind is invalid.  0 = off. */
+ * their launches and then return NGP_ERR_DEBUG: the chain they leave behind is invalid.  0 = off.  A model with a BayesRCpi set
+ * takes 0 only (NGP_ERR_ARG otherwise): its sweep kernel has no timing modes. */
 int32_t ngp_debug_set_mode(ngp_handle *h, int32_t mode);
 /* Tuning knob of the row-owning streamer: pacing of its loader wave, 0..4 = s_sleep units (64 clocks) after every four tile
  * requests (default 0), + 16 = count every partial before the block's barrier, + 1024 (before the panel is set) = build the Gram window
@@ -523,6 +527,33 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
  * inert block of 64 zero columns in place of the panel: state and file formats are those of a model with P = 64 and no marker set
  * (beta and its sums 64 zeros, delta 64 ones, no variance component), nothing is ever swept. */
 int32_t ngp_set_records(ngp_handle *h, int64_t N);
+
+/* BayesRCpi marker set -- annotation-informed BayesR, BayesRCπ(pi, class, v, annot) of the reference (set-up src/mme.jl:384-403, :493-516;
+ * sampler src/functions.jl:291-360, :518-520, :536-544; output src/mme.jl:573-576, src/samplers.jl:85-87).  A annotations (annot:
+ * ncol x A int32 entries 0 / 1, column-major with leading dimension ld), K variance classes vClass with probabilities pi (sum 1), ONE
+ * variance per annotation (nVarCov = A, all starting at varBeta0), piHat[a] = pi for every annotation, annotProb[l, a] = annot[l, a] /
+ * sum_a annot[l, a].  Limits: K >= 2, 1 <= A <= 8, A K <= 16.  NGP_ERR_ARG for a locus without an annotation (the reference divides
+ * 0 / 0 there and throws in Categorical; its own comment says such loci belong in another set) and for entries other than 0 / 1.
+ * Per sweep and locus: the annotation by one inverse-CDF uniform on the annotations' total weights, then the class inside it by the
+ * search of BayesR (a fresh uniform per comparison), from log-weights log pi[a][v] - log(varc lhs) / 2 + log annotProb[l, a] taken
+ * relative to their maximum ("BayesRCpi sets": the normative arithmetic, the draw keys and the departures from
+ * the literal lines).  Behind the sweep: varBeta[a] = (scale df + sumS[a]) / chi2(df + nNonZero[a]); estPi: pi[a] ~ Dirichlet(nLoci[a, :]
+ * + 1); and always annotProb[l, present] ~ Dirichlet(1 + [a == annotCat[l]]).  delta holds the class, annotCat the annotation of a
+ * locus, both from 1.  In ngp_get_state / ngp_set_state / ngp_sweep_set the set has A variances; piHat is a [0.5, 0.5] placeholder
+ * there (ngp_sweep_set takes piHat == NULL).  ngp_get_rc_state / ngp_set_rc_state carry the rest: piHat[A K] and sum_pi[A K]
+ * (annotation-major; ngp_get_class_state sees the same A K words), annotProb[ncol A] and sum_annot[ncol A] (column-major, leading
+ * dimension ncol), annotCat[ncol]; any pointer may be NULL.  sum_annot[l, a] counts the kept iterations with annotCat[l] = a + 1.  All
+ * of it travels in the packed posterior (sums), sample records and snapshots (csrc/ngp_state.h).  Served by the persistent sweep
+ * (fp32 and compact tiles; a kernel of its own) and the per-block engine, also beside other methods in one 64-column block; fp32
+ * panels whose streamer workgroups own several shards are refused.  ngp_run_many runs chains of such a model side by side (unfused):
+ * a fused kernel for them does not exist.  BayesRCplus is not on the device (one step per annotation on the same column,
+ * src/functions.jl:362-419: a different block chain). */
+int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double df, double scale, double varBeta0, const double *vClass,
+                              const double *pi, int32_t K, const int32_t *annot, int64_t ld, int32_t A, int32_t estPi, const double *lhs0,
+                              const double *rhs0, int32_t *set_id);
+int32_t ngp_get_rc_state(ngp_handle *h, int32_t set_id, double *piHat, double *sum_pi, double *annotProb, int32_t *annotCat, double *sum_annot);
+int32_t ngp_set_rc_state(ngp_handle *h, int32_t set_id, const double *piHat, const double *sum_pi, const double *annotProb, const int32_t *annotCat,
+                         const double *sum_annot);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NGP_HIP_LIB") or os.path.join(_HERE, "libnextgp_hip.so")  # override: a library built elsewhere
 
-METHOD_BAYESPR, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESR, METHOD_TUPLE, METHOD_BAYESLV = 0, 1, 2, 3, 4, 5
+METHOD_BAYESPR, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESR, METHOD_TUPLE, METHOD_BAYESLV, METHOD_BAYESRC = 0, 1, 2, 3, 4, 5, 6
 LV_MAXCOV, LV_WORDS = 16, 17  # a BayesLV set in a sample record: c padded to 16 words | varZeta
 
 
@@ -20,18 +20,23 @@ def _sample_header(f, path):
     """(P, nvb, nsets, nfix, nclass, record bytes, sets, random-effect q per set, (set, ncov) per BayesLV set) of an open sample file,
     positioned at its first record."""
     magic = f.read(8)
-    if magic not in (b"NGPSMP01", b"NGPSMP02", b"NGPSMP03"):
+    if magic not in (b"NGPSMP01", b"NGPSMP02", b"NGPSMP03", b"NGPSMP04"):
         raise NextGPHipError(f"not a sample file: {path}")
     P, nvb, nsets, nfix, ncls, rec = (int(v) for v in np.frombuffer(f.read(48), dtype=np.int64))
     sets = [dict(zip(("method", "K", "col0", "ncol", "nvb", "tk"), np.frombuffer(f.read(48), dtype=np.int64).tolist())) for _ in range(nsets)]
     rq = []
-    if magic in (b"NGPSMP02", b"NGPSMP03"):  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
+    if magic in (b"NGPSMP02", b"NGPSMP03", b"NGPSMP04"):  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
         nr = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
         rq = np.frombuffer(f.read(8 * nr), dtype=np.int64).tolist()
     lv = []
-    if magic == b"NGPSMP03":  # BayesLV sets: int64 nlv | (marker set, ncov) per set; records hold c[16] | varZeta behind the class probabilities
+    if magic in (b"NGPSMP03", b"NGPSMP04"):  # BayesLV sets: int64 nlv | (marker set, ncov) per set; records hold c[16] | varZeta behind the class probabilities
         nl = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
         lv = [tuple(np.frombuffer(f.read(16), dtype=np.int64).tolist()) for _ in range(nl)]
+    if magic == b"NGPSMP04":  # BayesRCpi sets: int64 nrc | (marker set, A, K) per set; records hold annotProb[A][ncol] behind the BayesLV words
+        nrc = int(np.frombuffer(f.read(8), dtype=np.int64)[0])  # and annotCat[ncol] (uint8) behind delta.  They ride on the sets' entries.
+        for _ in range(nrc):
+            si, A, K = np.frombuffer(f.read(24), dtype=np.int64).tolist()
+            sets[si].update(rcA=A, rcK=K)
     return P, nvb, nsets, nfix, ncls, rec, sets, rq, lv
 
 
@@ -48,6 +53,17 @@ def _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv):
                     ("beta", P), ("varBeta", nvb), ("piHat", 2 * nsets), ("class_pi", ncls)] + [(f"lv{i}", LV_WORDS) for i in range(len(lv))]):
         at[name] = (o, n); o += n
     return at, o
+
+
+def _sample_rc(sets, nd, P):
+    """BayesRCpi sets of a sample file: [(marker set, ncol, A, first double of annotProb, first byte of annotCat behind the doubles)],
+    and the doubles of a record in front of delta with their annotProb counted in."""
+    out, cat = [], P
+    for si, s in enumerate(sets):
+        if "rcA" in s:
+            out.append((si, s["ncol"], s["rcA"], nd, cat))
+            nd += s["rcA"] * s["ncol"]; cat += s["ncol"]
+    return out, nd
 
 
 def _sample_record(d, at, rq, lv):
@@ -71,9 +87,14 @@ def read_sample_file(path):
         raw = np.frombuffer(f.read(), dtype=np.uint8)
     n = len(raw) // rec
     raw = raw[:n * rec].reshape(n, rec)
-    at, nd = _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv)
-    out = _sample_record(raw[:, :nd * 8].copy().view(np.float64), at, rq, lv)
+    at, nd0 = _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv)
+    rcs, nd = _sample_rc(sets, nd0, P)
+    d = raw[:, :nd * 8].copy().view(np.float64)
+    out = _sample_record(d, at, rq, lv)
     out.update(iter=raw[:, :8].copy().view(np.int64)[:, 0], sets=sets, delta=raw[:, nd * 8:nd * 8 + P])
+    if rcs:  # per BayesRCpi set, keyed by its marker set: annotProb [n, ncol, A], annotCat [n, ncol]
+        out["annotProb"] = {si: d[:, o:o + A * nc].reshape(n, A, nc).transpose(0, 2, 1) for si, nc, A, o, _ in rcs}
+        out["annotCat"] = {si: raw[:, nd * 8 + c:nd * 8 + c + nc] for si, nc, A, _, c in rcs}
     return out
 
 
@@ -88,11 +109,16 @@ def iter_sample_file(path):
     n = (size - off) // rec
     if n <= 0:
         return
-    at, nd = _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv)
+    at, nd0 = _sample_fields(P, nvb, nsets, nfix, ncls, rq, lv)
+    rcs, nd = _sample_rc(sets, nd0, P)
     mm = np.memmap(path, dtype=np.uint8, mode="r", offset=off, shape=(n, rec))
     for i in range(n):
-        out = _sample_record(np.frombuffer(mm[i, :nd * 8].tobytes(), dtype=np.float64), at, rq, lv)
+        d = np.frombuffer(mm[i, :nd * 8].tobytes(), dtype=np.float64)
+        out = _sample_record(d, at, rq, lv)
         out.update(iter=int(np.frombuffer(mm[i, :8].tobytes(), dtype=np.int64)[0]), sets=sets, delta=np.asarray(mm[i, nd * 8:nd * 8 + P]))
+        if rcs:
+            out["annotProb"] = {si: d[o:o + A * nc].reshape(A, nc).T for si, nc, A, o, _ in rcs}
+            out["annotCat"] = {si: np.asarray(mm[i, nd * 8 + c:nd * 8 + c + nc]) for si, nc, A, _, c in rcs}
         yield out
     del mm
 
@@ -157,6 +183,7 @@ SYMBOLS = [
     "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
     "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
     "ngp_get_warmer",
+    "ngp_add_marker_set_rc", "ngp_get_rc_state", "ngp_set_rc_state",
 ]
 
 _lib = None
@@ -623,6 +650,47 @@ class Sampler:
         self.set_shapes.append((ncol, 1))
         self.nclasses = getattr(self, "nclasses", 0) + len(vc)
         return sid.value
+
+    def add_marker_set_rc(self, col0, ncol, df, scale, varBeta0, vClass, pi, annot, estPi=False, lhs0=None, rhs0=None):
+        """BayesRCpi set (annotation-informed BayesR, src/mme.jl:384-403): annot is ncol x A with entries 0 / 1, every locus with at least
+        one annotation; K classes vClass with probabilities pi for every annotation; one variance per annotation (A K <= 16, A <= 8)."""
+        vc = np.ascontiguousarray(vClass, dtype=np.float64); pp = np.ascontiguousarray(pi, dtype=np.float64)
+        if len(vc) != len(pp):
+            raise ValueError("vClass and pi need one entry per class")
+        an = np.asarray(annot)
+        an = an.reshape(ncol, -1)
+        if not np.all(an == np.round(an)):
+            raise ValueError("annot: entries 0 / 1")
+        an = np.asfortranarray(an, dtype=np.int32)
+        l0 = None if lhs0 is None else np.ascontiguousarray(lhs0, dtype=np.float64)
+        r0 = None if rhs0 is None else np.ascontiguousarray(rhs0, dtype=np.float64)
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_marker_set_rc(self.h, C.c_int64(col0), C.c_int64(ncol), C.c_double(df), C.c_double(scale), C.c_double(varBeta0),
+                                               _p(vc, C.c_double), _p(pp, C.c_double), C.c_int32(len(vc)), _p(an, C.c_int32), C.c_int64(ncol),
+                                               C.c_int32(an.shape[1]), C.c_int32(int(estPi)), _p(l0, C.c_double), _p(r0, C.c_double), C.byref(sid)))
+        self.nsets += 1
+        self.set_shapes.append((ncol, an.shape[1]))
+        self.nclasses = getattr(self, "nclasses", 0) + len(vc) * an.shape[1]
+        self.rc_shape = dict(getattr(self, "rc_shape", {}))
+        self.rc_shape[sid.value] = (ncol, an.shape[1], len(vc))
+        return sid.value
+
+    def rc_state(self, set_id):
+        """dict(piHat[A, K], sum_pi[A, K], annotProb[ncol, A], annotCat[ncol] (from 1), sum_annot[ncol, A]) of a BayesRCpi set."""
+        ncol, A, K = self.rc_shape[set_id]
+        pi = np.empty(A * K); sp = np.empty(A * K); ap = np.empty((ncol, A), order="F"); sa = np.empty((ncol, A), order="F")
+        cat = np.empty(ncol, dtype=np.int32)
+        self._chk(self.L.ngp_get_rc_state(self.h, C.c_int32(set_id), _p(pi, C.c_double), _p(sp, C.c_double), _p(ap, C.c_double), _p(cat, C.c_int32),
+                                          _p(sa, C.c_double)))
+        return dict(piHat=pi.reshape(A, K), sum_pi=sp.reshape(A, K), annotProb=ap, annotCat=cat, sum_annot=sa)
+
+    def set_rc_state(self, set_id, st):
+        """Resume / fine seam: st as rc_state returns it; a missing key is left as it is on the device."""
+        f = lambda k, order: None if st.get(k) is None else np.require(np.asarray(st[k], dtype=np.float64), requirements=[order])
+        pi, sp, ap, sa = f("piHat", "C"), f("sum_pi", "C"), f("annotProb", "F"), f("sum_annot", "F")
+        cat = None if st.get("annotCat") is None else np.ascontiguousarray(st["annotCat"], dtype=np.int32)
+        self._chk(self.L.ngp_set_rc_state(self.h, C.c_int32(set_id), _p(pi, C.c_double), _p(sp, C.c_double), _p(ap, C.c_double), _p(cat, C.c_int32),
+                                          _p(sa, C.c_double)))
 
     def add_marker_set_tuple(self, col0, nloc, k, df, scale, regions, varBeta0):
         """Correlated sets (BayesPR's Tuple method, src/functions.jl:140-154): k sets, nloc loci, columns as tuple_columns(col0, nloc, k);

@@ -16,7 +16,7 @@ Same names, argument meaning and output files as the reference, so a model scrip
 
 Interpreted here: the response, the intercept `1`, covariate / factor columns (optionally grouped by `blockThese`), `(1|g)` random
 effects, `PED(col)` pedigree effects (with `userPedData`), correlated (Tuple) pedigree effects -- a VCV key ("ID", "Dam") with a k x k
-covariance -- and `SNP(...)` terms.  Interactions and BayesRC are outside the accelerated path and raise NotImplementedError naming the reference code that handles them.
+covariance -- and `SNP(...)` terms.  Interactions and BayesRCplus are outside the accelerated path and raise NotImplementedError naming the reference code that handles them.
 All arithmetic happens in libnextgp_hip.so; this file only parses, reshapes and writes files.
 """
 import os
@@ -28,7 +28,7 @@ import numpy as np
 
 from ._lib import pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
+__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -63,6 +63,16 @@ class BayesRType:  # src/runTime.jl:78-93
     class_: object  # variance-class multipliers (the reference's field is `class`, a Python keyword)
     v: float
     name: str = "BayesR"
+    estimatePi: bool = False
+
+
+@dataclass
+class BayesRCType:  # BayesRCπ(pi, class, v, annot): annotation-informed BayesR (src/mme.jl:384-403, src/functions.jl:291-360)
+    pi: object      # class probabilities, the start of every annotation's row
+    class_: object  # variance-class multipliers
+    v: float        # the start of every annotation's variance
+    annot: object   # nSNPs x nAnnot matrix of 0 / 1; every SNP in at least one annotation
+    name: str = "BayesRCπ"
     estimatePi: bool = False
 
 
@@ -105,6 +115,32 @@ def BayesC(pi, v, name="BayesC", estimatePi=False):
 def BayesR(pi, class_, v, name="BayesR", estimatePi=False):
     """BayesR(pi, class, v; estimatePi) of src/runTime.jl:87-93: `class_` = variance-class multipliers, `pi` their probabilities."""
     return BayesRType([float(x) for x in pi], [float(x) for x in class_], float(v), name, bool(estimatePi))
+
+
+def BayesRCπ(pi, class_, v, annot, name="BayesRCπ", estimatePi=False):
+    """BayesRCπ(pi, class, v, annot; estimatePi): BayesR whose class probabilities and variance belong to an annotation; every SNP draws
+    the annotation it acts through among those it has (`annot`: nSNPs x nAnnot, entries 0 / 1, no all-zero row; at most 8 annotations
+    and nAnnot * classes <= 16).  BayesRCpi is the same constructor under an ASCII name."""
+    an = np.asarray(annot)
+    if an.ndim != 2 or an.size == 0:
+        raise ValueError("BayesRCπ: annot is a matrix, one row per SNP and one column per annotation")
+    if not np.isin(an, (0, 1)).all():
+        raise ValueError("BayesRCπ: annot holds entries other than 0 / 1")
+    if (an.sum(axis=1) == 0).any():
+        raise ValueError(f"BayesRCπ: SNP {int(np.argmax(an.sum(axis=1) == 0)) + 1} has no annotation; the reference divides 0 / 0 there "
+                         "(src/mme.jl:396) -- put such SNPs in a set of their own")
+    if an.shape[1] > 8 or an.shape[1] * len(pi) > 16 or len(pi) < 2 or len(pi) != len(class_):
+        raise ValueError("BayesRCπ: 2 or more classes with one probability each, at most 8 annotations, annotations x classes <= 16")
+    return BayesRCType([float(x) for x in pi], [float(x) for x in class_], float(v), an.astype(np.int32), name, bool(estimatePi))
+
+
+BayesRCpi = BayesRCπ
+
+
+def BayesRCplus(*args, **kwargs):
+    raise NotImplementedError("BayesRCplus takes one step per annotation on the same column inside a locus and keeps only their sum "
+                              "(src/functions.jl:362-419): a different block chain from BayesRCπ's, which is on the device; it stays on the "
+                              "reference's Julia path")
 
 
 def BayesLV(v, f, covariates, varZeta, name="BayesLV", estimateVarZeta=False):
@@ -539,7 +575,7 @@ def _regions_for(prior, P, map_path, out_folder, set_name):
     """M[set][:regionArray] (src/mme.jl:324-358)."""
     if isinstance(prior, (BayesBType, BayesLogVarType)):   # one region per locus (src/mme.jl:356, :421)
         return [(j, j + 1) for j in range(P)]
-    if isinstance(prior, (BayesCType, BayesRType)):  # one variance for the set (nVarCov = 1, src/mme.jl:370, :381)
+    if isinstance(prior, (BayesCType, BayesRType, BayesRCType)):  # one variance for the set (nVarCov = 1, src/mme.jl:370, :381; BayesRCπ: one per annotation, no regions)
         return [(0, P)]
     if not map_path:
         if prior.r == 1:
@@ -646,7 +682,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
                 vu_off += kk
             vb_off, cls_off = 0, 0
             for k, s in enumerate(sets):
-                K = len(s["prior"].pi) if isinstance(s["prior"], BayesRType) else 0
+                K = len(s["prior"].pi) * s.get("A", 1) if isinstance(s["prior"], (BayesRType, BayesRCType)) else 0
                 for m, nm in enumerate(s["members"]):
                     row(f"beta{nm}", _fmt(S["beta"][s["cols"][:, m]]))
                     row(f"delta{nm}", [str(int(v)) for v in S["delta"][s["cols"][:, m]]])
@@ -654,6 +690,8 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
                     row(f"pi{s['name']}", _fmt(S["piHat"][2 * k:2 * k + 2]))
                 if K:
                     row(f"pi{s['name']}", _fmt(S["class_pi"][cls_off:cls_off + K]))
+                if isinstance(s["prior"], BayesRCType):       # src/samplers.jl:85-87
+                    row(f"annot{s['name']}", [str(int(v)) for v in S["annotCat"][s["id"]]])
                 if isinstance(s["prior"], BayesLogVarType):   # src/samplers.jl:89-92
                     row(f"c{s['name']}", _fmt(S["lv_c"][s["lv"]]))
                     row(f"varZeta{s['name']}", _fmt(S["lv_varZeta"][s["lv"]]))
@@ -1018,8 +1056,8 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
         prior = VCV.get(t.name)
         if prior is None:  # src/mme.jl:324-329, 504, 518
             prior = BayesPR(9999, 0.05)
-        if not isinstance(prior, (BayesPRType, BayesBType, BayesCType, BayesRType, BayesLogVarType)):
-            raise NotImplementedError(f"prior {type(prior).__name__} for {t.name}: only BayesPR, BayesB, BayesC, BayesR and BayesLV are on the accelerated path")
+        if not isinstance(prior, (BayesPRType, BayesBType, BayesCType, BayesRType, BayesRCType, BayesLogVarType)):
+            raise NotImplementedError(f"prior {type(prior).__name__} for {t.name}: only BayesPR, BayesB, BayesC, BayesR, BayesRCπ and BayesLV are on the accelerated path")
         df = 4.0                                  # 3 + size(v,1), src/mme.jl:493
         scale = prior.v * (df - 2.0) / df         # src/mme.jl:501
         regions = regions_of(prior, P, t.map, t.name)
@@ -1044,6 +1082,13 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
             n_lv = sum(1 for q in sets if "lv" in q)
             sets.append(dict(id=sid, name=t.name, members=[t.name], cols=np.arange(col0, col0 + P)[:, None], P=P, prior=prior, nreg=P, nvb=P, k=1,
                              lv=n_lv, ncov=Cm.shape[1], cnames=cnames))
+            continue
+        elif isinstance(prior, BayesRCType):  # src/mme.jl:384-403
+            if prior.annot.shape[0] != P:
+                raise ValueError(f"BayesRCπ prior of {t.name}: {prior.annot.shape[0]} annotation rows for {P} SNPs")
+            A = prior.annot.shape[1]
+            sid = smp.add_marker_set_rc(col0, P, df, scale, prior.v, prior.class_, prior.pi, prior.annot, estPi=prior.estimatePi, lhs0=lhs0, rhs0=rhs0)
+            sets.append(dict(id=sid, name=t.name, members=[t.name], cols=np.arange(col0, col0 + P)[:, None], P=P, prior=prior, nreg=A, nvb=A, k=1, A=A))
             continue
         elif isinstance(prior, BayesRType):  # src/mme.jl:374-383
             sid = smp.add_marker_set_r(col0, P, df, scale, prior.v, prior.class_, prior.pi, estPi=prior.estimatePi, lhs0=lhs0, rhs0=rhs0)
@@ -1109,6 +1154,9 @@ def _write_headers(outFolder, sets, fixed_names, randoms=()):
             _out(outFolder, f"pi{s['name']}", ["pi1", "pi2"])
         if isinstance(s["prior"], BayesRType):               # one column per class (src/mme.jl:589-591)
             _out(outFolder, f"pi{s['name']}", [f"pi{v + 1}" for v in range(len(s["prior"].pi))])
+        if isinstance(s["prior"], BayesRCType):              # annotation-major, and the category of every SNP (src/mme.jl:573-576)
+            _out(outFolder, f"pi{s['name']}", [f"pi{v + 1}" for v in range(len(s["prior"].pi) * s["A"])])
+            _out(outFolder, f"annot{s['name']}", names)
         if isinstance(s["prior"], BayesLogVarType):          # src/mme.jl:577-580
             _out(outFolder, f"c{s['name']}", [f"c{v + 1}" for v in range(s["ncov"])])
             _out(outFolder, f"varZeta{s['name']}", ["varZeta"])
@@ -1139,8 +1187,10 @@ def _run_one(smp, outFolder, sets, fixed_names, intercept, nChain, nBurn, nThin,
                     _out(outFolder, f"delta{nm}", [str(int(v)) for v in st["delta"][s["cols"][:, m]]])
                 if isinstance(s["prior"], (BayesBType, BayesCType)):
                     _out(outFolder, f"pi{s['name']}", _fmt(st["piHat"][2 * k:2 * k + 2]))
-                if isinstance(s["prior"], BayesRType):
+                if isinstance(s["prior"], (BayesRType, BayesRCType)):
                     _out(outFolder, f"pi{s['name']}", _fmt(smp.get_class_state(s["id"])["piHat"]))
+                if isinstance(s["prior"], BayesRCType):
+                    _out(outFolder, f"annot{s['name']}", [str(int(v)) for v in smp.rc_state(s["id"])["annotCat"]])
                 if isinstance(s["prior"], BayesLogVarType):
                     lv = smp.lv_state(s["id"])
                     _out(outFolder, f"c{s['name']}", _fmt(lv["c"]))
@@ -1171,6 +1221,10 @@ def _posterior_means(smp, sets, fixed_names, intercept, randoms=()):
                 res["sets"][nm]["var"] = (ps["sum_varBeta"][vb_off:vb_off + s["nvb"]] / n).reshape(s["nreg"], s["k"], s["k"])
         if isinstance(s["prior"], BayesRType):
             res["sets"][s["name"]]["pi"] = smp.get_class_state(s["id"])["sum_pi"] / n
+        if isinstance(s["prior"], BayesRCType):       # pi per annotation and the posterior membership probabilities of every SNP
+            rc = smp.rc_state(s["id"])
+            res["sets"][s["name"]]["pi"] = rc["sum_pi"] / n
+            res["sets"][s["name"]]["annot"] = rc["sum_annot"] / n
         if isinstance(s["prior"], BayesLogVarType):   # posterior means of the variance model's coefficients and of varZeta
             lv = smp.lv_state(s["id"])
             res["sets"][s["name"]]["c"] = lv["sum_c"] / n

@@ -3,6 +3,7 @@
 // blocked Gibbs sweep, state and posterior read-back.  gfx950 only; there is NO CPU fallback:
 // without a usable device every entry point fails with NGP_ERR_NODEVICE / NGP_ERR_HIP.
 #include <hip/hip_runtime.h>
+#include <cassert>
 
 #include <dlfcn.h>
 
@@ -143,6 +144,17 @@ struct HLv {  // the variance model of one BayesLV marker set (src/mme.jl:418-43
     DevArray<int> d_trapseg;
 };
 
+struct HRc {  // the per-locus state of one BayesRCpi marker set (src/mme.jl:384-403; kernels in ngp_bayesrc.h)
+    int set = -1;              // its marker set
+    int A = 0, Kc = 0;         // annotations, classes
+    int64_t n = 0, nseg = 0;   // loci, 256-locus segments
+    std::vector<uint8_t> mask; // bit a: the locus has annotation a (annotInput)
+    DevArray<uint8_t> d_mask, d_cat;
+    DevArray<double> d_prob, d_sum, d_part;  // annotProb [A][n], sum_annot [A][n], segment partials [nseg][A]
+    DevArray<int> d_cnt;       // [nseg][NGP_RMAX]
+    DRc dev() { DRc R; R.prob = d_prob; R.mask = d_mask; R.cat = d_cat; R.sum = d_sum; R.part = d_part; R.cnt = d_cnt; R.nseg = nseg; return R; }
+};
+
 // The arrays of one uploaded panel: the handles that share it (ngp_share_panel) hold a std::shared_ptr each
 struct PanelMem {
     DevArray<float> tiles;  // fp32 tiles, or (compact storage) one byte per element behind the same pointer
@@ -190,6 +202,7 @@ struct HSet {
     int tk = 0;               // Tuple (correlated BayesPR) set: number of correlated sets; nreg k x k variance matrices in varBeta
     int64_t nloc = 0;
     int lv = -1;              // BayesLV set: its entry of ModelMem::lv (the device's DSet says BayesPR: the sweep is BayesPR's)
+    int rc = -1;              // BayesRCpi set: its entry of ModelMem::rc; K then counts its A * Kc slots, vcls / rpi are indexed by the slot
 };
 
 std::string g_create_err;
@@ -277,7 +290,12 @@ int64_t sweep_grid(const SweepPlan &p, int K = 1) { return K + ngp_multi_reducer
 
 // the kernel of a sweep launch over K chains (K = 1: one chain; K >= 2: a fused pass); diag: time stamps or a timing mode are on;
 // tup / rset: a chain has a Tuple / a BayesR set
-SweepKernel pick_kernel(const SweepPlan &p, int K, bool diag, bool tup, bool rset) {
+SweepKernel pick_kernel(const SweepPlan &p, int K, bool diag, bool tup, bool rset, bool rcset = false) {
+    // a BayesRCpi set: the kernel of its own that carries eval_rcform (one chain per pass, one shard per workgroup: ngp_add_marker_set_rc
+    // refuses the other layouts; no time stamps there)
+    // (ngp_add_marker_set_rc refuses V > 1, fusable() a fused pass, ngp_debug_stamps / ngp_debug_set_mode the diagnostics: no other
+    // kernel's eval_rform may ever see a lane of method 6)
+    if (rcset) { assert(K == 1 && p.V == 1 && !diag); return SweepKernel::rc; }
     if (K > 1) {  // (BayesR: the samplers of k_sweep_r, their class coefficients staged in LDS -- where that fits beside the
                   // sampler's own; else the chain of k_sweep_multi(_tup))
         if (rset && sweep_lds(p, SweepKernel::multi_r, K) <= NGP_LDS_MAX) return SweepKernel::multi_r;
@@ -297,7 +315,7 @@ SweepKernel pick_kernel(const SweepPlan &p, int K, bool diag, bool tup, bool rse
 
 // host address of a sweep kernel: each translation unit of ngp_sweep_inst.hip knows the kernels it defines
 const void *sweep_kernel(SweepKernel k) {
-    for (auto unit : {sweep_kernel_0, sweep_kernel_1, sweep_kernel_2, sweep_kernel_3})
+    for (auto unit : {sweep_kernel_0, sweep_kernel_1, sweep_kernel_2, sweep_kernel_3, sweep_kernel_4})
         if (const void *f = unit(k)) return f;
     return nullptr;
 }
@@ -442,6 +460,8 @@ struct ModelMem {
     DevArray<double> d_bfix, d_sum_bfix;
     std::vector<HRand> rnd;            // (1|g) random-effect sets (src/functions.jl:57-110), sampled after the fixed-effect sets, in order
     std::vector<HLv> lv;               // variance models of the BayesLV sets (src/functions.jl:442-485), in the order of their sets
+    std::vector<HRc> rc;               // per-locus annotation state of the BayesRCpi sets (src/functions.jl:291-360), in the order of their sets
+    DevArray<DRc> d_rctab;             // [16] their device arrays by marker set (k_prep); allocated with the first such set
     // optional per-iteration traces of selected effects, variances and pi (ngp_set_trace_loci)
     DevArray<int64_t> d_trace_loci;
     int64_t ntl = 0, ntvb = 0;
@@ -704,7 +724,7 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     if (req.storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
     if (plan.mode == 1) {
         // the single-chain kernels, each with the LDS this plan launches it with (k_sweep_r where that fits)
-        for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::tall}) {
+        for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::rc, SweepKernel::tall}) {
             const size_t lds = sweep_lds(plan, k);
             if (lds <= NGP_LDS_MAX) HCHK(hipFuncSetAttribute(sweep_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
@@ -1015,7 +1035,7 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
         // (the hand-off counters were zeroed by k_prep, which precedes every sweep in the stream)
         SweepArgs A;
         fill_sweep_args(h, tb0, tb1, A);
-        const SweepKernel k = pick_kernel(h->plan, 1, h->hm.d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0);
+        const SweepKernel k = pick_kernel(h->plan, 1, h->hm.d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0, !h->mm.rc.empty());
         h->last_grid = sweep_grid(h->plan);
         if (evs) (void)hipEventRecord(evs[0], h->stream);
         launch_sweep_kernel(k, h->last_grid, sweep_lds(h->plan, k), h->stream, &A);
@@ -1031,7 +1051,7 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
                            S, (int)t, do_upd, do_gemv);
         if (evs && do_gemv) (void)hipEventRecord(evs[e++], h->stream);
         if (do_gemv)
-            hipLaunchKernelGGL(k_recur, dim3(1), dim3(256), 0, h->stream, h->cm.d_part, h->pm->gramx, h->plan.D, S, (int)t, h->cm.d_beta, h->cm.d_delta,
+            hipLaunchKernelGGL(h->mm.rc.empty() ? k_recur<false> : k_recur<true>, dim3(1), dim3(256), 0, h->stream, h->cm.d_part, h->pm->gramx, h->plan.D, S, (int)t, h->cm.d_beta, h->cm.d_delta,
                                h->cm.d_c, h->cm.d_w, h->cm.d_q, h->pm->mpm, h->cm.d_chi, h->cm.d_setof, h->cm.d_vbidx, h->cm.d_sets, h->mm.d_varBeta, h->cm.d_dlt, h->mm.d_rcls,
                                (long long)h->Ppad, h->cm.d_rhs0, h->cm.d_scal, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg,
                                (const double *)((wants_tinv(h) && h->cm.tinv_blocks == h->NBLK && h->cm.lin_any) ? h->cm.d_tinv : nullptr), (const unsigned *)h->cm.d_blin);
@@ -1135,6 +1155,17 @@ void launch_variance(ngp_handle *h, int active_set, uint64_t it) {
     }
     hipLaunchKernelGGL(k_pidraw, dim3(1), dim3(64), 0, h->stream, (int)h->sets.size(), h->cm.d_sets, active_set, h->seed,
                        (uint64_t)h->chain, it, h->cm.d_abort);
+    for (auto &Rc : h->mm.rc) {  // BayesRCpi sets: class / annotation of every locus, the A variances, pi, annotProb (ngp_bayesrc.h)
+        if (active_set >= 0 && Rc.set != active_set) continue;
+        const DRc R = Rc.dev();
+        const unsigned *ab = (const unsigned *)h->cm.d_abort;
+        hipLaunchKernelGGL(k_rc_count, dim3((unsigned)((Rc.nseg + 3) / 4)), dim3(256), 0, h->stream, (const DSet *)h->cm.d_sets, Rc.set, R,
+                           (const double *)h->cm.d_beta, h->cm.d_delta.get(), ab);
+        hipLaunchKernelGGL(k_rc_draw, dim3(1), dim3(64), 0, h->stream, h->cm.d_sets.get(), Rc.set, R, h->mm.d_varBeta + h->sets[(size_t)Rc.set].vb_off,
+                           h->seed, (uint64_t)h->chain, it, ab);
+        hipLaunchKernelGGL(k_rc_annot, dim3((unsigned)((Rc.n + 255) / 256)), dim3(256), 0, h->stream, (const DSet *)h->cm.d_sets, Rc.set, R, h->seed,
+                           (uint64_t)h->chain, it, ab);
+    }
 }
 
 // resume_mid: the head of this iteration (varE, intercept, fixed-effect sets) has run already -- its sweep ended at the census
@@ -1248,7 +1279,7 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->cm.d_setof, h->cm.d_loc,
                        h->cm.d_vbidx, h->cm.d_sets, h->cm.d_scal, h->mm.d_varBeta, h->pm->mpm, h->cm.d_lhs0, h->cm.d_rhs0, h->cm.d_beta, h->cm.d_c, h->cm.d_w,
                        h->cm.d_q, h->cm.d_T, h->cm.d_chi, -1, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->mm.d_regs, h->mm.d_regchi, h->mm.d_rcls,
-                       h->cm.d_ccnt, (long long)(h->plan.mode == 1 ? h->cm.ccnt_words : 0), h->cm.d_abort, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg);
+                       h->cm.d_ccnt, (long long)(h->plan.mode == 1 ? h->cm.ccnt_words : 0), h->cm.d_abort, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg, (const DRc *)h->mm.d_rctab.get());
     launch_tinv(h);
 }
 
@@ -1277,6 +1308,9 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
         }
         for (auto &V : h->mm.lv)  // BayesLV sets: c and varZeta (src/samplers.jl:89-92)
             hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, (long long)NGP_LV_SUM, V.d_st, V.d_st + NGP_LV_SUM, h->cm.d_abort);
+        for (auto &Rc : h->mm.rc)  // BayesRCpi sets: the annotation category of every locus (src/samplers.jl:85-87)
+            hipLaunchKernelGGL(k_rc_accum, dim3((unsigned)((Rc.n + 255) / 256)), dim3(256), 0, h->stream, (const DSet *)h->cm.d_sets, Rc.set, Rc.dev(),
+                               (const unsigned *)h->cm.d_abort);
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
     return NGP_OK;
@@ -1367,6 +1401,11 @@ void describe(ngp_handle *h, ChainState &st) {
         st.dev(SEG_LV, v, V.d_st, NGP_LV_SUM * 8); st.dev(SEG_SUM_LV, v, V.d_st + NGP_LV_SUM, NGP_LV_SUM * 8);
         st.dev(SEG_LV_ALL, v, V.d_st, NGP_LV_WORDS * 8); st.dev(SEG_ZETA, v, V.d_zeta, (size_t)V.n * 8);
     }
+    for (int r = 0; r < (int)h->mm.rc.size(); r++) {  // (pi, its sums and the A variances of such a set: SEG_CLS, SEG_SUM_CLS, SEG_VARBETA)
+        HRc &Rc = h->mm.rc[(size_t)r];
+        const size_t an8 = (size_t)Rc.A * (size_t)Rc.n * 8;
+        st.dev(SEG_RC_PROB, r, Rc.d_prob, an8); st.dev(SEG_RC_CAT, r, Rc.d_cat, (size_t)Rc.n); st.dev(SEG_SUM_RC, r, Rc.d_sum, an8);
+    }
 }
 static_assert(offsetof(DSet, piHat1) == offsetof(DSet, piHat0) + 8 && offsetof(DSet, sum_pi1) == offsetof(DSet, sum_pi0) + 8, "SEG_PI / SEG_SUM_PI");
 
@@ -1454,8 +1493,9 @@ int sample_enqueue(ngp_handle *h) {
         }
         const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->mm.nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
         // (the header, by magic: ngp_state.h)
-        const bool has_lv = !h->mm.lv.empty();
-        bool ok = std::fwrite(has_lv ? "NGPSMP03" : h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
+        const bool has_rc = !h->mm.rc.empty();
+        const bool has_lv = !h->mm.lv.empty() || has_rc;  // (04 holds the parts of 03, also when empty)
+        bool ok = std::fwrite(has_rc ? "NGPSMP04" : has_lv ? "NGPSMP03" : h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
         for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f.get()) == 1; }
         if (!h->mm.rnd.empty() || has_lv) {
             const int64_t nr = (int64_t)h->mm.rnd.size();
@@ -1466,6 +1506,11 @@ int sample_enqueue(ngp_handle *h) {
             const int64_t nl = (int64_t)h->mm.lv.size();
             ok = ok && std::fwrite(&nl, 8, 1, S->f.get()) == 1;
             for (auto &V : h->mm.lv) { const int64_t lg[2] = {V.set, V.ncov}; ok = ok && std::fwrite(lg, sizeof(lg), 1, S->f.get()) == 1; }
+        }
+        if (has_rc) {
+            const int64_t nrc = (int64_t)h->mm.rc.size();
+            ok = ok && std::fwrite(&nrc, 8, 1, S->f.get()) == 1;
+            for (auto &Rc : h->mm.rc) { const int64_t rg[3] = {Rc.set, Rc.A, Rc.Kc}; ok = ok && std::fwrite(rg, sizeof(rg), 1, S->f.get()) == 1; }
         }
         if (!ok) return fail(h, NGP_ERR_ARG, "cannot write the sample file header: " + S->path);
         S->header_written = true;
@@ -1490,7 +1535,7 @@ int sample_enqueue(ngp_handle *h) {
                        h->cm.d_scal, h->mm.d_bfix, h->cm.d_abort);
     hipError_t e = hipSuccess;
     for (auto &a : pl.at)
-        if (e == hipSuccess && (a.s->id == SEG_U || a.s->id == SEG_VARU || a.s->id == SEG_LV))
+        if (e == hipSuccess && (a.s->id == SEG_U || a.s->id == SEG_VARU || a.s->id == SEG_LV || a.s->id == SEG_RC_PROB || a.s->id == SEG_RC_CAT))
             e = hipMemcpyAsync(S->d_slot[slot].get() + a.off, a.s->p, a.s->bytes, hipMemcpyDeviceToDevice, h->stream);
     // (a HIP call that fails here gives the slot back: the next enqueue would otherwise wait for it forever instead of reporting)
     if (e == hipSuccess) e = hipEventRecord(S->ev_packed[slot], h->stream);
@@ -1530,6 +1575,23 @@ int grow_pair(ngp_handle *h, DevArray<double> &a, DevArray<double> &sum_a, int64
     }
     HCHK(hipStreamSynchronize(h->stream));
     a = std::move(na); sum_a = std::move(ns);
+    return NGP_OK;
+}
+
+// a BayesRCpi set's per-locus state as ngp_add_marker_set_rc leaves it: annotProb[l][a] = annot[l][a] / sum_a annot[l][a]
+// (src/mme.jl:395), sum_annot = 0, annotCat = 1.  The reference starts annotCat as zeros(Int64, 1, P) (src/mme.jl:403); nothing reads it
+// before the first sweep writes it, and starting at 1 is this library's choice: a valid category from the first get / set on.
+int rc_reset(ngp_handle *h, HRc &Rc) {
+    std::vector<double> pr((size_t)Rc.A * (size_t)Rc.n, 0.0);
+    for (int64_t l = 0; l < Rc.n; l++) {
+        const double np = (double)__builtin_popcount((unsigned)Rc.mask[(size_t)l]);
+        for (int a = 0; a < Rc.A; a++)
+            if ((Rc.mask[(size_t)l] >> a) & 1) pr[(size_t)a * (size_t)Rc.n + (size_t)l] = 1.0 / np;
+    }
+    HCHK(hipMemcpyAsync(Rc.d_prob, pr.data(), pr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemsetAsync(Rc.d_cat, 1, (size_t)Rc.n, h->stream));
+    HCHK(hipMemsetAsync(Rc.d_sum, 0, pr.size() * sizeof(double), h->stream));
+    HCHK(hipStreamSynchronize(h->stream));  // (pr is a local)
     return NGP_OK;
 }
 
@@ -1706,6 +1768,15 @@ struct PanelHeader { char magic[8]; int64_t N, P; int32_t bits, zero; };
 // snapshot signature of a BayesLV set (added to its second word): the covariate count and how varZeta is estimated
 static int64_t lv_sig(const ngp_handle *h, const HSet &hs) {
     return hs.lv < 0 ? 0 : 256 * ((int64_t)h->mm.lv[(size_t)hs.lv].ncov + 32 * (int64_t)h->mm.lv[(size_t)hs.lv].mode);
+}
+
+// ... and of a BayesRCpi set: 47 bits of a digest (FNV-1a) of its annotation masks from bit 8 up -- a snapshot's annotProb is positive
+// exactly where the mask it was saved under has a bit, so it may only load into a model with the same annotations
+static int64_t rc_sig(const ngp_handle *h, const HSet &hs) {
+    if (hs.rc < 0) return 0;
+    uint64_t d = 1469598103934665603ull;
+    for (uint8_t m : h->mm.rc[(size_t)hs.rc].mask) { d ^= m; d *= 1099511628211ull; }
+    return (int64_t)((d >> 17) << 8);
 }
 
 int32_t ngp_write_panel_file(const char *path, const uint8_t *G, int64_t N, int64_t P, int64_t ld, int32_t bits) {
@@ -2053,6 +2124,10 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
         int rc2 = lv_reset(h, V);
         if (rc2) return rc2;
     }
+    for (auto &Rc : h->mm.rc) {  // BayesRCpi sets: annotProb = annot / its row sum, no category yet, empty sums (src/mme.jl:393-399)
+        int rc2 = rc_reset(h, Rc);
+        if (rc2) return rc2;
+    }
     HCHK(hipStreamSynchronize(h->stream));
     h->iter = 0; h->have_y = true; h->poisoned = false; h->ntrace = 0;
     for (auto &hs : h->sets) hs.fine_calls = 0;
@@ -2164,6 +2239,7 @@ bool fusable(ngp_handle **hs, int n) {
     for (int i = 0; i < n; i++) {
         ngp_handle *h = hs[i];
         if (h->pm != h0->pm || h->device != h0->device || h->dbg_mode != 0 || h->hm.d_dbg || h->dbg_census_fail_iter > 0) return false;
+        if (!h->mm.rc.empty()) return false;  // a BayesRCpi set: no fused kernel carries its rule, the chains run side by side
     }
     // (the samplers sit at blocks 0, 8, .., 8 (n - 1) of the grid -- one XCD under round-robin placement: the grid must reach the last)
     const int64_t grid = sweep_grid(h0->plan, n);
@@ -2426,7 +2502,7 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
     const int64_t nvbs = (int64_t)hs.vb0.size();  // variance entries of the set: regions (loci for BayesB), k x k per region for a tuple set
     // (device arrays are not read back to be looked at: a variance that is not finite poisons the chain visibly -- k_prep -- as in ngp_run)
     if (!dev) for (int64_t r = 0; r < nvbs; r++) REQUIRE(std::isfinite(varBeta[r]) && (varBeta[r] >= 0.0 || hs.tk > 1), NGP_ERR_ARG, "varBeta must be finite, >= 0");
-    const bool has_pi = hs.method != NGP_METHOD_BAYESPR && hs.method != NGP_METHOD_TUPLE && hs.method != NGP_METHOD_BAYESLV;
+    const bool has_pi = hs.method != NGP_METHOD_BAYESPR && hs.method != NGP_METHOD_TUPLE && hs.method != NGP_METHOD_BAYESLV && hs.method != NGP_METHOD_BAYESRC;
     if (has_pi) REQUIRE(piHat != nullptr, NGP_ERR_ARG, "BayesB / BayesC need piHat");
     const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const uint64_t it = ++hs.fine_calls;
@@ -2450,7 +2526,7 @@ int sweep_set_impl(ngp_handle *h, int32_t set_id, double varE, double *ycorr, do
         hipLaunchKernelGGL(k_prep, dim3((unsigned)(h->Ppad / 256 + 1)), dim3(256), 0, h->stream, (long long)h->Ppad, h->cm.d_setof, h->cm.d_loc,
                            h->cm.d_vbidx, h->cm.d_sets, h->cm.d_scal, h->mm.d_varBeta, h->pm->mpm, h->cm.d_lhs0, h->cm.d_rhs0, h->cm.d_beta, h->cm.d_c, h->cm.d_w,
                            h->cm.d_q, h->cm.d_T, h->cm.d_chi, (int)set_id, h->seed, (uint64_t)h->chain, it, (long long)h->h_regs.size(), h->mm.d_regs, h->mm.d_regchi, h->mm.d_rcls,
-                           h->cm.d_ccnt, (long long)(h->plan.mode == 1 ? h->cm.ccnt_words : 0), h->cm.d_abort, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg);
+                           h->cm.d_ccnt, (long long)(h->plan.mode == 1 ? h->cm.ccnt_words : 0), h->cm.d_abort, h->mm.d_tup, h->mm.d_tupc, h->mm.d_tupg, (const DRc *)h->mm.d_rctab.get());
         launch_tinv(h);
         launch_sweep(h, tb0, tb1, nullptr);
         launch_variance(h, (int)set_id, it);
@@ -2563,6 +2639,7 @@ int32_t ngp_debug_stamps(ngp_handle *h, int32_t enable, uint64_t *out, int64_t n
     int rc;
     if ((rc = enter(h))) return rc;
     const size_t words = (size_t)2 << 20;
+    REQUIRE(!(enable && !h->mm.rc.empty()), NGP_ERR_ARG, "time stamps exist in the diagnostic kernel only, which does not carry the rule of BayesRCpi sets");
     if (enable && !h->hm.d_dbg) { if ((rc = h->hm.d_dbg.alloc(h, words))) return rc; HCHK(hipStreamSynchronize(h->stream)); }
     if (out && h->hm.d_dbg) HCHK(hipMemcpy(out, h->hm.d_dbg, std::min<size_t>((size_t)n, words) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (!enable && h->hm.d_dbg) { HCHK(hipStreamSynchronize(h->stream)); h->hm.d_dbg.reset(); }
@@ -2675,6 +2752,7 @@ int32_t ngp_debug_set_mode(ngp_handle *h, int32_t mode) {
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(mode >= 0 && mode <= 6, NGP_ERR_ARG, "diagnostic mode must be in 0..6");
+    REQUIRE(mode == 0 || h->mm.rc.empty(), NGP_ERR_ARG, "timing modes exist in the diagnostic kernel only, which does not carry the rule of BayesRCpi sets");
     h->dbg_mode = mode;
     return NGP_OK;
     NGP_CATCH(h)
@@ -2842,7 +2920,7 @@ struct ModelSig {
     std::vector<int64_t> fix;   // ncol per fixed-effect set
     ModelSig() = default;
     explicit ModelSig(const ngp_handle *h) {
-        for (auto &hs : h->sets) sets.insert(sets.end(), {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs), hs.nreg, hs.col0, hs.ncol});
+        for (auto &hs : h->sets) sets.insert(sets.end(), {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs) + rc_sig(h, hs), hs.nreg, hs.col0, hs.ncol});
         nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM);
         if (!h->h_rw.empty()) digest = weights_digest(h->h_rw);
         if (!h->mm.rnd.empty()) {
@@ -3208,6 +3286,177 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
     if ((rc = set_class_state_dev(h, sid, pi, std::vector<double>((size_t)K, 0.0).data()))) return rc;
     h->nclass_total += K;
     if (set_id) *set_id = sid;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* BayesRCpi marker set -- annotation-informed BayesR (src/runTime.jl, BayesRCπ(pi, class, v, annot); set-up src/mme.jl:384-403, :493-516;
+ * sampler src/functions.jl:291-360): A annotations (columns of annot, entries 0 / 1, column-major with leading dimension ld), K variance
+ * classes, one variance per annotation (all start at varBeta0), piHat[a] = pi for every annotation.  1 <= A <= 8, K >= 2, A K <= 16.
+ * Refused: a locus without an annotation (the reference divides 0 / 0 there and throws in Categorical: such loci belong in another
+ * set), entries other than 0 / 1.  delta holds the class, annotCat the annotation of a locus, both from 1.  Models with such a set
+ * run the persistent sweep in a kernel of their own (k_sweep_rc) or the per-block engine; fp32 panels so tall that a streamer
+ * workgroup owns several shards are refused here (compact storage or ngp_configure mode 0 serve them). */
+int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double df, double scale, double varBeta0, const double *vClass,
+                              const double *pi, int32_t K, const int32_t *annot, int64_t ld, int32_t A, int32_t estPi, const double *lhs0,
+                              const double *rhs0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
+    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
+    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
+    REQUIRE(vClass && pi && annot, NGP_ERR_ARG, "BayesRCpi: classes, their probabilities or the annotations missing");
+    REQUIRE(K >= 2 && A >= 1 && A <= NGP_AMAX && (int64_t)A * K <= NGP_RMAX, NGP_ERR_ARG,
+            "BayesRCpi needs K >= 2 classes and 1..8 annotations with A * K <= 16");
+    REQUIRE(ld >= ncol, NGP_ERR_ARG, "BayesRCpi: leading dimension of annot smaller than ncol");
+    REQUIRE(std::isfinite(df) && std::isfinite(scale) && df > 0, NGP_ERR_ARG, "df/scale must be finite, df > 0");
+    REQUIRE(!h->hm.d_dbg && h->dbg_mode == 0, NGP_ERR_ARG, "BayesRCpi sets run in a kernel without time stamps and timing modes: switch the diagnostics off first");
+    REQUIRE(h->plan.V == 1, NGP_ERR_ARG, "BayesRCpi sets are not served on fp32 panels whose streamer workgroups own several shards: use compact storage or ngp_configure mode 0");
+    double ps = 0.0;
+    for (int v = 0; v < K; v++) {
+        REQUIRE(std::isfinite(vClass[v]) && vClass[v] >= 0.0 && std::isfinite(pi[v]) && pi[v] > 0.0, NGP_ERR_ARG,
+                "BayesRCpi: class multipliers must be >= 0 and class probabilities > 0");
+        ps += pi[v];
+    }
+    REQUIRE(std::fabs(ps - 1.0) < 1e-8, NGP_ERR_ARG, "BayesRCpi: class probabilities must sum to 1");
+    REQUIRE(std::isfinite(varBeta0) && varBeta0 > 0.0, NGP_ERR_ARG, "BayesRCpi varBeta0 must be positive");
+    for (int64_t k = col0; k < col0 + ncol; k++) REQUIRE(h->h_setof[k] == -1, NGP_ERR_ARG, "marker sets overlap");
+    HRc Rc;
+    Rc.set = (int)h->sets.size(); Rc.A = A; Rc.Kc = K; Rc.n = ncol; Rc.nseg = (ncol + NGP_SEG - 1) / NGP_SEG;
+    Rc.mask.assign((size_t)ncol, 0);
+    for (int64_t l = 0; l < ncol; l++) {
+        for (int a = 0; a < A; a++) {
+            const int32_t e = annot[(size_t)a * (size_t)ld + (size_t)l];
+            REQUIRE(e == 0 || e == 1, NGP_ERR_ARG, "BayesRCpi: annotation entries must be 0 or 1 (locus " + std::to_string(l) + ")");
+            if (e) Rc.mask[(size_t)l] |= (uint8_t)(1u << a);
+        }
+        REQUIRE(Rc.mask[(size_t)l] != 0, NGP_ERR_ARG, "BayesRCpi: locus " + std::to_string(l) + " has no annotation (the reference divides 0 / 0 there, "
+                                                      "src/mme.jl:396: such loci belong in another set)");
+    }
+    // device arrays first: a failure leaves the handle as it was
+    const size_t an = (size_t)A * (size_t)ncol;
+    if ((rc = Rc.d_mask.alloc(h, (size_t)ncol))) return rc;
+    if ((rc = Rc.d_cat.alloc(h, (size_t)ncol))) return rc;
+    if ((rc = Rc.d_prob.alloc(h, an))) return rc;
+    if ((rc = Rc.d_sum.alloc(h, an))) return rc;
+    if ((rc = Rc.d_part.alloc(h, (size_t)Rc.nseg * (size_t)A))) return rc;
+    if ((rc = Rc.d_cnt.alloc(h, (size_t)Rc.nseg * NGP_RMAX))) return rc;
+    HCHK(hipMemcpy(Rc.d_mask, Rc.mask.data(), (size_t)ncol, hipMemcpyHostToDevice));
+    if ((rc = rc_reset(h, Rc))) return rc;
+    if (!h->mm.d_rcls) {
+        if ((rc = h->mm.d_rcls.alloc(h, (size_t)4 * NGP_RMAX * (size_t)h->Ppad))) return rc;
+    }
+    if (!h->mm.d_rctab) {
+        if ((rc = h->mm.d_rctab.alloc(h, 16))) return rc;
+    }
+    // the marker set: A variances outside the region tables (k_rc_draw draws them), A * K slots of class state
+    const int si = (int)h->sets.size(), ns = A * K;
+    HSet hs{col0, ncol, NGP_METHOD_BAYESRC, df, scale, (int64_t)A, h->nvb, estPi, 0, 0.5, std::vector<double>((size_t)A, varBeta0)};
+    hs.K = ns; hs.rc = (int)h->mm.rc.size();
+    for (int i = 0; i < ns; i++) { hs.vcls.push_back(vClass[i % K]); hs.rpi.push_back(pi[i % K]); }
+    const int64_t new_nvb = h->nvb + A;
+    if (new_nvb > h->mm.vb_cap) {
+        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
+        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
+        h->mm.vb_cap = cap;
+    }
+    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, hs.vb0.data(), (size_t)A * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> z((size_t)ncol, 0.0);
+    HCHK(hipMemcpy(h->cm.d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
+    DSet ds;
+    memset(&ds, 0, sizeof(ds));
+    ds.method = NGP_METHOD_BAYESRC; ds.estPi = estPi; ds.df = df; ds.scale = scale; ds.sdf = scale * df; ds.col0 = col0; ds.ncol = ncol;
+    ds.K = ns; ds.rcA = A; ds.rcK = K;
+    for (int i = 0; i < ns; i++) ds.vcls[i] = hs.vcls[(size_t)i];
+    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.5, 0.5);  // the placeholder of sets without a two-class pi
+    const DRc dr = Rc.dev();
+    HCHK(hipMemcpy(h->mm.d_rctab + si, &dr, sizeof(DRc), hipMemcpyHostToDevice));
+    HCHK(hipStreamSynchronize(h->stream));
+    for (int64_t l = 0; l < ncol; l++) {
+        h->h_setof[col0 + l] = (int8_t)si;
+        h->h_loc[col0 + l] = (int32_t)l;
+        h->h_vbidx[col0 + l] = (int32_t)h->nvb;  // (the first of the set's A variances: k_prep adds the annotation)
+    }
+    h->nvb = new_nvb;
+    h->sets.push_back(hs);
+    h->mm.rc.push_back(std::move(Rc));
+    if ((rc = set_class_state_dev(h, si, hs.rpi.data(), std::vector<double>((size_t)ns, 0.0).data()))) return rc;
+    h->nclass_total += ns;
+    h->tables_dirty = true;
+    h->mm.trace_ext_cap = 0;
+    if (set_id) *set_id = si;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* The per-locus state of a BayesRCpi set and its class probabilities (any pointer may be null): piHat / sum_pi hold A K entries,
+ * annotation-major; annotProb / sum_annot ncol A entries, column-major (locus l, annotation a at l + a ncol); annotCat ncol entries,
+ * from 1.  sum_annot[l, a] counts the kept iterations with annotCat[l] = a + 1: divided by the kept iterations it is the
+ * posterior membership probability.  The A variances travel with ngp_get_state / ngp_set_state. */
+int32_t ngp_get_rc_state(ngp_handle *h, int32_t set_id, double *piHat, double *sum_pi, double *annotProb, int32_t *annotCat, double *sum_annot) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int)h->sets.size() && h->sets[(size_t)set_id].rc >= 0, NGP_ERR_ARG, "not a BayesRCpi set");
+    const HSet &hs = h->sets[(size_t)set_id];
+    HRc &Rc = h->mm.rc[(size_t)hs.rc];
+    HCHK(hipStreamSynchronize(h->stream));
+    DSet ds;
+    HCHK(hipMemcpy(&ds, h->cm.d_sets + set_id, sizeof(DSet), hipMemcpyDeviceToHost));
+    for (int i = 0; i < hs.K; i++) {
+        if (piHat) piHat[i] = ds.pic[i];
+        if (sum_pi) sum_pi[i] = ds.sum_pic[i];
+    }
+    const size_t an = (size_t)Rc.A * (size_t)Rc.n;
+    if (annotProb) HCHK(hipMemcpy(annotProb, Rc.d_prob, an * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_annot) HCHK(hipMemcpy(sum_annot, Rc.d_sum, an * sizeof(double), hipMemcpyDeviceToHost));
+    if (annotCat) {
+        std::vector<uint8_t> c8((size_t)Rc.n);
+        HCHK(hipMemcpy(c8.data(), Rc.d_cat, (size_t)Rc.n, hipMemcpyDeviceToHost));
+        for (int64_t l = 0; l < Rc.n; l++) annotCat[l] = c8[(size_t)l];
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_rc_state(ngp_handle *h, int32_t set_id, const double *piHat, const double *sum_pi, const double *annotProb, const int32_t *annotCat,
+                         const double *sum_annot) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(set_id >= 0 && set_id < (int)h->sets.size() && h->sets[(size_t)set_id].rc >= 0, NGP_ERR_ARG, "not a BayesRCpi set");
+    const HSet &hs = h->sets[(size_t)set_id];
+    HRc &Rc = h->mm.rc[(size_t)hs.rc];
+    const size_t an = (size_t)Rc.A * (size_t)Rc.n;
+    if (piHat)
+        for (int i = 0; i < hs.K; i++) REQUIRE(std::isfinite(piHat[i]) && piHat[i] > 0.0, NGP_ERR_ARG, "BayesRCpi: class probabilities must be > 0");
+    if (annotProb)
+        for (int64_t l = 0; l < Rc.n; l++)
+            for (int a = 0; a < Rc.A; a++) {
+                const double p = annotProb[(size_t)a * (size_t)Rc.n + (size_t)l];
+                const bool has = (Rc.mask[(size_t)l] >> a) & 1;
+                REQUIRE(has ? (std::isfinite(p) && p > 0.0) : p == 0.0, NGP_ERR_ARG,
+                        "BayesRCpi: annotProb must be > 0 where the locus has the annotation and 0 elsewhere");
+            }
+    std::vector<uint8_t> c8;
+    if (annotCat) {
+        c8.resize((size_t)Rc.n);
+        for (int64_t l = 0; l < Rc.n; l++) {
+            REQUIRE(annotCat[l] >= 1 && annotCat[l] <= Rc.A, NGP_ERR_ARG, "BayesRCpi: annotCat counts the annotations from 1");
+            c8[(size_t)l] = (uint8_t)annotCat[l];
+        }
+    }
+    HCHK(hipStreamSynchronize(h->stream));
+    if (piHat || sum_pi)
+        if ((rc = set_class_state_dev(h, set_id, piHat, sum_pi))) return rc;
+    if (annotProb) HCHK(hipMemcpy(Rc.d_prob, annotProb, an * sizeof(double), hipMemcpyHostToDevice));
+    if (sum_annot) HCHK(hipMemcpy(Rc.d_sum, sum_annot, an * sizeof(double), hipMemcpyHostToDevice));
+    if (annotCat) HCHK(hipMemcpy(Rc.d_cat, c8.data(), (size_t)Rc.n, hipMemcpyHostToDevice));
     return NGP_OK;
     NGP_CATCH(h)
 }

@@ -17,6 +17,8 @@
                     // from the coefficient arrays of k_prep each time a candidate is formed
 #define NGP_KMAX 4  // marker sets of one tuple (correlated BayesPR, src/functions.jl:140-154)
 #define NGP_METHOD_TUPLE_DEV 4
+#define NGP_METHOD_RC_DEV 6  // BayesRCpi set (NGP_METHOD_BAYESRC): annotation-informed BayesR, slots i = annotation * classes + class
+#define NGP_AMAX 8           // annotations of a BayesRCpi set (their presence is one byte per locus)
 
 namespace ngp {
 
@@ -32,6 +34,9 @@ struct DSet {  // one marker set (src/mme.jl:324-361, 492-520)
     int K, pad2_;
     double vcls[NGP_RMAX], pic[NGP_RMAX], logpic[NGP_RMAX], sum_pic[NGP_RMAX];
     int ncls[NGP_RMAX];  // loci per class of the running sweep
+    // BayesRCpi (src/functions.jl:291-360, set-up src/mme.jl:384-403): A annotations x Kc classes; K above = A * Kc slots, slot
+    // i = a * Kc + v, and vcls / pic / logpic / sum_pic are indexed by the slot (vcls[i] = vClass[v]); 0 for every other method
+    int rcA, rcK;
 };
 
 // Correlated (Tuple) BayesPR set (src/functions.jl:140-154, 513-516; set-up src/mme.jl:448-489): k sets share nloc loci, the k
@@ -310,6 +315,143 @@ __device__ inline void eval_rform(const int meth, const double r, const double b
     } else {
         eval_rform_other(r, bo, cc, ww, st, cand, cls);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// One lane's rule of a BayesRCpi locus in the r-form chain ("BayesRCpi sets"; src/functions.jl:291-360).
+// The lane's coefficient tables are BayesR's with A * Kc slots, slot i = a * Kc + v: q_i = 1 / lhs_i, t_i = sd_i z,
+// a_i = log pi[a][v] - log(varc lhs_i) / 2 + log annotProb[l][a], u_i the comparison uniform of the slot; a slot of an annotation
+// the locus does not have carries a_i = -inf and u_i = +inf (k_prep), as a class a BayesR set does not have (load_rlane).
+//   L_i = q_i == 0 ? a_i : fma(hs, q_i, a_i);  m = max L in slot order;  e_i = det_exp(L_i - m)
+//   T_a = sum_v e_{a Kc + v} in class order;  S = sum_a T_a in annotation order
+//   annotation: the first a with sum_{a' <= a} T_a' >= U S, else the last one the locus has (alast)
+//   class:      the first v with sum_{m <= v} e_{a Kc + m} >= u_{a Kc + v} T_a, else the last one
+// U (one keyed uniform per locus) and alast travel in the lane's w and c, which a class lane does not use otherwise.
+// cls = slot + 1: the chain's delta byte; k_rc_count (ngp_bayesrc.h) splits it into class and annotation behind the sweep.
+// All 64 lanes are evaluated (no lazy search: a lane that ends in a zero class still needs its annotation).
+// ------------------------------------------------------------------------------------------
+__device__ inline void eval_rcform(const int meth, const double r, const double bo, const double cc, const double ww, const double st,
+                                   const RLane &L, const int Kc, const double iVarE, double &cand, int &cls) {
+    if (meth != NGP_METHOD_RC_DEV) {
+        eval_rform(meth, r, bo, cc, ww, st, L, iVarE, cand, cls);
+        return;
+    }
+    if (st != 2.0) {  // a lane of a set this call does not sample (fine seam): no step, as the inactive lanes of the other methods
+        // (cls = 1 goes into the lane's delta byte, as it does for an inactive lane of every other method: in a block two sets share,
+        // the device's class of the other set's loci reads 1 until that set's own next call -- which takes delta from its chain, never
+        // from here -- and k_rc_count is not run for a set that is not sampled, so annotCat keeps its value)
+        cand = 0.0;
+        cls = 1;
+        return;
+    }
+    const double t = r * iVarE;
+    const double rhs = t + L.rhs0;
+    const double s2 = rhs * rhs;
+    const double hs = 0.5 * s2;
+    const int ns = L.K;
+    const double ninf = -__builtin_inf();
+    double e[NGP_RMAX];
+#pragma unroll
+    for (int i = 0; i < NGP_RREG; i++) e[i] = (L.q[i] == 0.0) ? L.a[i] : __builtin_fma(hs, L.q[i], L.a[i]);  // (-inf: no such slot, load_rlane)
+#pragma unroll
+    for (int i = NGP_RREG; i < NGP_RMAX; i++) e[i] = (i < ns) ? rlane_L(L, i, hs) : ninf;
+    double m = e[0];
+#pragma unroll
+    for (int i = 1; i < NGP_RMAX; i++) m = (e[i] > m) ? e[i] : m;
+    // the exponentials four side by side (det_exp4: the bits of det_exp); slots 9..16 only where the set has them
+    static_assert(NGP_RMAX == 16 && NGP_RREG == 4, "four groups of four slots");
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        if (g < 2 || 4 * g < ns) {
+            double xm[4], ev[4];
+#pragma unroll
+            for (int v = 0; v < 4; v++) xm[v] = e[4 * g + v] - m;
+            det_exp4(xm, ev);
+#pragma unroll
+            for (int v = 0; v < 4; v++) e[4 * g + v] = ev[v];
+        } else {
+#pragma unroll
+            for (int v = 0; v < 4; v++) e[4 * g + v] = 0.0;
+        }
+    }
+    // T_a in class order, S in annotation order; then the annotation by one inverse-CDF uniform (the T_a are formed again, by the
+    // same additions: no table of them, no division by the class count)
+    const int alast = (int)cc;
+    double S = 0.0;
+    {
+        double tcur = 0.0;
+        int a = 0, v = 0;
+#pragma unroll
+        for (int i = 0; i < NGP_RMAX; i++) {
+            const bool on = i < ns;
+            tcur = (v == 0) ? e[i] : tcur + e[i];
+            const bool end = on && (v == Kc - 1);
+            const double sn = (a == 0) ? tcur : S + tcur;
+            S = end ? sn : S;
+            a = end ? a + 1 : a;
+            v = end ? 0 : v + 1;
+        }
+    }
+    const double thrA = ww * S;
+    int asel = alast;
+    double Tsel = 0.0;
+    {
+        double tcur = 0.0, cumA = 0.0, Tlast = 0.0;
+        bool foundA = false;
+        int a = 0, v = 0;
+#pragma unroll
+        for (int i = 0; i < NGP_RMAX; i++) {
+            const bool on = i < ns;
+            tcur = (v == 0) ? e[i] : tcur + e[i];
+            const bool end = on && (v == Kc - 1);
+            const double cn = (a == 0) ? tcur : cumA + tcur;
+            const bool take = end && !foundA;
+            const bool hit = take && (cn >= thrA);
+            cumA = take ? cn : cumA;
+            asel = hit ? a : asel;
+            Tsel = hit ? tcur : Tsel;
+            Tlast = (end && a == alast) ? tcur : Tlast;
+            foundA = foundA || hit;
+            a = end ? a + 1 : a;
+            v = end ? 0 : v + 1;
+        }
+        Tsel = foundA ? Tsel : Tlast;
+    }
+    // the class inside the annotation: a fresh uniform per comparison (the slot's)
+    const int i0 = asel * Kc;
+    int c = Kc - 1;
+    {
+        double cum = 0.0;
+        bool found = false;
+#pragma unroll
+        for (int i = 0; i < NGP_RMAX; i++) {
+            const int v = i - i0;
+            const bool in = v >= 0 && v < Kc && !found;
+            double ui = __builtin_inf();
+            if (i < NGP_RREG) ui = L.u[i];
+            else if (in) ui = L.ext[(size_t)i * L.Ppad + (size_t)3 * L.astride];
+            const double cn = (v == 0) ? e[i] : cum + e[i];
+            const double thr = ui * Tsel;
+            const bool hit = in && (cn >= thr);
+            cum = in ? cn : cum;
+            c = hit ? v : c;
+            found = found || hit;
+        }
+    }
+    const int slot = i0 + c;
+    double qc = L.q[0], tc = L.t[0];
+#pragma unroll
+    for (int v = 1; v < NGP_RREG; v++) {
+        qc = (slot == v) ? L.q[v] : qc;
+        tc = (slot == v) ? L.t[v] : tc;
+    }
+    asm volatile("" : "+v"(qc), "+v"(tc));
+    if (slot >= NGP_RREG) { qc = L.ext[(size_t)slot * L.Ppad]; tc = L.ext[(size_t)slot * L.Ppad + (size_t)2 * L.astride]; }
+    if (qc != 0.0) {
+        const double d = __builtin_fma(rhs, qc, tc);
+        cand = d - bo;
+    } else cand = -bo;
+    cls = slot + 1;
 }
 
 // ------------------------------------------------------------------------------------------

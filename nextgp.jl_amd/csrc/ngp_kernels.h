@@ -10,6 +10,7 @@
 //   src/functions.jl:509-511  sampleVarBetaPR  src/functions.jl:531-533 samplePi
 #pragma once
 #include "ngp_common.h"
+#include "ngp_bayesrc.h"
 
 #pragma clang fp contract(off)
 
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(256) void k_prep(long long Ppad, const int8_t *__re
                                               uint64_t chain, uint64_t it, long long nreg, const DReg *__restrict__ regs,
                                               double *__restrict__ regchi, double *__restrict__ rcls, unsigned *__restrict__ ccnt,
                                               long long ccnt_words, const unsigned *__restrict__ abort_w, const DTup *__restrict__ tup,
-                                              double *__restrict__ tupc, const double *__restrict__ tupg) {
+                                              double *__restrict__ tupc, const double *__restrict__ tupg, const DRc *__restrict__ rc) {
     if (abort_w && *abort_w != 0u) return;  // an earlier sweep of this call gave up (ngp_sweep_args.h, abort_w)
     // the hand-off counters of the persistent sweep that follows in the stream start from zero (was a memset launch of its own)
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < ccnt_words; i += (long long)gridDim.x * 256) ccnt[i] = 0u;
@@ -265,6 +266,56 @@ __global__ __launch_bounds__(256) void k_prep(long long Ppad, const int8_t *__re
         c[k] = 0.0;
         w[k] = bad ? __builtin_nan("") : acc - beta[k];  // a variance matrix that is not positive definite poisons the chain visibly
         q[k] = -1.0;
+        T[k] = 1.0;
+        chi[k] = 1.0;
+        return;
+    }
+    if (S.method == NGP_METHOD_RC_DEV) {
+        // BayesRCpi: the tables of BayesR with A * Kc slots, slot i = a * Kc + v (src/functions.jl:300-316): variance varBeta[a] vClass[v],
+        // log-weight log pi[a][v] - log(varc lhs) / 2 + log annotProb[l][a]; a slot of an annotation the locus lacks: log-weight -inf,
+        // comparison uniform +inf.  The locus' annotation uniform travels in w, its last annotation in c, and q = 2 marks the lane
+        // as a sampled one (eval_rcform; a lane of a set that a fine-seam call leaves alone keeps q = -1 above and is passed over).
+        double *rq = rcls, *ra = rcls + (size_t)NGP_RMAX * Ppad, *rt = rcls + (size_t)2 * NGP_RMAX * Ppad, *ru = rcls + (size_t)3 * NGP_RMAX * Ppad;
+        const DRc R = rc[si];
+        const int Kc = S.rcK, A = S.rcA;
+        const unsigned mk = R.mask[l];
+        const double t1r = mpm[k] * iVarE;
+        const double t2r = t1r + lhs0[k];
+        Rng rz = rng_seed(seed, chain, it, NGP_KIND_BETA_NORMAL, key);
+        const double zr = rng_normal(rz);
+        int alast = 0;
+        for (int a = 0; a < A; a++) {
+            const bool has = (mk >> a) & 1u;
+            if (has) alast = a;
+            const double varB = varBeta[vbidx[k] + a];
+            const double lp = has ? det_log(R.prob[(size_t)a * (size_t)S.ncol + l]) : 0.0;
+            for (int v = 0; v < Kc; v++) {
+                const int i = a * Kc + v;
+                const size_t o = (size_t)i * Ppad + k;
+                Rng ruu = rng_seed(seed, chain, it, i < 8 ? NGP_KIND_R_UNIFORM : NGP_KIND_R_UNIFORM_HI, ((uint64_t)si << 40) | (l << 3) | (uint64_t)(i & 7));
+                const double uv = rng_uniform(ruu);
+                const double varc = varB * S.vcls[i];
+                if (!has) {
+                    rq[o] = 0.0; ra[o] = -__builtin_inf(); rt[o] = 0.0; ru[o] = __builtin_inf();
+                } else if (varc == 0.0) {
+                    rq[o] = 0.0; ra[o] = S.logpic[i] + lp; rt[o] = 0.0; ru[o] = uv;
+                } else {
+                    const double iv = 1.0 / varc;
+                    const double lhsv = t2r + iv;
+                    const double ilhs = 1.0 / lhsv;
+                    const double prod = varc * lhsv;
+                    const double lg = det_log(prod);
+                    const double hl = 0.5 * lg;
+                    const double sd = det_sqrt(ilhs);
+                    const double a0 = S.logpic[i] - hl;
+                    rq[o] = ilhs; ra[o] = a0 + lp; rt[o] = sd * zr; ru[o] = uv;
+                }
+            }
+        }
+        Rng rua = rng_seed(seed, chain, it, NGP_KIND_RC_UNIFORM, key);
+        c[k] = (double)alast;
+        w[k] = rng_uniform(rua);
+        q[k] = 2.0;
         T[k] = 1.0;
         chi[k] = 1.0;
         return;
@@ -580,6 +631,9 @@ __global__ __launch_bounds__(256) void k_step(const float *__restrict__ tiles, d
 // block recursion of block t: reduce the S shard partials (groups of 32, sequential), then
 // the 64-step serial chain on wave 0 with the Gram block in registers.  ONE workgroup.
 // ------------------------------------------------------------------------------------------
+// RC: the model holds a BayesRCpi set -- its lanes' rule (eval_rcform) is compiled into that instantiation only, so that the kernel of
+// every other model keeps the code and the registers it had
+template <bool RC>
 __global__ __launch_bounds__(256) void k_recur(const double *__restrict__ part, const double *__restrict__ gramx, int D, int S, int t,
                                                double *__restrict__ beta, uint8_t *__restrict__ delta,
                                                const double *__restrict__ c, const double *__restrict__ w,
@@ -649,16 +703,18 @@ __global__ __launch_bounds__(256) void k_recur(const double *__restrict__ part, 
             return;
         }
     }
-    if (__ballot(meth0 == 3) != 0ull) {  // a BayesR locus in the block: r-form chain (eval_rform)
+    if (__ballot(meth0 == 3 || (RC && meth0 == NGP_METHOD_RC_DEV)) != 0ull) {  // a BayesR / BayesRCpi locus in the block: r-form chain (eval_rform, eval_rcform)
         RLane RL = empty_rlane();
-        if (meth0 == 3) RL = load_rlane(rcls, Ppad, k, sets[si0].K, rhs0);
+        if (meth0 == 3 || (RC && meth0 == NGP_METHOD_RC_DEV)) RL = load_rlane(rcls, Ppad, k, sets[si0].K, rhs0);
+        const int Kc = (RC && meth0 == NGP_METHOD_RC_DEV) ? sets[si0].rcK : 1;
         const double iVarE = sc->iVarE;
         double rcur = r, dfin = 0.0;
         int cfin = 1, kstart = 0;
         for (int guard = 0; guard < NGP_BLK + 1; ++guard) {
             double cand;
             int cls;
-            eval_rform(meth0, rcur, bo, cc, ww, st, RL, iVarE, cand, cls);
+            if constexpr (RC) eval_rcform(meth0, rcur, bo, cc, ww, st, RL, Kc, iVarE, cand, cls);  // (eval_rform for every lane that is not a BayesRCpi one)
+            else eval_rform(meth0, rcur, bo, cc, ww, st, RL, iVarE, cand, cls);
             if (j >= kstart) { dfin = cand; cfin = cls; }
             const unsigned long long todo = __ballot(cand != 0.0) & (~0ull << kstart);
             if (!todo) break;
@@ -940,6 +996,7 @@ __global__ void k_pidraw(int nsets, DSet *__restrict__ sets, int active_set, uin
     if (si >= nsets) return;
     if (active_set >= 0 && si != active_set) return;
     DSet *S = &sets[si];
+    if (S->method == NGP_METHOD_RC_DEV) return;  // BayesRCpi: pi is drawn per annotation by k_rc_draw (ngp_bayesrc.h)
     if (S->method == 3) {  // BayesR: Dirichlet(nLoci + 1) as normalised gammas (src/functions.jl:284-288, :536-538)
         if (S->estPi) {
             double g[NGP_RMAX], gsum = 0.0;

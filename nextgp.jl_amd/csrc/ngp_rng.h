@@ -29,6 +29,9 @@
 #define NGP_KIND_LV_START 16    // BayesLV sets: the starting value of a locus' zeta (iteration 0), (set << 40) | locus (src/mme.jl:430)
 #define NGP_KIND_U_WISHART 17   // tuple random-effect sets: Bartlett factor of varU's inverse-Wishart draw, (set << 40) | (i << 4) | j, (i, j) != (0, 0)
 #define NGP_KIND_R_UNIFORM_HI 18  // BayesR: comparisons v >= 8 of the class search, (set << 40) | (locus << 3) | (v - 8); kind 8 keeps v < 8 with (locus << 3) | v
+#define NGP_KIND_RC_UNIFORM 19  // BayesRCpi: the uniform of a locus' annotation draw, (set << 40) | locus (src/functions.jl:318); its class search
+                                // takes kinds 8 / 18 with the slot a * K + v as the comparison
+#define NGP_KIND_RC_ANNOT 20    // BayesRCpi: gamma of annotation a of a locus' annotProb Dirichlet, (set << 40) | (locus << 3) | a (src/functions.jl:541-544)
 
 #define NGP_GOLD 0x9E3779B97F4A7C15ULL
 

@@ -21,15 +21,18 @@
 //  Packed posterior (ngp_posterior_len, ngp_export_posterior_device, ngp_allreduce_posterior) -- posterior_layout:
 //    sum_beta[P] | sum_beta2[P] | sum_delta[P] | sum_varBeta[nvb] | sum_pi[2] per marker set | class sums[K] per BayesR set |
 //    fixed-effect sums (every column of every set) | sum_u[q] of every random-effect set, then sum_varU of every set |
-//    per BayesLV set sum_c[16], sum_varZeta | sum_varE | sum_b | nKept (as a double; rounded with llround on the way back)
+//    per BayesLV set sum_c[16], sum_varZeta | per BayesRCpi set sum_annot[A][ncol] | sum_varE | sum_b | nKept (as a double; rounded with
+//    llround on the way back).  A BayesRCpi set's pi sums are the class sums of its A K slots, its A variance sums lie in sum_varBeta.
 //
 //  Sample file (ngp_set_sample_file) -- record: sample_layout, padded to a multiple of 8 bytes:
 //    header  char[8] magic | int64 P, nvb, nsets, nfix, nclass, record bytes | per marker set int64 {method, K, col0, ncol, variance
 //            entries, tuple k}; magic "NGPSMP01": nothing more; "NGPSMP02" (random-effect sets): int64 nrand | int64 q per set;
 //            "NGPSMP03" (BayesLV sets): the random-effect part as in 02, also when empty, then int64 nlv | per set int64 marker set, ncov
+//            "NGPSMP04" (BayesRCpi sets): the parts of 03, also when empty, then int64 nrc | per set int64 marker set, A, K
 //    record  int64 iter (-1: a sweep of the call gave up, the record is not written) | varE | b | b_fixed[nfix] | u[q] of every
 //            random-effect set, then varU of every set | beta[P] | varBeta[nvb] | piHat[2] per marker set | class probabilities[K]
-//            per BayesR set | per BayesLV set c[16] (the first ncov used), varZeta | delta[P] (uint8)
+//            per BayesR set (the A K slots of a BayesRCpi set, annotation-major) | per BayesLV set c[16] (the first ncov used), varZeta |
+//            per BayesRCpi set annotProb[A][ncol] | delta[P] (uint8) | per BayesRCpi set annotCat[ncol] (uint8, from 1)
 //
 //  Snapshot (ngp_save_snapshot / ngp_load_snapshot):
 //    char[8] "NGPSNAP2" | int64 N, P, nvb, nsets | snapshot_head_layout: int64 iter, nKept | uint64 seed, chain |
@@ -41,7 +44,9 @@
 //      device) | beta[P] | delta[P] (uint8, 0 / 1) | varBeta[nvb] | piHat[2] per set | sum_beta[P] | sum_beta2[P] | sum_delta[P] |
 //      sum_varBeta[nvb] | sum_pi[2] per set | uint64 fine_calls per set | int64 nfix | b_fixed[nfix] | sum_b_fixed[nfix] |
 //      per BayesR set piHat[K], sum_pi[K] | per random-effect set u[q], sum_u[q], varU, sum_varU, uint64 fine_calls |
-//      per BayesLV set the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums, ...), zeta[ncol]
+//      per BayesLV set the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums, ...), zeta[ncol] |
+//      per BayesRCpi set annotProb[A][ncol], sum_annot[A][ncol], annotCat[ncol] (uint8); its signature words are method 6,
+//      K = A K slots + a 47-bit digest of the annotation masks from bit 8 up, and nreg = A
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -64,7 +69,9 @@ enum SegId : int {
     // ... posterior sums ...
     SEG_SUM_BETA, SEG_SUM_BETA2, SEG_SUM_DELTA, SEG_SUM_VARBETA, SEG_SUM_FIX, SEG_SUM_U, SEG_SUM_VARU, SEG_SUM_LV,
     // ... and arrays that hold value and sum side by side, whole
-    SEG_VU, SEG_LV_ALL
+    SEG_VU, SEG_LV_ALL,
+    // BayesRCpi sets, per set: annotProb[A][ncol], annotCat[ncol] (uint8, from 1), sum_annot[A][ncol]
+    SEG_RC_PROB, SEG_RC_CAT, SEG_SUM_RC
 };
 
 struct Seg {
@@ -93,13 +100,14 @@ struct ChainState {
 using Layout = std::vector<std::vector<SegId>>;
 
 inline const Layout posterior_layout = {{SEG_SUM_BETA}, {SEG_SUM_BETA2}, {SEG_SUM_DELTA}, {SEG_SUM_VARBETA}, {SEG_SUM_PI}, {SEG_SUM_CLS}, {SEG_SUM_FIX},
-                                        {SEG_SUM_U}, {SEG_SUM_VARU}, {SEG_SUM_LV}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_NKEPT_F64}};
+                                        {SEG_SUM_U}, {SEG_SUM_VARU}, {SEG_SUM_LV}, {SEG_SUM_RC}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_NKEPT_F64}};
 inline const Layout sample_layout = {{SEG_ITER}, {SEG_VARE}, {SEG_B}, {SEG_FIX}, {SEG_U}, {SEG_VARU}, {SEG_BETA}, {SEG_VARBETA}, {SEG_PI}, {SEG_CLS},
-                                     {SEG_LV}, {SEG_DELTA}};
+                                     {SEG_LV}, {SEG_RC_PROB}, {SEG_DELTA}, {SEG_RC_CAT}};
 inline const Layout snapshot_head_layout = {{SEG_ITER}, {SEG_NKEPT}, {SEG_SEED}, {SEG_CHAIN}};
 inline const Layout snapshot_body_layout = {{SEG_VARE}, {SEG_B}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_YCORR}, {SEG_BETA}, {SEG_DELTA}, {SEG_VARBETA}, {SEG_PI},
                                             {SEG_SUM_BETA}, {SEG_SUM_BETA2}, {SEG_SUM_DELTA}, {SEG_SUM_VARBETA}, {SEG_SUM_PI}, {SEG_FINE}, {SEG_NFIX}, {SEG_FIX},
-                                            {SEG_SUM_FIX}, {SEG_CLS, SEG_SUM_CLS}, {SEG_U, SEG_SUM_U, SEG_VU, SEG_RFINE}, {SEG_LV_ALL, SEG_ZETA}};
+                                            {SEG_SUM_FIX}, {SEG_CLS, SEG_SUM_CLS}, {SEG_U, SEG_SUM_U, SEG_VU, SEG_RFINE}, {SEG_LV_ALL, SEG_ZETA},
+                                            {SEG_RC_PROB, SEG_SUM_RC, SEG_RC_CAT}};
 
 // a layout applied to a chain: every segment with its byte offset, and the size of the whole
 struct Plan {

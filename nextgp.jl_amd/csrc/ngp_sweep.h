@@ -1635,7 +1635,8 @@ __device__ __attribute__((always_inline)) inline void publish_block(const SweepA
 // the previous library on the same box).
 // RCLS: 0 = no BayesR chain, 1 = BayesR with the lane coefficients fetched inside the block, 2 = fetched one block ahead through LDS by
 // wave 1 like the Tuple ones (10.4 -> 8.9 us per block; a flavour of its own, k_sweep_r: inside the full kernel this code cost the
-// 50k x 600k sweep of the other methods 2 %)
+// 50k x 600k sweep of the other methods 2 %), 3 = as 1, with the lanes of BayesRCpi sets evaluated by eval_rcform (k_sweep_rc, a
+// flavour of its own for the same reason)
 // Class search of ONE BayesR locus with nine to sixteen classes, its classes spread over lanes 0 .. K-1 (role_sampler's lazy search,
 // RCLS == 2): lanes 8 .. K-1 read their class from the coefficient arrays in memory -- the sampler's LDS holds eight -- and the
 // steps of eval_rform run as loops over the classes.  Returns the class; dmine = this lane's dlt should its class be the one.
@@ -1845,7 +1846,7 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
             int isave = 1;
             // BayesR: the lane's set and method (one byte per lane, read only when the model has a BayesR set at all)
             int meth0 = -1, si0 = -1, rblk = 0;
-            if constexpr (RCLS == 1) {
+            if constexpr (RCLS == 1 || RCLS == 3) {
                 if (A.rcls) {
                     si0 = A.setof[(long long)t * NGP_BLK + j];
                     meth0 = (si0 >= 0) ? smeth[si0] : -1;
@@ -1906,7 +1907,7 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
                 TL.ww = tsrc[2 * NGP_KMAX * NGP_BLK];
                 dsave = tuple_chain_nv(tk, nvalid, j, tot, bo, TL, [&](int sl, int cc2) { return Gd[(u % 3) * 4096 + sl * NGP_BLK + cc2]; });
                 isave = 1;
-            } else if (RCLS != 0 && A.rcls && (RCLS == 2 ? rblk != 0 : __ballot(meth0 == 3) != 0ull)) {
+            } else if (RCLS != 0 && A.rcls && (RCLS == 2 ? rblk != 0 : (RCLS == 3 ? __ballot(meth0 == 3 || meth0 == NGP_METHOD_RC_DEV) != 0ull : __ballot(meth0 == 3) != 0ull))) {
                 // r-form chain (eval_rform, ngp_kernels.h): candidates of all lanes from the current r, the first non-zero one at
                 // or behind the cursor takes its step.  With most loci in the zero class that is a few steps per block.
                 double dfin = 0.0;
@@ -2027,8 +2028,14 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
                 } else {
                 RLane RL = empty_rlane();
                 double iVarE;
+                int Kc = 1;  // (RCLS == 3: classes per annotation of a BayesRCpi lane; its K counts the slots)
                 {
+                    if constexpr (RCLS == 3) {
+                        if (meth0 == 3 || meth0 == NGP_METHOD_RC_DEV) RL = load_rlane(A.rcls, A.Ppad, (long long)t * NGP_BLK + j, sK[si0], A.rhs0);
+                        if (meth0 == NGP_METHOD_RC_DEV) Kc = A.sets[si0].rcK;
+                    } else {
                     if (meth0 == 3) RL = load_rlane(A.rcls, A.Ppad, (long long)t * NGP_BLK + j, sK[si0], A.rhs0);
+                    }
                     iVarE = A.scal->iVarE;
                 }
                 double rcur = r;
@@ -2036,6 +2043,10 @@ __device__ __attribute__((always_inline)) inline void role_sampler(const SweepAr
                 for (int guard = 0; guard < NGP_BLK + 1; ++guard) {
                     double cand;
                     int cls;
+                    // (RCLS == 3: the 64-wide rule of BayesRCpi sets -- every lane evaluated, the first non-zero candidate behind the
+                    // cursor steps, the lanes are evaluated again; a lane that is passed over keeps what it had then)
+                    if constexpr (RCLS == 3) eval_rcform(meth0, rcur, bo, cc, ww, st, RL, Kc, iVarE, cand, cls);
+                    else
                     eval_rform(meth0, rcur, bo, cc, ww, st, RL, iVarE, cand, cls);
                     if (j >= kstart) { dfin = cand; cfin = cls; }
                     const unsigned long long todo = __ballot(cand != 0.0) & (~0ull << kstart);
@@ -2393,6 +2404,14 @@ __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_r(SweepArgs A) {
     constexpr bool DBG = false, TUP = true;
     constexpr int RCLSV = 2;
+#include "ngp_sweep_body.inc"
+}
+#endif
+#if defined(NGP_INST_DBG) && NGP_INST_DBG == 4  // models with a BayesRCpi set: the 64-wide rule of eval_rcform (fifth translation unit, so that
+                                                // the code of its sixteen-slot evaluation stands beside no other kernel's hot loop)
+__global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_rc(SweepArgs A) {
+    constexpr bool DBG = false, TUP = true;
+    constexpr int RCLSV = 3;
 #include "ngp_sweep_body.inc"
 }
 #endif

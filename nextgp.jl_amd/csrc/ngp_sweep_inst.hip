@@ -1,12 +1,12 @@
 // ngp_sweep_inst.hip -- one instantiation of the persistent sweep kernel (ngp_sweep.h) and the lookup of its host addresses.
-// Compiled four times: -DNGP_INST_DBG=0 (lean production kernel, K chains per pass), =1 (diagnostic kernel: time stamps, timing modes;
-// tall fp32 panels), =2 (full production kernel: Tuple sets, tall shards), =3 (models with a BayesR set).
+// Compiled five times: -DNGP_INST_DBG=0 (lean production kernel, K chains per pass), =1 (diagnostic kernel: time stamps, timing modes;
+// tall fp32 panels), =2 (full production kernel: Tuple sets, tall shards), =3 (models with a BayesR set), =4 (models with a BayesRCpi set).
 #include <hip/hip_runtime.h>
 
 #include "ngp_sweep.h"
 
 #ifndef NGP_INST_DBG
-#error "compile with -DNGP_INST_DBG=0, 1, 2 or 3"
+#error "compile with -DNGP_INST_DBG=0, 1, 2, 3 or 4"
 #endif
 
 #define NGP_CAT_(a, b) a##b
@@ -14,7 +14,7 @@
 
 namespace ngp {
 
-// sweep_kernel_0 .. sweep_kernel_3 (ngp_sweep_args.h): the kernels this translation unit defines
+// sweep_kernel_0 .. sweep_kernel_4 (ngp_sweep_args.h): the kernels this translation unit defines
 const void *NGP_CAT(sweep_kernel_, NGP_INST_DBG)(SweepKernel k) {
     switch (k) {
 #if NGP_INST_DBG == 0
@@ -29,6 +29,8 @@ const void *NGP_CAT(sweep_kernel_, NGP_INST_DBG)(SweepKernel k) {
 #elif NGP_INST_DBG == 3
     case SweepKernel::r: return (const void *)k_sweep_r;
     case SweepKernel::multi_r: return (const void *)k_sweep_multi_r;
+#elif NGP_INST_DBG == 4
+    case SweepKernel::rc: return (const void *)k_sweep_rc;
 #endif
     default: return nullptr;
     }

@@ -108,6 +108,71 @@ function add_marker_set_r!(h::Handle, col0::Integer, ncol::Integer, df::Float64,
     return id[]
 end
 
+# BayesRCπ set (src/mme.jl:384-403): annot = M[s].annotInput (nSNPs x nAnnot, entries 0 / 1, no all-zero row), K classes with the
+# probabilities every annotation starts from, ONE variance per annotation (all varBeta0 at first).  nAnnot <= 8, nAnnot * K <= 16.
+function add_marker_set_rc!(h::Handle, col0::Integer, ncol::Integer, df::Float64, scale::Float64, varBeta0::Float64,
+                            vClass::Vector{Float64}, pi::Vector{Float64}, annot::AbstractMatrix; estPi::Bool=false, lhs0=C_NULL, rhs0=C_NULL)
+    an = Matrix{Int32}(annot)
+    size(an, 1) == ncol || error("BayesRCπ: one annotation row per locus")
+    id = Ref{Int32}(0)
+    check(h, ccall((:ngp_add_marker_set_rc, LIB), Int32,
+                   (Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Int64, Int32, Int32,
+                    Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+                   h.ptr, col0, ncol, df, scale, varBeta0, vClass, pi, length(vClass), an, size(an, 1), size(an, 2), estPi, lhs0, rhs0, id))
+    return id[]
+end
+
+# (piHat, sum_pi: A vectors of K entries each, as the reference holds M[s].piHat (src/mme.jl:393); annotProb [ncol x A], annotCat [ncol],
+# sum_annot [ncol x A]) of a BayesRCπ set
+function rc_state(h::Handle, set_id::Integer, ncol::Integer, A::Integer, K::Integer)
+    pi = Vector{Float64}(undef, A * K); sp = similar(pi)
+    ap = Matrix{Float64}(undef, ncol, A); sa = similar(ap); cat = Vector{Int32}(undef, ncol)
+    check(h, ccall((:ngp_get_rc_state, LIB), Int32,
+                   (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                   h.ptr, set_id, pi, sp, ap, cat, sa))
+    # the library holds pi annotation-major (slot a K + v): entry a of the reference's vector of A vectors is slots (a-1) K + 1 .. a K
+    rows(x) = [x[(a - 1) * K + 1:a * K] for a in 1:A]
+    return (piHat = rows(pi), sum_pi = rows(sp), annotProb = ap, annotCat = cat, sum_annot = sa)
+end
+
+# the library's copy of a BayesRCπ set's state (nothing: left as it is); piHat / sum_pi as the reference holds piHat: a vector of A
+# vectors of K entries (vcat of them is the library's annotation-major order, as src/samplers.jl:86 writes them)
+function set_rc_state!(h::Handle, set_id::Integer; piHat=nothing, sum_pi=nothing, annotProb=nothing, annotCat=nothing, sum_annot=nothing)
+    pm(x) = x === nothing ? C_NULL : Vector{Float64}(reduce(vcat, x))
+    p(x) = x === nothing ? C_NULL : Matrix{Float64}(x)
+    c = annotCat === nothing ? C_NULL : Vector{Int32}(vec(annotCat))
+    check(h, ccall((:ngp_set_rc_state, LIB), Int32,
+                   (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                   h.ptr, set_id, pm(piHat), pm(sum_pi), p(annotProb), c, p(sum_annot)))
+end
+
+"""
+    sampleBayesRCπ!(h, set_id, mSet, M, beta, delta, ycorr, varE, varBeta)
+
+Fine seam of a BayesRCπ set: the argument list of the reference's `sampleBayesRCπ!(mSet, M, beta, delta, ycorr, varE, varBeta)`
+(src/functions.jl:291) plus the handle and the set id.  The caller's `M[mSet].piHat` and `M[mSet].annotProb` go in, one call does the
+sweep, the per-annotation variances, pi and the annotation probabilities; `M[mSet].piHat`, `.logPi`, `.annotProb` and `.annotCat` are
+written back.  `M[mSet].annotInput` is never changed.
+"""
+function sampleBayesRCπ!(h::Handle, set_id::Integer, mSet, M, beta, delta, ycorr::Vector{Float64}, varE::Float64, varBeta)
+    A, K = length(M[mSet].piHat), length(M[mSet].vClass)   # piHat: A vectors of K probabilities (src/mme.jl:393)
+    set_rc_state!(h, set_id; piHat = M[mSet].piHat, annotProb = M[mSet].annotProb)
+    b = vec(beta[M[mSet].pos]); d = vec(delta[M[mSet].pos])
+    vb = varBeta[mSet] isa Vector{Float64} ? varBeta[mSet] : Float64.(varBeta[mSet])
+    check(h, ccall((:ngp_sweep_set, LIB), Int32,
+                   (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                   h.ptr, set_id, varE, ycorr, b, d, vb, C_NULL))
+    varBeta[mSet] isa Vector{Float64} || (varBeta[mSet] .= vb)
+    st = rc_state(h, set_id, length(b), A, K)
+    for a in 1:A                               # src/functions.jl:355-356
+        M[mSet].piHat[a] = st.piHat[a]
+        M[mSet].logPi[a] = log.(st.piHat[a])
+    end
+    M[mSet].annotProb .= st.annotProb
+    vec(M[mSet].annotCat) .= st.annotCat       # 1 x P Matrix{Int64} (src/mme.jl:403): vec() shares the memory
+    return nothing
+end
+
 # BayesLV set (src/mme.jl:418-439): one variance per locus (all varBeta0 at first), covariates = M[s].covariates (the design matrix of
 # the variance formula, ncol x ncov), varZeta = M[s].varZeta[1], estVarZeta = M[s].estVarZeta (false / true / a Float64 fraction),
 # zeta0 = M[s].SNPVARRESID (the reference's unseeded start) or nothing for the library's keyed start
@@ -217,17 +282,22 @@ set_sample_file!(h::Handle, path::Union{AbstractString,Nothing}) =
 function foreach_sample(f, path::AbstractString)
     open(path, "r") do io
         magic = String(read(io, 8))
-        magic in ("NGPSMP01", "NGPSMP02", "NGPSMP03") || error("not a sample file: $path")
+        magic in ("NGPSMP01", "NGPSMP02", "NGPSMP03", "NGPSMP04") || error("not a sample file: $path")
         P, nvb, nsets, nfix, ncls, rec = ntuple(_ -> read(io, Int64), 6)
         sets = [ntuple(_ -> read(io, Int64), 6) for _ in 1:nsets]     # (method, K, col0, ncol, variance entries, tuple k)
         rq = magic != "NGPSMP01" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each (a tuple set: k - 1 in the bits from 32 up)
         # BayesLV sets ("NGPSMP03"): (marker set, ncov) of each; a record holds c (16 words, ncov used) | varZeta per set behind class_pi
-        lvs = magic == "NGPSMP03" ? [(read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64}[]
+        lvs = magic in ("NGPSMP03", "NGPSMP04") ? [(read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64}[]
+        # BayesRCπ sets ("NGPSMP04"): (marker set, A, K) of each; a record holds annotProb [A][ncol] per set behind the BayesLV words and
+        # annotCat [ncol] (one byte each) per set behind delta
+        rcs = magic == "NGPSMP04" ? [(read(io, Int64), read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64,Int64}[]
+        rcn = [Int(sets[r[1] + 1][4]) for r in rcs]                   # loci of each
         rk = [Int(w >> 32) + 1 for w in rq]                           # components of each set (1: a (1|g) / PED / GBLUP set)
         rq = [Int(w & 0xffffffff) * k for (w, k) in zip(rq, rk)]      # words of u per set: q k, the components of a level adjacent
         nr = sum(rq; init = 0) + sum(rk .^ 2; init = 0)               # u (set after set) and varU (k k words per set) between b_fixed and beta
         ncp = 3 + nfix + nr + P + nvb + 2 * nsets + ncls               # doubles in front of the BayesLV words
-        nd = ncp + 17 * length(lvs)
+        nlv = ncp + 17 * length(lvs)
+        nd = nlv + sum(Int(r[2]) * n for (r, n) in zip(rcs, rcn); init = 0)
         raw = Vector{UInt8}(undef, rec)
         while !eof(io)
             readbytes!(io, raw, rec) == rec || break
@@ -241,7 +311,9 @@ function foreach_sample(f, path::AbstractString)
                      piHat = d[o + nfix + P + nvb + 1:o + nfix + P + nvb + 2 * nsets],
                      class_pi = d[o + nfix + P + nvb + 2 * nsets + 1:ncp],
                      lv_c = [d[ncp + 17 * (i - 1) + 1:ncp + 17 * (i - 1) + lvs[i][2]] for i in eachindex(lvs)],
-                     lv_varZeta = [d[ncp + 17 * i] for i in eachindex(lvs)], delta = raw[8 * nd + 1:8 * nd + P]))
+                     lv_varZeta = [d[ncp + 17 * i] for i in eachindex(lvs)], delta = raw[8 * nd + 1:8 * nd + P],
+                     annotProb = [reshape(d[nlv + sum(Int(rcs[j][2]) * rcn[j] for j in 1:i-1; init = 0) + 1:nlv + sum(Int(rcs[j][2]) * rcn[j] for j in 1:i; init = 0)], rcn[i], Int(rcs[i][2])) for i in eachindex(rcs)],   # ncol x A
+                     annotCat = [raw[8 * nd + P + sum(rcn[1:i-1]; init = 0) + 1:8 * nd + P + sum(rcn[1:i]; init = 0)] for i in eachindex(rcs)]))
         end
     end
 end
@@ -497,12 +569,14 @@ end
 
 Coarse seam: drop-in for `samplers.runSampler!` (src/samplers.jl:23) for models made of fixed effects (intercept, covariates,
 factors, blocked groups), Symbol / Expr random effects -- (1|g) terms and PED sets, whose Ainv the reference has built -- and Symbol marker
-sets with BayesPR / BayesB / BayesC / BayesR / BayesLV priors.  Anything else falls back to the reference sampler.
+sets with BayesPR / BayesB / BayesC / BayesR / BayesRCπ / BayesLV priors.  Anything else -- "BayesRCplus" among the methods -- falls back
+to the reference sampler.
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
                      seed::Integer=1, device::Integer=0)
     all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110); the device draws the exact Gibbs conditional of the model, NOT the reference's lines (they leave Z_ID'Z_Dam u_Dam of the other levels in a level's right-hand side), so a run sent there would not be the reference's chain -- add_random_set_tuple! / sampleZ_tuple! are there for callers who want the exact one")
     (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
+    any(s -> M[s].method == "BayesRCplus", keys(M)) && error("BayesRCplus: use the reference sampler (one step per annotation on the same column, src/functions.jl:362-419: not on the device)")
     h = Handle(device=device, seed=seed)
     E.str == "D" && set_residual_weights!(h, Vector{Float64}(E.iVarStr))   # before the panel (src/mme.jl:71-75)
     sets = collect(keys(M))                       # Dict order, as src/samplers.jl:50
@@ -526,6 +600,10 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         if M[s].method == "BayesLV"   # covariates, varZeta, estVarZeta and the reference's starting zeta (src/mme.jl:418-439)
             ids[s] = add_marker_set_lv!(h, col0, P, Float64(varBeta[s][1]), M[s].covariates, Float64(M[s].varZeta[1]), M[s].estVarZeta;
                                         zeta0 = M[s].SNPVARRESID, lhs0 = Float64.(M[s].lhs), rhs0 = Float64.(M[s].rhs))
+        elseif M[s].method == "BayesRCπ"   # per annotation a variance and a row of pi; the annotations as given (src/mme.jl:384-403)
+            ids[s] = add_marker_set_rc!(h, col0, P, Float64(M[s].df), Float64(M[s].scale), Float64(varBeta[s][1]), Float64.(vec(M[s].vClass)),
+                                        Float64.(M[s].piHat[1]), M[s].annotInput; estPi = M[s].estPi, lhs0 = Float64.(M[s].lhs),
+                                        rhs0 = Float64.(M[s].rhs))
         elseif method == 3   # ONE variance, class multipliers and class probabilities (src/mme.jl:374-383)
             ids[s] = add_marker_set_r!(h, col0, P, Float64(M[s].df), Float64(M[s].scale), Float64(varBeta[s][1]), Float64.(vec(M[s].vClass)),
                                        Float64.(vec(M[s].piHat)); estPi = M[s].estPi, lhs0 = Float64.(M[s].lhs), rhs0 = Float64.(M[s].rhs))
@@ -571,6 +649,7 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     set_sample_file!(h, nothing)                 # flushes and closes
     # ... and become the rows of the reference's *Out files afterwards, one record in memory at a time
     lvsets = [s for s in sets if M[s].method == "BayesLV"]                  # in the order the library numbers them
+    rcsets = [s for s in sets if M[s].method == "BayesRCπ"]
     foreach_sample(smpfile) do sinfo, smp
         open(io -> writedlm(io, smp.b_fixed'), outPut * "/bOut", "a")       # src/samplers.jl:57
         open(io -> writedlm(io, smp.varE), outPut * "/varEOut", "a")        # src/samplers.jl:58
@@ -587,6 +666,12 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
             if M[s].method == "BayesR"                                                              # one column per class
                 K = Int(sinfo[k][2])
                 open(io -> writedlm(io, smp.class_pi[k0+1:k0+K]'), outPut * "/pi$(s)Out", "a")
+                k0 += K
+            end
+            if M[s].method == "BayesRCπ"                                                            # :85-87; pi annotation-major
+                K = Int(sinfo[k][2])
+                open(io -> writedlm(io, smp.class_pi[k0+1:k0+K]'), outPut * "/pi$(s)Out", "a")
+                open(io -> writedlm(io, Int.(smp.annotCat[findfirst(==(s), rcsets)])'), outPut * "/annot$(s)Out", "a")
                 k0 += K
             end
             if M[s].method == "BayesLV"                                                             # :89-92
@@ -623,6 +708,13 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         P = M[s].dims[2]; nr = length(varBeta[s])
         vec(beta[M[s].pos]) .= bet[c0+1:c0+P]; vec(delta[M[s].pos]) .= del[c0+1:c0+P]
         varBeta[s] isa Vector{Float64} && (varBeta[s] .= vb[v0+1:v0+nr])
+        if M[s].method == "BayesRCπ"              # as sampleBayesRCπ! leaves it (src/functions.jl:322-360)
+            st = rc_state(h, ids[s], P, length(M[s].piHat), length(M[s].vClass))
+            for a in eachindex(M[s].piHat)
+                M[s].piHat[a] = st.piHat[a]; M[s].logPi[a] = log.(st.piHat[a])
+            end
+            M[s].annotProb .= st.annotProb; vec(M[s].annotCat) .= st.annotCat
+        end
         if M[s].method == "BayesLV"               # the variance model's state as sampleBayesLV! leaves it (src/functions.jl:466-485)
             st = lv_state(h, ids[s], P, length(M[s].c))
             M[s].c .= st.c; M[s].varZeta[1] = st.varZeta; M[s].logVar .= log.(vb[v0+1:v0+nr]); M[s].SNPVARRESID .= st.zeta

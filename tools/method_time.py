@@ -1,4 +1,5 @@
-"""Sweep time per method on one generated panel: python tools/method_time.py N P [iters]  (PR, B, C, R with 4 / 8 classes)"""
+"""Sweep time per method on one generated panel: python tools/method_time.py N P [iters]  (PR, B, C, R with 4 / 8 classes; RC with
+NGP_TOOL_METHODS=...,RC: BayesRCpi with 3 annotations x 4 classes, 5 % non-zero)"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +19,9 @@ for kind in os.environ.get("NGP_TOOL_METHODS", "PR,B,C,R4,R8").split(","):
     elif kind == "B": s.add_marker_set(0, P, 1, 4.0, v * 0.5, [(j, j + 1) for j in range(P)], np.full(P, v), pi0=0.01, estPi=True)
     elif kind == "C": s.add_marker_set(0, P, 2, 4.0, v * 0.5, [(0, P)], [v], pi0=0.01, estPi=True)
     elif kind == "R4": s.add_marker_set_r(0, P, 4.0, v * 0.5, v, [0.0, 0.01, 0.1, 1.0], [0.95, 0.03, 0.015, 0.005], estPi=True)
+    elif kind == "RC":   # three annotations (every locus in one to three of them), four classes
+        an = (np.random.default_rng(3).random((P, 3)) < 0.4).astype(np.int32); an[np.arange(P), np.random.default_rng(4).integers(0, 3, P)] = 1
+        s.add_marker_set_rc(0, P, 4.0, v * 0.5, v, [0.0, 0.01, 0.1, 1.0], [0.95, 0.03, 0.015, 0.005], an, estPi=True)
     else: s.add_marker_set_r(0, P, 4.0, v * 0.5, v, [0.0, 1e-4, 1e-3, 0.01, 0.05, 0.2, 0.5, 1.0], [0.9, 0.03, 0.02, 0.02, 0.01, 0.01, 0.005, 0.005], estPi=True)
     s.set_y(y); s.set_residual_prior(4.0, 0.25 * y.var())
     s.run(5)
