@@ -365,7 +365,8 @@ int32_t ngp_shards_for_chains(ngp_handle *h, int32_t chains, int32_t *max_shards
  * ngp_share_panel(h, first) in place of a panel upload -- no copy of the panel is made; then each handle gets its own marker sets,
  * y and seeds, and ngp_run_many(handles, K, niter) runs them fused (engines served: persistent sweep over fp32 tiles with shards of at
  * most 64 rows, lag 6 or 8, 2..8 chains -- e.g. 10k x 100k; shards of 64..224 rows, lag 4..6, two chains -- e.g. 50k x 600k; compact storage,
- * two or three chains; every method, Tuple and BayesR sets included; other layouts run the handles side by side as before).  Independent chains are
+ * two or three chains; every method, Tuple, BayesR and BayesRCpi sets included, and the chains of a pass need not hold the same
+ * methods; other layouts -- fp32 panels whose streamer workgroups own several shards among them -- run the handles side by side as before).  Independent chains are
  * the path's own parallelism (src/samplers.jl:23: one chain per Julia task). */
 int32_t ngp_share_panel(ngp_handle *h, ngp_handle *owner);
 int32_t ngp_shards_for_pass(ngp_handle *h, int32_t chains, int32_t *max_shards);
@@ -544,9 +545,9 @@ int32_t ngp_set_records(ngp_handle *h, int64_t N);
  * (annotation-major; ngp_get_class_state sees the same A K words), annotProb[ncol A] and sum_annot[ncol A] (column-major, leading
  * dimension ncol), annotCat[ncol]; any pointer may be NULL.  sum_annot[l, a] counts the kept iterations with annotCat[l] = a + 1.  All
  * of it travels in the packed posterior (sums), sample records and snapshots (csrc/ngp_state.h).  Served by the persistent sweep
- * (fp32 and compact tiles; a kernel of its own) and the per-block engine, also beside other methods in one 64-column block; fp32
- * panels whose streamer workgroups own several shards are refused.  ngp_run_many runs chains of such a model side by side (unfused):
- * a fused kernel for them does not exist.  BayesRCplus is not on the device (one step per annotation on the same column,
+ * (fp32 and compact tiles, fp32 panels whose streamer workgroups own several shards included; kernels of its own) and the per-block
+ * engine, also beside other methods in one 64-column block.  ngp_run_many fuses chains of such a model wherever it fuses chains of
+ * any other (K chains per pass, above).  Time stamps and timing modes stay refused.  BayesRCplus is not on the device (one step per annotation on the same column,
  * src/functions.jl:362-419: a different block chain). */
 int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double df, double scale, double varBeta0, const double *vClass,
                               const double *pi, int32_t K, const int32_t *annot, int64_t ld, int32_t A, int32_t estPi, const double *lhs0,

@@ -252,7 +252,8 @@ void choose_layout(int64_t N, int64_t max_shards, int64_t r_cap, int64_t *R, int
 }
 
 // LDS of the sampler workgroup: 3 Gram planes, the dlt ring, 6 vectors of the block, 2 of ints, scalars -- and the staging area of
-// the chains the kernel carries: none in the lean kernel, Tuple coefficients in the full ones, BayesR coefficients on top in the _r ones
+// the chains the kernel carries: none in the lean kernel, Tuple coefficients in the full ones (the three BayesRCpi kernels -- rc,
+// tall_rc, multi_rc -- among them: their lanes' class coefficients stay in registers), BayesR coefficients on top in the _r ones
 size_t sampler_lds(SweepKernel k) {
     const size_t base = (size_t)(3 * 4096 + 2 * NGP_RING * NGP_BLK + 6 * NGP_BLK) * sizeof(double) + 2 * NGP_BLK * sizeof(int) + 320;
     if (k == SweepKernel::lean) return base;
@@ -291,11 +292,15 @@ int64_t sweep_grid(const SweepPlan &p, int K = 1) { return K + ngp_multi_reducer
 // the kernel of a sweep launch over K chains (K = 1: one chain; K >= 2: a fused pass); diag: time stamps or a timing mode are on;
 // tup / rset: a chain has a Tuple / a BayesR set
 SweepKernel pick_kernel(const SweepPlan &p, int K, bool diag, bool tup, bool rset, bool rcset = false) {
-    // a BayesRCpi set: the kernel of its own that carries eval_rcform (one chain per pass, one shard per workgroup: ngp_add_marker_set_rc
-    // refuses the other layouts; no time stamps there)
-    // (ngp_add_marker_set_rc refuses V > 1, fusable() a fused pass, ngp_debug_stamps / ngp_debug_set_mode the diagnostics: no other
-    // kernel's eval_rform may ever see a lane of method 6)
-    if (rcset) { assert(K == 1 && p.V == 1 && !diag); return SweepKernel::rc; }
+    // a BayesRCpi set in any chain of the launch: the kernels of the fifth translation unit, whose samplers carry eval_rcform (and the
+    // Tuple and BayesR chains, so the other chains of a fused pass may hold any set) -- one chain, one chain over several shards per
+    // workgroup, K chains per pass.  No time stamps or timing modes there.
+    // (ngp_debug_stamps / ngp_debug_set_mode refuse the diagnostics, fusable() a fused pass over tall shards: no other kernel's
+    // eval_rform may ever see a lane of method 6)
+    if (rcset) {
+        assert(!diag && (K == 1 || p.V == 1));
+        return K > 1 ? SweepKernel::multi_rc : (p.V > 1 ? SweepKernel::tall_rc : SweepKernel::rc);
+    }
     if (K > 1) {  // (BayesR: the samplers of k_sweep_r, their class coefficients staged in LDS -- where that fits beside the
                   // sampler's own; else the chain of k_sweep_multi(_tup))
         if (rset && sweep_lds(p, SweepKernel::multi_r, K) <= NGP_LDS_MAX) return SweepKernel::multi_r;
@@ -724,7 +729,7 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     if (req.storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
     if (plan.mode == 1) {
         // the single-chain kernels, each with the LDS this plan launches it with (k_sweep_r where that fits)
-        for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::rc, SweepKernel::tall}) {
+        for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::rc, SweepKernel::tall, SweepKernel::tall_rc}) {
             const size_t lds = sweep_lds(plan, k);
             if (lds <= NGP_LDS_MAX) HCHK(hipFuncSetAttribute(sweep_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
@@ -2221,7 +2226,8 @@ int prepare_run(ngp_handle *h, int64_t niter) {
 
 // K chains per pass over the panel (k_sweep_multi, ngp_sweep.h): can these handles' chains share ONE sweep launch?  They must
 // share one panel (ngp_share_panel) and run the engine the fused kernel is built for: persistent sweep, fp32 tiles, phase streamer
-// on shards of at most 64 rows, lag 6 or 8, no diagnostics -- and the fused grid must fit the device.
+// on shards of at most 64 rows, lag 6 or 8, no diagnostics -- and the fused grid must fit the device.  Any marker method may sit in
+// any chain: a BayesRCpi set anywhere in the pass selects k_sweep_multi_rc (pick_kernel), on the same three streamer families.
 
 bool fusable(ngp_handle **hs, int n) {
     if (n < 2 || n > NGP_MAXC) return false;
@@ -2236,11 +2242,14 @@ bool fusable(ngp_handle **hs, int n) {
         bytes = (nt == 1 && (h0->plan.D == 4 || h0->plan.D == 6 || h0->plan.D == 8)) || (nt == 2 && (h0->plan.D == 4 || h0->plan.D == 8)) || (nt == 4 && n == 2 && h0->plan.D == 4);
     }
     if (!phase && !rows && !bytes) return false;
+    bool rcset = false;
     for (int i = 0; i < n; i++) {
         ngp_handle *h = hs[i];
         if (h->pm != h0->pm || h->device != h0->device || h->dbg_mode != 0 || h->hm.d_dbg || h->dbg_census_fail_iter > 0) return false;
-        if (!h->mm.rc.empty()) return false;  // a BayesRCpi set: no fused kernel carries its rule, the chains run side by side
+        rcset = rcset || !h->mm.rc.empty();
     }
+    // a BayesRCpi set in any chain: k_sweep_multi_rc, whose samplers stage the Tuple coefficients beside their own
+    if (rcset && sweep_lds(h0->plan, SweepKernel::multi_rc, n) > NGP_LDS_MAX) return false;
     // (the samplers sit at blocks 0, 8, .., 8 (n - 1) of the grid -- one XCD under round-robin placement: the grid must reach the last)
     const int64_t grid = sweep_grid(h0->plan, n);
     return grid <= h0->cu_count && grid > (int64_t)8 * (n - 1);
@@ -2253,9 +2262,9 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     int rc;
     for (int i = 0; i < n; i++)
         if ((rc = prepare_run(hs[i], niter))) { if (i) h->err = hs[i]->err; return rc; }
-    bool tup = false, rset = false;  // a chain with a Tuple / BayesR set: the fused kernel whose samplers hold that chain
-    for (int i = 0; i < n; i++) { tup = tup || hs[i]->ntuple > 0; rset = rset || hs[i]->nclass_total > 0; }
-    const SweepKernel kern = pick_kernel(h->plan, n, false, tup, rset);
+    bool tup = false, rset = false, rcset = false;  // a chain with a Tuple / BayesR / BayesRCpi set: the fused kernel whose samplers hold that chain
+    for (int i = 0; i < n; i++) { tup = tup || hs[i]->ntuple > 0; rset = rset || hs[i]->nclass_total > 0; rcset = rcset || !hs[i]->mm.rc.empty(); }
+    const SweepKernel kern = pick_kernel(h->plan, n, false, tup, rset, rcset);
     const int64_t grid = sweep_grid(h->plan, n);
     const size_t lds = sweep_lds(h->plan, kern, n);
     REQUIRE(lds <= NGP_LDS_MAX, NGP_ERR_STATE, "fused sweep: LDS of a streamer with this many chains exceeds 160 KiB");
@@ -3295,8 +3304,8 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
  * classes, one variance per annotation (all start at varBeta0), piHat[a] = pi for every annotation.  1 <= A <= 8, K >= 2, A K <= 16.
  * Refused: a locus without an annotation (the reference divides 0 / 0 there and throws in Categorical: such loci belong in another
  * set), entries other than 0 / 1.  delta holds the class, annotCat the annotation of a locus, both from 1.  Models with such a set
- * run the persistent sweep in a kernel of their own (k_sweep_rc) or the per-block engine; fp32 panels so tall that a streamer
- * workgroup owns several shards are refused here (compact storage or ngp_configure mode 0 serve them). */
+ * run the persistent sweep in kernels of their own (k_sweep_rc; k_sweep_tall_rc on fp32 panels so tall that a streamer workgroup owns
+ * several shards; k_sweep_multi_rc for K chains per pass) or the per-block engine. */
 int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double df, double scale, double varBeta0, const double *vClass,
                               const double *pi, int32_t K, const int32_t *annot, int64_t ld, int32_t A, int32_t estPi, const double *lhs0,
                               const double *rhs0, int32_t *set_id) {
@@ -3314,7 +3323,6 @@ int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double 
     REQUIRE(ld >= ncol, NGP_ERR_ARG, "BayesRCpi: leading dimension of annot smaller than ncol");
     REQUIRE(std::isfinite(df) && std::isfinite(scale) && df > 0, NGP_ERR_ARG, "df/scale must be finite, df > 0");
     REQUIRE(!h->hm.d_dbg && h->dbg_mode == 0, NGP_ERR_ARG, "BayesRCpi sets run in a kernel without time stamps and timing modes: switch the diagnostics off first");
-    REQUIRE(h->plan.V == 1, NGP_ERR_ARG, "BayesRCpi sets are not served on fp32 panels whose streamer workgroups own several shards: use compact storage or ngp_configure mode 0");
     double ps = 0.0;
     for (int v = 0; v < K; v++) {
         REQUIRE(std::isfinite(vClass[v]) && vClass[v] >= 0.0 && std::isfinite(pi[v]) && pi[v] > 0.0, NGP_ERR_ARG,

@@ -8,7 +8,7 @@
 // variances and (estPi) the A Dirichlet rows of pi; k_rc_annot redraws every locus' annotation probabilities.  None of them sits
 // in the chain; every one returns at once when the abort word is set.
 //
-// Fused passes (ngp_run_many's multi kernels) do not carry the rule: chains of a model with such a set run side by side, unfused.
+// In a fused pass (ngp_run_many, k_sweep_multi_rc) every chain launches these on its own stream, behind the event of the pass' sweep.
 #pragma once
 #include "ngp_common.h"
 

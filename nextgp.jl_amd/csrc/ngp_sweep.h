@@ -1636,7 +1636,7 @@ __device__ __attribute__((always_inline)) inline void publish_block(const SweepA
 // RCLS: 0 = no BayesR chain, 1 = BayesR with the lane coefficients fetched inside the block, 2 = fetched one block ahead through LDS by
 // wave 1 like the Tuple ones (10.4 -> 8.9 us per block; a flavour of its own, k_sweep_r: inside the full kernel this code cost the
 // 50k x 600k sweep of the other methods 2 %), 3 = as 1, with the lanes of BayesRCpi sets evaluated by eval_rcform (k_sweep_rc, a
-// flavour of its own for the same reason)
+// flavour of its own for the same reason; with NGBIG k_sweep_tall_rc, per chain of a fused pass k_sweep_multi_rc)
 // Class search of ONE BayesR locus with nine to sixteen classes, its classes spread over lanes 0 .. K-1 (role_sampler's lazy search,
 // RCLS == 2): lanes 8 .. K-1 read their class from the coefficient arrays in memory -- the sampler's LDS holds eight -- and the
 // steps of eval_rform run as loops over the classes.  Returns the class; dmine = this lane's dlt should its class be the one.
@@ -2414,6 +2414,23 @@ __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     constexpr int RCLSV = 3;
 #include "ngp_sweep_body.inc"
 }
+// ... on fp32 panels too tall for one shard per workgroup: the body of k_sweep_tall (below) around the same sampler, which then adds up
+// to 22 group sums (NGBIG) one block ahead.  Nothing in role_sampler ties RCLS to NGBIG: the group sums reach the chain wave as the
+// block's total before any rule of a lane is looked at.
+__global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_tall_rc(SweepArgs A) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int b = blockIdx.x;
+    if (ld_u32(A.abort_w) != 0u) return;
+    if (!sweep_census(A, b, smem)) return;
+    if (b == 0)
+        role_sampler<false, true, true, 3>(A, smem);
+    else if (b <= A.NG)
+        role_reducer<false>(A, b - 1, smem);
+    else if (A.V == 2)
+        role_streamer_rows_tall<3, 2>(A, b - 1 - A.NG, smem);
+    else
+        role_streamer_rows_tall<2, 3>(A, b - 1 - A.NG, smem);
+}
 #endif
 
 #if defined(NGP_INST_DBG) && NGP_INST_DBG == 1  // one definition: the second translation unit (it is the shorter one to compile)
@@ -3106,7 +3123,7 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows_multi(c
 #undef NGP_RSY
 }
 
-#if !defined(NGP_INST_DBG) || !NGP_INST_DBG || NGP_INST_DBG == 2 || NGP_INST_DBG == 3  // the production translation unit (ngp_sweep_inst.hip, -DNGP_INST_DBG=0), the Tuple and the BayesR one
+#if !defined(NGP_INST_DBG) || !NGP_INST_DBG || NGP_INST_DBG == 2 || NGP_INST_DBG == 3 || NGP_INST_DBG == 4  // the production translation unit (ngp_sweep_inst.hip, -DNGP_INST_DBG=0), the Tuple, the BayesR and the BayesRCpi one
 // A chain's launch arguments by RUN-TIME chain index: indexing the by-value argument M.a[c] makes the compiler copy all of M to
 // scratch (3 KB per lane) and read every field from there.  The arguments already sit in the kernarg segment -- constant address
 // space, read with scalar loads -- so the entry is addressed there directly (M is the kernel's first argument: offset 0).
@@ -3135,6 +3152,14 @@ __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_multi_r(MultiArgs M) {
     constexpr bool TUPM = true;
     constexpr int RCLSM = 2;
+#include "ngp_sweep_multi_body.inc"
+}
+#endif
+#if defined(NGP_INST_DBG) && NGP_INST_DBG == 4  // K chains per pass of which any holds a BayesRCpi set: the samplers of k_sweep_rc (they carry the Tuple and
+                                                // the BayesR chain too, so the other chains of the pass may hold any set) -- the BayesRCpi translation unit
+__global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_multi_rc(MultiArgs M) {
+    constexpr bool TUPM = true;
+    constexpr int RCLSM = 3;
 #include "ngp_sweep_multi_body.inc"
 }
 #endif

@@ -149,9 +149,10 @@ __host__ __device__ inline size_t ngp_rows_multi_lds_bytes(int R, int K, bool u8
 //   1: diag = k_sweep<true> (time stamps and timing modes exist only there), tall = k_sweep_tall (several shards per workgroup)
 //   2: tup = k_sweep_tup (models with a Tuple set), multi_tup = k_sweep_multi_tup
 //   3: r = k_sweep_r (models with a BayesR set), multi_r = k_sweep_multi_r
-//   4: rc = k_sweep_rc (models with a BayesRCpi set; no fused kernel: ngp_run_many runs such chains side by side, unfused)
+//   4: rc = k_sweep_rc (models with a BayesRCpi set), tall_rc = k_sweep_tall_rc (such models, several shards per workgroup),
+//      multi_rc = k_sweep_multi_rc (K chains per pass of which any holds such a set)
 // The single-chain kernels take a SweepArgs, the multi ones a MultiArgs.
-enum class SweepKernel { lean, diag, tup, r, tall, multi, multi_tup, multi_r, rc };
+enum class SweepKernel { lean, diag, tup, r, tall, multi, multi_tup, multi_r, rc, tall_rc, multi_rc };
 const void *sweep_kernel_0(SweepKernel k);
 const void *sweep_kernel_1(SweepKernel k);
 const void *sweep_kernel_2(SweepKernel k);

@@ -1,6 +1,6 @@
 // ngp_sweep_inst.hip -- one instantiation of the persistent sweep kernel (ngp_sweep.h) and the lookup of its host addresses.
 // Compiled five times: -DNGP_INST_DBG=0 (lean production kernel, K chains per pass), =1 (diagnostic kernel: time stamps, timing modes;
-// tall fp32 panels), =2 (full production kernel: Tuple sets, tall shards), =3 (models with a BayesR set), =4 (models with a BayesRCpi set).
+// tall fp32 panels), =2 (full production kernel: Tuple sets, tall shards), =3 (models with a BayesR set), =4 (models with a BayesRCpi set: one chain, tall fp32 panels, K chains per pass).
 #include <hip/hip_runtime.h>
 
 #include "ngp_sweep.h"
@@ -31,6 +31,8 @@ const void *NGP_CAT(sweep_kernel_, NGP_INST_DBG)(SweepKernel k) {
     case SweepKernel::multi_r: return (const void *)k_sweep_multi_r;
 #elif NGP_INST_DBG == 4
     case SweepKernel::rc: return (const void *)k_sweep_rc;
+    case SweepKernel::tall_rc: return (const void *)k_sweep_tall_rc;
+    case SweepKernel::multi_rc: return (const void *)k_sweep_multi_rc;
 #endif
     default: return nullptr;
     }

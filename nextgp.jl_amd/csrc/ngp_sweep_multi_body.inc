@@ -1,6 +1,7 @@
-// ngp_sweep_multi_body.inc -- body of the fused kernel of K chains per pass, included into its two instantiations with the compile-time
+// ngp_sweep_multi_body.inc -- body of the fused kernel of K chains per pass, included into its instantiations with the compile-time
 // flags TUPM / RCLSM in scope: k_sweep_multi (models without a Tuple set: the sampler of k_sweep<false> plus the BayesR chain),
-// k_sweep_multi_tup (models with a Tuple set) and k_sweep_multi_r (models with a BayesR set: the sampler of k_sweep_r).  Text inclusion for the reason given in ngp_sweep_body.inc.
+// k_sweep_multi_tup (models with a Tuple set), k_sweep_multi_r (models with a BayesR set: the sampler of k_sweep_r) and k_sweep_multi_rc
+// (any chain with a BayesRCpi set: the sampler of k_sweep_rc).  Text inclusion for the reason given in ngp_sweep_body.inc.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = blockIdx.x, K = M.K, NG = M.a[0].NG;
     if (ld_u32(M.a[0].abort_w) != 0u) return;
