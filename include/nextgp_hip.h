@@ -134,7 +134,8 @@ int32_t ngp_xbeta(ngp_handle *h, const double *beta, int64_t P, double *out, int
  * varBeta0 holds nreg initial variances (src/mme.jl:516); BayesB needs nreg == ncol (one region
  * per locus, src/mme.jl:356), pi0 = prior inclusion probability, estPi (src/mme.jl:359); BayesC has nreg == 1 (one
  * variance for the whole set, src/functions.jl:205,231) and, like the reference, ignores rhs0 (src/functions.jl:220);
- * lhs0/rhs0 (ncol each or NULL) are the summary-statistics terms (src/mme.jl:314-322). */
+ * lhs0/rhs0 (ncol each or NULL) are the summary-statistics terms (src/mme.jl:314-322).
+ * For every ngp_add_marker_set*: a call that is refused or fails leaves the handle as it was -- no set, no set id, the columns free. */
 int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t method, double df, double scale,
                            const int64_t *reg_start, const int64_t *reg_stop, int64_t nreg, const double *varBeta0,
                            double pi0, int32_t estPi, const double *lhs0, const double *rhs0, int32_t *set_id);
@@ -456,7 +457,7 @@ int32_t ngp_debug_throw(ngp_handle *h, int32_t kind);
  * 2 to est_fraction var(logVar) after every step (estimateVarZeta false / true / a Float64).  zeta0: ncol starting values of zeta
  * (the reference: unseeded rand(ncol), src/mme.jl:430), or NULL for keyed uniforms (kind 16); ngp_set_y goes back to them.
  * lhs0 / rhs0 as for ngp_add_marker_set.  The set contributes ncol entries to varBeta and a [0.5, 0.5] placeholder to piHat.
- * NGP_ERR_ARG (the handle unchanged): ncov outside 1..16, a non-finite entry of C or zeta0, varBeta0 <= 0, varZeta0 <= 0, est_mode
+ * NGP_ERR_ARG: ncov outside 1..16, a non-finite entry of C or zeta0, varBeta0 <= 0, varZeta0 <= 0, est_mode
  * outside 0..2, est_fraction <= 0 in mode 2, ncol < 2 with an estimated varZeta, a C'C whose Cholesky factorisation fails.
  * The fine seam (ngp_sweep_set, ngp_sweep_set_dev) on such a set does the sweep AND the variance step: varBeta (ncol) is in / out on
  * the caller's arrays; zeta, c and varZeta live in the handle. */

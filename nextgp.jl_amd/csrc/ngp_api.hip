@@ -541,7 +541,6 @@ struct ngp_handle {
                    // requests), bit 4 counts every partial before the block's barrier, bit 8 flips the publisher's early signal (the
                    // streamers read these through SweepArgs.knob); bit 10 builds the Gram window on the matrix cores (gram_engine)
                    // bit 11 switches the streamers' L2 warming off, bit 13 withholds the warmer role, bit 14 offers it below 160-row shards, bits 16-27 select the shard of the diagnostic timeline (ngp_sweep.h)
-    bool adding_r = false;  // ngp_add_marker_set is being called by ngp_add_marker_set_r
     bool poisoned = false;  // a sweep gave up half-way (abort word): the chain state is unusable until ngp_set_y / ngp_set_state
     bool exclusive = false;  // a grid of this handle was once not co-resident beside other chains' grids: its calls now lease the whole device
     int64_t last_grid = 0;       // workgroups of the last sweep launch this handle led (fused launches: K (1 + NG) + S)
@@ -1360,8 +1359,7 @@ int run_iterations(ngp_handle *h, int64_t niter, CuLease &lease, hipEvent_t *evs
 }
 
 // class probabilities / their posterior sums of a BayesR set (either may be null); also clears the class counters
-int set_class_state_dev(ngp_handle *h, int si, const double *pi, const double *sum_pi) {
-    const int K = h->sets[(size_t)si].K;
+int set_class_state_dev(ngp_handle *h, int si, int K, const double *pi, const double *sum_pi) {
     DevArray<double> d;
     int rc;
     if ((rc = d.alloc(h, (size_t)2 * NGP_RMAX))) return rc;
@@ -1431,7 +1429,7 @@ int commit(ngp_handle *h, ChainState &st, bool values, bool sums) {
         DSet &d = st.ds[(size_t)s];
         if (values) hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, s, d.piHat0, d.piHat1);
         if (sums) hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, s, d.sum_pi0, d.sum_pi1);
-        if (h->sets[(size_t)s].K > 0 && (rc = set_class_state_dev(h, s, values ? d.pic : nullptr, sums ? d.sum_pic : nullptr))) return rc;
+        if (h->sets[(size_t)s].K > 0 && (rc = set_class_state_dev(h, s, h->sets[(size_t)s].K, values ? d.pic : nullptr, sums ? d.sum_pic : nullptr))) return rc;
     }
     DScal sc;  // (the other words -- db, the fixed-point scales -- stay as they are on the device)
     HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
@@ -1608,6 +1606,221 @@ int lv_reset(ngp_handle *h, HLv &V) {
     if (!V.zeta0.empty()) HCHK(hipMemcpyAsync(V.d_zeta, V.zeta0.data(), (size_t)V.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     else hipLaunchKernelGGL(k_lv_start, dim3((unsigned)((V.n + 255) / 256)), dim3(256), 0, h->stream, (long long)V.n, V.d_zeta.get(), V.set, h->seed, (uint64_t)h->chain);
     HCHK(hipStreamSynchronize(h->stream));  // (st is a local)
+    return NGP_OK;
+}
+
+// BayesLV: inv = inv(C'C + ridge I) of the ncol x nc covariates C (column-major, leading dimension ld), Float64, fixed order:
+// (C'C)_ij = sum over the loci in ascending order of C_li C_lj (from 0.0); ridge = min_i |(C'C)_ii / 10000| (src/mme.jl:433-436);
+// A = L L' (lower Cholesky, row by row); W = inv(L) by forward substitution, column by column; inv_ij = sum_{k >= max(i, j)} W_ki W_kj
+// (ascending k)
+int lv_icpc(ngp_handle *h, const double *C, int64_t ld, int64_t ncol, int nc, std::vector<double> &inv) {
+    std::vector<double> A((size_t)nc * nc), L((size_t)nc * nc, 0.0), W((size_t)nc * nc, 0.0);
+    inv.assign((size_t)nc * nc, 0.0);
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j <= i; j++) {
+            double a = 0.0;
+            for (int64_t l = 0; l < ncol; l++) a = a + C[(size_t)i * ld + l] * C[(size_t)j * ld + l];
+            A[(size_t)i * nc + j] = a; A[(size_t)j * nc + i] = a;
+        }
+    double ridge = std::fabs(A[0] / 10000.0);
+    for (int i = 1; i < nc; i++) ridge = std::min(ridge, std::fabs(A[(size_t)i * nc + i] / 10000.0));
+    for (int i = 0; i < nc; i++) A[(size_t)i * nc + i] = A[(size_t)i * nc + i] + ridge;
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j <= i; j++) {
+            double sres = A[(size_t)i * nc + j];
+            for (int k = 0; k < j; k++) sres = sres - L[(size_t)i * nc + k] * L[(size_t)j * nc + k];
+            if (i == j) {
+                REQUIRE(std::isfinite(sres) && sres > 0.0, NGP_ERR_ARG, "BayesLV: C'C (+ ridge) is not positive definite (its Cholesky factorisation fails)");
+                L[(size_t)i * nc + i] = std::sqrt(sres);
+            } else {
+                L[(size_t)i * nc + j] = sres / L[(size_t)j * nc + j];
+            }
+        }
+    for (int j = 0; j < nc; j++)
+        for (int i = j; i < nc; i++) {
+            double sres = (i == j) ? 1.0 : 0.0;
+            for (int k = j; k < i; k++) sres = sres - L[(size_t)i * nc + k] * W[(size_t)k * nc + j];
+            W[(size_t)i * nc + j] = sres / L[(size_t)i * nc + i];
+        }
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j <= i; j++) {
+            double a = 0.0;
+            for (int k = i; k < nc; k++) a = a + W[(size_t)k * nc + i] * W[(size_t)k * nc + j];
+            REQUIRE(std::isfinite(a), NGP_ERR_ARG, "BayesLV: inverting C'C (+ ridge) overflowed");
+            inv[(size_t)i * nc + j] = a; inv[(size_t)j * nc + i] = a;
+        }
+    return NGP_OK;
+}
+
+/* ---- adding a marker set.  Every ngp_add_marker_set* is its own argument checks, a MarkerSetSpec, and commit_marker_set ---------- */
+
+struct MarkerSetSpec {
+    HSet hs;                     // the host's entry; vb_off = h->nvb: the set's variances follow those of the sets before it
+    DSet ds;                     // the device's entry (dset): complete but for pi and the class probabilities, which reset_marker_set writes
+    int64_t own0 = 0, own1 = 0;  // the columns [own0, own1) must be free and become the set's; those without a locus are marked -2
+    struct Locus { int64_t col; int32_t loc, vb; };
+    std::vector<Locus> loci;     // the columns that carry a locus, with their h_loc and h_vbidx
+    enum Regions { none, sumsq, tuple } regions = none;  // the table of region draws the set enters: h_regs (a chi-square from a sum of
+                                                         // squares), h_tregs (an inverse-Wishart), or neither (BayesB, BayesLV, BayesRCpi)
+    const int64_t *reg_start = nullptr, *reg_stop = nullptr;  // its hs.nreg regions, in loci
+    const double *lhs0 = nullptr, *rhs0 = nullptr;            // hs.ncol entries each; null: zeros
+    // the method's own state, built by its adder and taken over by the commit
+    const DTup *tup = nullptr;   // Tuple: its row of d_tup
+    HLv *lv = nullptr;           // BayesLV: becomes mm.lv[hs.lv]
+    HRc *rc = nullptr;           // BayesRCpi: becomes mm.rc[hs.rc]
+};
+
+// one locus per column of the set; locus l takes the variance vb_first + vb_step l
+void column_loci(MarkerSetSpec &sp, int64_t vb_first, int64_t vb_step) {
+    sp.own0 = sp.hs.col0; sp.own1 = sp.hs.col0 + sp.hs.ncol;
+    for (int64_t l = 0; l < sp.hs.ncol; l++) sp.loci.push_back({sp.hs.col0 + l, (int32_t)l, (int32_t)(vb_first + vb_step * l)});
+}
+
+DSet dset(int method, int estPi, double df, double scale, int64_t col0, int64_t ncol) {
+    DSet ds;
+    memset(&ds, 0, sizeof(ds));
+    ds.method = method; ds.estPi = estPi; ds.df = df; ds.scale = scale; ds.sdf = scale * df; ds.col0 = col0; ds.ncol = ncol;
+    return ds;
+}
+
+// May a set take the columns [col0, col0 + span) and own [col0, col0 + owned)?  (A tuple set owns its last 64-column block whole.)
+int check_marker_slot(ngp_handle *h, int64_t col0, int64_t span, int64_t owned, const char *outside) {
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
+    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
+    REQUIRE(col0 >= 0 && span > 0 && col0 + span <= h->P, NGP_ERR_ARG, outside);
+    for (int64_t c = col0; c < std::min<int64_t>(col0 + owned, h->Ppad); c++) REQUIRE(h->h_setof[c] == -1, NGP_ERR_ARG, "marker sets overlap");
+    return NGP_OK;
+}
+
+// regions must tile [0, n) in order (regionArray of UnitRanges, src/mme.jl:335-347)
+int check_regions(ngp_handle *h, const int64_t *reg_start, const int64_t *reg_stop, int64_t nreg, int64_t n, const char *not_covered) {
+    int64_t expect = 0;
+    for (int64_t r = 0; r < nreg; r++) {
+        REQUIRE(reg_start[r] == expect && reg_stop[r] > reg_start[r], NGP_ERR_ARG, "regions must be consecutive and non-empty");
+        expect = reg_stop[r];
+    }
+    REQUIRE(expect == n, NGP_ERR_ARG, not_covered);
+    return NGP_OK;
+}
+
+int check_classes(ngp_handle *h, const std::string &method, const double *vClass, const double *pi, int K) {
+    double ps = 0.0;
+    for (int v = 0; v < K; v++) {
+        REQUIRE(std::isfinite(vClass[v]) && vClass[v] >= 0.0 && std::isfinite(pi[v]) && pi[v] > 0.0, NGP_ERR_ARG,
+                method + ": class multipliers must be >= 0 and class probabilities > 0");
+        ps += pi[v];
+    }
+    REQUIRE(std::fabs(ps - 1.0) < 1e-8, NGP_ERR_ARG, method + ": class probabilities must sum to 1");
+    return NGP_OK;
+}
+
+// A set as a chain starts from it: the variances, pi and the class probabilities at their prior values, empty pi sums (src/mme.jl:351-360,
+// 374-383, 516).  The commit of a new set and ngp_set_y both come here: a set starts the way it restarts.  Device only; hs is the set's
+// entry, which the commit has not stored yet.
+int reset_marker_set(ngp_handle *h, int si, const HSet &hs) {
+    HCHK(hipMemcpyAsync(h->mm.d_varBeta + hs.vb_off, hs.vb0.data(), hs.vb0.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 1.0 - hs.pi0, hs.pi0);
+    hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.0, 0.0);
+    if (hs.K > 0) return set_class_state_dev(h, si, hs.K, hs.rpi.data(), std::vector<double>((size_t)hs.K, 0.0).data());
+    return NGP_OK;
+}
+
+// the variance segments (at most NGP_SEG loci each) of the region [start, stop) of set si, appended to a segment table; rg: its entry
+template <typename Reg>
+void push_region(Reg &rg, int64_t first, int64_t start, int64_t stop, int si, std::vector<long long> &seg_first, std::vector<int32_t> &seg_len,
+                 std::vector<int32_t> &seg_set) {
+    rg.seg0 = (long long)seg_first.size(); rg.set = si; rg.n = stop - start; rg.nseg = 0;
+    for (int64_t l0 = start; l0 < stop; l0 += NGP_SEG) {
+        seg_first.push_back(first + l0);
+        seg_len.push_back((int32_t)std::min<int64_t>(NGP_SEG, stop - l0));
+        seg_set.push_back((int32_t)si);
+        rg.nseg++;
+    }
+}
+
+/* The one way a marker set enters the handle.  Phase 1 is everything that can fail -- host and device memory, every upload and launch
+ * -- and writes only where no reader looks before phase 2: behind nvb, at d_sets[si] and the method's tables of a set that does not
+ * exist yet, over columns no set owns.  Phase 2 makes the set exist in the host tables and cannot fail.  A refused or failed add
+ * therefore leaves the handle as it was. */
+int commit_marker_set(ngp_handle *h, MarkerSetSpec &sp, int32_t *set_id) {
+    int rc;
+    const HSet &hs = sp.hs;
+    const int si = (int)h->sets.size();
+    const int64_t new_nvb = h->nvb + (int64_t)hs.vb0.size();
+    // ---- phase 1 ----
+    size_t nseg = 0;
+    for (int64_t r = 0; sp.regions != MarkerSetSpec::none && r < hs.nreg; r++) nseg += (size_t)((sp.reg_stop[r] - sp.reg_start[r] + NGP_SEG - 1) / NGP_SEG);
+    h->sets.reserve(h->sets.size() + 1);
+    if (sp.regions == MarkerSetSpec::sumsq) {
+        h->h_regs.reserve(h->h_regs.size() + (size_t)hs.nreg);
+        for (auto *v : {&h->h_seg_len, &h->h_seg_set}) v->reserve(v->size() + nseg);
+        h->h_seg_k0.reserve(h->h_seg_k0.size() + nseg);
+    } else if (sp.regions == MarkerSetSpec::tuple) {
+        h->h_tregs.reserve(h->h_tregs.size() + (size_t)hs.nreg);
+        for (auto *v : {&h->h_tseg_len, &h->h_tseg_set}) v->reserve(v->size() + nseg);
+        h->h_tseg_l0.reserve(h->h_tseg_l0.size() + nseg);
+    }
+    if (sp.lv) h->mm.lv.reserve(h->mm.lv.size() + 1);
+    if (sp.rc) h->mm.rc.reserve(h->mm.rc.size() + 1);
+    if (new_nvb > h->mm.vb_cap) {
+        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
+        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
+        h->mm.vb_cap = cap;
+    }
+    if (hs.K > 0 && !h->mm.d_rcls && (rc = h->mm.d_rcls.alloc(h, (size_t)4 * NGP_RMAX * (size_t)h->Ppad))) return rc;
+    if (sp.rc && !h->mm.d_rctab && (rc = h->mm.d_rctab.alloc(h, 16))) return rc;
+    if (sp.tup) {
+        if (!h->mm.d_tup && (rc = h->mm.d_tup.alloc(h, 16))) return rc;
+        if (!h->mm.d_tupc && (rc = h->mm.d_tupc.alloc(h, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
+        if (!h->mm.d_tupg && (rc = h->mm.d_tupg.alloc(h, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
+    }
+    const std::vector<double> z((size_t)((sp.lhs0 && sp.rhs0) ? 0 : hs.ncol), 0.0);
+    HCHK(hipMemcpyAsync(h->cm.d_lhs0 + hs.col0, sp.lhs0 ? sp.lhs0 : z.data(), (size_t)hs.ncol * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(h->cm.d_rhs0 + hs.col0, sp.rhs0 ? sp.rhs0 : z.data(), (size_t)hs.ncol * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(h->cm.d_sets + si, &sp.ds, sizeof(DSet), hipMemcpyHostToDevice, h->stream));
+    DRc dr;
+    if (sp.rc) {
+        dr = sp.rc->dev();
+        HCHK(hipMemcpyAsync(h->mm.d_rctab + si, &dr, sizeof(DRc), hipMemcpyHostToDevice, h->stream));
+    }
+    if (sp.tup) {
+        HCHK(hipMemcpyAsync(h->mm.d_tup + si, sp.tup, sizeof(DTup), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_tuple_gkk, dim3((unsigned)((sp.tup->nloc * sp.tup->k + 255) / 256)), dim3(256), 0, h->stream, h->pm->gramx, h->plan.D, h->pm->mpm,
+                           *sp.tup, h->mm.d_tupg, (long long)h->Ppad);
+    }
+    if ((rc = reset_marker_set(h, si, hs))) return rc;
+    HCHK(hipStreamSynchronize(h->stream));  // (the sources of the copies are the caller's, sp's and this function's locals)
+    // ---- phase 2 ----
+    std::fill(h->h_setof.begin() + sp.own0, h->h_setof.begin() + sp.own1, (int8_t)-2);
+    for (const MarkerSetSpec::Locus &l : sp.loci) {
+        h->h_setof[l.col] = (int8_t)si;
+        h->h_loc[l.col] = l.loc;
+        h->h_vbidx[l.col] = l.vb;
+    }
+    for (int64_t r = 0; sp.regions != MarkerSetSpec::none && r < hs.nreg; r++) {
+        if (sp.regions == MarkerSetSpec::sumsq) {
+            DReg dg;
+            dg.rg = (int)r; dg.vb = (int)(hs.vb_off + r);
+            push_region(dg, hs.col0, sp.reg_start[r], sp.reg_stop[r], si, h->h_seg_k0, h->h_seg_len, h->h_seg_set);
+            h->h_regs.push_back(dg);
+        } else {
+            DTReg tg;
+            tg.rg = r;
+            push_region(tg, 0, sp.reg_start[r], sp.reg_stop[r], si, h->h_tseg_l0, h->h_tseg_len, h->h_tseg_set);
+            h->h_tregs.push_back(tg);
+        }
+    }
+    h->nvb = new_nvb;
+    h->nclass_total += hs.K;
+    if (sp.tup) h->ntuple += 1;
+    if (sp.lv) h->mm.lv.push_back(std::move(*sp.lv));
+    if (sp.rc) h->mm.rc.push_back(std::move(*sp.rc));
+    h->sets.push_back(std::move(sp.hs));
+    h->tables_dirty = true;
+    h->mm.trace_ext_cap = 0;  // d_tr_pi holds one column per set: sized again by the next traced ngp_run
+    if (set_id) *set_id = si;
     return NGP_OK;
 }
 
@@ -2003,17 +2216,12 @@ int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t me
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
-    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
-    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
-    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
+    if ((rc = check_marker_slot(h, col0, ncol, ncol, "marker set outside the panel"))) return rc;
     REQUIRE(method == NGP_METHOD_BAYESPR || method == NGP_METHOD_BAYESB || method == NGP_METHOD_BAYESC || method == NGP_METHOD_BAYESR, NGP_ERR_ARG,
             "unknown method");
-    if (method == NGP_METHOD_BAYESR) REQUIRE(h->adding_r, NGP_ERR_ARG, "BayesR sets are added with ngp_add_marker_set_r (classes and their probabilities)");
+    REQUIRE(method != NGP_METHOD_BAYESR, NGP_ERR_ARG, "BayesR sets are added with ngp_add_marker_set_r (classes and their probabilities)");
     REQUIRE(reg_start && reg_stop && varBeta0 && nreg > 0, NGP_ERR_ARG, "regions / varBeta0 missing");
     REQUIRE(std::isfinite(df) && std::isfinite(scale) && df > 0, NGP_ERR_ARG, "df/scale must be finite, df > 0");
-    for (int64_t k = col0; k < col0 + ncol; k++) REQUIRE(h->h_setof[k] == -1, NGP_ERR_ARG, "marker sets overlap");
     if (method == NGP_METHOD_BAYESB) {
         REQUIRE(nreg == ncol, NGP_ERR_ARG, "BayesB needs one region per locus (src/mme.jl:356)");
         REQUIRE(pi0 > 0.0 && pi0 < 1.0, NGP_ERR_ARG, "BayesB pi must be in (0,1)");
@@ -2023,63 +2231,19 @@ int32_t ngp_add_marker_set(ngp_handle *h, int64_t col0, int64_t ncol, int32_t me
         REQUIRE(pi0 > 0.0 && pi0 < 1.0, NGP_ERR_ARG, "BayesC pi must be in (0,1)");
         REQUIRE(varBeta0[0] > 0.0, NGP_ERR_ARG, "BayesC varBeta0 must be positive");
     }
-    // regions must tile [0,ncol) in order (regionArray of UnitRanges, src/mme.jl:335-347)
-    int64_t expect = 0;
-    for (int64_t r = 0; r < nreg; r++) {
-        REQUIRE(reg_start[r] == expect && reg_stop[r] > reg_start[r], NGP_ERR_ARG, "regions must be consecutive and non-empty");
-        REQUIRE(std::isfinite(varBeta0[r]) && varBeta0[r] >= 0.0, NGP_ERR_ARG, "varBeta0 must be finite and >= 0");
-        expect = reg_stop[r];
-    }
-    REQUIRE(expect == ncol, NGP_ERR_ARG, "regions must cover the whole set");
-    const int si = (int)h->sets.size();
-    HSet hs{col0, ncol, method, df, scale, nreg, h->nvb, estPi, 0, pi0, std::vector<double>(varBeta0, varBeta0 + nreg)};
-    // grow varBeta storage
-    const int64_t new_nvb = h->nvb + nreg;
-    if (new_nvb > h->mm.vb_cap) {
-        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
-        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
-        h->mm.vb_cap = cap;
-    }
-    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, varBeta0, (size_t)nreg * sizeof(double), hipMemcpyHostToDevice));
-    for (int64_t r = 0; r < nreg; r++)
-        for (int64_t l = reg_start[r]; l < reg_stop[r]; l++) {
-            int64_t k = col0 + l;
-            h->h_setof[k] = (int8_t)si;
-            h->h_loc[k] = (int32_t)l;
-            h->h_vbidx[k] = (int32_t)(h->nvb + (method == NGP_METHOD_BAYESB ? l : r));
-        }
-    if (method == NGP_METHOD_BAYESPR || method == NGP_METHOD_BAYESC || method == NGP_METHOD_BAYESR) {  // sets whose variance comes from a sum of squares
-        for (int64_t r = 0; r < nreg; r++) {
-            DReg dr;
-            dr.seg0 = (long long)h->h_seg_k0.size();
-            dr.set = si; dr.rg = (int)r; dr.vb = (int)(h->nvb + r); dr.n = reg_stop[r] - reg_start[r];
-            int ns = 0;
-            for (int64_t l0 = reg_start[r]; l0 < reg_stop[r]; l0 += NGP_SEG) {
-                h->h_seg_k0.push_back(col0 + l0);
-                h->h_seg_len.push_back((int32_t)std::min<int64_t>(NGP_SEG, reg_stop[r] - l0));
-                h->h_seg_set.push_back((int32_t)si);
-                ns++;
-            }
-            dr.nseg = ns;
-            h->h_regs.push_back(dr);
-        }
-    }
-    std::vector<double> z((size_t)ncol, 0.0);
-    HCHK(hipMemcpy(h->cm.d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->cm.d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    DSet ds;
-    memset(&ds, 0, sizeof(ds));
-    ds.method = method; ds.estPi = estPi; ds.df = df; ds.scale = scale; ds.sdf = scale * df; ds.col0 = col0; ds.ncol = ncol;
-    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
-    const double p1 = pi0, p0 = 1.0 - pi0;
-    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, p0, p1);  // src/mme.jl:351,360
-    HCHK(hipStreamSynchronize(h->stream));
-    h->nvb = new_nvb;
-    h->sets.push_back(hs);
-    h->tables_dirty = true;
-    h->mm.trace_ext_cap = 0;  // d_tr_pi holds one column per set: sized again by the next traced ngp_run
-    if (set_id) *set_id = si;
-    return NGP_OK;
+    if ((rc = check_regions(h, reg_start, reg_stop, nreg, ncol, "regions must cover the whole set"))) return rc;
+    for (int64_t r = 0; r < nreg; r++) REQUIRE(std::isfinite(varBeta0[r]) && varBeta0[r] >= 0.0, NGP_ERR_ARG, "varBeta0 must be finite and >= 0");
+    MarkerSetSpec sp;
+    sp.hs = HSet{col0, ncol, method, df, scale, nreg, h->nvb, estPi, 0, pi0, std::vector<double>(varBeta0, varBeta0 + nreg)};
+    sp.ds = dset(method, estPi, df, scale, col0, ncol);
+    sp.own0 = col0; sp.own1 = col0 + ncol;
+    for (int64_t r = 0; r < nreg; r++)  // BayesB: a variance per locus; BayesPR, BayesC: one per region
+        for (int64_t l = reg_start[r]; l < reg_stop[r]; l++)
+            sp.loci.push_back({col0 + l, (int32_t)l, (int32_t)(h->nvb + (method == NGP_METHOD_BAYESB ? l : r))});
+    if (method != NGP_METHOD_BAYESB) sp.regions = MarkerSetSpec::sumsq;  // sets whose variance comes from a sum of squares
+    sp.reg_start = reg_start; sp.reg_stop = reg_stop;
+    sp.lhs0 = lhs0; sp.rhs0 = rhs0;
+    return commit_marker_set(h, sp, set_id);
     NGP_CATCH(h)
 }
 
@@ -2101,16 +2265,8 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     HCHK(hipMemsetAsync(h->cm.d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     // a second chain on the same handle starts from the priors, with empty posterior sums (src/mme.jl:351-360, 516)
     if (h->nvb > 0) HCHK(hipMemsetAsync(h->mm.d_sum_varBeta, 0, (size_t)h->nvb * sizeof(double), h->stream));
-    for (size_t si = 0; si < h->sets.size(); si++) {
-        const HSet &hs = h->sets[si];
-        HCHK(hipMemcpyAsync(h->mm.d_varBeta + hs.vb_off, hs.vb0.data(), hs.vb0.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, 1.0 - hs.pi0, hs.pi0);
-        hipLaunchKernelGGL(k_set_sum_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, (int)si, 0.0, 0.0);
-        if (hs.K > 0) {
-            int rc2 = set_class_state_dev(h, (int)si, hs.rpi.data(), std::vector<double>((size_t)hs.K, 0.0).data());
-            if (rc2) return rc2;
-        }
-    }
+    for (size_t si = 0; si < h->sets.size(); si++)
+        if ((rc = reset_marker_set(h, (int)si, h->sets[si]))) return rc;
     if (h->mm.nfixcol > 0) {
         HCHK(hipMemsetAsync(h->mm.d_bfix, 0, (size_t)h->mm.nfixcol * sizeof(double), h->stream));
         HCHK(hipMemsetAsync(h->mm.d_sum_bfix, 0, (size_t)h->mm.nfixcol * sizeof(double), h->stream));
@@ -3264,38 +3420,22 @@ int32_t ngp_add_marker_set_r(ngp_handle *h, int64_t col0, int64_t ncol, double d
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
-    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
+    if ((rc = check_marker_slot(h, col0, ncol, ncol, "marker set outside the panel"))) return rc;
     REQUIRE(vClass && pi && K >= 2 && K <= NGP_RMAX, NGP_ERR_ARG, "BayesR needs 2..16 variance classes with their probabilities");
-    double ps = 0.0;
-    for (int v = 0; v < K; v++) {
-        REQUIRE(std::isfinite(vClass[v]) && vClass[v] >= 0.0 && std::isfinite(pi[v]) && pi[v] > 0.0, NGP_ERR_ARG,
-                "BayesR: class multipliers must be >= 0 and class probabilities > 0");
-        ps += pi[v];
-    }
-    REQUIRE(std::fabs(ps - 1.0) < 1e-8, NGP_ERR_ARG, "BayesR: class probabilities must sum to 1");
+    if ((rc = check_classes(h, "BayesR", vClass, pi, K))) return rc;
     REQUIRE(std::isfinite(varBeta0) && varBeta0 > 0.0, NGP_ERR_ARG, "BayesR varBeta0 must be positive");
-    if (!h->mm.d_rcls) {
-        if ((rc = h->mm.d_rcls.alloc(h, (size_t)4 * NGP_RMAX * (size_t)h->Ppad))) return rc;
-    }
+    REQUIRE(std::isfinite(df) && std::isfinite(scale) && df > 0, NGP_ERR_ARG, "df/scale must be finite, df > 0");
+    MarkerSetSpec sp;
+    sp.hs = HSet{col0, ncol, NGP_METHOD_BAYESR, df, scale, 1, h->nvb, estPi, 0, 0.5, std::vector<double>(1, varBeta0)};
+    sp.hs.K = K; sp.hs.vcls.assign(vClass, vClass + K); sp.hs.rpi.assign(pi, pi + K);
+    sp.ds = dset(NGP_METHOD_BAYESR, estPi, df, scale, col0, ncol);
+    sp.ds.K = K;
+    for (int v = 0; v < K; v++) sp.ds.vcls[v] = vClass[v];
+    column_loci(sp, h->nvb, 0);  // one variance for the set, one region: drawn with BayesPR's regions
     const int64_t rs = 0, re = ncol;
-    int32_t sid = -1;
-    h->adding_r = true;
-    rc = ngp_add_marker_set(h, col0, ncol, NGP_METHOD_BAYESR, df, scale, &rs, &re, 1, &varBeta0, 0.5, estPi, lhs0, rhs0, &sid);
-    h->adding_r = false;
-    if (rc) return rc;
-    HSet &hs = h->sets[(size_t)sid];
-    hs.K = K; hs.vcls.assign(vClass, vClass + K); hs.rpi.assign(pi, pi + K);
-    DSet ds;
-    HCHK(hipMemcpy(&ds, h->cm.d_sets + sid, sizeof(DSet), hipMemcpyDeviceToHost));
-    ds.K = K;
-    for (int v = 0; v < NGP_RMAX; v++) { ds.vcls[v] = v < K ? vClass[v] : 0.0; ds.pic[v] = 0.0; ds.logpic[v] = 0.0; ds.sum_pic[v] = 0.0; ds.ncls[v] = 0; }
-    HCHK(hipMemcpy(h->cm.d_sets + sid, &ds, sizeof(DSet), hipMemcpyHostToDevice));
-    if ((rc = set_class_state_dev(h, sid, pi, std::vector<double>((size_t)K, 0.0).data()))) return rc;
-    h->nclass_total += K;
-    if (set_id) *set_id = sid;
-    return NGP_OK;
+    sp.regions = MarkerSetSpec::sumsq; sp.reg_start = &rs; sp.reg_stop = &re;
+    sp.lhs0 = lhs0; sp.rhs0 = rhs0;
+    return commit_marker_set(h, sp, set_id);
     NGP_CATCH(h)
 }
 
@@ -3312,26 +3452,15 @@ int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double 
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
-    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
-    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
-    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
+    if ((rc = check_marker_slot(h, col0, ncol, ncol, "marker set outside the panel"))) return rc;
     REQUIRE(vClass && pi && annot, NGP_ERR_ARG, "BayesRCpi: classes, their probabilities or the annotations missing");
     REQUIRE(K >= 2 && A >= 1 && A <= NGP_AMAX && (int64_t)A * K <= NGP_RMAX, NGP_ERR_ARG,
             "BayesRCpi needs K >= 2 classes and 1..8 annotations with A * K <= 16");
     REQUIRE(ld >= ncol, NGP_ERR_ARG, "BayesRCpi: leading dimension of annot smaller than ncol");
     REQUIRE(std::isfinite(df) && std::isfinite(scale) && df > 0, NGP_ERR_ARG, "df/scale must be finite, df > 0");
     REQUIRE(!h->hm.d_dbg && h->dbg_mode == 0, NGP_ERR_ARG, "BayesRCpi sets run in a kernel without time stamps and timing modes: switch the diagnostics off first");
-    double ps = 0.0;
-    for (int v = 0; v < K; v++) {
-        REQUIRE(std::isfinite(vClass[v]) && vClass[v] >= 0.0 && std::isfinite(pi[v]) && pi[v] > 0.0, NGP_ERR_ARG,
-                "BayesRCpi: class multipliers must be >= 0 and class probabilities > 0");
-        ps += pi[v];
-    }
-    REQUIRE(std::fabs(ps - 1.0) < 1e-8, NGP_ERR_ARG, "BayesRCpi: class probabilities must sum to 1");
+    if ((rc = check_classes(h, "BayesRCpi", vClass, pi, K))) return rc;
     REQUIRE(std::isfinite(varBeta0) && varBeta0 > 0.0, NGP_ERR_ARG, "BayesRCpi varBeta0 must be positive");
-    for (int64_t k = col0; k < col0 + ncol; k++) REQUIRE(h->h_setof[k] == -1, NGP_ERR_ARG, "marker sets overlap");
     HRc Rc;
     Rc.set = (int)h->sets.size(); Rc.A = A; Rc.Kc = K; Rc.n = ncol; Rc.nseg = (ncol + NGP_SEG - 1) / NGP_SEG;
     Rc.mask.assign((size_t)ncol, 0);
@@ -3344,7 +3473,6 @@ int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double 
         REQUIRE(Rc.mask[(size_t)l] != 0, NGP_ERR_ARG, "BayesRCpi: locus " + std::to_string(l) + " has no annotation (the reference divides 0 / 0 there, "
                                                       "src/mme.jl:396: such loci belong in another set)");
     }
-    // device arrays first: a failure leaves the handle as it was
     const size_t an = (size_t)A * (size_t)ncol;
     if ((rc = Rc.d_mask.alloc(h, (size_t)ncol))) return rc;
     if ((rc = Rc.d_cat.alloc(h, (size_t)ncol))) return rc;
@@ -3354,51 +3482,21 @@ int32_t ngp_add_marker_set_rc(ngp_handle *h, int64_t col0, int64_t ncol, double 
     if ((rc = Rc.d_cnt.alloc(h, (size_t)Rc.nseg * NGP_RMAX))) return rc;
     HCHK(hipMemcpy(Rc.d_mask, Rc.mask.data(), (size_t)ncol, hipMemcpyHostToDevice));
     if ((rc = rc_reset(h, Rc))) return rc;
-    if (!h->mm.d_rcls) {
-        if ((rc = h->mm.d_rcls.alloc(h, (size_t)4 * NGP_RMAX * (size_t)h->Ppad))) return rc;
-    }
-    if (!h->mm.d_rctab) {
-        if ((rc = h->mm.d_rctab.alloc(h, 16))) return rc;
-    }
     // the marker set: A variances outside the region tables (k_rc_draw draws them), A * K slots of class state
-    const int si = (int)h->sets.size(), ns = A * K;
-    HSet hs{col0, ncol, NGP_METHOD_BAYESRC, df, scale, (int64_t)A, h->nvb, estPi, 0, 0.5, std::vector<double>((size_t)A, varBeta0)};
-    hs.K = ns; hs.rc = (int)h->mm.rc.size();
-    for (int i = 0; i < ns; i++) { hs.vcls.push_back(vClass[i % K]); hs.rpi.push_back(pi[i % K]); }
-    const int64_t new_nvb = h->nvb + A;
-    if (new_nvb > h->mm.vb_cap) {
-        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
-        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
-        h->mm.vb_cap = cap;
+    const int ns = A * K;
+    MarkerSetSpec sp;
+    sp.hs = HSet{col0, ncol, NGP_METHOD_BAYESRC, df, scale, (int64_t)A, h->nvb, estPi, 0, 0.5, std::vector<double>((size_t)A, varBeta0)};
+    sp.hs.K = ns; sp.hs.rc = (int)h->mm.rc.size();
+    sp.ds = dset(NGP_METHOD_BAYESRC, estPi, df, scale, col0, ncol);
+    sp.ds.K = ns; sp.ds.rcA = A; sp.ds.rcK = K;
+    for (int i = 0; i < ns; i++) {
+        sp.hs.vcls.push_back(vClass[i % K]); sp.hs.rpi.push_back(pi[i % K]);
+        sp.ds.vcls[i] = vClass[i % K];
     }
-    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, hs.vb0.data(), (size_t)A * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<double> z((size_t)ncol, 0.0);
-    HCHK(hipMemcpy(h->cm.d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->cm.d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    DSet ds;
-    memset(&ds, 0, sizeof(ds));
-    ds.method = NGP_METHOD_BAYESRC; ds.estPi = estPi; ds.df = df; ds.scale = scale; ds.sdf = scale * df; ds.col0 = col0; ds.ncol = ncol;
-    ds.K = ns; ds.rcA = A; ds.rcK = K;
-    for (int i = 0; i < ns; i++) ds.vcls[i] = hs.vcls[(size_t)i];
-    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.5, 0.5);  // the placeholder of sets without a two-class pi
-    const DRc dr = Rc.dev();
-    HCHK(hipMemcpy(h->mm.d_rctab + si, &dr, sizeof(DRc), hipMemcpyHostToDevice));
-    HCHK(hipStreamSynchronize(h->stream));
-    for (int64_t l = 0; l < ncol; l++) {
-        h->h_setof[col0 + l] = (int8_t)si;
-        h->h_loc[col0 + l] = (int32_t)l;
-        h->h_vbidx[col0 + l] = (int32_t)h->nvb;  // (the first of the set's A variances: k_prep adds the annotation)
-    }
-    h->nvb = new_nvb;
-    h->sets.push_back(hs);
-    h->mm.rc.push_back(std::move(Rc));
-    if ((rc = set_class_state_dev(h, si, hs.rpi.data(), std::vector<double>((size_t)ns, 0.0).data()))) return rc;
-    h->nclass_total += ns;
-    h->tables_dirty = true;
-    h->mm.trace_ext_cap = 0;
-    if (set_id) *set_id = si;
-    return NGP_OK;
+    column_loci(sp, h->nvb, 0);  // (the first of the set's A variances: k_prep adds the annotation)
+    sp.lhs0 = lhs0; sp.rhs0 = rhs0;
+    sp.rc = &Rc;
+    return commit_marker_set(h, sp, set_id);
     NGP_CATCH(h)
 }
 
@@ -3461,7 +3559,7 @@ int32_t ngp_set_rc_state(ngp_handle *h, int32_t set_id, const double *piHat, con
     }
     HCHK(hipStreamSynchronize(h->stream));
     if (piHat || sum_pi)
-        if ((rc = set_class_state_dev(h, set_id, piHat, sum_pi))) return rc;
+        if ((rc = set_class_state_dev(h, set_id, hs.K, piHat, sum_pi))) return rc;
     if (annotProb) HCHK(hipMemcpy(Rc.d_prob, annotProb, an * sizeof(double), hipMemcpyHostToDevice));
     if (sum_annot) HCHK(hipMemcpy(Rc.d_sum, sum_annot, an * sizeof(double), hipMemcpyHostToDevice));
     if (annotCat) HCHK(hipMemcpy(Rc.d_cat, c8.data(), (size_t)Rc.n, hipMemcpyHostToDevice));
@@ -3479,86 +3577,35 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
-    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
-    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
     REQUIRE(k >= 1 && k <= NGP_KMAX, NGP_ERR_ARG, "a tuple holds 1..4 correlated sets");
     REQUIRE(nloc >= 1 && col0 >= 0 && col0 % NGP_BLK == 0, NGP_ERR_ARG, "tuple set: first column on a 64-column block boundary");
+    // the set owns its 64-column blocks to the end of the last one (its block chain draws whole loci; no other set's column may sit there)
+    const int64_t Lb = NGP_BLK / k, nblk = (nloc + Lb - 1) / Lb, span = NGP_BLK * (nblk - 1) + (int64_t)k * (nloc - Lb * (nblk - 1));
+    if ((rc = check_marker_slot(h, col0, span, NGP_BLK * nblk, "tuple set outside the panel"))) return rc;
     REQUIRE(scale && varBeta0 && reg_start && reg_stop && nreg > 0, NGP_ERR_ARG, "scale / varBeta0 / regions missing");
     REQUIRE(std::isfinite(df) && df > 0, NGP_ERR_ARG, "df must be finite and positive");
-    const int64_t Lb = NGP_BLK / k, nblk = (nloc + Lb - 1) / Lb, span = NGP_BLK * (nblk - 1) + (int64_t)k * (nloc - Lb * (nblk - 1));
-    REQUIRE(col0 + span <= h->P, NGP_ERR_ARG, "tuple set outside the panel");
-    REQUIRE((int64_t)nloc * k < ((int64_t)1 << 31), NGP_ERR_ARG, "tuple set too large");  // (every check in front of the first change to the host tables)
-    // the set owns its 64-column blocks to the end of the last one (its block chain draws whole loci; no other set's column may sit there)
-    for (int64_t c = col0; c < std::min<int64_t>(col0 + NGP_BLK * nblk, h->Ppad); c++) REQUIRE(h->h_setof[c] == -1, NGP_ERR_ARG, "marker sets overlap");
+    REQUIRE((int64_t)nloc * k < ((int64_t)1 << 31), NGP_ERR_ARG, "tuple set too large");
     for (int a = 0; a < k * k; a++) REQUIRE(std::isfinite(scale[a]) && std::isfinite(varBeta0[a]), NGP_ERR_ARG, "scale / varBeta0 must be finite");
     for (int a = 0; a < k; a++) REQUIRE(varBeta0[a * k + a] > 0.0, NGP_ERR_ARG, "varBeta0 must be positive definite");
-    int64_t expect = 0;
-    for (int64_t r = 0; r < nreg; r++) {
-        REQUIRE(reg_start[r] == expect && reg_stop[r] > reg_start[r], NGP_ERR_ARG, "regions must be consecutive and non-empty");
-        expect = reg_stop[r];
-    }
-    REQUIRE(expect == nloc, NGP_ERR_ARG, "regions must cover all loci of the set");
-    const int si = (int)h->sets.size();
-    const int64_t nv = nreg * k * k;
-    std::vector<double> vb0((size_t)nv);
+    if ((rc = check_regions(h, reg_start, reg_stop, nreg, nloc, "regions must cover all loci of the set"))) return rc;
+    std::vector<double> vb0((size_t)(nreg * k * k));
     for (int64_t r = 0; r < nreg; r++) for (int a = 0; a < k * k; a++) vb0[(size_t)(r * k * k + a)] = varBeta0[a];  // src/mme.jl:516
-    HSet hs{col0, span, NGP_METHOD_TUPLE, df, 0.0, nreg, h->nvb, 0, 0, 0.5, vb0};
-    hs.tk = k; hs.nloc = nloc;
-    const int64_t new_nvb = h->nvb + nv;
-    if (new_nvb > h->mm.vb_cap) {
-        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
-        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
-        h->mm.vb_cap = cap;
-    }
-    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, vb0.data(), (size_t)nv * sizeof(double), hipMemcpyHostToDevice));
-    if (!h->mm.d_tup) {
-        if ((rc = h->mm.d_tup.alloc(h, 16))) return rc;
-        if ((rc = h->mm.d_tupc.alloc(h, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
-        if ((rc = h->mm.d_tupg.alloc(h, (size_t)NGP_KMAX * (size_t)h->Ppad))) return rc;
-    }
-    for (int64_t c = col0; c < std::min<int64_t>(col0 + NGP_BLK * nblk, h->Ppad); c++) h->h_setof[c] = (int8_t)-2;  // owned, no locus (unused lanes)
-    for (int64_t r = 0; r < nreg; r++) {
+    MarkerSetSpec sp;
+    sp.hs = HSet{col0, span, NGP_METHOD_TUPLE, df, 0.0, nreg, h->nvb, 0, 0, 0.5, std::move(vb0)};
+    sp.hs.tk = k; sp.hs.nloc = nloc;
+    sp.ds = dset(NGP_METHOD_TUPLE, 0, df, 0.0, col0, span);
+    sp.own0 = col0; sp.own1 = std::min<int64_t>(col0 + NGP_BLK * nblk, h->Ppad);  // (the lanes of the last block behind the last locus: unused)
+    for (int64_t r = 0; r < nreg; r++)
         for (int64_t l = reg_start[r]; l < reg_stop[r]; l++)
-            for (int m = 0; m < k; m++) {
-                const int64_t c = tuple_col(col0, k, l, m);
-                h->h_setof[c] = (int8_t)si;
-                h->h_loc[c] = (int32_t)(l * k + m);   // also the key of the component's normal draw
-                h->h_vbidx[c] = (int32_t)(h->nvb + r * k * k);
-            }
-        DTReg tr;
-        tr.seg0 = (long long)h->h_tseg_l0.size(); tr.rg = r; tr.n = reg_stop[r] - reg_start[r]; tr.set = si;
-        int ns = 0;
-        for (int64_t l0 = reg_start[r]; l0 < reg_stop[r]; l0 += NGP_SEG) {
-            h->h_tseg_l0.push_back(l0);
-            h->h_tseg_len.push_back((int32_t)std::min<int64_t>(NGP_SEG, reg_stop[r] - l0));
-            h->h_tseg_set.push_back((int32_t)si);
-            ns++;
-        }
-        tr.nseg = ns;
-        h->h_tregs.push_back(tr);
-    }
+            for (int m = 0; m < k; m++)  // h_loc is also the key of the component's normal draw
+                sp.loci.push_back({tuple_col(col0, k, l, m), (int32_t)(l * k + m), (int32_t)(h->nvb + r * k * k)});
+    sp.regions = MarkerSetSpec::tuple; sp.reg_start = reg_start; sp.reg_stop = reg_stop;
     DTup tp;
     memset(&tp, 0, sizeof(tp));
     tp.k = k; tp.col0 = col0; tp.nloc = nloc; tp.vb_off = h->nvb; tp.df = df;
     for (int a = 0; a < k * k; a++) tp.scale[a] = scale[a];
-    HCHK(hipMemcpy(h->mm.d_tup + si, &tp, sizeof(DTup), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_tuple_gkk, dim3((unsigned)((nloc * k + 255) / 256)), dim3(256), 0, h->stream, h->pm->gramx, h->plan.D, h->pm->mpm, tp, h->mm.d_tupg,
-                       (long long)h->Ppad);
-    DSet ds;
-    memset(&ds, 0, sizeof(ds));
-    ds.method = NGP_METHOD_TUPLE; ds.df = df; ds.col0 = col0; ds.ncol = span;
-    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.5, 0.5);
-    HCHK(hipStreamSynchronize(h->stream));
-    h->nvb = new_nvb;
-    h->sets.push_back(hs);
-    h->ntuple += 1;
-    h->tables_dirty = true;
-    h->mm.trace_ext_cap = 0;
-    if (set_id) *set_id = si;
-    return NGP_OK;
+    sp.tup = &tp;
+    return commit_marker_set(h, sp, set_id);
     NGP_CATCH(h)
 }
 
@@ -3586,7 +3633,7 @@ int32_t ngp_set_class_state(ngp_handle *h, int32_t set_id, const double *piHat, 
     REQUIRE(set_id >= 0 && set_id < (int)h->sets.size(), NGP_ERR_ARG, "unknown set id");
     REQUIRE(h->sets[(size_t)set_id].K > 0 && K == h->sets[(size_t)set_id].K, NGP_ERR_ARG, "not a BayesR set, or another number of classes");
     if (piHat) for (int64_t v = 0; v < K; v++) REQUIRE(std::isfinite(piHat[v]) && piHat[v] > 0.0, NGP_ERR_ARG, "class probabilities must be > 0");
-    return set_class_state_dev(h, set_id, piHat, sum_pi);
+    return set_class_state_dev(h, set_id, (int)K, piHat, sum_pi);
     NGP_CATCH(h)
 }
 
@@ -4260,11 +4307,7 @@ int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double 
     NGP_TRY
     int rc;
     if ((rc = enter(h))) return rc;
-    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
-    REQUIRE(!h->records_only, NGP_ERR_STATE, "this handle has records but no genotype panel (ngp_set_records): it takes no marker sets and sweeps none");
-    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
-    REQUIRE(h->sets.size() < 16, NGP_ERR_ARG, "at most 16 marker sets");
-    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "marker set outside the panel");
+    if ((rc = check_marker_slot(h, col0, ncol, ncol, "marker set outside the panel"))) return rc;
     REQUIRE(ncov >= 1 && ncov <= NGP_LV_MAXCOV, NGP_ERR_ARG, "BayesLV: the covariate matrix needs 1..16 columns");
     REQUIRE(C != nullptr && ld >= ncol, NGP_ERR_ARG, "BayesLV: covariates missing (ncol x ncov, column-major, ld >= ncol)");
     REQUIRE(std::isfinite(varBeta0) && varBeta0 > 0.0, NGP_ERR_ARG, "BayesLV: varBeta0 must be finite and positive (its logarithm is modelled)");
@@ -4272,55 +4315,17 @@ int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double 
     REQUIRE(est_mode >= 0 && est_mode <= 2, NGP_ERR_ARG, "BayesLV: est_mode is 0 (fixed), 1 (var(zeta)) or 2 (fraction of var(logVar))");
     if (est_mode == 2) REQUIRE(std::isfinite(est_fraction) && est_fraction > 0.0, NGP_ERR_ARG, "BayesLV: est_fraction must be positive in mode 2");
     if (est_mode != 0) REQUIRE(ncol >= 2, NGP_ERR_ARG, "BayesLV: an estimated varZeta needs at least two loci (a sample variance)");
-    for (int64_t k = col0; k < col0 + ncol; k++) REQUIRE(h->h_setof[k] == -1, NGP_ERR_ARG, "marker sets overlap");
     for (int k = 0; k < ncov; k++)
         for (int64_t l = 0; l < ncol; l++) REQUIRE(std::isfinite(C[(size_t)k * ld + l]), NGP_ERR_ARG, "BayesLV: non-finite covariate");
     if (zeta0) for (int64_t l = 0; l < ncol; l++) REQUIRE(std::isfinite(zeta0[l]), NGP_ERR_ARG, "BayesLV: non-finite zeta0");
-    // iCpC = inv(C'C + ridge I), Float64, fixed order: (C'C)_ij = sum over the loci in ascending order of C_li C_lj (from 0.0);
-    // ridge = min_i |(C'C)_ii / 10000| (src/mme.jl:433-436); A = L L' (lower Cholesky, row by row); W = inv(L) by forward substitution,
-    // column by column; iCpC_ij = sum_{k >= max(i, j)} W_ki W_kj (ascending k)
-    const int nc = ncov;
-    std::vector<double> A((size_t)nc * nc), L((size_t)nc * nc, 0.0), W((size_t)nc * nc, 0.0), inv((size_t)nc * nc);
-    for (int i = 0; i < nc; i++)
-        for (int j = 0; j <= i; j++) {
-            double a = 0.0;
-            for (int64_t l = 0; l < ncol; l++) a = a + C[(size_t)i * ld + l] * C[(size_t)j * ld + l];
-            A[(size_t)i * nc + j] = a; A[(size_t)j * nc + i] = a;
-        }
-    double ridge = std::fabs(A[0] / 10000.0);
-    for (int i = 1; i < nc; i++) ridge = std::min(ridge, std::fabs(A[(size_t)i * nc + i] / 10000.0));
-    for (int i = 0; i < nc; i++) A[(size_t)i * nc + i] = A[(size_t)i * nc + i] + ridge;
-    for (int i = 0; i < nc; i++)
-        for (int j = 0; j <= i; j++) {
-            double sres = A[(size_t)i * nc + j];
-            for (int k = 0; k < j; k++) sres = sres - L[(size_t)i * nc + k] * L[(size_t)j * nc + k];
-            if (i == j) {
-                REQUIRE(std::isfinite(sres) && sres > 0.0, NGP_ERR_ARG, "BayesLV: C'C (+ ridge) is not positive definite (its Cholesky factorisation fails)");
-                L[(size_t)i * nc + i] = std::sqrt(sres);
-            } else {
-                L[(size_t)i * nc + j] = sres / L[(size_t)j * nc + j];
-            }
-        }
-    for (int j = 0; j < nc; j++)
-        for (int i = j; i < nc; i++) {
-            double sres = (i == j) ? 1.0 : 0.0;
-            for (int k = j; k < i; k++) sres = sres - L[(size_t)i * nc + k] * W[(size_t)k * nc + j];
-            W[(size_t)i * nc + j] = sres / L[(size_t)i * nc + i];
-        }
-    for (int i = 0; i < nc; i++)
-        for (int j = 0; j <= i; j++) {
-            double a = 0.0;
-            for (int k = i; k < nc; k++) a = a + W[(size_t)k * nc + i] * W[(size_t)k * nc + j];
-            REQUIRE(std::isfinite(a), NGP_ERR_ARG, "BayesLV: inverting C'C (+ ridge) overflowed");
-            inv[(size_t)i * nc + j] = a; inv[(size_t)j * nc + i] = a;
-        }
-    // device arrays first: a failure leaves the handle as it was
+    std::vector<double> inv;
+    if ((rc = lv_icpc(h, C, ld, ncol, ncov, inv))) return rc;
     HLv V;
     V.set = (int)h->sets.size(); V.n = ncol; V.ncov = ncov; V.mode = est_mode; V.frac = (est_mode == 2) ? est_fraction : 0.0; V.varZeta0 = varZeta0;
     if (zeta0) V.zeta0.assign(zeta0, zeta0 + ncol);
     const size_t nseg = (size_t)((ncol + 255) / 256);
     if ((rc = V.d_C.alloc(h, (size_t)ncol * ncov))) return rc;
-    if ((rc = V.d_iCpC.alloc(h, (size_t)nc * nc))) return rc;
+    if ((rc = V.d_iCpC.alloc(h, inv.size()))) return rc;
     if ((rc = V.d_zeta.alloc(h, (size_t)ncol))) return rc;
     if ((rc = V.d_logv.alloc(h, (size_t)ncol))) return rc;
     if ((rc = V.d_part.alloc(h, nseg * (size_t)ncov))) return rc;
@@ -4331,38 +4336,15 @@ int32_t ngp_add_marker_set_lv(ngp_handle *h, int64_t col0, int64_t ncol, double 
         HCHK(hipMemcpy(V.d_C + (size_t)k * ncol, C + (size_t)k * ld, (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
     HCHK(hipMemcpy(V.d_iCpC, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
     if ((rc = lv_reset(h, V))) return rc;
-    // the marker set: BayesPR with one region per locus, outside the region tables
-    const int si = (int)h->sets.size();
-    HSet hs{col0, ncol, NGP_METHOD_BAYESLV, 4.0, 0.0, ncol, h->nvb, 0, 0, 0.5, std::vector<double>((size_t)ncol, varBeta0)};
-    hs.lv = (int)h->mm.lv.size();
-    const int64_t new_nvb = h->nvb + ncol;
-    if (new_nvb > h->mm.vb_cap) {
-        const int64_t cap = std::max<int64_t>(new_nvb, 2 * h->mm.vb_cap);
-        if ((rc = grow_pair(h, h->mm.d_varBeta, h->mm.d_sum_varBeta, h->nvb, cap))) return rc;
-        h->mm.vb_cap = cap;
-    }
-    HCHK(hipMemcpy(h->mm.d_varBeta + h->nvb, hs.vb0.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<double> z((size_t)ncol, 0.0);
-    HCHK(hipMemcpy(h->cm.d_lhs0 + col0, lhs0 ? lhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    HCHK(hipMemcpy(h->cm.d_rhs0 + col0, rhs0 ? rhs0 : z.data(), (size_t)ncol * sizeof(double), hipMemcpyHostToDevice));
-    DSet ds;
-    memset(&ds, 0, sizeof(ds));
-    ds.method = NGP_METHOD_BAYESPR; ds.df = 4.0; ds.col0 = col0; ds.ncol = ncol;  // (df, scale: never read -- no region draw)
-    HCHK(hipMemcpy(h->cm.d_sets + si, &ds, sizeof(DSet), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_set_pi, dim3(1), dim3(1), 0, h->stream, h->cm.d_sets, si, 0.5, 0.5);  // the placeholder of sets without pi
-    HCHK(hipStreamSynchronize(h->stream));
-    for (int64_t l = 0; l < ncol; l++) {
-        h->h_setof[col0 + l] = (int8_t)si;
-        h->h_loc[col0 + l] = (int32_t)l;
-        h->h_vbidx[col0 + l] = (int32_t)(h->nvb + l);
-    }
-    h->nvb = new_nvb;
-    h->sets.push_back(hs);
-    h->mm.lv.push_back(std::move(V));
-    h->tables_dirty = true;
-    h->mm.trace_ext_cap = 0;
-    if (set_id) *set_id = si;
-    return NGP_OK;
+    // the marker set: BayesPR with one variance per locus, outside the region tables (df, scale: never read -- no region draw)
+    MarkerSetSpec sp;
+    sp.hs = HSet{col0, ncol, NGP_METHOD_BAYESLV, 4.0, 0.0, ncol, h->nvb, 0, 0, 0.5, std::vector<double>((size_t)ncol, varBeta0)};
+    sp.hs.lv = (int)h->mm.lv.size();
+    sp.ds = dset(NGP_METHOD_BAYESPR, 0, 4.0, 0.0, col0, ncol);
+    column_loci(sp, h->nvb, 1);
+    sp.lhs0 = lhs0; sp.rhs0 = rhs0;
+    sp.lv = &V;
+    return commit_marker_set(h, sp, set_id);
     NGP_CATCH(h)
 }
 
