@@ -557,6 +557,44 @@ int32_t ngp_get_rc_state(ngp_handle *h, int32_t set_id, double *piHat, double *s
 int32_t ngp_set_rc_state(ngp_handle *h, int32_t set_id, const double *piHat, const double *sum_pi, const double *annotProb, const int32_t *annotCat,
                          const double *sum_annot);
 
+/* ---- prediction of new individuals: mean and SD of X_new beta over the kept draws ----
+ * A prediction panel holds Np individuals x the training panel's P columns in the same column order, in the handle's storage (fp32
+ * tiles filled from f64 / f32 / u8 input; under NGP_STORAGE_U8 the byte codes, from u8 input only).  It belongs to the shared panel
+ * object: every handle that shares the training panel (ngp_share_panel, before or after) sees it, no second copy is made, and a new
+ * training panel drops it together with every chain's prediction sums.  Upload as for the training panel: ngp_begin_prediction_panel,
+ * then ngp_prediction_columns_* (any order, any boundaries; columns never written are zero columns), then ngp_end_prediction_panel;
+ * between begin and end every other call on the handle is NGP_ERR_STATE.  centre != 0 subtracts the TRAINING panel's column means
+ * (ngp_get_storage), never means of the prediction rows: fp32 tiles store (float)((double)v - mu_j) as the training tiles do, byte
+ * tiles are centred analytically with the same mu_j.  Residual weights never scale prediction rows.  ngp_load_prediction_file reads
+ * an NGPPNL01 file (8 or 2 bits) of P columns.
+ * NGP_ERR_STATE: no finished training panel, a records-only (GBLUP) handle; NGP_ERR_ARG: columns outside [0, P), Np < 1, compact
+ * storage given f64 / f32 input.  A refused call leaves a handle that still runs.
+ *
+ * From then on every KEPT iteration (the ones that accumulate the posterior sums, no others) is followed by one pass over the
+ * prediction panel: for every marker set s over its own columns g_s(i) = sum_j x_ij beta_j, g(i) = sum_s g_s(i) in set order
+ * (columns no set owns contribute nothing), accumulated in fp64 into sum[s][i] += g_s(i), sum2[s][i] += g_s(i)^2, s = 0 .. nsets with
+ * row nsets the total.  The summation order is normative and fixed ("Prediction"): the result does not depend on
+ * the grid, the device or the number of chains served by a launch.  In a fused ngp_run_many ONE launch per kept iteration serves
+ * every chain whose marker sets lie on the same columns as the leader's, each chain bit for bit what it computes alone;
+ * ngp_get_prediction_stats counts the launches a handle made and the chains they served (fused: the leader counts, the others 0).
+ * The sums are zeroed by ngp_set_y.  They are not part of snapshots, of the packed posterior or of ngp_allreduce_posterior (formats
+ * unchanged): a host carries them beside a snapshot with ngp_get_prediction / ngp_set_prediction, and pools chains itself.
+ * Arrays are [nsets + 1][Np], row-major (row s contiguous).  nKept is the count ngp_get_posterior_sums reports.
+ * ngp_get_prediction_last: g_s and g of the last kept draw.  ngp_get_prediction_layout: rows per shard R, shards S of the prediction
+ * tiles, the chunk length in columns of the normative sum, and the rows of this handle's prediction arrays (nsets + 1; 0 while it
+ * has no marker set); any pointer may be NULL. */
+int32_t ngp_begin_prediction_panel(ngp_handle *h, int64_t Np);
+int32_t ngp_prediction_columns_f64(ngp_handle *h, int64_t col0, const double *M, int64_t ncol, int64_t ld, int32_t centre);
+int32_t ngp_prediction_columns_f32(ngp_handle *h, int64_t col0, const float *M, int64_t ncol, int64_t ld, int32_t centre);
+int32_t ngp_prediction_columns_u8(ngp_handle *h, int64_t col0, const uint8_t *G, int64_t ncol, int64_t ld, int32_t centre);
+int32_t ngp_end_prediction_panel(ngp_handle *h);
+int32_t ngp_load_prediction_file(ngp_handle *h, const char *path, int32_t centre);
+int32_t ngp_get_prediction_layout(ngp_handle *h, int64_t *Np, int64_t *R, int64_t *S, int64_t *chunk_cols, int64_t *rows);
+int32_t ngp_get_prediction(ngp_handle *h, double *sum, double *sum2, int64_t rows, int64_t Np, int64_t *nKept);
+int32_t ngp_set_prediction(ngp_handle *h, const double *sum, const double *sum2, int64_t rows, int64_t Np);
+int32_t ngp_get_prediction_last(ngp_handle *h, double *out, int64_t rows, int64_t Np);
+int32_t ngp_get_prediction_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,9 +184,22 @@ SYMBOLS = [
     "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
     "ngp_get_warmer",
     "ngp_add_marker_set_rc", "ngp_get_rc_state", "ngp_set_rc_state",
+    "ngp_begin_prediction_panel", "ngp_prediction_columns_f64", "ngp_prediction_columns_f32", "ngp_prediction_columns_u8",
+    "ngp_end_prediction_panel", "ngp_load_prediction_file", "ngp_get_prediction_layout", "ngp_get_prediction", "ngp_set_prediction",
+    "ngp_get_prediction_last", "ngp_get_prediction_stats",
 ]
 
 _lib = None
+
+
+def prediction_summary(ps):
+    """Mean and SD per row of prediction sums ({"sum", "sum2", "nKept"}; sums of several chains may have been added up)."""
+    n = int(ps["nKept"])
+    if n < 1:
+        raise ValueError("no kept draw yet: the prediction sums are empty")
+    mean = ps["sum"] / n
+    sd = np.sqrt(np.maximum(0.0, ps["sum2"] / n - mean * mean))
+    return dict(nKept=n, mean=mean[-1], sd=sd[-1], sets=[dict(mean=mean[s], sd=sd[s]) for s in range(mean.shape[0] - 1)])
 
 
 class NextGPHipError(RuntimeError):
@@ -442,6 +455,77 @@ class Sampler:
         out = np.empty(self.N)
         self._chk(self.L.ngp_xbeta(self.h, _p(beta, C.c_double), C.c_int64(len(beta)), _p(out, C.c_double), C.c_int64(self.N)))
         return out
+
+    # ---- prediction panel: new individuals x the training panel's columns ---------------
+    def begin_prediction_panel(self, Np):
+        """A prediction panel of Np individuals beside the training panel: begin_prediction_panel, prediction_columns(col0, M)
+        for every column range, end_prediction_panel.  Every kept iteration then accumulates g = X_new beta (prediction())."""
+        self._chk(self.L.ngp_begin_prediction_panel(self.h, C.c_int64(Np)))
+
+    def prediction_columns(self, col0, M, centre=False):
+        """centre: subtract the TRAINING panel's column means (means()), never means of these rows."""
+        M = np.asarray(M)
+        if M.dtype == np.uint8:     # genotype codes: the only form the compact storage takes
+            M = np.asfortranarray(M)
+            f, t = self.L.ngp_prediction_columns_u8, C.c_uint8
+        elif M.dtype == np.float32:
+            M = np.asfortranarray(M)
+            f, t = self.L.ngp_prediction_columns_f32, C.c_float
+        else:
+            M = np.asfortranarray(M, dtype=np.float64)
+            f, t = self.L.ngp_prediction_columns_f64, C.c_double
+        self._chk(f(self.h, C.c_int64(col0), _p(M, t), C.c_int64(M.shape[1]), C.c_int64(M.shape[0]), C.c_int32(int(centre))))
+
+    def end_prediction_panel(self):
+        self._chk(self.L.ngp_end_prediction_panel(self.h))
+
+    def set_prediction_panel(self, M, centre=False):
+        """The three calls above for one matrix of Np x P."""
+        M = np.asarray(M)
+        self.begin_prediction_panel(M.shape[0])
+        self.prediction_columns(0, M, centre=centre)
+        self.end_prediction_panel()
+
+    def load_prediction_file(self, path, centre=True):
+        """Binary panel file (write_panel_file) of the training panel's P columns as the prediction panel."""
+        self._chk(self.L.ngp_load_prediction_file(self.h, str(path).encode(), C.c_int32(1 if centre else 0)))
+
+    def prediction_layout(self):
+        """(Np, rows per shard, shards, columns per chunk of the normative sum) of the prediction panel."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(self.L.ngp_get_prediction_layout(self.h, *[C.byref(x) for x in v], None))
+        return tuple(x.value for x in v)
+
+    def prediction_sums(self):
+        """Sums over the kept draws: sum and sum2 are [nsets + 1][Np] (last row: all sets together), nKept the number of draws."""
+        Np = self.prediction_layout()[0]
+        rows = self.nsets + 1
+        s1, s2, n = np.empty((rows, Np)), np.empty((rows, Np)), C.c_int64()
+        self._chk(self.L.ngp_get_prediction(self.h, _p(s1, C.c_double), _p(s2, C.c_double), C.c_int64(rows), C.c_int64(Np), C.byref(n)))
+        return dict(sum=s1, sum2=s2, nKept=n.value)
+
+    def set_prediction_sums(self, ps):
+        s1 = np.ascontiguousarray(ps["sum"], dtype=np.float64)
+        s2 = np.ascontiguousarray(ps["sum2"], dtype=np.float64)
+        self._chk(self.L.ngp_set_prediction(self.h, _p(s1, C.c_double), _p(s2, C.c_double), C.c_int64(s1.shape[0]), C.c_int64(s1.shape[1])))
+
+    def prediction_last(self):
+        """g of the last kept draw, [nsets + 1][Np]."""
+        Np = self.prediction_layout()[0]
+        out = np.empty((self.nsets + 1, Np))
+        self._chk(self.L.ngp_get_prediction_last(self.h, _p(out, C.c_double), C.c_int64(out.shape[0]), C.c_int64(Np)))
+        return out
+
+    def prediction_stats(self):
+        """(launches of the prediction pass this handle made, chains they served)."""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(self.L.ngp_get_prediction_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def prediction(self):
+        """Posterior mean and SD of the breeding values of the prediction panel's individuals: {"nKept", "mean", "sd" (all sets
+        together), "sets": [{"mean", "sd"} per marker set]}, sd = sqrt(max(0, sum2 / n - mean^2))."""
+        return prediction_summary(self.prediction_sums())
 
     # ---- model -------------------------------------------------------------------------
     def add_marker_set(self, col0, ncol, method, df, scale, regions, varBeta0, pi0=0.0, estPi=False, lhs0=None, rhs0=None):

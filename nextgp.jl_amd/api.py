@@ -28,7 +28,7 @@ import numpy as np
 
 from ._lib import pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names"]
+__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -708,7 +708,8 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 # runLMEM (src/MCMC.jl:31-41)
 # ----------------------------------------------------------------------------------------------
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
-            summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None):
+            summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
+            predict=None, predict_ids=None):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -730,6 +731,14 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     device subtracts it ("Correlated random-effect sets").  The two agree when no record links two different levels.  One
     u<member>Out file per component and one varU(:ID, :Dam)Out (the matrix column by column); res["random"][("ID", "Dam")] holds u
     (k x q), varU (k x k) and levels.  Refused: a GBLUP term or a (1|g) term inside a tuple, summaryStat on a tuple.
+    (8) predict={name: source for every SNP(...) term} predicts new individuals on the device: each source (a text file, an .npy
+    file, an NGPPNL01 file or an array) holds the term's columns for the SAME Np individuals; they are centred with the TRAINING column
+    means and every kept draw accumulates X_new beta (ngp_begin_prediction_panel; DESIGN.md section 2, "Prediction").  The result gains
+    res["predict"] = {"ids", "mean", "sd", "sets": {name: {"mean", "sd"}}} (mean and SD of the breeding value over the kept draws, all
+    marker sets together and per set; correlated sets count as the one set they are, under their joined name) and outFolder/gebvPredict.txt
+    holds the same columns: ID mean sd mean_<set> sd_<set> ...  predict_ids names the individuals (default 1..Np).  With chains=K the
+    sums are pooled over the chains and res["chains"][c]["predict"] is each chain's own.  GBLUP terms together with predict= raise
+    NotImplementedError; without predict= nothing differs.
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -778,6 +787,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     gblup = {t.name: dict(M=M, prior=VCV[t.name]) for t, M in zip(snps, mats_all) if t.name in gb_names}
     mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
     snps = [t for t in snps if t.name not in gb_names]
+    pmats = _prediction_sources(predict, predict_ids, snps, mats, gb_names)   # (checked before any device work)
     if not snps:
         storage = None   # (storage concerns panels only: a model without marker sets has none)
     if storage in ("u8", 1):  # codes stay codes: integer-valued float input is converted, anything else refused
@@ -789,8 +799,16 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
                 M = np.asfortranarray(M.astype(np.uint8))
             conv.append(M)
         mats = conv
+        if pmats is not None:
+            for i, M in enumerate(pmats):
+                if M.dtype != np.uint8:
+                    if not (np.all(M == np.rint(M)) and M.min() >= 0 and M.max() <= 255):
+                        raise ValueError('storage="u8" needs integer genotype codes in 0..255 in every prediction source')
+                    pmats[i] = np.asfortranarray(M.astype(np.uint8))
     if mats and not all(M.dtype == np.uint8 for M in mats):  # one byte per genotype only when every set comes that way
         mats = [np.asarray(M, dtype=np.float64) for M in mats]
+    if pmats is not None and not all(M.dtype == np.uint8 for M in pmats):
+        pmats = [np.asarray(M, dtype=np.float64) for M in pmats]
     # Correlated marker sets: a VCV key that is a TUPLE of set names (src/mme.jl:448-489) joins those sets into one unit whose loci
     # draw their k effects together (src/functions.jl:140-154).  On the device the k columns of a locus sit side by side, from a
     # 64-column boundary on (ngp_add_marker_set_tuple): the panel is assembled accordingly, everything else in formula order.
@@ -808,27 +826,8 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
             raise ValueError("Not available to use summary statistics in correlated effects")  # src/mme.jl:469
         for nm in key:
             in_tuple[nm] = key
-    units, pieces, ncols = [], [], 0          # units: ("set", name) | ("tuple", key), in formula order of their first member
-    done_t = set()
-    for t in snps:
-        if t.name in in_tuple:
-            key = in_tuple[t.name]
-            if key in done_t:
-                continue
-            done_t.add(key)
-            pad = (-ncols) % 64
-            if pad:
-                pieces.append(np.zeros((len(y), pad), dtype=mats[0].dtype)); ncols += pad
-            blk = tuple_panel([np.asfortranarray(mats[by_name[nm]]) for nm in key])
-            nloc = mats[by_name[key[0]]].shape[1]
-            units.append(("tuple", key, ncols, nloc))
-            pieces.append(blk); ncols += blk.shape[1]
-            pad = (-ncols) % 64                  # the set owns its blocks to the end of the last one
-            if pad:
-                pieces.append(np.zeros((len(y), pad), dtype=mats[0].dtype)); ncols += pad
-        else:
-            units.append(("set", t.name, ncols, mats[by_name[t.name]].shape[1]))
-            pieces.append(mats[by_name[t.name]]); ncols += mats[by_name[t.name]].shape[1]
+    units, pieces, ncols = _panel_pieces(snps, mats, by_name, in_tuple)
+    ppieces = _panel_pieces(snps, pmats, by_name, in_tuple)[1] if pmats is not None else None   # the same columns for the new individuals
     K = int(chains)
     if K < 1 or K > 8:
         raise ValueError("chains: 1..8")
@@ -857,6 +856,14 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         smp.end_panel()
     else:
         smp.set_panel(np.asfortranarray(np.concatenate(pieces, axis=1)), centre=True)  # centring: src/prepMatVec.jl:129
+    if ppieces is not None:   # the prediction panel beside it, centred with the training means; the chains that share the panel see it
+        smp.begin_prediction_panel(pmats[0].shape[0])
+        c0 = 0
+        for pc in ppieces:
+            if pc.shape[1] and np.any(pc):
+                smp.prediction_columns(c0, pc, centre=True)
+            c0 += pc.shape[1]
+        smp.end_prediction_panel()
     samplers = [smp]
     for c in range(1, K):  # the other chains share the first one's panel by reference (no copy, no second upload)
         sc = Sampler(device=device, seed=seed, chain=chain + c, storage=storage, **skw)
@@ -877,7 +884,99 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     folders = [outFolder] if K == 1 else [os.path.join(outFolder, f"chain{chain + c}") for c in range(K)]
     for f in folders:
         os.makedirs(f, exist_ok=True)
-    return _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
+    res = _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
+    if pmats is not None:
+        ids = [str(i + 1) for i in range(pmats[0].shape[0])] if predict_ids is None else [str(a) for a in predict_ids]
+        sums = [sc.prediction_sums() for sc in samplers]
+        names = [s["name"] for s in sets]
+        for r, ps in zip(res.get("chains", []), sums):
+            r["predict"] = _prediction_result(ps, ids, names)
+        pooled = dict(sum=sum(ps["sum"] for ps in sums), sum2=sum(ps["sum2"] for ps in sums), nKept=sum(ps["nKept"] for ps in sums))
+        res["predict"] = _prediction_result(pooled, ids, names)
+        write_prediction_file(os.path.join(outFolder, "gebvPredict.txt"), res["predict"])
+    return res
+
+
+def _panel_pieces(snps, mats, by_name, in_tuple):
+    """The column pieces of ONE panel from the matrices of the SNP terms (the rows may be the records' or new individuals'): a set
+    takes the next columns; the members of a correlated (Tuple) unit are interleaved from a 64-column boundary on and own their blocks
+    to the end of the last one.  Returns (units, pieces, ncols); units: ("set", name, col0, P) | ("tuple", key, col0, nloc), in formula
+    order of their first member."""
+    units, pieces, ncols = [], [], 0
+    nrows = mats[0].shape[0] if mats else 0
+    done_t = set()
+    for t in snps:
+        if t.name in in_tuple:
+            key = in_tuple[t.name]
+            if key in done_t:
+                continue
+            done_t.add(key)
+            pad = (-ncols) % 64
+            if pad:
+                pieces.append(np.zeros((nrows, pad), dtype=mats[0].dtype)); ncols += pad
+            blk = tuple_panel([np.asfortranarray(mats[by_name[nm]]) for nm in key])
+            nloc = mats[by_name[key[0]]].shape[1]
+            units.append(("tuple", key, ncols, nloc))
+            pieces.append(blk); ncols += blk.shape[1]
+            pad = (-ncols) % 64                  # the set owns its blocks to the end of the last one
+            if pad:
+                pieces.append(np.zeros((nrows, pad), dtype=mats[0].dtype)); ncols += pad
+        else:
+            units.append(("set", t.name, ncols, mats[by_name[t.name]].shape[1]))
+            pieces.append(mats[by_name[t.name]]); ncols += mats[by_name[t.name]].shape[1]
+    return units, pieces, ncols
+
+
+def _prediction_sources(predict, predict_ids, snps, mats, gb_names):
+    """runLMEM(predict=...): the genotype matrices of the new individuals, one per marker-set term in the order of `snps`, or None
+    without predict=.  Host checks only; a ValueError here comes before any device work."""
+    if predict is None:
+        if predict_ids is not None:
+            raise ValueError("predict_ids without predict=")
+        return None
+    if gb_names:
+        raise NotImplementedError(f"predict= with the GBLUP term(s) {sorted(gb_names)}: a breeding value of a new individual under GBLUP needs its "
+                                  "relationships to the records (makeG over both, src/misc.jl:145-160); prediction on the device covers marker sets")
+    if not hasattr(predict, "keys"):
+        raise ValueError("predict: a mapping from the name of every SNP(...) term to its genotype source")
+    want = [t.name for t in snps]
+    if sorted(predict.keys()) != sorted(want):
+        raise ValueError(f"predict needs exactly one source per SNP(...) term {want}, got {sorted(predict.keys())}")
+    pm = [read_genotypes(predict[nm]) for nm in want]
+    for nm, M, T in zip(want, pm, mats):
+        if M.ndim != 2 or M.shape[1] != T.shape[1]:
+            raise ValueError(f"predict[{nm!r}] holds {M.shape[1] if M.ndim == 2 else '?'} columns, the term {T.shape[1]}")
+    if len({M.shape[0] for M in pm}) != 1 or pm[0].shape[0] < 1:
+        raise ValueError(f"every prediction source needs the same individuals: rows {[M.shape[0] for M in pm]}")
+    if predict_ids is not None and len(predict_ids) != pm[0].shape[0]:
+        raise ValueError(f"predict_ids names {len(predict_ids)} individuals, the prediction sources hold {pm[0].shape[0]}")
+    return pm
+
+
+def _prediction_result(ps, ids, names):
+    from ._lib import prediction_summary
+    pr = prediction_summary(ps)
+    return dict(ids=list(ids), nKept=pr["nKept"], mean=pr["mean"], sd=pr["sd"], sets={nm: pr["sets"][k] for k, nm in enumerate(names)})
+
+
+def write_prediction_file(path, pred):
+    """gebvPredict.txt: one row per predicted individual, tab-separated: ID mean sd mean_<set> sd_<set> ... (values with the digits
+    that read back to the same Float64)."""
+    with open(path, "w") as f:
+        f.write("\t".join(["ID", "mean", "sd"] + [f"{c}_{nm}" for nm in pred["sets"] for c in ("mean", "sd")]) + "\n")
+        for i, a in enumerate(pred["ids"]):
+            row = [pred["mean"][i], pred["sd"][i]] + [pred["sets"][nm][c][i] for nm in pred["sets"] for c in ("mean", "sd")]
+            f.write("\t".join([str(a)] + [repr(float(v)) for v in row]) + "\n")
+
+
+def read_prediction_file(path):
+    """gebvPredict.txt back as {"ids", "mean", "sd", "sets": {name: {"mean", "sd"}}}."""
+    with open(path) as f:
+        head = f.readline().rstrip("\n").split("\t")
+        rows = [ln.rstrip("\n").split("\t") for ln in f if ln.strip()]
+    cols = {h: np.array([float(r[k]) for r in rows]) for k, h in enumerate(head) if k > 0}
+    names = [h[len("mean_"):] for h in head[3:] if h.startswith("mean_")]
+    return dict(ids=[r[0] for r in rows], mean=cols["mean"], sd=cols["sd"], sets={nm: dict(mean=cols[f"mean_{nm}"], sd=cols[f"sd_{nm}"]) for nm in names})
 
 
 def _random_tuples(VCV, parsed, summaryStat):

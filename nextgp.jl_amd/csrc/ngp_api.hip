@@ -16,6 +16,7 @@
 #include <cstddef>
 #include <cstring>
 #include <array>
+#include <atomic>
 #include <deque>
 #include <map>
 #include <memory>
@@ -31,6 +32,7 @@
 #include "ngp_random_tuple.h"
 #include "ngp_dense.h"
 #include "ngp_logvar.h"
+#include "ngp_predict.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
 
@@ -155,8 +157,19 @@ struct HRc {  // the per-locus state of one BayesRCpi marker set (src/mme.jl:384
     DRc dev() { DRc R; R.prob = d_prob; R.mask = d_mask; R.cat = d_cat; R.sum = d_sum; R.part = d_part; R.cnt = d_cnt; R.nseg = nseg; return R; }
 };
 
+// The prediction panel beside a training panel (ngp_begin_prediction_panel): Np individuals x the training panel's columns, in the
+// training tile layout with a plan of its own -- S shards of R <= NGP_PRED_MAXR rows
+struct PredPanel {
+    DevArray<float> tiles;  // fp32 tiles, or (compact storage) one byte per element behind the same pointer
+    DevArray<double> mean;  // Ppad: what was subtracted from every column (the training mean where the caller asked for centring, else 0)
+    int64_t Np = 0, R = 0, S = 0;
+    uint64_t id = 0;        // unique per panel: what a chain remembers of the panel its sums belong to
+    bool done = false;      // ngp_end_prediction_panel has run: the kept iterations of every chain on the panel now predict
+};
+
 // The arrays of one uploaded panel: the handles that share it (ngp_share_panel) hold a std::shared_ptr each
 struct PanelMem {
+    std::shared_ptr<PredPanel> pred;  // null: no prediction panel
     DevArray<float> tiles;  // fp32 tiles, or (compact storage) one byte per element behind the same pointer
     DevArray<double> mean;  // column means, Ppad
     DevArray<double> gramx, mpm;  // Gram window (D planes per block), x'x
@@ -441,6 +454,15 @@ struct ChainMem {
     DevArray<unsigned> d_blin;     // [NBLK] 1 = linear block (static for a model and an active set: written by sync_linear_blocks)
     int blin_for = -2;             // active set d_blin was written for (-1: the whole model, -2: stale)
     int lin_all = 0, lin_any = 0;  // every / any block of d_blin is linear
+    // prediction (ngp_predict.h): this chain's sums over kept draws [nsets + 1][Np] (last row: the total), g of the last kept draw, the
+    // chunk partials of a launch and the work items of this chain's marker sets; sized by ensure_prediction for (panel, number of sets)
+    DevArray<double> d_pred_sum, d_pred_sum2, d_pred_last, d_pred_part, d_pred_mpart;
+    DevArray<PredItem> d_pred_items;
+    DevArray<int> d_pred_set0;
+    std::vector<PredItem> pred_items;
+    uint64_t pred_for = 0;  // the panel (its id) and the number of sets the arrays above were sized for
+    int64_t pred_rows = 0;
+    int64_t pred_launches = 0, pred_served = 0;  // ngp_get_prediction_stats: launches this handle made, chains they served
 };
 
 // The model's arrays beyond the chain's: what a new panel discards (alloc_panel resets the whole group)
@@ -500,6 +522,7 @@ struct ngp_handle {
     bool records_only = false;  // ngp_set_records: N records and no genotype panel (one inert block of 64 zero columns stands in for it)
     Grm grm;                    // ngp_grm_*: independent of the panel and of the model
     bool panel_open = false;  // between ngp_begin_panel and ngp_end_panel: columns may still arrive, the Gram window does not exist yet
+    bool pred_open = false;   // between ngp_begin_prediction_panel and ngp_end_prediction_panel: only prediction columns may be called
     int cu_count = 256;
     double setup_ms[3] = {0.0, 0.0, 0.0};   // wall time of the last panel set-up: device allocation (+ zeroing) | tiles (generation / upload) | Gram window
     unsigned launch_seq = 0;                // launch nonce of the granule tags
@@ -632,8 +655,10 @@ struct CuLease {
     ~CuLease() { release(); }
 };
 
-int enter(ngp_handle *h) {
+int enter(ngp_handle *h, bool pred_call = false) {
     if (!h) return fail(nullptr, NGP_ERR_ARG, "null handle");
+    if (h->pred_open && !pred_call)
+        return fail(h, NGP_ERR_STATE, "a prediction panel is open: only ngp_prediction_columns_* and ngp_end_prediction_panel may be called until it is ended");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     return NGP_OK;
@@ -659,7 +684,7 @@ void drop_panel(ngp_handle *h) {
     h->h_setof.clear(); h->h_loc.clear(); h->h_vbidx.clear();
     h->h_regs.clear(); h->h_seg_k0.clear(); h->h_seg_len.clear(); h->h_seg_set.clear();
     h->h_tregs.clear(); h->h_tseg_l0.clear(); h->h_tseg_len.clear(); h->h_tseg_set.clear();
-    h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false; h->records_only = false;
+    h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false; h->records_only = false; h->pred_open = false;
 }
 
 // A new panel of N x P (owner: ngp_share_panel's, whose arrays and plan are taken as they are).  The old panel goes first, so that
@@ -1266,6 +1291,110 @@ void launch_random(ngp_handle *h, int r, uint64_t it) {
                        (const double *)R.d_u, R.d_vu, R.df, R.sdf, r, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
 }
 
+/* ---- prediction: g = X_new beta of every kept draw (ngp_predict.h) ---- */
+
+// does a kept iteration of this chain predict?  (a finished prediction panel beside its training panel, and marker sets to predict from)
+bool predicts(const ngp_handle *h) {
+    return h->pm && h->pm->pred && h->pm->pred->done && !h->records_only && h->cm.pred_for == h->pm->pred->id && h->cm.pred_rows > 0;
+}
+
+// the work items of a chain: every marker set in chunks of NGP_PRED_CB blocks counted from the set's first block
+std::vector<PredItem> build_pred_items(const ngp_handle *h, std::vector<int> *set0) {
+    std::vector<PredItem> items;
+    set0->assign(1, 0);
+    for (size_t s = 0; s < h->sets.size(); s++) {
+        const HSet &st = h->sets[s];
+        const int64_t j0 = st.col0, j1 = st.col0 + st.ncol, tb0 = j0 / NGP_BLK, tb1 = (j1 + NGP_BLK - 1) / NGP_BLK;
+        for (int64_t t = tb0; t < tb1; t += NGP_PRED_CB) {
+            const int64_t te = std::min<int64_t>(t + NGP_PRED_CB, tb1);
+            items.push_back(PredItem{(int)s, (int)t, (int)te, 0, (long long)std::max<int64_t>(j0, t * NGP_BLK), (long long)std::min<int64_t>(j1, te * NGP_BLK)});
+        }
+        set0->push_back((int)items.size());
+    }
+    return items;
+}
+
+bool same_pred_items(const ngp_handle *a, const ngp_handle *b) {
+    if (a->pm != b->pm || a->sets.size() != b->sets.size()) return false;
+    for (size_t s = 0; s < a->sets.size(); s++)
+        if (a->sets[s].col0 != b->sets[s].col0 || a->sets[s].ncol != b->sets[s].ncol) return false;
+    return true;
+}
+
+// The chain's prediction arrays for the panel and the sets it has now: allocated (zeroed) when either changed, zeroed again on request
+// (ngp_set_y).  Nothing to do without a finished prediction panel.
+int ensure_prediction(ngp_handle *h, bool zero) {
+    const PredPanel *pp = (h->pm && h->pm->pred && h->pm->pred->done && !h->records_only) ? h->pm->pred.get() : nullptr;
+    ChainMem &c = h->cm;
+    if (!pp || h->sets.empty()) { c.pred_for = 0; c.pred_rows = 0; return NGP_OK; }
+    const int64_t rows = (int64_t)h->sets.size() + 1, Lp = pp->R * pp->S;
+    int rc;
+    if (c.pred_for != pp->id || c.pred_rows != rows) {
+        c.pred_for = 0; c.pred_rows = 0;
+        std::vector<int> set0;
+        c.pred_items = build_pred_items(h, &set0);
+        const size_t ni = c.pred_items.size();
+        if ((rc = c.d_pred_sum.alloc(h, (size_t)rows * pp->Np)) || (rc = c.d_pred_sum2.alloc(h, (size_t)rows * pp->Np)) ||
+            (rc = c.d_pred_last.alloc(h, (size_t)rows * pp->Np)) || (rc = c.d_pred_part.alloc(h, ni * (size_t)Lp)) || (rc = c.d_pred_mpart.alloc(h, ni)) ||
+            (rc = c.d_pred_items.alloc(h, ni)) || (rc = c.d_pred_set0.alloc(h, set0.size())))
+            return rc;
+        HCHK(hipMemcpyAsync(c.d_pred_items, c.pred_items.data(), ni * sizeof(PredItem), hipMemcpyHostToDevice, h->stream));
+        HCHK(hipMemcpyAsync(c.d_pred_set0, set0.data(), set0.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));  // (set0 is a local)
+        c.pred_for = pp->id; c.pred_rows = rows;
+    } else if (zero) {
+        HCHK(hipMemsetAsync(c.d_pred_sum, 0, (size_t)rows * pp->Np * sizeof(double), h->stream));
+        HCHK(hipMemsetAsync(c.d_pred_sum2, 0, (size_t)rows * pp->Np * sizeof(double), h->stream));
+        HCHK(hipMemsetAsync(c.d_pred_last, 0, (size_t)rows * pp->Np * sizeof(double), h->stream));
+    }
+    return NGP_OK;
+}
+
+// ONE pass over the prediction panel for the n chains hs (they predict and hold their marker sets on the same columns as hs[0]), on
+// lead's stream: chunk partials, then every chain's sums.  The panel is read once however many chains there are.
+void launch_predict(ngp_handle *lead, ngp_handle **hs, int n) {
+    const PredPanel &pp = *lead->pm->pred;
+    const ChainMem &c0 = hs[0]->cm;
+    PredArgs A;
+    std::memset(&A, 0, sizeof A);
+    for (int i = 0; i < n; i++) {
+        ChainMem &c = hs[i]->cm;
+        A.c[i] = PredChain{(const double *)c.d_beta.get(), c.d_pred_part.get(), c.d_pred_mpart.get(), c.d_pred_sum.get(), c.d_pred_sum2.get(), c.d_pred_last.get()};
+    }
+    const bool u8 = lead->req.storage == 1;
+    const unsigned nitems = (unsigned)c0.pred_items.size();
+    const size_t lds = predict_lds_bytes((int)pp.R, n, u8);
+    const PredItem *items = c0.d_pred_items.get();
+    const unsigned *ab = (const unsigned *)lead->cm.d_abort;
+#define NGP_PRED_CASE(KK)                                                                                                                     \
+    case KK:                                                                                                                                  \
+        if (u8) {                                                                                                                             \
+            (void)hipFuncSetAttribute((const void *)k_predict<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
+            hipLaunchKernelGGL((k_predict<KK, true>), dim3(nitems, (unsigned)pp.S), dim3(256), lds, lead->stream, (const void *)pp.tiles.get(), \
+                               (const double *)pp.mean, items, A, (int)pp.R, (int)pp.S, (long long)(pp.R * pp.S), ab);                        \
+        } else {                                                                                                                              \
+            (void)hipFuncSetAttribute((const void *)k_predict<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
+            hipLaunchKernelGGL((k_predict<KK, false>), dim3(nitems, (unsigned)pp.S), dim3(256), lds, lead->stream, (const void *)pp.tiles.get(), \
+                               (const double *)pp.mean, items, A, (int)pp.R, (int)pp.S, (long long)(pp.R * pp.S), ab);                        \
+        }                                                                                                                                     \
+        break;
+    switch (n) {
+        NGP_PRED_CASE(1) NGP_PRED_CASE(2) NGP_PRED_CASE(3) NGP_PRED_CASE(4) NGP_PRED_CASE(5) NGP_PRED_CASE(6) NGP_PRED_CASE(7) NGP_PRED_CASE(8)
+        default: return;
+    }
+#undef NGP_PRED_CASE
+    const dim3 cg((unsigned)((pp.Np + 255) / 256), (unsigned)n);
+    const int nsets = (int)hs[0]->sets.size();
+    if (u8)
+        hipLaunchKernelGGL(k_predict_combine<true>, cg, dim3(256), 0, lead->stream, A, (const int *)c0.d_pred_set0.get(), nsets, (long long)pp.Np,
+                           (long long)(pp.R * pp.S), ab);
+    else
+        hipLaunchKernelGGL(k_predict_combine<false>, cg, dim3(256), 0, lead->stream, A, (const int *)c0.d_pred_set0.get(), nsets, (long long)pp.Np,
+                           (long long)(pp.R * pp.S), ab);
+    lead->cm.pred_launches += 1;
+    lead->cm.pred_served += n;
+}
+
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
@@ -1287,7 +1416,8 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     launch_tinv(h);
 }
 
-int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, traces and posterior sums; advances h->iter
+// predict: this chain launches its own prediction pass in a kept iteration (false: the caller serves several chains with one launch)
+int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true) {  // variance / pi draws, traces and posterior sums; advances h->iter
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!h->records_only) launch_variance(h, -1, it);
     h->iter += 1;
@@ -1315,6 +1445,7 @@ int iteration_post(ngp_handle *h, int64_t trace_idx) {  // variance / pi draws, 
         for (auto &Rc : h->mm.rc)  // BayesRCpi sets: the annotation category of every locus (src/samplers.jl:85-87)
             hipLaunchKernelGGL(k_rc_accum, dim3((unsigned)((Rc.n + 255) / 256)), dim3(256), 0, h->stream, (const DSet *)h->cm.d_sets, Rc.set, Rc.dev(),
                                (const unsigned *)h->cm.d_abort);
+        if (predict && predicts(h)) launch_predict(h, &h, 1);  // g = X_new beta of this draw, behind the posterior sums
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
     return NGP_OK;
@@ -1347,6 +1478,9 @@ int run_iterations(ngp_handle *h, int64_t niter, CuLease &lease, hipEvent_t *evs
                 // kernels behind the failing launch returned at once (abort word): the chain stands at iteration itf, head done
                 h->exclusive = true; h->census_retries += 1;
                 lease.make_exclusive();
+                if (predicts(h))  // the prediction passes behind the failing launch returned at once: they are launched again
+                    for (int64_t r = itf; r <= h->iter; r++)
+                        if (is_kept(h, r)) { h->cm.pred_launches -= 1; h->cm.pred_served -= 1; }
                 h->iter = itf - 1;
                 n = h->iter - iter0;
                 resume_mid = true;
@@ -2263,6 +2397,7 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     HCHK(hipMemsetAsync(h->cm.d_sum_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     HCHK(hipMemsetAsync(h->cm.d_sum_beta2, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     HCHK(hipMemsetAsync(h->cm.d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
+    if ((rc = ensure_prediction(h, true))) return rc;  // the prediction sums are zeroed wherever sum_beta is
     // a second chain on the same handle starts from the priors, with empty posterior sums (src/mme.jl:351-360, 516)
     if (h->nvb > 0) HCHK(hipMemsetAsync(h->mm.d_sum_varBeta, 0, (size_t)h->nvb * sizeof(double), h->stream));
     for (size_t si = 0; si < h->sets.size(); si++)
@@ -2377,7 +2512,7 @@ int prepare_run(ngp_handle *h, int64_t niter) {
         h->hm.trace_cap = niter;
     }
     h->ntrace = niter;
-    return NGP_OK;
+    return ensure_prediction(h, false);
 }
 
 // K chains per pass over the panel (k_sweep_multi, ngp_sweep.h): can these handles' chains share ONE sweep launch?  They must
@@ -2456,6 +2591,10 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
         for (int i = 1; i < n; i++) { hipError_t q = hipStreamSynchronize(hs[i]->stream); if (r == hipSuccess) r = q; }
         return r;
     };
+    // prediction: ONE pass over the prediction panel per kept iteration serves every chain of the call whose marker sets lie on the same
+    // columns as the leader's; a chain with another layout launches its own
+    std::vector<char> pred_with_leader((size_t)n, 0);
+    for (int i = 0; i < n; i++) pred_with_leader[(size_t)i] = predicts(hs[i]) && same_pred_items(h, hs[i]);
     CuLease lease(h, grid);
     e = hipEventRecord(h->ev0, h->stream);
     rc = NGP_OK;
@@ -2475,8 +2614,15 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
         h->sweep_launches += 1; h->last_grid = grid;
         (void)hipEventRecord(ev.evs, h->stream);
         for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(hs[i]->stream, ev.evs, 0);
-        for (int i = 0; i < n && rc == NGP_OK; i++) { rc = iteration_post(hs[i], it); if (rc && i) h->err = hs[i]->err; }
+        for (int i = 0; i < n && rc == NGP_OK; i++) { rc = iteration_post(hs[i], it, !pred_with_leader[(size_t)i]); if (rc && i) h->err = hs[i]->err; }
         if (rc) break;
+        {   // the chains kept in this iteration, served together on the leader's stream (their effects are final: the sweep ran there)
+            ngp_handle *served[NGP_PRED_MAXK];
+            int ns = 0;
+            for (int i = 0; i < n; i++)
+                if (pred_with_leader[(size_t)i] && is_kept(hs[i], hs[i]->iter)) served[ns++] = hs[i];
+            if (ns > 0) launch_predict(h, served, ns);
+        }
         if ((it & 15) == 15 || it + 1 == niter) {  // bound the launch queue
             e = sync_all();
             if (e == hipSuccess) {
@@ -4793,6 +4939,246 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
     if (from_grm) h->grm = Grm();  // consumed: the set owns the matrix now
     if (set_id) *set_id = (int32_t)h->mm.rnd.size();
     h->mm.rnd.push_back(std::move(R));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+}  // extern "C"
+
+/* ---- prediction panel and prediction results (ngp_predict.h; DESIGN.md section 2, "Prediction") ---- */
+namespace {
+std::atomic<uint64_t> g_pred_id{0};
+
+// the open prediction panel is abandoned: the handle is as it was without one
+void drop_prediction(ngp_handle *h) {
+    if (h->pm) h->pm->pred.reset();
+    h->pred_open = false;
+    h->cm.pred_for = 0; h->cm.pred_rows = 0;
+}
+
+int begin_prediction(ngp_handle *h, int64_t Np) {
+    REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "a prediction panel needs a finished training panel (ngp_set_panel_* / ngp_end_panel)");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "a records-only (GBLUP) handle has no marker panel to predict from");
+    REQUIRE(Np >= 1 && Np <= ((int64_t)1 << 30), NGP_ERR_ARG, "prediction panel: Np must be at least 1");
+    auto pp = std::make_shared<PredPanel>();
+    pp->Np = Np;
+    pp->R = std::min<int64_t>(NGP_PRED_MAXR, (Np + 15) / 16 * 16);
+    pp->S = (Np + pp->R - 1) / pp->R;
+    pp->id = ++g_pred_id;
+    const size_t elems = (size_t)h->NBLK * (size_t)pp->S * (size_t)pp->R * NGP_BLK;
+    int rc;
+    h->pm->pred.reset();  // (the old one goes first: two never coexist on the device)
+    if ((rc = pp->tiles.alloc(h, h->req.storage == 1 ? elems / 4 : elems))) return rc;  // born zero: columns never uploaded stay zero
+    if ((rc = pp->mean.alloc(h, (size_t)h->Ppad))) return rc;
+    HCHK(hipStreamSynchronize(h->stream));
+    h->pm->pred = std::move(pp);
+    h->pred_open = true;
+    return NGP_OK;
+}
+
+template <typename TIn>
+int prediction_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64_t ld, int centre) {
+    int rc;
+    if ((rc = enter(h, true))) return rc;
+    REQUIRE(h->pred_open && h->pm && h->pm->pred, NGP_ERR_STATE, "ngp_prediction_columns_* needs an open prediction panel (ngp_begin_prediction_panel)");
+    PredPanel &pp = *h->pm->pred;
+    REQUIRE(M != nullptr, NGP_ERR_ARG, "null panel pointer");
+    REQUIRE(ld >= pp.Np, NGP_ERR_ARG, "leading dimension smaller than Np");
+    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "column range outside the panel");
+    REQUIRE(h->req.storage == 0 || sizeof(TIn) == 1, NGP_ERR_ARG, "compact storage takes genotype codes: ngp_prediction_columns_u8 or ngp_load_prediction_file");
+    const int64_t Np = pp.Np, Lp = pp.R * pp.S;
+    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, ((int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
+    DevArray<TIn> d_g;
+    DevArray<unsigned> d_bad;
+    DevArray<double> d_scr;
+    if (d_g.alloc_raw((size_t)cchunk * ld) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
+    if ((rc = d_bad.alloc(h, 1)) || (rc = d_scr.alloc(h, (size_t)cchunk))) return rc;
+    hipError_t e = hipSuccess;
+    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += cchunk) {
+        const int64_t nc = std::min<int64_t>(cchunk, ncol - c0);
+        e = hipMemcpyAsync(d_g, M + (size_t)c0 * ld, ((size_t)(nc - 1) * ld + (size_t)Np) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) break;
+        // what is subtracted: the TRAINING panel's column means (never means of these rows), or nothing
+        double *d_mu = pp.mean + col0 + c0;
+        if (centre) e = hipMemcpyAsync(d_mu, h->pm->mean + col0 + c0, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        else e = hipMemsetAsync(d_mu, 0, (size_t)nc * sizeof(double), h->stream);
+        if (e != hipSuccess) break;
+        if constexpr (sizeof(TIn) != 1)  // (the column sums only flag non-finite values here)
+            hipLaunchKernelGGL(k_cols_mean<TIn>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, h->stream, (const TIn *)d_g, (long long)Np, (long long)ld,
+                               (long long)nc, 0, d_scr.get(), d_bad.get());
+        if constexpr (sizeof(TIn) == 1) {
+            if (h->req.storage == 1)
+                hipLaunchKernelGGL(k_cols_fill8, dim3((unsigned)((Lp / 16 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, (uint8_t *)pp.tiles.get(),
+                                   (const uint8_t *)d_g, (long long)Np, (long long)ld, (long long)(col0 + c0), (int)pp.R, (int)pp.S);
+        }
+        if (h->req.storage == 0)  // x = (float)((double)v - mu), as the training tiles are formed; residual weights never scale these rows
+            hipLaunchKernelGGL(k_cols_fill<TIn>, dim3((unsigned)((Lp / 4 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream, pp.tiles.get(), (const TIn *)d_g,
+                               (long long)Np, (long long)ld, (long long)(col0 + c0), (int)pp.R, (int)pp.S, (const double *)d_mu, (const double *)nullptr);
+        e = hipStreamSynchronize(h->stream);  // the staging buffer is reused by the next chunk
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("prediction columns: ") + hipGetErrorString(e));
+    REQUIRE(bad == 0u, NGP_ERR_ARG, "non-finite genotype value in the prediction panel");
+    return NGP_OK;
+}
+
+int end_prediction(ngp_handle *h) {
+    REQUIRE(h->pred_open && h->pm && h->pm->pred, NGP_ERR_STATE, "no open prediction panel (ngp_begin_prediction_panel)");
+    HCHK(hipStreamSynchronize(h->stream));
+    h->pm->pred->done = true;
+    h->pred_open = false;
+    return ensure_prediction(h, false);
+}
+
+// the chain's prediction arrays, checked against the caller's shape
+int prediction_shape(ngp_handle *h, int64_t rows, int64_t Np) {
+    int rc;
+    if ((rc = ensure_prediction(h, false))) return rc;
+    REQUIRE(predicts(h), NGP_ERR_STATE, "no prediction: a finished prediction panel (ngp_end_prediction_panel) and at least one marker set are needed");
+    REQUIRE(rows == h->cm.pred_rows && Np == h->pm->pred->Np, NGP_ERR_ARG,
+            "prediction arrays are [nsets + 1][Np] = [" + std::to_string(h->cm.pred_rows) + "][" + std::to_string(h->pm->pred->Np) + "]");
+    HCHK(hipStreamSynchronize(h->stream));
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t ngp_begin_prediction_panel(ngp_handle *h, int64_t Np) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    return begin_prediction(h, Np);
+    NGP_CATCH(h)
+}
+int32_t ngp_prediction_columns_f64(ngp_handle *h, int64_t col0, const double *M, int64_t ncol, int64_t ld, int32_t centre) {
+    NGP_TRY
+    return prediction_columns<double>(h, col0, M, ncol, ld, centre);
+    NGP_CATCH(h)
+}
+int32_t ngp_prediction_columns_f32(ngp_handle *h, int64_t col0, const float *M, int64_t ncol, int64_t ld, int32_t centre) {
+    NGP_TRY
+    return prediction_columns<float>(h, col0, M, ncol, ld, centre);
+    NGP_CATCH(h)
+}
+int32_t ngp_prediction_columns_u8(ngp_handle *h, int64_t col0, const uint8_t *G, int64_t ncol, int64_t ld, int32_t centre) {
+    NGP_TRY
+    return prediction_columns<uint8_t>(h, col0, G, ncol, ld, centre);
+    NGP_CATCH(h)
+}
+int32_t ngp_end_prediction_panel(ngp_handle *h) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h, true))) return rc;
+    return end_prediction(h);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_load_prediction_file(ngp_handle *h, const char *path, int32_t centre) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(path != nullptr, NGP_ERR_ARG, "null path");
+    REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "a prediction panel needs a finished training panel (ngp_set_panel_* / ngp_end_panel)");
+    File f(std::fopen(path, "rb"));
+    REQUIRE(f != nullptr, NGP_ERR_ARG, std::string("cannot open panel file ") + path);
+    PanelHeader hd;
+    if (std::fread(&hd, sizeof hd, 1, f.get()) != 1 || std::memcmp(hd.magic, "NGPPNL01", 8) != 0 || hd.N <= 0 || hd.P <= 0 || (hd.bits != 8 && hd.bits != 2))
+        return fail(h, NGP_ERR_ARG, std::string("not a panel file (magic NGPPNL01, bits 8 or 2): ") + path);
+    REQUIRE(hd.P == h->P, NGP_ERR_ARG, "the prediction file holds " + std::to_string(hd.P) + " columns, the training panel " + std::to_string(h->P));
+    const int64_t N = hd.N, P = hd.P;
+    if ((rc = begin_prediction(h, N))) return rc;
+    // whole columns through a host buffer of about 64 MiB; two-bit columns are unpacked on the host
+    const int64_t colbytes = (hd.bits == 8) ? N : (N + 3) / 4;
+    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(P, ((int64_t)64 << 20) / N));
+    std::vector<uint8_t> buf((size_t)cchunk * (size_t)N), packed((hd.bits == 2) ? (size_t)colbytes : 0);
+    std::string why;
+    rc = NGP_OK;
+    for (int64_t c0 = 0; c0 < P && why.empty() && rc == NGP_OK; c0 += cchunk) {
+        const int64_t nc = std::min<int64_t>(cchunk, P - c0);
+        for (int64_t jc = 0; jc < nc && why.empty(); jc++) {
+            uint8_t *dst = buf.data() + (size_t)jc * N;
+            if (hd.bits == 8) {
+                if (std::fread(dst, 1, (size_t)N, f.get()) != (size_t)N) why = "panel file truncated";
+            } else {
+                if (std::fread(packed.data(), 1, packed.size(), f.get()) != packed.size()) { why = "panel file truncated"; break; }
+                for (int64_t i = 0; i < N; i++) {
+                    const uint8_t g = (uint8_t)((packed[(size_t)i >> 2] >> (2 * (i & 3))) & 3u);
+                    if (g == 3) { why = "panel file holds a missing genotype (code 3): impute before loading"; break; }
+                    dst[i] = g;
+                }
+            }
+        }
+        if (why.empty()) rc = prediction_columns<uint8_t>(h, c0, buf.data(), nc, N, centre);
+    }
+    if (!why.empty()) { drop_prediction(h); return fail(h, NGP_ERR_ARG, why); }
+    if (rc) { drop_prediction(h); return rc; }
+    return end_prediction(h);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_prediction_layout(ngp_handle *h, int64_t *Np, int64_t *R, int64_t *S, int64_t *chunk_cols, int64_t *rows) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h, true))) return rc;
+    REQUIRE(h->pm && h->pm->pred, NGP_ERR_STATE, "no prediction panel");
+    if (Np) *Np = h->pm->pred->Np;
+    if (R) *R = h->pm->pred->R;
+    if (S) *S = h->pm->pred->S;
+    if (chunk_cols) *chunk_cols = (int64_t)NGP_PRED_CB * NGP_BLK;
+    if (rows) *rows = h->sets.empty() ? 0 : (int64_t)h->sets.size() + 1;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_prediction(ngp_handle *h, double *sum, double *sum2, int64_t rows, int64_t Np, int64_t *nKept) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if ((rc = prediction_shape(h, rows, Np))) return rc;
+    const size_t bytes = (size_t)rows * (size_t)Np * sizeof(double);
+    if (sum) HCHK(hipMemcpy(sum, h->cm.d_pred_sum, bytes, hipMemcpyDeviceToHost));
+    if (sum2) HCHK(hipMemcpy(sum2, h->cm.d_pred_sum2, bytes, hipMemcpyDeviceToHost));
+    if (nKept) {
+        DScal sc;
+        HCHK(hipMemcpy(&sc, h->cm.d_scal, sizeof(DScal), hipMemcpyDeviceToHost));
+        *nKept = (int64_t)sc.nKept;
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_prediction(ngp_handle *h, const double *sum, const double *sum2, int64_t rows, int64_t Np) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(sum && sum2, NGP_ERR_ARG, "null prediction sums");
+    if ((rc = prediction_shape(h, rows, Np))) return rc;
+    const size_t bytes = (size_t)rows * (size_t)Np * sizeof(double);
+    HCHK(hipMemcpy(h->cm.d_pred_sum, sum, bytes, hipMemcpyHostToDevice));
+    HCHK(hipMemcpy(h->cm.d_pred_sum2, sum2, bytes, hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_prediction_last(ngp_handle *h, double *out, int64_t rows, int64_t Np) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(out != nullptr, NGP_ERR_ARG, "null output");
+    if ((rc = prediction_shape(h, rows, Np))) return rc;
+    HCHK(hipMemcpy(out, h->cm.d_pred_last, (size_t)rows * (size_t)Np * sizeof(double), hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_prediction_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if (launches) *launches = h->cm.pred_launches;
+    if (chains_served) *chains_served = h->cm.pred_served;
     return NGP_OK;
     NGP_CATCH(h)
 }

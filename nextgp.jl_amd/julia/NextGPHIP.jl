@@ -84,6 +84,88 @@ end
 load_panel_file!(h::Handle, path::AbstractString; centre::Bool=true) =
     check(h, ccall((:ngp_load_panel_file, LIB), Int32, (Ptr{Cvoid}, Cstring, Int32), h.ptr, path, centre))
 
+# ---- prediction of new individuals (include/nextgp_hip.h, "prediction") ----
+# A second panel beside the training panel: Np individuals x the same columns in the same order, centred with the TRAINING means.
+# Every kept iteration then accumulates g = X_new beta per marker set on the device.  Column ranges as for the training panel.
+begin_prediction_panel!(h::Handle, Np::Integer) =
+    check(h, ccall((:ngp_begin_prediction_panel, LIB), Int32, (Ptr{Cvoid}, Int64), h.ptr, Np))
+prediction_columns!(h::Handle, col0::Integer, data::Matrix{Float64}; centre::Bool=true) =
+    check(h, ccall((:ngp_prediction_columns_f64, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int64, Int32),
+                   h.ptr, col0, data, size(data, 2), stride(data, 2), centre))
+prediction_columns!(h::Handle, col0::Integer, data::Matrix{Float32}; centre::Bool=true) =
+    check(h, ccall((:ngp_prediction_columns_f32, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Int64, Int32),
+                   h.ptr, col0, data, size(data, 2), stride(data, 2), centre))
+prediction_columns!(h::Handle, col0::Integer, data::Matrix{UInt8}; centre::Bool=true) =
+    check(h, ccall((:ngp_prediction_columns_u8, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Int64, Int64, Int32),
+                   h.ptr, col0, data, size(data, 2), stride(data, 2), centre))
+end_prediction_panel!(h::Handle) = check(h, ccall((:ngp_end_prediction_panel, LIB), Int32, (Ptr{Cvoid},), h.ptr))
+load_prediction_file!(h::Handle, path::AbstractString; centre::Bool=true) =
+    check(h, ccall((:ngp_load_prediction_file, LIB), Int32, (Ptr{Cvoid}, Cstring, Int32), h.ptr, path, centre))
+
+function prediction_layout(h::Handle)   # Np, rows per shard, shards, columns per chunk of the normative sum, rows of the arrays (nsets + 1)
+    np = Ref{Int64}(0); r = Ref{Int64}(0); s = Ref{Int64}(0); c = Ref{Int64}(0); rows = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_prediction_layout, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                   h.ptr, np, r, s, c, rows))
+    return (Np = Int(np[]), R = Int(r[]), S = Int(s[]), chunk = Int(c[]), rows = Int(rows[]))
+end
+
+"""
+    setPrediction!(h, Mpred::Dict; sets = collect(keys(Mpred)), centre = false)
+
+The genotypes of the individuals to predict, one matrix per marker set under the keys of `M`: handed over one set after another in
+the order `runSampler!` hands over `M[set].data` (pass `sets = collect(keys(M))`), never concatenated on the host.  `Mpred[s]` is
+`Np x M[s].dims[2]`.  The reference's `M[set].data` is already centred (src/prepMatVec.jl:129) and the library then holds zero means,
+so `Mpred[s]` must be centred by the caller with the TRAINING column means (`centre = false`, the default here); with raw codes on
+both sides (`set_panel!(h, ::Matrix{UInt8})`) pass `centre = true` and the library subtracts the training means it computed.
+"""
+function setPrediction!(h::Handle, Mpred::Dict; sets = collect(keys(Mpred)), centre::Bool=false)
+    isempty(sets) && error("setPrediction!: no marker set")
+    Np = size(Mpred[sets[1]], 1)
+    all(s -> size(Mpred[s], 1) == Np, sets) || error("setPrediction!: every set needs the same individuals (rows)")
+    begin_prediction_panel!(h, Np)
+    col0 = 0
+    for s in sets
+        prediction_columns!(h, col0, Mpred[s]; centre = centre)
+        col0 += size(Mpred[s], 2)
+    end
+    end_prediction_panel!(h)
+    return h
+end
+
+"""
+    getPrediction(h)
+
+Posterior mean and SD of the breeding values of the prediction panel's individuals over the kept draws: `mean` and `sd` for all
+marker sets together, `set_mean` / `set_sd` (`nsets x Np`, in the order the sets were added), `nKept`, and the sums themselves
+(`sum`, `sum2`: `Np x (nsets + 1)` as Julia sees the library's row-major `[nsets + 1][Np]`), which `setPrediction_sums!` restores on a
+resumed chain.  `sd = sqrt(max(0, sum2 / n - mean^2))`.
+"""
+function getPrediction(h::Handle)
+    lay = prediction_layout(h)
+    lay.rows > 0 || error("getPrediction: the handle has no marker set")
+    s1 = Matrix{Float64}(undef, lay.Np, lay.rows); s2 = similar(s1); n = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_prediction, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ref{Int64}),
+                   h.ptr, s1, s2, lay.rows, lay.Np, n))
+    nk = max(Int(n[]), 1)
+    m = s1 ./ nk
+    sd = sqrt.(max.(0.0, s2 ./ nk .- m .* m))
+    return (nKept = Int(n[]), mean = m[:, end], sd = sd[:, end], set_mean = permutedims(m[:, 1:end-1]), set_sd = permutedims(sd[:, 1:end-1]),
+            sum = s1, sum2 = s2)
+end
+setPrediction_sums!(h::Handle, s1::Matrix{Float64}, s2::Matrix{Float64}) =
+    check(h, ccall((:ngp_set_prediction, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64), h.ptr, s1, s2, size(s1, 2), size(s1, 1)))
+function prediction_last(h::Handle)      # g of the last kept draw, Np x (nsets + 1)
+    lay = prediction_layout(h)
+    out = Matrix{Float64}(undef, lay.Np, lay.rows)
+    check(h, ccall((:ngp_get_prediction_last, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64), h.ptr, out, lay.rows, lay.Np))
+    return out
+end
+function prediction_stats(h::Handle)     # launches of the prediction pass this handle made, chains they served
+    a = Ref{Int64}(0); b = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_prediction_stats, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), h.ptr, a, b))
+    return (launches = Int(a[]), chains_served = Int(b[]))
+end
+
 # regionArray::Vector{UnitRange{Int}} (1-based, src/mme.jl:335-358) -> 0-based [start, stop)
 function add_marker_set!(h::Handle, col0::Integer, ncol::Integer, method::Integer, df::Float64, scale::Float64,
                          regionArray, varBeta0::Vector{Float64}; pi0::Float64=0.0, estPi::Bool=false,
