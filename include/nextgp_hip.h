@@ -595,6 +595,37 @@ int32_t ngp_set_prediction(ngp_handle *h, const double *sum, const double *sum2,
 int32_t ngp_get_prediction_last(ngp_handle *h, double *out, int64_t rows, int64_t Np);
 int32_t ngp_get_prediction_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served);
 
+/* ---- genomic variance of every kept draw: windows, marker sets, total, and the window posterior probability of association ----
+ * Behind every KEPT iteration (and in no other) one pass over the training panel forms, over the N training individuals,
+ * V_w = var_i sum_{j in w} x_ij beta_j for every window w, V_s for every marker set and V_g for all sets together (sample variance,
+ * N - 1, clamped at 0), q = V / V_g (0 when V_g == 0), r = V_g / (V_g + varE) and the indicator [q > threshold].  The arithmetic is
+ * normative ("Genomic variance"; tests/ref_genvar.py): the results do not depend on the layout of the tiles,
+ * the engine, the chains of a fused launch or the device.
+ * ngp_set_variance_windows: the windows of marker set set_id as half-open column ranges [start, stop) relative to the set's first
+ * column (a Tuple set: relative to its span): ascending, disjoint, non-empty, inside the set; they need not cover it.  nwin = 0
+ * drops the set's windows.  Legal any time after the set exists; zeroes this chain's variance sums.
+ * ngp_enable_genomic_variance: on / off, the threshold in [0, 1], and the rows of the per-draw trace (0: none; draws beyond it are
+ * counted, not stored).  Needs a finished panel; refused (NGP_ERR_STATE) on a records-only handle, with residual weights (the tiles
+ * then hold row-scaled values whose variance is not var(X beta)), with N < 2 and with N > 2^18 (the head-room of the 64-bit
+ * fixed-point sums is argued for 2^18 terms).  Enabling zeroes the sums.
+ * Slots, in order: the windows of set 0, of set 1, ..., then one per set in set order, then the total: nslots = nwin_total + nsets + 1.
+ * ngp_get_genomic_variance: sums over the kept draws per slot -- V, V^2, q, q^2, the count of q > threshold -- the last draw's V,
+ * ratio[2] = sum r, sum r^2, and the number of draws in them (any pointer may be NULL); ngp_set_genomic_variance puts them back
+ * (resume).  ngp_get_genomic_variance_trace: V [rows][nslots] and r [rows] of the first `traced` draws.
+ * ngp_get_genomic_variance_stats: passes this handle launched and the chains they served; in a fused ngp_run_many ONE pass per kept
+ * iteration serves every chain whose sets and windows equal the leader's (the leader counts, the others report 0).
+ * The sums are zeroed wherever sum_beta is (ngp_set_y), dropped with a new panel or a change of the sets, and are not part of
+ * snapshots, the packed posterior, sample records or ngp_allreduce_posterior: a host pools chains by adding their sums. */
+int32_t ngp_set_variance_windows(ngp_handle *h, int32_t set_id, const int64_t *start, const int64_t *stop, int64_t nwin);
+int32_t ngp_enable_genomic_variance(ngp_handle *h, int32_t on, double threshold, int64_t trace_rows);
+int32_t ngp_get_genomic_variance_layout(ngp_handle *h, int64_t *nslots, int64_t *nwin_total, int64_t *nsets, int64_t *traced, int64_t *trace_dropped);
+int32_t ngp_get_genomic_variance(ngp_handle *h, double *sumV, double *sumV2, double *sumQ, double *sumQ2, double *count, double *last, int64_t nslots,
+                                 double *ratio, int64_t *nKept);
+int32_t ngp_set_genomic_variance(ngp_handle *h, const double *sumV, const double *sumV2, const double *sumQ, const double *sumQ2, const double *count,
+                                 const double *last, int64_t nslots, const double *ratio, int64_t nKept);
+int32_t ngp_get_genomic_variance_trace(ngp_handle *h, double *V, double *ratio, int64_t rows, int64_t nslots);
+int32_t ngp_get_genomic_variance_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served);
+
 #ifdef __cplusplus
 }
 #endif

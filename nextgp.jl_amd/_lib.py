@@ -187,6 +187,8 @@ SYMBOLS = [
     "ngp_begin_prediction_panel", "ngp_prediction_columns_f64", "ngp_prediction_columns_f32", "ngp_prediction_columns_u8",
     "ngp_end_prediction_panel", "ngp_load_prediction_file", "ngp_get_prediction_layout", "ngp_get_prediction", "ngp_set_prediction",
     "ngp_get_prediction_last", "ngp_get_prediction_stats",
+    "ngp_set_variance_windows", "ngp_enable_genomic_variance", "ngp_get_genomic_variance_layout", "ngp_get_genomic_variance",
+    "ngp_set_genomic_variance", "ngp_get_genomic_variance_trace", "ngp_get_genomic_variance_stats",
 ]
 
 _lib = None
@@ -200,6 +202,28 @@ def prediction_summary(ps):
     mean = ps["sum"] / n
     sd = np.sqrt(np.maximum(0.0, ps["sum2"] / n - mean * mean))
     return dict(nKept=n, mean=mean[-1], sd=sd[-1], sets=[dict(mean=mean[s], sd=sd[s]) for s in range(mean.shape[0] - 1)])
+
+
+def genomic_variance_names(nwin_per_set):
+    """Slot names in slot order: "set<s>:win_<k>" for the windows of every set, then "set<s>", then "total"."""
+    return ([f"set{s}:win_{k + 1}" for s, n in enumerate(nwin_per_set) for k in range(n)] + [f"set{s}" for s in range(len(nwin_per_set))] + ["total"])
+
+
+def genomic_variance_summary(gs, names=None):
+    """Means, SDs and WPPA per slot of genomic-variance sums ({"sumV", "sumV2", "sumQ", "sumQ2", "count", "ratio", "nKept"}; sums of
+    several chains may have been added up): mean / SD of V and of q = V / V_g, wppa = share of the draws with q > threshold, and
+    ratio = mean and SD of V_g / (V_g + varE)."""
+    n = int(gs["nKept"])
+    if n < 1:
+        raise ValueError("no kept draw yet: the genomic-variance sums are empty")
+    mV, mQ = gs["sumV"] / n, gs["sumQ"] / n
+    out = dict(nKept=n, meanV=mV, sdV=np.sqrt(np.maximum(0.0, gs["sumV2"] / n - mV * mV)), meanQ=mQ,
+               sdQ=np.sqrt(np.maximum(0.0, gs["sumQ2"] / n - mQ * mQ)), wppa=gs["count"] / n)
+    mr = gs["ratio"][0] / n
+    out["ratio"] = (mr, float(np.sqrt(max(0.0, gs["ratio"][1] / n - mr * mr))))
+    if names is not None:
+        out["names"] = list(names)
+    return out
 
 
 class NextGPHipError(RuntimeError):
@@ -526,6 +550,71 @@ class Sampler:
         """Posterior mean and SD of the breeding values of the prediction panel's individuals: {"nKept", "mean", "sd" (all sets
         together), "sets": [{"mean", "sd"} per marker set]}, sd = sqrt(max(0, sum2 / n - mean^2))."""
         return prediction_summary(self.prediction_sums())
+
+    # ---- genomic variance of the kept draws: windows, sets, total, WPPA ------------------
+    def set_variance_windows(self, set_id, windows):
+        """Windows of marker set set_id: [(a, b), ...] half-open column ranges relative to the set's first column (ascending,
+        disjoint, non-empty, inside the set); [] drops them.  Zeroes this chain's variance sums."""
+        a = np.ascontiguousarray([w[0] for w in windows], dtype=np.int64)
+        b = np.ascontiguousarray([w[1] for w in windows], dtype=np.int64)
+        self._chk(self.L.ngp_set_variance_windows(self.h, C.c_int32(int(set_id)), _p(a, C.c_int64), _p(b, C.c_int64), C.c_int64(len(a))))
+        if not hasattr(self, "_gv_nwin"):
+            self._gv_nwin = {}
+        self._gv_nwin[int(set_id)] = len(a)
+
+    def enable_genomic_variance(self, on=True, threshold=0.01, trace_rows=0):
+        """Every kept iteration then forms var(X beta) per window, set and in all (genomic_variance()); trace_rows: draws whose V and
+        r are kept for genomic_variance_trace()."""
+        self._chk(self.L.ngp_enable_genomic_variance(self.h, C.c_int32(int(bool(on))), C.c_double(threshold), C.c_int64(int(trace_rows))))
+
+    def genomic_variance_layout(self):
+        """(nslots, windows in all, marker sets, trace rows stored, draws beyond the trace's capacity)."""
+        v = [C.c_int64() for _ in range(5)]
+        self._chk(self.L.ngp_get_genomic_variance_layout(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def genomic_variance_names(self):
+        nw = getattr(self, "_gv_nwin", {})
+        return genomic_variance_names([nw.get(s, 0) for s in range(self.nsets)])
+
+    def genomic_variance_sums(self):
+        """The sums over the kept draws per slot (windows of set 0, of set 1, ..., the sets, the total): dict(sumV, sumV2, sumQ, sumQ2,
+        count, last, ratio=[sum r, sum r^2], nKept)."""
+        n = self.genomic_variance_layout()[0]
+        a = [np.empty(n) for _ in range(6)]
+        ratio, k = np.empty(2), C.c_int64()
+        self._chk(self.L.ngp_get_genomic_variance(self.h, *[_p(x, C.c_double) for x in a], C.c_int64(n), _p(ratio, C.c_double), C.byref(k)))
+        return dict(sumV=a[0], sumV2=a[1], sumQ=a[2], sumQ2=a[3], count=a[4], last=a[5], ratio=ratio, nKept=k.value)
+
+    def set_genomic_variance_sums(self, gs):
+        a = [np.ascontiguousarray(gs[k], dtype=np.float64) for k in ("sumV", "sumV2", "sumQ", "sumQ2", "count", "last")]
+        ratio = np.ascontiguousarray(gs["ratio"], dtype=np.float64)
+        self._chk(self.L.ngp_set_genomic_variance(self.h, *[_p(x, C.c_double) for x in a], C.c_int64(len(a[0])), _p(ratio, C.c_double),
+                                                  C.c_int64(int(gs["nKept"]))))
+
+    def genomic_variance(self):
+        """Posterior means and SDs of V and q per slot, WPPA per slot, mean and SD of r, with slot names (genomic_variance_summary)."""
+        return genomic_variance_summary(self.genomic_variance_sums(), self.genomic_variance_names())
+
+    def genomic_variance_last(self):
+        """V of the last kept draw per slot."""
+        n = self.genomic_variance_layout()[0]
+        out = np.empty(n)
+        self._chk(self.L.ngp_get_genomic_variance(self.h, None, None, None, None, None, _p(out, C.c_double), C.c_int64(n), None, None))
+        return out
+
+    def genomic_variance_trace(self):
+        """(V [rows][nslots], r [rows]) of the kept draws the trace holds."""
+        n, _, _, rows, _ = self.genomic_variance_layout()
+        V, r = np.empty((rows, n)), np.empty(rows)
+        self._chk(self.L.ngp_get_genomic_variance_trace(self.h, _p(V, C.c_double), _p(r, C.c_double), C.c_int64(rows), C.c_int64(n)))
+        return V, r
+
+    def genomic_variance_stats(self):
+        """(variance passes this handle launched, chains they served)."""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(self.L.ngp_get_genomic_variance_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # ---- model -------------------------------------------------------------------------
     def add_marker_set(self, col0, ncol, method, df, scale, regions, varBeta0, pi0=0.0, estPi=False, lhs0=None, rhs0=None):

@@ -28,7 +28,7 @@ import numpy as np
 
 from ._lib import pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file"]
+__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file", "write_variance_out_files", "write_gwas_files"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -709,7 +709,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 # ----------------------------------------------------------------------------------------------
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
-            predict=None, predict_ids=None):
+            predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -739,6 +739,15 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     holds the same columns: ID mean sd mean_<set> sd_<set> ...  predict_ids names the individuals (default 1..Np).  With chains=K the
     sums are pooled over the chains and res["chains"][c]["predict"] is each chain's own.  GBLUP terms together with predict= raise
     NotImplementedError; without predict= nothing differs.
+    (9) windows={name: W | [(a, b), ...]} (or genomicVariance=True with windows={} for set and total slots only) forms the genomic
+    variance of every kept draw on the device (ngp_enable_genomic_variance; DESIGN.md section 2, "Genomic variance"): var(X beta) over the
+    training individuals per window, per marker set and in all, the share q = V / V_g of each, r = V_g / (V_g + varE), and the window
+    posterior probability of association WPPA = share of the kept draws with q > windowThreshold.  An integer W means windows of W SNPs
+    -- inside each chromosome where the SNP term has a map file (prep2RegionData), plain windows of W columns otherwise; a list holds
+    half-open 0-based column ranges of the set.  Files in the *Out format (summaryMCMC reads them): windowVar<set>Out (columns win_1 ...)
+    and genVarOut (one column per set, then total, then ratio), per chain under chain<c>/ with chains=K; gwas<set>.txt in outFolder:
+    window, first and last SNP (1-based), mean V, mean q, SD of q, WPPA.  res["variance"] holds the same, pooled over the chains
+    (res["chains"][c]["variance"]: each chain's own).  Not available for a member of a correlated (Tuple) unit or a GBLUP term.
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -788,6 +797,10 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
     snps = [t for t in snps if t.name not in gb_names]
     pmats = _prediction_sources(predict, predict_ids, snps, mats, gb_names)   # (checked before any device work)
+    gv_windows = _variance_windows(windows, windowThreshold, genomicVariance, snps, mats, gb_names, VCV)   # (the same)
+    if gv_windows is not None and w_res is not None:
+        raise NotImplementedError("genomic variance with weighted residuals (Random(d, v)): the tiles hold row-scaled values whose variance is "
+                                  "not var(X beta) (ngp_enable_genomic_variance refuses it)")
     if not snps:
         storage = None   # (storage concerns panels only: a model without marker sets has none)
     if storage in ("u8", 1):  # codes stay codes: integer-valued float input is converted, anything else refused
@@ -881,6 +894,12 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
              for sc in samplers]
     sets, fixed_names = built[0]
     randoms = samplers[0].randoms
+    if gv_windows is not None:   # behind set_y: the pass is switched on with empty sums; one trace row per kept draw
+        for sc in samplers:
+            for st in sets:
+                if gv_windows.get(st["name"]):
+                    sc.set_variance_windows(st["id"], gv_windows[st["name"]])
+            sc.enable_genomic_variance(True, float(windowThreshold), max(0, (int(nChain) - int(nBurn)) // int(nThin)))
     folders = [outFolder] if K == 1 else [os.path.join(outFolder, f"chain{chain + c}") for c in range(K)]
     for f in folders:
         os.makedirs(f, exist_ok=True)
@@ -894,7 +913,118 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         pooled = dict(sum=sum(ps["sum"] for ps in sums), sum2=sum(ps["sum2"] for ps in sums), nKept=sum(ps["nKept"] for ps in sums))
         res["predict"] = _prediction_result(pooled, ids, names)
         write_prediction_file(os.path.join(outFolder, "gebvPredict.txt"), res["predict"])
+    if gv_windows is not None:
+        by_id = sorted(sets, key=lambda st: st["id"])                       # slot order: the device's set order
+        names = [st["name"] for st in by_id]
+        wins = [gv_windows.get(nm) or [] for nm in names]
+        sums = []
+        for sc, folder in zip(samplers, folders):
+            gs = sc.genomic_variance_sums()
+            V, r = sc.genomic_variance_trace()
+            write_variance_out_files(folder, names, wins, V, r)
+            sums.append(gs)
+        for rr, gs in zip(res.get("chains", []), sums):
+            rr["variance"] = _variance_result(gs, names, wins, float(windowThreshold))
+        pooled = {k: sum(gs[k] for gs in sums) for k in ("sumV", "sumV2", "sumQ", "sumQ2", "count", "ratio", "nKept")}
+        res["variance"] = _variance_result(pooled, names, wins, float(windowThreshold))
+        write_gwas_files(outFolder, res["variance"])
     return res
+
+
+def _variance_windows(windows, threshold, genomic_variance, snps, mats, gb_names, VCV):
+    """runLMEM(windows=..., windowThreshold=..., genomicVariance=...): {set name: [(a, b), ...]} with 0-based half-open column ranges
+    of the set, or None when the pass is off.  Host checks only; a ValueError here comes before any device work."""
+    if windows is None and not genomic_variance:
+        return None
+    windows = {} if windows is None else windows
+    if not hasattr(windows, "keys"):
+        raise ValueError("windows: a mapping from the name of a SNP(...) term to a window size or a list of (start, stop) column ranges")
+    thr = float(threshold)
+    if not (0.0 <= thr <= 1.0):
+        raise ValueError(f"windowThreshold is a share of the genomic variance, in [0, 1]: got {threshold}")
+    if not snps:
+        raise ValueError("genomic variance needs at least one SNP(...) marker set")
+    ncol = {t.name: M.shape[1] for t, M in zip(snps, mats)}
+    in_tuple = {nm for key in VCV if isinstance(key, tuple) for nm in key}
+    out = {}
+    for name, spec in windows.items():
+        if name in gb_names:
+            raise ValueError(f"windows[{name!r}]: a GBLUP term has no marker effects whose variance a window could carry")
+        if name not in ncol:
+            raise ValueError(f"windows for an unknown set {name!r}: the SNP(...) marker sets are {sorted(ncol)}")
+        if name in in_tuple:
+            raise NotImplementedError(f"windows[{name!r}]: a member of a correlated (Tuple) unit shares its loci's columns with the other members")
+        P = ncol[name]
+        if isinstance(spec, (int, np.integer)) and not isinstance(spec, bool):
+            W = int(spec)
+            if W < 1:
+                raise ValueError(f"windows[{name!r}]: a window size of at least one SNP, got {W}")
+            t = [t for t in snps if t.name == name][0]
+            if t.map:   # windows inside each chromosome, as the variance regions of BayesPR are cut (src/misc.jl:163-215)
+                w = prep2RegionData(None, name, t.map, W)
+                if not w or w[-1][1] != P:
+                    raise ValueError(f"windows[{name!r}]: the map file {t.map} lists {w[-1][1] if w else 0} SNPs, the set holds {P}")
+            else:
+                w = [(a, min(a + W, P)) for a in range(0, P, W)]
+        else:
+            try:
+                w = [(int(a), int(b)) for a, b in spec]
+            except (TypeError, ValueError):
+                raise ValueError(f"windows[{name!r}]: a window size or a list of (start, stop) column ranges") from None
+            at = 0
+            for k, (a, b) in enumerate(w):
+                if a < at or b <= a or b > P:
+                    raise ValueError(f"windows[{name!r}] must be ascending, disjoint, non-empty and inside the set's {P} columns (window {k}: {(a, b)})")
+                at = b
+        out[name] = w
+    return out
+
+
+def _variance_result(gs, names, wins, threshold):
+    """res["variance"] from genomic-variance sums (one chain's, or several chains' added up)."""
+    from ._lib import genomic_variance_summary
+    sm = genomic_variance_summary(gs)
+    nw = sum(len(w) for w in wins)
+    out = dict(nKept=sm["nKept"], threshold=threshold, ratio=dict(mean=sm["ratio"][0], sd=sm["ratio"][1]),
+               total=dict(meanV=float(sm["meanV"][-1]), sdV=float(sm["sdV"][-1])), sets={})
+    o = 0
+    for k, (nm, w) in enumerate(zip(names, wins)):
+        sl = slice(o, o + len(w))
+        out["sets"][nm] = dict(meanV=float(sm["meanV"][nw + k]), sdV=float(sm["sdV"][nw + k]), meanQ=float(sm["meanQ"][nw + k]), sdQ=float(sm["sdQ"][nw + k]),
+                               windows=dict(first=np.array([a + 1 for a, _ in w], dtype=np.int64), last=np.array([b for _, b in w], dtype=np.int64),
+                                            meanV=sm["meanV"][sl], sdV=sm["sdV"][sl], meanQ=sm["meanQ"][sl], sdQ=sm["sdQ"][sl], wppa=sm["wppa"][sl]))
+        o += len(w)
+    return out
+
+
+def write_variance_out_files(folder, names, wins, V, r):
+    """The per-draw trace in the reference's *Out format (a header row, then one tab-separated row per kept draw): windowVar<set>Out with
+    the columns win_1 ... for every set that has windows, and genVarOut with one column per set, then total, then ratio."""
+    nw = sum(len(w) for w in wins)
+    o = 0
+    for nm, w in zip(names, wins):
+        if w:
+            with open(os.path.join(folder, f"windowVar{nm}Out"), "w") as f:
+                f.write("\t".join(f"win_{k + 1}" for k in range(len(w))) + "\n")
+                for row in V:
+                    f.write("\t".join(_fmt(row[o:o + len(w)])) + "\n")
+        o += len(w)
+    with open(os.path.join(folder, "genVarOut"), "w") as f:
+        f.write("\t".join(list(names) + ["total", "ratio"]) + "\n")
+        for row, rr in zip(V, r):
+            f.write("\t".join(_fmt(row[nw:]) + _fmt(rr)) + "\n")
+
+
+def write_gwas_files(folder, variance):
+    """gwas<set>.txt for every set with windows: window, first and last SNP (1-based, inside the set), mean V, mean q, SD of q, WPPA."""
+    for nm, st in variance["sets"].items():
+        w = st["windows"]
+        if len(w["first"]) == 0:
+            continue
+        with open(os.path.join(folder, f"gwas{nm}.txt"), "w") as f:
+            f.write("window\tfirstSNP\tlastSNP\tmeanV\tmeanQ\tsdQ\tWPPA\n")
+            for k in range(len(w["first"])):
+                f.write("\t".join([str(k + 1), str(int(w["first"][k])), str(int(w["last"][k]))] + _fmt([w["meanV"][k], w["meanQ"][k], w["sdQ"][k], w["wppa"][k]])) + "\n")
 
 
 def _panel_pieces(snps, mats, by_name, in_tuple):

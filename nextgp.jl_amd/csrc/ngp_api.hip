@@ -33,6 +33,7 @@
 #include "ngp_dense.h"
 #include "ngp_logvar.h"
 #include "ngp_predict.h"
+#include "ngp_genvar.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
 
@@ -426,8 +427,30 @@ int plan_sweep(int64_t N, int cu_count, const PlanRequest &q, SweepPlan *out, co
     return NGP_OK;
 }
 
+// Genomic variance of the kept draws (ngp_genvar.h; DESIGN.md section 2, "Genomic variance"): the caller's windows per marker set, the
+// segments / items / slots built from them for the sets the chain has now, and the chain's partials, sums and trace on the device
+struct GenVar {
+    bool on = false;
+    double thr = 0.01;
+    int64_t trace_rows = 0;
+    std::vector<std::vector<int64_t>> win;  // per marker set: start, stop of every window, relative to the set's first column
+    bool built = false;
+    std::vector<int64_t> built_for;         // col0, ncol of every set the tables below were built for
+    std::vector<GvSeg> segs;
+    std::vector<GvItem> items;
+    int64_t nwin = 0, nslots = 0, ncol_w = 0, nblk_r = 0;
+    int ex = 0;                             // 2^ex > max |x_ij| over the live rows of the panel (k_genvar_xmax, when the tables are built)
+    DevArray<GvSeg> d_segs;
+    DevArray<GvItem> d_items;
+    DevArray<int> d_set_item0, d_set_seg0, d_slot_seg, d_slot_e;
+    DevArray<double> d_part, d_segm, d_sega, d_acc, d_trace;  // d_acc: [6][nslots] | sum r | sum r^2
+    DevArray<long long> d_qw, d_qs, d_cnt;
+    int64_t launches = 0, served = 0;       // ngp_get_genomic_variance_stats
+};
+
 // The chain's arrays on one panel (sized by its N, P and plan): allocated whole by alloc_panel, dropped whole with the panel
 struct ChainMem {
+    GenVar gv;
     DevArray<double> d_lhs0, d_rhs0, d_beta, d_c, d_w, d_q, d_T, d_chi;
     DevArray<int8_t> d_setof;
     DevArray<int32_t> d_loc, d_vbidx;
@@ -1116,7 +1139,7 @@ std::string census_report(ngp_handle *h) {
 // says which iteration; the abort words are cleared, the caller runs it again with the device to itself) or an error (poisoned)
 #define NGP_RETRY_CENSUS 1
 int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
-    if (h->plan.mode != 1) return NGP_OK;
+    if (h->plan.mode != 1 && !h->cm.gv.on) return NGP_OK;  // (the per-block engine raises no abort word; the variance pass may)
     unsigned w[2] = {0, 0};
     HCHK(hipMemcpy(w, h->cm.d_abort, sizeof(w), hipMemcpyDeviceToHost));
     if (w[0] == 0) return NGP_OK;
@@ -1133,6 +1156,10 @@ int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
     if (w[0] == NGP_ABORT_CENSUS)
         return fail(h, NGP_ERR_HIP, "persistent sweep: the grid did not become resident although this call had leased the whole device (" +
                                         census_report(h) + "): another process holding CUs?  The chain state is invalid until ngp_set_y / ngp_set_state");
+    if (w[0] == NGP_ABORT_GENVAR)
+        return fail(h, NGP_ERR_HIP, "genomic variance: a term left the fixed-point range of its sum (non-finite effects?); the pass and every kernel "
+                                    "behind it that reads the abort word returned at once: the variance sums and the chain state are invalid until "
+                                    "ngp_set_y / ngp_set_state");
     if (w[0] == 7u)  // NGP_ABORT_FX
         return fail(h, NGP_ERR_HIP, "persistent sweep: a partial dot product left the fixed-point range of its accumulator (non-finite residual or effects, "
                                     "or the residual grew more than 32-fold within one sweep); the chain state is invalid until ngp_set_y / ngp_set_state");
@@ -1395,6 +1422,133 @@ void launch_predict(ngp_handle *lead, ngp_handle **hs, int n) {
     lead->cm.pred_served += n;
 }
 
+/* ---- genomic variance: var_i (X beta)_i of every kept draw per window, set and in all (ngp_genvar.h) ---- */
+
+// does a kept iteration of this chain run the variance pass?
+bool gv_active(const ngp_handle *h) { return h->pm && !h->records_only && h->cm.gv.on && h->cm.gv.built; }
+
+// Segments, items and slots of the chain's sets and windows ("Genomic variance", steps 1 and 4), the device
+// arrays sized for them; everything the chain has accumulated is dropped (the arrays come back zeroed).
+int build_genvar(ngp_handle *h) {
+    GenVar &g = h->cm.gv;
+    g.built = false;
+    g.segs.clear(); g.items.clear(); g.built_for.clear();
+    const size_t nsets = h->sets.size();
+    g.win.resize(nsets);
+    std::vector<int> set_item0(1, 0), set_seg0(1, 0), slot_seg;
+    for (size_t s = 0; s < nsets; s++) {
+        const HSet &st = h->sets[s];
+        g.built_for.push_back(st.col0); g.built_for.push_back(st.ncol);
+        const std::vector<int64_t> &w = g.win[s];
+        auto gap = [&](int64_t a, int64_t b) {  // columns [a, b) of the set outside every window, in pieces of NGP_GV_ITEM_COLS
+            for (int64_t j = a; j < b; j += NGP_GV_ITEM_COLS)
+                g.segs.push_back(GvSeg{(long long)(st.col0 + j), (long long)(st.col0 + std::min<int64_t>(j + NGP_GV_ITEM_COLS, b)), -1, 0});
+        };
+        int64_t at = 0;
+        for (size_t k = 0; k + 1 < w.size(); k += 2) {
+            gap(at, w[k]);
+            slot_seg.push_back((int)g.segs.size());
+            g.segs.push_back(GvSeg{(long long)(st.col0 + w[k]), (long long)(st.col0 + w[k + 1]), (int)slot_seg.size() - 1, 0});
+            at = w[k + 1];
+        }
+        gap(at, st.ncol);
+        // items: whole segments, in order, while they fit into NGP_GV_ITEM_COLS columns; a longer window stands alone
+        for (int e = set_seg0.back(); e < (int)g.segs.size();) {
+            int f = e + 1;
+            while (f < (int)g.segs.size() && g.segs[(size_t)f].j1 - g.segs[(size_t)e].j0 <= NGP_GV_ITEM_COLS) f++;
+            g.items.push_back(GvItem{(int)s, e, f, 0, g.segs[(size_t)e].j0, g.segs[(size_t)f - 1].j1});
+            e = f;
+        }
+        set_seg0.push_back((int)g.segs.size());
+        set_item0.push_back((int)g.items.size());
+    }
+    g.nwin = (int64_t)slot_seg.size();
+    g.nslots = g.nwin + (int64_t)nsets + 1;
+    g.ncol_w = (h->L + NGP_GV_ROWS - 1) / NGP_GV_ROWS;  // workgroup columns: 256 rows of the padded row space each
+    g.nblk_r = (h->N + 255) / 256;
+    const size_t nseg = g.segs.size(), ni = g.items.size(), n = (size_t)g.nslots;
+    int rc;
+    if ((rc = g.d_segs.alloc(h, nseg)) || (rc = g.d_items.alloc(h, ni)) || (rc = g.d_set_item0.alloc(h, set_item0.size())) ||
+        (rc = g.d_set_seg0.alloc(h, set_seg0.size())) || (rc = g.d_slot_seg.alloc(h, slot_seg.size())) || (rc = g.d_slot_e.alloc(h, n)) ||
+        (rc = g.d_part.alloc(h, ni * (size_t)h->L)) || (rc = g.d_segm.alloc(h, nseg)) || (rc = g.d_sega.alloc(h, nseg)) ||
+        (rc = g.d_acc.alloc(h, 6 * n + 2)) || (rc = g.d_trace.alloc(h, (size_t)g.trace_rows * (n + 1))) ||
+        (rc = g.d_qw.alloc(h, (size_t)g.ncol_w * (size_t)g.nwin * 2)) || (rc = g.d_qs.alloc(h, (size_t)g.nblk_r * (nsets + 1) * 2)) ||
+        (rc = g.d_cnt.alloc(h, 2)))
+        return rc;
+    HCHK(hipMemcpyAsync(g.d_segs, g.segs.data(), nseg * sizeof(GvSeg), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(g.d_items, g.items.data(), ni * sizeof(GvItem), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(g.d_set_item0, set_item0.data(), set_item0.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(g.d_set_seg0, set_seg0.data(), set_seg0.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (!slot_seg.empty()) HCHK(hipMemcpyAsync(g.d_slot_seg, slot_seg.data(), slot_seg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    {   // the range of the stored values: one pass over the panel, an integer maximum (d_cnt[1] is free until the first pass)
+        unsigned long long bits = 0ull;
+        HCHK(genvar_xmax((const void *)h->pm->tiles.get(), (const double *)h->pm->mean.get(), h->req.storage == 1, (long long)h->N, (long long)h->L,
+                         (long long)h->NBLK, (unsigned long long *)(g.d_cnt.get() + 1), h->stream));
+        HCHK(hipMemcpyAsync(&bits, g.d_cnt.get() + 1, sizeof bits, hipMemcpyDeviceToHost, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));  // (the tables are locals)
+        HCHK(hipMemsetAsync(g.d_cnt.get() + 1, 0, sizeof(long long), h->stream));
+        double xmax;
+        std::memcpy(&xmax, &bits, sizeof xmax);
+        g.ex = gv_xexp(xmax);
+    }
+    g.built = true;
+    return NGP_OK;
+}
+
+// The chain's variance arrays for the sets and windows it has now: built (zeroed) when either changed, zeroed again on request
+// (ngp_set_y).  Nothing to do while the pass is off.
+int ensure_genvar(ngp_handle *h, bool zero) {
+    GenVar &g = h->cm.gv;
+    if (!g.on || !h->pm || h->records_only || h->sets.empty()) { g.built = false; return NGP_OK; }
+    bool same = g.built && g.built_for.size() == 2 * h->sets.size();
+    for (size_t s = 0; same && s < h->sets.size(); s++) same = g.built_for[2 * s] == h->sets[s].col0 && g.built_for[2 * s + 1] == h->sets[s].ncol;
+    if (!same) return build_genvar(h);
+    if (zero) {
+        HCHK(hipMemsetAsync(g.d_acc, 0, (size_t)(6 * g.nslots + 2) * sizeof(double), h->stream));
+        HCHK(hipMemsetAsync(g.d_cnt, 0, 2 * sizeof(long long), h->stream));
+        if (g.trace_rows > 0) HCHK(hipMemsetAsync(g.d_trace, 0, (size_t)g.trace_rows * (size_t)(g.nslots + 1) * sizeof(double), h->stream));
+    }
+    return NGP_OK;
+}
+
+// the same panel, sets and windows: one pass serves both chains
+bool same_genvar(const ngp_handle *a, const ngp_handle *b) {
+    const GenVar &x = a->cm.gv, &y = b->cm.gv;
+    if (a->pm != b->pm || x.built_for != y.built_for || x.segs.size() != y.segs.size()) return false;
+    for (size_t i = 0; i < x.segs.size(); i++)
+        if (x.segs[i].j0 != y.segs[i].j0 || x.segs[i].j1 != y.segs[i].j1 || x.segs[i].slot != y.segs[i].slot) return false;
+    return true;
+}
+
+// ONE pass over the training panel for the n chains hs (their sets and windows equal hs[0]'s), on lead's stream: segment scalars and
+// scales, the tile pass, the rows' set values, then every chain's V, q, r and sums.  Threshold and trace capacity are each chain's own.
+int launch_genvar(ngp_handle *lead, ngp_handle **hs, int n) {
+    ngp_handle *h = lead;
+    const GenVar &g0 = hs[0]->cm.gv;
+    GvLaunch q;
+    std::memset(&q, 0, sizeof q);
+    for (int i = 0; i < n; i++) {
+        ChainMem &c = hs[i]->cm;
+        GenVar &g = c.gv;
+        q.A.c[i] = GvChain{(const double *)c.d_beta.get(), (const DScal *)c.d_scal.get(), g.d_part.get(), g.d_segm.get(), g.d_sega.get(), g.d_slot_e.get(),
+                           g.d_qw.get(), g.d_qs.get(), g.d_acc.get(), g.d_acc.get() + 6 * g.nslots, g.d_trace.get(), g.d_cnt.get()};
+        q.thr[i] = g.thr; q.trace_rows[i] = (long long)g.trace_rows;
+    }
+    q.n = n; q.u8 = lead->req.storage == 1;
+    q.tiles = (const void *)lead->pm->tiles.get(); q.mean = (const double *)lead->pm->mean.get();
+    q.segs = g0.d_segs.get(); q.items = g0.d_items.get();
+    q.slot_seg = g0.d_slot_seg.get(); q.set_seg0 = g0.d_set_seg0.get(); q.set_item0 = g0.d_set_item0.get();
+    q.nseg = (int)g0.segs.size(); q.nitems = (int)g0.items.size(); q.nsets = (int)hs[0]->sets.size(); q.nwin = (int)g0.nwin; q.nslots = (int)g0.nslots;
+    q.ex = g0.ex; q.ncol_w = (int)g0.ncol_w; q.nblk_r = (int)g0.nblk_r;
+    q.N = (long long)lead->N; q.L = (long long)lead->L;
+    q.abort_w = lead->cm.d_abort; q.stream = lead->stream;
+    const hipError_t e = genvar_launch(q);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("genomic variance pass: ") + hipGetErrorString(e));
+    lead->cm.gv.launches += 1;
+    lead->cm.gv.served += n;
+    return NGP_OK;
+}
+
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
@@ -1417,7 +1571,8 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
 }
 
 // predict: this chain launches its own prediction pass in a kept iteration (false: the caller serves several chains with one launch)
-int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true) {  // variance / pi draws, traces and posterior sums; advances h->iter
+// genvar: the same for the genomic-variance pass
+int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true, bool genvar = true) {  // variance / pi draws, traces and posterior sums; advances h->iter
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!h->records_only) launch_variance(h, -1, it);
     h->iter += 1;
@@ -1446,6 +1601,8 @@ int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true) {  // 
             hipLaunchKernelGGL(k_rc_accum, dim3((unsigned)((Rc.n + 255) / 256)), dim3(256), 0, h->stream, (const DSet *)h->cm.d_sets, Rc.set, Rc.dev(),
                                (const unsigned *)h->cm.d_abort);
         if (predict && predicts(h)) launch_predict(h, &h, 1);  // g = X_new beta of this draw, behind the posterior sums
+        if (genvar && gv_active(h))                            // var(X beta) of this draw per window, set and in all
+            if (int e = launch_genvar(h, &h, 1)) return e;
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
     return NGP_OK;
@@ -1481,6 +1638,9 @@ int run_iterations(ngp_handle *h, int64_t niter, CuLease &lease, hipEvent_t *evs
                 if (predicts(h))  // the prediction passes behind the failing launch returned at once: they are launched again
                     for (int64_t r = itf; r <= h->iter; r++)
                         if (is_kept(h, r)) { h->cm.pred_launches -= 1; h->cm.pred_served -= 1; }
+                if (gv_active(h))  // ... and so are the variance passes
+                    for (int64_t r = itf; r <= h->iter; r++)
+                        if (is_kept(h, r)) { h->cm.gv.launches -= 1; h->cm.gv.served -= 1; }
                 h->iter = itf - 1;
                 n = h->iter - iter0;
                 resume_mid = true;
@@ -2398,6 +2558,7 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     HCHK(hipMemsetAsync(h->cm.d_sum_beta2, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     HCHK(hipMemsetAsync(h->cm.d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     if ((rc = ensure_prediction(h, true))) return rc;  // the prediction sums are zeroed wherever sum_beta is
+    if ((rc = ensure_genvar(h, true))) return rc;      // ... and the genomic-variance sums
     // a second chain on the same handle starts from the priors, with empty posterior sums (src/mme.jl:351-360, 516)
     if (h->nvb > 0) HCHK(hipMemsetAsync(h->mm.d_sum_varBeta, 0, (size_t)h->nvb * sizeof(double), h->stream));
     for (size_t si = 0; si < h->sets.size(); si++)
@@ -2512,6 +2673,7 @@ int prepare_run(ngp_handle *h, int64_t niter) {
         h->hm.trace_cap = niter;
     }
     h->ntrace = niter;
+    if ((rc = ensure_genvar(h, false))) return rc;
     return ensure_prediction(h, false);
 }
 
@@ -2595,6 +2757,9 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     // columns as the leader's; a chain with another layout launches its own
     std::vector<char> pred_with_leader((size_t)n, 0);
     for (int i = 0; i < n; i++) pred_with_leader[(size_t)i] = predicts(hs[i]) && same_pred_items(h, hs[i]);
+    // genomic variance: the same -- one pass per kept iteration for every chain whose sets AND windows equal the leader's
+    std::vector<char> gv_with_leader((size_t)n, 0);
+    for (int i = 0; i < n; i++) gv_with_leader[(size_t)i] = gv_active(h) && gv_active(hs[i]) && same_genvar(h, hs[i]);
     CuLease lease(h, grid);
     e = hipEventRecord(h->ev0, h->stream);
     rc = NGP_OK;
@@ -2614,7 +2779,7 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
         h->sweep_launches += 1; h->last_grid = grid;
         (void)hipEventRecord(ev.evs, h->stream);
         for (int i = 1; i < n; i++) (void)hipStreamWaitEvent(hs[i]->stream, ev.evs, 0);
-        for (int i = 0; i < n && rc == NGP_OK; i++) { rc = iteration_post(hs[i], it, !pred_with_leader[(size_t)i]); if (rc && i) h->err = hs[i]->err; }
+        for (int i = 0; i < n && rc == NGP_OK; i++) { rc = iteration_post(hs[i], it, !pred_with_leader[(size_t)i], !gv_with_leader[(size_t)i]); if (rc && i) h->err = hs[i]->err; }
         if (rc) break;
         {   // the chains kept in this iteration, served together on the leader's stream (their effects are final: the sweep ran there)
             ngp_handle *served[NGP_PRED_MAXK];
@@ -2622,6 +2787,15 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
             for (int i = 0; i < n; i++)
                 if (pred_with_leader[(size_t)i] && is_kept(hs[i], hs[i]->iter)) served[ns++] = hs[i];
             if (ns > 0) launch_predict(h, served, ns);
+            ns = 0;
+            for (int i = 0; i < n; i++)
+                if (gv_with_leader[(size_t)i] && is_kept(hs[i], hs[i]->iter)) served[ns++] = hs[i];
+            if (ns > 0) {  // the pass reads each chain's effects and varE: the chain's next iteration waits for it
+                rc = launch_genvar(h, served, ns);
+                (void)hipEventRecord(ev.evs, h->stream);
+                for (int i = 0; i < ns; i++)
+                    if (served[i] != h) (void)hipStreamWaitEvent(served[i]->stream, ev.evs, 0);
+            }
         }
         if ((it & 15) == 15 || it + 1 == niter) {  // bound the launch queue
             e = sync_all();
@@ -5179,6 +5353,150 @@ int32_t ngp_get_prediction_stats(ngp_handle *h, int64_t *launches, int64_t *chai
     if ((rc = enter(h))) return rc;
     if (launches) *launches = h->cm.pred_launches;
     if (chains_served) *chains_served = h->cm.pred_served;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ---- genomic variance (ngp_genvar.h; DESIGN.md section 2, "Genomic variance") ---- */
+
+int32_t ngp_set_variance_windows(ngp_handle *h, int32_t set_id, const int64_t *start, const int64_t *stop, int64_t nwin) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm && !h->panel_open && !h->records_only, NGP_ERR_STATE, "variance windows need a finished panel and a marker set");
+    REQUIRE(set_id >= 0 && (size_t)set_id < h->sets.size(), NGP_ERR_ARG, "variance windows: no marker set " + std::to_string(set_id));
+    REQUIRE(nwin >= 0 && (nwin == 0 || (start && stop)), NGP_ERR_ARG, "variance windows: null arrays");
+    const int64_t ncol = h->sets[(size_t)set_id].ncol;
+    std::vector<int64_t> w;
+    int64_t at = 0;
+    for (int64_t k = 0; k < nwin; k++) {
+        REQUIRE(start[k] >= at && stop[k] > start[k] && stop[k] <= ncol, NGP_ERR_ARG,
+                "variance windows must be ascending, disjoint, non-empty and inside the set's " + std::to_string(ncol) + " columns (window " + std::to_string(k) + ")");
+        w.push_back(start[k]); w.push_back(stop[k]);
+        at = stop[k];
+    }
+    GenVar &g = h->cm.gv;
+    g.win.resize(h->sets.size());
+    g.win[(size_t)set_id] = std::move(w);
+    g.built = false;  // (the sums go with the tables)
+    return ensure_genvar(h, false);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_enable_genomic_variance(ngp_handle *h, int32_t on, double threshold, int64_t trace_rows) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    GenVar &g = h->cm.gv;
+    if (!on) { g.on = false; g.built = false; return NGP_OK; }
+    REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "genomic variance needs a finished training panel (ngp_set_panel_* / ngp_end_panel)");
+    REQUIRE(!h->records_only, NGP_ERR_STATE, "a records-only (GBLUP) handle has no marker panel whose variance could be formed");
+    REQUIRE(h->h_rw.empty(), NGP_ERR_STATE, "genomic variance with residual weights is not supported: the tiles hold row-scaled values whose variance is not var(X beta)");
+    REQUIRE(h->N >= 2, NGP_ERR_STATE, "genomic variance needs at least two individuals");
+    REQUIRE(h->N <= NGP_GV_MAXN, NGP_ERR_STATE, "genomic variance: more than 2^18 individuals would leave the head-room of the 64-bit fixed-point sums");
+    REQUIRE(threshold >= 0.0 && threshold <= 1.0, NGP_ERR_ARG, "genomic variance: the threshold is a share of the variance, in [0, 1]");
+    REQUIRE(trace_rows >= 0 && trace_rows <= ((int64_t)1 << 32), NGP_ERR_ARG, "genomic variance: trace_rows must be >= 0");
+    REQUIRE(genvar_lds_bytes(NGP_GV_MAXK, h->req.storage == 1) <= NGP_LDS_MAX, NGP_ERR_STATE, "genomic variance: LDS of the pass exceeds 160 KiB");
+    HCHK(genvar_prepare());
+    g.on = true; g.thr = threshold; g.trace_rows = trace_rows;
+    g.built = false;
+    return ensure_genvar(h, false);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_genomic_variance_layout(ngp_handle *h, int64_t *nslots, int64_t *nwin_total, int64_t *nsets, int64_t *traced, int64_t *trace_dropped) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if ((rc = ensure_genvar(h, false))) return rc;
+    REQUIRE(gv_active(h), NGP_ERR_STATE, "no genomic variance: ngp_enable_genomic_variance and at least one marker set are needed");
+    const GenVar &g = h->cm.gv;
+    long long cnt[2] = {0, 0};
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(cnt, g.d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+    if (nslots) *nslots = g.nslots;
+    if (nwin_total) *nwin_total = g.nwin;
+    if (nsets) *nsets = (int64_t)h->sets.size();
+    if (traced) *traced = std::min<int64_t>(cnt[0], g.trace_rows);
+    if (trace_dropped) *trace_dropped = cnt[0] - std::min<int64_t>(cnt[0], g.trace_rows);
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_genomic_variance(ngp_handle *h, double *sumV, double *sumV2, double *sumQ, double *sumQ2, double *count, double *last, int64_t nslots,
+                                 double *ratio, int64_t *nKept) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if ((rc = ensure_genvar(h, false))) return rc;
+    REQUIRE(gv_active(h), NGP_ERR_STATE, "no genomic variance: ngp_enable_genomic_variance and at least one marker set are needed");
+    const GenVar &g = h->cm.gv;
+    REQUIRE(nslots == g.nslots, NGP_ERR_ARG, "genomic variance arrays hold nslots = " + std::to_string(g.nslots) + " entries");
+    HCHK(hipStreamSynchronize(h->stream));
+    double *out[6] = {sumV, sumV2, sumQ, sumQ2, count, last};
+    for (int a = 0; a < 6; a++)
+        if (out[a]) HCHK(hipMemcpy(out[a], g.d_acc.get() + (size_t)a * g.nslots, (size_t)g.nslots * sizeof(double), hipMemcpyDeviceToHost));
+    if (ratio) HCHK(hipMemcpy(ratio, g.d_acc.get() + (size_t)6 * g.nslots, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (nKept) {
+        long long cnt[2] = {0, 0};
+        HCHK(hipMemcpy(cnt, g.d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+        *nKept = (int64_t)cnt[0];
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_genomic_variance(ngp_handle *h, const double *sumV, const double *sumV2, const double *sumQ, const double *sumQ2, const double *count,
+                                 const double *last, int64_t nslots, const double *ratio, int64_t nKept) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if ((rc = ensure_genvar(h, false))) return rc;
+    REQUIRE(gv_active(h), NGP_ERR_STATE, "no genomic variance: ngp_enable_genomic_variance and at least one marker set are needed");
+    GenVar &g = h->cm.gv;
+    REQUIRE(nslots == g.nslots, NGP_ERR_ARG, "genomic variance arrays hold nslots = " + std::to_string(g.nslots) + " entries");
+    REQUIRE(nKept >= 0, NGP_ERR_ARG, "genomic variance: nKept must be >= 0");
+    HCHK(hipStreamSynchronize(h->stream));
+    const double *in[6] = {sumV, sumV2, sumQ, sumQ2, count, last};
+    for (int a = 0; a < 6; a++)
+        if (in[a]) HCHK(hipMemcpy(g.d_acc.get() + (size_t)a * g.nslots, in[a], (size_t)g.nslots * sizeof(double), hipMemcpyHostToDevice));
+    if (ratio) HCHK(hipMemcpy(g.d_acc.get() + (size_t)6 * g.nslots, ratio, 2 * sizeof(double), hipMemcpyHostToDevice));
+    const long long cnt[2] = {(long long)nKept, (long long)nKept};
+    HCHK(hipMemcpy(g.d_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_genomic_variance_trace(ngp_handle *h, double *V, double *ratio, int64_t rows, int64_t nslots) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if ((rc = ensure_genvar(h, false))) return rc;
+    REQUIRE(gv_active(h), NGP_ERR_STATE, "no genomic variance: ngp_enable_genomic_variance and at least one marker set are needed");
+    const GenVar &g = h->cm.gv;
+    REQUIRE(nslots == g.nslots, NGP_ERR_ARG, "genomic variance arrays hold nslots = " + std::to_string(g.nslots) + " entries");
+    long long cnt[2] = {0, 0};
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(cnt, g.d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+    REQUIRE(rows >= 0 && rows <= std::min<int64_t>(cnt[0], g.trace_rows), NGP_ERR_ARG,
+            "genomic variance trace: " + std::to_string(std::min<int64_t>(cnt[0], g.trace_rows)) + " rows are stored");
+    if (rows == 0) return NGP_OK;
+    std::vector<double> t((size_t)rows * (size_t)(nslots + 1));
+    HCHK(hipMemcpy(t.data(), g.d_trace, t.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < rows; r++) {
+        if (V) std::memcpy(V + (size_t)r * nslots, t.data() + (size_t)r * (nslots + 1), (size_t)nslots * sizeof(double));
+        if (ratio) ratio[r] = t[(size_t)r * (nslots + 1) + nslots];
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_genomic_variance_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if (launches) *launches = h->cm.gv.launches;
+    if (chains_served) *chains_served = h->cm.gv.served;
     return NGP_OK;
     NGP_CATCH(h)
 }

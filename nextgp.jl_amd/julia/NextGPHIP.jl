@@ -166,6 +166,93 @@ function prediction_stats(h::Handle)     # launches of the prediction pass this 
     return (launches = Int(a[]), chains_served = Int(b[]))
 end
 
+# ---- genomic variance of every kept draw (include/nextgp_hip.h, "genomic variance") ----
+# windows::Vector{UnitRange{Int}} (1-based columns of the set) -> 0-based [start, stop)
+function set_variance_windows!(h::Handle, set_id::Integer, windows)
+    ws = Int64[first(w) - 1 for w in windows]
+    we = Int64[last(w) for w in windows]
+    check(h, ccall((:ngp_set_variance_windows, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Int64), h.ptr, set_id, ws, we, length(ws)))
+end
+enable_genomic_variance!(h::Handle; on::Bool=true, threshold::Float64=0.01, trace_rows::Integer=0) =
+    check(h, ccall((:ngp_enable_genomic_variance, LIB), Int32, (Ptr{Cvoid}, Int32, Float64, Int64), h.ptr, on, threshold, trace_rows))
+function genomic_variance_layout(h::Handle)   # slots, windows in all, marker sets, trace rows stored, draws beyond the trace's capacity
+    n = Ref{Int64}(0); w = Ref{Int64}(0); s = Ref{Int64}(0); t = Ref{Int64}(0); d = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_genomic_variance_layout, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                   h.ptr, n, w, s, t, d))
+    return (nslots = Int(n[]), nwin = Int(w[]), nsets = Int(s[]), traced = Int(t[]), dropped = Int(d[]))
+end
+
+"""
+    getGenomicVariance(h)
+
+Sums over the kept draws per slot (the windows of set 1, of set 2, ..., then one slot per set, then the total): `sumV`, `sumV2`, `sumQ`,
+`sumQ2` (q = V / V_g), `count` of q > threshold, `last` (V of the last draw), `ratio = [sum r, sum r^2]` with r = V_g / (V_g + varE), and
+`nKept`; with them `meanV`, `meanQ`, `sdQ` and `wppa = count / nKept`.  `setGenomicVariance_sums!` restores them on a resumed chain.
+"""
+function getGenomicVariance(h::Handle)
+    n = genomic_variance_layout(h).nslots
+    a = [Vector{Float64}(undef, n) for _ in 1:6]; ratio = Vector{Float64}(undef, 2); k = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_genomic_variance, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ref{Int64}),
+                   h.ptr, a[1], a[2], a[3], a[4], a[5], a[6], n, ratio, k))
+    nk = max(Int(k[]), 1)
+    mq = a[3] ./ nk
+    return (nKept = Int(k[]), sumV = a[1], sumV2 = a[2], sumQ = a[3], sumQ2 = a[4], count = a[5], last = a[6], ratio = ratio,
+            meanV = a[1] ./ nk, meanQ = mq, sdQ = sqrt.(max.(0.0, a[4] ./ nk .- mq .* mq)), wppa = a[5] ./ nk)
+end
+setGenomicVariance_sums!(h::Handle, sumV::Vector{Float64}, sumV2::Vector{Float64}, sumQ::Vector{Float64}, sumQ2::Vector{Float64},
+                         count::Vector{Float64}, last::Vector{Float64}, ratio::Vector{Float64}, nKept::Integer) =
+    check(h, ccall((:ngp_set_genomic_variance, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+                   h.ptr, sumV, sumV2, sumQ, sumQ2, count, last, length(sumV), ratio, nKept))
+function genomic_variance_trace(h::Handle)    # V (nslots x rows as Julia sees the library's [rows][nslots]) and r of the traced draws
+    lay = genomic_variance_layout(h)
+    V = Matrix{Float64}(undef, lay.nslots, lay.traced); r = Vector{Float64}(undef, lay.traced)
+    check(h, ccall((:ngp_get_genomic_variance_trace, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64), h.ptr, V, r, lay.traced, lay.nslots))
+    return (V = V, ratio = r)
+end
+function genomic_variance_stats(h::Handle)    # variance passes this handle launched, chains they served
+    a = Ref{Int64}(0); b = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_genomic_variance_stats, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), h.ptr, a, b))
+    return (launches = Int(a[]), chains_served = Int(b[]))
+end
+
+"""
+    write_genomic_variance(h, outPut, sets, ids, wins)
+
+The files of `runSampler!(...; windows = ...)`, in the reference's *Out format: `windowVar<set>Out` (header win_1 ..., one row per kept
+draw) for every set with windows, `genVarOut` (one column per set, then total, then ratio), and `gwas<set>.txt` (window, first and last
+SNP, mean V, mean q, SD of q, WPPA).  `sets` in the order they were added, `ids[s]` the library's set id, `wins[s]` 1-based ranges.
+"""
+function write_genomic_variance(h::Handle, outPut, sets, ids, wins)
+    gv = getGenomicVariance(h)
+    tr = genomic_variance_trace(h)
+    ord = sort(collect(sets), by = s -> ids[s])          # slot order: the library's set order
+    nw = [length(get(wins, s, UnitRange{Int}[])) for s in ord]
+    nwin = sum(nw)
+    o = 0
+    for (k, s) in enumerate(ord)
+        if nw[k] > 0
+            open(outPut * "/windowVar$(s)Out", "w") do io
+                writedlm(io, permutedims(["win_$(i)" for i in 1:nw[k]]))
+                writedlm(io, permutedims(tr.V[o+1:o+nw[k], :]))
+            end
+            open(outPut * "/gwas$(s).txt", "w") do io
+                writedlm(io, ["window" "firstSNP" "lastSNP" "meanV" "meanQ" "sdQ" "WPPA"])
+                for i in 1:nw[k]
+                    writedlm(io, Any[i first(wins[s][i]) last(wins[s][i]) gv.meanV[o+i] gv.meanQ[o+i] gv.sdQ[o+i] gv.wppa[o+i]])
+                end
+            end
+        end
+        o += nw[k]
+    end
+    open(outPut * "/genVarOut", "w") do io
+        writedlm(io, permutedims(vcat(["$(s)" for s in ord], ["total", "ratio"])))
+        writedlm(io, hcat(permutedims(tr.V[nwin+1:end, :]), tr.ratio))
+    end
+    return gv
+end
+
 # regionArray::Vector{UnitRange{Int}} (1-based, src/mme.jl:335-358) -> 0-based [start, stop)
 function add_marker_set!(h::Handle, col0::Integer, ncol::Integer, method::Integer, df::Float64, scale::Float64,
                          regionArray, varBeta0::Vector{Float64}; pi0::Float64=0.0, estPi::Bool=false,
@@ -655,7 +742,7 @@ sets with BayesPR / BayesB / BayesC / BayesR / BayesRCπ / BayesLV priors.  Anyt
 to the reference sampler.
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
-                     seed::Integer=1, device::Integer=0)
+                     seed::Integer=1, device::Integer=0, windows::Dict=Dict(), windowThreshold::Float64=0.01, genomicVariance::Bool=false)
     all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110); the device draws the exact Gibbs conditional of the model, NOT the reference's lines (they leave Z_ID'Z_Dam u_Dam of the other levels in a level's right-hand side), so a run sent there would not be the reference's chain -- add_random_set_tuple! / sampleZ_tuple! are there for callers who want the exact one")
     (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
     any(s -> M[s].method == "BayesRCplus", keys(M)) && error("BayesRCplus: use the reference sampler (one step per annotation on the same column, src/functions.jl:362-419: not on the device)")
@@ -723,6 +810,20 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     set_residual_prior!(h, E.df, E.scale)
     check(h, ccall((:ngp_set_intercept, LIB), Int32, (Ptr{Cvoid}, Int32), h.ptr, 0))
     set_schedule!(h, chainLength, burnIn, outputFreq)
+    # genomic variance of every kept draw (windows = Dict(set => W | Vector{UnitRange}), or genomicVariance = true for the set and total
+    # slots alone): switched on behind set_y!, one trace row per kept draw; the files are written after the run
+    gvar = genomicVariance || !isempty(windows)
+    gvwins = Dict{Any,Vector{UnitRange{Int}}}()
+    if gvar
+        E.str == "I" || error("genomic variance: residual structure \"D\" scales the rows of the tiles (ngp_enable_genomic_variance refuses it)")
+        for (s, w) in windows
+            haskey(ids, s) || error("windows for an unknown set $(s): the marker sets are $(sets)")
+            P = M[s].dims[2]
+            gvwins[s] = w isa Integer ? [a:min(a + w - 1, P) for a in 1:w:P] : collect(UnitRange{Int}, w)
+            set_variance_windows!(h, ids[s], gvwins[s])
+        end
+        enable_genomic_variance!(h; threshold = windowThreshold, trace_rows = max(0, div(chainLength - burnIn, outputFreq)))
+    end
     # ONE call for the whole chain: the kept samples (these2Keep, src/samplers.jl:26) go to a binary file through a copy stream and
     # a writer thread of the library while the chain runs -- the device never stops for a sample
     smpfile = joinpath(outPut, "samples.ngp")
@@ -766,6 +867,7 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
             c0 += P; v0 += nr
         end
     end
+    gvar && write_genomic_variance(h, outPut, sets, ids, gvwins)
     # the caller's arrays as the reference's sampler leaves them: the state after the last iteration
     # read-back buffers by the HANDLE's P: a handle made by set_records! carries one inert block of RECORDS_ONLY_P zero columns, which
     # ngp_get_state copies out like any panel's (include/nextgp_hip.h, ngp_set_records)
