@@ -291,7 +291,8 @@ int32_t ngp_get_posterior_sums(ngp_handle *h, double *sum_beta, double *sum_beta
  * sum_pi 2*nsets | class-probability sums of the BayesR sets, K each | sums of the fixed effects beyond the intercept, all
  * columns of all sets in order (ngp_get_fixed) | with random-effect sets: sums of u, set after set, then the sums of varU, one per set |
  * sum_varE | sum_b | nKept] so the host can all-reduce them over RCCL without a PCIe round trip.  len = 3P + nvb + 2 nsets + sum K +
- * nfixcol (+ sum q + nrand) + 3 doubles. */
+ * nfixcol (+ sum q + nrand) + 3 doubles; a chain with held-out records (ngp_set_holdout, m > 0) appends sum_fit[N] | sum_fit2[N] |
+ * n_fit[N], 3 N doubles more, so that ngp_allreduce_posterior over K fold-chains leaves every record's pooled sums on every handle. */
 int32_t ngp_posterior_len(ngp_handle *h, int64_t *len);
 int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len);
 
@@ -625,6 +626,27 @@ int32_t ngp_set_genomic_variance(ngp_handle *h, const double *sumV, const double
                                  const double *last, int64_t nslots, const double *ratio, int64_t nKept);
 int32_t ngp_get_genomic_variance_trace(ngp_handle *h, double *V, double *ratio, int64_t rows, int64_t nslots);
 int32_t ngp_get_genomic_variance_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served);
+
+/* ---- held-out records: missing phenotypes and cross-validation folds by data augmentation ----
+ * A handle may carry a hold-out set H: m strictly increasing 0-based rows, 0 <= i < N, m < N.  A held-out record stays in the panel;
+ * its phenotype is never read (ngp_set_y accepts NaN there and starts the record at the mean of the observed phenotypes) and is
+ * redrawn at the head of every iteration of ngp_run / ngp_run_many from y_i | rest ~ N(fitted_i, varE / w_i): in the residual,
+ * ycorr_i <- e_i ("Held-out records": the arithmetic and the draw keys are normative).  Every engine runs
+ * unchanged, and K folds are K chains over one shared panel, each with its own mask (a sharer does not inherit the owner's).
+ * In every KEPT iteration fit_i = yaug_i - ycorr_i, the whole linear predictor of the record (intercept, fixed, random and marker
+ * terms), is accumulated: sum_fit[i] += fit, sum_fit2[i] += fit^2, n_fit[i] += 1; rows off H stay 0.
+ * ngp_set_holdout: after the panel (or ngp_set_records / ngp_share_panel) and before ngp_set_y, NGP_ERR_STATE once y is set (a new
+ * panel starts without a mask); NULL, 0 removes the mask; NGP_ERR_ARG for rows that are unsorted, repeated or out of range and for
+ * m >= N.  ngp_get_holdout: rows[m], yaug[m], and the sums [N] each, n_fit as doubles (any pointer may be NULL);
+ * ngp_set_holdout_state puts them back (resume).  ngp_get_holdout_layout: m (0 without a mask).
+ * With a mask the packed posterior and snapshots carry the hold-out state (see ngp_posterior_len, ngp_save_snapshot; a snapshot is
+ * refused by a handle with another mask or none); without one every format is byte for byte unchanged and nothing is launched.
+ * The fine seam is not concerned: the caller owns ycorr there. */
+int32_t ngp_set_holdout(ngp_handle *h, const int64_t *rows, int64_t m);
+int32_t ngp_get_holdout(ngp_handle *h, int64_t *rows, double *yaug, double *sum_fit, double *sum_fit2, double *n_fit, int64_t m, int64_t N);
+int32_t ngp_set_holdout_state(ngp_handle *h, const double *yaug, const double *sum_fit, const double *sum_fit2, const double *n_fit, int64_t m,
+                              int64_t N);
+int32_t ngp_get_holdout_layout(ngp_handle *h, int64_t *m);
 
 #ifdef __cplusplus
 }

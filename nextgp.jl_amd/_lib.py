@@ -189,6 +189,7 @@ SYMBOLS = [
     "ngp_get_prediction_last", "ngp_get_prediction_stats",
     "ngp_set_variance_windows", "ngp_enable_genomic_variance", "ngp_get_genomic_variance_layout", "ngp_get_genomic_variance",
     "ngp_set_genomic_variance", "ngp_get_genomic_variance_trace", "ngp_get_genomic_variance_stats",
+    "ngp_set_holdout", "ngp_get_holdout", "ngp_set_holdout_state", "ngp_get_holdout_layout",
 ]
 
 _lib = None
@@ -202,6 +203,31 @@ def prediction_summary(ps):
     mean = ps["sum"] / n
     sd = np.sqrt(np.maximum(0.0, ps["sum2"] / n - mean * mean))
     return dict(nKept=n, mean=mean[-1], sd=sd[-1], sets=[dict(mean=mean[s], sd=sd[s]) for s in range(mean.shape[0] - 1)])
+
+
+def holdout_summary(hs):
+    """Mean and SD of the fitted value of every record of hold-out sums ({"sum_fit", "sum_fit2", "n_fit"}, N entries each; the sums of
+    several fold-chains may have been added up): {"rows" (the records with at least one kept draw), "n", "mean", "sd"}."""
+    n = np.asarray(hs["n_fit"], dtype=np.float64)
+    rows = np.flatnonzero(n > 0)
+    if len(rows) == 0:
+        raise ValueError("no kept draw yet: the hold-out sums are empty")
+    mean = np.asarray(hs["sum_fit"])[rows] / n[rows]
+    sd = np.sqrt(np.maximum(0.0, np.asarray(hs["sum_fit2"])[rows] / n[rows] - mean * mean))
+    return dict(rows=rows.astype(np.int64), n=n[rows].astype(np.int64), mean=mean, sd=sd)
+
+
+def deal_folds(y, folds, foldSeed=1):
+    """Fold of every record for K-fold cross-validation: the records with an observed (non-NaN) response, in the order of
+    np.random.default_rng(foldSeed).permutation, dealt round-robin into folds 0 .. K-1; a record without a response gets -1."""
+    y = np.asarray(y, dtype=np.float64)
+    K = int(folds)
+    obs = np.flatnonzero(~np.isnan(y))
+    if K < 2 or K > len(obs):
+        raise ValueError(f"folds={folds}: between 2 and the number of records with a response ({len(obs)})")
+    fold = np.full(len(y), -1, dtype=np.int64)
+    fold[obs[np.random.default_rng(foldSeed).permutation(len(obs))]] = np.arange(len(obs)) % K
+    return fold
 
 
 def genomic_variance_names(nwin_per_set):
@@ -927,6 +953,50 @@ class Sampler:
     def set_y(self, y):
         y = np.ascontiguousarray(y, dtype=np.float64)
         self._chk(self.L.ngp_set_y(self.h, _p(y, C.c_double), C.c_int64(len(y))))
+
+    # ---- held-out records: missing phenotypes, cross-validation folds ---------------------
+    def set_holdout(self, rows):
+        """Hold out the records `rows` (0-based, strictly increasing, fewer than N): after the panel and before set_y, whose values on
+        these rows are then not read (NaN is fine).  Every iteration redraws their phenotypes from their conditional; every kept
+        iteration accumulates their fitted values (holdout()).  None or an empty list removes the mask."""
+        r = np.ascontiguousarray([] if rows is None else rows, dtype=np.int64)
+        if r.ndim != 1:
+            raise ValueError("set_holdout: a list of rows")
+        self._chk(self.L.ngp_set_holdout(self.h, _p(r, C.c_int64) if len(r) else None, C.c_int64(len(r))))
+
+    def holdout_rows(self):
+        m = C.c_int64()
+        self._chk(self.L.ngp_get_holdout_layout(self.h, C.byref(m)))
+        r = np.empty(m.value, dtype=np.int64)
+        if m.value:
+            self._chk(self.L.ngp_get_holdout(self.h, _p(r, C.c_int64), None, None, None, None, m, C.c_int64(self.N)))
+        return r
+
+    def holdout_state(self):
+        """{"rows", "yaug" (m entries), "sum_fit", "sum_fit2", "n_fit" (N entries, zero off the rows)} of a chain with a mask."""
+        m = C.c_int64()
+        self._chk(self.L.ngp_get_holdout_layout(self.h, C.byref(m)))
+        r = np.empty(m.value, dtype=np.int64); ya = np.empty(m.value)
+        s1 = np.empty(self.N); s2 = np.empty(self.N); nf = np.empty(self.N)
+        self._chk(self.L.ngp_get_holdout(self.h, _p(r, C.c_int64), _p(ya, C.c_double), _p(s1, C.c_double), _p(s2, C.c_double), _p(nf, C.c_double),
+                                         m, C.c_int64(self.N)))
+        return dict(rows=r, yaug=ya, sum_fit=s1, sum_fit2=s2, n_fit=nf)
+
+    def set_holdout_state(self, hs):
+        """Put back what holdout_state() gave (resume beside set_state / set_posterior_sums); a missing key leaves that array as it is."""
+        a = {k: (None if hs.get(k) is None else np.ascontiguousarray(hs[k], dtype=np.float64)) for k in ("yaug", "sum_fit", "sum_fit2", "n_fit")}
+        m = C.c_int64()
+        self._chk(self.L.ngp_get_holdout_layout(self.h, C.byref(m)))
+        for k, n in (("yaug", m.value), ("sum_fit", self.N), ("sum_fit2", self.N), ("n_fit", self.N)):
+            if a[k] is not None and a[k].shape != (n,):
+                raise ValueError(f"set_holdout_state: {k} must have {n} entries")
+        self._chk(self.L.ngp_set_holdout_state(self.h, _p(a["yaug"], C.c_double), _p(a["sum_fit"], C.c_double), _p(a["sum_fit2"], C.c_double),
+                                               _p(a["n_fit"], C.c_double), m, C.c_int64(self.N)))
+
+    def holdout(self):
+        """Posterior mean and SD of the fitted value (intercept, fixed, random and marker terms) of the records with hold-out sums:
+        {"rows", "n", "mean", "sd"}; after allreduce_posterior over fold-chains, of every validated record."""
+        return holdout_summary(self.holdout_state())
 
     def set_residual_prior(self, df, scale):
         self._chk(self.L.ngp_set_residual_prior(self.h, C.c_double(df), C.c_double(scale)))

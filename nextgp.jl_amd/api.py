@@ -709,7 +709,8 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 # ----------------------------------------------------------------------------------------------
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
-            predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False):
+            predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
+            foldSeed=1):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -748,6 +749,16 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     and genVarOut (one column per set, then total, then ratio), per chain under chain<c>/ with chains=K; gwas<set>.txt in outFolder:
     window, first and last SNP (1-based), mean V, mean q, SD of q, WPPA.  res["variance"] holds the same, pooled over the chains
     (res["chains"][c]["variance"]: each chain's own).  Not available for a member of a correlated (Tuple) unit or a GBLUP term.
+    (10) held-out records (ngp_set_holdout; DESIGN.md section 2, "Held-out records"): holdout=rows (0-based records) keeps these records
+    in the panel but never reads their response -- each iteration redraws it from its conditional, each kept draw accumulates the
+    record's fitted value (intercept, fixed, random and marker terms).  missing="holdout" does the same for the records whose response is
+    NaN (the default "error" refuses them as before).  res["holdout"] = {"rows", "y", "yhat", "sd", "n"} and outFolder/holdoutPredict.txt
+    (record y yhat sd, records counted from 1) hold the result, pooled over the chains with chains=K.  folds=K (2..8) is K-fold
+    cross-validation in one run: the records with a response are dealt into K folds (deal_folds: np.random.default_rng(foldSeed)
+    .permutation, round-robin), K chains (the same seed, chain ids chain .. chain+K-1) run over ONE copy of the panel as chains=K does,
+    chain c holding out fold c.  res["cv"] = {"fold", "yhat", "sd" (N entries, NaN where not validated), "accuracy" (Pearson correlation
+    of yhat and y), "slope" (regression of y on yhat), "mse", "per_fold", "pooled_over_folds": True -- the returned marker means are
+    pooled over the fold-chains}, and cvPredict.txt holds record fold y yhat sd.  folds= with chains= or holdout= raises ValueError.
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -759,6 +770,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     if not snps and not parsed.ped:
         raise ValueError("the accelerated path needs at least one SNP(...) term")
     y = np.asarray(userData[lhs], dtype=np.float64)
+    masks, cv_fold, chains = _holdout_masks(y, holdout, missing, folds, foldSeed, chains)   # (checked before any device work)
     ped = None
     if has_ped:   # makePed (src/misc.jl:98-115) once for all PED terms and all chains
         ids = []
@@ -889,6 +901,9 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
             region_cache[name] = _regions_for(prior, P, map_path, outFolder, name)
         return region_cache[name]
 
+    if masks is not None:   # every chain sets its own mask (a chain that shares the panel does not inherit one), in front of set_y
+        for sc, rows in zip(samplers, masks):
+            sc.set_holdout(rows)
     built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
                           gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0], ped=ped)
              for sc in samplers]
@@ -913,6 +928,8 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         pooled = dict(sum=sum(ps["sum"] for ps in sums), sum2=sum(ps["sum2"] for ps in sums), nKept=sum(ps["nKept"] for ps in sums))
         res["predict"] = _prediction_result(pooled, ids, names)
         write_prediction_file(os.path.join(outFolder, "gebvPredict.txt"), res["predict"])
+    if masks is not None:
+        _holdout_results(res, samplers, masks, cv_fold, y, outFolder)
     if gv_windows is not None:
         by_id = sorted(sets, key=lambda st: st["id"])                       # slot order: the device's set order
         names = [st["name"] for st in by_id]
@@ -929,6 +946,82 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         res["variance"] = _variance_result(pooled, names, wins, float(windowThreshold))
         write_gwas_files(outFolder, res["variance"])
     return res
+
+
+def _holdout_masks(y, holdout, missing, folds, foldSeed, chains):
+    """runLMEM(holdout=..., missing=..., folds=..., foldSeed=...): (the held-out rows of every chain or None, the fold of every record or
+    None, the number of chains).  Host checks only; a ValueError here comes before any device work."""
+    from ._lib import deal_folds
+    if missing not in ("error", "holdout"):
+        raise ValueError('missing: "error" or "holdout"')
+    N = len(y)
+    if folds is not None:
+        if int(chains) != 1:
+            raise ValueError("folds= together with chains=: the K folds ARE the chains of the run")
+        if holdout is not None:
+            raise ValueError("folds= together with holdout=: every record with a response is held out by its fold's chain")
+        if int(folds) != folds or not 2 <= int(folds) <= 8:
+            raise ValueError("folds: 2..8")
+    if holdout is None and missing == "error" and folds is None:
+        return None, None, chains
+    rows = np.zeros(0, dtype=np.int64)
+    if holdout is not None:
+        h = np.asarray(holdout)
+        if h.ndim != 1 or len(h) == 0 or h.dtype.kind not in "iu":
+            raise ValueError("holdout: a non-empty list of 0-based record numbers")
+        rows = np.unique(h.astype(np.int64))
+        if len(rows) != len(h):
+            raise ValueError("holdout: a record is listed twice")
+        if rows[0] < 0 or rows[-1] >= N:
+            raise ValueError(f"holdout: records are numbered 0..{N - 1}")
+    if missing == "holdout":
+        rows = np.union1d(rows, np.flatnonzero(np.isnan(y))).astype(np.int64)
+    if folds is None:
+        if len(rows) >= N:
+            raise ValueError("holdout: at least one record must keep its response")
+        return ([rows] * int(chains) if len(rows) else None), None, chains
+    fold = deal_folds(y, int(folds), foldSeed)
+    return [np.union1d(rows, np.flatnonzero(fold == c)).astype(np.int64) for c in range(int(folds))], fold, int(folds)
+
+
+def _holdout_results(res, samplers, masks, cv_fold, y, outFolder):
+    """res["holdout"] / holdoutPredict.txt (the records every chain holds out, sums pooled over the chains) and, for folds=K,
+    res["cv"] / cvPredict.txt (every record with a response, predicted by the chain that held its fold out)."""
+    from ._lib import holdout_summary
+    states = [sc.holdout_state() for sc in samplers]
+    common = masks[0] if cv_fold is None else np.setdiff1d(masks[0], np.flatnonzero(cv_fold == 0))   # what EVERY chain holds out
+    for r, hs in zip(res.get("chains", []), states):
+        r["holdout"] = holdout_summary(hs)
+    if len(common):
+        keep = np.zeros(len(y)); keep[common] = 1.0   # (a fold-chain's own fold does not belong to what all chains hold out)
+        hm = holdout_summary({k: sum(hs[k] for hs in states) * keep for k in ("sum_fit", "sum_fit2", "n_fit")})
+        res["holdout"] = dict(rows=hm["rows"], y=y[hm["rows"]], yhat=hm["mean"], sd=hm["sd"], n=hm["n"])
+        with open(os.path.join(outFolder, "holdoutPredict.txt"), "w") as f:
+            f.write("record\ty\tyhat\tsd\n")
+            for i, yh, sd in zip(hm["rows"], hm["mean"], hm["sd"]):
+                f.write(f"{i + 1}\t{repr(float(y[i]))}\t{repr(float(yh))}\t{repr(float(sd))}\n")
+    if cv_fold is None:
+        return
+    yhat = np.full(len(y), np.nan); sd = np.full(len(y), np.nan)
+    for c, hs in enumerate(states):
+        own = holdout_summary(hs)
+        sel = np.isin(own["rows"], np.flatnonzero(cv_fold == c))
+        yhat[own["rows"][sel]] = own["mean"][sel]; sd[own["rows"][sel]] = own["sd"][sel]
+
+    def score(v):
+        a, b = yhat[v], y[v]
+        da, db = a - a.mean(), b - b.mean()
+        saa = float(da @ da)
+        return dict(n=int(len(v)), accuracy=float(da @ db / np.sqrt(saa * float(db @ db))) if saa > 0 and db @ db > 0 else float("nan"),
+                    slope=float(da @ db / saa) if saa > 0 else float("nan"), mse=float(np.mean((b - a) ** 2)))
+
+    allv = score(np.flatnonzero(cv_fold >= 0))
+    res["cv"] = dict(fold=cv_fold, yhat=yhat, sd=sd, accuracy=allv["accuracy"], slope=allv["slope"], mse=allv["mse"],
+                     per_fold=[dict(fold=c, **score(np.flatnonzero(cv_fold == c))) for c in range(len(states))], pooled_over_folds=True)
+    with open(os.path.join(outFolder, "cvPredict.txt"), "w") as f:
+        f.write("record\tfold\ty\tyhat\tsd\n")
+        for i in np.flatnonzero(cv_fold >= 0):
+            f.write(f"{i + 1}\t{cv_fold[i]}\t{repr(float(y[i]))}\t{repr(float(yhat[i]))}\t{repr(float(sd[i]))}\n")
 
 
 def _variance_windows(windows, threshold, genomic_variance, snps, mats, gb_names, VCV):

@@ -33,6 +33,7 @@
 #include "ngp_dense.h"
 #include "ngp_logvar.h"
 #include "ngp_predict.h"
+#include "ngp_holdout.h"
 #include "ngp_genvar.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
@@ -486,6 +487,11 @@ struct ChainMem {
     uint64_t pred_for = 0;  // the panel (its id) and the number of sets the arrays above were sized for
     int64_t pred_rows = 0;
     int64_t pred_launches = 0, pred_served = 0;  // ngp_get_prediction_stats: launches this handle made, chains they served
+    // held-out records (ngp_holdout.h; ngp_set_holdout): the rows on the host and on the device, the augmented phenotype of each, and
+    // the sums of their fitted values over kept draws [N] (zero off the rows); all empty for a chain without a mask
+    std::vector<long long> ho_rows;
+    DevArray<long long> d_ho_rows;
+    DevArray<double> d_yaug, d_sum_fit, d_sum_fit2, d_n_fit;
 };
 
 // The model's arrays beyond the chain's: what a new panel discards (alloc_panel resets the whole group)
@@ -833,6 +839,13 @@ uint64_t weights_digest(const std::vector<double> &w) {
     uint64_t x = 1469598103934665603ull;
     const unsigned char *p = (const unsigned char *)w.data();
     for (size_t k = 0; k < w.size() * sizeof(double); k++) { x ^= p[k]; x *= 1099511628211ull; }
+    return x;
+}
+// the same over the held-out rows (int64 each): what a snapshot of a chain with a mask records of it
+uint64_t rows_digest(const std::vector<long long> &rows) {
+    uint64_t x = 1469598103934665603ull;
+    const unsigned char *p = (const unsigned char *)rows.data();
+    for (size_t k = 0; k < rows.size() * sizeof(long long); k++) { x ^= p[k]; x *= 1099511628211ull; }
     return x;
 }
 
@@ -1552,6 +1565,9 @@ int launch_genvar(ngp_handle *lead, ngp_handle **hs, int n) {
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
+    if (const long long m = (long long)h->cm.ho_rows.size())  // held-out records: their phenotypes are redrawn first (ycorr_i <- e_i)
+        hipLaunchKernelGGL(k_holdout_augment, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)h->cm.d_ho_rows, m, h->cm.d_ycorr.get(),
+                           h->cm.d_yaug.get(), (const double *)h->cm.d_rs, (const DScal *)h->cm.d_scal, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
     hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->L, (long long)h->N, h->cm.d_scal, h->e_df,
                        h->e_scale, h->intercept, 1, h->seed, (uint64_t)h->chain, it, h->hm.d_tr_varE, h->hm.d_tr_b, (long long)trace_idx, h->cm.d_abort, h->pm->mpm_max,
                        (const double *)h->cm.d_rs, h->sum_w);
@@ -1600,6 +1616,10 @@ int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true, bool g
         for (auto &Rc : h->mm.rc)  // BayesRCpi sets: the annotation category of every locus (src/samplers.jl:85-87)
             hipLaunchKernelGGL(k_rc_accum, dim3((unsigned)((Rc.n + 255) / 256)), dim3(256), 0, h->stream, (const DSet *)h->cm.d_sets, Rc.set, Rc.dev(),
                                (const unsigned *)h->cm.d_abort);
+        if (const long long m = (long long)h->cm.ho_rows.size())  // held-out records: the fitted value of this draw
+            hipLaunchKernelGGL(k_holdout_accum, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)h->cm.d_ho_rows, m,
+                               (const double *)h->cm.d_ycorr, (const double *)h->cm.d_yaug, (const double *)h->cm.d_rs, h->cm.d_sum_fit.get(), h->cm.d_sum_fit2.get(),
+                               h->cm.d_n_fit.get(), (const unsigned *)h->cm.d_abort);
         if (predict && predicts(h)) launch_predict(h, &h, 1);  // g = X_new beta of this draw, behind the posterior sums
         if (genvar && gv_active(h))                            // var(X beta) of this draw per window, set and in all
             if (int e = launch_genvar(h, &h, 1)) return e;
@@ -1702,6 +1722,11 @@ void describe(ngp_handle *h, ChainState &st) {
         HRc &Rc = h->mm.rc[(size_t)r];
         const size_t an8 = (size_t)Rc.A * (size_t)Rc.n * 8;
         st.dev(SEG_RC_PROB, r, Rc.d_prob, an8); st.dev(SEG_RC_CAT, r, Rc.d_cat, (size_t)Rc.n); st.dev(SEG_SUM_RC, r, Rc.d_sum, an8);
+    }
+    if (!h->cm.ho_rows.empty()) {  // held-out records: only a chain with a mask has these segments
+        const size_t N8 = (size_t)h->N * 8;
+        st.dev(SEG_YAUG, 0, h->cm.d_yaug, h->cm.ho_rows.size() * 8);
+        st.dev(SEG_SUM_FIT, 0, h->cm.d_sum_fit, N8); st.dev(SEG_SUM_FIT2, 0, h->cm.d_sum_fit2, N8); st.dev(SEG_N_FIT, 0, h->cm.d_n_fit, N8);
     }
 }
 static_assert(offsetof(DSet, piHat1) == offsetof(DSet, piHat0) + 8 && offsetof(DSet, sum_pi1) == offsetof(DSet, sum_pi0) + 8, "SEG_PI / SEG_SUM_PI");
@@ -2122,7 +2147,9 @@ int ready(ngp_handle *h) {
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: ngp_end_panel builds the Gram window the sweep needs");
     REQUIRE(h->have_y, NGP_ERR_STATE, "y not set");
-    if (h->records_only) REQUIRE(!h->mm.rnd.empty(), NGP_ERR_STATE, "no random-effect set added (a handle made by ngp_set_records has no marker sets)");
+    // (a records-only handle with a hold-out set may be the intercept-only model y = b + e: the closed-form case of the augmentation step)
+    if (h->records_only) REQUIRE(!h->mm.rnd.empty() || (h->intercept && !h->cm.ho_rows.empty()), NGP_ERR_STATE,
+                                 "no random-effect set added (a handle made by ngp_set_records has no marker sets)");
     else REQUIRE(!h->sets.empty(), NGP_ERR_STATE, "no marker set added");
     int rc;
     if ((rc = sync_tables(h))) return rc;
@@ -2277,6 +2304,7 @@ struct PanelHeader { char magic[8]; int64_t N, P; int32_t bits, zero; };
 }
 #define NGP_SNAP_WEIGHTED ((int64_t)1 << 62)  // snapshot: the fixed-set count's flag of a weighted chain (ngp_save_snapshot)
 #define NGP_SNAP_RANDOM ((int64_t)1 << 61)    // ... and of a chain with random-effect sets
+#define NGP_SNAP_HOLDOUT ((int64_t)1 << 60)   // ... and of a chain with held-out records (ngp_set_holdout)
 // snapshot signature of a BayesLV set (added to its second word): the covariate count and how varZeta is estimated
 static int64_t lv_sig(const ngp_handle *h, const HSet &hs) {
     return hs.lv < 0 ? 0 : 256 * ((int64_t)h->mm.lv[(size_t)hs.lv].ncov + 32 * (int64_t)h->mm.lv[(size_t)hs.lv].mode);
@@ -2547,9 +2575,32 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(y && N == h->N, NGP_ERR_ARG, "y must have N entries");
-    for (int64_t i = 0; i < N; i++) REQUIRE(std::isfinite(y[i]), NGP_ERR_ARG, "non-finite phenotype");
+    const std::vector<long long> &ho = h->cm.ho_rows;
+    std::vector<double> y_aug;  // held-out records: y with the mean of the observed phenotypes on the held-out rows, which are not read
+    if (ho.empty()) {
+        for (int64_t i = 0; i < N; i++) REQUIRE(std::isfinite(y[i]), NGP_ERR_ARG, "non-finite phenotype");
+    } else {
+        double sum_obs = 0.0;
+        size_t k = 0;
+        for (int64_t i = 0; i < N; i++) {
+            if (k < ho.size() && ho[k] == i) { k++; continue; }
+            REQUIRE(std::isfinite(y[i]), NGP_ERR_ARG, "non-finite phenotype");
+            sum_obs = sum_obs + y[i];  // index order, left to right
+        }
+        const double ybar = sum_obs / (double)(N - (int64_t)ho.size());
+        y_aug.assign(y, y + N);
+        for (long long i : ho) y_aug[(size_t)i] = ybar;
+        y = y_aug.data();
+        const std::vector<double> ya(ho.size(), ybar);
+        const size_t N8 = (size_t)N * sizeof(double);
+        HCHK(hipMemcpy(h->cm.d_yaug, ya.data(), ya.size() * sizeof(double), hipMemcpyHostToDevice));
+        HCHK(hipMemsetAsync(h->cm.d_sum_fit, 0, N8, h->stream));
+        HCHK(hipMemsetAsync(h->cm.d_sum_fit2, 0, N8, h->stream));
+        HCHK(hipMemsetAsync(h->cm.d_n_fit, 0, N8, h->stream));
+    }
     HCHK(hipMemsetAsync(h->cm.d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
     HCHK(hipMemcpyAsync(h->cm.d_ycorr, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // src/mme.jl:57
+    if (!y_aug.empty()) HCHK(hipStreamSynchronize(h->stream));  // (the copy reads y_aug)
     if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: y~ = s y
     HCHK(hipMemsetAsync(h->cm.d_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));                  // src/mme.jl:443
     HCHK(hipMemsetAsync(h->cm.d_delta, 1, (size_t)h->Ppad, h->stream));                                  // src/mme.jl:444
@@ -3399,15 +3450,18 @@ namespace {
 // random-effect sets writes neither flag, digest nor random part: its bytes are those of the first snapshots.
 struct ModelSig {
     std::vector<int64_t> sets;  // per marker set {method, K + 16 tuple k + the BayesLV word, nreg, col0, ncol}
-    int64_t nfs = 0;            // fixed-effect sets | NGP_SNAP_WEIGHTED | NGP_SNAP_RANDOM
+    int64_t nfs = 0;            // fixed-effect sets | NGP_SNAP_WEIGHTED | NGP_SNAP_RANDOM | NGP_SNAP_HOLDOUT
     uint64_t digest = 0;        // of the residual weights
+    uint64_t ho_digest = 0;     // of the held-out rows
     std::vector<uint64_t> rnd;  // nrand | per set q, digest of its level coding and K
     std::vector<int64_t> fix;   // ncol per fixed-effect set
     ModelSig() = default;
     explicit ModelSig(const ngp_handle *h) {
         for (auto &hs : h->sets) sets.insert(sets.end(), {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs) + rc_sig(h, hs), hs.nreg, hs.col0, hs.ncol});
-        nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM);
+        nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM) |
+              (h->cm.ho_rows.empty() ? 0 : NGP_SNAP_HOLDOUT);
         if (!h->h_rw.empty()) digest = weights_digest(h->h_rw);
+        if (!h->cm.ho_rows.empty()) ho_digest = rows_digest(h->cm.ho_rows);
         if (!h->mm.rnd.empty()) {
             rnd.push_back((uint64_t)h->mm.rnd.size());
             for (auto &R : h->mm.rnd) { rnd.push_back((uint64_t)rand_q_word(R)); rnd.push_back(R.sig); }
@@ -3447,6 +3501,7 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     W("NGPSNAP2", 8); W(dims, sizeof(dims)); W(himg.data(), himg.size());
     W(sig.sets.data(), sig.sets.size() * 8); W(&sig.nfs, 8);
     if (sig.nfs & NGP_SNAP_WEIGHTED) W(&sig.digest, 8);
+    if (sig.nfs & NGP_SNAP_HOLDOUT) W(&sig.ho_digest, 8);
     W(sig.rnd.data(), sig.rnd.size() * 8); W(sig.fix.data(), sig.fix.size() * 8);
     W(img.data(), img.size());
     if (fclose(f.release()) != 0) ok = false;  // (a failed close is a failed write)
@@ -3484,7 +3539,14 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         got.sets.assign(want.sets.size(), -1); got.nfs = -1;
         Rd(got.sets.data(), got.sets.size() * 8); Rd(&got.nfs, 8);
         const bool snap_w = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_WEIGHTED) != 0, snap_r = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_RANDOM) != 0;
+        const bool snap_h = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_HOLDOUT) != 0;
         if (snap_w) Rd(&got.digest, 8);
+        if (snap_h) Rd(&got.ho_digest, 8);
+        if (ok && snap_h != !h->cm.ho_rows.empty())
+            return fail(h, NGP_ERR_ARG, snap_h ? "snapshot of a chain with held-out records: this handle has none (ngp_set_holdout)"
+                                               : "snapshot of a chain without held-out records: this handle has them");
+        if (ok && snap_h && got.ho_digest != want.ho_digest)
+            return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its held-out records differ)");
         if (ok && snap_r != !want.rnd.empty())
             return fail(h, NGP_ERR_ARG, snap_r ? "snapshot of a chain with random-effect sets: this handle has none (ngp_add_random_set)"
                                                : "snapshot of a chain without random-effect sets: this handle has them");
@@ -5497,6 +5559,86 @@ int32_t ngp_get_genomic_variance_stats(ngp_handle *h, int64_t *launches, int64_t
     if ((rc = enter(h))) return rc;
     if (launches) *launches = h->cm.gv.launches;
     if (chains_served) *chains_served = h->cm.gv.served;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Held-out records ("Held-out records"; kernels in ngp_holdout.h): m strictly increasing rows whose phenotypes
+ * are not read but redrawn from their conditional at the head of every iteration.  Set after the panel (or ngp_set_records /
+ * ngp_share_panel: a sharer does not inherit the owner's mask) and before ngp_set_y; NULL, 0 removes the mask. */
+int32_t ngp_set_holdout(ngp_handle *h, const int64_t *rows, int64_t m) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set (the hold-out set belongs to the panel's records)");
+    REQUIRE(!h->have_y, NGP_ERR_STATE, "ngp_set_holdout: the phenotypes are set already; the hold-out set comes before ngp_set_y");
+    REQUIRE(m >= 0 && (rows != nullptr || m == 0), NGP_ERR_ARG, "ngp_set_holdout: m >= 0 rows (or NULL and 0 to remove the mask)");
+    REQUIRE(m < h->N, NGP_ERR_ARG, "ngp_set_holdout: at least one record must keep its phenotype (m < N)");
+    for (int64_t k = 0; k < m; k++)
+        REQUIRE(rows[k] >= 0 && rows[k] < h->N && (k == 0 || rows[k] > rows[k - 1]), NGP_ERR_ARG,
+                "ngp_set_holdout: rows must be strictly increasing and lie in [0, N)");
+    ChainMem &c = h->cm;
+    c.ho_rows.clear();
+    c.d_ho_rows.reset(); c.d_yaug.reset(); c.d_sum_fit.reset(); c.d_sum_fit2.reset(); c.d_n_fit.reset();
+    if (m == 0) return NGP_OK;
+    std::vector<long long> r(rows, rows + m);
+    DevArray<long long> d_rows;
+    DevArray<double> d_yaug, d_s, d_s2, d_n;
+    if ((rc = d_rows.alloc(h, (size_t)m)) || (rc = d_yaug.alloc(h, (size_t)m)) || (rc = d_s.alloc(h, (size_t)h->N)) || (rc = d_s2.alloc(h, (size_t)h->N)) ||
+        (rc = d_n.alloc(h, (size_t)h->N)))
+        return rc;
+    HCHK(hipMemcpyAsync(d_rows, r.data(), (size_t)m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
+    c.ho_rows = std::move(r);
+    c.d_ho_rows = std::move(d_rows); c.d_yaug = std::move(d_yaug); c.d_sum_fit = std::move(d_s); c.d_sum_fit2 = std::move(d_s2); c.d_n_fit = std::move(d_n);
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_holdout_layout(ngp_handle *h, int64_t *m) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    if (m) *m = (int64_t)h->cm.ho_rows.size();
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_holdout(ngp_handle *h, int64_t *rows, double *yaug, double *sum_fit, double *sum_fit2, double *n_fit, int64_t m, int64_t N) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm && !h->cm.ho_rows.empty(), NGP_ERR_STATE, "no hold-out set on this handle (ngp_set_holdout)");
+    REQUIRE(m == (int64_t)h->cm.ho_rows.size() && N == h->N, NGP_ERR_ARG, "hold-out buffers must hold m and N entries (ngp_get_holdout_layout)");
+    REQUIRE(h->have_y || !(yaug || sum_fit || sum_fit2 || n_fit), NGP_ERR_STATE, "y not set: the hold-out state does not exist yet");
+    HCHK(hipStreamSynchronize(h->stream));
+    if (rows) for (int64_t k = 0; k < m; k++) rows[k] = (int64_t)h->cm.ho_rows[(size_t)k];
+    const size_t N8 = (size_t)N * sizeof(double);
+    if (yaug) HCHK(hipMemcpy(yaug, h->cm.d_yaug, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_fit) HCHK(hipMemcpy(sum_fit, h->cm.d_sum_fit, N8, hipMemcpyDeviceToHost));
+    if (sum_fit2) HCHK(hipMemcpy(sum_fit2, h->cm.d_sum_fit2, N8, hipMemcpyDeviceToHost));
+    if (n_fit) HCHK(hipMemcpy(n_fit, h->cm.d_n_fit, N8, hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_holdout_state(ngp_handle *h, const double *yaug, const double *sum_fit, const double *sum_fit2, const double *n_fit, int64_t m, int64_t N) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm && !h->cm.ho_rows.empty(), NGP_ERR_STATE, "no hold-out set on this handle (ngp_set_holdout)");
+    REQUIRE(h->have_y, NGP_ERR_STATE, "y not set (ngp_set_y starts the hold-out state, this call replaces it)");
+    REQUIRE(m == (int64_t)h->cm.ho_rows.size() && N == h->N, NGP_ERR_ARG, "hold-out buffers must hold m and N entries (ngp_get_holdout_layout)");
+    if (yaug) for (int64_t k = 0; k < m; k++) REQUIRE(std::isfinite(yaug[k]), NGP_ERR_ARG, "non-finite augmented phenotype");
+    for (const double *a : {sum_fit, sum_fit2, n_fit})
+        if (a) for (int64_t i = 0; i < N; i++) REQUIRE(std::isfinite(a[i]), NGP_ERR_ARG, "non-finite hold-out sum");
+    HCHK(hipStreamSynchronize(h->stream));
+    const size_t N8 = (size_t)N * sizeof(double);
+    if (yaug) HCHK(hipMemcpy(h->cm.d_yaug, yaug, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    if (sum_fit) HCHK(hipMemcpy(h->cm.d_sum_fit, sum_fit, N8, hipMemcpyHostToDevice));
+    if (sum_fit2) HCHK(hipMemcpy(h->cm.d_sum_fit2, sum_fit2, N8, hipMemcpyHostToDevice));
+    if (n_fit) HCHK(hipMemcpy(h->cm.d_n_fit, n_fit, N8, hipMemcpyHostToDevice));
     return NGP_OK;
     NGP_CATCH(h)
 }

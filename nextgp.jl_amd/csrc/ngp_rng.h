@@ -32,6 +32,7 @@
 #define NGP_KIND_RC_UNIFORM 19  // BayesRCpi: the uniform of a locus' annotation draw, (set << 40) | locus (src/functions.jl:318); its class search
                                 // takes kinds 8 / 18 with the slot a * K + v as the comparison
 #define NGP_KIND_RC_ANNOT 20    // BayesRCpi: gamma of annotation a of a locus' annotProb Dirichlet, (set << 40) | (locus << 3) | a (src/functions.jl:541-544)
+#define NGP_KIND_AUGMENT 21     // held-out records: the normal of a record's augmented phenotype, keyed by the row (ngp_holdout.h)
 
 #define NGP_GOLD 0x9E3779B97F4A7C15ULL
 

@@ -23,6 +23,8 @@
 //    fixed-effect sums (every column of every set) | sum_u[q] of every random-effect set, then sum_varU of every set |
 //    per BayesLV set sum_c[16], sum_varZeta | per BayesRCpi set sum_annot[A][ncol] | sum_varE | sum_b | nKept (as a double; rounded with
 //    llround on the way back).  A BayesRCpi set's pi sums are the class sums of its A K slots, its A variance sums lie in sum_varBeta.
+//    A chain with held-out records (ngp_set_holdout, m > 0) appends sum_fit[N] | sum_fit2[N] | n_fit[N] (doubles, zero off the held-out
+//    rows); a chain without a mask appends nothing.
 //
 //  Sample file (ngp_set_sample_file) -- record: sample_layout, padded to a multiple of 8 bytes:
 //    header  char[8] magic | int64 P, nvb, nsets, nfix, nclass, record bytes | per marker set int64 {method, K, col0, ncol, variance
@@ -37,8 +39,9 @@
 //  Snapshot (ngp_save_snapshot / ngp_load_snapshot):
 //    char[8] "NGPSNAP2" | int64 N, P, nvb, nsets | snapshot_head_layout: int64 iter, nKept | uint64 seed, chain |
 //    model signature (ModelSig in ngp_api.hip): per marker set int64 {method, K + 16 tuple k + 256 (ncov + 32 est_mode) of a
-//      BayesLV set, nreg, col0, ncol} | int64 number of fixed-effect sets, bit 62: residual weights, bit 61: random-effect sets |
-//      with weights: uint64 digest of the weights | with random-effect sets: int64 nrand, per set int64 q, uint64 digest of its level
+//      BayesLV set, nreg, col0, ncol} | int64 number of fixed-effect sets, bit 62: residual weights, bit 61: random-effect sets,
+//      bit 60: held-out records | with weights: uint64 digest of the weights | with held-out records: uint64 digest of their rows |
+//      with random-effect sets: int64 nrand, per set int64 q, uint64 digest of its level
 //      coding and K | int64 ncol per fixed-effect set
 //    snapshot_body_layout: varE, b, sum_varE, sum_b | ycorr[N] (with residual weights the scaled residual as it lies on the
 //      device) | beta[P] | delta[P] (uint8, 0 / 1) | varBeta[nvb] | piHat[2] per set | sum_beta[P] | sum_beta2[P] | sum_delta[P] |
@@ -46,7 +49,8 @@
 //      per BayesR set piHat[K], sum_pi[K] | per random-effect set u[q], sum_u[q], varU, sum_varU, uint64 fine_calls |
 //      per BayesLV set the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums, ...), zeta[ncol] |
 //      per BayesRCpi set annotProb[A][ncol], sum_annot[A][ncol], annotCat[ncol] (uint8); its signature words are method 6,
-//      K = A K slots + a 47-bit digest of the annotation masks from bit 8 up, and nreg = A
+//      K = A K slots + a 47-bit digest of the annotation masks from bit 8 up, and nreg = A |
+//      with held-out records: yaug[m], sum_fit[N], sum_fit2[N], n_fit[N] (doubles)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -71,7 +75,9 @@ enum SegId : int {
     // ... and arrays that hold value and sum side by side, whole
     SEG_VU, SEG_LV_ALL,
     // BayesRCpi sets, per set: annotProb[A][ncol], annotCat[ncol] (uint8, from 1), sum_annot[A][ncol]
-    SEG_RC_PROB, SEG_RC_CAT, SEG_SUM_RC
+    SEG_RC_PROB, SEG_RC_CAT, SEG_SUM_RC,
+    // held-out records (described only for a chain that has a mask): yaug[m], and sum_fit[N], sum_fit2[N], n_fit[N] (doubles)
+    SEG_YAUG, SEG_SUM_FIT, SEG_SUM_FIT2, SEG_N_FIT
 };
 
 struct Seg {
@@ -100,14 +106,15 @@ struct ChainState {
 using Layout = std::vector<std::vector<SegId>>;
 
 inline const Layout posterior_layout = {{SEG_SUM_BETA}, {SEG_SUM_BETA2}, {SEG_SUM_DELTA}, {SEG_SUM_VARBETA}, {SEG_SUM_PI}, {SEG_SUM_CLS}, {SEG_SUM_FIX},
-                                        {SEG_SUM_U}, {SEG_SUM_VARU}, {SEG_SUM_LV}, {SEG_SUM_RC}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_NKEPT_F64}};
+                                        {SEG_SUM_U}, {SEG_SUM_VARU}, {SEG_SUM_LV}, {SEG_SUM_RC}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_NKEPT_F64},
+                                        {SEG_SUM_FIT}, {SEG_SUM_FIT2}, {SEG_N_FIT}};
 inline const Layout sample_layout = {{SEG_ITER}, {SEG_VARE}, {SEG_B}, {SEG_FIX}, {SEG_U}, {SEG_VARU}, {SEG_BETA}, {SEG_VARBETA}, {SEG_PI}, {SEG_CLS},
                                      {SEG_LV}, {SEG_RC_PROB}, {SEG_DELTA}, {SEG_RC_CAT}};
 inline const Layout snapshot_head_layout = {{SEG_ITER}, {SEG_NKEPT}, {SEG_SEED}, {SEG_CHAIN}};
 inline const Layout snapshot_body_layout = {{SEG_VARE}, {SEG_B}, {SEG_SUM_VARE}, {SEG_SUM_B}, {SEG_YCORR}, {SEG_BETA}, {SEG_DELTA}, {SEG_VARBETA}, {SEG_PI},
                                             {SEG_SUM_BETA}, {SEG_SUM_BETA2}, {SEG_SUM_DELTA}, {SEG_SUM_VARBETA}, {SEG_SUM_PI}, {SEG_FINE}, {SEG_NFIX}, {SEG_FIX},
                                             {SEG_SUM_FIX}, {SEG_CLS, SEG_SUM_CLS}, {SEG_U, SEG_SUM_U, SEG_VU, SEG_RFINE}, {SEG_LV_ALL, SEG_ZETA},
-                                            {SEG_RC_PROB, SEG_SUM_RC, SEG_RC_CAT}};
+                                            {SEG_RC_PROB, SEG_SUM_RC, SEG_RC_CAT}, {SEG_YAUG, SEG_SUM_FIT, SEG_SUM_FIT2, SEG_N_FIT}};
 
 // a layout applied to a chain: every segment with its byte offset, and the size of the whole
 struct Plan {

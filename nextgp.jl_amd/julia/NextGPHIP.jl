@@ -84,6 +84,42 @@ end
 load_panel_file!(h::Handle, path::AbstractString; centre::Bool=true) =
     check(h, ccall((:ngp_load_panel_file, LIB), Int32, (Ptr{Cvoid}, Cstring, Int32), h.ptr, path, centre))
 
+# ---- held-out records: missing phenotypes, cross-validation folds (include/nextgp_hip.h, "held-out records") ----
+# rows: 0-BASED records, strictly increasing, after the panel and before set_y!; nothing / an empty vector removes the mask
+function set_holdout!(h::Handle, rows::Union{Nothing,Vector{Int64}})
+    r = rows === nothing ? Int64[] : rows
+    check(h, ccall((:ngp_set_holdout, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64), h.ptr, isempty(r) ? C_NULL : pointer(r), length(r)))
+end
+function holdout_layout(h::Handle)       # m: the number of held-out records (0 without a mask)
+    m = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_holdout_layout, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), h.ptr, m))
+    return m[]
+end
+function holdout_state(h::Handle, N::Integer)   # rows (0-based), yaug (m each), sum_fit, sum_fit2, n_fit (N each, zero off the rows)
+    m = holdout_layout(h)
+    rows = Vector{Int64}(undef, m); yaug = Vector{Float64}(undef, m)
+    s1 = Vector{Float64}(undef, N); s2 = similar(s1); nf = similar(s1)
+    check(h, ccall((:ngp_get_holdout, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64),
+                   h.ptr, rows, yaug, s1, s2, nf, m, N))
+    return (rows = rows, yaug = yaug, sum_fit = s1, sum_fit2 = s2, n_fit = nf)
+end
+set_holdout_state!(h::Handle, yaug::Vector{Float64}, sum_fit::Vector{Float64}, sum_fit2::Vector{Float64}, n_fit::Vector{Float64}) =
+    check(h, ccall((:ngp_set_holdout_state, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64),
+                   h.ptr, yaug, sum_fit, sum_fit2, n_fit, length(yaug), length(sum_fit)))
+"""
+    getHoldout(h, N)
+
+Posterior mean and SD of the fitted value (intercept, fixed, random and marker terms) of every held-out record over the kept draws:
+`rows` (1-based), `n`, `mean`, `sd`.
+"""
+function getHoldout(h::Handle, N::Integer)
+    st = holdout_state(h, N)
+    keep = findall(>(0), st.n_fit)
+    mean = st.sum_fit[keep] ./ st.n_fit[keep]
+    sd = sqrt.(max.(0.0, st.sum_fit2[keep] ./ st.n_fit[keep] .- mean .^ 2))
+    return (rows = keep, n = Int.(st.n_fit[keep]), mean = mean, sd = sd)
+end
+
 # ---- prediction of new individuals (include/nextgp_hip.h, "prediction") ----
 # A second panel beside the training panel: Np individuals x the same columns in the same order, centred with the TRAINING means.
 # Every kept iteration then accumulates g = X_new beta per marker set on the device.  Column ranges as for the training panel.
@@ -742,7 +778,8 @@ sets with BayesPR / BayesB / BayesC / BayesR / BayesRCπ / BayesLV priors.  Anyt
 to the reference sampler.
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
-                     seed::Integer=1, device::Integer=0, windows::Dict=Dict(), windowThreshold::Float64=0.01, genomicVariance::Bool=false)
+                     seed::Integer=1, device::Integer=0, windows::Dict=Dict(), windowThreshold::Float64=0.01, genomicVariance::Bool=false,
+                     holdout::Vector{Int}=Int[])
     all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110); the device draws the exact Gibbs conditional of the model, NOT the reference's lines (they leave Z_ID'Z_Dam u_Dam of the other levels in a level's right-hand side), so a run sent there would not be the reference's chain -- add_random_set_tuple! / sampleZ_tuple! are there for callers who want the exact one")
     (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
     any(s -> M[s].method == "BayesRCplus", keys(M)) && error("BayesRCplus: use the reference sampler (one step per annotation on the same column, src/functions.jl:362-419: not on the device)")
@@ -806,6 +843,8 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
             zids[z] = add_random_set!(h, random_levels(Z[z].data), q, Z[z].iVarStr, Float64(Z[z].df), Float64(Z[z].scale), Float64(varU[z]))
         end
     end
+    # held-out records (1-BASED rows, as Julia counts): their entries of ycorr are not read and may be NaN / missing-coded
+    isempty(holdout) || set_holdout!(h, Vector{Int64}(sort(holdout) .- 1))
     set_y!(h, Vector{Float64}(ycorr))            # ycorr == y at this point (src/mme.jl:57)
     set_residual_prior!(h, E.df, E.scale)
     check(h, ccall((:ngp_set_intercept, LIB), Int32, (Ptr{Cvoid}, Int32), h.ptr, 0))
@@ -868,6 +907,15 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         end
     end
     gvar && write_genomic_variance(h, outPut, sets, ids, gvwins)
+    if !isempty(holdout)                         # holdoutPredict.txt: record (1-based), y as given, posterior mean and SD of the fitted value
+        yin = Vector{Float64}(ycorr); ho = getHoldout(h, nData)
+        open(outPut * "/holdoutPredict.txt", "w") do io
+            writedlm(io, ["record" "y" "yhat" "sd"])
+            for (i, r) in enumerate(ho.rows)
+                writedlm(io, Any[r yin[r] ho.mean[i] ho.sd[i]])
+            end
+        end
+    end
     # the caller's arrays as the reference's sampler leaves them: the state after the last iteration
     # read-back buffers by the HANDLE's P: a handle made by set_records! carries one inert block of RECORDS_ONLY_P zero columns, which
     # ngp_get_state copies out like any panel's (include/nextgp_hip.h, ngp_set_records)
