@@ -387,6 +387,8 @@ int32_t ngp_debug_set_mode(ngp_handle *h, int32_t mode);
  * on the matrix cores (v_mfma_f64_16x16x4_f64) instead of the fp64 VALU kernel: the same sums in the same order, bit for bit;
  * + 2048 = the row-owning streamers over fp32 tiles on the sampler's XCD do not warm its L2 with the next block's Gram planes;
  * + 8192 = the warmer role (ngp_get_warmer) is withheld, + 16384 = it is offered below 160-row shards too;
+ * + 32768 = the row waves of the row-owning streamer over fp32 tiles load none of their quads themselves (the loader wave requests every
+ * quad, ngp_get_census), + 1 << 28 = they do so below 160-row shards too, wherever the loader keeps its early part;
  * bits 16-27 = shard + 1 whose barrier-arrival timeline the diagnostic kernel records (0: shard 1).  Changes timing only, never results. */
 int32_t ngp_debug_set_knob(ngp_handle *h, int32_t knob);
 
@@ -427,7 +429,8 @@ int32_t ngp_run_many(ngp_handle **hs, int32_t n, int64_t niter);
  * every record holds u (set after set) and varU[nrand] between b_fixed and beta. */
 int32_t ngp_set_sample_file(ngp_handle *h, const char *path);
 /* Placement census of the last persistent-sweep launch: out[b] = (XCC id + 1) << 32 | HW_REG_HW_ID of workgroup b (0: never resident),
- * n >= *grid entries.  Every launch of the persistent kernel opens with a census of its own grid (all of its workgroups wait for
+ * n >= *grid entries; bits 40-63 of a row-owning streamer's entry over fp32 tiles: quads of that launch which its wave 0 loaded itself
+ * instead of taking them from the loader wave (0 where the loader brings every quad).  Every launch of the persistent kernel opens with a census of its own grid (all of its workgroups wait for
  * each other, so all must be resident at once); a launch whose grid is not complete within 20 ms ends before any role has touched
  * the chain, and the call runs it again with the whole device leased (the chains of one process then take turns) -- *retries counts
  * those, *exclusive says whether this handle now always leases the whole device.  Any pointer may be NULL. */

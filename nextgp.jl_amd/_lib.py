@@ -1120,13 +1120,14 @@ class Sampler:
 
     def census(self):
         """Placement of the workgroups of the last persistent-sweep launch (ngp_get_census): dict(grid, retries, exclusive,
-        xcc[grid] (0-7, -1 = never resident), hw_id[grid])."""
+        xcc[grid] (0-7, -1 = never resident), hw_id[grid], direct[grid] (quads of that launch which wave 0 of a row-owning streamer
+        loaded itself and fed to its GEMV chain; 0 where the loader brings every quad))."""
         g, r, e = C.c_int64(), C.c_int64(), C.c_int32()
         self._chk(self.L.ngp_get_census(self.h, None, C.c_int64(0), C.byref(g), C.byref(r), C.byref(e)))
         tb = np.zeros(g.value, dtype=np.uint64)
         self._chk(self.L.ngp_get_census(self.h, _p(tb, C.c_uint64), C.c_int64(g.value), None, None, None))
-        return dict(grid=g.value, retries=r.value, exclusive=bool(e.value), xcc=(tb >> np.uint64(32)).astype(np.int64) - 1,
-                    hw_id=(tb & np.uint64(0xFFFFFFFF)).astype(np.int64))
+        return dict(grid=g.value, retries=r.value, exclusive=bool(e.value), xcc=((tb >> np.uint64(32)) & np.uint64(0xFF)).astype(np.int64) - 1,
+                    hw_id=(tb & np.uint64(0xFFFFFFFF)).astype(np.int64), direct=(tb >> np.uint64(40)).astype(np.int64))
 
     def warmer(self):
         """The warmer of the last persistent-sweep launch (ngp_get_warmer): dict(active, blocks)."""

@@ -271,7 +271,7 @@ void choose_layout(int64_t N, int64_t max_shards, int64_t r_cap, int64_t *R, int
 // tall_rc, multi_rc -- among them: their lanes' class coefficients stay in registers), BayesR coefficients on top in the _r ones
 size_t sampler_lds(SweepKernel k) {
     const size_t base = (size_t)(3 * 4096 + 2 * NGP_RING * NGP_BLK + 6 * NGP_BLK) * sizeof(double) + 2 * NGP_BLK * sizeof(int) + 320;
-    if (k == SweepKernel::lean) return base;
+    if (k == SweepKernel::lean || k == SweepKernel::lean_dq) return base;
     if (k == SweepKernel::r || k == SweepKernel::multi_r) return base + NGP_SAMPLER_TUPLE_LDS + NGP_SAMPLER_R_LDS;
     return base + NGP_SAMPLER_TUPLE_LDS;
 }
@@ -335,7 +335,7 @@ SweepKernel pick_kernel(const SweepPlan &p, int K, bool diag, bool tup, bool rse
 
 // host address of a sweep kernel: each translation unit of ngp_sweep_inst.hip knows the kernels it defines
 const void *sweep_kernel(SweepKernel k) {
-    for (auto unit : {sweep_kernel_0, sweep_kernel_1, sweep_kernel_2, sweep_kernel_3, sweep_kernel_4})
+    for (auto unit : {sweep_kernel_0, sweep_kernel_1, sweep_kernel_2, sweep_kernel_3, sweep_kernel_4, sweep_kernel_5})
         if (const void *f = unit(k)) return f;
     return nullptr;
 }
@@ -782,7 +782,7 @@ int alloc_panel(ngp_handle *h, int64_t N, int64_t P, ngp_handle *owner = nullptr
     if (req.storage == 0) HCHK(hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
     if (plan.mode == 1) {
         // the single-chain kernels, each with the LDS this plan launches it with (k_sweep_r where that fits)
-        for (SweepKernel k : {SweepKernel::lean, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::rc, SweepKernel::tall, SweepKernel::tall_rc}) {
+        for (SweepKernel k : {SweepKernel::lean, SweepKernel::lean_dq, SweepKernel::diag, SweepKernel::tup, SweepKernel::r, SweepKernel::rc, SweepKernel::tall, SweepKernel::tall_rc}) {
             const size_t lds = sweep_lds(plan, k);
             if (lds <= NGP_LDS_MAX) HCHK(hipFuncSetAttribute(sweep_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
@@ -1052,6 +1052,16 @@ bool is_kept(const ngp_handle *h, int64_t it) {  // src/samplers.jl:26
     return ((it - h->burnIn) % h->thin) == 0;
 }
 
+// Direct quads (role_streamer_rows): the row waves of the row-owning streamer over fp32 tiles load the last NGP_ROWS_DIRECT quads of
+// their GEMV chains themselves, and the loader wave requests that much less through its LDS-DMA queue.  One shard per workgroup, the
+// loader's early part [0, H) untouched (NQ - 7 KD >= H), and only from shards of NGP_DIRECT_MIN_R rows on.  Knob bit 15 (timing only)
+// withholds them, bit 16 (timing and tests) offers them at any height the early part allows.  The values and their order do not change.
+static bool sweep_direct_quads(const ngp_handle *h) {
+    const int nq = (int)h->plan.R / 4, hq = std::min<int>(NGP_ROWS_HMAX, (nq + 1) / 2);
+    return h->plan.mode == 1 && h->plan.streamer == 2 && h->plan.V == 1 && h->req.storage == 0 && !(h->knob & NGP_KNOB_NO_DIRECT) &&
+           nq - NGP_ROWS_NW * NGP_ROWS_DIRECT >= hq && (h->plan.R >= NGP_DIRECT_MIN_R || (h->knob & NGP_KNOB_DIRECT_ANY_R));
+}
+
 // launch arguments of the persistent sweep over blocks [tb0, tb1) of this handle's chain (advances the launch nonce)
 void fill_sweep_args(ngp_handle *h, int64_t tb0, int64_t tb1, SweepArgs &A) {
     const int R = (int)h->plan.R, S = (int)h->plan.S;
@@ -1088,7 +1098,7 @@ void fill_sweep_args(ngp_handle *h, int64_t tb0, int64_t tb1, SweepArgs &A) {
     const bool warmer_idle = h->plan.NG > 0 && h->plan.NG % 8 == 0 && h->plan.near + h->plan.NG >= h->plan.D;
     const bool warmer = h->dbg_mode == 0 && h->plan.streamer == 2 && h->plan.V == 1 && !(h->knob & NGP_KNOB_NO_WARMER) &&
                         warmer_tall && warmer_idle;
-    A.variant = h->plan.streamer; A.knob = (h->knob & ~NGP_KNOB_WARMER) | (warmer ? NGP_KNOB_WARMER : 0);
+    A.variant = h->plan.streamer; A.knob = (h->knob & ~(NGP_KNOB_WARMER | NGP_KNOB_DIRECT)) | (warmer ? NGP_KNOB_WARMER : 0) | (sweep_direct_quads(h) ? NGP_KNOB_DIRECT : 0);
     A.mean = h->pm->mean; A.N = h->N;
     A.dbg_mode = h->dbg_mode;
 }
@@ -1100,7 +1110,10 @@ void launch_sweep(ngp_handle *h, int64_t tb0, int64_t tb1, hipEvent_t *evs) {
         // (the hand-off counters were zeroed by k_prep, which precedes every sweep in the stream)
         SweepArgs A;
         fill_sweep_args(h, tb0, tb1, A);
-        const SweepKernel k = pick_kernel(h->plan, 1, h->hm.d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0, !h->mm.rc.empty());
+        SweepKernel k = pick_kernel(h->plan, 1, h->hm.d_dbg || h->dbg_mode, h->ntuple > 0, h->nclass_total > 0, !h->mm.rc.empty());
+        // the direct quads exist in two instantiations: k_sweep_dq, which takes the lean kernel's place, and the diagnostic kernel
+        if (k == SweepKernel::lean && (A.knob & NGP_KNOB_DIRECT)) k = SweepKernel::lean_dq;
+        else if (k != SweepKernel::diag) A.knob &= ~NGP_KNOB_DIRECT;
         h->last_grid = sweep_grid(h->plan);
         if (evs) (void)hipEventRecord(evs[0], h->stream);
         launch_sweep_kernel(k, h->last_grid, sweep_lds(h->plan, k), h->stream, &A);

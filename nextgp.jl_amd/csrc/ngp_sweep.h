@@ -628,11 +628,16 @@ __device__ __attribute__((always_inline)) inline void fmac4_bcast(double (&a)[GN
 //
 //   wave 7     is the loader and nothing else: it keeps the LDS-DMA queue of the CU full (tile u+1 and the first H quads
 //              of tile u+2 are requested during block u, into a ring of 2 NQ + H quad slots) and joins the ONE barrier of
-//              the block after a counted vmcnt wait that leaves those H requests in flight;
+//              the block after a counted vmcnt wait that leaves those H requests in flight.  In k_sweep_dq (fp32 tiles of
+//              160-row shards and taller) the last seven quads of a tile are not its business: each comes by a plain load
+//              of the row wave that owns it ("direct quads" below; 51 -> 44 requests per block at 204-row shards; account
+//              in DESIGN.md 4.1);
 //   waves 0-6  own rows: wave w holds quads w, w+7, w+14, ... of the shard (a quad = 4 rows).  It forms the GEMV chain of
 //              exactly those quads (lane = column) and applies the update to exactly those rows (lane = (quad, 8-column
 //              chain), the 8 chain partials of a row meet in a DPP tree inside the wave), so ycorr never crosses a wave:
 //              no barrier between the update and the GEMV, no partial-sum array, one LDS read of the shard per quad.
+//              The last quad of its chain it may fetch itself, behind the GEMV of the block before, and store into the
+//              quad's ring slot when the chain reaches it: nobody else reads that slot, LDS serves a wave in order.
 //   wave 2     also publishes the 64 partial dot products of the previous block right after the barrier and counts them
 //              when its own VM_CNT shows the store acknowledged (it has no other memory traffic);
 //   wave 6     also fetches dlt of the block to be applied next (flag requested at the start of the block, read after its
@@ -696,7 +701,9 @@ __device__ inline void wait_vmcnt_le(int n) {
 // 4 rows x 8 columns (8 VGPRs per task and lag instead of 32: lags 3, 4, 6, 8, 12 with one task, 4 and 8 with two, 4 with four; shards of up to 896 rows).  Centring is
 // analytic: the shard partial is sum_i g_ij y_i - m_j sum_i y_i, the update subtracts
 // sum_j g_ij dlt_j - sum_j m_j dlt_j from the valid rows.
-template <bool DBG, int DT, int ST>
+// DQ: the instantiation carries the direct quads (k_sweep_dq, and the diagnostic kernel for its timelines and timing modes); every other
+// kernel keeps the loader-only text -- beside the sampler of the shapes it bounds the extra code cost 1.4 % (10k x 100k).
+template <bool DBG, int DT, int ST, bool DQ = false>
 __device__ __attribute__((always_inline)) inline void role_streamer_rows(const SweepArgs &A, const int s, char *smem) {
     NGP_DBG_ROWS
     constexpr bool U8 = (ST != 0);
@@ -706,6 +713,15 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
     const int NQ = U8 ? (R >> 4) : (R >> 2);                 // 1 KiB ring slots per tile: quads (fp32) or units of 16 rows (bytes)
     const int H = min(NGP_ROWS_HMAX, (NQ + 1) >> 1);         // quads of a tile requested one block earlier than the rest
     const int RQ = 2 * NQ + H;                               // ring slots: tile u in use, tile u+1 complete, H quads of tile u+2
+    // Direct quads (fp32 tiles, offered by the host through NGP_KNOB_DIRECT): the last 7 KD quads of a tile -- KD per row wave, the
+    // last KD of its GEMV chain -- do not pass through the loader's LDS-DMA queue.  The wave that owns such a quad reads it alone
+    // (GEMV and delay line), and its 16 bytes per lane in LDS are what a plain 16-byte load of the quad delivers: the wave
+    // requests it into registers behind the GEMV of block u, and in block u+1 stores it into its ring slot and feeds it to the
+    // same fma of the same chain position.  The loader requests quads [0, NQD) only.
+    constexpr int KD = NGP_ROWS_DIRECT;
+    static_assert(!DQ || !U8, "direct quads: fp32 tiles only");
+    const bool direct = DQ ? (A.knob & NGP_KNOB_DIRECT) != 0 : false;
+    const int NQD = DQ ? (direct ? NQ - NGP_ROWS_NW * KD : NQ) : NQ;  // quads of a tile the loader requests
     char *ring = smem;
     double *ys = (double *)(smem + (size_t)RQ * NGP_QS);     // the shard of ycorr, resident for the whole sweep
     double *red = ys + ((R + 7) & ~7);                       // 2 (block parity) x 7 chains x 64 columns
@@ -731,6 +747,7 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
     const bool early = U8 ? ((A.knob & 256) != 0) : ((A.knob & 256) == 0);
     if (tid == 0) { *sflag = 1; *gcnt0 = 0; *gcnt1 = 0; }
     int base = 0;  // ring slot of quad 0 of tile u
+    int ndirect = 0;  // direct quads wave 0 has fed to its chain (reported beside this workgroup's census entry)
     auto wrap = [&](int p) __attribute__((always_inline)) { return p >= RQ ? p - RQ : p; };
     if (wv == NGP_ROWS_NW) {
         // ------------------------------ loader ------------------------------
@@ -784,7 +801,7 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
         const size_t slice_bytes = ((gram_bytes / nslice + 1023) / 1024) * 1024;
         bool same_xcd = false, xcc_known = false;
         __builtin_amdgcn_s_setprio(3);  // the loader's few scalar instructions go first on its SIMD: a late request costs the whole CU
-        if (nb > 0) dma_quads(0, 0, NQ, 0);
+        if (nb > 0) dma_quads(0, 0, NQD, 0);
         if (nb > 1) dma_quads(1, 0, H, NQ);
         drain_vm();  // tile 0 has landed
         wg_barrier();
@@ -822,11 +839,11 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
             // so that more than H requests are in flight while the loader sits at the barrier -- was built and measured: 50k x 600k
             // 24.1 -> 25.1 ms per iteration.  The stream itself gains, but the partial sums going out and dlt coming in queue behind
             // the deeper request queue, and the hand-off loop is what bounds the sweep.)
-            if (u + 1 < nb) dma_quads(u + 1, H, NQ, base1);
+            if (u + 1 < nb) dma_quads(u + 1, H, NQD, base1);
             int n2 = 0;
             if (u + 2 < nb) n2 = dma_quads(u + 2, 0, H, base2);
             NGP_FINE(1);
-            wait_vmcnt_le(n2);  // everything up to the last quad of tile u+1 has landed
+            wait_vmcnt_le(n2);  // everything up to the last requested quad of tile u+1 has landed
             NGP_FINE(2);
             wg_barrier();
             if (!*sflag) return;
@@ -837,6 +854,7 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
         // ------------------------------ row-owning waves ------------------------------
         const int c = lane & 7, ql = lane >> 3;
         const int nqw = (NQ - wv + NGP_ROWS_NW - 1) / NGP_ROWS_NW;  // ring slots (quads / units) of this wave (wave-uniform)
+        const int nqg = DQ ? (direct ? nqw - KD : nqw) : nqw;       // of which the GEMV reads from the ring what the loader brought
         // fp32: the update task of this lane is quad wv + 7 ql.  Compact: task i is tau = ql + 8 i -> unit wv + 7 (tau >> 2), row quad
         // tau & 3 of that unit.  Idle lanes shadow a valid slot (nothing is stored).
         int tslot[NT], trow[NT];   // ring slot (relative to the tile) and first row of task i
@@ -879,6 +897,17 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
         // publisher: the stored, not yet counted partial (ring slot), counted once VM_CNT of this wave reads zero
         const double fxs = A.scal->fx_scale;
         auto try_signal = [&](bool) __attribute__((always_inline)) {};  // (nothing to count since the partial sums are atomic adds)
+        // direct quads of this wave: quads wv + 7 nqg (and + 7) of the tile after the one in use (timing mode 4 moves no tile bytes)
+        float4 dq0 = make_float4(0.f, 0.f, 0.f, 0.f), dq1 = dq0;
+        const bool direct_ld = direct && !(DBG && dbg_mode == 4);
+        auto direct_request = [&](const int tile) __attribute__((always_inline)) {
+            const char *g = (const char *)A.tiles + ((size_t)(A.t0 + tile) * S + s) * tile_bytes + (size_t)(wv + NGP_ROWS_NW * nqg) * 1024 + (size_t)lane * 16;
+            dq0 = *(const float4 *)g;
+            if constexpr (KD > 1) dq1 = *(const float4 *)(g + NGP_ROWS_NW * 1024);
+        };
+        if constexpr (DQ) {
+            if (direct_ld && nb > 0) direct_request(0);
+        }
         // the 64 partial dot products of block u: the 7 chains in their fixed tree (compact storage: minus m_j x the shard's sum of y)
         auto publish = [&](const int u) __attribute__((always_inline)) {
             const int slot = u % NGP_RING;
@@ -1000,7 +1029,7 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
                     // ---- GEMV chain of this wave: slots wv, wv+7, ... (lane = column); LDS serves a wave in order, so the
                     //      rows written above are read back without a barrier ----
                     double acc = 0.0;
-                    for (int k = 0; k < nqw; k++) {
+                    for (int k = 0; k < nqg; k++) {
                         const int q = wv + NGP_ROWS_NW * k;
                         if constexpr (U8) {
                             const uint4 x = *(const uint4 *)(ring + (size_t)wrap(base + q) * NGP_QS + (size_t)lane * 16);
@@ -1034,6 +1063,32 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
 #endif
                         }
                     }
+                    if constexpr (DQ) {
+                        if (direct) {
+                            // the chain's last KD quads: requested by this wave a block ago (the only wait for them is here), stored
+                            // where the delay-line fill below expects them, and fed to the chain as the ring's copy would have been
+                            ndirect += KD;
+#pragma unroll
+                            for (int i = 0; i < KD; i++) {
+                                const int q = wv + NGP_ROWS_NW * (nqg + i);
+                                const float4 x = i ? dq1 : dq0;
+                                *(float4 *)(ring + (size_t)wrap(base + q) * NGP_QS + (size_t)lane * 16) = x;
+#if NGP_ROWS_DPP
+                                const double xd[4] = {(double)x.x, (double)x.y, (double)x.z, (double)x.w};
+                                double yv[1] = {ys[4 * q + (lane & 3)]}, ac[1] = {acc};
+                                fmac4_bcast<1>(ac, yv, xd);
+                                acc = ac[0];
+#else
+                                const double *yq = ys + 4 * q;
+                                const double y0 = yq[0], y1 = yq[1], y2 = yq[2], y3 = yq[3];
+                                acc = __builtin_fma((double)x.x, y0, acc);
+                                acc = __builtin_fma((double)x.y, y1, acc);
+                                acc = __builtin_fma((double)x.z, y2, acc);
+                                acc = __builtin_fma((double)x.w, y3, acc);
+#endif
+                            }
+                        }
+                    }
                     red[((u & 1) * NGP_ROWS_NW + wv) * NGP_BLK + lane] = acc;
                     if (early) {
                         asm volatile("" ::: "memory");  // LDS serves a wave in order: the count follows the sum
@@ -1041,6 +1096,15 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
                     }
                     NGP_FINE(2);
                     try_signal(false);
+                    if constexpr (DQ) {
+                        // The next tile's direct quads, a block ahead of their use (their registers are free from here on).  Measured
+                        // at 50k x 600k against the parent's 47.3-47.8 it/s: here, every row wave, 48.3-48.9; behind
+                        // the publication (the publisher then waits for its atomic add's acknowledgement ahead of the barrier, the
+                        // compiler's wait in front of a register load being vmcnt(0)) 46.7; the publisher's and the poller's quads left
+                        // to the loader, 47.7-47.9.
+                        asm volatile("" ::: "memory");
+                        if (direct_ld && u + 1 < nb) direct_request(u + 1);
+                    }
                     // ---- tile u into the delay line (task view of the same slots) ----
                     if constexpr (U8) {
 #pragma unroll
@@ -1122,6 +1186,9 @@ __device__ __attribute__((always_inline)) inline void role_streamer_rows(const S
 #undef NGP_FINE
     __syncthreads();
     for (int i = tid; i < R; i += NGP_WG) yg[i] = ys[i];
+    if constexpr (DQ) {  // bits 40.. of the census entry this thread wrote at the head of the launch (ngp_get_census)
+        if (direct && A.census && tid == 0) A.census_tbl[1 + A.NG + s] += (unsigned long long)ndirect << 40;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2389,20 +2456,29 @@ __device__ __attribute__((always_inline)) inline bool sweep_census(const SweepAr
 // modes; every method); k_sweep_tup: the production kernel of models with a Tuple set (third translation unit)
 template <bool DBG>
 __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep(SweepArgs A) {
-    constexpr bool TUP = DBG;
+    constexpr bool TUP = DBG, DQV = DBG;
     constexpr int RCLSV = DBG ? 1 : 0;
 #include "ngp_sweep_body.inc"
 }
+#if defined(NGP_INST_DBG) && NGP_INST_DBG == 5
+// k_sweep<false> with the direct quads of the row-owning streamer over fp32 tiles (role_streamer_rows<.., DQ = true>): launched in its
+// place where the host offers them (fill_sweep_args).  A kernel and a translation unit of its own, so that k_sweep<false> keeps its text.
+__global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_dq(SweepArgs A) {
+    constexpr bool DBG = false, TUP = false, DQV = true;
+    constexpr int RCLSV = 0;
+#include "ngp_sweep_body.inc"
+}
+#endif
 #if defined(NGP_INST_DBG) && NGP_INST_DBG == 2
 __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_tup(SweepArgs A) {
-    constexpr bool DBG = false, TUP = true;
+    constexpr bool DBG = false, TUP = true, DQV = false;
     constexpr int RCLSV = 1;
 #include "ngp_sweep_body.inc"
 }
 #endif
 #if defined(NGP_INST_DBG) && NGP_INST_DBG == 3  // models with a BayesR set: its coefficients fetched one block ahead (fourth translation unit)
 __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_r(SweepArgs A) {
-    constexpr bool DBG = false, TUP = true;
+    constexpr bool DBG = false, TUP = true, DQV = false;
     constexpr int RCLSV = 2;
 #include "ngp_sweep_body.inc"
 }
@@ -2410,7 +2486,7 @@ __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #if defined(NGP_INST_DBG) && NGP_INST_DBG == 4  // models with a BayesRCpi set: the 64-wide rule of eval_rcform (fifth translation unit, so that
                                                 // the code of its sixteen-slot evaluation stands beside no other kernel's hot loop)
 __global__ __launch_bounds__(NGP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sweep_rc(SweepArgs A) {
-    constexpr bool DBG = false, TUP = true;
+    constexpr bool DBG = false, TUP = true, DQV = false;
     constexpr int RCLSV = 3;
 #include "ngp_sweep_body.inc"
 }

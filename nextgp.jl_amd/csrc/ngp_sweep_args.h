@@ -30,6 +30,10 @@
 #define NGP_KNOB_WARMER 4096   // bit 12, set by the host alone (fill_sweep_args): workgroup NG has no far lag and takes the warmer role if it shares the sampler's XCD
 #define NGP_KNOB_NO_WARMER 8192    // bit 13 (timing only): the host withholds the warmer role
 #define NGP_KNOB_WARMER_ANY_R 16384  // bit 14 (timing only): the host offers the role below NGP_WARMER_MIN_R rows per shard too
+#define NGP_KNOB_NO_DIRECT 32768     // bit 15 (timing only): the host withholds the direct quads of the row-owning streamer (role_streamer_rows)
+#define NGP_KNOB_DIRECT_ANY_R (1 << 28)  // bit 28 (timing and tests only; bits 16-27 name the diagnostic timeline's shard): the host offers them below NGP_DIRECT_MIN_R rows per shard too
+#define NGP_KNOB_DIRECT (1 << 29)    // bit 29, set by the host alone (fill_sweep_args): the row waves load the last quads of every fp32 tile themselves
+#define NGP_DIRECT_MIN_R 160         // shard height from which the host offers the direct quads
 #define NGP_WARMER_MIN_R 160       // shard height from which the warmer was measured to pay ("The warmer")
 
 namespace ngp {
@@ -96,6 +100,9 @@ struct SweepArgs {
 #define NGP_ROWS_HMAX 32
 #endif
 //   // quads of tile u+2 requested during block u (the counted wait keeps them in flight)
+#ifndef NGP_ROWS_DIRECT
+#define NGP_ROWS_DIRECT 1  // row-owning streamer, fp32 tiles: quads per row wave and tile that the wave loads itself (1 or 2; see role_streamer_rows, ngp_sweep.h; 2: k_sweep<true> spills 8 VGPRs)
+#endif
 #define NGP_ROWS_PUBW 2
 #define NGP_ROWS_POLLW 6
 #define NGP_DLS 72            // doubles per parity of the dlt buffer: 64 + the scalar of the compact update
@@ -151,12 +158,14 @@ __host__ __device__ inline size_t ngp_rows_multi_lds_bytes(int R, int K, bool u8
 //   3: r = k_sweep_r (models with a BayesR set), multi_r = k_sweep_multi_r
 //   4: rc = k_sweep_rc (models with a BayesRCpi set), tall_rc = k_sweep_tall_rc (such models, several shards per workgroup),
 //      multi_rc = k_sweep_multi_rc (K chains per pass of which any holds such a set)
+//   5: lean_dq = k_sweep_dq (the lean kernel whose row waves load the last quads of every fp32 tile themselves: NGP_KNOB_DIRECT)
 // The single-chain kernels take a SweepArgs, the multi ones a MultiArgs.
-enum class SweepKernel { lean, diag, tup, r, tall, multi, multi_tup, multi_r, rc, tall_rc, multi_rc };
+enum class SweepKernel { lean, diag, tup, r, tall, multi, multi_tup, multi_r, rc, tall_rc, multi_rc, lean_dq };
 const void *sweep_kernel_0(SweepKernel k);
 const void *sweep_kernel_1(SweepKernel k);
 const void *sweep_kernel_2(SweepKernel k);
 const void *sweep_kernel_3(SweepKernel k);
 const void *sweep_kernel_4(SweepKernel k);
+const void *sweep_kernel_5(SweepKernel k);
 
 }  // namespace ngp

@@ -1,5 +1,5 @@
 // ngp_sweep_body.inc -- body of the persistent sweep kernel, included into every instantiation (k_sweep<DBG>, k_sweep_tup) with the
-// compile-time flags DBG, TUP and RCLSV (role_sampler) in scope.  Text inclusion, not a common function: every kernel then reads its launch arguments as
+// compile-time flags DBG, TUP and RCLSV (role_sampler) and DQV (role_streamer_rows: direct quads) in scope.  Text inclusion, not a common function: every kernel then reads its launch arguments as
 // its own by-value parameter A (scalar loads from the kernarg segment), exactly as k_sweep always did -- handed on by reference to
 // a shared function, the register allocation of the row-owning streamer moved and 50k x 600k lost 1.7 %.
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -19,10 +19,10 @@
         const int s = b - 1 - A.NG;
         if (A.variant == 2) {  // row-owning waves + loader wave (host: R <= NGP_ROWS_MAX_R, lag 3..6)
             switch (A.D) {
-                case 3: role_streamer_rows<DBG, 3, 0>(A, s, smem); break;
-                case 4: role_streamer_rows<DBG, 4, 0>(A, s, smem); break;
-                case 5: role_streamer_rows<DBG, 5, 0>(A, s, smem); break;
-                default: role_streamer_rows<DBG, 6, 0>(A, s, smem); break;  // (lag 7 was built: 58 VGPRs of the delay line spill, 2.58 -> 3.08 us per block)
+                case 3: role_streamer_rows<DBG, 3, 0, DQV>(A, s, smem); break;
+                case 4: role_streamer_rows<DBG, 4, 0, DQV>(A, s, smem); break;
+                case 5: role_streamer_rows<DBG, 5, 0, DQV>(A, s, smem); break;
+                default: role_streamer_rows<DBG, 6, 0, DQV>(A, s, smem); break;  // (lag 7 was built: 58 VGPRs of the delay line spill, 2.58 -> 3.08 us per block)
             }
             return;
         }

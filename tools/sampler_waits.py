@@ -85,7 +85,7 @@ def main():
     lines = [l + "\n" for l in lines]
     ks = kernels(lines)
     if want is None:
-        want = {0: "k_sweepILb0", 1: "k_sweep_tall", 2: "k_sweep_tup", 3: "k_sweep_r"}[unit]
+        want = {0: "k_sweepILb0", 1: "k_sweep_tall", 2: "k_sweep_tup", 3: "k_sweep_r", 5: "k_sweep_dq"}[unit]
     for name, (lo, hi) in ks.items():
         if want not in name:
             continue
