@@ -651,6 +651,41 @@ int32_t ngp_set_holdout_state(ngp_handle *h, const double *yaug, const double *s
                               int64_t N);
 int32_t ngp_get_holdout_layout(ngp_handle *h, int64_t *m);
 
+/* ---- liability traits: binary and ordered classes (threshold / probit model), censored records (Tobit) ----
+ * A record with a liability stays in the panel.  Its latent liability l_i is redrawn at the head of every iteration of ngp_run /
+ * ngp_run_many from N(fitted_i, varE / w_i) truncated to the record's interval; in the residual, ycorr_i <- e_i, as for a held-out
+ * record ("Liability traits": the truncated-normal sampler, the threshold draw, the start values and the draw
+ * keys are normative).  Every engine runs unchanged.
+ * ngp_set_liability_classes: cls[N] in 1..C, 2 <= C <= 8; class c means t_{c-1} < l <= t_c with t_0 = -inf, t_1 = 0, t_C = +inf, the
+ *   thresholds between them drawn every iteration (C >= 3).  Entries of held-out rows are not read; every class needs a record that
+ *   is not held out (NGP_ERR_ARG).  The residual variance is then held at 1 (the probit scale) and ngp_set_y reads y at no row.
+ * ngp_set_liability_bounds: m strictly increasing rows, none held out, with lo < hi and at least one of them finite; ngp_set_y reads
+ *   y off these rows only; varE is sampled as usual.
+ * Both come after the panel (or ngp_set_records / ngp_share_panel) and the hold-out mask and before ngp_set_y (NGP_ERR_STATE once y
+ * is set); they exclude one another (NGP_ERR_STATE); NULL, 0 removes either.  A failed call leaves the handle as it was.
+ * ngp_get_liability_layout: m (0 without liabilities) and C (0 for bounds).  ngp_get_liability: rows[m], liab[m], and with classes
+ *   thr, sum_thr, sum_thr2 of C - 1 entries each: the thresholds t_1 .. t_{C-1} and the sums of them and of their squares over kept
+ *   iterations (any pointer may be NULL); ngp_set_liability_state puts them back (resume).
+ * ngp_get_liability_stats: draws whose rejection loop ran out of its 256 rounds (they return the midpoint or the finite bound);
+ *   0 in any sane chain.
+ * ngp_fix_residual_variance: v > 0 holds varE = v from ngp_set_y on (no draw, the trace reports v), v = 0 returns to sampling; with
+ *   classes only v = 1 is accepted.
+ * With liabilities the packed posterior appends sum_thr | sum_thr2 (classes) and snapshots carry the liabilities and thresholds
+ * (a snapshot is refused by a handle with other classes, other bounds or none); without them every format is byte for byte
+ * unchanged and nothing is launched.  The fine seam is not concerned: the caller owns ycorr there. */
+int32_t ngp_set_liability_classes(ngp_handle *h, const int32_t *cls, int32_t C);
+int32_t ngp_set_liability_bounds(ngp_handle *h, const int64_t *rows, const double *lo, const double *hi, int64_t m);
+int32_t ngp_get_liability_layout(ngp_handle *h, int64_t *m, int32_t *C);
+int32_t ngp_get_liability(ngp_handle *h, int64_t *rows, double *liab, double *thr, double *sum_thr, double *sum_thr2, int64_t m, int32_t C);
+int32_t ngp_set_liability_state(ngp_handle *h, const double *liab, const double *thr, const double *sum_thr, const double *sum_thr2, int64_t m,
+                                int32_t C);
+int32_t ngp_get_liability_stats(ngp_handle *h, int64_t *fallthrough);
+int32_t ngp_fix_residual_variance(ngp_handle *h, double v);
+/* Test probe of the truncated standard normal, beside ngp_draws_indexed: out[i] is the draw on the interval a[i] < z < b[i] (either
+ * bound may be infinite) of stream (seed,chain,iter,kind,index0+i). */
+int32_t ngp_tnormal_indexed(ngp_handle *h, uint64_t iter, uint64_t kind, uint64_t index0, const double *a, const double *b, int64_t n,
+                            double *out);
+
 #ifdef __cplusplus
 }
 #endif

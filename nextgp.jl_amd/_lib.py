@@ -17,27 +17,30 @@ LV_MAXCOV, LV_WORDS = 16, 17  # a BayesLV set in a sample record: c padded to 16
 
 
 def _sample_header(f, path):
-    """(P, nvb, nsets, nfix, nclass, record bytes, sets, random-effect q per set, (set, ncov) per BayesLV set) of an open sample file,
-    positioned at its first record."""
+    """(P, nvb, nsets, nfix, nclass, record bytes, sets, random-effect q per set, (set, ncov) per BayesLV set, thresholds per record) of an
+    open sample file, positioned at its first record."""
     magic = f.read(8)
-    if magic not in (b"NGPSMP01", b"NGPSMP02", b"NGPSMP03", b"NGPSMP04"):
+    if magic not in (b"NGPSMP01", b"NGPSMP02", b"NGPSMP03", b"NGPSMP04", b"NGPSMP05"):
         raise NextGPHipError(f"not a sample file: {path}")
     P, nvb, nsets, nfix, ncls, rec = (int(v) for v in np.frombuffer(f.read(48), dtype=np.int64))
     sets = [dict(zip(("method", "K", "col0", "ncol", "nvb", "tk"), np.frombuffer(f.read(48), dtype=np.int64).tolist())) for _ in range(nsets)]
     rq = []
-    if magic in (b"NGPSMP02", b"NGPSMP03", b"NGPSMP04"):  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
+    if magic in (b"NGPSMP02", b"NGPSMP03", b"NGPSMP04", b"NGPSMP05"):  # random-effect sets: int64 nrand | q per set; records hold u and varU behind b_fixed
         nr = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
         rq = np.frombuffer(f.read(8 * nr), dtype=np.int64).tolist()
     lv = []
-    if magic in (b"NGPSMP03", b"NGPSMP04"):  # BayesLV sets: int64 nlv | (marker set, ncov) per set; records hold c[16] | varZeta behind the class probabilities
+    if magic in (b"NGPSMP03", b"NGPSMP04", b"NGPSMP05"):  # BayesLV sets: int64 nlv | (marker set, ncov) per set; records hold c[16] | varZeta behind the class probabilities
         nl = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
         lv = [tuple(np.frombuffer(f.read(16), dtype=np.int64).tolist()) for _ in range(nl)]
-    if magic == b"NGPSMP04":  # BayesRCpi sets: int64 nrc | (marker set, A, K) per set; records hold annotProb[A][ncol] behind the BayesLV words
+    if magic in (b"NGPSMP04", b"NGPSMP05"):  # BayesRCpi sets: int64 nrc | (marker set, A, K) per set; records hold annotProb[A][ncol] behind the BayesLV words
         nrc = int(np.frombuffer(f.read(8), dtype=np.int64)[0])  # and annotCat[ncol] (uint8) behind delta.  They ride on the sets' entries.
         for _ in range(nrc):
             si, A, K = np.frombuffer(f.read(24), dtype=np.int64).tolist()
             sets[si].update(rcA=A, rcK=K)
-    return P, nvb, nsets, nfix, ncls, rec, sets, rq, lv
+    nthr = 0
+    if magic == b"NGPSMP05":  # C >= 3 liability classes: int64 nthr; records end with thr[nthr] (t_2 .. t_{C-1}) directly behind their bytes
+        nthr = int(np.frombuffer(f.read(8), dtype=np.int64)[0])
+    return P, nvb, nsets, nfix, ncls, rec, sets, rq, lv, nthr
 
 
 def _rand_qk(w):
@@ -83,7 +86,7 @@ def read_sample_file(path):
     lv_c=[[n, ncov] per BayesLV set], lv_varZeta[n, nlv]).  A correlated (Tuple) random-effect set of k components has u [n, q k] (the
     components of a level adjacent) and k k words in varU (row-major, in set order)."""
     with open(path, "rb") as f:
-        P, nvb, nsets, nfix, ncls, rec, sets, rq, lv = _sample_header(f, path)
+        P, nvb, nsets, nfix, ncls, rec, sets, rq, lv, nthr = _sample_header(f, path)
         raw = np.frombuffer(f.read(), dtype=np.uint8)
     n = len(raw) // rec
     raw = raw[:n * rec].reshape(n, rec)
@@ -95,6 +98,9 @@ def read_sample_file(path):
     if rcs:  # per BayesRCpi set, keyed by its marker set: annotProb [n, ncol, A], annotCat [n, ncol]
         out["annotProb"] = {si: d[:, o:o + A * nc].reshape(n, A, nc).transpose(0, 2, 1) for si, nc, A, o, _ in rcs}
         out["annotCat"] = {si: raw[:, nd * 8 + c:nd * 8 + c + nc] for si, nc, A, _, c in rcs}
+    if nthr:  # the thresholds t_2 .. t_{C-1} of every draw [n, nthr]
+        to = nd * 8 + P + sum(nc for _, nc, _, _, _ in rcs)
+        out["thr"] = raw[:, to:to + 8 * nthr].copy().view(np.float64)
     return out
 
 
@@ -103,7 +109,7 @@ def iter_sample_file(path):
     5 GB): yields dicts with the fields of read_sample_file for a single kept iteration.  Memory-mapped, nothing is copied but
     the record being looked at."""
     with open(path, "rb") as f:
-        P, nvb, nsets, nfix, ncls, rec, sets, rq, lv = _sample_header(f, path)
+        P, nvb, nsets, nfix, ncls, rec, sets, rq, lv, nthr = _sample_header(f, path)
         off = f.tell()
         size = os.fstat(f.fileno()).st_size
     n = (size - off) // rec
@@ -119,6 +125,9 @@ def iter_sample_file(path):
         if rcs:
             out["annotProb"] = {si: d[o:o + A * nc].reshape(A, nc).T for si, nc, A, o, _ in rcs}
             out["annotCat"] = {si: np.asarray(mm[i, nd * 8 + c:nd * 8 + c + nc]) for si, nc, A, _, c in rcs}
+        if nthr:
+            to = nd * 8 + P + sum(nc for _, nc, _, _, _ in rcs)
+            out["thr"] = np.frombuffer(mm[i, to:to + 8 * nthr].tobytes(), dtype=np.float64)
         yield out
     del mm
 
@@ -190,6 +199,8 @@ SYMBOLS = [
     "ngp_set_variance_windows", "ngp_enable_genomic_variance", "ngp_get_genomic_variance_layout", "ngp_get_genomic_variance",
     "ngp_set_genomic_variance", "ngp_get_genomic_variance_trace", "ngp_get_genomic_variance_stats",
     "ngp_set_holdout", "ngp_get_holdout", "ngp_set_holdout_state", "ngp_get_holdout_layout",
+    "ngp_set_liability_classes", "ngp_set_liability_bounds", "ngp_get_liability_layout", "ngp_get_liability", "ngp_set_liability_state",
+    "ngp_get_liability_stats", "ngp_fix_residual_variance", "ngp_tnormal_indexed",
 ]
 
 _lib = None
@@ -215,6 +226,62 @@ def holdout_summary(hs):
     mean = np.asarray(hs["sum_fit"])[rows] / n[rows]
     sd = np.sqrt(np.maximum(0.0, np.asarray(hs["sum_fit2"])[rows] / n[rows] - mean * mean))
     return dict(rows=rows.astype(np.int64), n=n[rows].astype(np.int64), mean=mean, sd=sd)
+
+
+LIABILITY_MAX_CLASSES = 8
+
+
+def check_classes(cls, N, C_=None):
+    """cls as the int32 vector ngp_set_liability_classes takes: N integers in 1..C, 2 <= C <= 8 (C_ or the largest class)."""
+    a = np.asarray(cls)
+    if a.shape != (N,):
+        raise ValueError(f"classes: one entry per record ({N})")
+    c = a.astype(np.int32)
+    if not np.array_equal(c, a):
+        raise ValueError("classes: integers 1..C")
+    nc = int(c.max()) if C_ is None else int(C_)
+    if nc < 2 or nc > LIABILITY_MAX_CLASSES:
+        raise ValueError(f"classes: between 2 and {LIABILITY_MAX_CLASSES} classes, not {nc}")
+    return np.ascontiguousarray(c)  # (the range 1..C is checked where the held-out rows, whose entries are not read, are known)
+
+
+def class_codes(y):
+    """Classes of a categorical response: the sorted distinct values of y become 1..C; a NaN (a record without a response) gets 0.
+    Returns (codes int32, the distinct values)."""
+    y = np.asarray(y, dtype=np.float64)
+    obs = ~np.isnan(y)
+    vals = np.unique(y[obs])
+    if len(vals) < 2 or len(vals) > LIABILITY_MAX_CLASSES:
+        raise ValueError(f'trait="categorical": the response takes {len(vals)} distinct values; between 2 and {LIABILITY_MAX_CLASSES} classes are supported')
+    codes = np.zeros(len(y), dtype=np.int32)
+    codes[obs] = np.searchsorted(vals, y[obs]) + 1
+    return codes, vals
+
+
+def check_bounds(rows, lo, hi, N):
+    """(rows int64, lo, hi) as ngp_set_liability_bounds takes them: strictly increasing rows in [0, N), lo < hi, one of them finite."""
+    r = np.ascontiguousarray(rows, dtype=np.int64)
+    lo = np.ascontiguousarray(lo, dtype=np.float64); hi = np.ascontiguousarray(hi, dtype=np.float64)
+    if r.ndim != 1 or len(r) == 0 or lo.shape != r.shape or hi.shape != r.shape:
+        raise ValueError("censored records: rows, lo and hi are non-empty vectors of one length")
+    if r[0] < 0 or r[-1] >= N or np.any(np.diff(r) <= 0):
+        raise ValueError(f"censored records: rows strictly increasing in 0..{N - 1}")
+    if not np.all(lo < hi) or np.any(~np.isfinite(lo) & ~np.isfinite(hi)):
+        raise ValueError("censored records: lo < hi, at least one of them finite")
+    return r, lo, hi
+
+
+def censored_bounds(lower, upper):
+    """runLMEM(censored={"lower", "upper"}): (rows, lo, hi) of the censored records.  A record with lower == upper is exact (not
+    listed); NaN or an infinity means open on that side; a record open on both sides, or with lower > upper, raises ValueError."""
+    lo = np.asarray(lower, dtype=np.float64).copy(); hi = np.asarray(upper, dtype=np.float64).copy()
+    if lo.ndim != 1 or lo.shape != hi.shape:
+        raise ValueError("censored: lower and upper have one entry per record")
+    lo[np.isnan(lo)] = -np.inf; hi[np.isnan(hi)] = np.inf
+    if np.any(lo > hi) or np.any(np.isinf(lo) & np.isinf(hi)):
+        raise ValueError("censored: lower <= upper, and at least one of them finite, at every record")
+    rows = np.flatnonzero(lo < hi).astype(np.int64)
+    return rows, lo[rows], hi[rows]
 
 
 def deal_folds(y, folds, foldSeed=1):
@@ -998,6 +1065,64 @@ class Sampler:
         {"rows", "n", "mean", "sd"}; after allreduce_posterior over fold-chains, of every validated record."""
         return holdout_summary(self.holdout_state())
 
+    # ---- liability traits: binary / ordered classes, censored records ---------------------
+    def set_classes(self, cls, C_=None):
+        """Threshold (probit) trait: cls[N] in 1..C, 2 <= C <= 8 (C defaults to the largest class).  After the panel and the hold-out
+        mask, before set_y, which then reads y nowhere; entries of held-out rows are not read.  The residual variance is held at 1.
+        None removes the classes."""
+        if cls is None:
+            self._chk(self.L.ngp_set_liability_classes(self.h, None, C.c_int32(0)))
+            return
+        c = check_classes(cls, self.N, C_)
+        self._chk(self.L.ngp_set_liability_classes(self.h, _p(c, C.c_int32), C.c_int32(int(c.max()) if C_ is None else int(C_))))
+
+    def set_censored(self, rows, lo, hi):
+        """Censored (Tobit) records: the response of record rows[k] is only known to lie in (lo[k], hi[k]), lo < hi, one of them
+        possibly infinite.  rows 0-based and strictly increasing, none held out; after the panel and the hold-out mask, before set_y,
+        which reads y off these rows only.  rows=None removes the bounds."""
+        if rows is None:
+            self._chk(self.L.ngp_set_liability_bounds(self.h, None, None, None, C.c_int64(0)))
+            return
+        r, lo, hi = check_bounds(rows, lo, hi, self.N)
+        self._chk(self.L.ngp_set_liability_bounds(self.h, _p(r, C.c_int64), _p(lo, C.c_double), _p(hi, C.c_double), C.c_int64(len(r))))
+
+    def liability_layout(self):
+        """(m, C): the augmented records (0 without liabilities) and the classes (0 for censored records)."""
+        m = C.c_int64(); c = C.c_int32()
+        self._chk(self.L.ngp_get_liability_layout(self.h, C.byref(m), C.byref(c)))
+        return m.value, c.value
+
+    def liability_state(self):
+        """{"rows", "liab" (m entries), "thr", "sum_thr", "sum_thr2" (the C - 1 thresholds t_1 .. t_{C-1}, t_1 = 0, and their sums over
+        kept iterations; empty for censored records)} of a chain with liabilities."""
+        m, c = self.liability_layout()
+        nt = max(c - 1, 0)
+        r = np.empty(m, dtype=np.int64); l = np.empty(m)
+        t = np.empty(nt); s1 = np.empty(nt); s2 = np.empty(nt)
+        self._chk(self.L.ngp_get_liability(self.h, _p(r, C.c_int64), _p(l, C.c_double), _p(t, C.c_double), _p(s1, C.c_double), _p(s2, C.c_double),
+                                           C.c_int64(m), C.c_int32(c)))
+        return dict(rows=r, liab=l, thr=t, sum_thr=s1, sum_thr2=s2)
+
+    def set_liability_state(self, ls):
+        """Put back what liability_state() gave (resume beside set_state / set_posterior_sums); a missing key leaves that array as it is."""
+        a = {k: (None if ls.get(k) is None else np.ascontiguousarray(ls[k], dtype=np.float64)) for k in ("liab", "thr", "sum_thr", "sum_thr2")}
+        m, c = self.liability_layout()
+        for k, n in (("liab", m), ("thr", max(c - 1, 0)), ("sum_thr", max(c - 1, 0)), ("sum_thr2", max(c - 1, 0))):
+            if a[k] is not None and a[k].shape != (n,):
+                raise ValueError(f"set_liability_state: {k} must have {n} entries")
+        self._chk(self.L.ngp_set_liability_state(self.h, _p(a["liab"], C.c_double), _p(a["thr"], C.c_double), _p(a["sum_thr"], C.c_double),
+                                                 _p(a["sum_thr2"], C.c_double), C.c_int64(m), C.c_int32(c)))
+
+    def liability_fallthrough(self):
+        """Truncated-normal draws of this handle whose rejection loop ran out of rounds (0 in any sane chain)."""
+        n = C.c_int64()
+        self._chk(self.L.ngp_get_liability_stats(self.h, C.byref(n)))
+        return n.value
+
+    def fix_residual_variance(self, v):
+        """v > 0 holds varE = v from set_y on (no draw; the trace reports v); 0 returns to sampling."""
+        self._chk(self.L.ngp_fix_residual_variance(self.h, C.c_double(float(v))))
+
     def set_residual_prior(self, df, scale):
         self._chk(self.L.ngp_set_residual_prior(self.h, C.c_double(df), C.c_double(scale)))
 
@@ -1169,6 +1294,16 @@ class Sampler:
         out = np.empty(n)
         self._chk(self.L.ngp_draws_indexed(self.h, C.c_uint64(it), C.c_uint64(kind), C.c_uint64(index0), C.c_int32(what),
                                            C.c_double(p1), C.c_double(p2), C.c_int64(n), _p(out, C.c_double)))
+        return out
+
+    def tnormal_indexed(self, it, kind, index0, a, b):
+        """Truncated standard normals: draw i on (a[i], b[i]) from stream (seed, chain, it, kind, index0 + i)."""
+        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("tnormal_indexed: a and b are vectors of one length")
+        out = np.empty(len(a))
+        self._chk(self.L.ngp_tnormal_indexed(self.h, C.c_uint64(it), C.c_uint64(kind), C.c_uint64(index0), _p(a, C.c_double), _p(b, C.c_double),
+                                             C.c_int64(len(a)), _p(out, C.c_double)))
         return out
 
     def eval_math(self, which, x):

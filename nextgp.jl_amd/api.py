@@ -698,6 +698,8 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
                 row(f"var{s['name']}", _fmt(S["varBeta"][vb_off:vb_off + s["nvb"]]))
                 vb_off += s["nvb"]
                 cls_off += K
+            if "thr" in S:                                    # an ordered trait of C >= 3 classes: t_2 .. t_{C-1} of this draw
+                row("threshold", _fmt(S["thr"]))
     finally:
         for f in handles.values():
             f.close()
@@ -710,7 +712,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1):
+            foldSeed=1, trait="gaussian", censored=None):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -759,6 +761,17 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     chain c holding out fold c.  res["cv"] = {"fold", "yhat", "sd" (N entries, NaN where not validated), "accuracy" (Pearson correlation
     of yhat and y), "slope" (regression of y on yhat), "mse", "per_fold", "pooled_over_folds": True -- the returned marker means are
     pooled over the fold-chains}, and cvPredict.txt holds record fold y yhat sd.  folds= with chains= or holdout= raises ValueError.
+    (11) liability traits (ngp_set_liability_classes / ngp_set_liability_bounds; DESIGN.md section 2, "Liability traits").
+    trait="categorical": a threshold (probit) model -- the sorted distinct values of the response become the classes 1..C (2..8), the
+    latent liability of every record is redrawn each iteration, the residual variance is 1 (VCV["e"], if given, must have the value 1,
+    else ValueError; varEOut is all ones), the thresholds t_2 .. t_{C-1} are drawn for C >= 3 (t_1 = 0): res["thresholds"] = {"mean",
+    "sd"} (empty for two classes), pooled over the chains, res["classes"] the response value of every class.  Effects, predict=,
+    holdout=, missing= and folds= work as they are and report on the LIABILITY scale (res["cv"]'s accuracy then compares liabilities
+    with class values: a rank measure only).  censored={"lower": column or array, "upper": column or array}: a Tobit model -- a record
+    with lower == upper is exact and takes that value, NaN or an infinity means open on that side, and the response column is ignored on
+    the censored records; varE is sampled as usual.  The two exclude one another.  With samples="text" and C >= 3 thresholdOut holds the
+    thresholds of every kept draw (columns t2 .. t{C-1}; per chain under chain<c>/ with chains=K); its column means are res["thresholds"]["mean"]
+    (the text round-trips every double).
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -770,7 +783,14 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     if not snps and not parsed.ped:
         raise ValueError("the accelerated path needs at least one SNP(...) term")
     y = np.asarray(userData[lhs], dtype=np.float64)
+    liab = _liability_spec(trait, censored, y, userData, VCV)   # (checked before any device work)
+    if liab is not None and liab["kind"] == "bounds":          # exact records take their value; the censored ones are not read
+        y = liab["y"]
     masks, cv_fold, chains = _holdout_masks(y, holdout, missing, folds, foldSeed, chains)   # (checked before any device work)
+    if liab is not None and liab["kind"] == "classes" and missing != "holdout" and np.any(liab["codes"] == 0):
+        raise ValueError('trait="categorical": a record has no response (NaN); missing="holdout" predicts such records')
+    if liab is not None and liab["kind"] == "bounds" and masks is not None and any(len(np.intersect1d(m, liab["rows"])) for m in masks):
+        raise ValueError("censored: a censored record cannot be held out as well (holdout=, folds=); records without any bound are missing records")
     ped = None
     if has_ped:   # makePed (src/misc.jl:98-115) once for all PED terms and all chains
         ids = []
@@ -904,6 +924,12 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     if masks is not None:   # every chain sets its own mask (a chain that shares the panel does not inherit one), in front of set_y
         for sc, rows in zip(samplers, masks):
             sc.set_holdout(rows)
+    if liab is not None:    # behind the mask (held-out records carry no liability) and in front of set_y
+        for sc in samplers:
+            if liab["kind"] == "classes":
+                sc.set_classes(np.maximum(liab["codes"], 1), liab["C"])   # (a record without a response is held out: its entry is not read)
+            else:
+                sc.set_censored(liab["rows"], liab["lo"], liab["hi"])
     built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
                           gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0], ped=ped)
              for sc in samplers]
@@ -918,6 +944,9 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     folders = [outFolder] if K == 1 else [os.path.join(outFolder, f"chain{chain + c}") for c in range(K)]
     for f in folders:
         os.makedirs(f, exist_ok=True)
+    if liab is not None and liab["kind"] == "classes" and liab["C"] >= 3 and samples == "text":   # header row of thresholdOut
+        for f in folders:
+            _out(f, "threshold", [f"t{c}" for c in range(2, liab["C"])])
     res = _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
     if pmats is not None:
         ids = [str(i + 1) for i in range(pmats[0].shape[0])] if predict_ids is None else [str(a) for a in predict_ids]
@@ -930,6 +959,12 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         write_prediction_file(os.path.join(outFolder, "gebvPredict.txt"), res["predict"])
     if masks is not None:
         _holdout_results(res, samplers, masks, cv_fold, y, outFolder)
+    if liab is not None and liab["kind"] == "classes":
+        states = [sc.liability_state() for sc in samplers]
+        for r, ls in zip(res.get("chains", []), states):
+            r["thresholds"] = _threshold_summary(ls["sum_thr"], ls["sum_thr2"], r["nKept"])
+        res["thresholds"] = _threshold_summary(sum(ls["sum_thr"] for ls in states), sum(ls["sum_thr2"] for ls in states), res["nKept"])
+        res["classes"] = liab["values"]
     if gv_windows is not None:
         by_id = sorted(sets, key=lambda st: st["id"])                       # slot order: the device's set order
         names = [st["name"] for st in by_id]
@@ -946,6 +981,42 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         res["variance"] = _variance_result(pooled, names, wins, float(windowThreshold))
         write_gwas_files(outFolder, res["variance"])
     return res
+
+
+def _liability_spec(trait, censored, y, userData, VCV):
+    """runLMEM(trait=..., censored=...): None, or {"kind": "classes", "codes", "C", "values"} / {"kind": "bounds", "rows", "lo", "hi", "y"}.
+    Host checks only; a ValueError here comes before any device work."""
+    from ._lib import censored_bounds, class_codes
+    if trait not in ("gaussian", "categorical"):
+        raise ValueError('trait: "gaussian" or "categorical"')
+    if trait == "categorical":
+        if censored is not None:
+            raise ValueError('trait="categorical" together with censored=: a record is a class or a censored value, not both')
+        e = VCV.get("e")
+        if e is not None and not (np.ndim(e.v) == 0 and e.v == 1.0):
+            raise ValueError('trait="categorical": the residual variance of the probit scale is 1; VCV["e"] must have the value 1 (or be left out)')
+        codes, values = class_codes(y)
+        return dict(kind="classes", codes=codes, C=len(values), values=values)
+    if censored is None:
+        return None
+    if not isinstance(censored, dict) or set(censored) != {"lower", "upper"}:
+        raise ValueError('censored: {"lower": column or array, "upper": column or array}')
+    lower, upper = (np.asarray(userData[censored[k]] if isinstance(censored[k], str) else censored[k], dtype=np.float64) for k in ("lower", "upper"))
+    if lower.shape != y.shape or upper.shape != y.shape:
+        raise ValueError("censored: lower and upper have one entry per record")
+    rows, lo, hi = censored_bounds(lower, upper)
+    if len(rows) == 0:
+        raise ValueError("censored: no record is censored (lower == upper everywhere)")
+    ye = np.where(np.isnan(lower) | np.isinf(lower), upper, lower).astype(np.float64)   # exact records: lower == upper
+    ye[rows] = 0.0                                                                     # (not read on the censored records)
+    return dict(kind="bounds", rows=rows, lo=lo, hi=hi, y=ye)
+
+
+def _threshold_summary(sum_thr, sum_thr2, nKept):
+    """Mean and SD of the thresholds t_2 .. t_{C-1} over the kept draws (t_1 = 0 is not listed)."""
+    n = max(int(nKept), 1)
+    mean = np.asarray(sum_thr)[1:] / n
+    return dict(mean=mean, sd=np.sqrt(np.maximum(0.0, np.asarray(sum_thr2)[1:] / n - mean * mean)))
 
 
 def _holdout_masks(y, holdout, missing, folds, foldSeed, chains):

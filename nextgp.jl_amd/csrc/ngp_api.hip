@@ -34,6 +34,7 @@
 #include "ngp_logvar.h"
 #include "ngp_predict.h"
 #include "ngp_holdout.h"
+#include "ngp_liability.h"
 #include "ngp_genvar.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
@@ -449,9 +450,26 @@ struct GenVar {
     int64_t launches = 0, served = 0;       // ngp_get_genomic_variance_stats
 };
 
+// Liability traits (ngp_liability.h; ngp_set_liability_classes / ngp_set_liability_bounds): the augmented rows with their classes
+// (C >= 2) or bounds (C == 0) on the host and on the device, the liability of each, and d_thr = thr[C+1] | sum_thr[C+1] |
+// sum_thr2[C+1] (thr[0] = -inf, thr[1] = 0, thr[C] = +inf; the sums are used at 2 .. C-1); all empty for a chain without them
+struct Liab {
+    std::vector<long long> rows;
+    std::vector<int> cls;
+    std::vector<double> lo, hi;
+    int C = 0;
+    uint64_t digest = 0;  // of rows, C and classes or bounds (snapshot signature)
+    DevArray<long long> d_rows;
+    DevArray<int> d_cls;
+    DevArray<double> d_lo, d_hi, d_liab, d_thr;
+    bool on() const { return !rows.empty(); }
+    size_t thr_bytes() const { return C >= 2 ? (size_t)(C - 1) * 8 : 0; }  // t_1 .. t_{C-1}, as the formats carry them
+};
+
 // The chain's arrays on one panel (sized by its N, P and plan): allocated whole by alloc_panel, dropped whole with the panel
 struct ChainMem {
     GenVar gv;
+    Liab lb;
     DevArray<double> d_lhs0, d_rhs0, d_beta, d_c, d_w, d_q, d_T, d_chi;
     DevArray<int8_t> d_setof;
     DevArray<int32_t> d_loc, d_vbidx;
@@ -530,6 +548,7 @@ struct HandleMem {
     DevArray<double> d_tr_varE, d_tr_b;  // varE / b traces of the last run
     int64_t trace_cap = 0;               // iterations they were allocated for
     DevArray<unsigned long long> d_dbg;  // time stamps (ngp_debug_stamps)
+    DevArray<unsigned long long> d_tn_fall;  // truncated-normal draws whose loop ran out (ngp_get_liability_stats); allocated on first use
 };
 
 }  // namespace
@@ -572,6 +591,7 @@ struct ngp_handle {
     std::vector<int32_t> h_loc, h_vbidx;
     int64_t nvb = 0;
     double e_df = 4.0, e_scale = 0.0005;
+    double fix_varE = 0.0;  // ngp_fix_residual_variance: > 0 holds varE at this value (k_head draws none), 0 samples it
     // weighted residuals (ngp_set_residual_weights, E.str == "D"): w as given (empty = unweighted) and their sum (index order); the
     // row scales on the device are cm.d_rs
     std::vector<double> h_rw;
@@ -707,6 +727,7 @@ int DevArray<T>::alloc(ngp_handle *h, size_t n) {
 // random-effect sets hold rows of the old N, the trace selection loci of the old P) and what a failed one leaves behind
 void drop_panel(ngp_handle *h) {
     h->pm.reset();  // (handles that share the old panel keep it alive)
+    if (h->cm.lb.C > 0) h->fix_varE = 0.0;  // (the classes that fixed varE at 1 go with the panel)
     h->cm = ChainMem();
     h->mm = ModelMem();
     h->sets.clear(); h->nvb = 0; h->nclass_total = 0; h->ntuple = 0;
@@ -1578,11 +1599,21 @@ int launch_genvar(ngp_handle *lead, ngp_handle **hs, int n) {
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
+    if (const long long m = (long long)h->cm.lb.rows.size()) {  // liability traits: thresholds (C >= 3), then every liability (ycorr_i <- e_i)
+        const Liab &lb = h->cm.lb;
+        const int C1 = lb.C + 1;
+        if (lb.C >= 3)
+            hipLaunchKernelGGL(k_thresholds, dim3(1), dim3(1024), 0, h->stream, (const int *)lb.d_cls.get(), (const double *)lb.d_liab.get(), m, lb.C, lb.d_thr.get(),
+                               lb.d_thr.get() + C1, lb.d_thr.get() + 2 * C1, (int)is_kept(h, h->iter + 1), h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
+        hipLaunchKernelGGL(k_liability_augment, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)lb.d_rows.get(), m, h->cm.d_ycorr.get(),
+                           lb.d_liab.get(), (const double *)lb.d_lo.get(), (const double *)lb.d_hi.get(), (const int *)lb.d_cls.get(), (const double *)lb.d_thr.get(),
+                           (const double *)h->cm.d_rs, (const DScal *)h->cm.d_scal, h->seed, (uint64_t)h->chain, it, h->hm.d_tn_fall.get(), (const unsigned *)h->cm.d_abort);
+    }
     if (const long long m = (long long)h->cm.ho_rows.size())  // held-out records: their phenotypes are redrawn first (ycorr_i <- e_i)
         hipLaunchKernelGGL(k_holdout_augment, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)h->cm.d_ho_rows, m, h->cm.d_ycorr.get(),
                            h->cm.d_yaug.get(), (const double *)h->cm.d_rs, (const DScal *)h->cm.d_scal, h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
     hipLaunchKernelGGL(k_head, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->L, (long long)h->N, h->cm.d_scal, h->e_df,
-                       h->e_scale, h->intercept, 1, h->seed, (uint64_t)h->chain, it, h->hm.d_tr_varE, h->hm.d_tr_b, (long long)trace_idx, h->cm.d_abort, h->pm->mpm_max,
+                       h->e_scale, h->intercept, h->fix_varE > 0.0 ? 0 : 1, h->seed, (uint64_t)h->chain, it, h->hm.d_tr_varE, h->hm.d_tr_b, (long long)trace_idx, h->cm.d_abort, h->pm->mpm_max,
                        (const double *)h->cm.d_rs, h->sum_w);
     for (size_t f = 0; f < h->mm.fix.size(); f++)  // the other fixed-effect sets, in the order they were added (src/samplers.jl:39-41)
         hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->N, h->mm.fix[f].d_X, (int)h->mm.fix[f].ncol, h->mm.fix[f].d_xpx0,
@@ -1698,6 +1729,64 @@ int set_class_state_dev(ngp_handle *h, int si, int K, const double *pi, const do
     return NGP_OK;
 }
 
+// ---- liability traits (ngp_liability.h) ----
+// the counter of truncated-normal draws that ran out of rounds: one word of the handle, allocated (zeroed) on first use
+int ensure_tn_fall(ngp_handle *h) {
+    return h->hm.d_tn_fall ? NGP_OK : h->hm.d_tn_fall.alloc(h, 1);
+}
+uint64_t liab_digest(const Liab &lb) {  // FNV-1a over the rows, C and the classes or bounds
+    uint64_t d = 1469598103934665603ull;
+    auto eat = [&d](const void *p, size_t n) { for (size_t i = 0; i < n; i++) { d ^= ((const unsigned char *)p)[i]; d *= 1099511628211ull; } };
+    eat(lb.rows.data(), lb.rows.size() * sizeof(long long));
+    eat(&lb.C, sizeof lb.C);
+    eat(lb.cls.data(), lb.cls.size() * sizeof(int));
+    eat(lb.lo.data(), lb.lo.size() * 8); eat(lb.hi.data(), lb.hi.size() * 8);
+    return d;
+}
+// Start values (ngp_set_y; DESIGN.md section 2, "Liability traits").  Classes: t_c = ppnd16(F_c) - ppnd16(F_1) with F_c the cumulative
+// class frequency over the augmented rows (ppnd16 on the device: the draw layer's own), the liability the midpoint of an inner
+// interval, t_1 - 0.5 in class 1, t_{C-1} + 0.5 in class C.  Bounds: the finite bound where only one is, else the midpoint.  y_out: y
+// with the liability on every augmented row (classes: 0 elsewhere -- y is not read); left empty for a chain without liabilities.
+int start_liabilities(ngp_handle *h, const double *y, std::vector<double> &y_out) {
+    Liab &lb = h->cm.lb;
+    if (!lb.on()) return NGP_OK;
+    int rc;
+    const size_t m = lb.rows.size(), C1 = (size_t)lb.C + 1;
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> l0(m), thr(3 * C1, 0.0);
+    if (lb.C >= 2) {
+        const int C = lb.C;
+        std::vector<long long> cnt((size_t)C + 1, 0);
+        for (int c : lb.cls) cnt[(size_t)c] += 1;
+        std::vector<double> F((size_t)C - 1), q((size_t)C - 1);
+        long long cum = 0;
+        for (int c = 1; c < C; c++) { cum += cnt[(size_t)c]; F[(size_t)c - 1] = (double)cum / (double)m; }
+        DevArray<double> di, dq;
+        if ((rc = di.alloc(h, F.size())) || (rc = dq.alloc(h, F.size()))) return rc;
+        HCHK(hipMemcpyAsync(di, F.data(), F.size() * 8, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_eval_math, dim3(1), dim3(64), 0, h->stream, 1, (const double *)di.get(), (long long)F.size(), dq.get());
+        HCHK(hipMemcpyAsync(q.data(), dq, q.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));
+        thr[0] = -inf; thr[(size_t)C] = inf;
+        for (int c = 1; c < C; c++) thr[(size_t)c] = q[(size_t)c - 1] - q[0];
+        for (size_t k = 0; k < m; k++) {
+            const int c = lb.cls[k];
+            l0[k] = c == 1 ? thr[1] - 0.5 : c == C ? thr[(size_t)C - 1] + 0.5 : (thr[(size_t)c - 1] + thr[(size_t)c]) / 2.0;
+        }
+        y_out.assign((size_t)h->N, 0.0);
+        HCHK(hipMemcpy(lb.d_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice));
+    } else {
+        for (size_t k = 0; k < m; k++) {
+            const bool fl = std::isfinite(lb.lo[k]), fh = std::isfinite(lb.hi[k]);
+            l0[k] = (fl && fh) ? (lb.lo[k] + lb.hi[k]) / 2.0 : fl ? lb.lo[k] : lb.hi[k];
+        }
+        y_out.assign(y, y + h->N);
+    }
+    for (size_t k = 0; k < m; k++) y_out[(size_t)lb.rows[k]] = l0[k];
+    HCHK(hipMemcpy(lb.d_liab, l0.data(), m * 8, hipMemcpyHostToDevice));
+    return NGP_OK;
+}
+
 // ---- the chain's state as segments (ngp_state.h: the segment ids, the three layouts, the formats) ----
 // every segment of h's chain.  No device access: the staged words (st.ds, st.sc) are filled by stage()
 void describe(ngp_handle *h, ChainState &st) {
@@ -1740,6 +1829,16 @@ void describe(ngp_handle *h, ChainState &st) {
         const size_t N8 = (size_t)h->N * 8;
         st.dev(SEG_YAUG, 0, h->cm.d_yaug, h->cm.ho_rows.size() * 8);
         st.dev(SEG_SUM_FIT, 0, h->cm.d_sum_fit, N8); st.dev(SEG_SUM_FIT2, 0, h->cm.d_sum_fit2, N8); st.dev(SEG_N_FIT, 0, h->cm.d_n_fit, N8);
+    }
+    if (h->cm.lb.on()) {  // liability traits: only a chain that has them; the thresholds t_1 .. t_{C-1} and their sums only with classes
+        const Liab &lb = h->cm.lb;
+        st.dev(SEG_LIAB, 0, lb.d_liab, lb.rows.size() * 8);
+        if (lb.C >= 2) {
+            const size_t C1 = (size_t)lb.C + 1;
+            st.dev(SEG_THR, 0, lb.d_thr + 1, lb.thr_bytes());
+            st.dev(SEG_SUM_THR, 0, lb.d_thr + C1 + 1, lb.thr_bytes()); st.dev(SEG_SUM_THR2, 0, lb.d_thr + 2 * C1 + 1, lb.thr_bytes());
+            if (lb.C >= 3) st.dev(SEG_THR_SMP, 0, lb.d_thr + 2, (size_t)(lb.C - 2) * 8);  // the drawn thresholds: what a sample record carries
+        }
     }
 }
 static_assert(offsetof(DSet, piHat1) == offsetof(DSet, piHat0) + 8 && offsetof(DSet, sum_pi1) == offsetof(DSet, sum_pi0) + 8, "SEG_PI / SEG_SUM_PI");
@@ -1828,9 +1927,10 @@ int sample_enqueue(ngp_handle *h) {
         }
         const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->mm.nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
         // (the header, by magic: ngp_state.h)
-        const bool has_rc = !h->mm.rc.empty();
+        const bool has_thr = h->cm.lb.C >= 3;               // (05 holds the parts of 04, also when empty)
+        const bool has_rc = !h->mm.rc.empty() || has_thr;
         const bool has_lv = !h->mm.lv.empty() || has_rc;  // (04 holds the parts of 03, also when empty)
-        bool ok = std::fwrite(has_rc ? "NGPSMP04" : has_lv ? "NGPSMP03" : h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
+        bool ok = std::fwrite(has_thr ? "NGPSMP05" : has_rc ? "NGPSMP04" : has_lv ? "NGPSMP03" : h->mm.rnd.empty() ? "NGPSMP01" : "NGPSMP02", 1, 8, S->f.get()) == 8 && std::fwrite(hd, sizeof(hd), 1, S->f.get()) == 1;
         for (auto &hs : h->sets) { const int64_t sg[6] = {hs.method, hs.K, hs.col0, hs.ncol, (int64_t)hs.vb0.size(), hs.tk}; ok = ok && std::fwrite(sg, sizeof(sg), 1, S->f.get()) == 1; }
         if (!h->mm.rnd.empty() || has_lv) {
             const int64_t nr = (int64_t)h->mm.rnd.size();
@@ -1846,6 +1946,10 @@ int sample_enqueue(ngp_handle *h) {
             const int64_t nrc = (int64_t)h->mm.rc.size();
             ok = ok && std::fwrite(&nrc, 8, 1, S->f.get()) == 1;
             for (auto &Rc : h->mm.rc) { const int64_t rg[3] = {Rc.set, Rc.A, Rc.Kc}; ok = ok && std::fwrite(rg, sizeof(rg), 1, S->f.get()) == 1; }
+        }
+        if (has_thr) {
+            const int64_t nthr = h->cm.lb.C - 2;
+            ok = ok && std::fwrite(&nthr, 8, 1, S->f.get()) == 1;
         }
         if (!ok) return fail(h, NGP_ERR_ARG, "cannot write the sample file header: " + S->path);
         S->header_written = true;
@@ -1870,7 +1974,7 @@ int sample_enqueue(ngp_handle *h) {
                        h->cm.d_scal, h->mm.d_bfix, h->cm.d_abort);
     hipError_t e = hipSuccess;
     for (auto &a : pl.at)
-        if (e == hipSuccess && (a.s->id == SEG_U || a.s->id == SEG_VARU || a.s->id == SEG_LV || a.s->id == SEG_RC_PROB || a.s->id == SEG_RC_CAT))
+        if (e == hipSuccess && (a.s->id == SEG_U || a.s->id == SEG_VARU || a.s->id == SEG_LV || a.s->id == SEG_RC_PROB || a.s->id == SEG_RC_CAT || a.s->id == SEG_THR_SMP))
             e = hipMemcpyAsync(S->d_slot[slot].get() + a.off, a.s->p, a.s->bytes, hipMemcpyDeviceToDevice, h->stream);
     // (a HIP call that fails here gives the slot back: the next enqueue would otherwise wait for it forever instead of reporting)
     if (e == hipSuccess) e = hipEventRecord(S->ev_packed[slot], h->stream);
@@ -2161,7 +2265,8 @@ int ready(ngp_handle *h) {
     REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: ngp_end_panel builds the Gram window the sweep needs");
     REQUIRE(h->have_y, NGP_ERR_STATE, "y not set");
     // (a records-only handle with a hold-out set may be the intercept-only model y = b + e: the closed-form case of the augmentation step)
-    if (h->records_only) REQUIRE(!h->mm.rnd.empty() || (h->intercept && !h->cm.ho_rows.empty()), NGP_ERR_STATE,
+    // (... and so may one with liability traits: the intercept-only probit and Tobit models)
+    if (h->records_only) REQUIRE(!h->mm.rnd.empty() || (h->intercept && (!h->cm.ho_rows.empty() || h->cm.lb.on())), NGP_ERR_STATE,
                                  "no random-effect set added (a handle made by ngp_set_records has no marker sets)");
     else REQUIRE(!h->sets.empty(), NGP_ERR_STATE, "no marker set added");
     int rc;
@@ -2318,6 +2423,8 @@ struct PanelHeader { char magic[8]; int64_t N, P; int32_t bits, zero; };
 #define NGP_SNAP_WEIGHTED ((int64_t)1 << 62)  // snapshot: the fixed-set count's flag of a weighted chain (ngp_save_snapshot)
 #define NGP_SNAP_RANDOM ((int64_t)1 << 61)    // ... and of a chain with random-effect sets
 #define NGP_SNAP_HOLDOUT ((int64_t)1 << 60)   // ... and of a chain with held-out records (ngp_set_holdout)
+#define NGP_SNAP_LIABILITY ((int64_t)1 << 59) // ... of a chain with liability traits (ngp_set_liability_classes / ngp_set_liability_bounds)
+#define NGP_SNAP_FIXVARE ((int64_t)1 << 58)   // ... and of a chain whose residual variance is held fixed (ngp_fix_residual_variance)
 // snapshot signature of a BayesLV set (added to its second word): the covariate count and how varZeta is estimated
 static int64_t lv_sig(const ngp_handle *h, const HSet &hs) {
     return hs.lv < 0 ? 0 : 256 * ((int64_t)h->mm.lv[(size_t)hs.lv].ncov + 32 * (int64_t)h->mm.lv[(size_t)hs.lv].mode);
@@ -2588,6 +2695,9 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
     REQUIRE(y && N == h->N, NGP_ERR_ARG, "y must have N entries");
+    std::vector<double> y_lb;  // liability traits: y with the starting liability on every augmented row (classes: y is read nowhere)
+    if ((rc = start_liabilities(h, y, y_lb))) return rc;
+    if (!y_lb.empty()) y = y_lb.data();
     const std::vector<long long> &ho = h->cm.ho_rows;
     std::vector<double> y_aug;  // held-out records: y with the mean of the observed phenotypes on the held-out rows, which are not read
     if (ho.empty()) {
@@ -2613,11 +2723,12 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     }
     HCHK(hipMemsetAsync(h->cm.d_ycorr, 0, (size_t)h->L * sizeof(double), h->stream));
     HCHK(hipMemcpyAsync(h->cm.d_ycorr, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // src/mme.jl:57
-    if (!y_aug.empty()) HCHK(hipStreamSynchronize(h->stream));  // (the copy reads y_aug)
+    if (!y_aug.empty() || !y_lb.empty()) HCHK(hipStreamSynchronize(h->stream));  // (the copy reads y_aug / y_lb)
     if (h->cm.d_rs) launch_rows(h, h->cm.d_ycorr, h->cm.d_ycorr, false);  // weighted residuals: y~ = s y
     HCHK(hipMemsetAsync(h->cm.d_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));                  // src/mme.jl:443
     HCHK(hipMemsetAsync(h->cm.d_delta, 1, (size_t)h->Ppad, h->stream));                                  // src/mme.jl:444
     HCHK(hipMemsetAsync(h->cm.d_scal, 0, sizeof(DScal), h->stream));
+    if (h->fix_varE > 0.0) hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->cm.d_scal, h->fix_varE);  // held from here on
     HCHK(hipMemsetAsync(h->cm.d_sum_beta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     HCHK(hipMemsetAsync(h->cm.d_sum_beta2, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     HCHK(hipMemsetAsync(h->cm.d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
@@ -3463,16 +3574,19 @@ namespace {
 // random-effect sets writes neither flag, digest nor random part: its bytes are those of the first snapshots.
 struct ModelSig {
     std::vector<int64_t> sets;  // per marker set {method, K + 16 tuple k + the BayesLV word, nreg, col0, ncol}
-    int64_t nfs = 0;            // fixed-effect sets | NGP_SNAP_WEIGHTED | NGP_SNAP_RANDOM | NGP_SNAP_HOLDOUT
+    int64_t nfs = 0;            // fixed-effect sets | NGP_SNAP_WEIGHTED | NGP_SNAP_RANDOM | NGP_SNAP_HOLDOUT | NGP_SNAP_LIABILITY | NGP_SNAP_FIXVARE
     uint64_t digest = 0;        // of the residual weights
     uint64_t ho_digest = 0;     // of the held-out rows
+    uint64_t lb_digest = 0;     // of the augmented rows and their classes or bounds
+    double fix_varE = 0.0;      // the fixed residual variance
     std::vector<uint64_t> rnd;  // nrand | per set q, digest of its level coding and K
     std::vector<int64_t> fix;   // ncol per fixed-effect set
     ModelSig() = default;
     explicit ModelSig(const ngp_handle *h) {
         for (auto &hs : h->sets) sets.insert(sets.end(), {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs) + rc_sig(h, hs), hs.nreg, hs.col0, hs.ncol});
         nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM) |
-              (h->cm.ho_rows.empty() ? 0 : NGP_SNAP_HOLDOUT);
+              (h->cm.ho_rows.empty() ? 0 : NGP_SNAP_HOLDOUT) | (h->cm.lb.on() ? NGP_SNAP_LIABILITY : 0) | (h->fix_varE > 0.0 ? NGP_SNAP_FIXVARE : 0);
+        lb_digest = h->cm.lb.digest; fix_varE = h->fix_varE;
         if (!h->h_rw.empty()) digest = weights_digest(h->h_rw);
         if (!h->cm.ho_rows.empty()) ho_digest = rows_digest(h->cm.ho_rows);
         if (!h->mm.rnd.empty()) {
@@ -3515,6 +3629,8 @@ int32_t ngp_save_snapshot(ngp_handle *h, const char *path) {
     W(sig.sets.data(), sig.sets.size() * 8); W(&sig.nfs, 8);
     if (sig.nfs & NGP_SNAP_WEIGHTED) W(&sig.digest, 8);
     if (sig.nfs & NGP_SNAP_HOLDOUT) W(&sig.ho_digest, 8);
+    if (sig.nfs & NGP_SNAP_LIABILITY) W(&sig.lb_digest, 8);
+    if (sig.nfs & NGP_SNAP_FIXVARE) W(&sig.fix_varE, 8);
     W(sig.rnd.data(), sig.rnd.size() * 8); W(sig.fix.data(), sig.fix.size() * 8);
     W(img.data(), img.size());
     if (fclose(f.release()) != 0) ok = false;  // (a failed close is a failed write)
@@ -3555,6 +3671,16 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         const bool snap_h = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_HOLDOUT) != 0;
         if (snap_w) Rd(&got.digest, 8);
         if (snap_h) Rd(&got.ho_digest, 8);
+        const bool snap_l = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_LIABILITY) != 0, snap_f = ok && got.nfs >= 0 && (got.nfs & NGP_SNAP_FIXVARE) != 0;
+        if (snap_l) Rd(&got.lb_digest, 8);
+        if (snap_f) Rd(&got.fix_varE, 8);
+        if (ok && snap_l != h->cm.lb.on())
+            return fail(h, NGP_ERR_ARG, snap_l ? "snapshot of a chain with liability traits: this handle has none (ngp_set_liability_classes / ngp_set_liability_bounds)"
+                                               : "snapshot of a chain without liability traits: this handle has them");
+        if (ok && snap_l && got.lb_digest != want.lb_digest)
+            return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its liability rows, classes or bounds differ)");
+        if (ok && (snap_f != (h->fix_varE > 0.0) || (snap_f && got.fix_varE != want.fix_varE)))
+            return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its residual variance is fixed at another value, or sampled)");
         if (ok && snap_h != !h->cm.ho_rows.empty())
             return fail(h, NGP_ERR_ARG, snap_h ? "snapshot of a chain with held-out records: this handle has none (ngp_set_holdout)"
                                                : "snapshot of a chain without held-out records: this handle has them");
@@ -3685,6 +3811,8 @@ int32_t ngp_run_many(ngp_handle **hs, int32_t n, int64_t niter) {
         if (!hs[i]) return fail(nullptr, NGP_ERR_ARG, "ngp_run_many: null handle");
         for (int k = 0; k < i; k++)
             if (hs[k] == hs[i]) return fail(hs[0], NGP_ERR_ARG, "ngp_run_many: the same handle twice");
+        if (hs[i]->cm.lb.on() != hs[0]->cm.lb.on() || hs[i]->cm.lb.C != hs[0]->cm.lb.C)  // one trait per call: liabilities on every chain or on none
+            return fail(hs[0], NGP_ERR_ARG, "ngp_run_many: the chains of a call all carry liability traits of one kind (classes, bounds) or none does");
     }
     // chains that share one panel (ngp_share_panel) and run the engine the fused kernel serves take ONE sweep launch per iteration:
     // the panel is streamed once for all of them (K chains per pass)
@@ -5585,6 +5713,7 @@ int32_t ngp_set_holdout(ngp_handle *h, const int64_t *rows, int64_t m) {
     if ((rc = enter(h))) return rc;
     REQUIRE(h->pm, NGP_ERR_STATE, "panel not set (the hold-out set belongs to the panel's records)");
     REQUIRE(!h->have_y, NGP_ERR_STATE, "ngp_set_holdout: the phenotypes are set already; the hold-out set comes before ngp_set_y");
+    REQUIRE(!h->cm.lb.on(), NGP_ERR_STATE, "ngp_set_holdout: this handle has liability traits already; the hold-out set comes before them (they leave its rows out)");
     REQUIRE(m >= 0 && (rows != nullptr || m == 0), NGP_ERR_ARG, "ngp_set_holdout: m >= 0 rows (or NULL and 0 to remove the mask)");
     REQUIRE(m < h->N, NGP_ERR_ARG, "ngp_set_holdout: at least one record must keep its phenotype (m < N)");
     for (int64_t k = 0; k < m; k++)
@@ -5652,6 +5781,201 @@ int32_t ngp_set_holdout_state(ngp_handle *h, const double *yaug, const double *s
     if (sum_fit) HCHK(hipMemcpy(h->cm.d_sum_fit, sum_fit, N8, hipMemcpyHostToDevice));
     if (sum_fit2) HCHK(hipMemcpy(h->cm.d_sum_fit2, sum_fit2, N8, hipMemcpyHostToDevice));
     if (n_fit) HCHK(hipMemcpy(h->cm.d_n_fit, n_fit, N8, hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Liability traits ("Liability traits"; kernels in ngp_liability.h).  A record with a liability keeps its row in
+ * the panel; its latent value is redrawn from a truncated normal at the head of every iteration.  Both setters come after the panel
+ * (or ngp_set_records / ngp_share_panel) and the hold-out mask and before ngp_set_y; they exclude one another; NULL, 0 removes either. */
+namespace {
+void clear_liabilities(ngp_handle *h) {
+    if (h->cm.lb.C > 0) h->fix_varE = 0.0;  // (the classes had fixed it at 1)
+    h->cm.lb = Liab();
+}
+// the device side of a Liab whose host side is filled
+int commit_liabilities(ngp_handle *h, Liab &n) {
+    int rc;
+    const size_t m = n.rows.size();
+    if ((rc = ensure_tn_fall(h))) return rc;
+    if ((rc = n.d_rows.alloc(h, m)) || (rc = n.d_liab.alloc(h, m))) return rc;
+    HCHK(hipMemcpyAsync(n.d_rows, n.rows.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    if (n.C >= 2) {
+        if ((rc = n.d_cls.alloc(h, m)) || (rc = n.d_thr.alloc(h, 3 * ((size_t)n.C + 1)))) return rc;
+        HCHK(hipMemcpyAsync(n.d_cls, n.cls.data(), m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    } else {
+        if ((rc = n.d_lo.alloc(h, m)) || (rc = n.d_hi.alloc(h, m))) return rc;
+        HCHK(hipMemcpyAsync(n.d_lo, n.lo.data(), m * 8, hipMemcpyHostToDevice, h->stream));
+        HCHK(hipMemcpyAsync(n.d_hi, n.hi.data(), m * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    HCHK(hipStreamSynchronize(h->stream));
+    n.digest = liab_digest(n);
+    h->cm.lb = std::move(n);
+    return NGP_OK;
+}
+}  // namespace
+
+int32_t ngp_fix_residual_variance(ngp_handle *h, double v) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(std::isfinite(v) && v >= 0.0, NGP_ERR_ARG, "ngp_fix_residual_variance: v > 0 holds varE at v, v = 0 samples it");
+    REQUIRE(h->cm.lb.C == 0 || v == 1.0, NGP_ERR_ARG, "ngp_fix_residual_variance: liability classes live on the probit scale, varE = 1");
+    h->fix_varE = v;
+    if (v > 0.0 && h->pm && h->have_y) {
+        hipLaunchKernelGGL(k_set_varE, dim3(1), dim3(1), 0, h->stream, h->cm.d_scal, v);
+        HCHK(hipStreamSynchronize(h->stream));
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_liability_classes(ngp_handle *h, const int32_t *cls, int32_t C) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set (the classes belong to the panel's records)");
+    REQUIRE(!h->have_y, NGP_ERR_STATE, "ngp_set_liability_classes: the phenotypes are set already; the classes come before ngp_set_y");
+    if (cls == nullptr && C == 0) {
+        if (h->cm.lb.C > 0) clear_liabilities(h);
+        return NGP_OK;
+    }
+    REQUIRE(h->cm.lb.C > 0 || !h->cm.lb.on(), NGP_ERR_STATE, "ngp_set_liability_classes: this handle has liability bounds (ngp_set_liability_bounds); remove them first");
+    REQUIRE(cls != nullptr && C >= 2 && C <= NGP_LIAB_MAXC, NGP_ERR_ARG, "ngp_set_liability_classes: N classes in 1..C with 2 <= C <= 8 (or NULL and 0 to remove them)");
+    REQUIRE(h->fix_varE == 0.0 || h->fix_varE == 1.0, NGP_ERR_ARG, "ngp_set_liability_classes: the residual variance is fixed at a value other than 1 (ngp_fix_residual_variance)");
+    Liab n;
+    n.C = C;
+    const std::vector<long long> &ho = h->cm.ho_rows;
+    std::vector<long long> cnt((size_t)C + 1, 0);
+    size_t kh = 0;
+    for (int64_t i = 0; i < h->N; i++) {
+        if (kh < ho.size() && ho[kh] == i) { kh++; continue; }  // (entries of held-out rows are not read)
+        REQUIRE(cls[i] >= 1 && cls[i] <= C, NGP_ERR_ARG, "ngp_set_liability_classes: a class outside 1..C");
+        n.rows.push_back(i); n.cls.push_back(cls[i]); cnt[(size_t)cls[i]] += 1;
+    }
+    for (int c = 1; c <= C; c++) REQUIRE(cnt[(size_t)c] > 0, NGP_ERR_ARG, "ngp_set_liability_classes: every class needs at least one record that is not held out");
+    if ((rc = commit_liabilities(h, n))) return rc;
+    h->fix_varE = 1.0;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_liability_bounds(ngp_handle *h, const int64_t *rows, const double *lo, const double *hi, int64_t m) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set (the bounds belong to the panel's records)");
+    REQUIRE(!h->have_y, NGP_ERR_STATE, "ngp_set_liability_bounds: the phenotypes are set already; the bounds come before ngp_set_y");
+    if (rows == nullptr && m == 0) {
+        if (h->cm.lb.C == 0) clear_liabilities(h);
+        return NGP_OK;
+    }
+    REQUIRE(h->cm.lb.C == 0, NGP_ERR_STATE, "ngp_set_liability_bounds: this handle has liability classes (ngp_set_liability_classes); remove them first");
+    REQUIRE(rows && lo && hi && m > 0, NGP_ERR_ARG, "ngp_set_liability_bounds: m > 0 rows with their bounds (or NULL and 0 to remove them)");
+    const std::vector<long long> &ho = h->cm.ho_rows;
+    for (int64_t k = 0; k < m; k++) {
+        REQUIRE(rows[k] >= 0 && rows[k] < h->N && (k == 0 || rows[k] > rows[k - 1]), NGP_ERR_ARG, "ngp_set_liability_bounds: rows must be strictly increasing and lie in [0, N)");
+        REQUIRE(!std::binary_search(ho.begin(), ho.end(), (long long)rows[k]), NGP_ERR_ARG, "ngp_set_liability_bounds: a row is held out (ngp_set_holdout) and bounded");
+        REQUIRE(lo[k] < hi[k] && (std::isfinite(lo[k]) || std::isfinite(hi[k])), NGP_ERR_ARG, "ngp_set_liability_bounds: lo < hi, at least one of them finite");
+    }
+    Liab n;
+    n.rows.assign(rows, rows + m); n.lo.assign(lo, lo + m); n.hi.assign(hi, hi + m);
+    return commit_liabilities(h, n);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_liability_layout(ngp_handle *h, int64_t *m, int32_t *C) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    if (m) *m = (int64_t)h->cm.lb.rows.size();
+    if (C) *C = h->cm.lb.C;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* rows, liab: m entries; thr, sum_thr, sum_thr2: the C - 1 thresholds t_1 .. t_{C-1} (t_1 = 0) and their sums over kept draws (classes
+ * only).  Any pointer may be NULL. */
+int32_t ngp_get_liability(ngp_handle *h, int64_t *rows, double *liab, double *thr, double *sum_thr, double *sum_thr2, int64_t m, int32_t C) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.on(), NGP_ERR_STATE, "no liability traits on this handle (ngp_set_liability_classes / ngp_set_liability_bounds)");
+    REQUIRE(m == (int64_t)lb.rows.size() && C == lb.C, NGP_ERR_ARG, "liability buffers must hold m and C - 1 entries (ngp_get_liability_layout)");
+    REQUIRE(h->have_y || !(liab || thr || sum_thr || sum_thr2), NGP_ERR_STATE, "y not set: the liabilities do not exist yet");
+    HCHK(hipStreamSynchronize(h->stream));
+    if (rows) for (int64_t k = 0; k < m; k++) rows[k] = (int64_t)lb.rows[(size_t)k];
+    if (liab) HCHK(hipMemcpy(liab, lb.d_liab, (size_t)m * 8, hipMemcpyDeviceToHost));
+    const size_t C1 = (size_t)C + 1, tb = lb.thr_bytes();
+    if (thr && tb) HCHK(hipMemcpy(thr, lb.d_thr + 1, tb, hipMemcpyDeviceToHost));
+    if (sum_thr && tb) HCHK(hipMemcpy(sum_thr, lb.d_thr + C1 + 1, tb, hipMemcpyDeviceToHost));
+    if (sum_thr2 && tb) HCHK(hipMemcpy(sum_thr2, lb.d_thr + 2 * C1 + 1, tb, hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Resume beside ngp_set_state / ngp_set_posterior_sums: what ngp_get_liability gave; a NULL pointer leaves that array as it is. */
+int32_t ngp_set_liability_state(ngp_handle *h, const double *liab, const double *thr, const double *sum_thr, const double *sum_thr2, int64_t m, int32_t C) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.on(), NGP_ERR_STATE, "no liability traits on this handle (ngp_set_liability_classes / ngp_set_liability_bounds)");
+    REQUIRE(h->have_y, NGP_ERR_STATE, "y not set (ngp_set_y starts the liabilities, this call replaces them)");
+    REQUIRE(m == (int64_t)lb.rows.size() && C == lb.C, NGP_ERR_ARG, "liability buffers must hold m and C - 1 entries (ngp_get_liability_layout)");
+    if (liab) for (int64_t k = 0; k < m; k++) REQUIRE(std::isfinite(liab[k]), NGP_ERR_ARG, "non-finite liability");
+    if (thr && C >= 2) {
+        REQUIRE(thr[0] == 0.0, NGP_ERR_ARG, "the first threshold is 0");
+        for (int c = 1; c < C - 1; c++) REQUIRE(std::isfinite(thr[c]) && thr[c] >= thr[c - 1], NGP_ERR_ARG, "thresholds must be finite and increasing");
+    }
+    for (const double *a : {sum_thr, sum_thr2})
+        if (a) for (int c = 0; c < C - 1; c++) REQUIRE(std::isfinite(a[c]), NGP_ERR_ARG, "non-finite threshold sum");
+    HCHK(hipStreamSynchronize(h->stream));
+    if (liab) HCHK(hipMemcpy(lb.d_liab, liab, (size_t)m * 8, hipMemcpyHostToDevice));
+    const size_t C1 = (size_t)C + 1, tb = lb.thr_bytes();
+    if (thr && tb) HCHK(hipMemcpy(lb.d_thr + 1, thr, tb, hipMemcpyHostToDevice));
+    if (sum_thr && tb) HCHK(hipMemcpy(lb.d_thr + C1 + 1, sum_thr, tb, hipMemcpyHostToDevice));
+    if (sum_thr2 && tb) HCHK(hipMemcpy(lb.d_thr + 2 * C1 + 1, sum_thr2, tb, hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* fallthrough: truncated-normal draws of this handle (chain and probe) whose rejection loop ran out of its 256 rounds; 0 in any sane chain */
+int32_t ngp_get_liability_stats(ngp_handle *h, int64_t *fallthrough) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    unsigned long long n = 0;
+    if (h->hm.d_tn_fall) {
+        HCHK(hipStreamSynchronize(h->stream));
+        HCHK(hipMemcpy(&n, h->hm.d_tn_fall, sizeof n, hipMemcpyDeviceToHost));
+    }
+    if (fallthrough) *fallthrough = (int64_t)n;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* probe of the draw layer (beside ngp_draws_indexed): out[i] = the truncated standard normal on (a[i], b[i]) of stream
+ * (seed, chain, iter, kind, index0 + i) */
+int32_t ngp_tnormal_indexed(ngp_handle *h, uint64_t iter, uint64_t kind, uint64_t index0, const double *a, const double *b, int64_t n, double *out) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(a && b && out && n > 0, NGP_ERR_ARG, "bad buffers");
+    if ((rc = ensure_tn_fall(h))) return rc;
+    DevArray<double> da, db, d;
+    if ((rc = da.alloc(h, (size_t)n)) || (rc = db.alloc(h, (size_t)n)) || (rc = d.alloc(h, (size_t)n))) return rc;
+    hipError_t e = hipMemcpyAsync(da, a, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_tnormal_indexed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->seed, (uint64_t)h->chain, iter, kind, index0,
+                           (const double *)da.get(), (const double *)db.get(), (long long)n, d.get(), h->hm.d_tn_fall.get());
+        e = hipMemcpyAsync(out, d, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("tnormal draws: ") + hipGetErrorString(e));
     return NGP_OK;
     NGP_CATCH(h)
 }

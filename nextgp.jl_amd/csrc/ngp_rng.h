@@ -34,6 +34,9 @@
 #define NGP_KIND_RC_ANNOT 20    // BayesRCpi: gamma of annotation a of a locus' annotProb Dirichlet, (set << 40) | (locus << 3) | a (src/functions.jl:541-544)
 #define NGP_KIND_AUGMENT 21     // held-out records: the normal of a record's augmented phenotype, keyed by the row (ngp_holdout.h)
 
+#define NGP_KIND_LIABILITY 22   // liability traits: the uniforms of a record's truncated-normal draw, keyed by the row (ngp_liability.h)
+#define NGP_KIND_THRESHOLD 23   // liability traits: the uniform of threshold c of an ordered trait, keyed by c (ngp_liability.h)
+
 #define NGP_GOLD 0x9E3779B97F4A7C15ULL
 
 namespace ngp {

@@ -24,23 +24,28 @@
 //    per BayesLV set sum_c[16], sum_varZeta | per BayesRCpi set sum_annot[A][ncol] | sum_varE | sum_b | nKept (as a double; rounded with
 //    llround on the way back).  A BayesRCpi set's pi sums are the class sums of its A K slots, its A variance sums lie in sum_varBeta.
 //    A chain with held-out records (ngp_set_holdout, m > 0) appends sum_fit[N] | sum_fit2[N] | n_fit[N] (doubles, zero off the held-out
-//    rows); a chain without a mask appends nothing.
+//    rows); a chain without a mask appends nothing.  A chain with C liability classes (ngp_set_liability_classes) then appends
+//    sum_thr[C-1] | sum_thr2[C-1], the sums of the thresholds t_1 .. t_{C-1} (t_1 = 0) and of their squares; any other chain nothing.
 //
 //  Sample file (ngp_set_sample_file) -- record: sample_layout, padded to a multiple of 8 bytes:
 //    header  char[8] magic | int64 P, nvb, nsets, nfix, nclass, record bytes | per marker set int64 {method, K, col0, ncol, variance
 //            entries, tuple k}; magic "NGPSMP01": nothing more; "NGPSMP02" (random-effect sets): int64 nrand | int64 q per set;
 //            "NGPSMP03" (BayesLV sets): the random-effect part as in 02, also when empty, then int64 nlv | per set int64 marker set, ncov
 //            "NGPSMP04" (BayesRCpi sets): the parts of 03, also when empty, then int64 nrc | per set int64 marker set, A, K
+//            "NGPSMP05" (C >= 3 liability classes): the parts of 04, also when empty, then int64 nthr = C - 2
 //    record  int64 iter (-1: a sweep of the call gave up, the record is not written) | varE | b | b_fixed[nfix] | u[q] of every
 //            random-effect set, then varU of every set | beta[P] | varBeta[nvb] | piHat[2] per marker set | class probabilities[K]
 //            per BayesR set (the A K slots of a BayesRCpi set, annotation-major) | per BayesLV set c[16] (the first ncov used), varZeta |
-//            per BayesRCpi set annotProb[A][ncol] | delta[P] (uint8) | per BayesRCpi set annotCat[ncol] (uint8, from 1)
+//            per BayesRCpi set annotProb[A][ncol] | delta[P] (uint8) | per BayesRCpi set annotCat[ncol] (uint8, from 1) |
+//            "NGPSMP05": thr[nthr], the thresholds t_2 .. t_{C-1} of this draw (doubles, directly behind the bytes in front: not aligned)
 //
 //  Snapshot (ngp_save_snapshot / ngp_load_snapshot):
 //    char[8] "NGPSNAP2" | int64 N, P, nvb, nsets | snapshot_head_layout: int64 iter, nKept | uint64 seed, chain |
 //    model signature (ModelSig in ngp_api.hip): per marker set int64 {method, K + 16 tuple k + 256 (ncov + 32 est_mode) of a
 //      BayesLV set, nreg, col0, ncol} | int64 number of fixed-effect sets, bit 62: residual weights, bit 61: random-effect sets,
-//      bit 60: held-out records | with weights: uint64 digest of the weights | with held-out records: uint64 digest of their rows |
+//      bit 60: held-out records, bit 59: liability traits, bit 58: a fixed residual variance | with weights: uint64 digest of the
+//      weights | with held-out records: uint64 digest of their rows | with liabilities: uint64 digest of the augmented rows, C and the
+//      classes or bounds | with a fixed residual variance: its value (double) |
 //      with random-effect sets: int64 nrand, per set int64 q, uint64 digest of its level
 //      coding and K | int64 ncol per fixed-effect set
 //    snapshot_body_layout: varE, b, sum_varE, sum_b | ycorr[N] (with residual weights the scaled residual as it lies on the
@@ -50,7 +55,8 @@
 //      per BayesLV set the NGP_LV_WORDS doubles of its small state (c, varZeta, their sums, ...), zeta[ncol] |
 //      per BayesRCpi set annotProb[A][ncol], sum_annot[A][ncol], annotCat[ncol] (uint8); its signature words are method 6,
 //      K = A K slots + a 47-bit digest of the annotation masks from bit 8 up, and nreg = A |
-//      with held-out records: yaug[m], sum_fit[N], sum_fit2[N], n_fit[N] (doubles)
+//      with held-out records: yaug[m], sum_fit[N], sum_fit2[N], n_fit[N] (doubles) |
+//      with liabilities: liab[m] | with classes also thr[C-1] (t_1 .. t_{C-1}), sum_thr[C-1], sum_thr2[C-1]
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -116,6 +122,20 @@ inline const Layout snapshot_body_layout = {{SEG_VARE}, {SEG_B}, {SEG_SUM_VARE},
                                             {SEG_SUM_FIX}, {SEG_CLS, SEG_SUM_CLS}, {SEG_U, SEG_SUM_U, SEG_VU, SEG_RFINE}, {SEG_LV_ALL, SEG_ZETA},
                                             {SEG_RC_PROB, SEG_SUM_RC, SEG_RC_CAT}, {SEG_YAUG, SEG_SUM_FIT, SEG_SUM_FIT2, SEG_N_FIT}};
 
+// Liability traits (ngp_liability.h; described only for a chain that has them): liab[m]; with classes thr[C-1], sum_thr[C-1],
+// sum_thr2[C-1].  The ids continue the enumeration, and the groups follow the tables above as tails: place() appends a table's tail, so
+// the tables themselves stay what every chain without liabilities is written by.  SEG_THR_SMP: the drawn thresholds t_2 .. t_{C-1}
+// (described for C >= 3 only), the sample record's tail behind its bytes.
+constexpr SegId SEG_LIAB = (SegId)(SEG_N_FIT + 1), SEG_THR = (SegId)(SEG_N_FIT + 2), SEG_SUM_THR = (SegId)(SEG_N_FIT + 3), SEG_SUM_THR2 = (SegId)(SEG_N_FIT + 4),
+                SEG_THR_SMP = (SegId)(SEG_N_FIT + 5);
+inline const Layout liability_posterior_tail = {{SEG_SUM_THR}, {SEG_SUM_THR2}};
+inline const Layout liability_snapshot_tail = {{SEG_LIAB, SEG_THR, SEG_SUM_THR, SEG_SUM_THR2}};
+inline const Layout liability_sample_tail = {{SEG_THR_SMP}};
+inline const Layout *tail_of(const Layout &L) {
+    return &L == &posterior_layout ? &liability_posterior_tail : &L == &snapshot_body_layout ? &liability_snapshot_tail
+         : &L == &sample_layout ? &liability_sample_tail : nullptr;
+}
+
 // a layout applied to a chain: every segment with its byte offset, and the size of the whole
 struct Plan {
     struct At { const Seg *s; size_t off; };
@@ -139,13 +159,17 @@ struct Plan {
 // pad: the total is rounded up to a multiple of it
 inline Plan place(const ChainState &st, const Layout &L, size_t pad = 1) {
     Plan pl;
-    for (auto &group : L)
-        for (auto &first : st.segs) {  // the instances of a group: those of its first id, in the order describe() lists them
-            if (first.id != group[0]) continue;
-            for (SegId id : group)
-                for (auto &s : st.segs)
-                    if (s.id == id && s.inst == first.inst) { pl.at.push_back({&s, pl.bytes}); pl.bytes += s.bytes; }
-        }
+    const Layout *tail = tail_of(L);
+    for (const Layout *part : {&L, tail}) {
+        if (!part) continue;
+        for (auto &group : *part)
+            for (auto &first : st.segs) {  // the instances of a group: those of its first id, in the order describe() lists them
+                if (first.id != group[0]) continue;
+                for (SegId id : group)
+                    for (auto &s : st.segs)
+                        if (s.id == id && s.inst == first.inst) { pl.at.push_back({&s, pl.bytes}); pl.bytes += s.bytes; }
+            }
+    }
     pl.bytes = (pl.bytes + pad - 1) / pad * pad;
     return pl;
 }

@@ -120,6 +120,62 @@ function getHoldout(h::Handle, N::Integer)
     return (rows = keep, n = Int.(st.n_fit[keep]), mean = mean, sd = sd)
 end
 
+# ---- liability traits: binary / ordered classes, censored records (include/nextgp_hip.h, "liability traits") ----
+# cls: one class 1..C per record (entries of held-out records are not read), 2 <= C <= 8; after the panel and the hold-out mask and
+# before set_y!, which then reads y nowhere; varE is held at 1.  nothing removes the classes.
+function set_classes!(h::Handle, cls::Union{Nothing,Vector{Int32}}, C::Integer=(cls === nothing ? 0 : Int(maximum(cls))))
+    c = cls === nothing ? Int32[] : cls
+    check(h, ccall((:ngp_set_liability_classes, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Int32), h.ptr, isempty(c) ? C_NULL : pointer(c), isempty(c) ? 0 : C))
+end
+# rows: 0-BASED records, strictly increasing, none held out; lo < hi, one of them possibly infinite; set_y! reads y off these rows only
+function set_censored!(h::Handle, rows::Vector{Int64}, lo::Vector{Float64}, hi::Vector{Float64})
+    m = length(rows)
+    check(h, ccall((:ngp_set_liability_bounds, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                   h.ptr, m == 0 ? C_NULL : pointer(rows), m == 0 ? C_NULL : pointer(lo), m == 0 ? C_NULL : pointer(hi), m))
+end
+function liability_layout(h::Handle)     # (m, C): augmented records (0 without liabilities), classes (0 for censored records)
+    m = Ref{Int64}(0); C = Ref{Int32}(0)
+    check(h, ccall((:ngp_get_liability_layout, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}), h.ptr, m, C))
+    return (Int(m[]), Int(C[]))
+end
+function liability_state(h::Handle)      # rows (0-based), liab (m each); thr, sum_thr, sum_thr2: t_1 .. t_{C-1} and their sums over kept draws
+    m, C = liability_layout(h)
+    nt = max(C - 1, 0)
+    rows = Vector{Int64}(undef, m); liab = Vector{Float64}(undef, m)
+    thr = Vector{Float64}(undef, nt); s1 = similar(thr); s2 = similar(thr)
+    check(h, ccall((:ngp_get_liability, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32),
+                   h.ptr, rows, liab, thr, s1, s2, m, C))
+    return (rows = rows, liab = liab, thr = thr, sum_thr = s1, sum_thr2 = s2)
+end
+set_liability_state!(h::Handle, liab::Vector{Float64}, thr::Vector{Float64}, sum_thr::Vector{Float64}, sum_thr2::Vector{Float64}) =
+    check(h, ccall((:ngp_set_liability_state, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32),
+                   h.ptr, liab, thr, sum_thr, sum_thr2, length(liab), isempty(thr) ? 0 : length(thr) + 1))
+function liability_fallthrough(h::Handle)   # truncated-normal draws whose rejection loop ran out of rounds: 0 in any sane chain
+    n = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_liability_stats, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), h.ptr, n))
+    return n[]
+end
+# v > 0 holds varE = v from set_y! on, 0 returns to sampling
+fix_residual_variance!(h::Handle, v::Real) =
+    check(h, ccall((:ngp_fix_residual_variance, LIB), Int32, (Ptr{Cvoid}, Float64), h.ptr, v))
+function tnormal_indexed(h::Handle, iter::Integer, kind::Integer, index0::Integer, a::Vector{Float64}, b::Vector{Float64})   # probe of the draw layer
+    out = Vector{Float64}(undef, length(a))
+    check(h, ccall((:ngp_tnormal_indexed, LIB), Int32, (Ptr{Cvoid}, UInt64, UInt64, UInt64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
+                   h.ptr, iter, kind, index0, a, b, length(a), out))
+    return out
+end
+"""
+    getThresholds(h, nKept)
+
+Posterior mean and SD of the thresholds `t_2 .. t_{C-1}` of an ordered trait over the kept draws (`nKept` of them).
+"""
+function getThresholds(h::Handle, nKept::Integer)
+    st = liability_state(h)
+    mean = st.sum_thr[2:end] ./ nKept
+    sd = sqrt.(max.(0.0, st.sum_thr2[2:end] ./ nKept .- mean .^ 2))
+    return (mean = mean, sd = sd)
+end
+
 # ---- prediction of new individuals (include/nextgp_hip.h, "prediction") ----
 # A second panel beside the training panel: Np individuals x the same columns in the same order, centred with the TRAINING means.
 # Every kept iteration then accumulates g = X_new beta per marker set on the device.  Column ranges as for the training panel.
@@ -487,15 +543,17 @@ set_sample_file!(h::Handle, path::Union{AbstractString,Nothing}) =
 function foreach_sample(f, path::AbstractString)
     open(path, "r") do io
         magic = String(read(io, 8))
-        magic in ("NGPSMP01", "NGPSMP02", "NGPSMP03", "NGPSMP04") || error("not a sample file: $path")
+        magic in ("NGPSMP01", "NGPSMP02", "NGPSMP03", "NGPSMP04", "NGPSMP05") || error("not a sample file: $path")
         P, nvb, nsets, nfix, ncls, rec = ntuple(_ -> read(io, Int64), 6)
         sets = [ntuple(_ -> read(io, Int64), 6) for _ in 1:nsets]     # (method, K, col0, ncol, variance entries, tuple k)
         rq = magic != "NGPSMP01" ? [read(io, Int64) for _ in 1:read(io, Int64)] : Int64[]   # random-effect sets: q of each (a tuple set: k - 1 in the bits from 32 up)
         # BayesLV sets ("NGPSMP03"): (marker set, ncov) of each; a record holds c (16 words, ncov used) | varZeta per set behind class_pi
-        lvs = magic in ("NGPSMP03", "NGPSMP04") ? [(read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64}[]
+        lvs = magic in ("NGPSMP03", "NGPSMP04", "NGPSMP05") ? [(read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64}[]
         # BayesRCπ sets ("NGPSMP04"): (marker set, A, K) of each; a record holds annotProb [A][ncol] per set behind the BayesLV words and
         # annotCat [ncol] (one byte each) per set behind delta
-        rcs = magic == "NGPSMP04" ? [(read(io, Int64), read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64,Int64}[]
+        rcs = magic in ("NGPSMP04", "NGPSMP05") ? [(read(io, Int64), read(io, Int64), read(io, Int64)) for _ in 1:read(io, Int64)] : Tuple{Int64,Int64,Int64}[]
+        # liability classes, C >= 3 ("NGPSMP05"): a record ends with its nthr thresholds t_2 .. t_{C-1}, behind everything read here
+        nthr = magic == "NGPSMP05" ? Int(read(io, Int64)) : 0
         rcn = [Int(sets[r[1] + 1][4]) for r in rcs]                   # loci of each
         rk = [Int(w >> 32) + 1 for w in rq]                           # components of each set (1: a (1|g) / PED / GBLUP set)
         rq = [Int(w & 0xffffffff) * k for (w, k) in zip(rq, rk)]      # words of u per set: q k, the components of a level adjacent
