@@ -1209,7 +1209,9 @@ int check_abort(ngp_handle *h, int64_t *iter_failed = nullptr) {
                                     "ngp_set_y / ngp_set_state");
     if (w[0] == 7u)  // NGP_ABORT_FX
         return fail(h, NGP_ERR_HIP, "persistent sweep: a partial dot product left the fixed-point range of its accumulator (non-finite residual or effects, "
-                                    "or the residual grew more than 32-fold within one sweep); the chain state is invalid until ngp_set_y / ngp_set_state");
+                                    "or within one iteration the residual grew more than 32-fold over the larger of its norm at the head and "
+                                    "sqrt(W varE) / 16, W the number of records or the sum of their weights); the chain state is invalid until "
+                                    "ngp_set_y / ngp_set_state");
     return fail(h, NGP_ERR_HIP, "persistent sweep kernel gave up waiting (role code " + std::to_string(w[0]) +
                                     "): workgroups not co-resident (another kernel holding CUs?) or a hand-off was lost; the chain "
                                     "state is invalid until ngp_set_y / ngp_set_state");

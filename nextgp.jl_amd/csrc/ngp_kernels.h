@@ -63,11 +63,6 @@ __global__ __launch_bounds__(1024) void k_head(double *__restrict__ ycorr, long 
             yy = yy + wyy[k];
             sy = sy + wsy[k];
         }
-        {   // fixed-point scale of this iteration's X_t'ycorr accumulators (ngp_common.h): from ycorr'ycorr as it stands here
-            const int fe = fx_exponent(mpm_max * yy);
-            sc->fx_scale = fx_pow2(52 - fe);
-            sc->fx_inv = fx_pow2(fe - 52);
-        }
         double varE = sc->varE, iVarE = sc->iVarE;
         if (draw_varE) {
             Rng r = rng_seed(seed, chain, it, NGP_KIND_VARE_CHI2, 0);
@@ -78,6 +73,15 @@ __global__ __launch_bounds__(1024) void k_head(double *__restrict__ ycorr, long 
             iVarE = 1.0 / varE;
             sc->varE = varE;
             sc->iVarE = iVarE;
+        }
+        {   // fixed-point scale of this iteration's X_t'ycorr accumulators (ngp_common.h): from ycorr'ycorr as it stands here, or from
+            // W varE / 256 where that is larger (W = N or the sum of weights, varE this iteration's: drawn above, fixed, or the fine
+            // seam's) -- a head residual that is small against the priors leaves room for what this iteration's draws make of it
+            const double W = rs ? sum_w : (double)N;
+            const double fl = 0x1p-8 * W * varE;
+            const int fe = fx_exponent(mpm_max * (yy > fl ? yy : fl));
+            sc->fx_scale = fx_pow2(52 - fe);
+            sc->fx_inv = fx_pow2(fe - 52);
         }
         double db = 0.0;
         if (intercept) {

@@ -446,6 +446,8 @@ typedef struct {
     int64_t nvb; double *varBeta; double *sum_varBeta;
     double e_df, e_scale;
     int intercept;
+    double fix_varE;          /* > 0: the residual variance is held at this value and the head draws none (ngp_fix_residual_variance) */
+    int fx_rule;              /* 0: the scale rule of the library; 1 (tests only): the rule before the floor, from ycorr'ycorr alone */
     /* state */
     double *y;     /* N */
     double *ycorr; /* N (blocked: S*R padded) */
@@ -492,6 +494,13 @@ int ora_set_nchain(ora_t *h, int64_t n) {
 }
 /* chain form of the linear blocks (the library reports its choice: ngp_get_chain_form): 0 = 64 steps (default), 1 = inverse form */
 int ora_set_tform(ora_t *h, int on) { h->tform = on ? 1 : 0; return ORA_OK; }
+/* hold the residual variance at v > 0 (the library's ngp_fix_residual_variance); 0 samples it again */
+int ora_fix_residual_variance(ora_t *h, double v) {
+    if (!(v >= 0.0) || isinf(v)) { snprintf(h->err, 256, "fixed residual variance must be finite and >= 0"); return ORA_ERR; }
+    h->fix_varE = v; return ORA_OK;
+}
+/* TESTS ONLY: 1 takes the fixed-point scale from ycorr'ycorr alone, as the library did before the scale had a floor */
+int ora_set_fx_rule(ora_t *h, int rule) { h->fx_rule = rule ? 1 : 0; return ORA_OK; }
 static void free_sets(ora_t *h) {
     for (int s = 0; s < h->nsets; s++) { free(h->sets[s].reg_start); free(h->sets[s].reg_stop); free(h->sets[s].tmpm); }
 }
@@ -1279,19 +1288,24 @@ static void iter_blocked(ora_t *h) {
     }
     double yy = wyy[0], sy = wsy[0];
     for (int wv = 1; wv < 16; wv++) { yy = yy + wyy[wv]; sy = sy + wsy[wv]; }
-    /* fixed-point scale of this iteration's X_t'ycorr accumulators (csrc/ngp_common.h; DESIGN.md section 2, step 3f): every shard
-       partial and every far look-ahead term is scaled by 2^(52 - E), rounded to the nearest integer and added as an integer -- an
-       order-free sum.  2^E > 16 sqrt(max_j x_j'x_j * ycorr'ycorr), the norms as they stand at the head of the iteration. */
     double mpm_max = 0.0;
     for (int64_t k = 0; k < h->Ppad; k++) if (h->mpm[k] > mpm_max) mpm_max = h->mpm[k];
-    const int fe = fx_exponent(mpm_max * yy);
-    const double fxs = ldexp(1.0, 52 - fe), fxi = ldexp(1.0, fe - 52);
-    rng_seed(&r, h->seed, h->chain, it, KIND_VARE_CHI2, 0);
-    double chi = rng_chisq(&r, h->e_df + (double)N);
-    double t = h->e_df * h->e_scale; t = t + yy;
-    double varE = t / chi;
+    double varE = h->varE;
+    if (!(h->fix_varE > 0.0)) {
+        rng_seed(&r, h->seed, h->chain, it, KIND_VARE_CHI2, 0);
+        double chi = rng_chisq(&r, h->e_df + (double)N);
+        double t = h->e_df * h->e_scale; t = t + yy;
+        varE = t / chi;
+    } else varE = h->fix_varE;
     double iVarE = 1.0 / varE;
     h->varE = varE;
+    /* fixed-point scale of this iteration's X_t'ycorr accumulators (csrc/ngp_common.h; DESIGN.md section 2, step 3f): every shard
+       partial and every far look-ahead term is scaled by 2^(52 - E), rounded to the nearest integer and added as an integer -- an
+       order-free sum.  2^E > 16 sqrt(max_j x_j'x_j * max(ycorr'ycorr, N varE / 256)): the norm as it stands at the head of the
+       iteration, or -- where the head residual is small against the priors -- what this iteration's varE says it may become. */
+    const double fl = 0x1p-8 * (double)N * varE;
+    const int fe = fx_exponent(mpm_max * ((h->fx_rule == 1 || yy > fl) ? yy : fl));
+    const double fxs = ldexp(1.0, 52 - fe), fxi = ldexp(1.0, fe - 52);
     if (h->intercept) {
         double Nd = (double)N;
         double tb = Nd * h->b; double sb = sy + tb;
@@ -1510,10 +1524,11 @@ static void iter_blocked(ora_t *h) {
         int raw_linear = 1;
         for (int j = 0; j < BLK; j++)
             if (lane_set[j] >= 0 && h->sets[lane_set[j]].method != METHOD_PR) raw_linear = 0;
+        int fx_out = 0;   /* a term outside the fixed-point range, |term * scale| >= 2^53: the library's sweep stops there (abort 7) */
         for (int j = 0; j < BLK; j++) {
             /* the shard partials as fixed-point terms: integer addition, no order */
             long long qsum = 0;
-            for (int64_t s = 0; s < S; s++) qsum += llrint(part[s * BLK + j] * fxs);
+            for (int64_t s = 0; s < S; s++) { const double x = part[s * BLK + j] * fxs; if (!(fabs(x) < 0x1p53)) fx_out = 1; else qsum += llrint(x); }
             /* look-ahead corrections v_d = G[tb, tb-d] dlt_{tb-d} of the blocks whose update the GEMV has not seen.
                Far lags d = h->near+1 .. D-1 are folded into the group sums (the reducer workgroups compute them):
                lag d goes to group (d-h->near-1) mod NG, ascending d.  Lags h->near .. 1 stay with the sampler. */
@@ -1528,7 +1543,7 @@ static void iter_blocked(ora_t *h) {
                 vd[d] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
             }
             for (int64_t d = h->near + 1; d < D; d++)
-                if (hv[d]) qsum += llrint((-vd[d]) * fxs);   /* far lags: one more term each (the "reducer" workgroups) */
+                if (hv[d]) { const double x = (-vd[d]) * fxs; if (!(fabs(x) < 0x1p53)) fx_out = 1; else qsum += llrint(x); }   /* far lags: one more term each (the "reducer" workgroups) */
             double tot = (double)qsum * fxi;
             {   /* near lags stay with the sampler: cor = (((v_near + ...) + v_2) + v_1) over the terms that exist */
                 double c = 0.0; int have = 0;
@@ -1543,6 +1558,12 @@ static void iter_blocked(ora_t *h) {
                 if (j < (BLK / kk) * kk)
                     for (int b = 0; b < kk; b++) rr[j] = __builtin_fma(h->tupg[(size_t)b * h->Ppad + k0 + j], h->beta[k0 + (j / kk) * kk + b], rr[j]);
             }
+        }
+        if (fx_out) {   /* the iteration gives up, as the library's does: h->iter stays, ora_run returns the error */
+            snprintf(h->err, 256, "blocked sweep: a term of X_t'ycorr left the fixed-point range (|term| >= 2^%d at block %lld, iteration %lld)",
+                     fe + 1, (long long)tb, (long long)it);
+            free(part); free(hist);
+            return;
         }
         if (has_t >= 0) {
             /* Tuple block (functions.jl:144-151 in 64-column space): the k effects of a locus are drawn in ONE step from the r of its

@@ -234,6 +234,14 @@ class Oracle:
     def set_residual_prior(self, df, scale):
         self._chk(self.L.ora_set_residual_prior(self.h, C.c_double(df), C.c_double(scale)))
 
+    def fix_residual_variance(self, v):
+        """Blocked order: hold varE at v > 0, the head draws none (the library's ngp_fix_residual_variance); 0 samples it again."""
+        self._chk(self.L.ora_fix_residual_variance(self.h, C.c_double(float(v))))
+
+    def set_fx_rule(self, old):
+        """TESTS ONLY: True takes the fixed-point scale of X_t'ycorr from ycorr'ycorr alone (the rule before the scale had a floor)."""
+        self._chk(self.L.ora_set_fx_rule(self.h, C.c_int(1 if old else 0)))
+
     def set_intercept(self, on):
         self._chk(self.L.ora_set_intercept(self.h, C.c_int(int(on))))
 
