@@ -450,6 +450,12 @@ int32_t ngp_debug_set_virtual_device(ngp_handle *h, int32_t vdev);
 /* Test hook of the exception barrier: throws a C++ exception inside an entry point (kind 0 std::bad_alloc, 1 std::length_error,
  * 2 a non-standard one); what comes back is a negative status and a message -- never an unwind into the caller.  h may be NULL. */
 int32_t ngp_debug_throw(ngp_handle *h, int32_t kind);
+/* Test hook of the staged loaders: every loop that stages host columns or a panel file through a fixed-size buffer (256 MiB:
+ * ngp_set_panel_f64 / _f32, ngp_panel_columns_*, ngp_grm_columns_*, ngp_prediction_columns_*; 64 MiB: ngp_set_panel_u8,
+ * ngp_load_panel_file, ngp_load_prediction_file) takes `bytes` for that size, so that a small panel crosses many chunk boundaries.
+ * The rounding of each loop stays (at least one column, one 64-column block, 64 columns of a relationship matrix and multiples of
+ * 64 there); results never depend on the value.  0 = the defaults; negative: NGP_ERR_ARG. */
+int32_t ngp_debug_set_staging_bytes(ngp_handle *h, int64_t bytes);
 
 /* ---- BayesLV sets: a log-linear model of the SNP variances (src/runTime.jl:116-133, src/functions.jl:421-486) ----
  * Columns [col0, col0 + ncol) with one variance per locus (all varBeta0 at first).  The sweep is BayesPR's with one region per locus

@@ -201,6 +201,7 @@ SYMBOLS = [
     "ngp_set_holdout", "ngp_get_holdout", "ngp_set_holdout_state", "ngp_get_holdout_layout",
     "ngp_set_liability_classes", "ngp_set_liability_bounds", "ngp_get_liability_layout", "ngp_get_liability", "ngp_set_liability_state",
     "ngp_get_liability_stats", "ngp_fix_residual_variance", "ngp_tnormal_indexed",
+    "ngp_debug_set_staging_bytes",
 ]
 
 _lib = None
@@ -342,6 +343,21 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
 
+def _columns(M):
+    """(array, ctypes element type, suffix, leading dimension) of a host matrix handed over in whole columns: uint8 and float32 go as they
+    are, anything else as float64.  The first N rows of a taller Fortran-ordered array (M = big[:N]) go over without a copy, with the
+    parent's leading dimension; everything else is made Fortran-contiguous."""
+    M = np.asarray(M)
+    t, sfx = {np.dtype(np.uint8): (C.c_uint8, "u8"), np.dtype(np.float32): (C.c_float, "f32")}.get(M.dtype, (C.c_double, "f64"))
+    if t is C.c_double and M.dtype != np.float64:
+        M = np.asfortranarray(M, dtype=np.float64)
+    if M.ndim != 2:
+        raise ValueError("a matrix of N rows and one column per marker")
+    if not (M.strides[0] == M.itemsize and M.strides[1] % M.itemsize == 0 and M.strides[1] >= M.shape[0] * M.itemsize):
+        M = np.asfortranarray(M)
+    return M, t, sfx, max(M.strides[1] // M.itemsize, M.shape[0])
+
+
 def write_panel_file(path, G, bits=8):
     """Genotype codes (N x P, uint8) as a binary panel file: 8 bits per genotype, or 2 (allele counts 0/1/2 only)."""
     G = np.asfortranarray(G, dtype=np.uint8)
@@ -476,6 +492,10 @@ class Sampler:
     def debug_set_knob(self, knob):
         self._chk(self.L.ngp_debug_set_knob(self.h, C.c_int32(knob)))
 
+    def debug_set_staging_bytes(self, nbytes):
+        """Test hook: the size every staged loader takes for its chunk in place of 256 MiB / 64 MiB (0: those)."""
+        self._chk(self.L.ngp_debug_set_staging_bytes(self.h, C.c_int64(int(nbytes))))
+
     def debug_set_mode(self, mode):
         self._chk(self.L.ngp_debug_set_mode(self.h, C.c_int32(mode)))
 
@@ -512,18 +532,12 @@ class Sampler:
         self.N, self.P = n, p
 
     def set_panel(self, M, centre=False):
-        M = np.asarray(M)
-        if M.dtype == np.uint8:  # one byte per genotype: converted and centred on the device
-            M = np.asfortranarray(M)
-            f, t = self.L.ngp_set_panel_u8, C.c_uint8
-        elif M.dtype == np.float32:
-            M = np.asfortranarray(M)
-            f, t = self.L.ngp_set_panel_f32, C.c_float
-        else:
-            M = np.asfortranarray(M, dtype=np.float64)
-            f, t = self.L.ngp_set_panel_f64, C.c_double
+        """uint8 (one byte per genotype: converted and centred on the device), float32 or float64; big[:N] of a taller Fortran-ordered
+        array goes over without a copy (_columns)."""
+        M, t, sfx, ld = _columns(M)
         self.N, self.P = M.shape
-        self._chk(f(self.h, _p(M, t), C.c_int64(self.N), C.c_int64(self.P), C.c_int64(self.N), C.c_int32(int(centre))))
+        f = getattr(self.L, "ngp_set_panel_" + sfx)
+        self._chk(f(self.h, _p(M, t), C.c_int64(self.N), C.c_int64(self.P), C.c_int64(ld), C.c_int32(int(centre))))
 
     def begin_panel(self, N, P):
         """A panel handed over in column ranges (one marker set after another, no concatenated host copy): begin_panel,
@@ -532,17 +546,10 @@ class Sampler:
         self.N, self.P = N, P
 
     def panel_columns(self, col0, M, centre=False):
-        M = np.asarray(M)
-        if M.dtype == np.uint8:     # genotype codes: the only form the compact storage takes
-            M = np.asfortranarray(M)
-            f, t = self.L.ngp_panel_columns_u8, C.c_uint8
-        elif M.dtype == np.float32:
-            M = np.asfortranarray(M)
-            f, t = self.L.ngp_panel_columns_f32, C.c_float
-        else:
-            M = np.asfortranarray(M, dtype=np.float64)
-            f, t = self.L.ngp_panel_columns_f64, C.c_double
-        self._chk(f(self.h, C.c_int64(col0), _p(M, t), C.c_int64(M.shape[1]), C.c_int64(M.shape[0]), C.c_int32(int(centre))))
+        """uint8 (genotype codes: the only form the compact storage takes), float32 or float64; big[:N] without a copy (_columns)."""
+        M, t, sfx, ld = _columns(M)
+        f = getattr(self.L, "ngp_panel_columns_" + sfx)
+        self._chk(f(self.h, C.c_int64(col0), _p(M, t), C.c_int64(M.shape[1]), C.c_int64(ld), C.c_int32(int(centre))))
 
     def end_panel(self):
         self._chk(self.L.ngp_end_panel(self.h))
@@ -580,18 +587,10 @@ class Sampler:
         self._chk(self.L.ngp_begin_prediction_panel(self.h, C.c_int64(Np)))
 
     def prediction_columns(self, col0, M, centre=False):
-        """centre: subtract the TRAINING panel's column means (means()), never means of these rows."""
-        M = np.asarray(M)
-        if M.dtype == np.uint8:     # genotype codes: the only form the compact storage takes
-            M = np.asfortranarray(M)
-            f, t = self.L.ngp_prediction_columns_u8, C.c_uint8
-        elif M.dtype == np.float32:
-            M = np.asfortranarray(M)
-            f, t = self.L.ngp_prediction_columns_f32, C.c_float
-        else:
-            M = np.asfortranarray(M, dtype=np.float64)
-            f, t = self.L.ngp_prediction_columns_f64, C.c_double
-        self._chk(f(self.h, C.c_int64(col0), _p(M, t), C.c_int64(M.shape[1]), C.c_int64(M.shape[0]), C.c_int32(int(centre))))
+        """centre: subtract the TRAINING panel's column means (means()), never means of these rows.  Input forms as panel_columns."""
+        M, t, sfx, ld = _columns(M)
+        f = getattr(self.L, "ngp_prediction_columns_" + sfx)
+        self._chk(f(self.h, C.c_int64(col0), _p(M, t), C.c_int64(M.shape[1]), C.c_int64(ld), C.c_int32(int(centre))))
 
     def end_prediction_panel(self):
         self._chk(self.L.ngp_end_prediction_panel(self.h))

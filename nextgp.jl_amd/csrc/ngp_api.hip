@@ -620,6 +620,7 @@ struct ngp_handle {
     int64_t dbg_census_fail_iter = 0;  // ngp_debug_fail_census: the sweep of this iteration ends at its census (once)
     std::unique_ptr<SampleStream> smp;  // ngp_set_sample_file
     int vdev = -1;           // ngp_debug_set_virtual_device: the device ngp_allreduce_posterior groups this handle under (-1: the real one)
+    int64_t dbg_staging_bytes = 0;  // ngp_debug_set_staging_bytes: in place of the 256 MiB / 64 MiB of every staged loader (0: those)
     std::string err;
 };
 
@@ -703,6 +704,9 @@ struct CuLease {
     void make_exclusive() { release(); acquire(true); }
     ~CuLease() { release(); }
 };
+
+// bytes one staging chunk of a host loader may hold: the loader's own constant unless a test shrank it (ngp_debug_set_staging_bytes)
+int64_t staging_bytes(const ngp_handle *h, int64_t dflt) { return h->dbg_staging_bytes > 0 ? h->dbg_staging_bytes : dflt; }
 
 int enter(ngp_handle *h, bool pred_call = false) {
     if (!h) return fail(nullptr, NGP_ERR_ARG, "null handle");
@@ -943,7 +947,7 @@ int panel_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, int64
     REQUIRE(h->req.storage == 0 || sizeof(TIn) == 1, NGP_ERR_ARG,
             "compact storage takes genotype codes: ngp_panel_columns_u8, ngp_set_panel_u8, ngp_load_panel_file or ngp_generate_panel");
     const int64_t N = h->N;
-    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, ((int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
+    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, staging_bytes(h, (int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
     DevArray<TIn> d_g;
     DevArray<unsigned> d_bad;
     if (d_g.alloc_raw((size_t)cchunk * ld) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
@@ -2394,7 +2398,7 @@ int32_t ngp_set_panel_u8(ngp_handle *h, const uint8_t *G, int64_t N, int64_t P, 
     if ((rc = alloc_panel(h, N, P))) return rc;
     // staged through the device in chunks of whole 64-column blocks (about 64 MiB of genotypes at a time)
     const int64_t blk_bytes = (int64_t)NGP_BLK * ld;
-    const int64_t nb_chunk = std::max<int64_t>(1, std::min<int64_t>(h->NBLK, ((int64_t)64 << 20) / blk_bytes));
+    const int64_t nb_chunk = std::max<int64_t>(1, std::min<int64_t>(h->NBLK, staging_bytes(h, (int64_t)64 << 20) / blk_bytes));
     DevArray<uint8_t> d_g;
     DevArray<double> d_mu;
     if (d_g.alloc_raw((size_t)nb_chunk * blk_bytes) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
@@ -2500,7 +2504,7 @@ int32_t ngp_load_panel_file(ngp_handle *h, const char *path, int32_t centre) {
     // the file streams through a pinned host buffer in chunks of whole 64-column blocks; two-bit columns are unpacked on the host
     const int64_t colbytes = (hd.bits == 8) ? N : (N + 3) / 4;
     const int64_t blk_bytes = (int64_t)NGP_BLK * N;
-    const int64_t nb_chunk = std::max<int64_t>(1, std::min<int64_t>(h->NBLK, ((int64_t)64 << 20) / blk_bytes));
+    const int64_t nb_chunk = std::max<int64_t>(1, std::min<int64_t>(h->NBLK, staging_bytes(h, (int64_t)64 << 20) / blk_bytes));
     DevArray<uint8_t> d_g;
     PinnedArray<uint8_t> h_g;
     DevArray<double> d_mu;
@@ -5008,6 +5012,20 @@ int32_t ngp_debug_set_virtual_device(ngp_handle *h, int32_t vdev) {
     NGP_CATCH(h)
 }
 
+/* Test hook of the staged loaders (tests/test_gpu_ingest.py): every host loop that stages a caller's matrix or a panel file through a
+ * fixed-size buffer (256 MiB of columns, 64 MiB of blocks) takes `bytes` for that size instead, so that a panel of a few hundred
+ * columns crosses many chunk boundaries.  Each loop rounds as before (one column, one 64-column block, 64 GRM columns at least).
+ * 0 = the defaults. */
+int32_t ngp_debug_set_staging_bytes(ngp_handle *h, int64_t bytes) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h, true))) return rc;
+    REQUIRE(bytes >= 0, NGP_ERR_ARG, "staging bytes: 0 (the defaults) or a positive size");
+    h->dbg_staging_bytes = bytes;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
 /* Test hook of the exception barrier (tests/test_abi.py): throws inside an entry point, past the same NGP_TRY / NGP_CATCH every
  * other one runs in.  kind 0: std::bad_alloc, 1: std::length_error (a std::vector asked for more than max_size), 2: a
  * non-standard exception.  h may be NULL (the message then goes where ngp_create's go).  Never returns NGP_OK. */
@@ -5063,7 +5081,7 @@ int grm_columns(ngp_handle *h, const TIn *M, int64_t ncol, int64_t ld) {
     REQUIRE(M != nullptr && ncol > 0, NGP_ERR_ARG, "genotype columns: a matrix of at least one column");
     REQUIRE(ld >= g.N, NGP_ERR_ARG, "leading dimension smaller than N");
     const int64_t N = g.N, Npad = g.m->ld;
-    int64_t cchunk = std::min<int64_t>((ncol + 63) / 64 * 64, ((int64_t)256 << 20) / (int64_t)(std::max<int64_t>(ld, Npad) * (int64_t)sizeof(double)));
+    int64_t cchunk = std::min<int64_t>((ncol + 63) / 64 * 64, staging_bytes(h, (int64_t)256 << 20) / (int64_t)(std::max<int64_t>(ld, Npad) * (int64_t)sizeof(double)));
     cchunk = std::max<int64_t>(64, cchunk / 64 * 64);
     DevArray<TIn> d_g;
     DevArray<double> d_xc, d_tp;
@@ -5366,7 +5384,7 @@ int prediction_columns(ngp_handle *h, int64_t col0, const TIn *M, int64_t ncol, 
     REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "column range outside the panel");
     REQUIRE(h->req.storage == 0 || sizeof(TIn) == 1, NGP_ERR_ARG, "compact storage takes genotype codes: ngp_prediction_columns_u8 or ngp_load_prediction_file");
     const int64_t Np = pp.Np, Lp = pp.R * pp.S;
-    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, ((int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
+    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, staging_bytes(h, (int64_t)256 << 20) / (int64_t)(ld * sizeof(TIn))));
     DevArray<TIn> d_g;
     DevArray<unsigned> d_bad;
     DevArray<double> d_scr;
@@ -5470,7 +5488,7 @@ int32_t ngp_load_prediction_file(ngp_handle *h, const char *path, int32_t centre
     if ((rc = begin_prediction(h, N))) return rc;
     // whole columns through a host buffer of about 64 MiB; two-bit columns are unpacked on the host
     const int64_t colbytes = (hd.bits == 8) ? N : (N + 3) / 4;
-    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(P, ((int64_t)64 << 20) / N));
+    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(P, staging_bytes(h, (int64_t)64 << 20) / N));
     std::vector<uint8_t> buf((size_t)cchunk * (size_t)N), packed((hd.bits == 2) ? (size_t)colbytes : 0);
     std::string why;
     rc = NGP_OK;
