@@ -692,6 +692,36 @@ int32_t ngp_fix_residual_variance(ngp_handle *h, double v);
 int32_t ngp_tnormal_indexed(ngp_handle *h, uint64_t iter, uint64_t kind, uint64_t index0, const double *a, const double *b, int64_t n,
                             double *out);
 
+/* ---- ordered traits on the scale of the trait: Cowles' threshold step, class probabilities of held-out records ----
+ * Both are options of a handle with liability classes; without them nothing is launched and every format is byte for byte what it
+ * was ("Normal distribution function", "Cowles' threshold step", "Class probabilities": normative).
+ * ngp_set_threshold_step: mode 0 = Albert-Chib (the default: each threshold uniform between the liabilities of its two classes),
+ *   mode 1 = Cowles (1996): one joint Metropolis-Hastings move of t_2 .. t_{C-1} per iteration, proposed from truncated normals of SD
+ *   sigma around the current values and decided on the records' fitted values alone; the liabilities are redrawn behind it as before.
+ *   sigma > 0 is a fixed proposal SD; sigma = 0 starts at 1 / sqrt(m) and follows the acceptance rate (target 0.44) in the iterations
+ *   <= burnIn, fixed from then on.  After ngp_set_liability_classes (which puts the step back to mode 0) and before ngp_set_y:
+ *   NGP_ERR_STATE without classes or once y is set, NGP_ERR_ARG for mode 1 with C < 3, a mode other than 0 / 1 or sigma < 0; a failed
+ *   call changes nothing.
+ * ngp_get_threshold_step: the mode, the SD in force (0 in mode 0) and the proposals made / taken since ngp_set_y (any pointer may be
+ *   NULL); ngp_set_threshold_step_state puts the last three back (resume).
+ * In mode 1 a snapshot appends sigma | tries | accepted and its signature names the mode: a handle in the other mode refuses it.
+ * ngp_enable_class_probabilities: needs classes AND a hold-out mask, before ngp_set_y (NGP_ERR_STATE otherwise).  In every kept
+ *   iteration p_c = Phi((t_c - fit) / sd) - Phi((t_{c-1} - fit) / sd) of every held-out record is added to sum_prob[c-1][k]; the
+ *   number of draws is n_fit of ngp_get_holdout.  ngp_get_class_probabilities: sum_prob[C][m], class-major, rows in the order of the
+ *   hold-out set; ngp_set_class_probabilities puts it back (resume).  The packed posterior and the snapshot body then end with
+ *   sum_prob[C m]; ngp_allreduce_posterior pools it over chains that hold out the SAME records and refuses (NGP_ERR_ARG) chains whose
+ *   masks differ, since the sums are laid out by position in the hold-out set (pool fold-chains on the host).  A snapshot is refused by a
+ *   handle without the option, and the other way round.
+ * ngp_debug_pnorm: test probe; which 0: out[i] = Phi(a[i]) (b may be NULL), 1: out[i] = log(Phi(b[i]) - Phi(a[i])), -inf unless
+ *   a[i] < b[i]. */
+int32_t ngp_set_threshold_step(ngp_handle *h, int32_t mode, double sigma);
+int32_t ngp_get_threshold_step(ngp_handle *h, int32_t *mode, double *sigma, int64_t *tries, int64_t *accepted);
+int32_t ngp_set_threshold_step_state(ngp_handle *h, double sigma, int64_t tries, int64_t accepted);
+int32_t ngp_enable_class_probabilities(ngp_handle *h, int32_t on);
+int32_t ngp_get_class_probabilities(ngp_handle *h, double *sum_prob, int64_t m, int32_t C);
+int32_t ngp_set_class_probabilities(ngp_handle *h, const double *sum_prob, int64_t m, int32_t C);
+int32_t ngp_debug_pnorm(ngp_handle *h, int32_t which, const double *a, const double *b, int64_t n, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,7 +202,11 @@ SYMBOLS = [
     "ngp_set_liability_classes", "ngp_set_liability_bounds", "ngp_get_liability_layout", "ngp_get_liability", "ngp_set_liability_state",
     "ngp_get_liability_stats", "ngp_fix_residual_variance", "ngp_tnormal_indexed",
     "ngp_debug_set_staging_bytes",
+    "ngp_set_threshold_step", "ngp_get_threshold_step", "ngp_set_threshold_step_state",
+    "ngp_enable_class_probabilities", "ngp_get_class_probabilities", "ngp_set_class_probabilities", "ngp_debug_pnorm",
 ]
+
+THRESHOLD_STEPS = {"albert-chib": 0, "cowles": 1}
 
 _lib = None
 
@@ -227,6 +231,36 @@ def holdout_summary(hs):
     mean = np.asarray(hs["sum_fit"])[rows] / n[rows]
     sd = np.sqrt(np.maximum(0.0, np.asarray(hs["sum_fit2"])[rows] / n[rows] - mean * mean))
     return dict(rows=rows.astype(np.int64), n=n[rows].astype(np.int64), mean=mean, sd=sd)
+
+
+def class_metrics(prob, obs):
+    """Scores of class probabilities prob[n][C] against the observed classes obs[n] (1..C): {"n", "brier" (sum over the classes of the
+    squared error, mean over the records), "logloss" (mean of -log p of the observed class, p floored at the smallest normal double),
+    "class_accuracy" (share of the records whose most probable class is the observed one; ties go to the lower class)} and, for
+    C == 2, "auc": the probability that a record of class 2 has a larger p_2 than a record of class 1, ties counting half (NaN when a
+    class has no record)."""
+    p = np.asarray(prob, dtype=np.float64)
+    o = np.asarray(obs).astype(np.int64)
+    n, nc = p.shape
+    if n == 0:
+        out = dict(n=0, brier=float("nan"), logloss=float("nan"), class_accuracy=float("nan"))
+        if nc == 2:
+            out["auc"] = float("nan")
+        return out
+    hit = np.zeros_like(p)
+    hit[np.arange(n), o - 1] = 1.0
+    po = p[np.arange(n), o - 1]
+    out = dict(n=int(n), brier=float(((p - hit) ** 2).sum(axis=1).mean()), logloss=float(-np.log(np.maximum(po, np.finfo(np.float64).tiny)).mean()),
+               class_accuracy=float((p.argmax(axis=1) + 1 == o).mean()))
+    if nc == 2:
+        npos, nneg = int((o == 2).sum()), int((o == 1).sum())
+        if npos and nneg:   # rank-sum with average ranks
+            _, inv, cnt = np.unique(p[:, 1], return_inverse=True, return_counts=True)
+            rank = (np.cumsum(cnt) - (cnt - 1) / 2.0)[inv]
+            out["auc"] = float((rank[o == 2].sum() - npos * (npos + 1) / 2.0) / (float(npos) * float(nneg)))
+        else:
+            out["auc"] = float("nan")
+    return out
 
 
 LIABILITY_MAX_CLASSES = 8
@@ -1117,6 +1151,66 @@ class Sampler:
         n = C.c_int64()
         self._chk(self.L.ngp_get_liability_stats(self.h, C.byref(n)))
         return n.value
+
+    # ---- ordered traits: Cowles' threshold step, class probabilities of held-out records ----
+    def set_threshold_step(self, mode="cowles", sigma=0.0):
+        """How the thresholds of C >= 3 classes move: "albert-chib" (the default of a handle: uniform between the liabilities of the
+        two classes) or "cowles" (one joint Metropolis-Hastings move per iteration, decided on the fitted values alone; it mixes where
+        a class holds many records).  sigma > 0 is a fixed proposal SD, 0 one that starts at 1 / sqrt(m) and follows the acceptance
+        rate during burn-in.  After set_classes, before set_y."""
+        if mode not in THRESHOLD_STEPS:
+            raise ValueError(f"set_threshold_step: mode is one of {sorted(THRESHOLD_STEPS)}")
+        self._chk(self.L.ngp_set_threshold_step(self.h, C.c_int32(THRESHOLD_STEPS[mode]), C.c_double(float(sigma))))
+
+    def threshold_step(self):
+        """{"mode" ("albert-chib" / "cowles"), "sigma" (the proposal SD in force, 0 under Albert-Chib), "tries", "accepted"}."""
+        mode = C.c_int32(); sigma = C.c_double(); tries = C.c_int64(); acc = C.c_int64()
+        self._chk(self.L.ngp_get_threshold_step(self.h, C.byref(mode), C.byref(sigma), C.byref(tries), C.byref(acc)))
+        return dict(mode={v: k for k, v in THRESHOLD_STEPS.items()}[mode.value], sigma=sigma.value, tries=tries.value, accepted=acc.value)
+
+    def set_threshold_step_state(self, ts):
+        """Put back what threshold_step() gave (resume beside set_liability_state)."""
+        self._chk(self.L.ngp_set_threshold_step_state(self.h, C.c_double(float(ts["sigma"])), C.c_int64(int(ts["tries"])), C.c_int64(int(ts["accepted"]))))
+
+    def enable_class_probabilities(self, on=True):
+        """Accumulate P(class) of every held-out record in every kept iteration (class_probabilities()).  Needs classes and a hold-out
+        mask; before set_y."""
+        self._chk(self.L.ngp_enable_class_probabilities(self.h, C.c_int32(int(bool(on)))))
+
+    def class_probability_sums(self):
+        """sum_prob[C][m]: the sums over kept draws as the library holds them (class-major, rows in the order of the hold-out set)."""
+        m = C.c_int64()
+        self._chk(self.L.ngp_get_holdout_layout(self.h, C.byref(m)))
+        _, c = self.liability_layout()
+        out = np.empty((c, m.value))
+        self._chk(self.L.ngp_get_class_probabilities(self.h, _p(out, C.c_double), m, C.c_int32(c)))
+        return out
+
+    def set_class_probability_sums(self, sum_prob):
+        """Put back what class_probability_sums() gave (resume beside set_holdout_state)."""
+        a = np.ascontiguousarray(sum_prob, dtype=np.float64)
+        self._chk(self.L.ngp_set_class_probabilities(self.h, _p(a, C.c_double), C.c_int64(a.shape[1]), C.c_int32(a.shape[0])))
+
+    def class_probabilities(self):
+        """{"rows", "n", "prob" (m x C)}: the posterior mean of P(class) of every held-out record with at least one kept draw; after
+        allreduce_posterior over fold-chains that share one mask, of their pooled draws."""
+        hs = self.holdout_state()
+        n = hs["n_fit"][hs["rows"]]
+        if not (n > 0).any():
+            raise ValueError("no kept draw yet: the class probabilities are empty")
+        sp = self.class_probability_sums()
+        keep = n > 0
+        return dict(rows=hs["rows"][keep], n=n[keep].astype(np.int64), prob=np.ascontiguousarray((sp[:, keep] / n[keep]).T))
+
+    def debug_pnorm(self, which, a, b=None):
+        """Test probe of the normal distribution function: which 0: Phi(a), 1: log(Phi(b) - Phi(a))."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        if b is not None and b.shape != a.shape:
+            raise ValueError("debug_pnorm: a and b are vectors of one length")
+        out = np.empty(len(a))
+        self._chk(self.L.ngp_debug_pnorm(self.h, C.c_int32(int(which)), _p(a, C.c_double), _p(b, C.c_double), C.c_int64(len(a)), _p(out, C.c_double)))
+        return out
 
     def fix_residual_variance(self, v):
         """v > 0 holds varE = v from set_y on (no draw; the trace reports v); 0 returns to sampling."""

@@ -712,7 +712,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -772,6 +772,16 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     the censored records; varE is sampled as usual.  The two exclude one another.  With samples="text" and C >= 3 thresholdOut holds the
     thresholds of every kept draw (columns t2 .. t{C-1}; per chain under chain<c>/ with chains=K); its column means are res["thresholds"]["mean"]
     (the text round-trips every double).
+    (12) ordered traits on the scale of the trait (ngp_set_threshold_step / ngp_enable_class_probabilities; DESIGN.md section 2,
+    "Cowles' threshold step", "Class probabilities"), both with trait="categorical" only (ValueError otherwise).
+    thresholdStep="cowles" (three classes or more, else ValueError) moves the thresholds by Cowles' joint Metropolis-Hastings step,
+    which mixes where a class holds thousands of records and the default "albert-chib" step barely moves; res["thresholds"] gains
+    "acceptance" (accepted / proposed, pooled over the chains) and "sigma" (the proposal SD after burn-in, the mean over the chains).
+    classProb=True, together with any of folds= / holdout= / missing="holdout" (ValueError without one), accumulates P(class) of every
+    held-out record per kept draw: res["holdout"]["prob"] (records x C, beside "rows") and outFolder/holdoutProb.txt; with folds=K
+    res["cv"]["prob"] (N x C, NaN where not validated), "brier", "logloss", "class_accuracy" (arg-max class) and, for two classes,
+    "auc" (class_metrics), each also in every entry of "per_fold", and cvProb.txt: record fold class p1 .. pC (records from 1, fold -1
+    and class 0 where there is none).  holdoutPredict.txt and cvPredict.txt keep their columns.
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -789,6 +799,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     masks, cv_fold, chains = _holdout_masks(y, holdout, missing, folds, foldSeed, chains)   # (checked before any device work)
     if liab is not None and liab["kind"] == "classes" and missing != "holdout" and np.any(liab["codes"] == 0):
         raise ValueError('trait="categorical": a record has no response (NaN); missing="holdout" predicts such records')
+    _ordered_options(trait, liab, thresholdStep, classProb, masks)
     if liab is not None and liab["kind"] == "bounds" and masks is not None and any(len(np.intersect1d(m, liab["rows"])) for m in masks):
         raise ValueError("censored: a censored record cannot be held out as well (holdout=, folds=); records without any bound are missing records")
     ped = None
@@ -928,6 +939,10 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         for sc in samplers:
             if liab["kind"] == "classes":
                 sc.set_classes(np.maximum(liab["codes"], 1), liab["C"])   # (a record without a response is held out: its entry is not read)
+                if thresholdStep == "cowles":
+                    sc.set_threshold_step("cowles", 0.0)
+                if classProb:
+                    sc.enable_class_probabilities(True)
             else:
                 sc.set_censored(liab["rows"], liab["lo"], liab["hi"])
     built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
@@ -965,6 +980,14 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
             r["thresholds"] = _threshold_summary(ls["sum_thr"], ls["sum_thr2"], r["nKept"])
         res["thresholds"] = _threshold_summary(sum(ls["sum_thr"] for ls in states), sum(ls["sum_thr2"] for ls in states), res["nKept"])
         res["classes"] = liab["values"]
+        if thresholdStep == "cowles":
+            steps = [sc.threshold_step() for sc in samplers]
+            for r, ts in zip(res.get("chains", []), steps):
+                r["thresholds"].update(acceptance=ts["accepted"] / max(ts["tries"], 1), sigma=ts["sigma"])
+            res["thresholds"].update(acceptance=sum(ts["accepted"] for ts in steps) / max(sum(ts["tries"] for ts in steps), 1),
+                                     sigma=float(np.mean([ts["sigma"] for ts in steps])))
+        if classProb:
+            _class_prob_results(res, samplers, masks, cv_fold, liab["codes"], liab["C"], outFolder)
     if gv_windows is not None:
         by_id = sorted(sets, key=lambda st: st["id"])                       # slot order: the device's set order
         names = [st["name"] for st in by_id]
@@ -1010,6 +1033,66 @@ def _liability_spec(trait, censored, y, userData, VCV):
     ye = np.where(np.isnan(lower) | np.isinf(lower), upper, lower).astype(np.float64)   # exact records: lower == upper
     ye[rows] = 0.0                                                                     # (not read on the censored records)
     return dict(kind="bounds", rows=rows, lo=lo, hi=hi, y=ye)
+
+
+def _ordered_options(trait, liab, thresholdStep, classProb, masks):
+    """runLMEM(thresholdStep=..., classProb=...): host checks only; a ValueError here comes before any device work."""
+    from ._lib import THRESHOLD_STEPS
+    if thresholdStep not in THRESHOLD_STEPS:
+        raise ValueError(f"thresholdStep: one of {sorted(THRESHOLD_STEPS)}")
+    if classProb not in (True, False):
+        raise ValueError("classProb: True or False")
+    if trait != "categorical":
+        if thresholdStep != "albert-chib":
+            raise ValueError('thresholdStep: only a trait="categorical" model has thresholds')
+        if classProb:
+            raise ValueError('classProb: only a trait="categorical" model has classes')
+        return
+    if thresholdStep == "cowles" and liab["C"] < 3:
+        raise ValueError('thresholdStep="cowles": two classes have no threshold to move (three classes or more)')
+    if classProb and masks is None:
+        raise ValueError('classProb: the probabilities are those of held-out records; give folds=, holdout= or missing="holdout"')
+
+
+def _class_prob_results(res, samplers, masks, cv_fold, codes, C, outFolder):
+    """res["holdout"]["prob"] / holdoutProb.txt (the records every chain holds out, sums pooled over the chains) and, for folds=K,
+    res["cv"]["prob"], its scores and cvProb.txt (every record with a response, by the chain that held its fold out)."""
+    from ._lib import class_metrics
+    N = len(codes)
+    hstates = [sc.holdout_state() for sc in samplers]
+    sums = [sc.class_probability_sums() for sc in samplers]   # [C][m of the chain], rows in the order of the chain's mask
+
+    def write(path, rows, fold, prob):
+        with open(os.path.join(outFolder, path), "w") as f:
+            f.write("record\tfold\tclass\t" + "\t".join(f"p{c}" for c in range(1, C + 1)) + "\n")
+            for i, p in zip(rows, prob):
+                f.write(f"{i + 1}\t{-1 if fold is None else fold[i]}\t{int(codes[i])}\t" + "\t".join(repr(float(v)) for v in p) + "\n")
+
+    for r, hs, sp in zip(res.get("chains", []), hstates, sums):
+        n = hs["n_fit"][hs["rows"]]
+        r["holdout"]["prob"] = (sp[:, n > 0] / n[n > 0]).T
+    if "holdout" in res:   # the rows every chain holds out: the chains' sums added, divided by the draws of all of them
+        rows = res["holdout"]["rows"]
+        tot = np.zeros((C, len(rows))); n = np.zeros(len(rows))
+        for hs, sp in zip(hstates, sums):
+            at = np.searchsorted(hs["rows"], rows)
+            tot += sp[:, at]; n += hs["n_fit"][rows]
+        res["holdout"]["prob"] = (tot / n).T
+        write("holdoutProb.txt", rows, None, res["holdout"]["prob"])
+    if cv_fold is None:
+        return
+    prob = np.full((N, C), np.nan)
+    for c, (hs, sp) in enumerate(zip(hstates, sums)):
+        own = np.flatnonzero(cv_fold == c)
+        own = own[hs["n_fit"][own] > 0]
+        prob[own] = (sp[:, np.searchsorted(hs["rows"], own)] / hs["n_fit"][own]).T
+    val = np.flatnonzero((cv_fold >= 0) & ~np.isnan(prob[:, 0]))
+    res["cv"]["prob"] = prob
+    res["cv"].update({k: v for k, v in class_metrics(prob[val], codes[val]).items() if k != "n"})
+    for pf in res["cv"]["per_fold"]:
+        v = val[cv_fold[val] == pf["fold"]]
+        pf.update({k: s for k, s in class_metrics(prob[v], codes[v]).items() if k != "n"})
+    write("cvProb.txt", val, cv_fold, prob[val])
 
 
 def _threshold_summary(sum_thr, sum_thr2, nKept):

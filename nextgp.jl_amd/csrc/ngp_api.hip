@@ -35,6 +35,7 @@
 #include "ngp_predict.h"
 #include "ngp_holdout.h"
 #include "ngp_liability.h"
+#include "ngp_threshold.h"
 #include "ngp_genvar.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
@@ -462,6 +463,15 @@ struct Liab {
     DevArray<long long> d_rows;
     DevArray<int> d_cls;
     DevArray<double> d_lo, d_hi, d_liab, d_thr;
+    // Cowles' threshold step (ngp_threshold.h; ngp_set_threshold_step): 0 = Albert-Chib, 1 = Cowles; adapt: sigma was given as 0 and
+    // follows the acceptance rate through burn-in; d_ts the step's words, d_tg = g[C+1] | in-order flag, d_tpart the workgroups' partials
+    int ts_mode = 0;
+    bool ts_adapt = false;
+    double ts_sigma0 = 0.0;  // the SD a fresh chain starts with (ngp_set_y): the caller's, or 1 / sqrt(m) under adaptation
+    DevArray<ThrStep> d_ts;
+    DevArray<double> d_tg, d_tpart;
+    // class probabilities of the held-out records (ngp_enable_class_probabilities): sum_prob[C][m_holdout], class-major; null when off
+    DevArray<double> d_sum_prob;
     bool on() const { return !rows.empty(); }
     size_t thr_bytes() const { return C >= 2 ? (size_t)(C - 1) * 8 : 0; }  // t_1 .. t_{C-1}, as the formats carry them
 };
@@ -1608,7 +1618,16 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     if (const long long m = (long long)h->cm.lb.rows.size()) {  // liability traits: thresholds (C >= 3), then every liability (ycorr_i <- e_i)
         const Liab &lb = h->cm.lb;
         const int C1 = lb.C + 1;
-        if (lb.C >= 3)
+        if (lb.C >= 3 && lb.ts_mode == 1) {  // Cowles' joint move in the place of k_thresholds: proposal and likelihood terms, then the decision
+            const int nwg = (int)((m + NGP_THR_WG - 1) / NGP_THR_WG);
+            hipLaunchKernelGGL(k_threshold_terms, dim3((unsigned)nwg), dim3(NGP_THR_WG), 0, h->stream, (const long long *)lb.d_rows.get(), (const int *)lb.d_cls.get(),
+                               (const double *)lb.d_liab.get(), m, lb.C, (const double *)h->cm.d_ycorr.get(), (const double *)h->cm.d_rs, (const DScal *)h->cm.d_scal,
+                               (const double *)lb.d_thr.get(), (const ThrStep *)lb.d_ts.get(), lb.d_tg.get(), lb.d_tpart.get(), h->seed, (uint64_t)h->chain, it,
+                               h->hm.d_tn_fall.get(), (const unsigned *)h->cm.d_abort);
+            hipLaunchKernelGGL(k_threshold_decide, dim3(1), dim3(64), 0, h->stream, lb.C, lb.d_thr.get(), lb.d_thr.get() + C1, lb.d_thr.get() + 2 * C1,
+                               (const double *)lb.d_tg.get(), (const double *)lb.d_tpart.get(), nwg, lb.d_ts.get(), (int)is_kept(h, h->iter + 1),
+                               (int)(lb.ts_adapt && h->iter + 1 <= h->burnIn), h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
+        } else if (lb.C >= 3)
             hipLaunchKernelGGL(k_thresholds, dim3(1), dim3(1024), 0, h->stream, (const int *)lb.d_cls.get(), (const double *)lb.d_liab.get(), m, lb.C, lb.d_thr.get(),
                                lb.d_thr.get() + C1, lb.d_thr.get() + 2 * C1, (int)is_kept(h, h->iter + 1), h->seed, (uint64_t)h->chain, it, (const unsigned *)h->cm.d_abort);
         hipLaunchKernelGGL(k_liability_augment, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)lb.d_rows.get(), m, h->cm.d_ycorr.get(),
@@ -1670,6 +1689,13 @@ int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true, bool g
             hipLaunchKernelGGL(k_holdout_accum, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)h->cm.d_ho_rows, m,
                                (const double *)h->cm.d_ycorr, (const double *)h->cm.d_yaug, (const double *)h->cm.d_rs, h->cm.d_sum_fit.get(), h->cm.d_sum_fit2.get(),
                                h->cm.d_n_fit.get(), (const unsigned *)h->cm.d_abort);
+        if (h->cm.lb.d_sum_prob) {  // ... and their class probabilities under the thresholds of this draw
+            const Liab &lb = h->cm.lb;
+            const long long m = (long long)h->cm.ho_rows.size();
+            hipLaunchKernelGGL(k_holdout_prob, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const long long *)h->cm.d_ho_rows, m, lb.C,
+                               (const double *)h->cm.d_ycorr, (const double *)h->cm.d_yaug, (const double *)h->cm.d_rs, (const DScal *)h->cm.d_scal,
+                               (const double *)lb.d_thr.get(), lb.d_sum_prob.get(), (const unsigned *)h->cm.d_abort);
+        }
         if (predict && predicts(h)) launch_predict(h, &h, 1);  // g = X_new beta of this draw, behind the posterior sums
         if (genvar && gv_active(h))                            // var(X beta) of this draw per window, set and in all
             if (int e = launch_genvar(h, &h, 1)) return e;
@@ -1749,6 +1775,15 @@ uint64_t liab_digest(const Liab &lb) {  // FNV-1a over the rows, C and the class
     eat(lb.lo.data(), lb.lo.size() * 8); eat(lb.hi.data(), lb.hi.size() * 8);
     return d;
 }
+// ... as the snapshot signature carries it: the word ts_mode + 2 (class probabilities on) is folded in where it is not 0, so a chain
+// under Albert-Chib without class probabilities keeps the digest every earlier snapshot has
+uint64_t liab_sig_digest(uint64_t digest, int ts_mode, bool prob) {
+    const uint32_t w = (uint32_t)ts_mode + (prob ? 2u : 0u);
+    if (w == 0) return digest;
+    uint64_t d = digest;
+    for (int i = 0; i < 4; i++) { d ^= (unsigned char)((w >> (8 * i)) & 0xff); d *= 1099511628211ull; }
+    return d;
+}
 // Start values (ngp_set_y; DESIGN.md section 2, "Liability traits").  Classes: t_c = ppnd16(F_c) - ppnd16(F_1) with F_c the cumulative
 // class frequency over the augmented rows (ppnd16 on the device: the draw layer's own), the liability the midpoint of an inner
 // interval, t_1 - 0.5 in class 1, t_{C-1} + 0.5 in class C.  Bounds: the finite bound where only one is, else the midpoint.  y_out: y
@@ -1781,6 +1816,11 @@ int start_liabilities(ngp_handle *h, const double *y, std::vector<double> &y_out
         }
         y_out.assign((size_t)h->N, 0.0);
         HCHK(hipMemcpy(lb.d_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice));
+        if (lb.ts_mode == 1) {  // a fresh chain: the proposal SD it starts with, nothing proposed yet
+            const ThrStep t0{lb.ts_sigma0, 0, 0};
+            HCHK(hipMemcpy(lb.d_ts, &t0, sizeof t0, hipMemcpyHostToDevice));
+        }
+        if (lb.d_sum_prob) HCHK(hipMemset(lb.d_sum_prob, 0, (size_t)C * h->cm.ho_rows.size() * 8));
     } else {
         for (size_t k = 0; k < m; k++) {
             const bool fl = std::isfinite(lb.lo[k]), fh = std::isfinite(lb.hi[k]);
@@ -1844,6 +1884,8 @@ void describe(ngp_handle *h, ChainState &st) {
             st.dev(SEG_THR, 0, lb.d_thr + 1, lb.thr_bytes());
             st.dev(SEG_SUM_THR, 0, lb.d_thr + C1 + 1, lb.thr_bytes()); st.dev(SEG_SUM_THR2, 0, lb.d_thr + 2 * C1 + 1, lb.thr_bytes());
             if (lb.C >= 3) st.dev(SEG_THR_SMP, 0, lb.d_thr + 2, (size_t)(lb.C - 2) * 8);  // the drawn thresholds: what a sample record carries
+            if (lb.ts_mode == 1) st.dev(SEG_THR_STEP, 0, lb.d_ts, sizeof(ThrStep));        // Cowles' step: sigma | tries | accepted
+            if (lb.d_sum_prob) st.dev(SEG_SUM_PROB, 0, lb.d_sum_prob, (size_t)lb.C * h->cm.ho_rows.size() * 8);
         }
     }
 }
@@ -3592,7 +3634,7 @@ struct ModelSig {
         for (auto &hs : h->sets) sets.insert(sets.end(), {hs.method, hs.K + 16 * hs.tk + lv_sig(h, hs) + rc_sig(h, hs), hs.nreg, hs.col0, hs.ncol});
         nfs = (int64_t)h->mm.fix.size() | (h->h_rw.empty() ? 0 : NGP_SNAP_WEIGHTED) | (h->mm.rnd.empty() ? 0 : NGP_SNAP_RANDOM) |
               (h->cm.ho_rows.empty() ? 0 : NGP_SNAP_HOLDOUT) | (h->cm.lb.on() ? NGP_SNAP_LIABILITY : 0) | (h->fix_varE > 0.0 ? NGP_SNAP_FIXVARE : 0);
-        lb_digest = h->cm.lb.digest; fix_varE = h->fix_varE;
+        lb_digest = liab_sig_digest(h->cm.lb.digest, h->cm.lb.ts_mode, (bool)h->cm.lb.d_sum_prob); fix_varE = h->fix_varE;
         if (!h->h_rw.empty()) digest = weights_digest(h->h_rw);
         if (!h->cm.ho_rows.empty()) ho_digest = rows_digest(h->cm.ho_rows);
         if (!h->mm.rnd.empty()) {
@@ -3683,8 +3725,19 @@ int32_t ngp_load_snapshot(ngp_handle *h, const char *path) {
         if (ok && snap_l != h->cm.lb.on())
             return fail(h, NGP_ERR_ARG, snap_l ? "snapshot of a chain with liability traits: this handle has none (ngp_set_liability_classes / ngp_set_liability_bounds)"
                                                : "snapshot of a chain without liability traits: this handle has them");
-        if (ok && snap_l && got.lb_digest != want.lb_digest)
+        if (ok && snap_l && got.lb_digest != want.lb_digest) {
+            const Liab &lb = h->cm.lb;
+            const bool prob = (bool)lb.d_sum_prob;
+            for (int w = 0; w < 4; w++) {  // the same rows and classes under another threshold step, or with / without class probabilities?
+                if (got.lb_digest != liab_sig_digest(lb.digest, w & 1, (w & 2) != 0)) continue;
+                if ((w & 1) != lb.ts_mode)
+                    return fail(h, NGP_ERR_ARG, (w & 1) ? "snapshot of a chain under Cowles' threshold step: this handle runs Albert-Chib (ngp_set_threshold_step)"
+                                                        : "snapshot of a chain under the Albert-Chib threshold step: this handle runs Cowles' (ngp_set_threshold_step)");
+                return fail(h, NGP_ERR_ARG, prob ? "snapshot of a chain without class probabilities: this handle has them (ngp_enable_class_probabilities)"
+                                                 : "snapshot of a chain with class probabilities: this handle has none (ngp_enable_class_probabilities)");
+            }
             return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its liability rows, classes or bounds differ)");
+        }
         if (ok && (snap_f != (h->fix_varE > 0.0) || (snap_f && got.fix_varE != want.fix_varE)))
             return fail(h, NGP_ERR_ARG, "snapshot does not match the model of this handle (its residual variance is fixed at another value, or sampled)");
         if (ok && snap_h != !h->cm.ho_rows.empty())
@@ -3858,6 +3911,10 @@ int32_t ngp_allreduce_posterior(ngp_handle **hs, int32_t n) {
         ChainState sti;  // one model: the packed posteriors hold the same segments, each of the same length
         describe(hs[i], sti);
         REQUIRE(place(sti, posterior_layout).same_shape(pl0), NGP_ERR_ARG, "ngp_allreduce_posterior: the chains do not share one model");
+        // (sum_fit is indexed by the record, sum_prob by the position in the hold-out set: it pools only over chains with one mask)
+        REQUIRE(!hs[i]->cm.lb.d_sum_prob || hs[i]->cm.ho_rows == h->cm.ho_rows, NGP_ERR_ARG,
+                "ngp_allreduce_posterior: class probabilities are summed by position in the hold-out set and these chains hold out different records "
+                "(pool fold-chains on the host, from ngp_get_class_probabilities)");
         for (int k = 0; k < i; k++) REQUIRE(hs[k] != hs[i], NGP_ERR_ARG, "ngp_allreduce_posterior: a handle is listed twice");
     }
     struct Buffers {  // the packed sums of every handle, on its device: freed there, with that device current
@@ -5996,6 +6053,148 @@ int32_t ngp_tnormal_indexed(ngp_handle *h, uint64_t iter, uint64_t kind, uint64_
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("tnormal draws: ") + hipGetErrorString(e));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* probe of the normal distribution function (ngp_pnorm.h): which 0: out[i] = det_pnorm(a[i]) (b may be NULL); 1: out[i] =
+ * det_lpdiff(a[i], b[i]) */
+int32_t ngp_debug_pnorm(ngp_handle *h, int32_t which, const double *a, const double *b, int64_t n, double *out) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE((which == 0 || which == 1) && a && (b || which == 0) && out && n > 0, NGP_ERR_ARG, "bad buffers");
+    DevArray<double> da, db, d;
+    if ((rc = da.alloc(h, (size_t)n)) || (rc = db.alloc(h, (size_t)n)) || (rc = d.alloc(h, (size_t)n))) return rc;
+    hipError_t e = hipMemcpyAsync(da, a, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, which == 1 ? b : a, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_pnorm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int)which, (const double *)da.get(), (const double *)db.get(),
+                           (long long)n, d.get());
+        e = hipMemcpyAsync(out, d, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("pnorm probe: ") + hipGetErrorString(e));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Cowles' threshold step ("Cowles' threshold step"; kernels in ngp_threshold.h).  mode 0: Albert-Chib (the
+ * default), 1: Cowles' joint Metropolis-Hastings move; sigma > 0 a fixed proposal SD, 0 one that follows the acceptance rate through
+ * burn-in.  After ngp_set_liability_classes (which puts the step back to mode 0) and before ngp_set_y. */
+int32_t ngp_set_threshold_step(ngp_handle *h, int32_t mode, double sigma) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.on() && lb.C >= 2, NGP_ERR_STATE, "ngp_set_threshold_step: no liability classes on this handle (ngp_set_liability_classes comes first)");
+    REQUIRE(!h->have_y, NGP_ERR_STATE, "ngp_set_threshold_step: the phenotypes are set already; the threshold step comes before ngp_set_y");
+    REQUIRE(mode == 0 || mode == 1, NGP_ERR_ARG, "ngp_set_threshold_step: mode 0 (Albert-Chib) or 1 (Cowles)");
+    REQUIRE(sigma >= 0.0 && std::isfinite(sigma), NGP_ERR_ARG, "ngp_set_threshold_step: sigma > 0 (a fixed proposal SD) or 0 (adapted during burn-in)");
+    REQUIRE(mode == 0 || lb.C >= 3, NGP_ERR_ARG, "ngp_set_threshold_step: two classes have no threshold to move (Cowles' step needs C >= 3)");
+    if (mode == 0) {
+        lb.ts_mode = 0; lb.ts_adapt = false; lb.ts_sigma0 = 0.0;
+        lb.d_ts.reset(); lb.d_tg.reset(); lb.d_tpart.reset();
+        return NGP_OK;
+    }
+    const size_t m = lb.rows.size(), nwg = (m + NGP_THR_WG - 1) / NGP_THR_WG;
+    DevArray<ThrStep> d_ts;
+    DevArray<double> d_tg, d_tpart;
+    if ((rc = d_ts.alloc(h, 1)) || (rc = d_tg.alloc(h, (size_t)lb.C + 2)) || (rc = d_tpart.alloc(h, nwg))) return rc;
+    const double s0 = sigma > 0.0 ? sigma : 1.0 / std::sqrt((double)m);
+    const ThrStep t0{s0, 0, 0};
+    HCHK(hipMemcpy(d_ts, &t0, sizeof t0, hipMemcpyHostToDevice));
+    lb.ts_mode = 1; lb.ts_adapt = sigma == 0.0; lb.ts_sigma0 = s0;
+    lb.d_ts = std::move(d_ts); lb.d_tg = std::move(d_tg); lb.d_tpart = std::move(d_tpart);
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* mode, the proposal SD in force (0 in mode 0), and the proposals made and taken since ngp_set_y (any pointer may be NULL) */
+int32_t ngp_get_threshold_step(ngp_handle *h, int32_t *mode, double *sigma, int64_t *tries, int64_t *accepted) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.on() && lb.C >= 2, NGP_ERR_STATE, "no liability classes on this handle (ngp_set_liability_classes)");
+    ThrStep t{0.0, 0, 0};
+    if (lb.ts_mode == 1) {
+        HCHK(hipStreamSynchronize(h->stream));
+        HCHK(hipMemcpy(&t, lb.d_ts, sizeof t, hipMemcpyDeviceToHost));
+    }
+    if (mode) *mode = lb.ts_mode;
+    if (sigma) *sigma = t.sigma;
+    if (tries) *tries = (int64_t)t.tries;
+    if (accepted) *accepted = (int64_t)t.accepted;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Resume beside ngp_set_liability_state: what ngp_get_threshold_step gave */
+int32_t ngp_set_threshold_step_state(ngp_handle *h, double sigma, int64_t tries, int64_t accepted) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.on() && lb.ts_mode == 1, NGP_ERR_STATE, "this handle does not run Cowles' threshold step (ngp_set_threshold_step)");
+    REQUIRE(h->have_y, NGP_ERR_STATE, "y not set (ngp_set_y starts the step, this call replaces its state)");
+    REQUIRE(sigma > 0.0 && std::isfinite(sigma) && tries >= 0 && accepted >= 0 && accepted <= tries, NGP_ERR_ARG,
+            "ngp_set_threshold_step_state: sigma > 0 and 0 <= accepted <= tries");
+    const ThrStep t{sigma, (long long)tries, (long long)accepted};
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(lb.d_ts, &t, sizeof t, hipMemcpyHostToDevice));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Class probabilities of the held-out records per kept draw ("Class probabilities"; k_holdout_prob).  Needs
+ * liability classes and a hold-out mask; before ngp_set_y.  ngp_set_liability_classes switches them off again. */
+int32_t ngp_enable_class_probabilities(ngp_handle *h, int32_t on) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.on() && lb.C >= 2 && !h->cm.ho_rows.empty(), NGP_ERR_STATE,
+            "ngp_enable_class_probabilities: needs liability classes and held-out records (ngp_set_holdout, then ngp_set_liability_classes)");
+    REQUIRE(!h->have_y, NGP_ERR_STATE, "ngp_enable_class_probabilities: the phenotypes are set already; the option comes before ngp_set_y");
+    if (!on) { lb.d_sum_prob.reset(); return NGP_OK; }
+    if (lb.d_sum_prob) return NGP_OK;
+    DevArray<double> d;
+    const size_t n = (size_t)lb.C * h->cm.ho_rows.size();
+    if ((rc = d.alloc(h, n))) return rc;
+    HCHK(hipMemset(d, 0, n * 8));
+    lb.d_sum_prob = std::move(d);
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* sum_prob[C][m]: the sums of the class probabilities over kept draws, class-major, in the row order of the hold-out set; the number
+ * of draws is n_fit of ngp_get_holdout */
+int32_t ngp_get_class_probabilities(ngp_handle *h, double *sum_prob, int64_t m, int32_t C) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.d_sum_prob, NGP_ERR_STATE, "class probabilities are not enabled on this handle (ngp_enable_class_probabilities)");
+    REQUIRE(sum_prob && m == (int64_t)h->cm.ho_rows.size() && C == lb.C, NGP_ERR_ARG, "sum_prob must hold C x m entries (ngp_get_holdout_layout, ngp_get_liability_layout)");
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(sum_prob, lb.d_sum_prob, (size_t)C * (size_t)m * 8, hipMemcpyDeviceToHost));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Resume: what ngp_get_class_probabilities gave */
+int32_t ngp_set_class_probabilities(ngp_handle *h, const double *sum_prob, int64_t m, int32_t C) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Liab &lb = h->cm.lb;
+    REQUIRE(h->pm && lb.d_sum_prob, NGP_ERR_STATE, "class probabilities are not enabled on this handle (ngp_enable_class_probabilities)");
+    REQUIRE(h->have_y, NGP_ERR_STATE, "y not set (ngp_set_y clears the sums, this call replaces them)");
+    REQUIRE(sum_prob && m == (int64_t)h->cm.ho_rows.size() && C == lb.C, NGP_ERR_ARG, "sum_prob must hold C x m entries (ngp_get_holdout_layout, ngp_get_liability_layout)");
+    for (int64_t k = 0; k < (int64_t)C * m; k++) REQUIRE(std::isfinite(sum_prob[k]) && sum_prob[k] >= 0.0, NGP_ERR_ARG, "a sum of probabilities is finite and not negative");
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(lb.d_sum_prob, sum_prob, (size_t)C * (size_t)m * 8, hipMemcpyHostToDevice));
     return NGP_OK;
     NGP_CATCH(h)
 }

@@ -26,6 +26,8 @@
 //    A chain with held-out records (ngp_set_holdout, m > 0) appends sum_fit[N] | sum_fit2[N] | n_fit[N] (doubles, zero off the held-out
 //    rows); a chain without a mask appends nothing.  A chain with C liability classes (ngp_set_liability_classes) then appends
 //    sum_thr[C-1] | sum_thr2[C-1], the sums of the thresholds t_1 .. t_{C-1} (t_1 = 0) and of their squares; any other chain nothing.
+//    A chain with class probabilities (ngp_enable_class_probabilities) then appends sum_prob[C][m], class-major over the m held-out
+//    records in the order of the hold-out set; any other chain nothing.
 //
 //  Sample file (ngp_set_sample_file) -- record: sample_layout, padded to a multiple of 8 bytes:
 //    header  char[8] magic | int64 P, nvb, nsets, nfix, nclass, record bytes | per marker set int64 {method, K, col0, ncol, variance
@@ -56,7 +58,10 @@
 //      per BayesRCpi set annotProb[A][ncol], sum_annot[A][ncol], annotCat[ncol] (uint8); its signature words are method 6,
 //      K = A K slots + a 47-bit digest of the annotation masks from bit 8 up, and nreg = A |
 //      with held-out records: yaug[m], sum_fit[N], sum_fit2[N], n_fit[N] (doubles) |
-//      with liabilities: liab[m] | with classes also thr[C-1] (t_1 .. t_{C-1}), sum_thr[C-1], sum_thr2[C-1]
+//      with liabilities: liab[m] | with classes also thr[C-1] (t_1 .. t_{C-1}), sum_thr[C-1], sum_thr2[C-1] |
+//      with Cowles' threshold step (ngp_set_threshold_step, mode 1): sigma (double), tries, accepted (int64); the mode is folded into
+//      the liability digest of the signature, whose bytes in mode 0 are those of a chain that never heard of the step |
+//      with class probabilities: sum_prob[C][m]
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -136,6 +141,18 @@ inline const Layout *tail_of(const Layout &L) {
          : &L == &sample_layout ? &liability_sample_tail : nullptr;
 }
 
+// Ordered traits on the scale of the trait (ngp_threshold.h), a second tail behind the liabilities', built the same way.  Cowles'
+// threshold step (ngp_set_threshold_step, mode 1; described for such a chain only): SEG_THR_STEP = sigma (double) | tries | accepted
+// (int64), in the snapshot.  Class probabilities of the held-out records (ngp_enable_class_probabilities; described only where they
+// are on): SEG_SUM_PROB = sum_prob[C][m], class-major, m the held-out records in the order of the hold-out set -- the end of the
+// packed posterior and of the snapshot body.  The sample record has no such tail.
+constexpr SegId SEG_THR_STEP = (SegId)(SEG_N_FIT + 6), SEG_SUM_PROB = (SegId)(SEG_N_FIT + 7);
+inline const Layout ordered_posterior_tail = {{SEG_SUM_PROB}};
+inline const Layout ordered_snapshot_tail = {{SEG_THR_STEP}, {SEG_SUM_PROB}};
+inline const Layout *ordered_tail_of(const Layout &L) {
+    return &L == &posterior_layout ? &ordered_posterior_tail : &L == &snapshot_body_layout ? &ordered_snapshot_tail : nullptr;
+}
+
 // a layout applied to a chain: every segment with its byte offset, and the size of the whole
 struct Plan {
     struct At { const Seg *s; size_t off; };
@@ -160,7 +177,7 @@ struct Plan {
 inline Plan place(const ChainState &st, const Layout &L, size_t pad = 1) {
     Plan pl;
     const Layout *tail = tail_of(L);
-    for (const Layout *part : {&L, tail}) {
+    for (const Layout *part : {&L, tail, ordered_tail_of(L)}) {
         if (!part) continue;
         for (auto &group : *part)
             for (auto &first : st.segs) {  // the instances of a group: those of its first id, in the order describe() lists them

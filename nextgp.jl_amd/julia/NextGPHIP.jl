@@ -176,6 +176,44 @@ function getThresholds(h::Handle, nKept::Integer)
     return (mean = mean, sd = sd)
 end
 
+# ---- ordered traits: Cowles' threshold step, class probabilities of held-out records (include/nextgp_hip.h, "ordered traits") ----
+# mode 0: Albert-Chib (the default), 1: Cowles' joint Metropolis-Hastings move (C >= 3); sigma > 0 a fixed proposal SD, 0 adapted
+# during burn-in.  After set_classes!, before set_y!.
+set_threshold_step!(h::Handle, mode::Integer=1, sigma::Real=0.0) =
+    check(h, ccall((:ngp_set_threshold_step, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), h.ptr, mode, sigma))
+function threshold_step(h::Handle)       # mode, the proposal SD in force, the proposals made and taken
+    mode = Ref{Int32}(0); sigma = Ref{Float64}(0.0); tries = Ref{Int64}(0); acc = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_threshold_step, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}, Ref{Int64}, Ref{Int64}), h.ptr, mode, sigma, tries, acc))
+    return (mode = Int(mode[]), sigma = sigma[], tries = tries[], accepted = acc[])
+end
+set_threshold_step_state!(h::Handle, sigma::Real, tries::Integer, accepted::Integer) =
+    check(h, ccall((:ngp_set_threshold_step_state, LIB), Int32, (Ptr{Cvoid}, Float64, Int64, Int64), h.ptr, sigma, tries, accepted))
+# needs classes and a hold-out mask; before set_y!
+enable_class_probabilities!(h::Handle, on::Bool=true) =
+    check(h, ccall((:ngp_enable_class_probabilities, LIB), Int32, (Ptr{Cvoid}, Int32), h.ptr, on))
+function class_probability_sums(h::Handle)   # m x C: column c the sums of P(class c) over the kept draws, rows in the order of the hold-out set
+    m = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_holdout_layout, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), h.ptr, m))
+    _, C = liability_layout(h)
+    sp = Matrix{Float64}(undef, Int(m[]), C)
+    check(h, ccall((:ngp_get_class_probabilities, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32), h.ptr, sp, m[], C))
+    return sp
+end
+set_class_probability_sums!(h::Handle, sp::Matrix{Float64}) =
+    check(h, ccall((:ngp_set_class_probabilities, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32), h.ptr, sp, size(sp, 1), size(sp, 2)))
+"""
+    getClassProbabilities(h, N)
+
+Posterior mean of P(class) of every held-out record over the kept draws: `rows` (1-based), `n`, `prob` (records x classes).
+"""
+function getClassProbabilities(h::Handle, N::Integer)
+    st = holdout_state(h, N)
+    n = st.n_fit[st.rows .+ 1]
+    keep = findall(>(0), n)
+    sp = class_probability_sums(h)
+    return (rows = st.rows[keep] .+ 1, n = Int.(n[keep]), prob = sp[keep, :] ./ n[keep])
+end
+
 # ---- prediction of new individuals (include/nextgp_hip.h, "prediction") ----
 # A second panel beside the training panel: Np individuals x the same columns in the same order, centred with the TRAINING means.
 # Every kept iteration then accumulates g = X_new beta per marker set on the device.  Column ranges as for the training panel.
