@@ -243,6 +243,14 @@ int32_t ngp_sample_random_set_tuple(ngp_handle *h, int32_t set_id, double varE, 
  * than it is NGP_ERR_ARG with k_ptr and f_out filled and k_col / k_val untouched: call with cap = 0 to count, then again to fill. */
 int32_t ngp_pedigree_ainv(int64_t n, const int32_t *sire, const int32_t *dam, double *f_out, int64_t *k_ptr, int32_t *k_col, double *k_val,
                           int64_t cap, int64_t *nnz_out);
+/* A22 = A[idx, idx] of the same pedigree WITHOUT the dense A (host only): Colleau's indirect method, one column per listed animal in O(n)
+ * over A = T diag(d) T'.  f: the n inbreeding coefficients ngp_pedigree_ainv returns; idx: m 0-based positions (any order; outside 0..n-1:
+ * NGP_ERR_ARG); A22: m x m out with leading dimension ld >= m, exactly symmetric (the triangle k >= j of column j is mirrored).  Per
+ * column, x = e_idx[j]: backward from the animal to the oldest x[sire] += x[i]/2, x[dam] += x[i]/2; x[i] *= d_i (1, 0.75 - F_p/4,
+ * 0.5 - (F_s + F_d)/4 with no, one, two known parents); forward w[i] = x[i] + (w[sire] + w[dam])/2; A22[j][k] = w[idx[k]].  The columns
+ * are spread over min(16, m) host threads -- a fixed count, never the machine's -- and no bit depends on it. */
+int32_t ngp_pedigree_a22(int64_t n, const int32_t *sire, const int32_t *dam, const double *f, const int64_t *idx, int64_t m, double *A22,
+                         int64_t ld);
 
 /* Phenotypes; resets the chain: ycorr = y (src/mme.jl:57), b = 0, beta = 0, delta = 1, u = 0, varU = varU0, iter = 0, every variance and pi back to
  * the values given to ngp_add_marker_set (src/mme.jl:351-360, 516), all posterior sums and nKept zero. */
@@ -531,6 +539,38 @@ int32_t ngp_grm_invert(ngp_handle *h);
  * share the word. */
 int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q, const double *K, ngp_handle *k_src, int32_t k_src_set,
                                  double df, double scale, double varU0, int32_t *set_id);
+
+/* ---- single-step GBLUP (Aguilar et al. 2010; Christensen & Lund 2010): one breeding value per animal of the pedigree, precision
+ *        H^-1 = A^-1 + [ 0 0 ; 0  G_w^-1 - A22^-1 ],   G_w = (1 - w) G + w A22,   A22 = A over the genotyped animals ----
+ * H^-1 is sparse except for one n_g x n_g corner, so neither engine above fits: ngp_add_random_set_hybrid walks ONE Gauss-Seidel sweep
+ * over a CSR S plus a dense block D on the LAST nd levels, K = S + embed(D) (the caller numbers the genotyped animals last).
+ *
+ * ngp_grm_single_step: after ngp_grm_end (G with the reference's + 0.001 ridge), in place of ngp_grm_invert; before ngp_grm_end or after
+ * ngp_grm_invert: NGP_ERR_STATE.  A22 is N x N (ld >= N), host memory.  Forms G_w entry by entry in fp64, inverts G_w and A22 by the
+ * rocSOLVER path of ngp_grm_invert (A22 in a second N^2 buffer, released on return) and leaves D = G_w^-1 - A22^-1 as the handle's matrix,
+ * mirrored from the computed triangle: exactly symmetric; ngp_grm_get returns it.  NGP_ERR_ARG, with the matrix dropped and the handle
+ * usable: w outside [0, 1), an A22 that is not finite or not exactly symmetric, G_w or A22 not positive definite.  G is not tuned to the
+ * scale of A22 and there is no tau / omega scaling.
+ *
+ * ngp_add_random_set_hybrid: S is q x q CSR (columns ascending, symmetric, finite; k_col / k_val may be NULL when k_ptr[q] == 0); D is
+ * nd x nd over the levels q - nd .. q - 1, 1 <= nd <= q, from ONE of
+ *   D != NULL                   a host array of nd x nd doubles, exactly symmetric and finite (else NGP_ERR_ARG), copied;
+ *   D == NULL, k_src != NULL    the block of HYBRID set k_src_set of another handle on the same device, by reference (that set's T,
+ *                               below: chains = K hold one matrix; the caller gives the same S);
+ *   D == NULL, k_src == NULL    this handle's own corner block (ngp_grm_single_step), taken over: the builder is empty afterwards.
+ * Set-up: the entries of S with row and column both among the last nd levels are added into the block, T = D + S_tt (one sum per stored
+ * entry), and leave the CSR; K_ll of a trailing level is T_ll; a K_ll that is not > 0 is NGP_ERR_ARG.  The head rows 0 .. q - nd - 1 get
+ * the depths ngp_add_random_set gives them; ngp_set_random_schedule / ngp_get_random_schedule apply to the head (refused when nd == q).
+ * One step: k_rand_levels for all q levels; the head rows through the serial or level-scheduled CSR engine (same bits under both); per
+ * trailing row the seed sum_{c < hd} S_lc u_c with this sweep's head values; the blocked chain of the dense engine over T started from the
+ * seed; u'Ku with the cross block counted exactly twice ("Hybrid random-effect sets": the normative orders).
+ * nd == q with an empty S gives the bits of ngp_add_random_set_dense on D.  Everything ngp_add_random_set says about levels, df, scale,
+ * varU0, draw keys, weighted residuals, ngp_get_random / ngp_set_random / ngp_sample_random_set, posterior sums, sample files and
+ * snapshots holds; the model signature digests S as a CSR set does and T as a dense set does. */
+int32_t ngp_grm_single_step(ngp_handle *h, const double *A22, int64_t ld, double w);
+int32_t ngp_add_random_set_hybrid(ngp_handle *h, const int32_t *level, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
+                                  int64_t nd, const double *D, ngp_handle *k_src, int32_t k_src_set, double df, double scale, double varU0,
+                                  int32_t *set_id);
 /* A handle with N records and NO genotype panel -- the canonical GBLUP model y ~ 1 + SNP(M1) with VCV M1 = Random("G", v) has no
  * marker set.  Takes the place of the panel call in the call sequence (a new model, like every ngp_set_panel_*; residual weights
  * before it).  On such a handle ngp_set_y, the residual prior, fixed-effect sets, random-effect sets of both engines, ngp_run,

@@ -190,6 +190,7 @@ SYMBOLS = [
     "ngp_grm_begin", "ngp_grm_columns_f64", "ngp_grm_columns_f32", "ngp_grm_columns_u8", "ngp_grm_end", "ngp_grm_get", "ngp_grm_invert",
     "ngp_add_random_set_dense", "ngp_set_records",
     "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
+    "ngp_pedigree_a22", "ngp_grm_single_step", "ngp_add_random_set_hybrid",
     "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
     "ngp_get_warmer",
     "ngp_add_marker_set_rc", "ngp_get_rc_state", "ngp_set_rc_state",
@@ -420,6 +421,23 @@ def pedigree_ainv(sire, dam):
     if rc != 0:
         raise NextGPHipError(f"ngp_pedigree_ainv failed ({rc}): " + (L.ngp_last_error(None) or b"").decode())
     return F, (kp, kc, kv)
+
+
+def pedigree_a22(sire, dam, F, idx):
+    """A[idx, idx] of a pedigree without the dense A (ngp_pedigree_a22: Colleau's indirect method, one O(n) column per listed animal,
+    on the host).  sire / dam as pedigree_ainv takes them, F the inbreeding coefficients it returns, idx 0-based positions."""
+    s = np.ascontiguousarray(sire, dtype=np.int32); d = np.ascontiguousarray(dam, dtype=np.int32)
+    f = np.ascontiguousarray(F, dtype=np.float64); ix = np.ascontiguousarray(idx, dtype=np.int64)
+    if s.ndim != 1 or s.shape != d.shape or f.shape != s.shape or ix.ndim != 1 or len(ix) < 1:
+        raise ValueError("pedigree_a22: one sire, dam and F per animal, and at least one listed animal")
+    m = len(ix)
+    out = np.empty((m, m))
+    L = load()
+    rc = L.ngp_pedigree_a22(C.c_int64(len(s)), _p(s, C.c_int32), _p(d, C.c_int32), _p(f, C.c_double), _p(ix, C.c_int64), C.c_int64(m),
+                            _p(out, C.c_double), C.c_int64(m))
+    if rc != 0:
+        raise NextGPHipError(f"ngp_pedigree_a22 failed ({rc}): " + (L.ngp_last_error(None) or b"").decode())
+    return out
 
 
 def read_panel_header(path):
@@ -819,6 +837,31 @@ class Sampler:
         self.rand_q = getattr(self, "rand_q", []) + [int(q)]
         return sid.value
 
+    def add_random_set_hybrid(self, level, q, S, nd, D=None, df=4.0, scale=None, varU0=100.0):
+        """Random-effect set over K = S + embed(D) (single-step GBLUP's H^-1): S the sparse q x q part as add_random_set takes K (a CSR
+        triple or a dense array sent as its nonzeros), D a dense block over the LAST nd levels: a symmetric nd x nd array (copied),
+        (other_sampler, set_id) to share that hybrid set's block by reference, or None to take over this sampler's own corner block
+        (grm_single_step).  Everything else as add_random_set; returns the set id."""
+        lv = np.ascontiguousarray(level, dtype=np.int32)
+        if scale is None:
+            scale = varU0 * (df - 2.0) / df
+        kp, kc, kv = k_csr(S)
+        if len(kp) != int(q) + 1:
+            raise ValueError("S: a q x q matrix or a CSR triple with q + 1 row pointers")
+        Dh, src, src_set = None, None, 0
+        if isinstance(D, tuple):
+            src, src_set = D[0].h, int(D[1])
+        elif D is not None:
+            Dh = np.ascontiguousarray(D, dtype=np.float64)
+            if Dh.shape != (int(nd), int(nd)):
+                raise ValueError("D: an nd x nd matrix, (other_sampler, set_id) or None")
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_random_set_hybrid(self.h, _p(lv, C.c_int32), C.c_int64(int(q)), _p(kp, C.c_int64), _p(kc, C.c_int32),
+                                                   _p(kv, C.c_double), C.c_int64(int(nd)), _p(Dh, C.c_double), src, C.c_int32(src_set),
+                                                   C.c_double(df), C.c_double(scale), C.c_double(varU0), C.byref(sid)))
+        self.rand_q = getattr(self, "rand_q", []) + [int(q)]
+        return sid.value
+
     # ---- GBLUP: relationship matrix on the device ------------------------------------------
     def set_records(self, N):
         """N records and no genotype panel (a model without marker sets); in place of set_panel."""
@@ -853,6 +896,15 @@ class Sampler:
 
     def grm_invert(self):
         self._chk(self.L.ngp_grm_invert(self.h))
+
+    def grm_single_step(self, A22, w=0.05):
+        """After grm_end, in place of grm_invert: the matrix becomes D = inv((1 - w) G + w A22) - inv(A22), the dense corner of single-step
+        GBLUP's H^-1 (grm_get returns it; add_random_set_hybrid(..., D=None) takes it over).  A22: the pedigree relationships of the
+        genotyped animals in the row order of the genotypes (pedigree_a22)."""
+        A = np.ascontiguousarray(A22, dtype=np.float64)
+        if A.shape != (self.grm_N, self.grm_N):
+            raise ValueError("grm_single_step: A22 is N x N over the genotyped animals")
+        self._chk(self.L.ngp_grm_single_step(self.h, _p(A, C.c_double), C.c_int64(self.grm_N), C.c_double(float(w))))
 
     def get_random(self, set_id):
         q = self.rand_q[set_id]

@@ -26,7 +26,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
+from ._lib import pedigree_a22, pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
 __all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file", "write_variance_out_files", "write_gwas_files"]
 
@@ -400,6 +400,93 @@ def makePed(path_or_rows, userIDs=None):
     return dict(origID=orig, ID=np.arange(1, len(orig) + 1), Sire=sire, Dam=dam, F=F, pos=pos), Ainv
 
 
+def single_step_order(n, geno_pos):
+    """perm[new] = old position: the levels of a single-step set -- the animals without a genotype first, in pedigree order, then the
+    genotyped ones in the order given (the row order of the genotypes), so that the dense block sits on the LAST levels."""
+    g = np.asarray(geno_pos, dtype=np.int64)
+    is_g = np.zeros(int(n), dtype=bool)
+    is_g[g] = True
+    return np.concatenate([np.flatnonzero(~is_g), g]).astype(np.int64)
+
+
+def permute_csr(K, perm):
+    """P K P' of a CSR triple (k_ptr, k_col, k_val) for perm[new] = old: new row r is old row perm[r] with its columns renumbered and
+    sorted ascending again.  The values move, none is recomputed: a symmetric K stays exactly symmetric."""
+    kp, kc, kv = (np.asarray(a) for a in K)
+    perm = np.asarray(perm, dtype=np.int64)
+    inv = np.empty(len(perm), dtype=np.int64)
+    inv[perm] = np.arange(len(perm))
+    cnt = (kp[1:] - kp[:-1])[perm]
+    np_ = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    nc = np.empty(len(kc), dtype=np.int32); nv = np.empty(len(kv), dtype=np.float64)
+    for r, o in enumerate(perm):
+        c = inv[kc[kp[o]:kp[o + 1]]]
+        srt = np.argsort(c, kind="stable")
+        nc[np_[r]:np_[r + 1]] = c[srt]
+        nv[np_[r]:np_[r + 1]] = kv[kp[o]:kp[o + 1]][srt]
+    return np_, nc, nv
+
+
+def single_step_terms(singleStep, VCV, parsed, summaryStat=None):
+    """{col: {"geno", "ids", "w"}} of the PED(col) terms whose prior is Random("H", v, type=1|2): single-step GBLUP, one breeding value
+    per animal of the pedigree over H^-1 = A^-1 + [0 0; 0 inv((1 - w) G + w A22) - inv(A22)].  Host checks only, before any device work."""
+    singleStep = dict(singleStep or {})
+    summaryStat = summaryStat or {}
+    is_h = lambda p: isinstance(p, RandomEffectType) and isinstance(p.str, str) and p.str == "H"
+    for key, prior in VCV.items():
+        if isinstance(key, tuple) and is_h(prior):
+            raise NotImplementedError(f"VCV key {key}: \"H\" inside a correlated (Tuple) random effect; a single-step set has one component")
+        if not isinstance(key, tuple) and is_h(prior) and key not in parsed.ped:
+            raise ValueError(f"Random(\"H\", v) under {key!r}: single-step GBLUP is the prior of a PED(col) term")
+    out = {}
+    for col in parsed.ped:
+        prior = VCV.get(col)
+        if not is_h(prior):
+            if col in singleStep:
+                raise ValueError(f"singleStep[{col!r}] is given, but the prior of PED({col}) is not Random(\"H\", v)")
+            continue
+        if col not in singleStep:
+            raise ValueError(f"PED({col}) with Random(\"H\", v) needs singleStep={{{col!r}: {{\"geno\": ..., \"ids\": [...], \"w\": 0.05}}}}")
+        if prior.type not in (1, 2):
+            raise ValueError("enter a valid method")                  # src/misc.jl:156
+        if col in summaryStat:
+            raise NotImplementedError(f"summaryStat for the single-step term PED({col}): summary statistics enter marker sets and fixed effects only")
+        spec = singleStep[col]
+        if not isinstance(spec, dict) or "geno" not in spec or "ids" not in spec or set(spec) - {"geno", "ids", "w"}:
+            raise ValueError(f"singleStep[{col!r}]: {{\"geno\": path | array, \"ids\": [...], \"w\": 0.05}}")
+        w = float(spec.get("w", 0.05))
+        if not (0.0 <= w < 1.0):
+            raise ValueError(f"singleStep[{col!r}]: the blending weight w must be in [0, 1)")
+        out[col] = dict(geno=spec["geno"], ids=[str(a) for a in spec["ids"]], w=w)
+    for col in singleStep:
+        if col not in parsed.ped:
+            raise ValueError(f"singleStep[{col!r}]: the model has no PED({col}) term")
+    return out
+
+
+def _single_step_prepare(spec, table, Ainv):
+    """The host side of one single-step term: the genotypes, the pedigree positions of the genotyped animals, the renumbering, A^-1
+    permuted to it, A22 by Colleau's method (ngp_pedigree_a22)."""
+    ids = spec["ids"]
+    if len(set(ids)) != len(ids):
+        dup = sorted({a for a in ids if ids.count(a) > 1})[0]
+        raise ValueError(f"singleStep: genotyped ID {dup} is listed twice")
+    for a in ids:
+        if a not in table["pos"]:
+            raise ValueError(f"singleStep: genotyped ID {a} is not in the pedigree")
+    M = read_genotypes(spec["geno"] if isinstance(spec["geno"], (str, os.PathLike)) else np.asarray(spec["geno"]))
+    if M.ndim != 2 or M.shape[0] != len(ids):
+        raise ValueError(f"singleStep: the genotypes have {M.shape[0] if M.ndim == 2 else '?'} rows for {len(ids)} ids")
+    gpos = np.array([table["pos"][a] for a in ids], dtype=np.int64)
+    n = len(table["origID"])
+    perm = single_step_order(n, gpos)
+    inv = np.empty(n, dtype=np.int64)
+    inv[perm] = np.arange(n)
+    A22 = pedigree_a22(table["Sire"], table["Dam"], table["F"], gpos)
+    return dict(M=M, w=spec["w"], gpos=gpos, perm=perm, inv=inv, S=permute_csr(Ainv, perm), A22=A22, ng=len(ids),
+                levels=[table["origID"][o] for o in perm])
+
+
 def gblup_terms(snps, VCV, summaryStat=None):
     """Names of the SNP terms that are GBLUP: a Random("G", v; type = 1|2) prior under the term's name (src/prepMatVec.jl:122-126).
     What the reference would handle elsewhere and this path does not is refused here, before any device is touched."""
@@ -712,7 +799,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -782,6 +869,14 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     res["cv"]["prob"] (N x C, NaN where not validated), "brier", "logloss", "class_accuracy" (arg-max class) and, for two classes,
     "auc" (class_metrics), each also in every entry of "per_fold", and cvProb.txt: record fold class p1 .. pC (records from 1, fold -1
     and class 0 where there is none).  holdoutPredict.txt and cvPredict.txt keep their columns.
+    (13) single-step GBLUP (ngp_grm_single_step / ngp_add_random_set_hybrid; DESIGN.md section 2, "Hybrid random-effect sets"): a
+    PED(col) term with VCV={col: Random("H", v, type=1|2)} and singleStep={col: {"geno": path | array, "ids": [...], "w": 0.05}} has one
+    breeding value per animal of the pedigree over H^-1 = A^-1 + [0 0; 0 inv((1 - w) G + w A22) - inv(A22)]; ids names the genotyped
+    animals in the row order of geno, all of them in the pedigree (an unknown or repeated ID: ValueError).  The set's levels are
+    renumbered -- the animals without a genotype first, in pedigree order, then the genotyped ones in ids order -- and u<col>Out's header
+    and res["random"][col]["levels"] name them in that order.  G is built on the device (type: VanRaden's method), A22 by Colleau's
+    method on the host; chains=K share the dense block by reference.  "H" without singleStep[col], singleStep for a term whose prior is
+    not "H": ValueError; "H" inside a tuple key and summaryStat on the term: NotImplementedError.  G is not scaled to A22.
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
@@ -792,6 +887,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         raise ValueError(f"PED({parsed.ped[0]}) needs userPedData: the pedigree file (ID Sire Dam), or its rows")
     if not snps and not parsed.ped:
         raise ValueError("the accelerated path needs at least one SNP(...) term")
+    ss_terms = single_step_terms(singleStep, VCV, parsed, summaryStat)   # (checked before any device work)
     y = np.asarray(userData[lhs], dtype=np.float64)
     liab = _liability_spec(trait, censored, y, userData, VCV)   # (checked before any device work)
     if liab is not None and liab["kind"] == "bounds":          # exact records take their value; the censored ones are not read
@@ -816,7 +912,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
                                           "ngp_add_random_set takes a level for every record, so such records are not on the accelerated path")
             ids += c
         table, Ainv = makePed(userPedData, ids)
-        ped = dict(table=table, Ainv=Ainv, tuples=ped_tuples)
+        ped = dict(table=table, Ainv=Ainv, tuples=ped_tuples, single={col: _single_step_prepare(sp, table, Ainv) for col, sp in ss_terms.items()})
     # weighted residuals, E.str == "D" (src/mme.jl:71-75): w = inv.(d), set on the handle before its panel (the rows are scaled at upload)
     w_res = _residual_weights(VCV.get("e", Random("I", 100.0)), len(y))
     if w_res is not None and storage in ("u8", 1):
@@ -1489,6 +1585,21 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
                 prior = Random("I", 100.0)                           # src/mme.jl:40-44: the identity over the pedigree's levels
             if not isinstance(prior, RandomEffectType):
                 raise ValueError(f"prior of PED({g}): Random(\"A\", v)")
+            if g in ped.get("single", {}):   # Random("H", v): single-step GBLUP, the hybrid engine over A^-1 and the genotyped corner
+                ss = ped["single"][g]
+                rdf = 3.0 + 1.0                                      # src/mme.jl:261
+                v = float(prior.v)
+                n = len(table["origID"])
+                if k_owner is None:   # G on the matrix cores, the corner block on the device, handed to the set without a copy
+                    _grm_build(smp, ss["M"], prior.type)
+                    smp.grm_single_step(ss["A22"], ss["w"])
+                    Dsrc = None
+                else:                 # the other chains read the first chain's block
+                    Dsrc = (k_owner, [rd["id"] for rd in k_owner.randoms if rd.get("key") == g][0])
+                rid = smp.add_random_set_hybrid(ss["inv"][level].astype(np.int32), n, ss["S"], ss["ng"], D=Dsrc, df=rdf, scale=v * (rdf - 2.0) / rdf,
+                                                varU0=v)
+                smp.randoms.append(dict(id=rid, g=g, key=g, levels=list(ss["levels"]), q=n, files=(f"u{g}", f"varU{g}", g)))
+                continue
             if isinstance(prior.str, str) and prior.str == "A":
                 K = ped["Ainv"]
             elif prior.str is None or (isinstance(prior.str, str) and prior.str in ("I", "")):

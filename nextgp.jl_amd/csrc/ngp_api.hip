@@ -31,6 +31,7 @@
 #include "ngp_random.h"
 #include "ngp_random_tuple.h"
 #include "ngp_dense.h"
+#include "ngp_hybrid.h"
 #include "ngp_logvar.h"
 #include "ngp_predict.h"
 #include "ngp_holdout.h"
@@ -98,7 +99,8 @@ struct DenseK {
 };
 
 // The genomic relationship matrix under construction (ngp_grm_begin .. ngp_grm_invert): column-major with leading dimension ld = N
-// rounded up to 64, rows and columns beyond N zero.  state: 1 columns may arrive, 2 G complete (ngp_grm_end), 3 inverted.
+// rounded up to 64, rows and columns beyond N zero.  state: 1 columns may arrive, 2 G complete (ngp_grm_end), 3 inverted, 4 the corner
+// block D = G_w^-1 - A22^-1 of single-step GBLUP (ngp_grm_single_step).
 struct Grm {
     std::shared_ptr<DenseK> m;
     int state = 0, method = 1;
@@ -126,6 +128,10 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     DevArray<double> d_wd, d_wval, d_scaleM;
     uint64_t sig = 0;          // digest of the level coding and K (snapshots refuse another random-effect model)
     std::shared_ptr<DenseK> dk;  // a dense K (ngp_add_random_set_dense): the blocked engine of ngp_dense.h instead of k_rand_gs / k_rand_var
+    // a hybrid set (ngp_add_random_set_hybrid, ngp_hybrid.h): the CSR holds S without its trailing x trailing entries, dk the nd x nd block
+    // T = D + S_tt over the levels hd .. q - 1; the level schedule covers the head rows 0 .. hd - 1
+    bool hyb = false;
+    int64_t hd = 0;
     // the level schedule of a CSR K with off-diagonal entries (ngp_random.h, k_rand_sched_*): rows sorted by (depth, row), and the launches
     struct Launch { int wide; int d0, d1; long long r0, r1; };  // wide: the rows order[r0 .. r1) of depth d0; else the depths d0 .. d1 - 1 in one workgroup
     DevArray<int> d_order;
@@ -133,7 +139,7 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     std::vector<Launch> plan;
     int64_t ndepth = 0;
     int sched_mode = 0;        // ngp_set_random_schedule: 0 automatic, 1 serial (k_rand_gs), 2 scheduled
-    bool scheduled() const { return sched_mode == 2 || (sched_mode == 0 && q > NGP_RS_AUTO_LEVELS_PER_DEPTH * ndepth); }
+    bool scheduled() const { return sched_mode == 2 || (sched_mode == 0 && (hyb ? hd : q) > NGP_RS_AUTO_LEVELS_PER_DEPTH * ndepth); }
 };
 // q of a set as the sample file's header and the snapshot signature carry it: q, and k - 1 of a tuple set in the bits from 32 up
 // (q < 2^31; a set of one component writes the word it always wrote)
@@ -1333,6 +1339,41 @@ void launch_random(ngp_handle *h, int r, uint64_t it) {
                            (const int *)R.d_level, (const double *)T.du, ab);
         hipLaunchKernelGGL(k_tup_var, dim3(1), dim3(1024), 0, h->stream, q, k, kp, kc, kv, (const double *)R.d_u, R.d_vu.get(), R.df, (const double *)R.d_scaleM, r,
                            h->seed, (uint64_t)h->chain, it, ab);
+        return;
+    }
+    if (R.hyb) {  // sparse S plus a dense trailing block (ngp_hybrid.h): the CSR engine over the head rows, the seed, the blocked engine over T
+        const long long hd = (long long)R.hd, nd = q - hd, ld = (long long)R.dk->ld;
+        const double *T = R.dk->K;
+        const unsigned *ab = (const unsigned *)h->cm.d_abort;
+        const long long *kp = R.d_kptr;
+        const int *kc = R.d_kcol;
+        const double *kv = R.d_kval;
+        hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, (const double *)h->cm.d_rs, q,
+                           (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag, kp, kc, kv, R.d_u,
+                           (const double *)R.d_vu, R.d_scr, 1, (const DScal *)h->cm.d_scal, r, h->seed, (uint64_t)h->chain, it, ab);
+        hipLaunchKernelGGL(k_hyb_dhi, dim3((unsigned)((nd + 3) / 4)), dim3(256), 0, h->stream, T, ld, nd, (const double *)(R.d_u + hd), R.d_scr + hd, q, ab);
+        if (hd > 0 && R.scheduled()) {  // the level schedule of the head rows, as a CSR set runs it (q: the stride of the scratch rows)
+            for (const HRand::Launch &pl : R.plan) {
+                if (pl.wide)
+                    hipLaunchKernelGGL(k_rand_sched_wide, dim3((unsigned)((pl.r1 - pl.r0 + 255) / 256)), dim3(256), 0, h->stream, q, kp, kc, kv, R.d_u.get(),
+                                       (const double *)R.d_vu, R.d_scr.get(), (const int *)R.d_order, pl.r0, pl.r1, ab);
+                else
+                    hipLaunchKernelGGL(k_rand_sched_fused, dim3(1), dim3(1024), 0, h->stream, q, kp, kc, kv, R.d_u.get(), (const double *)R.d_vu,
+                                       R.d_scr.get(), (const int *)R.d_order, (const long long *)R.d_dptr, pl.d0, pl.d1, ab);
+            }
+        } else if (hd > 0) {
+            hipLaunchKernelGGL(k_hyb_gs, dim3(1), dim3(64), 0, h->stream, hd, q, kp, kc, kv, R.d_u.get(), (const double *)R.d_vu, R.d_scr.get(), ab);
+        }
+        hipLaunchKernelGGL(k_hyb_seed, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->stream, hd, q, kp, kc, kv, (const double *)R.d_u, R.d_scr, ab);
+        for (long long t = 0; t * 64 < nd; t++) {
+            const long long below = nd - 64 * t - 64;
+            const unsigned nwg = below > 0 ? (unsigned)((below + NGP_DENSE_WG_ROWS - 1) / NGP_DENSE_WG_ROWS) : 1u;
+            hipLaunchKernelGGL(k_hyb_block, dim3(nwg), dim3(256), 0, h->stream, T, ld, nd, (int)t, R.d_u + hd, (const double *)R.d_vu, R.d_scr + hd, q, ab);
+        }
+        hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr, (const double *)h->cm.d_rs, (long long)h->N,
+                           (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), ab);
+        hipLaunchKernelGGL(k_hyb_var, dim3(1), dim3(1024), 0, h->stream, q, hd, kp, kc, kv, (const double *)R.d_kdiag, (const double *)R.d_u,
+                           (const double *)R.d_scr, R.d_vu, R.df, R.sdf, r, h->seed, (uint64_t)h->chain, it, ab);
         return;
     }
     if (R.dk) {  // dense K: the blocked engine (ngp_dense.h), one launch per block of 64 levels between the level terms and the ycorr update
@@ -4366,7 +4407,7 @@ void group_levels(const ngp_handle *h, const int32_t *level, int64_t q, std::vec
 // K of a random-effect set from the caller's CSR (all three NULL: the identity), checked: rows with their columns ascending (the
 // summation order of DESIGN.md), symmetric, finite, with a positive diagonal
 int parse_k(ngp_handle *h, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val, std::vector<long long> &kp,
-            std::vector<int> &kc, std::vector<double> &kv, std::vector<double> &kd, bool &offdiag) {
+            std::vector<int> &kc, std::vector<double> &kv, std::vector<double> &kd, bool &offdiag, bool need_diag = true) {
     kp.assign((size_t)q + 1, 0); kc.clear(); kv.clear(); kd.assign((size_t)q, 0.0);
     offdiag = false;
     const bool ident = !k_ptr && !k_col && !k_val;
@@ -4396,7 +4437,8 @@ int parse_k(ngp_handle *h, int64_t q, const int64_t *k_ptr, const int32_t *k_col
                 if (row[k].first == l) { diag = true; kd[(size_t)l] = row[k].second; }
                 else offdiag = true;
             }
-            REQUIRE(diag && kd[(size_t)l] > 0.0, NGP_ERR_ARG, "random-effect set: every diagonal entry of K must be present and > 0");
+            // (need_diag false: S of a hybrid set, whose trailing diagonal may live in the dense block alone; its caller checks K_ll > 0)
+            REQUIRE(!need_diag || (diag && kd[(size_t)l] > 0.0), NGP_ERR_ARG, "random-effect set: every diagonal entry of K must be present and > 0");
             kp[(size_t)l] = k_ptr[l];
         }
         kp[(size_t)q] = nnz;
@@ -4414,7 +4456,7 @@ int parse_k(ngp_handle *h, int64_t q, const int64_t *k_ptr, const int32_t *k_col
 // the launches of one step of the level schedule (ngp_random.h) from the depth of every row: the rows by (depth, row), a depth of more
 // than NGP_RS_FUSE_ROWS rows a launch of its own, a run of narrower depths one launch
 int plan_schedule(ngp_handle *h, HRand &R, const std::vector<int> &dep) {
-    const int64_t q = R.q;
+    const int64_t q = (int64_t)dep.size();  // (the set's q; the head rows of a hybrid set)
     int rc, maxd = 0;
     for (int64_t l = 0; l < q; l++) maxd = std::max(maxd, dep[(size_t)l]);
     std::vector<int> ord((size_t)q);
@@ -4773,8 +4815,9 @@ int32_t ngp_set_random_schedule(ngp_handle *h, int32_t set_id, int32_t mode) {
     REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     REQUIRE(mode >= 0 && mode <= 2, NGP_ERR_ARG, "random-effect schedule: 0 automatic, 1 serial, 2 level-scheduled");
     HRand &R = h->mm.rnd[(size_t)set_id];
-    REQUIRE(!R.dk && R.offdiag, NGP_ERR_ARG, "random-effect schedule: only a CSR set whose K has off-diagonal entries runs a Gauss-Seidel engine "
-                                             "(a diagonal K draws every level on its own, a dense K runs the blocked engine)");
+    REQUIRE(R.hyb ? R.hd > 0 : (!R.dk && R.offdiag), NGP_ERR_ARG,
+            "random-effect schedule: only a CSR set whose K has off-diagonal entries, or a hybrid set with head rows, runs a Gauss-Seidel engine "
+            "(a diagonal K draws every level on its own, a dense K runs the blocked engine)");
     R.sched_mode = mode;
     return NGP_OK;
     NGP_CATCH(h)
@@ -4788,9 +4831,9 @@ int32_t ngp_get_random_schedule(ngp_handle *h, int32_t set_id, int32_t *engine, 
     if ((rc = enter(h))) return rc;
     REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     const HRand &R = h->mm.rnd[(size_t)set_id];
-    const bool gs = !R.dk && R.offdiag;
+    const bool gs = R.hyb ? R.hd > 0 : (!R.dk && R.offdiag);  // (a hybrid set: the engine, depths and launches of its head rows)
     if (engine) *engine = !gs ? 0 : R.scheduled() ? 2 : 1;
-    if (depths) *depths = R.dk ? 0 : gs ? R.ndepth : 1;
+    if (depths) *depths = gs ? R.ndepth : R.dk ? 0 : 1;
     if (launches) *launches = !gs ? 0 : R.scheduled() ? (int64_t)R.plan.size() : 1;
     return NGP_OK;
     NGP_CATCH(h)
@@ -4876,6 +4919,67 @@ int32_t ngp_pedigree_ainv(int64_t n, const int32_t *sire, const int32_t *dam, do
         const double a = 1.0 / D[(size_t)i];
         k_val[std::lower_bound(b, e, (int32_t)c) - k_col] += a * w;
     });
+    return NGP_OK;
+    NGP_CATCH(nullptr)
+}
+
+/* A22 = A[idx, idx] of a pedigree without the dense A (host only): Colleau's indirect method, A = T diag(d) T' with T the gene flow
+ * (T = I + T P, P the parent matrix with 1/2 entries).  Per listed animal g = idx[j], with x = e_g:
+ *   backward, i = g .. 0:  x[sire_i] = x[sire_i] + x[i] / 2;  x[dam_i] = x[dam_i] + x[i] / 2          (x = T' e_g)
+ *   x[i] = x[i] * d_i,  d_i = 1, 0.75 - F_p / 4, 0.5 - (F_s + F_d) / 4 with no, one, two known parents
+ *   forward, i = 0 .. n - 1:  w[i] = x[i] + (w[sire_i] + w[dam_i]) / 2  (an unknown parent adds 0.0)   (w = T x = A e_g)
+ * and A22[j][k] = w[idx[k]] for k >= j, mirrored into A22[k][j]: exactly symmetric.  The columns are spread over min(16, m) threads,
+ * column j to thread j mod that count; no column depends on another, so the count changes no bit.  f: the inbreeding coefficients
+ * ngp_pedigree_ainv returns.  idx: 0-based positions, any order, repeats allowed. */
+int32_t ngp_pedigree_a22(int64_t n, const int32_t *sire, const int32_t *dam, const double *f, const int64_t *idx, int64_t m, double *A22, int64_t ld) {
+    NGP_TRY
+    ngp_handle *h = nullptr;
+    REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && sire && dam && f, NGP_ERR_ARG, "pedigree: 1 <= n < 2^31 animals with their sires, dams and inbreeding coefficients");
+    REQUIRE(m >= 1 && idx && A22 && ld >= m, NGP_ERR_ARG, "pedigree A22: m >= 1 listed animals, an m x m output with ld >= m");
+    for (int64_t i = 0; i < n; i++) {
+        REQUIRE(sire[i] >= 0 && (int64_t)sire[i] <= i && dam[i] >= 0 && (int64_t)dam[i] <= i, NGP_ERR_ARG, "pedigree: parents must come in front of their offspring (0 = unknown)");
+        REQUIRE(std::isfinite(f[i]), NGP_ERR_ARG, "pedigree: non-finite inbreeding coefficient");
+    }
+    for (int64_t j = 0; j < m; j++) REQUIRE(idx[j] >= 0 && idx[j] < n, NGP_ERR_ARG, "pedigree A22: a listed animal is outside 0..n-1");
+    std::vector<double> d((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int s = sire[i], dm = dam[i];
+        if (s && dm) d[(size_t)i] = 0.5 - (f[(size_t)s - 1] + f[(size_t)dm - 1]) / 4.0;
+        else if (s || dm) d[(size_t)i] = 0.75 - f[(size_t)(s ? s : dm) - 1] / 4.0;
+        else d[(size_t)i] = 1.0;
+    }
+    const int nt = (int)std::min<int64_t>(16, m);
+    std::vector<std::vector<double>> xs((size_t)nt, std::vector<double>((size_t)n)), ws(xs);  // (allocated here: a thread must not throw)
+    auto work = [&](int t) {
+        std::vector<double> &x = xs[(size_t)t], &w = ws[(size_t)t];
+        for (int64_t j = t; j < m; j += nt) {
+            const int64_t g = idx[j];
+            std::fill(x.begin(), x.end(), 0.0);
+            x[(size_t)g] = 1.0;
+            for (int64_t i = g; i >= 0; i--) {
+                const double hx = x[(size_t)i] / 2.0;
+                if (hx == 0.0) continue;
+                if (sire[i]) x[(size_t)sire[i] - 1] = x[(size_t)sire[i] - 1] + hx;
+                if (dam[i]) x[(size_t)dam[i] - 1] = x[(size_t)dam[i] - 1] + hx;
+            }
+            for (int64_t i = 0; i <= g; i++) x[(size_t)i] = x[(size_t)i] * d[(size_t)i];
+            for (int64_t i = 0; i < n; i++) {
+                const double ws = sire[i] ? w[(size_t)sire[i] - 1] : 0.0, wd = dam[i] ? w[(size_t)dam[i] - 1] : 0.0;
+                w[(size_t)i] = x[(size_t)i] + (ws + wd) / 2.0;
+            }
+            for (int64_t k = j; k < m; k++) A22[(size_t)j * (size_t)ld + (size_t)k] = w[(size_t)idx[k]];
+        }
+    };
+    {
+        struct Joiner {  // (a std::thread constructor that throws must not unwind past joinable threads)
+            std::vector<std::thread> th;
+            ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
+        } pool;
+        for (int t = 1; t < nt; t++) pool.th.emplace_back(work, t);
+        work(0);
+    }
+    for (int64_t j = 0; j < m; j++)
+        for (int64_t k = j + 1; k < m; k++) A22[(size_t)k * (size_t)ld + (size_t)j] = A22[(size_t)j * (size_t)ld + (size_t)k];
     return NGP_OK;
     NGP_CATCH(nullptr)
 }
@@ -5353,8 +5457,8 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
         REQUIRE(k_src != h, NGP_ERR_ARG, "dense random-effect set: k_src is this handle (a set shares the K of a set on ANOTHER handle)");
         REQUIRE(k_src->stream != nullptr && k_src->pm && !k_src->panel_open, NGP_ERR_ARG, "dense random-effect set: k_src has no panel or records yet (or its panel is still open)");
         REQUIRE(k_src->device == h->device, NGP_ERR_ARG, "dense random-effect set: a shared K must be on this handle's device");
-        REQUIRE(k_src_set >= 0 && k_src_set < (int32_t)k_src->mm.rnd.size() && k_src->mm.rnd[(size_t)k_src_set].dk, NGP_ERR_ARG,
-                "dense random-effect set: k_src_set is not a dense set of k_src");
+        REQUIRE(k_src_set >= 0 && k_src_set < (int32_t)k_src->mm.rnd.size() && k_src->mm.rnd[(size_t)k_src_set].dk && !k_src->mm.rnd[(size_t)k_src_set].hyb,
+                NGP_ERR_ARG, "dense random-effect set: k_src_set is not a dense set of k_src");
         dk = k_src->mm.rnd[(size_t)k_src_set].dk;
         REQUIRE(dk->q == q, NGP_ERR_ARG, "dense random-effect set: the shared K has another q");
         HCHK(hipStreamSynchronize(k_src->stream));
@@ -5391,6 +5495,198 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
     dk->digest = kdig;
     R.dk = std::move(dk);
     if (from_grm) h->grm = Grm();  // consumed: the set owns the matrix now
+    if (set_id) *set_id = (int32_t)h->mm.rnd.size();
+    h->mm.rnd.push_back(std::move(R));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ---- single-step GBLUP: the corner block D = G_w^-1 - A22^-1 on the device, and the hybrid random-effect set (ngp_hybrid.h) ---- */
+
+/* After ngp_grm_end, in place of ngp_grm_invert: G_w = (1 - w) G + w A22 (k_ss_blend), both G_w and A22 inverted by rocSOLVER (A22 in a
+ * second N x N buffer, released on return), D = G_w^-1 - A22^-1 on the computed triangle, mirrored.  A refusal by NGP_ERR_ARG (w outside
+ * [0, 1), A22 not finite or not symmetric, either matrix not positive definite) drops the matrix; the handle stays usable. */
+int32_t ngp_grm_single_step(ngp_handle *h, const double *A22, int64_t ld, double w) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Grm &g = h->grm;
+    REQUIRE(g.state == 2, NGP_ERR_STATE, "ngp_grm_single_step needs a complete relationship matrix that is not inverted yet (ngp_grm_end)");
+    REQUIRE(A22 != nullptr && ld >= g.N, NGP_ERR_ARG, "single-step: A22 is N x N with ld >= N");
+    const int64_t N = g.N, Npad = g.m->ld;
+    bool ok = std::isfinite(w) && w >= 0.0 && w < 1.0;
+    const char *why = "single-step: the blending weight w must be in [0, 1); the matrix is dropped";
+    for (int64_t i = 0; ok && i < N; i++)
+        for (int64_t j = 0; j <= i; j++) {
+            const double a = A22[(size_t)i * (size_t)ld + (size_t)j];
+            if (!std::isfinite(a) || a != A22[(size_t)j * (size_t)ld + (size_t)i]) { ok = false; why = "single-step: A22 must be finite and exactly symmetric; the matrix is dropped"; break; }
+        }
+    if (!ok) { h->grm = Grm(); return fail(h, NGP_ERR_ARG, why); }
+    if (!g_rocsolver.load()) return fail(h, NGP_ERR_HIP, g_rocsolver.err + " (ngp_grm_single_step factorises on the device; there is no host fallback)");
+    struct Blas {  // a rocBLAS handle for this call, destroyed however it ends
+        void *p = nullptr;
+        ~Blas() { if (p) (void)g_rocsolver.DestroyHandle(p); }
+    } blas;
+    if (g_rocsolver.CreateHandle(&blas.p) != 0 || !blas.p || g_rocsolver.SetStream(blas.p, h->stream) != 0)
+        return fail(h, NGP_ERR_HIP, "rocblas_create_handle / rocblas_set_stream failed");
+    DevArray<double> d_a;  // A22, laid out as G is (leading dimension Npad, zero beyond N); released when this call returns
+    DevArray<int> d_info;
+    if ((rc = d_a.alloc(h, (size_t)Npad * (size_t)Npad)) || (rc = d_info.alloc(h, 1))) return rc;
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy2D(d_a, (size_t)Npad * sizeof(double), A22, (size_t)ld * sizeof(double), (size_t)N * sizeof(double), (size_t)N, hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)std::min<int64_t>(N, 65535));
+    hipLaunchKernelGGL(k_ss_blend, grid, dim3(256), 0, h->stream, g.m->K.get(), (const double *)d_a, (long long)N, (long long)Npad, 1.0 - w, w);
+    // the two inverses, lower triangle, column-major (as ngp_grm_invert): G_w first, then A22
+    double *mats[2] = {g.m->K.get(), d_a.get()};
+    const char *names[2] = {"G_w = (1 - w) G + w A22", "A22"};
+    for (int k = 0; k < 2; k++) {
+        int info = 0;
+        int st = g_rocsolver.Dpotrf(blas.p, ROCBLAS_FILL_LOWER, (int)N, mats[k], (int)Npad, d_info.get());
+        HCHK(hipStreamSynchronize(h->stream));
+        HCHK(hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+        if (st == 0 && info == 0) {
+            st = g_rocsolver.Dpotri(blas.p, ROCBLAS_FILL_LOWER, (int)N, mats[k], (int)Npad, d_info.get());
+            HCHK(hipStreamSynchronize(h->stream));
+            HCHK(hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+        }
+        if (st != 0 || info != 0) {  // the factorisation has overwritten part of the matrix: it is gone either way
+            h->grm = Grm();
+            if (st != 0) return fail(h, NGP_ERR_HIP, "rocsolver_dpotrf / dpotri failed (rocblas status " + std::to_string(st) + "); the relationship matrix is dropped");
+            return fail(h, NGP_ERR_ARG, std::string("single-step: ") + names[k] + " is not positive definite (pivot " + std::to_string(info) +
+                                            ", 1-based); the matrix is dropped");
+        }
+    }
+    hipLaunchKernelGGL(k_ss_diff, grid, dim3(256), 0, h->stream, g.m->K.get(), (const double *)d_a, (long long)N, (long long)Npad);
+    hipLaunchKernelGGL(k_grm_mirror, grid, dim3(256), 0, h->stream, g.m->K.get(), (long long)N, (long long)Npad, 0, 1.0);
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    g.state = 4;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* A random-effect set with K = S + embed(D): S a q x q CSR, D a dense nd x nd block over the LAST nd levels (ngp_hybrid.h).  Every argument
+ * is checked before anything changes: a refused call leaves the handle (and its relationship matrix) as it was. */
+int32_t ngp_add_random_set_hybrid(ngp_handle *h, const int32_t *level, int64_t q, const int64_t *k_ptr, const int32_t *k_col, const double *k_val,
+                                  int64_t nd, const double *D, ngp_handle *k_src, int32_t k_src_set, double df, double scale, double varU0,
+                                  int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
+    REQUIRE(level != nullptr && q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: levels of N records and 1 <= q < 2^31");
+    REQUIRE(nd >= 1 && nd <= q, NGP_ERR_ARG, "hybrid random-effect set: the dense block covers the last nd levels, 1 <= nd <= q");
+    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
+    REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
+    REQUIRE(k_ptr != nullptr && (k_ptr[q] == 0 || (k_col && k_val)), NGP_ERR_ARG, "hybrid random-effect set: S as CSR (k_ptr, k_col, k_val); an empty S needs k_ptr alone");
+    REQUIRE(!(D && k_src), NGP_ERR_ARG, "hybrid random-effect set: D from a host pointer OR from a set of another handle, not both");
+    const int64_t N = h->N, hd = q - nd;
+    for (int64_t i = 0; i < N; i++) REQUIRE(level[i] >= 0 && (int64_t)level[i] < q, NGP_ERR_ARG, "random-effect set: a record's level is outside 0..q-1");
+    std::vector<long long> kp;
+    std::vector<int> kc;
+    std::vector<double> kv, kd;
+    bool offdiag = false;
+    if ((rc = parse_k(h, q, k_ptr, k_col, k_val, kp, kc, kv, kd, offdiag, false))) return rc;
+    // S split: the CSR the engine walks (everything but the trailing x trailing entries) and the entries that go into the dense block
+    std::vector<long long> fp((size_t)q + 1, 0);
+    std::vector<int> fcol, tr, tc;
+    std::vector<double> fval, tv;
+    for (int64_t l = 0; l < q; l++) {
+        for (long long k = kp[(size_t)l]; k < kp[(size_t)l + 1]; k++) {
+            if (l >= hd && kc[(size_t)k] >= hd) { tr.push_back((int)(l - hd)); tc.push_back(kc[(size_t)k] - (int)hd); tv.push_back(kv[(size_t)k]); }
+            else { fcol.push_back(kc[(size_t)k]); fval.push_back(kv[(size_t)k]); }
+        }
+        fp[(size_t)l + 1] = (long long)fcol.size();
+    }
+    for (int64_t l = 0; l < hd; l++) REQUIRE(kd[(size_t)l] > 0.0, NGP_ERR_ARG, "hybrid random-effect set: every diagonal entry of K must be > 0 (a head row of S lacks one)");
+    // where D comes from: a host matrix (copied, S_tt added on the host), a hybrid set of another handle (its T, by reference), or this
+    // handle's own corner block (ngp_grm_single_step; S_tt added on the device once nothing can refuse the call any more)
+    std::shared_ptr<DenseK> dk;
+    bool from_grm = false;
+    std::vector<double> td((size_t)nd);  // the diagonal of T
+    if (D) {
+        std::vector<double> T((size_t)nd * (size_t)nd);
+        for (int64_t l = 0; l < nd; l++)
+            for (int64_t c = 0; c <= l; c++) {
+                const double a = D[(size_t)l * (size_t)nd + (size_t)c];
+                REQUIRE(std::isfinite(a), NGP_ERR_ARG, "hybrid random-effect set: non-finite entry in D");
+                REQUIRE(a == D[(size_t)c * (size_t)nd + (size_t)l], NGP_ERR_ARG, "hybrid random-effect set: D is not symmetric");
+                T[(size_t)l * (size_t)nd + (size_t)c] = a; T[(size_t)c * (size_t)nd + (size_t)l] = a;
+            }
+        for (size_t e = 0; e < tv.size(); e++) { double &x = T[(size_t)tr[e] * (size_t)nd + (size_t)tc[e]]; x = x + tv[e]; }
+        for (int64_t l = 0; l < nd; l++) td[(size_t)l] = T[(size_t)l * (size_t)nd + (size_t)l];
+        for (int64_t l = 0; l < nd; l++) REQUIRE(std::isfinite(td[(size_t)l]) && td[(size_t)l] > 0.0, NGP_ERR_ARG, "hybrid random-effect set: every diagonal entry of K must be > 0");
+        dk = std::make_shared<DenseK>();
+        if (dk->K.alloc_raw((size_t)nd * (size_t)nd) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "dense block of a hybrid set");
+        dk->q = nd; dk->ld = nd;
+        HCHK(hipMemcpy(dk->K, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else if (k_src) {
+        REQUIRE(k_src != h, NGP_ERR_ARG, "hybrid random-effect set: k_src is this handle (a set shares the block of a set on ANOTHER handle)");
+        REQUIRE(k_src->stream != nullptr && k_src->pm && !k_src->panel_open, NGP_ERR_ARG, "hybrid random-effect set: k_src has no panel or records yet (or its panel is still open)");
+        REQUIRE(k_src->device == h->device, NGP_ERR_ARG, "hybrid random-effect set: a shared block must be on this handle's device");
+        REQUIRE(k_src_set >= 0 && k_src_set < (int32_t)k_src->mm.rnd.size() && k_src->mm.rnd[(size_t)k_src_set].hyb, NGP_ERR_ARG,
+                "hybrid random-effect set: k_src_set is not a hybrid set of k_src");
+        dk = k_src->mm.rnd[(size_t)k_src_set].dk;  // (T of that set: its S_tt is in it already; this set's S_tt is taken to be the same)
+        REQUIRE(dk->q == nd, NGP_ERR_ARG, "hybrid random-effect set: the shared block has another nd");
+        HCHK(hipStreamSynchronize(k_src->stream));
+        HCHK(hipMemcpy2D(td.data(), sizeof(double), dk->K, (size_t)(dk->ld + 1) * sizeof(double), sizeof(double), (size_t)nd, hipMemcpyDeviceToHost));
+    } else {
+        REQUIRE(h->grm.state == 4, NGP_ERR_STATE, "hybrid random-effect set without D: this handle has no single-step corner block (ngp_grm_single_step)");
+        REQUIRE(h->grm.N == nd, NGP_ERR_ARG, "hybrid random-effect set: the corner block has another size than nd");
+        dk = h->grm.m;
+        from_grm = true;
+        HCHK(hipStreamSynchronize(h->stream));
+        HCHK(hipMemcpy2D(td.data(), sizeof(double), dk->K, (size_t)(dk->ld + 1) * sizeof(double), sizeof(double), (size_t)nd, hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < tv.size(); e++) if (tr[e] == tc[e]) td[(size_t)tr[e]] = td[(size_t)tr[e]] + tv[e];  // (the sum k_hyb_fold forms)
+    }
+    for (int64_t l = 0; l < nd; l++) REQUIRE(std::isfinite(td[(size_t)l]) && td[(size_t)l] > 0.0, NGP_ERR_ARG, "hybrid random-effect set: every diagonal entry of K must be > 0");
+    for (int64_t l = 0; l < nd; l++) kd[(size_t)(hd + l)] = td[(size_t)l];
+    std::vector<long long> lp;
+    std::vector<int> lr, lv;
+    std::vector<double> zpz;
+    group_levels(h, level, q, lp, lr, lv, zpz);
+    HRand R;
+    R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = true; R.hyb = true; R.hd = hd;
+    R.sdf = scale * df; R.scaleM = {R.sdf}; R.varU0M = {varU0};
+    if (hd > 0) {  // the level schedule of the head rows, exactly as ngp_add_random_set plans it: every column c < l of a head row is a head column
+        std::vector<int> dep((size_t)hd, 0);
+        for (int64_t l = 0; l < hd; l++) {
+            int d = 0;
+            for (long long p = fp[(size_t)l]; p < fp[(size_t)l + 1] && fcol[(size_t)p] < l; p++) d = std::max(d, dep[(size_t)fcol[(size_t)p]] + 1);
+            dep[(size_t)l] = d;
+        }
+        if ((rc = plan_schedule(h, R, dep))) return rc;
+    }
+    if (fcol.empty()) { fcol.push_back(0); fval.push_back(0.0); }  // (no empty device arrays; fp says that nothing is stored)
+    const double vu[2] = {varU0, 0.0};
+    if ((rc = upload(h, R.d_lptr, lp)) || (rc = upload(h, R.d_lrows, lr)) || (rc = upload(h, R.d_level, lv)) || (rc = upload(h, R.d_kptr, fp)) ||
+        (rc = upload(h, R.d_kcol, fcol)) || (rc = upload(h, R.d_kval, fval)) || (rc = upload(h, R.d_kdiag, kd)) || (rc = upload(h, R.d_zpz, zpz)))
+        return rc;
+    if ((rc = R.d_u.alloc(h, (size_t)q)) || (rc = R.d_sum_u.alloc(h, (size_t)q)) || (rc = R.d_vu.alloc(h, 2)) ||
+        (rc = R.d_scr.alloc(h, (size_t)NGP_RS_ROWS_HYBRID * (size_t)q)))
+        return rc;
+    HCHK(hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice));
+    if (from_grm && !tv.empty()) {  // T = D + S_tt on the device, one sum per stored entry (nothing below refuses the call on an argument)
+        DevArray<int> d_tr, d_tc;
+        DevArray<double> d_tv;
+        if ((rc = upload(h, d_tr, tr)) || (rc = upload(h, d_tc, tc)) || (rc = upload(h, d_tv, tv))) return rc;
+        hipLaunchKernelGGL(k_hyb_fold, dim3((unsigned)((tv.size() + 255) / 256)), dim3(256), 0, h->stream, dk->K.get(), (long long)dk->ld, (long long)tv.size(),
+                           (const int *)d_tr, (const int *)d_tc, (const double *)d_tv);
+        HCHK(hipStreamSynchronize(h->stream));
+    }
+    uint64_t kdig = dk->digest;
+    if (!k_src && (rc = dense_digest(h, *dk, &kdig))) return rc;
+    // the model signature: the level coding and S as a CSR set digests them, then the dense block as a dense set digests it
+    R.sig = bytes_digest(bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull ^ 0x485942ull, lv.data(), lv.size() * 4), kp.data(), kp.size() * 8), kc.data(),
+                                      kc.size() * 4), kv.data(), kv.size() * 8);
+    R.sig = bytes_digest(bytes_digest(R.sig, &nd, sizeof(nd)), &kdig, sizeof(kdig));
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    dk->digest = kdig;
+    R.dk = std::move(dk);
+    if (from_grm) h->grm = Grm();  // consumed: the set owns the block now
     if (set_id) *set_id = (int32_t)h->mm.rnd.size();
     h->mm.rnd.push_back(std::move(R));
     return NGP_OK;

@@ -700,6 +700,37 @@ function grm_get(h::Handle, N::Integer)
     check(h, ccall((:ngp_grm_get, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, G))
     return G
 end
+# ---- single-step GBLUP (include/nextgp_hip.h): H^-1 = A^-1 + [0 0; 0 inv((1 - w) G + w A22) - inv(A22)].  The reference has no single-step
+# model, so nothing of the coarse seam routes here: these are direct bindings for a caller that builds the model itself. ----
+# A22 = A[idx, idx] without the dense A (ngp_pedigree_a22: Colleau's indirect method on the host); F from pedigree_ainv, idx 0-based
+function pedigree_a22(sire::Vector{Int32}, dam::Vector{Int32}, F::Vector{Float64}, idx::Vector{Int64})
+    n = length(sire); m = length(idx)
+    (length(dam) == n && length(F) == n && m >= 1) || error("pedigree_a22: one sire, dam and F per animal, and at least one listed animal")
+    A22 = Matrix{Float64}(undef, m, m)
+    rc = ccall((:ngp_pedigree_a22, LIB), Int32, (Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Float64}, Int64),
+               n, sire, dam, F, idx, m, A22, m)
+    rc == 0 || error("ngp_pedigree_a22: " * unsafe_string(ccall((:ngp_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return A22
+end
+# after grm_end!, in place of grm_invert!: the handle's matrix becomes the corner block D (grm_get returns it)
+function grm_single_step!(h::Handle, A22::Matrix{Float64}, w::Float64)
+    size(A22, 1) == size(A22, 2) || error("single-step: A22 must be square")
+    check(h, ccall((:ngp_grm_single_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64), h.ptr, A22, size(A22, 1), w))
+end
+# K = S + embed(D): S as CSR with 0-based ascending columns (pedigree_ainv's layout, renumbered so that the genotyped animals are the
+# LAST nd levels); D === nothing takes over the handle's own corner block (grm_single_step!), a matrix is copied to the device
+function add_random_set_hybrid!(h::Handle, level::Vector{Int32}, q::Integer, kp::Vector{Int64}, kc::Vector{Int32}, kv::Vector{Float64}, nd::Integer,
+                                D::Union{Nothing,Matrix{Float64}}, df::Float64, scale::Float64, varU0::Float64)
+    length(kp) == q + 1 || error("hybrid random-effect set: k_ptr needs q + 1 entries")
+    (D === nothing || size(D) == (nd, nd)) || error("hybrid random-effect set: D must be $nd x $nd")
+    id = Ref{Int32}(0)
+    dp = D === nothing ? Ptr{Float64}(C_NULL) : pointer(D)
+    GC.@preserve D check(h, ccall((:ngp_add_random_set_hybrid, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Cvoid}, Int32, Float64, Float64, Float64, Ref{Int32}),
+                   h.ptr, level, q, kp, kc, kv, nd, dp, C_NULL, 0, df, scale, varU0, id))
+    return id[]
+end
+
 function makeG(M::Matrix; method::Integer=1, device::Integer=0, inverse::Bool=false)
     h = Handle(device=device)
     grm_begin!(h, size(M, 1), method); grm_columns!(h, M); grm_end!(h)
