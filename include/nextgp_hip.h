@@ -70,7 +70,8 @@ int32_t ngp_get_near_lags(ngp_handle *h, int32_t *near);
  * sweep (k_tinv) -- the forward substitution the 64 steps carry out, as one 64 x 64 product.  The same Markov chain in real
  * arithmetic; the floating-point order differs, so the blocked oracle is told (ora_set_tform).  Measured:
  * pays where the sampler's serial chain is the bound (compact storage), costs 2-4 % where its CU's memory traffic is.  Any time
- * before ngp_run. */
+ * before ngp_run, also between two runs of one chain: the next ngp_run / ngp_run_many / ngp_sweep_set takes the form in force, and
+ * ngp_get_chain_form reports the form the next sweep runs. */
 int32_t ngp_set_chain_form(ngp_handle *h, int32_t form);
 int32_t ngp_get_chain_form(ngp_handle *h, int32_t *form);
 /* Diagnostic only: enable != 0 makes the persistent kernel write 100 MHz time stamps (sampler: 4 words per
@@ -305,7 +306,11 @@ int32_t ngp_posterior_len(ngp_handle *h, int64_t *len);
 int32_t ngp_export_posterior_device(ngp_handle *h, void *device_ptr, int64_t len);
 
 /* Fine seam: one call of M[set].funct(mSet, M, beta, delta, ycorr, varE, varBeta) (src/samplers.jl:52).
- * In/out arrays are the caller's: ycorr N, beta ncol, delta ncol (out), varBeta nreg, piHat 2 (BayesB). */
+ * In/out arrays are the caller's: ycorr N, beta ncol, delta ncol (out), varBeta nreg, piHat 2 (BayesB).
+ * The call works in the handle's own chain arrays: the handle's residual, the set's effects, indicators, variances and pi, and varE
+ * then hold the caller's values, so a chain that ngp_run has under way on the same handle does not go on as if the call had not been
+ * made (put its state back with ngp_set_state, or keep one handle per seam).  What the call returns does not depend on the handle's
+ * chain: the set's own call counter keys its draws, ngp_set_y restarts it. */
 int32_t ngp_sweep_set(ngp_handle *h, int32_t set_id, double varE, double *ycorr, double *beta, int64_t *delta, double *varBeta,
                       double *piHat);
 /* The same call with the caller's state in DEVICE memory of the handle's device (ycorr N, beta ncol, varBeta nreg doubles; delta
@@ -627,8 +632,11 @@ int32_t ngp_set_rc_state(ngp_handle *h, int32_t set_id, const double *piHat, con
  * the grid, the device or the number of chains served by a launch.  In a fused ngp_run_many ONE launch per kept iteration serves
  * every chain whose marker sets lie on the same columns as the leader's, each chain bit for bit what it computes alone;
  * ngp_get_prediction_stats counts the launches a handle made and the chains they served (fused: the leader counts, the others 0).
- * The sums are zeroed by ngp_set_y.  They are not part of snapshots, of the packed posterior or of ngp_allreduce_posterior (formats
- * unchanged): a host carries them beside a snapshot with ngp_get_prediction / ngp_set_prediction, and pools chains itself.
+ * The sums are zeroed by ngp_set_y.  A prediction panel loaded or replaced while a chain is under way starts the prediction sums of
+ * that chain at zero (its next ngp_run sizes them for the new panel) while nKept goes on counting the chain's kept draws: the sums
+ * then hold the kept draws since the panel came, fewer than nKept.  They are not part of snapshots, of the packed posterior or of
+ * ngp_allreduce_posterior (formats unchanged): a host carries them beside a snapshot with ngp_get_prediction / ngp_set_prediction, and
+ * pools chains itself.
  * Arrays are [nsets + 1][Np], row-major (row s contiguous).  nKept is the count ngp_get_posterior_sums reports.
  * ngp_get_prediction_last: g_s and g of the last kept draw.  ngp_get_prediction_layout: rows per shard R, shards S of the prediction
  * tiles, the chunk length in columns of the normative sum, and the rows of this handle's prediction arrays (nsets + 1; 0 while it

@@ -486,7 +486,8 @@ class Sampler:
         return dict(alloc_ms=a.value, tiles_ms=t.value, gram_ms=g.value)
 
     def set_chain_form(self, form):
-        """1 (default): BayesPR blocks as dlt = T e0 (k_tinv); 0: the 64 serial steps per block."""
+        """0 (default): the 64 serial steps per block; 1: linear blocks (BayesPR, BayesLV, Tuple) as dlt = T e0 (k_tinv).  May be called
+        between runs of one chain: the next run takes the new form."""
         self._chk(self.L.ngp_set_chain_form(self.h, C.c_int32(int(form))))
 
     def chain_form(self):

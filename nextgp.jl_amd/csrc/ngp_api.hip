@@ -1026,7 +1026,8 @@ bool wants_tinv(const ngp_handle *h) {
 // one: those lanes are inactive): their chain takes the inverse form (k_tinv).  Static for a model; the table goes to the device when
 // the model or the active set changed.  A Tuple set owns its blocks to the end of the last one (ncol = its span).
 int sync_linear_blocks(ngp_handle *h, int active_set) {
-    if (!wants_tinv(h) || h->cm.tinv_blocks != h->NBLK) { h->cm.lin_all = 0; h->cm.lin_any = 0; return NGP_OK; }
+    // (the flags are cleared: the key goes stale with them, or a later call under form 1 would find it matching and keep them zero)
+    if (!wants_tinv(h) || h->cm.tinv_blocks != h->NBLK) { h->cm.lin_all = 0; h->cm.lin_any = 0; h->cm.blin_for = -2; return NGP_OK; }
     if (h->cm.blin_for == active_set) return NGP_OK;
     // 1 = BayesPR / unowned / inactive lanes only; 1 + k = a block of a k-set Tuple (its chain is linear too: one step per locus);
     // 0 = a lane of BayesB / BayesC / BayesR: the step chains
@@ -3433,6 +3434,9 @@ int32_t ngp_set_chain_form(ngp_handle *h, int32_t form) {
     int rc;
     if ((rc = enter(h))) return rc;
     REQUIRE(form == 0 || form == 1, NGP_ERR_ARG, "chain form: 0 (64 steps per block) or 1 (linear blocks by the inverse form)");
+    // the table of linear blocks and its flags belong to the form they were built under.  (Belt and braces: sync_linear_blocks already
+    // drops the key whenever it clears the flags, which alone keeps "flags zero behind a matching key" impossible.)
+    if (form != h->chain_form) h->cm.blin_for = -2;
     h->chain_form = form;
     return NGP_OK;
     NGP_CATCH(h)

@@ -39,3 +39,25 @@ def test_inverse_form_equals_the_step_chain_and_the_reference_order(O):
             assert np.abs(res[key]["beta"] - res["ref"]["beta"]).max() <= tol * scale, (rho, key)
             assert abs(res[key]["varE"] / res["ref"]["varE"] - 1) <= tol
         assert not np.array_equal(res["inv"]["beta"], res["steps"]["beta"])   # another summation order, not the same bits
+
+
+def test_a_chain_toggled_between_the_forms_is_neither_untoggled_chain(O):
+    """The form switched 1 -> 0 -> 1 between three segments of one chain (Oracle.set_tform, what ngp_set_chain_form does on a used
+    handle): after the third segment its bits differ from the chain that stayed on form 1 and from the one that stayed on form 0.  So a
+    device that silently keeps running form 0 after the switch back (tests/test_gpu_lifecycle.py, case 1a) cannot equal this oracle."""
+    N, P, seg = 300, 200, 5
+    X, y, bt, v = make_problem(O, N, P, seed=3)
+    res = {}
+    for key, forms in (("toggled", (1, 0, 1)), ("inv", (1, 1, 1)), ("steps", (0, 0, 0))):
+        o = O.Oracle(order=1, seed=17, chain=1)
+        o.set_panel_f32(X, R=40, S=8, D=4, near=2, nchain=8, tform=forms[0])
+        add_sets(o, [(0, 120, "PR"), (120, 80, "B")], v)
+        o.set_y(y); o.set_residual_prior(4.0, 0.25 * y.var()); o.set_schedule(3 * seg, 2, 2)
+        for f in forms:
+            o.set_tform(f)
+            o.run(seg)
+        res[key] = o.get_state()
+    for key in ("inv", "steps"):
+        assert res[key]["iter"] == res["toggled"]["iter"] == 3 * seg
+        assert not np.array_equal(res["toggled"]["beta"], res[key]["beta"]), key
+        assert not np.array_equal(res["toggled"]["ycorr"], res[key]["ycorr"]), key
