@@ -684,6 +684,39 @@ int32_t ngp_set_genomic_variance(ngp_handle *h, const double *sumV, const double
 int32_t ngp_get_genomic_variance_trace(ngp_handle *h, double *V, double *ratio, int64_t rows, int64_t nslots);
 int32_t ngp_get_genomic_variance_stats(ngp_handle *h, int64_t *launches, int64_t *chains_served);
 
+/* ---- convergence diagnostics of every kept draw: mean, SD, effective sample size and Monte-Carlo standard error per parameter ----
+ * Behind every KEPT iteration (and in no other) one element-wise pass updates a streaming lag-window autocovariance of every
+ * monitored scalar; nothing is launched while the diagnostics are off.  The monitored vector theta[D] is the doubles of the sample
+ * record in record order (csrc/ngp_state.h, diag_layout): varE | b | b_fixed | u, then varU of the random-effect sets | beta[P] |
+ * varBeta | piHat[2] per marker set | class probabilities | per BayesLV set c[16], varZeta | the drawn thresholds t_2 .. t_{C-1}.
+ * The arithmetic is normative ("Convergence diagnostics"; tests/ref_diag.py) and bit for bit the same alone
+ * and in a fused ngp_run_many.  The ESS is Geyer's initial positive sequence estimator over the lags 0 .. lags-1.
+ * ngp_enable_diagnostics: on / off, the window (lags even, 2 .. 256; 64 is the usual choice) and split: draws with index < split feed
+ * half 0, the others half 1 (the halves are the sequences of a split-R-hat; a host pools chains).  Needs a model (a finished panel or
+ * ngp_set_records); zeroes the state.  NGP_ERR_ARG for an odd lags or one out of range and for split < 0; NGP_ERR_NOMEM when the
+ * (3 lags + 5) D doubles do not fit -- the diagnostics are then off and the handle runs on.  D follows the model until the first kept
+ * draw; a model that changes afterwards makes ngp_run fail with NGP_ERR_STATE (enable again).
+ * ngp_get_diagnostics_layout: D, lags, split, the draws taken and the words of the state image.
+ * ngp_get_diagnostics: per parameter mean, sample variance, ESS, MCSE = sqrt(var / ESS), truncated (1: the positive sequence had not
+ * ended inside the window -- the ESS is an upper bound; raise lags or thin more), and per half the number of draws half_n[2], the
+ * means half_mean[2][D] and the variances half_var[2][D] (NaN below two draws).  Any pointer may be NULL; with no draw taken the call
+ * returns NGP_OK, sets *n = 0 and leaves the arrays untouched.
+ * ngp_get_diagnostics_state / ngp_set_diagnostics_state: the state as x1[D] | S1[2][D] | S2[2][D] | C[lags][D] | head[lags][D] |
+ * ring[lags][D] with the draws taken, for resume beside a snapshot.  ngp_get_diagnostics_stats: updates this handle launched.
+ * The state is zeroed wherever sum_beta is (ngp_set_y), dropped with a new panel, and is not part of snapshots, the packed
+ * posterior, sample records or ngp_allreduce_posterior. */
+int32_t ngp_enable_diagnostics(ngp_handle *h, int32_t on, int32_t lags, int64_t split);
+int32_t ngp_get_diagnostics_layout(ngp_handle *h, int64_t *D, int32_t *lags, int64_t *split, int64_t *n, int64_t *state_words);
+int32_t ngp_get_diagnostics(ngp_handle *h, double *mean, double *var, double *ess, double *mcse, double *truncated, double *half_n, double *half_mean,
+                            double *half_var, int64_t D, int64_t *n);
+int32_t ngp_get_diagnostics_state(ngp_handle *h, double *state, int64_t words, int64_t *n);
+int32_t ngp_set_diagnostics_state(ngp_handle *h, const double *state, int64_t words, int64_t n);
+int32_t ngp_get_diagnostics_stats(ngp_handle *h, int64_t *launches);
+/* Timing hook of the diagnostics: device events around reps full-window updates (gather + update at draw indices >= lags, on a scratch
+ * copy of the state: the chain's state and draw count stay what they are) and around reps finalise kernels over the chain's state;
+ * milliseconds per launch (finalise: 0 while no draw is taken).  Allocates a second state for the call. */
+int32_t ngp_debug_time_diagnostics(ngp_handle *h, int32_t reps, double *update_ms, double *finalise_ms);
+
 /* ---- held-out records: missing phenotypes and cross-validation folds by data augmentation ----
  * A handle may carry a hold-out set H: m strictly increasing 0-based rows, 0 <= i < N, m < N.  A held-out record stays in the panel;
  * its phenotype is never read (ngp_set_y accepts NaN there and starts the record at the mean of the observed phenotypes) and is

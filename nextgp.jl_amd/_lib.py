@@ -205,6 +205,8 @@ SYMBOLS = [
     "ngp_debug_set_staging_bytes",
     "ngp_set_threshold_step", "ngp_get_threshold_step", "ngp_set_threshold_step_state",
     "ngp_enable_class_probabilities", "ngp_get_class_probabilities", "ngp_set_class_probabilities", "ngp_debug_pnorm",
+    "ngp_enable_diagnostics", "ngp_get_diagnostics_layout", "ngp_get_diagnostics", "ngp_get_diagnostics_state", "ngp_set_diagnostics_state",
+    "ngp_get_diagnostics_stats", "ngp_debug_time_diagnostics",
 ]
 
 THRESHOLD_STEPS = {"albert-chib": 0, "cowles": 1}
@@ -759,6 +761,57 @@ class Sampler:
         """(variance passes this handle launched, chains they served)."""
         a, b = C.c_int64(), C.c_int64()
         self._chk(self.L.ngp_get_genomic_variance_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    # ---- convergence diagnostics (ngp_enable_diagnostics; DESIGN.md section 2, "Convergence diagnostics") ----
+    def enable_diagnostics(self, on=True, lags=64, split=0):
+        """Every kept iteration then updates a lag-window autocovariance (lags 0 .. lags-1) of every monitored scalar (diagnostics());
+        draws with index < split feed half 0, the others half 1.  Zeroes the state."""
+        self._chk(self.L.ngp_enable_diagnostics(self.h, C.c_int32(int(bool(on))), C.c_int32(int(lags)), C.c_int64(int(split))))
+
+    def diagnostics_layout(self):
+        """(D, lags, split, draws taken, words of the state image)."""
+        D, L, H, n, w = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.L.ngp_get_diagnostics_layout(self.h, C.byref(D), C.byref(L), C.byref(H), C.byref(n), C.byref(w)))
+        return D.value, L.value, H.value, n.value, w.value
+
+    def diagnostics(self):
+        """dict(n, mean, var, sd, ess, mcse, truncated [D], half_n [2], half_mean, half_var [2, D]); the arrays are NaN while no draw is taken."""
+        D = self.diagnostics_layout()[0]
+        a = {k: np.full(D, np.nan) for k in ("mean", "var", "ess", "mcse", "truncated")}
+        hn, hm, hv, n = np.zeros(2), np.full((2, D), np.nan), np.full((2, D), np.nan), C.c_int64()
+        self._chk(self.L.ngp_get_diagnostics(self.h, *[_p(a[k], C.c_double) for k in ("mean", "var", "ess", "mcse", "truncated")], _p(hn, C.c_double),
+                                             _p(hm, C.c_double), _p(hv, C.c_double), C.c_int64(D), C.byref(n)))
+        return dict(n=n.value, sd=np.sqrt(a["var"]), half_n=hn, half_mean=hm, half_var=hv, **a)
+
+    def diagnostics_names(self):
+        """One name per monitored scalar, "<Out-file stem>:<column header>" (betaM1:M7, varM1:reg_1, varE:e): the names runLMEM derived
+        from the headers of its *Out files, or theta:<i> for a chain that was built by hand."""
+        D = self.diagnostics_layout()[0]
+        names = getattr(self, "_diag_names", None)
+        return list(names) if names is not None and len(names) == D else [f"theta:{i + 1}" for i in range(D)]
+
+    def diagnostics_state(self):
+        """dict(state, n): x1[D] | S1[2][D] | S2[2][D] | C[lags][D] | head[lags][D] | ring[lags][D] and the draws taken (resume)."""
+        w = self.diagnostics_layout()[4]
+        st, n = np.empty(w), C.c_int64()
+        self._chk(self.L.ngp_get_diagnostics_state(self.h, _p(st, C.c_double), C.c_int64(w), C.byref(n)))
+        return dict(state=st, n=n.value)
+
+    def set_diagnostics_state(self, ds):
+        st = np.ascontiguousarray(ds["state"], dtype=np.float64)
+        self._chk(self.L.ngp_set_diagnostics_state(self.h, _p(st, C.c_double), C.c_int64(st.size), C.c_int64(int(ds["n"]))))
+
+    def diagnostics_stats(self):
+        """Updates this handle launched."""
+        a = C.c_int64()
+        self._chk(self.L.ngp_get_diagnostics_stats(self.h, C.byref(a)))
+        return a.value
+
+    def debug_time_diagnostics(self, reps=20):
+        """(ms per full-window update, ms per finalise kernel) between device events; the chain's state is not touched."""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.ngp_debug_time_diagnostics(self.h, C.c_int32(int(reps)), C.byref(a), C.byref(b)))
         return a.value, b.value
 
     # ---- model -------------------------------------------------------------------------

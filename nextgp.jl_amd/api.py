@@ -740,6 +740,125 @@ def summaryMCMC(param, outFolder=None):
     return np.loadtxt(os.path.join(outFolder, f"{param}Out"), delimiter="\t", skiprows=1, ndmin=2).mean(axis=0, keepdims=True)
 
 
+# ----------------------------------------------------------------------------------------------
+# convergence diagnostics (ngp_enable_diagnostics; DESIGN.md section 2, "Convergence diagnostics")
+# ----------------------------------------------------------------------------------------------
+def pool_diagnostics(per_chain):
+    """Chains' diagnostics (Sampler.diagnostics()) pooled on the host.  The sequences of the split-R-hat are every half with n_s >= 2 of
+    every chain: W = mean(var_s), n_bar = mean(n_s), B/n = var(mean_s, ddof=1), var+ = (n_bar - 1) / n_bar W + B/n, rhat = sqrt(var+ / W)
+    (NaN with fewer than two sequences or W = 0).  mean: the n-weighted mean of the chains' means; sd = sqrt(var+) (with a single
+    sequence: of its variance); ess = sum of the chains'; mcse = sd / sqrt(ess); truncated: the OR over the chains."""
+    per_chain = list(per_chain)
+    D = len(per_chain[0]["mean"])
+    seq = [(float(c["half_n"][h]), np.asarray(c["half_mean"][h], dtype=np.float64), np.asarray(c["half_var"][h], dtype=np.float64))
+           for c in per_chain for h in range(2) if c["half_n"][h] >= 2]
+    ns = np.array([float(c["n"]) for c in per_chain])
+    with np.errstate(all="ignore"):
+        mean = sum(n * np.asarray(c["mean"], dtype=np.float64) for n, c in zip(ns, per_chain)) / ns.sum()
+        ess = sum(np.asarray(c["ess"], dtype=np.float64) for c in per_chain)
+        W = np.mean([v for _, _, v in seq], axis=0) if seq else np.full(D, np.nan)
+        if len(seq) >= 2:
+            n_bar = float(np.mean([n for n, _, _ in seq]))
+            var_plus = (n_bar - 1.0) / n_bar * W + np.var(np.array([m for _, m, _ in seq]), axis=0, ddof=1)
+            rhat = np.where(W > 0, np.sqrt(var_plus / W), np.nan)
+        else:
+            var_plus, rhat = W, np.full(D, np.nan)
+        sd = np.sqrt(var_plus)
+        truncated = np.any([np.asarray(c["truncated"]) > 0 for c in per_chain], axis=0).astype(np.float64)
+        return dict(n=int(ns.sum()), mean=mean, sd=sd, mcse=sd / np.sqrt(ess), ess=ess, rhat=rhat, truncated=truncated)
+
+
+def _diagnostics_option(diagnostics):
+    """runLMEM(diagnostics=False | True | {"lags": L}) -> None or the lags.  Host checks only."""
+    if diagnostics is False or diagnostics is None:
+        return None
+    if diagnostics is True:
+        return 64
+    if isinstance(diagnostics, dict) and set(diagnostics) == {"lags"}:
+        L = diagnostics["lags"]
+        if isinstance(L, (int, np.integer)) and not isinstance(L, bool) and 2 <= int(L) <= 256 and int(L) % 2 == 0:
+            return int(L)
+        raise ValueError("diagnostics: lags must be an even integer, 2 .. 256")
+    raise ValueError('diagnostics: False, True or {"lags": L}')
+
+
+def _diagnostics_names(D, sets, fixed_names, intercept, randoms=(), nthr=0):
+    """One name per monitored scalar, "<Out-file stem>:<column header>", in the order of the sample record (csrc/ngp_state.h,
+    diag_layout), from the headers _write_headers gives the *Out files and the indexing samples_to_out_files cuts their rows with."""
+    fx = list(fixed_names)
+    head = ["varE:e", f"b:{fx[0]}" if intercept and fx else "b:intercept"] + [f"b:{nm}" for nm in (fx[1:] if intercept else fx)]
+    for rd in randoms:   # u: the levels in order; the k components of a level of a correlated set adjacent
+        if "members" not in rd:
+            head += [f"{_rd_files(rd)[0]}:{lv}" for lv in rd["levels"]]
+        else:
+            head += [f"u{m}:{lv}" for lv in rd["levels"] for m in rd["members"]]
+    for rd in randoms:   # varU: row-major in the record, column by column in the file
+        file, fields = _rd_headers(rd)[-1]
+        k = _rd_k(rd)
+        head += [f"{file}:{fields[b * k + a]}" for a in range(k) for b in range(k)]
+    tail = []
+    for s in sets:
+        tail += [f"var{s['name']}:{nm}" for nm in _var_names(s)]
+    for s in sets:       # piHat[2] of every set; only BayesB / BayesC sets write it (as pi<set>Out)
+        stem = f"pi{s['name']}" if isinstance(s["prior"], (BayesBType, BayesCType)) else f"piHat{s['name']}"
+        tail += [f"{stem}:pi1", f"{stem}:pi2"]
+    for s in sets:
+        K = len(s["prior"].pi) * s.get("A", 1) if isinstance(s["prior"], (BayesRType, BayesRCType)) else 0
+        tail += [f"pi{s['name']}:pi{v + 1}" for v in range(K)]
+    for s in sorted((s for s in sets if isinstance(s["prior"], BayesLogVarType)), key=lambda s: s["lv"]):
+        # (c<set>Out has ncov columns; the slots behind them are constants of the record, named apart so that a file's rows are its columns)
+        tail += [f"c{s['name']}:c{v + 1}" if v < s["ncov"] else f"cUnused{s['name']}:slot{v + 1}" for v in range(16)] + [f"varZeta{s['name']}:varZeta"]
+    tail += [f"threshold:t{c + 2}" for c in range(nthr)]
+    P = D - len(head) - len(tail)
+    if P < 0:
+        raise ValueError("internal: the monitored vector is shorter than the names of the model's parameters")
+    beta = [f"beta:col{j + 1}" for j in range(P)]   # (columns no set owns: the padding between correlated sets)
+    for s in sets:
+        for m, nm in enumerate(s["members"]):
+            for j, c in enumerate(np.asarray(s["cols"])[:, m]):
+                beta[int(c)] = f"beta{nm}:M{j + 1}"
+    return head + beta + tail
+
+
+def _worst(names, d):
+    ess, rhat = np.asarray(d["ess"], dtype=np.float64), np.asarray(d.get("rhat", np.full(len(names), np.nan)), dtype=np.float64)
+    lo = [int(i) for i in np.argsort(np.where(np.isnan(ess), np.inf, ess), kind="stable")[:10]]
+    hi = [int(i) for i in np.argsort(-np.where(np.isnan(rhat), -np.inf, rhat), kind="stable")[:10] if not np.isnan(rhat[i])]
+    return dict(ess=[names[i] for i in lo], rhat=[names[i] for i in hi])
+
+
+def write_convergence_file(path, names, d):
+    """convergence.txt: a header, then one line per parameter: name mean sd mcse ess rhat truncated (tab-separated, every digit)."""
+    rhat = d.get("rhat", np.full(len(names), np.nan))
+    with open(path, "w") as f:
+        f.write("\t".join(["name", "mean", "sd", "mcse", "ess", "rhat", "truncated"]) + "\n")
+        for i, nm in enumerate(names):
+            f.write("\t".join([nm] + [repr(float(d[k][i])) for k in ("mean", "sd", "mcse", "ess")] + [repr(float(rhat[i])), str(int(d["truncated"][i]))]) + "\n")
+
+
+def read_convergence_file(path):
+    """dict(names, mean, sd, mcse, ess, rhat, truncated) of a convergence.txt."""
+    rows = [ln.rstrip("\n").split("\t") for ln in open(path)][1:]
+    out = dict(names=[r[0] for r in rows])
+    for j, k in enumerate(("mean", "sd", "mcse", "ess", "rhat", "truncated")):
+        out[k] = np.array([float(r[j + 1]) for r in rows], dtype=np.float64)
+    return out
+
+
+def convergencyMCMC(param, summary=False, outFolder=None):
+    """The reference's convenience function (docs/src/index.md:62-88) without MCMCChains: the posterior-mean row of <param>Out, as
+    summaryMCMC gives it; with summary=True also the convergence.txt rows of that file's columns (a run with diagnostics=True wrote
+    them from the device's streaming sums -- the *Out file is not needed for them) as dict(names, mean, sd, mcse, ess, rhat, truncated)."""
+    outFolder = outFolder or os.path.join(os.getcwd(), "outMCMC")
+    if not summary:
+        return summaryMCMC(param, outFolder)
+    cv = read_convergence_file(os.path.join(outFolder, "convergence.txt"))
+    pick = [i for i, nm in enumerate(cv["names"]) if nm.split(":", 1)[0] == param]
+    rows = dict(names=[cv["names"][i].split(":", 1)[1] for i in pick], **{k: cv[k][pick] for k in ("mean", "sd", "mcse", "ess", "rhat", "truncated")})
+    mean = summaryMCMC(param, outFolder) if os.path.exists(os.path.join(outFolder, f"{param}Out")) else rows["mean"][None, :]
+    return mean, rows
+
+
 def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, randoms=()):
     """Binary sample stream (ngp_set_sample_file) -> the rows of the reference's *Out text files (src/samplers.jl:56-104), appended
     behind the header rows: the same text, number for number, as writing them at every kept iteration.  Record by record -- one
@@ -799,7 +918,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -877,9 +996,20 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     and res["random"][col]["levels"] name them in that order.  G is built on the device (type: VanRaden's method), A22 by Colleau's
     method on the host; chains=K share the dense block by reference.  "H" without singleStep[col], singleStep for a term whose prior is
     not "H": ValueError; "H" inside a tuple key and summaryStat on the term: NotImplementedError.  G is not scaled to A22.
+    diagnostics=True (or {"lags": L}, L even in 2..256; True means 64) follows every monitored scalar -- the doubles of a kept sample:
+    varE, b, the fixed and random effects, every marker effect and variance, pi -- with a streaming lag-window autocovariance on the
+    device (ngp_enable_diagnostics; DESIGN.md section 2, "Convergence diagnostics").  res["diagnostics"] = {"names", "n", "mean", "sd",
+    "mcse", "ess", "rhat", "truncated", "chains": [each chain's own], "worst": {"ess": the ten lowest-ESS names, "rhat": the ten largest}};
+    names are "<Out-file stem>:<column header>" (betaM1:M7, varM1:reg_1, varE:e).  outFolder/convergence.txt holds one line per
+    parameter: name mean sd mcse ess rhat truncated.  chains=K pools the chains into a split-R-hat (pool_diagnostics; the halves part at
+    the middle of the planned kept draws); folds=K pools nothing -- its chains see different data -- and reports per chain only
+    (convergence.txt under chain<c>/).  truncated = 1: the positive sequence had not ended inside the window, the ESS is an upper
+    bound -- raise lags or thin more.  convergencyMCMC(param, summary=True, outFolder=...) returns a file's rows of it.
+
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
+    diag_lags = _diagnostics_option(diagnostics)   # (checked before any device work)
     parsed = parse_formula(formula, random_effects=True, pedigree=True)
     lhs, intercept, snps = parsed
     has_ped = userPedData is not None and len(userPedData) > 0
@@ -1052,6 +1182,9 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
                 if gv_windows.get(st["name"]):
                     sc.set_variance_windows(st["id"], gv_windows[st["name"]])
             sc.enable_genomic_variance(True, float(windowThreshold), max(0, (int(nChain) - int(nBurn)) // int(nThin)))
+    if diag_lags is not None:   # behind set_y, with an empty state; the halves of the split-R-hat part at the middle of the planned draws
+        for sc in samplers:
+            sc.enable_diagnostics(True, diag_lags, max(0, (int(nChain) - int(nBurn)) // int(nThin)) // 2)
     folders = [outFolder] if K == 1 else [os.path.join(outFolder, f"chain{chain + c}") for c in range(K)]
     for f in folders:
         os.makedirs(f, exist_ok=True)
@@ -1099,6 +1232,21 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         pooled = {k: sum(gs[k] for gs in sums) for k in ("sumV", "sumV2", "sumQ", "sumQ2", "count", "ratio", "nKept")}
         res["variance"] = _variance_result(pooled, names, wins, float(windowThreshold))
         write_gwas_files(outFolder, res["variance"])
+    if diag_lags is not None:
+        nthr = liab["C"] - 2 if liab is not None and liab["kind"] == "classes" and liab["C"] >= 3 else 0
+        names = _diagnostics_names(samplers[0].diagnostics_layout()[0], sets, fixed_names, intercept, randoms, nthr)
+        per_chain = []
+        for sc in samplers:
+            sc._diag_names = names
+            per_chain.append(sc.diagnostics())
+        if cv_fold is not None:   # the chains of folds=K see different data: nothing is pooled
+            res["diagnostics"] = dict(names=names, chains=per_chain, pooled=False)
+            for c, (d, f) in enumerate(zip(per_chain, folders)):
+                write_convergence_file(os.path.join(f, "convergence.txt"), names, d)
+        else:
+            pooled = pool_diagnostics(per_chain)
+            res["diagnostics"] = dict(names=names, chains=per_chain, worst=_worst(names, pooled), pooled=True, **pooled)
+            write_convergence_file(os.path.join(outFolder, "convergence.txt"), names, pooled)
     return res
 
 

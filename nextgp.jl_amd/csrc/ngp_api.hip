@@ -38,6 +38,7 @@
 #include "ngp_liability.h"
 #include "ngp_threshold.h"
 #include "ngp_genvar.h"
+#include "ngp_diag.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
 
@@ -457,6 +458,22 @@ struct GenVar {
     int64_t launches = 0, served = 0;       // ngp_get_genomic_variance_stats
 };
 
+// Convergence diagnostics of the kept draws (ngp_diag.h; DESIGN.md section 2, "Convergence diagnostics"): the window, the draws taken,
+// the gather table of the monitored vector (ngp_state.h, diag_layout) and the chain's streaming state on the device
+struct Diag {
+    bool on = false;
+    int L = 64;                    // lags 0 .. L-1
+    int64_t split = 0, n = 0;      // draws with index < split feed half 0; draws taken (host bookkeeping, rewound with h->iter)
+    int64_t D = 0, Dp = 0;         // monitored scalars; the row stride on the device (D rounded up to even); 0: nothing allocated
+    bool fixed = false;            // a draw was taken or a state was set: D may no longer change
+    std::vector<DiagSeg> segs;     // the table d_segs holds
+    int64_t maxw = 0;              // words of its longest run
+    DevArray<DiagSeg> d_segs;
+    size_t seg_cap = 0;            // entries d_segs was allocated for
+    DevArray<double> d_x, d_st;   // theta of the draw [Dp] (pad 0); x1 | S1[2] | S2[2] | C[L] | head[L] | ring[L], rows of Dp
+    int64_t launches = 0;          // ngp_get_diagnostics_stats
+};
+
 // Liability traits (ngp_liability.h; ngp_set_liability_classes / ngp_set_liability_bounds): the augmented rows with their classes
 // (C >= 2) or bounds (C == 0) on the host and on the device, the liability of each, and d_thr = thr[C+1] | sum_thr[C+1] |
 // sum_thr2[C+1] (thr[0] = -inf, thr[1] = 0, thr[C] = +inf; the sums are used at 2 .. C-1); all empty for a chain without them
@@ -485,6 +502,7 @@ struct Liab {
 // The chain's arrays on one panel (sized by its N, P and plan): allocated whole by alloc_panel, dropped whole with the panel
 struct ChainMem {
     GenVar gv;
+    Diag dg;
     Liab lb;
     DevArray<double> d_lhs0, d_rhs0, d_beta, d_c, d_w, d_q, d_T, d_chi;
     DevArray<int8_t> d_setof;
@@ -1297,6 +1315,7 @@ void launch_variance(ngp_handle *h, int active_set, uint64_t it) {
 // resume_mid: the head of this iteration (varE, intercept, fixed-effect sets) has run already -- its sweep ended at the census
 // with nothing changed and is launched again, k_prep first (it redraws the same keyed numbers and clears the hand-off counters)
 int sample_enqueue(ngp_handle *h);  // (below)
+void launch_diag(ngp_handle *h);    // (below)
 
 // T = inv(L) of every linear block from this iteration's coefficients (k_tinv; behind k_prep in the stream, in front of the sweep)
 void launch_tinv(ngp_handle *h) {  // (sync_linear_blocks has run for this call's active set)
@@ -1602,6 +1621,7 @@ int build_genvar(ngp_handle *h) {
 
 // The chain's variance arrays for the sets and windows it has now: built (zeroed) when either changed, zeroed again on request
 // (ngp_set_y).  Nothing to do while the pass is off.
+int ensure_diag(ngp_handle *h, bool zero);  // (below)
 int ensure_genvar(ngp_handle *h, bool zero) {
     GenVar &g = h->cm.gv;
     if (!g.on || !h->pm || h->records_only || h->sets.empty()) { g.built = false; return NGP_OK; }
@@ -1741,6 +1761,7 @@ int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true, bool g
         if (predict && predicts(h)) launch_predict(h, &h, 1);  // g = X_new beta of this draw, behind the posterior sums
         if (genvar && gv_active(h))                            // var(X beta) of this draw per window, set and in all
             if (int e = launch_genvar(h, &h, 1)) return e;
+        if (h->cm.dg.on && h->cm.dg.D > 0) launch_diag(h);     // the lag-window autocovariance of every monitored scalar takes this draw
         if (h->smp) return sample_enqueue(h);  // the kept sample goes to the file without stopping the chain (src/samplers.jl:56-104)
     }
     return NGP_OK;
@@ -1779,6 +1800,9 @@ int run_iterations(ngp_handle *h, int64_t niter, CuLease &lease, hipEvent_t *evs
                 if (gv_active(h))  // ... and so are the variance passes
                     for (int64_t r = itf; r <= h->iter; r++)
                         if (is_kept(h, r)) { h->cm.gv.launches -= 1; h->cm.gv.served -= 1; }
+                if (h->cm.dg.on && h->cm.dg.D > 0)  // ... and the diagnostics updates: their draw index goes back with the iteration
+                    for (int64_t r = itf; r <= h->iter; r++)
+                        if (is_kept(h, r)) { h->cm.dg.n -= 1; h->cm.dg.launches -= 1; }
                 h->iter = itf - 1;
                 n = h->iter - iter0;
                 resume_mid = true;
@@ -1968,6 +1992,74 @@ int64_t posterior_words(ngp_handle *h) {
     return (int64_t)(place(st, posterior_layout).bytes / 8);
 }
 
+// ---- convergence diagnostics (ngp_diag.h; DESIGN.md section 2, "Convergence diagnostics") ----
+// The gather table and the state for the model the chain has now: D and the order come from diag_layout; a word staged on the host
+// (DScal, DSet) is read where it lives on the device.  Allocated (zeroed) when D changed -- an error once draws are held --, zeroed
+// again on request (ngp_set_y).  Nothing to do while the diagnostics are off.
+int ensure_diag(ngp_handle *h, bool zero) {
+    Diag &g = h->cm.dg;
+    if (!g.on) return NGP_OK;
+    ChainState st;
+    describe(h, st);
+    const Plan pl = place(st, diag_layout);
+    const int64_t D = (int64_t)(pl.bytes / 8), Dp = (D + 1) / 2 * 2;
+    std::vector<DiagSeg> segs;
+    int64_t maxw = 0;
+    for (auto &a : pl.at) {
+        if (a.s->bytes == 0) continue;
+        const char *src = (const char *)a.s->p;
+        if (a.s->host) {
+            const char *sc0 = (const char *)&st.sc, *ds0 = (const char *)st.ds.data();
+            if (src >= sc0 && src < sc0 + sizeof(DScal)) src = (const char *)h->cm.d_scal.get() + (src - sc0);
+            else if (!st.ds.empty() && src >= ds0 && src < ds0 + st.ds.size() * sizeof(DSet)) src = (const char *)h->cm.d_sets.get() + (src - ds0);
+            else return fail(h, NGP_ERR_STATE, "internal: a monitored word lives on the host only");
+        }
+        segs.push_back(DiagSeg{(const double *)src, (long long)(a.off / 8), (long long)(a.s->bytes / 8)});
+        maxw = std::max<int64_t>(maxw, (int64_t)(a.s->bytes / 8));
+    }
+    const size_t rows = (size_t)DiagRows::rows(g.L);
+    if (zero) { g.n = 0; g.fixed = false; }
+    if (D != g.D) {
+        REQUIRE(!g.fixed, NGP_ERR_STATE, "the model changed while the convergence diagnostics hold draws (ngp_enable_diagnostics again)");
+        g.D = 0; g.Dp = 0; g.segs.clear();
+        int rc;
+        if ((rc = g.d_st.alloc(h, rows * (size_t)Dp)) || (rc = g.d_x.alloc(h, (size_t)Dp))) {
+            g.on = false; g.d_st.reset(); g.d_x.reset(); g.d_segs.reset(); g.seg_cap = 0;  // (the handle runs on without them)
+            (void)hipGetLastError();  // (... and its next run does not find the failed hipMalloc in the runtime's error word)
+            return rc;
+        }
+        g.D = D; g.Dp = Dp; g.n = 0;
+    } else if (zero && D > 0) {
+        HCHK(hipMemsetAsync(g.d_st, 0, rows * (size_t)Dp * sizeof(double), h->stream));
+    }
+    bool same = segs.size() == g.segs.size();
+    for (size_t i = 0; same && i < segs.size(); i++) same = segs[i].src == g.segs[i].src && segs[i].off == g.segs[i].off && segs[i].words == g.segs[i].words;
+    if (!same) {
+        if (segs.size() > g.seg_cap) {  // (a model of the same D in more runs: the table grows)
+            int rc;
+            HCHK(hipStreamSynchronize(h->stream));
+            if ((rc = g.d_segs.alloc(h, segs.size()))) { g.seg_cap = 0; g.segs.clear(); return rc; }
+            g.seg_cap = segs.size();
+        }
+        g.segs = segs; g.maxw = maxw;
+        HCHK(hipMemcpyAsync(g.d_segs, g.segs.data(), g.segs.size() * sizeof(DiagSeg), hipMemcpyHostToDevice, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));
+    }
+    return NGP_OK;
+}
+
+// the kept draw of the iteration just enqueued on h->stream: gather theta, then the update for draw index n
+void launch_diag(ngp_handle *h) {
+    Diag &g = h->cm.dg;
+    const unsigned *ab = (const unsigned *)h->cm.d_abort;
+    hipLaunchKernelGGL(k_diag_gather, dim3((unsigned)((g.maxw + 255) / 256), (unsigned)g.segs.size()), dim3(256), 0, h->stream, (const DiagSeg *)g.d_segs.get(),
+                       g.d_x.get(), ab);
+    const long long np = (long long)(g.Dp / 2);
+    hipLaunchKernelGGL(k_diag_update, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, (const double2 *)g.d_x.get(), (double2 *)g.d_st.get(), np, g.L,
+                       (long long)g.n, (long long)g.split, ab);
+    g.n += 1; g.launches += 1; g.fixed = true;
+}
+
 // ---- sample stream (ngp_set_sample_file) ----
 void sample_writer_loop(SampleStream *S) {
     (void)hipSetDevice(S->device);
@@ -2014,6 +2106,7 @@ int sample_enqueue(ngp_handle *h) {
         for (int i = 0; i < SampleStream::NSLOT; i++) {
             if (S->d_slot[i].alloc_raw(S->rec_bytes) != hipSuccess || S->h_slot[i].alloc_raw(S->rec_bytes) != hipSuccess)
                 return fail(h, NGP_ERR_NOMEM, "sample ring");
+            HCHK(hipMemsetAsync(S->d_slot[i], 0, S->rec_bytes, h->stream));  // (the record's pad bytes: the file does not depend on what the allocator hands out)
         }
         const int64_t hd[6] = {h->P, h->nvb, (int64_t)h->sets.size(), h->mm.nfixcol, h->nclass_total, (int64_t)S->rec_bytes};
         // (the header, by magic: ngp_state.h)
@@ -2824,6 +2917,7 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
     HCHK(hipMemsetAsync(h->cm.d_sum_delta, 0, (size_t)h->Ppad * sizeof(double), h->stream));
     if ((rc = ensure_prediction(h, true))) return rc;  // the prediction sums are zeroed wherever sum_beta is
     if ((rc = ensure_genvar(h, true))) return rc;      // ... and the genomic-variance sums
+    if ((rc = ensure_diag(h, true))) return rc;        // ... and the convergence diagnostics
     // a second chain on the same handle starts from the priors, with empty posterior sums (src/mme.jl:351-360, 516)
     if (h->nvb > 0) HCHK(hipMemsetAsync(h->mm.d_sum_varBeta, 0, (size_t)h->nvb * sizeof(double), h->stream));
     for (size_t si = 0; si < h->sets.size(); si++)
@@ -2939,6 +3033,7 @@ int prepare_run(ngp_handle *h, int64_t niter) {
     }
     h->ntrace = niter;
     if ((rc = ensure_genvar(h, false))) return rc;
+    if ((rc = ensure_diag(h, false))) return rc;
     return ensure_prediction(h, false);
 }
 
@@ -6077,6 +6172,150 @@ int32_t ngp_get_genomic_variance_stats(ngp_handle *h, int64_t *launches, int64_t
     if ((rc = enter(h))) return rc;
     if (launches) *launches = h->cm.gv.launches;
     if (chains_served) *chains_served = h->cm.gv.served;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ---- convergence diagnostics (ngp_diag.h; DESIGN.md section 2, "Convergence diagnostics") ---- */
+
+int32_t ngp_enable_diagnostics(ngp_handle *h, int32_t on, int32_t lags, int64_t split) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Diag &g = h->cm.dg;
+    if (!on) { HCHK(hipStreamSynchronize(h->stream)); h->cm.dg = Diag(); return NGP_OK; }
+    REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "convergence diagnostics need a model: a finished panel (ngp_set_panel_* / ngp_end_panel) or ngp_set_records");
+    REQUIRE(lags >= 2 && lags <= NGP_DIAG_MAXL && lags % 2 == 0, NGP_ERR_ARG, "convergence diagnostics: lags must be even, 2 .. 256");
+    REQUIRE(split >= 0, NGP_ERR_ARG, "convergence diagnostics: split must be >= 0");
+    HCHK(hipStreamSynchronize(h->stream));
+    const int64_t launches = g.launches;
+    h->cm.dg = Diag();
+    g.on = true; g.L = lags; g.split = split; g.launches = launches;
+    return ensure_diag(h, true);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_diagnostics_layout(ngp_handle *h, int64_t *D, int32_t *lags, int64_t *split, int64_t *n, int64_t *state_words) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->cm.dg.on, NGP_ERR_STATE, "no convergence diagnostics: ngp_enable_diagnostics is needed");
+    if ((rc = ensure_diag(h, false))) return rc;
+    const Diag &g = h->cm.dg;
+    if (D) *D = g.D;
+    if (lags) *lags = g.L;
+    if (split) *split = g.split;
+    if (n) *n = g.n;
+    if (state_words) *state_words = (int64_t)DiagRows::rows(g.L) * g.D;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_diagnostics(ngp_handle *h, double *mean, double *var, double *ess, double *mcse, double *truncated, double *half_n, double *half_mean,
+                            double *half_var, int64_t D, int64_t *n) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->cm.dg.on, NGP_ERR_STATE, "no convergence diagnostics: ngp_enable_diagnostics is needed");
+    if ((rc = ensure_diag(h, false))) return rc;
+    const Diag &g = h->cm.dg;
+    REQUIRE(D == g.D, NGP_ERR_ARG, "convergence diagnostics arrays hold D = " + std::to_string(g.D) + " entries");
+    if (n) *n = g.n;
+    if (g.n == 0) return NGP_OK;
+    DevArray<double> d_out;
+    if ((rc = d_out.alloc(h, (size_t)NGP_DIAG_OUT * (size_t)D))) return rc;
+    hipLaunchKernelGGL(k_diag_finalise, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream, (const double *)g.d_st.get(), (long long)g.Dp, (long long)D, g.L,
+                       (long long)g.n, (long long)g.split, d_out.get());
+    HCHK(hipStreamSynchronize(h->stream));
+    double *out[5] = {mean, var, ess, mcse, truncated};
+    for (int a = 0; a < 5; a++)
+        if (out[a]) HCHK(hipMemcpy(out[a], d_out.get() + (size_t)a * D, (size_t)D * sizeof(double), hipMemcpyDeviceToHost));
+    if (half_mean) HCHK(hipMemcpy(half_mean, d_out.get() + (size_t)5 * D, (size_t)2 * D * sizeof(double), hipMemcpyDeviceToHost));
+    if (half_var) HCHK(hipMemcpy(half_var, d_out.get() + (size_t)7 * D, (size_t)2 * D * sizeof(double), hipMemcpyDeviceToHost));
+    if (half_n) { half_n[0] = (double)std::min<int64_t>(g.n, g.split); half_n[1] = (double)(g.n - std::min<int64_t>(g.n, g.split)); }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_diagnostics_state(ngp_handle *h, double *state, int64_t words, int64_t *n) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->cm.dg.on, NGP_ERR_STATE, "no convergence diagnostics: ngp_enable_diagnostics is needed");
+    if ((rc = ensure_diag(h, false))) return rc;
+    const Diag &g = h->cm.dg;
+    const int64_t rows = (int64_t)DiagRows::rows(g.L);
+    REQUIRE(state && words == rows * g.D, NGP_ERR_ARG, "convergence diagnostics state holds (3 lags + 5) D = " + std::to_string(rows * g.D) + " words");
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy2D(state, (size_t)g.D * 8, g.d_st.get(), (size_t)g.Dp * 8, (size_t)g.D * 8, (size_t)rows, hipMemcpyDeviceToHost));
+    if (n) *n = g.n;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_set_diagnostics_state(ngp_handle *h, const double *state, int64_t words, int64_t n) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->cm.dg.on, NGP_ERR_STATE, "no convergence diagnostics: ngp_enable_diagnostics is needed");
+    if ((rc = ensure_diag(h, false))) return rc;
+    Diag &g = h->cm.dg;
+    const int64_t rows = (int64_t)DiagRows::rows(g.L);
+    REQUIRE(state && words == rows * g.D, NGP_ERR_ARG, "convergence diagnostics state holds (3 lags + 5) D = " + std::to_string(rows * g.D) + " words");
+    REQUIRE(n >= 0, NGP_ERR_ARG, "convergence diagnostics: n must be >= 0");
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy2D(g.d_st.get(), (size_t)g.Dp * 8, state, (size_t)g.D * 8, (size_t)g.D * 8, (size_t)rows, hipMemcpyHostToDevice));
+    g.n = n; g.fixed = true;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* Timing hook of the diagnostics (tools/diag_time.py): device events around `reps` full-window updates (k_diag_gather + k_diag_update
+ * at draw indices >= lags, on a scratch copy of the chain's state -- the chain's own state and draw count stay what they are) and
+ * around `reps` launches of k_diag_finalise over the chain's state; milliseconds per launch.  The finalise leg needs a draw taken
+ * (0 otherwise). */
+int32_t ngp_debug_time_diagnostics(ngp_handle *h, int32_t reps, double *update_ms, double *finalise_ms) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->cm.dg.on, NGP_ERR_STATE, "no convergence diagnostics: ngp_enable_diagnostics is needed");
+    REQUIRE(reps >= 1 && reps <= 1000, NGP_ERR_ARG, "reps: 1 .. 1000");
+    if ((rc = ensure_diag(h, false))) return rc;
+    const Diag &g = h->cm.dg;
+    const size_t words = (size_t)DiagRows::rows(g.L) * (size_t)g.Dp;
+    DevArray<double> d_scr, d_out;
+    if ((rc = d_scr.alloc(h, words)) || (rc = d_out.alloc(h, (size_t)NGP_DIAG_OUT * (size_t)g.D))) { (void)hipGetLastError(); return rc; }
+    HCHK(hipMemcpyAsync(d_scr, g.d_st, words * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    const long long np = (long long)(g.Dp / 2), t0 = std::max<long long>((long long)g.n, (long long)g.L);
+    float ms = 0.f;
+    for (int leg = 0; leg < 2; leg++) {
+        if (leg == 1 && g.n == 0) { if (finalise_ms) *finalise_ms = 0.0; break; }
+        for (int r = -1; r < reps; r++) {  // (r = -1: a launch in front of the timed ones)
+            if (r == 0) HCHK(hipEventRecord(h->ev0, h->stream));
+            if (leg == 0) {
+                hipLaunchKernelGGL(k_diag_gather, dim3((unsigned)((g.maxw + 255) / 256), (unsigned)g.segs.size()), dim3(256), 0, h->stream,
+                                   (const DiagSeg *)g.d_segs.get(), g.d_x.get(), (const unsigned *)nullptr);
+                hipLaunchKernelGGL(k_diag_update, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, (const double2 *)g.d_x.get(), (double2 *)d_scr.get(), np,
+                                   g.L, t0 + r + 1, (long long)g.split, (const unsigned *)nullptr);
+            } else
+                hipLaunchKernelGGL(k_diag_finalise, dim3((unsigned)((g.D + 255) / 256)), dim3(256), 0, h->stream, (const double *)g.d_st.get(), (long long)g.Dp,
+                                   (long long)g.D, g.L, (long long)g.n, (long long)g.split, d_out.get());
+        }
+        HCHK(hipEventRecord(h->ev1, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));
+        HCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        if (leg == 0 && update_ms) *update_ms = (double)ms / reps;
+        if (leg == 1 && finalise_ms) *finalise_ms = (double)ms / reps;
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_get_diagnostics_stats(ngp_handle *h, int64_t *launches) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    if (launches) *launches = h->cm.dg.launches;
     return NGP_OK;
     NGP_CATCH(h)
 }

@@ -41,6 +41,11 @@
 //            per BayesRCpi set annotProb[A][ncol] | delta[P] (uint8) | per BayesRCpi set annotCat[ncol] (uint8, from 1) |
 //            "NGPSMP05": thr[nthr], the thresholds t_2 .. t_{C-1} of this draw (doubles, directly behind the bytes in front: not aligned)
 //
+//  Monitored vector of the convergence diagnostics (ngp_enable_diagnostics; ngp_diag.h) -- diag_layout, D doubles:
+//    the doubles of a sample record in record order: varE | b | b_fixed[nfix] | u of every random-effect set, then varU of every set |
+//    beta[P] | varBeta[nvb] | piHat[2] per marker set | class probabilities | per BayesLV set c[16], varZeta | "NGPSMP05": thr[nthr].
+//    Not monitored: iter, delta, annotCat (no doubles) and annotProb[A][ncol] of a BayesRCpi set.
+//
 //  Snapshot (ngp_save_snapshot / ngp_load_snapshot):
 //    char[8] "NGPSNAP2" | int64 N, P, nvb, nsets | snapshot_head_layout: int64 iter, nKept | uint64 seed, chain |
 //    model signature (ModelSig in ngp_api.hip): per marker set int64 {method, K + 16 tuple k + 256 (ncov + 32 est_mode) of a
@@ -140,6 +145,11 @@ inline const Layout *tail_of(const Layout &L) {
     return &L == &posterior_layout ? &liability_posterior_tail : &L == &snapshot_body_layout ? &liability_snapshot_tail
          : &L == &sample_layout ? &liability_sample_tail : nullptr;
 }
+
+// The monitored vector of the convergence diagnostics (ngp_diag.h): the doubles of a sample record in record order, without iter (not a
+// double) and the BayesRCpi annotProb block (A P words); the drawn thresholds end it as they end the record (a group without instances
+// places nothing, so the table needs no tail)
+inline const Layout diag_layout = {{SEG_VARE}, {SEG_B}, {SEG_FIX}, {SEG_U}, {SEG_VARU}, {SEG_BETA}, {SEG_VARBETA}, {SEG_PI}, {SEG_CLS}, {SEG_LV}, {SEG_THR_SMP}};
 
 // Ordered traits on the scale of the trait (ngp_threshold.h), a second tail behind the liabilities', built the same way.  Cowles'
 // threshold step (ngp_set_threshold_step, mode 1; described for such a chain only): SEG_THR_STEP = sigma (double) | tries | accepted

@@ -347,6 +347,63 @@ function genomic_variance_stats(h::Handle)    # variance passes this handle laun
     return (launches = Int(a[]), chains_served = Int(b[]))
 end
 
+# ---- convergence diagnostics of every kept draw (include/nextgp_hip.h, "convergence diagnostics") ----
+enable_diagnostics!(h::Handle; on::Bool=true, lags::Integer=64, split::Integer=0) =
+    check(h, ccall((:ngp_enable_diagnostics, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int64), h.ptr, on, lags, split))
+function diagnostics_layout(h::Handle)        # monitored scalars, lags, split, draws taken, words of the state image
+    D = Ref{Int64}(0); L = Ref{Int32}(0); H = Ref{Int64}(0); n = Ref{Int64}(0); w = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_diagnostics_layout, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                   h.ptr, D, L, H, n, w))
+    return (D = Int(D[]), lags = Int(L[]), split = Int(H[]), n = Int(n[]), words = Int(w[]))
+end
+
+"""
+    getDiagnostics(h)
+
+Per monitored scalar (the doubles of a kept sample, in record order): `mean`, `var`, `sd`, `ess` (Geyer's initial positive sequence
+inside the lag window), `mcse = sqrt(var / ess)`, `truncated` (1: the positive sequence had not ended inside the window, the ESS is an
+upper bound), and per half of the run `half_n` (2), `half_mean`, `half_var` (D x 2): the sequences of a split-R-hat.
+"""
+function getDiagnostics(h::Handle)
+    D = diagnostics_layout(h).D
+    a = [fill(NaN, D) for _ in 1:5]; hn = zeros(2); hm = fill(NaN, D, 2); hv = fill(NaN, D, 2); n = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_diagnostics, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Int64}),
+                   h.ptr, a[1], a[2], a[3], a[4], a[5], hn, hm, hv, D, n))
+    return (n = Int(n[]), mean = a[1], var = a[2], sd = sqrt.(a[2]), ess = a[3], mcse = a[4], truncated = a[5], half_n = hn, half_mean = hm, half_var = hv)
+end
+function diagnostics_state(h::Handle)         # x1 | S1[2] | S2[2] | C[lags] | head[lags] | ring[lags], rows of D, and the draws taken
+    w = diagnostics_layout(h).words
+    st = Vector{Float64}(undef, w); n = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_diagnostics_state, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Int64}), h.ptr, st, w, n))
+    return (state = st, n = Int(n[]))
+end
+set_diagnostics_state!(h::Handle, state::Vector{Float64}, n::Integer) =
+    check(h, ccall((:ngp_set_diagnostics_state, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64), h.ptr, state, length(state), n))
+function diagnostics_stats(h::Handle)         # updates this handle launched
+    a = Ref{Int64}(0)
+    check(h, ccall((:ngp_get_diagnostics_stats, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), h.ptr, a))
+    return Int(a[])
+end
+
+"""
+    write_diagnostics(h, outPut)
+
+`convergence.txt` of `runSampler!(...; diagnostics = true)`, in the columns `runLMEM` of the host mirror writes: name mean sd mcse ess
+rhat truncated, one line per monitored scalar in record order.  The names are `theta:<i>` (the seam does not know the *Out headers) and
+rhat is NaN: a single chain is not pooled; its halves are in `getDiagnostics`.
+"""
+function write_diagnostics(h::Handle, outPut)
+    d = getDiagnostics(h)
+    open(outPut * "/convergence.txt", "w") do io
+        writedlm(io, ["name" "mean" "sd" "mcse" "ess" "rhat" "truncated"])
+        for i in 1:length(d.mean)
+            writedlm(io, Any["theta:$(i)" d.mean[i] d.sd[i] d.mcse[i] d.ess[i] NaN Int(d.truncated[i])])
+        end
+    end
+    return d
+end
+
 """
     write_genomic_variance(h, outPut, sets, ids, wins)
 
@@ -906,7 +963,7 @@ to the reference sampler.
 """
 function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta, chainLength, burnIn, outputFreq, outPut;
                      seed::Integer=1, device::Integer=0, windows::Dict=Dict(), windowThreshold::Float64=0.01, genomicVariance::Bool=false,
-                     holdout::Vector{Int}=Int[])
+                     holdout::Vector{Int}=Int[], diagnostics::Union{Bool,Integer}=false)
     all(z -> z isa Union{Symbol,Expr}, keys(Z)) || error("correlated (Tuple) random effects: use the reference sampler (src/functions.jl:75-89, 100-110); the device draws the exact Gibbs conditional of the model, NOT the reference's lines (they leave Z_ID'Z_Dam u_Dam of the other levels in a level's right-hand side), so a run sent there would not be the reference's chain -- add_random_set_tuple! / sampleZ_tuple! are there for callers who want the exact one")
     (E.str == "I" || E.str == "D") || error("residual structure $(E.str): only \"I\" and \"D\" exist (src/mme.jl:63-79)")
     any(s -> M[s].method == "BayesRCplus", keys(M)) && error("BayesRCplus: use the reference sampler (one step per annotation on the same column, src/functions.jl:362-419: not on the device)")
@@ -990,6 +1047,10 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         end
         enable_genomic_variance!(h; threshold = windowThreshold, trace_rows = max(0, div(chainLength - burnIn, outputFreq)))
     end
+    # convergence diagnostics (diagnostics = true: a window of 64 lags, or the number of lags): switched on behind set_y!, the halves of
+    # the split part at the middle of the planned kept draws; convergence.txt is written after the run
+    dlags = diagnostics === true ? 64 : (diagnostics === false ? 0 : Int(diagnostics))
+    dlags > 0 && enable_diagnostics!(h; lags = dlags, split = div(max(0, div(chainLength - burnIn, outputFreq)), 2))
     # ONE call for the whole chain: the kept samples (these2Keep, src/samplers.jl:26) go to a binary file through a copy stream and
     # a writer thread of the library while the chain runs -- the device never stops for a sample
     smpfile = joinpath(outPut, "samples.ngp")
@@ -1034,6 +1095,7 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
         end
     end
     gvar && write_genomic_variance(h, outPut, sets, ids, gvwins)
+    dlags > 0 && write_diagnostics(h, outPut)
     if !isempty(holdout)                         # holdoutPredict.txt: record (1-based), y as given, posterior mean and SD of the fitted value
         yin = Vector{Float64}(ycorr); ho = getHoldout(h, nData)
         open(outPut * "/holdoutPredict.txt", "w") do io
