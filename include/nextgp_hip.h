@@ -97,6 +97,24 @@ int32_t ngp_panel_columns_f32(ngp_handle *h, int64_t col0, const float *M, int64
 /* ... and from one byte per genotype (codes 0..255; the tiles of ngp_set_panel_u8 bit for bit): the only form the compact storage
  * (ngp_set_storage) takes, and a quarter of the host footprint and PCIe transfer for the fp32 tiles. */
 int32_t ngp_panel_columns_u8(ngp_handle *h, int64_t col0, const uint8_t *G, int64_t ncol, int64_t ld, int32_t centre);
+/* ... and from the packed columns of a PLINK .bed file (SNP-major, magic 6c 1b 01; `packed` points behind the three magic bytes):
+ * ncol columns, stride >= ceil(n_file / 4) bytes apart, sample i of the file in bits 2 (i mod 4) .. 2 (i mod 4) + 1 of byte i / 4,
+ * two-bit values 0 = two copies of A1, 1 = missing, 2 = heterozygous, 3 = no copy of A1.  The stored genotype is the count of
+ * A1 (allele 1) or of A2 (allele 2).  rows: NULL (n_file == N, row i is sample i) or N host indices into the file's samples, any
+ * order, repeats allowed.  The columns cross PCIe packed and are decoded, gathered and tiled on the device (staging as above);
+ * the caller's buffer may end ceil(n_file / 4) bytes into its last column, and pad bits and pad bytes are never read as genotypes.
+ * missing: what a missing call among the selected rows becomes --
+ *   ERROR  the call fails (NGP_ERR_ARG, "column <j> holds <n> missing calls") before the tiles of that chunk are written;
+ *   MEAN   the column's mean over the observed calls, mu_obs: the stored mean is mu_obs and (centred) the tile value exactly 0.
+ *          fp32 storage only (byte tiles hold codes);
+ *   ROUND  the nearest code to mu_obs, (2 sum + n_obs) / (2 n_obs) in integers (ties up; 0 for a column without observed call):
+ *          tiles and stored mean are those of ngp_panel_columns_u8 on the imputed codes, bit for bit.
+ * counts: NULL or ncol x 4 int64, the numbers of 0, 1, 2 and missing among the N selected rows of every column. */
+#define NGP_BED_MISSING_ERROR 0
+#define NGP_BED_MISSING_MEAN  1
+#define NGP_BED_MISSING_ROUND 2
+int32_t ngp_panel_columns_bed(ngp_handle *h, int64_t col0, const uint8_t *packed, int64_t ncol, int64_t stride, int64_t n_file,
+                              const int64_t *rows, int32_t allele, int32_t missing, int32_t centre, int64_t *counts);
 int32_t ngp_end_panel(ngp_handle *h);
 /* Same panel from one byte per genotype (0/1/2 allele counts, or any value 0..255): a quarter of the fp32 host footprint and
  * of the PCIe transfer; centring and the fp32 conversion happen on the device and give bit for bit the tiles of
@@ -645,6 +663,11 @@ int32_t ngp_begin_prediction_panel(ngp_handle *h, int64_t Np);
 int32_t ngp_prediction_columns_f64(ngp_handle *h, int64_t col0, const double *M, int64_t ncol, int64_t ld, int32_t centre);
 int32_t ngp_prediction_columns_f32(ngp_handle *h, int64_t col0, const float *M, int64_t ncol, int64_t ld, int32_t centre);
 int32_t ngp_prediction_columns_u8(ngp_handle *h, int64_t col0, const uint8_t *G, int64_t ncol, int64_t ld, int32_t centre);
+/* Packed .bed columns of the candidates (arguments as ngp_panel_columns_bed, rows: NULL or Np indices).  What is subtracted is the
+ * training mean, as above.  A missing call takes the training mean (MEAN: the tile value is exactly 0; needs centre != 0) or the
+ * training mean rounded to a code, floor(mean + 0.5) in 0..2 (ROUND).  counts are over the prediction rows. */
+int32_t ngp_prediction_columns_bed(ngp_handle *h, int64_t col0, const uint8_t *packed, int64_t ncol, int64_t stride, int64_t n_file,
+                                   const int64_t *rows, int32_t allele, int32_t missing, int32_t centre, int64_t *counts);
 int32_t ngp_end_prediction_panel(ngp_handle *h);
 int32_t ngp_load_prediction_file(ngp_handle *h, const char *path, int32_t centre);
 int32_t ngp_get_prediction_layout(ngp_handle *h, int64_t *Np, int64_t *R, int64_t *S, int64_t *chunk_cols, int64_t *rows);

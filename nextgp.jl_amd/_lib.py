@@ -207,7 +207,10 @@ SYMBOLS = [
     "ngp_enable_class_probabilities", "ngp_get_class_probabilities", "ngp_set_class_probabilities", "ngp_debug_pnorm",
     "ngp_enable_diagnostics", "ngp_get_diagnostics_layout", "ngp_get_diagnostics", "ngp_get_diagnostics_state", "ngp_set_diagnostics_state",
     "ngp_get_diagnostics_stats", "ngp_debug_time_diagnostics",
+    "ngp_panel_columns_bed", "ngp_prediction_columns_bed",
 ]
+
+BED_MISSING = {"error": 0, "mean": 1, "round": 2}   # NGP_BED_MISSING_*
 
 THRESHOLD_STEPS = {"albert-chib": 0, "cowles": 1}
 
@@ -605,6 +608,30 @@ class Sampler:
         M, t, sfx, ld = _columns(M)
         f = getattr(self.L, "ngp_panel_columns_" + sfx)
         self._chk(f(self.h, C.c_int64(col0), _p(M, t), C.c_int64(M.shape[1]), C.c_int64(ld), C.c_int32(int(centre))))
+
+    def _columns_bed(self, f, col0, packed, n_file, rows, allele, missing, centre):
+        packed = np.asanyarray(packed)   # (a memmap stays a memmap: the library reads the file's pages, no copy)
+        if packed.dtype != np.uint8 or packed.ndim != 2 or not packed.flags.c_contiguous:
+            raise ValueError("packed .bed columns: a C-ordered uint8 array of (ncol, stride), one row per SNP")
+        if missing not in BED_MISSING:
+            raise ValueError(f"missing-call policy {missing!r}: one of 'error', 'mean', 'round'")
+        ncol, stride = packed.shape
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        counts = np.zeros((ncol, 4), dtype=np.int64)
+        self._chk(f(self.h, C.c_int64(col0), _p(packed, C.c_uint8), C.c_int64(ncol), C.c_int64(stride), C.c_int64(int(n_file)), _p(r, C.c_int64),
+                    C.c_int32(int(allele)), C.c_int32(BED_MISSING[missing]), C.c_int32(int(centre)), _p(counts, C.c_int64)))
+        return counts
+
+    def panel_columns_bed(self, col0, packed, n_file, rows=None, allele=1, missing="mean", centre=True):
+        """Packed PLINK .bed columns (read_plink()["bed"][a:b]: (ncol, stride) uint8, one row per SNP of n_file samples) into columns
+        col0 .. of the open panel, decoded on the device.  rows: the file's sample of every panel row (None: file order); allele: count
+        A1 or A2; missing: "error", "mean" (fp32 storage) or "round".  Returns the (ncol, 4) counts of 0, 1, 2 and missing calls."""
+        return self._columns_bed(self.L.ngp_panel_columns_bed, col0, packed, n_file, rows, allele, missing, centre)
+
+    def prediction_columns_bed(self, col0, packed, n_file, rows=None, allele=1, missing="mean", centre=True):
+        """The same into the open prediction panel: the training means are subtracted, and a missing call takes the training mean
+        ("mean") or the training mean rounded to a code ("round")."""
+        return self._columns_bed(self.L.ngp_prediction_columns_bed, col0, packed, n_file, rows, allele, missing, centre)
 
     def end_panel(self):
         self._chk(self.L.ngp_end_panel(self.h))

@@ -28,7 +28,8 @@ import numpy as np
 
 from ._lib import pedigree_a22, pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
-__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file", "write_variance_out_files", "write_gwas_files"]
+__all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file", "write_variance_out_files", "write_gwas_files",
+           "is_bed_file", "read_plink", "write_plink", "decode_bed"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -570,6 +571,9 @@ def read_genotypes(path):
         path = np.load(path, mmap_mode="r")
     elif isinstance(path, (str, os.PathLike)) and is_panel_file(path):
         return read_panel_file(path)
+    elif isinstance(path, (str, os.PathLike)) and is_bed_file(path):   # a PLINK fileset, file order, missing calls at the column mean
+        info = read_plink(path)
+        return decode_bed(info["bed"], info["n"])
     if isinstance(path, np.ndarray):
         if path.dtype == np.uint8:
             return np.asfortranarray(path)
@@ -615,6 +619,202 @@ def read_panel_file(path):
         else:
             raise ValueError(f"panel file with {bits} bits per genotype")
     return G
+
+
+# ----------------------------------------------------------------------------------------------
+# PLINK binary filesets (.bed / .bim / .fam): DESIGN.md section 2, "PLINK .bed panels"
+# ----------------------------------------------------------------------------------------------
+BED_POLICIES = ("error", "mean", "round")
+
+
+def _bed_path(path):
+    """x.bed for "x.bed" or the prefix "x"."""
+    p = os.fspath(path)
+    return p if p.endswith(".bed") else p + ".bed"
+
+
+def is_bed_file(path):
+    """True for a SNP-major PLINK .bed file (magic 6c 1b 01); the sample-major form (6c 1b 00) raises ValueError."""
+    if not isinstance(path, (str, os.PathLike)):
+        return False
+    try:
+        with open(path, "rb") as f:
+            magic = f.read(3)
+    except OSError:
+        return False
+    if magic == b"\x6c\x1b\x00":
+        raise ValueError(f"{path} is a sample-major .bed file (magic 6c 1b 00): only the SNP-major form (6c 1b 01) is read; convert it with PLINK")
+    return magic == b"\x6c\x1b\x01"
+
+
+def _read_table(path, ncol, what):
+    rows = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split()
+            if not t:
+                continue
+            if len(t) < ncol:
+                raise ValueError(f"{path}, line {ln}: {what} needs {ncol} columns")
+            rows.append(t)
+    return rows
+
+
+def read_plink(path):
+    """A PLINK binary fileset, `x.bed` or the prefix `x`, without decoding it: {"bed": np.memmap of the packed columns, (P, ceil(n/4))
+    uint8, one row per SNP; "n", "P"; "fid", "iid" (.fam); "chr", "snp", "pos", "a1", "a2" (.bim); "path"}."""
+    bed = _bed_path(path)
+    stem = bed[:-4]
+    for ext in (".bed", ".bim", ".fam"):
+        if not os.path.isfile(stem + ext):
+            raise ValueError(f"PLINK fileset {stem}: {stem + ext} is absent (a .bed needs its .bim and .fam)")
+    if not is_bed_file(bed):
+        raise ValueError(f"{bed} is not a PLINK .bed file (magic 6c 1b 01)")
+    fam = _read_table(stem + ".fam", 2, "a .fam line")
+    bim = _read_table(stem + ".bim", 6, "a .bim line")
+    n, P = len(fam), len(bim)
+    nb = (n + 3) // 4
+    size = os.path.getsize(bed)
+    if n < 1 or P < 1 or size != 3 + P * nb:
+        raise ValueError(f"{bed} holds {size} bytes; {P} SNPs (.bim) of {n} samples (.fam) need 3 + {P} x {nb} = {3 + P * nb}")
+    return dict(bed=np.memmap(bed, dtype=np.uint8, mode="r", offset=3, shape=(P, nb)), n=n, P=P, path=bed,
+                fid=[t[0] for t in fam], iid=[t[1] for t in fam], chr=[t[0] for t in bim], snp=[t[1] for t in bim],
+                pos=[int(float(t[3])) for t in bim], a1=[t[4] for t in bim], a2=[t[5] for t in bim])
+
+
+def write_plink(prefix, G, iid=None, snp=None, chr=None, missing=None):
+    """Writes prefix.bed / .bim / .fam from an N x P array of A1 counts 0/1/2; missing: an optional N x P boolean mask of missing calls.
+    iid, snp, chr default to 1..N, snp1..snpP and chromosome 1; alleles are written as A (A1) and B (A2).  Returns the .bed path."""
+    G = np.asarray(G)
+    if G.ndim != 2 or G.shape[0] < 1 or G.shape[1] < 1:
+        raise ValueError("write_plink: an N x P array of genotype codes")
+    N, P = G.shape
+    miss = np.zeros((N, P), dtype=bool) if missing is None else np.asarray(missing, dtype=bool)
+    if miss.shape != (N, P):
+        raise ValueError("write_plink: the missing mask has the shape of G")
+    if not np.all(np.isin(G[~miss], (0, 1, 2))):
+        raise ValueError("write_plink: genotype codes are the A1 counts 0, 1, 2")
+    code = np.array([3, 2, 0], dtype=np.uint8)[np.where(miss, 0, G).astype(np.int64)]   # A1 count -> two-bit value
+    code[miss] = 1
+    nb = (N + 3) // 4
+    pad = np.zeros((4 * nb, P), dtype=np.uint8)
+    pad[:N] = code
+    packed = (pad[0::4] | (pad[1::4] << 2) | (pad[2::4] << 4) | (pad[3::4] << 6)).T   # (P, nb)
+    iid = [str(i + 1) for i in range(N)] if iid is None else [str(a) for a in iid]
+    snp = [f"snp{j + 1}" for j in range(P)] if snp is None else [str(a) for a in snp]
+    chr = ["1"] * P if chr is None else [str(a) for a in chr]
+    if len(iid) != N or len(snp) != P or len(chr) != P:
+        raise ValueError("write_plink: one iid per row, one snp and chr per column")
+    stem = _bed_path(prefix)[:-4]
+    with open(stem + ".bed", "wb") as f:
+        f.write(b"\x6c\x1b\x01")
+        f.write(np.ascontiguousarray(packed).tobytes())
+    with open(stem + ".fam", "w") as f:
+        for a in iid:
+            f.write(f"{a} {a} 0 0 0 -9\n")
+    with open(stem + ".bim", "w") as f:
+        for j in range(P):
+            f.write(f"{chr[j]}\t{snp[j]}\t0\t{j + 1}\tA\tB\n")
+    return stem + ".bed"
+
+
+def bed_round_code(total, n_obs):
+    """The code a missing call takes under "round": the nearest code to the mean of the observed calls, ties up, in integers."""
+    total, n_obs = np.asarray(total, dtype=np.int64), np.asarray(n_obs, dtype=np.int64)
+    return np.where(n_obs > 0, (2 * total + n_obs) // np.maximum(2 * n_obs, 1), 0)
+
+
+def decode_bed(bed, n_file, rows=None, cols=None, allele=1, missing="mean", counts=False):
+    """Host decoder of packed .bed columns (read_plink()["bed"]): the (N, P) matrix of allele counts of the selected rows (file
+    samples, any order, repeats allowed; None: all) and columns, with the imputation rules of the device kernels (ngp_bed.h):
+    "error" refuses a missing call among the selected rows, "round" fills in (2 sum + n_obs) // (2 n_obs) of its column (uint8 result,
+    as under "error"), "mean" the mean of the observed calls (float64 result); a column without an observed call is all zero.
+    counts=True also returns the (P, 4) numbers of 0, 1, 2 and missing calls."""
+    if missing not in BED_POLICIES:
+        raise ValueError(f"missing-call policy {missing!r}: one of {BED_POLICIES}")
+    if allele not in (1, 2):
+        raise ValueError("allele: 1 (count A1) or 2 (count A2)")
+    bed = np.asarray(bed) if cols is None else np.asarray(bed)[cols]
+    n_file = int(n_file)
+    if bed.ndim != 2 or bed.dtype != np.uint8 or bed.shape[1] < (n_file + 3) // 4:
+        raise ValueError("decode_bed: a uint8 array of (P, stride >= ceil(n_file / 4)), one row per SNP")
+    idx = np.arange(n_file) if rows is None else np.asarray(rows, dtype=np.int64)
+    if idx.ndim != 1 or (len(idx) and (idx.min() < 0 or idx.max() >= n_file)):
+        raise ValueError(f"decode_bed: rows outside the file's {n_file} samples")
+    lut = np.array([2, 3, 1, 0] if allele == 1 else [0, 3, 1, 2], dtype=np.uint8)   # two-bit value -> count, 3 = missing
+    G = lut[(bed[:, idx >> 2] >> (2 * (idx & 3)).astype(np.uint8)) & 3].T             # (N, P)
+    miss = G == 3
+    cnt = np.stack([(G == v).sum(axis=0) for v in range(4)], axis=1).astype(np.int64)
+    total, n_obs = cnt[:, 1] + 2 * cnt[:, 2], cnt[:, 0] + cnt[:, 1] + cnt[:, 2]
+    if missing == "error":
+        if miss.any():
+            j = int(np.flatnonzero(cnt[:, 3])[0])
+            raise ValueError(f"column {j} holds {int(cnt[j, 3])} missing calls")
+        out = np.asfortranarray(G)
+    elif missing == "round":
+        out = np.asfortranarray(np.where(miss, bed_round_code(total, n_obs).astype(np.uint8)[None, :], G))
+    else:
+        mu = np.where(n_obs > 0, total / np.maximum(n_obs, 1), 0.0)
+        out = np.asfortranarray(np.where(miss, mu[None, :], G.astype(np.float64)))
+    return (out, cnt) if counts else out
+
+
+class _BedSource:
+    """A marker set that stays packed: the memmap of a .bed file's columns and the file samples of the panel's rows.  It has the
+    `shape` of the matrix it stands for; panel_columns_bed decodes it on the device, decode() on the host."""
+    ndim = 2
+
+    def __init__(self, info, rows, allele, missing):
+        self.info, self.rows, self.allele, self.missing = info, rows, int(allele), missing
+        self.shape = (info["n"] if rows is None else len(rows), info["P"])
+        self.dtype = np.dtype(np.float64 if missing == "mean" else np.uint8)
+        self.counts = None
+
+    def decode(self):
+        out, self.counts = decode_bed(self.info["bed"], self.info["n"], rows=self.rows, allele=self.allele, missing=self.missing, counts=True)
+        return out
+
+
+def _is_bed(M):
+    return isinstance(M, _BedSource)
+
+
+def _bed_rows(info, ids):
+    """The file sample of every record: ids matched, as strings, to the .fam IID (the first sample of an IID listed twice)."""
+    at = {}
+    for k, a in enumerate(info["iid"]):
+        at.setdefault(a, k)
+    rows = np.empty(len(ids), dtype=np.int64)
+    for i, a in enumerate(ids):
+        if a not in at:
+            raise ValueError(f"genoID: {a!r} (record {i + 1}) is not an IID of {info['path'][:-4]}.fam")
+        rows[i] = at[a]
+    return rows
+
+
+def snp_stats(info, counts):
+    """Per-SNP figures of a loaded .bed set from the (P, 4) counts: {"snp", "a1", "a2", "n0", "n1", "n2", "nMissing", "freq"}; freq is
+    the frequency of the counted allele among the observed calls (NaN without one)."""
+    c = np.asarray(counts, dtype=np.int64)
+    n_obs = c[:, 0] + c[:, 1] + c[:, 2]
+    freq = np.where(n_obs > 0, (c[:, 1] + 2 * c[:, 2]) / np.maximum(2 * n_obs, 1), np.nan)
+    return dict(snp=list(info["snp"]), a1=list(info["a1"]), a2=list(info["a2"]), n0=c[:, 0].copy(), n1=c[:, 1].copy(), n2=c[:, 2].copy(),
+                nMissing=c[:, 3].copy(), freq=freq)
+
+
+def write_snp_stats(path, st):
+    with open(path, "w") as f:
+        f.write("snp a1 a2 n0 n1 n2 nMissing freq\n")
+        for j in range(len(st["snp"])):
+            f.write(f"{st['snp'][j]} {st['a1'][j]} {st['a2'][j]} {int(st['n0'][j])} {int(st['n1'][j])} {int(st['n2'][j])} {int(st['nMissing'][j])} {float(st['freq'][j])!r}\n")
+
+
+def write_bim_map(path, info):
+    """The map file prep2RegionData reads (header snpID,snpOrder,chrID) from a fileset's .bim."""
+    with open(path, "w") as f:
+        f.write("snpID,snpOrder,chrID\n")
+        for j, (s, c) in enumerate(zip(info["snp"], info["chr"])):
+            f.write(f"{s},{j + 1},{c}\n")
 
 
 def prep2RegionData(outPutFolder, markerSet, mapFile, fixedRegSize):
@@ -918,7 +1118,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -1005,11 +1205,31 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     the middle of the planned kept draws); folds=K pools nothing -- its chains see different data -- and reports per chain only
     (convergence.txt under chain<c>/).  truncated = 1: the positive sequence had not ended inside the window, the ESS is an upper
     bound -- raise lags or thin more.  convergencyMCMC(param, summary=True, outFolder=...) returns a file's rows of it.
+    (14) PLINK binary filesets (ngp_panel_columns_bed; DESIGN.md section 2, "PLINK .bed panels"): SNP(M1, "geno.bed") -- recognised by
+    the file's magic -- sends the packed columns to the device as they are in the file; no host matrix of the panel is formed.
+    genoID names the data column whose values are matched, as strings, to the .fam IID: the fileset may hold more individuals than the
+    records, in any order, and an animal with several records is gathered several times (an ID absent from the .fam: ValueError;
+    genoID=None: file order, as many samples as records).  missingGeno says what a missing call becomes: "mean" (the default: the mean
+    of the column's observed calls, a centred 0), "round" (the nearest code to that mean; the default, and the only imputing policy,
+    with storage="u8") or "error".  alleleCount=1 counts A1 (the .bim's first allele), 2 counts A2.  Nothing is filtered: the numbers of
+    0, 1, 2 and missing calls and the allele frequency of every SNP go to outFolder/snpStats<set>.txt (snp a1 a2 n0 n1 n2 nMissing
+    freq) and res["sets"][name]["snpStats"].  A term without a map file takes its chromosomes from the .bim (map_<set>.txt is written
+    into outFolder and serves regions and windows=).  predict={name: "cand.bed"} loads candidates the same way (predict_ids defaults
+    to the .fam IIDs; the .bim must list the training set's SNPs; a missing call takes the training mean, or its rounded code).
+    GBLUP terms, singleStep genotypes and members of a correlated (Tuple) unit are decoded on the host (decode_bed) by the same rules.
 
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
     summaryStat = dict(summaryStat or {})
     diag_lags = _diagnostics_option(diagnostics)   # (checked before any device work)
+    if missingGeno is None:
+        missingGeno = "round" if storage in ("u8", 1) else "mean"
+    if missingGeno not in BED_POLICIES:
+        raise ValueError(f"missingGeno: one of {BED_POLICIES}, got {missingGeno!r}")
+    if missingGeno == "mean" and storage in ("u8", 1):
+        raise ValueError('missingGeno="mean" with storage="u8": byte tiles hold genotype codes, a column mean is none; use "round" (or "error")')
+    if alleleCount not in (1, 2):
+        raise ValueError("alleleCount: 1 (count A1) or 2 (count A2)")
     parsed = parse_formula(formula, random_effects=True, pedigree=True)
     lhs, intercept, snps = parsed
     has_ped = userPedData is not None and len(userPedData) > 0
@@ -1058,14 +1278,23 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     # prep: SNP branch (src/prepMatVec.jl:113-134); marker sets become consecutive column ranges of ONE panel.  A term whose prior is
     # Random("G", v) is GBLUP (:122-126): its genotypes go to the GRM builder, never into the panel
     gb_names = gblup_terms(snps, VCV, summaryStat)
-    mats_all = [read_genotypes(t.path) for t in snps]
+    geno_ids = None if genoID is None else [str(a) for a in np.asarray(userData[genoID]).tolist()]
+    mats_all = [_genotype_source(t.path, geno_ids, alleleCount, missingGeno) for t in snps]
+    tuple_names = {nm for key in VCV if isinstance(key, tuple) for nm in key}
+    bed_sets = {t.name: M for t, M in zip(snps, mats_all) if _is_bed(M)}   # (their counts are reported below)
+    for t, M in zip(snps, mats_all):
+        if _is_bed(M) and not t.map and t.name not in tuple_names and t.name not in gb_names:   # chromosomes from the .bim
+            t.map = os.path.join(outFolder, f"map_{t.name}.txt")
+            write_bim_map(t.map, M.info)
+    # only a plain marker set stays packed for the device: GBLUP genotypes and members of a correlated unit are decoded on the host
+    mats_all = [M.decode() if _is_bed(M) and (t.name in gb_names or t.name in tuple_names) else M for t, M in zip(snps, mats_all)]
     for M in mats_all:
         if M.shape[0] != len(y):
             raise ValueError("genotype rows must match the phenotype records (marker files are ordered as the data, runTime.jl:23)")
     gblup = {t.name: dict(M=M, prior=VCV[t.name]) for t, M in zip(snps, mats_all) if t.name in gb_names}
     mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
     snps = [t for t in snps if t.name not in gb_names]
-    pmats = _prediction_sources(predict, predict_ids, snps, mats, gb_names)   # (checked before any device work)
+    pmats = _prediction_sources(predict, predict_ids, snps, mats, gb_names, alleleCount, missingGeno, tuple_names)   # (checked before any device work)
     gv_windows = _variance_windows(windows, windowThreshold, genomicVariance, snps, mats, gb_names, VCV)   # (the same)
     if gv_windows is not None and w_res is not None:
         raise NotImplementedError("genomic variance with weighted residuals (Random(d, v)): the tiles hold row-scaled values whose variance is "
@@ -1075,7 +1304,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     if storage in ("u8", 1):  # codes stay codes: integer-valued float input is converted, anything else refused
         conv = []
         for M in mats:
-            if M.dtype != np.uint8:
+            if not _is_bed(M) and M.dtype != np.uint8:
                 if not (np.all(M == np.rint(M)) and M.min() >= 0 and M.max() <= 255):
                     raise ValueError('storage="u8" needs integer genotype codes in 0..255 in every SNP set')
                 M = np.asfortranarray(M.astype(np.uint8))
@@ -1083,14 +1312,14 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         mats = conv
         if pmats is not None:
             for i, M in enumerate(pmats):
-                if M.dtype != np.uint8:
+                if not _is_bed(M) and M.dtype != np.uint8:
                     if not (np.all(M == np.rint(M)) and M.min() >= 0 and M.max() <= 255):
                         raise ValueError('storage="u8" needs integer genotype codes in 0..255 in every prediction source')
                     pmats[i] = np.asfortranarray(M.astype(np.uint8))
-    if mats and not all(M.dtype == np.uint8 for M in mats):  # one byte per genotype only when every set comes that way
-        mats = [np.asarray(M, dtype=np.float64) for M in mats]
-    if pmats is not None and not all(M.dtype == np.uint8 for M in pmats):
-        pmats = [np.asarray(M, dtype=np.float64) for M in pmats]
+    if mats and not all(M.dtype == np.uint8 for M in mats if not _is_bed(M)):  # one byte per genotype only when every set comes that way
+        mats = [M if _is_bed(M) else np.asarray(M, dtype=np.float64) for M in mats]
+    if pmats is not None and not all(M.dtype == np.uint8 for M in pmats if not _is_bed(M)):
+        pmats = [M if _is_bed(M) else np.asarray(M, dtype=np.float64) for M in pmats]
     # Correlated marker sets: a VCV key that is a TUPLE of set names (src/mme.jl:448-489) joins those sets into one unit whose loci
     # draw their k effects together (src/functions.jl:140-154).  On the device the k columns of a locus sit side by side, from a
     # 64-column boundary on (ngp_add_marker_set_tuple): the panel is assembled accordingly, everything else in formula order.
@@ -1124,15 +1353,18 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     elif K > 1:  # the layout with which K chains share one fused sweep launch (fp32 tiles), or the device side by side
         # (compact storage: the fused kernel serves two or three chains; more run side by side on disjoint CU shares)
         smp.set_max_shards(smp.shards_for_pass(K) if (storage is None or K <= 3) else smp.shards_for_chains(K))
-    kinds = {np.asarray(pc).dtype == np.uint8 for pc in pieces if pc.shape[1]}
+    kinds = {np.asarray(pc).dtype == np.uint8 for pc in pieces if pc.shape[1] and not _is_bed(pc)}
+    has_bed = any(_is_bed(pc) for pc in pieces)   # (a packed piece goes up in its own call beside pieces of any other kind)
     if not snps:   # GBLUP terms only: records, no genotype panel (ngp_set_records)
         smp.set_records(len(y))
-    elif (storage is None and kinds == {False}) or kinds == {True}:
+    elif has_bed or (storage is None and kinds == {False}) or kinds == {True}:
         # the sets go to the device one after another (ngp_begin_panel / ngp_panel_columns_* / ngp_end_panel): no concatenated host copy
         smp.begin_panel(len(y), ncols)
         c0 = 0
         for pc in pieces:
-            if pc.shape[1] and np.any(pc):       # (padding columns stay the zero columns they are born as)
+            if _is_bed(pc):                      # packed .bed columns: decoded, gathered and imputed on the device
+                pc.counts = smp.panel_columns_bed(c0, pc.info["bed"], pc.info["n"], rows=pc.rows, allele=pc.allele, missing=pc.missing, centre=True)
+            elif pc.shape[1] and np.any(pc):     # (padding columns stay the zero columns they are born as)
                 smp.panel_columns(c0, pc, centre=True)  # centring: src/prepMatVec.jl:129
             c0 += pc.shape[1]
         smp.end_panel()
@@ -1142,7 +1374,9 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         smp.begin_prediction_panel(pmats[0].shape[0])
         c0 = 0
         for pc in ppieces:
-            if pc.shape[1] and np.any(pc):
+            if _is_bed(pc):
+                pc.counts = smp.prediction_columns_bed(c0, pc.info["bed"], pc.info["n"], rows=None, allele=pc.allele, missing=pc.missing, centre=True)
+            elif pc.shape[1] and np.any(pc):
                 smp.prediction_columns(c0, pc, centre=True)
             c0 += pc.shape[1]
         smp.end_prediction_panel()
@@ -1192,8 +1426,16 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         for f in folders:
             _out(f, "threshold", [f"t{c}" for c in range(2, liab["C"])])
     res = _run_model(samplers, folders, sets, fixed_names, intercept, nChain, nBurn, nThin, samples, randoms)
+    for nm, src in bed_sets.items():   # what the fileset held among the records: counted, never filtered
+        st = snp_stats(src.info, src.counts)
+        write_snp_stats(os.path.join(outFolder, f"snpStats{nm}.txt"), st)
+        if nm in res["sets"]:
+            res["sets"][nm]["snpStats"] = st
     if pmats is not None:
-        ids = [str(i + 1) for i in range(pmats[0].shape[0])] if predict_ids is None else [str(a) for a in predict_ids]
+        if predict_ids is not None:
+            ids = [str(a) for a in predict_ids]
+        else:   # a candidate fileset names its own individuals
+            ids = list(pmats[0].info["iid"]) if _is_bed(pmats[0]) else [str(i + 1) for i in range(pmats[0].shape[0])]
         sums = [sc.prediction_sums() for sc in samplers]
         names = [s["name"] for s in sets]
         for r, ps in zip(res.get("chains", []), sums):
@@ -1548,7 +1790,16 @@ def _panel_pieces(snps, mats, by_name, in_tuple):
     return units, pieces, ncols
 
 
-def _prediction_sources(predict, predict_ids, snps, mats, gb_names):
+def _genotype_source(path, ids, allele, missing):
+    """The genotypes of one SNP(...) term: a PLINK fileset stays packed (_BedSource; ids: the records' IIDs, or None for file order),
+    everything else is read into a host matrix (read_genotypes)."""
+    if isinstance(path, (str, os.PathLike)) and not str(path).endswith(".npy") and is_bed_file(path):
+        info = read_plink(path)
+        return _BedSource(info, None if ids is None else _bed_rows(info, ids), allele, missing)
+    return read_genotypes(path)
+
+
+def _prediction_sources(predict, predict_ids, snps, mats, gb_names, allele=1, missing="mean", tuple_names=()):
     """runLMEM(predict=...): the genotype matrices of the new individuals, one per marker-set term in the order of `snps`, or None
     without predict=.  Host checks only; a ValueError here comes before any device work."""
     if predict is None:
@@ -1563,14 +1814,23 @@ def _prediction_sources(predict, predict_ids, snps, mats, gb_names):
     want = [t.name for t in snps]
     if sorted(predict.keys()) != sorted(want):
         raise ValueError(f"predict needs exactly one source per SNP(...) term {want}, got {sorted(predict.keys())}")
-    pm = [read_genotypes(predict[nm]) for nm in want]
+    pm = [_genotype_source(predict[nm], None, allele, missing) for nm in want]
     for nm, M, T in zip(want, pm, mats):
+        if _is_bed(M) and _is_bed(T) and M.info["snp"] != T.info["snp"]:
+            raise ValueError(f"predict[{nm!r}]: the SNP IDs of {M.info['path'][:-4]}.bim differ from the training set's ({T.info['path'][:-4]}.bim)")
         if M.ndim != 2 or M.shape[1] != T.shape[1]:
             raise ValueError(f"predict[{nm!r}] holds {M.shape[1] if M.ndim == 2 else '?'} columns, the term {T.shape[1]}")
     if len({M.shape[0] for M in pm}) != 1 or pm[0].shape[0] < 1:
         raise ValueError(f"every prediction source needs the same individuals: rows {[M.shape[0] for M in pm]}")
     if predict_ids is not None and len(predict_ids) != pm[0].shape[0]:
         raise ValueError(f"predict_ids names {len(predict_ids)} individuals, the prediction sources hold {pm[0].shape[0]}")
+    for i, nm in enumerate(want):   # members of a correlated unit are interleaved on the host
+        if _is_bed(pm[i]) and nm in tuple_names:
+            src = pm[i]
+            pm[i] = src.decode()
+            if src.counts[:, 3].any():
+                raise NotImplementedError(f"predict[{nm!r}]: missing calls of candidates in a correlated (Tuple) unit -- the host decoder knows "
+                                          "the candidates' column means, not the training means a missing call takes; impute them first")
     return pm
 
 

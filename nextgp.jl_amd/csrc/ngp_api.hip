@@ -34,6 +34,7 @@
 #include "ngp_hybrid.h"
 #include "ngp_logvar.h"
 #include "ngp_predict.h"
+#include "ngp_bed.h"
 #include "ngp_holdout.h"
 #include "ngp_liability.h"
 #include "ngp_threshold.h"
@@ -5880,6 +5881,83 @@ int end_prediction(ngp_handle *h) {
     return ensure_prediction(h, false);
 }
 
+// ---- PLINK .bed columns (ngp_bed.h; DESIGN.md section 2, "PLINK .bed panels") ----
+// Packed SNP-major columns [col0, col0 + ncol) of the open training panel (pred == false) or of the open prediction panel: staged as
+// they are in the file in chunks of whole columns (256 MiB), counted, decoded, gathered by rows[] and tiled on the device.  Every
+// argument is checked here, before any launch: an index of rows[] outside the file never reaches a kernel.
+int bed_columns(ngp_handle *h, bool pred, int64_t col0, const uint8_t *packed, int64_t ncol, int64_t stride, int64_t n_file, const int64_t *rows,
+                int allele, int missing, int centre, int64_t *counts) {
+    int rc;
+    if ((rc = enter(h, pred))) return rc;
+    if (pred) REQUIRE(h->pred_open && h->pm && h->pm->pred, NGP_ERR_STATE, "ngp_prediction_columns_bed needs an open prediction panel (ngp_begin_prediction_panel)");
+    else REQUIRE(h->panel_open && h->pm, NGP_ERR_STATE, "ngp_panel_columns_bed needs an open panel (ngp_begin_panel)");
+    const int64_t N = pred ? h->pm->pred->Np : h->N;
+    const int R = pred ? (int)h->pm->pred->R : (int)h->plan.R, S = pred ? (int)h->pm->pred->S : (int)h->plan.S;
+    REQUIRE(packed != nullptr, NGP_ERR_ARG, "null pointer to the packed .bed columns");
+    REQUIRE(n_file >= 1 && n_file <= ((int64_t)1 << 40), NGP_ERR_ARG, ".bed columns: n_file must be at least 1");
+    const int64_t colbytes = (n_file + 3) / 4;
+    REQUIRE(stride >= colbytes, NGP_ERR_ARG, ".bed columns: stride " + std::to_string(stride) + " is smaller than ceil(n_file / 4) = " + std::to_string(colbytes));
+    REQUIRE(col0 >= 0 && ncol > 0 && col0 + ncol <= h->P, NGP_ERR_ARG, "column range outside the panel");
+    REQUIRE(rows != nullptr || n_file == N, NGP_ERR_ARG,
+            ".bed columns without a row map: the file holds " + std::to_string(n_file) + " samples, the panel " + std::to_string(N) + " rows");
+    if (rows)
+        for (int64_t i = 0; i < N; i++)
+            REQUIRE(rows[i] >= 0 && rows[i] < n_file, NGP_ERR_ARG,
+                    ".bed row map: rows[" + std::to_string(i) + "] = " + std::to_string(rows[i]) + " is outside the file's " + std::to_string(n_file) + " samples");
+    REQUIRE(allele == 1 || allele == 2, NGP_ERR_ARG, ".bed columns: allele must be 1 (count A1) or 2 (count A2)");
+    REQUIRE(missing == NGP_BED_MISSING_ERROR || missing == NGP_BED_MISSING_MEAN || missing == NGP_BED_MISSING_ROUND, NGP_ERR_ARG,
+            ".bed columns: unknown missing-call policy " + std::to_string(missing));
+    REQUIRE(!(missing == NGP_BED_MISSING_MEAN && h->req.storage == 1), NGP_ERR_ARG,
+            ".bed columns: NGP_BED_MISSING_MEAN needs fp32 storage (byte tiles hold genotype codes: NGP_BED_MISSING_ROUND)");
+    REQUIRE(!(pred && missing == NGP_BED_MISSING_MEAN && centre == 0), NGP_ERR_ARG,
+            ".bed prediction columns: NGP_BED_MISSING_MEAN writes the training mean, which needs centre != 0");
+    const int64_t L = (int64_t)R * S;
+    const unsigned lut = allele == 1 ? NGP_BED_LUT_A1 : NGP_BED_LUT_A2;
+    const int64_t cchunk = std::max<int64_t>(1, std::min<int64_t>(ncol, staging_bytes(h, (int64_t)256 << 20) / stride));
+    DevArray<uint8_t> d_g;
+    DevArray<long long> d_rows, d_cnt;
+    DevArray<double> d_vm;
+    if (d_g.alloc_raw((size_t)cchunk * (size_t)stride) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer");
+    if ((rc = d_cnt.alloc(h, (size_t)cchunk * 4)) || (rc = d_vm.alloc(h, (size_t)cchunk))) return rc;
+    if (rows) {  // the row map goes up once per call
+        if (d_rows.alloc_raw((size_t)N) != hipSuccess) return fail(h, NGP_ERR_NOMEM, ".bed row map");
+        HCHK(hipMemcpyAsync(d_rows, rows, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    }
+    const bool want_cnt = counts != nullptr || missing == NGP_BED_MISSING_ERROR;
+    std::vector<long long> cnt(want_cnt ? (size_t)cchunk * 4 : 0);
+    for (int64_t c0 = 0; c0 < ncol; c0 += cchunk) {
+        const int64_t nc = std::min<int64_t>(cchunk, ncol - c0), j0 = col0 + c0;
+        // the last column may end ceil(n_file / 4) bytes in: nc - 1 full strides + one column's bytes
+        HCHK(hipMemcpyAsync(d_g, packed + (size_t)c0 * (size_t)stride, (size_t)(nc - 1) * (size_t)stride + (size_t)colbytes, hipMemcpyHostToDevice, h->stream));
+        double *d_mu = pred ? h->pm->pred->mean + j0 : h->pm->mean + j0;
+        const double *d_train = pred ? h->pm->mean + j0 : nullptr;
+        hipLaunchKernelGGL(k_bed_stats, dim3((unsigned)nc), dim3(256), 0, h->stream, (const uint8_t *)d_g, (long long)stride, (const long long *)d_rows.get(),
+                           (long long)N, lut, missing, centre, d_train, d_cnt.get(), d_mu, d_vm.get());
+        if (want_cnt) {
+            HCHK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)nc * 4 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+            HCHK(hipStreamSynchronize(h->stream));
+            if (counts)
+                for (int64_t k = 0; k < nc * 4; k++) counts[(size_t)c0 * 4 + (size_t)k] = (int64_t)cnt[(size_t)k];
+            if (missing == NGP_BED_MISSING_ERROR)
+                for (int64_t c = 0; c < nc; c++)
+                    REQUIRE(cnt[(size_t)c * 4 + 3] == 0, NGP_ERR_ARG,
+                            "column " + std::to_string(j0 + c) + " holds " + std::to_string(cnt[(size_t)c * 4 + 3]) + " missing calls");
+        }
+        if (h->req.storage == 1)
+            hipLaunchKernelGGL(k_bed_fill8, dim3((unsigned)((L / 16 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream,
+                               pred ? (uint8_t *)h->pm->pred->tiles.get() : (uint8_t *)h->pm->tiles.get(), (const uint8_t *)d_g, (long long)stride,
+                               (const long long *)d_rows.get(), (long long)N, lut, (long long)j0, R, S, (const double *)d_vm.get());
+        else  // residual weights never scale prediction rows
+            hipLaunchKernelGGL(k_bed_fill, dim3((unsigned)((L / 4 + 255) / 256), (unsigned)nc), dim3(256), 0, h->stream,
+                               pred ? h->pm->pred->tiles.get() : h->pm->tiles.get(), (const uint8_t *)d_g, (long long)stride, (const long long *)d_rows.get(),
+                               (long long)N, lut, (long long)j0, R, S, (const double *)d_mu, (const double *)d_vm.get(),
+                               pred ? (const double *)nullptr : (const double *)h->cm.d_rs);
+        HCHK(hipGetLastError());
+        HCHK(hipStreamSynchronize(h->stream));  // the staging buffer is reused by the next chunk
+    }
+    return NGP_OK;
+}
+
 // the chain's prediction arrays, checked against the caller's shape
 int prediction_shape(ngp_handle *h, int64_t rows, int64_t Np) {
     int rc;
@@ -5914,6 +5992,18 @@ int32_t ngp_prediction_columns_f32(ngp_handle *h, int64_t col0, const float *M, 
 int32_t ngp_prediction_columns_u8(ngp_handle *h, int64_t col0, const uint8_t *G, int64_t ncol, int64_t ld, int32_t centre) {
     NGP_TRY
     return prediction_columns<uint8_t>(h, col0, G, ncol, ld, centre);
+    NGP_CATCH(h)
+}
+int32_t ngp_panel_columns_bed(ngp_handle *h, int64_t col0, const uint8_t *packed, int64_t ncol, int64_t stride, int64_t n_file,
+                              const int64_t *rows, int32_t allele, int32_t missing, int32_t centre, int64_t *counts) {
+    NGP_TRY
+    return bed_columns(h, false, col0, packed, ncol, stride, n_file, rows, allele, missing, centre, counts);
+    NGP_CATCH(h)
+}
+int32_t ngp_prediction_columns_bed(ngp_handle *h, int64_t col0, const uint8_t *packed, int64_t ncol, int64_t stride, int64_t n_file,
+                                   const int64_t *rows, int32_t allele, int32_t missing, int32_t centre, int64_t *counts) {
+    NGP_TRY
+    return bed_columns(h, true, col0, packed, ncol, stride, n_file, rows, allele, missing, centre, counts);
     NGP_CATCH(h)
 }
 int32_t ngp_end_prediction_panel(ngp_handle *h) {

@@ -16,6 +16,7 @@
 module NextGPHIP
 
 using DelimitedFiles
+using Mmap
 
 const LIB = get(ENV, "NEXTGP_HIP_LIB", "libnextgp_hip")
 
@@ -56,6 +57,45 @@ panel_columns!(h::Handle, col0::Integer, data::Matrix{UInt8}; centre::Bool=true)
     check(h, ccall((:ngp_panel_columns_u8, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Int64, Int64, Int32),
                    h.ptr, col0, data, size(data, 2), stride(data, 2), centre))
 end_panel!(h::Handle) = check(h, ccall((:ngp_end_panel, LIB), Int32, (Ptr{Cvoid},), h.ptr))
+
+# ---- PLINK binary filesets (include/nextgp_hip.h, ngp_panel_columns_bed) ----
+# read_plink("x") or read_plink("x.bed"): the packed columns as an Mmap-backed ceil(n/4) x P Matrix{UInt8} (one column per SNP, as they
+# are in the file; nothing is decoded) plus the IDs of x.fam and x.bim.
+function read_plink(prefix::AbstractString)
+    stem = endswith(prefix, ".bed") ? prefix[1:end-4] : prefix
+    fam = [split(l) for l in eachline(stem * ".fam") if !isempty(strip(l))]
+    bim = [split(l) for l in eachline(stem * ".bim") if !isempty(strip(l))]
+    n = length(fam); P = length(bim); nb = cld(n, 4)
+    io = open(stem * ".bed", "r")
+    magic = read(io, 3)
+    magic == UInt8[0x6c, 0x1b, 0x00] && error("$stem.bed is sample-major (magic 6c 1b 00): only the SNP-major form is read")
+    magic == UInt8[0x6c, 0x1b, 0x01] || error("$stem.bed is not a PLINK .bed file (magic 6c 1b 01)")
+    filesize(stem * ".bed") == 3 + P * nb || error("$stem.bed: $P SNPs of $n samples need $(3 + P * nb) bytes")
+    bed = Mmap.mmap(io, Matrix{UInt8}, (nb, P), 3)
+    return (bed = bed, n = n, P = P, fid = [String(t[1]) for t in fam], iid = [String(t[2]) for t in fam],
+            chr = [String(t[1]) for t in bim], snp = [String(t[2]) for t in bim], a1 = [String(t[5]) for t in bim], a2 = [String(t[6]) for t in bim])
+end
+
+const BED_MISSING = Dict(:error => 0, :mean => 1, :round => 2)   # NGP_BED_MISSING_*
+
+# Packed columns into columns col0 .. (0-based) of the open panel, decoded on the device.  rows: the file's sample (1-based) of every
+# panel row, or nothing for file order; allele: count A1 or A2; missing: :error, :mean (fp32 tiles) or :round.  Returns the
+# 4 x ncol counts of 0, 1, 2 and missing calls.
+function panel_columns_bed!(h::Handle, col0::Integer, bed::Matrix{UInt8}, n_file::Integer; rows=nothing, allele::Integer=1, missing::Symbol=:mean, centre::Bool=true)
+    counts = zeros(Int64, 4, size(bed, 2))
+    r0 = rows === nothing ? C_NULL : Int64.(rows) .- 1
+    check(h, ccall((:ngp_panel_columns_bed, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Int64, Int64, Int64, Ptr{Int64}, Int32, Int32, Int32, Ptr{Int64}),
+                   h.ptr, col0, bed, size(bed, 2), stride(bed, 2), n_file, r0, allele, BED_MISSING[missing], centre, counts))
+    return counts
+end
+# ... and into the open prediction panel: a missing call takes the training mean (:mean) or its rounded code (:round)
+function prediction_columns_bed!(h::Handle, col0::Integer, bed::Matrix{UInt8}, n_file::Integer; rows=nothing, allele::Integer=1, missing::Symbol=:mean, centre::Bool=true)
+    counts = zeros(Int64, 4, size(bed, 2))
+    r0 = rows === nothing ? C_NULL : Int64.(rows) .- 1
+    check(h, ccall((:ngp_prediction_columns_bed, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt8}, Int64, Int64, Int64, Ptr{Int64}, Int32, Int32, Int32, Ptr{Int64}),
+                   h.ptr, col0, bed, size(bed, 2), stride(bed, 2), n_file, r0, allele, BED_MISSING[missing], centre, counts))
+    return counts
+end
 
 # one byte per genotype (raw allele counts, e.g. read from a binary file instead of src/prepMatVec.jl:116): centred on the device
 set_panel!(h::Handle, data::Matrix{UInt8}; centre::Bool=true) =
