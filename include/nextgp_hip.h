@@ -194,6 +194,18 @@ int32_t ngp_add_marker_set_tuple(ngp_handle *h, int64_t col0, int64_t nloc, int3
  * current effects and their posterior sums (all columns of all sets, in order); ngp_set_fixed restores them (resume). */
 int32_t ngp_add_fixed_set(ngp_handle *h, const double *X, int64_t N, int64_t ncol, int64_t ld, const double *lhs0, const double *rhs0,
                           int32_t *set_id);
+/* The same kind of set given as a sparse matrix: a classification factor of thousands of levels (herd, contemporary group), or a
+ * block of crossed factors and covariates.  CSC: col_ptr holds ncol + 1 offsets (col_ptr[0] = 0), row / val col_ptr[ncol] entries, the
+ * rows strictly ascending inside a column.  2 <= ncol <= 2^20 (the draw key is (set + 1) << 20 | column, as for the dense set),
+ * fewer than 2^31 entries, every column at least one, every value finite; else NGP_ERR_ARG and the handle is unchanged.  Single
+ * columns and the summary-statistics terms stay with ngp_add_fixed_set.  The set takes its place among the fixed-effect sets in the
+ * order added, dense and sparse mixed (16 in all), and appends its columns to what ngp_get_fixed / ngp_set_fixed, the packed
+ * posterior, sample records, snapshots and diagnostics carry.  It is bit for bit the dense set of the same design wherever both
+ * exist (a snapshot of one loads into the other): the stored entries are visited in the dense kernel's order and the partial sums
+ * combined along its tree ("Sparse fixed-effect sets").  Cost per iteration: one pass over the stored entries
+ * and over the stored entries of X'X, instead of N x ncol.  Under residual weights the values are scaled on the host (s_i val). */
+int32_t ngp_add_fixed_set_sparse(ngp_handle *h, int64_t N, int64_t ncol, const int64_t *col_ptr, const int32_t *row, const double *val,
+                                 int32_t *set_id);
 int32_t ngp_get_fixed(ngp_handle *h, double *b, double *sum_b, int64_t *ncols_total);
 int32_t ngp_set_fixed(ngp_handle *h, const double *b, const double *sum_b, int64_t ncols_total);
 

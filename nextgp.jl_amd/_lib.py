@@ -147,6 +147,50 @@ def k_csr(K):
     return kp, np.ascontiguousarray(cols, dtype=np.int32), np.ascontiguousarray(K[rows, cols], dtype=np.float64)
 
 
+def factors_csc(codes, covariates=None):
+    """Factors and covariates as one sparse design in CSC form: (N, ncol, col_ptr int64, row int32, val float64).  codes: a list of int
+    arrays, one per factor; code c >= 0 puts a 1.0 into column c of that factor, -1 is the base level (no column).  covariates: None,
+    an N vector or an N x k array, stored as full columns behind the factors.  Rows ascend inside every column.  No dense matrix is
+    built.  A level without a record (an empty column) is a ValueError."""
+    codes = [np.asarray(c, dtype=np.int64) for c in codes]
+    cov = None if covariates is None else np.asarray(covariates, dtype=np.float64)
+    if cov is not None and cov.ndim == 1:
+        cov = cov[:, None]
+    if not codes and cov is None:
+        raise ValueError("no factor and no covariate")
+    N = len(codes[0]) if codes else cov.shape[0]
+    counts, rows, vals = [], [], []
+    for f, c in enumerate(codes):
+        if c.ndim != 1 or len(c) != N or (len(c) and c.min() < -1):
+            raise ValueError(f"factor {f}: {N} codes, each -1 (base level) or a level 0, 1, ...")
+        q = int(c.max()) + 1 if len(c) else 0
+        keep = np.nonzero(c >= 0)[0]
+        order = keep[np.argsort(c[keep], kind="stable")]            # by level, records ascending inside a level
+        cnt = np.bincount(c[keep], minlength=q)
+        if np.any(cnt == 0):
+            raise ValueError(f"factor {f}: level {int(np.nonzero(cnt == 0)[0][0])} has no record")
+        counts.append(cnt); rows.append(order); vals.append(np.ones(len(order)))
+    if cov is not None:
+        if cov.shape[0] != N:
+            raise ValueError(f"covariates: {cov.shape[0]} rows for {N} records")
+        for j in range(cov.shape[1]):
+            counts.append(np.array([N])); rows.append(np.arange(N)); vals.append(cov[:, j])
+    cp = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
+    return (N, len(cp) - 1, cp, np.ascontiguousarray(np.concatenate(rows), dtype=np.int32),
+            np.ascontiguousarray(np.concatenate(vals), dtype=np.float64))
+
+
+def dense_csc(X):
+    """The nonzero entries of a dense N x ncol design in CSC form: (N, ncol, col_ptr, row, val) as factors_csc returns them."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X: an N x ncol matrix")
+    nz = (X != 0.0).T                                                # by columns, rows ascending
+    cols, rows = np.nonzero(nz)
+    cp = np.concatenate([[0], np.cumsum(nz.sum(axis=1))]).astype(np.int64)
+    return X.shape[0], X.shape[1], cp, np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(X[rows, cols], dtype=np.float64)
+
+
 def tuple_columns(col0, nloc, k):
     """Panel columns of a Tuple (correlated BayesPR) set: array [nloc, k], component m of locus l at col0 + 64 (l // Lb) + k (l % Lb) + m
     with Lb = 64 // k loci per 64-column block (include/nextgp_hip.h, ngp_add_marker_set_tuple)."""
@@ -183,7 +227,7 @@ SYMBOLS = [
     "ngp_get_trace", "ngp_get_posterior_sums", "ngp_posterior_len", "ngp_export_posterior_device", "ngp_sweep_set", "ngp_sweep_set_dev",
     "ngp_get_timing", "ngp_profile_iteration", "ngp_draws_indexed", "ngp_eval_math", "ngp_configure", "ngp_get_config", "ngp_debug_stamps", "ngp_set_near_lags", "ngp_get_near_lags",
     "ngp_set_streamer", "ngp_get_streamer", "ngp_set_storage", "ngp_get_storage", "ngp_set_max_shards", "ngp_shards_for_chains", "ngp_run_many", "ngp_write_panel_file", "ngp_read_panel_header", "ngp_load_panel_file", "ngp_debug_set_mode", "ngp_debug_set_knob", "ngp_set_posterior_sums", "ngp_save_snapshot", "ngp_load_snapshot",
-    "ngp_set_trace_loci", "ngp_get_trace_ext", "ngp_allreduce_posterior", "ngp_add_marker_set_r", "ngp_get_class_state", "ngp_set_class_state", "ngp_add_fixed_set", "ngp_get_fixed", "ngp_set_fixed", "ngp_debug_throw", "ngp_get_census", "ngp_debug_set_virtual_device", "ngp_debug_fail_census", "ngp_add_marker_set_tuple", "ngp_share_panel", "ngp_shards_for_pass", "ngp_set_sample_file",
+    "ngp_set_trace_loci", "ngp_get_trace_ext", "ngp_allreduce_posterior", "ngp_add_marker_set_r", "ngp_get_class_state", "ngp_set_class_state", "ngp_add_fixed_set", "ngp_add_fixed_set_sparse", "ngp_get_fixed", "ngp_set_fixed", "ngp_debug_throw", "ngp_get_census", "ngp_debug_set_virtual_device", "ngp_debug_fail_census", "ngp_add_marker_set_tuple", "ngp_share_panel", "ngp_shards_for_pass", "ngp_set_sample_file",
     "ngp_set_chain_form", "ngp_get_chain_form", "ngp_get_setup_timing", "ngp_set_residual_weights", "ngp_get_residual_weights",
     "ngp_add_random_set", "ngp_get_random", "ngp_set_random", "ngp_sample_random_set",
     "ngp_add_marker_set_lv", "ngp_get_lv_state", "ngp_set_lv_state",
@@ -871,6 +915,28 @@ class Sampler:
                                            _p(l0, C.c_double), _p(r0, C.c_double), C.byref(sid)))
         self.nfixcol = getattr(self, "nfixcol", 0) + X.shape[1]
         return sid.value
+
+    def add_fixed_set_sparse(self, N, ncol, col_ptr, row, val):
+        """A fixed-effect set as a sparse N x ncol matrix in CSC form (rows strictly ascending inside a column, every column at least
+        one entry, 2 <= ncol <= 2^20): a factor of many levels, or a block of crossed factors and covariates.  Bit for bit the dense
+        set of the same design (add_fixed_set) wherever both exist; returns the set id."""
+        cp = np.ascontiguousarray(col_ptr, dtype=np.int64)
+        rw = np.ascontiguousarray(row, dtype=np.int32)
+        vl = np.ascontiguousarray(val, dtype=np.float64)
+        if len(cp) != int(ncol) + 1 or len(rw) != len(vl) or (len(cp) and int(cp[-1]) != len(rw)):
+            raise ValueError("CSC arrays: col_ptr holds ncol + 1 offsets, row and val col_ptr[ncol] entries each")
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_fixed_set_sparse(self.h, C.c_int64(int(N)), C.c_int64(int(ncol)), _p(cp, C.c_int64), _p(rw, C.c_int32),
+                                                  _p(vl, C.c_double), C.byref(sid)))
+        self.nfixcol = getattr(self, "nfixcol", 0) + int(ncol)
+        return sid.value
+
+    def add_fixed_factors(self, codes, covariates=None):
+        """One sparse fixed-effect set from factors and covariates.  codes: a list of int arrays (one per factor, N entries each), level
+        codes 0, 1, ...; -1 is the base level, which gets no column.  covariates: None, or an N x k array (k columns, or one vector).
+        The columns are the factors in order, each with its levels ascending, then the covariates.  Returns the set id."""
+        N, ncol, cp, rw, vl = factors_csc(codes, covariates)
+        return self.add_fixed_set_sparse(N, ncol, cp, rw, vl)
 
     def get_fixed(self):
         n = getattr(self, "nfixcol", 0)

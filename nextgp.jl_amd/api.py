@@ -559,6 +559,49 @@ def design_columns(name, col):
     return X, [f"{name}: {lv}" for lv in levels[1:]]
 
 
+def design_codes(name, col):
+    """A factor term -> (codes, names) without a dense matrix: codes[i] is the column of record i among the term's dummy columns, -1 for
+    the base level (the first of the sorted levels); names and level order are design_columns'.  Float columns are covariates, not
+    factors: ValueError."""
+    col = np.asarray(col)
+    if col.dtype.kind == "f":
+        raise ValueError(f"{name} is a Float column (a covariate): design_columns centres it; only factors have level codes")
+    levels, inv = np.unique(col, return_inverse=True)
+    if len(levels) < 2:
+        raise ValueError(f"factor {name} has a single level")
+    return inv.astype(np.int64).ravel() - 1, [f"{name}: {lv}" for lv in levels.tolist()[1:]]
+
+
+def _fixed_unit_width(cols, userData):
+    """Number of design columns of a fixed unit (a term, or the terms of a blockThese group) without building them."""
+    n = 0
+    for c in cols:
+        col = np.asarray(userData[c])
+        n += 1 if col.dtype.kind == "f" else len(set(col.tolist())) - 1
+    return n
+
+
+def _add_fixed_unit_sparse(smp, cols, userData):
+    """One fixed unit as a sparse set (Sampler.add_fixed_set_sparse): the terms' columns in model order, a factor's dummy columns from its
+    level codes, a covariate's centred column in full.  Returns the column names."""
+    from ._lib import factors_csc
+    names, cps, rows, vals, N = [], [], [], [], None
+    for c in cols:
+        col = np.asarray(userData[c])
+        if col.dtype.kind == "f":
+            x = col.astype(np.float64)
+            n_, _, cp, rw, vl = factors_csc([], (x - x.mean())[:, None])
+            nm = [c]
+        else:
+            codes, nm = design_codes(c, col)
+            n_, _, cp, rw, vl = factors_csc([codes])
+        N = n_
+        cps.append(np.diff(cp)); rows.append(rw); vals.append(vl); names += nm
+    cp = np.concatenate([[0], np.cumsum(np.concatenate(cps))]).astype(np.int64)
+    smp.add_fixed_set_sparse(N, len(cp) - 1, cp, np.concatenate(rows), np.concatenate(vals))
+    return names
+
+
 # ----------------------------------------------------------------------------------------------
 # marker-matrix builders (src/prepMatVec.jl:113-134, src/misc.jl:163-215)
 # ----------------------------------------------------------------------------------------------
@@ -1118,7 +1161,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1, sparseFixed="auto"):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -1217,6 +1260,11 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     into outFolder and serves regions and windows=).  predict={name: "cand.bed"} loads candidates the same way (predict_ids defaults
     to the .fam IIDs; the .bim must list the training set's SNPs; a missing call takes the training mean, or its rounded code).
     GBLUP terms, singleStep genotypes and members of a correlated (Tuple) unit are decoded on the host (decode_bed) by the same rules.
+    (15) sparse fixed-effect sets (ngp_add_fixed_set_sparse; DESIGN.md section 2, "Sparse fixed-effect sets"): a fixed unit -- a term, or
+    a blockThese group -- whose design has more than 64 columns (a herd or contemporary-group factor) goes to the device as a sparse
+    matrix built from the level codes; no dense design is formed.  sparseFixed=True sends every unit of several columns that way,
+    False none (a unit wider than 64 columns is then refused by the library, as before).  The chain does not depend on the route: a
+    sparse set is bit for bit the dense set of the same design.  bOut headers and fixed_names keep their form ("herd: b").
 
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
@@ -1230,6 +1278,8 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         raise ValueError('missingGeno="mean" with storage="u8": byte tiles hold genotype codes, a column mean is none; use "round" (or "error")')
     if alleleCount not in (1, 2):
         raise ValueError("alleleCount: 1 (count A1) or 2 (count A2)")
+    if not (sparseFixed is True or sparseFixed is False or sparseFixed == "auto"):
+        raise ValueError(f'sparseFixed: "auto", True or False, got {sparseFixed!r}')
     parsed = parse_formula(formula, random_effects=True, pedigree=True)
     lhs, intercept, snps = parsed
     has_ped = userPedData is not None and len(userPedData) > 0
@@ -1406,7 +1456,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
             else:
                 sc.set_censored(liab["rows"], liab["lo"], liab["hi"])
     built = [_build_model(sc, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
-                          gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0], ped=ped)
+                          gblup=gblup, k_owner=None if sc is samplers[0] else samplers[0], ped=ped, sparseFixed=sparseFixed)
              for sc in samplers]
     sets, fixed_names = built[0]
     randoms = samplers[0].randoms
@@ -1913,7 +1963,7 @@ def _residual_weights(e_prior, N):
 
 
 def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept, units, snps, by_name, regions_of, y, nChain, nBurn, nThin,
-                 gblup=None, k_owner=None, ped=None):
+                 gblup=None, k_owner=None, ped=None, sparseFixed="auto"):
     """Priors, fixed-effect sets, random-effect sets, marker sets, y and the schedule of ONE chain's handle (its panel is set); returns
     (sets, fixed_names).  gblup: {term name: dict(M, prior)} of the GBLUP terms; k_owner: the chain whose dense K this one shares;
     ped: dict(table, Ainv) of makePed when the model has userPedData."""
@@ -1928,20 +1978,31 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
     # model order (the reference walks a Julia Dict, whose order is not defined: documented difference)
     covs = list(parsed.covariates)
     fixed_names = ["(Intercept)"] if intercept else []
-    designs = {c: design_columns(c, userData[c]) for c in covs}
+    # a unit goes to the device as a sparse set (ngp_add_fixed_set_sparse: the same chain, bit for bit) when it has more than 64 design
+    # columns (sparseFixed="auto"), or whenever it has several (True); never with False.  No dense design is built for such a unit.
+    def as_sparse(cols):
+        w = _fixed_unit_width(cols, userData)
+        return w >= 2 and (sparseFixed is True or (sparseFixed == "auto" and w > 64))
     used = set()
     for blk in (blockThese or []):
         blk = [c for c in covs if c in set(blk)]          # columns inside a block keep the model's order
         if not blk:
             continue
-        smp.add_fixed_set(np.column_stack([designs[c][0] for c in blk]))
-        for c in blk:
-            fixed_names += designs[c][1]
-            used.add(c)
+        if as_sparse(blk):
+            fixed_names += _add_fixed_unit_sparse(smp, blk, userData)
+        else:
+            designs = [design_columns(c, userData[c]) for c in blk]
+            smp.add_fixed_set(np.column_stack([d[0] for d in designs]))
+            for d in designs:
+                fixed_names += d[1]
+        used.update(blk)
     for c in covs:
         if c in used:
             continue
-        Xc, names = designs[c]
+        if as_sparse([c]):
+            fixed_names += _add_fixed_unit_sparse(smp, [c], userData)
+            continue
+        Xc, names = design_columns(c, userData[c])
         if c in summaryStat and Xc.shape[1] == 1:         # src/mme.jl:140-147
             m, vv = float(np.atleast_1d(summaryStat[c][0])[0]), float(np.atleast_1d(summaryStat[c][1])[0])
             smp.add_fixed_set(Xc, lhs0=[1.0 / vv], rhs0=[m / vv])

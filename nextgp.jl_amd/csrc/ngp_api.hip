@@ -29,6 +29,7 @@
 #include "../../include/nextgp_hip.h"
 #include "ngp_kernels.h"
 #include "ngp_random.h"
+#include "ngp_fixed_sparse.h"
 #include "ngp_random_tuple.h"
 #include "ngp_dense.h"
 #include "ngp_hybrid.h"
@@ -90,6 +91,16 @@ using File = std::unique_ptr<FILE, FileCloser>;  // a FILE * closed when it goes
 struct HFix {  // one fixed-effect set beyond the intercept
     int64_t ncol = 0, off = 0;
     DevArray<double> d_X, d_xpx0, d_xpxR, d_lhs0, d_rhs0;
+    // a set given as a sparse matrix (ngp_add_fixed_set_sparse; kernels in ngp_fixed_sparse.h) holds none of the above, but:
+    bool sparse = false;
+    DevArray<long long> d_cptr, d_rptr, d_xptr;  // X by columns (CSC) and by records (CSR); X'X by rows (CSR, columns ascending)
+    DevArray<int> d_crow, d_rcol, d_xcol;
+    DevArray<double> d_cval, d_rval, d_xval;     // (d_xval: the unridged X'X; the ridge changes its diagonal only)
+    DevArray<double> d_diagR, d_scr;             // the ridged diagonal; NGP_FS_ROWS x ncol scratch
+    struct Launch { int wide; int d0, d1; long long r0, r1; };  // wide: the columns order[r0 .. r1) of depth d0; else the depths d0 .. d1 - 1 in one workgroup
+    DevArray<int> d_order;                       // the columns by (depth, column)
+    DevArray<long long> d_dptr;
+    std::vector<Launch> plan;
 };
 
 // A dense q x q precision on the device (ngp_add_random_set_dense): row l at K + l ld.  Read-only once a set uses it; sets of several
@@ -1675,6 +1686,30 @@ int launch_genvar(ngp_handle *lead, ngp_handle **hs, int n) {
     return NGP_OK;
 }
 
+// one step of a sparse fixed-effect set (ngp_fixed_sparse.h): Yi of every column, the Gauss-Seidel depth by depth, the residual
+void launch_fixed_sparse(ngp_handle *h, int f, uint64_t it) {
+    const HFix &F = h->mm.fix[(size_t)f];
+    const long long nc = (long long)F.ncol;
+    const unsigned *ab = (const unsigned *)h->cm.d_abort;
+    const DScal *sc = (const DScal *)h->cm.d_scal;
+    double *b = h->mm.d_bfix + F.off;
+    const long long *xp = F.d_xptr;
+    const int *xc = F.d_xcol;
+    const double *xv = F.d_xval, *dg = F.d_diagR;
+    hipLaunchKernelGGL(k_fixs_yi, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, nc, (const long long *)F.d_cptr,
+                       (const int *)F.d_crow, (const double *)F.d_cval, xp, xc, xv, (const double *)b, F.d_scr.get(), sc, ab);
+    for (const HFix::Launch &pl : F.plan) {
+        if (pl.wide)
+            hipLaunchKernelGGL(k_fixs_gs_wide, dim3((unsigned)((pl.r1 - pl.r0 + 255) / 256)), dim3(256), 0, h->stream, nc, xp, xc, xv, dg, b, F.d_scr.get(),
+                               (const int *)F.d_order, pl.r0, pl.r1, sc, f, h->seed, (uint64_t)h->chain, it, ab);
+        else
+            hipLaunchKernelGGL(k_fixs_gs_fused, dim3(1), dim3(1024), 0, h->stream, nc, xp, xc, xv, dg, b, F.d_scr.get(), (const int *)F.d_order,
+                               (const long long *)F.d_dptr, pl.d0, pl.d1, sc, f, h->seed, (uint64_t)h->chain, it, ab);
+    }
+    hipLaunchKernelGGL(k_fixs_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr.get(), (long long)h->N, nc,
+                       (const long long *)F.d_rptr, (const int *)F.d_rcol, (const double *)F.d_rval, (const double *)F.d_scr.get(), ab);
+}
+
 void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // everything in front of the sweep
     const uint64_t it = (uint64_t)(h->iter + 1);
     if (!resume_mid) {
@@ -1704,7 +1739,8 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
                        h->e_scale, h->intercept, h->fix_varE > 0.0 ? 0 : 1, h->seed, (uint64_t)h->chain, it, h->hm.d_tr_varE, h->hm.d_tr_b, (long long)trace_idx, h->cm.d_abort, h->pm->mpm_max,
                        (const double *)h->cm.d_rs, h->sum_w);
     for (size_t f = 0; f < h->mm.fix.size(); f++)  // the other fixed-effect sets, in the order they were added (src/samplers.jl:39-41)
-        hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->N, h->mm.fix[f].d_X, (int)h->mm.fix[f].ncol, h->mm.fix[f].d_xpx0,
+        if (h->mm.fix[f].sparse) launch_fixed_sparse(h, (int)f, it);
+        else hipLaunchKernelGGL(k_fixed, dim3(1), dim3(1024), 0, h->stream, h->cm.d_ycorr, (long long)h->N, h->mm.fix[f].d_X, (int)h->mm.fix[f].ncol, h->mm.fix[f].d_xpx0,
                            h->mm.fix[f].d_xpxR, h->mm.fix[f].d_lhs0, h->mm.fix[f].d_rhs0, h->mm.d_bfix + h->mm.fix[f].off, h->cm.d_scal, (int)f, h->seed,
                            (uint64_t)h->chain, it, h->cm.d_abort);
     for (size_t r = 0; r < h->mm.rnd.size(); r++)  // the random-effect sets, in the order they were added (src/samplers.jl:43-46)
@@ -4471,6 +4507,102 @@ int upload(ngp_handle *h, DevArray<T> &d, const std::vector<T> &v) {
     if (!v.empty()) HCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return NGP_OK;
 }
+// Host set-up of a sparse fixed-effect set from its CSC arrays (rows strictly ascending inside a column; weights already applied):
+//   rptr/rcol/rval   X by records, per record its columns ascending
+//   xptr/xcol/xval   X'X by rows, columns ascending: entry (a, c) is fma-accumulated over the records in ascending order from 0.0 --
+//                    the bits of the dense set's x0 (a zero product is a no-op there)
+//   diagR            the ridged diagonal: X'X[a][a] + min_a |X'X[a][a]| / 10000 (src/mme.jl:149-152)
+//   order/dptr       the columns by (Gauss-Seidel depth, column): depth(a) = 1 + max depth(c) over the stored c < a of row a, else 0
+struct FixSparseHost {
+    std::vector<long long> rptr, xptr, dptr;
+    std::vector<int> rcol, xcol, order;
+    std::vector<double> rval, xval, diagR;
+};
+void fixed_sparse_host(int64_t N, int64_t ncol, const std::vector<long long> &cp, const std::vector<int> &cr, const std::vector<double> &cv,
+                       FixSparseHost &H) {
+    const size_t nnz = cr.size();
+    H.rptr.assign((size_t)N + 1, 0);
+    for (size_t k = 0; k < nnz; k++) H.rptr[(size_t)cr[k] + 1]++;
+    for (int64_t i = 0; i < N; i++) H.rptr[(size_t)i + 1] += H.rptr[(size_t)i];
+    H.rcol.resize(nnz); H.rval.resize(nnz);
+    {
+        std::vector<long long> pos(H.rptr.begin(), H.rptr.end() - 1);
+        for (int64_t a = 0; a < ncol; a++)  // columns in ascending order: every record's columns come out ascending
+            for (long long k = cp[(size_t)a]; k < cp[(size_t)a + 1]; k++) {
+                const long long p = pos[(size_t)cr[(size_t)k]]++;
+                H.rcol[(size_t)p] = (int)a; H.rval[(size_t)p] = cv[(size_t)k];
+            }
+    }
+    // the lower triangle row by row: row a's entries (a, c <= a) through a workspace over the columns
+    std::vector<double> w((size_t)ncol, 0.0);
+    std::vector<char> mark((size_t)ncol, 0);
+    std::vector<int> touched;
+    std::vector<long long> lptr((size_t)ncol + 1, 0);
+    std::vector<int> lcol;
+    std::vector<double> lval;
+    for (int64_t a = 0; a < ncol; a++) {
+        touched.clear();
+        for (long long k = cp[(size_t)a]; k < cp[(size_t)a + 1]; k++) {  // the records of column a, ascending
+            const int i = cr[(size_t)k];
+            const double xa = cv[(size_t)k];
+            for (long long p = H.rptr[(size_t)i]; p < H.rptr[(size_t)i + 1]; p++) {
+                const int c = H.rcol[(size_t)p];
+                if (c > a) break;
+                if (!mark[(size_t)c]) { mark[(size_t)c] = 1; touched.push_back(c); }
+                w[(size_t)c] = std::fma(xa, H.rval[(size_t)p], w[(size_t)c]);
+            }
+        }
+        std::sort(touched.begin(), touched.end());
+        for (int c : touched) {
+            lcol.push_back(c); lval.push_back(w[(size_t)c]);
+            w[(size_t)c] = 0.0; mark[(size_t)c] = 0;
+        }
+        lptr[(size_t)a + 1] = (long long)lcol.size();
+    }
+    // both triangles: row r = its lower entries and diagonal, then the mirrored (a, r) of the rows a > r in ascending a
+    H.xptr.assign((size_t)ncol + 1, 0);
+    for (int64_t a = 0; a < ncol; a++)
+        for (long long k = lptr[(size_t)a]; k < lptr[(size_t)a + 1]; k++) {
+            H.xptr[(size_t)a + 1]++;
+            if (lcol[(size_t)k] != a) H.xptr[(size_t)lcol[(size_t)k] + 1]++;
+        }
+    for (int64_t a = 0; a < ncol; a++) H.xptr[(size_t)a + 1] += H.xptr[(size_t)a];
+    H.xcol.resize((size_t)H.xptr[(size_t)ncol]); H.xval.resize((size_t)H.xptr[(size_t)ncol]);
+    {
+        std::vector<long long> pos(H.xptr.begin(), H.xptr.end() - 1);
+        for (int64_t a = 0; a < ncol; a++)
+            for (long long k = lptr[(size_t)a]; k < lptr[(size_t)a + 1]; k++) {
+                const long long p = pos[(size_t)a]++;
+                H.xcol[(size_t)p] = lcol[(size_t)k]; H.xval[(size_t)p] = lval[(size_t)k];
+            }
+        for (int64_t a = 0; a < ncol; a++)
+            for (long long k = lptr[(size_t)a]; k < lptr[(size_t)a + 1]; k++) {
+                const int c = lcol[(size_t)k];
+                if (c == a) continue;
+                const long long p = pos[(size_t)c]++;
+                H.xcol[(size_t)p] = (int)a; H.xval[(size_t)p] = lval[(size_t)k];
+            }
+    }
+    // ridge and depths (the diagonal is the last entry of a lower row: every column has an entry)
+    H.diagR.resize((size_t)ncol);
+    for (int64_t a = 0; a < ncol; a++) H.diagR[(size_t)a] = lval[(size_t)lptr[(size_t)a + 1] - 1];
+    double mn = std::fabs(H.diagR[0]);
+    for (int64_t a = 1; a < ncol; a++) mn = std::min(mn, std::fabs(H.diagR[(size_t)a]));
+    for (int64_t a = 0; a < ncol; a++) H.diagR[(size_t)a] += mn / 10000.0;
+    std::vector<int> dep((size_t)ncol, 0);
+    int maxd = 0;
+    for (int64_t a = 0; a < ncol; a++) {
+        int d = 0;
+        for (long long k = lptr[(size_t)a]; k < lptr[(size_t)a + 1] - 1; k++) d = std::max(d, dep[(size_t)lcol[(size_t)k]] + 1);
+        dep[(size_t)a] = d; maxd = std::max(maxd, d);
+    }
+    H.dptr.assign((size_t)maxd + 2, 0);
+    for (int64_t a = 0; a < ncol; a++) H.dptr[(size_t)dep[(size_t)a] + 1]++;
+    for (int d = 0; d <= maxd; d++) H.dptr[(size_t)d + 1] += H.dptr[(size_t)d];
+    H.order.resize((size_t)ncol);
+    std::vector<long long> pos(H.dptr.begin(), H.dptr.end() - 1);
+    for (int64_t a = 0; a < ncol; a++) H.order[(size_t)pos[(size_t)dep[(size_t)a]]++] = (int)a;
+}
 // digest of a dense K without bringing it to the host: k_dense_digest hashes every row on the device (one fixed order), the q row
 // words are folded here.  Done once per matrix; sets that share it share the word.
 int dense_digest(ngp_handle *h, const DenseK &dk, uint64_t *out) {
@@ -4698,6 +4830,67 @@ int add_random_csr(ngp_handle *h, const int32_t *level, int k, int64_t q, const 
 }  // namespace
 
 extern "C" {
+
+/* A fixed-effect set given as a sparse matrix: a factor of many levels, or a block of crossed factors and covariates (sampleb!,
+ * src/functions.jl:22-36; X'X + min|diag| / 10000, src/mme.jl:149-152).  CSC: col_ptr (ncol + 1), row (strictly ascending inside a
+ * column), val.  It takes its place among the fixed-effect sets in the order added and is, bit for bit, the dense set of the same
+ * design wherever both exist ("Sparse fixed-effect sets").  Every argument is checked before anything changes. */
+int32_t ngp_add_fixed_set_sparse(ngp_handle *h, int64_t N, int64_t ncol, const int64_t *col_ptr, const int32_t *row, const double *val,
+                                 int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open: x'x and the Gram window exist after ngp_end_panel");
+    REQUIRE(col_ptr && row && val && N == h->N && ncol >= 2 && ncol <= ((int64_t)1 << 20), NGP_ERR_ARG,
+            "sparse fixed-effect set: N rows, 2..2^20 columns (a single column is a dense set: ngp_add_fixed_set)");
+    REQUIRE(h->mm.fix.size() < 16, NGP_ERR_ARG, "at most 16 fixed-effect sets");
+    REQUIRE(col_ptr[0] == 0, NGP_ERR_ARG, "sparse fixed-effect set: col_ptr[0] must be 0");
+    for (int64_t a = 0; a < ncol; a++) {
+        REQUIRE(col_ptr[a + 1] > col_ptr[a], NGP_ERR_ARG, "sparse fixed-effect set: column " + std::to_string(a) + " has no entry (or col_ptr descends)");
+        REQUIRE(col_ptr[a + 1] < ((int64_t)1 << 31), NGP_ERR_ARG, "sparse fixed-effect set: 2^31 entries or more");
+    }
+    const int64_t nnz = col_ptr[ncol];
+    std::vector<long long> cp((size_t)ncol + 1);
+    std::vector<int> cr((size_t)nnz);
+    std::vector<double> cv((size_t)nnz);
+    for (int64_t a = 0; a <= ncol; a++) cp[(size_t)a] = (long long)col_ptr[a];
+    for (int64_t a = 0; a < ncol; a++)
+        for (int64_t k = col_ptr[a]; k < col_ptr[a + 1]; k++) {
+            const int64_t i = row[k];
+            REQUIRE(i >= 0 && i < N, NGP_ERR_ARG, "sparse fixed-effect set: row index outside 0 .. N - 1");
+            REQUIRE(k == col_ptr[a] || (int64_t)row[k - 1] < i, NGP_ERR_ARG, "sparse fixed-effect set: the rows of column " + std::to_string(a) + " are not strictly ascending");
+            REQUIRE(std::isfinite(val[k]), NGP_ERR_ARG, "non-finite value in a fixed-effect column");
+            cr[(size_t)k] = (int)i;
+            cv[(size_t)k] = h->h_rw.empty() ? val[k] : std::sqrt(h->h_rw[(size_t)i]) * val[k];  // weighted residuals: X~ = s X, the multiply of k_row_scale
+        }
+    HFix fx;
+    fx.sparse = true; fx.ncol = ncol; fx.off = h->mm.nfixcol;
+    FixSparseHost H;
+    fixed_sparse_host(N, ncol, cp, cr, cv, H);
+    int run0 = -1;  // the launches: a depth of more than NGP_FS_FUSE_ROWS columns on its own, a run of narrower depths in one workgroup
+    const int nd = (int)H.dptr.size() - 1;
+    for (int d = 0; d < nd; d++) {
+        if (H.dptr[(size_t)d + 1] - H.dptr[(size_t)d] > NGP_FS_FUSE_ROWS) {
+            if (run0 >= 0) fx.plan.push_back({0, run0, d, H.dptr[(size_t)run0], H.dptr[(size_t)d]});
+            run0 = -1;
+            fx.plan.push_back({1, d, d + 1, H.dptr[(size_t)d], H.dptr[(size_t)d + 1]});
+        } else if (run0 < 0) run0 = d;
+    }
+    if (run0 >= 0) fx.plan.push_back({0, run0, nd, H.dptr[(size_t)run0], H.dptr[(size_t)nd]});
+    if ((rc = upload(h, fx.d_cptr, cp)) || (rc = upload(h, fx.d_crow, cr)) || (rc = upload(h, fx.d_cval, cv))) return rc;
+    if ((rc = upload(h, fx.d_rptr, H.rptr)) || (rc = upload(h, fx.d_rcol, H.rcol)) || (rc = upload(h, fx.d_rval, H.rval))) return rc;
+    if ((rc = upload(h, fx.d_xptr, H.xptr)) || (rc = upload(h, fx.d_xcol, H.xcol)) || (rc = upload(h, fx.d_xval, H.xval))) return rc;
+    if ((rc = upload(h, fx.d_diagR, H.diagR)) || (rc = upload(h, fx.d_order, H.order)) || (rc = upload(h, fx.d_dptr, H.dptr))) return rc;
+    if ((rc = fx.d_scr.alloc(h, (size_t)NGP_FS_ROWS * (size_t)ncol))) return rc;
+    const int64_t nn = h->mm.nfixcol + ncol;
+    if ((rc = grow_pair(h, h->mm.d_bfix, h->mm.d_sum_bfix, h->mm.nfixcol, nn))) return rc;
+    h->mm.nfixcol = nn;
+    if (set_id) *set_id = (int32_t)h->mm.fix.size();
+    h->mm.fix.push_back(std::move(fx));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
 
 /* A (1|g) random-effect set (src/mme.jl:165-272; sampled by sampleZ!, src/functions.jl:57-72, 92-97, 498-501).  Every argument is
  * checked before anything changes: a refused call leaves the handle as it was. */

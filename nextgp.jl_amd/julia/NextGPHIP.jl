@@ -17,6 +17,7 @@ module NextGPHIP
 
 using DelimitedFiles
 using Mmap
+using SparseArrays
 
 const LIB = get(ENV, "NEXTGP_HIP_LIB", "libnextgp_hip")
 
@@ -723,6 +724,18 @@ function read_sample_file(path::AbstractString)
     return (sets = sets, samples = samples)
 end
 
+# A fixed-effect set given as a sparse matrix (ngp_add_fixed_set_sparse): a factor of thousands of levels, or a block of crossed
+# factors and covariates, N x ncol with 2 <= ncol <= 2^20.  A SparseMatrixCSC is the ABI's layout (rows ascending inside a column)
+# with 1-based offsets; stored zeros are dropped first.  Bit for bit the dense set of the same design wherever both exist.
+function add_fixed_set_sparse!(h::Handle, X::SparseMatrixCSC)
+    Xs = dropzeros(X)
+    cp = Int64.(Xs.colptr .- 1); rw = Int32.(Xs.rowval .- 1); vl = Float64.(Xs.nzval)
+    id = Ref{Int32}(0)
+    check(h, ccall((:ngp_add_fixed_set_sparse, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ref{Int32}),
+                   h.ptr, size(Xs, 1), size(Xs, 2), cp, rw, vl, id))
+    return id[]
+end
+
 # (1|g) random-effect set (ngp_add_random_set): level[i] in 0..q-1 per record, K = Z.iVarStr (any AbstractMatrix) sent as CSR
 function add_random_set!(h::Handle, level::Vector{Int32}, q::Integer, K, df::Float64, scale::Float64, varU0::Float64)
     kp = Vector{Int64}(undef, q + 1); kc = Int32[]; kv = Float64[]
@@ -1051,6 +1064,10 @@ function runSampler!(ycorr, nData, E, X, b, Z, u, varU, M, beta, varBeta, delta,
     xsets = collect(keys(X))
     for x in xsets
         Xd = Matrix{Float64}(reshape(X[x].data, :, X[x].nCol))
+        if X[x].nCol > 64   # wider than a dense set of the library: the same chain through the sparse entry point
+            add_fixed_set_sparse!(h, SparseArrays.sparse(Xd))
+            continue
+        end
         check(h, ccall((:ngp_add_fixed_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
                        h.ptr, Xd, size(Xd, 1), size(Xd, 2), size(Xd, 1), Float64.(X[x].lhs), Float64.(X[x].rhs), Ref{Int32}(0)))
     end
