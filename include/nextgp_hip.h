@@ -575,6 +575,38 @@ int32_t ngp_grm_invert(ngp_handle *h);
 int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q, const double *K, ngp_handle *k_src, int32_t k_src_set,
                                  double df, double scale, double varU0, int32_t *set_id);
 
+/* ---- SNP effects from GBLUP: every kept draw of the breeding values solved back to the markers ----
+ * A dense set whose K = inv(G) was built here (ngp_grm_begin .. ngp_grm_invert, K == NULL above, or k_src of such a set) knows how G was
+ * formed from the genotype columns Z: with w_t = K u_t,  beta_{j,t} = d_j sum_i (z_ij - mu_j) w_{i,t},  mu_j = 2 p_j,
+ * d_j = 1 / sum_k 2 p_k q_k (method 1) or 1 / (P 2 p_j q_j) (method 2): u_t = (G - 0.001 I) w_t = sum_j (z_j - mu_j) beta_{j,t}.  The
+ * 0.001 ridge of G is not solved back: it is the part of u that no SNP explains.  mu_j, p_j and the scale come from the same column
+ * statistics as the relationship matrix (csrc/ngp_grm_stats.h).  Everything runs on the device in fp64, the two products on the matrix
+ * cores (csrc/ngp_backsolve.h; DESIGN.md section 2, "SNP effects from GBLUP": the normative orders, the results are reproducible bit
+ * for bit run to run).
+ * ngp_backsolve_enable: before the run (NGP_ERR_STATE once the chain has iterated; ngp_set_y starts a new chain and empties the store);
+ *   allocates the draw store, q x max_draws doubles (1 <= max_draws <= 64 x 65535, else NGP_ERR_ARG), which lives as long as the set.  Every kept iteration then copies u into the next
+ *   column, on the chain's stream, where the posterior sums take u: a draw is stored iff it is kept.  A run that keeps more than max_draws
+ *   draws returns NGP_ERR_STATE at its end (the first max_draws are stored).  Under ngp_run_many every chain stores its own draws.
+ * ngp_backsolve_get_draws: the stored draws, q x T column-major, and T (either pointer may be NULL).
+ * ngp_backsolve_begin: after the run; forms W = K U and cw_t = sum_i w_{i,t}.  NGP_ERR_STATE without ngp_backsolve_enable or before any
+ *   kept draw.  On a set whose back-solve is open it starts again.
+ * ngp_backsolve_columns_*: the raw, uncentred genotype columns of the relationship matrix, in its column order, split into calls at any
+ *   boundaries (the input of ngp_grm_columns_*: column-major, ld >= q, host memory, staged in chunks); the handle counts them.
+ *   The staging buffers are allocated by the first call and kept until ngp_backsolve_end.
+ *   NGP_ERR_ARG: ld < q (the columns have another number of rows than the set has levels), more columns than G had, a non-finite value.
+ * ngp_backsolve_end: per SNP the sums over the T stored draws, sum[j] = sum_t beta_{j,t} and sumsq[j] = sum_t beta_{j,t}^2 (P doubles each),
+ *   n = T; mean and SD follow on the host and chains pool exactly by adding sums and n.  Releases W.  NGP_ERR_STATE unless exactly the
+ *   relationship matrix's P columns were handed over (the back-solve then stays open).
+ * Refused with NGP_ERR_ARG, the handle working on: a CSR, tuple or hybrid (single-step) set, and a dense set whose K the caller gave
+ * (its column weights are unknown). */
+int32_t ngp_backsolve_enable(ngp_handle *h, int32_t rset, int64_t max_draws);
+int32_t ngp_backsolve_get_draws(ngp_handle *h, int32_t rset, double *U_out, int64_t *T_out);
+int32_t ngp_backsolve_begin(ngp_handle *h, int32_t rset);
+int32_t ngp_backsolve_columns_f64(ngp_handle *h, const double *M, int64_t ncol, int64_t ld);
+int32_t ngp_backsolve_columns_f32(ngp_handle *h, const float *M, int64_t ncol, int64_t ld);
+int32_t ngp_backsolve_columns_u8(ngp_handle *h, const uint8_t *M, int64_t ncol, int64_t ld);
+int32_t ngp_backsolve_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, int64_t *n);
+
 /* ---- single-step GBLUP (Aguilar et al. 2010; Christensen & Lund 2010): one breeding value per animal of the pedigree, precision
  *        H^-1 = A^-1 + [ 0 0 ; 0  G_w^-1 - A22^-1 ],   G_w = (1 - w) G + w A22,   A22 = A over the genotyped animals ----
  * H^-1 is sparse except for one n_g x n_g corner, so neither engine above fits: ngp_add_random_set_hybrid walks ONE Gauss-Seidel sweep

@@ -233,6 +233,8 @@ SYMBOLS = [
     "ngp_add_marker_set_lv", "ngp_get_lv_state", "ngp_set_lv_state",
     "ngp_grm_begin", "ngp_grm_columns_f64", "ngp_grm_columns_f32", "ngp_grm_columns_u8", "ngp_grm_end", "ngp_grm_get", "ngp_grm_invert",
     "ngp_add_random_set_dense", "ngp_set_records",
+    "ngp_backsolve_enable", "ngp_backsolve_get_draws", "ngp_backsolve_begin", "ngp_backsolve_columns_f64", "ngp_backsolve_columns_f32",
+    "ngp_backsolve_columns_u8", "ngp_backsolve_end",
     "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
     "ngp_pedigree_a22", "ngp_grm_single_step", "ngp_add_random_set_hybrid",
     "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
@@ -259,6 +261,26 @@ BED_MISSING = {"error": 0, "mean": 1, "round": 2}   # NGP_BED_MISSING_*
 THRESHOLD_STEPS = {"albert-chib": 0, "cowles": 1}
 
 _lib = None
+
+
+def backsolve_summary(sum_, sumsq, n):
+    """SNP effects from their sums over n draws: {"sum", "sumsq", "n", "mean", "sd"} (sd: the draws' standard deviation, n - 1 below)."""
+    sum_, sumsq, n = np.asarray(sum_, dtype=np.float64), np.asarray(sumsq, dtype=np.float64), int(n)
+    mean = sum_ / max(n, 1)
+    var = np.maximum(sumsq - n * mean * mean, 0.0) / max(n - 1, 1)
+    return dict(sum=sum_, sumsq=sumsq, n=n, mean=mean, sd=np.sqrt(var))
+
+
+def pool_backsolve(parts):
+    """Chains' back-solved SNP effects (Sampler.backsolve) pooled exactly: the sums and the draw counts are added, in the order given."""
+    parts = list(parts)
+    if len({len(r["sum"]) for r in parts}) != 1:
+        raise ValueError("pool_backsolve: the parts hold different numbers of SNPs")
+    tot, tot2 = parts[0]["sum"].copy(), parts[0]["sumsq"].copy()
+    for r in parts[1:]:
+        tot = tot + r["sum"]
+        tot2 = tot2 + r["sumsq"]
+    return backsolve_summary(tot, tot2, sum(int(r["n"]) for r in parts))
 
 
 def prediction_summary(ps):
@@ -982,6 +1004,10 @@ class Sampler:
         self._chk(self.L.ngp_add_random_set_dense(self.h, _p(lv, C.c_int32), C.c_int64(int(q)), _p(Kh, C.c_double), src, C.c_int32(src_set),
                                                   C.c_double(df), C.c_double(scale), C.c_double(varU0), C.byref(sid)))
         self.rand_q = getattr(self, "rand_q", []) + [int(q)]
+        # how the set's matrix was built (backsolve(method=...) checks against it): this sampler's GRM, the owner's for a shared K
+        self.rand_grm_method = getattr(self, "rand_grm_method", {})
+        self.rand_grm_method[sid.value] = (K[0].rand_grm_method.get(int(K[1])) if isinstance(K, tuple) else
+                                           getattr(self, "grm_method", None) if K is None else None)
         return sid.value
 
     def add_random_set_hybrid(self, level, q, S, nd, D=None, df=4.0, scale=None, varU0=100.0):
@@ -1017,7 +1043,7 @@ class Sampler:
 
     def grm_begin(self, N, method=1):
         self._chk(self.L.ngp_grm_begin(self.h, C.c_int64(int(N)), C.c_int32(int(method))))
-        self.grm_N = int(N)
+        self.grm_N, self.grm_method = int(N), int(method)
 
     def grm_columns(self, M):
         """Raw (uncentred) genotype columns, N x ncol: uint8 and float32 are sent as they are, anything else as float64.  The first N
@@ -1052,6 +1078,49 @@ class Sampler:
         if A.shape != (self.grm_N, self.grm_N):
             raise ValueError("grm_single_step: A22 is N x N over the genotyped animals")
         self._chk(self.L.ngp_grm_single_step(self.h, _p(A, C.c_double), C.c_int64(self.grm_N), C.c_double(float(w))))
+
+    # ---- SNP effects from GBLUP (include/nextgp_hip.h, "SNP effects from GBLUP") ----------------
+    BACKSOLVE_COLUMNS_PER_CALL = 4096
+
+    def enable_backsolve(self, rset, max_draws):
+        """Before the run: every kept draw of the dense set rset (K built by grm_begin .. grm_invert) is stored on the device, max_draws at most."""
+        self._chk(self.L.ngp_backsolve_enable(self.h, C.c_int32(int(rset)), C.c_int64(int(max_draws))))
+
+    def backsolve_draws(self, rset):
+        """The stored draws of set rset, q x T (one column per kept draw, in the order kept)."""
+        T = C.c_int64()
+        self._chk(self.L.ngp_backsolve_get_draws(self.h, C.c_int32(int(rset)), None, C.byref(T)))
+        U = np.empty((self.rand_q[rset], T.value), order="F")
+        self._chk(self.L.ngp_backsolve_get_draws(self.h, C.c_int32(int(rset)), _p(U, C.c_double), C.byref(T)))
+        return U
+
+    def backsolve(self, rset, source, method=None, splits=None):
+        """After the run: SNP effects of every stored draw of set rset, summed over the draws on the device.  source: the genotypes the
+        relationship matrix was built from -- an N x P array (uint8 and float32 go as they are, anything else as float64) or whatever
+        read_genotypes reads (text, .npy, panel file, PLINK fileset).  They go over in column ranges (splits: the ranges' first columns
+        beyond 0; default every BACKSOLVE_COLUMNS_PER_CALL columns); the result does not depend on the split.  method: None, or the
+        GRM method (1 / 2) the caller takes the set's matrix to have been built with -- the handle solves back with the method it was
+        built with, another one here is a ValueError.  Returns {"sum", "sumsq", "n", "mean", "sd"}, P entries each (backsolve_summary;
+        pool_backsolve pools chains)."""
+        built = getattr(self, "rand_grm_method", {}).get(int(rset))
+        if method is not None and built is not None and int(method) != built:
+            raise ValueError(f"backsolve: method {method}, but the relationship matrix of set {rset} was built with method {built}")
+        if not isinstance(source, np.ndarray):
+            from .api import read_genotypes
+            source = read_genotypes(source)
+        M = np.asarray(source)
+        q = self.rand_q[rset]
+        if M.ndim != 2 or M.shape[0] != q:
+            raise ValueError(f"backsolve: an N x P genotype matrix with one row per level of the set (N = {q})")
+        P = M.shape[1]
+        cuts = [0] + (list(splits) if splits is not None else list(range(self.BACKSOLVE_COLUMNS_PER_CALL, P, self.BACKSOLVE_COLUMNS_PER_CALL))) + [P]
+        self._chk(self.L.ngp_backsolve_begin(self.h, C.c_int32(int(rset))))
+        for c0, c1 in zip(cuts[:-1], cuts[1:]):
+            A, t, sfx, ld = _columns(M[:, c0:c1])
+            self._chk(getattr(self.L, "ngp_backsolve_columns_" + sfx)(self.h, _p(A, t), C.c_int64(A.shape[1]), C.c_int64(ld)))
+        s1, s2, n = np.empty(P), np.empty(P), C.c_int64()
+        self._chk(self.L.ngp_backsolve_end(self.h, C.c_int32(int(rset)), _p(s1, C.c_double), _p(s2, C.c_double), C.byref(n)))
+        return backsolve_summary(s1, s2, n.value)
 
     def get_random(self, set_id):
         q = self.rand_q[set_id]

@@ -26,7 +26,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import pedigree_a22, pedigree_ainv, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
+from ._lib import pedigree_a22, pedigree_ainv, pool_backsolve, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
 __all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file", "write_variance_out_files", "write_gwas_files",
            "is_bed_file", "read_plink", "write_plink", "decode_bed"]
@@ -1161,7 +1161,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1, sparseFixed="auto"):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1, sparseFixed="auto", snpEffects=False):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -1265,6 +1265,13 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     matrix built from the level codes; no dense design is formed.  sparseFixed=True sends every unit of several columns that way,
     False none (a unit wider than 64 columns is then refused by the library, as before).  The chain does not depend on the route: a
     sparse set is bit for bit the dense set of the same design.  bOut headers and fixed_names keep their form ("herd: b").
+    (16) SNP effects from GBLUP (ngp_backsolve_*; DESIGN.md section 2, "SNP effects from GBLUP"): snpEffects=True, or a list of GBLUP term
+    names, stores every kept draw of the term's breeding values on the device and, after the run, hands the term's genotypes -- the
+    host array the relationship matrix was built from, kept since then; no file is read twice -- to the device once more, once per
+    chain, and solves each draw back to the markers: beta = d (Z - mu)' inv(G) u with the weights G was built with.  The 0.001 ridge of G
+    is not solved back.  res["random"][name]["snp"] = {"mean", "sd", "n"} and snpEffects<name>.txt (snp mean sd mean/sd; SNP names from
+    the .bim, else M1..MP) hold the result, pooled over the chains with chains=K.  A term that is not GBLUP raises NotImplementedError:
+    marker sets report their effects already (beta<set>Out, res["sets"][name], gwas<set>.txt); single-step ("H") terms are not covered.
 
     Returns a dict of posterior means taken from the on-device sums."""
     VCV = dict(VCV or {})
@@ -1342,6 +1349,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         if M.shape[0] != len(y):
             raise ValueError("genotype rows must match the phenotype records (marker files are ordered as the data, runTime.jl:23)")
     gblup = {t.name: dict(M=M, prior=VCV[t.name]) for t, M in zip(snps, mats_all) if t.name in gb_names}
+    snp_fx = _snp_effects_terms(snpEffects, gb_names, [t.name for t in snps], nChain, nBurn, nThin, folds)   # (checked before any device work)
     mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
     snps = [t for t in snps if t.name not in gb_names]
     pmats = _prediction_sources(predict, predict_ids, snps, mats, gb_names, alleleCount, missingGeno, tuple_names)   # (checked before any device work)
@@ -1460,6 +1468,9 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
              for sc in samplers]
     sets, fixed_names = built[0]
     randoms = samplers[0].randoms
+    for sc in samplers:   # behind set_y: the draw store of every back-solved term, one column per kept draw
+        for nm in snp_fx:
+            sc.enable_backsolve([rd["id"] for rd in sc.randoms if rd.get("key") == nm][0], (int(nChain) - int(nBurn)) // int(nThin))
     if gv_windows is not None:   # behind set_y: the pass is switched on with empty sums; one trace row per kept draw
         for sc in samplers:
             for st in sets:
@@ -1481,6 +1492,13 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         write_snp_stats(os.path.join(outFolder, f"snpStats{nm}.txt"), st)
         if nm in res["sets"]:
             res["sets"][nm]["snpStats"] = st
+    for nm in snp_fx:   # the term's genotypes once more, per chain; the chains' sums added
+        rid = [rd["id"] for rd in randoms if rd.get("key") == nm][0]
+        fx = pool_backsolve([sc.backsolve(rid, gblup[nm]["M"]) for sc in samplers])
+        P = len(fx["mean"])
+        names = list(bed_sets[nm].info["snp"]) if nm in bed_sets else [f"M{i + 1}" for i in range(P)]   # src/prepMatVec.jl:131
+        res.setdefault("random", {}).setdefault(nm, {})["snp"] = dict(mean=fx["mean"], sd=fx["sd"], n=fx["n"])
+        write_snp_effects_file(os.path.join(outFolder, f"snpEffects{nm}.txt"), names, fx["mean"], fx["sd"])
     if pmats is not None:
         if predict_ids is not None:
             ids = [str(a) for a in predict_ids]
@@ -1540,6 +1558,36 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
             res["diagnostics"] = dict(names=names, chains=per_chain, worst=_worst(names, pooled), pooled=True, **pooled)
             write_convergence_file(os.path.join(outFolder, "convergence.txt"), names, pooled)
     return res
+
+
+def _snp_effects_terms(snpEffects, gb_names, snp_names, nChain, nBurn, nThin, folds):
+    """runLMEM(snpEffects=...): the GBLUP terms whose draws are solved back to the markers.  Host checks only."""
+    if snpEffects is False or snpEffects is None:
+        return []
+    want = list(gb_names) if snpEffects is True else [str(a) for a in snpEffects]
+    for nm in want:
+        if nm not in gb_names:
+            raise NotImplementedError(f"snpEffects: {nm} is not a GBLUP term (a SNP(...) term with a Random(\"G\", v) prior)" +
+                                      ("; a marker set reports its SNP effects already: beta" + nm + "Out, res[\"sets\"][name] and, with windows=, gwas" + nm +
+                                       ".txt" if nm in snp_names else "; single-step (\"H\") terms are not back-solved"))
+    if not want:
+        raise NotImplementedError("snpEffects=True without a GBLUP term: marker sets report their SNP effects already (beta<set>Out, res[\"sets\"], "
+                                  "gwas<set>.txt with windows=)")
+    if folds is not None:
+        raise ValueError("snpEffects= with folds=: the fold-chains see different data, their SNP effects do not pool")
+    if (int(nChain) - int(nBurn)) // int(nThin) < 1:
+        raise ValueError("snpEffects: the schedule keeps no draw")
+    return want
+
+
+def write_snp_effects_file(path, names, mean, sd):
+    """snpEffects<set>.txt: snp, posterior mean, posterior SD, mean / SD (tab-separated, one row per SNP in genotype order)."""
+    with open(path, "w") as f:
+        f.write("snp\tmean\tsd\tmean/sd\n")
+        with np.errstate(all="ignore"):
+            z = np.where(sd > 0, mean / sd, np.nan)
+        for nm, m, d, r in zip(names, mean, sd, z):
+            f.write(f"{nm}\t{float(m)!r}\t{float(d)!r}\t{float(r)!r}\n")
 
 
 def _liability_spec(trait, censored, y, userData, VCV):

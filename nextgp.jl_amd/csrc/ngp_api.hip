@@ -41,6 +41,7 @@
 #include "ngp_threshold.h"
 #include "ngp_genvar.h"
 #include "ngp_diag.h"
+#include "ngp_backsolve.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
 
@@ -109,6 +110,10 @@ struct DenseK {
     DevArray<double> K;
     int64_t q = 0, ld = 0;
     uint64_t digest = 0;  // of all q x q entries (dense_digest, once, when a set first takes the matrix): the model signature of snapshots
+    // how ngp_grm_* built the matrix (method 0: the caller gave K): the column weights of the SNP back-solve (ngp_backsolve.h)
+    int grm_method = 0;
+    int64_t grm_ncols = 0;
+    double grm_sum2pq = 0.0;
 };
 
 // The genomic relationship matrix under construction (ngp_grm_begin .. ngp_grm_invert): column-major with leading dimension ld = N
@@ -152,6 +157,24 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     std::vector<Launch> plan;
     int64_t ndepth = 0;
     int sched_mode = 0;        // ngp_set_random_schedule: 0 automatic, 1 serial (k_rand_gs), 2 scheduled
+    // SNP back-solve of a dense set built by ngp_grm_* (ngp_backsolve.h): the draw store U (q x max_draws, column-major; lives as long as
+    // the set), kept draws seen so far (n > max_draws: the run ends with NGP_ERR_STATE); between ngp_backsolve_begin and _end W = K U
+    // (q x T), cw (T), the sums over the draws per SNP (grm_ncols each) and the columns handed over so far
+    struct Backsolve {
+        DevArray<double> U, W, cw, sum, sumsq;
+        int64_t max_draws = 0, n = 0, T = 0, cols = 0;
+        // the column pass's staging chunk (bytes of the input's type), mu_j / d_j of its columns and the two flag words: allocated by the
+        // first ngp_backsolve_columns_* call that needs them, grown if a later call needs more, released by ngp_backsolve_end
+        DevArray<unsigned char> stage;
+        DevArray<double> mu, dj;
+        DevArray<unsigned> bad;
+        size_t stage_bytes = 0;
+        int64_t stage_cols = 0;
+        void release_pass() {
+            W.reset(); cw.reset(); sum.reset(); sumsq.reset(); stage.reset(); mu.reset(); dj.reset(); bad.reset();
+            stage_bytes = 0; stage_cols = 0; T = 0; cols = 0;
+        }
+    } bs;
     bool scheduled() const { return sched_mode == 2 || (sched_mode == 0 && (hyb ? hd : q) > NGP_RS_AUTO_LEVELS_PER_DEPTH * ndepth); }
 };
 // q of a set as the sample file's header and the snapshot signature carry it: q, and k - 1 of a tuple set in the bits from 32 up
@@ -615,6 +638,7 @@ struct ngp_handle {
     HandleMem hm;
     bool records_only = false;  // ngp_set_records: N records and no genotype panel (one inert block of 64 zero columns stands in for it)
     Grm grm;                    // ngp_grm_*: independent of the panel and of the model
+    int bs_open = -1;           // the random-effect set between ngp_backsolve_begin and ngp_backsolve_end (-1: none)
     bool panel_open = false;  // between ngp_begin_panel and ngp_end_panel: columns may still arrive, the Gram window does not exist yet
     bool pred_open = false;   // between ngp_begin_prediction_panel and ngp_end_prediction_panel: only prediction columns may be called
     int cu_count = 256;
@@ -785,6 +809,7 @@ void drop_panel(ngp_handle *h) {
     h->h_regs.clear(); h->h_seg_k0.clear(); h->h_seg_len.clear(); h->h_seg_set.clear();
     h->h_tregs.clear(); h->h_tseg_l0.clear(); h->h_tseg_len.clear(); h->h_tseg_set.clear();
     h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false; h->records_only = false; h->pred_open = false;
+    h->bs_open = -1;
 }
 
 // A new panel of N x P (owner: ngp_share_panel's, whose arrays and plan are taken as they are).  The old panel goes first, so that
@@ -1754,6 +1779,17 @@ void iteration_pre(ngp_handle *h, int64_t trace_idx, bool resume_mid) {  // ever
     launch_tinv(h);
 }
 
+// a run that kept more draws than a set's draw store holds (ngp_backsolve_enable) ends with an error, not with draws silently dropped
+int backsolve_overflow(ngp_handle *h) {
+    for (size_t r = 0; r < h->mm.rnd.size(); r++) {
+        const HRand::Backsolve &b = h->mm.rnd[r].bs;
+        if (b.max_draws > 0 && b.n > b.max_draws)
+            return fail(h, NGP_ERR_STATE, "SNP back-solve of random-effect set " + std::to_string(r) + ": " + std::to_string(b.n) + " kept draws, the draw store holds " +
+                                              std::to_string(b.max_draws) + " (ngp_backsolve_enable); the first " + std::to_string(b.max_draws) + " are stored");
+    }
+    return NGP_OK;
+}
+
 // predict: this chain launches its own prediction pass in a kept iteration (false: the caller serves several chains with one launch)
 // genvar: the same for the genomic-variance pass
 int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true, bool genvar = true) {  // variance / pi draws, traces and posterior sums; advances h->iter
@@ -1778,6 +1814,13 @@ int iteration_post(ngp_handle *h, int64_t trace_idx, bool predict = true, bool g
             const long long qk = (long long)R.q * R.tk, kk = (long long)R.tk * R.tk;
             hipLaunchKernelGGL(k_accum_fixed, dim3((unsigned)((qk + 255) / 256)), dim3(256), 0, h->stream, qk, R.d_u, R.d_sum_u, h->cm.d_abort);
             hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, kk, R.d_vu, R.d_vu + kk, h->cm.d_abort);
+            if (R.bs.max_draws > 0) {  // the SNP back-solve's draw store takes u where the posterior sums take it: stored iff kept
+                if (R.bs.n < R.bs.max_draws) {  // (a launch that fails ends the run: the count and the stored columns never part)
+                    const hipError_t e = backsolve_store((long long)R.q, R.d_u, R.bs.U.get() + (size_t)R.bs.n * (size_t)R.q, h->cm.d_abort, h->stream);
+                    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("draw store of the SNP back-solve: ") + hipGetErrorString(e));
+                }
+                R.bs.n += 1;
+            }
         }
         for (auto &V : h->mm.lv)  // BayesLV sets: c and varZeta (src/samplers.jl:89-92)
             hipLaunchKernelGGL(k_accum_fixed, dim3(1), dim3(64), 0, h->stream, (long long)NGP_LV_SUM, V.d_st, V.d_st + NGP_LV_SUM, h->cm.d_abort);
@@ -1840,6 +1883,10 @@ int run_iterations(ngp_handle *h, int64_t niter, CuLease &lease, hipEvent_t *evs
                 if (h->cm.dg.on && h->cm.dg.D > 0)  // ... and the diagnostics updates: their draw index goes back with the iteration
                     for (int64_t r = itf; r <= h->iter; r++)
                         if (is_kept(h, r)) { h->cm.dg.n -= 1; h->cm.dg.launches -= 1; }
+                for (auto &R : h->mm.rnd)  // ... and the stores of the SNP back-solve: the draws go into their columns again
+                    if (R.bs.max_draws > 0)
+                        for (int64_t r = itf; r <= h->iter; r++)
+                            if (is_kept(h, r)) R.bs.n -= 1;
                 h->iter = itf - 1;
                 n = h->iter - iter0;
                 resume_mid = true;
@@ -2972,6 +3019,7 @@ int32_t ngp_set_y(ngp_handle *h, const double *y, int64_t N) {
         HCHK(hipMemcpyAsync(R.d_vu, vu.data(), vu.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HCHK(hipStreamSynchronize(h->stream));
         R.fine_calls = 0;
+        R.bs.n = 0;  // (the draw store of the SNP back-solve starts again with the chain)
     }
     for (auto &V : h->mm.lv) {  // BayesLV sets: zeta back to its start, c = 0, varZeta its prior value, empty sums (src/mme.jl:429-437)
         int rc2 = lv_reset(h, V);
@@ -3213,6 +3261,8 @@ int run_fused(ngp_handle **hs, int n, int64_t niter) {
     for (int i = 0; i < n; i++) { hs[i]->iter_ms += ms; hs[i]->iters_timed += niter; }
     for (int i = 0; i < n; i++)
         if ((rc = sample_flush(hs[i]))) { if (i) h->err = hs[i]->err; return rc; }
+    for (int i = 0; i < n; i++)
+        if ((rc = backsolve_overflow(hs[i]))) { if (i) h->err = hs[i]->err; return rc; }
     return NGP_OK;
 }
 }  // namespace
@@ -3234,7 +3284,7 @@ int32_t ngp_run(ngp_handle *h, int64_t niter) {
     h->iter_ms += ms; h->iters_timed += niter;
     if ((rc = sample_flush(h))) return rc;
     if (h->dbg_mode != 0) return fail(h, NGP_ERR_DEBUG, "diagnostic timing mode " + std::to_string(h->dbg_mode) + " is active: the chain is invalid (ngp_debug_set_mode(h, 0) ends it)");
-    return NGP_OK;
+    return backsolve_overflow(h);
     NGP_CATCH(h)
 }
 
@@ -5786,10 +5836,186 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
     HCHK(hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice));
     HCHK(hipStreamSynchronize(h->stream));
     dk->digest = kdig;
+    if (from_grm) { dk->grm_method = h->grm.method; dk->grm_ncols = h->grm.ncols; dk->grm_sum2pq = h->grm.sum2pq; }  // (the SNP back-solve's column weights)
     R.dk = std::move(dk);
     if (from_grm) h->grm = Grm();  // consumed: the set owns the matrix now
     if (set_id) *set_id = (int32_t)h->mm.rnd.size();
     h->mm.rnd.push_back(std::move(R));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ---- SNP effects from GBLUP: the kept draws of a dense set solved back to the markers (ngp_backsolve.h) ---- */
+}  // extern "C"
+
+namespace {
+// the set a back-solve call names: a dense set whose K this library built from genotype columns (their weights are then known)
+int backsolve_set(ngp_handle *h, int32_t rset, HRand **out) {
+    REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "panel (or records) not set");
+    REQUIRE(rset >= 0 && rset < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "SNP back-solve: no such random-effect set");
+    HRand &R = h->mm.rnd[(size_t)rset];
+    REQUIRE(R.dk && !R.hyb && R.tk == 1, NGP_ERR_ARG,
+            "SNP back-solve: the set is not a dense one (ngp_add_random_set_dense); CSR and hybrid (single-step) sets have no genotype columns behind all their levels");
+    REQUIRE(R.dk->grm_method != 0, NGP_ERR_ARG,
+            "SNP back-solve: the caller gave this set's K; the column weights are known only for a matrix built by ngp_grm_begin .. ngp_grm_invert");
+    *out = &R;
+    return NGP_OK;
+}
+
+template <typename TIn>
+int backsolve_columns_t(ngp_handle *h, int type, const TIn *M, int64_t ncol, int64_t ld) {
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->bs_open >= 0 && h->bs_open < (int)h->mm.rnd.size(), NGP_ERR_STATE, "ngp_backsolve_columns_* needs an open back-solve (ngp_backsolve_begin)");
+    HRand &R = h->mm.rnd[(size_t)h->bs_open];
+    HRand::Backsolve &B = R.bs;
+    const int64_t N = R.q, P = R.dk->grm_ncols;
+    REQUIRE(M != nullptr && ncol > 0, NGP_ERR_ARG, "genotype columns: a matrix of at least one column");
+    REQUIRE(ld >= N, NGP_ERR_ARG, "SNP back-solve: the genotype columns have fewer rows than the set has levels (leading dimension smaller than q)");
+    REQUIRE(B.cols + ncol <= P, NGP_ERR_ARG, "SNP back-solve: more columns than the relationship matrix was built from (" + std::to_string(P) + ")");
+    int64_t cchunk = std::min<int64_t>((ncol + 63) / 64 * 64, staging_bytes(h, (int64_t)256 << 20) / (int64_t)(ld * (int64_t)sizeof(TIn)));
+    cchunk = std::max<int64_t>(64, cchunk / 64 * 64);
+    // the buffers stay with the open back-solve: a caller that hands the columns over in many calls allocates once
+    const size_t need = (size_t)cchunk * (size_t)ld * sizeof(TIn);
+    if (B.stage_bytes < need) {
+        B.stage_bytes = 0;
+        if (B.stage.alloc_raw(need) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer of the SNP back-solve");
+        B.stage_bytes = need;
+    }
+    if (B.stage_cols < cchunk) {
+        B.stage_cols = 0;
+        if ((rc = B.mu.alloc(h, (size_t)cchunk)) || (rc = B.dj.alloc(h, (size_t)cchunk))) return rc;
+        B.stage_cols = cchunk;
+    }
+    if (!B.bad && (rc = B.bad.alloc(h, 2))) return rc;
+    TIn *d_g = (TIn *)B.stage.get();
+    double *d_mu = B.mu.get(), *d_dj = B.dj.get();
+    unsigned *d_bad = B.bad.get();
+    for (int64_t c0 = 0; c0 < ncol; c0 += cchunk) {
+        const int64_t nc = std::min<int64_t>(cchunk, ncol - c0);
+        const unsigned bad0[2] = {0u, 0xFFFFFFFFu};
+        unsigned bad[2] = {0u, 0u};
+        hipError_t e = hipMemcpyAsync(d_bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, h->stream);
+        // (the last column may be shorter than ld in the caller's buffer: nc - 1 full columns + N elements)
+        if (e == hipSuccess) e = hipMemcpyAsync(d_g, M + (size_t)c0 * (size_t)ld, ((size_t)(nc - 1) * (size_t)ld + (size_t)N) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            BsCols c;
+            c.type = type; c.method = R.dk->grm_method; c.src = d_g; c.N = N; c.ld = ld; c.nc = nc; c.P = P; c.sum2pq = R.dk->grm_sum2pq;
+            c.W = B.W.get(); c.cw = B.cw.get(); c.T = B.T; c.mu = d_mu; c.dj = d_dj; c.bad = d_bad;
+            c.sum = B.sum.get() + B.cols; c.sumsq = B.sumsq.get() + B.cols;
+            e = backsolve_columns(c, h->stream);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the staging buffer is reused by the next chunk
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("SNP back-solve columns: ") + hipGetErrorString(e));
+        // a refused chunk is not counted: the columns before it stay, the back-solve stays open
+        if (bad[0] != 0u) return fail(h, NGP_ERR_ARG, "non-finite genotype value in the columns of the SNP back-solve");
+        if (bad[1] != 0xFFFFFFFFu)
+            return fail(h, NGP_ERR_ARG, "SNP back-solve, method 2: column " + std::to_string(B.cols + (int64_t)bad[1] - 1) +
+                                            " (0-based, counted over all calls) is monomorphic: these are not the relationship matrix's columns");
+        B.cols += nc;
+    }
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t ngp_backsolve_enable(ngp_handle *h, int32_t rset, int64_t max_draws) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HRand *R = nullptr;
+    if ((rc = backsolve_set(h, rset, &R))) return rc;
+    // (k_bs_kw takes the draws in groups of 64 along the grid's second dimension, which ends at 65535)
+    REQUIRE(max_draws >= 1 && max_draws <= (int64_t)64 * 65535, NGP_ERR_ARG, "SNP back-solve: 1 <= max_draws <= 4,194,240 (64 x 65535)");
+    REQUIRE(h->iter == 0, NGP_ERR_STATE, "ngp_backsolve_enable comes before the run: this chain has run already (ngp_set_y starts a new one)");
+    REQUIRE(h->bs_open < 0, NGP_ERR_STATE, "a back-solve is open on this handle (ngp_backsolve_end)");
+    DevArray<double> U;
+    if (U.alloc_raw((size_t)R->q * (size_t)max_draws) != hipSuccess)
+        return fail(h, NGP_ERR_NOMEM, "draw store of the SNP back-solve: " + std::to_string(R->q) + " x " + std::to_string(max_draws) + " doubles");
+    R->bs.U = std::move(U);
+    R->bs.max_draws = max_draws; R->bs.n = 0;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_backsolve_get_draws(ngp_handle *h, int32_t rset, double *U_out, int64_t *T_out) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HRand *R = nullptr;
+    if ((rc = backsolve_set(h, rset, &R))) return rc;
+    REQUIRE(R->bs.max_draws > 0, NGP_ERR_STATE, "this set stores no draws (ngp_backsolve_enable)");
+    const int64_t T = std::min(R->bs.n, R->bs.max_draws);
+    HCHK(hipStreamSynchronize(h->stream));
+    if (U_out && T > 0) HCHK(hipMemcpy(U_out, R->bs.U, (size_t)R->q * (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_out) *T_out = T;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_backsolve_begin(ngp_handle *h, int32_t rset) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HRand *R = nullptr;
+    if ((rc = backsolve_set(h, rset, &R))) return rc;
+    HRand::Backsolve &B = R->bs;
+    REQUIRE(B.max_draws > 0, NGP_ERR_STATE, "this set stores no draws (ngp_backsolve_enable, before the run)");
+    REQUIRE(B.n >= 1, NGP_ERR_STATE, "ngp_backsolve_begin: no kept draw is stored yet (ngp_run past the burn-in)");
+    REQUIRE(h->bs_open < 0 || h->bs_open == rset, NGP_ERR_STATE, "a back-solve of another set is open on this handle (ngp_backsolve_end)");
+    // (begin on the open set starts it again: what an abandoned column pass left goes)
+    h->bs_open = -1;
+    B.release_pass();
+    const int64_t T = std::min(B.n, B.max_draws), P = R->dk->grm_ncols;
+    if (B.W.alloc_raw((size_t)R->q * (size_t)T) != hipSuccess || B.cw.alloc_raw((size_t)T) != hipSuccess)
+        return fail(h, NGP_ERR_NOMEM, "W = K U of the SNP back-solve: " + std::to_string(R->q) + " x " + std::to_string(T) + " doubles");
+    if ((rc = B.sum.alloc(h, (size_t)P)) || (rc = B.sumsq.alloc(h, (size_t)P))) return rc;
+    hipError_t e = backsolve_kw(R->dk->K.get(), (long long)R->dk->ld, (long long)R->q, B.U.get(), (long long)T, B.W.get(), B.cw.get(), h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("ngp_backsolve_begin: ") + hipGetErrorString(e));
+    B.T = T; B.cols = 0;
+    h->bs_open = rset;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_backsolve_columns_f64(ngp_handle *h, const double *M, int64_t ncol, int64_t ld) {
+    NGP_TRY
+    return backsolve_columns_t<double>(h, 0, M, ncol, ld);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_backsolve_columns_f32(ngp_handle *h, const float *M, int64_t ncol, int64_t ld) {
+    NGP_TRY
+    return backsolve_columns_t<float>(h, 1, M, ncol, ld);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_backsolve_columns_u8(ngp_handle *h, const uint8_t *M, int64_t ncol, int64_t ld) {
+    NGP_TRY
+    return backsolve_columns_t<uint8_t>(h, 2, M, ncol, ld);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_backsolve_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, int64_t *n) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HRand *R = nullptr;
+    if ((rc = backsolve_set(h, rset, &R))) return rc;
+    HRand::Backsolve &B = R->bs;
+    REQUIRE(h->bs_open == rset, NGP_ERR_STATE, "ngp_backsolve_end: no back-solve of this set is open (ngp_backsolve_begin)");
+    const int64_t P = R->dk->grm_ncols;
+    REQUIRE(B.cols == P, NGP_ERR_STATE, "ngp_backsolve_end: " + std::to_string(B.cols) + " genotype columns were handed over, the relationship matrix was built from " +
+                                            std::to_string(P) + " (hand over the rest, or start again with ngp_backsolve_begin)");
+    HCHK(hipStreamSynchronize(h->stream));
+    if (sum) HCHK(hipMemcpy(sum, B.sum, (size_t)P * sizeof(double), hipMemcpyDeviceToHost));
+    if (sumsq) HCHK(hipMemcpy(sumsq, B.sumsq, (size_t)P * sizeof(double), hipMemcpyDeviceToHost));
+    if (n) *n = B.T;
+    B.release_pass();
+    h->bs_open = -1;
     return NGP_OK;
     NGP_CATCH(h)
 }

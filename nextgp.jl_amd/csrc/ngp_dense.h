@@ -15,6 +15,7 @@
 #pragma once
 #include "ngp_kernels.h"
 #include "ngp_random.h"
+#include "ngp_grm_stats.h"
 
 #pragma clang fp contract(off)
 
@@ -188,19 +189,10 @@ __global__ __launch_bounds__(64) void k_grm_cols(const TIn *__restrict__ src, lo
         return;
     }
     const TIn *col = src + (size_t)c * (size_t)ld;
-    double acc = 0.0;
-    bool nf = false;
-    for (long long i = lane; i < N; i += 64) {
-        const double x = (double)col[i];
-        nf = nf || !isfinite(x);
-        acc = acc + x;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off);
+    double mean, tp;
+    bool nf;
+    grm_col_stats<TIn>(col, N, lane, mean, tp, nf);  // (ngp_grm_stats.h: the SNP back-solve weights its columns by the same text)
     if (nf) atomicOr(&bad[0], 1u);
-    const double mean = acc / (double)N;
-    const double p = mean / 2.0;
-    const double tp = (2.0 * p) * (1.0 - p);
     double sd = 1.0;
     if (method == 2) {
         if (!(tp > 0.0)) {

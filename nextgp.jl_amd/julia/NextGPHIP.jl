@@ -810,6 +810,30 @@ function grm_get(h::Handle, N::Integer)
     check(h, ccall((:ngp_grm_get, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, G))
     return G
 end
+# ---- SNP effects from GBLUP (include/nextgp_hip.h): the kept draws of a dense set whose K came from grm_invert! are stored on the device
+# (backsolve_enable! before run!) and solved back to the markers afterwards: backsolve_begin!, the genotype columns of the relationship
+# matrix once more in its column order (backsolve_columns!, any split into calls), backsolve_end! -> (sum, sumsq, n) per SNP over the draws.
+backsolve_enable!(h::Handle, rset::Integer, max_draws::Integer) =
+    check(h, ccall((:ngp_backsolve_enable, LIB), Int32, (Ptr{Cvoid}, Int32, Int64), h.ptr, rset, max_draws))
+backsolve_begin!(h::Handle, rset::Integer) = check(h, ccall((:ngp_backsolve_begin, LIB), Int32, (Ptr{Cvoid}, Int32), h.ptr, rset))
+backsolve_columns!(h::Handle, M::Matrix{Float64}) =
+    check(h, ccall((:ngp_backsolve_columns_f64, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64), h.ptr, M, size(M, 2), size(M, 1)))
+backsolve_columns!(h::Handle, M::Matrix{Float32}) =
+    check(h, ccall((:ngp_backsolve_columns_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64), h.ptr, M, size(M, 2), size(M, 1)))
+backsolve_columns!(h::Handle, M::Matrix{UInt8}) =
+    check(h, ccall((:ngp_backsolve_columns_u8, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt8}, Int64, Int64), h.ptr, M, size(M, 2), size(M, 1)))
+function backsolve_end!(h::Handle, rset::Integer, P::Integer)
+    s1 = Vector{Float64}(undef, P); s2 = Vector{Float64}(undef, P); n = Ref{Int64}(0)
+    check(h, ccall((:ngp_backsolve_end, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int64}), h.ptr, rset, s1, s2, n))
+    return s1, s2, n[]
+end
+function backsolve_draws(h::Handle, rset::Integer, q::Integer)
+    T = Ref{Int64}(0)
+    check(h, ccall((:ngp_backsolve_get_draws, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{Int64}), h.ptr, rset, C_NULL, T))
+    U = Matrix{Float64}(undef, q, T[])
+    check(h, ccall((:ngp_backsolve_get_draws, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{Int64}), h.ptr, rset, U, T))
+    return U
+end
 # ---- single-step GBLUP (include/nextgp_hip.h): H^-1 = A^-1 + [0 0; 0 inv((1 - w) G + w A22) - inv(A22)].  The reference has no single-step
 # model, so nothing of the coarse seam routes here: these are direct bindings for a caller that builds the model itself. ----
 # A22 = A[idx, idx] without the dense A (ngp_pedigree_a22: Colleau's indirect method on the host); F from pedigree_ainv, idx 0-based
