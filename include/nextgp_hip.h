@@ -607,6 +607,40 @@ int32_t ngp_backsolve_columns_f32(ngp_handle *h, const float *M, int64_t ncol, i
 int32_t ngp_backsolve_columns_u8(ngp_handle *h, const uint8_t *M, int64_t ncol, int64_t ld);
 int32_t ngp_backsolve_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, int64_t *n);
 
+/* ---- GBLUP prediction: new individuals from their genotypes, after the chain has run on the records alone ----
+ * For a candidate with raw genotypes z_c and the records' column statistics (mu_j, d_j as above, from the RECORDS' columns):
+ *   C_ci = sum_j (z_cj - mu_j) d_j (z_ij - mu_j)   its relationships to the N records (no ridge: that belongs to the diagonal of G)
+ *   gcc_c = sum_j d_j (z_cj - mu_j)^2              its own diagonal, without the ridge
+ *   m_ct = sum_i C_ci w_it, w_t = K u_t            E[u_c | u_t] per stored draw (the draw store of ngp_backsolve_enable)
+ *   s_c = gcc_c - sum_i C_ci (K C')_ic             the part of its genomic variance the records do not determine, in units of varU
+ * The host forms mean_c = sum / n and sd_c^2 = var_t(m_ct) + s_c mean_t(varU_t).  Everything runs on the device in fp64, C on the matrix
+ * cores (csrc/ngp_gpred.h; DESIGN.md section 2, "GBLUP prediction": the normative orders; the same bits run to run and split to split,
+ * and a candidate with the genotypes of record r gets row r of ngp_grm_get's G off the diagonal, C_cr + 0.001 = G_rr).
+ * ngp_gpred_begin: after the run (or before: C and s need no draw).  Allocates C (8 N Nc bytes; V = K C' of the same size follows in
+ *   ngp_gpred_end) -- NGP_ERR_NOMEM with what does not fit; predict the candidates in slabs then.  1 <= Nc <= 64 x 65535.
+ *   NGP_ERR_STATE while a prediction or a back-solve is open on the handle.
+ * ngp_gpred_columns_*: the raw genotype columns of the relationship matrix in its column order, of the records (Ztrain, N rows, ldt >= N)
+ *   and of the candidates (Zcand, Nc rows, ldc >= Nc) for the same ncol columns; column-major host memory, staged in chunks that share
+ *   256 MiB.  Every call but the last brings a multiple of 64 columns.  NGP_ERR_ARG: a leading dimension too small, more columns than G
+ *   had, a call behind a tail, a non-finite value on either side, a column monomorphic among the records under method 2.  A refused
+ *   chunk has not touched C; the chunks of the same call in front of it are in and counted (the message says how many columns),
+ *   the prediction stays open for the rest, or ngp_gpred_abort drops it.
+ * ngp_gpred_end: sum[c] = sum_t m_ct, sumsq[c] = sum_t m_ct^2, s, gcc (Nc doubles each; any may be NULL), n = T stored draws.  With no
+ *   stored draw n = 0 and sum / sumsq are zeros; s, gcc and C are valid all the same.  NGP_ERR_STATE unless exactly the relationship
+ *   matrix's P columns were handed over (the prediction then stays open).  An end that fails further down (memory, a HIP error) leaves
+ *   the prediction open as well and may be called again: C and gcc are divided once.
+ * ngp_gpred_get_cross: C of the last ended prediction, Nc rows of N entries, row c at C_out + c ld (ld >= N); it stays until the next
+ *   ngp_gpred_begin or a new model.
+ * ngp_gpred_abort: drops an open prediction (after a refused call, say) and the block of an ended one; never refused.
+ * Refused with NGP_ERR_ARG like the back-solve: a CSR, tuple or hybrid (single-step) set, and a dense set whose K the caller gave. */
+int32_t ngp_gpred_begin(ngp_handle *h, int32_t rset, int64_t Nc);
+int32_t ngp_gpred_columns_f64(ngp_handle *h, const double *Ztrain, int64_t ldt, const double *Zcand, int64_t ldc, int64_t ncol);
+int32_t ngp_gpred_columns_f32(ngp_handle *h, const float *Ztrain, int64_t ldt, const float *Zcand, int64_t ldc, int64_t ncol);
+int32_t ngp_gpred_columns_u8(ngp_handle *h, const uint8_t *Ztrain, int64_t ldt, const uint8_t *Zcand, int64_t ldc, int64_t ncol);
+int32_t ngp_gpred_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, double *s, double *gcc, int64_t *n);
+int32_t ngp_gpred_get_cross(ngp_handle *h, double *C_out, int64_t ld);
+int32_t ngp_gpred_abort(ngp_handle *h);
+
 /* ---- single-step GBLUP (Aguilar et al. 2010; Christensen & Lund 2010): one breeding value per animal of the pedigree, precision
  *        H^-1 = A^-1 + [ 0 0 ; 0  G_w^-1 - A22^-1 ],   G_w = (1 - w) G + w A22,   A22 = A over the genotyped animals ----
  * H^-1 is sparse except for one n_g x n_g corner, so neither engine above fits: ngp_add_random_set_hybrid walks ONE Gauss-Seidel sweep

@@ -235,6 +235,7 @@ SYMBOLS = [
     "ngp_add_random_set_dense", "ngp_set_records",
     "ngp_backsolve_enable", "ngp_backsolve_get_draws", "ngp_backsolve_begin", "ngp_backsolve_columns_f64", "ngp_backsolve_columns_f32",
     "ngp_backsolve_columns_u8", "ngp_backsolve_end",
+    "ngp_gpred_begin", "ngp_gpred_columns_f64", "ngp_gpred_columns_f32", "ngp_gpred_columns_u8", "ngp_gpred_end", "ngp_gpred_get_cross", "ngp_gpred_abort",
     "ngp_set_random_schedule", "ngp_get_random_schedule", "ngp_pedigree_ainv",
     "ngp_pedigree_a22", "ngp_grm_single_step", "ngp_add_random_set_hybrid",
     "ngp_add_random_set_tuple", "ngp_get_random_tuple", "ngp_set_random_tuple", "ngp_sample_random_set_tuple",
@@ -281,6 +282,35 @@ def pool_backsolve(parts):
         tot = tot + r["sum"]
         tot2 = tot2 + r["sumsq"]
     return backsolve_summary(tot, tot2, sum(int(r["n"]) for r in parts))
+
+
+def gblup_predict_summary(sum_, sumsq, n, s, gcc, sum_varU):
+    """GBLUP prediction of candidates from the raw sums (Sampler.gblup_predict): mean = sum / n and
+    sd^2 = var_t(m_ct) + s mean_t(varU_t), the spread of the conditional mean over the n stored draws (n - 1 below) plus the part of the
+    candidate's own genomic variance that the records do not determine.  Without a stored draw mean and sd are NaN."""
+    sum_, sumsq, n = np.asarray(sum_, dtype=np.float64), np.asarray(sumsq, dtype=np.float64), int(n)
+    s, gcc = np.asarray(s, dtype=np.float64), np.asarray(gcc, dtype=np.float64)
+    if n < 1:
+        mean = sd = np.full(len(sum_), np.nan)
+    else:
+        mean = sum_ / n
+        var = np.maximum(sumsq - n * mean * mean, 0.0) / max(n - 1, 1)
+        sd = np.sqrt(var + np.maximum(s, 0.0) * (float(sum_varU) / n))
+    return dict(sum=sum_, sumsq=sumsq, n=n, s=s, gcc=gcc, sum_varU=float(sum_varU), mean=mean, sd=sd)
+
+
+def pool_gblup_predict(parts):
+    """Chains' GBLUP predictions (Sampler.gblup_predict) pooled exactly: sum, sumsq, n and the varU sums are added, in the order given;
+    s and gcc belong to the genotypes and are the first chain's."""
+    parts = list(parts)
+    if len({len(r["sum"]) for r in parts}) != 1:
+        raise ValueError("pool_gblup_predict: the parts hold different numbers of candidates")
+    tot, tot2, sv = parts[0]["sum"].copy(), parts[0]["sumsq"].copy(), float(parts[0]["sum_varU"])
+    for r in parts[1:]:
+        tot = tot + r["sum"]
+        tot2 = tot2 + r["sumsq"]
+        sv = sv + float(r["sum_varU"])
+    return gblup_predict_summary(tot, tot2, sum(int(r["n"]) for r in parts), parts[0]["s"], parts[0]["gcc"], sv)
 
 
 def prediction_summary(ps):
@@ -635,7 +665,9 @@ class Sampler:
 
     def _chk(self, rc):
         if rc != 0:
-            raise NextGPHipError(f"libnextgp_hip error {rc}: " + (self.L.ngp_last_error(self.h) or b"").decode())
+            e = NextGPHipError(f"libnextgp_hip error {rc}: " + (self.L.ngp_last_error(self.h) or b"").decode())
+            e.code = int(rc)   # (NGP_ERR_*: callers that act on the kind of refusal read this, not the text)
+            raise e
 
     def close(self):
         if getattr(self, "h", None):
@@ -1121,6 +1153,51 @@ class Sampler:
         s1, s2, n = np.empty(P), np.empty(P), C.c_int64()
         self._chk(self.L.ngp_backsolve_end(self.h, C.c_int32(int(rset)), _p(s1, C.c_double), _p(s2, C.c_double), C.byref(n)))
         return backsolve_summary(s1, s2, n.value)
+
+    # ---- GBLUP prediction (include/nextgp_hip.h, "GBLUP prediction") ---------------------------
+    def gblup_predict(self, set_id, M_train, M_cand, splits=None):
+        """After the run: candidates predicted from their genotypes under the dense set set_id (K built by grm_begin .. grm_invert).
+        M_train: the N x P genotypes the relationship matrix was built from; M_cand: Nc x P, the same columns (uint8 and float32 go as
+        they are when both arrays have that type, anything else as float64).  Both go over in column ranges (splits: the ranges' first
+        columns beyond 0, multiples of 64; default every BACKSOLVE_COLUMNS_PER_CALL columns); the result does not depend on the split.
+        Returns {"sum", "sumsq", "n", "s", "gcc", "sum_varU", "mean", "sd"} (gblup_predict_summary; pool_gblup_predict pools chains);
+        the draws are those stored by enable_backsolve -- without them n = 0, mean and sd are NaN, s, gcc and gblup_cross() still hold."""
+        A, B = np.asarray(M_train), np.asarray(M_cand)
+        q = self.rand_q[set_id]
+        if A.ndim != 2 or A.shape[0] != q:
+            raise ValueError(f"gblup_predict: M_train is the N x P genotype matrix with one row per level of the set (N = {q})")
+        if B.ndim != 2 or B.shape[1] != A.shape[1] or B.shape[0] < 1:
+            raise ValueError(f"gblup_predict: M_cand holds one row per candidate and the {A.shape[1]} columns of M_train")
+        if A.dtype != B.dtype or A.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+            A, B = (A if A.dtype == np.float64 else A.astype(np.float64)), (B if B.dtype == np.float64 else B.astype(np.float64))
+        P, Nc = A.shape[1], B.shape[0]
+        cuts = [0] + (list(splits) if splits is not None else list(range(self.BACKSOLVE_COLUMNS_PER_CALL, P, self.BACKSOLVE_COLUMNS_PER_CALL))) + [P]
+        self._gpred_shape = None   # (begin drops the block of the prediction before)
+        self._chk(self.L.ngp_gpred_begin(self.h, C.c_int32(int(set_id)), C.c_int64(Nc)))
+        s1, s2, s, gcc, n = np.empty(Nc), np.empty(Nc), np.empty(Nc), np.empty(Nc), C.c_int64()
+        try:
+            for c0, c1 in zip(cuts[:-1], cuts[1:]):
+                At, t, sfx, ldt = _columns(A[:, c0:c1])
+                Bc, _, _, ldc = _columns(B[:, c0:c1])
+                self._chk(getattr(self.L, "ngp_gpred_columns_" + sfx)(self.h, _p(At, t), C.c_int64(ldt), _p(Bc, t), C.c_int64(ldc), C.c_int64(At.shape[1])))
+            self._chk(self.L.ngp_gpred_end(self.h, C.c_int32(int(set_id)), _p(s1, C.c_double), _p(s2, C.c_double), _p(s, C.c_double),
+                                           _p(gcc, C.c_double), C.byref(n)))
+        except Exception:   # (a refused call leaves the prediction open: dropped, so that the sampler can start another)
+            self.L.ngp_gpred_abort(self.h)
+            self._gpred_shape = None
+            raise
+        self._gpred_shape = (Nc, q)   # (the block the handle now holds: gblup_cross)
+        return gblup_predict_summary(s1, s2, n.value, s, gcc, self.get_random(set_id)["sum_varU"])
+
+    def gblup_cross(self):
+        """The candidates x records relationship block C (Nc x N) of the last gblup_predict on this sampler -- of its last slab of
+        candidates where a caller predicts in slabs: the companion of makeG / grm_get."""
+        if getattr(self, "_gpred_shape", None) is None:
+            raise ValueError("gblup_cross: this sampler has completed no gblup_predict (or its last one was refused)")
+        Nc, N = self._gpred_shape
+        out = np.empty((Nc, N))
+        self._chk(self.L.ngp_gpred_get_cross(self.h, _p(out, C.c_double), C.c_int64(N)))
+        return out
 
     def get_random(self, set_id):
         q = self.rand_q[set_id]

@@ -26,7 +26,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import pedigree_a22, pedigree_ainv, pool_backsolve, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
+from ._lib import pedigree_a22, pedigree_ainv, pool_backsolve, pool_gblup_predict, LV_MAXCOV, METHOD_BAYESB, METHOD_BAYESC, METHOD_BAYESPR, Sampler, tuple_columns, tuple_panel, tuple_span
 
 __all__ = ["makePed", "makeA", "makeG", "gblup_terms", "BayesPR", "BayesB", "BayesC", "BayesR", "BayesRCπ", "BayesRCpi", "BayesRCplus", "BayesLV", "lv_design_matrix", "Random", "SNP", "runLMEM", "summaryMCMC", "read_genotypes", "read_panel_file", "is_panel_file", "prep2RegionData", "parse_formula", "design_columns", "samples_to_out_files", "random_levels", "random_prior", "random_file_names", "read_prediction_file", "write_prediction_file", "write_variance_out_files", "write_gwas_files",
            "is_bed_file", "read_plink", "write_plink", "decode_bed"]
@@ -767,12 +767,13 @@ def bed_round_code(total, n_obs):
     return np.where(n_obs > 0, (2 * total + n_obs) // np.maximum(2 * n_obs, 1), 0)
 
 
-def decode_bed(bed, n_file, rows=None, cols=None, allele=1, missing="mean", counts=False):
+def decode_bed(bed, n_file, rows=None, cols=None, allele=1, missing="mean", counts=False, fill=None):
     """Host decoder of packed .bed columns (read_plink()["bed"]): the (N, P) matrix of allele counts of the selected rows (file
     samples, any order, repeats allowed; None: all) and columns, with the imputation rules of the device kernels (ngp_bed.h):
     "error" refuses a missing call among the selected rows, "round" fills in (2 sum + n_obs) // (2 n_obs) of its column (uint8 result,
     as under "error"), "mean" the mean of the observed calls (float64 result); a column without an observed call is all zero.
-    counts=True also returns the (P, 4) numbers of 0, 1, 2 and missing calls."""
+    counts=True also returns the (P, 4) numbers of 0, 1, 2 and missing calls.  fill: None, or one mean per column that a missing call takes
+    in place of the selected rows' own (candidates imputed at the records' means): as it is under "mean", floor(fill + 0.5) under "round"."""
     if missing not in BED_POLICIES:
         raise ValueError(f"missing-call policy {missing!r}: one of {BED_POLICIES}")
     if allele not in (1, 2):
@@ -789,15 +790,20 @@ def decode_bed(bed, n_file, rows=None, cols=None, allele=1, missing="mean", coun
     miss = G == 3
     cnt = np.stack([(G == v).sum(axis=0) for v in range(4)], axis=1).astype(np.int64)
     total, n_obs = cnt[:, 1] + 2 * cnt[:, 2], cnt[:, 0] + cnt[:, 1] + cnt[:, 2]
+    if fill is not None:
+        fill = np.asarray(fill, dtype=np.float64)
+        if fill.shape != (G.shape[1],):
+            raise ValueError("decode_bed: fill holds one mean per decoded column")
     if missing == "error":
         if miss.any():
             j = int(np.flatnonzero(cnt[:, 3])[0])
             raise ValueError(f"column {j} holds {int(cnt[j, 3])} missing calls")
         out = np.asfortranarray(G)
     elif missing == "round":
-        out = np.asfortranarray(np.where(miss, bed_round_code(total, n_obs).astype(np.uint8)[None, :], G))
+        code = bed_round_code(total, n_obs).astype(np.uint8) if fill is None else np.floor(fill + 0.5).astype(np.uint8)
+        out = np.asfortranarray(np.where(miss, code[None, :], G))
     else:
-        mu = np.where(n_obs > 0, total / np.maximum(n_obs, 1), 0.0)
+        mu = np.where(n_obs > 0, total / np.maximum(n_obs, 1), 0.0) if fill is None else fill
         out = np.asfortranarray(np.where(miss, mu[None, :], G.astype(np.float64)))
     return (out, cnt) if counts else out
 
@@ -1189,8 +1195,13 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     res["predict"] = {"ids", "mean", "sd", "sets": {name: {"mean", "sd"}}} (mean and SD of the breeding value over the kept draws, all
     marker sets together and per set; correlated sets count as the one set they are, under their joined name) and outFolder/gebvPredict.txt
     holds the same columns: ID mean sd mean_<set> sd_<set> ...  predict_ids names the individuals (default 1..Np).  With chains=K the
-    sums are pooled over the chains and res["chains"][c]["predict"] is each chain's own.  GBLUP terms together with predict= raise
-    NotImplementedError; without predict= nothing differs.
+    sums are pooled over the chains and res["chains"][c]["predict"] is each chain's own.  On a model whose SNP(...) terms are all GBLUP
+    terms predict={name: source} predicts the candidates after the run (ngp_gpred_*; DESIGN.md section 2, "GBLUP prediction"): every kept
+    draw is stored on the device, the candidates x records relationship block is built from both genotype arrays (ranges of 4,096
+    columns, slabs of candidates where it does not fit), and res["predict"]["sets"][name] = {"mean", "sd", "s", ...} with
+    sd^2 = var_t(E[u_c | u_t]) + s mean(varU); the total sd is that of a single GBLUP term and NaN for several (the covariance between
+    terms is not tracked).  Marker sets beside GBLUP terms in one predict= raise NotImplementedError, as do single-step terms; without
+    predict= nothing differs.
     (9) windows={name: W | [(a, b), ...]} (or genomicVariance=True with windows={} for set and total slots only) forms the genomic
     variance of every kept draw on the device (ngp_enable_genomic_variance; DESIGN.md section 2, "Genomic variance"): var(X beta) over the
     training individuals per window, per marker set and in all, the share q = V / V_g of each, r = V_g / (V_g + varE), and the window
@@ -1352,6 +1363,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     snp_fx = _snp_effects_terms(snpEffects, gb_names, [t.name for t in snps], nChain, nBurn, nThin, folds)   # (checked before any device work)
     mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
     snps = [t for t in snps if t.name not in gb_names]
+    gpred = _gblup_prediction_sources(predict, predict_ids, snps, gblup, ped, alleleCount, missingGeno, (int(nChain) - int(nBurn)) // int(nThin), folds, bed_sets)
     pmats = _prediction_sources(predict, predict_ids, snps, mats, gb_names, alleleCount, missingGeno, tuple_names)   # (checked before any device work)
     gv_windows = _variance_windows(windows, windowThreshold, genomicVariance, snps, mats, gb_names, VCV)   # (the same)
     if gv_windows is not None and w_res is not None:
@@ -1469,7 +1481,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     sets, fixed_names = built[0]
     randoms = samplers[0].randoms
     for sc in samplers:   # behind set_y: the draw store of every back-solved term, one column per kept draw
-        for nm in snp_fx:
+        for nm in list(snp_fx) + [nm for nm in (gpred["M"] if gpred else ()) if nm not in snp_fx]:   # (GBLUP prediction reads the same store)
             sc.enable_backsolve([rd["id"] for rd in sc.randoms if rd.get("key") == nm][0], (int(nChain) - int(nBurn)) // int(nThin))
     if gv_windows is not None:   # behind set_y: the pass is switched on with empty sums; one trace row per kept draw
         for sc in samplers:
@@ -1499,6 +1511,15 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         names = list(bed_sets[nm].info["snp"]) if nm in bed_sets else [f"M{i + 1}" for i in range(P)]   # src/prepMatVec.jl:131
         res.setdefault("random", {}).setdefault(nm, {})["snp"] = dict(mean=fx["mean"], sd=fx["sd"], n=fx["n"])
         write_snp_effects_file(os.path.join(outFolder, f"snpEffects{nm}.txt"), names, fx["mean"], fx["sd"])
+    if gpred is not None:   # GBLUP terms: both genotype arrays once more, per chain; the chains' sums added
+        per_chain = []
+        for sc in samplers:
+            per_chain.append({nm: _gblup_predict_chain(sc, [rd["id"] for rd in randoms if rd.get("key") == nm][0], gblup[nm]["M"], cand)
+                              for nm, cand in gpred["M"].items()})
+        for r, pc in zip(res.get("chains", []), per_chain):
+            r["predict"] = _gblup_prediction_result(pc, gpred["ids"])
+        res["predict"] = _gblup_prediction_result({nm: pool_gblup_predict([pc[nm] for pc in per_chain]) for nm in gpred["M"]}, gpred["ids"])
+        write_prediction_file(os.path.join(outFolder, "gebvPredict.txt"), res["predict"])
     if pmats is not None:
         if predict_ids is not None:
             ids = [str(a) for a in predict_ids]
@@ -1904,9 +1925,12 @@ def _prediction_sources(predict, predict_ids, snps, mats, gb_names, allele=1, mi
         if predict_ids is not None:
             raise ValueError("predict_ids without predict=")
         return None
+    if gb_names and snps:
+        raise NotImplementedError(f"predict= with marker sets beside the GBLUP term(s) {sorted(gb_names)}: the marker sets' X_new beta is accumulated "
+                                  "draw by draw in the sweep, a GBLUP term's E[u_c | u_t] after the run from the stored draws; a model of GBLUP "
+                                  "terms alone, or of marker sets alone, is predicted")
     if gb_names:
-        raise NotImplementedError(f"predict= with the GBLUP term(s) {sorted(gb_names)}: a breeding value of a new individual under GBLUP needs its "
-                                  "relationships to the records (makeG over both, src/misc.jl:145-160); prediction on the device covers marker sets")
+        return None   # (GBLUP terms alone: _gblup_prediction_sources)
     if not hasattr(predict, "keys"):
         raise ValueError("predict: a mapping from the name of every SNP(...) term to its genotype source")
     want = [t.name for t in snps]
@@ -1930,6 +1954,80 @@ def _prediction_sources(predict, predict_ids, snps, mats, gb_names, allele=1, mi
                 raise NotImplementedError(f"predict[{nm!r}]: missing calls of candidates in a correlated (Tuple) unit -- the host decoder knows "
                                           "the candidates' column means, not the training means a missing call takes; impute them first")
     return pm
+
+
+def _gblup_prediction_sources(predict, predict_ids, snps, gblup, ped, allele, missing, nKept, folds, bed_sets=None):
+    """runLMEM(predict=...) on a model whose SNP(...) terms are all GBLUP terms: {"M": {term: Nc x P genotypes of the candidates}, "ids"}, or None where
+    _prediction_sources serves (or refuses) the request.  A candidate .bed is decoded on the host (decode_bed) under the missing-call
+    policy of the run, a missing call at the mean of the RECORDS' column (rounded under "round", refused under "error"); its SNP IDs
+    must be those of the records' fileset (bed_sets: {term: the records' _BedSource}).  Called in front of _prediction_sources; host
+    checks only."""
+    if predict is None:
+        return None
+    if hasattr(predict, "keys") and ped and any(k in ped.get("single", {}) for k in predict):
+        raise NotImplementedError(f"predict= with the single-step term(s) {sorted(k for k in predict if k in ped['single'])}: a candidate's value "
+                                  "under H needs its pedigree part as well as its genotypes; GBLUP prediction covers Random(\"G\", v) terms")
+    if snps or not gblup:
+        return None
+    if not hasattr(predict, "keys"):
+        raise ValueError("predict: a mapping from the name of every SNP(...) term to its genotype source")
+    want = list(gblup)
+    if sorted(predict.keys()) != sorted(want):
+        raise ValueError(f"predict needs exactly one source per SNP(...) term {want}, got {sorted(predict.keys())}")
+    if folds is not None:
+        raise ValueError("predict= with GBLUP terms and folds=: the fold-chains see different data, their predictions do not pool")
+    if nKept < 1:
+        raise ValueError("predict= with GBLUP terms: the schedule keeps no draw")
+    out, bed_ids = {}, None
+    for nm in want:
+        T, src = gblup[nm]["M"], _genotype_source(predict[nm], None, allele, missing)
+        if _is_bed(src):   # decoded here: a missing call takes the records' mean of its column, which only this side knows
+            if bed_sets and nm in bed_sets and src.info["snp"] != bed_sets[nm].info["snp"]:
+                raise ValueError(f"predict[{nm!r}]: the SNP IDs of {src.info['path'][:-4]}.bim differ from the training set's ({bed_sets[nm].info['path'][:-4]}.bim)")
+            if src.shape[1] != T.shape[1]:
+                raise ValueError(f"predict[{nm!r}] holds {src.shape[1]} columns, the term {T.shape[1]}")
+            M = decode_bed(src.info["bed"], src.info["n"], allele=src.allele, missing=src.missing, fill=np.asarray(T, dtype=np.float64).mean(axis=0))
+            bed_ids = bed_ids or list(src.info["iid"])   # (a candidate fileset names its own individuals)
+        else:
+            M = np.asarray(src)
+        if M.ndim != 2 or M.shape[1] != T.shape[1]:
+            raise ValueError(f"predict[{nm!r}] holds {M.shape[1] if M.ndim == 2 else '?'} columns, the term {T.shape[1]}")
+        out[nm] = M
+    rows = [M.shape[0] for M in out.values()]
+    if len(set(rows)) != 1 or rows[0] < 1:
+        raise ValueError(f"every prediction source needs the same individuals: rows {rows}")
+    if predict_ids is not None and len(predict_ids) != rows[0]:
+        raise ValueError(f"predict_ids names {len(predict_ids)} individuals, the prediction sources hold {rows[0]}")
+    ids = [str(a) for a in predict_ids] if predict_ids is not None else bed_ids or [str(i + 1) for i in range(rows[0])]
+    return dict(M=out, ids=ids)
+
+
+def _gblup_predict_chain(sc, rid, M, cand):
+    """One chain's GBLUP prediction of all candidates, in slabs of candidates where the relationship block of all of them does not fit on
+    the device (the slab is halved until it does; 64 candidates at the least)."""
+    from ._lib import NextGPHipError, gblup_predict_summary
+    Nc, slab, parts, c0 = cand.shape[0], cand.shape[0], [], 0
+    while c0 < Nc:
+        try:
+            parts.append(sc.gblup_predict(rid, M, cand[c0:c0 + slab]))
+        except NextGPHipError as e:
+            if getattr(e, "code", 0) != -4 or slab <= 64:   # (NGP_ERR_NOMEM: the block, V or W did not fit)
+                raise
+            slab = max(64, (slab // 2 + 63) // 64 * 64)
+            continue
+        c0 += slab
+    cat = {k: np.concatenate([p[k] for p in parts]) for k in ("sum", "sumsq", "s", "gcc")}
+    return gblup_predict_summary(cat["sum"], cat["sumsq"], parts[0]["n"], cat["s"], cat["gcc"], parts[0]["sum_varU"])
+
+
+def _gblup_prediction_result(per_term, ids):
+    """res["predict"] of GBLUP terms: {term: gblup_predict_summary}.  The total mean is the sum of the terms' means; the total SD is that
+    of a single term, and NaN for several: the covariance between terms is not tracked."""
+    names = list(per_term)
+    mean = sum(per_term[nm]["mean"] for nm in names)
+    sd = per_term[names[0]]["sd"] if len(names) == 1 else np.full(len(mean), np.nan)
+    return dict(ids=list(ids), nKept=int(per_term[names[0]]["n"]), mean=mean, sd=sd,
+                sets={nm: {k: per_term[nm][k] for k in ("mean", "sd", "s", "gcc", "sum", "sumsq", "n", "sum_varU")} for nm in names})
 
 
 def _prediction_result(ps, ids, names):

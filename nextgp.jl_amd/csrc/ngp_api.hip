@@ -42,6 +42,7 @@
 #include "ngp_genvar.h"
 #include "ngp_diag.h"
 #include "ngp_backsolve.h"
+#include "ngp_gpred.h"
 #include "ngp_sweep_args.h"
 #include "ngp_state.h"
 
@@ -177,6 +178,22 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     } bs;
     bool scheduled() const { return sched_mode == 2 || (sched_mode == 0 && (hyb ? hd : q) > NGP_RS_AUTO_LEVELS_PER_DEPTH * ndepth); }
 };
+// GBLUP prediction (ngp_gpred.h): between ngp_gpred_begin and ngp_gpred_end (open) C' (N x Ncpad, leading dimension N), gcc, the columns
+// handed over so far and the staging chunks of both genotype arrays; after ngp_gpred_end C' stays for ngp_gpred_get_cross until the next
+// ngp_gpred_begin or a new model
+struct Gpred {
+    int rset = -1;         // the set C belongs to (-1: none)
+    bool open = false;
+    bool scaled = false;   // ngp_gpred_end has divided C and gcc: an end that failed later and is called again does not divide twice
+    int64_t N = 0, Nc = 0, Ncpad = 0, cols = 0;
+    DevArray<double> Ct, gcc, mu, sd;
+    DevArray<unsigned char> stage_t, stage_c;
+    DevArray<unsigned> bad;
+    size_t bytes_t = 0, bytes_c = 0;
+    int64_t stage_cols = 0;
+    void release_pass() { mu.reset(); sd.reset(); stage_t.reset(); stage_c.reset(); bad.reset(); bytes_t = bytes_c = 0; stage_cols = 0; }
+};
+
 // q of a set as the sample file's header and the snapshot signature carry it: q, and k - 1 of a tuple set in the bits from 32 up
 // (q < 2^31; a set of one component writes the word it always wrote)
 inline int64_t rand_q_word(const HRand &R) { return R.q | ((int64_t)(R.tk - 1) << 32); }
@@ -639,6 +656,7 @@ struct ngp_handle {
     bool records_only = false;  // ngp_set_records: N records and no genotype panel (one inert block of 64 zero columns stands in for it)
     Grm grm;                    // ngp_grm_*: independent of the panel and of the model
     int bs_open = -1;           // the random-effect set between ngp_backsolve_begin and ngp_backsolve_end (-1: none)
+    Gpred gp;                   // ngp_gpred_*: the relationship block of the candidates (goes with the model)
     bool panel_open = false;  // between ngp_begin_panel and ngp_end_panel: columns may still arrive, the Gram window does not exist yet
     bool pred_open = false;   // between ngp_begin_prediction_panel and ngp_end_prediction_panel: only prediction columns may be called
     int cu_count = 256;
@@ -810,6 +828,7 @@ void drop_panel(ngp_handle *h) {
     h->h_tregs.clear(); h->h_tseg_l0.clear(); h->h_tseg_len.clear(); h->h_tseg_set.clear();
     h->have_y = false; h->iter = 0; h->poisoned = false; h->panel_open = false; h->records_only = false; h->pred_open = false;
     h->bs_open = -1;
+    h->gp = Gpred();
 }
 
 // A new panel of N x P (owner: ngp_share_panel's, whose arrays and plan are taken as they are).  The old panel goes first, so that
@@ -5850,14 +5869,14 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
 
 namespace {
 // the set a back-solve call names: a dense set whose K this library built from genotype columns (their weights are then known)
-int backsolve_set(ngp_handle *h, int32_t rset, HRand **out) {
+int backsolve_set(ngp_handle *h, int32_t rset, HRand **out, const std::string &what = "SNP back-solve") {
     REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "panel (or records) not set");
-    REQUIRE(rset >= 0 && rset < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "SNP back-solve: no such random-effect set");
+    REQUIRE(rset >= 0 && rset < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, what + ": no such random-effect set");
     HRand &R = h->mm.rnd[(size_t)rset];
     REQUIRE(R.dk && !R.hyb && R.tk == 1, NGP_ERR_ARG,
-            "SNP back-solve: the set is not a dense one (ngp_add_random_set_dense); CSR and hybrid (single-step) sets have no genotype columns behind all their levels");
+            what + ": the set is not a dense one (ngp_add_random_set_dense); CSR and hybrid (single-step) sets have no genotype columns behind all their levels");
     REQUIRE(R.dk->grm_method != 0, NGP_ERR_ARG,
-            "SNP back-solve: the caller gave this set's K; the column weights are known only for a matrix built by ngp_grm_begin .. ngp_grm_invert");
+            what + ": the caller gave this set's K; the column weights are known only for a matrix built by ngp_grm_begin .. ngp_grm_invert");
     *out = &R;
     return NGP_OK;
 }
@@ -6016,6 +6035,210 @@ int32_t ngp_backsolve_end(ngp_handle *h, int32_t rset, double *sum, double *sums
     if (n) *n = B.T;
     B.release_pass();
     h->bs_open = -1;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ---- GBLUP prediction: the candidates x records relationship block, the conditional mean per kept draw and the part of a candidate's
+ * variance the records do not determine (ngp_gpred.h; DESIGN.md section 2, "GBLUP prediction") ---- */
+}  // extern "C"
+
+namespace {
+// device memory a call is about to take, checked against what is free: a clear refusal in place of a failed allocation
+int gpred_fits(ngp_handle *h, double bytes, const std::string &what) {
+    size_t free_b = 0, total_b = 0;
+    HCHK(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > (double)free_b)
+        return fail(h, NGP_ERR_NOMEM, "GBLUP prediction: " + what + " needs " + std::to_string((long long)(bytes / 1048576.0) + 1) + " MiB, " +
+                                          std::to_string((long long)(free_b >> 20)) + " MiB of device memory are free (predict the candidates in slabs)");
+    return NGP_OK;
+}
+
+template <typename TIn>
+int gpred_columns_t(ngp_handle *h, int type, const TIn *Mt, int64_t ldt, const TIn *Mc, int64_t ldc, int64_t ncol) {
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Gpred &g = h->gp;
+    REQUIRE(g.open && g.rset >= 0 && g.rset < (int)h->mm.rnd.size(), NGP_ERR_STATE, "ngp_gpred_columns_* needs an open prediction (ngp_gpred_begin)");
+    const HRand &R = h->mm.rnd[(size_t)g.rset];
+    const int64_t N = g.N, Nc = g.Nc, P = R.dk->grm_ncols;
+    REQUIRE(Mt != nullptr && Mc != nullptr && ncol > 0, NGP_ERR_ARG, "genotype columns: the records' and the candidates' matrices of at least one column");
+    REQUIRE(ldt >= N, NGP_ERR_ARG, "GBLUP prediction: the records' genotype columns have fewer rows than the set has levels (leading dimension smaller than q)");
+    REQUIRE(ldc >= Nc, NGP_ERR_ARG, "GBLUP prediction: the candidates' genotype columns have fewer rows than Nc (leading dimension smaller than Nc)");
+    REQUIRE(g.cols + ncol <= P, NGP_ERR_ARG, "GBLUP prediction: more columns than the relationship matrix was built from (" + std::to_string(P) + ")");
+    REQUIRE(g.cols % 64 == 0, NGP_ERR_ARG, "GBLUP prediction: every call but the last brings a multiple of 64 columns (the call before brought a tail)");
+    // both arrays share the staging budget, in the input's own type
+    int64_t cchunk = std::min<int64_t>((ncol + 63) / 64 * 64, staging_bytes(h, (int64_t)256 << 20) / (int64_t)((ldt + ldc) * (int64_t)sizeof(TIn)));
+    cchunk = std::max<int64_t>(64, cchunk / 64 * 64);
+    const size_t need_t = (size_t)cchunk * (size_t)ldt * sizeof(TIn), need_c = (size_t)cchunk * (size_t)ldc * sizeof(TIn);
+    if (g.bytes_t < need_t) {
+        g.bytes_t = 0;
+        if (g.stage_t.alloc_raw(need_t) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer of GBLUP prediction (records)");
+        g.bytes_t = need_t;
+    }
+    if (g.bytes_c < need_c) {
+        g.bytes_c = 0;
+        if (g.stage_c.alloc_raw(need_c) != hipSuccess) return fail(h, NGP_ERR_NOMEM, "staging buffer of GBLUP prediction (candidates)");
+        g.bytes_c = need_c;
+    }
+    if (g.stage_cols < cchunk) {
+        g.stage_cols = 0;
+        if ((rc = g.mu.alloc(h, (size_t)cchunk)) || (rc = g.sd.alloc(h, (size_t)cchunk))) return rc;
+        g.stage_cols = cchunk;
+    }
+    if (!g.bad && (rc = g.bad.alloc(h, 2))) return rc;
+    TIn *d_t = (TIn *)g.stage_t.get(), *d_c = (TIn *)g.stage_c.get();
+    for (int64_t c0 = 0; c0 < ncol; c0 += cchunk) {
+        const int64_t nc = std::min<int64_t>(cchunk, ncol - c0);
+        const unsigned bad0[2] = {0u, 0xFFFFFFFFu};
+        unsigned bad[2] = {0u, 0u};
+        hipError_t e = hipMemcpyAsync(g.bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, h->stream);
+        // (the last column may be shorter than ld in the caller's buffer: nc - 1 full columns + the rows)
+        if (e == hipSuccess) e = hipMemcpyAsync(d_t, Mt + (size_t)c0 * (size_t)ldt, ((size_t)(nc - 1) * (size_t)ldt + (size_t)N) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_c, Mc + (size_t)c0 * (size_t)ldc, ((size_t)(nc - 1) * (size_t)ldc + (size_t)Nc) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
+        GpCols c;
+        c.type = type; c.method = R.dk->grm_method; c.train = d_t; c.cand = d_c; c.N = N; c.ldt = ldt; c.Nc = Nc; c.ldc = ldc; c.nc = nc;
+        c.mu = g.mu.get(); c.sd = g.sd.get(); c.bad = g.bad.get(); c.Ct = g.Ct.get(); c.gcc = g.gcc.get();
+        if (e == hipSuccess) e = gpred_colstats(c, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(bad, g.bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("GBLUP prediction columns: ") + hipGetErrorString(e));
+        // a refused chunk has not touched C: the columns before it stay (those of this call's earlier chunks included -- the message
+        // says how many are in), the prediction stays open
+        if (bad[0] != 0u)
+            return fail(h, NGP_ERR_ARG, "non-finite genotype value in the columns of GBLUP prediction; " + std::to_string(g.cols) + " columns are in so far");
+        if (bad[1] != 0xFFFFFFFFu)
+            return fail(h, NGP_ERR_ARG, "GBLUP prediction, method 2: column " + std::to_string(g.cols + (int64_t)bad[1] - 1) +
+                                            " (0-based, counted over all calls) is monomorphic among the records: these are not the relationship matrix's columns; " +
+                                            std::to_string(g.cols) + " columns are in so far");
+        e = gpred_cross(c, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the staging buffers are reused by the next chunk
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("GBLUP prediction columns: ") + hipGetErrorString(e));
+        g.cols += nc;
+    }
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t ngp_gpred_begin(ngp_handle *h, int32_t rset, int64_t Nc) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HRand *R = nullptr;
+    if ((rc = backsolve_set(h, rset, &R, "GBLUP prediction"))) return rc;
+    REQUIRE(Nc >= 1 && Nc <= (int64_t)64 * 65535, NGP_ERR_ARG, "GBLUP prediction: 1 <= Nc <= 4,194,240 candidates per call (64 x 65535; predict more in slabs)");
+    REQUIRE(!h->gp.open, NGP_ERR_STATE, "a GBLUP prediction is open on this handle (ngp_gpred_end)");
+    REQUIRE(h->bs_open < 0, NGP_ERR_STATE, "a back-solve is open on this handle (ngp_backsolve_end): both form W = K U of the stored draws, one at a time");
+    h->gp = Gpred();  // (the block of the prediction before goes first)
+    const int64_t N = R->q, Ncpad = (Nc + 63) / 64 * 64;
+    // C' now, V = K C' of the same size in ngp_gpred_end
+    if ((rc = gpred_fits(h, 8.0 * (double)N * ((double)Ncpad + (double)Nc), "the relationship block C (8 Nc N bytes) and V = K C' (the same)"))) return rc;
+    Gpred g;
+    if ((rc = g.Ct.alloc(h, (size_t)N * (size_t)Ncpad)) || (rc = g.gcc.alloc(h, (size_t)Ncpad))) return rc;
+    HCHK(hipStreamSynchronize(h->stream));
+    g.rset = rset; g.open = true; g.N = N; g.Nc = Nc; g.Ncpad = Ncpad;
+    h->gp = std::move(g);
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_gpred_columns_f64(ngp_handle *h, const double *Ztrain, int64_t ldt, const double *Zcand, int64_t ldc, int64_t ncol) {
+    NGP_TRY
+    return gpred_columns_t<double>(h, 0, Ztrain, ldt, Zcand, ldc, ncol);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_gpred_columns_f32(ngp_handle *h, const float *Ztrain, int64_t ldt, const float *Zcand, int64_t ldc, int64_t ncol) {
+    NGP_TRY
+    return gpred_columns_t<float>(h, 1, Ztrain, ldt, Zcand, ldc, ncol);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_gpred_columns_u8(ngp_handle *h, const uint8_t *Ztrain, int64_t ldt, const uint8_t *Zcand, int64_t ldc, int64_t ncol) {
+    NGP_TRY
+    return gpred_columns_t<uint8_t>(h, 2, Ztrain, ldt, Zcand, ldc, ncol);
+    NGP_CATCH(h)
+}
+
+int32_t ngp_gpred_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, double *s, double *gcc, int64_t *n) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HRand *R = nullptr;
+    if ((rc = backsolve_set(h, rset, &R, "GBLUP prediction"))) return rc;
+    Gpred &g = h->gp;
+    REQUIRE(g.open && g.rset == rset, NGP_ERR_STATE, "ngp_gpred_end: no GBLUP prediction of this set is open (ngp_gpred_begin)");
+    const int64_t P = R->dk->grm_ncols, N = g.N, Nc = g.Nc;
+    REQUIRE(g.cols == P, NGP_ERR_STATE, "ngp_gpred_end: " + std::to_string(g.cols) + " genotype columns were handed over, the relationship matrix was built from " +
+                                            std::to_string(P) + " (hand over the rest, or start again with ngp_gpred_begin)");
+    REQUIRE(h->bs_open < 0, NGP_ERR_STATE, "a back-solve is open on this handle (ngp_backsolve_end): both form W = K U of the stored draws, one at a time");
+    const int64_t T = std::min(R->bs.n, R->bs.max_draws);  // (0 without a draw store)
+    g.release_pass();
+    if ((rc = gpred_fits(h, 8.0 * ((double)N * (double)Nc + 6.0 * (double)Nc + (double)T * ((double)N + 1.0)), "V = K C' (8 Nc N bytes) and W = K U (8 N T bytes)"))) {
+        h->gp = Gpred();  // (dropped: the caller starts again with fewer candidates)
+        return rc;
+    }
+    DevArray<double> V, cv, W, cw, d_s, d_sum, d_sumsq, mu0, d1;
+    if (V.alloc_raw((size_t)N * (size_t)Nc) != hipSuccess || cv.alloc_raw((size_t)Nc) != hipSuccess || d_s.alloc_raw((size_t)Nc) != hipSuccess)
+        return fail(h, NGP_ERR_NOMEM, "V = K C' of GBLUP prediction: " + std::to_string(N) + " x " + std::to_string(Nc) + " doubles");
+    // the one division of ngp_grm_end (k_grm_mirror), without the ridge: it belongs to the diagonal of G
+    const double denom = R->dk->grm_method == 1 ? R->dk->grm_sum2pq : (double)P;
+    hipError_t e = hipSuccess;
+    if (!g.scaled) {  // (once: an end that fails further down leaves the prediction open and may be called again)
+        e = gpred_scale(g.Ct.get(), (long long)N, (long long)Nc, g.gcc.get(), denom, h->stream);
+        g.scaled = e == hipSuccess;
+    }
+    if (e == hipSuccess) e = backsolve_kw(R->dk->K.get(), (long long)R->dk->ld, (long long)N, g.Ct.get(), (long long)Nc, V.get(), cv.get(), h->stream);
+    if (e == hipSuccess) e = gpred_resid(g.Ct.get(), V.get(), (long long)N, (long long)Nc, g.gcc.get(), d_s.get(), h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("ngp_gpred_end: ") + hipGetErrorString(e));
+    V.reset(); cv.reset();
+    if (s) HCHK(hipMemcpy(s, d_s, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (gcc) HCHK(hipMemcpy(gcc, g.gcc, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (T >= 1) {
+        if (W.alloc_raw((size_t)N * (size_t)T) != hipSuccess || cw.alloc_raw((size_t)T) != hipSuccess || d_sum.alloc_raw((size_t)Nc) != hipSuccess ||
+            d_sumsq.alloc_raw((size_t)Nc) != hipSuccess || mu0.alloc_raw((size_t)Nc) != hipSuccess || d1.alloc_raw((size_t)Nc) != hipSuccess)
+            return fail(h, NGP_ERR_NOMEM, "W = K U of GBLUP prediction: " + std::to_string(N) + " x " + std::to_string(T) + " doubles");
+        e = backsolve_kw(R->dk->K.get(), (long long)R->dk->ld, (long long)N, R->bs.U.get(), (long long)T, W.get(), cw.get(), h->stream);
+        if (e == hipSuccess) e = gpred_fill(mu0.get(), (long long)Nc, 0.0, h->stream);
+        if (e == hipSuccess) e = gpred_fill(d1.get(), (long long)Nc, 1.0, h->stream);
+        if (e == hipSuccess) e = backsolve_project(g.Ct.get(), (long long)N, (long long)Nc, W.get(), (long long)T, cw.get(), mu0.get(), d1.get(), d_sum.get(), d_sumsq.get(), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("ngp_gpred_end: ") + hipGetErrorString(e));
+        if (sum) HCHK(hipMemcpy(sum, d_sum, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost));
+        if (sumsq) HCHK(hipMemcpy(sumsq, d_sumsq, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+        if (sum) std::fill(sum, sum + Nc, 0.0);
+        if (sumsq) std::fill(sumsq, sumsq + Nc, 0.0);
+    }
+    if (n) *n = T;
+    g.open = false;  // (C stays for ngp_gpred_get_cross)
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_gpred_abort(ngp_handle *h) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    HCHK(hipStreamSynchronize(h->stream));
+    h->gp = Gpred();
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+int32_t ngp_gpred_get_cross(ngp_handle *h, double *C_out, int64_t ld) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    const Gpred &g = h->gp;
+    REQUIRE(g.rset >= 0 && !g.open && g.Ct, NGP_ERR_STATE, "no complete relationship block on this handle (ngp_gpred_begin .. ngp_gpred_end)");
+    REQUIRE(C_out != nullptr, NGP_ERR_ARG, "null output pointer");
+    REQUIRE(ld >= g.N, NGP_ERR_ARG, "ngp_gpred_get_cross: a row of C holds N entries, ld is smaller");
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy2D(C_out, (size_t)ld * sizeof(double), g.Ct, (size_t)g.N * sizeof(double), (size_t)g.N * sizeof(double), (size_t)g.Nc, hipMemcpyDeviceToHost));
     return NGP_OK;
     NGP_CATCH(h)
 }

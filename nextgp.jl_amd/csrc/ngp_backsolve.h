@@ -35,6 +35,10 @@ struct BsCols {
     double *sum, *sumsq;      // the chunk's first column
 };
 hipError_t backsolve_columns(const BsCols &c, hipStream_t stream);
+// k_bs_cols over the rows of a relationship block in the place of genotype columns (ngp_gpred.h): Ct is N x Nc with leading dimension N,
+// mu0 holds Nc zeros and d1 Nc ones, so that sum[c] = sum_t m_ct and sumsq[c] = sum_t m_ct^2 with m_ct = sum_i Ct[i, c] W[i, t], k_bs_cols' chain
+hipError_t backsolve_project(const double *Ct, long long N, long long Nc, const double *W, long long T, const double *cw, const double *mu0, const double *d1,
+                             double *sum, double *sumsq, hipStream_t stream);
 
 #ifdef NGP_BACKSOLVE_KERNELS
 

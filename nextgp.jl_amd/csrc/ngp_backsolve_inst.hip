@@ -36,4 +36,11 @@ hipError_t backsolve_columns(const BsCols &c, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t backsolve_project(const double *Ct, long long N, long long Nc, const double *W, long long T, const double *cw, const double *mu0, const double *d1,
+                             double *sum, double *sumsq, hipStream_t stream) {
+    if (N < 1 || Nc < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bs_cols<double>, dim3((unsigned)((Nc + 63) / 64)), dim3(256), 0, stream, Ct, N, N, Nc, W, T, cw, mu0, d1, sum, sumsq);
+    return hipGetLastError();
+}
+
 }  // namespace ngp

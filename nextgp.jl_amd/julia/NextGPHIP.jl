@@ -834,6 +834,27 @@ function backsolve_draws(h::Handle, rset::Integer, q::Integer)
     check(h, ccall((:ngp_backsolve_get_draws, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{Int64}), h.ptr, rset, U, T))
     return U
 end
+# ---- GBLUP prediction (include/nextgp_hip.h): candidates from their genotypes after the run.  gpred_begin!, then the records' and the
+# candidates' genotype columns of the relationship matrix in its column order (gpred_columns!, every call but the last a multiple of 64
+# columns), gpred_end! -> (sum, sumsq, s, gcc, n) per candidate; gpred_cross -> C' (N x Nc: column c holds the relationships of candidate c).
+gpred_begin!(h::Handle, rset::Integer, Nc::Integer) = check(h, ccall((:ngp_gpred_begin, LIB), Int32, (Ptr{Cvoid}, Int32, Int64), h.ptr, rset, Nc))
+gpred_columns!(h::Handle, Zt::Matrix{Float64}, Zc::Matrix{Float64}) =
+    check(h, ccall((:ngp_gpred_columns_f64, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64), h.ptr, Zt, size(Zt, 1), Zc, size(Zc, 1), size(Zt, 2)))
+gpred_columns!(h::Handle, Zt::Matrix{Float32}, Zc::Matrix{Float32}) =
+    check(h, ccall((:ngp_gpred_columns_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Int64), h.ptr, Zt, size(Zt, 1), Zc, size(Zc, 1), size(Zt, 2)))
+gpred_columns!(h::Handle, Zt::Matrix{UInt8}, Zc::Matrix{UInt8}) =
+    check(h, ccall((:ngp_gpred_columns_u8, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt8}, Int64, Ptr{UInt8}, Int64, Int64), h.ptr, Zt, size(Zt, 1), Zc, size(Zc, 1), size(Zt, 2)))
+function gpred_end!(h::Handle, rset::Integer, Nc::Integer)
+    s1 = Vector{Float64}(undef, Nc); s2 = Vector{Float64}(undef, Nc); s = Vector{Float64}(undef, Nc); g = Vector{Float64}(undef, Nc); n = Ref{Int64}(0)
+    check(h, ccall((:ngp_gpred_end, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}), h.ptr, rset, s1, s2, s, g, n))
+    return s1, s2, s, g, n[]
+end
+function gpred_cross(h::Handle, N::Integer, Nc::Integer)
+    Ct = Matrix{Float64}(undef, N, Nc)
+    check(h, ccall((:ngp_gpred_get_cross, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, Ct, N))
+    return Ct
+end
+gpred_abort!(h::Handle) = check(h, ccall((:ngp_gpred_abort, LIB), Int32, (Ptr{Cvoid},), h.ptr))
 # ---- single-step GBLUP (include/nextgp_hip.h): H^-1 = A^-1 + [0 0; 0 inv((1 - w) G + w A22) - inv(A22)].  The reference has no single-step
 # model, so nothing of the coarse seam routes here: these are direct bindings for a caller that builds the model itself. ----
 # A22 = A[idx, idx] without the dense A (ngp_pedigree_a22: Colleau's indirect method on the host); F from pedigree_ainv, idx 0-based
