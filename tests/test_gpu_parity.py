@@ -38,9 +38,7 @@ def test_draws_bit_exact(dev, O, what, p1, p2):
     assert np.array_equal(got, exp)
 
 
-# (mode, lag[, near lags]): per-block launches / persistent sweep; near = 4 is what tall shards (R > 128) run with
-# (mode, lag[, near lags[, streamer variant]]): per-block launches / persistent sweep; near = 4 is what tall shards (R > 128) run
-# with; streamer 2 = row-owning waves + loader wave (7 GEMV chains; the default for shards of 132..224 rows, forced here)
+# (mode, lag[, near lags[, streamer variant]]): per-block launches / persistent sweep; streamer 2 = row-owning waves, forced here
 ENGINES = [(0, 1), (1, 1), (1, 2), (1, 3), (1, 4), (1, 6), (1, 8), (1, 5, 4), (1, 8, 4), (1, 3, 3, 2), (1, 4, 3, 2), (1, 5, 4, 2), (1, 6, 4, 2),
            (1, 8, 2), (1, 6, 2, 2), (1, 6, 1, 2), (1, 8, 1)]
 ENGINE_IDS = ["blocklaunch", "persist_lag1", "persist_lag2", "persist_lag3", "persist_lag4", "persist_lag6", "persist_lag8",
