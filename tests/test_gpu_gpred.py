@@ -51,6 +51,16 @@ def _typed(A, kind):
     return np.asfortranarray(A.astype(DTYPES[kind]))
 
 
+def parity_bounds(ref, n, p, T):
+    """The module's bound for C, gcc, s, sum and sumsq of n records, p columns and T draws, from the absolute sums of ref_gpred.reference
+    (tests/test_gpu_gblup_edges.py imports it for its own shapes)."""
+    c = 8.0 * (p + 2 * n) * EPS
+    bm = c * (ref["A"] @ ref["B"])                                   # per (candidate, draw)
+    return dict(C=c * ref["A"], gcc=c * ref["gcc"], s=c * (ref["gcc"] + ref["AKA"]),
+                sum=bm.sum(axis=1) + T * EPS * np.abs(ref["m"]).sum(axis=1),
+                sumsq=((2 * np.abs(ref["m"]) + bm) * bm).sum(axis=1) + (T + 1) * EPS * (ref["m"] ** 2).sum(axis=1))
+
+
 @gpu
 @pytest.mark.parametrize("kind,method,Nc", [(k, m, c) for k in ("f64", "u8") for m in (1, 2) for c in (1, 65)] + [("f32", 1, 65)])
 def test_rows_of_G_bit_for_bit(ngp, kind, method, Nc):
@@ -102,11 +112,7 @@ def test_parity_and_the_two_device_paths(ngp, kind, method, Nc, T):
     r = f["s"].gblup_predict(0, _typed(f["Z"], kind), _typed(Zc, kind), splits=[64])
     Cd = f["s"].gblup_cross()
     ref = reference(f["Z"], Zc, f["K"], f["U"], method)
-    c = 8.0 * (P + 2 * N) * EPS
-    bm = c * (ref["A"] @ ref["B"])                                   # per (candidate, draw)
-    tol = dict(C=c * ref["A"], gcc=c * ref["gcc"], s=c * (ref["gcc"] + ref["AKA"]),
-               sum=bm.sum(axis=1) + T * EPS * np.abs(ref["m"]).sum(axis=1),
-               sumsq=((2 * np.abs(ref["m"]) + bm) * bm).sum(axis=1) + (T + 1) * EPS * (ref["m"] ** 2).sum(axis=1))
+    tol = parity_bounds(ref, N, P, T)
     got = dict(C=Cd, gcc=r["gcc"], s=r["s"], sum=r["sum"], sumsq=r["sumsq"])
     frac = {k: float(np.max(np.abs(got[k].astype(L) - ref[k]) / tol[k])) for k in tol}
     print("worst error / bound:", {k: f"{v:.3g}" for k, v in frac.items()})

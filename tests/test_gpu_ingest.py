@@ -23,13 +23,13 @@ import pytest
 import ref_gblup as RG
 import ref_predict as RP
 from conftest import add_sets
+from layout_helpers import PAD, padded, short_buffer
 
 gpu = pytest.mark.gpu                        # every test but the wrapper's stride check needs the device
 
 EPS = 2.0 ** -53
 N, P = 333, 330                              # five full 64-column blocks and a partial one; N % 4 = 1 (two-bit columns end mid-byte)
 CALLS = ((130, 330), (0, 57), (57, 130))     # boundaries inside blocks, out of order
-PAD = 43
 NP_ = 70                                     # prediction individuals
 SPEC = [(0, 100, "PR"), (100, 230, "R")]     # one BayesPR and one BayesR set, split at column 100
 SETS = [(0, 100), (100, 230)]
@@ -103,29 +103,6 @@ def assert_same_summary(a, b):
     assert a["layout"] == b["layout"]
     for k in ("means", "mpm", "gram"):
         assert np.array_equal(a[k], b[k]), k
-
-
-def padded(V, fill_rows=PAD):
-    """V on top of `fill_rows` rows that must never be read as genotypes: NaN and inf (255 for codes)."""
-    big = np.empty((V.shape[0] + fill_rows, V.shape[1]), dtype=V.dtype, order="F")
-    big[:V.shape[0]] = V
-    if V.dtype == np.uint8:
-        big[V.shape[0]:] = 255
-    else:
-        big[V.shape[0]::2] = np.nan
-        big[V.shape[0] + 1::2] = np.inf
-    view = big[:V.shape[0]]
-    assert view.strides == (V.itemsize, (V.shape[0] + fill_rows) * V.itemsize) and not view.flags.f_contiguous
-    return view
-
-
-def short_buffer(V, ld):
-    """The C contract's short form: ncol - 1 columns of ld elements and a last one of N, not an element more; NaN (255) between."""
-    n, ncol = V.shape
-    flat = np.full((ncol - 1) * ld + n, 255 if V.dtype == np.uint8 else np.nan, dtype=V.dtype)
-    for j in range(ncol):
-        flat[j * ld:j * ld + n] = V[:, j]
-    return flat
 
 
 def new_sampler(ngp, storage=None, weights=None, seed=1):
