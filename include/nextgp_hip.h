@@ -575,6 +575,42 @@ int32_t ngp_grm_invert(ngp_handle *h);
 int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q, const double *K, ngp_handle *k_src, int32_t k_src_set,
                                  double df, double scale, double varU0, int32_t *set_id);
 
+/* ---- GBLUP at scale: the APY form of inv(G) (algorithm for proven and young) ----
+ * The dense set above costs 8 N^2 bytes of K and N / 64 dependent launches per iteration.  APY replaces inv(G) by a structured
+ * precision: the levels are numbered core first (0 .. nc - 1), every other animal conditions on the core only.  With G VanRaden's matrix
+ * exactly as ngp_grm_* build it (method 1 or 2, the 0.001 on the diagonal, column statistics over all N animals):
+ *   Kc0 = inv(Gcc);  P = Gnc Kc0 (nn x nc, nn = N - nc);  m_i = g_ii - P_i. (Gnc)_i.;  d_i = 1 / m_i;  Kcc = Kc0 + P' diag(d) P;
+ *   K_APY = [Kcc, -P'D; -DP, D].
+ * The N x N matrix is never held: the builder keeps the N x nc column panel G[:, 0:nc] and the diagonal.
+ *
+ * ngp_grm_begin_apy: ngp_grm_begin with a core, 1 <= nc <= N and nc <= 8192 (the non-core pass keeps a core-long vector in registers:
+ * csrc/ngp_apy.h states the budget); else NGP_ERR_ARG.  ngp_grm_columns_* and ngp_grm_end serve the builder as they serve ngp_grm_begin,
+ * with the same refusals; ngp_grm_get, ngp_grm_invert and ngp_grm_single_step refuse it (NGP_ERR_STATE).  With nc == N the panel is G.
+ * ngp_grm_apy: after ngp_grm_end, the analogue of ngp_grm_invert.  Kc0 by the same rocSOLVER path with the same error behaviour; P and
+ * Kcc on the matrix cores in fp64; Kcc mirrored, exactly symmetric.  A level with m_i <= 0 is NGP_ERR_ARG naming the level (the form
+ * is dropped).  The column panel is released.
+ * ngp_grm_get_apy: a piece to the host, row-major.  set_id < 0: of this handle's complete form; else of the APY set set_id.
+ * which: 0 P (nn x nc), 1 m (nn), 2 Kcc (nc x nc), 3 Kc0 (nc x nc), 4 d (nn); of a set also 5 the seed s = -P' D u_n (nc) as the next
+ * sweep will take it and 6 u'Ku as the last step formed it (one double).
+ * ngp_add_random_set_apy: a random-effect set over the form, q = N levels of which the first nc are the core.  k_src == NULL: this
+ * handle's own form (ngp_grm_apy), which the set takes over; else the form of the APY set k_src_set of ANOTHER handle on the same device,
+ * by reference and read-only, as ngp_add_random_set_dense shares a K.  Everything ngp_add_random_set_dense says about levels, df, scale,
+ * varU0, the sampling order, the draw keys, weighted residuals, ngp_get_random / ngp_set_random / ngp_sample_random_set, the packed
+ * posterior, sample files and snapshots holds here too.  One step is the reference's sampleU over K_APY in level order: the core levels by
+ * the blocked chain over Kcc, whose below-block accumulator starts from the seed s; then all non-core levels in ONE pass over P
+ * (k_apy_tail: v_i = P_i. u_c, rhs = Yi_i + iVarU d_i v_i, lhs = zpz_i iVarE + d_i iVarU, the draw, and s for the next sweep); then
+ * u'Ku = u_c' Kc0 u_c + sum_i d_i (u_i - v_i)^2 and varU as any set draws it (df + N).  With nc == N the set is, bit for bit, the dense
+ * set over ngp_grm_invert of the same G.  The seed is derived state: it is formed again from u whenever u no longer is the vector it
+ * was formed from (ngp_set_random, a snapshot, ngp_set_y).  Results are identical run to run and do not depend on the device: the
+ * rows of P go to workgroups by (nn, a compile-time constant), partial sums are added in workgroup order, no floating-point atomics, no
+ * FMA ("APY random-effect sets": the normative orders).  The model signature digests the level coding, nc, P, Kcc
+ * and d, hashed on the device.  The SNP back-solve and GBLUP prediction refuse an APY set: they multiply by the dense K. */
+int32_t ngp_grm_begin_apy(ngp_handle *h, int64_t N, int64_t nc, int32_t method);
+int32_t ngp_grm_apy(ngp_handle *h);
+int32_t ngp_grm_get_apy(ngp_handle *h, int32_t set_id, int32_t which, double *out);
+int32_t ngp_add_random_set_apy(ngp_handle *h, const int32_t *level, int64_t q, int64_t nc, ngp_handle *k_src, int32_t k_src_set, double df,
+                               double scale, double varU0, int32_t *set_id);
+
 /* ---- SNP effects from GBLUP: every kept draw of the breeding values solved back to the markers ----
  * A dense set whose K = inv(G) was built here (ngp_grm_begin .. ngp_grm_invert, K == NULL above, or k_src of such a set) knows how G was
  * formed from the genotype columns Z: with w_t = K u_t,  beta_{j,t} = d_j sum_i (z_ij - mu_j) w_{i,t},  mu_j = 2 p_j,

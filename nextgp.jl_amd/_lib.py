@@ -233,6 +233,7 @@ SYMBOLS = [
     "ngp_add_marker_set_lv", "ngp_get_lv_state", "ngp_set_lv_state",
     "ngp_grm_begin", "ngp_grm_columns_f64", "ngp_grm_columns_f32", "ngp_grm_columns_u8", "ngp_grm_end", "ngp_grm_get", "ngp_grm_invert",
     "ngp_add_random_set_dense", "ngp_set_records",
+    "ngp_grm_begin_apy", "ngp_grm_apy", "ngp_grm_get_apy", "ngp_add_random_set_apy",
     "ngp_backsolve_enable", "ngp_backsolve_get_draws", "ngp_backsolve_begin", "ngp_backsolve_columns_f64", "ngp_backsolve_columns_f32",
     "ngp_backsolve_columns_u8", "ngp_backsolve_end",
     "ngp_gpred_begin", "ngp_gpred_columns_f64", "ngp_gpred_columns_f32", "ngp_gpred_columns_u8", "ngp_gpred_end", "ngp_gpred_get_cross", "ngp_gpred_abort",
@@ -1101,6 +1102,48 @@ class Sampler:
 
     def grm_invert(self):
         self._chk(self.L.ngp_grm_invert(self.h))
+
+    # ---- GBLUP at scale: the APY form (include/nextgp_hip.h, "GBLUP at scale") ----------------
+    APY_PIECES = {"P": 0, "m": 1, "Kcc": 2, "Kc0": 3, "d": 4, "s": 5, "uKu": 6}
+
+    def grm_begin_apy(self, N, nc, method=1):
+        """grm_begin with a core: the first nc of the N animals.  grm_columns / grm_end then build only G[:, 0:nc] and the diagonal."""
+        self._chk(self.L.ngp_grm_begin_apy(self.h, C.c_int64(int(N)), C.c_int64(int(nc)), C.c_int32(int(method))))
+        self.grm_N, self.grm_method, self.grm_nc = int(N), int(method), int(nc)
+
+    def grm_apy(self):
+        """After grm_end, in place of grm_invert: Kc0 = inv(Gcc), P, m and Kcc of the APY form (add_random_set_apy takes it over)."""
+        self._chk(self.L.ngp_grm_apy(self.h))
+
+    def grm_get_apy(self, which=None, rset=None):
+        """Pieces of this sampler's APY form (rset None) or of the APY set rset: one of "P" (nn x nc), "m", "d" (nn), "Kcc", "Kc0"
+        (nc x nc), and of a set "s" (nc) and "uKu" (the quadratic form of its last step); which None: a dict of the form's five."""
+        if which is None:
+            return {k: self.grm_get_apy(k, rset) for k in ("P", "m", "d", "Kcc", "Kc0")}
+        N, nc = (self.grm_N, self.grm_nc) if rset is None else self.rand_apy[int(rset)]
+        nn = N - nc
+        out = np.zeros({"P": (nn, nc), "m": (nn,), "d": (nn,), "Kcc": (nc, nc), "Kc0": (nc, nc), "s": (nc,), "uKu": (1,)}[which])
+        buf = out if out.size else np.zeros(1)
+        self._chk(self.L.ngp_grm_get_apy(self.h, C.c_int32(-1 if rset is None else int(rset)), C.c_int32(self.APY_PIECES[which]), _p(buf, C.c_double)))
+        return float(out[0]) if which == "uKu" else out
+
+    def add_random_set_apy(self, level, q, nc, K=None, df=4.0, scale=None, varU0=100.0):
+        """Random-effect set over the APY form of inv(G): q levels, the first nc the core; the core runs the blocked chain, all other
+        levels are drawn in one pass over P.  K: None to take over this sampler's own form (grm_apy), or (other_sampler, set_id) to
+        share that APY set's form by reference.  Everything else as add_random_set_dense; returns the set id."""
+        lv = None if level is None else np.ascontiguousarray(level, dtype=np.int32)
+        if scale is None:
+            scale = varU0 * (df - 2.0) / df
+        src, src_set = (K[0].h, int(K[1])) if isinstance(K, tuple) else (None, 0)
+        if K is not None and not isinstance(K, tuple):
+            raise ValueError("K: (other_sampler, set_id) or None")
+        sid = C.c_int32()
+        self._chk(self.L.ngp_add_random_set_apy(self.h, _p(lv, C.c_int32), C.c_int64(int(q)), C.c_int64(int(nc)), src, C.c_int32(src_set),
+                                                C.c_double(df), C.c_double(scale), C.c_double(varU0), C.byref(sid)))
+        self.rand_q = getattr(self, "rand_q", []) + [int(q)]
+        self.rand_apy = getattr(self, "rand_apy", {})
+        self.rand_apy[sid.value] = (int(q), int(nc))
+        return sid.value
 
     def grm_single_step(self, A22, w=0.05):
         """After grm_end, in place of grm_invert: the matrix becomes D = inv((1 - w) G + w A22) - inv(A22), the dense corner of single-step

@@ -519,19 +519,65 @@ def gblup_terms(snps, VCV, summaryStat=None):
 GRM_COLUMNS_PER_CALL = 4096  # columns handed to the GRM builder per call (a multiple of 64: the result does not depend on the split)
 
 
-def _grm_build(smp, M, method):
-    """G of the raw genotypes M (N x P, any dtype read_genotypes returns) on smp's device, in column ranges: no concatenated host copy."""
+def _grm_build(smp, M, method, nc=None):
+    """G of the raw genotypes M (N x P, any dtype read_genotypes returns) on smp's device, in column ranges: no concatenated host copy.
+    nc: only the column panel of the first nc animals and the diagonal (the APY builder)."""
     N, P = M.shape
-    smp.grm_begin(N, method)
+    if nc is None:
+        smp.grm_begin(N, method)
+    else:
+        smp.grm_begin_apy(N, nc, method)
     for c0 in range(0, P, GRM_COLUMNS_PER_CALL):
         smp.grm_columns(M[:, c0:c0 + GRM_COLUMNS_PER_CALL])
     smp.grm_end()
 
 
-def makeG(M, method=1, device=0):
+def apy_order(N, core, apySeed=1):
+    """The APY level order of N animals, core first: core is a count (drawn without replacement by np.random.default_rng(apySeed),
+    kept in ascending order) or a list of 0-based indices (in the order given); the other animals follow in ascending order.
+    Returns (order, nc): level l is animal order[l]."""
+    if np.ndim(core) == 0:
+        nc = int(core)
+        if not 1 <= nc <= N:
+            raise ValueError(f"apy: a core of {nc} animals out of {N}")
+        idx = np.sort(np.random.default_rng(apySeed).choice(N, size=nc, replace=False))
+    else:
+        idx = np.asarray(core, dtype=np.int64)
+        if idx.ndim != 1 or len(idx) < 1 or len(set(idx.tolist())) != len(idx) or idx.min() < 0 or idx.max() >= N:
+            raise ValueError("apy: the core is a non-empty list of distinct 0-based indices below N")
+    rest = np.setdiff1d(np.arange(N), idx)
+    return np.concatenate([idx, rest]), len(idx)
+
+
+def apy_terms(apy, VCV, parsed, snpEffects=False, predict=None):
+    """{term: core} of runLMEM's apy= after its refusals (host only).  apy applies to a SNP term whose prior is Random("G", v); the paths
+    that multiply by the dense K are not built for it."""
+    out = {}
+    for key, core in dict(apy or {}).items():
+        if isinstance(key, tuple):
+            raise NotImplementedError(f"apy[{key!r}]: APY inside a correlated (Tuple) random effect; an APY set has one component")
+        if any(isinstance(k, tuple) and key in k for k in VCV):
+            raise NotImplementedError(f"apy[{key!r}]: the term is a member of the tuple key {[k for k in VCV if isinstance(k, tuple) and key in k][0]}; "
+                                      "an APY set has one component")
+        prior = VCV.get(key)
+        if isinstance(prior, RandomEffectType) and isinstance(prior.str, str) and prior.str == "H":
+            raise NotImplementedError(f"apy[{key!r}]: APY inside single-step H is not built (the genotyped corner of H^-1 is a dense block)")
+        if key not in {t.name for t in parsed[2]} or not (isinstance(prior, RandomEffectType) and isinstance(prior.str, str) and prior.str == "G"):
+            raise ValueError(f"apy[{key!r}]: apy applies to a SNP term whose prior is Random(\"G\", v)")
+        if snpEffects is True or (snpEffects and key in [str(a) for a in snpEffects]):
+            raise NotImplementedError(f"apy[{key!r}] with snpEffects=: the SNP back-solve multiplies by the dense K = inv(G), which an APY set never holds")
+        if predict is not None and (not hasattr(predict, "keys") or key in predict):
+            raise NotImplementedError(f"apy[{key!r}] with predict=: GBLUP prediction multiplies by the dense K = inv(G), which an APY set never holds")
+        out[key] = core
+    return out
+
+
+def makeG(M, method=1, device=0, core=None, apySeed=1):
     """VanRaden's genomic relationship matrix (src/misc.jl:145-160), built on the device in fp64 (matrix cores), returned as numpy.
     M: raw allele counts, N x P (uint8, float32 and float64 give the same bits on equal values).  Unlike the reference, M is not centred
-    in place, and method 2 refuses a monomorphic column instead of filling G with NaN."""
+    in place, and method 2 refuses a monomorphic column instead of filling G with NaN.
+    core (a count or a list of 0-based indices: apy_order): the APY form of inv(G) instead, never holding N x N -- a dict of "P", "m",
+    "d", "Kcc", "Kc0" over the levels in "order" (core first) with "nc" core animals; K_APY = [Kcc, -P'D; -DP, D]."""
     if method not in (1, 2):
         raise ValueError("enter a valid method")
     M = np.asarray(M)
@@ -539,6 +585,11 @@ def makeG(M, method=1, device=0):
         raise ValueError("makeG: an N x P genotype matrix")
     smp = Sampler(device=device)
     try:
+        if core is not None:
+            order, nc = apy_order(M.shape[0], core, apySeed)
+            _grm_build(smp, M[order], method, nc)
+            smp.grm_apy()
+            return dict(smp.grm_get_apy(), order=order, nc=nc)
         _grm_build(smp, M, method)
         return smp.grm_get()
     finally:
@@ -1167,7 +1218,7 @@ def samples_to_out_files(sample_path, outFolder, sets, intercept, has_fixed, ran
 def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=None, outFolder="outMCMC", VCV=None, userPedData=None,
             summaryStat=None, seed=1, chain=0, device=0, samples="text", overwrite=False, engine=None, storage=None, chains=1, max_shards=None,
             predict=None, predict_ids=None, windows=None, windowThreshold=0.01, genomicVariance=False, holdout=None, missing="error", folds=None,
-            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1, sparseFixed="auto", snpEffects=False):
+            foldSeed=1, trait="gaussian", censored=None, thresholdStep="albert-chib", classProb=False, singleStep=None, diagnostics=False, genoID=None, missingGeno=None, alleleCount=1, sparseFixed="auto", snpEffects=False, apy=None, apySeed=1):
     """Runs the chain on the GPU and writes the reference's *Out files.
 
     Differences from the reference, all deliberate: (1) `seed`/`chain` key the random streams (the reference never
@@ -1242,6 +1293,11 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     res["cv"]["prob"] (N x C, NaN where not validated), "brier", "logloss", "class_accuracy" (arg-max class) and, for two classes,
     "auc" (class_metrics), each also in every entry of "per_fold", and cvProb.txt: record fold class p1 .. pC (records from 1, fold -1
     and class 0 where there is none).  holdoutPredict.txt and cvPredict.txt keep their columns.
+    APY GBLUP (ngp_grm_begin_apy .. ngp_add_random_set_apy; DESIGN.md section 2, "APY random-effect sets"): apy={"M1": core} on a SNP term
+    whose prior is Random("G", v) samples the term over the APY form of inv(G) -- N x N is never built.  core: a count, drawn without
+    replacement by np.random.default_rng(apySeed), or a list of 0-based record indices (apy_order).  The levels are renumbered core first;
+    uM1Out and res["random"]["M1"]["levels"] carry the animals' names (Ind<record>) in the new order.  apy= on an "H" term, inside a tuple
+    key, or together with snpEffects= or a GBLUP predict= on that term: NotImplementedError (those paths multiply by the dense K).
     (13) single-step GBLUP (ngp_grm_single_step / ngp_add_random_set_hybrid; DESIGN.md section 2, "Hybrid random-effect sets"): a
     PED(col) term with VCV={col: Random("H", v, type=1|2)} and singleStep={col: {"geno": path | array, "ids": [...], "w": 0.05}} has one
     breeding value per animal of the pedigree over H^-1 = A^-1 + [0 0; 0 inv((1 - w) G + w A22) - inv(A22)]; ids names the genotyped
@@ -1345,6 +1401,7 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
     os.makedirs(outFolder, exist_ok=True)
     # prep: SNP branch (src/prepMatVec.jl:113-134); marker sets become consecutive column ranges of ONE panel.  A term whose prior is
     # Random("G", v) is GBLUP (:122-126): its genotypes go to the GRM builder, never into the panel
+    apy_cores = apy_terms(apy, VCV, parsed, snpEffects, predict)   # (checked before any device work)
     gb_names = gblup_terms(snps, VCV, summaryStat)
     geno_ids = None if genoID is None else [str(a) for a in np.asarray(userData[genoID]).tolist()]
     mats_all = [_genotype_source(t.path, geno_ids, alleleCount, missingGeno) for t in snps]
@@ -1360,6 +1417,8 @@ def runLMEM(formula, userData, nChain, nBurn, nThin, myHints=None, blockThese=No
         if M.shape[0] != len(y):
             raise ValueError("genotype rows must match the phenotype records (marker files are ordered as the data, runTime.jl:23)")
     gblup = {t.name: dict(M=M, prior=VCV[t.name]) for t, M in zip(snps, mats_all) if t.name in gb_names}
+    for nm, core in apy_cores.items():   # the APY level order of the term's animals, core first (one order for all chains)
+        gblup[nm]["apy"] = apy_order(len(y), core, apySeed)
     snp_fx = _snp_effects_terms(snpEffects, gb_names, [t.name for t in snps], nChain, nBurn, nThin, folds)   # (checked before any device work)
     mats = [M for t, M in zip(snps, mats_all) if t.name not in gb_names]
     snps = [t for t in snps if t.name not in gb_names]
@@ -2167,6 +2226,19 @@ def _build_model(smp, VCV, summaryStat, parsed, userData, blockThese, intercept,
             prior, N = gblup[g]["prior"], len(y)
             rdf = 3.0 + 1.0                                          # src/mme.jl:261
             v = float(prior.v)
+            if "apy" in gblup[g]:   # the APY form over the renumbered animals: level l is record order[l], the files carry the records' names
+                order, nc = gblup[g]["apy"]
+                if k_owner is None:
+                    _grm_build(smp, gblup[g]["M"][order], prior.type, nc)
+                    smp.grm_apy()
+                    Ksrc = None
+                else:
+                    Ksrc = (k_owner, [rd["id"] for rd in k_owner.randoms if rd.get("key") == g][0])
+                level = np.empty(N, dtype=np.int32)
+                level[order] = np.arange(N, dtype=np.int32)
+                rid = smp.add_random_set_apy(level, N, nc, K=Ksrc, df=rdf, scale=v * (rdf - 2.0) / rdf, varU0=v)
+                smp.randoms.append(dict(id=rid, g=g, key=g, levels=[f"Ind{i + 1}" for i in order], q=N, files=(f"u{g}", f"varU{g}", g)))
+                continue
             if k_owner is None:   # G on the matrix cores, inverted on the device, handed to the set without a copy
                 _grm_build(smp, gblup[g]["M"], prior.type)
                 smp.grm_invert()

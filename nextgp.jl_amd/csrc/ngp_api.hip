@@ -32,6 +32,7 @@
 #include "ngp_fixed_sparse.h"
 #include "ngp_random_tuple.h"
 #include "ngp_dense.h"
+#include "ngp_apy.h"
 #include "ngp_hybrid.h"
 #include "ngp_logvar.h"
 #include "ngp_predict.h"
@@ -117,6 +118,7 @@ struct DenseK {
     double grm_sum2pq = 0.0;
 };
 
+struct ApyK;
 // The genomic relationship matrix under construction (ngp_grm_begin .. ngp_grm_invert): column-major with leading dimension ld = N
 // rounded up to 64, rows and columns beyond N zero.  state: 1 columns may arrive, 2 G complete (ngp_grm_end), 3 inverted, 4 the corner
 // block D = G_w^-1 - A22^-1 of single-step GBLUP (ngp_grm_single_step).
@@ -125,6 +127,18 @@ struct Grm {
     int state = 0, method = 1;
     int64_t N = 0, ncols = 0;
     double sum2pq = 0.0;  // method 1: sum of 2 p q over the columns so far, in column order
+    // ngp_grm_begin_apy: m->K is the N x nc column panel G[:, 0:nc] (column-major, leading dimension m->ld, nc rounded up to 64 columns)
+    // and gdiag the diagonal of G; state 5: the APY form is complete (ngp_grm_apy), the panel is gone
+    int64_t nc = 0;  // > 0: an APY builder
+    DevArray<double> gdiag;
+    std::shared_ptr<ApyK> ak;
+};
+
+// The APY form of inv(G) on the device (ngp_apy.h): read-only once a set uses it; sets of several handles may share it.
+struct ApyK {
+    int64_t N = 0, nc = 0, nn = 0, nnpad = 0, ldp = 0, ldk = 0;  // P: nnpad x ldp row-major (zeros beyond nn and nc); Kc0, Kcc: ldk x ldk
+    DevArray<double> P, m, d, Kc0, Kcc, kdiag0, kdiag;           // kdiag: diag(Kcc) | d, the N diagonal entries of the precision
+    uint64_t digest = 0;  // of P, Kcc and d (apy_digest_all, once, when a set first takes the form)
 };
 
 struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled after the fixed-effect sets (src/samplers.jl:43-46)
@@ -151,6 +165,11 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     // T = D + S_tt over the levels hd .. q - 1; the level schedule covers the head rows 0 .. hd - 1
     bool hyb = false;
     int64_t hd = 0;
+    // an APY set (ngp_add_random_set_apy, ngp_apy.h): the shared form, and the set's own seed s (nc), the workgroups' partials of s and
+    // of the tail's quadratic term, quad = [the tail's term, u'Ku of the last step], the u_n that s was formed from, the stale word
+    std::shared_ptr<ApyK> apy;
+    DevArray<double> d_as, d_aspart, d_aqpart, d_aquad, d_auprev;
+    DevArray<unsigned> d_astale;
     // the level schedule of a CSR K with off-diagonal entries (ngp_random.h, k_rand_sched_*): rows sorted by (depth, row), and the launches
     struct Launch { int wide; int d0, d1; long long r0, r1; };  // wide: the rows order[r0 .. r1) of depth d0; else the depths d0 .. d1 - 1 in one workgroup
     DevArray<int> d_order;
@@ -1450,6 +1469,36 @@ void launch_random(ngp_handle *h, int r, uint64_t it) {
                            (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), ab);
         hipLaunchKernelGGL(k_hyb_var, dim3(1), dim3(1024), 0, h->stream, q, hd, kp, kc, kv, (const double *)R.d_kdiag, (const double *)R.d_u,
                            (const double *)R.d_scr, R.d_vu, R.df, R.sdf, r, h->seed, (uint64_t)h->chain, it, ab);
+        return;
+    }
+    if (R.apy) {  // the APY form (ngp_apy.h): the seeded blocked chain over the nc core levels, then one pass over P for all the others
+        const ApyK &A = *R.apy;
+        const long long nc = (long long)A.nc, ld = (long long)A.ldk;
+        const double *Kcc = A.Kcc;
+        const unsigned *ab = (const unsigned *)h->cm.d_abort;
+        double *scr = R.d_scr;
+        ApyStep a;
+        a.q = q; a.nc = nc; a.ldp = (long long)A.ldp; a.ldk = ld;
+        a.P = A.P; a.d = A.d; a.Kc0 = A.Kc0; a.kdiag0 = A.kdiag0;
+        a.u = R.d_u; a.vu = R.d_vu;
+        a.Yi = scr + NGP_RS_YI * q; a.inv = scr + NGP_RS_INV * q; a.tz = scr + NGP_RS_TZ * q;
+        a.du = scr + NGP_RS_DU * q; a.acc = scr + NGP_RS_ACC * q; a.acc0 = scr + NGP_RS_ACC0 * q; a.seed = scr + NGP_RS_SEED * q; a.dlo = scr + NGP_RS_DLO * q;
+        a.s = R.d_as; a.spart = R.d_aspart; a.qpart = R.d_aqpart; a.quad = R.d_aquad; a.uprev = R.d_auprev; a.stale = R.d_astale; a.abort_w = ab;
+        hipLaunchKernelGGL(k_rand_levels, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, h->stream, (const double *)h->cm.d_ycorr, (const double *)h->cm.d_rs, q,
+                           (const long long *)R.d_lptr, (const int *)R.d_lrows, (const double *)R.d_zpz, (const double *)R.d_kdiag,
+                           (const long long *)nullptr, (const int *)nullptr, (const double *)nullptr, R.d_u, (const double *)R.d_vu, R.d_scr, 1,
+                           (const DScal *)h->cm.d_scal, r, h->seed, (uint64_t)h->chain, it, ab);
+        hipLaunchKernelGGL(k_hyb_dhi, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, h->stream, Kcc, ld, nc, (const double *)R.d_u, scr, q, ab);
+        (void)apy_seed(a, h->stream);
+        for (long long t = 0; t * 64 < nc; t++) {
+            const long long below = nc - 64 * t - 64;
+            const unsigned nwg = below > 0 ? (unsigned)((below + NGP_DENSE_WG_ROWS - 1) / NGP_DENSE_WG_ROWS) : 1u;
+            hipLaunchKernelGGL(k_hyb_block, dim3(nwg), dim3(256), 0, h->stream, Kcc, ld, nc, (int)t, R.d_u.get(), (const double *)R.d_vu, scr, q, ab);
+        }
+        (void)apy_tail(a, h->stream);
+        hipLaunchKernelGGL(k_rand_update, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->cm.d_ycorr, (const double *)h->cm.d_rs, (long long)h->N,
+                           (const int *)R.d_level, (const double *)(R.d_scr + NGP_RS_DU * q), ab);
+        (void)apy_var(a, R.d_vu, R.df, R.scale, r, h->seed, (uint64_t)h->chain, it, h->stream);
         return;
     }
     if (R.dk) {  // dense K: the blocked engine (ngp_dense.h), one launch per block of 64 levels between the level terms and the ycorr update
@@ -5177,7 +5226,7 @@ int32_t ngp_set_random_schedule(ngp_handle *h, int32_t set_id, int32_t mode) {
     REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     REQUIRE(mode >= 0 && mode <= 2, NGP_ERR_ARG, "random-effect schedule: 0 automatic, 1 serial, 2 level-scheduled");
     HRand &R = h->mm.rnd[(size_t)set_id];
-    REQUIRE(R.hyb ? R.hd > 0 : (!R.dk && R.offdiag), NGP_ERR_ARG,
+    REQUIRE(R.hyb ? R.hd > 0 : (!R.dk && !R.apy && R.offdiag), NGP_ERR_ARG,
             "random-effect schedule: only a CSR set whose K has off-diagonal entries, or a hybrid set with head rows, runs a Gauss-Seidel engine "
             "(a diagonal K draws every level on its own, a dense K runs the blocked engine)");
     R.sched_mode = mode;
@@ -5193,9 +5242,9 @@ int32_t ngp_get_random_schedule(ngp_handle *h, int32_t set_id, int32_t *engine, 
     if ((rc = enter(h))) return rc;
     REQUIRE(set_id >= 0 && set_id < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, "unknown random-effect set id");
     const HRand &R = h->mm.rnd[(size_t)set_id];
-    const bool gs = R.hyb ? R.hd > 0 : (!R.dk && R.offdiag);  // (a hybrid set: the engine, depths and launches of its head rows)
+    const bool gs = R.hyb ? R.hd > 0 : (!R.dk && !R.apy && R.offdiag);  // (a hybrid set: the engine, depths and launches of its head rows)
     if (engine) *engine = !gs ? 0 : R.scheduled() ? 2 : 1;
-    if (depths) *depths = gs ? R.ndepth : R.dk ? 0 : 1;
+    if (depths) *depths = gs ? R.ndepth : (R.dk || R.apy) ? 0 : 1;
     if (launches) *launches = !gs ? 0 : R.scheduled() ? (int64_t)R.plan.size() : 1;
     return NGP_OK;
     NGP_CATCH(h)
@@ -5636,8 +5685,12 @@ int grm_columns(ngp_handle *h, const TIn *M, int64_t ncol, int64_t ld) {
                                                 " (0-based, counted over all calls) is monomorphic: 2 p (1 - p) = 0 divides 0 by 0 (src/misc.jl:152-154)");
         }
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_grm_syrk, dim3(nb64, nb64), dim3(256), 0, h->stream, (const double *)d_xc, (long long)Npad, (long long)cpad, g.m->K.get());
-            e = hipStreamSynchronize(h->stream);  // the staging buffers are reused by the next chunk
+            // (an APY builder: only the core's column tiles of the lower triangle, G[:, 0:nc], and the diagonal of G by row norms)
+            const unsigned ncb64 = g.nc > 0 ? (unsigned)((g.nc + 63) / 64) : nb64;
+            hipLaunchKernelGGL(k_grm_syrk, dim3(nb64, ncb64), dim3(256), 0, h->stream, (const double *)d_xc, (long long)Npad, (long long)cpad, g.m->K.get());
+            if (g.nc > 0) e = apy_rownorm(d_xc, (long long)Npad, (long long)N, (long long)cpad, g.gdiag, h->stream);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(h->stream);  // the staging buffers are reused by the next chunk
         }
         if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("relationship matrix columns: ") + hipGetErrorString(e));
         if (g.method == 1) for (int64_t c = 0; c < nc; c++) sum2pq = sum2pq + tp[(size_t)c];
@@ -5715,8 +5768,12 @@ int32_t ngp_grm_end(ngp_handle *h) {
         return fail(h, NGP_ERR_ARG, "relationship matrix, method 1: the sum of 2 p (1 - p) over the columns is not positive (every column monomorphic?): "
                                     "G would be 0 / 0 (src/misc.jl:150); the matrix is dropped");
     }
-    const unsigned gy = (unsigned)std::min<int64_t>(g.N, 65535);
-    hipLaunchKernelGGL(k_grm_mirror, dim3((unsigned)((g.N + 255) / 256), gy), dim3(256), 0, h->stream, g.m->K.get(), (long long)g.N, (long long)g.m->ld, 1, denom);
+    if (g.nc > 0) {  // an APY builder: the same division and ridge over the column panel and the diagonal
+        HCHK(apy_finish(g.m->K.get(), (long long)g.N, (long long)g.m->ld, (long long)g.nc, g.gdiag, denom, h->stream));
+    } else {
+        const unsigned gy = (unsigned)std::min<int64_t>(g.N, 65535);
+        hipLaunchKernelGGL(k_grm_mirror, dim3((unsigned)((g.N + 255) / 256), gy), dim3(256), 0, h->stream, g.m->K.get(), (long long)g.N, (long long)g.m->ld, 1, denom);
+    }
     HCHK(hipStreamSynchronize(h->stream));
     HCHK(hipGetLastError());
     g.state = 2;
@@ -5730,6 +5787,7 @@ int32_t ngp_grm_get(ngp_handle *h, double *G_out) {
     if ((rc = enter(h))) return rc;
     const Grm &g = h->grm;
     REQUIRE(g.state >= 2, NGP_ERR_STATE, "no complete relationship matrix on this handle (ngp_grm_end; a dense set may have taken it)");
+    REQUIRE(g.nc == 0, NGP_ERR_STATE, "this handle builds the APY form, which never holds N x N (ngp_grm_get_apy returns its pieces)");
     REQUIRE(G_out != nullptr, NGP_ERR_ARG, "null output pointer");
     HCHK(hipStreamSynchronize(h->stream));
     HCHK(hipMemcpy2D(G_out, (size_t)g.N * sizeof(double), g.m->K, (size_t)g.m->ld * sizeof(double), (size_t)g.N * sizeof(double), (size_t)g.N, hipMemcpyDeviceToHost));
@@ -5743,6 +5801,7 @@ int32_t ngp_grm_invert(ngp_handle *h) {
     if ((rc = enter(h))) return rc;
     Grm &g = h->grm;
     REQUIRE(g.state == 2, NGP_ERR_STATE, g.state == 3 ? "the relationship matrix is inverted already" : "ngp_grm_invert needs a complete relationship matrix (ngp_grm_end)");
+    REQUIRE(g.nc == 0, NGP_ERR_STATE, "ngp_grm_invert: this handle builds the APY form (ngp_grm_begin_apy); its analogue is ngp_grm_apy");
     if (!g_rocsolver.load()) return fail(h, NGP_ERR_HIP, g_rocsolver.err + " (ngp_grm_invert factorises on the device; there is no host fallback)");
     struct Blas {  // a rocBLAS handle for this call, destroyed however it ends
         void *p = nullptr;
@@ -5858,6 +5917,218 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
     if (from_grm) { dk->grm_method = h->grm.method; dk->grm_ncols = h->grm.ncols; dk->grm_sum2pq = h->grm.sum2pq; }  // (the SNP back-solve's column weights)
     R.dk = std::move(dk);
     if (from_grm) h->grm = Grm();  // consumed: the set owns the matrix now
+    if (set_id) *set_id = (int32_t)h->mm.rnd.size();
+    h->mm.rnd.push_back(std::move(R));
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* ---- GBLUP at scale: the APY form of inv(G) and the sets over it (ngp_apy.h; DESIGN.md section 2, "APY random-effect sets") ---- */
+
+/* ngp_grm_begin with a core: the levels 0 .. nc - 1 are the core animals.  ngp_grm_columns_* then accumulate the N x nc column panel
+ * G[:, 0:nc] and the diagonal of G only; the column statistics still run over all N rows. */
+int32_t ngp_grm_begin_apy(ngp_handle *h, int64_t N, int64_t nc, int32_t method) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(N >= 1 && N < ((int64_t)1 << 31) - 64, NGP_ERR_ARG, "relationship matrix: 1 <= N < 2^31");
+    REQUIRE(nc >= 1 && nc <= N, NGP_ERR_ARG, "APY relationship matrix: 1 <= nc <= N core animals");
+    REQUIRE(nc <= NGP_APY_MAX_CORE, NGP_ERR_ARG, "APY relationship matrix: at most 8192 core animals (k_apy_tail keeps a core-long vector in registers: ngp_apy.h)");
+    REQUIRE(method == 1 || method == 2, NGP_ERR_ARG, "relationship matrix: method 1 or 2 (src/misc.jl:149-156)");
+    h->grm = Grm();
+    auto m = std::make_shared<DenseK>();
+    const int64_t Npad = (N + 63) / 64 * 64, ncpad = (nc + 63) / 64 * 64;
+    if ((rc = m->K.alloc(h, (size_t)Npad * (size_t)ncpad)) || (rc = h->grm.gdiag.alloc(h, (size_t)N))) { h->grm = Grm(); return rc; }
+    HCHK(hipStreamSynchronize(h->stream));
+    m->q = N; m->ld = Npad;
+    h->grm.m = std::move(m); h->grm.state = 1; h->grm.method = method; h->grm.N = N; h->grm.nc = nc;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* After ngp_grm_end, the analogue of ngp_grm_invert: Kc0 = inv(Gcc) by rocSOLVER (as ngp_grm_invert, with its error behaviour),
+ * P = Gnc Kc0 and Kcc = Kc0 + P' diag(d) P on the matrix cores, m_i = g_ii - P_i. Gnc_i. (m_i <= 0: NGP_ERR_ARG naming the level; the
+ * form is dropped), Kcc mirrored.  The column panel is released. */
+int32_t ngp_grm_apy(ngp_handle *h) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    Grm &g = h->grm;
+    REQUIRE(g.nc > 0, NGP_ERR_STATE, "ngp_grm_apy needs a relationship matrix begun with a core (ngp_grm_begin_apy)");
+    REQUIRE(g.state == 2, NGP_ERR_STATE, g.state == 5 ? "the APY form is complete already" : "ngp_grm_apy needs a complete column panel (ngp_grm_end)");
+    if (!g_rocsolver.load()) return fail(h, NGP_ERR_HIP, g_rocsolver.err + " (ngp_grm_apy factorises on the device; there is no host fallback)");
+    struct Blas {
+        void *p = nullptr;
+        ~Blas() { if (p) (void)g_rocsolver.DestroyHandle(p); }
+    } blas;
+    if (g_rocsolver.CreateHandle(&blas.p) != 0 || !blas.p || g_rocsolver.SetStream(blas.p, h->stream) != 0)
+        return fail(h, NGP_ERR_HIP, "rocblas_create_handle / rocblas_set_stream failed");
+    const int64_t N = g.N, nc = g.nc, nn = N - nc, Npad = g.m->ld, ldk = (nc + 63) / 64 * 64, nnpad = std::max<int64_t>(4, (nn + 3) / 4 * 4);
+    auto A = std::make_shared<ApyK>();
+    A->N = N; A->nc = nc; A->nn = nn; A->nnpad = nnpad; A->ldp = ldk; A->ldk = ldk;
+    DevArray<int> d_info;
+    if ((rc = d_info.alloc(h, 1)) || (rc = A->Kc0.alloc(h, (size_t)ldk * (size_t)ldk)) || (rc = A->Kcc.alloc(h, (size_t)ldk * (size_t)ldk)) ||
+        (rc = A->P.alloc(h, (size_t)nnpad * (size_t)ldk)) || (rc = A->m.alloc(h, (size_t)nnpad)) || (rc = A->d.alloc(h, (size_t)nnpad)) ||
+        (rc = A->kdiag0.alloc(h, (size_t)nc)) || (rc = A->kdiag.alloc(h, (size_t)N)))
+        return rc;
+    // Gcc into a matrix of its own, of the shape ngp_grm_invert inverts (leading dimension nc rounded up to 64, zeros beyond nc)
+    HCHK(hipMemcpy2DAsync(A->Kc0, (size_t)ldk * sizeof(double), g.m->K, (size_t)Npad * sizeof(double), (size_t)nc * sizeof(double), (size_t)nc,
+                          hipMemcpyDeviceToDevice, h->stream));
+    int info = 0;
+    int st = g_rocsolver.Dpotrf(blas.p, ROCBLAS_FILL_LOWER, (int)nc, A->Kc0.get(), (int)ldk, d_info.get());
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+    if (st != 0 || info != 0) {
+        h->grm = Grm();
+        if (st != 0) return fail(h, NGP_ERR_HIP, "rocsolver_dpotrf failed (rocblas status " + std::to_string(st) + "); the relationship matrix is dropped");
+        return fail(h, NGP_ERR_ARG, "the core block of the relationship matrix is not positive definite: the Cholesky factorisation failed at pivot " +
+                                        std::to_string(info) + " (1-based); the matrix is dropped");
+    }
+    st = g_rocsolver.Dpotri(blas.p, ROCBLAS_FILL_LOWER, (int)nc, A->Kc0.get(), (int)ldk, d_info.get());
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+    if (st != 0 || info != 0) {
+        h->grm = Grm();
+        if (st != 0) return fail(h, NGP_ERR_HIP, "rocsolver_dpotri failed (rocblas status " + std::to_string(st) + "); the relationship matrix is dropped");
+        return fail(h, NGP_ERR_ARG, "inverse of the core block of the relationship matrix: zero pivot " + std::to_string(info) + " (1-based); the matrix is dropped");
+    }
+    const dim3 mgrid((unsigned)((nc + 255) / 256), (unsigned)std::min<int64_t>(nc, 65535));
+    hipLaunchKernelGGL(k_grm_mirror, mgrid, dim3(256), 0, h->stream, A->Kc0.get(), (long long)nc, (long long)ldk, 0, 1.0);
+    HCHK(hipMemcpyAsync(A->Kcc, A->Kc0, (size_t)ldk * (size_t)ldk * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (nn > 0) {
+        HCHK(apy_gemm_p(g.m->K, (long long)N, (long long)Npad, (long long)nc, A->Kc0, (long long)ldk, A->P, (long long)ldk, h->stream));
+        HCHK(apy_m(g.m->K, (long long)Npad, (long long)nc, (long long)nn, A->P, (long long)ldk, g.gdiag, A->m, A->d, h->stream));
+        std::vector<double> hm((size_t)nn);
+        HCHK(hipMemcpyAsync(hm.data(), A->m, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < nn; i++)
+            if (!(hm[(size_t)i] > 0.0) || !std::isfinite(hm[(size_t)i])) {
+                h->grm = Grm();
+                return fail(h, NGP_ERR_ARG, "APY: level " + std::to_string(nc + i) + " has m = g_ii - P_i. G_i. = " + std::to_string(hm[(size_t)i]) +
+                                                " <= 0: the animal is no better known than the core explains it (a copy of a core animal?); the matrix is dropped");
+            }
+        HCHK(apy_gemm_kcc(A->P, (long long)ldk, (long long)nnpad, A->d, A->Kcc, (long long)ldk, h->stream));
+        hipLaunchKernelGGL(k_grm_mirror, mgrid, dim3(256), 0, h->stream, A->Kcc.get(), (long long)nc, (long long)ldk, 0, 1.0);
+        HCHK(hipMemcpyAsync(A->kdiag + nc, A->d, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    HCHK(hipMemcpy2DAsync(A->kdiag0, sizeof(double), A->Kc0, (size_t)(ldk + 1) * sizeof(double), sizeof(double), (size_t)nc, hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipMemcpy2DAsync(A->kdiag, sizeof(double), A->Kcc, (size_t)(ldk + 1) * sizeof(double), sizeof(double), (size_t)nc, hipMemcpyDeviceToDevice, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
+    HCHK(hipGetLastError());
+    g.m.reset(); g.gdiag.reset();  // the column panel has served
+    g.ak = std::move(A);
+    g.state = 5;
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* The pieces of an APY form, row-major: of this handle's complete form (set_id < 0) or of an APY set.  which: 0 P (nn x nc), 1 m (nn),
+ * 2 Kcc (nc x nc), 3 Kc0 (nc x nc), 4 d (nn); of a set also 5 the seed s (nc) and 6 u'Ku of its last step (one double). */
+int32_t ngp_grm_get_apy(ngp_handle *h, int32_t set_id, int32_t which, double *out) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(out != nullptr, NGP_ERR_ARG, "null output pointer");
+    const HRand *R = nullptr;
+    const ApyK *A = nullptr;
+    if (set_id < 0) {
+        REQUIRE(h->grm.state == 5, NGP_ERR_STATE, "no complete APY form on this handle (ngp_grm_apy; a set may have taken it)");
+        A = h->grm.ak.get();
+    } else {
+        REQUIRE(set_id < (int32_t)h->mm.rnd.size() && h->mm.rnd[(size_t)set_id].apy, NGP_ERR_ARG, "not an APY random-effect set of this handle");
+        R = &h->mm.rnd[(size_t)set_id];
+        A = R->apy.get();
+    }
+    HCHK(hipStreamSynchronize(h->stream));
+    const size_t w = (size_t)A->nc * sizeof(double);
+    switch (which) {
+        case 0: if (A->nn > 0) HCHK(hipMemcpy2D(out, w, A->P, (size_t)A->ldp * sizeof(double), w, (size_t)A->nn, hipMemcpyDeviceToHost)); break;
+        case 1: if (A->nn > 0) HCHK(hipMemcpy(out, A->m, (size_t)A->nn * sizeof(double), hipMemcpyDeviceToHost)); break;
+        case 2: HCHK(hipMemcpy2D(out, w, A->Kcc, (size_t)A->ldk * sizeof(double), w, (size_t)A->nc, hipMemcpyDeviceToHost)); break;
+        case 3: HCHK(hipMemcpy2D(out, w, A->Kc0, (size_t)A->ldk * sizeof(double), w, (size_t)A->nc, hipMemcpyDeviceToHost)); break;
+        case 4: if (A->nn > 0) HCHK(hipMemcpy(out, A->d, (size_t)A->nn * sizeof(double), hipMemcpyDeviceToHost)); break;
+        case 5: REQUIRE(R, NGP_ERR_ARG, "the seed s belongs to a set"); HCHK(hipMemcpy(out, R->d_as, w, hipMemcpyDeviceToHost)); break;
+        case 6: REQUIRE(R, NGP_ERR_ARG, "u'Ku belongs to a set"); HCHK(hipMemcpy(out, R->d_aquad + 1, sizeof(double), hipMemcpyDeviceToHost)); break;
+        default: return fail(h, NGP_ERR_ARG, "ngp_grm_get_apy: which is 0 .. 6");
+    }
+    return NGP_OK;
+    NGP_CATCH(h)
+}
+
+/* A random-effect set over an APY form: q levels, the first nc the core.  The form is this handle's (ngp_grm_apy; consumed) or, read-only,
+ * that of the APY set k_src_set of another handle.  Every argument is checked before anything changes. */
+int32_t ngp_add_random_set_apy(ngp_handle *h, const int32_t *level, int64_t q, int64_t nc, ngp_handle *k_src, int32_t k_src_set, double df, double scale,
+                               double varU0, int32_t *set_id) {
+    NGP_TRY
+    int rc;
+    if ((rc = enter(h))) return rc;
+    REQUIRE(h->pm, NGP_ERR_STATE, "panel not set");
+    REQUIRE(!h->panel_open, NGP_ERR_STATE, "the panel is still open (ngp_end_panel)");
+    REQUIRE(q >= 1 && q < ((int64_t)1 << 31), NGP_ERR_ARG, "random-effect set: 1 <= q < 2^31");
+    REQUIRE(level != nullptr || q == h->N, NGP_ERR_ARG, "random-effect set: level == NULL means record i is level i and needs q == N");
+    REQUIRE(h->mm.rnd.size() < 16, NGP_ERR_ARG, "at most 16 random-effect sets");
+    REQUIRE(std::isfinite(df) && df > 0.0 && std::isfinite(scale) && scale >= 0.0, NGP_ERR_ARG, "random-effect set: df > 0 and scale >= 0, finite");
+    REQUIRE(std::isfinite(varU0) && varU0 > 0.0, NGP_ERR_ARG, "random-effect set: varU0 must be finite and > 0");
+    const int64_t N = h->N;
+    std::vector<int32_t> ident;
+    if (!level) { ident.resize((size_t)N); for (int64_t i = 0; i < N; i++) ident[(size_t)i] = (int32_t)i; level = ident.data(); }
+    for (int64_t i = 0; i < N; i++) REQUIRE(level[i] >= 0 && (int64_t)level[i] < q, NGP_ERR_ARG, "random-effect set: a record's level is outside 0..q-1");
+    std::shared_ptr<ApyK> A;
+    if (k_src) {
+        REQUIRE(k_src != h, NGP_ERR_ARG, "APY random-effect set: k_src is this handle (a set shares the form of a set on ANOTHER handle)");
+        REQUIRE(k_src->stream != nullptr && k_src->pm && !k_src->panel_open, NGP_ERR_ARG, "APY random-effect set: k_src has no panel or records yet (or its panel is still open)");
+        REQUIRE(k_src->device == h->device, NGP_ERR_ARG, "APY random-effect set: a shared form must be on this handle's device");
+        REQUIRE(k_src_set >= 0 && k_src_set < (int32_t)k_src->mm.rnd.size() && k_src->mm.rnd[(size_t)k_src_set].apy, NGP_ERR_ARG,
+                "APY random-effect set: k_src_set is not an APY set of k_src");
+        A = k_src->mm.rnd[(size_t)k_src_set].apy;
+        HCHK(hipStreamSynchronize(k_src->stream));
+    } else {
+        REQUIRE(h->grm.state == 5, NGP_ERR_STATE, "APY random-effect set: this handle has no complete APY form (ngp_grm_begin_apy .. ngp_grm_apy)");
+        A = h->grm.ak;
+    }
+    REQUIRE(A->N == q && A->nc == nc, NGP_ERR_ARG, "APY random-effect set: the form has another q or another core size");
+    std::vector<double> kd((size_t)q);
+    HCHK(hipMemcpy(kd.data(), A->kdiag, (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t l = 0; l < q; l++) REQUIRE(std::isfinite(kd[(size_t)l]) && kd[(size_t)l] > 0.0, NGP_ERR_ARG, "random-effect set: every diagonal entry of K must be > 0");
+    uint64_t kdig = A->digest;
+    if (!k_src) {  // P, Kcc and d hashed on the device, as dense_digest hashes a dense K: row words, folded here in the order P | Kcc | d
+        const int64_t nn = A->nn, rows = nn + nc + (nn > 0 ? 1 : 0);
+        DevArray<unsigned long long> d_rh;
+        if ((rc = d_rh.alloc(h, (size_t)rows))) return rc;
+        if (nn > 0) {
+            HCHK(apy_digest(A->P, (long long)nn, (long long)nc, (long long)A->ldp, d_rh.get(), h->stream));
+            HCHK(apy_digest(A->d, 1, (long long)nn, (long long)nn, d_rh.get() + nn + nc, h->stream));
+        }
+        HCHK(apy_digest(A->Kcc, (long long)nc, (long long)nc, (long long)A->ldk, d_rh.get() + nn, h->stream));
+        std::vector<unsigned long long> rh((size_t)rows);
+        HCHK(hipMemcpyAsync(rh.data(), d_rh, rh.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HCHK(hipStreamSynchronize(h->stream));
+        kdig = bytes_digest(1469598103934665603ull, rh.data(), rh.size() * sizeof(unsigned long long));
+    }
+    std::vector<long long> lp;
+    std::vector<int> lr, lv;
+    std::vector<double> zpz;
+    group_levels(h, level, q, lp, lr, lv, zpz);
+    HRand R;
+    R.q = q; R.df = df; R.scale = scale; R.varU0 = varU0; R.offdiag = true;
+    R.sdf = scale * df; R.scaleM = {R.sdf}; R.varU0M = {varU0};
+    const int64_t ncw = nc;
+    R.sig = bytes_digest(bytes_digest(bytes_digest(1469598103934665603ull ^ 0x415059ull, lv.data(), lv.size() * 4), &ncw, sizeof(ncw)), &kdig, sizeof(kdig));
+    const double vu[2] = {varU0, 0.0};
+    const size_t nwg = (size_t)std::max<long long>(1, apy_tail_wgs((long long)A->nn));
+    if ((rc = upload(h, R.d_lptr, lp)) || (rc = upload(h, R.d_lrows, lr)) || (rc = upload(h, R.d_level, lv)) || (rc = upload(h, R.d_kdiag, kd)) ||
+        (rc = upload(h, R.d_zpz, zpz)))
+        return rc;
+    if ((rc = R.d_u.alloc(h, (size_t)q)) || (rc = R.d_sum_u.alloc(h, (size_t)q)) || (rc = R.d_vu.alloc(h, 2)) ||
+        (rc = R.d_scr.alloc(h, (size_t)NGP_RS_ROWS_HYBRID * (size_t)q)) || (rc = R.d_as.alloc(h, (size_t)nc)) || (rc = R.d_aspart.alloc(h, nwg * (size_t)nc)) ||
+        (rc = R.d_aqpart.alloc(h, nwg)) || (rc = R.d_aquad.alloc(h, 2)) || (rc = R.d_auprev.alloc(h, (size_t)std::max<int64_t>(1, A->nn))) ||
+        (rc = R.d_astale.alloc(h, 1)))
+        return rc;
+    HCHK(hipMemcpy(R.d_vu, vu, sizeof(vu), hipMemcpyHostToDevice));
+    HCHK(hipStreamSynchronize(h->stream));
+    A->digest = kdig;
+    R.apy = std::move(A);
+    if (!k_src) h->grm = Grm();  // consumed: the set owns the form now
     if (set_id) *set_id = (int32_t)h->mm.rnd.size();
     h->mm.rnd.push_back(std::move(R));
     return NGP_OK;
@@ -6254,6 +6525,7 @@ int32_t ngp_grm_single_step(ngp_handle *h, const double *A22, int64_t ld, double
     if ((rc = enter(h))) return rc;
     Grm &g = h->grm;
     REQUIRE(g.state == 2, NGP_ERR_STATE, "ngp_grm_single_step needs a complete relationship matrix that is not inverted yet (ngp_grm_end)");
+    REQUIRE(g.nc == 0, NGP_ERR_STATE, "ngp_grm_single_step: APY inside single-step H is not built (this handle holds an APY column panel)");
     REQUIRE(A22 != nullptr && ld >= g.N, NGP_ERR_ARG, "single-step: A22 is N x N with ld >= N");
     const int64_t N = g.N, Npad = g.m->ld;
     bool ok = std::isfinite(w) && w >= 0.0 && w < 1.0;

@@ -810,6 +810,25 @@ function grm_get(h::Handle, N::Integer)
     check(h, ccall((:ngp_grm_get, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, G))
     return G
 end
+# GBLUP at scale (include/nextgp_hip.h, "GBLUP at scale"): the APY form of inv(G), the first nc animals the core.  The entry points are
+# bound here; the coarse seam routes nothing to them (the reference has no APY).  grm_get_apy: which 0 P, 1 m, 2 Kcc, 3 Kc0, 4 d (and of a
+# set 5 s, 6 u'Ku) into a vector of n doubles, row-major; set_id < 0: the handle's own form.
+grm_begin_apy!(h::Handle, N::Integer, nc::Integer, method::Integer) =
+    check(h, ccall((:ngp_grm_begin_apy, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Int32), h.ptr, N, nc, method))
+grm_apy!(h::Handle) = check(h, ccall((:ngp_grm_apy, LIB), Int32, (Ptr{Cvoid},), h.ptr))
+function grm_get_apy(h::Handle, set_id::Integer, which::Integer, n::Integer)
+    out = Vector{Float64}(undef, max(n, 1))
+    check(h, ccall((:ngp_grm_get_apy, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), h.ptr, set_id, which, out))
+    return out[1:n]
+end
+function add_random_set_apy!(h::Handle, level::Union{Nothing,Vector{Int32}}, q::Integer, nc::Integer, df::Float64, scale::Float64, varU0::Float64)
+    id = Ref{Int32}(0)
+    lv = level === nothing ? Ptr{Int32}(C_NULL) : pointer(level)
+    GC.@preserve level check(h, ccall((:ngp_add_random_set_apy, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Int32}, Int64, Int64, Ptr{Cvoid}, Int32, Float64, Float64, Float64, Ref{Int32}),
+                   h.ptr, lv, q, nc, C_NULL, 0, df, scale, varU0, id))
+    return id[]
+end
 # ---- SNP effects from GBLUP (include/nextgp_hip.h): the kept draws of a dense set whose K came from grm_invert! are stored on the device
 # (backsolve_enable! before run!) and solved back to the markers afterwards: backsolve_begin!, the genotype columns of the relationship
 # matrix once more in its column order (backsolve_columns!, any split into calls), backsolve_end! -> (sum, sumsq, n) per SNP over the draws.
