@@ -604,7 +604,8 @@ int32_t ngp_add_random_set_dense(ngp_handle *h, const int32_t *level, int64_t q,
  * was formed from (ngp_set_random, a snapshot, ngp_set_y).  Results are identical run to run and do not depend on the device: the
  * rows of P go to workgroups by (nn, a compile-time constant), partial sums are added in workgroup order, no floating-point atomics, no
  * FMA ("APY random-effect sets": the normative orders).  The model signature digests the level coding, nc, P, Kcc
- * and d, hashed on the device.  The SNP back-solve and GBLUP prediction refuse an APY set: they multiply by the dense K. */
+ * and d, hashed on the device.  The SNP back-solve and GBLUP prediction below serve an APY set as they serve a dense one: W = K_APY X
+ * is formed from the pieces (E = Xn - P Xc, Wn = D E, Wc = Kc0 Xc - P' Wn: k_apy_kw_tail, k_apy_kw_core), never from an N x N matrix. */
 int32_t ngp_grm_begin_apy(ngp_handle *h, int64_t N, int64_t nc, int32_t method);
 int32_t ngp_grm_apy(ngp_handle *h);
 int32_t ngp_grm_get_apy(ngp_handle *h, int32_t set_id, int32_t which, double *out);
@@ -612,8 +613,8 @@ int32_t ngp_add_random_set_apy(ngp_handle *h, const int32_t *level, int64_t q, i
                                double scale, double varU0, int32_t *set_id);
 
 /* ---- SNP effects from GBLUP: every kept draw of the breeding values solved back to the markers ----
- * A dense set whose K = inv(G) was built here (ngp_grm_begin .. ngp_grm_invert, K == NULL above, or k_src of such a set) knows how G was
- * formed from the genotype columns Z: with w_t = K u_t,  beta_{j,t} = d_j sum_i (z_ij - mu_j) w_{i,t},  mu_j = 2 p_j,
+ * A dense or an APY set whose K was built here (ngp_grm_begin .. ngp_grm_invert or ngp_grm_begin_apy .. ngp_grm_apy, K == NULL above,
+ * or k_src of such a set; of an APY set K is K_APY) knows how G was formed from the genotype columns Z: with w_t = K u_t,  beta_{j,t} = d_j sum_i (z_ij - mu_j) w_{i,t},  mu_j = 2 p_j,
  * d_j = 1 / sum_k 2 p_k q_k (method 1) or 1 / (P 2 p_j q_j) (method 2): u_t = (G - 0.001 I) w_t = sum_j (z_j - mu_j) beta_{j,t}.  The
  * 0.001 ridge of G is not solved back: it is the part of u that no SNP explains.  mu_j, p_j and the scale come from the same column
  * statistics as the relationship matrix (csrc/ngp_grm_stats.h).  Everything runs on the device in fp64, the two products on the matrix
@@ -628,6 +629,7 @@ int32_t ngp_add_random_set_apy(ngp_handle *h, const int32_t *level, int64_t q, i
  *   kept draw.  On a set whose back-solve is open it starts again.
  * ngp_backsolve_columns_*: the raw, uncentred genotype columns of the relationship matrix, in its column order, split into calls at any
  *   boundaries (the input of ngp_grm_columns_*: column-major, ld >= q, host memory, staged in chunks); the handle counts them.
+ *   The rows are in the set's level order -- of an APY set core first: the same rows, in the same order, as ngp_grm_columns_* received.
  *   The staging buffers are allocated by the first call and kept until ngp_backsolve_end.
  *   NGP_ERR_ARG: ld < q (the columns have another number of rows than the set has levels), more columns than G had, a non-finite value.
  * ngp_backsolve_end: per SNP the sums over the T stored draws, sum[j] = sum_t beta_{j,t} and sumsq[j] = sum_t beta_{j,t}^2 (P doubles each),
@@ -650,7 +652,8 @@ int32_t ngp_backsolve_end(ngp_handle *h, int32_t rset, double *sum, double *sums
  *   m_ct = sum_i C_ci w_it, w_t = K u_t            E[u_c | u_t] per stored draw (the draw store of ngp_backsolve_enable)
  *   s_c = gcc_c - sum_i C_ci (K C')_ic             the part of its genomic variance the records do not determine, in units of varU
  * The host forms mean_c = sum / n and sd_c^2 = var_t(m_ct) + s_c mean_t(varU_t).  Everything runs on the device in fp64, C on the matrix
- * cores (csrc/ngp_gpred.h; DESIGN.md section 2, "GBLUP prediction": the normative orders; the same bits run to run and split to split,
+ * cores, under a dense or an APY set (K is then K_APY, and Ztrain's rows are in the set's level order, core first, as ngp_grm_columns_*
+ * received them) (csrc/ngp_gpred.h; DESIGN.md section 2, "GBLUP prediction": the normative orders; the same bits run to run and split to split,
  * and a candidate with the genotypes of record r gets row r of ngp_grm_get's G off the diagonal, C_cr + 0.001 = G_rr).
  * ngp_gpred_begin: after the run (or before: C and s need no draw).  Allocates C (8 N Nc bytes; V = K C' of the same size follows in
  *   ngp_gpred_end) -- NGP_ERR_NOMEM with what does not fit; predict the candidates in slabs then.  1 <= Nc <= 64 x 65535.

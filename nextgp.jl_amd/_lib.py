@@ -1143,6 +1143,9 @@ class Sampler:
         self.rand_q = getattr(self, "rand_q", []) + [int(q)]
         self.rand_apy = getattr(self, "rand_apy", {})
         self.rand_apy[sid.value] = (int(q), int(nc))
+        # (as add_random_set_dense: the method the form was built with -- this sampler's builder, the owner's for a shared form)
+        self.rand_grm_method = getattr(self, "rand_grm_method", {})
+        self.rand_grm_method[sid.value] = K[0].rand_grm_method.get(int(K[1])) if isinstance(K, tuple) else getattr(self, "grm_method", None)
         return sid.value
 
     def grm_single_step(self, A22, w=0.05):
@@ -1158,7 +1161,8 @@ class Sampler:
     BACKSOLVE_COLUMNS_PER_CALL = 4096
 
     def enable_backsolve(self, rset, max_draws):
-        """Before the run: every kept draw of the dense set rset (K built by grm_begin .. grm_invert) is stored on the device, max_draws at most."""
+        """Before the run: every kept draw of the dense set rset (K built by grm_begin .. grm_invert) or of the APY set rset
+        (grm_begin_apy .. grm_apy) is stored on the device, max_draws at most."""
         self._chk(self.L.ngp_backsolve_enable(self.h, C.c_int32(int(rset)), C.c_int64(int(max_draws))))
 
     def backsolve_draws(self, rset):
@@ -1172,7 +1176,8 @@ class Sampler:
     def backsolve(self, rset, source, method=None, splits=None):
         """After the run: SNP effects of every stored draw of set rset, summed over the draws on the device.  source: the genotypes the
         relationship matrix was built from -- an N x P array (uint8 and float32 go as they are, anything else as float64) or whatever
-        read_genotypes reads (text, .npy, panel file, PLINK fileset).  They go over in column ranges (splits: the ranges' first columns
+        read_genotypes reads (text, .npy, panel file, PLINK fileset) -- of an APY set in its level order, core first, the rows grm_columns
+        received.  They go over in column ranges (splits: the ranges' first columns
         beyond 0; default every BACKSOLVE_COLUMNS_PER_CALL columns); the result does not depend on the split.  method: None, or the
         GRM method (1 / 2) the caller takes the set's matrix to have been built with -- the handle solves back with the method it was
         built with, another one here is a ValueError.  Returns {"sum", "sumsq", "n", "mean", "sd"}, P entries each (backsolve_summary;
@@ -1199,8 +1204,9 @@ class Sampler:
 
     # ---- GBLUP prediction (include/nextgp_hip.h, "GBLUP prediction") ---------------------------
     def gblup_predict(self, set_id, M_train, M_cand, splits=None):
-        """After the run: candidates predicted from their genotypes under the dense set set_id (K built by grm_begin .. grm_invert).
-        M_train: the N x P genotypes the relationship matrix was built from; M_cand: Nc x P, the same columns (uint8 and float32 go as
+        """After the run: candidates predicted from their genotypes under the dense set set_id (K built by grm_begin .. grm_invert) or the
+        APY set set_id (grm_begin_apy .. grm_apy; K is then K_APY, applied in its factored form).
+        M_train: the N x P genotypes the relationship matrix was built from (an APY set: in its level order, core first); M_cand: Nc x P, the same columns (uint8 and float32 go as
         they are when both arrays have that type, anything else as float64).  Both go over in column ranges (splits: the ranges' first
         columns beyond 0, multiples of 64; default every BACKSOLVE_COLUMNS_PER_CALL columns); the result does not depend on the split.
         Returns {"sum", "sumsq", "n", "s", "gcc", "sum_varU", "mean", "sd"} (gblup_predict_summary; pool_gblup_predict pools chains);

@@ -550,8 +550,8 @@ def apy_order(N, core, apySeed=1):
 
 
 def apy_terms(apy, VCV, parsed, snpEffects=False, predict=None):
-    """{term: core} of runLMEM's apy= after its refusals (host only).  apy applies to a SNP term whose prior is Random("G", v); the paths
-    that multiply by the dense K are not built for it."""
+    """{term: core} of runLMEM's apy= after its refusals (host only).  apy applies to a SNP term whose prior is Random("G", v); snpEffects=
+    and predict= on such a term are not routed through runLMEM yet (a Sampler's backsolve and gblup_predict serve an APY set)."""
     out = {}
     for key, core in dict(apy or {}).items():
         if isinstance(key, tuple):
@@ -565,9 +565,9 @@ def apy_terms(apy, VCV, parsed, snpEffects=False, predict=None):
         if key not in {t.name for t in parsed[2]} or not (isinstance(prior, RandomEffectType) and isinstance(prior.str, str) and prior.str == "G"):
             raise ValueError(f"apy[{key!r}]: apy applies to a SNP term whose prior is Random(\"G\", v)")
         if snpEffects is True or (snpEffects and key in [str(a) for a in snpEffects]):
-            raise NotImplementedError(f"apy[{key!r}] with snpEffects=: the SNP back-solve multiplies by the dense K = inv(G), which an APY set never holds")
+            raise NotImplementedError(f"apy[{key!r}] with snpEffects=: not routed through runLMEM yet; on a Sampler, enable_backsolve / backsolve serve an APY set")
         if predict is not None and (not hasattr(predict, "keys") or key in predict):
-            raise NotImplementedError(f"apy[{key!r}] with predict=: GBLUP prediction multiplies by the dense K = inv(G), which an APY set never holds")
+            raise NotImplementedError(f"apy[{key!r}] with predict=: not routed through runLMEM yet; on a Sampler, enable_backsolve / gblup_predict serve an APY set")
         out[key] = core
     return out
 

@@ -139,6 +139,10 @@ struct ApyK {
     int64_t N = 0, nc = 0, nn = 0, nnpad = 0, ldp = 0, ldk = 0;  // P: nnpad x ldp row-major (zeros beyond nn and nc); Kc0, Kcc: ldk x ldk
     DevArray<double> P, m, d, Kc0, Kcc, kdiag0, kdiag;           // kdiag: diag(Kcc) | d, the N diagonal entries of the precision
     uint64_t digest = 0;  // of P, Kcc and d (apy_digest_all, once, when a set first takes the form)
+    // how the builder formed G (ngp_grm_apy; as DenseK's): the column weights of the SNP back-solve and of GBLUP prediction
+    int grm_method = 0;
+    int64_t grm_ncols = 0;
+    double grm_sum2pq = 0.0;
 };
 
 struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled after the fixed-effect sets (src/samplers.jl:43-46)
@@ -177,7 +181,7 @@ struct HRand {  // one (1|g) random-effect set (src/mme.jl:165-272), sampled aft
     std::vector<Launch> plan;
     int64_t ndepth = 0;
     int sched_mode = 0;        // ngp_set_random_schedule: 0 automatic, 1 serial (k_rand_gs), 2 scheduled
-    // SNP back-solve of a dense set built by ngp_grm_* (ngp_backsolve.h): the draw store U (q x max_draws, column-major; lives as long as
+    // SNP back-solve of a dense or an APY set built by ngp_grm_* (ngp_backsolve.h, ngp_apy.h): the draw store U (q x max_draws, column-major; lives as long as
     // the set), kept draws seen so far (n > max_draws: the run ends with NGP_ERR_STATE); between ngp_backsolve_begin and _end W = K U
     // (q x T), cw (T), the sums over the draws per SNP (grm_ncols each) and the columns handed over so far
     struct Backsolve {
@@ -5966,6 +5970,7 @@ int32_t ngp_grm_apy(ngp_handle *h) {
     const int64_t N = g.N, nc = g.nc, nn = N - nc, Npad = g.m->ld, ldk = (nc + 63) / 64 * 64, nnpad = std::max<int64_t>(4, (nn + 3) / 4 * 4);
     auto A = std::make_shared<ApyK>();
     A->N = N; A->nc = nc; A->nn = nn; A->nnpad = nnpad; A->ldp = ldk; A->ldk = ldk;
+    A->grm_method = g.method; A->grm_ncols = g.ncols; A->grm_sum2pq = g.sum2pq;
     DevArray<int> d_info;
     if ((rc = d_info.alloc(h, 1)) || (rc = A->Kc0.alloc(h, (size_t)ldk * (size_t)ldk)) || (rc = A->Kcc.alloc(h, (size_t)ldk * (size_t)ldk)) ||
         (rc = A->P.alloc(h, (size_t)nnpad * (size_t)ldk)) || (rc = A->m.alloc(h, (size_t)nnpad)) || (rc = A->d.alloc(h, (size_t)nnpad)) ||
@@ -6144,12 +6149,34 @@ int backsolve_set(ngp_handle *h, int32_t rset, HRand **out, const std::string &w
     REQUIRE(h->pm && !h->panel_open, NGP_ERR_STATE, "panel (or records) not set");
     REQUIRE(rset >= 0 && rset < (int32_t)h->mm.rnd.size(), NGP_ERR_ARG, what + ": no such random-effect set");
     HRand &R = h->mm.rnd[(size_t)rset];
-    REQUIRE(R.dk && !R.hyb && R.tk == 1, NGP_ERR_ARG,
+    REQUIRE((R.dk || R.apy) && !R.hyb && R.tk == 1, NGP_ERR_ARG,
             what + ": the set is not a dense one (ngp_add_random_set_dense); CSR and hybrid (single-step) sets have no genotype columns behind all their levels");
-    REQUIRE(R.dk->grm_method != 0, NGP_ERR_ARG,
+    REQUIRE(R.apy || R.dk->grm_method != 0, NGP_ERR_ARG,
             what + ": the caller gave this set's K; the column weights are known only for a matrix built by ngp_grm_begin .. ngp_grm_invert");
     *out = &R;
     return NGP_OK;
+}
+
+// What the back-solve and the prediction read of the set's precision, whichever kind backsolve_set let through: how ngp_grm_* built it
+// (the column weights), and W = K X with cw_t = sum_i W[i, t] -- k_bs_kw over a dense K, the factored product of ngp_apy.h over an APY form
+struct BsForm {
+    int method;
+    int64_t ncols;
+    double sum2pq;
+};
+BsForm bs_form(const HRand &R) {
+    if (R.apy) return BsForm{R.apy->grm_method, R.apy->grm_ncols, R.apy->grm_sum2pq};
+    return BsForm{R.dk->grm_method, R.dk->grm_ncols, R.dk->grm_sum2pq};
+}
+hipError_t bs_kw(const HRand &R, const double *X, int64_t T, double *W, double *cw, hipStream_t stream) {
+    if (R.apy) {
+        const ApyK &A = *R.apy;
+        ApyKw k;
+        k.N = (long long)A.N; k.nc = (long long)A.nc; k.ldp = (long long)A.ldp; k.ldk = (long long)A.ldk;
+        k.P = A.P.get(); k.d = A.d.get(); k.Kc0 = A.Kc0.get();
+        return apy_kw(k, X, (long long)T, W, cw, stream);
+    }
+    return backsolve_kw(R.dk->K.get(), (long long)R.dk->ld, (long long)R.q, X, (long long)T, W, cw, stream);
 }
 
 template <typename TIn>
@@ -6159,7 +6186,8 @@ int backsolve_columns_t(ngp_handle *h, int type, const TIn *M, int64_t ncol, int
     REQUIRE(h->bs_open >= 0 && h->bs_open < (int)h->mm.rnd.size(), NGP_ERR_STATE, "ngp_backsolve_columns_* needs an open back-solve (ngp_backsolve_begin)");
     HRand &R = h->mm.rnd[(size_t)h->bs_open];
     HRand::Backsolve &B = R.bs;
-    const int64_t N = R.q, P = R.dk->grm_ncols;
+    const BsForm F = bs_form(R);
+    const int64_t N = R.q, P = F.ncols;
     REQUIRE(M != nullptr && ncol > 0, NGP_ERR_ARG, "genotype columns: a matrix of at least one column");
     REQUIRE(ld >= N, NGP_ERR_ARG, "SNP back-solve: the genotype columns have fewer rows than the set has levels (leading dimension smaller than q)");
     REQUIRE(B.cols + ncol <= P, NGP_ERR_ARG, "SNP back-solve: more columns than the relationship matrix was built from (" + std::to_string(P) + ")");
@@ -6190,7 +6218,7 @@ int backsolve_columns_t(ngp_handle *h, int type, const TIn *M, int64_t ncol, int
         if (e == hipSuccess) e = hipMemcpyAsync(d_g, M + (size_t)c0 * (size_t)ld, ((size_t)(nc - 1) * (size_t)ld + (size_t)N) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) {
             BsCols c;
-            c.type = type; c.method = R.dk->grm_method; c.src = d_g; c.N = N; c.ld = ld; c.nc = nc; c.P = P; c.sum2pq = R.dk->grm_sum2pq;
+            c.type = type; c.method = F.method; c.src = d_g; c.N = N; c.ld = ld; c.nc = nc; c.P = P; c.sum2pq = F.sum2pq;
             c.W = B.W.get(); c.cw = B.cw.get(); c.T = B.T; c.mu = d_mu; c.dj = d_dj; c.bad = d_bad;
             c.sum = B.sum.get() + B.cols; c.sumsq = B.sumsq.get() + B.cols;
             e = backsolve_columns(c, h->stream);
@@ -6258,11 +6286,11 @@ int32_t ngp_backsolve_begin(ngp_handle *h, int32_t rset) {
     // (begin on the open set starts it again: what an abandoned column pass left goes)
     h->bs_open = -1;
     B.release_pass();
-    const int64_t T = std::min(B.n, B.max_draws), P = R->dk->grm_ncols;
+    const int64_t T = std::min(B.n, B.max_draws), P = bs_form(*R).ncols;
     if (B.W.alloc_raw((size_t)R->q * (size_t)T) != hipSuccess || B.cw.alloc_raw((size_t)T) != hipSuccess)
         return fail(h, NGP_ERR_NOMEM, "W = K U of the SNP back-solve: " + std::to_string(R->q) + " x " + std::to_string(T) + " doubles");
     if ((rc = B.sum.alloc(h, (size_t)P)) || (rc = B.sumsq.alloc(h, (size_t)P))) return rc;
-    hipError_t e = backsolve_kw(R->dk->K.get(), (long long)R->dk->ld, (long long)R->q, B.U.get(), (long long)T, B.W.get(), B.cw.get(), h->stream);
+    hipError_t e = bs_kw(*R, B.U.get(), T, B.W.get(), B.cw.get(), h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("ngp_backsolve_begin: ") + hipGetErrorString(e));
     B.T = T; B.cols = 0;
@@ -6297,7 +6325,7 @@ int32_t ngp_backsolve_end(ngp_handle *h, int32_t rset, double *sum, double *sums
     if ((rc = backsolve_set(h, rset, &R))) return rc;
     HRand::Backsolve &B = R->bs;
     REQUIRE(h->bs_open == rset, NGP_ERR_STATE, "ngp_backsolve_end: no back-solve of this set is open (ngp_backsolve_begin)");
-    const int64_t P = R->dk->grm_ncols;
+    const int64_t P = bs_form(*R).ncols;
     REQUIRE(B.cols == P, NGP_ERR_STATE, "ngp_backsolve_end: " + std::to_string(B.cols) + " genotype columns were handed over, the relationship matrix was built from " +
                                             std::to_string(P) + " (hand over the rest, or start again with ngp_backsolve_begin)");
     HCHK(hipStreamSynchronize(h->stream));
@@ -6332,7 +6360,8 @@ int gpred_columns_t(ngp_handle *h, int type, const TIn *Mt, int64_t ldt, const T
     Gpred &g = h->gp;
     REQUIRE(g.open && g.rset >= 0 && g.rset < (int)h->mm.rnd.size(), NGP_ERR_STATE, "ngp_gpred_columns_* needs an open prediction (ngp_gpred_begin)");
     const HRand &R = h->mm.rnd[(size_t)g.rset];
-    const int64_t N = g.N, Nc = g.Nc, P = R.dk->grm_ncols;
+    const BsForm F = bs_form(R);
+    const int64_t N = g.N, Nc = g.Nc, P = F.ncols;
     REQUIRE(Mt != nullptr && Mc != nullptr && ncol > 0, NGP_ERR_ARG, "genotype columns: the records' and the candidates' matrices of at least one column");
     REQUIRE(ldt >= N, NGP_ERR_ARG, "GBLUP prediction: the records' genotype columns have fewer rows than the set has levels (leading dimension smaller than q)");
     REQUIRE(ldc >= Nc, NGP_ERR_ARG, "GBLUP prediction: the candidates' genotype columns have fewer rows than Nc (leading dimension smaller than Nc)");
@@ -6368,7 +6397,7 @@ int gpred_columns_t(ngp_handle *h, int type, const TIn *Mt, int64_t ldt, const T
         if (e == hipSuccess) e = hipMemcpyAsync(d_t, Mt + (size_t)c0 * (size_t)ldt, ((size_t)(nc - 1) * (size_t)ldt + (size_t)N) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_c, Mc + (size_t)c0 * (size_t)ldc, ((size_t)(nc - 1) * (size_t)ldc + (size_t)Nc) * sizeof(TIn), hipMemcpyHostToDevice, h->stream);
         GpCols c;
-        c.type = type; c.method = R.dk->grm_method; c.train = d_t; c.cand = d_c; c.N = N; c.ldt = ldt; c.Nc = Nc; c.ldc = ldc; c.nc = nc;
+        c.type = type; c.method = F.method; c.train = d_t; c.cand = d_c; c.N = N; c.ldt = ldt; c.Nc = Nc; c.ldc = ldc; c.nc = nc;
         c.mu = g.mu.get(); c.sd = g.sd.get(); c.bad = g.bad.get(); c.Ct = g.Ct.get(); c.gcc = g.gcc.get();
         if (e == hipSuccess) e = gpred_colstats(c, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(bad, g.bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream);
@@ -6441,7 +6470,8 @@ int32_t ngp_gpred_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, d
     if ((rc = backsolve_set(h, rset, &R, "GBLUP prediction"))) return rc;
     Gpred &g = h->gp;
     REQUIRE(g.open && g.rset == rset, NGP_ERR_STATE, "ngp_gpred_end: no GBLUP prediction of this set is open (ngp_gpred_begin)");
-    const int64_t P = R->dk->grm_ncols, N = g.N, Nc = g.Nc;
+    const BsForm F = bs_form(*R);
+    const int64_t P = F.ncols, N = g.N, Nc = g.Nc;
     REQUIRE(g.cols == P, NGP_ERR_STATE, "ngp_gpred_end: " + std::to_string(g.cols) + " genotype columns were handed over, the relationship matrix was built from " +
                                             std::to_string(P) + " (hand over the rest, or start again with ngp_gpred_begin)");
     REQUIRE(h->bs_open < 0, NGP_ERR_STATE, "a back-solve is open on this handle (ngp_backsolve_end): both form W = K U of the stored draws, one at a time");
@@ -6455,13 +6485,13 @@ int32_t ngp_gpred_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, d
     if (V.alloc_raw((size_t)N * (size_t)Nc) != hipSuccess || cv.alloc_raw((size_t)Nc) != hipSuccess || d_s.alloc_raw((size_t)Nc) != hipSuccess)
         return fail(h, NGP_ERR_NOMEM, "V = K C' of GBLUP prediction: " + std::to_string(N) + " x " + std::to_string(Nc) + " doubles");
     // the one division of ngp_grm_end (k_grm_mirror), without the ridge: it belongs to the diagonal of G
-    const double denom = R->dk->grm_method == 1 ? R->dk->grm_sum2pq : (double)P;
+    const double denom = F.method == 1 ? F.sum2pq : (double)P;
     hipError_t e = hipSuccess;
     if (!g.scaled) {  // (once: an end that fails further down leaves the prediction open and may be called again)
         e = gpred_scale(g.Ct.get(), (long long)N, (long long)Nc, g.gcc.get(), denom, h->stream);
         g.scaled = e == hipSuccess;
     }
-    if (e == hipSuccess) e = backsolve_kw(R->dk->K.get(), (long long)R->dk->ld, (long long)N, g.Ct.get(), (long long)Nc, V.get(), cv.get(), h->stream);
+    if (e == hipSuccess) e = bs_kw(*R, g.Ct.get(), Nc, V.get(), cv.get(), h->stream);
     if (e == hipSuccess) e = gpred_resid(g.Ct.get(), V.get(), (long long)N, (long long)Nc, g.gcc.get(), d_s.get(), h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, NGP_ERR_HIP, std::string("ngp_gpred_end: ") + hipGetErrorString(e));
@@ -6472,7 +6502,7 @@ int32_t ngp_gpred_end(ngp_handle *h, int32_t rset, double *sum, double *sumsq, d
         if (W.alloc_raw((size_t)N * (size_t)T) != hipSuccess || cw.alloc_raw((size_t)T) != hipSuccess || d_sum.alloc_raw((size_t)Nc) != hipSuccess ||
             d_sumsq.alloc_raw((size_t)Nc) != hipSuccess || mu0.alloc_raw((size_t)Nc) != hipSuccess || d1.alloc_raw((size_t)Nc) != hipSuccess)
             return fail(h, NGP_ERR_NOMEM, "W = K U of GBLUP prediction: " + std::to_string(N) + " x " + std::to_string(T) + " doubles");
-        e = backsolve_kw(R->dk->K.get(), (long long)R->dk->ld, (long long)N, R->bs.U.get(), (long long)T, W.get(), cw.get(), h->stream);
+        e = bs_kw(*R, R->bs.U.get(), T, W.get(), cw.get(), h->stream);
         if (e == hipSuccess) e = gpred_fill(mu0.get(), (long long)Nc, 0.0, h->stream);
         if (e == hipSuccess) e = gpred_fill(d1.get(), (long long)Nc, 1.0, h->stream);
         if (e == hipSuccess) e = backsolve_project(g.Ct.get(), (long long)N, (long long)Nc, W.get(), (long long)T, cw.get(), mu0.get(), d1.get(), d_sum.get(), d_sumsq.get(), h->stream);

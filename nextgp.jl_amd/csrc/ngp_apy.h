@@ -68,6 +68,14 @@ hipError_t apy_m(const double *panel, long long Npad, long long nc, long long nn
                  hipStream_t stream);
 hipError_t apy_gemm_kcc(const double *P, long long ldp, long long nnpad, const double *d, double *Kcc, long long ldk, hipStream_t stream);
 hipError_t apy_digest(const double *A, long long rows, long long cols, long long ld, unsigned long long *rowhash, hipStream_t stream);
+// W = K_APY X for the SNP back-solve and GBLUP prediction (k_apy_kw_tail, k_apy_kw_core below; cw by k_bs_cw of ngp_backsolve.h).  X and W
+// are N x T, column-major with leading dimension N, levels core first; cw_t = sum_i W[i, t].  The pieces as ApyK holds them: P nnpad x ldp
+// row-major with zeros beyond nn and nc, ldp a multiple of 64; d nn; Kc0 column-major (symmetric) with leading dimension ldk.
+struct ApyKw {
+    long long N, nc, ldp, ldk;
+    const double *P, *d, *Kc0;
+};
+hipError_t apy_kw(const ApyKw &k, const double *X, long long T, double *W, double *cw, hipStream_t stream);
 
 #ifdef NGP_APY_KERNELS
 
@@ -450,6 +458,142 @@ __global__ __launch_bounds__(256) void k_apy_digest(const double *__restrict__ A
     unsigned long long r = 1469598103934665603ull;
     for (int j = 0; j < 64; j++) { r ^= __shfl(x, j); r *= 1099511628211ull; }
     if (lane == 0) rowhash[l] = r;
+}
+
+// ==========================================================================================
+// W = K_APY X for a batch of T vectors (the draw store U of the SNP back-solve, or the relationship block C' of GBLUP prediction), by
+// the factored form -- the N x N matrix is never formed, and Kc0 is used, not Kcc, so that P'DP is not cancelled against itself:
+//   E = Xn - P Xc;   Wn = D E;   Wc = Kc0 Xc - P' Wn
+// Two kernels on the matrix cores (v_mfma_f64_16x16x4_f64) in the conventions of k_bs_kw and k_grm_syrk: lane l = (cc = l & 15,
+// rr = l >> 4) supplies A[row cc][k = rr] and B[k = rr][col cc], the core adds the four products one after the other, k ascending; D:
+// lane l, register v holds row rr + 4 v, column cc.  A workgroup of 256 threads owns 64 rows x 64 draws, wave w the 16-draw group w as
+// four 16 x 16 accumulators.  Every entry of W is a function of its row and its draw alone: each sum is ONE chain from 0.0 over all of
+// its terms in their order, so neither the grid nor T nor the grouping of the draws shows in the bits.
+// LDS tiles hold 64 lines (rows of P, or draws) of 64 k-values at a stride of NGP_APY_KS = 66 doubles: the loaders write 64 adjacent
+// doubles per wave; the half wave rr = 0, 1 (and 2, 3) reads the doubles 66 cc + rr, dwords 4 cc + 2 rr (mod 64): every bank once.
+// ==========================================================================================
+#define NGP_APY_KS 66
+#define NGP_APY_KW_TAIL_LDS (2 * 64 * NGP_APY_KS * sizeof(double))  // the tile of P and the tile of Xc: 67,584 bytes (dynamic: above 64 KiB)
+
+// The thread's share of the step's two tiles into registers: line w + 4 j (j < 16), k-value l -- a wave reads 64 adjacent doubles of a row
+// of P (row-major) or of a draw of Xc.  Rows >= nn, k >= nc of Xc and draws >= T are zeros by predication; a row of P holds zeros from nc
+// to ldp (a multiple of 64), so the step's 64 columns lie inside it.
+__device__ __forceinline__ void apy_kw_fetch(const double *__restrict__ P, long long ldp, long long nn, long long i0, const double *__restrict__ X, long long N,
+                                             long long nc, long long T, long long t0, long long k0, int w, int l, double (&p)[16], double (&x)[16]) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const long long i = i0 + w + 4 * j, t = t0 + w + 4 * j, k = k0 + l;
+        p[j] = i < nn ? P[(size_t)i * (size_t)ldp + (size_t)k] : 0.0;
+        x[j] = (k < nc && t < T) ? X[(size_t)k + (size_t)t * (size_t)N] : 0.0;
+    }
+}
+
+// Wn: grid (ceil(nn / 64), ceil(T / 64)).  The core is walked in steps of 64: A[row i][k] = P[i][k] is wanted by columns and P lies by rows,
+// so its 64 x 64 tile goes through LDS (as the tile of Xc does, shared by the four waves); the global loads of step k + 1 are issued into
+// registers before the matrix steps of step k and written to LDS behind them (one buffer: the registers hide the load).  Then, each
+// rounded on its own:  acc = (P Xc)[i, t], one chain from 0.0, k ascending in fours;  e = x_{nc + i, t} - acc;  w = d_i * e.
+__global__ __launch_bounds__(256) void k_apy_kw_tail(const double *__restrict__ P, long long ldp, const double *__restrict__ d, long long N, long long nc,
+                                                     const double *__restrict__ X, long long T, double *__restrict__ W) {
+    extern __shared__ double apy_kw_lds[];
+    double *sP = apy_kw_lds, *sX = apy_kw_lds + 64 * NGP_APY_KS;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, rr = l >> 4, cc = l & 15;
+    const long long nn = N - nc, i0 = 64LL * blockIdx.x, t0 = 64LL * blockIdx.y;
+    apy_d4 acc[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) acc[s] = apy_d4{0.0, 0.0, 0.0, 0.0};
+    double p[16], x[16];
+    apy_kw_fetch(P, ldp, nn, i0, X, N, nc, T, t0, 0, w, l, p, x);
+    for (long long k0 = 0; k0 < nc; k0 += 64) {
+        __syncthreads();  // (the tiles of the step before have been read)
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            sP[(w + 4 * j) * NGP_APY_KS + l] = p[j];
+            sX[(w + 4 * j) * NGP_APY_KS + l] = x[j];
+        }
+        __syncthreads();
+        if (k0 + 64 < nc) apy_kw_fetch(P, ldp, nn, i0, X, N, nc, T, t0, k0 + 64, w, l, p, x);  // (uniform; in flight during the matrix steps)
+#pragma unroll
+        for (int kb = 0; kb < 16; kb++) {
+            const double b = sX[(16 * w + cc) * NGP_APY_KS + 4 * kb + rr];
+#pragma unroll
+            for (int s = 0; s < 4; s++) acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(sP[(16 * s + cc) * NGP_APY_KS + 4 * kb + rr], b, acc[s], 0, 0, 0);
+        }
+    }
+    const long long t = t0 + 16 * w + cc;
+    if (t < T) {
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const long long i = i0 + 16 * s + rr + 4 * v;
+                if (i < nn) {
+                    const size_t at = (size_t)(nc + i) + (size_t)t * (size_t)N;
+                    const double e = X[at] - acc[s][v];
+                    W[at] = d[i] * e;
+                }
+            }
+    }
+}
+
+// acc[s] += sum_k A[k][r0 + 16 s + cc] B[k, t0 + 16 w + cc], k ascending in fours over 0 .. klim - 1: k_bs_kw's loop.  Row k of A lies at
+// A + k lda with the 64 wanted entries adjacent -- sixteen consecutive doubles per quarter wave, straight from memory into the A operand
+// (each element is used once per draw group); the 64 x 64 tile of B (column-major, leading dimension ldb) goes through LDS.  Entries with
+// k >= klim, r >= rlim or t >= T are zeros by predicated loads.
+__device__ __forceinline__ void apy_kw_chain(const double *__restrict__ A, long long lda, long long rlim, long long klim, long long r0, const double *B,
+                                             long long ldb, long long T, long long t0, double *sX, apy_d4 (&acc)[4]) {
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, rr = l >> 4, cc = l & 15;
+    for (long long k0 = 0; k0 < klim; k0 += 64) {
+        double a[4][16];  // the A tile of this lane: in flight while the B tile is staged
+#pragma unroll
+        for (int kb = 0; kb < 16; kb++) {
+            const long long k = k0 + 4 * kb + rr;
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                const long long r = r0 + 16 * s + cc;
+                a[s][kb] = (k < klim && r < rlim) ? A[(size_t)k * (size_t)lda + (size_t)r] : 0.0;
+            }
+        }
+        __syncthreads();  // (the tile of the step before has been read)
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const long long k = k0 + l, t = t0 + w + 4 * j;
+            sX[(w + 4 * j) * NGP_APY_KS + l] = (k < klim && t < T) ? B[(size_t)k + (size_t)t * (size_t)ldb] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kb = 0; kb < 16; kb++) {
+            const double b = sX[(16 * w + cc) * NGP_APY_KS + 4 * kb + rr];
+#pragma unroll
+            for (int s = 0; s < 4; s++) acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][kb], b, acc[s], 0, 0, 0);
+        }
+    }
+}
+
+// Wc: grid (ceil(nc / 64), ceil(T / 64)), after k_apy_kw_tail on the same stream.  Two chains per entry, each from 0.0:
+//   a1 = (Kc0 Xc)[c, t], k ascending in fours -- Kc0 is symmetric, row k serves as column k: k_bs_kw's chain over K, so with nc = N this
+//        is k_bs_kw's W bit for bit;
+//   a2 = sum_i P[i][c] Wn[i, t], i ascending in fours over the non-core rows -- row-major P plays the part the symmetric K plays above.
+// w = a1 - a2, one subtraction; without non-core rows the kernel stores a1 itself.
+__global__ __launch_bounds__(256) void k_apy_kw_core(const double *__restrict__ K0, long long ldk, const double *__restrict__ P, long long ldp, long long N,
+                                                     long long nc, const double *__restrict__ X, long long T, double *W) {
+    __shared__ double sX[64 * NGP_APY_KS];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, rr = l >> 4, cc = l & 15;
+    const long long nn = N - nc, c0 = 64LL * blockIdx.x, t0 = 64LL * blockIdx.y;
+    apy_d4 a1[4], a2[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) { a1[s] = apy_d4{0.0, 0.0, 0.0, 0.0}; a2[s] = a1[s]; }
+    apy_kw_chain(K0, ldk, nc, nc, c0, X, N, T, t0, sX, a1);
+    if (nn > 0) apy_kw_chain(P, ldp, nc, nn, c0, W + nc, N, T, t0, sX, a2);  // (uniform over the grid)
+    const long long t = t0 + 16 * w + cc;
+    if (t < T) {
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const long long c = c0 + 16 * s + rr + 4 * v;
+                if (c < nc) W[(size_t)c + (size_t)t * (size_t)N] = nn > 0 ? a1[s][v] - a2[s][v] : a1[s][v];
+            }
+    }
 }
 
 #endif  // NGP_APY_KERNELS

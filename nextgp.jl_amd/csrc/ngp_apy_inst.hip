@@ -2,6 +2,7 @@
 // prediction's, so that neither the API unit nor the sweep units carry code they did not carry before.
 #define NGP_APY_KERNELS
 #include "ngp_apy.h"
+#include "ngp_backsolve.h"  // (declarations only: backsolve_cw launches k_bs_cw from the back-solve's unit)
 
 namespace ngp {
 
@@ -83,6 +84,21 @@ hipError_t apy_digest(const double *A, long long rows, long long cols, long long
     if (rows < 1 || cols < 1 || ld < cols) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_apy_digest, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, A, rows, cols, ld, rowhash);
     return hipGetLastError();
+}
+
+// the tail first (Wn), then the core (it reads Wn), then the column sums over the finished W; all core: k_apy_kw_core alone
+hipError_t apy_kw(const ApyKw &k, const double *X, long long T, double *W, double *cw, hipStream_t stream) {
+    const long long nn = k.N - k.nc;
+    if (k.nc < 1 || k.nc > NGP_APY_MAX_CORE || nn < 0 || T < 1 || T > 64LL * 65535 || k.ldp < k.nc || k.ldp % 64 != 0 || k.ldk < k.nc) return hipErrorInvalidValue;
+    const unsigned gt = (unsigned)((T + 63) / 64);
+    if (nn > 0) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_apy_kw_tail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NGP_APY_KW_TAIL_LDS);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_apy_kw_tail, dim3((unsigned)((nn + 63) / 64), gt), dim3(256), NGP_APY_KW_TAIL_LDS, stream, k.P, k.ldp, k.d, k.N, k.nc, X, T, W);
+    }
+    hipLaunchKernelGGL(k_apy_kw_core, dim3((unsigned)((k.nc + 63) / 64), gt), dim3(256), 0, stream, k.Kc0, k.ldk, k.P, k.ldp, k.N, k.nc, X, T, W);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : backsolve_cw(W, k.N, T, cw, stream);
 }
 
 }  // namespace ngp

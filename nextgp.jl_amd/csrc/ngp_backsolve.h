@@ -23,6 +23,7 @@ namespace ngp {
 // the launches (ngp_backsolve_inst.hip); type: 0 f64, 1 f32, 2 u8 genotypes
 hipError_t backsolve_store(long long q, const double *u, double *dst, const unsigned *abort_w, hipStream_t stream);
 hipError_t backsolve_kw(const double *K, long long ld, long long q, const double *U, long long T, double *W, double *cw, hipStream_t stream);
+hipError_t backsolve_cw(const double *W, long long q, long long T, double *cw, hipStream_t stream);  // k_bs_cw alone, over a W formed elsewhere (ngp_apy.h)
 struct BsCols {
     int type, method;         // genotype type; GRM method 1 / 2
     const void *src;          // the staged chunk: nc raw columns of N rows, leading dimension ld (elements)

@@ -17,6 +17,12 @@ hipError_t backsolve_kw(const double *K, long long ld, long long q, const double
     return hipGetLastError();
 }
 
+hipError_t backsolve_cw(const double *W, long long q, long long T, double *cw, hipStream_t stream) {
+    if (q < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bs_cw, dim3((unsigned)T), dim3(64), 0, stream, W, q, cw);
+    return hipGetLastError();
+}
+
 template <typename TIn>
 static void launch_cols(const BsCols &c, hipStream_t stream) {
     const TIn *src = (const TIn *)c.src;
